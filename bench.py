@@ -12,7 +12,8 @@ K timed frames is rendered completely inside the timed region.  Workload at ever
 gaussians at 1920x1080 (scene bytes resident in HBM before the timed region).
 N>1 splits ONE frame across ranks by screen-tile columns and all-gathers the
 framebuffer over RCCL: fixed total work, so `scaling` is "strong".
-Rank 0 prints one JSON line.
+Rank 0 prints one JSON line.  --dump-outputs DIR (N=1) also writes the last timed step's image and depthIndex
+as DIR/*.npy, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -404,6 +405,39 @@ def split_config(gh, torch, dist, name, rank, world, local_rank, F, steps, warmu
     return out
 
 
+# --dump-outputs: at most 64 MB per run; C3's 33 MB image and 8 MB depthIndex are written whole
+DUMP_MAX_BYTES = {"image": 40_000_000, "depth_index": 20_000_000}
+
+
+def sample_rows(n, k):
+    """Ascending numbers of at most k of n rows, fixed by n and k alone: one row out of every `every` consecutive ones, at an
+    offset that an integer hash of the group's number picks (so no column, tile or channel phase is left out, as a plain
+    stride would; integer arithmetic only, so the choice does not depend on the numpy version).  -> (rows, every)"""
+    every = -(-n // k)
+    group = np.arange(-(-n // every), dtype=np.uint64)
+    offset = ((group * np.uint64(0x9E3779B97F4A7C15)) >> np.uint64(40)) % np.uint64(every)
+    return np.minimum(group * np.uint64(every) + offset, np.uint64(n - 1)).astype(np.int64), every
+
+
+def bounded(a, max_bytes):
+    """`a` itself when it fits into max_bytes, else sample_rows of it, a row being one index of every axis but the last
+    (a whole RGBA pixel of an image).  -> (array, record for the result line)"""
+    rows = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a
+    n, k = len(rows), max_bytes // (a.nbytes // len(rows))
+    if n <= k:
+        return a, {"shape": list(a.shape), "dtype": str(a.dtype), "sample_of": None}
+    pick, every = sample_rows(n, k)
+    return rows[pick], {"shape": [len(pick)] + list(rows.shape[1:]), "dtype": str(a.dtype),
+                        "sample_of": {"shape": list(a.shape), "one_row_of_every": every, "rows": "bench.sample_rows(%d, %d)[0]" % (n, k)}}
+
+
+def last_outputs(rr):
+    """What a caller of render(scene, camera) receives from context `rr` for the frame it rendered last, bounded for the dump:
+    image = readPixelsFloat() (premultiplied RGBA float32 [H, W, 4]), depth_index = lastDepthIndex() (as float64: exact).
+    -> {name: (array, record)}"""
+    arrays = {"image": rr.readPixelsFloat(), "depth_index": rr.lastDepthIndex().astype(np.float64)}
+    return {name: bounded(a, DUMP_MAX_BYTES[name]) for name, a in arrays.items()}
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -437,7 +471,16 @@ def main():
                          "driven through a host-staged gloo all-gather (gsr_comm_init_custom) -- a rehearsal of its control flow on one GPU")
     ap.add_argument("--emulate-rank", default=None, metavar="Q/G",
                     help="single GPU only: render just the band rank Q of G would own (no exchange) -> per-rank device time of a G-GPU run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="single GPU only: after the timed steps, write what the last of them rendered to DIR/image.npy (float32) and "
+                         "DIR/depth_index.npy (float64); a fixed sample of the rows of an array too large for the 64 MB a dump may take "
+                         "(`dumped_outputs` of the result line says which). "
+                         "The scene and the poses are seeded: the same arguments give the same inputs in every run and every build")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs reads one context's frame: single GPU only")
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -615,6 +658,9 @@ def main():
     for k in range(WARM_FRAMES):
         step(k)
     elapsed = timed(0)
+    # read here, before the stage-time pass below renders over it (the last timed step ran on context (W + K - 1) mod F, and
+    # timed() has fenced every context); written once the run is known to have dropped no frame
+    dumped = last_outputs(rs[(args.warmup + args.steps - 1) % F]) if args.dump_outputs else None
     for rr in rs:
         rr.set_timing_interval(max(1, args.timing_interval))
         rr.reset_stats()
@@ -637,6 +683,10 @@ def main():
     if dropped_frames:
         # a frame whose lists did not fit is not composited; a timed region containing one has not rendered K frames
         raise SystemExit("bench.py: %d frame(s) of the timed region were dropped by a bin-list overflow: result invalid" % dropped_frames)
+    if dumped:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, (a, _) in dumped.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     st = {k: sum(x[k] for x in sts) for k in sts[0] if k.startswith("sum_") or k == "frames"}
     frames = max(int(st["frames"]), 1)
     ms = {k: st["sum_ms_" + k] / frames for k in ("project_key", "sort", "bin", "blend", "combine", "total")}
@@ -857,6 +907,7 @@ def main():
                 "note": "`value` = exactly K steps after W warm-up steps on a device that has been rendering; this = the same on a device "
                         "that has rendered a dozen frames since the process started"},
             "build_id": gh.build_id(),
+            "dumped_outputs": None if not dumped else {name + ".npy": rec for name, (_, rec) in dumped.items()},
             "stage_roofline": {
                 # 52 N covers the whole sort path of wasm.cpp (key + min/max: 28 N, radix passes: 24 N): over key pass + radix
                 # stage (the sort-only leg); the radix stage alone moves 24 N + the 8 N of keys it writes and re-reads
