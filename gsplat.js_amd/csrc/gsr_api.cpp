@@ -153,6 +153,21 @@ struct gsr_ctx {
     SlabEdges comm_edges{};
     bool frame8_valid = false;
 
+    // frame delivery (gsr_delivery_open): a ring of pinned host blocks, each with its device staging and "copy done" event
+    struct DeliverySlot {
+        uint8_t* host = nullptr;        // hipHostMalloc: W * H * 4 pixel bytes + the trailer
+        uint32_t* staging = nullptr;    // device, same size: k_deliver_rgba8 writes it, the copy reads it
+        hipEvent_t done = nullptr;      // recorded behind the slot's copy
+        uint64_t serial = 0;
+        enum State { FREE, IN_FLIGHT, HELD } state = FREE;
+    };
+    std::vector<DeliverySlot> ring;
+    hipStream_t copy_stream = nullptr;
+    hipEvent_t ev_staged = nullptr;     // render stream -> copy stream: the conversion kernel has written the staging buffer
+    int ring_W = 0, ring_H = 0;
+    int ring_next = 0;                  // where the search for a free slot starts: the slots are used in turn
+    uint64_t deliver_serial = 0;        // the last serial handed out; never restarts
+
     CamParams cam{};
     CamParams cam_frame{};            // the camera of the last rendered frame
     CamParams* cam_dev = nullptr;     // a camera slot in device memory (written by the one-time initialisation only)
@@ -419,6 +434,9 @@ int alloc_fb(gsr_ctx* c)
 
 int finish_frame(gsr_ctx* c);
 void comm_release(gsr_ctx* c);
+int delivery_alloc(gsr_ctx* c, int slots);
+void delivery_free(gsr_ctx* c);
+bool delivery_frame_held(const gsr_ctx* c);
 int handle_overflow(gsr_ctx* c, uint64_t* newly);
 inline bool overflow_pending(const gsr_ctx* c);
 
@@ -798,6 +816,7 @@ int gsr_destroy(gsr_ctx* c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     comm_release(c);
+    delivery_free(c);
     dev_free(&c->px); dev_free(&c->py); dev_free(&c->pz);
     dev_free(&c->cov0); dev_free(&c->cov1); dev_free(&c->cov2); dev_free(&c->rgba);
     dev_free(&c->sh_r); dev_free(&c->sh_g); dev_free(&c->sh_b); dev_free(&c->shcol);
@@ -1082,6 +1101,9 @@ int gsr_resize(gsr_ctx* c, int32_t w, int32_t h)
 {
     if (!c) return GSR_ERR_ARG;
     if (w <= 0 || h <= 0 || w > 8192 || h > 8192) return fail(c, GSR_ERR_ARG, "bad framebuffer size %dx%d (1..8192)", w, h);
+    const bool new_ring = !c->ring.empty() && (w != c->ring_W || h != c->ring_H);
+    if (new_ring && delivery_frame_held(c))
+        return fail(c, GSR_ERR_ARG, "gsr_resize: a delivered frame is held (gsr_release_frame first): its pixels would be freed");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->comm && (w != c->W || h != c->H)) comm_release(c);   // slabs and band edges belong to the old size: join again
@@ -1089,6 +1111,7 @@ int gsr_resize(gsr_ctx* c, int32_t w, int32_t h)
     c->band_x0 = c->band_x1 = 0;
     c->have_frame = false;
     if (int r = alloc_fb(c)) return r;
+    if (new_ring) { if (int r = delivery_alloc(c, (int)c->ring.size())) return r; }
     return alloc_bins(c);
 }
 
@@ -1165,6 +1188,7 @@ int gsr_sync(gsr_ctx* c)
     HIP_TRY(c, hipSetDevice(c->device));
     if (int r = sync_and_repair(c)) return r;
     if (c->comm_stream) HIP_TRY(c, hipStreamSynchronize(c->comm_stream));   // the frame exchange, if one is in flight
+    if (c->copy_stream) HIP_TRY(c, hipStreamSynchronize(c->copy_stream));   // frame deliveries in flight
     if (c->dropped_unreported) {
         const unsigned long long k = c->dropped_unreported;
         c->dropped_unreported = 0;
@@ -1686,6 +1710,207 @@ int gsr_read_frame_rgba8(gsr_ctx* c, uint8_t* out)
 
 void* gsr_frame8_device_ptr(gsr_ctx* c) { return c ? (void*)c->frame8 : nullptr; }
 void* gsr_comm_stream_handle(gsr_ctx* c) { return c ? (void*)c->comm_stream : nullptr; }
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------
+// Frame delivery: finished RGBA8 frames reach the host through a ring of pinned blocks while the next frames render.
+// A slot is FREE, IN_FLIGHT (gsr_deliver_frame_async took it: kernel and copy are enqueued) or HELD (the host acquired it
+// and reads its pixels).  It becomes FREE again only through the host -- gsr_release_frame, or a gsr_acquire_frame that
+// refuses the frame -- and both come after a wait for the slot's copy: a free slot never has device work outstanding, so
+// taking one needs no device-side wait on its previous use.
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+
+using DeliverySlot = gsr_ctx::DeliverySlot;
+
+inline size_t ring_pixel_bytes(const gsr_ctx* c) { return (size_t)c->ring_W * c->ring_H * 4; }
+inline bool in_group(const gsr_ctx* c) { return c->comm || c->comm_fn; }
+
+bool delivery_frame_held(const gsr_ctx* c)
+{
+    for (const DeliverySlot& sl : c->ring) if (sl.state == DeliverySlot::HELD) return true;
+    return false;
+}
+
+// waits for every copy in flight (and the conversion kernels in front of them), then frees the ring
+void delivery_free(gsr_ctx* c)
+{
+    if (!c->ring.empty()) {
+        if (c->stream) (void)hipStreamSynchronize(c->stream);
+        if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
+    }
+    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+    for (DeliverySlot& sl : c->ring) {
+        if (sl.done) (void)hipEventSynchronize(sl.done);   // (a copy issued on an exchange stream this context has left since)
+        if (sl.done) (void)hipEventDestroy(sl.done);
+        if (sl.host) (void)hipHostFree(sl.host);
+        dev_free(&sl.staging);
+    }
+    c->ring.clear();
+    if (c->ev_staged) (void)hipEventDestroy(c->ev_staged);
+    c->ev_staged = nullptr;
+    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
+    c->copy_stream = nullptr;
+    c->ring_W = c->ring_H = 0;
+    c->ring_next = 0;
+}
+
+// (re)allocates the ring for the context's current size; frames in flight are waited for and dropped
+int delivery_alloc(gsr_ctx* c, int slots)
+{
+    delivery_free(c);
+    c->ring_W = c->W; c->ring_H = c->H;
+    const size_t bytes = ring_pixel_bytes(c) + DELIVER_TRAILER_WORDS * 4;
+    auto bail = [c](int code) { delivery_free(c); return code; };
+    hipError_t e = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_staged, hipEventDisableTiming);
+    c->ring.resize((size_t)slots);
+    for (DeliverySlot& sl : c->ring) {
+        if (e == hipSuccess) e = hipHostMalloc((void**)&sl.host, bytes, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc((void**)&sl.staging, bytes);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
+    }
+    if (e != hipSuccess) return bail(fail(c, GSR_ERR_HIP, "allocating the delivery ring (%d slots of %zu bytes) failed: %s", slots, bytes, hipGetErrorString(e)));
+    return GSR_OK;
+}
+
+// the slot holding frame `serial` in state `want`; serial 0: the oldest frame in flight
+DeliverySlot* find_slot(gsr_ctx* c, uint64_t serial, DeliverySlot::State want)
+{
+    DeliverySlot* found = nullptr;
+    for (DeliverySlot& sl : c->ring) {
+        if (sl.state != want) continue;
+        if (serial ? sl.serial == serial : (!found || sl.serial < found->serial)) found = &sl;
+    }
+    return found;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gsr_delivery_open(gsr_ctx* c, int32_t slots)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (slots < 2 || slots > 8) return fail(c, GSR_ERR_ARG, "gsr_delivery_open: %d slots (2..8)", slots);
+    if (!c->W || !c->H) return fail(c, GSR_ERR_ARG, "gsr_delivery_open: set the framebuffer size first");
+    if (delivery_frame_held(c)) return fail(c, GSR_ERR_ARG, "gsr_delivery_open: a delivered frame is held (gsr_release_frame first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return delivery_alloc(c, slots);
+}
+
+int gsr_delivery_close(gsr_ctx* c)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (c->ring.empty()) return fail(c, GSR_ERR_ARG, "gsr_delivery_close: no delivery ring (gsr_delivery_open)");
+    if (delivery_frame_held(c)) return fail(c, GSR_ERR_ARG, "gsr_delivery_close: a delivered frame is held (gsr_release_frame first): its pixels would be freed");
+    HIP_TRY(c, hipSetDevice(c->device));
+    delivery_free(c);
+    return GSR_OK;
+}
+
+int gsr_deliver_frame_async(gsr_ctx* c, uint64_t* serial)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (c->ring.empty()) return fail(c, GSR_ERR_ARG, "gsr_deliver_frame_async: no delivery ring (gsr_delivery_open)");
+    const bool group = in_group(c);
+    if (group ? !c->frame8_valid : !c->have_frame)
+        return fail(c, GSR_ERR_ARG, group ? "gsr_deliver_frame_async: no gathered frame yet (gsr_allgather_frame_async)" : "gsr_deliver_frame_async: nothing rendered yet");
+    DeliverySlot* sl = nullptr;
+    const int slots = (int)c->ring.size();
+    for (int k = 0; k < slots && !sl; k++) {
+        DeliverySlot& cand = c->ring[(size_t)((c->ring_next + k) % slots)];
+        if (cand.state == DeliverySlot::FREE) sl = &cand;
+    }
+    if (!sl) return fail(c, GSR_ERR_BUSY, "gsr_deliver_frame_async: all %d delivery slots are in flight or held (gsr_acquire_frame / gsr_release_frame)", slots);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint64_t k = c->deliver_serial + 1;
+    const size_t bytes = ring_pixel_bytes(c) + DELIVER_TRAILER_WORDS * 4;
+    hipError_t e;
+    if (group) {
+        // the gathered frame and the word behind it (one bit per rank whose band is stale) are what k_unpack_slabs_rgba8 left on the
+        // exchange stream; the copy goes behind it there, in front of the next frame's de-slab
+        static_assert(SLAB_FLAG_WORDS == DELIVER_TRAILER_WORDS, "the gathered frame's flag words are the delivered frame's trailer");
+        e = hipMemcpyAsync(sl->host, c->frame8, bytes, hipMemcpyDeviceToHost, c->comm_stream);
+        if (e == hipSuccess) e = hipEventRecord(sl->done, c->comm_stream);
+    } else {
+        // render stream: the conversion only (it has read fb before the next frame's compositor starts); copy stream: the copy
+        launch_deliver_rgba8(c->fb, sl->staging, c->W, c->H, k, &c->fstate->overflow, c->stream);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipEventRecord(c->ev_staged, c->stream);
+        if (e == hipSuccess) e = hipStreamWaitEvent(c->copy_stream, c->ev_staged, 0);
+        if (e == hipSuccess) e = hipMemcpyAsync(sl->host, sl->staging, bytes, hipMemcpyDeviceToHost, c->copy_stream);
+        if (e == hipSuccess) e = hipEventRecord(sl->done, c->copy_stream);
+    }
+    if (e != hipSuccess)   // (the slot was never marked taken: it is still on the free list)
+        return fail(c, GSR_ERR_HIP, "gsr_deliver_frame_async: frame %llu: %s", (unsigned long long)k, hipGetErrorString(e));
+    sl->serial = c->deliver_serial = k;
+    sl->state = DeliverySlot::IN_FLIGHT;
+    c->ring_next = (int)(sl - c->ring.data() + 1) % slots;
+    if (serial) *serial = k;
+    return GSR_OK;
+}
+
+int gsr_frame_ready(gsr_ctx* c, uint64_t serial)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (c->ring.empty()) return fail(c, GSR_ERR_ARG, "gsr_frame_ready: no delivery ring (gsr_delivery_open)");
+    if (serial && find_slot(c, serial, DeliverySlot::HELD)) return 1;
+    DeliverySlot* sl = find_slot(c, serial, DeliverySlot::IN_FLIGHT);
+    if (!sl) return fail(c, GSR_ERR_ARG, "gsr_frame_ready: frame %llu is not in the ring", (unsigned long long)serial);
+    const hipError_t e = hipEventQuery(sl->done);
+    if (e == hipSuccess) return 1;
+    if (e == hipErrorNotReady) return 0;
+    return fail(c, GSR_ERR_HIP, "gsr_frame_ready: frame %llu: %s", (unsigned long long)sl->serial, hipGetErrorString(e));
+}
+
+int gsr_acquire_frame(gsr_ctx* c, uint64_t serial, gsr_frame* out)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (!out) return fail(c, GSR_ERR_ARG, "gsr_acquire_frame: out is NULL");
+    if (c->ring.empty()) return fail(c, GSR_ERR_ARG, "gsr_acquire_frame: no delivery ring (gsr_delivery_open)");
+    DeliverySlot* sl = find_slot(c, serial, DeliverySlot::IN_FLIGHT);
+    if (!sl) return fail(c, GSR_ERR_ARG, serial ? "gsr_acquire_frame: frame %llu is not in flight" : "gsr_acquire_frame: no frame is in flight", (unsigned long long)serial);
+    // this frame's copy only: the frames enqueued behind it keep running
+    const hipError_t e = hipEventSynchronize(sl->done);
+    if (e != hipSuccess) {
+        sl->state = DeliverySlot::FREE;
+        return fail(c, GSR_ERR_HIP, "gsr_acquire_frame: frame %llu: %s", (unsigned long long)sl->serial, hipGetErrorString(e));
+    }
+    uint32_t flag;   // the frame's overflow word; in a group: the ranks whose band is stale
+    memcpy(&flag, sl->host + ring_pixel_bytes(c), 4);
+    if (flag) {
+        sl->state = DeliverySlot::FREE;
+        return fail(c, GSR_ERR_OVERFLOW, "delivered frame %llu was not composited (flags 0x%x): its bin lists did not fit and the framebuffer kept "
+                                         "the preceding image; the slot is free again, render and deliver that pose again (gsr_render_async regrows the lists)",
+                    (unsigned long long)sl->serial, flag);
+    }
+    sl->state = DeliverySlot::HELD;
+    out->pixels = sl->host;
+    out->width = c->ring_W; out->height = c->ring_H;
+    out->slot = (int32_t)(sl - c->ring.data());
+    out->serial = sl->serial;
+    return GSR_OK;
+}
+
+int gsr_release_frame(gsr_ctx* c, uint64_t serial)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (c->ring.empty()) return fail(c, GSR_ERR_ARG, "gsr_release_frame: no delivery ring (gsr_delivery_open)");
+    DeliverySlot* sl = serial ? find_slot(c, serial, DeliverySlot::HELD) : nullptr;
+    if (!sl) return fail(c, GSR_ERR_ARG, "gsr_release_frame: frame %llu is not held", (unsigned long long)serial);
+    sl->state = DeliverySlot::FREE;
+    return GSR_OK;
+}
+
+void* gsr_delivery_slot_ptr(gsr_ctx* c, int32_t slot, uint64_t* bytes)
+{
+    if (bytes) *bytes = 0;
+    if (!c || slot < 0 || (size_t)slot >= c->ring.size()) return nullptr;
+    if (bytes) *bytes = ring_pixel_bytes(c);
+    return c->ring[(size_t)slot].host;
+}
 
 }  // extern "C"
 

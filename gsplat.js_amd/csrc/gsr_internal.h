@@ -269,6 +269,23 @@ struct BlendBuffers {
 void launch_blend(const BlendBuffers& b, const BinGrid& g, float early_out_eps, hipStream_t s, hipEvent_t between);
 void launch_clear_fb(float4* fb, int32_t W, int32_t H, hipStream_t s);
 void launch_to_rgba8(const float4* fb, uint32_t* out, uint32_t npix, hipStream_t s);
+// The one statement of the f32 -> RGBA8 rounding (k_to_rgba8, k_pack_band_rgba8, k_deliver_rgba8): round(clamp(x, 0, 1) * 255),
+// built without contraction like the rest of the device code.
+#ifdef __HIPCC__
+__device__ __forceinline__ uint32_t to_rgba8(float4 v)
+{
+    auto q = [](float x) -> uint32_t {
+        x = fminf(fmaxf(x, 0.0f), 1.0f);
+        return (uint32_t)(x * 255.0f + 0.5f);
+    };
+    return q(v.x) | (q(v.y) << 8) | (q(v.z) << 16) | (q(v.w) << 24);
+}
+#endif
+// Frame delivery (k_deliver.hip): the framebuffer as RGBA8 into a delivery slot's device staging, npix pixels followed by a
+// DELIVER_TRAILER_WORDS trailer: [0] the frame's overflow word (non-zero: the frame was not composited, the pixels are the
+// preceding image), [1] W | H << 16, [2] / [3] the frame's serial, low / high word.
+constexpr int DELIVER_TRAILER_WORDS = 4;
+void launch_deliver_rgba8(const float4* fb, uint32_t* staging, int32_t W, int32_t H, uint64_t serial, const uint32_t* overflow, hipStream_t s);
 
 // multi-GPU exchange helpers (RGBA8 slabs of the all-gather)
 constexpr int MAX_SLABS = 16;

@@ -733,15 +733,6 @@ void launch_clear_fb(float4* fb, int32_t W, int32_t H, hipStream_t s)
     hipLaunchKernelGGL(k_clear_fb, dim3((npix + 255) / 256), dim3(256), 0, s, fb, npix);
 }
 
-__device__ __forceinline__ uint32_t to_rgba8(float4 v)
-{
-    auto q = [](float x) -> uint32_t {
-        x = fminf(fmaxf(x, 0.0f), 1.0f);
-        return (uint32_t)(x * 255.0f + 0.5f);
-    };
-    return q(v.x) | (q(v.y) << 8) | (q(v.z) << 16) | (q(v.w) << 24);
-}
-
 // round(clamp(x, 0, 1) * 255) per channel (Appendix A of SURVEY.md: output framebuffer contract)
 __global__ void k_to_rgba8(const float4* __restrict__ fb, uint32_t* __restrict__ out, uint32_t npix)
 {

@@ -96,6 +96,13 @@ export interface FrameStats {
     msProjectKey: number; msSort: number; msBin: number; msBlend: number; msCombine: number; msTotal: number;
     visible: number; binEntries: number; tileEntries: number; n: number; frames: number;
 }
+export interface DeliveredFrame {
+    serial: number;
+    /** RGBA8, row 0 = top: byte for byte what readPixels() returns for that frame */
+    pixels: Uint8Array;
+    width: number; height: number;
+    release(): void;
+}
 export class HIPRenderer {
     width: number; height: number;
     constructor(targetOrOptions?: HIPRendererOptions | { width: number; height: number } | null, shaderPasses?: ShaderPass[] | null);
@@ -137,6 +144,21 @@ export class HIPRenderer {
     /** RGBA8, row 0 = top; pass an array of width*height*4 elements to have it filled and returned (no allocation per frame). */
     readPixels(out?: Uint8Array): Uint8Array;
     readPixelsFloat(out?: Float32Array): Float32Array;
+    /** Frame delivery: a ring of `slots` (2..8, default 3) pinned RGBA8 frames inside the library.  renderAsync() +
+     *  deliverFrame() enqueue a frame and its copy to the host without waiting; acquireFrame() waits for that frame's copy
+     *  only, so frame k is presented while k+1 and k+2 render.  Works after joinGroup() too (the gathered frame). */
+    openDelivery(slots?: number): void;
+    /** throws while a frame is held; detaches the slots' ArrayBuffers (old `pixels` views then have length 0) */
+    closeDelivery(): void;
+    /** enqueue the delivery of the frame enqueued last; returns its serial (1, 2, 3 ...).  Throws ("... (-7) ...") and
+     *  enqueues nothing when every slot is in flight or held. */
+    deliverFrame(): number;
+    /** has the frame's copy finished?  never blocks.  serial 0 / omitted: the oldest frame not acquired yet */
+    frameReady(serial?: number): boolean;
+    /** Waits for frame `serial` (omitted: the oldest not acquired yet).  `pixels` views the slot's pinned block -- no copy,
+     *  no allocation, `pixels.buffer` is the same ArrayBuffer every lap of the ring -- and stays valid until release().
+     *  A frame that was not composited (list overflow) throws ("... (-5) ...") and frees its slot: render that pose again. */
+    acquireFrame(serial?: number): DeliveredFrame;
     lastDepthIndex(): Uint32Array;
     stats(): FrameStats;
     deviceInfo(): { name: string; computeUnits: number; clockKhz: number };

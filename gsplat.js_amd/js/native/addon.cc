@@ -1,6 +1,7 @@
 // gsplat_hip.node -- N-API (raw node_api.h, N-API <= 8, Node >= 12) binding of the C ABI in
 // include/gsplat_hip.h.  TypedArray backing stores are handed to the library zero-copy for the duration of
 // each call; nothing is retained.  Every failure becomes a JavaScript exception carrying gsr_last_error().
+// The one thing handed the other way is the delivery ring: its pinned blocks become external ArrayBuffers (see DeliverySlots).
 #include <node_api.h>
 
 #include <cstdint>
@@ -449,6 +450,141 @@ napi_value ReadFrame(napi_env env, napi_callback_info info)
     return rc ? throw_gsr(env, c, rc, "gsr_read_frame_rgba8") : undefined(env);
 }
 
+// ---- frame delivery (gsr_delivery_*): the ring's pinned blocks as external ArrayBuffers, wrapped ONCE per slot ----
+// An ArrayBuffer must never outlive the block it views.  Two guards: (1) every ArrayBuffer holds a reference to the renderer
+// handle until it is collected, so a renderer that is merely dropped keeps its context (and ring) alive as long as any
+// `pixels` view is reachable; (2) before the ring is freed or reallocated on purpose (closeDelivery, setSize, dispose) the
+// JavaScript side hands the buffers to detachBuffers(): a detached ArrayBuffer has length 0 and its views read nothing.
+void release_handle_ref(napi_env env, void*, void* hint)
+{
+    if (hint) napi_delete_reference(env, static_cast<napi_ref>(hint));
+}
+
+// deliverySlots(handle) -> [ArrayBuffer, ...], one per slot of the open ring
+napi_value DeliverySlots(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    if (!c) return nullptr;
+    napi_value arr;
+    NAPI_OK_OR_NULL(env, napi_create_array(env, &arr));
+    for (int32_t k = 0;; k++) {
+        uint64_t bytes = 0;
+        void* p = gsr_delivery_slot_ptr(c, k, &bytes);
+        if (!p) break;
+        napi_ref keep = nullptr;
+        NAPI_OK_OR_NULL(env, napi_create_reference(env, argv[0], 1, &keep));
+        napi_value ab;
+        if (napi_create_external_arraybuffer(env, p, (size_t)bytes, release_handle_ref, keep, &ab) != napi_ok) {
+            napi_delete_reference(env, keep);
+            napi_throw_error(env, nullptr, "napi_create_external_arraybuffer failed");
+            return nullptr;
+        }
+        NAPI_OK_OR_NULL(env, napi_set_element(env, arr, (uint32_t)k, ab));
+    }
+    return arr;
+}
+
+// openDelivery(handle, slots) -> [ArrayBuffer, ...]
+napi_value OpenDelivery(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    int32_t slots;
+    if (!c || !get_i32(env, argv[1], &slots)) return nullptr;
+    const int rc = gsr_delivery_open(c, slots);
+    if (rc) return throw_gsr(env, c, rc, "gsr_delivery_open");
+    return DeliverySlots(env, info);
+}
+
+// detachBuffers([ArrayBuffer, ...]): the blocks behind them are about to be freed
+napi_value DetachBuffers(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    uint32_t n = 0;
+    if (napi_get_array_length(env, argv[0], &n) != napi_ok) { napi_throw_type_error(env, nullptr, "expected an array of ArrayBuffers"); return nullptr; }
+    for (uint32_t k = 0; k < n; k++) {
+        napi_value ab;
+        bool detached = false;
+        NAPI_OK_OR_NULL(env, napi_get_element(env, argv[0], k, &ab));
+        if (napi_is_detached_arraybuffer(env, ab, &detached) == napi_ok && detached) continue;
+        NAPI_OK_OR_NULL(env, napi_detach_arraybuffer(env, ab));
+    }
+    return undefined(env);
+}
+
+// deliverFrame(handle) -> serial (a Number: 2^53 frames are out of reach)
+napi_value DeliverFrame(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    if (!c) return nullptr;
+    uint64_t serial = 0;
+    const int rc = gsr_deliver_frame_async(c, &serial);
+    if (rc) return throw_gsr(env, c, rc, "gsr_deliver_frame_async");
+    napi_value v;
+    NAPI_OK_OR_NULL(env, napi_create_double(env, (double)serial, &v));
+    return v;
+}
+
+bool get_serial(napi_env env, napi_value v, uint64_t* out)
+{
+    double d = 0;
+    if (!get_f64(env, v, &d) || d < 0) { napi_throw_type_error(env, nullptr, "expected a frame serial"); return false; }
+    *out = (uint64_t)d;
+    return true;
+}
+
+// frameReady(handle, serial) -> boolean
+napi_value FrameReady(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    uint64_t serial;
+    if (!c || !get_serial(env, argv[1], &serial)) return nullptr;
+    const int rc = gsr_frame_ready(c, serial);
+    if (rc < 0) return throw_gsr(env, c, rc, "gsr_frame_ready");
+    napi_value b;
+    NAPI_OK_OR_NULL(env, napi_get_boolean(env, rc != 0, &b));
+    return b;
+}
+
+// acquireFrame(handle, serial) -> [serial, slot]
+napi_value AcquireFrame(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    uint64_t serial;
+    if (!c || !get_serial(env, argv[1], &serial)) return nullptr;
+    gsr_frame f;
+    const int rc = gsr_acquire_frame(c, serial, &f);
+    if (rc) return throw_gsr(env, c, rc, "gsr_acquire_frame");
+    napi_value arr, a, b;
+    NAPI_OK_OR_NULL(env, napi_create_array_with_length(env, 2, &arr));
+    NAPI_OK_OR_NULL(env, napi_create_double(env, (double)f.serial, &a));
+    NAPI_OK_OR_NULL(env, napi_create_int32(env, f.slot, &b));
+    NAPI_OK_OR_NULL(env, napi_set_element(env, arr, 0, a));
+    NAPI_OK_OR_NULL(env, napi_set_element(env, arr, 1, b));
+    return arr;
+}
+
+napi_value ReleaseFrame(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    uint64_t serial;
+    if (!c || !get_serial(env, argv[1], &serial)) return nullptr;
+    const int rc = gsr_release_frame(c, serial);
+    return rc ? throw_gsr(env, c, rc, "gsr_release_frame") : undefined(env);
+}
+
 napi_value BuildId(napi_env env, napi_callback_info)
 {
     napi_value s;
@@ -509,6 +645,8 @@ napi_value Init(napi_env env, napi_value exports)
         {"deviceInfo", DeviceInfo}, {"sortHost", SortHost}, {"overflowPending", OverflowPending},
         {"setListCapacity", SetListCapacity}, {"buildId", BuildId}, {"commUniqueId", CommUniqueId}, {"commInit", CommInit}, {"commShare", CommShare},
         {"commDestroy", Call0<gsr_comm_destroy>}, {"allgatherFrameAsync", Call0<gsr_allgather_frame_async>}, {"readFrame", ReadFrame},
+        {"openDelivery", OpenDelivery}, {"closeDelivery", Call0<gsr_delivery_close>}, {"deliverySlots", DeliverySlots}, {"detachBuffers", DetachBuffers},
+        {"deliverFrame", DeliverFrame}, {"frameReady", FrameReady}, {"acquireFrame", AcquireFrame}, {"releaseFrame", ReleaseFrame},
     };
     for (auto& f : fns) {
         napi_value fn;

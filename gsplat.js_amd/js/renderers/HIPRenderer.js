@@ -49,10 +49,54 @@ class HIPRenderer {
         };
         const onSceneChange = () => upload();   // WebGLRenderer.ts:234-239
 
+        // ---- frame delivery: finished RGBA8 frames through the library's pinned ring while the next frames render ----
+        //   renderer.openDelivery(3);
+        //   renderer.renderAsync(scene, camera); const k = renderer.deliverFrame();   // no host wait; throws when the ring is full
+        //   ... further frames ...
+        //   const f = renderer.acquireFrame(k);   // waits for THAT frame's copy only; f.pixels: Uint8Array, width*height*4
+        //   present(f.pixels); f.release();       // the slot may be reused
+        // `pixels` is a view of the slot's pinned block: one external ArrayBuffer per slot, created when the ring is opened, so
+        // nothing is allocated or copied per frame and `pixels.buffer` is the same object every lap.  Before the blocks are freed
+        // (closeDelivery, setSize to another size, dispose) the buffers are detached: an old view then has length 0.
+        let slotBuffers = null, slotViews = null;
+        const held = new Map();                  // serial -> frame object
+        const wrapSlots = (buffers) => { slotBuffers = buffers; slotViews = buffers.map((b) => new Uint8Array(b)); };
+        const dropSlots = () => {
+            if (slotBuffers) this._n.detachBuffers(slotBuffers);
+            slotBuffers = slotViews = null;
+        };
+        const refuseWhileHeld = (what) => {
+            if (held.size) throw new Error(what + ": a delivered frame is held (release() it first): its pixels would be freed");
+        };
+        this.openDelivery = (slots) => {
+            refuseWhileHeld("openDelivery");
+            dropSlots();
+            wrapSlots(this._n.openDelivery(this._h, slots === undefined ? 3 : slots));
+        };
+        this.closeDelivery = () => {
+            refuseWhileHeld("closeDelivery");
+            dropSlots();
+            this._n.closeDelivery(this._h);
+        };
+        this.deliverFrame = () => this._n.deliverFrame(this._h);
+        this.frameReady = (serial) => this._n.frameReady(this._h, serial || 0);
+        // A frame that was not composited (bin-list overflow behind renderAsync) throws ("... was not composited") and frees its
+        // slot: render and deliver that pose again.
+        this.acquireFrame = (serial) => {
+            const f = this._n.acquireFrame(this._h, serial || 0);
+            const frame = { serial: f[0], pixels: slotViews[f[1]], width: this.width, height: this.height,
+                            release: () => { if (held.delete(frame.serial)) this._n.releaseFrame(this._h, frame.serial); } };
+            held.set(frame.serial, frame);
+            return frame;
+        };
+
         this.setSize = (width, height) => {     // WebGLRenderer.ts:85-102
+            const ring = slotBuffers !== null && (width !== this.width || height !== this.height);
+            if (ring) { refuseWhileHeld("setSize"); dropSlots(); }
             this.width = width;
             this.height = height;
             this._n.resize(this._h, width, height);
+            if (ring) wrapSlots(this._n.deliverySlots(this._h));   // the ring follows the framebuffer: new blocks
         };
         this.resize = () => {};                  // no DOM: nothing to measure
         this.setBand = (x0, x1) => this._n.setBand(this._h, x0, x1);
@@ -146,7 +190,8 @@ class HIPRenderer {
         this.dispose = () => {                   // WebGLRenderer.ts:298-310
             if (activeScene) activeScene.removeEventListener("change", onSceneChange);
             activeScene = null;
-            if (this._h) { this._n.destroy(this._h); this._h = null; }
+            held.clear();
+            if (this._h) { dropSlots(); this._n.destroy(this._h); this._h = null; }
             initialized = false;
         };
 

@@ -21,6 +21,8 @@ LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "lib", "libgsplat_hi
 
 GSR_FLAG_TIMING = 1
 GSR_FLAG_THROUGHPUT = 2
+GSR_ERR_OVERFLOW = -5
+GSR_ERR_BUSY = -7
 
 
 class GsrOptions(ctypes.Structure):
@@ -41,6 +43,11 @@ class GsrTimings(ctypes.Structure):
                 ("overflow_frames", ctypes.c_uint64), ("dropped_frames", ctypes.c_uint64)]
 
 
+class GsrFrame(ctypes.Structure):
+    _fields_ = [("pixels", ctypes.c_void_p), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("slot", ctypes.c_int32),
+                ("serial", ctypes.c_uint64)]
+
+
 def edge_arrays(edges):
     """[(x0, x1)] per rank -> (c_int32[world], c_int32[world]) for gsr_unpack_slabs_rgba8_async."""
     world = len(edges)
@@ -48,7 +55,8 @@ def edge_arrays(edges):
 
 
 class GsplatError(RuntimeError):
-    pass
+    """`code`: the library's return code (GSR_ERR_*), None for errors raised by the harness itself."""
+    code = None
 
 
 _lib = None
@@ -65,6 +73,8 @@ EXPORTS = [
     "gsr_overflow_pending", "gsr_set_list_capacity", "gsr_scene_count", "gsr_build_id",
     "gsr_comm_unique_id", "gsr_comm_init", "gsr_comm_destroy", "gsr_allgather_frame_async", "gsr_read_frame_rgba8",
     "gsr_frame8_device_ptr", "gsr_comm_stream_handle", "gsr_read_work_items", "gsr_comm_share", "gsr_comm_init_custom",
+    "gsr_delivery_open", "gsr_delivery_close", "gsr_deliver_frame_async", "gsr_frame_ready", "gsr_acquire_frame",
+    "gsr_release_frame", "gsr_delivery_slot_ptr",
 ]
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p)
 GSR_COMM_ID_BYTES = 128
@@ -166,6 +176,14 @@ def load_library(path=None):
     L.gsr_frame8_device_ptr.restype = vp
     L.gsr_comm_stream_handle.argtypes = [vp]
     L.gsr_comm_stream_handle.restype = vp
+    L.gsr_delivery_open.argtypes = [vp, ctypes.c_int32]
+    L.gsr_delivery_close.argtypes = [vp]
+    L.gsr_deliver_frame_async.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+    L.gsr_frame_ready.argtypes = [vp, ctypes.c_uint64]
+    L.gsr_acquire_frame.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(GsrFrame)]
+    L.gsr_release_frame.argtypes = [vp, ctypes.c_uint64]
+    L.gsr_delivery_slot_ptr.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64)]
+    L.gsr_delivery_slot_ptr.restype = vp
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int and name not in ("gsplat_sort_host",):
@@ -296,12 +314,15 @@ class HIPRenderer:
         self._scene = None
         self._camera = None
         self._n = 0
+        self._slot_views = {}   # delivery slot -> [H, W, 4] uint8 view of its pinned block
         self._on_change = lambda _e: self._upload(self._scene)
 
     # -- helpers --
     def _check(self, rc):
         if rc:
-            raise GsplatError("libgsplat_hip error %d: %s" % (rc, self._L.gsr_last_error(self._ctx).decode()))
+            err = GsplatError("libgsplat_hip error %d: %s" % (rc, self._L.gsr_last_error(self._ctx).decode()))
+            err.code = rc
+            raise err
 
     def _upload(self, scene):
         data = np.ascontiguousarray(scene.data, dtype=np.uint32)
@@ -315,6 +336,7 @@ class HIPRenderer:
     def setSize(self, width, height):
         self._check(self._L.gsr_resize(self._ctx, width, height))
         self.width, self.height = width, height
+        self._slot_views = {}   # (a ring of another size has new blocks)
 
     def set_band(self, x0, x1):
         self._check(self._L.gsr_set_band(self._ctx, x0, x1))
@@ -431,6 +453,7 @@ class HIPRenderer:
 
     def dispose(self):
         if self._ctx:
+            self._slot_views = {}
             self._L.gsr_destroy(self._ctx)
             self._ctx = ctypes.c_void_p()
 
@@ -463,6 +486,47 @@ class HIPRenderer:
             raise ValueError("out must be a C-contiguous uint8 array of height*width*4 elements")
         self._check(self._L.gsr_read_pixels_rgba8(self._ctx, out.ctypes.data))
         return out
+
+    # -- frame delivery: RGBA8 frames through the library's pinned ring while the next frames render (gsr_delivery_*) --
+    def open_delivery(self, slots=3):
+        """A ring of `slots` (2..8) pinned frames for deliver() / acquire() / release()."""
+        self._slot_views = {}
+        self._check(self._L.gsr_delivery_open(self._ctx, slots))
+
+    def close_delivery(self):
+        self._slot_views = {}
+        self._check(self._L.gsr_delivery_close(self._ctx))
+
+    def deliver(self):
+        """Enqueue the delivery of the frame enqueued last (in a group: of the frame gathered last); returns its serial.
+        No host wait.  Raises GsplatError with code GSR_ERR_BUSY, and enqueues nothing, when every slot is taken."""
+        k = ctypes.c_uint64(0)
+        self._check(self._L.gsr_deliver_frame_async(self._ctx, ctypes.byref(k)))
+        return k.value
+
+    def frame_ready(self, serial=0):
+        rc = self._L.gsr_frame_ready(self._ctx, serial)
+        if rc < 0:
+            self._check(rc)
+        return bool(rc)
+
+    def acquire(self, serial=0):
+        """Wait for frame `serial`'s copy (0: the oldest frame not acquired yet) -- not for the frames behind it -- and
+        return (serial, pixels): a read-only zero-copy [H, W, 4] uint8 view of the slot's pinned block, valid until
+        release(serial).  A frame that was not composited (list overflow) raises GsplatError with code GSR_ERR_OVERFLOW
+        and frees its slot: render and deliver that pose again."""
+        f = GsrFrame()
+        self._check(self._L.gsr_acquire_frame(self._ctx, serial, ctypes.byref(f)))
+        view = self._slot_views.get(f.slot)
+        if view is None:
+            block = (ctypes.c_uint8 * (f.width * f.height * 4)).from_address(f.pixels)
+            view = np.frombuffer(block, dtype=np.uint8).reshape(f.height, f.width, 4)
+            view.flags.writeable = False
+            self._slot_views[f.slot] = view
+        return f.serial, view
+
+    def release(self, serial):
+        self._check(self._L.gsr_release_frame(self._ctx, serial))
 
     def read_keys(self):
         keys = np.empty(self._n, dtype=np.uint32)

@@ -44,6 +44,7 @@ extern "C" {
 #define GSR_ERR_SCENE (-4)    /* scene buffers inconsistent */
 #define GSR_ERR_OVERFLOW (-5) /* internal list capacity exceeded even after regrowth; or: asynchronous frames were lost (gsr_sync) */
 #define GSR_ERR_COMM (-6)     /* RCCL is unavailable or a collective call failed */
+#define GSR_ERR_BUSY (-7)     /* every delivery slot is in flight or held by the caller (gsr_deliver_frame_async) */
 
 typedef struct gsr_ctx gsr_ctx;
 
@@ -248,6 +249,47 @@ int gsr_allgather_frame_async(gsr_ctx *ctx);
 int gsr_read_frame_rgba8(gsr_ctx *ctx, uint8_t *out /* w*h*4: the gathered frame */);
 void *gsr_frame8_device_ptr(gsr_ctx *ctx);    /* uint8[h][w][4], the gathered frame on the device */
 void *gsr_comm_stream_handle(gsr_ctx *ctx);   /* hipStream_t the exchange runs on */
+
+/* ---- frame delivery: finished RGBA8 frames reach the host through a pinned ring while the next frames render ----
+ * The presenting side of renderer.render (src/renderers/WebGLRenderer.ts:279-290 draws into the canvas every frame).
+ * gsr_read_pixels_rgba8 converts, copies into pageable memory and waits for the whole stream; the ring instead gives
+ * every frame in flight a slot -- one pinned host block of width * height * 4 bytes plus a 16-byte trailer, one device
+ * staging buffer of the same size, one "copy done" event -- and the context a second stream for the copies.  Per frame:
+ *     gsr_render_async(ctx);
+ *     gsr_deliver_frame_async(ctx, &k);   conversion kernel on the render stream (it reads the framebuffer before the next
+ *                                         compositor overwrites it), ONE copy of pixels + trailer on the copy stream, the
+ *                                         slot's event behind it; no host wait, nothing allocated
+ *     ... further frames ...
+ *     gsr_acquire_frame(ctx, k, &f);      waits for THAT frame's copy only, never for the render stream
+ *     ... f.pixels ...                    byte for byte what gsr_read_pixels_rgba8 would have returned for frame k
+ *     gsr_release_frame(ctx, k);          the slot may be reused
+ * Serials count 1, 2, 3 ... per context in gsr_deliver_frame_async order and never restart.  serial 0 means the oldest
+ * delivered frame that has not been acquired.  A slot is taken by gsr_deliver_frame_async and stays taken until
+ * gsr_release_frame (or a failed gsr_acquire_frame); with every slot taken gsr_deliver_frame_async returns GSR_ERR_BUSY
+ * and enqueues nothing.
+ * Overflow: an asynchronous frame whose bin lists did not fit was not composited (see "List overflow" above); the trailer
+ * carries that frame's overflow word, and gsr_acquire_frame on it frees the slot and returns GSR_ERR_OVERFLOW.  The
+ * caller renders that pose again (gsr_render_async regrows the lists before it enqueues).
+ * In a group (gsr_comm_init* / gsr_comm_share) the delivered frame is the gathered frame of the last
+ * gsr_allgather_frame_async: no conversion kernel, the copy runs on the exchange stream behind the de-slab kernel, and a
+ * gathered frame with a stale band is refused with GSR_ERR_OVERFLOW where gsr_read_frame_rgba8 refuses it.
+ * gsr_resize to another size and gsr_delivery_close fail with GSR_ERR_ARG while a frame is held (acquired, not released);
+ * otherwise they wait for the copies and free or reallocate the ring (frames delivered but not acquired are gone, slot
+ * pointers change).  gsr_sync also waits for the copies in flight; gsr_destroy waits and frees the ring. */
+typedef struct gsr_frame {
+    const uint8_t *pixels;  /* pinned host memory, uint8[height][width][4], row 0 = top; valid until gsr_release_frame */
+    int32_t width, height, slot;
+    uint64_t serial;
+} gsr_frame;
+int gsr_delivery_open(gsr_ctx *ctx, int32_t slots /* 2..8 */);
+int gsr_delivery_close(gsr_ctx *ctx);
+int gsr_deliver_frame_async(gsr_ctx *ctx, uint64_t *serial /* out; may be NULL */);
+int gsr_frame_ready(gsr_ctx *ctx, uint64_t serial);   /* 1: its copy has finished, 0: not yet, < 0: error; never blocks */
+int gsr_acquire_frame(gsr_ctx *ctx, uint64_t serial, gsr_frame *out);
+int gsr_release_frame(gsr_ctx *ctx, uint64_t serial);
+/* The pinned block of slot `slot` (0 .. slots-1) and its size in pixel bytes, for hosts that wrap every slot once
+ * (an external ArrayBuffer per slot); NULL without a ring.  The pointers change only when the ring is reallocated. */
+void *gsr_delivery_slot_ptr(gsr_ctx *ctx, int32_t slot, uint64_t *bytes);
 
 /* ---- device interop (torch / RCCL plumbing in the harness) ---- */
 void *gsr_framebuffer_device_ptr(gsr_ctx *ctx); /* float4[h][w] on the device */

@@ -5,6 +5,10 @@
 #   ab ARGS...                scripts/ab_bench.py ARGS (variants "base@ENV=v,ENV2=v" or lib_exp names) -> gpurun_out/ab.log
 #   py SCRIPT [ARGS]          python SCRIPT ARGS
 #   trace NAME [BENCH_ARGS]   rocprofv3 --kernel-trace --stats of `bench.py --timed-only BENCH_ARGS` -> gpurun_out/trace_NAME/
+#   copytrace DIR [ARGS]   the trace task's profiler run with --memory-copy-trace added, around `scripts/bench_delivery.py --timed-only ARGS`:
+#                             kernels AND copies on one timeline (the delivery ring's device-to-host copies under the next frames'
+#                             kernels; no counters in this run) -> DIR/ (pass a directory under the runner's output directory);
+#                             scripts/copy_overlap.py DIR BYTES summarises it
 #   pmc LEG [BENCH_ARGS]      LEG = solo (one frame at a time) | inflight (the default bench's timed region): four separate
 #                             rocprofv3 --pmc passes (never combined with a tracing domain) of `bench.py --timed-only`
 #                             -> gpurun_out/pmc/LEG_{sq1,sq2,fetch,write} (scripts/pmc_summary.py, make_blend_traffic.py)
@@ -25,6 +29,9 @@ run_task() {
     trace) local name=$1; shift; rm -rf gpurun_out/trace_$name
            (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/trace_$name -- \
               python3 $R/bench.py --timed-only --no-cpu-baseline "$@" > $R/gpurun_out/trace_$name.log 2>&1) ;;
+    copytrace) local dir=$R/$1; shift; rm -rf "$dir"; mkdir -p "$dir"
+           (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d "$dir" -- \
+              python3 $R/scripts/bench_delivery.py --timed-only "$@" > "$dir/bench_delivery.log" 2>&1) ;;
     pmc)   local leg=$1; shift; mkdir -p gpurun_out/pmc; rm -rf gpurun_out/pmc/${leg}_*
            local legargs=""; [ "$leg" = solo ] && legargs="--frames-in-flight 1"
            python -c "import sys; sys.path[:0]=['$R','$R/gsplat.js_amd/py']; import gsplat_hip as g; print(g.build_id())" > gpurun_out/pmc/build_id.txt

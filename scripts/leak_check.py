@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Create / render / resize / destroy contexts in a loop and watch the device's free memory (hipMemGetInfo via torch)."""
+"""Create / render / resize / destroy contexts (some with a delivery ring) in a loop and watch the device's free memory (hipMemGetInfo via torch)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "gsplat.js_amd", "py"))
@@ -15,6 +15,14 @@ for it in range(120):
         if k == 3:
             r.setSize(512 + 32 * (it % 4), 384)
     r.lastDepthIndex()
+    if it % 3 == 1:    # a delivery ring (pinned blocks, staging, copy stream): resized with the context, destroyed with copies in flight
+        r.open_delivery(2 + it % 2)
+        cam = gh.orbit_camera(4, width=r.width, height=r.height, fx=cfg["fx"])
+        r.render(scene, cam, sync=False); r.deliver()
+        r.release(r.acquire()[0])
+        r.setSize(640, 480)
+        r.render(scene, cam, sync=False); r.deliver()
+        r.render_async(); r.deliver()
     if it % 6 == 0:    # a 4K framebuffer: the two-level binning's buffers come and go with the context too
         r.setSize(3840, 2160)
         r.render(scene, gh.orbit_camera(1, width=3840, height=2160, fx=2.0 * cfg["fx"]))

@@ -3,7 +3,10 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver]
+// --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
+// gsr_deliver_frame_async, gsr_acquire_frame, gsr_release_frame: three slots per context, the oldest frame picked up when the
+// ring is full) -- the header alone is enough to consume frames -- and reports its rate and the checksum of a delivered frame.
 //
 // Scene: the seeded synthetic generator of gsplat_hip/synth.py (mulberry32 counter PRNG, 24 draws per splat) written
 // out again in C++; log/exp/cos come from libm here and from numpy there, so a byte may differ in a rare rounding --
@@ -120,6 +123,7 @@ int main(int argc, char** argv)
 {
     std::string config = "C1", rows_path, dump;
     int frames = 240, warmup = 20, in_flight = 3;
+    bool deliver = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : ""; };
@@ -129,7 +133,8 @@ int main(int argc, char** argv)
         else if (a == "--warmup") warmup = std::atoi(next());
         else if (a == "--in-flight") in_flight = std::atoi(next());
         else if (a == "--dump") dump = next();
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix]\n"); return 2; }
+        else if (a == "--deliver") deliver = true;
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
@@ -190,15 +195,68 @@ int main(int argc, char** argv)
         f = std::fopen((dump + ".rgba8.bin").c_str(), "wb");
         if (f) { std::fwrite(px.data(), 1, px.size(), f); std::fclose(f); }
     }
+    // --deliver: the same orbit with every frame delivered; then pose 0 once more, delivered, against the blocking read above
+    double delivered_sec = 0;
+    unsigned long long delivered_hash = 0;
+    uint64_t delivered = 0, sink = 0;
+    if (deliver) {
+        for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_delivery_open(c, 3)); }
+        auto pick_up = [&](gsr_ctx* c) -> int {   // the oldest frame of this context
+            gsr_frame f;
+            if (int rc = gsr_acquire_frame(c, 0, &f)) return rc;
+            sink += f.pixels[(size_t)f.width * f.height * 2];
+            delivered++;
+            return gsr_release_frame(c, f.serial);
+        };
+        auto deliver_step = [&](int k) -> int {
+            gsr_ctx* c = ctx[k % in_flight];
+            if (int rc = step(k)) return rc;
+            int rc = gsr_deliver_frame_async(c, nullptr);
+            if (rc == GSR_ERR_BUSY) {
+                if ((rc = pick_up(c))) return rc;
+                rc = gsr_deliver_frame_async(c, nullptr);
+            }
+            return rc;
+        };
+        auto drain = [&]() -> int {
+            for (gsr_ctx* c : ctx)
+                while (gsr_frame_ready(c, 0) >= 0) { ctx0 = c; if (int rc = pick_up(c)) return rc; }
+            return 0;
+        };
+        for (int k = 0; k < warmup; k++) { ctx0 = ctx[k % in_flight]; CHECK(deliver_step(k)); }
+        CHECK(drain());
+        delivered = 0;
+        const auto d0 = std::chrono::steady_clock::now();
+        for (int k = 0; k < frames; k++) { ctx0 = ctx[(warmup + k) % in_flight]; CHECK(deliver_step(warmup + k)); }
+        CHECK(drain());
+        delivered_sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - d0).count();
+        if (delivered != (uint64_t)frames) { std::fprintf(stderr, "%llu of %d frames were delivered\n", (unsigned long long)delivered, frames); return 1; }
+        ctx0 = ctx[0];
+        CHECK(gsr_set_camera(ctx[0], poses[0].view, poses[0].proj, poses[0].vp, (float)cfg->fx, (float)cfg->fx));
+        CHECK(gsr_render_async(ctx[0]));
+        uint64_t serial = 0;
+        gsr_frame f;
+        CHECK(gsr_deliver_frame_async(ctx[0], &serial));
+        CHECK(gsr_acquire_frame(ctx[0], serial, &f));
+        delivered_hash = (unsigned long long)fnv1a(f.pixels, (size_t)f.width * f.height * 4);
+        const bool same = f.width == cfg->w && f.height == cfg->h && !std::memcmp(f.pixels, px.data(), px.size());
+        CHECK(gsr_release_frame(ctx[0], serial));
+        if (!same) { std::fprintf(stderr, "the delivered frame differs from gsr_read_pixels_rgba8\n"); return 1; }
+    }
     char name[128] = "";
     int32_t cus = 0, khz = 0;
     (void)gsr_device_info(ctx[0], name, (int32_t)sizeof name, &cus, &khz);
     std::printf("{\"caller\": \"C++ (tools/bench_cabi.cpp)\", \"config\": \"%s\", \"n\": %u, \"width\": %d, \"height\": %d, "
                 "\"frames\": %d, \"warmup\": %d, \"frames_in_flight\": %d, \"frames_per_sec\": %.1f, \"ms_per_frame\": %.4f, "
-                "\"rows_fnv1a\": \"%016llx\", \"depth_index_fnv1a\": \"%016llx\", \"rgba8_fnv1a\": \"%016llx\", \"device\": \"%s\", \"compute_units\": %d}\n",
+                "\"rows_fnv1a\": \"%016llx\", \"depth_index_fnv1a\": \"%016llx\", \"rgba8_fnv1a\": \"%016llx\", \"device\": \"%s\", \"compute_units\": %d",
                 cfg->name, n, cfg->w, cfg->h, frames, warmup, in_flight, frames / sec, sec / frames * 1e3,
                 (unsigned long long)fnv1a(rows.data(), rows.size()), (unsigned long long)fnv1a(di.data(), di.size() * 4),
                 (unsigned long long)fnv1a(px.data(), px.size()), name, cus);
+    if (deliver)
+        std::printf(", \"frames_per_sec_delivered\": %.1f, \"delivery_slots\": 3, \"delivered_rgba8_fnv1a\": \"%016llx\", "
+                    "\"delivered_equals_read_pixels\": true, \"sink\": %d",
+                    frames / delivered_sec, delivered_hash, (int)(sink & 1));
+    std::printf("}\n");
     for (gsr_ctx* c : ctx) gsr_destroy(c);
     return 0;
 }

@@ -53,6 +53,39 @@ const asyncMs = (now() - t0) / frames;
 const info = rs[0].deviceInfo ? rs[0].deviceInfo() : null;
 rs.forEach((x) => x.dispose());
 
+// (3) every frame delivered to the host as RGBA8 through the library's pinned ring (openDelivery(3) / deliverFrame /
+// acquireFrame): `pixels` views the slot, nothing is allocated or copied per frame; a renderer's oldest frame is picked up
+// when its ring is full.  One default renderer, then three throughput renderers with a ring each.
+function delivered(renderers, count) {
+    const pending = renderers.map(() => []);
+    const pickUp = (c) => { const f = renderers[c].acquireFrame(pending[c].shift()); sink += f.pixels[1]; f.release(); };
+    const t = now();
+    for (let k = 0; k < count; k++) {
+        const c = k % renderers.length;
+        if (pending[c].length === 3) pickUp(c);
+        renderers[c].renderAsync(scene, cams[(warm + k) % 120]);
+        pending[c].push(renderers[c].deliverFrame());
+    }
+    for (let c = 0; c < renderers.length; c++) while (pending[c].length) pickUp(c);
+    return (now() - t) / count;
+}
+const d1 = new G.WebGLRenderer({ width: +W, height: +H }, []);
+d1.openDelivery(3);
+delivered([d1], warm);
+const deliver1Ms = delivered([d1], frames);
+// the last delivered frame against readPixels() of the same pose
+d1.renderAsync(scene, cams[5]);
+const last = d1.acquireFrame(d1.deliverFrame());
+d1.readPixels(pixels);
+const deliveredEqual = Buffer.compare(Buffer.from(last.pixels.buffer, last.pixels.byteOffset, last.pixels.byteLength), Buffer.from(pixels.buffer)) === 0;
+last.release();
+d1.dispose();
+const d3 = [0, 1, 2].map(() => new G.WebGLRenderer({ width: +W, height: +H, throughput: true }, []));
+d3.forEach((x) => x.openDelivery(3));
+delivered(d3, warm);
+const deliver3Ms = delivered(d3, frames);
+d3.forEach((x) => x.dispose());
+
 console.log(JSON.stringify({
     host: "node " + process.version + ", gsplat.js_amd/js (N-API addon over libgsplat_hip.so)",
     scene: path.basename(file), splats: scene.vertexCount, width: +W, height: +H, frames: frames, warmup: warm,
@@ -60,5 +93,8 @@ console.log(JSON.stringify({
     render_sync_with_readPixels: { frames_per_sec: 1000 / readMs, ms_per_frame: readMs, note: "fresh Uint8Array per frame" },
     render_sync_with_readPixels_reused_array: { frames_per_sec: 1000 / readReuseMs, ms_per_frame: readReuseMs },
     render_async_3_renderers: { frames_per_sec: 1000 / asyncMs, ms_per_frame: asyncMs },
+    render_async_deliver: { frames_per_sec: 1000 / deliver1Ms, ms_per_frame: deliver1Ms, slots: 3, delivered_equals_readPixels: deliveredEqual,
+                            note: "one renderer; every frame acquired as a Uint8Array view of its pinned slot, no allocation per frame" },
+    render_async_deliver_3_renderers: { frames_per_sec: 1000 / deliver3Ms, ms_per_frame: deliver3Ms, slots: 3 },
     device: info, sink: sink & 1,
 }));
