@@ -1,0 +1,320 @@
+// The host side of libgsplat_hip.so: the context behind the C ABI (include/gsplat_hip.h), shared by the gsr_*.cpp units.
+// Host only; what the kernels and their launchers see is gsr_internal.h.
+#pragma once
+#include "../../include/gsplat_hip.h"
+#include "gsr_internal.h"
+
+#include <algorithm>
+#include <cstddef>
+#include <string>
+#include <type_traits>
+#include <utility>
+#include <vector>
+
+struct ncclComm;   // RCCL's communicator (ncclComm_t is a pointer to it); only gsr_comm.cpp knows more
+
+// Everything below is internal to the library's host units and hidden: the library exports the C ABI and the launchers only.
+#pragma GCC visibility push(hidden)
+
+namespace gsr {
+
+// records the message in the context (or, without one, for gsr_last_error(NULL)) and returns `code`
+int fail(gsr_ctx* c, int code, const char* fmt, ...);
+
+#define HIP_TRY(c, expr)                                                                         \
+    do {                                                                                         \
+        hipError_t e_ = (expr);                                                                  \
+        if (e_ != hipSuccess) return gsr::fail((c), GSR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+// A device allocation and its one owner: freed when the owner goes, never copied.  Reads as the plain pointer.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); return *this; }
+    ~DevBuf() { reset(); }
+    void reset() { if (p) { (void)hipFree(p); p = nullptr; } }
+    // frees what it holds, then allocates `count` (at least one) elements
+    int alloc(gsr_ctx* c, size_t count)
+    {
+        reset();
+        if (!count) count = 1;
+        HIP_TRY(c, hipMalloc((void**)&p, count * sizeof(T)));
+        return GSR_OK;
+    }
+    operator T*() const { return p; }
+    T* operator->() const { return p; }
+};
+
+enum Stage { EV_BEGIN = 0, EV_PROJECT, EV_SORT, EV_BIN, EV_BLEND /* after k_blend */, EV_COMBINE /* after k_combine */, EV_COUNT };
+
+struct FrameState {  // small per-frame device words; initialised once (k_begin_frame), then every frame STORES them -- only `overflow`
+                     // is accumulated, and zeroed by k_project_key
+    int32_t minmax[2];
+    uint32_t overflow;
+    uint32_t queue;   // compositor work-item counter
+    uint64_t visible;
+    uint64_t tile_entries;
+    uint64_t report[6];  // written by k_bin_finalize for the host: running sums accum[0..4], this frame's bin entries
+    uint32_t digit_total[RADIX_LO_BINS + RADIX_HI_BINS];
+    uint32_t sorted_count;  // entries of depth_index: n, or the band's survivors (SortBuffers::count)
+    uint32_t seg_len;       // the frame's compositor segment length (k_bin_finalize -> k_blend)
+    uint32_t n_items;       // and its number of work items (directly behind seg_len: k_blend reads both through one pointer)
+    uint32_t spec;          // reserved (0)
+};
+
+// The environment's tuning and A/B knobs, read once when a context is created: the context keeps
+// them for its whole life.  A member holds the parsed, clamped value; "unset" is the default written here.
+struct Knobs {
+    bool graphs = true;          // GSR_NO_GRAPH=1: individual launches, no HIP graph
+    bool fuse_combine = true;    // GSR_FUSE_COMBINE=0: separate k_combine launch
+    bool saturate = true;        // GSR_SATURATE=0: composite every entry (no skip of quadrants that can no longer change)
+    int items_by_size = -1;      // GSR_ITEMS_BY_SIZE: 0 / 1; -1: by the kind of context (one frame at a time: heaviest first)
+    int long_items = -1;         // GSR_LONG_ITEMS: 0 / 1 pin the work-item length policy; -1: where the frame's optical depth says so
+    uint32_t long_tau = 0;       // GSR_LONG_TAU: the per-bin optical depth (true mass) from which a bin is one work item (0: the built-in rule)
+    long bin_rounds = 0;         // GSR_BIN_ROUNDS: rounds of 2048 ranks per binning workgroup on large grids (0: by the scene's size)
+    uint32_t bin_big = 2;        // GSR_BIN_BIG: large bin grids: k_bin_scatter_big (0: the 64-register kernel + k_bin_finalize; 1: 2048-rank rounds)
+    int bin_two_level = -1;      // GSR_BIN_TWO_LEVEL: 0 / 1 force the one- / two-level binning; -1: by the bin grid
+    bool rect_carry = true;      // GSR_RECT_CARRY=0: LSD sort order: the binning gathers the packed rectangles instead of the sort carrying them
+    bool rect_carry_bucket = false;   // GSR_RECT_CARRY=2: carried in the bucket order too (measured: what k_bin_count saves, the two sort
+                                      // kernels pay -- C3 sort 35.0 -> 41.8 us, binning 47.6 -> 41.3 us -- so not by default)
+    int blend_sub = 0;           // GSR_BLEND_SUB: 1 / 2 compositor waves per 16x16 tile; 0: by the kind of context and the bin grid
+    int sort_order = -1;         // GSR_SORT_ORDER=lsd|bucket: 0 / 1; -1: chosen per frame from the reported bucket size
+    uint32_t timing_every = 1;   // GSR_TIMING_EVERY: every n-th frame carries the stage events (contexts with GSR_FLAG_TIMING)
+    uint32_t cell_grid = 0;      // GSR_CELL_GRID: workgroups of the level-two binning kernels (0: by the device)
+    uint32_t seg_target = 0;     // GSR_SEG_TARGET: full segments a frame is cut into at least (0: by the kind of context)
+    uint32_t blend_grid = 0;     // GSR_BLEND_GRID: persistent compositor workgroups (0: by the device)
+    uint32_t seg_len = 0;        // GSR_SEG_LEN: entries per compositor work item, a multiple of 256 (0: the built-in length)
+    uint32_t sort_kpb = 0;       // GSR_SORT_KPB: keys per radix workgroup, 2048, 4096 or 8192 (0: by the scene's size)
+};
+
+// The scene's per-splat arrays: everything the on-device build, the transforms and the compaction move together.
+struct SceneArrays {
+    DevBuf<float> px, py, pz;
+    DevBuf<uint32_t> cov0, cov1, cov2, rgba;
+    DevBuf<float4> rot, scl;   // rotations / scales, only for scenes built on the device from .splat rows
+    int alloc(gsr_ctx* c, size_t n, bool with_rows)
+    {
+        int r;
+        if ((r = px.alloc(c, n)) || (r = py.alloc(c, n)) || (r = pz.alloc(c, n)) || (r = cov0.alloc(c, n)) || (r = cov1.alloc(c, n)) ||
+            (r = cov2.alloc(c, n)) || (r = rgba.alloc(c, n)))
+            return r;
+        rot.reset(); scl.reset();
+        if (with_rows && ((r = rot.alloc(c, n)) || (r = scl.alloc(c, n)))) return r;
+        return GSR_OK;
+    }
+    SceneDev view() const { return SceneDev{px, py, pz, cov0, cov1, cov2, rgba, rot, scl}; }
+};
+
+// k_project_key's arguments but the splat count and the camera (ProjectLaunch without what changes from frame to frame)
+struct ProjectArgs {
+    SceneSoA sc;
+    int32_t* depth; int32_t* slots; Record* rec; uint32_t* rect; uint32_t* overflow; uint32_t* kept; uint8_t* kept_lane;
+};
+
+// Everything a frame's launches are handed, except the camera: build_frame_args derives it from the context, enqueue_chain
+// launches from it and from nothing else, and a captured graph is replayed exactly while the next frame's FrameArgs equal,
+// byte for byte, the ones it was captured from.  Trivially copyable; filled by name into zeroed storage and copied with
+// memcpy, so that the comparison never depends on a padding byte.
+struct FrameArgs {
+    ProjectArgs proj;        // render frames
+    int32_t* slots_next;     // sort-only frames: the slot set k_depth_key resets for the next one
+    SortBuffers sort;
+    BinBuffers bin;
+    BinGrid grid;
+    BlendBuffers blend;
+    float early_out_eps;
+    uint32_t n;
+    bool render;             // false: a sort-only frame (depth key + sort)
+    bool sort_culled;        // the sort keeps only the band's survivors (depth_index / keys are partial)
+};
+static_assert(std::is_trivially_copyable<FrameArgs>::value, "FrameArgs is compared and copied as bytes");
+
+}  // namespace gsr
+
+struct gsr_ctx {
+    int device = 0;
+    int cu_count = 256;               // compute units of the device (the compositor's persistent grid is sized from it)
+    hipStream_t stream = nullptr;
+    std::string error;
+    gsr_options opt{};
+    gsr::Knobs knobs;
+    int W = 0, H = 0;
+    int band_x0 = 0, band_x1 = 0;
+    uint32_t n = 0;                   // splats of the scene
+    gsr::CamParams cam{};
+    gsr::CamParams cam_frame{};       // the camera of the last rendered frame
+    bool have_cam = false, have_frame = false, have_sort = false;
+    hipEvent_t link_ev[2] = {nullptr, nullptr};  // gsr_stream_order
+
+    struct Scene {   // gsr_scene.cpp
+        gsr::SceneArrays arr;
+        bool have_rows = false;
+        // spherical harmonics (optional)
+        gsr::DevBuf<uint32_t> sh_r, sh_g, sh_b;
+        gsr::DevBuf<float4> shcol;
+        uint32_t sh_count = 0;
+        int32_t band[3] = {-1, -1, -1};
+        gsr::SceneSoA soa() const { return gsr::SceneSoA{arr.px, arr.py, arr.pz, arr.cov0, arr.cov1, arr.cov2, arr.rgba, sh_r, sh_g, sh_b, shcol}; }
+        void drop_sh() { sh_count = 0; band[0] = band[1] = band[2] = -1; sh_r.reset(); sh_g.reset(); sh_b.reset(); shcol.reset(); }
+    } scene;
+
+    struct Sort {    // per splat and frame: what the projection writes and the sort permutes; sized by alloc_scene
+        gsr::DevBuf<int32_t> depth;
+        gsr::DevBuf<uint32_t> kept;        // band mode: survivors per 256-splat workgroup of k_project_key, packed to the front of its depth slots
+        gsr::DevBuf<uint8_t> kept_lane;    // band mode: the lane a packed slot's splat came from
+        gsr::DevBuf<uint32_t> koff;        // band mode: survivors in front of every workgroup's block (k_kept_scan)
+        gsr::DevBuf<uint32_t> keys, keys_tmp, idx_tmp, depth_index, block_hist;
+        gsr::DevBuf<gsr::Record> rec;
+        gsr::DevBuf<uint32_t> rect_idx;    // per splat: packed bin rectangle (k_project_key); rects holds them in depth order
+        gsr::DevBuf<uint32_t> rects;
+        gsr::DevBuf<uint32_t> rect_tmp;    // the rectangles between the two LSD passes (rect_carry)
+        gsr::DevBuf<uint32_t> chunk_tab;   // bucket order: k_local_sort's work list
+        uint32_t blocks = 0, kpb = 0;
+        int parity = 0;                    // which of the two sort-only slot sets the next sort-only frame uses
+        bool culled = false;               // the last sort kept only the band's survivors (depth_index / keys are partial)
+    } sort;
+
+    struct Bin {     // bin lists and compositor work items; sized by alloc_bins (gsr_frame.cpp)
+        gsr::DevBuf<uint32_t> table, total, start, start_pre, list;
+        gsr::DevBuf<uint32_t> cell_list, cell_total, cell_start, chunk_start, chunk_info, cell_table2, cell_wcnt;
+        gsr::DevBuf<uint32_t> seg_start, items;
+        gsr::DevBuf<unsigned long long> mask;   // per-bin arrival masks of the compositor (null: separate k_combine launch)
+        gsr::DevBuf<float4> partial;
+        uint32_t rounds = 1;               // rounds of 2048 ranks per binning workgroup
+        bool two_level = false;
+        uint32_t cell_capacity_alloc = 0, cell_ncells_alloc = 0, cell_grid = 0;
+        uint32_t blocks = 0, capacity = 0, table_elems = 0, nbins_alloc = 0;
+        uint32_t max_items = 0, seg_len = 0, blend_grid = 2048;
+        uint32_t seg_target_items = 5000;
+        uint32_t blend_sub = 1;            // compositor waves per 16x16 tile: 1 (k_blend) or 2 (k_blend2)
+    } bin;
+
+    struct Words {   // the small device words every frame shares, and what the host knows of them
+        gsr::DevBuf<gsr::FrameState> fstate;
+        gsr::FrameState* fstate_host = nullptr;  // pinned
+        gsr::DevBuf<int32_t> slots;         // 3 x FRAME_SLOTS x 128 B: partial depth (min, max), visible and tile sums of k_project_key
+                                            // (the render frames' set, then the two of the sort-only frames)
+        bool slots_need_init = true;        // frame words and the three slot sets: initialised once, by the first frame's enqueue
+        gsr::DevBuf<gsr::CamParams> cam_dev;  // a camera slot in device memory (written by the one-time initialisation only)
+        gsr::DevBuf<uint64_t> accum;        // [8]: sums over frames (visible, bin entries, tile entries, frames), [4] entries of
+                                            // the last frame, sticky [5] frames that did not fit, [6]/[7] most entries/items one needed
+        uint64_t* mailbox = nullptr;        // pinned host words the device stores into: [0] accum[5] (k_bin_finalize), [1] low half: keys in the
+                                            // largest high-digit bucket of the last sorted frame (k_local_sort / last LSD pass)
+        uint64_t* mailbox_dev = nullptr;    // its device address
+        uint64_t overflow_seen = 0;         // accum[5] as of the last regrowth
+        uint64_t overflow_frames = 0;       // frames that did not fit, since the context was created
+        uint64_t dropped_frames = 0;        // of those, frames never composited (later frames had been enqueued before the host noticed)
+        uint64_t dropped_unreported = 0;    // dropped frames gsr_sync has not reported yet
+    } words;
+
+    struct Out {
+        gsr::DevBuf<float4> fb;
+        gsr::DevBuf<uint32_t> fb8;
+        size_t pixels = 0;
+    } out;
+
+    // the frame's launch chain replayed as a HIP graph (frames that carry no stage events)
+    struct Graph {
+        bool enabled = true;
+        hipGraph_t graph = nullptr;
+        hipGraphExec_t exec = nullptr;
+        hipGraphNode_t project = nullptr;   // the captured chain's projection node: its camera argument is rewritten every replay
+        gsr::FrameArgs key;                 // what `exec` was captured from (valid while exec is set)
+    } graph;
+    gsr::ProjectLaunch proj{};              // the projection kernel's arguments of the current frame
+
+    // timing: a ring of event sets so that frames can be enqueued back to back without a host
+    // sync per frame; gsr_sync / gsr_get_timings drain the ring
+    struct Timing {
+        static constexpr int EV_RING = 128;
+        hipEvent_t evring[EV_RING][gsr::EV_COUNT]{};
+        bool is_render[EV_RING]{};
+        int head = 0, pending = 0;
+        hipEvent_t* ev = nullptr;  // the set being recorded
+        bool valid = false, recorded = false, render = false;
+        uint32_t every = 1, frame_no = 0;
+        gsr_timings tm{};
+    } timing;
+
+    // multi-GPU exchange (gsr_comm_init): RCCL communicator, its stream, the RGBA8 slab / gathered slabs / full frame
+    struct Comm {
+        ncclComm* nccl = nullptr;
+        gsr_allgather_fn fn = nullptr;    // gsr_comm_init_custom: the caller's collective in place of ncclAllGather
+        void* fn_user = nullptr;
+        bool owned = true;                // false: communicator and exchange stream belong to another context (gsr_comm_share)
+        gsr_ctx* leader = nullptr;        // that context; it lists this one in followers and detaches it when it leaves the group first
+        std::vector<gsr_ctx*> followers;
+        int rank = 0, world = 0, slab_w = 0;
+        hipStream_t stream = nullptr;
+        hipEvent_t ev_packed = nullptr, ev_slab_free = nullptr;
+        gsr::DevBuf<uint32_t> slab, gathered, frame8;
+        gsr::SlabEdges edges{};
+        bool frame8_valid = false;
+        bool joined() const { return nccl || fn; }
+    } comm;
+
+    // frame delivery (gsr_delivery_open): a ring of pinned host blocks, each with its device staging and "copy done" event
+    struct Delivery {
+        struct Slot {
+            uint8_t* host = nullptr;        // hipHostMalloc: W * H * 4 pixel bytes + the trailer
+            gsr::DevBuf<uint32_t> staging;  // device, same size: k_deliver_rgba8 writes it, the copy reads it
+            hipEvent_t done = nullptr;      // recorded behind the slot's copy
+            uint64_t serial = 0;
+            enum State { FREE, IN_FLIGHT, HELD } state = FREE;
+        };
+        std::vector<Slot> ring;
+        hipStream_t copy_stream = nullptr;
+        hipEvent_t ev_staged = nullptr;     // render stream -> copy stream: the conversion kernel has written the staging buffer
+        int W = 0, H = 0;
+        int next = 0;                       // where the search for a free slot starts: the slots are used in turn
+        uint64_t serial = 0;                // the last serial handed out; never restarts
+    } delivery;
+};
+
+namespace gsr {
+
+inline BinGrid make_grid(const gsr_ctx* c)
+{
+    BinGrid g;
+    g.W = c->W; g.H = c->H;
+    g.nbx = (c->W + BIN_PX - 1) / BIN_PX;
+    g.nby = (c->H + BIN_PX - 1) / BIN_PX;
+    if (c->band_x1 > c->band_x0) {
+        g.bx_lo = c->band_x0 / BIN_PX;
+        g.bx_hi = std::min((c->band_x1 + BIN_PX - 1) / BIN_PX, g.nbx);
+    } else {
+        g.bx_lo = 0; g.bx_hi = g.nbx;
+    }
+    return g;
+}
+
+// gsr_frame.cpp
+int alloc_bins(gsr_ctx* c);
+int enqueue_frame(gsr_ctx* c, bool render);
+int finish_frame(gsr_ctx* c);
+int sync_and_repair(gsr_ctx* c);
+void drop_graph(gsr_ctx* c);
+// gsr_scene.cpp
+int alloc_scene(gsr_ctx* c, uint32_t n, bool with_rows);
+// gsr_comm.cpp
+void comm_release(gsr_ctx* c);
+// gsr_delivery.cpp
+int delivery_alloc(gsr_ctx* c, int slots);
+void delivery_free(gsr_ctx* c);
+bool delivery_frame_held(const gsr_ctx* c);
+
+// true when the device has counted frames that did not fit (k_bin_finalize, sticky accum[5] mirrored into the
+// host-mapped mailbox) that the host has not sized the buffers for yet: a plain host read, no copy, no sync
+inline bool overflow_pending(const gsr_ctx* c)
+{
+    return c->words.mailbox && *reinterpret_cast<volatile const uint64_t*>(c->words.mailbox) != c->words.overflow_seen;
+}
+
+}  // namespace gsr
+
+#pragma GCC visibility pop

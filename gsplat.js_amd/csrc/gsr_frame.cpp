@@ -1,0 +1,580 @@
+// The frame: what its launches are handed (build_frame_args), the chain itself, its capture and replay as a HIP graph,
+// stage timing, and the repair of frames whose bin lists did not fit.  Also the sizing of everything the binning and the
+// compositor use (alloc_bins), next to the policy constants it is sized by.
+#include "gsr_ctx.h"
+
+#include <algorithm>
+#include <cstring>
+
+using namespace gsr;
+
+namespace {
+
+// Compositor work-item granularity: list entries per (bin, segment) item.  0x7fffff00 = one item per
+// bin, which early termination needs (a segment cannot see whether earlier ones saturated the bin).
+constexpr uint32_t SEG_LEN_MIN = 512;            // shortest segment; k_bin_finalize lengthens it so that the frame is cut
+                                                 // into about SEG_TARGET_* full segments (multiples of 256 entries)
+constexpr uint32_t SEG_TARGET_EXACT = 5000;      // one frame at a time: concurrency from the frame's own segments (C3: 512)
+constexpr uint32_t SEG_TARGET_THROUGHPUT = 1300; // GSR_FLAG_THROUGHPUT: concurrency comes from the other frames in flight
+                                                 // (C3: 2048-entry segments; a 1/8-screen band stays at 512)
+// Persistent compositor workgroups per CU.  k_blend is built for 7 waves per SIMD (72 VGPRs), so 7 four-wave
+// workgroups are resident per CU and the grid must not exceed that: a workgroup that is not resident at launch still
+// owns its first work item by index (a heavy one: the queue is ordered heaviest first) and starts it only when a
+// resident workgroup exits.  With 8 per CU, one item in eight began at 222 us of a 270 us kernel (in-kernel stamps,
+// scripts/blend_stamps.py): k_blend 271 -> 252 us on C3 at 7 per CU.
+constexpr uint32_t BLEND_WG_PER_CU_EXACT = 7;
+// Contexts that overlap with others' kernels (GSR_FLAG_THROUGHPUT): 6 per CU left a wave slot per SIMD to the other
+// contexts and was best while the fold of the partials was a kernel of its own; with the fold inside k_blend 7 is
+// (bench.py, three frames in flight, C3: 3324 -> 3400 frames/s, reproducible; C2 -0.8 %, C4 and early-out unchanged).
+constexpr uint32_t BLEND_WG_PER_CU_THROUGHPUT = 7;
+// Two waves per tile (k_blend2, 512-thread workgroups): three workgroups per CU are resident (6 waves per SIMD).
+constexpr uint32_t BLEND_WG_PER_CU_SUB2 = 3;
+constexpr uint32_t SUB2_MAX_BINS = 4096, SEG_LEN_MIN_SUB2 = 1024;
+constexpr uint32_t BIN_BLOCKS_TARGET = 640, BIN_ROUNDS_MAX = 8;
+constexpr uint32_t TWO_LEVEL_MIN_BINS = 4096, CELL_WG_PER_CU = 4;
+constexpr uint32_t SEG_LEN_WHOLE_BIN = 0x7fffff00u;
+
+// Sort order.  Up to BUCKET_ORDER_MAX_N splats the radix sort runs high digit first with one workgroup per bucket
+// (four launches, k_sort.hip) -- unless the last sorted frame reported a bucket above LOCAL_BUCKET_LIMIT keys: depth
+// outliers stretch the key range and can put most of a scene into one bucket, which would serialise in its workgroup.
+// Then, for the first frame of a scene, and above BUCKET_ORDER_MAX_N (the average bucket alone needs several chunks)
+// it runs the LSD order (six launches).  Same permutation either way.  GSR_SORT_ORDER=lsd|bucket pins it.
+constexpr uint32_t BUCKET_ORDER_MAX_N = 3u << 20;
+constexpr uint32_t LOCAL_BUCKET_LIMIT = 48u << 10;
+
+// Work-item length.  With the saturation skip of k_blend a work item ends as soon as nothing it could still add can change
+// a bit of its pixels, and that needs the item to contain the splats that saturate it: a bin cut into 512-entry segments
+// never saturates inside one of them (every segment starts from transmittance 1), a bin processed as one item stops
+// after the few thousand entries that matter (C3: 3430 -> 4990 frames/s with three frames in flight, 2670 -> 2945 one at
+// a time; C4: 292 -> 856).  Where the scene does not saturate (C2: small splats, 9 % of the entries skipped against 53 %
+// on C3 and 85 % on C4; or any thin, low-opacity scene) long items only cost balance (C2: 6670 -> 2780 frames/s).
+// k_bin_finalize decides per frame, from a figure the projection already has: the frame's optical depth
+//     tau = sum over visible splats of opacity x (16x16 tiles its box overlaps) x 256 / pixels
+// (C1 14, C2 74, C3 362, C4 1090): items are at least SEG_LEN_LONG entries (in practice whole bins) from LONG_TAU_* on.
+// A function of the frame alone: no feedback from earlier frames, the same frame always takes the same path.
+// Where long items start to pay (scripts/tau_crossover.py: the C3 and C2 generators at 0.25 .. 1.6 M splats, 1080p): with
+// other frames' kernels filling the gaps, between tau 90 and 145 for both generators (tau 90: 10 390 -> 10 080 frames/s,
+// tau 145: 7350 -> 8640, tau 250: 4730 -> 6800); one frame at a time the few long items are the frame's tail and the
+// crossover depends on the scene (C3 generator: tau ~ 255, C3 itself +23 %; the C2 generator's small splats still lose
+// 8 % at tau 390), so the threshold there stays high.
+constexpr uint32_t SEG_LEN_LONG = 32768;   // (16384: C4 k_blend 437 instead of 405 us -- its heaviest bins hold 50-100 k entries; 65536 measures the same)
+constexpr uint32_t LONG_TAU_EXACT = 340, LONG_TAU_THROUGHPUT = 120;
+// a frame that is not dense as a whole: bins far past saturation become one item only where a list entry carries at least this
+// optical mass (pixels): C3 14, C2 8, 2 M tiny splats 1.9 -- one frame at a time a 3000-entry serial walk is the frame's tail
+constexpr uint32_t LONG_MASS_MIN_EXACT = 12, LONG_MASS_MIN_THROUGHPUT = 0;
+constexpr uint32_t LONG_TILES_X2_EXACT = 9;   // one frame at a time: and at least 4.5 tiles per visible splat (k_bin_finalize)
+constexpr uint32_t LONG_TILES_X2_THROUGHPUT = 6;   // with frames in flight: 3 (scripts/policy_check.py: 2 M tiny splats, 1.9 tiles each, tau 264:
+                                                   // long items -26 %; the C2 generator, 3.6 tiles each: +10 % at the same tau)
+
+inline bool use_bucket_order(const gsr_ctx* c)
+{
+    if (c->knobs.sort_order >= 0) return c->knobs.sort_order == 1;
+    if (c->n > BUCKET_ORDER_MAX_N) return false;
+    const uint32_t largest = reinterpret_cast<volatile const uint32_t*>(c->words.mailbox)[2];   // low half of mailbox[1]
+    return largest <= LOCAL_BUCKET_LIMIT;   // 0xffffffff until a frame of this scene has reported
+}
+
+bool band_is_partial(const BinGrid& g) { return g.bx_lo > 0 || g.bx_hi < g.nbx; }
+
+// What a frame's launches are handed, from the context as it stands: every buffer, size and policy value, by name.
+void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
+{
+    memset(&a, 0, sizeof a);
+    const BinGrid g = make_grid(c);
+    const bool throughput = (c->opt.flags & GSR_FLAG_THROUGHPUT) != 0;
+    const bool bucket_order = use_bucket_order(c);
+    // band mode (a context that composites only part of the screen): the projection's workgroups pack their survivors (see
+    // k_project_key) and only those are sorted and binned; the full depthIndex is produced on demand (gsr_read_depth_index)
+    const bool cull = render && band_is_partial(g);
+    FrameState* fs = c->words.fstate;
+    a.render = render;
+    a.n = c->n;
+    a.grid = g;
+    a.early_out_eps = c->opt.early_out_eps;
+    a.sort_culled = cull && c->n;   // (an empty frame sorts nothing, so nothing of it is partial)
+
+    // a sort-only frame has its own slots (sets 1 and 2 in turn; set 0 belongs to the render frames and k_begin_frame)
+    const size_t slot_set = (size_t)FRAME_SLOTS * FRAME_SLOT_WORDS;
+    int32_t* slots_now = render ? c->words.slots.p : c->words.slots + (size_t)(1 + c->sort.parity) * slot_set;
+    a.slots_next = render ? nullptr : c->words.slots + (size_t)(2 - c->sort.parity) * slot_set;
+
+    a.proj.sc = c->scene.soa();
+    a.proj.depth = c->sort.depth;
+    a.proj.slots = slots_now;
+    if (render) {
+        a.proj.rec = c->sort.rec;
+        a.proj.rect = c->sort.rect_idx;
+        a.proj.overflow = &fs->overflow;
+        a.proj.kept = cull ? c->sort.kept.p : nullptr;
+        a.proj.kept_lane = cull ? c->sort.kept_lane.p : nullptr;
+    }
+
+    SortBuffers& sb = a.sort;
+    sb.depth = c->sort.depth;
+    sb.slots = slots_now;
+    sb.minmax = fs->minmax;
+    sb.keys = c->sort.keys;
+    sb.keys_tmp = c->sort.keys_tmp;
+    sb.idx_tmp = c->sort.idx_tmp;
+    sb.depth_index = c->sort.depth_index;
+    sb.block_hist = c->sort.block_hist;
+    sb.digit_total = fs->digit_total;
+    sb.rect = c->sort.rect_idx;
+    sb.kept = c->sort.kept;
+    sb.kept_lane = c->sort.kept_lane;
+    sb.koff = cull ? c->sort.koff.p : nullptr;
+    sb.count = &fs->sorted_count;
+    sb.keys_per_block = c->sort.kpb;
+    sb.nblocks = c->sort.blocks;
+    sb.bucket_order = bucket_order ? 1 : 0;
+    sb.max_bucket = reinterpret_cast<uint32_t*>(c->words.mailbox_dev + 1);
+    sb.chunk_tab = c->sort.chunk_tab;
+    sb.rect_tmp = c->sort.rect_tmp;
+    sb.rects_out = (render && c->knobs.rect_carry && (c->knobs.rect_carry_bucket || !bucket_order)) ? c->sort.rects.p : nullptr;
+    if (!render) return;
+
+    const uint32_t queue_start = std::min<uint32_t>(c->bin.max_items, c->bin.blend_grid);
+    BinBuffers& bb = a.bin;
+    bb.depth_index = c->sort.depth_index;
+    bb.count = &fs->sorted_count;
+    bb.table = c->bin.table;
+    bb.slots = c->words.slots;
+    bb.rect_idx = c->sort.rect_idx;
+    bb.rects = c->sort.rects;
+    bb.rects_sorted = (c->n && sb.rects_out) ? 1u : 0u;
+    bb.bin_total = c->bin.total;
+    bb.bin_start = c->bin.start;
+    bb.bin_start_pre = c->bin.start_pre;
+    bb.rounds = c->bin.rounds;
+    bb.big = c->knobs.bin_big;
+    bb.seg_start = c->bin.seg_start;
+    bb.items = c->bin.items;
+    bb.list = c->bin.list;
+    bb.overflow = &fs->overflow;
+    bb.visible = &fs->visible;
+    bb.tile_entries = &fs->tile_entries;
+    bb.accum = c->words.accum;
+    bb.mailbox = c->words.mailbox_dev;
+    bb.report = fs->report;
+    bb.capacity = c->bin.capacity;
+    bb.max_items = c->bin.max_items;
+    bb.seg_len = c->bin.seg_len;
+    bb.seg_len_dev = &fs->seg_len;
+    // work items heaviest first (one frame at a time) or in raster order
+    bb.items_by_size = c->knobs.items_by_size >= 0 ? c->knobs.items_by_size : throughput ? 0 : 1;
+    bb.queue = &fs->queue;
+    bb.queue_start = queue_start;
+    bb.seg_target_items = c->bin.seg_target_items;
+    bb.nblocks = c->bin.blocks;
+    bb.bin_mask = c->bin.mask;
+    bb.long_policy = c->bin.seg_len == SEG_LEN_WHOLE_BIN ? 0 : c->knobs.long_items >= 0 ? c->knobs.long_items : c->knobs.saturate ? -1 : 0;
+    bb.seg_len_long = SEG_LEN_LONG;
+    bb.long_tau = throughput ? LONG_TAU_THROUGHPUT : LONG_TAU_EXACT;
+    bb.npix = (uint32_t)((g.bx_hi - g.bx_lo) * BIN_PX) * (uint32_t)c->H;
+    bb.long_tiles_x2 = throughput ? LONG_TILES_X2_THROUGHPUT : LONG_TILES_X2_EXACT;
+    bb.long_tau_bin = c->knobs.long_tau;
+    bb.long_mass_min = throughput ? LONG_MASS_MIN_THROUGHPUT : LONG_MASS_MIN_EXACT;
+    bb.two_level = c->bin.two_level ? 1u : 0u;
+    bb.cell_list = c->bin.cell_list;
+    bb.cell_total = c->bin.cell_total;
+    bb.cell_start = c->bin.cell_start;
+    bb.chunk_start = c->bin.chunk_start;
+    bb.chunk_info = c->bin.chunk_info;
+    bb.cell_wcnt = c->bin.cell_wcnt;
+    bb.cell_table2 = c->bin.cell_table2;
+    bb.cell_grid = c->bin.cell_grid;
+    bb.band = band_is_partial(g) ? 1u : 0u;
+    bb.n_max = c->n;
+
+    BlendBuffers& bl = a.blend;
+    bl.items = c->bin.items;
+    bl.seg_start = c->bin.seg_start;
+    bl.bin_start = c->bin.start;
+    bl.list = c->bin.list;
+    bl.rec = c->sort.rec;
+    bl.bbox = nullptr;   // (nothing on the frame path reads the pixel boxes)
+    bl.shcol = c->scene.shcol;
+    bl.fb = c->out.fb;
+    bl.partial = c->bin.partial;
+    bl.queue = &fs->queue;
+    bl.seg_len = c->bin.seg_len;
+    bl.seg_len_dev = &fs->seg_len;
+    bl.grid = queue_start;
+    bl.capacity = c->bin.capacity;
+    bl.nsplats = std::max(c->n, 1u);
+    bl.bin_mask = c->bin.mask;
+    bl.saturate = c->knobs.saturate ? 1u : 0u;
+    bl.sub = c->bin.blend_sub;
+}
+
+// the projection's launch of this frame: its arguments from `a`, the context's current camera
+void set_projection(gsr_ctx* c, const FrameArgs& a)
+{
+    ProjectLaunch& p = c->proj;
+    p.sc = a.proj.sc;
+    p.n = a.n;
+    p.cam = c->cam;
+    p.do_project = 1;
+    p.depth = a.proj.depth;
+    p.slots = a.proj.slots;
+    p.rec = a.proj.rec;
+    p.bbox = nullptr;
+    p.rect = a.proj.rect;
+    p.overflow = a.proj.overflow;
+    p.kept = a.proj.kept;
+    p.kept_lane = a.proj.kept_lane;
+    p.bind();
+}
+
+// the frame's device work on the context's stream: projection + depth key, sort, (bin, blend).  Launches from `a` (and, for
+// a render frame, c->proj, which set_projection filled from it) and records the stage events; changes nothing in the context.
+int enqueue_chain(gsr_ctx* c, const FrameArgs& a, bool timing)
+{
+    hipStream_t s = c->stream;
+    hipEvent_t* ev = c->timing.ev;
+    if (timing) HIP_TRY(c, hipEventRecord(ev[EV_BEGIN], s));
+    if (a.n) {
+        if (a.render) launch_project_key(c->proj, s);
+        else launch_depth_key(a.proj.sc, a.n, c->cam, a.proj.depth, a.proj.slots, a.slots_next, s);
+    }
+    if (timing) HIP_TRY(c, hipEventRecord(ev[EV_PROJECT], s));
+    launch_sort(a.sort, a.n, s);
+    if (timing) HIP_TRY(c, hipEventRecord(ev[EV_SORT], s));
+    if (a.render) {
+        if (!a.n) {
+            const int nbins = (a.grid.bx_hi - a.grid.bx_lo) * a.grid.nby;
+            HIP_TRY(c, hipMemsetAsync(a.bin.bin_total, 0, sizeof(uint32_t) * nbins, s));
+            HIP_TRY(c, hipMemsetAsync(a.bin.overflow, 0, sizeof(uint32_t), s));   // (k_project_key zeroes it otherwise)
+        }
+        launch_bin(a.bin, a.grid, a.n, s);
+        if (timing) HIP_TRY(c, hipEventRecord(ev[EV_BIN], s));
+        launch_blend(a.blend, a.grid, a.early_out_eps, s, (timing && !a.blend.bin_mask) ? ev[EV_BLEND] : nullptr);
+        if (timing) HIP_TRY(c, hipEventRecord(ev[EV_COMBINE], s));
+    }
+    HIP_TRY(c, hipGetLastError());
+    return GSR_OK;
+}
+
+// captures the chain of `a` into c->graph; false: this runtime cannot (the caller falls back to individual launches)
+bool capture_graph(gsr_ctx* c, const FrameArgs& a)
+{
+    hipStream_t s = c->stream;
+    if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) != hipSuccess) return false;
+    const int r = enqueue_chain(c, a, false);
+    hipGraph_t gph = nullptr;
+    bool ok = (hipStreamEndCapture(s, &gph) == hipSuccess) && r == GSR_OK && gph;
+    hipGraphNode_t project = nullptr;
+    if (ok && a.n) {   // the node whose camera argument changes from frame to frame
+        size_t nn = 0;
+        ok = hipGraphGetNodes(gph, nullptr, &nn) == hipSuccess && nn > 0;
+        std::vector<hipGraphNode_t> nodes(nn);
+        if (ok) ok = hipGraphGetNodes(gph, nodes.data(), &nn) == hipSuccess;
+        for (size_t k = 0; ok && k < nn && !project; k++) {
+            hipGraphNodeType ty;
+            hipKernelNodeParams kp{};
+            if (hipGraphNodeGetType(nodes[k], &ty) == hipSuccess && ty == hipGraphNodeTypeKernel &&
+                hipGraphKernelNodeGetParams(nodes[k], &kp) == hipSuccess && kp.func == project_key_kernel())
+                project = nodes[k];
+        }
+        ok = ok && project != nullptr;
+    }
+    if (ok) ok = hipGraphInstantiate(&c->graph.exec, gph, nullptr, nullptr, 0) == hipSuccess;
+    if (ok) { c->graph.graph = gph; c->graph.project = project; memcpy(&c->graph.key, &a, sizeof a); }
+    else if (gph) (void)hipGraphDestroy(gph);
+    return ok;
+}
+
+// the captured graph with this frame's camera in its projection node; false: this runtime cannot rewrite the node
+bool set_graph_camera(gsr_ctx* c)
+{
+    hipKernelNodeParams kp{};
+    kp.func = const_cast<void*>(project_key_kernel());
+    kp.gridDim = project_key_grid(c->proj.n);
+    kp.blockDim = dim3(PROJ_THREADS);
+    kp.sharedMemBytes = 0;
+    kp.kernelParams = c->proj.ptrs;
+    kp.extra = nullptr;
+    return hipGraphExecKernelNodeSetParams(c->graph.exec, c->graph.project, &kp) == hipSuccess;
+}
+
+// after a synchronised render: pull the frame words of the last frame (counts for gsr_timings, its overflow word)
+int check_frame_words(gsr_ctx* c, bool* overflowed)
+{
+    // one small copy: the frame words up to and including k_bin_finalize's report
+    FrameState* host = c->words.fstate_host;
+    HIP_TRY(c, hipMemcpyAsync(host, c->words.fstate, offsetof(FrameState, digit_total), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const uint64_t* acc = host->report;
+    gsr_timings& tm = c->timing.tm;
+    tm.sum_visible = acc[0]; tm.sum_bin_entries = acc[1]; tm.sum_tile_entries = acc[2]; tm.sum_frames = acc[3];
+    tm.visible = host->visible;
+    tm.tile_entries = host->tile_entries;
+    tm.bin_entries = (uint32_t)host->report[5];
+    tm.n = c->n;
+    *overflowed = host->overflow != 0;
+    return GSR_OK;
+}
+
+// Frames did not fit since the host last looked: wait for the stream, regrow the list for the largest of them and
+// count them (*newly).  Those frames were not composited: a frame whose lists do not fit publishes no work items, so
+// the framebuffer kept the image before it.  The caller decides whether one of them can still be rendered again.
+int handle_overflow(gsr_ctx* c, uint64_t* newly)
+{
+    *newly = 0;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    uint64_t acc[8];
+    HIP_TRY(c, hipMemcpyAsync(acc, c->words.accum, sizeof acc, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (acc[5] == c->words.overflow_seen) return GSR_OK;
+    *newly = acc[5] - c->words.overflow_seen;
+    c->words.overflow_seen = acc[5];
+    c->words.overflow_frames += *newly;
+    const uint64_t need = acc[6];
+    const uint64_t want = need + (need >> 2) + (1u << 20);
+    if (want > 0xfffffff0ull) return fail(c, GSR_ERR_OVERFLOW, "bin list would need %llu entries", (unsigned long long)want);
+    if (want > c->bin.capacity) {
+        c->bin.capacity = (uint32_t)want;
+        if (int r = c->bin.list.alloc(c, c->bin.capacity)) return r;
+    }
+    c->bin.max_items = 0;
+    return alloc_bins(c);
+}
+
+}  // namespace
+
+namespace gsr {
+
+int alloc_bins(gsr_ctx* c)
+{
+    if (!c->W) return GSR_OK;
+    gsr_ctx::Bin& b = c->bin;
+    const Knobs& k = c->knobs;
+    const BinGrid g = make_grid(c);
+    const uint32_t nbins = (uint32_t)((g.bx_hi - g.bx_lo) * g.nby);
+    // Ranks per binning workgroup: rounds of 2048.  The count / scan / scatter passes exchange a [workgroup][bin] table; with
+    // one round per workgroup it is 80 MB at 5 M splats and 8160 bins.  Large grids (the k_bin_scatter_big form, > 4096 bins)
+    // take several rounds per workgroup, keeping about BIN_BLOCKS_TARGET workgroups (C4: 4 rounds, 611 workgroups, 20 MB).
+    // Two-level binning (k_bin.hip): grids above TWO_LEVEL_MIN_BINS bins whose cells of 4 x 4 bins number at most 4096.
+    const uint32_t ncells = (uint32_t)(((g.bx_hi - g.bx_lo + 3) >> 2) * ((g.nby + 3) >> 2));
+    // (its level-two stores address the list with 32-bit byte offsets: lists of 2^30 entries or more take the one-level pass)
+    const uint64_t cap_now = b.capacity ? b.capacity : std::max<uint64_t>(6ull * c->n + (1u << 20), 1u << 22);
+    b.two_level = ncells <= 4096u && cap_now < (1ull << 30) &&
+                  (k.bin_two_level >= 0 ? k.bin_two_level == 1 : nbins > TWO_LEVEL_MIN_BINS);
+    b.rounds = 1;
+    if (!b.two_level && k.bin_big && nbins > 4096)
+        b.rounds = std::min<uint32_t>(BIN_ROUNDS_MAX, std::max<uint32_t>(1u, ((c->n + 2047u) / 2048u + BIN_BLOCKS_TARGET - 1u) / BIN_BLOCKS_TARGET));
+    if (!b.two_level && k.bin_big && nbins > 4096 && k.bin_rounds > 0) b.rounds = (uint32_t)k.bin_rounds;
+    b.blocks = (c->n + 2048u * b.rounds - 1u) / (2048u * b.rounds);
+    const size_t table = (size_t)std::max(b.blocks, 1u) * (b.two_level ? ncells + 1u : nbins);
+    if (table > b.table_elems) {
+        if (int r = b.table.alloc(c, table)) return r;
+        b.table_elems = (uint32_t)table;
+    }
+    bool items_dirty = false;
+    if (nbins > b.nbins_alloc) {
+        if (int r = b.total.alloc(c, nbins)) return r;
+        if (int r = b.start.alloc(c, nbins + 1)) return r;
+        if (int r = b.start_pre.alloc(c, nbins + 1)) return r;
+        if (int r = b.seg_start.alloc(c, nbins + 1)) return r;
+        if (k.fuse_combine) {
+            if (int r = b.mask.alloc(c, nbins)) return r;
+        }
+        b.nbins_alloc = nbins;
+        items_dirty = true;
+    }
+    if (!b.capacity) {
+        b.capacity = std::max<uint32_t>(6u * c->n + (1u << 20), 1u << 22);
+        if (int r = b.list.alloc(c, b.capacity)) return r;
+        items_dirty = true;
+    }
+    if (b.two_level) {
+        if (ncells > b.cell_ncells_alloc) {
+            if (int r = b.cell_total.alloc(c, ncells + 1)) return r;
+            if (int r = b.cell_start.alloc(c, ncells + 1)) return r;
+            if (int r = b.chunk_start.alloc(c, ncells + 2)) return r;
+            b.cell_ncells_alloc = ncells;
+            b.cell_capacity_alloc = 0;
+        }
+        if (b.capacity > b.cell_capacity_alloc) {
+            const size_t chunks = (size_t)b.capacity / 2048u + ncells + 1u;
+            if (int r = b.cell_list.alloc(c, (size_t)b.capacity * 2)) return r;
+            if (int r = b.cell_table2.alloc(c, chunks * 16u)) return r;
+            if (int r = b.chunk_info.alloc(c, chunks * 4u)) return r;
+            if (int r = b.cell_wcnt.alloc(c, chunks * 64u)) return r;
+            b.cell_capacity_alloc = b.capacity;
+        }
+        // the level-two kernels stride over the frame's chunks: two 16-wave workgroups per CU, twice over
+        b.cell_grid = k.cell_grid ? k.cell_grid : (uint32_t)std::max(c->cu_count, 1) * CELL_WG_PER_CU;
+    }
+    const bool throughput = (c->opt.flags & GSR_FLAG_THROUGHPUT) != 0;
+    b.seg_len = c->opt.early_out_eps > 0.0f ? SEG_LEN_WHOLE_BIN : SEG_LEN_MIN;
+    b.seg_target_items = k.seg_target ? k.seg_target : throughput ? SEG_TARGET_THROUGHPUT : SEG_TARGET_EXACT;
+    // Waves per tile.  Two (k_blend2) halve a wave's serial walk over a work item -- the pole of a frame rendered alone, where a
+    // wave needs ~560 cycles per entry visit whatever else the chip does -- and pay with occupancy (24 instead of 28 waves
+    // per CU) and saturation tests at chunk instead of 64-entry boundaries.  Measured one frame at a time: C3 k_blend 194 ->
+    // 147 us, C1 20 -> 15; C2 (short segments) 77 -> 86, with 1024-entry segments 80; C4, whose 8160 bins keep every slot
+    // busy: 412 -> 509; three frames in flight, C3: 5280 -> 4410 frames/s.  So: contexts that render one frame at a time, up
+    // to SUB2_MAX_BINS bins, with segments of at least 1024 entries.  (Leaving the choice to k_bin_finalize per frame --
+    // both kernels launched, the other one returning at once -- cost 4.5 us per frame for the idle launch.)
+    b.blend_sub = k.blend_sub ? (uint32_t)k.blend_sub : (!throughput && nbins <= SUB2_MAX_BINS) ? 2u : 1u;
+    if (b.blend_sub >= 2 && b.seg_len != SEG_LEN_WHOLE_BIN) b.seg_len = SEG_LEN_MIN_SUB2;
+    b.blend_grid = (b.blend_sub >= 2 ? BLEND_WG_PER_CU_SUB2 : throughput ? BLEND_WG_PER_CU_THROUGHPUT : BLEND_WG_PER_CU_EXACT) * (uint32_t)std::max(c->cu_count, 1);
+    if (k.blend_grid) b.blend_grid = k.blend_grid;
+    if (k.seg_len && b.seg_len != SEG_LEN_WHOLE_BIN) b.seg_len = k.seg_len;
+    // segments = work items (each may need a partial slot): one per bin plus one per seg_len entries
+    const uint32_t want_items = nbins + b.capacity / b.seg_len + 16;
+    if (items_dirty || want_items > b.max_items) {
+        b.max_items = want_items;
+        if (int r = b.items.alloc(c, (size_t)b.max_items * 4)) return r;   // (four words per work item: k_bin_finalize)
+        if (b.seg_len != SEG_LEN_WHOLE_BIN) {
+            if (int r = b.partial.alloc(c, (size_t)want_items * BIN_PX * BIN_PX)) return r;
+        }
+    }
+    return GSR_OK;
+}
+
+void drop_graph(gsr_ctx* c)
+{
+    if (c->graph.exec) (void)hipGraphExecDestroy(c->graph.exec);
+    if (c->graph.graph) (void)hipGraphDestroy(c->graph.graph);
+    c->graph.exec = nullptr; c->graph.graph = nullptr; c->graph.project = nullptr;
+}
+
+// enqueue one frame: the chain as individual launches when the frame carries stage events or is sort-only, as one graph
+// launch otherwise (13 launches and a copy become one: the host issues a frame in ~12 us instead of ~45 us, which is
+// what a rank of a multi-GPU run or a small scene is bound by)
+int enqueue_frame(gsr_ctx* c, bool render)
+{
+    if (!c->have_cam) return fail(c, GSR_ERR_ARG, "gsr_set_camera has not been called");
+    if (render && (!c->W || !c->H)) return fail(c, GSR_ERR_ARG, "framebuffer size is 0");
+    hipStream_t s = c->stream;
+    if (render && overflow_pending(c)) {
+        // an earlier asynchronous frame did not fit: regrow before this one is enqueued.  The frames that overflowed
+        // are lost (later frames were already behind them); gsr_sync reports how many.
+        uint64_t newly = 0;
+        if (int r = handle_overflow(c, &newly)) return r;
+        c->words.dropped_frames += newly;
+        c->words.dropped_unreported += newly;
+    }
+    // stage timing is sampled: every timing.every-th frame carries the six events (each is a packet the command
+    // processor has to retire; on short frames they cost more than they measure)
+    gsr_ctx::Timing& t = c->timing;
+    const bool timing = t.valid && t.every != 0xffffffffu && (t.frame_no++ % t.every) == 0;   // (0xffffffff: no frame)
+    if (timing) {
+        if (t.pending == gsr_ctx::Timing::EV_RING) { if (int r = finish_frame(c)) return r; }
+        const int slot = (t.head + t.pending) % gsr_ctx::Timing::EV_RING;
+        t.ev = t.evring[slot];
+        t.is_render[slot] = render;
+    }
+    FrameArgs a;
+    build_frame_args(c, render, a);
+    c->cam.W = c->W; c->cam.H = c->H;
+    c->cam.band_px0 = a.grid.bx_lo * BIN_PX;
+    c->cam.band_px1 = a.grid.bx_hi * BIN_PX;
+    c->cam.sh_on = c->scene.sh_count ? 1 : 0;
+    c->cam.band[0] = c->scene.band[0]; c->cam.band[1] = c->scene.band[1]; c->cam.band[2] = c->scene.band[2];
+    if (render) c->cam_frame = c->cam;   // (gsr_read_records projects once more for this camera to get the pixel boxes)
+    // No kernel in front of the frame: the camera is an argument of the projection kernel (k_project_key; k_depth_key in a
+    // sort-only frame), the frame slots are left clean by their last reader, the frame words are stored, not accumulated
+    // (the overflow word is zeroed by k_project_key).  The context's first frame initialises all of them, once.
+    static_assert(offsetof(FrameState, minmax) == 0 && sizeof(FrameState) % 4 == 0, "k_begin_frame initialises the frame words");
+    if (c->words.slots_need_init) {
+        for (int k = 0; k < 3; k++)   // the render frames' slot set and the two of the sort-only frames
+            launch_begin_frame(c->cam, c->words.cam_dev, reinterpret_cast<uint32_t*>(c->words.fstate.p), (uint32_t)(sizeof(FrameState) / 4),
+                               c->words.slots + (size_t)k * FRAME_SLOTS * FRAME_SLOT_WORDS, s);
+        c->words.slots_need_init = false;
+    }
+    if (render) set_projection(c, a);
+
+    bool replayed = false;
+    if (c->graph.enabled && render && !timing) {
+        // the graph is replayed while the frame's launches are, byte for byte, the ones it was captured from
+        bool ok = true;
+        if (!c->graph.exec || memcmp(&a, &c->graph.key, sizeof a) != 0) {
+            drop_graph(c);
+            ok = capture_graph(c, a);   // (holds this frame's camera already)
+        }
+        else if (c->graph.project) ok = set_graph_camera(c);
+        if (!ok) {   // this runtime cannot capture the chain or rewrite the node: individual launches from now on
+            (void)hipGetLastError();
+            drop_graph(c);
+            c->graph.enabled = false;
+        }
+        if (c->graph.exec) {
+            HIP_TRY(c, hipGraphLaunch(c->graph.exec, s));   // (a failure marks the frame slots for re-initialisation: fail())
+            replayed = true;
+        }
+    }
+    if (!replayed) { if (int r = enqueue_chain(c, a, timing)) return r; }
+    // what the context remembers of the frame, whichever way it was issued
+    // (the parity names the slot set the last k_depth_key reset for its successor: it moves only when that kernel ran, which it
+    // does not for an empty scene -- nothing else ever cleans the sort-only frames' two sets)
+    if (!render && a.n) c->sort.parity ^= 1;
+    c->sort.culled = a.sort_culled;
+    if (timing) t.pending++;
+    t.recorded = timing;
+    t.render = render;
+    c->have_sort = true;
+    c->have_frame = c->have_frame || render;
+    return GSR_OK;
+}
+
+int finish_frame(gsr_ctx* c)
+{
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    gsr_ctx::Timing& t = c->timing;
+    while (t.pending > 0) {
+        hipEvent_t* ev = t.evring[t.head];
+        const bool render = t.is_render[t.head];
+        float a = 0, b = 0, d = 0, e = 0, f = 0, tot = 0;
+        HIP_TRY(c, hipEventElapsedTime(&a, ev[EV_BEGIN], ev[EV_PROJECT]));
+        HIP_TRY(c, hipEventElapsedTime(&b, ev[EV_PROJECT], ev[EV_SORT]));
+        tot = a + b;
+        if (render) {
+            HIP_TRY(c, hipEventElapsedTime(&d, ev[EV_SORT], ev[EV_BIN]));
+            if (c->bin.mask) {   // the fold of multi-segment bins runs inside k_blend: one stage, no event in between
+                HIP_TRY(c, hipEventElapsedTime(&e, ev[EV_BIN], ev[EV_COMBINE]));
+            } else {
+                HIP_TRY(c, hipEventElapsedTime(&e, ev[EV_BIN], ev[EV_BLEND]));
+                HIP_TRY(c, hipEventElapsedTime(&f, ev[EV_BLEND], ev[EV_COMBINE]));
+            }
+            HIP_TRY(c, hipEventElapsedTime(&tot, ev[EV_BEGIN], ev[EV_COMBINE]));
+        }
+        t.tm.ms_project_key = a; t.tm.ms_sort = b; t.tm.ms_bin = d; t.tm.ms_blend = e; t.tm.ms_combine = f; t.tm.ms_total = tot;
+        t.tm.sum_ms_project_key += a; t.tm.sum_ms_sort += b; t.tm.sum_ms_bin += d; t.tm.sum_ms_blend += e; t.tm.sum_ms_combine += f;
+        t.tm.sum_ms_total += tot;
+        t.tm.frames++;
+        t.head = (t.head + 1) % gsr_ctx::Timing::EV_RING;
+        t.pending--;
+    }
+    t.recorded = false;
+    return GSR_OK;
+}
+
+// wait for the context's stream; if frames overflowed, regrow and render the last frame again (when it was one of
+// them); lost frames are added to dropped_unreported, which gsr_sync turns into one GSR_ERR_OVERFLOW
+int sync_and_repair(gsr_ctx* c)
+{
+    if (int r = finish_frame(c)) return r;
+    bool last_ov = false;
+    if (c->have_frame && c->timing.render) {
+        if (int r = check_frame_words(c, &last_ov)) return r;
+    }
+    if (overflow_pending(c)) {
+        uint64_t newly = 0;
+        if (int r = handle_overflow(c, &newly)) return r;   // buffers regrown for the largest frame seen
+        if (last_ov && newly) {  // the last frame is one of them and nothing has been enqueued behind it: render it again
+            if (int r = enqueue_frame(c, true)) return r;
+            if (int r = finish_frame(c)) return r;
+            bool again = false;
+            if (int r = check_frame_words(c, &again)) return r;
+            if (again) return fail(c, GSR_ERR_OVERFLOW, "bin list overflow after regrowth");
+            newly -= 1;
+        }
+        c->words.dropped_frames += newly;
+        c->words.dropped_unreported += newly;
+    }
+    return GSR_OK;
+}
+
+}  // namespace gsr

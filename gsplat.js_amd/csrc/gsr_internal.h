@@ -48,8 +48,8 @@ constexpr uint32_t BBOX_INVISIBLE_Y = 1u;
 
 // Bin rectangle of a splat's pixel box inside a context's band of bin columns [bx_lo, bx_hi), packed in 4 bytes:
 // x0 | x1 << 8 | y0 << 16 | y1 << 24 (inclusive bin coordinates, x relative to the band; at most 256 bins per axis);
-// 1 = nothing to draw.  Written once per splat by k_project_key; k_bin_count gathers them into depth order (4-byte
-// gathers; carrying them through the last radix pass instead moved the same cost into that kernel: measured, dropped).
+// 1 = nothing to draw.  Written once per splat by k_project_key.  In the LSD sort order they travel through the radix passes
+// with the keys (SortBuffers::rects_out); in the bucket order k_bin_count gathers them into depth order (4-byte gathers).
 constexpr uint32_t RECT_NONE = 1u;
 __host__ __device__ inline uint32_t pack_bin_rect(uint32_t bbx, uint32_t bby, int bx_lo, int bx_hi)
 {

@@ -1,0 +1,210 @@
+// Read-backs and raw access: the sort's and the frame's buffers copied to the host, the framebuffer as floats or RGBA8,
+// device pointers and the stream for hosts that keep the pixels on the GPU, and the slab pack / unpack of a caller-run exchange.
+#include "gsr_ctx.h"
+
+#include <cstring>
+
+using namespace gsr;
+
+extern "C" {
+
+int gsr_read_depth_index(gsr_ctx* c, uint32_t* out)
+{
+    if (!c || !out) return c ? fail(c, GSR_ERR_ARG, "out is NULL") : GSR_ERR_ARG;
+    if (!c->have_sort) return fail(c, GSR_ERR_ARG, "no sort has run yet");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->sort.culled) {  // the band's frame sorted only its survivors: the caller wants the whole permutation
+        if (int r = enqueue_frame(c, false)) return r;
+        if (int r = finish_frame(c)) return r;
+    }
+    HIP_TRY(c, hipMemcpyAsync(out, c->sort.depth_index, (size_t)c->n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return GSR_OK;
+}
+
+int gsr_read_pixels_rgba32f(gsr_ctx* c, float* out)
+{
+    if (!c || !out) return c ? fail(c, GSR_ERR_ARG, "out is NULL") : GSR_ERR_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(out, c->out.fb, (size_t)c->W * c->H * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return GSR_OK;
+}
+
+int gsr_read_pixels_rgba8(gsr_ctx* c, uint8_t* out)
+{
+    if (!c || !out) return c ? fail(c, GSR_ERR_ARG, "out is NULL") : GSR_ERR_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t np = (uint32_t)c->W * (uint32_t)c->H;
+    launch_to_rgba8(c->out.fb, c->out.fb8, np, c->stream);
+    HIP_TRY(c, hipMemcpyAsync(out, c->out.fb8, (size_t)np * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return GSR_OK;
+}
+
+int gsr_read_keys(gsr_ctx* c, uint32_t* keys, int32_t* minmax)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (!c->have_sort) return fail(c, GSR_ERR_ARG, "no sort has run yet");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->sort.culled) {
+        if (int r = enqueue_frame(c, false)) return r;
+        if (int r = finish_frame(c)) return r;
+    }
+    if (keys) HIP_TRY(c, hipMemcpyAsync(keys, c->sort.keys, (size_t)c->n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (minmax) HIP_TRY(c, hipMemcpyAsync(minmax, c->words.fstate->minmax, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return GSR_OK;
+}
+
+int gsr_read_records(gsr_ctx* c, float* rec, int32_t* bbox)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (!c->have_frame) return fail(c, GSR_ERR_ARG, "no frame has been rendered yet");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (rec) HIP_TRY(c, hipMemcpyAsync(rec, c->sort.rec, (size_t)c->n * 32, hipMemcpyDeviceToHost, c->stream));
+    std::vector<uint2> tmp;
+    if (bbox) {
+        // the pixel boxes are not part of a frame (no kernel reads them): project once more for the frame's camera, records and
+        // boxes only (k_project_key, do_project == 2: the same arithmetic, so the same records)
+        tmp.resize(c->n);
+        if (c->n) {
+            DevBuf<uint2> boxes;
+            if (int r = boxes.alloc(c, c->n)) return r;
+            ProjectLaunch again{};   // (kept / kept_lane null: no packing)
+            again.sc = c->scene.soa(); again.n = c->n; again.cam = c->cam_frame; again.do_project = 2;
+            again.depth = c->sort.depth; again.slots = c->words.slots; again.rec = c->sort.rec; again.bbox = boxes;
+            again.rect = c->sort.rect_idx; again.overflow = &c->words.fstate->overflow;
+            launch_project_key(again, c->stream);
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipMemcpyAsync(tmp.data(), boxes, (size_t)c->n * 8, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+        }
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (bbox)
+        for (uint32_t i = 0; i < c->n; i++) {
+            bbox[4 * (size_t)i + 0] = (int32_t)(tmp[i].x & 0xffff);
+            bbox[4 * (size_t)i + 1] = (int32_t)(tmp[i].y & 0xffff);
+            bbox[4 * (size_t)i + 2] = (int32_t)(tmp[i].x >> 16);
+            bbox[4 * (size_t)i + 3] = (int32_t)(tmp[i].y >> 16);
+        }
+    return GSR_OK;
+}
+
+int gsr_read_sh_colors(gsr_ctx* c, float* rgba)
+{
+    if (!c || !rgba) return c ? fail(c, GSR_ERR_ARG, "out is NULL") : GSR_ERR_ARG;
+    if (!c->have_frame || !c->scene.sh_count) return fail(c, GSR_ERR_ARG, "no frame rendered with SH colours yet");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(rgba, c->scene.shcol, (size_t)c->n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return GSR_OK;
+}
+
+int gsr_read_work_items(gsr_ctx* c, uint32_t* out)
+{
+    if (!c || !out) return c ? fail(c, GSR_ERR_ARG, "out is NULL") : GSR_ERR_ARG;
+    if (!c->have_frame) return fail(c, GSR_ERR_ARG, "no frame has been rendered yet");
+    HIP_TRY(c, hipSetDevice(c->device));
+    static_assert(offsetof(FrameState, n_items) == offsetof(FrameState, seg_len) + 4 && offsetof(FrameState, spec) == offsetof(FrameState, seg_len) + 8,
+                  "seg_len, n_items, spec are read through one pointer");
+    HIP_TRY(c, hipMemcpyAsync(out, &c->words.fstate->seg_len, 12, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const BinGrid g = make_grid(c);
+    out[3] = std::min(c->bin.blend_sub, 2u);
+    out[4] = (uint32_t)((g.bx_hi - g.bx_lo) * g.nby);
+    return GSR_OK;
+}
+
+int gsr_read_bin_totals(gsr_ctx* c, uint32_t* out, int32_t* nbx, int32_t* nby)
+{
+    if (!c || !out) return c ? fail(c, GSR_ERR_ARG, "out is NULL") : GSR_ERR_ARG;
+    if (!c->have_frame) return fail(c, GSR_ERR_ARG, "no frame has been rendered yet");
+    const BinGrid g = make_grid(c);
+    const int w = g.bx_hi - g.bx_lo;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(out, c->bin.total, (size_t)w * g.nby * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (nbx) *nbx = w;
+    if (nby) *nby = g.nby;
+    return GSR_OK;
+}
+
+int gsr_read_bin_lists(gsr_ctx* c, uint32_t* starts, uint32_t* list, uint64_t list_words)
+{
+    if (!c || !starts) return c ? fail(c, GSR_ERR_ARG, "starts is NULL") : GSR_ERR_ARG;
+    if (!c->have_frame) return fail(c, GSR_ERR_ARG, "no frame has been rendered yet");
+    const BinGrid g = make_grid(c);
+    const size_t nbins = (size_t)(g.bx_hi - g.bx_lo) * g.nby;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(starts, c->bin.start, (nbins + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const uint64_t total = starts[nbins];
+    if (list) {
+        if (total > list_words || total > c->bin.capacity) return fail(c, GSR_ERR_ARG, "the frame's lists hold %llu entries", (unsigned long long)total);
+        HIP_TRY(c, hipMemcpyAsync(list, c->bin.list, total * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return GSR_OK;
+}
+
+int gsr_convert_rgba8_async(gsr_ctx* c)
+{
+    if (!c) return GSR_ERR_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    launch_to_rgba8(c->out.fb, c->out.fb8, (uint32_t)c->W * (uint32_t)c->H, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return GSR_OK;
+}
+
+void* gsr_framebuffer8_device_ptr(gsr_ctx* c) { return c ? (void*)c->out.fb8 : nullptr; }
+
+int gsr_pack_band_rgba8_async(gsr_ctx* c, void* slab, int32_t slab_width_px)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (!slab || !c->out.fb) return fail(c, GSR_ERR_ARG, "gsr_pack_band_rgba8_async: no slab / nothing rendered yet");
+    const BinGrid g = make_grid(c);
+    const int x0 = g.bx_lo * BIN_PX, x1 = std::min(g.bx_hi * BIN_PX, c->W);
+    if (slab_width_px < x1 - x0) return fail(c, GSR_ERR_ARG, "gsr_pack_band_rgba8_async: slab narrower than the band");
+    HIP_TRY(c, hipSetDevice(c->device));
+    launch_pack_band_rgba8(c->out.fb, (uint32_t*)slab, c->W, c->H, x0, x1, slab_width_px, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return GSR_OK;
+}
+
+int gsr_unpack_slabs_rgba8_async(gsr_ctx* c, const void* gathered, void* image, int32_t slab_width_px, int32_t world,
+                                 const int32_t* x0, const int32_t* x1, void* stream)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (!gathered || !image || !x0 || !x1 || world < 1 || world > MAX_SLABS)
+        return fail(c, GSR_ERR_ARG, "gsr_unpack_slabs_rgba8_async: bad argument (1 <= world <= 16)");
+    SlabEdges e{};
+    for (int q = 0; q < world; q++) {
+        if (x0[q] < 0 || x1[q] > c->W || x1[q] - x0[q] > slab_width_px)
+            return fail(c, GSR_ERR_ARG, "gsr_unpack_slabs_rgba8_async: band outside the image or wider than the slab");
+        e.x0[q] = x0[q]; e.x1[q] = x1[q];
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    launch_unpack_slabs_rgba8((const uint32_t*)gathered, (uint32_t*)image, c->W, c->H, slab_width_px, world, e, (hipStream_t)stream);
+    HIP_TRY(c, hipGetLastError());
+    return GSR_OK;
+}
+
+void* gsr_framebuffer_device_ptr(gsr_ctx* c) { return c ? (void*)c->out.fb : nullptr; }
+void* gsr_stream_handle(gsr_ctx* c) { return c ? (void*)c->stream : nullptr; }
+
+int gsr_stream_order(gsr_ctx* c, void* other_stream, int32_t ctx_waits)
+{
+    if (!c) return GSR_ERR_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipEvent_t& ev = c->link_ev[ctx_waits ? 1 : 0];
+    if (!ev) HIP_TRY(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipStream_t from = ctx_waits ? (hipStream_t)other_stream : c->stream;
+    hipStream_t to = ctx_waits ? c->stream : (hipStream_t)other_stream;
+    HIP_TRY(c, hipEventRecord(ev, from));
+    HIP_TRY(c, hipStreamWaitEvent(to, ev, 0));
+    return GSR_OK;
+}
+
+}  // extern "C"

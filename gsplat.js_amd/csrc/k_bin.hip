@@ -298,7 +298,7 @@ __device__ __forceinline__ void bin_finalize_body(const FinalizeArgs& fa, uint32
     // 1.6 M splats: tau 394, 3.6 tiles per splat, long items 8 % slower; C3: 5.3 tiles per splat, 23 % faster)
     const bool dense = optical * (16u * 256u) >= (uint64_t)fa.long_tau * 255u * (uint64_t)fa.npix &&
                        (uint64_t)ctot.v[1] * 2u >= (uint64_t)fa.long_tiles_x2 * ctot.v[0];
-    // Which bins become ONE work item (gsr_api.cpp, "Work-item length").  A whole-bin item stops where the bin saturates, which
+    // Which bins become ONE work item (gsr_frame.cpp, "Work-item length").  A whole-bin item stops where the bin saturates, which
     // pays where the bin holds much more than it takes to saturate it -- and costs a serial pole as long as that takes; a bin cut
     // into segments is composited by several workgroups at once, every segment in full.  A frame can mix both kinds of bins (a
     // dense object in front of a sparse background), so the choice is made PER BIN, deterministically from figures of this

@@ -140,7 +140,7 @@ __device__ __forceinline__ float eval_sh_texture(const uint32_t* __restrict__ te
 // ---------------------------------------------------------------------------
 // The camera is a kernel argument (scalar loads from the kernarg segment).  It is the one argument of the frame's chain that
 // changes from frame to frame: when the chain is replayed as a HIP graph, the host rewrites this kernel node's parameters
-// (hipGraphExecKernelNodeSetParams, gsr_api.cpp) -- there is no kernel in front of the frame that would carry the camera to
+// (hipGraphExecKernelNodeSetParams, gsr_frame.cpp) -- there is no kernel in front of the frame that would carry the camera to
 // device memory and reset the frame's words.  What such a kernel did is done where it costs nothing: the frame slots are
 // reset by their last reader (the finalize step, k_bin.hip), the overflow word here.
 __global__ __launch_bounds__(PROJ_THREADS) void k_project_key(SceneSoA sc, uint32_t n, CamParams cam,

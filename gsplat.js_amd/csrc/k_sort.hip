@@ -555,7 +555,7 @@ __global__ __launch_bounds__(SCAT_THREADS) void k_scatter(const uint32_t* __rest
 // inside every digit) -- a redundant read of the bucket, which sits in L2 -- then ranks its chunk exactly like
 // k_scatter does and places it.  The redundant counting is quadratic in the bucket size, so a bucket holding most of
 // the scene (depth outliers stretch the key range) is slow this way: every frame reports its largest bucket to the
-// host, which falls back to the LSD order while that exceeds LOCAL_BUCKET_LIMIT (gsr_api.cpp).
+// host, which falls back to the LSD order while that exceeds LOCAL_BUCKET_LIMIT (gsr_frame.cpp).
 // ---------------------------------------------------------------------------
 inline uint32_t local_sort_grid(uint32_t n) { return (n + LOCAL_CHUNK - 1) / LOCAL_CHUNK + RADIX_HI_BINS / 2 + 1; }   // >= sum over buckets of ceil(size / chunk)
 // (a 2-D grid -- chunk x bucket, bucket starts handed over by the partition pass, no search -- was measured slower:

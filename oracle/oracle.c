@@ -8,7 +8,7 @@
  * Parity status
  *   sort path   (orc_sort)        PINNED: checked bit-for-bit against the
  *                                 reference's own wasm/wasm.cpp compiled from
- *                                 source (oracle/_ref, tests/test_oracle_ref.py)
+ *                                 source (oracle/_ref, tests/test_oracle_sort.py)
  *                                 and against tests/golden/ fixtures generated
  *                                 from it (tests/golden/make_golden.py).
  *   scene pack / build / transforms (orc_scene_*)
@@ -60,7 +60,7 @@
  * Defined semantics for the reference's max-bucket overflow:
  * the key domain is [0, 65536] (17 bits); splats whose key is 65536 go LAST,
  * in ascending original index.  The unmodified reference produces exactly
- * this when starts[65536] is preset to N - #{q==65536} (oracle/ref_driver.c
+ * this when starts[65536] is preset to N - #{q==65536} (oracle.py:ref_sort
  * does that); here the counting arrays simply have 65537 entries.
  * Degenerate maxDepth==minDepth (reference: 0*inf = NaN, undefined cast):
  * every key is 0, identity permutation.

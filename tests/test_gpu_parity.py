@@ -570,7 +570,7 @@ def test_native_slab_exchange_single_device(gh, scenes):
 def test_graph_replay_equals_individual_launches(gh, scenes, monkeypatch):
     # frames without stage events are replayed from a captured HIP graph; the same frames issued as individual launches
     # (GSR_NO_GRAPH=1 at context creation) must give identical pixels and permutations, across camera changes, a resize
-    # (new chain signature -> recapture) and sampled timing (every 3rd frame takes the individual-launch path)
+    # (other launch arguments -> recapture) and sampled timing (every 3rd frame takes the individual-launch path)
     cfg = gh.synth.CONFIGS["C1"]
     rows, data, pos = scenes("C1")
     monkeypatch.setenv("GSR_NO_GRAPH", "1")
@@ -592,6 +592,27 @@ def test_graph_replay_equals_individual_launches(gh, scenes, monkeypatch):
     assert 2 <= st["frames"] <= 4          # 7 renders + the sort-only calls of lastDepthIndex do not all carry events
     with pytest.raises(gh.GsplatError):
         graph.set_timing_interval(0)
+    # the calls that reallocate what a captured graph points at or change what its launches are sized by: after each, two
+    # frames on both contexts (at most one of two consecutive frames carries events, so one of them is a graph launch)
+    n = pos.size // 3
+    m = n // 2
+    sh = [np.full(8 * n, 0x34003400, dtype=np.uint32) for _ in range(3)]     # (every half-float coefficient 0.25)
+    rows2 = gh.synth.synth_rows(4096, 17)
+    changes = [lambda r: r.set_list_capacity(1 << 21),
+               lambda r: r.set_band(128, 384), lambda r: r.set_band(0, 0),
+               lambda r: r.set_sh(sh, [-1, n // 4, n // 2]), lambda r: r.set_sh(sh, [n - 1, n - 1, n - 1]),
+               lambda r: r.set_scene_rows(rows2), lambda r: r.scene_limit_box([-1.0, 1.0, -1.0, 1.0, -1.0, 1.0]),
+               lambda r: r.set_raw_scene(data[:8 * m], pos[:3 * m])]
+    for step, change in enumerate(changes):
+        for r in (plain, graph):
+            change(r)
+        for k in (20 + 2 * step, 21 + 2 * step):
+            for r in (plain, graph):
+                r.set_camera(gh.orbit_camera(k, width=r.width, height=r.height, fx=cfg["fx"]))
+                r.render_async(); r.sync()
+            assert np.array_equal(plain.readPixelsFloat(), graph.readPixelsFloat()), (step, k)
+            assert np.array_equal(plain.lastDepthIndex(), graph.lastDepthIndex()), (step, k)
+    assert plain.stats()["overflow_frames"] == 0 and graph.stats()["overflow_frames"] == 0
     plain.dispose(); graph.dispose()
 
 
@@ -803,6 +824,15 @@ def test_sort_host_sees_positions_edited_in_place(gh, oracle, scenes):
     out2 = np.empty(m, dtype=np.uint32)
     L.gsplat_sort_host(vp.ctypes.data, m, buf.ctypes.data, None, out2.ctypes.data, None, None)
     assert np.array_equal(out2, oracle.sort(vp, buf[:3 * m])[0])
+    # an empty scene between two sorts (a viewer that resets and reloads its scene): it runs no kernel, so it must not move on
+    # the sort-only frames' slot sets either -- the sort behind it would fold the depth range of the sort before it into its own
+    L.gsplat_sort_host(vp.ctypes.data, out.size, buf.ctypes.data, None, out.ctypes.data, None, None)
+    L.gsplat_sort_host(vp.ctypes.data, 0, buf.ctypes.data, None, out2.ctypes.data, None, None)
+    near = np.ascontiguousarray(buf[:3 * m] * np.float32(0.25))      # another depth range than the whole scene's
+    keys2 = np.empty(m, dtype=np.uint32)
+    L.gsplat_sort_host(vp.ctypes.data, m, near.ctypes.data, keys2.ctypes.data, out2.ctypes.data, None, None)
+    odi3, okeys3, _ = oracle.sort(vp, near)
+    assert np.array_equal(keys2, okeys3) and np.array_equal(out2, odi3)
 
 
 def test_limit_box_clears_sh_state(gh):
@@ -1388,7 +1418,7 @@ def test_bins_with_more_than_64_segments(gh, monkeypatch, sub):
     monkeypatch.setenv("GSR_BLEND_SUB", sub)
     cam0 = gh.orbit_camera(5, 120, W, H, cfg["fx"])
     fused = gh.HIPRenderer(W, H)
-    fused.render(scene, cam0)          # (the cut's knobs are read when the scene is set: while they are in the environment)
+    fused.render(scene, cam0)
     monkeypatch.setenv("GSR_FUSE_COMBINE", "0")
     separate = gh.HIPRenderer(W, H)
     separate.render(scene, cam0)
