@@ -19,8 +19,9 @@ namespace {
 
 thread_local std::string g_create_error;
 
-// the one place the library reads its environment (Knobs, gsr_ctx.h)
-Knobs read_knobs()
+// the one place the library reads its environment (Knobs, gsr_ctx.h).  A knob that selects among kernels built for a fixed set
+// of values (GSR_FRONT_WAVES) refuses anything else: `bad` then says what, and gsr_create fails with it.
+Knobs read_knobs(std::string& bad)
 {
     Knobs k;
     if (const char* e = getenv("GSR_NO_GRAPH")) k.graphs = atoi(e) == 0;
@@ -41,6 +42,12 @@ Knobs read_knobs()
     if (const char* e = getenv("GSR_BLEND_GRID")) { const long v = atol(e); if (v >= 1) k.blend_grid = (uint32_t)v; }
     if (const char* e = getenv("GSR_SEG_LEN")) { const long v = atol(e); if (v >= 256) k.seg_len = (uint32_t)(v / 256 * 256); }
     if (const char* e = getenv("GSR_SORT_KPB")) { const long v = atol(e); if (v == 2048 || v == 4096 || v == 8192) k.sort_kpb = (uint32_t)v; }
+    if (const char* e = getenv("GSR_FRONT_WAVES")) {
+        char* end = nullptr;
+        const long v = strtol(e, &end, 10);
+        if (end != e && *end == 0 && (v == (long)FRONT_WAVES_NARROW || v == (long)FRONT_WAVES_WIDE)) k.front_waves = (uint32_t)v;
+        else bad = std::string("GSR_FRONT_WAVES must be ") + std::to_string(FRONT_WAVES_NARROW) + " or " + std::to_string(FRONT_WAVES_WIDE) + ", not \"" + e + "\"";
+    }
     return k;
 }
 
@@ -84,6 +91,9 @@ int gsr_create(gsr_ctx** out, const gsr_options* opt)
 {
     if (!out) return fail(nullptr, GSR_ERR_ARG, "out is NULL");
     *out = nullptr;
+    std::string bad_knob;
+    const Knobs knobs = read_knobs(bad_knob);
+    if (!bad_knob.empty()) return fail(nullptr, GSR_ERR_ARG, "%s", bad_knob.c_str());
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
         return fail(nullptr, GSR_ERR_NO_DEVICE, "no HIP device is visible (this library has no CPU path)");
@@ -95,7 +105,7 @@ int gsr_create(gsr_ctx** out, const gsr_options* opt)
     gsr_ctx* c = new gsr_ctx();
     c->device = o.device;
     c->opt = o;
-    c->knobs = read_knobs();
+    c->knobs = knobs;
     c->graph.enabled = c->knobs.graphs;
     c->timing.every = c->knobs.timing_every;
     auto bail = [&](int code) {

@@ -90,6 +90,7 @@ struct Knobs {
     uint32_t blend_grid = 0;     // GSR_BLEND_GRID: persistent compositor workgroups (0: by the device)
     uint32_t seg_len = 0;        // GSR_SEG_LEN: entries per compositor work item, a multiple of 256 (0: the built-in length)
     uint32_t sort_kpb = 0;       // GSR_SORT_KPB: keys per radix workgroup, 2048, 4096 or 8192 (0: by the scene's size)
+    uint32_t front_waves = 0;    // GSR_FRONT_WAVES=8|16: waves per workgroup of the heavy front-end kernels (0: by the kind of context)
 };
 
 // The scene's per-splat arrays: everything the on-device build, the transforms and the compaction move together.
@@ -129,6 +130,7 @@ struct FrameArgs {
     BlendBuffers blend;
     float early_out_eps;
     uint32_t n;
+    uint32_t front_waves;    // waves per workgroup of the heavy front-end kernels: FRONT_WAVES_WIDE, or FRONT_WAVES_NARROW (gsr_internal.h)
     bool render;             // false: a sort-only frame (depth key + sort)
     bool sort_culled;        // the sort keeps only the band's survivors (depth_index / keys are partial)
 };

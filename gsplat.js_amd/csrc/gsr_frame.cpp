@@ -91,6 +91,9 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
     a.n = c->n;
     a.grid = g;
     a.early_out_eps = c->opt.early_out_eps;
+    // throughput contexts run beside other frames' compositors: their front-end workgroups are narrow, so that they fit what
+    // a few retired compositor workgroups leave free on a CU (the launchers keep the wide forms off the one-level 1080p chain)
+    a.front_waves = c->knobs.front_waves ? c->knobs.front_waves : throughput ? FRONT_WAVES_NARROW : FRONT_WAVES_WIDE;
     a.sort_culled = cull && c->n;   // (an empty frame sorts nothing, so nothing of it is partial)
 
     // a sort-only frame has its own slots (sets 1 and 2 in turn; set 0 belongs to the render frames and k_begin_frame)
@@ -238,7 +241,7 @@ int enqueue_chain(gsr_ctx* c, const FrameArgs& a, bool timing)
         else launch_depth_key(a.proj.sc, a.n, c->cam, a.proj.depth, a.proj.slots, a.slots_next, s);
     }
     if (timing) HIP_TRY(c, hipEventRecord(ev[EV_PROJECT], s));
-    launch_sort(a.sort, a.n, s);
+    launch_sort(a.sort, a.n, s, a.front_waves);
     if (timing) HIP_TRY(c, hipEventRecord(ev[EV_SORT], s));
     if (a.render) {
         if (!a.n) {
@@ -246,7 +249,7 @@ int enqueue_chain(gsr_ctx* c, const FrameArgs& a, bool timing)
             HIP_TRY(c, hipMemsetAsync(a.bin.bin_total, 0, sizeof(uint32_t) * nbins, s));
             HIP_TRY(c, hipMemsetAsync(a.bin.overflow, 0, sizeof(uint32_t), s));   // (k_project_key zeroes it otherwise)
         }
-        launch_bin(a.bin, a.grid, a.n, s);
+        launch_bin(a.bin, a.grid, a.n, s, a.front_waves);
         if (timing) HIP_TRY(c, hipEventRecord(ev[EV_BIN], s));
         launch_blend(a.blend, a.grid, a.early_out_eps, s, (timing && !a.blend.bin_mask) ? ev[EV_BLEND] : nullptr);
         if (timing) HIP_TRY(c, hipEventRecord(ev[EV_COMBINE], s));

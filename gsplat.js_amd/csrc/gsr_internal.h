@@ -153,6 +153,12 @@ const void* project_key_kernel();
 dim3 project_key_grid(uint32_t n);
 void launch_project_key(ProjectLaunch& a, hipStream_t s);
 
+// Waves per workgroup of the four heavy front-end kernels of the one-level 1080p chain (k_scatter's bucket-order pass, k_local_sort,
+// k_bin_count, k_bin_scatter): WIDE everywhere, NARROW in throughput contexts, where a front-end workgroup has to fit the wave
+// slots and registers that retiring compositor workgroups of the other frames free on a CU (FrameArgs::front_waves).  A
+// workgroup owns the same keys / ranks and the same table row at either width, and both widths write the same bits.
+constexpr uint32_t FRONT_WAVES_WIDE = 16, FRONT_WAVES_NARROW = 8;
+
 // radix sort of the 17-bit keys; see k_sort.hip
 struct SortBuffers {
     const int32_t* depth;      // n
@@ -177,7 +183,7 @@ struct SortBuffers {
     uint32_t* rect_tmp;        // LSD order with rects_out: the rectangles after the first pass
     uint32_t* rects_out;       // LSD order: out: the packed bin rectangles in depth order (null: not carried; the binning gathers them)
 };
-void launch_sort(const SortBuffers& b, uint32_t n, hipStream_t s);
+void launch_sort(const SortBuffers& b, uint32_t n, hipStream_t s, uint32_t front_waves = FRONT_WAVES_WIDE);
 // column scan (k_sort.hip), shared with the binning
 // (live: the frame holds *live keys or ranks, live_unit of them per table row: the rows behind are neither written nor scanned)
 void launch_column_scan(uint32_t* table, uint32_t* total, int ncols, uint32_t nrows, hipStream_t s, const uint32_t* live = nullptr, uint32_t live_unit = 1);
@@ -242,7 +248,7 @@ struct BinBuffers {
     uint32_t band;               // 1: a band context (the frame holds fewer ranks than the scene: scans and workgroups stop at *count's rows)
     uint32_t n_max;              // entries the rank-ordered buffers hold (the scene's splats): k_bin_count may load that far before it knows *count
 };
-void launch_bin(const BinBuffers& b, const BinGrid& g, uint32_t n, hipStream_t s);
+void launch_bin(const BinBuffers& b, const BinGrid& g, uint32_t n, hipStream_t s, uint32_t front_waves = FRONT_WAVES_WIDE);
 
 struct BlendBuffers {
     const uint32_t* items;      // work items, four words each (BinBuffers::items)

@@ -65,15 +65,16 @@ __device__ __forceinline__ uint32_t lanes_below64(uint64_t mask)
 // (4 bytes per splat, k_project_key) are gathered through depth_index and left in depth order for the scatter pass.
 // No global atomics: hundreds of workgroups hitting the same few words cost more than the whole pass.
 // ---------------------------------------------------------------------------
-constexpr int CNT_THREADS = 1024;
-constexpr int CNT_STEPS = (int)BIN_RANKS_PER_BLOCK / CNT_THREADS;  // 2
+constexpr int CNT_WAVES = 16;        // (WAVES: 16, or FRONT_WAVES_NARROW in throughput contexts -- the same 2048 ranks and table row per workgroup)
 constexpr int CNT_MAX_BINS = 12288;  // LDS counters per workgroup (48 KiB); larger grids are cut into row slices (blockIdx.y)
 
-__global__ __launch_bounds__(CNT_THREADS) void k_bin_count(const uint32_t* __restrict__ depth_index, const uint32_t* __restrict__ rect_idx,
+template <int WAVES>
+__global__ __launch_bounds__(WAVES * WAVE) void k_bin_count(const uint32_t* __restrict__ depth_index, const uint32_t* __restrict__ rect_idx,
                                                            const uint32_t* __restrict__ count, BinGrid g, int slice_rows,
                                                            uint32_t rounds, uint32_t* __restrict__ table, uint32_t* __restrict__ rects, int shift, int sorted,
                                                            uint32_t n_max)
 {
+    constexpr int CNT_THREADS = WAVES * WAVE, CNT_STEPS = (int)BIN_RANKS_PER_BLOCK / CNT_THREADS;   // 2 ranks per thread and round, or 4
     // the first round's ranks (or their rectangles) do not depend on how many ranks the frame holds, only on how many the
     // buffers do (n_max): their loads go out in front of the count's, one round trip instead of two
     const uint32_t begin0 = blockIdx.x * rounds * BIN_RANKS_PER_BLOCK;
@@ -165,10 +166,10 @@ __global__ __launch_bounds__(CNT_THREADS) void k_bin_count(const uint32_t* __res
 constexpr int FIN_THREADS = 1024;
 constexpr int FIN_WAVES = FIN_THREADS / WAVE;
 
-// exclusive scan of N independent u32 streams over the workgroup's FIN_THREADS threads; totals in *tot
+// exclusive scan of N independent u32 streams over the workgroup's FIN_WAVES waves; totals in *tot
 template <int N> struct UN { uint32_t v[N]; };
 
-template <int N>
+template <int N, int FIN_WAVES = gsr::FIN_WAVES>
 __device__ __forceinline__ UN<N> block_exclusive_scan(UN<N> x, uint32_t (*s_w)[FIN_WAVES], UN<N>* tot)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -240,11 +241,14 @@ struct FinalizeArgs {
 constexpr int FIN_LAYERS = 64;   // segments per bin at most (one bit each in the bin's arrival mask, k_blend)
 constexpr int FIN_SCRATCH_WORDS = 64;   // LDS words the finalize step asks of its caller (none are used any more; kept so that every launch passes a non-zero size)
 
-// One workgroup of FIN_THREADS threads.  It runs as an EXTRA workgroup of k_bin_scatter (the scatter workgroups
+// One workgroup of FIN_THREADS threads (1024; 512 as the extra workgroup of the narrow k_bin_scatter: the bins per thread
+// double, what it publishes is the same).  It runs as an EXTRA workgroup of k_bin_scatter (the scatter workgroups
 // compute the bin starts they need themselves), so its ~9 us no longer sit between the column scan and the scatter;
 // k_bin_finalize is the stand-alone form for frames without splats.
+template <int FIN_THREADS = gsr::FIN_THREADS>
 __device__ __forceinline__ void bin_finalize_body(const FinalizeArgs& fa, uint32_t* __restrict__ scratch /* LDS, FIN_SCRATCH_WORDS */)
 {
+    constexpr int FIN_WAVES = FIN_THREADS / WAVE;
     const uint32_t* __restrict__ bin_total = fa.bin_total;
     const int nbins = fa.nbins;
     const uint32_t seg_len_min = fa.seg_len_min, seg_target_items = fa.seg_target_items, max_items = fa.max_items, capacity = fa.capacity;
@@ -364,7 +368,7 @@ __device__ __forceinline__ void bin_finalize_body(const FinalizeArgs& fa, uint32
         }
     }
     UN<3> tot;
-    const UN<3> ex3 = block_exclusive_scan<3>(mine, s_w, &tot);   // (its barriers also order the class counts)
+    const UN<3> ex3 = block_exclusive_scan<3, FIN_WAVES>(mine, s_w, &tot);   // (its barriers also order the class counts)
     uint32_t ex = ex3.v[0], sx = ex3.v[1], fx = ex3.v[2];
     if (by_size && threadIdx.x < WAVE) {   // class counts -> first item index of each class, heaviest class first
         static_assert(FIN_CLASSES == WAVE, "one class per lane");
@@ -579,7 +583,9 @@ __device__ __forceinline__ void cell_finalize_body(const uint32_t* __restrict__ 
 //    carrying over, so that the [workgroup][bin] table all three binning kernels exchange is 20 MB instead of 80 MB at
 //    5 M splats (more than the lists it helps to build).  Inside the 64-register kernel the same two things spilled 15 and
 //    44 registers and cost more than they saved (C4 binning 477 -> 533 us, profiles/r03_experiments.txt).
-template <int GROUPS, bool FUSED, bool BIG, int SPW /* 64-rank steps per wave and round */, bool CELLS = false>
+// WAVES (16; FRONT_WAVES_NARROW for the narrow k_bin_scatter): the workgroup's width.  The steps, the groups and the LDS tables
+// are those of the round -- STEPS = WAVES x SPW -- so half the waves take twice the steps each, in the same (group, step, lane) order.
+template <int GROUPS, bool FUSED, bool BIG, int SPW /* 64-rank steps per wave and round */, bool CELLS = false, int WAVES = 16>
 __device__ __forceinline__ void bin_scatter_body(const uint32_t* __restrict__ depth_index,
                                                               const uint32_t* __restrict__ rects,
                                                               const uint32_t* __restrict__ count, BinGrid g, BinSlices sl,
@@ -590,14 +596,16 @@ __device__ __forceinline__ void bin_scatter_body(const uint32_t* __restrict__ de
                                                               uint32_t* __restrict__ overflow, uint32_t rounds, const FinalizeArgs& fa,
                                                               const CellArgs& ca)
 {
-    static_assert(FIN_THREADS == SCAT_THREADS, "the finalize step runs as a workgroup of this kernel");
+    constexpr int SCAT_THREADS = WAVES * WAVE, SCAT_WAVES = WAVES;   // (of this instantiation)
+    static_assert(SCAT_WAVES % GROUPS == 0, "whole waves per group");
+    static_assert(WAVES == gsr::SCAT_WAVES || (FUSED && !CELLS), "the narrow form is the fused one-level kernel");
     static_assert(!(FUSED && BIG), "the large-grid form reads the bin starts from k_bin_starts");
     static_assert(!CELLS || FUSED, "the cell pass of the two-level binning is the fused form");
     constexpr bool EXTRA = FUSED || BIG;   // the finalize step is a workgroup of this launch
     if (EXTRA && blockIdx.x == (BIG ? 0u : gridDim.x - 1u)) {   // bin starts, work items and frame counters for the compositor
         extern __shared__ uint32_t s_fin[];   // this workgroup's share of the kernel's dynamic LDS (>= FIN_SCRATCH_WORDS, launch_bin)
         if (CELLS) cell_finalize_body(bin_total, (g.bx_hi - g.bx_lo) * g.nby, capacity, ca);   // (the cell pass: cell and chunk starts for level two)
-        else if (blockIdx.y == 0) bin_finalize_body(fa, s_fin);
+        else if (blockIdx.y == 0) bin_finalize_body<SCAT_THREADS>(fa, s_fin);   // (the finalize step at this kernel's width)
         return;
     }
     const int shift = CELLS ? ca.shift : 0;
@@ -787,6 +795,13 @@ template <int GROUPS, bool FUSED>
 __global__ __launch_bounds__(SCAT_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_bin_scatter(GSR_SCATTER_PARAMS)
 {
     bin_scatter_body<GROUPS, FUSED, false, SCAT_STEPS_PER_WAVE>(GSR_SCATTER_ARGS);
+}
+// the narrow form (throughput contexts, small bin grids): FRONT_WAVES_NARROW waves of 4 steps each over the same 2048 ranks.
+// At most 72 registers: two of its waves fit a SIMD beside five of the compositor's seven.
+template <int GROUPS>
+__global__ __launch_bounds__(FRONT_WAVES_NARROW * WAVE) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_bin_scatter_narrow(GSR_SCATTER_PARAMS)
+{
+    bin_scatter_body<GROUPS, true, false, SCAT_STEPS / (int)FRONT_WAVES_NARROW, false, (int)FRONT_WAVES_NARROW>(GSR_SCATTER_ARGS);
 }
 // level one of the two-level binning: the same pass over a grid of CELLS, entries = (splat index, rectangle in bins)
 template <int GROUPS>
@@ -1017,7 +1032,8 @@ static void set_scatter_lds_attribute()
         for (const void* fn : {(const void*)k_bin_scatter<8, true>, (const void*)k_bin_scatter<8, false>,
                                (const void*)k_bin_scatter<4, true>, (const void*)k_bin_scatter<4, false>,
                                (const void*)k_bin_scatter_big<8, 2>, (const void*)k_bin_scatter_big<4, 2>,
-                               (const void*)k_bin_scatter_big<4, 1>, (const void*)k_cell_scatter1<8>, (const void*)k_cell_scatter1<4>})
+                               (const void*)k_bin_scatter_big<4, 1>, (const void*)k_cell_scatter1<8>, (const void*)k_cell_scatter1<4>,
+                               (const void*)k_bin_scatter_narrow<8>})
             (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, want);
         (void)hipGetLastError();  // a failure shows up as the launch error
     });
@@ -1050,7 +1066,7 @@ static void launch_bin_two_level(const BinBuffers& b, const BinGrid& g, hipStrea
     const uint4* ci = reinterpret_cast<const uint4*>(b.chunk_info);
     const CellGeom cg{ncx, ncells, nbxb, g.nby};
     // level one (b.nblocks workgroups of 2048 ranks; the table's last column sums the rectangles' areas in bins)
-    hipLaunchKernelGGL(k_bin_count, dim3(b.nblocks), dim3(CNT_THREADS), (size_t)(ncells + 1) * sizeof(uint32_t), s, b.depth_index, b.rect_idx,
+    hipLaunchKernelGGL(k_bin_count<CNT_WAVES>, dim3(b.nblocks), dim3(CNT_WAVES * WAVE), (size_t)(ncells + 1) * sizeof(uint32_t), s, b.depth_index, b.rect_idx,
                        b.count, gc, ncy, 1u, b.table, b.rects, CELL_SHIFT, (int)b.rects_sorted, b.n_max);
     launch_column_scan(b.table, b.cell_total, ncells + 1, b.nblocks, s, b.band ? b.count : nullptr, BIN_RANKS_PER_BLOCK);
     {
@@ -1073,7 +1089,7 @@ static void launch_bin_two_level(const BinBuffers& b, const BinGrid& g, hipStrea
                        (const uint32_t*)b.bin_start_pre, b.list, b.capacity, fa);
 }
 
-void launch_bin(const BinBuffers& b, const BinGrid& g, uint32_t n, hipStream_t s)
+void launch_bin(const BinBuffers& b, const BinGrid& g, uint32_t n, hipStream_t s, uint32_t front_waves)
 {
     const int nbxb = g.bx_hi - g.bx_lo, nbins = nbxb * g.nby;
     if (nbins <= 0) return;
@@ -1094,18 +1110,26 @@ void launch_bin(const BinBuffers& b, const BinGrid& g, uint32_t n, hipStream_t s
     // the count pass keeps one counter per bin in LDS and is cut into row slices only beyond 12288 bins (above 4K)
     const int cnt_slices = (nbins + CNT_MAX_BINS - 1) / CNT_MAX_BINS;
     const int cnt_rows = (g.nby + cnt_slices - 1) / cnt_slices;
+    const bool fused = n && nbins <= 4096;   // see bin_scatter_body
+    // the narrow forms of the count and the scatter kernel: the 1080p chain of a throughput context (same grids, same table rows)
+    const bool narrow = front_waves == FRONT_WAVES_NARROW && fused && eight;
     if (n) {
-        hipLaunchKernelGGL(k_bin_count, dim3(b.nblocks, (g.nby + cnt_rows - 1) / cnt_rows), dim3(CNT_THREADS),
-                           (size_t)cnt_rows * nbxb * sizeof(uint32_t), s, b.depth_index, b.rect_idx, b.count, g, cnt_rows, b.rounds, b.table, b.rects, 0, (int)b.rects_sorted, b.n_max);
+        const dim3 cgrid(b.nblocks, (g.nby + cnt_rows - 1) / cnt_rows);
+        const size_t clds = (size_t)cnt_rows * nbxb * sizeof(uint32_t);
+        if (narrow)
+            hipLaunchKernelGGL(k_bin_count<(int)FRONT_WAVES_NARROW>, cgrid, dim3(FRONT_WAVES_NARROW * WAVE), clds, s, b.depth_index, b.rect_idx, b.count, g,
+                               cnt_rows, b.rounds, b.table, b.rects, 0, (int)b.rects_sorted, b.n_max);
+        else
+            hipLaunchKernelGGL(k_bin_count<CNT_WAVES>, cgrid, dim3(CNT_WAVES * WAVE), clds, s, b.depth_index, b.rect_idx, b.count, g,
+                               cnt_rows, b.rounds, b.table, b.rects, 0, (int)b.rects_sorted, b.n_max);
         launch_column_scan(b.table, b.bin_total, nbins, b.nblocks, s, b.band ? b.count : nullptr, b.rounds * BIN_RANKS_PER_BLOCK);
     }
     const FinalizeArgs fa = make_finalize_args(b, nbins, n);
-    const bool fused = n && nbins <= 4096;   // see bin_scatter_body
     const bool big = n && !fused && b.big;   // the large-grid form: finalize as the first workgroup, rounds
     if (!fused && !big) hipLaunchKernelGGL(k_bin_finalize, dim3(1), dim3(FIN_THREADS), FIN_SCRATCH_WORDS * sizeof(uint32_t), s, fa);
     if (n) {
         if (big) hipLaunchKernelGGL(k_bin_starts, dim3(1), dim3(FIN_THREADS), 0, s, (const uint32_t*)b.bin_total, nbins, b.bin_start_pre);
-        const dim3 grid(b.nblocks + ((fused || big) ? 1 : 0), sl.sx * sl.sy), block(SCAT_THREADS);
+        const dim3 grid(b.nblocks + ((fused || big) ? 1 : 0), sl.sx * sl.sy), block(narrow ? FRONT_WAVES_NARROW * WAVE : SCAT_THREADS);
 #define GSR_LAUNCH_SCATTER(K, STARTS)                                                                                               \
     hipLaunchKernelGGL((K), grid, block, lds, s, b.depth_index, (const uint32_t*)b.rects, b.count, g, sl,                           \
                        (const uint32_t*)b.table, (const uint32_t*)b.bin_total, (const uint32_t*)(STARTS), b.list, b.capacity,       \
@@ -1113,6 +1137,7 @@ void launch_bin(const BinBuffers& b, const BinGrid& g, uint32_t n, hipStream_t s
         if (big && eight) GSR_LAUNCH_SCATTER((k_bin_scatter_big<8, 2>), b.bin_start_pre);
         else if (big && short_rounds) GSR_LAUNCH_SCATTER((k_bin_scatter_big<4, 1>), b.bin_start_pre);
         else if (big) GSR_LAUNCH_SCATTER((k_bin_scatter_big<4, 2>), b.bin_start_pre);
+        else if (narrow) GSR_LAUNCH_SCATTER((k_bin_scatter_narrow<8>), b.bin_start);
         else if (eight && fused) GSR_LAUNCH_SCATTER((k_bin_scatter<8, true>), b.bin_start);
         else if (eight) GSR_LAUNCH_SCATTER((k_bin_scatter<8, false>), b.bin_start);
         else if (fused) GSR_LAUNCH_SCATTER((k_bin_scatter<4, true>), b.bin_start);

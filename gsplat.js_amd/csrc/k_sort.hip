@@ -337,6 +337,9 @@ void launch_column_scan(uint32_t* table, uint32_t* total, int ncols, uint32_t nr
 //   phase 3  rank with ballot matching and write (key, index) into LDS at the local position
 //   phase 4  stream the LDS image out: consecutive lanes hold consecutive local positions, so within a digit they store
 //            to consecutive addresses.
+// WAVES (16, or 8: the narrow form of throughput contexts, launch_sort) is the workgroup's width, not what it owns: the
+// same keys_per_block keys, the same table row, each wave a contiguous WAVES-th of them in twice as many steps -- the
+// order above is the input order either way, so both widths write the same bits.
 // Phase 4 is what the pass is about.  Storing straight from phase 3 gave every lane of a wave its own destination
 // line: 64 cache lines per store instruction, and the address path -- not HBM -- set the kernel's time (in-kernel
 // stamps on C3: 4.4 of a workgroup's 7.1 us in the rank-and-store phase; at 20 M splats the pass reached 15 % of the
@@ -347,23 +350,25 @@ void launch_column_scan(uint32_t* table, uint32_t* total, int ncols, uint32_t nr
 constexpr int SCAT_THREADS = 1024;
 constexpr int SCAT_WAVES = SCAT_THREADS / WAVE;
 constexpr int SCAT_MAX_STEPS = 8;  // keys_per_block <= SCAT_THREADS * SCAT_MAX_STEPS = 8192
+// The narrow forms (FRONT_WAVES_NARROW waves per workgroup) of the bucket order's two kernels: a workgroup that fits the wave
+// slots and registers one or two retired compositor workgroups leave on a CU ("front-end width").  They take
+// NARROW_KEYS_PER_BLOCK-key blocks only (4 steps per wave: fewer key registers than the wide form's 8).
+constexpr uint32_t NARROW_KEYS_PER_BLOCK = 2048;
+constexpr int scat_max_steps(int waves) { return waves == SCAT_WAVES ? SCAT_MAX_STEPS : (int)NARROW_KEYS_PER_BLOCK / (waves * WAVE); }
 // (the bucket order's second kernel, k_local_sort below: one workgroup per LOCAL_CHUNK keys of a bucket)
-constexpr int LOCAL_THREADS = 1024;
-constexpr int LOCAL_WAVES = LOCAL_THREADS / WAVE;
-constexpr int LOCAL_STEPS = 4;                                    // 64-key steps per wave
-constexpr uint32_t LOCAL_CHUNK = LOCAL_THREADS * LOCAL_STEPS;     // 4096 keys per workgroup
+constexpr uint32_t LOCAL_CHUNK = 4096;                            // keys per workgroup: 16 waves x 4 steps of 64 keys, or 8 x 8
 
 template <int BITS>
-constexpr size_t scatter_lds_bytes(uint32_t keys_per_block)
+constexpr size_t scatter_lds_bytes(uint32_t keys_per_block, int waves = SCAT_WAVES)
 {
-    return (size_t)(SCAT_WAVES * (1 << BITS) + 2 * (1 << BITS) + 3 * ((1 << BITS) / WAVE) + 2 * keys_per_block) * sizeof(uint32_t);
+    return (size_t)(waves * (1 << BITS) + 2 * (1 << BITS) + 3 * ((1 << BITS) / WAVE) + 2 * keys_per_block) * sizeof(uint32_t);
 }
 
 // PAY: one more word per key travels with it (the splat's packed bin rectangle, from rect order to depth order in the two
 // LSD passes: the binning then reads it in rank order instead of gathering 4 bytes per rank through depthIndex -- 5 M
 // random reads, 60 of k_bin_count's 79 us on C4).  It takes the index image's place in LDS once that has been streamed out.
-template <int BITS, int SHIFT, bool FIRST, bool PAY = false>
-__global__ __launch_bounds__(SCAT_THREADS) void k_scatter(const uint32_t* __restrict__ keys_in,
+template <int BITS, int SHIFT, bool FIRST, bool PAY = false, int WAVES = SCAT_WAVES>
+__global__ __launch_bounds__(WAVES * WAVE) void k_scatter(const uint32_t* __restrict__ keys_in,
                                                           const uint32_t* __restrict__ idx_in, uint32_t n_in,
                                                           uint32_t* __restrict__ count,
                                                           uint32_t keys_per_block, const uint32_t* __restrict__ base,
@@ -374,7 +379,8 @@ __global__ __launch_bounds__(SCAT_THREADS) void k_scatter(const uint32_t* __rest
                                                           uint4* __restrict__ chunk_tab = nullptr)
 {
     constexpr int BINS = 1 << BITS;
-    static_assert(BINS <= SCAT_THREADS, "one digit per thread");
+    constexpr int THREADS = WAVES * WAVE, MAX_STEPS = scat_max_steps(WAVES);
+    static_assert(BINS <= THREADS, "one digit per thread");
     // the first pass runs on all n_in keys (their indices are their positions) and publishes the number as *count -- or, in
     // band mode (idx_in set), on the *count survivors k_quantise_hist left dense, with their original indices in idx_in;
     // the second pass runs on *count
@@ -382,7 +388,7 @@ __global__ __launch_bounds__(SCAT_THREADS) void k_scatter(const uint32_t* __rest
     const uint32_t n = (FIRST && !band) ? n_in : *count;
     extern __shared__ uint32_t s_scat[];
     uint32_t (*cnt)[BINS] = reinterpret_cast<uint32_t (*)[BINS]>(s_scat);   // [wave][digit]: counts, then local positions
-    uint32_t* gdelta = s_scat + SCAT_WAVES * BINS;   // [digit]: global destination of local position p is gdelta[digit] + p
+    uint32_t* gdelta = s_scat + WAVES * BINS;   // [digit]: global destination of local position p is gdelta[digit] + p
     uint32_t* lstart = gdelta + BINS;                // [digit]: first local position of the digit (phase 2 scratch)
     uint32_t* wsum = lstart + BINS;                  // [3][BINS / WAVE]: per-wave sums of the two scans, per-wave maxima of the totals
     uint32_t* lkey = wsum + 3 * (BINS / WAVE);       // [keys_per_block]
@@ -399,20 +405,20 @@ __global__ __launch_bounds__(SCAT_THREADS) void k_scatter(const uint32_t* __rest
         tot = total[threadIdx.x];
         wg_base = base[(size_t)blk * BINS + threadIdx.x];
     }
-    for (int d = threadIdx.x; d < SCAT_WAVES * BINS; d += SCAT_THREADS) (&cnt[0][0])[d] = 0;
+    for (int d = threadIdx.x; d < WAVES * BINS; d += THREADS) (&cnt[0][0])[d] = 0;
     __syncthreads();
     KSTAMP(1);
 
-    const uint32_t per_wave = keys_per_block / SCAT_WAVES;  // multiple of 64
-    const uint32_t steps = per_wave / WAVE;                 // <= SCAT_MAX_STEPS
+    const uint32_t per_wave = keys_per_block / WAVES;  // multiple of 64
+    const uint32_t steps = per_wave / WAVE;                 // <= MAX_STEPS
     const uint32_t wbegin = blk * keys_per_block + wave * per_wave;
     const uint32_t wend = min(wbegin + per_wave, n);
 
     // phase 1: load this wave's keys (and, in the last pass, their indices) into registers; count digits per wave
-    uint32_t key[SCAT_MAX_STEPS], src[SCAT_MAX_STEPS];
-    uint32_t pay[PAY ? SCAT_MAX_STEPS : 1], pos[PAY ? SCAT_MAX_STEPS : 1];
+    uint32_t key[MAX_STEPS], src[MAX_STEPS];
+    uint32_t pay[PAY ? MAX_STEPS : 1], pos[PAY ? MAX_STEPS : 1];
 #pragma unroll
-    for (int k = 0; k < SCAT_MAX_STEPS; k++) {
+    for (int k = 0; k < MAX_STEPS; k++) {
         const uint32_t i = wbegin + k * WAVE + lane;
         const bool in = (uint32_t)k < steps && i < wend;
         key[k] = in ? keys_in[i] : 0xffffffffu;
@@ -421,7 +427,7 @@ __global__ __launch_bounds__(SCAT_THREADS) void k_scatter(const uint32_t* __rest
         if (PAY) pay[k] = in ? pay_in[band ? src[k] : i] : 0u;   // (band mode: the rectangle stayed at the splat's own index)
     }
 #pragma unroll
-    for (int k = 0; k < SCAT_MAX_STEPS; k++)
+    for (int k = 0; k < MAX_STEPS; k++)
         if (key[k] != 0xffffffffu) atomicAdd(&cnt[wave][(key[k] >> SHIFT) & (BINS - 1)], 1u);
     __syncthreads();
     KSTAMP(2);
@@ -432,7 +438,7 @@ __global__ __launch_bounds__(SCAT_THREADS) void k_scatter(const uint32_t* __rest
     if (threadIdx.x < BINS) {
         const int d = threadIdx.x;
 #pragma unroll
-        for (int w = 0; w < SCAT_WAVES; w++) {
+        for (int w = 0; w < WAVES; w++) {
             const uint32_t c = cnt[w][d];
             cnt[w][d] = H;
             H += c;
@@ -494,7 +500,7 @@ __global__ __launch_bounds__(SCAT_THREADS) void k_scatter(const uint32_t* __rest
     // phase 3: local position = digit start + keys of the digit in earlier waves + rank among this wave's earlier keys
     uint32_t* wc = cnt[wave];   // private to this wave from here on
 #pragma unroll
-    for (int k = 0; k < SCAT_MAX_STEPS; k++) {
+    for (int k = 0; k < MAX_STEPS; k++) {
         if ((uint32_t)k >= steps) break;  // wave-uniform
         const bool valid = key[k] != 0xffffffffu;
         const uint32_t digit = (key[k] >> SHIFT) & (BINS - 1);
@@ -519,8 +525,8 @@ __global__ __launch_bounds__(SCAT_THREADS) void k_scatter(const uint32_t* __rest
     }
     __syncthreads();
     // phase 4: the LDS image, in order, to its runs in global memory
-    const uint32_t nlocal = lstart[BINS - 1] + cnt[SCAT_WAVES - 1][BINS - 1];   // keys this workgroup holds (absent ones excluded)
-    for (uint32_t p = threadIdx.x; p < nlocal; p += SCAT_THREADS) {
+    const uint32_t nlocal = lstart[BINS - 1] + cnt[WAVES - 1][BINS - 1];   // keys this workgroup holds (absent ones excluded)
+    for (uint32_t p = threadIdx.x; p < nlocal; p += THREADS) {
         const uint32_t kv = lkey[p];
         const uint32_t dst = gdelta[(kv >> SHIFT) & (BINS - 1)] + p;
         GSR_BOUND(sort, 0, dst, n);
@@ -531,12 +537,12 @@ __global__ __launch_bounds__(SCAT_THREADS) void k_scatter(const uint32_t* __rest
     if (PAY) {
         __syncthreads();   // the index image has been streamed out
 #pragma unroll
-        for (int k = 0; k < SCAT_MAX_STEPS; k++) {
+        for (int k = 0; k < MAX_STEPS; k++) {
             if ((uint32_t)k >= steps) break;
             if (key[k] != 0xffffffffu) lidx[pos[k]] = pay[k];
         }
         __syncthreads();
-        for (uint32_t p = threadIdx.x; p < nlocal; p += SCAT_THREADS) pay_out[gdelta[(lkey[p] >> SHIFT) & (BINS - 1)] + p] = lidx[p];
+        for (uint32_t p = threadIdx.x; p < nlocal; p += THREADS) pay_out[gdelta[(lkey[p] >> SHIFT) & (BINS - 1)] + p] = lidx[p];
     }
 #ifdef GSR_KSTAMPS
     __syncthreads();
@@ -561,12 +567,15 @@ inline uint32_t local_sort_grid(uint32_t n) { return (n + LOCAL_CHUNK - 1) / LOC
 // (a 2-D grid -- chunk x bucket, bucket starts handed over by the partition pass, no search -- was measured slower:
 //  3084 mostly empty 1024-thread workgroups cost more to dispatch than the search saves: 13.7 -> 21.0 us on C3)
 
-__global__ __launch_bounds__(LOCAL_THREADS) void k_local_sort(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ idx,
+template <int WAVES>
+__global__ __launch_bounds__(WAVES * WAVE) void k_local_sort(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ idx,
                                                               const uint4* __restrict__ chunk_tab,
                                                               uint32_t* __restrict__ depth_index,
                                                               const uint32_t* __restrict__ pay_in, uint32_t* __restrict__ pay_out)
 {
     constexpr int BINS = RADIX_LO_BINS;
+    constexpr int LOCAL_THREADS = WAVES * WAVE, LOCAL_WAVES = WAVES, LOCAL_STEPS = (int)LOCAL_CHUNK / LOCAL_THREADS;   // 4 or 8 steps of 64 keys per wave
+    static_assert(BINS <= LOCAL_THREADS && LOCAL_STEPS * LOCAL_THREADS == (int)LOCAL_CHUNK, "one digit per thread, whole steps");
     __shared__ uint32_t cnt[LOCAL_WAVES][BINS];   // per wave: counts of my chunk, then keys of the digit in earlier waves
     __shared__ uint32_t tot[BINS];                // digit counts of the bucket behind my chunk, then the digit's first position
     __shared__ uint32_t bef[BINS];                // digit counts of the chunks in front of mine
@@ -660,7 +669,7 @@ __global__ __launch_bounds__(LOCAL_THREADS) void k_local_sort(const uint32_t* __
     }
 }
 
-void launch_sort(const SortBuffers& b, uint32_t n, hipStream_t s)
+void launch_sort(const SortBuffers& b, uint32_t n, hipStream_t s, uint32_t front_waves)
 {
     if (!n) return;
     const dim3 grid(b.nblocks), block(SORT_THREADS);
@@ -686,6 +695,10 @@ void launch_sort(const SortBuffers& b, uint32_t n, hipStream_t s)
                                       (int)scatter_lds_bytes<RADIX_LO_BITS>(SCAT_THREADS * SCAT_MAX_STEPS));
             (void)hipFuncSetAttribute((const void*)k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)scatter_lds_bytes<RADIX_HI_BITS>(SCAT_THREADS * SCAT_MAX_STEPS));
+            (void)hipFuncSetAttribute((const void*)k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, true, false, FRONT_WAVES_NARROW>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)scatter_lds_bytes<RADIX_HI_BITS>(NARROW_KEYS_PER_BLOCK, FRONT_WAVES_NARROW));
+            (void)hipFuncSetAttribute((const void*)k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, true, true, FRONT_WAVES_NARROW>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)scatter_lds_bytes<RADIX_HI_BITS>(NARROW_KEYS_PER_BLOCK, FRONT_WAVES_NARROW));
             (void)hipGetLastError();   // a failure shows up as the launch error
         });
     }
@@ -706,16 +719,24 @@ void launch_sort(const SortBuffers& b, uint32_t n, hipStream_t s)
                            live, b.keys, b.block_hist, RADIX_LO_BITS, RADIX_HI_BINS);
         launch_column_scan(b.block_hist, total_hi, RADIX_HI_BINS, b.nblocks, s, live, b.keys_per_block);
         uint4* tab = reinterpret_cast<uint4*>(b.chunk_tab);   // k_local_sort's work list, written by the partition pass's first workgroup
-        if (b.rects_out)
-            hipLaunchKernelGGL((k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, true, true>), grid, dim3(SCAT_THREADS), lds_hi, s, (const uint32_t*)b.keys,
-                               (const uint32_t*)band_idx, n, b.count, b.keys_per_block, (const uint32_t*)b.block_hist,
-                               (const uint32_t*)total_hi, b.keys_tmp, b.idx_tmp, b.max_bucket, b.rect, b.rect_tmp, tab);
+        // the narrow forms: same grid, same blocks, same table rows, half the waves per workgroup
+        const bool narrow = front_waves == FRONT_WAVES_NARROW && b.keys_per_block == NARROW_KEYS_PER_BLOCK;
+#define GSR_LAUNCH_PARTITION(PAY, W, PAY_IN, PAY_OUT)                                                                                          \
+    hipLaunchKernelGGL((k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, true, PAY, W>), grid, dim3(W * WAVE),                                          \
+                       scatter_lds_bytes<RADIX_HI_BITS>(b.keys_per_block, W), s, (const uint32_t*)b.keys, (const uint32_t*)band_idx, n, b.count, \
+                       b.keys_per_block, (const uint32_t*)b.block_hist, (const uint32_t*)total_hi, b.keys_tmp, b.idx_tmp, b.max_bucket,       \
+                       (const uint32_t*)(PAY_IN), (uint32_t*)(PAY_OUT), tab)
+        if (b.rects_out && narrow) GSR_LAUNCH_PARTITION(true, FRONT_WAVES_NARROW, b.rect, b.rect_tmp);
+        else if (b.rects_out) GSR_LAUNCH_PARTITION(true, SCAT_WAVES, b.rect, b.rect_tmp);
+        else if (narrow) GSR_LAUNCH_PARTITION(false, FRONT_WAVES_NARROW, nullptr, nullptr);
+        else GSR_LAUNCH_PARTITION(false, SCAT_WAVES, nullptr, nullptr);
+#undef GSR_LAUNCH_PARTITION
+        if (narrow)
+            hipLaunchKernelGGL(k_local_sort<FRONT_WAVES_NARROW>, dim3(local_sort_grid(n)), dim3(FRONT_WAVES_NARROW * WAVE), 0, s, (const uint32_t*)b.keys_tmp,
+                               (const uint32_t*)b.idx_tmp, (const uint4*)tab, b.depth_index, (const uint32_t*)b.rect_tmp, b.rects_out);
         else
-            hipLaunchKernelGGL((k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, true>), grid, dim3(SCAT_THREADS), lds_hi, s, (const uint32_t*)b.keys,
-                               (const uint32_t*)band_idx, n, b.count, b.keys_per_block, (const uint32_t*)b.block_hist,
-                               (const uint32_t*)total_hi, b.keys_tmp, b.idx_tmp, b.max_bucket, (const uint32_t*)nullptr, (uint32_t*)nullptr, tab);
-        hipLaunchKernelGGL(k_local_sort, dim3(local_sort_grid(n)), dim3(LOCAL_THREADS), 0, s, (const uint32_t*)b.keys_tmp,
-                           (const uint32_t*)b.idx_tmp, (const uint4*)tab, b.depth_index, (const uint32_t*)b.rect_tmp, b.rects_out);
+            hipLaunchKernelGGL(k_local_sort<SCAT_WAVES>, dim3(local_sort_grid(n)), dim3(SCAT_THREADS), 0, s, (const uint32_t*)b.keys_tmp,
+                               (const uint32_t*)b.idx_tmp, (const uint4*)tab, b.depth_index, (const uint32_t*)b.rect_tmp, b.rects_out);
         return;
     }
     hipLaunchKernelGGL(k_quantise_hist, grid, block, 0, s, depth_in, b.slots, b.minmax, n, b.keys_per_block,
