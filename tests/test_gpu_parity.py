@@ -173,8 +173,9 @@ def test_image_odd_size_and_empty_scene(gh, oracle, scenes):
 
 
 def test_large_framebuffer_sliced_binning(gh, oracle, scenes):
-    # above 4K the bin grid (192 x 101 bins here) no longer fits one workgroup's LDS: the count pass runs in row
-    # slices and the scatter pass in 64x36-bin sub-grids; same image, same permutation
+    # above 4096 bins the binning runs in two levels (cells of 4 x 4 bins, then every cell list's chunks into the cell's bins):
+    # 192 x 101 bins = 48 x 26 cells here, k_cell_scatter1<8>; same image, same permutation.  (The one-level pass that cuts such
+    # a grid into sub-grids and count row slices runs only with GSR_BIN_TWO_LEVEL=0: tests/test_gpu_bin_lists.py.)
     W, H = 6144, 3216
     rows, data, pos = scenes(30000, 33)
     cam = gh.orbit_camera(17, width=W, height=H, fx=3600.0)
@@ -183,12 +184,21 @@ def test_large_framebuffer_sliced_binning(gh, oracle, scenes):
     assert st["visible"] == V and st["tile_entries"] == D
     err = np.abs(img.astype(np.float64) - oimg.astype(np.float64)).max()
     assert err <= TOL_EXACT, err
-    # the largest framebuffer the ABI accepts renders too (256 x 256 bins)
+    # the largest framebuffer the ABI accepts renders too (256 x 256 bins = 64 x 64 cells, the only grid of k_cell_scatter1<4>):
+    # its lists are the reference's, entry for entry
+    import bin_reference
     r = gh.HIPRenderer(8192, 8192)
     r.set_raw_scene(data, pos)
-    r.set_camera(gh.orbit_camera(17, width=8192, height=8192, fx=4800.0))
+    cam = gh.orbit_camera(17, width=8192, height=8192, fx=4800.0)
+    r.set_camera(cam)
     r.render_async(); r.sync()
     assert r.stats()["visible"] > 0 and r.bin_totals().shape == (256, 256)
+    v, p, vp = cam.f32()
+    obbox = oracle.project(data, v, p, cam.fx, cam.fy, 8192, 8192)[1]
+    want_starts, want_list = bin_reference.bin_lists_reference(obbox, oracle.sort(vp, pos)[0], 8192, 8192)
+    starts, lst = r.bin_lists()
+    assert bin_reference.first_difference(starts, lst, want_starts, want_list, obbox) is None
+    assert r.stats()["visible"] == bin_reference.visible_reference(obbox, 8192, 8192) and r.stats()["bin_entries"] == want_list.size > 0
     r.dispose()
 
 
