@@ -48,6 +48,7 @@ Knobs read_knobs(std::string& bad)
         if (end != e && *end == 0 && (v == (long)FRONT_WAVES_NARROW || v == (long)FRONT_WAVES_WIDE)) k.front_waves = (uint32_t)v;
         else bad = std::string("GSR_FRONT_WAVES must be ") + std::to_string(FRONT_WAVES_NARROW) + " or " + std::to_string(FRONT_WAVES_WIDE) + ", not \"" + e + "\"";
     }
+    if (const char* e = getenv("GSR_DEPTH_SKIP")) k.depth_skip = atoi(e) != 0;
     return k;
 }
 

@@ -91,6 +91,7 @@ struct Knobs {
     uint32_t seg_len = 0;        // GSR_SEG_LEN: entries per compositor work item, a multiple of 256 (0: the built-in length)
     uint32_t sort_kpb = 0;       // GSR_SORT_KPB: keys per radix workgroup, 2048, 4096 or 8192 (0: by the scene's size)
     uint32_t front_waves = 0;    // GSR_FRONT_WAVES=8|16: waves per workgroup of the heavy front-end kernels (0: by the kind of context)
+    bool depth_skip = true;      // GSR_DEPTH_SKIP=0: the depth pass visits every entry in every tile (no skip of entries that cannot reach a tile)
 };
 
 // The scene's per-splat arrays: everything the on-device build, the transforms and the compaction move together.
@@ -151,6 +152,8 @@ struct gsr_ctx {
     gsr::CamParams cam{};
     gsr::CamParams cam_frame{};       // the camera of the last rendered frame
     bool have_cam = false, have_frame = false, have_sort = false;
+    uint64_t frame_serial = 0;        // render frames enqueued so far (the depth pass remembers which one its planes belong to)
+    bool frame_lists = false;         // the last render frame's bin lists are still what the bin buffers hold (alloc_bins drops it)
     hipEvent_t link_ev[2] = {nullptr, nullptr};  // gsr_stream_order
 
     struct Scene {   // gsr_scene.cpp
@@ -259,6 +262,19 @@ struct gsr_ctx {
         bool frame8_valid = false;
         bool joined() const { return nccl || fn; }
     } comm;
+
+    // depth planes and picking (gsr_depth.cpp); nothing is allocated until the first call that needs it
+    struct Depth {
+        gsr::DevBuf<float> mean, hit;
+        gsr::DevBuf<uint32_t> index;
+        size_t pixels = 0;                  // pixels the planes hold
+        gsr::DevBuf<int32_t> query;         // gsr_pick: MAX_PICKS (x, y) pairs
+        gsr::DevBuf<gsr::PickResult> result;
+        gsr::DevBuf<uint32_t> invalid;      // [0] the planes pass, [1] the pick pass: 1 = it refused a frame whose lists did not fit
+        float hit_alpha = 0.5f;
+        uint64_t planes_serial = 0;         // frame_serial of the frame the planes were enqueued behind (0: none, or hit_alpha changed)
+        int fill_key[4] = {0, 0, 0, 0};     // band contexts: W, H and bin columns the planes' other columns were last filled for
+    } depth;
 
     // frame delivery (gsr_delivery_open): a ring of pinned host blocks, each with its device staging and "copy done" event
     struct Delivery {

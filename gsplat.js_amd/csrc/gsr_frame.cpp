@@ -350,6 +350,7 @@ namespace gsr {
 int alloc_bins(gsr_ctx* c)
 {
     if (!c->W) return GSR_OK;
+    c->frame_lists = false;   // (grid, lists or work items change: what the last frame left in them is not walked again)
     gsr_ctx::Bin& b = c->bin;
     const Knobs& k = c->knobs;
     const BinGrid g = make_grid(c);
@@ -519,6 +520,7 @@ int enqueue_frame(gsr_ctx* c, bool render)
     t.render = render;
     c->have_sort = true;
     c->have_frame = c->have_frame || render;
+    if (render) { c->frame_serial++; c->frame_lists = true; }
     return GSR_OK;
 }
 

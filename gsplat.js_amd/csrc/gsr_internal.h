@@ -293,6 +293,24 @@ __device__ __forceinline__ uint32_t to_rgba8(float4 v)
 constexpr int DELIVER_TRAILER_WORDS = 4;
 void launch_deliver_rgba8(const float4* fb, uint32_t* staging, int32_t W, int32_t H, uint64_t serial, const uint32_t* overflow, hipStream_t s);
 
+// Depth planes and picking (k_depth.hip): the last frame's bin lists walked once more for depth instead of colour.
+struct DepthBuffers {
+    const uint32_t* bin_start;   // nbins + 1
+    const uint32_t* list;
+    const Record* rec;
+    const float *px, *py, *pz;   // the scene's positions (a splat's depth is computed from them and the frame's camera)
+    const uint32_t* overflow;    // the frame's overflow word: non-zero = its lists did not fit, nothing of it may be walked
+    uint32_t* invalid;           // out: 1 when the pass refused the frame (nothing written), 0 otherwise
+    float* mean; float* hit; uint32_t* index;   // the planes, W x H each (null for k_pick)
+    uint32_t capacity;           // entries the list can hold
+    uint32_t nsplats;
+    float hit_alpha;
+};
+struct PickResult { uint32_t index; float depth, mean, alpha; };   // gsr_pick_result
+void launch_depth_planes(const DepthBuffers& b, const BinGrid& g, const CamParams& cam, bool skip, hipStream_t s);
+void launch_pick(const DepthBuffers& b, const BinGrid& g, const CamParams& cam, const int32_t* xy, uint32_t count, PickResult* out, hipStream_t s);
+void launch_depth_fill(float* mean, float* hit, uint32_t* index, uint32_t npix, hipStream_t s);
+
 // multi-GPU exchange helpers (RGBA8 slabs of the all-gather)
 constexpr int MAX_SLABS = 16;
 struct SlabEdges { int32_t x0[MAX_SLABS], x1[MAX_SLABS]; };

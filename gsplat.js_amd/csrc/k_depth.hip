@@ -1,0 +1,277 @@
+// Depth planes and picking: the last frame's bin lists walked once more, writing depth instead of colour.
+//
+// For a pixel, its fragments are the entries of its bin's list, in list order, that pass the compositor's coverage test
+// (|vPosition|^2 <= 4, the same f32 expression as k_blend's walk), with weight B = exp2(-q log2(e) + log2(opacity)); z of
+// a splat is the w of its centre's clip position, the unfused sums of k_project_key.  Sequentially, from T = 1, D = 0:
+//     w = T * B;  D = fma(w, z, D);  T = T - w;  the first fragment with 1 - T >= hit_alpha is the pixel's hit.
+// Three planes: mean (D, premultiplied like the colour channels), hit (z of the hit, +inf without one) and index (the hit's
+// splat index, 0xffffffff without one).
+//
+// k_depth_planes: one workgroup per bin, from the list's first entry to its last: no work items, no segments, no partials,
+// no saturation skip -- the recurrence above is literally what runs, so the planes do not depend on how the compositor cut
+// the frame.  k_pick: one wave per query pixel, the same recurrence in the same order.  Both go through depth_weight /
+// depth_accumulate below, and through nothing else, for a fragment.
+//
+// Compiled with -ffp-contract=off like the rest of the device code: the fused multiply-adds are the explicit ones.
+#include "gsr_internal.h"
+
+namespace gsr {
+
+GSR_BOUNDS_DECL(depth)   // sites: 0 bin -> bin_start, 1 list position, 2 splat index in the list, 3 LDS cell, 4 query pixel
+constexpr int DEPTH_THREADS = 256;
+constexpr int DEPTH_CHUNK = DEPTH_THREADS;
+constexpr float DEPTH_LOG2E = 1.4426950408889634f;
+constexpr uint32_t HIT_NONE = 0xffffffffu;
+
+struct DepthPixel {
+    float T, D, hit_z;
+    uint32_t hit;
+};
+__device__ __forceinline__ DepthPixel depth_pixel_start()
+{
+    return DepthPixel{1.0f, 0.0f, __uint_as_float(0x7f800000u), HIT_NONE};
+}
+
+// One entry as the walk reads it: the record folded to bin-relative form (k_blend's staging: o = centre of the bin's first pixel),
+// the splat's depth and its index.
+struct DepthEntry {
+    float ux, uy, ncu, wx, wy, ncw, la, z;
+    uint32_t index;
+};
+
+// z of a splat: w of projection * (view * (x, y, z, 1)), k_project_key's sums term by term
+__device__ __forceinline__ float depth_of(const CamParams& cam, float x, float y, float z)
+{
+    float camv[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        float s = cam.view[0 * 4 + r] * x;
+        s = s + cam.view[1 * 4 + r] * y;
+        s = s + cam.view[2 * 4 + r] * z;
+        s = s + cam.view[3 * 4 + r];
+        camv[r] = s;
+    }
+    float s = cam.proj[0 * 4 + 3] * camv[0];
+    s = s + cam.proj[1 * 4 + 3] * camv[1];
+    s = s + cam.proj[2 * 4 + 3] * camv[2];
+    s = s + cam.proj[3 * 4 + 3] * camv[3];
+    return s;
+}
+
+__device__ __forceinline__ DepthEntry depth_entry(const Record* __restrict__ rec, const float* __restrict__ px, const float* __restrict__ py,
+                                                  const float* __restrict__ pz, uint32_t i, const CamParams& cam, float bx0c, float by0c)
+{
+    const float4* rp = reinterpret_cast<const float4*>(rec + i);
+    const float4 ra = rp[0], rb = rp[1];   // (cx, cy, ux, uy), (wx, wy, la, rgb8)
+    const float cxr = ra.x - bx0c, cyr = ra.y - by0c;
+    DepthEntry e;
+    e.ux = ra.z; e.uy = ra.w; e.ncu = -__builtin_fmaf(ra.w, cyr, ra.z * cxr);
+    e.wx = rb.x; e.wy = rb.y; e.ncw = -__builtin_fmaf(rb.y, cyr, rb.x * cxr);
+    e.la = rb.z;
+    e.z = depth_of(cam, px[i], py[i], pz[i]);
+    e.index = i;
+    return e;
+}
+
+// THE per-fragment arithmetic, in two steps so that k_pick can evaluate the weights of 64 entries across its lanes and still
+// apply them one after the other: the weight B of an entry at the pixel (pxf, pyf) (bin-relative, small exact integers), or a
+// negative value where the fragment is discarded ...
+__device__ __forceinline__ float depth_weight(const DepthEntry& e, float pxf, float ur, float wr)
+{
+    const float vx = __builtin_fmaf(e.ux, pxf, ur), vy = __builtin_fmaf(e.wx, pxf, wr);
+    const float q = __builtin_fmaf(vy, vy, vx * vx);
+    return q <= 4.0f ? __builtin_amdgcn_exp2f(__builtin_fmaf(q, -DEPTH_LOG2E, e.la)) : -1.0f;
+}
+// ... and the recurrence
+__device__ __forceinline__ void depth_accumulate(DepthPixel& p, float B, float z, uint32_t index, float hit_alpha)
+{
+    if (B >= 0.0f) {
+        const float w = p.T * B;
+        p.D = __builtin_fmaf(w, z, p.D);
+        p.T = p.T - w;
+        if (p.hit == HIT_NONE && 1.0f - p.T >= hit_alpha) { p.hit = index; p.hit_z = z; }
+    }
+}
+// the row terms of vPosition, shared by the pixels of a row: uy * py - dot(u, c), wy * py - dot(w, c)
+__device__ __forceinline__ float depth_row_u(const DepthEntry& e, float pyf) { return __builtin_fmaf(e.uy, pyf, e.ncu); }
+__device__ __forceinline__ float depth_row_w(const DepthEntry& e, float pyf) { return __builtin_fmaf(e.wy, pyf, e.ncw); }
+
+// SKIP: a wave leaves out the entries that provably cannot reach its 16x16 tile -- a conservative test at staging, k_blend's
+// quadrant test at tile size: the tile's pixel centres lie outside the oriented box |vPosition.x|, |vPosition.y| <= 2
+// (separating axes u and w), or farther from the centre than the longer semi-axis.  Every fragment left out has q > 4, so the
+// planes are bit-identical with and without it (GSR_DEPTH_SKIP=0 is the build of the same walk that visits every entry).
+template <bool SKIP>
+__global__ __launch_bounds__(DEPTH_THREADS) void k_depth_planes(DepthBuffers a, BinGrid g, CamParams cam)
+{
+    __shared__ float4 s_a[DEPTH_CHUNK];       // ux, uy, ncu, wx
+    __shared__ float4 s_b[DEPTH_CHUNK];       // wy, ncw, la, z
+    __shared__ uint32_t s_idx[DEPTH_CHUNK];
+    __shared__ uint32_t s_tiles[DEPTH_CHUNK]; // one bit per tile of the bin the entry can reach
+
+    // A frame whose lists did not fit published no work (k_bin_finalize): nothing of it is walked, nothing is written, and the
+    // host learns at its next synchronisation that the planes are not this frame's.
+    const bool unfit = *a.overflow != 0u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *a.invalid = unfit ? 1u : 0u;
+    if (unfit) return;
+
+    const int nbxb = g.bx_hi - g.bx_lo;
+    const int bin = blockIdx.x;
+    GSR_BOUND(depth, 0, bin, nbxb * g.nby);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lx = lane & 7, ly = lane >> 3;
+    const int by = bin / nbxb, bxl = bin - by * nbxb;
+    const int binX0 = (g.bx_lo + bxl) * BIN_PX, binY0 = by * BIN_PX;
+    const int ox = (wave & 1) * TILE, oy = (wave >> 1) * TILE;
+    const float pxf0 = (float)(ox + lx), pxf1 = pxf0 + 8.0f;
+    const float pyf0 = (float)(oy + ly), pyf1 = pyf0 + 8.0f;
+    const float bx0c = (float)binX0 + 0.5f, by0c = (float)binY0 + 0.5f;
+
+    const uint32_t end = min(a.bin_start[bin + 1], a.capacity), begin = min(a.bin_start[bin], end);
+    GSR_BOUND(depth, 1, a.bin_start[bin + 1], (unsigned long long)a.capacity + 1ull);
+    GSR_BOUND(depth, 1, a.bin_start[bin], (unsigned long long)a.bin_start[bin + 1] + 1ull);
+
+    DepthPixel p00 = depth_pixel_start(), p10 = p00, p01 = p00, p11 = p00;   // pij: pixel (x + 8i, y + 8j)
+
+    for (uint32_t base = begin; base < end; base += DEPTH_CHUNK) {
+        __syncthreads();   // the previous chunk is consumed
+        const uint32_t e = base + threadIdx.x;
+        uint32_t tiles = 0;
+        if (e < end) {
+            GSR_BOUND(depth, 1, e, a.capacity);
+            GSR_BOUND(depth, 2, a.list[e], a.nsplats);
+            const uint32_t i = min(a.list[e], a.nsplats - 1u);
+            const DepthEntry en = depth_entry(a.rec, a.px, a.py, a.pz, i, cam, bx0c, by0c);
+            s_a[threadIdx.x] = make_float4(en.ux, en.uy, en.ncu, en.wx);
+            s_b[threadIdx.x] = make_float4(en.wy, en.ncw, en.la, en.z);
+            s_idx[threadIdx.x] = en.index;
+            tiles = 0xfu;
+            if (SKIP) {
+                // vPosition at a tile's centre (pixel offset 7.5 from its first pixel centre) and how far it can move over the
+                // tile's pixel centres (7.5 each way); the slack covers the rounding of these sums
+                const float eu = 7.5f * (fabsf(en.ux) + fabsf(en.uy)) + 2.0005f;
+                const float ew = 7.5f * (fabsf(en.wx) + fabsf(en.wy)) + 2.0005f;
+                const float minlen2 = fminf(en.ux * en.ux + en.uy * en.uy, en.wx * en.wx + en.wy * en.wy);
+                const Record* r = a.rec + i;
+                tiles = 0;
+#pragma unroll
+                for (int t = 0; t < 4; t++) {
+                    const float dx = ((float)(binX0 + (t & 1) * TILE) + 8.0f) - r->cx, dy = ((float)(binY0 + (t >> 1) * TILE) + 8.0f) - r->cy;
+                    const float ddx = fmaxf(fabsf(dx) - 7.5f, 0.0f), ddy = fmaxf(fabsf(dy) - 7.5f, 0.0f);
+                    const bool reach = fabsf(en.ux * dx + en.uy * dy) <= eu && fabsf(en.wx * dx + en.wy * dy) <= ew &&
+                                       (ddx * ddx + ddy * ddy) * minlen2 <= 4.002f;
+                    if (reach) tiles |= 1u << t;
+                }
+            }
+        }
+        s_tiles[threadIdx.x] = tiles;
+        __syncthreads();
+
+        const uint32_t cnt = min((uint32_t)DEPTH_CHUNK, end - base);
+        for (uint32_t c0 = 0; c0 < cnt; c0 += WAVE) {
+            // my tile's entries among these 64, in list order (entries behind the list's end carry no bit)
+            uint64_t bal = __ballot(((s_tiles[c0 + lane] >> wave) & 1u) != 0u);
+            while (bal) {
+                const uint32_t cell = c0 + (uint32_t)__builtin_ctzll(bal);
+                bal &= bal - 1ull;
+                GSR_BOUND(depth, 3, cell, DEPTH_CHUNK);
+                const float4 ra = s_a[cell], rb = s_b[cell];   // the same address in every lane: a broadcast
+                DepthEntry en;
+                en.ux = ra.x; en.uy = ra.y; en.ncu = ra.z; en.wx = ra.w; en.wy = rb.x; en.ncw = rb.y; en.la = rb.z; en.z = rb.w;
+                en.index = s_idx[cell];
+                const float ur0 = depth_row_u(en, pyf0), wr0 = depth_row_w(en, pyf0);
+                const float ur1 = depth_row_u(en, pyf1), wr1 = depth_row_w(en, pyf1);
+                depth_accumulate(p00, depth_weight(en, pxf0, ur0, wr0), en.z, en.index, a.hit_alpha);
+                depth_accumulate(p10, depth_weight(en, pxf1, ur0, wr0), en.z, en.index, a.hit_alpha);
+                depth_accumulate(p01, depth_weight(en, pxf0, ur1, wr1), en.z, en.index, a.hit_alpha);
+                depth_accumulate(p11, depth_weight(en, pxf1, ur1, wr1), en.z, en.index, a.hit_alpha);
+            }
+        }
+    }
+
+    const int x0 = binX0 + ox + lx, x1 = x0 + 8, y0 = binY0 + oy + ly, y1 = y0 + 8;
+    auto store = [&](int x, int y, const DepthPixel& p) {
+        if (x < g.W && y < g.H) {
+            const size_t o = (size_t)y * g.W + x;
+            a.mean[o] = p.D; a.hit[o] = p.hit_z; a.index[o] = p.hit;
+        }
+    };
+    store(x0, y0, p00); store(x1, y0, p10); store(x0, y1, p01); store(x1, y1, p11);
+}
+
+// One wave per query pixel: 64 entries of the pixel's bin list per step, every lane the weight and z of its entry, then the
+// recurrence over the covering entries one after the other in list order (never a scan: the association is the planes kernel's).
+__global__ __launch_bounds__(WAVE) void k_pick(DepthBuffers a, BinGrid g, CamParams cam, const int32_t* __restrict__ xy, uint32_t count,
+                                               PickResult* __restrict__ out)
+{
+    const bool unfit = *a.overflow != 0u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *a.invalid = unfit ? 1u : 0u;
+    if (unfit) return;
+    const uint32_t qi = blockIdx.x;
+    if (qi >= count) return;
+    const int nbxb = g.bx_hi - g.bx_lo;
+    const int lane = threadIdx.x;
+    // (the host refuses pixels outside the image or the band; the clamp keeps every index below in range whatever arrives)
+    const int xlo = g.bx_lo * BIN_PX, xhi = min(g.bx_hi * BIN_PX, g.W) - 1;
+    GSR_BOUND(depth, 4, xy[2 * qi] - xlo, xhi - xlo + 1);
+    GSR_BOUND(depth, 4, xy[2 * qi + 1], g.H);
+    const int x = min(max(xy[2 * qi], xlo), xhi), y = min(max(xy[2 * qi + 1], 0), g.H - 1);
+    const int bxl = x / BIN_PX - g.bx_lo, by = y / BIN_PX;
+    const int bin = by * nbxb + bxl;
+    GSR_BOUND(depth, 0, bin, nbxb * g.nby);
+    const int binX0 = (g.bx_lo + bxl) * BIN_PX, binY0 = by * BIN_PX;
+    const float pxf = (float)(x - binX0), pyf = (float)(y - binY0);
+    const float bx0c = (float)binX0 + 0.5f, by0c = (float)binY0 + 0.5f;
+    const uint32_t end = min(a.bin_start[bin + 1], a.capacity), begin = min(a.bin_start[bin], end);
+
+    DepthPixel p = depth_pixel_start();
+    for (uint32_t base = begin; base < end; base += WAVE) {
+        const uint32_t e = base + lane;
+        float B = -1.0f, z = 0.0f;
+        uint32_t index = 0;
+        if (e < end) {
+            GSR_BOUND(depth, 1, e, a.capacity);
+            GSR_BOUND(depth, 2, a.list[e], a.nsplats);
+            const uint32_t i = min(a.list[e], a.nsplats - 1u);
+            const DepthEntry en = depth_entry(a.rec, a.px, a.py, a.pz, i, cam, bx0c, by0c);
+            B = depth_weight(en, pxf, depth_row_u(en, pyf), depth_row_w(en, pyf));
+            z = en.z; index = en.index;
+        }
+        uint64_t bal = __ballot(B >= 0.0f);
+        while (bal) {
+            const int j = __builtin_ctzll(bal);
+            bal &= bal - 1ull;
+            depth_accumulate(p, __shfl(B, j), __shfl(z, j), __shfl(index, j), a.hit_alpha);
+        }
+    }
+    if (lane == 0) out[qi] = PickResult{p.hit, p.hit_z, p.D, 1.0f - p.T};
+}
+
+// the planes of pixels no bin of the context covers (a band context's other columns): 0 / +inf / none
+__global__ void k_depth_fill(float* __restrict__ mean, float* __restrict__ hit, uint32_t* __restrict__ index, uint32_t npix)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    mean[i] = 0.0f; hit[i] = __uint_as_float(0x7f800000u); index[i] = HIT_NONE;
+}
+
+void launch_depth_planes(const DepthBuffers& b, const BinGrid& g, const CamParams& cam, bool skip, hipStream_t s)
+{
+    const int nbins = (g.bx_hi - g.bx_lo) * g.nby;
+    if (nbins <= 0) return;
+    if (skip) hipLaunchKernelGGL(k_depth_planes<true>, dim3(nbins), dim3(DEPTH_THREADS), 0, s, b, g, cam);
+    else hipLaunchKernelGGL(k_depth_planes<false>, dim3(nbins), dim3(DEPTH_THREADS), 0, s, b, g, cam);
+}
+
+void launch_pick(const DepthBuffers& b, const BinGrid& g, const CamParams& cam, const int32_t* xy, uint32_t count, PickResult* out, hipStream_t s)
+{
+    if (!count || (g.bx_hi - g.bx_lo) * g.nby <= 0) return;
+    hipLaunchKernelGGL(k_pick, dim3(count), dim3(WAVE), 0, s, b, g, cam, xy, count, out);
+}
+
+void launch_depth_fill(float* mean, float* hit, uint32_t* index, uint32_t npix, hipStream_t s)
+{
+    if (!npix) return;
+    hipLaunchKernelGGL(k_depth_fill, dim3((npix + 255) / 256), dim3(256), 0, s, mean, hit, index, npix);
+}
+
+}  // namespace gsr

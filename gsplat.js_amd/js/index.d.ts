@@ -144,6 +144,21 @@ export class HIPRenderer {
     /** RGBA8, row 0 = top; pass an array of width*height*4 elements to have it filled and returned (no allocation per frame). */
     readPixels(out?: Uint8Array): Uint8Array;
     readPixelsFloat(out?: Float32Array): Float32Array;
+    /** Depth planes of the last rendered frame, width*height each, row 0 = top; pass arrays to have them filled (like
+     *  readPixels(out)), omit a plane to skip it.  Per pixel, over the fragments of its bin's list front to back, from
+     *  T = 1, D = 0: w = T * B; D = fma(w, z, D); T -= w, z being the w of the splat centre's clip position.
+     *  mean: D, premultiplied like the colour channels (divide by the framebuffer's alpha for expected depth);
+     *  hit: z of the first fragment at which 1 - T reaches the hit alpha, Infinity when none does;
+     *  index: that fragment's splat index, 0xffffffff when none. */
+    readDepth(out?: { mean?: Float32Array; hit?: Float32Array; index?: Uint32Array }): { mean?: Float32Array; hit?: Float32Array; index?: Uint32Array };
+    /** enqueue the depth pass behind the frame enqueued last (no host wait); readDepth() runs it itself when needed */
+    depthAsync(): void;
+    /** The splat under pixel (x, y) of the last rendered frame: its index (0xffffffff: none), depth (Infinity: none), the
+     *  pixel's premultiplied mean depth and alpha, and `point`: the pixel centre un-projected to `depth` through the
+     *  active camera -- what to assign to an OrbitControls target; null when nothing is hit. */
+    pick(x: number, y: number): { index: number; depth: number; mean: number; alpha: number; point: Vector3 | null };
+    /** accumulated alpha at which a pixel's hit is taken, in (0, 1]; default 0.5 */
+    setHitAlpha(a: number): void;
     /** Frame delivery: a ring of `slots` (2..8, default 3) pinned RGBA8 frames inside the library.  renderAsync() +
      *  deliverFrame() enqueue a frame and its copy to the host without waiting; acquireFrame() waits for that frame's copy
      *  only, so frame k is presented while k+1 and k+2 render.  Works after joinGroup() too (the gathered frame). */

@@ -634,6 +634,52 @@ napi_value SortHost(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+// ---- depth planes and picking (gsr_depth_async / gsr_read_depth / gsr_pick) ----
+napi_value SetHitAlpha(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    double a;
+    if (!c || !get_f64(env, argv[1], &a)) return nullptr;
+    const int rc = gsr_set_hit_alpha(c, (float)a);
+    return rc ? throw_gsr(env, c, rc, "gsr_set_hit_alpha") : undefined(env);
+}
+
+// readDepth(handle, mean | null, hit | null, index | null, width, height): Float32Array, Float32Array, Uint32Array of width*height
+napi_value ReadDepth(napi_env env, napi_callback_info info)
+{
+    napi_value argv[6];
+    if (!get_args(env, info, 6, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    if (!c) return nullptr;
+    void* plane[3];
+    size_t len[3];
+    int32_t w, h;
+    if (!get_typed(env, argv[1], napi_float32_array, &plane[0], &len[0], true) || !get_typed(env, argv[2], napi_float32_array, &plane[1], &len[1], true) ||
+        !get_typed(env, argv[3], napi_uint32_array, &plane[2], &len[2], true) || !get_i32(env, argv[4], &w) || !get_i32(env, argv[5], &h))
+        return nullptr;
+    for (int k = 0; k < 3; k++)
+        if (plane[k] && len[k] < (size_t)w * h) { napi_throw_range_error(env, nullptr, "plane array is smaller than width*height"); return nullptr; }
+    const int rc = gsr_read_depth(c, (float*)plane[0], (float*)plane[1], (uint32_t*)plane[2]);
+    return rc ? throw_gsr(env, c, rc, "gsr_read_depth") : undefined(env);
+}
+
+// pick(handle, xy: Int32Array of (x, y) pairs, out: Float32Array of 4 per pixel): out holds index (its bits), depth, mean, alpha
+napi_value Pick(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    void *xy, *out;
+    size_t nxy, nout;
+    if (!c || !get_typed(env, argv[1], napi_int32_array, &xy, &nxy) || !get_typed(env, argv[2], napi_float32_array, &out, &nout)) return nullptr;
+    if (nout < nxy / 2 * 4) { napi_throw_range_error(env, nullptr, "output array is smaller than 4 per pixel"); return nullptr; }
+    static_assert(sizeof(gsr_pick_result) == 16, "four words per result");
+    const int rc = gsr_pick(c, (const int32_t*)xy, (uint32_t)(nxy / 2), (gsr_pick_result*)out);
+    return rc ? throw_gsr(env, c, rc, "gsr_pick") : undefined(env);
+}
+
 napi_value Init(napi_env env, napi_value exports)
 {
     struct { const char* name; napi_callback fn; } fns[] = {
@@ -647,6 +693,7 @@ napi_value Init(napi_env env, napi_value exports)
         {"commDestroy", Call0<gsr_comm_destroy>}, {"allgatherFrameAsync", Call0<gsr_allgather_frame_async>}, {"readFrame", ReadFrame},
         {"openDelivery", OpenDelivery}, {"closeDelivery", Call0<gsr_delivery_close>}, {"deliverySlots", DeliverySlots}, {"detachBuffers", DetachBuffers},
         {"deliverFrame", DeliverFrame}, {"frameReady", FrameReady}, {"acquireFrame", AcquireFrame}, {"releaseFrame", ReleaseFrame},
+        {"setHitAlpha", SetHitAlpha}, {"depthAsync", Call0<gsr_depth_async>}, {"readDepth", ReadDepth}, {"pick", Pick},
     };
     for (auto& f : fns) {
         napi_value fn;

@@ -8,6 +8,7 @@
 // There is no CPU fallback: the constructor throws if the addon or a GPU is missing.
 const path = require("path");
 const { FadeInPass } = require("./FadeInPass");
+const { Vector3 } = require("../math/Vector3");
 
 let native = null;
 function loadNative() {
@@ -235,6 +236,35 @@ class HIPRenderer {
             return a;
         };
         this.readPixelsFloat = (out) => { const a = out || new Float32Array(this.width * this.height * 4); this._n.readPixels(this._h, a, this.width, this.height); return a; };
+        // Depth planes and picking (gsr_read_depth / gsr_pick): which splat, and how far away, is under a pixel of the last
+        // rendered frame.  readDepth({mean?, hit?, index?}) fills the caller's arrays (width*height each; Float32Array,
+        // Float32Array, Uint32Array) like readPixels(out) and returns the same object; without an argument all three are
+        // allocated.  mean: sum of T_k B_k z_k, premultiplied like the colour channels; hit: z of the first fragment at
+        // which accumulated alpha reaches the hit alpha (Infinity: none); index: that fragment's splat (0xffffffff: none).
+        this.setHitAlpha = (a) => this._n.setHitAlpha(this._h, a);
+        this.depthAsync = () => this._n.depthAsync(this._h);
+        this.readDepth = (out) => {
+            const np = this.width * this.height;
+            const o = out || { mean: new Float32Array(np), hit: new Float32Array(np), index: new Uint32Array(np) };
+            this._n.readDepth(this._h, o.mean || null, o.hit || null, o.index || null, this.width, this.height);
+            return o;
+        };
+        // pick(x, y) -> { index, depth, alpha, point }: point is the pixel's centre un-projected to `depth` through the active
+        // camera, in doubles -- what a caller assigns to an OrbitControls target; null where nothing is hit
+        const pickXY = new Int32Array(2), pickOut = new Float32Array(4), pickBits = new Uint32Array(pickOut.buffer);
+        this.pick = (x, y) => {
+            pickXY[0] = x; pickXY[1] = y;
+            this._n.pick(this._h, pickXY, pickOut);
+            const index = pickBits[0], depth = pickOut[1];
+            let point = null;
+            if (index !== 0xffffffff && activeCamera) {
+                const v = activeCamera.viewMatrix.buffer, t = activeCamera.position;
+                const cx = (x + 0.5 - this.width / 2) * depth / activeCamera.fx, cy = (y + 0.5 - this.height / 2) * depth / activeCamera.fy;
+                point = new Vector3(v[0] * cx + v[1] * cy + v[2] * depth + t.x, v[4] * cx + v[5] * cy + v[6] * depth + t.y,
+                                    v[8] * cx + v[9] * cy + v[10] * depth + t.z);
+            }
+            return { index, depth, mean: pickOut[2], alpha: pickOut[3], point };
+        };
         this.stats = () => this._n.getTimings(this._h);
         this.deviceInfo = () => this._n.deviceInfo(this._h);
         this.isInitialized = () => initialized;

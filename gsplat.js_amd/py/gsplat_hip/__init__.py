@@ -75,9 +75,11 @@ EXPORTS = [
     "gsr_frame8_device_ptr", "gsr_comm_stream_handle", "gsr_read_work_items", "gsr_comm_share", "gsr_comm_init_custom",
     "gsr_delivery_open", "gsr_delivery_close", "gsr_deliver_frame_async", "gsr_frame_ready", "gsr_acquire_frame",
     "gsr_release_frame", "gsr_delivery_slot_ptr",
+    "gsr_set_hit_alpha", "gsr_depth_async", "gsr_read_depth", "gsr_depth_device_ptr", "gsr_pick",
 ]
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p)
 GSR_COMM_ID_BYTES = 128
+PICK_DTYPE = np.dtype([("index", np.uint32), ("depth", np.float32), ("mean", np.float32), ("alpha", np.float32)])   # gsr_pick_result
 
 
 def _assert_one_hip_runtime():
@@ -184,6 +186,12 @@ def load_library(path=None):
     L.gsr_release_frame.argtypes = [vp, ctypes.c_uint64]
     L.gsr_delivery_slot_ptr.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64)]
     L.gsr_delivery_slot_ptr.restype = vp
+    L.gsr_set_hit_alpha.argtypes = [vp, ctypes.c_float]
+    L.gsr_depth_async.argtypes = [vp]
+    L.gsr_read_depth.argtypes = [vp, vp, vp, vp]
+    L.gsr_depth_device_ptr.argtypes = [vp, ctypes.c_int32]
+    L.gsr_depth_device_ptr.restype = vp
+    L.gsr_pick.argtypes = [vp, vp, ctypes.c_uint32, vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int and name not in ("gsplat_sort_host",):
@@ -527,6 +535,37 @@ class HIPRenderer:
 
     def release(self, serial):
         self._check(self._L.gsr_release_frame(self._ctx, serial))
+
+    # -- depth planes and picking (gsr_depth_async / gsr_read_depth / gsr_pick) --
+    def set_hit_alpha(self, a):
+        """Accumulated alpha at which a pixel's hit is taken, in (0, 1]; default 0.5."""
+        self._check(self._L.gsr_set_hit_alpha(self._ctx, float(a)))
+
+    def depth_async(self):
+        """Enqueue the depth pass behind the frame enqueued last (no host wait)."""
+        self._check(self._L.gsr_depth_async(self._ctx))
+
+    def read_depth(self):
+        """(mean, hit, index) of the last rendered frame, [H, W] each, row 0 = top.  Per pixel, over the fragments of its
+        bin's list front to back (those the compositor's coverage test keeps, with the compositor's weight B), from T = 1,
+        D = 0: w = T * B; D = fma(w, z, D); T -= w, z being the w of the splat centre's clip position.
+        mean (float32): D, premultiplied like the colour channels (divide by the framebuffer's alpha for expected depth);
+        hit (float32): z of the first fragment at which 1 - T reaches hit_alpha, +inf when none does;
+        index (uint32): that fragment's splat index, 0xffffffff when none.
+        Waits for the frame (one that did not fit its lists is rendered again first) and runs the pass if needed."""
+        shape = (self.height, self.width)
+        mean, hit, index = np.empty(shape, np.float32), np.empty(shape, np.float32), np.empty(shape, np.uint32)
+        self._check(self._L.gsr_read_depth(self._ctx, mean.ctypes.data, hit.ctypes.data, index.ctypes.data))
+        return mean, hit, index
+
+    def pick(self, points):
+        """The splat under each pixel of `points` ([(x, y), ...], at most 4096) in the last rendered frame: a structured
+        array with index (uint32, 0xffffffff: none), depth (the hit's z, +inf: none), mean and alpha (= 1 - T) -- the same
+        bits as read_depth() holds for those pixels."""
+        xy = np.ascontiguousarray(points, dtype=np.int32).reshape(-1, 2)
+        out = np.zeros(max(len(xy), 1), dtype=PICK_DTYPE)
+        self._check(self._L.gsr_pick(self._ctx, xy.ctypes.data, len(xy), out.ctypes.data))
+        return out[:len(xy)]
 
     def read_keys(self):
         keys = np.empty(self._n, dtype=np.uint32)

@@ -291,6 +291,35 @@ int gsr_release_frame(gsr_ctx *ctx, uint64_t serial);
  * (an external ArrayBuffer per slot); NULL without a ring.  The pointers change only when the ring is reallocated. */
 void *gsr_delivery_slot_ptr(gsr_ctx *ctx, int32_t slot, uint64_t *bytes);
 
+/* ---- depth and pick: per-pixel depth planes of the last rendered frame, and the splat under a pixel ----
+ * No interface of the reference stands behind this section (its renderer returns colour only, WebGLRenderer.ts:241-296): it
+ * is what a viewer builds "double-click sets the orbit target" and "click selects" from, and what a compositor or a
+ * reprojecting client needs beside the colour.  A separate pass behind the frame on the context's stream, over the bin lists,
+ * records and positions the frame left on the device; the frame, its framebuffer and its statistics are not touched, and a
+ * context that never calls these functions allocates and launches nothing.
+ * Definitions.  A pixel's fragments are the entries of its bin's list, in list order (front to back),
+ * that pass the compositor's coverage test, each with the weight B the compositor gives it; z of a splat is the w of its
+ * centre's clip position for the frame's camera (view-space depth for a perspective camera).  From T = 1, D = 0:
+ *     w = T * B;  D = fma(w, z, D);  T = T - w;  the first fragment with 1 - T >= hit_alpha is the pixel's hit.
+ *   plane 0 "mean",  float:    D = sum of T_k B_k z_k, premultiplied like the colour channels (divide by the framebuffer's alpha)
+ *   plane 1 "hit",   float:    z of the hit; +infinity when accumulated alpha never reaches hit_alpha
+ *   plane 2 "index", uint32_t: the hit's splat index (the index depthIndex and the scene use); 0xffffffff when none
+ * Each plane is width * height, row 0 = top.  Early termination (early_out_eps) does not apply: the pass walks every entry.
+ * A band context defines the planes on its bin columns only; the other columns hold 0 / +infinity / 0xffffffff.
+ * gsr_depth_async enqueues the pass behind the last enqueued frame (legal after gsr_render / gsr_render_async; no host wait).
+ * gsr_read_depth and gsr_pick first do what gsr_sync does for the frame (a frame whose lists did not fit is rendered again),
+ * run the pass if the planes are not the current frame's, then copy; planes enqueued behind a frame that did not fit are
+ * never returned as data.  gsr_pick answers `count` (1..4096) pixels (x, y pairs) without the planes: index, depth (the
+ * hit's z), mean and alpha = 1 - T, bit for bit what the planes and the recurrence hold for those pixels.
+ * GSR_ERR_ARG: no frame rendered yet, the scene, size, band or list buffers changed since the frame, the last frame was
+ * sort-only, a pixel outside the image or the context's band, count 0 or above 4096, hit_alpha outside (0, 1]. */
+typedef struct gsr_pick_result { uint32_t index; float depth; float mean; float alpha; } gsr_pick_result;
+int gsr_set_hit_alpha(gsr_ctx *ctx, float a);                 /* (0, 1], default 0.5 */
+int gsr_depth_async(gsr_ctx *ctx);
+int gsr_read_depth(gsr_ctx *ctx, float *mean, float *hit, uint32_t *index);   /* each may be NULL; blocking */
+void *gsr_depth_device_ptr(gsr_ctx *ctx, int32_t plane);      /* 0 mean, 1 hit, 2 index; NULL until the planes exist */
+int gsr_pick(gsr_ctx *ctx, const int32_t *xy /* count x (x, y) */, uint32_t count, gsr_pick_result *out);   /* blocking */
+
 /* ---- device interop (torch / RCCL plumbing in the harness) ---- */
 void *gsr_framebuffer_device_ptr(gsr_ctx *ctx); /* float4[h][w] on the device */
 void *gsr_stream_handle(gsr_ctx *ctx);          /* hipStream_t */

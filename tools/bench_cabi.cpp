@@ -3,7 +3,9 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--depth] [--pick X,Y]
+// --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
+// and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
 // gsr_deliver_frame_async, gsr_acquire_frame, gsr_release_frame: three slots per context, the oldest frame picked up when the
 // ring is full) -- the header alone is enough to consume frames -- and reports its rate and the checksum of a delivered frame.
@@ -124,6 +126,8 @@ int main(int argc, char** argv)
     std::string config = "C1", rows_path, dump;
     int frames = 240, warmup = 20, in_flight = 3;
     bool deliver = false;
+    bool depth = false, pick = false;
+    int32_t pick_xy[2] = {0, 0};
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : ""; };
@@ -134,7 +138,9 @@ int main(int argc, char** argv)
         else if (a == "--in-flight") in_flight = std::atoi(next());
         else if (a == "--dump") dump = next();
         else if (a == "--deliver") deliver = true;
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver]\n"); return 2; }
+        else if (a == "--depth") depth = true;
+        else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--depth] [--pick X,Y]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
@@ -194,6 +200,30 @@ int main(int argc, char** argv)
         if (f) { std::fwrite(di.data(), 4, di.size(), f); std::fclose(f); }
         f = std::fopen((dump + ".rgba8.bin").c_str(), "wb");
         if (f) { std::fwrite(px.data(), 1, px.size(), f); std::fclose(f); }
+    }
+    // --depth: the orbit again, three legs without and three with the depth pass behind every frame, alternating
+    double depth_sec[2] = {0, 0};
+    if (depth) {
+        for (int leg = 0; leg < 6; leg++) {
+            const bool with = leg & 1;
+            auto depth_step = [&](int k) -> int {
+                if (int rc = step(k)) return rc;
+                return with ? gsr_depth_async(ctx[k % in_flight]) : 0;
+            };
+            for (int k = 0; k < warmup; k++) { ctx0 = ctx[k % in_flight]; CHECK(depth_step(k)); }
+            for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_sync(c)); }
+            const auto d0 = std::chrono::steady_clock::now();
+            for (int k = 0; k < frames; k++) { ctx0 = ctx[(warmup + k) % in_flight]; CHECK(depth_step(warmup + k)); }
+            for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_sync(c)); }
+            depth_sec[with] += std::chrono::duration<double>(std::chrono::steady_clock::now() - d0).count();
+        }
+    }
+    gsr_pick_result picked{};
+    if (pick) {
+        ctx0 = ctx[0];
+        CHECK(gsr_set_camera(ctx[0], poses[0].view, poses[0].proj, poses[0].vp, (float)cfg->fx, (float)cfg->fx));
+        CHECK(gsr_render(ctx[0]));
+        CHECK(gsr_pick(ctx[0], pick_xy, 1, &picked));
     }
     // --deliver: the same orbit with every frame delivered; then pose 0 once more, delivered, against the blocking read above
     double delivered_sec = 0;
@@ -256,6 +286,12 @@ int main(int argc, char** argv)
         std::printf(", \"frames_per_sec_delivered\": %.1f, \"delivery_slots\": 3, \"delivered_rgba8_fnv1a\": \"%016llx\", "
                     "\"delivered_equals_read_pixels\": true, \"sink\": %d",
                     frames / delivered_sec, delivered_hash, (int)(sink & 1));
+    if (depth)
+        std::printf(", \"frames_per_sec_plain\": %.1f, \"frames_per_sec_with_depth\": %.1f, \"depth_legs\": 3",
+                    3.0 * frames / depth_sec[0], 3.0 * frames / depth_sec[1]);
+    if (pick)
+        std::printf(", \"pick\": {\"x\": %d, \"y\": %d, \"index\": %u, \"depth\": %s, \"mean\": %.9g, \"alpha\": %.9g}",
+                    pick_xy[0], pick_xy[1], picked.index, picked.index == 0xffffffffu ? "null" : std::to_string(picked.depth).c_str(), (double)picked.mean, (double)picked.alpha);
     std::printf("}\n");
     for (gsr_ctx* c : ctx) gsr_destroy(c);
     return 0;
