@@ -279,8 +279,8 @@ struct gsr_ctx {
     // frame delivery (gsr_delivery_open): a ring of pinned host blocks, each with its device staging and "copy done" event
     struct Delivery {
         struct Slot {
-            uint8_t* host = nullptr;        // hipHostMalloc: W * H * 4 pixel bytes + the trailer
-            gsr::DevBuf<uint32_t> staging;  // device, same size: k_deliver_rgba8 writes it, the copy reads it
+            uint8_t* host = nullptr;        // hipHostMalloc: the format's payload (RGBA8: W * H * 4 bytes) rounded up to whole words + the trailer
+            gsr::DevBuf<uint32_t> staging;  // device, same size: k_deliver_rgba8 / k_deliver_yuv writes it, the copy reads it
             hipEvent_t done = nullptr;      // recorded behind the slot's copy
             uint64_t serial = 0;
             enum State { FREE, IN_FLIGHT, HELD } state = FREE;
@@ -289,6 +289,8 @@ struct gsr_ctx {
         hipStream_t copy_stream = nullptr;
         hipEvent_t ev_staged = nullptr;     // render stream -> copy stream: the conversion kernel has written the staging buffer
         int W = 0, H = 0;
+        int format = GSR_FORMAT_RGBA8;      // what the ring was opened for (gsr_delivery_open_ex); gsr_resize keeps it
+        gsr::YuvParams yuv{};               // NV12 / I420: the coefficient set and the background
         int next = 0;                       // where the search for a free slot starts: the slots are used in turn
         uint64_t serial = 0;                // the last serial handed out; never restarts
     } delivery;

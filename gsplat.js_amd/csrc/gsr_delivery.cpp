@@ -1,5 +1,6 @@
 // ---------------------------------------------------------------------------------------------------------
-// Frame delivery: finished RGBA8 frames reach the host through a ring of pinned blocks while the next frames render.
+// Frame delivery: finished frames (RGBA8, or 4:2:0 Y'CbCr as NV12 / I420) reach the host through a ring of pinned blocks while the
+// next frames render.
 // A slot is FREE, IN_FLIGHT (gsr_deliver_frame_async took it: kernel and copy are enqueued) or HELD (the host acquired it
 // and reads its pixels).  It becomes FREE again only through the host -- gsr_release_frame, or a gsr_acquire_frame that
 // refuses the frame -- and both come after a wait for the slot's copy: a free slot never has device work outstanding, so
@@ -13,7 +14,23 @@ using namespace gsr;
 
 using DeliverySlot = gsr_ctx::Delivery::Slot;
 
-static inline size_t ring_pixel_bytes(const gsr_ctx* c) { return (size_t)c->delivery.W * c->delivery.H * 4; }
+// the payload of one frame in the ring's format, and where the trailer lies behind it
+static inline size_t ring_pixel_bytes(const gsr_ctx* c)
+{
+    const gsr_ctx::Delivery& d = c->delivery;
+    return d.format == GSR_FORMAT_RGBA8 ? (size_t)d.W * d.H * 4 : yuv420_bytes(d.W, d.H);
+}
+static inline size_t ring_trailer_offset(const gsr_ctx* c) { return (ring_pixel_bytes(c) + 3) & ~(size_t)3; }
+static inline size_t ring_slot_bytes(const gsr_ctx* c) { return ring_trailer_offset(c) + DELIVER_TRAILER_WORDS * 4; }
+
+// BT.709 in 1/256: every chroma row sums to zero, the full-range luma row to 256, so greys are neutral exactly
+static YuvParams yuv_params(bool full_range, const uint8_t* bg)
+{
+    YuvParams k = full_range ? YuvParams{0, {54, 183, 19}, {-29, -99, 128}, {128, -116, -12}, 0, 255, 0}
+                             : YuvParams{16, {47, 157, 16}, {-26, -86, 112}, {112, -102, -10}, 16, 240, 0};
+    k.bg = (uint32_t)bg[0] | ((uint32_t)bg[1] << 8) | ((uint32_t)bg[2] << 16);
+    return k;
+}
 
 bool gsr::delivery_frame_held(const gsr_ctx* c)
 {
@@ -48,14 +65,14 @@ int gsr::delivery_alloc(gsr_ctx* c, int slots)
 {
     delivery_free(c);
     c->delivery.W = c->W; c->delivery.H = c->H;
-    const size_t bytes = ring_pixel_bytes(c) + DELIVER_TRAILER_WORDS * 4;
+    const size_t bytes = ring_slot_bytes(c);
     auto bail = [c](int code) { delivery_free(c); return code; };
     hipError_t e = hipStreamCreateWithFlags(&c->delivery.copy_stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->delivery.ev_staged, hipEventDisableTiming);
     c->delivery.ring.resize((size_t)slots);
     for (DeliverySlot& sl : c->delivery.ring) {
         if (e == hipSuccess) e = hipHostMalloc((void**)&sl.host, bytes, hipHostMallocDefault);
-        if (e == hipSuccess && sl.staging.alloc(c, bytes / 4) != GSR_OK) e = hipErrorOutOfMemory;   // (bytes: pixels + trailer, whole words)
+        if (e == hipSuccess && sl.staging.alloc(c, bytes / 4) != GSR_OK) e = hipErrorOutOfMemory;   // (bytes: payload + trailer, whole words)
         if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
     }
     if (e != hipSuccess) return bail(fail(c, GSR_ERR_HIP, "allocating the delivery ring (%d slots of %zu bytes) failed: %s", slots, bytes, hipGetErrorString(e)));
@@ -75,14 +92,60 @@ static DeliverySlot* find_slot(gsr_ctx* c, uint64_t serial, DeliverySlot::State 
 
 extern "C" {
 
+static int delivery_open_checked(gsr_ctx* c, const char* who, int32_t slots)
+{
+    if (slots < 2 || slots > 8) return fail(c, GSR_ERR_ARG, "%s: %d slots (2..8)", who, slots);
+    if (!c->W || !c->H) return fail(c, GSR_ERR_ARG, "%s: set the framebuffer size first", who);
+    if (delivery_frame_held(c)) return fail(c, GSR_ERR_ARG, "%s: a delivered frame is held (gsr_release_frame first)", who);
+    return GSR_OK;
+}
+
 int gsr_delivery_open(gsr_ctx* c, int32_t slots)
 {
     if (!c) return GSR_ERR_ARG;
-    if (slots < 2 || slots > 8) return fail(c, GSR_ERR_ARG, "gsr_delivery_open: %d slots (2..8)", slots);
-    if (!c->W || !c->H) return fail(c, GSR_ERR_ARG, "gsr_delivery_open: set the framebuffer size first");
-    if (delivery_frame_held(c)) return fail(c, GSR_ERR_ARG, "gsr_delivery_open: a delivered frame is held (gsr_release_frame first)");
+    if (int r = delivery_open_checked(c, "gsr_delivery_open", slots)) return r;
     HIP_TRY(c, hipSetDevice(c->device));
+    c->delivery.format = GSR_FORMAT_RGBA8;
     return delivery_alloc(c, slots);
+}
+
+int gsr_delivery_open_ex(gsr_ctx* c, const gsr_delivery_options* opt)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (!opt) return fail(c, GSR_ERR_ARG, "gsr_delivery_open_ex: options are NULL");
+    if (opt->format != GSR_FORMAT_RGBA8 && opt->format != GSR_FORMAT_NV12 && opt->format != GSR_FORMAT_I420)
+        return fail(c, GSR_ERR_ARG, "gsr_delivery_open_ex: unknown format %d (GSR_FORMAT_RGBA8, GSR_FORMAT_NV12, GSR_FORMAT_I420)", opt->format);
+    if (!c->delivery.ring.empty()) return fail(c, GSR_ERR_ARG, "gsr_delivery_open_ex: a delivery ring is open (gsr_delivery_close first)");
+    if (int r = delivery_open_checked(c, "gsr_delivery_open_ex", opt->slots)) return r;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->delivery.format = opt->format;
+    c->delivery.yuv = yuv_params(opt->full_range != 0, opt->background);
+    return delivery_alloc(c, opt->slots);
+}
+
+int gsr_delivery_layout(gsr_ctx* c, gsr_frame_layout* out)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (!out) return fail(c, GSR_ERR_ARG, "gsr_delivery_layout: out is NULL");
+    if (c->delivery.ring.empty()) return fail(c, GSR_ERR_ARG, "gsr_delivery_layout: no delivery ring (gsr_delivery_open)");
+    const gsr_ctx::Delivery& d = c->delivery;
+    const int32_t W = d.W, H = d.H, Wc = (W + 1) / 2, Hc = (H + 1) / 2;
+    *out = gsr_frame_layout{};
+    out->format = d.format; out->width = W; out->height = H;
+    out->bytes = ring_pixel_bytes(c);
+    out->stride[0] = W; out->rows[0] = H;
+    if (d.format == GSR_FORMAT_RGBA8) {
+        out->planes = 1;
+        out->stride[0] = W * 4;
+    } else if (d.format == GSR_FORMAT_NV12) {
+        out->planes = 2;
+        out->offset[1] = (uint64_t)W * H; out->stride[1] = 2 * Wc; out->rows[1] = Hc;
+    } else {
+        out->planes = 3;
+        out->offset[1] = (uint64_t)W * H; out->offset[2] = out->offset[1] + (uint64_t)Wc * Hc;
+        out->stride[1] = out->stride[2] = Wc; out->rows[1] = out->rows[2] = Hc;
+    }
+    return GSR_OK;
 }
 
 int gsr_delivery_close(gsr_ctx* c)
@@ -111,9 +174,18 @@ int gsr_deliver_frame_async(gsr_ctx* c, uint64_t* serial)
     if (!sl) return fail(c, GSR_ERR_BUSY, "gsr_deliver_frame_async: all %d delivery slots are in flight or held (gsr_acquire_frame / gsr_release_frame)", slots);
     HIP_TRY(c, hipSetDevice(c->device));
     const uint64_t k = c->delivery.serial + 1;
-    const size_t bytes = ring_pixel_bytes(c) + DELIVER_TRAILER_WORDS * 4;
+    const size_t bytes = ring_slot_bytes(c);
+    const bool yuv = c->delivery.format != GSR_FORMAT_RGBA8;
     hipError_t e;
-    if (group) {
+    if (group && yuv) {
+        // exchange stream, where the plain copy of an RGBA8 ring sits: the conversion reads the gathered frame behind its de-slab
+        // kernel and in front of the next one (its stale mask becomes the trailer's first word), the copy follows it there
+        launch_deliver_yuv(c->delivery.format, nullptr, c->comm.frame8, reinterpret_cast<uint8_t*>(sl->staging.p), bytes, c->W, c->H, c->delivery.yuv, k,
+                           c->comm.frame8 + (size_t)c->W * c->H, c->comm.stream);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(sl->host, sl->staging, bytes, hipMemcpyDeviceToHost, c->comm.stream);
+        if (e == hipSuccess) e = hipEventRecord(sl->done, c->comm.stream);
+    } else if (group) {
         // the gathered frame and the word behind it (one bit per rank whose band is stale) are what k_unpack_slabs_rgba8 left on the
         // exchange stream; the copy goes behind it there, in front of the next frame's de-slab
         static_assert(SLAB_FLAG_WORDS == DELIVER_TRAILER_WORDS, "the gathered frame's flag words are the delivered frame's trailer");
@@ -121,7 +193,11 @@ int gsr_deliver_frame_async(gsr_ctx* c, uint64_t* serial)
         if (e == hipSuccess) e = hipEventRecord(sl->done, c->comm.stream);
     } else {
         // render stream: the conversion only (it has read fb before the next frame's compositor starts); copy stream: the copy
-        launch_deliver_rgba8(c->out.fb, sl->staging, c->W, c->H, k, &c->words.fstate->overflow, c->stream);
+        if (yuv)
+            launch_deliver_yuv(c->delivery.format, c->out.fb, nullptr, reinterpret_cast<uint8_t*>(sl->staging.p), bytes, c->W, c->H, c->delivery.yuv, k,
+                               &c->words.fstate->overflow, c->stream);
+        else
+            launch_deliver_rgba8(c->out.fb, sl->staging, c->W, c->H, k, &c->words.fstate->overflow, c->stream);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipEventRecord(c->delivery.ev_staged, c->stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(c->delivery.copy_stream, c->delivery.ev_staged, 0);
@@ -164,7 +240,7 @@ int gsr_acquire_frame(gsr_ctx* c, uint64_t serial, gsr_frame* out)
         return fail(c, GSR_ERR_HIP, "gsr_acquire_frame: frame %llu: %s", (unsigned long long)sl->serial, hipGetErrorString(e));
     }
     uint32_t flag;   // the frame's overflow word; in a group: the ranks whose band is stale
-    memcpy(&flag, sl->host + ring_pixel_bytes(c), 4);
+    memcpy(&flag, sl->host + ring_trailer_offset(c), 4);
     if (flag) {
         sl->state = DeliverySlot::FREE;
         return fail(c, GSR_ERR_OVERFLOW, "delivered frame %llu was not composited (flags 0x%x): its bin lists did not fit and the framebuffer kept "

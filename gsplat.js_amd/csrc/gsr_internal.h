@@ -292,6 +292,20 @@ __device__ __forceinline__ uint32_t to_rgba8(float4 v)
 // preceding image), [1] W | H << 16, [2] / [3] the frame's serial, low / high word.
 constexpr int DELIVER_TRAILER_WORDS = 4;
 void launch_deliver_rgba8(const float4* fb, uint32_t* staging, int32_t W, int32_t H, uint64_t serial, const uint32_t* overflow, hipStream_t s);
+// The same frame as 4:2:0 Y'CbCr ("Frame delivery in Y'CbCr"): everything in integers on the frame's RGBA8
+// bytes.  y / cb / cr: the (R, G, B) rows in 1/256; chroma is taken from the sums of a 2 x 2 block, clamped to [c_lo, c_hi].
+struct YuvParams {
+    int32_t y0, y[3], cb[3], cr[3], c_lo, c_hi;
+    uint32_t bg;   // the background the premultiplied pixel is laid over, R | G << 8 | B << 16 (0: black, nothing to add)
+};
+constexpr int DELIVER_NV12 = 1, DELIVER_I420 = 2;   // (GSR_FORMAT_NV12 / GSR_FORMAT_I420)
+// payload bytes of a W x H frame in 4:2:0 (either layout); the trailer follows at the next multiple of four
+inline size_t yuv420_bytes(int32_t W, int32_t H) { return (size_t)W * H + 2 * (size_t)((W + 1) / 2) * ((H + 1) / 2); }
+// Exactly one of fb (the f32 framebuffer, through to_rgba8) and frame8 (a group's gathered RGBA8 frame) is the source.
+// `overflow`: the word the trailer's first word is read from (the frame's overflow word / the gathered frame's stale mask).
+// `staging_bytes`: what `staging` holds (payload, padding and trailer; the bounds-checked build compares against it).
+void launch_deliver_yuv(int format, const float4* fb, const uint32_t* frame8, uint8_t* staging, size_t staging_bytes, int32_t W, int32_t H,
+                        const YuvParams& k, uint64_t serial, const uint32_t* overflow, hipStream_t s);
 
 // Depth planes and picking (k_depth.hip): the last frame's bin lists walked once more for depth instead of colour.
 struct DepthBuffers {

@@ -44,4 +44,170 @@ void launch_deliver_rgba8(const float4* fb, uint32_t* staging, int32_t W, int32_
                        fb, staging, npix, (uint32_t)W | ((uint32_t)H << 16), (uint32_t)serial, (uint32_t)(serial >> 32), overflow);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// 4:2:0 Y'CbCr (NV12 / I420) for video encoders: the definition is DESIGN.md section 4, "Frame delivery in Y'CbCr".
+// ---------------------------------------------------------------------------------------------------------
+GSR_BOUNDS_DECL(deliver)   // sites: 0 source pixel, 1 byte of the Y plane, 2 byte of the chroma planes, 3 trailer inside the staging buffer
+
+constexpr int YUV_STRIP = 8;   // pixels of a row a lane owns (two rows of them)
+
+// a lane's two rows of YUV_STRIP pixels, all loads issued before anything is converted
+template <class Src> struct YuvStrip;
+template <> struct YuvStrip<float4> {
+    float4 v[2][YUV_STRIP];
+    __device__ __forceinline__ void load(const float4* r0, const float4* r1)
+    {
+#pragma unroll
+        for (int i = 0; i < YUV_STRIP; i++) { v[0][i] = r0[i]; v[1][i] = r1[i]; }
+    }
+    __device__ __forceinline__ uint32_t px(int r, int i) const { return to_rgba8(v[r][i]); }
+};
+template <> struct YuvStrip<uint32_t> {
+    uint4 v[2][YUV_STRIP / 4];
+    __device__ __forceinline__ void load(const uint32_t* r0, const uint32_t* r1)
+    {
+#pragma unroll
+        for (int i = 0; i < YUV_STRIP / 4; i++) {
+            v[0][i] = reinterpret_cast<const uint4*>(r0)[i];
+            v[1][i] = reinterpret_cast<const uint4*>(r1)[i];
+        }
+    }
+    __device__ __forceinline__ uint32_t px(int r, int i) const
+    {
+        const uint4 q = v[r][i >> 2];
+        return (i & 3) == 0 ? q.x : (i & 3) == 1 ? q.y : (i & 3) == 2 ? q.z : q.w;
+    }
+};
+__device__ __forceinline__ uint32_t yuv_source(const float4* p) { return to_rgba8(*p); }
+__device__ __forceinline__ uint32_t yuv_source(const uint32_t* p) { return *p; }
+
+// one pixel: laid over the background (nothing is added for black: (t * 0 + 127) / 255 = 0; the three multiply-adds cost less than
+// a second form of the kernel), its luma returned, its channels added to the block's sums
+__device__ __forceinline__ uint32_t yuv_luma(uint32_t p, const YuvParams& k, int32_t& rs, int32_t& gs, int32_t& bs)
+{
+    int32_t r = (int32_t)(p & 255u), g = (int32_t)((p >> 8) & 255u), b = (int32_t)((p >> 16) & 255u);
+    const uint32_t t = 255u - (p >> 24);
+    r = min(255, r + (int32_t)((t * (k.bg & 255u) + 127u) / 255u));
+    g = min(255, g + (int32_t)((t * ((k.bg >> 8) & 255u) + 127u) / 255u));
+    b = min(255, b + (int32_t)((t * ((k.bg >> 16) & 255u) + 127u) / 255u));
+    rs += r; gs += g; bs += b;
+    return (uint32_t)(k.y0 + ((k.y[0] * r + k.y[1] * g + k.y[2] * b + 128) >> 8));
+}
+__device__ __forceinline__ uint32_t yuv_chroma(const int32_t* c, int32_t rs, int32_t gs, int32_t bs, const YuvParams& k)
+{
+    return (uint32_t)min(max(128 + ((c[0] * rs + c[1] * gs + c[2] * bs + 512) >> 10), k.c_lo), k.c_hi);
+}
+
+// a loaded strip converted and stored whole: 8 bytes of Y per row, 8 (NV12) or 4 + 4 (I420) bytes of chroma
+template <int Format, class Strip>
+__device__ __forceinline__ void yuv_convert_strip(const Strip& in, const YuvParams& k, [[maybe_unused]] const uint8_t* staging, uint8_t* yrow,
+                                                  uint8_t* crow, int32_t W, [[maybe_unused]] uint32_t ysize, uint32_t csize)
+{
+    uint32_t ya[YUV_STRIP / 4] = {}, yb[YUV_STRIP / 4] = {}, cb[YUV_STRIP / 2], cr[YUV_STRIP / 2];
+#pragma unroll
+    for (int j = 0; j < YUV_STRIP / 2; j++) {
+        int32_t rs = 0, gs = 0, bs = 0;
+#pragma unroll
+        for (int d = 0; d < 2; d++) {
+            const int i = 2 * j + d;
+            ya[i >> 2] |= yuv_luma(in.px(0, i), k, rs, gs, bs) << (8 * (i & 3));
+            yb[i >> 2] |= yuv_luma(in.px(1, i), k, rs, gs, bs) << (8 * (i & 3));
+        }
+        cb[j] = yuv_chroma(k.cb, rs, gs, bs, k);
+        cr[j] = yuv_chroma(k.cr, rs, gs, bs, k);
+    }
+    static_assert(YUV_STRIP == 8, "the stores below are written for eight pixels");
+    GSR_BOUND(deliver, 1, (size_t)(yrow - staging) + W + YUV_STRIP - 1, ysize);
+    *reinterpret_cast<uint2*>(yrow) = make_uint2(ya[0], ya[1]);
+    *reinterpret_cast<uint2*>(yrow + W) = make_uint2(yb[0], yb[1]);
+    if (Format == DELIVER_NV12) {
+        GSR_BOUND(deliver, 2, (size_t)(crow - staging) - ysize + YUV_STRIP - 1, 2u * csize);
+        *reinterpret_cast<uint2*>(crow) = make_uint2(cb[0] | (cr[0] << 8) | (cb[1] << 16) | (cr[1] << 24), cb[2] | (cr[2] << 8) | (cb[3] << 16) | (cr[3] << 24));
+    } else {
+        GSR_BOUND(deliver, 2, (size_t)(crow - staging) - ysize + csize + YUV_STRIP / 2 - 1, 2u * csize);
+        *reinterpret_cast<uint32_t*>(crow) = cb[0] | (cb[1] << 8) | (cb[2] << 16) | (cb[3] << 24);
+        *reinterpret_cast<uint32_t*>(crow + csize) = cr[0] | (cr[1] << 8) | (cr[2] << 16) | (cr[3] << 24);
+    }
+}
+
+// A lane owns two rows by YUV_STRIP pixels = YUV_STRIP / 2 chroma samples.  Where the strip lies whole inside an image whose
+// width is a multiple of YUV_STRIP (every row, chroma row and plane then starts on 8 bytes; 4 for I420's chroma) it issues
+// its 16-byte loads -- 2 x 8 of the f32 framebuffer, 2 x 2 of a gathered RGBA8 frame; the lanes of a wave are neighbours in
+// the two rows, so every line fetched is used whole -- converts, and stores 8 bytes of Y per row and 8 (NV12) or 4 + 4 (I420)
+// bytes of chroma.  Any other lane -- the last row pair of an odd height, every lane of other widths -- goes pixel by pixel with
+// the coordinates clamped to the image (the edge column / row is replicated into the block) and stores bytes: it reads
+// nothing outside src[W * H] and writes nothing outside the planes.  Streams 16 (or 4) bytes in and 1.5 out per pixel.
+// The trailer is k_deliver_rgba8's, at the payload rounded up to whole words.
+template <int Format, class Src>
+__global__ __launch_bounds__(DELIVER_THREADS) void k_deliver_yuv(const Src* __restrict__ src, uint8_t* __restrict__ staging, int32_t W, int32_t H,
+                                                                 YuvParams k, uint32_t serial_lo, uint32_t serial_hi,
+                                                                 const uint32_t* __restrict__ overflow, [[maybe_unused]] uint32_t staging_bytes)
+{
+    const uint32_t Wc = (uint32_t)(W + 1) / 2u, Hc = (uint32_t)(H + 1) / 2u;
+    const uint32_t ysize = (uint32_t)W * (uint32_t)H, csize = Wc * Hc;   // (W, H <= 8192: the payload stays below 2^27)
+    [[maybe_unused]] const uint32_t payload = ysize + 2u * csize;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        uint32_t* tr = reinterpret_cast<uint32_t*>(staging + ((payload + 3u) & ~3u));
+        GSR_BOUND(deliver, 3, ((payload + 3u) & ~3u) + DELIVER_TRAILER_WORDS * 4 - 1, staging_bytes);
+        tr[0] = *overflow; tr[1] = (uint32_t)W | ((uint32_t)H << 16); tr[2] = serial_lo; tr[3] = serial_hi;
+    }
+    const uint32_t strips = (uint32_t)(W + YUV_STRIP - 1) / YUV_STRIP;
+    const uint32_t lane = blockIdx.x * DELIVER_THREADS + threadIdx.x;
+    const uint32_t cy = lane / strips, sx = lane - cy * strips;
+    if (cy >= Hc) return;
+    const uint32_t x0 = sx * YUV_STRIP, y0 = cy * 2u;
+    uint8_t* const yrow = staging + (size_t)y0 * W + x0;
+    // NV12: one plane of (Cb, Cr) pairs; I420: the Cb plane, then the Cr plane
+    uint8_t* const crow = staging + ysize + (Format == DELIVER_NV12 ? (size_t)cy * 2u * Wc + x0 : (size_t)cy * Wc + x0 / 2u);
+
+    if (W % YUV_STRIP == 0 && y0 + 1u < (uint32_t)H) {
+        YuvStrip<Src> in;
+        GSR_BOUND(deliver, 0, (size_t)(y0 + 1u) * W + x0 + YUV_STRIP - 1, ysize);
+        in.load(src + (size_t)y0 * W + x0, src + (size_t)(y0 + 1u) * W + x0);
+        __builtin_amdgcn_sched_barrier(0);   // every load is in flight before the first conversion (the scheduler would hold four back)
+        yuv_convert_strip<Format>(in, k, staging, yrow, crow, W, ysize, csize);
+        return;
+    }
+    for (uint32_t j = 0; j < YUV_STRIP / 2 && x0 + 2u * j < (uint32_t)W; j++) {
+        int32_t rs = 0, gs = 0, bs = 0;
+        for (uint32_t d = 0; d < 4u; d++) {
+            const uint32_t x = x0 + 2u * j + (d & 1u), y = y0 + (d >> 1);
+            const size_t at = (size_t)min(y, (uint32_t)H - 1u) * W + min(x, (uint32_t)W - 1u);
+            GSR_BOUND(deliver, 0, at, ysize);
+            const uint32_t luma = yuv_luma(yuv_source(src + at), k, rs, gs, bs);
+            if (x < (uint32_t)W && y < (uint32_t)H) {
+                GSR_BOUND(deliver, 1, (size_t)y * W + x, ysize);
+                staging[(size_t)y * W + x] = (uint8_t)luma;
+            }
+        }
+        uint8_t* const c0 = crow + (Format == DELIVER_NV12 ? 2u * j : j);
+        uint8_t* const c1 = Format == DELIVER_NV12 ? c0 + 1 : c0 + csize;
+        GSR_BOUND(deliver, 2, (size_t)(c0 - staging) - ysize, 2u * csize);
+        GSR_BOUND(deliver, 2, (size_t)(c1 - staging) - ysize, 2u * csize);
+        *c0 = (uint8_t)yuv_chroma(k.cb, rs, gs, bs, k);
+        *c1 = (uint8_t)yuv_chroma(k.cr, rs, gs, bs, k);
+    }
+}
+
+template <class Src>
+static void launch_deliver_yuv_from(int format, const Src* src, uint8_t* staging, size_t staging_bytes, int32_t W, int32_t H, const YuvParams& k,
+                                    uint64_t serial, const uint32_t* overflow, hipStream_t s)
+{
+    const uint32_t lanes = (uint32_t)((W + YUV_STRIP - 1) / YUV_STRIP) * (uint32_t)((H + 1) / 2);
+    const dim3 grid(std::max(1u, (lanes + DELIVER_THREADS - 1) / DELIVER_THREADS)), block(DELIVER_THREADS);
+    if (format == DELIVER_NV12)
+        hipLaunchKernelGGL((k_deliver_yuv<DELIVER_NV12, Src>), grid, block, 0, s, src, staging, W, H, k, (uint32_t)serial, (uint32_t)(serial >> 32), overflow,
+                           (uint32_t)staging_bytes);
+    else
+        hipLaunchKernelGGL((k_deliver_yuv<DELIVER_I420, Src>), grid, block, 0, s, src, staging, W, H, k, (uint32_t)serial, (uint32_t)(serial >> 32), overflow,
+                           (uint32_t)staging_bytes);
+}
+
+void launch_deliver_yuv(int format, const float4* fb, const uint32_t* frame8, uint8_t* staging, size_t staging_bytes, int32_t W, int32_t H,
+                        const YuvParams& k, uint64_t serial, const uint32_t* overflow, hipStream_t s)
+{
+    if (fb) launch_deliver_yuv_from(format, fb, staging, staging_bytes, W, H, k, serial, overflow, s);
+    else launch_deliver_yuv_from(format, frame8, staging, staging_bytes, W, H, k, serial, overflow, s);
+}
+
 }  // namespace gsr

@@ -96,11 +96,32 @@ export interface FrameStats {
     msProjectKey: number; msSort: number; msBin: number; msBlend: number; msCombine: number; msTotal: number;
     visible: number; binEntries: number; tileEntries: number; n: number; frames: number;
 }
+export type DeliveryFormat = "rgba8" | "nv12" | "i420";
+export interface DeliveryOptions {
+    /** "rgba8" (default), or 4:2:0 Y'CbCr (BT.709) for a video encoder: "nv12" (Y, interleaved CbCr) / "i420" (Y, Cb, Cr) */
+    format?: DeliveryFormat;
+    /** Y'CbCr: 0..255 ("pc", yuvj420p) instead of limited range 16..235 / 16..240 ("tv"); default false */
+    fullRange?: boolean;
+    /** Y'CbCr carries no alpha: the [R, G, B] bytes the premultiplied frame is laid over; default black */
+    background?: [number, number, number];
+}
+/** a view of one plane of a delivered frame, `rows` rows of `stride` bytes */
+export type DeliveredPlane = Uint8Array & { stride: number; rows: number };
+export interface DeliveryLayout {
+    format: DeliveryFormat; width: number; height: number;
+    /** the payload: `pixels.length` */
+    bytes: number;
+    planes: { offset: number; stride: number; rows: number }[];
+}
 export interface DeliveredFrame {
     serial: number;
-    /** RGBA8, row 0 = top: byte for byte what readPixels() returns for that frame */
+    /** RGBA8, row 0 = top: byte for byte what readPixels() returns for that frame.  On an "nv12" / "i420" ring: the whole
+     *  payload, planes tightly packed -- what `ffmpeg -f rawvideo -pix_fmt nv12 | yuv420p` reads; write it to a pipe as it is */
     pixels: Uint8Array;
     width: number; height: number;
+    format: DeliveryFormat;
+    /** views of `pixels.buffer`: one for "rgba8", Y and CbCr for "nv12", Y, Cb and Cr for "i420" */
+    planes: DeliveredPlane[];
     release(): void;
 }
 export class HIPRenderer {
@@ -162,7 +183,9 @@ export class HIPRenderer {
     /** Frame delivery: a ring of `slots` (2..8, default 3) pinned RGBA8 frames inside the library.  renderAsync() +
      *  deliverFrame() enqueue a frame and its copy to the host without waiting; acquireFrame() waits for that frame's copy
      *  only, so frame k is presented while k+1 and k+2 render.  Works after joinGroup() too (the gathered frame). */
-    openDelivery(slots?: number): void;
+    openDelivery(slots?: number, options?: DeliveryOptions): void;
+    /** the open ring's frame layout at the current size (it follows setSize) */
+    deliveryLayout(): DeliveryLayout;
     /** throws while a frame is held; detaches the slots' ArrayBuffers (old `pixels` views then have length 0) */
     closeDelivery(): void;
     /** enqueue the delivery of the frame enqueued last; returns its serial (1, 2, 3 ...).  Throws ("... (-7) ...") and

@@ -4,6 +4,7 @@
 // The one thing handed the other way is the delivery ring: its pinned blocks become external ArrayBuffers (see DeliverySlots).
 #include <node_api.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -499,6 +500,51 @@ napi_value OpenDelivery(napi_env env, napi_callback_info info)
     return DeliverySlots(env, info);
 }
 
+// openDeliveryEx(handle, slots, format, fullRange, bgR, bgG, bgB) -> [ArrayBuffer, ...]: a ring in GSR_FORMAT_* (gsr_delivery_open_ex)
+napi_value OpenDeliveryEx(napi_env env, napi_callback_info info)
+{
+    napi_value argv[7];
+    if (!get_args(env, info, 7, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    int32_t v[6];
+    if (!c) return nullptr;
+    for (int k = 0; k < 6; k++)
+        if (!get_i32(env, argv[1 + k], &v[k])) { napi_throw_type_error(env, nullptr, "openDeliveryEx(handle, slots, format, fullRange, r, g, b)"); return nullptr; }
+    gsr_delivery_options opt{};
+    opt.slots = v[0]; opt.format = v[1]; opt.full_range = v[2];
+    for (int k = 0; k < 3; k++) opt.background[k] = (uint8_t)std::min(255, std::max(0, v[3 + k]));
+    const int rc = gsr_delivery_open_ex(c, &opt);
+    if (rc) return throw_gsr(env, c, rc, "gsr_delivery_open_ex");
+    return DeliverySlots(env, info);
+}
+
+// deliveryLayout(handle) -> { format, width, height, bytes, planes: [{ offset, stride, rows }, ...] } of the open ring
+napi_value DeliveryLayout(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    if (!c) return nullptr;
+    gsr_frame_layout lay;
+    const int rc = gsr_delivery_layout(c, &lay);
+    if (rc) return throw_gsr(env, c, rc, "gsr_delivery_layout");
+    auto set = [&](napi_value obj, const char* key, double value) {
+        napi_value v;
+        return napi_create_double(env, value, &v) == napi_ok && napi_set_named_property(env, obj, key, v) == napi_ok;
+    };
+    napi_value out, planes;
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    NAPI_OK_OR_NULL(env, napi_create_array(env, &planes));
+    bool ok = set(out, "format", lay.format) && set(out, "width", lay.width) && set(out, "height", lay.height) && set(out, "bytes", (double)lay.bytes);
+    for (int32_t k = 0; ok && k < lay.planes; k++) {
+        napi_value pl;
+        ok = napi_create_object(env, &pl) == napi_ok && set(pl, "offset", (double)lay.offset[k]) && set(pl, "stride", lay.stride[k]) &&
+             set(pl, "rows", lay.rows[k]) && napi_set_element(env, planes, (uint32_t)k, pl) == napi_ok;
+    }
+    if (!ok || napi_set_named_property(env, out, "planes", planes) != napi_ok) { napi_throw_error(env, nullptr, "deliveryLayout: building the result failed"); return nullptr; }
+    return out;
+}
+
 // detachBuffers([ArrayBuffer, ...]): the blocks behind them are about to be freed
 napi_value DetachBuffers(napi_env env, napi_callback_info info)
 {
@@ -692,6 +738,7 @@ napi_value Init(napi_env env, napi_value exports)
         {"setListCapacity", SetListCapacity}, {"buildId", BuildId}, {"commUniqueId", CommUniqueId}, {"commInit", CommInit}, {"commShare", CommShare},
         {"commDestroy", Call0<gsr_comm_destroy>}, {"allgatherFrameAsync", Call0<gsr_allgather_frame_async>}, {"readFrame", ReadFrame},
         {"openDelivery", OpenDelivery}, {"closeDelivery", Call0<gsr_delivery_close>}, {"deliverySlots", DeliverySlots}, {"detachBuffers", DetachBuffers},
+        {"openDeliveryEx", OpenDeliveryEx}, {"deliveryLayout", DeliveryLayout},
         {"deliverFrame", DeliverFrame}, {"frameReady", FrameReady}, {"acquireFrame", AcquireFrame}, {"releaseFrame", ReleaseFrame},
         {"setHitAlpha", SetHitAlpha}, {"depthAsync", Call0<gsr_depth_async>}, {"readDepth", ReadDepth}, {"pick", Pick},
     };

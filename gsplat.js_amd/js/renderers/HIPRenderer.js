@@ -59,20 +59,43 @@ class HIPRenderer {
         // `pixels` is a view of the slot's pinned block: one external ArrayBuffer per slot, created when the ring is opened, so
         // nothing is allocated or copied per frame and `pixels.buffer` is the same object every lap.  Before the blocks are freed
         // (closeDelivery, setSize to another size, dispose) the buffers are detached: an old view then has length 0.
-        let slotBuffers = null, slotViews = null;
+        // For a video encoder: openDelivery(3, { format: "nv12" | "i420", fullRange: false, background: [0, 0, 0] }) delivers 4:2:0 Y'CbCr
+        // (BT.709), 1.5 bytes per pixel.  `pixels` is then the whole payload, as `ffmpeg -f rawvideo -pix_fmt nv12 | yuv420p` reads
+        // it -- process.stdout.write(f.pixels) -- and `planes` its parts: Uint8Array views carrying `stride` and `rows`.
+        const FORMATS = ["rgba8", "nv12", "i420"];
+        let slotBuffers = null, slotViews = null, slotPlanes = null, ringFormat = "rgba8";
         const held = new Map();                  // serial -> frame object
-        const wrapSlots = (buffers) => { slotBuffers = buffers; slotViews = buffers.map((b) => new Uint8Array(b)); };
+        const wrapSlots = (buffers) => {
+            const layout = this._n.deliveryLayout(this._h);
+            slotBuffers = buffers;
+            slotViews = buffers.map((b) => new Uint8Array(b));
+            slotPlanes = buffers.map((b) => layout.planes.map((p) => Object.assign(new Uint8Array(b, p.offset, p.stride * p.rows), { stride: p.stride, rows: p.rows })));
+            ringFormat = FORMATS[layout.format];
+        };
         const dropSlots = () => {
             if (slotBuffers) this._n.detachBuffers(slotBuffers);
-            slotBuffers = slotViews = null;
+            slotBuffers = slotViews = slotPlanes = null;
+        };
+        this.deliveryLayout = () => {
+            const layout = this._n.deliveryLayout(this._h);
+            layout.format = FORMATS[layout.format];
+            return layout;
         };
         const refuseWhileHeld = (what) => {
             if (held.size) throw new Error(what + ": a delivered frame is held (release() it first): its pixels would be freed");
         };
-        this.openDelivery = (slots) => {
+        this.openDelivery = (slots, options) => {
             refuseWhileHeld("openDelivery");
-            dropSlots();
-            wrapSlots(this._n.openDelivery(this._h, slots === undefined ? 3 : slots));
+            const o = options || {}, format = FORMATS.indexOf(o.format === undefined ? "rgba8" : o.format), bg = o.background || [0, 0, 0];
+            if (format < 0) throw new Error("openDelivery: format must be one of " + FORMATS.join(", "));
+            const n = slots === undefined ? 3 : slots;
+            if (format === 0) {
+                dropSlots();
+                wrapSlots(this._n.openDelivery(this._h, n));
+            } else {                             // (refused by the library while a ring is open: closeDelivery() first)
+                const buffers = this._n.openDeliveryEx(this._h, n, format, o.fullRange ? 1 : 0, bg[0] | 0, bg[1] | 0, bg[2] | 0);
+                wrapSlots(buffers);
+            }
         };
         this.closeDelivery = () => {
             refuseWhileHeld("closeDelivery");
@@ -85,7 +108,7 @@ class HIPRenderer {
         // slot: render and deliver that pose again.
         this.acquireFrame = (serial) => {
             const f = this._n.acquireFrame(this._h, serial || 0);
-            const frame = { serial: f[0], pixels: slotViews[f[1]], width: this.width, height: this.height,
+            const frame = { serial: f[0], pixels: slotViews[f[1]], width: this.width, height: this.height, format: ringFormat, planes: slotPlanes[f[1]],
                             release: () => { if (held.delete(frame.serial)) this._n.releaseFrame(this._h, frame.serial); } };
             held.set(frame.serial, frame);
             return frame;

@@ -48,6 +48,19 @@ class GsrFrame(ctypes.Structure):
                 ("serial", ctypes.c_uint64)]
 
 
+class GsrDeliveryOptions(ctypes.Structure):
+    _fields_ = [("slots", ctypes.c_int32), ("format", ctypes.c_int32), ("full_range", ctypes.c_int32), ("background", ctypes.c_uint8 * 4)]
+
+
+class GsrFrameLayout(ctypes.Structure):
+    _fields_ = [("format", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("planes", ctypes.c_int32),
+                ("offset", ctypes.c_uint64 * 3), ("stride", ctypes.c_int32 * 3), ("rows", ctypes.c_int32 * 3), ("bytes", ctypes.c_uint64)]
+
+
+GSR_FORMAT_RGBA8, GSR_FORMAT_NV12, GSR_FORMAT_I420 = 0, 1, 2
+DELIVERY_FORMATS = {"rgba8": GSR_FORMAT_RGBA8, "nv12": GSR_FORMAT_NV12, "i420": GSR_FORMAT_I420}
+
+
 def edge_arrays(edges):
     """[(x0, x1)] per rank -> (c_int32[world], c_int32[world]) for gsr_unpack_slabs_rgba8_async."""
     world = len(edges)
@@ -74,7 +87,7 @@ EXPORTS = [
     "gsr_comm_unique_id", "gsr_comm_init", "gsr_comm_destroy", "gsr_allgather_frame_async", "gsr_read_frame_rgba8",
     "gsr_frame8_device_ptr", "gsr_comm_stream_handle", "gsr_read_work_items", "gsr_comm_share", "gsr_comm_init_custom",
     "gsr_delivery_open", "gsr_delivery_close", "gsr_deliver_frame_async", "gsr_frame_ready", "gsr_acquire_frame",
-    "gsr_release_frame", "gsr_delivery_slot_ptr",
+    "gsr_release_frame", "gsr_delivery_slot_ptr", "gsr_delivery_open_ex", "gsr_delivery_layout",
     "gsr_set_hit_alpha", "gsr_depth_async", "gsr_read_depth", "gsr_depth_device_ptr", "gsr_pick",
 ]
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p)
@@ -186,6 +199,8 @@ def load_library(path=None):
     L.gsr_release_frame.argtypes = [vp, ctypes.c_uint64]
     L.gsr_delivery_slot_ptr.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_uint64)]
     L.gsr_delivery_slot_ptr.restype = vp
+    L.gsr_delivery_open_ex.argtypes = [vp, ctypes.POINTER(GsrDeliveryOptions)]
+    L.gsr_delivery_layout.argtypes = [vp, ctypes.POINTER(GsrFrameLayout)]
     L.gsr_set_hit_alpha.argtypes = [vp, ctypes.c_float]
     L.gsr_depth_async.argtypes = [vp]
     L.gsr_read_depth.argtypes = [vp, vp, vp, vp]
@@ -495,11 +510,31 @@ class HIPRenderer:
         self._check(self._L.gsr_read_pixels_rgba8(self._ctx, out.ctypes.data))
         return out
 
-    # -- frame delivery: RGBA8 frames through the library's pinned ring while the next frames render (gsr_delivery_*) --
-    def open_delivery(self, slots=3):
-        """A ring of `slots` (2..8) pinned frames for deliver() / acquire() / release()."""
+    # -- frame delivery: frames through the library's pinned ring while the next frames render (gsr_delivery_*) --
+    def open_delivery(self, slots=3, format="rgba8", full_range=False, background=(0, 0, 0)):
+        """A ring of `slots` (2..8) pinned frames for deliver() / acquire() / release().  `format`: "rgba8", or 4:2:0 Y'CbCr for a
+        video encoder, "nv12" / "i420" (BT.709; `full_range`: 0..255 instead of 16..235 / 16..240; `background`: the (R, G, B) the
+        premultiplied frame is laid over, Y'CbCr having no alpha).  A Y'CbCr ring is opened only when none is open."""
+        if format not in DELIVERY_FORMATS:
+            raise ValueError("format must be one of %s" % ", ".join(sorted(DELIVERY_FORMATS)))
         self._slot_views = {}
-        self._check(self._L.gsr_delivery_open(self._ctx, slots))
+        if format == "rgba8":
+            self._check(self._L.gsr_delivery_open(self._ctx, slots))
+            return
+        bg = [int(v) for v in background]
+        if len(bg) != 3 or min(bg) < 0 or max(bg) > 255:
+            raise ValueError("background must be three bytes (R, G, B)")
+        opt = GsrDeliveryOptions(slots, DELIVERY_FORMATS[format], 1 if full_range else 0, (ctypes.c_uint8 * 4)(*bg, 0))
+        self._check(self._L.gsr_delivery_open_ex(self._ctx, ctypes.byref(opt)))
+
+    def delivery_layout(self):
+        """The open ring's frame layout at the current size (gsr_delivery_layout): format, width, height, bytes (the payload) and
+        planes, a list of {offset, stride, rows} -- one for RGBA8, Y and CbCr for NV12, Y, Cb and Cr for I420."""
+        lay = GsrFrameLayout()
+        self._check(self._L.gsr_delivery_layout(self._ctx, ctypes.byref(lay)))
+        names = {v: k for k, v in DELIVERY_FORMATS.items()}
+        return {"format": names[lay.format], "width": lay.width, "height": lay.height, "bytes": int(lay.bytes),
+                "planes": [{"offset": int(lay.offset[k]), "stride": lay.stride[k], "rows": lay.rows[k]} for k in range(lay.planes)]}
 
     def close_delivery(self):
         self._slot_views = {}
@@ -521,15 +556,25 @@ class HIPRenderer:
     def acquire(self, serial=0):
         """Wait for frame `serial`'s copy (0: the oldest frame not acquired yet) -- not for the frames behind it -- and
         return (serial, pixels): a read-only zero-copy [H, W, 4] uint8 view of the slot's pinned block, valid until
-        release(serial).  A frame that was not composited (list overflow) raises GsplatError with code GSR_ERR_OVERFLOW
+        release(serial).  On a Y'CbCr ring: (serial, planes), a tuple of such views -- Y [H, W] and CbCr [Hc, Wc, 2] for "nv12",
+        Y [H, W], Cb [Hc, Wc] and Cr [Hc, Wc] for "i420" (Hc = (H + 1) // 2, Wc = (W + 1) // 2), contiguous in the block: the
+        payload a rawvideo pipe takes is the planes' bytes one after the other.  A frame that was not composited (list overflow) raises GsplatError with code GSR_ERR_OVERFLOW
         and frees its slot: render and deliver that pose again."""
         f = GsrFrame()
         self._check(self._L.gsr_acquire_frame(self._ctx, serial, ctypes.byref(f)))
         view = self._slot_views.get(f.slot)
         if view is None:
-            block = (ctypes.c_uint8 * (f.width * f.height * 4)).from_address(f.pixels)
-            view = np.frombuffer(block, dtype=np.uint8).reshape(f.height, f.width, 4)
-            view.flags.writeable = False
+            lay = GsrFrameLayout()
+            self._check(self._L.gsr_delivery_layout(self._ctx, ctypes.byref(lay)))
+            block = np.frombuffer((ctypes.c_uint8 * lay.bytes).from_address(f.pixels), dtype=np.uint8)
+            block.flags.writeable = False
+            if lay.format == GSR_FORMAT_RGBA8:
+                view = block.reshape(f.height, f.width, 4)
+            else:   # Y [H, W]; NV12: CbCr [Hc, Wc, 2]; I420: Cb [Hc, Wc], Cr [Hc, Wc]
+                planes = [block[lay.offset[k]:lay.offset[k] + lay.stride[k] * lay.rows[k]].reshape(lay.rows[k], lay.stride[k]) for k in range(lay.planes)]
+                if lay.format == GSR_FORMAT_NV12:
+                    planes[1] = planes[1].reshape(lay.rows[1], lay.stride[1] // 2, 2)
+                view = tuple(planes)
             self._slot_views[f.slot] = view
         return f.serial, view
 

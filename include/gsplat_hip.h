@@ -277,7 +277,8 @@ void *gsr_comm_stream_handle(gsr_ctx *ctx);   /* hipStream_t the exchange runs o
  * otherwise they wait for the copies and free or reallocate the ring (frames delivered but not acquired are gone, slot
  * pointers change).  gsr_sync also waits for the copies in flight; gsr_destroy waits and frees the ring. */
 typedef struct gsr_frame {
-    const uint8_t *pixels;  /* pinned host memory, uint8[height][width][4], row 0 = top; valid until gsr_release_frame */
+    const uint8_t *pixels;  /* pinned host memory, uint8[height][width][4], row 0 = top (a Y'CbCr ring: plane 0, see
+                             * gsr_delivery_layout); valid until gsr_release_frame */
     int32_t width, height, slot;
     uint64_t serial;
 } gsr_frame;
@@ -290,6 +291,45 @@ int gsr_release_frame(gsr_ctx *ctx, uint64_t serial);
 /* The pinned block of slot `slot` (0 .. slots-1) and its size in pixel bytes, for hosts that wrap every slot once
  * (an external ArrayBuffer per slot); NULL without a ring.  The pointers change only when the ring is reallocated. */
 void *gsr_delivery_slot_ptr(gsr_ctx *ctx, int32_t slot, uint64_t *bytes);
+
+/* ---- frame delivery in 4:2:0 Y'CbCr (NV12 / I420), for hosts that feed a video encoder ----
+ * A ring opened with gsr_delivery_open_ex delivers every frame in the format chosen there; the conversion runs on the device
+ * in front of the copy, which shrinks from 4 to 1.5 bytes per pixel, and slots are allocated at the format's size.
+ * Everything above holds for every format: serials, GSR_ERR_BUSY, the overflow refusal, gsr_resize (the layout follows the
+ * new size), gsr_sync / gsr_destroy, the gathered frame of a group (converted on the exchange stream).
+ * The definition, in integers on the bytes gsr_read_pixels_rgba8 / gsr_read_frame_rgba8 return for the
+ * frame, premultiplied (r, g, b, a):
+ *     R = min(255, r + ((255 - a) * background[0] + 127) / 255), G and B likewise      (default background: black, R = r)
+ *     Y = y0 + ((cYr * R + cYg * G + cYb * B + 128) >> 8)                               per pixel
+ *     Cb = clamp(128 + ((cBr * Rs + cBg * Gs + cBb * Bs + 512) >> 10), lo, hi), Cr likewise, per 2 x 2 block, Rs / Gs / Bs the
+ *     four pixels' sums; coordinates are clamped to the image, so odd sizes replicate the last column / row
+ * BT.709, limited range ("tv", full_range = 0): y0 16, Y (47, 157, 16), Cb (-26, -86, 112), Cr (112, -102, -10), chroma 16..240;
+ * full range ("pc", yuvj420p): y0 0, Y (54, 183, 19), Cb (-29, -99, 128), Cr (128, -116, -12), chroma 0..255.
+ * A slot, Wc = (width + 1) / 2, Hc = (height + 1) / 2, planes tightly packed, row 0 = top:
+ *     NV12: Y at 0 (stride width, height rows), interleaved CbCr at width * height (stride 2 * Wc, Hc rows)
+ *     I420: Y at 0, Cb at width * height (stride Wc, Hc rows), Cr at width * height + Wc * Hc
+ * -- for even sizes byte for byte what `ffmpeg -f rawvideo -pix_fmt nv12 | yuv420p -s WxH` reads.  gsr_frame.pixels points at
+ * plane 0; gsr_delivery_layout gives the rest; gsr_delivery_slot_ptr reports the format's payload bytes. */
+#define GSR_FORMAT_RGBA8 0
+#define GSR_FORMAT_NV12  1
+#define GSR_FORMAT_I420  2
+typedef struct gsr_delivery_options {
+    int32_t slots;          /* 2..8 */
+    int32_t format;         /* GSR_FORMAT_* */
+    int32_t full_range;     /* NV12 / I420: 0 limited range, otherwise full range */
+    uint8_t background[4];  /* NV12 / I420: R, G, B the premultiplied frame is laid over ([3] is ignored) */
+} gsr_delivery_options;
+typedef struct gsr_frame_layout {
+    int32_t format, width, height, planes;
+    uint64_t offset[3];     /* of every plane, in bytes from gsr_frame.pixels */
+    int32_t stride[3], rows[3];
+    uint64_t bytes;         /* the payload: what gsr_delivery_slot_ptr reports */
+} gsr_frame_layout;
+/* gsr_delivery_open(ctx, n) is format GSR_FORMAT_RGBA8.  GSR_ERR_ARG: a ring is open already (gsr_delivery_close first), an
+ * unknown format, slots outside 2..8, no framebuffer size yet. */
+int gsr_delivery_open_ex(gsr_ctx *ctx, const gsr_delivery_options *opt);
+/* The layout of the open ring's frames at the current size; GSR_ERR_ARG without a ring. */
+int gsr_delivery_layout(gsr_ctx *ctx, gsr_frame_layout *out);
 
 /* ---- depth and pick: per-pixel depth planes of the last rendered frame, and the splat under a pixel ----
  * No interface of the reference stands behind this section (its renderer returns colour only, WebGLRenderer.ts:241-296): it

@@ -13,11 +13,14 @@ the device from the seeded .splat rows.  Prints one JSON line:
   delivered_in_flight          F throughput contexts used round-robin, each with its own ring
   other_configs                `delivered` and `render_only` for the other configurations (--other C2,C4)
 Every delivered leg compares its last delivered frame with readPixels() of the same pose, byte for byte
-(`delivered_equals_read_pixels`).  --timed-only runs nothing but the warm-up and the timed `delivered` loop of the chosen
-configuration (with --frames-in-flight F > 1: the F-context loop): the run a profiler wraps.
+(`delivered_equals_read_pixels`).  --format nv12|i420 opens the rings in 4:2:0 Y'CbCr (BT.709 limited range, black background):
+the same legs and keys, `bytes_per_frame` of the format, and the comparison goes through the definition in plain numpy
+(tests/yuv_reference.py applied to readPixels() of the same pose: `delivered_equals_reference`).
+--timed-only runs nothing but the warm-up and the timed `delivered` loop of the chosen configuration (with
+--frames-in-flight F > 1: the F-context loop): the run a profiler wraps.
 
   python scripts/bench_delivery.py [--config C3] [--frames 480] [--warmup 30] [--slots 3] [--frames-in-flight 3]
-                                   [--other C2,C4] [--timed-only]
+                                   [--other C2,C4] [--timed-only] [--format rgba8|nv12|i420]
 There is no CPU path: without an MI355X the script fails."""
 import argparse
 import json
@@ -26,7 +29,7 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "gsplat.js_amd", "py")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "gsplat.js_amd", "py"), os.path.join(ROOT, "tests")]
 
 import numpy as np  # noqa: E402
 
@@ -39,9 +42,21 @@ def percentiles(lat):
     return {"p50": lat[len(lat) // 2], "p99": lat[min(len(lat) - 1, int(len(lat) * 0.99))], "mean": sum(lat) / len(lat), "frames": len(lat)}
 
 
+FORMAT = "rgba8"      # --format: what every ring of this run is opened for
+
+
+def same_key():
+    return "delivered_equals_read_pixels" if FORMAT == "rgba8" else "delivered_equals_reference"
+
+
+def open_ring(r, slots):
+    r.open_delivery(slots) if FORMAT == "rgba8" else r.open_delivery(slots, format=FORMAT)
+
+
 def delivered_run(ctxs, poses, fx, count, slots):
     """`count` orbit frames, every one delivered: the contexts round-robin, a context's oldest frame acquired and released only
-    when its ring is full.  Returns (frames/s, the last delivered frame equals readPixels() of the same pose)."""
+    when its ring is full.  Returns (frames/s, the last delivered frame equals readPixels() of the same pose -- for a Y'CbCr
+    ring: the numpy reference's payload of it)."""
     pending = [[] for _ in ctxs]
     last = None
 
@@ -64,10 +79,15 @@ def delivered_run(ctxs, poses, fx, count, slots):
             pick_up(j % len(ctxs))
     fps = count / (time.perf_counter() - t0)
     c, px = last
-    got = px.copy()                                          # (its slot is released, but nothing has been delivered since)
+    # (its slot is released, but nothing has been delivered since)
+    got = px.copy() if FORMAT == "rgba8" else np.concatenate([plane.ravel() for plane in px])
     ctxs[c].set_camera_arrays(*poses[(count - 1) % ORBIT_FRAMES], fx, fx)
     ctxs[c].render_async()
-    return fps, bool(np.array_equal(got, ctxs[c].readPixels()))
+    want = ctxs[c].readPixels()
+    if FORMAT != "rgba8":
+        import yuv_reference
+        want = yuv_reference.payload(want, FORMAT)
+    return fps, bool(np.array_equal(got, want))
 
 
 def make_contexts(gh, cfg, rows, poses, count, throughput, device):
@@ -89,14 +109,17 @@ def measure(gh, name, args, full):
     F = max(1, args.frames_in_flight)
     frames = args.frames if W * H <= 1920 * 1080 else max(60, args.frames // 4)
     out = {"workload": "%s: %d synthetic gaussians (seed %d), %dx%d, 120-pose orbit" % (name, cfg["n"], cfg["seed"], W, H),
-           "frames": frames, "warmup": args.warmup, "slots": args.slots, "bytes_per_frame": W * H * 4}
+           "frames": frames, "warmup": args.warmup, "slots": args.slots,
+           "bytes_per_frame": W * H * 4 if FORMAT == "rgba8" else W * H + 2 * ((W + 1) // 2) * ((H + 1) // 2)}
+    if FORMAT != "rgba8":
+        out["format"] = FORMAT
     if args.timed_only:
         rs = make_contexts(gh, cfg, rows, poses, F, F > 1, args.device)
         for rr in rs:
-            rr.open_delivery(args.slots)
+            open_ring(rr, args.slots)
         delivered_run(rs, poses, fx, args.warmup, args.slots)
         fps, same = delivered_run(rs, poses, fx, frames, args.slots)
-        out["delivered_in_flight" if F > 1 else "delivered"] = {"frames_per_sec": fps, "contexts": F, "delivered_equals_read_pixels": same}
+        out["delivered_in_flight" if F > 1 else "delivered"] = {"frames_per_sec": fps, "contexts": F, same_key(): same}
         for rr in rs:
             rr.dispose()
         return out
@@ -112,10 +135,10 @@ def measure(gh, name, args, full):
 
     render_only(args.warmup)
     out["render_only"] = {"frames_per_sec": render_only(frames)}
-    r.open_delivery(args.slots)
+    open_ring(r, args.slots)
     delivered_run([r], poses, fx, args.warmup, args.slots)
     fps, same = delivered_run([r], poses, fx, frames, args.slots)
-    out["delivered"] = {"frames_per_sec": fps, "contexts": 1, "delivered_equals_read_pixels": same}
+    out["delivered"] = {"frames_per_sec": fps, "contexts": 1, same_key(): same}
     if full:
         nread = min(frames, 120)
         buf = np.empty((H, W, 4), dtype=np.uint8)
@@ -145,10 +168,10 @@ def measure(gh, name, args, full):
     if full and F > 1:
         rs = make_contexts(gh, cfg, rows, poses, F, True, args.device)
         for rr in rs:
-            rr.open_delivery(args.slots)
+            open_ring(rr, args.slots)
         delivered_run(rs, poses, fx, args.warmup, args.slots)
         fps, same = delivered_run(rs, poses, fx, frames, args.slots)
-        out["delivered_in_flight"] = {"frames_per_sec": fps, "contexts": F, "delivered_equals_read_pixels": same}
+        out["delivered_in_flight"] = {"frames_per_sec": fps, "contexts": F, same_key(): same}
         for rr in rs:
             rr.dispose()
     return out
@@ -164,7 +187,10 @@ def main():
     ap.add_argument("--other", default="C2,C4", help="configurations measured beside --config (delivered and render_only); '' for none")
     ap.add_argument("--timed-only", action="store_true")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--format", default="rgba8", choices=["rgba8", "nv12", "i420"], help="what the rings deliver (default: RGBA8)")
     args = ap.parse_args()
+    global FORMAT
+    FORMAT = args.format
     import torch
     if not torch.cuda.is_available():
         sys.exit("bench_delivery.py needs an MI355X (torch.cuda.is_available() is False); there is no CPU path")

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Summary of a kernel + memory-copy trace of the delivery ring (scripts/gpu.sh copytrace DIR ...): how long the
 frames' device-to-host copies take, the rate that is for `bytes` per copy, how much of their time lies under compositor or
-front-end kernels of OTHER frames (the point of the ring), and k_deliver_rgba8's own time and rate.
+front-end kernels of OTHER frames (the point of the ring), and the conversion kernel's (k_deliver_rgba8 / k_deliver_yuv) own time
+and rate.
 usage: python scripts/copy_overlap.py DIR BYTES_PER_COPY [skip_fraction]      (DIR: the trace task's output directory)"""
 import csv
 import glob
@@ -39,8 +40,8 @@ if not frame_copies:
     sys.exit("no frame-sized device-to-host copy in the trace")
 dur = sorted(c[1] - c[0] for c in frame_copies)
 med = dur[len(dur) // 2]
-# time of every copy during which a kernel of the render chain (anything but k_deliver_rgba8) is running
-spans = sorted((k[0], k[1]) for k in kernels if k[2] != "k_deliver_rgba8")
+# time of every copy during which a kernel of the render chain (anything but the conversion kernel) is running
+spans = sorted((k[0], k[1]) for k in kernels if not k[2].startswith("k_deliver"))
 merged = []
 for s, e in spans:
     if merged and s <= merged[-1][1]:
@@ -57,15 +58,17 @@ for cs, ce in frame_copies:
         if s >= ce:
             break
         under += min(e, ce) - max(s, cs)
-dk = sorted(k[1] - k[0] for k in kernels if k[2] == "k_deliver_rgba8")
 print("frame copies (device to host, %d bytes each) by %s: %d in the steady state" % (nbytes, how, len(frame_copies)))
 print("  duration us: median %.1f  p10 %.1f  p90 %.1f  -> %.1f GB/s at the median" % (med / 1e3, dur[len(dur) // 10] / 1e3, dur[len(dur) * 9 // 10] / 1e3, nbytes / med))
 print("  share of copy time under render-chain kernels of other frames: %.1f %%" % (100.0 * under / total))
 span = frame_copies[-1][1] - frame_copies[0][0]
 print("  copy engine busy %.1f %% of the steady state (%.1f us per frame between copy starts)" % (100.0 * total / span, span / 1e3 / max(1, len(frame_copies) - 1)))
-if dk:
-    m = dk[len(dk) // 2]
-    print("k_deliver_rgba8: %d launches, median %.2f us (p90 %.2f): %.0f GB/s for the %d bytes it moves" % (len(dk), m / 1e3, dk[len(dk) * 9 // 10] / 1e3, nbytes * 5 / m, nbytes * 5))
+# the conversion kernel reads 16 bytes per pixel of the f32 framebuffer and writes the copy's bytes: 4 per pixel as RGBA8, 1.5 as 4:2:0
+for name, moved in (("k_deliver_rgba8", nbytes * 5), ("k_deliver_yuv", nbytes * 2 // 3 * 16 + nbytes)):
+    dk = sorted(k[1] - k[0] for k in kernels if k[2] == name)
+    if dk:
+        m = dk[len(dk) // 2]
+        print("%s: %d launches, median %.2f us (p90 %.2f): %.0f GB/s for the %d bytes it moves" % (name, len(dk), m / 1e3, dk[len(dk) * 9 // 10] / 1e3, moved / m, moved))
 by = {}
 for s, e, n, _q in kernels:
     by.setdefault(n, []).append(e - s)

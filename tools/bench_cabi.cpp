@@ -3,12 +3,14 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--depth] [--pick X,Y]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--depth] [--pick X,Y]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
 // gsr_deliver_frame_async, gsr_acquire_frame, gsr_release_frame: three slots per context, the oldest frame picked up when the
 // ring is full) -- the header alone is enough to consume frames -- and reports its rate and the checksum of a delivered frame.
+// --deliver-format nv12|i420 (beside --deliver) opens the rings in 4:2:0 Y'CbCr instead of RGBA8 (gsr_delivery_open_ex, BT.709 limited
+// range, black background) and reports the checksum of the last frame's payload (gsr_delivery_layout gives its size).
 //
 // Scene: the seeded synthetic generator of gsplat_hip/synth.py (mulberry32 counter PRNG, 24 draws per splat) written
 // out again in C++; log/exp/cos come from libm here and from numpy there, so a byte may differ in a rare rounding --
@@ -126,6 +128,7 @@ int main(int argc, char** argv)
     std::string config = "C1", rows_path, dump;
     int frames = 240, warmup = 20, in_flight = 3;
     bool deliver = false;
+    std::string deliver_format = "rgba8";
     bool depth = false, pick = false;
     int32_t pick_xy[2] = {0, 0};
     for (int i = 1; i < argc; i++) {
@@ -138,13 +141,16 @@ int main(int argc, char** argv)
         else if (a == "--in-flight") in_flight = std::atoi(next());
         else if (a == "--dump") dump = next();
         else if (a == "--deliver") deliver = true;
+        else if (a == "--deliver-format") deliver_format = next();
         else if (a == "--depth") depth = true;
         else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--depth] [--pick X,Y]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--depth] [--pick X,Y]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
     if (!cfg || in_flight < 1 || frames < 1) { std::fprintf(stderr, "bad arguments\n"); return 2; }
+    const int32_t format = deliver_format == "nv12" ? GSR_FORMAT_NV12 : deliver_format == "i420" ? GSR_FORMAT_I420 : GSR_FORMAT_RGBA8;
+    if (format == GSR_FORMAT_RGBA8 && deliver_format != "rgba8") { std::fprintf(stderr, "--deliver-format nv12|i420\n"); return 2; }
 
     std::vector<uint8_t> rows;
     if (!rows_path.empty()) {
@@ -230,11 +236,17 @@ int main(int argc, char** argv)
     unsigned long long delivered_hash = 0;
     uint64_t delivered = 0, sink = 0;
     if (deliver) {
-        for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_delivery_open(c, 3)); }
+        for (gsr_ctx* c : ctx) {
+            ctx0 = c;
+            if (format == GSR_FORMAT_RGBA8) { CHECK(gsr_delivery_open(c, 3)); continue; }
+            gsr_delivery_options dopt{};
+            dopt.slots = 3; dopt.format = format;
+            CHECK(gsr_delivery_open_ex(c, &dopt));
+        }
         auto pick_up = [&](gsr_ctx* c) -> int {   // the oldest frame of this context
             gsr_frame f;
             if (int rc = gsr_acquire_frame(c, 0, &f)) return rc;
-            sink += f.pixels[(size_t)f.width * f.height * 2];
+            sink += f.pixels[(size_t)f.width * f.height / 2];
             delivered++;
             return gsr_release_frame(c, f.serial);
         };
@@ -268,8 +280,12 @@ int main(int argc, char** argv)
         gsr_frame f;
         CHECK(gsr_deliver_frame_async(ctx[0], &serial));
         CHECK(gsr_acquire_frame(ctx[0], serial, &f));
-        delivered_hash = (unsigned long long)fnv1a(f.pixels, (size_t)f.width * f.height * 4);
-        const bool same = f.width == cfg->w && f.height == cfg->h && !std::memcmp(f.pixels, px.data(), px.size());
+        gsr_frame_layout lay;
+        CHECK(gsr_delivery_layout(ctx[0], &lay));
+        delivered_hash = (unsigned long long)fnv1a(f.pixels, (size_t)lay.bytes);
+        // (a Y'CbCr payload is held to the definition by tests/test_gpu_yuv_delivery.py, through this checksum)
+        const bool same = f.width == cfg->w && f.height == cfg->h && lay.format == format &&
+                          (format != GSR_FORMAT_RGBA8 || (lay.bytes == px.size() && !std::memcmp(f.pixels, px.data(), px.size())));
         CHECK(gsr_release_frame(ctx[0], serial));
         if (!same) { std::fprintf(stderr, "the delivered frame differs from gsr_read_pixels_rgba8\n"); return 1; }
     }
@@ -282,10 +298,14 @@ int main(int argc, char** argv)
                 cfg->name, n, cfg->w, cfg->h, frames, warmup, in_flight, frames / sec, sec / frames * 1e3,
                 (unsigned long long)fnv1a(rows.data(), rows.size()), (unsigned long long)fnv1a(di.data(), di.size() * 4),
                 (unsigned long long)fnv1a(px.data(), px.size()), name, cus);
-    if (deliver)
+    if (deliver && format == GSR_FORMAT_RGBA8)
         std::printf(", \"frames_per_sec_delivered\": %.1f, \"delivery_slots\": 3, \"delivered_rgba8_fnv1a\": \"%016llx\", "
                     "\"delivered_equals_read_pixels\": true, \"sink\": %d",
                     frames / delivered_sec, delivered_hash, (int)(sink & 1));
+    else if (deliver)
+        std::printf(", \"frames_per_sec_delivered\": %.1f, \"delivery_slots\": 3, \"delivery_format\": \"%s\", "
+                    "\"delivered_payload_fnv1a\": \"%016llx\", \"sink\": %d",
+                    frames / delivered_sec, deliver_format.c_str(), delivered_hash, (int)(sink & 1));
     if (depth)
         std::printf(", \"frames_per_sec_plain\": %.1f, \"frames_per_sec_with_depth\": %.1f, \"depth_legs\": 3",
                     3.0 * frames / depth_sec[0], 3.0 * frames / depth_sec[1]);
