@@ -293,6 +293,19 @@ struct gsr_ctx {
         gsr::YuvParams yuv{};               // NV12 / I420: the coefficient set and the background
         int next = 0;                       // where the search for a free slot starts: the slots are used in turn
         uint64_t serial = 0;                // the last serial handed out; never restarts
+        // a depth ring (gsr_delivery_open_depth): every delivered frame carries its hit plane behind the colour payload.  The pass has
+        // buffers of its own -- nothing of gsr_ctx::Depth but hit_alpha is read, nothing of it written -- allocated with the ring.
+        struct DepthPlane {
+            int format = GSR_DEPTH_NONE;    // GSR_DEPTH_*; NONE: a ring as it was before depth rings existed, nothing below is allocated
+            int step = 1;                   // 1 or 2: sample (i, j) is pixel (step * i, step * j)
+            float near = 0.0f;              // GSR_DEPTH_U16
+            int Wd = 0, Hd = 0;             // ceil(W / step), ceil(H / step)
+            gsr::DevBuf<float> hit;         // Wd x Hd: what the pass writes and k_deliver_depth reads; reused by every delivery (in-order on the render stream)
+            gsr::DevBuf<float> mean;        // step 1 only: k_depth_planes<.., 1> writes three planes; these two are scratch
+            gsr::DevBuf<uint32_t> index;
+            gsr::DevBuf<uint32_t> invalid;  // the pass's "refused an unfit frame" word: a third one, beside the planes' and the pick's
+            int fill_key[4] = {0, 0, 0, 0}; // band contexts: W, H and bin columns the hit plane's other columns were last filled for
+        } depth;
     } delivery;
 };
 
@@ -323,6 +336,10 @@ void drop_graph(gsr_ctx* c);
 int alloc_scene(gsr_ctx* c, uint32_t n, bool with_rows);
 // gsr_comm.cpp
 void comm_release(gsr_ctx* c);
+// gsr_depth.cpp: a depth ring's pass for the frame enqueued last.  check: what gsr_depth_async demands of the frame (GSR_ERR_ARG, nothing
+// enqueued); enqueue: the planes pass into the ring's own plane(s) on the render stream (launch errors are left for hipGetLastError)
+int delivery_depth_check(gsr_ctx* c, const char* who);
+int delivery_depth_enqueue(gsr_ctx* c);
 // gsr_delivery.cpp
 int delivery_alloc(gsr_ctx* c, int slots);
 void delivery_free(gsr_ctx* c);

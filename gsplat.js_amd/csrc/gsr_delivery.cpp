@@ -8,6 +8,7 @@
 // ---------------------------------------------------------------------------------------------------------
 #include "gsr_ctx.h"
 
+#include <cmath>
 #include <cstring>
 
 using namespace gsr;
@@ -20,7 +21,16 @@ static inline size_t ring_pixel_bytes(const gsr_ctx* c)
     const gsr_ctx::Delivery& d = c->delivery;
     return d.format == GSR_FORMAT_RGBA8 ? (size_t)d.W * d.H * 4 : yuv420_bytes(d.W, d.H);
 }
-static inline size_t ring_trailer_offset(const gsr_ctx* c) { return (ring_pixel_bytes(c) + 3) & ~(size_t)3; }
+// a depth ring: the plane behind the payload at the next multiple of 16, the trailer behind the plane at the next multiple of 16
+static inline bool ring_has_depth(const gsr_ctx* c) { return c->delivery.depth.format != GSR_DEPTH_NONE; }
+static inline size_t ring_depth_offset(const gsr_ctx* c) { return (ring_pixel_bytes(c) + 15) & ~(size_t)15; }
+static inline size_t ring_depth_stride(const gsr_ctx* c) { return (size_t)c->delivery.depth.Wd * (c->delivery.depth.format == GSR_DEPTH_U16 ? 2 : 4); }
+static inline size_t ring_depth_bytes(const gsr_ctx* c) { return ring_depth_stride(c) * c->delivery.depth.Hd; }
+static inline size_t ring_trailer_offset(const gsr_ctx* c)
+{
+    if (ring_has_depth(c)) return (ring_depth_offset(c) + ring_depth_bytes(c) + 15) & ~(size_t)15;
+    return (ring_pixel_bytes(c) + 3) & ~(size_t)3;
+}
 static inline size_t ring_slot_bytes(const gsr_ctx* c) { return ring_trailer_offset(c) + DELIVER_TRAILER_WORDS * 4; }
 
 // BT.709 in 1/256: every chroma row sums to zero, the full-range luma row to 256, so greys are neutral exactly
@@ -58,6 +68,10 @@ void gsr::delivery_free(gsr_ctx* c)
     c->delivery.copy_stream = nullptr;
     c->delivery.W = c->delivery.H = 0;
     c->delivery.next = 0;
+    gsr_ctx::Delivery::DepthPlane& dp = c->delivery.depth;   // (format, step and near stay: gsr_resize reallocates for them)
+    dp.hit.reset(); dp.mean.reset(); dp.index.reset(); dp.invalid.reset();
+    dp.Wd = dp.Hd = 0;
+    std::fill(dp.fill_key, dp.fill_key + 4, 0);
 }
 
 // (re)allocates the ring for the context's current size; frames in flight are waited for and dropped
@@ -65,8 +79,18 @@ int gsr::delivery_alloc(gsr_ctx* c, int slots)
 {
     delivery_free(c);
     c->delivery.W = c->W; c->delivery.H = c->H;
+    gsr_ctx::Delivery::DepthPlane& dp = c->delivery.depth;
+    if (ring_has_depth(c)) { dp.Wd = (c->W + dp.step - 1) / dp.step; dp.Hd = (c->H + dp.step - 1) / dp.step; }
     const size_t bytes = ring_slot_bytes(c);
     auto bail = [c](int code) { delivery_free(c); return code; };
+    if (ring_has_depth(c)) {
+        // the pass's own plane(s): the hit plane k_deliver_depth reads; at step 1 the full pass also writes mean and index
+        const size_t np = (size_t)dp.Wd * dp.Hd;
+        int r = dp.hit.alloc(c, np);
+        if (!r && dp.step == 1) { r = dp.mean.alloc(c, np); if (!r) r = dp.index.alloc(c, np); }
+        if (!r) r = dp.invalid.alloc(c, 1);
+        if (r) return bail(r);
+    }
     hipError_t e = hipStreamCreateWithFlags(&c->delivery.copy_stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->delivery.ev_staged, hipEventDisableTiming);
     c->delivery.ring.resize((size_t)slots);
@@ -106,21 +130,64 @@ int gsr_delivery_open(gsr_ctx* c, int32_t slots)
     if (int r = delivery_open_checked(c, "gsr_delivery_open", slots)) return r;
     HIP_TRY(c, hipSetDevice(c->device));
     c->delivery.format = GSR_FORMAT_RGBA8;
+    c->delivery.depth.format = GSR_DEPTH_NONE;
     return delivery_alloc(c, slots);
+}
+
+// gsr_delivery_open_ex, and with `depth` gsr_delivery_open_depth: nothing of the context changes unless every argument is accepted
+static int delivery_open_options(gsr_ctx* c, const char* who, const gsr_delivery_options* opt, const gsr_depth_delivery_options* depth)
+{
+    if (!opt) return fail(c, GSR_ERR_ARG, "%s: options are NULL", who);
+    if (opt->format != GSR_FORMAT_RGBA8 && opt->format != GSR_FORMAT_NV12 && opt->format != GSR_FORMAT_I420)
+        return fail(c, GSR_ERR_ARG, "%s: unknown format %d (GSR_FORMAT_RGBA8, GSR_FORMAT_NV12, GSR_FORMAT_I420)", who, opt->format);
+    if (depth) {
+        if (depth->format != GSR_DEPTH_F32 && depth->format != GSR_DEPTH_U16)
+            return fail(c, GSR_ERR_ARG, "%s: unknown depth format %d (GSR_DEPTH_NONE, GSR_DEPTH_F32, GSR_DEPTH_U16)", who, depth->format);
+        if (depth->step != 1 && depth->step != 2) return fail(c, GSR_ERR_ARG, "%s: depth step %d (1 or 2)", who, depth->step);
+        if (depth->format == GSR_DEPTH_U16 && !(depth->near > 0.0f && std::isfinite(depth->near)))
+            return fail(c, GSR_ERR_ARG, "%s: GSR_DEPTH_U16 needs a finite near > 0, not %g", who, (double)depth->near);
+        if (depth->reserved) return fail(c, GSR_ERR_ARG, "%s: gsr_depth_delivery_options.reserved must be 0", who);
+        if (c->comm.joined())
+            return fail(c, GSR_ERR_ARG, "%s: this context is in a group: depth is not exchanged between ranks, so a gathered frame has no depth plane to deliver", who);
+    }
+    if (!c->delivery.ring.empty()) return fail(c, GSR_ERR_ARG, "%s: a delivery ring is open (gsr_delivery_close first)", who);
+    if (int r = delivery_open_checked(c, who, opt->slots)) return r;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->delivery.format = opt->format;
+    c->delivery.yuv = yuv_params(opt->full_range != 0, opt->background);
+    gsr_ctx::Delivery::DepthPlane& dp = c->delivery.depth;
+    dp.format = depth ? depth->format : GSR_DEPTH_NONE;
+    dp.step = depth ? depth->step : 1;
+    dp.near = depth && depth->format == GSR_DEPTH_U16 ? depth->near : 0.0f;
+    return delivery_alloc(c, opt->slots);
 }
 
 int gsr_delivery_open_ex(gsr_ctx* c, const gsr_delivery_options* opt)
 {
     if (!c) return GSR_ERR_ARG;
-    if (!opt) return fail(c, GSR_ERR_ARG, "gsr_delivery_open_ex: options are NULL");
-    if (opt->format != GSR_FORMAT_RGBA8 && opt->format != GSR_FORMAT_NV12 && opt->format != GSR_FORMAT_I420)
-        return fail(c, GSR_ERR_ARG, "gsr_delivery_open_ex: unknown format %d (GSR_FORMAT_RGBA8, GSR_FORMAT_NV12, GSR_FORMAT_I420)", opt->format);
-    if (!c->delivery.ring.empty()) return fail(c, GSR_ERR_ARG, "gsr_delivery_open_ex: a delivery ring is open (gsr_delivery_close first)");
-    if (int r = delivery_open_checked(c, "gsr_delivery_open_ex", opt->slots)) return r;
-    HIP_TRY(c, hipSetDevice(c->device));
-    c->delivery.format = opt->format;
-    c->delivery.yuv = yuv_params(opt->full_range != 0, opt->background);
-    return delivery_alloc(c, opt->slots);
+    return delivery_open_options(c, "gsr_delivery_open_ex", opt, nullptr);
+}
+
+int gsr_delivery_open_depth(gsr_ctx* c, const gsr_delivery_options* opt, const gsr_depth_delivery_options* depth)
+{
+    if (!c) return GSR_ERR_ARG;
+    return delivery_open_options(c, "gsr_delivery_open_depth", opt, depth && depth->format != GSR_DEPTH_NONE ? depth : nullptr);
+}
+
+int gsr_delivery_depth_layout(gsr_ctx* c, gsr_depth_layout* out)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (!out) return fail(c, GSR_ERR_ARG, "gsr_delivery_depth_layout: out is NULL");
+    if (c->delivery.ring.empty()) return fail(c, GSR_ERR_ARG, "gsr_delivery_depth_layout: no delivery ring (gsr_delivery_open_depth)");
+    if (!ring_has_depth(c)) return fail(c, GSR_ERR_ARG, "gsr_delivery_depth_layout: the ring was opened without a depth plane (gsr_delivery_open_depth)");
+    const gsr_ctx::Delivery::DepthPlane& dp = c->delivery.depth;
+    *out = gsr_depth_layout{};
+    out->format = dp.format; out->step = dp.step; out->width = dp.Wd; out->height = dp.Hd;
+    out->stride = (int32_t)ring_depth_stride(c);
+    out->offset = ring_depth_offset(c);
+    out->bytes = ring_depth_bytes(c);
+    out->near = dp.near;
+    return GSR_OK;
 }
 
 int gsr_delivery_layout(gsr_ctx* c, gsr_frame_layout* out)
@@ -155,6 +222,7 @@ int gsr_delivery_close(gsr_ctx* c)
     if (delivery_frame_held(c)) return fail(c, GSR_ERR_ARG, "gsr_delivery_close: a delivered frame is held (gsr_release_frame first): its pixels would be freed");
     HIP_TRY(c, hipSetDevice(c->device));
     delivery_free(c);
+    c->delivery.depth.format = GSR_DEPTH_NONE;
     return GSR_OK;
 }
 
@@ -163,8 +231,14 @@ int gsr_deliver_frame_async(gsr_ctx* c, uint64_t* serial)
     if (!c) return GSR_ERR_ARG;
     if (c->delivery.ring.empty()) return fail(c, GSR_ERR_ARG, "gsr_deliver_frame_async: no delivery ring (gsr_delivery_open)");
     const bool group = c->comm.joined();
+    const bool depth = ring_has_depth(c);
+    if (depth && group)   // (refused before anything else is looked at: nothing enqueued, no slot taken)
+        return fail(c, GSR_ERR_ARG, "gsr_deliver_frame_async: this context joined a group after it opened a depth ring: depth is not exchanged "
+                                    "between ranks, so a gathered frame has no depth plane to deliver (gsr_delivery_close, then a ring without depth)");
     if (group ? !c->comm.frame8_valid : !c->have_frame)
         return fail(c, GSR_ERR_ARG, group ? "gsr_deliver_frame_async: no gathered frame yet (gsr_allgather_frame_async)" : "gsr_deliver_frame_async: nothing rendered yet");
+    // a depth ring needs what gsr_depth_async needs of the frame; refused before a slot is looked for: nothing enqueued, no slot taken
+    if (depth) { if (int r = delivery_depth_check(c, "gsr_deliver_frame_async (depth ring)")) return r; }
     DeliverySlot* sl = nullptr;
     const int slots = (int)c->delivery.ring.size();
     for (int k = 0; k < slots && !sl; k++) {
@@ -198,6 +272,15 @@ int gsr_deliver_frame_async(gsr_ctx* c, uint64_t* serial)
                                &c->words.fstate->overflow, c->stream);
         else
             launch_deliver_rgba8(c->out.fb, sl->staging, c->W, c->H, k, &c->words.fstate->overflow, c->stream);
+        if (depth) {
+            // behind the conversion, in front of ev_staged: the frame's depth pass into the ring's plane, then the plane into the slot and
+            // THE trailer behind it (the one the conversion wrote at the end of the colour payload lies under the padding and the plane).
+            // The next frame's chain follows on this stream, so lists, records and the ring's plane are read before they are overwritten.
+            const gsr_ctx::Delivery::DepthPlane& dp = c->delivery.depth;
+            if (int r = delivery_depth_enqueue(c)) return r;
+            launch_deliver_depth(dp.format, dp.hit, reinterpret_cast<uint8_t*>(sl->staging.p), ring_depth_offset(c), ring_trailer_offset(c), dp.Wd, dp.Hd,
+                                 dp.near, c->W, c->H, k, &c->words.fstate->overflow, c->stream);
+        }
         e = hipGetLastError();
         if (e == hipSuccess) e = hipEventRecord(c->delivery.ev_staged, c->stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(c->delivery.copy_stream, c->delivery.ev_staged, 0);

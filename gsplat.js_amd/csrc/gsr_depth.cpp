@@ -25,7 +25,9 @@ int check_frame(gsr_ctx* c, const char* who)
     return GSR_OK;
 }
 
-DepthBuffers buffers(gsr_ctx* c, uint32_t* invalid, bool planes)
+// the frame's lists, records and positions, and the planes a pass writes: the context's (gsr_depth_async / gsr_read_depth), a
+// delivery ring's own (delivery_depth_enqueue), or none (gsr_pick)
+DepthBuffers buffers(gsr_ctx* c, uint32_t* invalid, float* mean, float* hit, uint32_t* index)
 {
     DepthBuffers b{};
     b.bin_start = c->bin.start;
@@ -34,7 +36,7 @@ DepthBuffers buffers(gsr_ctx* c, uint32_t* invalid, bool planes)
     b.px = c->scene.arr.px; b.py = c->scene.arr.py; b.pz = c->scene.arr.pz;
     b.overflow = &c->words.fstate->overflow;
     b.invalid = invalid;
-    if (planes) { b.mean = c->depth.mean; b.hit = c->depth.hit; b.index = c->depth.index; }
+    b.mean = mean; b.hit = hit; b.index = index;
     b.capacity = c->bin.capacity;
     b.nsplats = std::max(c->n, 1u);
     b.hit_alpha = c->depth.hit_alpha;
@@ -74,7 +76,7 @@ int enqueue_planes(gsr_ctx* c)
         if (!whole) launch_depth_fill(d.mean, d.hit, d.index, (uint32_t)((size_t)c->W * c->H), c->stream);
         std::copy(key, key + 4, d.fill_key);
     }
-    launch_depth_planes(buffers(c, d.invalid, true), g, c->cam_frame, c->knobs.depth_skip, c->stream);
+    launch_depth_planes(buffers(c, d.invalid, d.mean, d.hit, d.index), g, c->cam_frame, c->knobs.depth_skip, 1, c->stream);
     HIP_TRY(c, hipGetLastError());
     d.planes_serial = c->frame_serial;
     return GSR_OK;
@@ -89,6 +91,26 @@ int settle_frame(gsr_ctx* c, const char* who)
 }
 
 }  // namespace
+
+int gsr::delivery_depth_check(gsr_ctx* c, const char* who) { return check_frame(c, who); }
+
+// The pass of a depth ring, behind the frame on the render stream: the frame's lists with the frame's camera and the context's
+// hit_alpha of this moment, into the ring's own plane(s).  c->depth (the planes gsr_read_depth caches, planes_serial) is not touched.
+int gsr::delivery_depth_enqueue(gsr_ctx* c)
+{
+    gsr_ctx::Delivery::DepthPlane& d = c->delivery.depth;
+    const BinGrid g = make_grid(c);
+    // a band context's bins do not cover the image: the other columns' samples are +inf, written when the plane, the size or the
+    // band are new (the pass writes the band's columns only; step 1's scratch planes are never read)
+    const bool whole = g.bx_lo == 0 && g.bx_hi == g.nbx;
+    const int key[4] = {c->W, c->H, g.bx_lo, g.bx_hi};
+    if (!std::equal(key, key + 4, d.fill_key)) {
+        if (!whole) HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)d.hit.p, 0x7f800000, (size_t)d.Wd * d.Hd, c->stream));
+        std::copy(key, key + 4, d.fill_key);
+    }
+    launch_depth_planes(buffers(c, d.invalid, d.mean, d.hit, d.index), g, c->cam_frame, c->knobs.depth_skip, d.step, c->stream);
+    return GSR_OK;
+}
 
 extern "C" {
 
@@ -164,7 +186,7 @@ int gsr_pick(gsr_ctx* c, const int32_t* xy, uint32_t count, gsr_pick_result* out
         if (int r = d.result.alloc(c, MAX_PICKS)) return r;
     }
     HIP_TRY(c, hipMemcpyAsync(d.query, xy, (size_t)count * 8, hipMemcpyHostToDevice, c->stream));
-    launch_pick(buffers(c, d.invalid + 1, false), g, c->cam_frame, d.query, count, d.result, c->stream);
+    launch_pick(buffers(c, d.invalid + 1, nullptr, nullptr, nullptr), g, c->cam_frame, d.query, count, d.result, c->stream);
     HIP_TRY(c, hipGetLastError());
     uint32_t invalid = 0;
     HIP_TRY(c, hipMemcpyAsync(&invalid, d.invalid + 1, 4, hipMemcpyDeviceToHost, c->stream));

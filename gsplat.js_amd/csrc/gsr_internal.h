@@ -306,6 +306,12 @@ inline size_t yuv420_bytes(int32_t W, int32_t H) { return (size_t)W * H + 2 * (s
 // `staging_bytes`: what `staging` holds (payload, padding and trailer; the bounds-checked build compares against it).
 void launch_deliver_yuv(int format, const float4* fb, const uint32_t* frame8, uint8_t* staging, size_t staging_bytes, int32_t W, int32_t H,
                         const YuvParams& k, uint64_t serial, const uint32_t* overflow, hipStream_t s);
+// The depth plane of a depth ring ("Frame delivery with depth"): `plane`, Wd x Hd f32 hit values, into
+// `staging` at `depth_offset` as f32 or as 16-bit inverse depth against `near`, and the slot's trailer (as above, W | H << 16
+// the frame's size) at `trailer_offset`; both offsets are multiples of 16, the plane ends at or in front of the trailer.
+constexpr int DELIVER_DEPTH_F32 = 1, DELIVER_DEPTH_U16 = 2;   // (GSR_DEPTH_F32 / GSR_DEPTH_U16)
+void launch_deliver_depth(int format, const float* plane, uint8_t* staging, size_t depth_offset, size_t trailer_offset, int32_t Wd, int32_t Hd, float near,
+                          int32_t W, int32_t H, uint64_t serial, const uint32_t* overflow, hipStream_t s);
 
 // Depth planes and picking (k_depth.hip): the last frame's bin lists walked once more for depth instead of colour.
 struct DepthBuffers {
@@ -321,7 +327,8 @@ struct DepthBuffers {
     float hit_alpha;
 };
 struct PickResult { uint32_t index; float depth, mean, alpha; };   // gsr_pick_result
-void launch_depth_planes(const DepthBuffers& b, const BinGrid& g, const CamParams& cam, bool skip, hipStream_t s);
+// step 1: mean, hit and index, W x H each; step 2: the hit plane only, at the pixels (2i, 2j): ceil(W / 2) x ceil(H / 2) samples
+void launch_depth_planes(const DepthBuffers& b, const BinGrid& g, const CamParams& cam, bool skip, int step, hipStream_t s);
 void launch_pick(const DepthBuffers& b, const BinGrid& g, const CamParams& cam, const int32_t* xy, uint32_t count, PickResult* out, hipStream_t s);
 void launch_depth_fill(float* mean, float* hit, uint32_t* index, uint32_t npix, hipStream_t s);
 

@@ -47,7 +47,8 @@ void launch_deliver_rgba8(const float4* fb, uint32_t* staging, int32_t W, int32_
 // ---------------------------------------------------------------------------------------------------------
 // 4:2:0 Y'CbCr (NV12 / I420) for video encoders: the definition is DESIGN.md section 4, "Frame delivery in Y'CbCr".
 // ---------------------------------------------------------------------------------------------------------
-GSR_BOUNDS_DECL(deliver)   // sites: 0 source pixel, 1 byte of the Y plane, 2 byte of the chroma planes, 3 trailer inside the staging buffer
+GSR_BOUNDS_DECL(deliver)   // sites: 0 source pixel, 1 byte of the Y plane, 2 byte of the chroma planes, 3 trailer inside the staging buffer,
+                           // 4 word of the depth plane
 
 constexpr int YUV_STRIP = 8;   // pixels of a row a lane owns (two rows of them)
 
@@ -187,6 +188,85 @@ __global__ __launch_bounds__(DELIVER_THREADS) void k_deliver_yuv(const Src* __re
         *c0 = (uint8_t)yuv_chroma(k.cb, rs, gs, bs, k);
         *c1 = (uint8_t)yuv_chroma(k.cr, rs, gs, bs, k);
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The depth plane of a depth ring (gsr_delivery_open_depth; the definition is DESIGN.md section 4, "Frame delivery with depth"):
+// the ring's f32 hit plane of n = Wd * Hd samples into the slot's staging at the depth offset (a multiple of 16), as it is or
+// quantised to 16 bits, and the slot's trailer behind it -- the one the host reads; the colour kernel in front of this one has
+// written its own at the end of the colour payload, where the padding and this plane now lie.
+// A lane owns 16 bytes of the output: four samples as f32, eight as u16 (two 16-byte loads, both issued before the first
+// division).  The last lane of a plane that is not a multiple of that takes its samples one (f32) or two (u16: a whole
+// word, the missing half zero -- the padding in front of the trailer) at a time.  Streams 4 bytes in and 4 or 2 out per sample.
+// ---------------------------------------------------------------------------------------------------------
+// inverse depth against `near` in 16 bits: 65535 unless z > 0 (NaN included); +infinity is 0.  The division is the correctly
+// rounded one (hipcc's default for `/`), the rounding to an integer is to nearest, ties to even (v_rndne_f32).
+__device__ __forceinline__ uint32_t depth_u16(float z, float near)
+{
+    if (!(z > 0.0f)) return 65535u;
+    const float q = fminf(near / z, 1.0f);
+    return (uint32_t)__builtin_rintf(q * 65535.0f);
+}
+
+template <int Format>
+__global__ __launch_bounds__(DELIVER_THREADS) void k_deliver_depth(const float* __restrict__ plane, uint32_t* __restrict__ out, uint32_t n, float near,
+                                                                   uint32_t* __restrict__ trailer, uint32_t dims, uint32_t serial_lo, uint32_t serial_hi,
+                                                                   const uint32_t* __restrict__ overflow, [[maybe_unused]] uint32_t out_words)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        *reinterpret_cast<uint4*>(trailer) = make_uint4(*overflow, dims, serial_lo, serial_hi);   // (16-byte aligned: see ring_trailer_offset)
+    }
+    constexpr uint32_t PER_LANE = Format == DELIVER_DEPTH_F32 ? 4u : 8u;
+    const uint32_t s = (blockIdx.x * DELIVER_THREADS + threadIdx.x) * PER_LANE;
+    if (s >= n) return;
+    const uint4* in = reinterpret_cast<const uint4*>(plane + s);
+    if (Format == DELIVER_DEPTH_F32) {
+        if (s + PER_LANE <= n) {
+            GSR_BOUND(deliver, 4, s + 3u, out_words);
+            *reinterpret_cast<uint4*>(out + s) = in[0];
+        } else {
+            for (uint32_t i = s; i < n; i++) {
+                GSR_BOUND(deliver, 4, i, out_words);
+                out[i] = __float_as_uint(plane[i]);
+            }
+        }
+    } else {
+        if (s + PER_LANE <= n) {
+            const uint4 a = in[0], b = in[1];
+            uint4 o;
+            o.x = depth_u16(__uint_as_float(a.x), near) | (depth_u16(__uint_as_float(a.y), near) << 16);
+            o.y = depth_u16(__uint_as_float(a.z), near) | (depth_u16(__uint_as_float(a.w), near) << 16);
+            o.z = depth_u16(__uint_as_float(b.x), near) | (depth_u16(__uint_as_float(b.y), near) << 16);
+            o.w = depth_u16(__uint_as_float(b.z), near) | (depth_u16(__uint_as_float(b.w), near) << 16);
+            GSR_BOUND(deliver, 4, s / 2u + 3u, out_words);
+            *reinterpret_cast<uint4*>(out + s / 2u) = o;
+        } else {
+            for (uint32_t i = s; i < n; i += 2u) {
+                const uint32_t lo = depth_u16(plane[i], near), hi = i + 1u < n ? depth_u16(plane[i + 1u], near) : 0u;
+                GSR_BOUND(deliver, 4, i / 2u, out_words);
+                out[i / 2u] = lo | (hi << 16);
+            }
+        }
+    }
+}
+
+void launch_deliver_depth(int format, const float* plane, uint8_t* staging, size_t depth_offset, size_t trailer_offset, int32_t Wd, int32_t Hd, float near,
+                          int32_t W, int32_t H, uint64_t serial, const uint32_t* overflow, hipStream_t s)
+{
+    const uint32_t n = (uint32_t)Wd * (uint32_t)Hd;   // (Wd, Hd <= 8192)
+    const uint32_t per_lane = format == DELIVER_DEPTH_F32 ? 4u : 8u;
+    const uint32_t lanes = (n + per_lane - 1u) / per_lane;
+    const dim3 grid(std::max(1u, (lanes + DELIVER_THREADS - 1) / DELIVER_THREADS)), block(DELIVER_THREADS);
+    uint32_t* out = reinterpret_cast<uint32_t*>(staging + depth_offset);
+    uint32_t* trailer = reinterpret_cast<uint32_t*>(staging + trailer_offset);
+    const uint32_t out_words = (uint32_t)((trailer_offset - depth_offset) / 4);
+    const uint32_t dims = (uint32_t)W | ((uint32_t)H << 16);
+    if (format == DELIVER_DEPTH_F32)
+        hipLaunchKernelGGL(k_deliver_depth<DELIVER_DEPTH_F32>, grid, block, 0, s, plane, out, n, near, trailer, dims, (uint32_t)serial, (uint32_t)(serial >> 32),
+                           overflow, out_words);
+    else
+        hipLaunchKernelGGL(k_deliver_depth<DELIVER_DEPTH_U16>, grid, block, 0, s, plane, out, n, near, trailer, dims, (uint32_t)serial, (uint32_t)(serial >> 32),
+                           overflow, out_words);
 }
 
 template <class Src>

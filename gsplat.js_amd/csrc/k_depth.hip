@@ -17,7 +17,8 @@
 
 namespace gsr {
 
-GSR_BOUNDS_DECL(depth)   // sites: 0 bin -> bin_start, 1 list position, 2 splat index in the list, 3 LDS cell, 4 query pixel
+GSR_BOUNDS_DECL(depth)   // sites: 0 bin -> bin_start, 1 list position, 2 splat index in the list, 3 LDS cell, 4 query pixel,
+                         // 5 sample of a strided hit plane
 constexpr int DEPTH_THREADS = 256;
 constexpr int DEPTH_CHUNK = DEPTH_THREADS;
 constexpr float DEPTH_LOG2E = 1.4426950408889634f;
@@ -100,13 +101,21 @@ __device__ __forceinline__ float depth_row_w(const DepthEntry& e, float pyf) { r
 // quadrant test at tile size: the tile's pixel centres lie outside the oriented box |vPosition.x|, |vPosition.y| <= 2
 // (separating axes u and w), or farther from the centre than the longer semi-axis.  Every fragment left out has q > 4, so the
 // planes are bit-identical with and without it (GSR_DEPTH_SKIP=0 is the build of the same walk that visits every entry).
-template <bool SKIP>
+//
+// STEP: 1 is the pass above, every pixel, three planes.  2 is the delivery ring's strided pass (gsr_delivery_open_depth): the
+// recurrence at the pixels (2i, 2j) only.  A wave still owns a 16x16 tile, but a lane owns ONE pixel of it, (ox + 2 lx,
+// oy + 2 ly): one DepthPixel, one pair of row terms and one weight per visited entry instead of four, two and four.  Staging,
+// the reach mask, the ballot and the list order are the same, and pxf / pyf are the same small exact integers the full pass
+// uses for that pixel, so a sample is the full hit plane's value bit for bit.  It writes the hit plane only, ceil(W / 2) x
+// ceil(H / 2) samples (a bin starts on an even pixel: sample (x / 2, y / 2)).
+template <bool SKIP, int STEP>
 __global__ __launch_bounds__(DEPTH_THREADS) void k_depth_planes(DepthBuffers a, BinGrid g, CamParams cam)
 {
     __shared__ float4 s_a[DEPTH_CHUNK];       // ux, uy, ncu, wx
     __shared__ float4 s_b[DEPTH_CHUNK];       // wy, ncw, la, z
     __shared__ uint32_t s_idx[DEPTH_CHUNK];
     __shared__ uint32_t s_tiles[DEPTH_CHUNK]; // one bit per tile of the bin the entry can reach
+    static_assert(STEP == 1 || STEP == 2, "every pixel, or every second one in both directions");
 
     // A frame whose lists did not fit published no work (k_bin_finalize): nothing of it is walked, nothing is written, and the
     // host learns at its next synchronisation that the planes are not this frame's.
@@ -122,15 +131,16 @@ __global__ __launch_bounds__(DEPTH_THREADS) void k_depth_planes(DepthBuffers a, 
     const int by = bin / nbxb, bxl = bin - by * nbxb;
     const int binX0 = (g.bx_lo + bxl) * BIN_PX, binY0 = by * BIN_PX;
     const int ox = (wave & 1) * TILE, oy = (wave >> 1) * TILE;
-    const float pxf0 = (float)(ox + lx), pxf1 = pxf0 + 8.0f;
-    const float pyf0 = (float)(oy + ly), pyf1 = pyf0 + 8.0f;
+    [[maybe_unused]] const float pxf0 = (float)(ox + STEP * lx), pxf1 = pxf0 + 8.0f;   // (pxf1, pyf1: STEP 1, the lane's other column and row)
+    [[maybe_unused]] const float pyf0 = (float)(oy + STEP * ly), pyf1 = pyf0 + 8.0f;
     const float bx0c = (float)binX0 + 0.5f, by0c = (float)binY0 + 0.5f;
 
     const uint32_t end = min(a.bin_start[bin + 1], a.capacity), begin = min(a.bin_start[bin], end);
     GSR_BOUND(depth, 1, a.bin_start[bin + 1], (unsigned long long)a.capacity + 1ull);
     GSR_BOUND(depth, 1, a.bin_start[bin], (unsigned long long)a.bin_start[bin + 1] + 1ull);
 
-    DepthPixel p00 = depth_pixel_start(), p10 = p00, p01 = p00, p11 = p00;   // pij: pixel (x + 8i, y + 8j)
+    DepthPixel p00 = depth_pixel_start();
+    [[maybe_unused]] DepthPixel p10 = p00, p01 = p00, p11 = p00;   // pij: pixel (x + 8i, y + 8j); STEP 2: p00 only
 
     for (uint32_t base = begin; base < end; base += DEPTH_CHUNK) {
         __syncthreads();   // the previous chunk is consumed
@@ -179,23 +189,37 @@ __global__ __launch_bounds__(DEPTH_THREADS) void k_depth_planes(DepthBuffers a, 
                 en.ux = ra.x; en.uy = ra.y; en.ncu = ra.z; en.wx = ra.w; en.wy = rb.x; en.ncw = rb.y; en.la = rb.z; en.z = rb.w;
                 en.index = s_idx[cell];
                 const float ur0 = depth_row_u(en, pyf0), wr0 = depth_row_w(en, pyf0);
-                const float ur1 = depth_row_u(en, pyf1), wr1 = depth_row_w(en, pyf1);
-                depth_accumulate(p00, depth_weight(en, pxf0, ur0, wr0), en.z, en.index, a.hit_alpha);
-                depth_accumulate(p10, depth_weight(en, pxf1, ur0, wr0), en.z, en.index, a.hit_alpha);
-                depth_accumulate(p01, depth_weight(en, pxf0, ur1, wr1), en.z, en.index, a.hit_alpha);
-                depth_accumulate(p11, depth_weight(en, pxf1, ur1, wr1), en.z, en.index, a.hit_alpha);
+                if constexpr (STEP == 1) {
+                    const float ur1 = depth_row_u(en, pyf1), wr1 = depth_row_w(en, pyf1);
+                    depth_accumulate(p00, depth_weight(en, pxf0, ur0, wr0), en.z, en.index, a.hit_alpha);
+                    depth_accumulate(p10, depth_weight(en, pxf1, ur0, wr0), en.z, en.index, a.hit_alpha);
+                    depth_accumulate(p01, depth_weight(en, pxf0, ur1, wr1), en.z, en.index, a.hit_alpha);
+                    depth_accumulate(p11, depth_weight(en, pxf1, ur1, wr1), en.z, en.index, a.hit_alpha);
+                } else {
+                    depth_accumulate(p00, depth_weight(en, pxf0, ur0, wr0), en.z, en.index, a.hit_alpha);
+                }
             }
         }
     }
 
-    const int x0 = binX0 + ox + lx, x1 = x0 + 8, y0 = binY0 + oy + ly, y1 = y0 + 8;
-    auto store = [&](int x, int y, const DepthPixel& p) {
+    if constexpr (STEP == 1) {
+        const int x0 = binX0 + ox + lx, x1 = x0 + 8, y0 = binY0 + oy + ly, y1 = y0 + 8;
+        auto store = [&](int x, int y, const DepthPixel& p) {
+            if (x < g.W && y < g.H) {
+                const size_t o = (size_t)y * g.W + x;
+                a.mean[o] = p.D; a.hit[o] = p.hit_z; a.index[o] = p.hit;
+            }
+        };
+        store(x0, y0, p00); store(x1, y0, p10); store(x0, y1, p01); store(x1, y1, p11);
+    } else {
+        const int x = binX0 + ox + STEP * lx, y = binY0 + oy + STEP * ly;   // (even: bins and tiles start on even pixels)
         if (x < g.W && y < g.H) {
-            const size_t o = (size_t)y * g.W + x;
-            a.mean[o] = p.D; a.hit[o] = p.hit_z; a.index[o] = p.hit;
+            const int Wd = (g.W + STEP - 1) / STEP;
+            const size_t o = (size_t)(y / STEP) * Wd + x / STEP;
+            GSR_BOUND(depth, 5, o, (size_t)Wd * ((g.H + STEP - 1) / STEP));
+            a.hit[o] = p00.hit_z;
         }
-    };
-    store(x0, y0, p00); store(x1, y0, p10); store(x0, y1, p01); store(x1, y1, p11);
+    }
 }
 
 // One wave per query pixel: 64 entries of the pixel's bin list per step, every lane the weight and z of its entry, then the
@@ -254,12 +278,18 @@ __global__ void k_depth_fill(float* __restrict__ mean, float* __restrict__ hit, 
     mean[i] = 0.0f; hit[i] = __uint_as_float(0x7f800000u); index[i] = HIT_NONE;
 }
 
-void launch_depth_planes(const DepthBuffers& b, const BinGrid& g, const CamParams& cam, bool skip, hipStream_t s)
+void launch_depth_planes(const DepthBuffers& b, const BinGrid& g, const CamParams& cam, bool skip, int step, hipStream_t s)
 {
     const int nbins = (g.bx_hi - g.bx_lo) * g.nby;
     if (nbins <= 0) return;
-    if (skip) hipLaunchKernelGGL(k_depth_planes<true>, dim3(nbins), dim3(DEPTH_THREADS), 0, s, b, g, cam);
-    else hipLaunchKernelGGL(k_depth_planes<false>, dim3(nbins), dim3(DEPTH_THREADS), 0, s, b, g, cam);
+    const dim3 grid(nbins), block(DEPTH_THREADS);
+    if (step == 2) {
+        if (skip) hipLaunchKernelGGL((k_depth_planes<true, 2>), grid, block, 0, s, b, g, cam);
+        else hipLaunchKernelGGL((k_depth_planes<false, 2>), grid, block, 0, s, b, g, cam);
+    } else {
+        if (skip) hipLaunchKernelGGL((k_depth_planes<true, 1>), grid, block, 0, s, b, g, cam);
+        else hipLaunchKernelGGL((k_depth_planes<false, 1>), grid, block, 0, s, b, g, cam);
+    }
 }
 
 void launch_pick(const DepthBuffers& b, const BinGrid& g, const CamParams& cam, const int32_t* xy, uint32_t count, PickResult* out, hipStream_t s)

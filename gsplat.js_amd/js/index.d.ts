@@ -104,6 +104,23 @@ export interface DeliveryOptions {
     fullRange?: boolean;
     /** Y'CbCr carries no alpha: the [R, G, B] bytes the premultiplied frame is laid over; default black */
     background?: [number, number, number];
+    /** a depth plane beside every frame, for a client that reprojects between server frames (not in a group) */
+    depth?: DepthDeliveryOptions;
+}
+export type DepthDeliveryFormat = "f32" | "u16";
+export interface DepthDeliveryOptions {
+    /** "u16" (default): 16-bit inverse depth against `near` -- 0 no hit, 65535 at or in front of `near`, z ~ near * 65535 / u;
+     *  "f32": the hit depth as it is, +Infinity without a hit */
+    format?: DepthDeliveryFormat;
+    /** 1 (default) or 2: the plane holds pixel (step * i, step * j) at (i, j): ceil(width / step) x ceil(height / step) samples */
+    step?: 1 | 2;
+    /** "u16": the depth that maps to 65535; > 0, default 0.1 */
+    near?: number;
+}
+export interface DepthLayout {
+    format: DepthDeliveryFormat; step: number; width: number; height: number;
+    /** bytes per row, and where the plane lies in the slot's ArrayBuffer (`depth.byteOffset`) */
+    stride: number; offset: number; bytes: number; near: number;
 }
 /** a view of one plane of a delivered frame, `rows` rows of `stride` bytes */
 export type DeliveredPlane = Uint8Array & { stride: number; rows: number };
@@ -122,6 +139,10 @@ export interface DeliveredFrame {
     format: DeliveryFormat;
     /** views of `pixels.buffer`: one for "rgba8", Y and CbCr for "nv12", Y, Cb and Cr for "i420" */
     planes: DeliveredPlane[];
+    /** a depth ring only: the SAME frame's hit depth, row 0 = top, `depthLayout.width` x `depthLayout.height` samples; a view of
+     *  `pixels.buffer` behind the colour payload, valid until release() */
+    depth?: Uint16Array | Float32Array;
+    depthLayout?: DepthLayout;
     release(): void;
 }
 export class HIPRenderer {
@@ -186,6 +207,8 @@ export class HIPRenderer {
     openDelivery(slots?: number, options?: DeliveryOptions): void;
     /** the open ring's frame layout at the current size (it follows setSize) */
     deliveryLayout(): DeliveryLayout;
+    /** the depth plane of the open depth ring's frames at the current size; throws on a ring without depth */
+    depthLayout(): DepthLayout;
     /** throws while a frame is held; detaches the slots' ArrayBuffers (old `pixels` views then have length 0) */
     closeDelivery(): void;
     /** enqueue the delivery of the frame enqueued last; returns its serial (1, 2, 3 ...).  Throws ("... (-7) ...") and

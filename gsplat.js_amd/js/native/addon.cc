@@ -461,7 +461,7 @@ void release_handle_ref(napi_env env, void*, void* hint)
     if (hint) napi_delete_reference(env, static_cast<napi_ref>(hint));
 }
 
-// deliverySlots(handle) -> [ArrayBuffer, ...], one per slot of the open ring
+// deliverySlots(handle) -> [ArrayBuffer, ...], one per slot of the open ring: the colour payload (a depth ring: up to the depth plane's end)
 napi_value DeliverySlots(napi_env env, napi_callback_info info)
 {
     napi_value argv[1];
@@ -474,6 +474,8 @@ napi_value DeliverySlots(napi_env env, napi_callback_info info)
         uint64_t bytes = 0;
         void* p = gsr_delivery_slot_ptr(c, k, &bytes);
         if (!p) break;
+        gsr_depth_layout dl;   // a depth ring: the buffer spans the colour payload AND the depth plane behind it
+        if (gsr_delivery_depth_layout(c, &dl) == GSR_OK) bytes = dl.offset + dl.bytes;
         napi_ref keep = nullptr;
         NAPI_OK_OR_NULL(env, napi_create_reference(env, argv[0], 1, &keep));
         napi_value ab;
@@ -516,6 +518,53 @@ napi_value OpenDeliveryEx(napi_env env, napi_callback_info info)
     const int rc = gsr_delivery_open_ex(c, &opt);
     if (rc) return throw_gsr(env, c, rc, "gsr_delivery_open_ex");
     return DeliverySlots(env, info);
+}
+
+// openDeliveryDepth(handle, slots, format, fullRange, bgR, bgG, bgB, depthFormat, depthStep, depthNear) -> [ArrayBuffer, ...]: openDeliveryEx's
+// ring with a depth plane in GSR_DEPTH_* beside every frame (gsr_delivery_open_depth)
+napi_value OpenDeliveryDepth(napi_env env, napi_callback_info info)
+{
+    napi_value argv[10];
+    if (!get_args(env, info, 10, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    int32_t v[8];
+    double near = 0;
+    if (!c) return nullptr;
+    for (int k = 0; k < 8; k++)
+        if (!get_i32(env, argv[1 + k], &v[k])) { napi_throw_type_error(env, nullptr, "openDeliveryDepth(handle, slots, format, fullRange, r, g, b, depthFormat, depthStep, depthNear)"); return nullptr; }
+    if (!get_f64(env, argv[9], &near)) { napi_throw_type_error(env, nullptr, "openDeliveryDepth: depthNear must be a number"); return nullptr; }
+    gsr_delivery_options opt{};
+    opt.slots = v[0]; opt.format = v[1]; opt.full_range = v[2];
+    for (int k = 0; k < 3; k++) opt.background[k] = (uint8_t)std::min(255, std::max(0, v[3 + k]));
+    gsr_depth_delivery_options depth{};
+    depth.format = v[6]; depth.step = v[7]; depth.near = (float)near;
+    const int rc = gsr_delivery_open_depth(c, &opt, &depth);
+    if (rc) return throw_gsr(env, c, rc, "gsr_delivery_open_depth");
+    return DeliverySlots(env, info);
+}
+
+// depthLayout(handle) -> { format, step, width, height, stride, offset, bytes, near } of the open depth ring
+napi_value DepthLayout(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    if (!c) return nullptr;
+    gsr_depth_layout dl;
+    const int rc = gsr_delivery_depth_layout(c, &dl);
+    if (rc) return throw_gsr(env, c, rc, "gsr_delivery_depth_layout");
+    auto set = [&](napi_value obj, const char* key, double value) {
+        napi_value v;
+        return napi_create_double(env, value, &v) == napi_ok && napi_set_named_property(env, obj, key, v) == napi_ok;
+    };
+    napi_value out;
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    if (!(set(out, "format", dl.format) && set(out, "step", dl.step) && set(out, "width", dl.width) && set(out, "height", dl.height) &&
+          set(out, "stride", dl.stride) && set(out, "offset", (double)dl.offset) && set(out, "bytes", (double)dl.bytes) && set(out, "near", dl.near))) {
+        napi_throw_error(env, nullptr, "depthLayout: building the result failed");
+        return nullptr;
+    }
+    return out;
 }
 
 // deliveryLayout(handle) -> { format, width, height, bytes, planes: [{ offset, stride, rows }, ...] } of the open ring
@@ -739,6 +788,7 @@ napi_value Init(napi_env env, napi_value exports)
         {"commDestroy", Call0<gsr_comm_destroy>}, {"allgatherFrameAsync", Call0<gsr_allgather_frame_async>}, {"readFrame", ReadFrame},
         {"openDelivery", OpenDelivery}, {"closeDelivery", Call0<gsr_delivery_close>}, {"deliverySlots", DeliverySlots}, {"detachBuffers", DetachBuffers},
         {"openDeliveryEx", OpenDeliveryEx}, {"deliveryLayout", DeliveryLayout},
+        {"openDeliveryDepth", OpenDeliveryDepth}, {"depthLayout", DepthLayout},
         {"deliverFrame", DeliverFrame}, {"frameReady", FrameReady}, {"acquireFrame", AcquireFrame}, {"releaseFrame", ReleaseFrame},
         {"setHitAlpha", SetHitAlpha}, {"depthAsync", Call0<gsr_depth_async>}, {"readDepth", ReadDepth}, {"pick", Pick},
     };

@@ -62,19 +62,34 @@ class HIPRenderer {
         // For a video encoder: openDelivery(3, { format: "nv12" | "i420", fullRange: false, background: [0, 0, 0] }) delivers 4:2:0 Y'CbCr
         // (BT.709), 1.5 bytes per pixel.  `pixels` is then the whole payload, as `ffmpeg -f rawvideo -pix_fmt nv12 | yuv420p` reads
         // it -- process.stdout.write(f.pixels) -- and `planes` its parts: Uint8Array views carrying `stride` and `rows`.
-        const FORMATS = ["rgba8", "nv12", "i420"];
-        let slotBuffers = null, slotViews = null, slotPlanes = null, ringFormat = "rgba8";
+        // For a client that reprojects: openDelivery(3, { format, depth: { format: "u16" | "f32", step: 1 | 2, near: 0.1 } }) delivers, beside
+        // every frame, that frame's hit depth at every step-th pixel in both directions: `f.depth`, a Uint16Array (inverse depth against
+        // `near`: 0 no hit, 65535 at or in front of near, z ~ near * 65535 / u) or Float32Array view of the same block, and `f.depthLayout`.
+        const FORMATS = ["rgba8", "nv12", "i420"], DEPTH_FORMATS = ["none", "f32", "u16"];
+        let slotBuffers = null, slotViews = null, slotPlanes = null, ringFormat = "rgba8", slotDepth = null, ringDepthLayout = null;
         const held = new Map();                  // serial -> frame object
         const wrapSlots = (buffers) => {
             const layout = this._n.deliveryLayout(this._h);
             slotBuffers = buffers;
-            slotViews = buffers.map((b) => new Uint8Array(b));
+            slotViews = buffers.map((b) => new Uint8Array(b, 0, layout.bytes));   // (a depth ring's buffer goes on behind the colour payload)
             slotPlanes = buffers.map((b) => layout.planes.map((p) => Object.assign(new Uint8Array(b, p.offset, p.stride * p.rows), { stride: p.stride, rows: p.rows })));
             ringFormat = FORMATS[layout.format];
+            slotDepth = ringDepthLayout = null;
+            if (buffers.length && buffers[0].byteLength > layout.bytes) {   // a depth ring
+                const d = this._n.depthLayout(this._h);
+                d.format = DEPTH_FORMATS[d.format];
+                ringDepthLayout = d;
+                slotDepth = buffers.map((b) => (d.format === "u16" ? new Uint16Array(b, d.offset, d.width * d.height) : new Float32Array(b, d.offset, d.width * d.height)));
+            }
         };
         const dropSlots = () => {
             if (slotBuffers) this._n.detachBuffers(slotBuffers);
-            slotBuffers = slotViews = slotPlanes = null;
+            slotBuffers = slotViews = slotPlanes = slotDepth = ringDepthLayout = null;
+        };
+        this.depthLayout = () => {
+            const d = this._n.depthLayout(this._h);
+            d.format = DEPTH_FORMATS[d.format];
+            return d;
         };
         this.deliveryLayout = () => {
             const layout = this._n.deliveryLayout(this._h);
@@ -89,7 +104,12 @@ class HIPRenderer {
             const o = options || {}, format = FORMATS.indexOf(o.format === undefined ? "rgba8" : o.format), bg = o.background || [0, 0, 0];
             if (format < 0) throw new Error("openDelivery: format must be one of " + FORMATS.join(", "));
             const n = slots === undefined ? 3 : slots;
-            if (format === 0) {
+            if (o.depth) {                       // (refused by the library while a ring is open: closeDelivery() first)
+                const depth = DEPTH_FORMATS.indexOf(o.depth.format === undefined ? "u16" : o.depth.format);
+                if (depth < 1) throw new Error("openDelivery: depth.format must be one of f32, u16");
+                const step = o.depth.step === undefined ? 1 : o.depth.step, near = o.depth.near === undefined ? 0.1 : o.depth.near;
+                wrapSlots(this._n.openDeliveryDepth(this._h, n, format, o.fullRange ? 1 : 0, bg[0] | 0, bg[1] | 0, bg[2] | 0, depth, step | 0, +near));
+            } else if (format === 0) {
                 dropSlots();
                 wrapSlots(this._n.openDelivery(this._h, n));
             } else {                             // (refused by the library while a ring is open: closeDelivery() first)
@@ -109,6 +129,7 @@ class HIPRenderer {
         this.acquireFrame = (serial) => {
             const f = this._n.acquireFrame(this._h, serial || 0);
             const frame = { serial: f[0], pixels: slotViews[f[1]], width: this.width, height: this.height, format: ringFormat, planes: slotPlanes[f[1]],
+                            depth: slotDepth ? slotDepth[f[1]] : undefined, depthLayout: ringDepthLayout || undefined,
                             release: () => { if (held.delete(frame.serial)) this._n.releaseFrame(this._h, frame.serial); } };
             held.set(frame.serial, frame);
             return frame;

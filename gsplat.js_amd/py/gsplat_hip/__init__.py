@@ -57,8 +57,20 @@ class GsrFrameLayout(ctypes.Structure):
                 ("offset", ctypes.c_uint64 * 3), ("stride", ctypes.c_int32 * 3), ("rows", ctypes.c_int32 * 3), ("bytes", ctypes.c_uint64)]
 
 
+class GsrDepthDeliveryOptions(ctypes.Structure):
+    _fields_ = [("format", ctypes.c_int32), ("step", ctypes.c_int32), ("near", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
+class GsrDepthLayout(ctypes.Structure):
+    _fields_ = [("format", ctypes.c_int32), ("step", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("stride", ctypes.c_int32), ("reserved", ctypes.c_int32), ("offset", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
+                ("near", ctypes.c_float), ("reserved2", ctypes.c_int32)]
+
+
 GSR_FORMAT_RGBA8, GSR_FORMAT_NV12, GSR_FORMAT_I420 = 0, 1, 2
 DELIVERY_FORMATS = {"rgba8": GSR_FORMAT_RGBA8, "nv12": GSR_FORMAT_NV12, "i420": GSR_FORMAT_I420}
+GSR_DEPTH_NONE, GSR_DEPTH_F32, GSR_DEPTH_U16 = 0, 1, 2
+DEPTH_DELIVERY_FORMATS = {"f32": GSR_DEPTH_F32, "u16": GSR_DEPTH_U16}
 
 
 def edge_arrays(edges):
@@ -88,6 +100,7 @@ EXPORTS = [
     "gsr_frame8_device_ptr", "gsr_comm_stream_handle", "gsr_read_work_items", "gsr_comm_share", "gsr_comm_init_custom",
     "gsr_delivery_open", "gsr_delivery_close", "gsr_deliver_frame_async", "gsr_frame_ready", "gsr_acquire_frame",
     "gsr_release_frame", "gsr_delivery_slot_ptr", "gsr_delivery_open_ex", "gsr_delivery_layout",
+    "gsr_delivery_open_depth", "gsr_delivery_depth_layout",
     "gsr_set_hit_alpha", "gsr_depth_async", "gsr_read_depth", "gsr_depth_device_ptr", "gsr_pick",
 ]
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p)
@@ -201,6 +214,8 @@ def load_library(path=None):
     L.gsr_delivery_slot_ptr.restype = vp
     L.gsr_delivery_open_ex.argtypes = [vp, ctypes.POINTER(GsrDeliveryOptions)]
     L.gsr_delivery_layout.argtypes = [vp, ctypes.POINTER(GsrFrameLayout)]
+    L.gsr_delivery_open_depth.argtypes = [vp, ctypes.POINTER(GsrDeliveryOptions), ctypes.POINTER(GsrDepthDeliveryOptions)]
+    L.gsr_delivery_depth_layout.argtypes = [vp, ctypes.POINTER(GsrDepthLayout)]
     L.gsr_set_hit_alpha.argtypes = [vp, ctypes.c_float]
     L.gsr_depth_async.argtypes = [vp]
     L.gsr_read_depth.argtypes = [vp, vp, vp, vp]
@@ -337,7 +352,8 @@ class HIPRenderer:
         self._scene = None
         self._camera = None
         self._n = 0
-        self._slot_views = {}   # delivery slot -> [H, W, 4] uint8 view of its pinned block
+        self._slot_views = {}   # delivery slot -> [H, W, 4] uint8 view of its pinned block (a depth ring: that and the depth view)
+        self._depth_ring = False
         self._on_change = lambda _e: self._upload(self._scene)
 
     # -- helpers --
@@ -520,12 +536,45 @@ class HIPRenderer:
         self._slot_views = {}
         if format == "rgba8":
             self._check(self._L.gsr_delivery_open(self._ctx, slots))
+            self._depth_ring = False
             return
+        self._check(self._L.gsr_delivery_open_ex(self._ctx, ctypes.byref(self._delivery_options(slots, format, full_range, background))))
+        self._depth_ring = False
+
+    @staticmethod
+    def _delivery_options(slots, format, full_range, background):
         bg = [int(v) for v in background]
         if len(bg) != 3 or min(bg) < 0 or max(bg) > 255:
             raise ValueError("background must be three bytes (R, G, B)")
-        opt = GsrDeliveryOptions(slots, DELIVERY_FORMATS[format], 1 if full_range else 0, (ctypes.c_uint8 * 4)(*bg, 0))
-        self._check(self._L.gsr_delivery_open_ex(self._ctx, ctypes.byref(opt)))
+        return GsrDeliveryOptions(slots, DELIVERY_FORMATS[format], 1 if full_range else 0, (ctypes.c_uint8 * 4)(*bg, 0))
+
+    def open_delivery_depth(self, slots=3, format="rgba8", full_range=False, background=(0, 0, 0), depth="u16", depth_step=1, depth_near=0.1):
+        """open_delivery's ring with a depth plane beside every frame (gsr_delivery_open_depth; opened only when no ring is open):
+        colour exactly as open_delivery(slots, format, full_range, background) delivers it, and the frame's hit plane (read_depth()[1])
+        sampled at every `depth_step`-th pixel (1 or 2) in both directions -- `depth` "f32": as it is; "u16": 16-bit inverse depth
+        against `depth_near` (0: no hit, 65535: at or in front of depth_near; z ~ depth_near * 65535 / u).  acquire() then returns
+        (serial, pixels or planes, depth).  depth=None: open_delivery.  (A method of its own, as the C ABI has an entry point of its
+        own: open_delivery keeps the signature its callers know.)"""
+        if format not in DELIVERY_FORMATS:
+            raise ValueError("format must be one of %s" % ", ".join(sorted(DELIVERY_FORMATS)))
+        if depth is None:
+            return self.open_delivery(slots, format, full_range, background)
+        if depth not in DEPTH_DELIVERY_FORMATS:
+            raise ValueError("depth must be None or one of %s" % ", ".join(sorted(DEPTH_DELIVERY_FORMATS)))
+        self._slot_views = {}
+        opt = self._delivery_options(slots, format, full_range, background)
+        dopt = GsrDepthDeliveryOptions(DEPTH_DELIVERY_FORMATS[depth], int(depth_step), float(depth_near), 0)
+        self._check(self._L.gsr_delivery_open_depth(self._ctx, ctypes.byref(opt), ctypes.byref(dopt)))
+        self._depth_ring = True
+
+    def depth_layout(self):
+        """The depth plane of the open depth ring's frames at the current size (gsr_delivery_depth_layout): format ("f32" / "u16"),
+        step, width and height (Wd, Hd), stride, offset (bytes from the slot's first pixel), bytes, near."""
+        lay = GsrDepthLayout()
+        self._check(self._L.gsr_delivery_depth_layout(self._ctx, ctypes.byref(lay)))
+        names = {v: k for k, v in DEPTH_DELIVERY_FORMATS.items()}
+        return {"format": names[lay.format], "step": lay.step, "width": lay.width, "height": lay.height, "stride": lay.stride,
+                "offset": int(lay.offset), "bytes": int(lay.bytes), "near": float(lay.near)}
 
     def delivery_layout(self):
         """The open ring's frame layout at the current size (gsr_delivery_layout): format, width, height, bytes (the payload) and
@@ -539,6 +588,7 @@ class HIPRenderer:
     def close_delivery(self):
         self._slot_views = {}
         self._check(self._L.gsr_delivery_close(self._ctx))
+        self._depth_ring = False
 
     def deliver(self):
         """Enqueue the delivery of the frame enqueued last (in a group: of the frame gathered last); returns its serial.
@@ -559,7 +609,9 @@ class HIPRenderer:
         release(serial).  On a Y'CbCr ring: (serial, planes), a tuple of such views -- Y [H, W] and CbCr [Hc, Wc, 2] for "nv12",
         Y [H, W], Cb [Hc, Wc] and Cr [Hc, Wc] for "i420" (Hc = (H + 1) // 2, Wc = (W + 1) // 2), contiguous in the block: the
         payload a rawvideo pipe takes is the planes' bytes one after the other.  A frame that was not composited (list overflow) raises GsplatError with code GSR_ERR_OVERFLOW
-        and frees its slot: render and deliver that pose again."""
+        and frees its slot: render and deliver that pose again.
+        On a depth ring (open_delivery_depth): (serial, pixels or planes, depth), depth a read-only zero-copy [Hd, Wd] float32 /
+        uint16 view of the same block: the hit plane of the SAME frame (depth_layout())."""
         f = GsrFrame()
         self._check(self._L.gsr_acquire_frame(self._ctx, serial, ctypes.byref(f)))
         view = self._slot_views.get(f.slot)
@@ -575,7 +627,16 @@ class HIPRenderer:
                 if lay.format == GSR_FORMAT_NV12:
                     planes[1] = planes[1].reshape(lay.rows[1], lay.stride[1] // 2, 2)
                 view = tuple(planes)
+            if self._depth_ring:
+                dl = GsrDepthLayout()
+                self._check(self._L.gsr_delivery_depth_layout(self._ctx, ctypes.byref(dl)))
+                dtype = np.float32 if dl.format == GSR_DEPTH_F32 else np.uint16
+                depth = np.frombuffer((ctypes.c_uint8 * dl.bytes).from_address(f.pixels + dl.offset), dtype=dtype).reshape(dl.height, dl.width)
+                depth.flags.writeable = False
+                view = (view, depth)
             self._slot_views[f.slot] = view
+        if self._depth_ring:
+            return f.serial, view[0], view[1]
         return f.serial, view
 
     def release(self, serial):

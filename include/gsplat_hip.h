@@ -331,6 +331,57 @@ int gsr_delivery_open_ex(gsr_ctx *ctx, const gsr_delivery_options *opt);
 /* The layout of the open ring's frames at the current size; GSR_ERR_ARG without a ring. */
 int gsr_delivery_layout(gsr_ctx *ctx, gsr_frame_layout *out);
 
+/* ---- frame delivery with depth: a depth plane beside every delivered frame, for clients that reproject ----
+ * A ring opened with gsr_delivery_open_depth delivers, with the colour of every frame, the "hit" plane of that frame (see
+ * "depth and pick" below: z of the first fragment at which accumulated alpha reaches hit_alpha, +infinity without one; the
+ * context's hit_alpha at the time of gsr_deliver_frame_async).  gsr_deliver_frame_async then also enqueues, on the render
+ * stream behind the frame and the colour conversion, a depth pass for that frame and its conversion into the slot; the slot's
+ * ONE copy carries colour payload, depth plane and trailer, and gsr_acquire_frame for serial k gives the colour of frame k and
+ * the depth of frame k.  No host wait is added.  The pass has buffers of its own: gsr_read_depth, gsr_depth_device_ptr and
+ * gsr_pick answer exactly as they do without a depth ring.
+ * The plane, step s = 1 or 2: Wd = ceil(width / s) columns, Hd = ceil(height / s) rows, row 0 = top;
+ * sample (i, j) is the hit value of pixel (s * i, s * j) -- a point sample, bit for bit what gsr_read_depth holds at that
+ * pixel; no filter, no minimum over the block.
+ *   GSR_DEPTH_F32: the float as it is, stride 4 * Wd.
+ *   GSR_DEPTH_U16: inverse depth against `near`, little-endian uint16_t, stride 2 * Wd (ffmpeg: -pix_fmt gray16le -s WdxHd), in
+ *     binary32: u = 65535 unless z > 0; otherwise q = min(near / z, 1), u = rint(q * 65535) (ties to even).  No hit is 0,
+ *     anything at or in front of `near` is 65535, and z ~ near * 65535 / u.
+ * A band context delivers +infinity (F32) / 0 (U16) outside its bin columns.
+ * A slot: the colour payload exactly as the same ring without depth holds it (gsr_delivery_layout and gsr_delivery_slot_ptr
+ * report the colour payload, as they do for every ring), the plane at gsr_depth_layout.offset bytes from gsr_frame.pixels (a
+ * multiple of 16), the trailer behind the plane.
+ * Everything said of rings above holds: serials, GSR_ERR_BUSY, gsr_frame_ready, gsr_release_frame, gsr_sync, gsr_destroy,
+ * gsr_delivery_close; gsr_resize reallocates the ring and the depth layout follows the new size; a frame whose lists did not fit
+ * is refused by gsr_acquire_frame with GSR_ERR_OVERFLOW (the depth pass wrote nothing for it) and its slot is freed.
+ * gsr_deliver_frame_async on a depth ring needs what gsr_depth_async needs -- a render frame; scene, size, band and list
+ * buffers unchanged since -- and otherwise returns GSR_ERR_ARG, enqueues nothing and takes no slot.
+ * Groups: depth is not exchanged between ranks.  gsr_delivery_open_depth with a depth format on a context in a group returns
+ * GSR_ERR_ARG, and so does gsr_deliver_frame_async on a context that joined a group after it opened a depth ring.
+ * A context that never opens a depth ring allocates and launches nothing of this. */
+#define GSR_DEPTH_NONE 0
+#define GSR_DEPTH_F32  1
+#define GSR_DEPTH_U16  2
+typedef struct gsr_depth_delivery_options {
+    int32_t format;         /* GSR_DEPTH_* */
+    int32_t step;           /* 1 or 2 */
+    float near;             /* GSR_DEPTH_U16: > 0, finite; ignored otherwise */
+    int32_t reserved;       /* 0 */
+} gsr_depth_delivery_options;
+typedef struct gsr_depth_layout {
+    int32_t format, step, width, height;   /* width, height: Wd, Hd */
+    int32_t stride, reserved;
+    uint64_t offset;        /* of the plane, in bytes from gsr_frame.pixels; a multiple of 16 */
+    uint64_t bytes;         /* stride * height */
+    float near;
+    int32_t reserved2;
+} gsr_depth_layout;
+/* Colour as gsr_delivery_open_ex(ctx, opt) would deliver it, plus the depth plane.  depth == NULL or format GSR_DEPTH_NONE:
+ * exactly gsr_delivery_open_ex.  GSR_ERR_ARG: what gsr_delivery_open_ex refuses; an unknown depth format, a step other than 1
+ * or 2, GSR_DEPTH_U16 with a near that is not finite and > 0, reserved != 0, a context in a group. */
+int gsr_delivery_open_depth(gsr_ctx *ctx, const gsr_delivery_options *opt, const gsr_depth_delivery_options *depth);
+/* The depth plane of the open ring's frames at the current size; GSR_ERR_ARG: no ring, or a ring without depth. */
+int gsr_delivery_depth_layout(gsr_ctx *ctx, gsr_depth_layout *out);
+
 /* ---- depth and pick: per-pixel depth planes of the last rendered frame, and the splat under a pixel ----
  * No interface of the reference stands behind this section (its renderer returns colour only, WebGLRenderer.ts:241-296): it
  * is what a viewer builds "double-click sets the orbit target" and "click selects" from, and what a compositor or a

@@ -16,11 +16,15 @@ Every delivered leg compares its last delivered frame with readPixels() of the s
 (`delivered_equals_read_pixels`).  --format nv12|i420 opens the rings in 4:2:0 Y'CbCr (BT.709 limited range, black background):
 the same legs and keys, `bytes_per_frame` of the format, and the comparison goes through the definition in plain numpy
 (tests/yuv_reference.py applied to readPixels() of the same pose: `delivered_equals_reference`).
+--depth f32|u16 [--depth-step 1|2] [--depth-near X] opens depth rings (gsr_delivery_open_depth): the same legs and keys with a
+depth plane beside every frame, `depth_bytes_per_frame`, and the last delivered plane compared with the definition
+(tests/depth_delivery_reference.py applied to read_depth() of the same pose: `delivered_depth_equals_reference`).
 --timed-only runs nothing but the warm-up and the timed `delivered` loop of the chosen configuration (with
 --frames-in-flight F > 1: the F-context loop): the run a profiler wraps.
 
   python scripts/bench_delivery.py [--config C3] [--frames 480] [--warmup 30] [--slots 3] [--frames-in-flight 3]
                                    [--other C2,C4] [--timed-only] [--format rgba8|nv12|i420]
+                                   [--depth f32|u16] [--depth-step 1|2] [--depth-near 0.1]
 There is no CPU path: without an MI355X the script fails."""
 import argparse
 import json
@@ -46,24 +50,34 @@ FORMAT = "rgba8"      # --format: what every ring of this run is opened for
 
 
 def same_key():
+    if DEPTH:
+        return "delivered_depth_equals_reference"    # (colour and depth both)
     return "delivered_equals_read_pixels" if FORMAT == "rgba8" else "delivered_equals_reference"
 
 
+DEPTH = None          # --depth: None, or the depth plane every ring of this run carries ("f32" / "u16")
+DEPTH_STEP = 1
+DEPTH_NEAR = 0.1
+
+
 def open_ring(r, slots):
-    r.open_delivery(slots) if FORMAT == "rgba8" else r.open_delivery(slots, format=FORMAT)
+    if DEPTH:
+        r.open_delivery_depth(slots, format=FORMAT, depth=DEPTH, depth_step=DEPTH_STEP, depth_near=DEPTH_NEAR)
+    else:
+        r.open_delivery(slots) if FORMAT == "rgba8" else r.open_delivery(slots, format=FORMAT)
 
 
 def delivered_run(ctxs, poses, fx, count, slots):
     """`count` orbit frames, every one delivered: the contexts round-robin, a context's oldest frame acquired and released only
     when its ring is full.  Returns (frames/s, the last delivered frame equals readPixels() of the same pose -- for a Y'CbCr
-    ring: the numpy reference's payload of it)."""
+    ring: the numpy reference's payload of it; on a depth ring: and its depth plane equals the reference's of read_depth())."""
     pending = [[] for _ in ctxs]
     last = None
 
     def pick_up(c):
         nonlocal last
-        s, px = ctxs[c].acquire(pending[c].pop(0))
-        last = (c, px)
+        s, px, *depth = ctxs[c].acquire(pending[c].pop(0))
+        last = (c, px, depth[0] if depth else None)
         ctxs[c].release(s)
 
     t0 = time.perf_counter()
@@ -78,16 +92,24 @@ def delivered_run(ctxs, poses, fx, count, slots):
         while pending[j % len(ctxs)]:
             pick_up(j % len(ctxs))
     fps = count / (time.perf_counter() - t0)
-    c, px = last
+    c, px, depth = last
     # (its slot is released, but nothing has been delivered since)
     got = px.copy() if FORMAT == "rgba8" else np.concatenate([plane.ravel() for plane in px])
+    got_depth = depth.copy() if DEPTH else None
     ctxs[c].set_camera_arrays(*poses[(count - 1) % ORBIT_FRAMES], fx, fx)
     ctxs[c].render_async()
     want = ctxs[c].readPixels()
     if FORMAT != "rgba8":
         import yuv_reference
         want = yuv_reference.payload(want, FORMAT)
-    return fps, bool(np.array_equal(got, want))
+    same = bool(np.array_equal(got, want))
+    if DEPTH:
+        import depth_delivery_reference as ddr
+        want_depth = ddr.subsample(ctxs[c].read_depth()[1], DEPTH_STEP)
+        if DEPTH == "u16":
+            want_depth = ddr.quantise_u16(want_depth, DEPTH_NEAR)
+        same = same and got_depth.dtype == want_depth.dtype and bool(np.array_equal(got_depth.view(np.uint8), want_depth.view(np.uint8)))
+    return fps, same
 
 
 def make_contexts(gh, cfg, rows, poses, count, throughput, device):
@@ -113,6 +135,9 @@ def measure(gh, name, args, full):
            "bytes_per_frame": W * H * 4 if FORMAT == "rgba8" else W * H + 2 * ((W + 1) // 2) * ((H + 1) // 2)}
     if FORMAT != "rgba8":
         out["format"] = FORMAT
+    if DEPTH:
+        Wd, Hd = (W + DEPTH_STEP - 1) // DEPTH_STEP, (H + DEPTH_STEP - 1) // DEPTH_STEP
+        out.update({"depth": DEPTH, "depth_step": DEPTH_STEP, "depth_near": DEPTH_NEAR, "depth_bytes_per_frame": Wd * Hd * (4 if DEPTH == "f32" else 2)})
     if args.timed_only:
         rs = make_contexts(gh, cfg, rows, poses, F, F > 1, args.device)
         for rr in rs:
@@ -159,7 +184,7 @@ def measure(gh, name, args, full):
             t0 = time.perf_counter()
             r.set_camera_arrays(*poses[k], fx, fx)
             r.render_async()
-            s, _px = r.acquire(r.deliver())
+            s = r.acquire(r.deliver())[0]
             lat_d.append((time.perf_counter() - t0) * 1e3)
             r.release(s)
         out["frame_latency_ms"] = percentiles(lat)
@@ -188,9 +213,12 @@ def main():
     ap.add_argument("--timed-only", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--format", default="rgba8", choices=["rgba8", "nv12", "i420"], help="what the rings deliver (default: RGBA8)")
+    ap.add_argument("--depth", default=None, choices=["f32", "u16"], help="a depth plane beside every delivered frame (default: none)")
+    ap.add_argument("--depth-step", type=int, default=1, choices=[1, 2], help="the depth plane holds every n-th pixel in both directions")
+    ap.add_argument("--depth-near", type=float, default=0.1, help="--depth u16: the depth that maps to 65535")
     args = ap.parse_args()
-    global FORMAT
-    FORMAT = args.format
+    global FORMAT, DEPTH, DEPTH_STEP, DEPTH_NEAR
+    FORMAT, DEPTH, DEPTH_STEP, DEPTH_NEAR = args.format, args.depth, args.depth_step, args.depth_near
     import torch
     if not torch.cuda.is_available():
         sys.exit("bench_delivery.py needs an MI355X (torch.cuda.is_available() is False); there is no CPU path")

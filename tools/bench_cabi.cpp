@@ -3,7 +3,7 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--depth] [--pick X,Y]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--pick X,Y]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
@@ -11,6 +11,9 @@
 // ring is full) -- the header alone is enough to consume frames -- and reports its rate and the checksum of a delivered frame.
 // --deliver-format nv12|i420 (beside --deliver) opens the rings in 4:2:0 Y'CbCr instead of RGBA8 (gsr_delivery_open_ex, BT.709 limited
 // range, black background) and reports the checksum of the last frame's payload (gsr_delivery_layout gives its size).
+// --deliver-depth f32|u16 (beside --deliver) opens depth rings (gsr_delivery_open_depth): every delivered frame carries its hit
+// plane, at every --depth-step-th pixel (1, the default, or 2), as float or as 16-bit inverse depth against --depth-near (default
+// 0.1), and the checksum of the last frame's plane is reported (gsr_delivery_depth_layout says where it lies in the slot).
 //
 // Scene: the seeded synthetic generator of gsplat_hip/synth.py (mulberry32 counter PRNG, 24 draws per splat) written
 // out again in C++; log/exp/cos come from libm here and from numpy there, so a byte may differ in a rare rounding --
@@ -129,6 +132,9 @@ int main(int argc, char** argv)
     int frames = 240, warmup = 20, in_flight = 3;
     bool deliver = false;
     std::string deliver_format = "rgba8";
+    std::string deliver_depth = "none";
+    int depth_step = 1;
+    float depth_near = 0.1f;
     bool depth = false, pick = false;
     int32_t pick_xy[2] = {0, 0};
     for (int i = 1; i < argc; i++) {
@@ -142,15 +148,21 @@ int main(int argc, char** argv)
         else if (a == "--dump") dump = next();
         else if (a == "--deliver") deliver = true;
         else if (a == "--deliver-format") deliver_format = next();
+        else if (a == "--deliver-depth") deliver_depth = next();
+        else if (a == "--depth-step") depth_step = std::atoi(next());
+        else if (a == "--depth-near") depth_near = (float)std::atof(next());
         else if (a == "--depth") depth = true;
         else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--depth] [--pick X,Y]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--pick X,Y]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
     if (!cfg || in_flight < 1 || frames < 1) { std::fprintf(stderr, "bad arguments\n"); return 2; }
     const int32_t format = deliver_format == "nv12" ? GSR_FORMAT_NV12 : deliver_format == "i420" ? GSR_FORMAT_I420 : GSR_FORMAT_RGBA8;
     if (format == GSR_FORMAT_RGBA8 && deliver_format != "rgba8") { std::fprintf(stderr, "--deliver-format nv12|i420\n"); return 2; }
+    const int32_t depth_format = deliver_depth == "f32" ? GSR_DEPTH_F32 : deliver_depth == "u16" ? GSR_DEPTH_U16 : GSR_DEPTH_NONE;
+    if (depth_format == GSR_DEPTH_NONE && deliver_depth != "none") { std::fprintf(stderr, "--deliver-depth f32|u16\n"); return 2; }
+    if (depth_format != GSR_DEPTH_NONE && !deliver) { std::fprintf(stderr, "--deliver-depth goes beside --deliver\n"); return 2; }
 
     std::vector<uint8_t> rows;
     if (!rows_path.empty()) {
@@ -233,23 +245,29 @@ int main(int argc, char** argv)
     }
     // --deliver: the same orbit with every frame delivered; then pose 0 once more, delivered, against the blocking read above
     double delivered_sec = 0;
-    unsigned long long delivered_hash = 0;
+    unsigned long long delivered_hash = 0, delivered_depth_hash = 0;
+    gsr_depth_layout dlay{};
     uint64_t delivered = 0, sink = 0;
     if (deliver) {
         for (gsr_ctx* c : ctx) {
             ctx0 = c;
-            if (format == GSR_FORMAT_RGBA8) { CHECK(gsr_delivery_open(c, 3)); continue; }
+            if (format == GSR_FORMAT_RGBA8 && depth_format == GSR_DEPTH_NONE) { CHECK(gsr_delivery_open(c, 3)); continue; }
             gsr_delivery_options dopt{};
             dopt.slots = 3; dopt.format = format;
-            CHECK(gsr_delivery_open_ex(c, &dopt));
+            if (depth_format == GSR_DEPTH_NONE) { CHECK(gsr_delivery_open_ex(c, &dopt)); continue; }
+            gsr_depth_delivery_options ddopt{};
+            ddopt.format = depth_format; ddopt.step = depth_step; ddopt.near = depth_near;
+            CHECK(gsr_delivery_open_depth(c, &dopt, &ddopt));
         }
         auto pick_up = [&](gsr_ctx* c) -> int {   // the oldest frame of this context
             gsr_frame f;
             if (int rc = gsr_acquire_frame(c, 0, &f)) return rc;
             sink += f.pixels[(size_t)f.width * f.height / 2];
+            if (depth_format != GSR_DEPTH_NONE) sink += f.pixels[dlay.offset + dlay.bytes / 2];
             delivered++;
             return gsr_release_frame(c, f.serial);
         };
+        if (depth_format != GSR_DEPTH_NONE) CHECK(gsr_delivery_depth_layout(ctx[0], &dlay));   // (every context's: same size, same options)
         auto deliver_step = [&](int k) -> int {
             gsr_ctx* c = ctx[k % in_flight];
             if (int rc = step(k)) return rc;
@@ -284,6 +302,8 @@ int main(int argc, char** argv)
         CHECK(gsr_delivery_layout(ctx[0], &lay));
         delivered_hash = (unsigned long long)fnv1a(f.pixels, (size_t)lay.bytes);
         // (a Y'CbCr payload is held to the definition by tests/test_gpu_yuv_delivery.py, through this checksum)
+        // (and the depth plane by tests/test_gpu_depth_delivery.py, through this one)
+        if (depth_format != GSR_DEPTH_NONE) delivered_depth_hash = (unsigned long long)fnv1a(f.pixels + dlay.offset, (size_t)dlay.bytes);
         const bool same = f.width == cfg->w && f.height == cfg->h && lay.format == format &&
                           (format != GSR_FORMAT_RGBA8 || (lay.bytes == px.size() && !std::memcmp(f.pixels, px.data(), px.size())));
         CHECK(gsr_release_frame(ctx[0], serial));
@@ -306,6 +326,10 @@ int main(int argc, char** argv)
         std::printf(", \"frames_per_sec_delivered\": %.1f, \"delivery_slots\": 3, \"delivery_format\": \"%s\", "
                     "\"delivered_payload_fnv1a\": \"%016llx\", \"sink\": %d",
                     frames / delivered_sec, deliver_format.c_str(), delivered_hash, (int)(sink & 1));
+    if (deliver && depth_format != GSR_DEPTH_NONE)
+        std::printf(", \"delivery_depth\": \"%s\", \"depth_step\": %d, \"depth_near\": %.9g, \"depth_width\": %d, \"depth_height\": %d, "
+                    "\"depth_bytes\": %llu, \"delivered_depth_fnv1a\": \"%016llx\"",
+                    deliver_depth.c_str(), dlay.step, (double)dlay.near, dlay.width, dlay.height, (unsigned long long)dlay.bytes, delivered_depth_hash);
     if (depth)
         std::printf(", \"frames_per_sec_plain\": %.1f, \"frames_per_sec_with_depth\": %.1f, \"depth_legs\": 3",
                     3.0 * frames / depth_sec[0], 3.0 * frames / depth_sec[1]);
