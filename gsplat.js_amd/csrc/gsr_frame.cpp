@@ -239,6 +239,11 @@ int enqueue_chain(gsr_ctx* c, const FrameArgs& a, bool timing)
     if (a.n) {
         if (a.render) launch_project_key(c->proj, s);
         else launch_depth_key(a.proj.sc, a.n, c->cam, a.proj.depth, a.proj.slots, a.slots_next, s);
+    } else {
+        // an empty scene runs no kernel that stores the frame's depth range (k_quantise_hist does otherwise): it is the range the
+        // reference starts from (wasm/wasm.cpp:14-15), not the one of a scene that is gone
+        HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)&a.sort.minmax[0], 0x7fffffff, 1, s));
+        HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)&a.sort.minmax[1], (int)0x80000000u, 1, s));
     }
     if (timing) HIP_TRY(c, hipEventRecord(ev[EV_PROJECT], s));
     launch_sort(a.sort, a.n, s, a.front_waves);

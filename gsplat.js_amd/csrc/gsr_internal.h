@@ -139,10 +139,17 @@ void launch_depth_key(const SceneSoA& sc, uint32_t n, const CamParams& cam, int3
 // (One struct for both, so that the graph replay rewrites exactly what a direct launch passes: the camera.)
 struct ProjectLaunch {
     SceneSoA sc; uint32_t n; CamParams cam; int do_project;   // do_project: 1 = project (render frames), 2 = records and pixel boxes only (read-back)
+    // INVARIANT (band contexts, `kept` set): depth[] and rect[] are NOT indexed by splat for every splat.  depth[] holds each
+    // workgroup's survivors packed to the front of its own 256 slots; rect[i] is written for survivors only.  Every other slot
+    // keeps what an OLDER frame (another band, the full frame, a sort-only frame) left there.  Whoever reads them goes through
+    // this frame's survivors -- kept[] / kept_lane[] / koff[], or depth_index[0 .. sorted_count) -- and through nothing else; a
+    // reader that indexes either by splat gets another frame's data with no warning.  rec[i] likewise is written for splats that
+    // pass the culls only (full-frame contexts too): it is read through the bin lists, which hold no other splat.  Pinned by
+    // tests/test_gpu_history.py (band -> full -> band, band moved, on the bounds-checked build as well).
     int32_t* depth;
     int32_t* slots;      // FRAME_SLOTS * FRAME_SLOT_WORDS, clean at the start of the frame (the finalize step resets them)
     Record* rec; uint2* bbox;   // bbox may be null (frames: nothing on the path reads the pixel boxes)
-    uint32_t* rect;      // n: packed bin rectangle per splat
+    uint32_t* rect;      // n: packed bin rectangle per splat (see the invariant above)
     uint32_t* overflow;  // the frame's overflow word, zeroed by the kernel
     uint32_t* kept;      // band mode: per 256-splat workgroup, the survivors it packed to the front of its depth slots (null: no packing)
     uint8_t* kept_lane;  // band mode: n: the lane (index & 255) a packed slot's splat came from

@@ -52,12 +52,13 @@ int gsr_set_scene(gsr_ctx* c, const uint32_t* data, const float* positions, uint
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     int r;
-    if ((r = alloc_scene(c, n, false))) return r;
+    // The upload is checked before anything of the context is touched: a refused scene (GSR_ERR_SCENE) leaves the one the context
+    // has, its SH state and its last frame as they were.  The arrays are filled beside the old ones and swapped in afterwards.
+    SceneArrays sa;
     if (n) {
         DevBuf<uint32_t> d_data, d_flag;
         DevBuf<float> d_pos;
-        if ((r = d_data.alloc(c, (size_t)n * 8)) || (r = d_pos.alloc(c, (size_t)n * 3)) || (r = d_flag.alloc(c, 1))) return r;
-        const SceneArrays& sa = c->scene.arr;
+        if ((r = sa.alloc(c, n, false)) || (r = d_data.alloc(c, (size_t)n * 8)) || (r = d_pos.alloc(c, (size_t)n * 3)) || (r = d_flag.alloc(c, 1))) return r;
         hipError_t e1 = hipMemcpyAsync(d_data, data, (size_t)n * 32, hipMemcpyHostToDevice, c->stream);
         hipError_t e2 = hipMemcpyAsync(d_pos, positions, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
         hipError_t e3 = hipMemsetAsync(d_flag, 0, 4, c->stream);
@@ -69,6 +70,8 @@ int gsr_set_scene(gsr_ctx* c, const uint32_t* data, const float* positions, uint
             if (e != hipSuccess) return fail(c, GSR_ERR_HIP, "scene upload failed: %s", hipGetErrorString(e));
         if (flag) return fail(c, GSR_ERR_SCENE, "positions differ from data words 0..2 (Scene.ts:141-143 keeps them equal)");
     }
+    if ((r = alloc_scene(c, n, false))) return r;
+    if (n) std::swap(c->scene.arr, sa);   // (the blank arrays alloc_scene made go with `sa`)
     c->n = n;
     c->bin.capacity = 0;
     return alloc_bins(c);

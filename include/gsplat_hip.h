@@ -102,8 +102,8 @@ const char *gsr_last_error(gsr_ctx *ctx); /* ctx may be NULL: error of the faile
 
 /* ---- per scene ---- */
 /* data: Scene.data layout, 8 u32 per splat (src/core/Scene.ts:141-148,174-176);
- * positions: Scene.positions, 3 f32 per splat, must equal data words 0..2.
- * Repacked once into SoA on the device. */
+ * positions: Scene.positions, 3 f32 per splat, must equal data words 0..2 (GSR_ERR_SCENE otherwise: the context then
+ * keeps the scene, SH state and frame it had).  Repacked once into SoA on the device. */
 int gsr_set_scene(gsr_ctx *ctx, const uint32_t *data, const float *positions, uint32_t n);
 
 /* On-device scene build: rows = .splat bytes, 32 per splat (src/core/Scene.ts:9,126-148).  The
