@@ -1198,27 +1198,32 @@ def test_two_level_binning_overflow_is_repaired_in_one_regrowth(gh, monkeypatch)
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("throughput", [False, True], ids=["k_blend2", "k_blend"])
 @pytest.mark.parametrize("long_items", ["0", "1"])
-def test_saturated_quadrants_are_skipped_without_changing_a_bit(gh, monkeypatch, long_items):
-    """k_blend drops a quadrant once every one of its pixels has a transmittance below 2^-27 of its smallest colour
+def test_saturated_quadrants_are_skipped_without_changing_a_bit(gh, monkeypatch, long_items, throughput):
+    """The compositor drops a quadrant once every one of its pixels has a transmittance below 2^-27 of its smallest colour
     channel: no later splat can change a bit of such a pixel (w <= T, c <= 1: w*c is under half an ulp of the channel; alpha
     is 1 - T = 1.0f), and what the segment's own T would still become only multiplies later segments in the fold, whose
     terms are then under half an ulp as well.  So the image must equal, BIT FOR BIT, the one composited without the skip
     (GSR_SATURATE=0) -- with short segments (512 entries: the fold of partials is in play) and with long work items
-    (whole bins, where most of the skipping happens: 53 % of C3's list entries)."""
+    (whole bins, where most of the skipping happens: 53 % of C3's list entries).  Both kernels, each asserted to be the one
+    that ran: a default context at 1080p runs k_blend2 (two waves per tile), which tests at the chunk boundaries; a
+    throughput context runs k_blend (one wave per tile), which tests after every 64-entry step."""
     cfg = gh.synth.CONFIGS["C3"]
     W, H = cfg["width"], cfg["height"]
     scene = gh.Scene()
     scene.setData(gh.synth.config_rows("C3"))
     monkeypatch.setenv("GSR_LONG_ITEMS", long_items)
     monkeypatch.setenv("GSR_SATURATE", "0")
-    full = gh.HIPRenderer(W, H)
+    full = gh.HIPRenderer(W, H, throughput=throughput)
     monkeypatch.delenv("GSR_SATURATE")
-    skip = gh.HIPRenderer(W, H)
+    skip = gh.HIPRenderer(W, H, throughput=throughput)
     for k in (2, 31, 64, 97):
         cam = gh.orbit_camera(k, 120, W, H, cfg["fx"])
         full.render(scene, cam)
         skip.render(scene, cam)
+        for r in (full, skip):
+            assert r.work_items()["waves_per_tile"] == (1 if throughput else 2)
         assert np.array_equal(skip.readPixelsFloat(), full.readPixelsFloat()), k
         assert np.array_equal(skip.readPixels(), full.readPixels()), k
     full.dispose(); skip.dispose()
@@ -1302,6 +1307,7 @@ def test_two_waves_per_tile_agree_with_one(gh, oracle, scenes, monkeypatch):
             assert one.work_items()["waves_per_tile"] == 1 and two.work_items()["waves_per_tile"] == 2
             assert auto.work_items()["waves_per_tile"] == 2 and thr.work_items()["waves_per_tile"] == 1
             assert np.abs(imgs["one"] - imgs["two"]).max() <= 2e-6, (name, k)
+            assert np.abs(imgs["one"] - imgs["thr"]).max() <= 2e-6, (name, k)      # k_blend as well, with the throughput cut of the lists
             assert np.array_equal(imgs["two"], imgs["auto"]), (name, k)
             assert np.array_equal(imgs["two_all"], imgs["two_pinned"]), (name, k)   # the saturation skip changes no bit here either
         for r in (one, two, two_all, two_pinned, auto, thr):
@@ -1498,12 +1504,14 @@ def test_assembly_walk_equals_the_cpp_loop(gh, monkeypatch):
     (k_blend.hip, GSR_ASM_WALK_STEP: s_ff1 / s_bitset0 / s_bitcmp1 for the walk, v_cmpx for the coverage); the same loop in C++
     is the `cppwalk` twin of the library (-DGSR_CPP_WALK, built by __graft_entry__.build()).  Same arithmetic instruction for
     instruction, so every image must be equal bit for bit: both compositor kernels, both cuts of the lists, the separate
-    fold, early termination, SH colours -- and the depthIndex, which the compositor does not touch."""
+    fold, early termination, throughput contexts (the benchmarked form, C3 and C4) -- and the depthIndex, which the compositor
+    does not touch."""
     import os
     lib = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gsplat.js_amd", "lib_exp", "cppwalk", "libgsplat_hip.so")
     assert os.path.exists(lib), "the C++-walk build is missing: run python -c 'import __graft_entry__ as g; g.build()'"
     cases = [("C1", {}, {}), ("C2", {}, {}), ("C3", {}, {}), ("C3", {"GSR_BLEND_SUB": "1"}, {}), ("C3", {"GSR_LONG_ITEMS": "0"}, {}),
-             ("C2", {"GSR_FUSE_COMBINE": "0"}, {}), ("C2", {}, {"early_out_eps": 1e-4}), ("C2", {}, {"throughput": True})]
+             ("C2", {"GSR_FUSE_COMBINE": "0"}, {}), ("C2", {}, {"early_out_eps": 1e-4}), ("C2", {}, {"throughput": True}), ("C3", {}, {"throughput": True}),
+             ("C4", {}, {"throughput": True})]
     for name, env, kw in cases:
         cfg = gh.synth.CONFIGS[name]
         W, H = cfg["width"], cfg["height"]
@@ -1513,7 +1521,7 @@ def test_assembly_walk_equals_the_cpp_loop(gh, monkeypatch):
             monkeypatch.setenv(k, v)
         a = gh.HIPRenderer(W, H, **kw)
         b = gh.HIPRenderer(W, H, lib_path=lib, **kw)
-        for k in (9, 77):
+        for k in ((9,) if name == "C4" else (9, 77)):
             cam = gh.orbit_camera(k, 120, W, H, cfg["fx"])
             a.render(scene, cam); b.render(scene, cam)
             assert np.array_equal(a.readPixelsFloat(), b.readPixelsFloat()), (name, env, kw, k)
