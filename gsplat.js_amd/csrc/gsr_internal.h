@@ -81,6 +81,11 @@ void launch_scene_rotate(uint32_t n, const SceneDev& sc, const double* q_xyzw, h
 void launch_scene_scale(uint32_t n, const SceneDev& sc, const double* sv, hipStream_t s);
 void launch_scene_limit_box(uint32_t n, const SceneDev& src, const SceneDev& dst, const double* box, uint32_t* block_count,
                             uint32_t* total, hipStream_t s);
+// Scene.scales (3 f32 per splat, device memory) -> scl; and the scene back into the layouts of Scene.data (8 words per splat,
+// 16-byte aligned), positions and scales (3 f32 per splat): a null output is skipped.  Rotations need neither: `rot` IS
+// Scene.rotations' layout.
+void launch_scene_import(const float* scales, uint32_t n, float4* scl, hipStream_t s);
+void launch_scene_export(uint32_t n, const SceneDev& sc, uint32_t* data, float* positions, float* scales, hipStream_t s);
 
 // ---- launchers (each enqueues on `s`; none synchronises) ----
 void launch_repack_scene(const uint32_t* data, const float* positions, uint32_t n, float* px, float* py, float* pz,

@@ -1,8 +1,6 @@
-// The scene on the device: upload (packed words or .splat rows), the transforms and the compaction of scenes built from
-// rows, spherical harmonics, and the scene's read-back.  alloc_scene sizes everything that holds one entry per splat.
+// The scene on the device: upload (packed words, the Scene's four arrays or .splat rows), the transforms and the compaction of
+// scenes that carry rotations and scales, spherical harmonics, and the scene's read-back.  alloc_scene sizes everything that holds one entry per splat.
 #include "gsr_ctx.h"
-
-#include <cstring>
 
 using namespace gsr;
 
@@ -34,10 +32,52 @@ namespace {
 
 int need_rows(gsr_ctx* c)
 {
-    if (!c->scene.have_rows) return fail(c, GSR_ERR_ARG, "scene transforms need a scene built with gsr_set_scene_rows");
+    if (!c->scene.have_rows) return fail(c, GSR_ERR_ARG, "scene transforms need a scene built with gsr_set_scene_rows or gsr_set_scene_arrays");
     HIP_TRY(c, hipSetDevice(c->device));
     c->have_frame = false; c->have_sort = false;
     return GSR_OK;
+}
+
+// gsr_set_scene (rotations / scales null) and gsr_set_scene_arrays: Scene.data and Scene.positions through the repack and its
+// check; with rotations and scales the result is a scene the transforms accept, as if built from rows.
+int upload_scene(gsr_ctx* c, const uint32_t* data, const float* positions, const float* rotations, const float* scales, uint32_t n)
+{
+    const bool with_rows = rotations != nullptr;
+    if (n > 0x7fffffffu / 8) return fail(c, GSR_ERR_ARG, "too many splats");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    int r;
+    // The upload is checked before anything of the context is touched: a refused scene (GSR_ERR_SCENE) leaves the one the context
+    // has, its SH state and its last frame as they were.  The arrays are filled beside the old ones and swapped in afterwards.
+    SceneArrays sa;
+    if (n) {
+        DevBuf<uint32_t> d_data, d_flag;
+        DevBuf<float> d_pos, d_scl;
+        if ((r = sa.alloc(c, n, with_rows)) || (r = d_data.alloc(c, (size_t)n * 8)) || (r = d_pos.alloc(c, (size_t)n * 3)) || (r = d_flag.alloc(c, 1))) return r;
+        hipError_t e1 = hipMemcpyAsync(d_data, data, (size_t)n * 32, hipMemcpyHostToDevice, c->stream);
+        hipError_t e2 = hipMemcpyAsync(d_pos, positions, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
+        hipError_t e3 = hipMemsetAsync(d_flag, 0, 4, c->stream);
+        launch_repack_scene(d_data, d_pos, n, sa.px, sa.py, sa.pz, sa.cov0, sa.cov1, sa.cov2, sa.rgba, d_flag, c->stream);
+        hipError_t e6 = hipSuccess, e7 = hipSuccess;
+        if (with_rows) {   // covariance words and colours stay the caller's; rotations are `rot`'s bytes already
+            if ((r = d_scl.alloc(c, (size_t)n * 3))) return r;
+            e6 = hipMemcpyAsync(sa.rot, rotations, (size_t)n * 16, hipMemcpyHostToDevice, c->stream);
+            e7 = hipMemcpyAsync(d_scl, scales, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
+            launch_scene_import(d_scl, n, sa.scl, c->stream);
+        }
+        uint32_t flag = 0;
+        hipError_t e4 = hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream);
+        hipError_t e5 = hipStreamSynchronize(c->stream);
+        for (hipError_t e : {e1, e2, e3, e4, e5, e6, e7, hipGetLastError()})
+            if (e != hipSuccess) return fail(c, GSR_ERR_HIP, "scene upload failed: %s", hipGetErrorString(e));
+        if (flag) return fail(c, GSR_ERR_SCENE, "positions differ from data words 0..2 (Scene.ts:141-143 keeps them equal)");
+    }
+    if ((r = alloc_scene(c, n, with_rows))) return r;
+    if (n) std::swap(c->scene.arr, sa);   // (the blank arrays alloc_scene made go with `sa`)
+    c->n = n;
+    c->scene.have_rows = with_rows;
+    c->bin.capacity = 0;
+    return alloc_bins(c);
 }
 
 }  // namespace
@@ -48,33 +88,14 @@ int gsr_set_scene(gsr_ctx* c, const uint32_t* data, const float* positions, uint
 {
     if (!c) return GSR_ERR_ARG;
     if (n && (!data || !positions)) return fail(c, GSR_ERR_ARG, "data/positions is NULL");
-    if (n > 0x7fffffffu / 8) return fail(c, GSR_ERR_ARG, "too many splats");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    int r;
-    // The upload is checked before anything of the context is touched: a refused scene (GSR_ERR_SCENE) leaves the one the context
-    // has, its SH state and its last frame as they were.  The arrays are filled beside the old ones and swapped in afterwards.
-    SceneArrays sa;
-    if (n) {
-        DevBuf<uint32_t> d_data, d_flag;
-        DevBuf<float> d_pos;
-        if ((r = sa.alloc(c, n, false)) || (r = d_data.alloc(c, (size_t)n * 8)) || (r = d_pos.alloc(c, (size_t)n * 3)) || (r = d_flag.alloc(c, 1))) return r;
-        hipError_t e1 = hipMemcpyAsync(d_data, data, (size_t)n * 32, hipMemcpyHostToDevice, c->stream);
-        hipError_t e2 = hipMemcpyAsync(d_pos, positions, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
-        hipError_t e3 = hipMemsetAsync(d_flag, 0, 4, c->stream);
-        launch_repack_scene(d_data, d_pos, n, sa.px, sa.py, sa.pz, sa.cov0, sa.cov1, sa.cov2, sa.rgba, d_flag, c->stream);
-        uint32_t flag = 0;
-        hipError_t e4 = hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream);
-        hipError_t e5 = hipStreamSynchronize(c->stream);
-        for (hipError_t e : {e1, e2, e3, e4, e5, hipGetLastError()})
-            if (e != hipSuccess) return fail(c, GSR_ERR_HIP, "scene upload failed: %s", hipGetErrorString(e));
-        if (flag) return fail(c, GSR_ERR_SCENE, "positions differ from data words 0..2 (Scene.ts:141-143 keeps them equal)");
-    }
-    if ((r = alloc_scene(c, n, false))) return r;
-    if (n) std::swap(c->scene.arr, sa);   // (the blank arrays alloc_scene made go with `sa`)
-    c->n = n;
-    c->bin.capacity = 0;
-    return alloc_bins(c);
+    return upload_scene(c, data, positions, nullptr, nullptr, n);
+}
+
+int gsr_set_scene_arrays(gsr_ctx* c, const uint32_t* data, const float* positions, const float* rotations, const float* scales, uint32_t n)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (n && (!data || !positions || !rotations || !scales)) return fail(c, GSR_ERR_ARG, "data/positions/rotations/scales is NULL");
+    return upload_scene(c, data, positions, rotations, scales, n);
 }
 
 int gsr_set_scene_rows(gsr_ctx* c, const uint8_t* rows, uint32_t n)
@@ -168,34 +189,23 @@ int gsr_read_scene(gsr_ctx* c, uint32_t* data, float* positions, float* rotation
     const uint32_t n = c->n;
     if (count) *count = n;
     if (!data && !positions && !rotations && !scales) return GSR_OK;  // count only: nothing to copy
-    if ((rotations || scales) && !c->scene.have_rows) return fail(c, GSR_ERR_ARG, "rotations/scales exist only for scenes built with gsr_set_scene_rows");
-    const SceneArrays& sa = c->scene.arr;
-    std::vector<float> x(n), y(n), z(n);
-    std::vector<uint32_t> c0, c1, c2, cw;
-    std::vector<float4> rv, sv;
-    HIP_TRY(c, hipMemcpyAsync(x.data(), sa.px, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(y.data(), sa.py, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(z.data(), sa.pz, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (data) {
-        c0.resize(n); c1.resize(n); c2.resize(n); cw.resize(n);
-        HIP_TRY(c, hipMemcpyAsync(c0.data(), sa.cov0, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c1.data(), sa.cov1, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c2.data(), sa.cov2, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(cw.data(), sa.rgba, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (rotations) { rv.resize(n); HIP_TRY(c, hipMemcpyAsync(rv.data(), sa.rot, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream)); }
-    if (scales) { sv.resize(n); HIP_TRY(c, hipMemcpyAsync(sv.data(), sa.scl, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream)); }
+    if ((rotations || scales) && !c->scene.have_rows) return fail(c, GSR_ERR_ARG, "rotations/scales exist only for scenes built with gsr_set_scene_rows or gsr_set_scene_arrays");
+    if (!n) return GSR_OK;
+    // One kernel lays the requested parts out in the callers' layouts in one staging allocation (k_scene_export), then one copy
+    // per output.  Rotations are copied from `rot` itself: it has Scene.rotations' layout.
+    const size_t data_words = data ? 8 * (size_t)n : 0, pos_words = positions ? 3 * (size_t)n : 0, scl_words = scales ? 3 * (size_t)n : 0;
+    DevBuf<uint32_t> stage;
+    if (int r = stage.alloc(c, data_words + pos_words + scl_words)) return r;
+    uint32_t* d_data = data ? (uint32_t*)stage : nullptr;
+    float* d_pos = positions ? (float*)(stage + data_words) : nullptr;
+    float* d_scl = scales ? (float*)(stage + data_words + pos_words) : nullptr;
+    launch_scene_export(n, c->scene.arr.view(), d_data, d_pos, d_scl, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    if (data) HIP_TRY(c, hipMemcpyAsync(data, d_data, data_words * 4, hipMemcpyDeviceToHost, c->stream));
+    if (positions) HIP_TRY(c, hipMemcpyAsync(positions, d_pos, pos_words * 4, hipMemcpyDeviceToHost, c->stream));
+    if (rotations) HIP_TRY(c, hipMemcpyAsync(rotations, c->scene.arr.rot, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
+    if (scales) HIP_TRY(c, hipMemcpyAsync(scales, d_scl, scl_words * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (uint32_t i = 0; i < n; i++) {
-        if (positions) { positions[3 * (size_t)i] = x[i]; positions[3 * (size_t)i + 1] = y[i]; positions[3 * (size_t)i + 2] = z[i]; }
-        if (data) {
-            uint32_t* d = data + 8 * (size_t)i;
-            memcpy(&d[0], &x[i], 4); memcpy(&d[1], &y[i], 4); memcpy(&d[2], &z[i], 4);
-            d[3] = 0; d[4] = c0[i]; d[5] = c1[i]; d[6] = c2[i]; d[7] = cw[i];
-        }
-        if (rotations) { float* r = rotations + 4 * (size_t)i; r[0] = rv[i].x; r[1] = rv[i].y; r[2] = rv[i].z; r[3] = rv[i].w; }
-        if (scales) { float* q = scales + 3 * (size_t)i; q[0] = sv[i].x; q[1] = sv[i].y; q[2] = sv[i].z; }
-    }
     return GSR_OK;
 }
 

@@ -196,6 +196,73 @@ __global__ __launch_bounds__(BOX_THREADS) void k_box_compact(uint32_t n, SceneDe
     dst.rot[o] = src.rot[i]; dst.scl[o] = src.scl[i];
 }
 
+// ---- a scene from the Scene's own arrays, and the scene back into them (gsr_set_scene_arrays / gsr_read_scene) ----
+// Neither does arithmetic: words move between the SoA scene and the layouts of Scene.data / positions / rotations / scales.
+// Scene.rotations is (w, x, y, z) per splat, byte for byte what `rot` holds, so rotations are copied straight in and out and
+// no kernel touches them.  The three-float arrays go through LDS, so that a wave loads and stores whole consecutive lines on
+// both sides: 256 splats = 768 consecutive words outside, one splat per lane (stride 3 words: no bank conflict) inside.
+constexpr int XFER_THREADS = 256;
+GSR_BOUNDS_DECL(scene)   // sites: 0 word of Scene.scales read by k_scene_import, 1 its LDS cell, 2 float4 it stores,
+                         //        3 row of Scene.data stored by k_scene_export, 4 its LDS cell, 5 word of positions / scales it stores
+
+// Scene.scales (3 f32 per splat) -> scl (float4 per splat, w = 0 as k_build_scene leaves it)
+__global__ __launch_bounds__(XFER_THREADS) void k_scene_import(const float* __restrict__ scales, uint32_t n, float4* __restrict__ scl)
+{
+    __shared__ float s_in[3 * XFER_THREADS];
+    const size_t base = (size_t)blockIdx.x * XFER_THREADS, words = 3 * (size_t)n;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const uint32_t cell = k * XFER_THREADS + threadIdx.x;
+        const size_t w = 3 * base + cell;
+        if (w < words) {
+            GSR_BOUND(scene, 0, w, words);
+            GSR_BOUND(scene, 1, cell, 3 * XFER_THREADS);
+            s_in[cell] = scales[w];
+        }
+    }
+    __syncthreads();
+    const size_t i = base + threadIdx.x;
+    if (i >= n) return;
+    GSR_BOUND(scene, 1, 3 * threadIdx.x + 2, 3 * XFER_THREADS);
+    GSR_BOUND(scene, 2, i, n);
+    scl[i] = make_float4(s_in[3 * threadIdx.x], s_in[3 * threadIdx.x + 1], s_in[3 * threadIdx.x + 2], 0.f);
+}
+
+// SoA scene -> Scene.data rows (word 3 = 0), positions x 3, scales x 3; a null output is not produced.  For `data` a lane owns
+// one splat: seven coalesced dword loads, two dwordx4 stores (its 32-byte row).
+__global__ __launch_bounds__(XFER_THREADS) void k_scene_export(uint32_t n, SceneDev sc, uint4* __restrict__ data, float* __restrict__ positions,
+                                                               float* __restrict__ scales)
+{
+    __shared__ float s_out[2][3 * XFER_THREADS];
+    const size_t base = (size_t)blockIdx.x * XFER_THREADS, i = base + threadIdx.x, words = 3 * (size_t)n;
+    if (i < n) {
+        const float x = sc.px[i], y = sc.py[i], z = sc.pz[i];
+        if (data) {
+            GSR_BOUND(scene, 3, 2 * i + 1, 2 * (size_t)n);
+            data[2 * i] = make_uint4(__float_as_uint(x), __float_as_uint(y), __float_as_uint(z), 0u);
+            data[2 * i + 1] = make_uint4(sc.cov0[i], sc.cov1[i], sc.cov2[i], sc.rgba[i]);
+        }
+        GSR_BOUND(scene, 4, 3 * threadIdx.x + 2, 3 * XFER_THREADS);
+        if (positions) { s_out[0][3 * threadIdx.x] = x; s_out[0][3 * threadIdx.x + 1] = y; s_out[0][3 * threadIdx.x + 2] = z; }
+        if (scales) {
+            const float4 s = sc.scl[i];
+            s_out[1][3 * threadIdx.x] = s.x; s_out[1][3 * threadIdx.x + 1] = s.y; s_out[1][3 * threadIdx.x + 2] = s.z;
+        }
+    }
+    if (!positions && !scales) return;   // (the same for every lane: nobody is left behind at the barrier)
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const uint32_t cell = k * XFER_THREADS + threadIdx.x;
+        const size_t w = 3 * base + cell;
+        if (w >= words) break;
+        GSR_BOUND(scene, 4, cell, 3 * XFER_THREADS);
+        GSR_BOUND(scene, 5, w, words);
+        if (positions) positions[w] = s_out[0][cell];
+        if (scales) scales[w] = s_out[1][cell];
+    }
+}
+
 // ---- launchers ----
 void launch_build_scene(const uint8_t* rows, uint32_t n, const SceneDev& sc, hipStream_t s)
 {
@@ -223,6 +290,16 @@ void launch_scene_limit_box(uint32_t n, const SceneDev& src, const SceneDev& dst
     hipLaunchKernelGGL(k_box_count, dim3(nblocks), dim3(BOX_THREADS), 0, s, n, src, b, block_count);
     hipLaunchKernelGGL(k_box_scan, dim3(1), dim3(BOX_THREADS), 0, s, block_count, nblocks, total);
     hipLaunchKernelGGL(k_box_compact, dim3(nblocks), dim3(BOX_THREADS), 0, s, n, src, dst, b, (const uint32_t*)block_count);
+}
+
+void launch_scene_import(const float* scales, uint32_t n, float4* scl, hipStream_t s)
+{
+    if (n) hipLaunchKernelGGL(k_scene_import, dim3((n + XFER_THREADS - 1) / XFER_THREADS), dim3(XFER_THREADS), 0, s, scales, n, scl);
+}
+void launch_scene_export(uint32_t n, const SceneDev& sc, uint32_t* data, float* positions, float* scales, hipStream_t s)
+{
+    if (n && (data || positions || scales))
+        hipLaunchKernelGGL(k_scene_export, dim3((n + XFER_THREADS - 1) / XFER_THREADS), dim3(XFER_THREADS), 0, s, n, sc, (uint4*)data, positions, scales);
 }
 
 }  // namespace gsr

@@ -4,6 +4,13 @@
 // truncated halves of 4*Sigma, rgba8; the reference's RGBA32UI texture image) -- so its f64 arithmetic follows
 // Scene.ts:126-177 operation for operation.  translate/rotate/scale/limitBox mutate the same buffers and fire
 // "change", which makes the renderer re-upload (WebGLRenderer.ts:234-239).
+//
+// While the scene is attached to renderers (attachDevice), the device copies are the scene: the four transforms run on
+// every attached *device scene* -- { transform(kind, Float64Array) -> vertexCount, read({data, positions, rotations,
+// scales}), hostOnly } -- instead of the loops below, nothing is uploaded, and the four arrays become mirrors that are
+// refreshed from the first device scene the next time they are read.  The Scene knows nothing else of a renderer, so
+// the protocol runs against a stub as well (tests/test_scene_binding.py).  DESIGN.md section 4, "Scene transforms on
+// the device".
 const { EventDispatcher } = require("./EventDispatcher");
 const { Matrix3 } = require("../math/Matrix3");
 const { Quaternion } = require("../math/Quaternion");
@@ -28,6 +35,70 @@ class Scene extends EventDispatcher {
         this._shs_rgb = [new Uint32Array(0), new Uint32Array(0), new Uint32Array(0)];
         this._g0bands = 0;
         this._bandsIndices = new Int32Array([-1, -1, -1]);
+        this._devices = [];            // attached device scenes, in attach order
+        this._stale = false;           // the device copies hold edits the four arrays have not seen
+        this._diverged = false;        // a plain setter replaced a buffer: the device copies are behind until the next "change"
+        this._editOnDevice = false;    // true while the "change" of an edit the devices have applied is dispatched
+        this._shDroppedOnDevice = false;
+        // A "change" that is not a device edit's (setData, an edit that ran here, one the caller dispatched after writing into
+        // the arrays) makes every attached renderer upload the host's arrays: afterwards the device copies are current again.
+        const dispatch = this.dispatchEvent;
+        this.dispatchEvent = (e) => {
+            dispatch(e);
+            if (e.type === "change" && !this._editOnDevice) this._diverged = false;
+        };
+    }
+
+    // ---- binding to device scenes ----
+    attachDevice(dev) { if (!this._devices.includes(dev)) this._devices.push(dev); }
+    // The last device scene to go hands its edits back first, so the scene never loses one.
+    detachDevice(dev) {
+        const k = this._devices.indexOf(dev);
+        if (k < 0) return;
+        if (this._devices.length === 1) { this._refresh(); this._diverged = false; }
+        this._devices.splice(k, 1);
+    }
+    // true inside the "change" of an edit every attached device scene has applied already: a renderer has nothing to upload
+    get deviceEditApplied() { return this._editOnDevice; }
+    // limitBox on the device renumbers the splats and drops the context's SH state; the SH textures here are stale from then
+    // on, and are not sent again before the next setData
+    get shDroppedOnDevice() { return this._shDroppedOnDevice; }
+
+    // Mirrors in the shapes the loops below leave: arrays of the right length are filled in place, others are replaced (a
+    // replaced `data` is zero behind 8 * vertexCount, where the limitBox loop leaves stale splats).
+    _refresh() {
+        if (!this._stale) return;
+        const n = this._vertexCount, fit = (a, T, len) => (a.length === len ? a : new T(len));
+        this._data = fit(this._data, Uint32Array, this._width * this._height * 4);
+        this._positions = fit(this._positions, Float32Array, 3 * n);
+        this._rotations = fit(this._rotations, Float32Array, 4 * n);
+        this._scales = fit(this._scales, Float32Array, 3 * n);
+        this._devices[0].read({ data: this._data, positions: this._positions, rotations: this._rotations, scales: this._scales });
+        this._data.fill(0, 8 * n);
+        this._stale = false;
+    }
+
+    // kind: 0 translate (x, y, z), 1 rotate (x, y, z, w), 2 scale (x, y, z), 3 limitBox (xMin, xMax, yMin, yMax, zMin, zMax).
+    // false: the edit has to run here (nothing attached, a host-only device scene among them, or buffers set by hand).
+    _editDevices(kind, args) {
+        if (!this._devices.length || this._diverged || this._devices.some((d) => d.hostOnly)) {
+            this._refresh();
+            return false;
+        }
+        const f = new Float64Array(args);
+        let count = -1;
+        for (const d of this._devices) {
+            const c = d.transform(kind, f);
+            if (count >= 0 && c !== count) throw new Error("device scenes disagree on vertexCount (" + count + " and " + c + ")");
+            count = c;
+        }
+        this._vertexCount = count;
+        this._height = Math.ceil((2 * count) / this._width);
+        this._stale = true;
+        if (kind === 3) this._shDroppedOnDevice = true;
+        this._editOnDevice = true;
+        try { this.dispatchEvent({ type: "change" }); } finally { this._editOnDevice = false; }
+        return true;
     }
 
     // 4*Sigma of splat i from its rotation/scale, packed as six truncated halves (Scene.ts:150-176)
@@ -53,6 +124,8 @@ class Scene extends EventDispatcher {
     setData(data, shs) {
         if (data.length % ROW) throw new Error("splat data length must be a multiple of " + ROW);
         const n = data.length / ROW;
+        this._stale = false;            // the host is the truth again: whatever the devices hold is replaced by the upload
+        this._shDroppedOnDevice = false;
         this._vertexCount = n;
         this._height = Math.ceil((2 * n) / this._width);
         this._data = new Uint32Array(this._width * this._height * 4);
@@ -86,6 +159,7 @@ class Scene extends EventDispatcher {
     }
 
     translate(t) {
+        if (this._editDevices(0, [t.x, t.y, t.z])) return;
         for (let i = 0; i < this._vertexCount; i++) {
             this._positions[3 * i] += t.x;
             this._positions[3 * i + 1] += t.y;
@@ -96,6 +170,7 @@ class Scene extends EventDispatcher {
     }
 
     rotate(rotation) {
+        if (this._editDevices(1, [rotation.x, rotation.y, rotation.z, rotation.w])) return;
         const R = Matrix3.RotationFromQuaternion(rotation).buffer;
         const p = this._positions, r = this._rotations;
         for (let i = 0; i < this._vertexCount; i++) {
@@ -113,6 +188,7 @@ class Scene extends EventDispatcher {
 
     scale(s) {
         const f = [s.x, s.y, s.z];
+        if (this._editDevices(2, f)) return;
         for (let i = 0; i < this._vertexCount; i++) {
             for (let k = 0; k < 3; k++) {
                 this._positions[3 * i + k] *= f[k];
@@ -128,6 +204,7 @@ class Scene extends EventDispatcher {
         if (xMin >= xMax) throw new Error("xMin (" + xMin + ") must be smaller than xMax (" + xMax + ")");
         if (yMin >= yMax) throw new Error("yMin (" + yMin + ") must be smaller than yMax (" + yMax + ")");
         if (zMin >= zMax) throw new Error("zMin (" + zMin + ") must be smaller than zMax (" + zMax + ")");
+        if (this._editDevices(3, [xMin, xMax, yMin, yMax, zMin, zMax])) return;
         const p = this._positions;
         let kept = 0;
         for (let i = 0; i < this._vertexCount; i++) {
@@ -150,6 +227,7 @@ class Scene extends EventDispatcher {
 
     // The 32-byte .splat rows of the current scene (what Scene.saveToFile downloads in a browser, Scene.ts:368-403).
     toSplatBytes() {
+        this._refresh();
         const n = this._vertexCount;
         const out = new Uint8Array(n * ROW), outF = new Float32Array(out.buffer), src8 = new Uint8Array(this._data.buffer);
         for (let i = 0; i < n; i++) {
@@ -171,12 +249,19 @@ class Scene extends EventDispatcher {
     updateColor() {}
 }
 
-// plain accessors, as in Scene.ts:414-508
+// plain accessors, as in Scene.ts:414-508.  Reading one of the four mirrors refreshes them first; assigning a buffer or a count
+// makes the host the truth (the mirrors are refreshed first, so no edit is lost) and takes the scene off the device path until
+// the next "change" has made the attached renderers upload it.
+const MIRRORS = ["data", "positions", "rotations", "scales"], UPLOADED = MIRRORS.concat(["vertexCount", "height"]);
 for (const k of ["data", "vertexCount", "width", "height", "positions", "rotations", "scales", "shs", "shs_rgb", "shHeight",
                  "g0bands", "bandsIndices"]) {
+    const mirror = MIRRORS.includes(k), uploaded = UPLOADED.includes(k);
     Object.defineProperty(Scene.prototype, k, {
-        get() { return this["_" + k]; },
-        set(v) { this["_" + k] = v; },
+        get() { if (mirror) this._refresh(); return this["_" + k]; },
+        set(v) {
+            if (uploaded) { this._refresh(); this._diverged = this._devices.length > 0; }
+            this["_" + k] = v;
+        },
         configurable: true,
     });
 }

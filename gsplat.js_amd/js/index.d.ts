@@ -45,6 +45,16 @@ export class Matrix4 {
     clone(): Matrix4;
 }
 export interface SceneEvent { type: string }
+/** What a renderer hands a Scene while the Scene is its active scene: the Scene's transforms run through it instead of the
+ *  JavaScript loops, and the Scene reads its arrays back through it when they are next asked for. */
+export interface DeviceScene {
+    /** the last upload carried no rotations / scales: the Scene's edits run in JavaScript and are uploaded again */
+    hostOnly: boolean;
+    /** kind 0 translate (x, y, z), 1 rotate (x, y, z, w), 2 scale (x, y, z), 3 limitBox (xMin, xMax, yMin, yMax, zMin, zMax); returns vertexCount */
+    transform(kind: number, args: Float64Array): number;
+    /** fills the first 8 / 3 / 4 / 3 words per splat of the four arrays */
+    read(out: { data: Uint32Array; positions: Float32Array; rotations: Float32Array; scales: Float32Array }): void;
+}
 export class Scene {
     static RowLength: number;
     constructor();
@@ -63,6 +73,15 @@ export class Scene {
     positions: Float32Array; rotations: Float32Array; scales: Float32Array;
     shs: Uint32Array; shs_rgb: [Uint32Array, Uint32Array, Uint32Array]; shHeight: number;
     g0bands: number; bandsIndices: Int32Array;
+    /** While device scenes are attached (HIPRenderer.render / renderAsync attach, dispose and another scene detach), translate /
+     *  rotate / scale / limitBox run on every one of them and `data`, `positions`, `rotations`, `scales` are refreshed from the
+     *  first when they are next read; setData and assigning a buffer make the host the truth again. */
+    attachDevice(device: DeviceScene): void;
+    detachDevice(device: DeviceScene): void;
+    /** true inside the "change" of an edit the attached device scenes have applied already (nothing to upload) */
+    readonly deviceEditApplied: boolean;
+    /** limitBox ran on the device, which drops the SH state there: the SH textures are not sent again before the next setData */
+    readonly shDroppedOnDevice: boolean;
 }
 export class Camera {
     position: Vector3; rotation: Quaternion;

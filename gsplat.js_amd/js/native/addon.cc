@@ -185,6 +185,27 @@ napi_value SetSceneRows(napi_env env, napi_callback_info info)
     return rc ? throw_gsr(env, c, rc, "gsr_set_scene_rows") : undefined(env);
 }
 
+// setSceneArrays(handle, Uint32Array data, Float32Array positions, Float32Array rotations, Float32Array scales, vertexCount)
+napi_value SetSceneArrays(napi_env env, napi_callback_info info)
+{
+    napi_value argv[6];
+    if (!get_args(env, info, 6, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    if (!c) return nullptr;
+    void *data, *pos, *rot, *scl;
+    size_t nd, np, nr, ns;
+    int32_t n;
+    if (!get_typed(env, argv[1], napi_uint32_array, &data, &nd) || !get_typed(env, argv[2], napi_float32_array, &pos, &np) ||
+        !get_typed(env, argv[3], napi_float32_array, &rot, &nr) || !get_typed(env, argv[4], napi_float32_array, &scl, &ns) || !get_i32(env, argv[5], &n))
+        return nullptr;
+    if (n < 0 || nd < (size_t)n * 8 || np < (size_t)n * 3 || nr < (size_t)n * 4 || ns < (size_t)n * 3) {
+        napi_throw_range_error(env, nullptr, "scene buffers are smaller than vertexCount requires");
+        return nullptr;
+    }
+    const int rc = gsr_set_scene_arrays(c, (const uint32_t*)data, (const float*)pos, (const float*)rot, (const float*)scl, (uint32_t)n);
+    return rc ? throw_gsr(env, c, rc, "gsr_set_scene_arrays") : undefined(env);
+}
+
 // sceneTransform(handle, kind, Float64Array args): kind 0 translate(3) 1 rotate(4: x,y,z,w) 2 scale(3) 3 limitBox(6) -> new count
 napi_value SceneTransform(napi_env env, napi_callback_info info)
 {
@@ -229,6 +250,33 @@ napi_value ReadScene(napi_env env, napi_callback_info info)
             return nullptr;
         }
         rc = gsr_read_scene(c, (uint32_t*)data, (float*)pos, nullptr, nullptr, &count);
+    }
+    if (rc) return throw_gsr(env, c, rc, "gsr_read_scene");
+    napi_value n;
+    napi_create_uint32(env, count, &n);
+    return n;
+}
+
+// readSceneArrays(handle, Uint32Array data | null, Float32Array positions | null, Float32Array rotations | null, Float32Array scales | null) -> count
+napi_value ReadSceneArrays(napi_env env, napi_callback_info info)
+{
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    void *data, *out[3];
+    size_t nd, len[3];
+    if (!c || !get_typed(env, argv[1], napi_uint32_array, &data, &nd, true)) return nullptr;
+    for (int k = 0; k < 3; k++)
+        if (!get_typed(env, argv[2 + k], napi_float32_array, &out[k], &len[k], true)) return nullptr;
+    uint32_t count = 0;
+    int rc = gsr_scene_count(c, &count);
+    if (!rc) {
+        if ((data && nd < (size_t)count * 8) || (out[0] && len[0] < (size_t)count * 3) || (out[1] && len[1] < (size_t)count * 4) ||
+            (out[2] && len[2] < (size_t)count * 3)) {
+            napi_throw_range_error(env, nullptr, "output arrays are smaller than the scene");
+            return nullptr;
+        }
+        rc = gsr_read_scene(c, (uint32_t*)data, (float*)out[0], (float*)out[1], (float*)out[2], &count);
     }
     if (rc) return throw_gsr(env, c, rc, "gsr_read_scene");
     napi_value n;
@@ -779,7 +827,7 @@ napi_value Init(napi_env env, napi_value exports)
 {
     struct { const char* name; napi_callback fn; } fns[] = {
         {"create", Create}, {"destroy", Destroy}, {"setScene", SetScene}, {"setSceneSh", SetSceneSh}, {"setDepthFade", SetDepthFade}, {"setSceneRows", SetSceneRows},
-        {"sceneTransform", SceneTransform}, {"readScene", ReadScene}, {"resize", Resize}, {"setBand", SetBand},
+        {"sceneTransform", SceneTransform}, {"readScene", ReadScene}, {"setSceneArrays", SetSceneArrays}, {"readSceneArrays", ReadSceneArrays}, {"resize", Resize}, {"setBand", SetBand},
         {"setCamera", SetCamera}, {"sort", Call0<gsr_sort>}, {"render", Call0<gsr_render>},
         {"renderAsync", Call0<gsr_render_async>}, {"sync", Call0<gsr_sync>}, {"resetTimings", Call0<gsr_reset_timings>},
         {"readDepthIndex", ReadDepthIndex}, {"readPixels", ReadPixels}, {"getTimings", GetTimings},

@@ -41,14 +41,44 @@ class HIPRenderer {
         let activeScene = null, activeCamera = null, initialized = false, vertexCount = 0;
         const f32 = { view: new Float32Array(16), proj: new Float32Array(16), vp: new Float32Array(16) };
 
+        // While a Scene is this renderer's active scene, the renderer is one of its device scenes (Scene.attachDevice): the
+        // Scene's transforms run here as kernels on this context's stream, behind whatever frames it has in flight, and the
+        // Scene reads its arrays back from here when somebody asks for them.  DESIGN.md section 4, "Scene transforms on the device".
+        const device = {
+            hostOnly: false,             // the last upload could not carry rotations / scales: edits run in JavaScript and upload
+            transform: (kind, f64) => (vertexCount = this._n.sceneTransform(this._h, kind, f64)),
+            read: (out) => this._n.readSceneArrays(this._h, out.data, out.positions, out.rotations, out.scales),
+        };
         const upload = () => {   // initWebGL's scene part: worker init + texImage2D (WebGLRenderer.ts:105-110,185-195)
-            vertexCount = activeScene.vertexCount;
-            this._n.setScene(this._h, activeScene.data, activeScene.positions, vertexCount);
+            const s = activeScene, n = s.vertexCount, positions = s.positions, rotations = s.rotations, scales = s.scales;
+            vertexCount = n;
+            // a Scene whose buffers were assigned one by one (Scene.ts:474-496) may carry no rotations or scales
+            device.hostOnly = !(positions.length === 3 * n && rotations.length === 4 * n && scales.length === 3 * n);
+            if (device.hostOnly) this._n.setScene(this._h, s.data, positions, n);
+            else this._n.setSceneArrays(this._h, s.data, positions, rotations, scales, n);
             this.setShTextures();
             for (const p of passes) p.init(this, null);
             initialized = true;
         };
-        const onSceneChange = () => upload();   // WebGLRenderer.ts:234-239
+        const onSceneChange = () => {           // WebGLRenderer.ts:234-239
+            if (!activeScene.deviceEditApplied) return upload();
+            vertexCount = activeScene.vertexCount;   // the edit ran here already: nothing to upload; the passes start over as after an upload
+            for (const p of passes) p.init(this, null);
+        };
+        const detach = () => {
+            if (!activeScene) return;
+            activeScene.removeEventListener("change", onSceneChange);
+            activeScene.detachDevice(device);
+            activeScene = null;
+        };
+        const attach = (scene) => {
+            if (scene === activeScene) return;
+            detach();
+            activeScene = scene;
+            scene.addEventListener("change", onSceneChange);
+            upload();
+            scene.attachDevice(device);
+        };
 
         // ---- frame delivery: finished RGBA8 frames through the library's pinned ring while the next frames render ----
         //   renderer.openDelivery(3);
@@ -158,7 +188,7 @@ class HIPRenderer {
         this.setDepthFade = (use, value) => this._n.setDepthFade(this._h, use ? 1 : 0, value);
         // SH textures + u_bandIndex, only for scenes that carry SH data (WebGLRenderer.ts:202-211,321-366)
         this.setShTextures = () => {
-            if (!activeScene || !activeScene.shHeight) return;
+            if (!activeScene || !activeScene.shHeight || activeScene.shDroppedOnDevice) return;
             const band = activeScene.bandsIndices;
             const t = activeScene.shs_rgb;
             this._n.setSceneSh(this._h, t[0], t[1], t[2], activeScene.vertexCount - (band[0] + 1), band);
@@ -189,12 +219,7 @@ class HIPRenderer {
         // WebGLRenderer.ts:241-296
         this.render = (scene, camera) => {
             activeCamera = camera;
-            if (scene !== activeScene) {
-                if (activeScene) activeScene.removeEventListener("change", onSceneChange);
-                activeScene = scene;
-                activeScene.addEventListener("change", onSceneChange);
-                upload();
-            }
+            attach(scene);
             pushCamera();
             for (const p of passes) p.render();
             if (group) {
@@ -212,12 +237,7 @@ class HIPRenderer {
         // and used round-robin keep the GPU full (bench.py --frames-in-flight).
         this.renderAsync = (scene, camera) => {
             activeCamera = camera;
-            if (scene !== activeScene) {
-                if (activeScene) activeScene.removeEventListener("change", onSceneChange);
-                activeScene = scene;
-                activeScene.addEventListener("change", onSceneChange);
-                upload();
-            }
+            attach(scene);
             pushCamera();
             for (const p of passes) p.render();
             this._n.renderAsync(this._h);
@@ -233,8 +253,7 @@ class HIPRenderer {
             this._n.sort(this._h);
         };
         this.dispose = () => {                   // WebGLRenderer.ts:298-310
-            if (activeScene) activeScene.removeEventListener("change", onSceneChange);
-            activeScene = null;
+            detach();                            // (while the context lives: a scene with edits reads them back from it)
             held.clear();
             if (this._h) { dropSlots(); this._n.destroy(this._h); this._h = null; }
             initialized = false;
@@ -243,8 +262,7 @@ class HIPRenderer {
         // ---- optional device-side scene (SURVEY 8(f) rank 2): .splat rows in, Scene.setData and the transforms run as
         // kernels (bit-identical to Scene.js), no re-upload per change; render with renderDeviceScene(camera) ----
         this.setSceneRows = (rows) => {
-            if (activeScene) activeScene.removeEventListener("change", onSceneChange);
-            activeScene = null;
+            detach();
             this._n.setSceneRows(this._h, rows);
             vertexCount = rows.length / 32;
             for (const p of passes) p.init(this, null);

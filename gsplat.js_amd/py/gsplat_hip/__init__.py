@@ -102,6 +102,7 @@ EXPORTS = [
     "gsr_release_frame", "gsr_delivery_slot_ptr", "gsr_delivery_open_ex", "gsr_delivery_layout",
     "gsr_delivery_open_depth", "gsr_delivery_depth_layout",
     "gsr_set_hit_alpha", "gsr_depth_async", "gsr_read_depth", "gsr_depth_device_ptr", "gsr_pick",
+    "gsr_set_scene_arrays",
 ]
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p)
 GSR_COMM_ID_BYTES = 128
@@ -153,6 +154,7 @@ def load_library(path=None):
     L.gsr_read_sh_colors.argtypes = [vp, vp]
     L.gsr_set_depth_fade.argtypes = [vp, ctypes.c_int32, ctypes.c_float]
     L.gsr_set_scene_rows.argtypes = [vp, vp, ctypes.c_uint32]
+    L.gsr_set_scene_arrays.argtypes = [vp, vp, vp, vp, vp, ctypes.c_uint32]
     for name in ("gsr_scene_translate", "gsr_scene_rotate", "gsr_scene_scale"):
         getattr(L, name).argtypes = [vp, vp]
     L.gsr_scene_limit_box.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_uint32)]
@@ -406,6 +408,19 @@ class HIPRenderer:
         rows = np.ascontiguousarray(rows, dtype=np.uint8).reshape(-1)
         self._check(self._L.gsr_set_scene_rows(self._ctx, rows.ctypes.data, rows.size // 32))
         self._n = rows.size // 32
+        self._scene = None
+
+    def set_scene_arrays(self, data, positions, rotations, scales):
+        """A device scene the transforms accept, from Scene.data / positions / rotations (w, x, y, z) / scales as they are."""
+        data = np.ascontiguousarray(data, dtype=np.uint32).reshape(-1)
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1)
+        rot = np.ascontiguousarray(rotations, dtype=np.float32).reshape(-1)
+        scl = np.ascontiguousarray(scales, dtype=np.float32).reshape(-1)
+        n = pos.size // 3
+        if data.size < 8 * n or rot.size != 4 * n or scl.size != 3 * n:
+            raise ValueError("data / rotations / scales do not hold %d splats" % n)
+        self._check(self._L.gsr_set_scene_arrays(self._ctx, data.ctypes.data, pos.ctypes.data, rot.ctypes.data, scl.ctypes.data, n))
+        self._n = n
         self._scene = None
 
     def scene_translate(self, t):

@@ -16,7 +16,7 @@
  *   + texImage2D(scene.data)         src/renderers/WebGLRenderer.ts:185-195
  *                                      -> gsr_set_scene
  *   Scene.setData / translate / rotate / scale / limitBox   src/core/Scene.ts:58-366
- *                                      -> gsr_set_scene_rows, gsr_scene_* (optional device-side versions)
+ *                                      -> gsr_set_scene_rows / gsr_set_scene_arrays, gsr_scene_* (device-side versions)
  *   setShTextures + u_bandIndex      WebGLRenderer.ts:202-211,321-366
  *                                      -> gsr_set_scene_sh
  *   uniforms projection/view/focal/viewport + postMessage({viewProj})
@@ -111,11 +111,19 @@ int gsr_set_scene(gsr_ctx *ctx, const uint32_t *data, const float *positions, ui
  * transforms below run as kernels instead of JavaScript loops + full re-upload.  Results are bit-identical to the
  * JavaScript ones (Scene.ts:126-366).  q = (x, y, z, w); box = xMin, xMax, yMin, yMax, zMin, zMax. */
 int gsr_set_scene_rows(gsr_ctx *ctx, const uint8_t *rows, uint32_t n);
+/* The same kind of scene from a Scene's own four arrays, for a Scene that was loaded or transformed on the host before its
+ * first frame: data / positions as gsr_set_scene takes and checks them (GSR_ERR_SCENE: the context keeps what it had),
+ * rotations = Scene.rotations (w, x, y, z per splat), scales = Scene.scales (3 per splat).  Nothing is recomputed: the
+ * covariance words and colours of `data` are taken as they are, so what the context renders is what gsr_set_scene renders
+ * from the same data, and gsr_scene_* / gsr_read_scene work as after gsr_set_scene_rows.  Clears SH and frame state. */
+int gsr_set_scene_arrays(gsr_ctx *ctx, const uint32_t *data, const float *positions, const float *rotations, const float *scales,
+                         uint32_t n);
 int gsr_scene_translate(gsr_ctx *ctx, const double *t /* 3 */);
 int gsr_scene_rotate(gsr_ctx *ctx, const double *q /* 4 */);
 int gsr_scene_scale(gsr_ctx *ctx, const double *s /* 3 */);
 int gsr_scene_limit_box(gsr_ctx *ctx, const double *box /* 6 */, uint32_t *new_count);
-/* Any of the outputs may be NULL.  data: 8 u32 per splat; rotations (w,x,y,z) / scales only for scenes built from rows. */
+/* Any of the outputs may be NULL.  data: 8 u32 per splat; rotations (w,x,y,z) / scales only for scenes built from rows or
+ * from the four arrays.  The device lays the outputs out (one kernel), then one copy per output. */
 int gsr_read_scene(gsr_ctx *ctx, uint32_t *data, float *positions, float *rotations, float *scales, uint32_t *count);
 int gsr_scene_count(gsr_ctx *ctx, uint32_t *count); /* splats in the device scene (changes with gsr_scene_limit_box); no copy */
 

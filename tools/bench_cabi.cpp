@@ -3,7 +3,7 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--pick X,Y]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--pick X,Y] [--scene-arrays] [--scene-edit rotate]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
@@ -14,6 +14,10 @@
 // --deliver-depth f32|u16 (beside --deliver) opens depth rings (gsr_delivery_open_depth): every delivered frame carries its hit
 // plane, at every --depth-step-th pixel (1, the default, or 2), as float or as 16-bit inverse depth against --depth-near (default
 // 0.1), and the checksum of the last frame's plane is reported (gsr_delivery_depth_layout says where it lies in the slot).
+//
+// --scene-arrays builds every context's scene through gsr_set_scene_arrays instead of gsr_set_scene_rows, from the four arrays
+// gsr_read_scene returns for the rows (same scene, same hashes); --scene-edit rotate adds a last leg with a gsr_scene_rotate by one
+// degree about y in front of every frame (a turntable: the scene is edited on the device, nothing is uploaded) and reports its rate.
 //
 // Scene: the seeded synthetic generator of gsplat_hip/synth.py (mulberry32 counter PRNG, 24 draws per splat) written
 // out again in C++; log/exp/cos come from libm here and from numpy there, so a byte may differ in a rare rounding --
@@ -135,7 +139,8 @@ int main(int argc, char** argv)
     std::string deliver_depth = "none";
     int depth_step = 1;
     float depth_near = 0.1f;
-    bool depth = false, pick = false;
+    bool depth = false, pick = false, scene_arrays = false;
+    std::string scene_edit = "none";
     int32_t pick_xy[2] = {0, 0};
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -152,8 +157,10 @@ int main(int argc, char** argv)
         else if (a == "--depth-step") depth_step = std::atoi(next());
         else if (a == "--depth-near") depth_near = (float)std::atof(next());
         else if (a == "--depth") depth = true;
+        else if (a == "--scene-arrays") scene_arrays = true;
+        else if (a == "--scene-edit") scene_edit = next();
         else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--pick X,Y]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--pick X,Y] [--scene-arrays] [--scene-edit rotate]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
@@ -162,6 +169,7 @@ int main(int argc, char** argv)
     if (format == GSR_FORMAT_RGBA8 && deliver_format != "rgba8") { std::fprintf(stderr, "--deliver-format nv12|i420\n"); return 2; }
     const int32_t depth_format = deliver_depth == "f32" ? GSR_DEPTH_F32 : deliver_depth == "u16" ? GSR_DEPTH_U16 : GSR_DEPTH_NONE;
     if (depth_format == GSR_DEPTH_NONE && deliver_depth != "none") { std::fprintf(stderr, "--deliver-depth f32|u16\n"); return 2; }
+    if (scene_edit != "none" && scene_edit != "rotate") { std::fprintf(stderr, "--scene-edit rotate\n"); return 2; }
     if (depth_format != GSR_DEPTH_NONE && !deliver) { std::fprintf(stderr, "--deliver-depth goes beside --deliver\n"); return 2; }
 
     std::vector<uint8_t> rows;
@@ -188,6 +196,13 @@ int main(int argc, char** argv)
         if (rc) { std::fprintf(stderr, "gsr_create failed (%d): %s\n", rc, gsr_last_error(nullptr)); return 1; }
         ctx0 = ctx[c];
         CHECK(gsr_set_scene_rows(ctx[c], rows.data(), n));
+    }
+    if (scene_arrays) {   // the same scene once more, as a host that holds a Scene's four arrays hands it over
+        std::vector<uint32_t> data((size_t)n * 8);
+        std::vector<float> positions((size_t)n * 3), rotations((size_t)n * 4), scales((size_t)n * 3);
+        ctx0 = ctx[0];
+        CHECK(gsr_read_scene(ctx[0], data.data(), positions.data(), rotations.data(), scales.data(), nullptr));
+        for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_set_scene_arrays(c, data.data(), positions.data(), rotations.data(), scales.data(), n)); }
     }
     std::vector<Cam> poses(120);
     for (int k = 0; k < 120; k++) poses[k] = orbit_camera(k, 120, cfg->w, cfg->h, cfg->fx);
@@ -309,6 +324,21 @@ int main(int argc, char** argv)
         CHECK(gsr_release_frame(ctx[0], serial));
         if (!same) { std::fprintf(stderr, "the delivered frame differs from gsr_read_pixels_rgba8\n"); return 1; }
     }
+    // --scene-edit rotate: the orbit once more with the scene turned on the device in front of every frame (last: it changes the scene)
+    double edit_sec = 0;
+    if (scene_edit == "rotate") {
+        const double half = 0.5 * 3.14159265358979323846 / 180.0, dq[4] = {0.0, std::sin(half), 0.0, std::cos(half)};
+        auto edit_step = [&](int k) -> int {
+            if (int rc = gsr_scene_rotate(ctx[k % in_flight], dq)) return rc;
+            return step(k);
+        };
+        for (int k = 0; k < warmup; k++) { ctx0 = ctx[k % in_flight]; CHECK(edit_step(k)); }
+        for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_sync(c)); }
+        const auto e0 = std::chrono::steady_clock::now();
+        for (int k = 0; k < frames; k++) { ctx0 = ctx[(warmup + k) % in_flight]; CHECK(edit_step(warmup + k)); }
+        for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_sync(c)); }
+        edit_sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - e0).count();
+    }
     char name[128] = "";
     int32_t cus = 0, khz = 0;
     (void)gsr_device_info(ctx[0], name, (int32_t)sizeof name, &cus, &khz);
@@ -333,6 +363,8 @@ int main(int argc, char** argv)
     if (depth)
         std::printf(", \"frames_per_sec_plain\": %.1f, \"frames_per_sec_with_depth\": %.1f, \"depth_legs\": 3",
                     3.0 * frames / depth_sec[0], 3.0 * frames / depth_sec[1]);
+    if (scene_arrays) std::printf(", \"scene_from\": \"gsr_set_scene_arrays\"");
+    if (scene_edit == "rotate") std::printf(", \"scene_edit\": \"rotate\", \"frames_per_sec_scene_edit\": %.1f", frames / edit_sec);
     if (pick)
         std::printf(", \"pick\": {\"x\": %d, \"y\": %d, \"index\": %u, \"depth\": %s, \"mean\": %.9g, \"alpha\": %.9g}",
                     pick_xy[0], pick_xy[1], picked.index, picked.index == 0xffffffffu ? "null" : std::to_string(picked.depth).c_str(), (double)picked.mean, (double)picked.alpha);
