@@ -190,10 +190,9 @@ struct gsr_ctx {
         gsr::DevBuf<uint32_t> seg_start, items;
         gsr::DevBuf<unsigned long long> mask;   // per-bin arrival masks of the compositor (null: separate k_combine launch)
         gsr::DevBuf<float4> partial;
-        uint32_t rounds = 1;               // rounds of 2048 ranks per binning workgroup
-        bool two_level = false;
-        uint32_t cell_capacity_alloc = 0, cell_ncells_alloc = 0, cell_grid = 0;
-        uint32_t blocks = 0, capacity = 0, table_elems = 0, nbins_alloc = 0;
+        gsr::BinPlan plan{};               // the binning's form and launch shapes for the context as it stands (plan_bins)
+        uint32_t cell_capacity_alloc = 0, cell_ncells_alloc = 0;
+        uint32_t capacity = 0, table_elems = 0, nbins_alloc = 0;
         uint32_t max_items = 0, seg_len = 0, blend_grid = 2048;
         uint32_t seg_target_items = 5000;
         uint32_t blend_sub = 1;            // compositor waves per 16x16 tile: 1 (k_blend) or 2 (k_blend2)
@@ -324,6 +323,13 @@ inline BinGrid make_grid(const gsr_ctx* c)
         g.bx_lo = 0; g.bx_hi = g.nbx;
     }
     return g;
+}
+
+// waves per workgroup of the heavy front-end kernels: throughput contexts run beside other frames' compositors, so their
+// front-end workgroups are narrow and fit what a few retired compositor workgroups leave free on a CU
+inline uint32_t front_waves_of(const gsr_ctx* c)
+{
+    return c->knobs.front_waves ? c->knobs.front_waves : (c->opt.flags & GSR_FLAG_THROUGHPUT) ? FRONT_WAVES_NARROW : FRONT_WAVES_WIDE;
 }
 
 // gsr_frame.cpp

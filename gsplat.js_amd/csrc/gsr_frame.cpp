@@ -30,8 +30,6 @@ constexpr uint32_t BLEND_WG_PER_CU_THROUGHPUT = 7;
 // Two waves per tile (k_blend2, 512-thread workgroups): three workgroups per CU are resident (6 waves per SIMD).
 constexpr uint32_t BLEND_WG_PER_CU_SUB2 = 3;
 constexpr uint32_t SUB2_MAX_BINS = 4096, SEG_LEN_MIN_SUB2 = 1024;
-constexpr uint32_t BIN_BLOCKS_TARGET = 640, BIN_ROUNDS_MAX = 8;
-constexpr uint32_t TWO_LEVEL_MIN_BINS = 4096, CELL_WG_PER_CU = 4;
 constexpr uint32_t SEG_LEN_WHOLE_BIN = 0x7fffff00u;
 
 // Sort order.  Up to BUCKET_ORDER_MAX_N splats the radix sort runs high digit first with one workgroup per bucket
@@ -91,9 +89,7 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
     a.n = c->n;
     a.grid = g;
     a.early_out_eps = c->opt.early_out_eps;
-    // throughput contexts run beside other frames' compositors: their front-end workgroups are narrow, so that they fit what
-    // a few retired compositor workgroups leave free on a CU (the launchers keep the wide forms off the one-level 1080p chain)
-    a.front_waves = c->knobs.front_waves ? c->knobs.front_waves : throughput ? FRONT_WAVES_NARROW : FRONT_WAVES_WIDE;
+    a.front_waves = front_waves_of(c);   // (the launchers keep the wide forms off the one-level 1080p chain)
     a.sort_culled = cull && c->n;   // (an empty frame sorts nothing, so nothing of it is partial)
 
     // a sort-only frame has its own slots (sets 1 and 2 in turn; set 0 belongs to the render frames and k_begin_frame)
@@ -148,8 +144,7 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
     bb.bin_total = c->bin.total;
     bb.bin_start = c->bin.start;
     bb.bin_start_pre = c->bin.start_pre;
-    bb.rounds = c->bin.rounds;
-    bb.big = c->knobs.bin_big;
+    bb.plan = c->bin.plan;
     bb.seg_start = c->bin.seg_start;
     bb.items = c->bin.items;
     bb.list = c->bin.list;
@@ -168,7 +163,6 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
     bb.queue = &fs->queue;
     bb.queue_start = queue_start;
     bb.seg_target_items = c->bin.seg_target_items;
-    bb.nblocks = c->bin.blocks;
     bb.bin_mask = c->bin.mask;
     bb.long_policy = c->bin.seg_len == SEG_LEN_WHOLE_BIN ? 0 : c->knobs.long_items >= 0 ? c->knobs.long_items : c->knobs.saturate ? -1 : 0;
     bb.seg_len_long = SEG_LEN_LONG;
@@ -177,7 +171,6 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
     bb.long_tiles_x2 = throughput ? LONG_TILES_X2_THROUGHPUT : LONG_TILES_X2_EXACT;
     bb.long_tau_bin = c->knobs.long_tau;
     bb.long_mass_min = throughput ? LONG_MASS_MIN_THROUGHPUT : LONG_MASS_MIN_EXACT;
-    bb.two_level = c->bin.two_level ? 1u : 0u;
     bb.cell_list = c->bin.cell_list;
     bb.cell_total = c->bin.cell_total;
     bb.cell_start = c->bin.cell_start;
@@ -185,7 +178,6 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
     bb.chunk_info = c->bin.chunk_info;
     bb.cell_wcnt = c->bin.cell_wcnt;
     bb.cell_table2 = c->bin.cell_table2;
-    bb.cell_grid = c->bin.cell_grid;
     bb.band = band_is_partial(g) ? 1u : 0u;
     bb.n_max = c->n;
 
@@ -250,11 +242,10 @@ int enqueue_chain(gsr_ctx* c, const FrameArgs& a, bool timing)
     if (timing) HIP_TRY(c, hipEventRecord(ev[EV_SORT], s));
     if (a.render) {
         if (!a.n) {
-            const int nbins = (a.grid.bx_hi - a.grid.bx_lo) * a.grid.nby;
-            HIP_TRY(c, hipMemsetAsync(a.bin.bin_total, 0, sizeof(uint32_t) * nbins, s));
+            HIP_TRY(c, hipMemsetAsync(a.bin.bin_total, 0, sizeof(uint32_t) * a.bin.plan.nbins, s));
             HIP_TRY(c, hipMemsetAsync(a.bin.overflow, 0, sizeof(uint32_t), s));   // (k_project_key zeroes it otherwise)
         }
-        launch_bin(a.bin, a.grid, a.n, s, a.front_waves);
+        launch_bin(a.bin, a.grid, s);
         if (timing) HIP_TRY(c, hipEventRecord(ev[EV_BIN], s));
         launch_blend(a.blend, a.grid, a.early_out_eps, s, (timing && !a.blend.bin_mask) ? ev[EV_BLEND] : nullptr);
         if (timing) HIP_TRY(c, hipEventRecord(ev[EV_COMBINE], s));
@@ -359,22 +350,12 @@ int alloc_bins(gsr_ctx* c)
     gsr_ctx::Bin& b = c->bin;
     const Knobs& k = c->knobs;
     const BinGrid g = make_grid(c);
-    const uint32_t nbins = (uint32_t)((g.bx_hi - g.bx_lo) * g.nby);
-    // Ranks per binning workgroup: rounds of 2048.  The count / scan / scatter passes exchange a [workgroup][bin] table; with
-    // one round per workgroup it is 80 MB at 5 M splats and 8160 bins.  Large grids (the k_bin_scatter_big form, > 4096 bins)
-    // take several rounds per workgroup, keeping about BIN_BLOCKS_TARGET workgroups (C4: 4 rounds, 611 workgroups, 20 MB).
-    // Two-level binning (k_bin.hip): grids above TWO_LEVEL_MIN_BINS bins whose cells of 4 x 4 bins number at most 4096.
-    const uint32_t ncells = (uint32_t)(((g.bx_hi - g.bx_lo + 3) >> 2) * ((g.nby + 3) >> 2));
-    // (its level-two stores address the list with 32-bit byte offsets: lists of 2^30 entries or more take the one-level pass)
-    const uint64_t cap_now = b.capacity ? b.capacity : std::max<uint64_t>(6ull * c->n + (1u << 20), 1u << 22);
-    b.two_level = ncells <= 4096u && cap_now < (1ull << 30) &&
-                  (k.bin_two_level >= 0 ? k.bin_two_level == 1 : nbins > TWO_LEVEL_MIN_BINS);
-    b.rounds = 1;
-    if (!b.two_level && k.bin_big && nbins > 4096)
-        b.rounds = std::min<uint32_t>(BIN_ROUNDS_MAX, std::max<uint32_t>(1u, ((c->n + 2047u) / 2048u + BIN_BLOCKS_TARGET - 1u) / BIN_BLOCKS_TARGET));
-    if (!b.two_level && k.bin_big && nbins > 4096 && k.bin_rounds > 0) b.rounds = (uint32_t)k.bin_rounds;
-    b.blocks = (c->n + 2048u * b.rounds - 1u) / (2048u * b.rounds);
-    const size_t table = (size_t)std::max(b.blocks, 1u) * (b.two_level ? ncells + 1u : nbins);
+    // the binning's form, grids and table shape for this grid, scene and list (plan_bins, k_bin.hip): the buffers follow it
+    const uint64_t capacity = b.capacity ? b.capacity : std::max<uint64_t>(6ull * c->n + (1u << 20), 1u << 22);   // (a new scene's list, allocated below)
+    b.plan = plan_bins(g, c->n, capacity, c->cu_count, front_waves_of(c), BinKnobs{k.bin_two_level, k.bin_big, k.bin_rounds, k.cell_grid});
+    const BinPlan& p = b.plan;
+    const uint32_t nbins = (uint32_t)p.nbins;
+    const size_t table = (size_t)p.table_rows * p.table_cols;
     if (table > b.table_elems) {
         if (int r = b.table.alloc(c, table)) return r;
         b.table_elems = (uint32_t)table;
@@ -392,11 +373,12 @@ int alloc_bins(gsr_ctx* c)
         items_dirty = true;
     }
     if (!b.capacity) {
-        b.capacity = std::max<uint32_t>(6u * c->n + (1u << 20), 1u << 22);
+        b.capacity = (uint32_t)capacity;
         if (int r = b.list.alloc(c, b.capacity)) return r;
         items_dirty = true;
     }
-    if (b.two_level) {
+    if (p.form == BIN_TWO_LEVEL) {
+        const uint32_t ncells = (uint32_t)p.ncells;
         if (ncells > b.cell_ncells_alloc) {
             if (int r = b.cell_total.alloc(c, ncells + 1)) return r;
             if (int r = b.cell_start.alloc(c, ncells + 1)) return r;
@@ -405,15 +387,12 @@ int alloc_bins(gsr_ctx* c)
             b.cell_capacity_alloc = 0;
         }
         if (b.capacity > b.cell_capacity_alloc) {
-            const size_t chunks = (size_t)b.capacity / 2048u + ncells + 1u;
             if (int r = b.cell_list.alloc(c, (size_t)b.capacity * 2)) return r;
-            if (int r = b.cell_table2.alloc(c, chunks * 16u)) return r;
-            if (int r = b.chunk_info.alloc(c, chunks * 4u)) return r;
-            if (int r = b.cell_wcnt.alloc(c, chunks * 64u)) return r;
+            if (int r = b.cell_table2.alloc(c, (size_t)p.chunks * 16u)) return r;
+            if (int r = b.chunk_info.alloc(c, (size_t)p.chunks * 4u)) return r;
+            if (int r = b.cell_wcnt.alloc(c, (size_t)p.chunks * 64u)) return r;
             b.cell_capacity_alloc = b.capacity;
         }
-        // the level-two kernels stride over the frame's chunks: two 16-wave workgroups per CU, twice over
-        b.cell_grid = k.cell_grid ? k.cell_grid : (uint32_t)std::max(c->cu_count, 1) * CELL_WG_PER_CU;
     }
     const bool throughput = (c->opt.flags & GSR_FLAG_THROUGHPUT) != 0;
     b.seg_len = c->opt.early_out_eps > 0.0f ? SEG_LEN_WHOLE_BIN : SEG_LEN_MIN;

@@ -205,10 +205,43 @@ struct BinGrid {
     int32_t bx_lo, bx_hi;      // bin columns of this context's band [lo, hi)
     int32_t W, H;
 };
+// The binning plan: which of k_bin.hip's forms a frame runs, with what grids, LDS sizes and table shape.  plan_bins (k_bin.hip)
+// is the one place that decides it; alloc_bins sizes the buffers from it and keeps it, launch_bin launches from it, and -- being
+// part of BinBuffers, hence of FrameArgs -- a captured graph is dropped exactly when it changes.  Trivially copyable, filled by
+// name into zeroed storage (FrameArgs is compared as bytes).
+enum BinForm : uint32_t {
+    BIN_FINALIZE_ONLY = 0,    // a scene without splats: k_bin_finalize alone
+    BIN_FUSED_WIDE,           // k_bin_count<16> + k_bin_scatter<groups, true> (the finalize step is the scatter's extra workgroup)
+    BIN_FUSED_NARROW,         // k_bin_count<8> + k_bin_scatter_narrow<8>: the same at FRONT_WAVES_NARROW (throughput contexts)
+    BIN_SEPARATE_FINALIZE,    // k_bin_count<16> + k_bin_finalize + k_bin_scatter<4, false>
+    BIN_LARGE_GRID,           // k_bin_count<16> + k_bin_starts + k_bin_scatter_big<4, steps_per_wave>, `rounds` rounds per workgroup
+    BIN_TWO_LEVEL,            // k_bin_count<16> + k_cell_scatter1<groups> over cells, then k_cell_count / _scan / k_bin_starts / k_cell_scatter2
+};
+struct BinSlices { int32_t sx, sy, w, h; };  // sx x sy sub-grids of w x h bins (the last ones may be smaller)
+struct BinPlan {
+    uint32_t form;               // BinForm
+    int32_t nbins;               // bins of the context's band
+    uint32_t groups;             // step groups of the scatter workgroup: 8 or 4
+    uint32_t steps_per_wave;     // 64-rank steps per wave and round: 2; 4 in the narrow form; 1 in the large-grid form's 1024-rank rounds
+    uint32_t rounds;             // rounds of 2048 ranks a binning workgroup takes (> 1 only in the large-grid form)
+    uint32_t blocks;             // binning workgroups = table rows in use: ceil(ranks / (2048 * rounds))
+    BinSlices slices;            // the scatter's sub-grids (blockIdx.y) -- of cells in the two-level form
+    uint32_t count_slices, count_rows;   // the count pass's row slices (blockIdx.y) and the bin rows of one
+    uint32_t count_lds, scatter_lds;     // dynamic LDS bytes of the count and the (level-one) scatter kernel
+    uint32_t extra_wg;           // 1: the scatter's grid has one more workgroup, the finalize step
+    uint32_t table_rows, table_cols;     // the [workgroup][bin] table (two levels: [workgroup][cell + 1]); elements = rows x columns
+    int32_t ncx, ncy, ncells;    // cells of 4 x 4 bins across / down the band
+    uint32_t cell_grid;          // two levels: workgroups of the level-two kernels (they stride over the frame's chunks)
+    uint32_t chunks;             // two levels: entries the per-chunk tables are allocated for
+};
+struct BinKnobs { int32_t two_level; uint32_t big; int64_t rounds; uint32_t cell_grid; };   // Knobs::bin_two_level, bin_big, bin_rounds, cell_grid
+// (capacity: entries of the list; cu_count: the device's compute units; front_waves: FRONT_WAVES_WIDE or _NARROW.  No HIP call.)
+BinPlan plan_bins(const BinGrid& g, uint32_t n, uint64_t capacity, int cu_count, uint32_t front_waves, const BinKnobs& k);
+
 struct BinBuffers {
     const uint32_t* depth_index; // *count entries
     const uint32_t* count;       // ranks to bin (SortBuffers::count)
-    uint32_t* table;             // nblocks * nbins  (counts, then per-workgroup offsets inside each bin)
+    uint32_t* table;             // plan.table_rows x plan.table_cols  (counts, then per-workgroup offsets inside each bin)
     int32_t* slots;              // FRAME_SLOTS partial (visible splats, 16x16 tile overlaps) sums of k_project_key; the finalize step,
                                  // their last reader in a frame, resets them for the next one
     const uint32_t* rect_idx;    // n: packed bin rectangle of every splat (k_project_key)
@@ -217,9 +250,7 @@ struct BinBuffers {
     uint32_t* bin_total;         // nbins (zeroed by the caller when n == 0)
     uint32_t* bin_start;         // nbins + 1
     uint32_t* bin_start_pre;     // nbins + 1: the same starts, computed ahead of the scatter by k_bin_starts (large-grid form)
-    uint32_t rounds;             // rounds of 2048 ranks a binning workgroup takes (table rows = ceil(ranks / (2048 * rounds)); > 1 only with big)
-    uint32_t big;                // large bin grids: 1 = k_bin_scatter_big (finalize as its first workgroup, rounds of 2048 ranks),
-                                 // 2 = the same with rounds of 1024 ranks (half the step loops); 0 = the 64-register kernel (A/B knob)
+    BinPlan plan;                // the form and its launch shapes (plan_bins)
     uint32_t* seg_start;         // nbins + 1: first compositor work item of each bin; [nbins] = item count
     uint32_t* items;             // max_items x 4 words: (bin | segment << 16, first list entry, end, first partial slot of the bin | its segments << 25)
     uint32_t* list;              // capacity entries (splat indices, depth order inside each bin)
@@ -239,7 +270,6 @@ struct BinBuffers {
     uint32_t* queue;             // the compositor's work-item counter, set to queue_start (= its grid size) by k_bin_finalize
     uint32_t queue_start;
     uint32_t seg_target_items;   // full segments the frame should be cut into at least (long lists -> longer segments)
-    uint32_t nblocks;
     unsigned long long* bin_mask; // nbins: the compositor's per-bin arrival masks (one bit per segment), zeroed by the finalize step (may be null)
     int32_t long_policy;         // work items of at least seg_len_long entries: 1 always, 0 never, -1 where the frame's optical depth >= long_tau
     uint32_t seg_len_long, long_tau;
@@ -248,7 +278,6 @@ struct BinBuffers {
     uint32_t long_tau_bin;       // 0: the built-in per-bin thresholds (k_bin_finalize); else: bins from this optical depth on are one item (GSR_LONG_TAU)
     uint32_t long_mass_min;      // a frame that is not dense as a whole: its saturated bins become items only from this optical mass per list entry on (pixels)
     // two-level binning (launch_bin; large bin grids): cells of 4 x 4 bins first, then the cell lists' chunks into the bins
-    uint32_t two_level;          // 1: on (nblocks = workgroups of 2048 ranks, rounds = 1; table holds nblocks x (cells + 1) words)
     uint32_t* cell_list;         // 2 x capacity words: (splat index, rectangle in bins) per cell-list entry
     uint32_t* cell_total;        // cells + 1: entries per cell; [cells] = list entries the frame needs
     uint32_t* cell_start;        // cells + 1
@@ -256,11 +285,10 @@ struct BinBuffers {
     uint32_t* chunk_info;        // (capacity / 2048 + cells) x 4: per chunk its cell, first and end entry
     uint32_t* cell_wcnt;         // (capacity / 2048 + cells) x 64 words: per chunk, bin and wave of k_cell_scatter2 one byte: the wave's entries
     uint32_t* cell_table2;       // (capacity / 2048 + cells) x 16: per chunk and bin of its cell: entries, then their first slot
-    uint32_t cell_grid;          // workgroups of the level-two kernels (they stride over the frame's chunks)
     uint32_t band;               // 1: a band context (the frame holds fewer ranks than the scene: scans and workgroups stop at *count's rows)
     uint32_t n_max;              // entries the rank-ordered buffers hold (the scene's splats): k_bin_count may load that far before it knows *count
 };
-void launch_bin(const BinBuffers& b, const BinGrid& g, uint32_t n, hipStream_t s, uint32_t front_waves = FRONT_WAVES_WIDE);
+void launch_bin(const BinBuffers& b, const BinGrid& g, hipStream_t s);
 
 struct BlendBuffers {
     const uint32_t* items;      // work items, four words each (BinBuffers::items)

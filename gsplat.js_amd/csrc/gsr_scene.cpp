@@ -8,6 +8,7 @@ using namespace gsr;
 int gsr::alloc_scene(gsr_ctx* c, uint32_t n, bool with_rows)
 {
     c->n = 0; c->have_frame = false; c->have_sort = false; c->scene.have_rows = false;
+    c->bin.plan.form = BIN_FINALIZE_ONLY;   // (no splats until the caller's alloc_bins plans for the new count: a frame in between only finalizes)
     if (c->words.mailbox) reinterpret_cast<volatile uint32_t*>(c->words.mailbox)[2] = 0xffffffffu;   // a new scene: LSD order until a frame reports
     c->scene.drop_sh();
     gsr_ctx::Sort& so = c->sort;
@@ -171,12 +172,14 @@ int gsr_scene_limit_box(gsr_ctx* c, const double* box, uint32_t* new_count)
         std::swap(c->scene.arr, dst);
         c->n = kept;   // arrays keep their old capacity; per-frame buffers sized for the old count still fit
         c->sort.blocks = (kept + c->sort.kpb - 1) / c->sort.kpb;
-        c->bin.blocks = (kept + 2048u * c->bin.rounds - 1u) / (2048u * c->bin.rounds);
         // The compaction renumbers the splats, so SH rows (indexed by splat - (bandsIndices[0] + 1)) and the band
         // thresholds no longer belong to them: the SH state is dropped and the scene falls back to its rgba8 colours
         // until gsr_set_scene_sh is called again.  (Scene.limitBox, Scene.ts:307-366, leaves shs_rgb / bandsIndices
         // untouched, i.e. stale; a host that wants SH after limitBox re-packs them for the kept splats.)
         c->scene.drop_sh();
+        // the binning's plan for the new count (plan_bins): fewer splats can mean fewer rounds and so MORE table rows, which
+        // alloc_bins regrows; like every alloc_bins it drops what the last frame left in the lists (they index the old numbering)
+        if ((r = alloc_bins(c))) return r;
     }
     if (new_count) *new_count = kept;
     return GSR_OK;

@@ -16,6 +16,7 @@
 #include "gsr_internal.h"
 
 #include <algorithm>
+#include <cstring>
 #include <mutex>
 
 
@@ -478,8 +479,7 @@ static_assert(SCAT_STEPS * WAVE == (int)BIN_RANKS_PER_BLOCK, "scatter and count 
 constexpr size_t SCAT_LDS_BUDGET = 150 * 1024;
 constexpr size_t SCAT_LDS_TWO_PER_CU = 72 * 1024;   // with at most this much, two workgroups share a CU
 
-struct BinSlices { int32_t sx, sy, w, h; };  // sx x sy sub-grids of w x h bins (the last ones may be smaller)
-
+// (BinSlices, sx x sy sub-grids of w x h bins, is in gsr_internal.h: the plan carries it)
 inline size_t scatter_lds_bytes(int w, int h, int groups, int steps = SCAT_STEPS)
 {
     return (size_t)(((1 + groups / 2) * w * h + 1) & ~1) * 4 + (size_t)steps * (w + h) * 8;
@@ -1029,121 +1029,199 @@ static void set_scatter_lds_attribute()
     (void)hipGetDevice(&dev);
     std::call_once(once[dev >= 0 && dev < 64 ? dev : 0], [] {
         const int want = (int)(SCAT_LDS_BUDGET + 1024);
-        for (const void* fn : {(const void*)k_bin_scatter<8, true>, (const void*)k_bin_scatter<8, false>,
-                               (const void*)k_bin_scatter<4, true>, (const void*)k_bin_scatter<4, false>,
-                               (const void*)k_bin_scatter_big<8, 2>, (const void*)k_bin_scatter_big<4, 2>,
-                               (const void*)k_bin_scatter_big<4, 1>, (const void*)k_cell_scatter1<8>, (const void*)k_cell_scatter1<4>,
-                               (const void*)k_bin_scatter_narrow<8>})
+        for (const void* fn : {(const void*)k_bin_scatter<8, true>, (const void*)k_bin_scatter<4, true>, (const void*)k_bin_scatter<4, false>,
+                               (const void*)k_bin_scatter_big<4, 2>, (const void*)k_bin_scatter_big<4, 1>,
+                               (const void*)k_cell_scatter1<8>, (const void*)k_cell_scatter1<4>, (const void*)k_bin_scatter_narrow<8>})
             (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, want);
         (void)hipGetLastError();  // a failure shows up as the launch error
     });
 }
 
-static FinalizeArgs make_finalize_args(const BinBuffers& b, int nbins, uint32_t n)
-{
-    return FinalizeArgs{b.bin_total, nbins, b.seg_len, b.seg_target_items, b.items_by_size, b.seg_len_dev, b.max_items, b.capacity,
-                        b.slots, n ? 1u : 0u, b.bin_start, b.seg_start, b.items, b.overflow, b.visible, b.tile_entries, b.accum,
-                        b.report, b.queue, b.queue_start, b.mailbox, b.bin_mask, b.long_policy, b.seg_len_long, b.long_tau, b.npix, b.long_tiles_x2, b.long_tau_bin, b.long_mass_min};
-}
+// ---------------------------------------------------------------------------
+// The plan: every choice between the forms above and every size that follows from it, made once (BinPlan, gsr_internal.h).
+// The thresholds live here and nowhere else; alloc_bins allocates by the result and launch_bin launches by it.
+// ---------------------------------------------------------------------------
+constexpr int FUSED_MAX_BINS = 4096;          // up to here every scatter workgroup scans the bin totals itself (bin_scatter_body, FUSED)
+constexpr int TWO_LEVEL_MIN_BINS = 4096;      // above: two levels, where they apply
+constexpr int TWO_LEVEL_MAX_CELLS = 4096;     // level one's count pass keeps one LDS counter per cell, unsliced
+constexpr uint64_t TWO_LEVEL_MAX_CAPACITY = 1ull << 30;   // (exclusive) level two's stores address the list with 32-bit byte offsets
+// Ranks per binning workgroup: rounds of 2048.  The count / scan / scatter passes exchange a [workgroup][bin] table; with one
+// round per workgroup it is 80 MB at 5 M splats and 8160 bins.  The large-grid form takes several rounds per workgroup,
+// keeping about BIN_BLOCKS_TARGET workgroups (C4: 4 rounds, 611 workgroups, 20 MB).
+constexpr uint32_t BIN_BLOCKS_TARGET = 640, BIN_ROUNDS_MAX = 8;
+constexpr uint32_t CELL_WG_PER_CU = 4;        // the level-two kernels stride over the frame's chunks: two 16-wave workgroups per CU, twice over
 
 // cells across / down a grid of bins
 inline int cells_of(int bins) { return (bins + CELL_SIDE - 1) >> CELL_SHIFT; }
+
+BinPlan plan_bins(const BinGrid& g, uint32_t n, uint64_t capacity, int cu_count, uint32_t front_waves, const BinKnobs& k)
+{
+    BinPlan p;
+    memset(&p, 0, sizeof p);
+    const int nbxb = g.bx_hi - g.bx_lo, nbins = nbxb * g.nby;
+    p.nbins = nbins;
+    p.ncx = cells_of(nbxb); p.ncy = cells_of(g.nby); p.ncells = p.ncx * p.ncy;
+    p.rounds = 1;
+    p.table_rows = 1; p.table_cols = (uint32_t)std::max(nbins, 1);
+    if (!n || nbins <= 0) return p;   // BIN_FINALIZE_ONLY
+    const bool two_level = p.ncells <= TWO_LEVEL_MAX_CELLS && capacity < TWO_LEVEL_MAX_CAPACITY &&
+                           (k.two_level >= 0 ? k.two_level == 1 : nbins > TWO_LEVEL_MIN_BINS);
+    const bool fused = nbins <= FUSED_MAX_BINS;
+    // the grid the scatter workgroups hold in LDS: the bins, or level one's cells
+    p.slices = two_level ? make_slices(p.ncx, p.ncy) : make_slices(nbxb, g.nby);
+    // 8 groups of 4 steps where their table still lets two workgroups share a CU, else 4 groups of 8 steps.  (One level above
+    // FUSED_MAX_BINS: the fewest sub-grids that fit 4 groups in the budget never leave one that fits 8 here, for any grid of
+    // up to 256 x 256 bins -- tests/test_bin_plan.py -- so those forms exist with 4 groups only; 8 groups' LDS would hold them.)
+    p.groups = scatter_lds_bytes(p.slices.w, p.slices.h, 8) <= SCAT_LDS_TWO_PER_CU ? 8 : 4;
+    p.steps_per_wave = SCAT_STEPS_PER_WAVE;
+    uint32_t waves = SCAT_WAVES;
+    if (two_level) {
+        p.form = BIN_TWO_LEVEL;
+        p.extra_wg = 1;
+        p.count_slices = 1; p.count_rows = (uint32_t)p.ncy;   // (the table's last column sums the rectangles' areas in bins)
+        p.count_lds = (uint32_t)((p.ncells + 1) * sizeof(uint32_t));
+        p.table_cols = (uint32_t)p.ncells + 1u;
+        p.cell_grid = k.cell_grid ? k.cell_grid : (uint32_t)std::max(cu_count, 1) * CELL_WG_PER_CU;
+        p.chunks = (uint32_t)(capacity / CELL_CHUNK) + (uint32_t)p.ncells + 1u;
+    } else {
+        if (fused) {
+            // the narrow forms of the count and the scatter kernel: the 1080p chain of a throughput context (same grids, same table rows)
+            const bool narrow = front_waves == FRONT_WAVES_NARROW && p.groups == 8;
+            p.form = narrow ? BIN_FUSED_NARROW : BIN_FUSED_WIDE;
+            p.extra_wg = 1;
+            if (narrow) { waves = FRONT_WAVES_NARROW; p.steps_per_wave = SCAT_STEPS / (int)FRONT_WAVES_NARROW; }
+        } else if (k.big) {
+            // the large-grid form; with 1024-rank rounds (one step per wave; k.big == 2): 4 groups of 4 steps -- ~6 instead of ~11 LDS
+            // reads per list entry in the slot phase, the phase the kernel is bound by -- at twice the per-round fixed work
+            // (at 1080p the large-grid form loses to the two-workgroups-per-CU kernel: C3 binning 47.3 -> 54.1 us, measured)
+            p.form = BIN_LARGE_GRID;
+            p.extra_wg = 1;
+            if (k.big == 2 && p.groups == 4) p.steps_per_wave = 1;
+            p.rounds = k.rounds > 0 ? (uint32_t)k.rounds
+                                    : std::min(BIN_ROUNDS_MAX, std::max(1u, ((n + BIN_RANKS_PER_BLOCK - 1u) / BIN_RANKS_PER_BLOCK + BIN_BLOCKS_TARGET - 1u) / BIN_BLOCKS_TARGET));
+        } else {
+            p.form = BIN_SEPARATE_FINALIZE;
+        }
+        // the count pass keeps one counter per bin in LDS and is cut into row slices only beyond CNT_MAX_BINS bins (above 4K)
+        // (whole rows: where rounding the rows up would pass CNT_MAX_BINS counters, one slice more)
+        const uint32_t rows = (uint32_t)g.nby;
+        uint32_t slices = (uint32_t)((nbins + CNT_MAX_BINS - 1) / CNT_MAX_BINS);
+        while (slices < rows && (rows + slices - 1u) / slices * (uint32_t)nbxb > (uint32_t)CNT_MAX_BINS) slices++;
+        p.count_rows = (rows + slices - 1u) / slices;
+        p.count_slices = (rows + p.count_rows - 1u) / p.count_rows;
+        p.count_lds = (uint32_t)(p.count_rows * nbxb * sizeof(uint32_t));
+        p.table_cols = (uint32_t)nbins;
+    }
+    p.blocks = (uint32_t)(((uint64_t)n + (uint64_t)BIN_RANKS_PER_BLOCK * p.rounds - 1u) / ((uint64_t)BIN_RANKS_PER_BLOCK * p.rounds));
+    p.table_rows = p.blocks;
+    // (the finalize step, when it runs as the scatter's extra workgroup, is handed FIN_SCRATCH_WORDS of the dynamic LDS)
+    p.scatter_lds = (uint32_t)std::max(scatter_lds_bytes(p.slices.w, p.slices.h, (int)p.groups, (int)(waves * p.steps_per_wave)), FIN_SCRATCH_WORDS * sizeof(uint32_t));
+    return p;
+}
+
+// The plan for a grid of nbxb x nby bins, for tests (tests/test_bin_plan.py): no context and no device, so it answers wherever
+// the library loads.  Returns sizeof(BinPlan), for the caller to check its idea of the layout against.
+extern "C" int gsr_debug_bin_plan(int nbxb, int nby, unsigned int n, unsigned long long capacity, int cu_count, unsigned int front_waves,
+                                   int two_level, unsigned int big, long long rounds, unsigned int cell_grid, BinPlan* out)
+{
+    BinGrid g;
+    g.nbx = nbxb; g.nby = nby; g.bx_lo = 0; g.bx_hi = nbxb; g.W = nbxb * BIN_PX; g.H = nby * BIN_PX;
+    *out = plan_bins(g, n, capacity, cu_count, front_waves, BinKnobs{two_level, big, rounds, cell_grid});
+    return (int)sizeof(BinPlan);
+}
+
+static FinalizeArgs make_finalize_args(const BinBuffers& b)
+{
+    return FinalizeArgs{b.bin_total, b.plan.nbins, b.seg_len, b.seg_target_items, b.items_by_size, b.seg_len_dev, b.max_items, b.capacity,
+                        b.slots, b.plan.form != BIN_FINALIZE_ONLY ? 1u : 0u, b.bin_start, b.seg_start, b.items, b.overflow, b.visible, b.tile_entries, b.accum,
+                        b.report, b.queue, b.queue_start, b.mailbox, b.bin_mask, b.long_policy, b.seg_len_long, b.long_tau, b.npix, b.long_tiles_x2, b.long_tau_bin, b.long_mass_min};
+}
 
 // Two levels (see "Two-level binning" above): count / scan / scatter over the cells, then count / scan / scatter of the
 // cell lists' chunks into the bins; the finalize step is the first workgroup of the last kernel.
 static void launch_bin_two_level(const BinBuffers& b, const BinGrid& g, hipStream_t s)
 {
-    const int nbxb = g.bx_hi - g.bx_lo, nbins = nbxb * g.nby;
-    const int ncx = cells_of(nbxb), ncy = cells_of(g.nby), ncells = ncx * ncy;
+    const BinPlan& p = b.plan;
     BinGrid gc = g;
-    gc.nbx = ncx; gc.nby = ncy; gc.bx_lo = 0; gc.bx_hi = ncx;
-    const BinSlices sl = make_slices(ncx, ncy);
-    const bool eight = scatter_lds_bytes(sl.w, sl.h, 8) <= SCAT_LDS_TWO_PER_CU;
-    const size_t lds1 = scatter_lds_bytes(sl.w, sl.h, eight ? 8 : 4);
-    set_scatter_lds_attribute();
-    const FinalizeArgs fa = make_finalize_args(b, nbins, 1u);
+    gc.nbx = p.ncx; gc.nby = p.ncy; gc.bx_lo = 0; gc.bx_hi = p.ncx;
+    const FinalizeArgs fa = make_finalize_args(b);
     const CellArgs ca{b.cell_start, b.chunk_start, reinterpret_cast<uint4*>(b.chunk_info), CELL_SHIFT};
     const uint4* ci = reinterpret_cast<const uint4*>(b.chunk_info);
-    const CellGeom cg{ncx, ncells, nbxb, g.nby};
-    // level one (b.nblocks workgroups of 2048 ranks; the table's last column sums the rectangles' areas in bins)
-    hipLaunchKernelGGL(k_bin_count<CNT_WAVES>, dim3(b.nblocks), dim3(CNT_WAVES * WAVE), (size_t)(ncells + 1) * sizeof(uint32_t), s, b.depth_index, b.rect_idx,
-                       b.count, gc, ncy, 1u, b.table, b.rects, CELL_SHIFT, (int)b.rects_sorted, b.n_max);
-    launch_column_scan(b.table, b.cell_total, ncells + 1, b.nblocks, s, b.band ? b.count : nullptr, BIN_RANKS_PER_BLOCK);
+    const CellGeom cg{p.ncx, p.ncells, g.bx_hi - g.bx_lo, g.nby};
+    // level one (p.blocks workgroups of 2048 ranks; the table's last column sums the rectangles' areas in bins)
+    hipLaunchKernelGGL(k_bin_count<CNT_WAVES>, dim3(p.blocks), dim3(CNT_WAVES * WAVE), p.count_lds, s, b.depth_index, b.rect_idx,
+                       b.count, gc, (int)p.count_rows, 1u, b.table, b.rects, CELL_SHIFT, (int)b.rects_sorted, b.n_max);
+    launch_column_scan(b.table, b.cell_total, (int)p.table_cols, p.blocks, s, b.band ? b.count : nullptr, BIN_RANKS_PER_BLOCK);
     {
-        const dim3 grid(b.nblocks + 1), block(SCAT_THREADS);
+        const dim3 grid(p.blocks + p.extra_wg), block(SCAT_THREADS);
 #define GSR_LAUNCH_CELLS(K)                                                                                                          \
-    hipLaunchKernelGGL((K), grid, block, lds1, s, b.depth_index, (const uint32_t*)b.rects, b.count, gc, sl, (const uint32_t*)b.table, \
+    hipLaunchKernelGGL((K), grid, block, p.scatter_lds, s, b.depth_index, (const uint32_t*)b.rects, b.count, gc, p.slices, (const uint32_t*)b.table, \
                        (const uint32_t*)b.cell_total, (const uint32_t*)nullptr, b.cell_list, b.capacity, b.overflow, 1u, fa, ca)
-        if (eight) GSR_LAUNCH_CELLS(k_cell_scatter1<8>);
+        if (p.groups == 8) GSR_LAUNCH_CELLS(k_cell_scatter1<8>);
         else GSR_LAUNCH_CELLS(k_cell_scatter1<4>);
 #undef GSR_LAUNCH_CELLS
     }
     // level two
     const uint2* cl = reinterpret_cast<const uint2*>(b.cell_list);
-    hipLaunchKernelGGL(k_cell_count, dim3(b.cell_grid), dim3(SCAT_THREADS), 0, s, cl, ci, (const uint32_t*)b.chunk_start, cg,
+    hipLaunchKernelGGL(k_cell_count, dim3(p.cell_grid), dim3(SCAT_THREADS), 0, s, cl, ci, (const uint32_t*)b.chunk_start, cg,
                        b.capacity, b.cell_table2, reinterpret_cast<uint8_t*>(b.cell_wcnt));
-    hipLaunchKernelGGL(k_cell_scan, dim3(ncells), dim3(WAVE), 0, s, b.cell_table2, (const uint32_t*)b.chunk_start, cg, b.capacity, b.bin_total);
-    hipLaunchKernelGGL(k_bin_starts, dim3(1), dim3(FIN_THREADS), 0, s, (const uint32_t*)b.bin_total, nbins, b.bin_start_pre);
-    hipLaunchKernelGGL(k_cell_scatter2, dim3(b.cell_grid + 1), dim3(SCAT_THREADS), FIN_SCRATCH_WORDS * sizeof(uint32_t), s, cl, ci,
+    hipLaunchKernelGGL(k_cell_scan, dim3(p.ncells), dim3(WAVE), 0, s, b.cell_table2, (const uint32_t*)b.chunk_start, cg, b.capacity, b.bin_total);
+    hipLaunchKernelGGL(k_bin_starts, dim3(1), dim3(FIN_THREADS), 0, s, (const uint32_t*)b.bin_total, p.nbins, b.bin_start_pre);
+    hipLaunchKernelGGL(k_cell_scatter2, dim3(p.cell_grid + 1), dim3(SCAT_THREADS), FIN_SCRATCH_WORDS * sizeof(uint32_t), s, cl, ci,
                        (const uint32_t*)b.chunk_start, cg, (const uint32_t*)b.cell_table2, reinterpret_cast<const uint8_t*>(b.cell_wcnt),
                        (const uint32_t*)b.bin_start_pre, b.list, b.capacity, fa);
 }
 
-void launch_bin(const BinBuffers& b, const BinGrid& g, uint32_t n, hipStream_t s, uint32_t front_waves)
+// the one-level count pass at WAVES waves per workgroup and the scan of its table down the workgroups
+template <int WAVES>
+static void launch_count_and_scan(const BinBuffers& b, const BinGrid& g, hipStream_t s)
 {
-    const int nbxb = g.bx_hi - g.bx_lo, nbins = nbxb * g.nby;
-    if (nbins <= 0) return;
-    const BinSlices sl = make_slices(nbxb, g.nby);
-    // 8 groups of 4 steps where their table still lets two workgroups share a CU, else 4 groups of 8 steps
-    const bool eight = scatter_lds_bytes(sl.w, sl.h, 8) <= SCAT_LDS_TWO_PER_CU;
-    // (the finalize step, when it runs as this kernel's extra workgroup, uses FIN_SCRATCH_WORDS of the dynamic LDS)
-    // the large-grid form with 1024-rank rounds (one step per wave): 4 groups of 4 steps -- ~6 instead of ~11 LDS reads per
-    // list entry in the slot phase, the phase the kernel is bound by -- at twice the per-round fixed work (b.big == 2)
-    // (at 1080p the large-grid form loses to the two-workgroups-per-CU kernel: C3 binning 47.3 -> 54.1 us, measured)
-    const bool short_rounds = n && nbins > 4096 && b.big == 2 && !eight;
-    const size_t lds = std::max(scatter_lds_bytes(sl.w, sl.h, eight ? 8 : 4, short_rounds ? SCAT_WAVES : SCAT_STEPS), FIN_SCRATCH_WORDS * sizeof(uint32_t));
+    const BinPlan& p = b.plan;
+    hipLaunchKernelGGL(k_bin_count<WAVES>, dim3(p.blocks, p.count_slices), dim3(WAVES * WAVE), p.count_lds, s, b.depth_index, b.rect_idx, b.count, g,
+                       (int)p.count_rows, p.rounds, b.table, b.rects, 0, (int)b.rects_sorted, b.n_max);
+    launch_column_scan(b.table, b.bin_total, p.nbins, p.blocks, s, b.band ? b.count : nullptr, p.rounds * BIN_RANKS_PER_BLOCK);
+}
+
+void launch_bin(const BinBuffers& b, const BinGrid& g, hipStream_t s)
+{
+    const BinPlan& p = b.plan;
+    if (p.nbins <= 0) return;
     set_scatter_lds_attribute();
-    if (n && b.two_level) {
-        launch_bin_two_level(b, g, s);
-        return;
-    }
-    // the count pass keeps one counter per bin in LDS and is cut into row slices only beyond 12288 bins (above 4K)
-    const int cnt_slices = (nbins + CNT_MAX_BINS - 1) / CNT_MAX_BINS;
-    const int cnt_rows = (g.nby + cnt_slices - 1) / cnt_slices;
-    const bool fused = n && nbins <= 4096;   // see bin_scatter_body
-    // the narrow forms of the count and the scatter kernel: the 1080p chain of a throughput context (same grids, same table rows)
-    const bool narrow = front_waves == FRONT_WAVES_NARROW && fused && eight;
-    if (n) {
-        const dim3 cgrid(b.nblocks, (g.nby + cnt_rows - 1) / cnt_rows);
-        const size_t clds = (size_t)cnt_rows * nbxb * sizeof(uint32_t);
-        if (narrow)
-            hipLaunchKernelGGL(k_bin_count<(int)FRONT_WAVES_NARROW>, cgrid, dim3(FRONT_WAVES_NARROW * WAVE), clds, s, b.depth_index, b.rect_idx, b.count, g,
-                               cnt_rows, b.rounds, b.table, b.rects, 0, (int)b.rects_sorted, b.n_max);
-        else
-            hipLaunchKernelGGL(k_bin_count<CNT_WAVES>, cgrid, dim3(CNT_WAVES * WAVE), clds, s, b.depth_index, b.rect_idx, b.count, g,
-                               cnt_rows, b.rounds, b.table, b.rects, 0, (int)b.rects_sorted, b.n_max);
-        launch_column_scan(b.table, b.bin_total, nbins, b.nblocks, s, b.band ? b.count : nullptr, b.rounds * BIN_RANKS_PER_BLOCK);
-    }
-    const FinalizeArgs fa = make_finalize_args(b, nbins, n);
-    const bool big = n && !fused && b.big;   // the large-grid form: finalize as the first workgroup, rounds
-    if (!fused && !big) hipLaunchKernelGGL(k_bin_finalize, dim3(1), dim3(FIN_THREADS), FIN_SCRATCH_WORDS * sizeof(uint32_t), s, fa);
-    if (n) {
-        if (big) hipLaunchKernelGGL(k_bin_starts, dim3(1), dim3(FIN_THREADS), 0, s, (const uint32_t*)b.bin_total, nbins, b.bin_start_pre);
-        const dim3 grid(b.nblocks + ((fused || big) ? 1 : 0), sl.sx * sl.sy), block(narrow ? FRONT_WAVES_NARROW * WAVE : SCAT_THREADS);
-#define GSR_LAUNCH_SCATTER(K, STARTS)                                                                                               \
-    hipLaunchKernelGGL((K), grid, block, lds, s, b.depth_index, (const uint32_t*)b.rects, b.count, g, sl,                           \
+    const FinalizeArgs fa = make_finalize_args(b);
+#define GSR_LAUNCH_SCATTER(K, THREADS, STARTS)                                                                                      \
+    hipLaunchKernelGGL((K), dim3(p.blocks + p.extra_wg, p.slices.sx * p.slices.sy), dim3(THREADS), p.scatter_lds, s,               \
+                       b.depth_index, (const uint32_t*)b.rects, b.count, g, p.slices,                                               \
                        (const uint32_t*)b.table, (const uint32_t*)b.bin_total, (const uint32_t*)(STARTS), b.list, b.capacity,       \
-                       b.overflow, b.rounds, fa, CellArgs{nullptr, nullptr, nullptr, 0})
-        if (big && eight) GSR_LAUNCH_SCATTER((k_bin_scatter_big<8, 2>), b.bin_start_pre);
-        else if (big && short_rounds) GSR_LAUNCH_SCATTER((k_bin_scatter_big<4, 1>), b.bin_start_pre);
-        else if (big) GSR_LAUNCH_SCATTER((k_bin_scatter_big<4, 2>), b.bin_start_pre);
-        else if (narrow) GSR_LAUNCH_SCATTER((k_bin_scatter_narrow<8>), b.bin_start);
-        else if (eight && fused) GSR_LAUNCH_SCATTER((k_bin_scatter<8, true>), b.bin_start);
-        else if (eight) GSR_LAUNCH_SCATTER((k_bin_scatter<8, false>), b.bin_start);
-        else if (fused) GSR_LAUNCH_SCATTER((k_bin_scatter<4, true>), b.bin_start);
-        else GSR_LAUNCH_SCATTER((k_bin_scatter<4, false>), b.bin_start);
-#undef GSR_LAUNCH_SCATTER
+                       b.overflow, p.rounds, fa, CellArgs{nullptr, nullptr, nullptr, 0})
+    switch (p.form) {
+    case BIN_FINALIZE_ONLY:
+        hipLaunchKernelGGL(k_bin_finalize, dim3(1), dim3(FIN_THREADS), FIN_SCRATCH_WORDS * sizeof(uint32_t), s, fa);
+        break;
+    case BIN_FUSED_WIDE:
+        launch_count_and_scan<CNT_WAVES>(b, g, s);
+        if (p.groups == 8) GSR_LAUNCH_SCATTER((k_bin_scatter<8, true>), SCAT_THREADS, b.bin_start);
+        else GSR_LAUNCH_SCATTER((k_bin_scatter<4, true>), SCAT_THREADS, b.bin_start);
+        break;
+    case BIN_FUSED_NARROW:
+        launch_count_and_scan<(int)FRONT_WAVES_NARROW>(b, g, s);
+        GSR_LAUNCH_SCATTER((k_bin_scatter_narrow<8>), FRONT_WAVES_NARROW * WAVE, b.bin_start);
+        break;
+    case BIN_SEPARATE_FINALIZE:
+        launch_count_and_scan<CNT_WAVES>(b, g, s);
+        hipLaunchKernelGGL(k_bin_finalize, dim3(1), dim3(FIN_THREADS), FIN_SCRATCH_WORDS * sizeof(uint32_t), s, fa);
+        GSR_LAUNCH_SCATTER((k_bin_scatter<4, false>), SCAT_THREADS, b.bin_start);
+        break;
+    case BIN_LARGE_GRID:   // the finalize step is the scatter's first workgroup; the starts come from k_bin_starts
+        launch_count_and_scan<CNT_WAVES>(b, g, s);
+        hipLaunchKernelGGL(k_bin_starts, dim3(1), dim3(FIN_THREADS), 0, s, (const uint32_t*)b.bin_total, p.nbins, b.bin_start_pre);
+        if (p.steps_per_wave == 1) GSR_LAUNCH_SCATTER((k_bin_scatter_big<4, 1>), SCAT_THREADS, b.bin_start_pre);
+        else GSR_LAUNCH_SCATTER((k_bin_scatter_big<4, 2>), SCAT_THREADS, b.bin_start_pre);
+        break;
+    case BIN_TWO_LEVEL:
+        launch_bin_two_level(b, g, s);
+        break;
     }
+#undef GSR_LAUNCH_SCATTER
 }
 
 }  // namespace gsr

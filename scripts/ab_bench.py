@@ -111,8 +111,11 @@ def main():
             base = med
         print("%-26s %8.1f | %s" % (name, med["fps"], " ".join("%11.1f" % med[s] for s in stages)))
         if med is not base:
-            print("%-26s %7.1f%% | %s" % ("  vs base", (med["fps"] / base["fps"] - 1) * 100,
+            print("%-26s %7.1f%% | %s" % ("  vs " + args.variants[0], (med["fps"] / base["fps"] - 1) * 100,
                                            " ".join("%10.1f%%" % ((med[s] / base[s] - 1) * 100 if base[s] else 0) for s in stages)))
+            # (a round renders every variant back to back: the spread of the per-round ratios is the session's own noise)
+            ratios = np.array(res[name]["fps"]) / np.array(res[args.variants[0]]["fps"])
+            print("%-26s fps ratio to %s per round: median %.4f, %.4f .. %.4f" % ("", args.variants[0], float(np.median(ratios)), float(ratios.min()), float(ratios.max())))
     for rs in ctxs.values():
         for r in rs:
             r.dispose()

@@ -1,13 +1,13 @@
 """Every bin list against an exact reference, in every form the binning stage can take.
 
-The binning stage (k_bin.hip) is about a dozen kernel instantiations picked by launch_bin / launch_bin_two_level from
-the bin grid, the kind of context and knobs.  Its result has an exact integer specification (tests/bin_reference.py,
-checked on the CPU by tests/test_bin_reference.py), and every test here renders through the ordinary API and then
+The binning stage (k_bin.hip) is about a dozen kernel instantiations; plan_bins picks the form from the bin grid, the kind
+of context and knobs, and launch_bin launches it (tests/test_bin_plan.py asks the plan itself, on the CPU).  Its result
+has an exact integer specification (tests/bin_reference.py, checked on the CPU by tests/test_bin_reference.py), and every test here renders through the ordinary API and then
 demands that `starts` and `list` equal that reference ENTRY FOR ENTRY -- the reference fed with the ORACLE's boxes and
 depth order (oracle.project / oracle.sort), never with the device's own read-backs -- together with bin_totals(), the
 frame's bin_entries and visible counts, depthIndex, and no overflow left pending.
 
-Forms (one test id at least names each; which kernel a geometry reaches follows scatter_lds_bytes / make_slices: 8 groups
+Forms (one test id at least names each; which kernel a geometry reaches is plan_bins' answer: 8 groups
 of steps fit two workgroups per CU up to 2408 bins; profiles/bin_lists_kernels.txt is the kernel table of one run of this
 file, the proof that they ran):
 
@@ -23,10 +23,10 @@ file, the proof that they ran):
     band contexts                                     inside one level 1080p, one level 4 groups, two level 4K; a band of
                                                       one bin column; bands that do not start or end on a cell
 
-k_bin_scatter<8, false> and k_bin_scatter_big<8, 2> are reached by NO geometry: both need more than 4096 bins whose
-sub-grid still fits 8 groups in 72 KiB, and make_slices returns the FEWEST sub-grids that fit 4 groups in 150 KiB, which
-for every grid of 1 .. 256 x 1 .. 256 bins (every framebuffer and band the ABI accepts) above 4096 bins leaves a sub-grid
-too large for 8 (enumerated; the largest grid that takes 8 groups has 2408 bins).  They stay in the source untested.
+There is no k_bin_scatter<8, false> and no k_bin_scatter_big<8, 2>: both would need more than 4096 bins whose sub-grid still
+fits 8 groups in 72 KiB, and make_slices returns the FEWEST sub-grids that fit 4 groups in 150 KiB, which for every grid of
+1 .. 256 x 1 .. 256 bins (every framebuffer and band the ABI accepts) above 4096 bins leaves a sub-grid too large for 8
+(tests/test_bin_plan.py asserts it of the plan for every such grid; the largest grid that takes 8 groups has 2408 bins).
 
 Where the rectangles come from changes the code that runs in k_bin_count and in the sort: a context's first frame of a
 scene sorts in the LSD order with the rectangles carried through the radix passes (rects_sorted), later frames in the
@@ -232,14 +232,17 @@ def test_form_builds_the_reference_lists(gh, scenes, frames, monkeypatch, scene,
 BOUNDS_SITES = ["splat index of a rank", "rectangle inside the bin grid", "LDS cell of the scatter", "table row", "count cell"]
 
 
-@pytest.mark.parametrize("scene,size,env,throughput,band", [
+BOUNDS_FORMS = [
     _case("k_bin_scatter<4,true> 2560x1440", "mid", (2560, 1440)),
     _case("k_bin_scatter<4,true> 2560x1600 throughput", "mid", (2560, 1600), throughput=True),
     _case("sliced 1x3 k_bin_scatter<4,false> 6144x3216", "big", (6144, 3216), dict(ONE_LEVEL, GSR_BIN_BIG="0")),
     _case("sliced 2x2 k_bin_scatter_big<4,1> 7680x4320", "big", (7680, 4320), dict(ONE_LEVEL, GSR_BIN_ROUNDS="2")),
     _case("sliced 2x2 k_bin_scatter_big<4,2> 7680x4320", "big", (7680, 4320), dict(ONE_LEVEL, GSR_BIN_BIG="1")),
     _case("two level k_cell_scatter1<4> 8192x8192", "big", (8192, 8192)),
-])
+]
+
+
+@pytest.mark.parametrize("scene,size,env,throughput,band", BOUNDS_FORMS)
 def test_bounds_checked_build_of_the_rarely_run_forms(gh, scenes, frames, monkeypatch, scene, size, env, throughput, band):
     """The forms no other test runs, on the bounds-checked build of the library (tests/test_gpu_bounds.py): the same lists,
     and no index derived from device data outside what it indexes.  (First in the file's order of cases by name: pytest
