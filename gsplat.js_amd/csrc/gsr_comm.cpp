@@ -91,7 +91,20 @@ void gsr::comm_release(gsr_ctx* c)
     c->comm.stream = nullptr;
     c->comm.owned = true;
     c->comm.slab.reset(); c->comm.gathered.reset(); c->comm.frame8.reset();
+    c->comm.depth.reset();   // (the option belongs to the group's contract: it goes with the group)
     c->comm.world = 0; c->comm.frame8_valid = false;
+}
+
+// the slab and the gathered slabs at the size the group's contract gives them now (colour, flag words and, after
+// gsr_comm_set_depth, the depth section); the caller has waited for both streams
+static int alloc_slabs(gsr_ctx* c, int world)
+{
+    const size_t words = c->comm.slab_bytes(c->H) / 4;
+    int r;
+    if ((r = c->comm.slab.alloc(c, words)) || (r = c->comm.gathered.alloc(c, words * world))) return r;
+    HIP_TRY(c, hipMemsetAsync(c->comm.slab, 0, words * 4, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return GSR_OK;
 }
 
 extern "C" {
@@ -132,13 +145,8 @@ static int comm_setup(gsr_ctx* c, const char* who, int32_t rank, int32_t world, 
     for (int q = 0; q < world; q++) { c->comm.edges.x0[q] = x0[q]; c->comm.edges.x1[q] = x1[q]; }
     // (a slab = the band's pixels + SLAB_FLAG_WORDS words "this band was not composited"; the assembled frame is followed by
     //  the word that collects those flags: k_pack_band_rgba8 / k_unpack_slabs_rgba8)
-    const size_t slab_px = (size_t)sw * c->H + SLAB_FLAG_WORDS;
     int r;
-    if ((r = c->comm.slab.alloc(c, slab_px)) || (r = c->comm.gathered.alloc(c, slab_px * world)) ||
-        (r = c->comm.frame8.alloc(c, (size_t)c->W * c->H + SLAB_FLAG_WORDS)))
-        return r;
-    HIP_TRY(c, hipMemsetAsync(c->comm.slab, 0, slab_px * 4, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if ((r = alloc_slabs(c, world)) || (r = c->comm.frame8.alloc(c, (size_t)c->W * c->H + SLAB_FLAG_WORDS))) return r;
     if (shared_stream) { c->comm.stream = shared_stream; c->comm.owned = false; }
     else HIP_TRY(c, hipStreamCreateWithFlags(&c->comm.stream, hipStreamNonBlocking));
     HIP_TRY(c, hipEventCreateWithFlags(&c->comm.ev_packed, hipEventDisableTiming));
@@ -201,10 +209,20 @@ int gsr_allgather_frame_async(gsr_ctx* c)
     if (!c) return GSR_ERR_ARG;
     if (!c->comm.joined()) return fail(c, GSR_ERR_ARG, "gsr_allgather_frame_async: gsr_comm_init has not been called");
     if (!c->have_frame) return fail(c, GSR_ERR_ARG, "gsr_allgather_frame_async: nothing rendered yet");
+    gsr_ctx::Comm::DepthExchange& dx = c->comm.depth;
+    // with depth the frame's lists are walked once more: what gsr_depth_async needs of the frame, refused before anything is enqueued
+    if (dx.on()) {
+        if (dx.W != c->W || dx.H != c->H)
+            return fail(c, GSR_ERR_ARG, "gsr_allgather_frame_async: the size changed since gsr_comm_set_depth (%dx%d, now %dx%d): join the group again", dx.W, dx.H, c->W, c->H);
+        if (int r = delivery_depth_check(c, "gsr_allgather_frame_async (depth exchange)")) return r;
+    }
     HIP_TRY(c, hipSetDevice(c->device));
     // never ship a band the compositor did not draw: if the device has reported a list overflow, regrow and render
     // the frame again first (lost earlier frames stay counted and are reported by the next gsr_sync)
-    if (overflow_pending(c)) { if (int r = sync_and_repair(c)) return r; }
+    if (overflow_pending(c)) {
+        if (int r = sync_and_repair(c)) return r;
+        if (dx.on()) { if (int r = delivery_depth_check(c, "gsr_allgather_frame_async (depth exchange)")) return r; }   // (a regrowth may have taken the lists)
+    }
     const BinGrid g = make_grid(c);
     const int x0 = g.bx_lo * BIN_PX, x1 = std::min(g.bx_hi * BIN_PX, c->W);
     // render stream: the previous all-gather must have read the slab before it is overwritten; then pack the band
@@ -212,10 +230,17 @@ int gsr_allgather_frame_async(gsr_ctx* c)
     // (the pack also records, behind the pixels, whether the frame it packs was composited at all: the frame's overflow word,
     //  which the next frame's projection resets -- stream order puts this read in front of it)
     launch_pack_band_rgba8(c->out.fb, c->comm.slab, c->W, c->H, x0, x1, c->comm.slab_w, c->stream, &c->words.fstate->overflow);
+    if (dx.on()) {
+        // the frame's hit plane on this rank's bin columns (the pass of a depth ring, the same hit_alpha rule), then the band's samples
+        // into the slab's depth section.  A frame whose lists did not fit leaves the plane as it was: the slab's flag says so.
+        comm_depth_enqueue(c);
+        launch_pack_band_depth(dx.format, dx.hit, reinterpret_cast<uint8_t*>(c->comm.slab.p) + dx.offset, dx.Wd, dx.Hd, dx.edges.x0[c->comm.rank],
+                               dx.edges.x1[c->comm.rank], dx.stride, dx.near, c->stream);
+    }
     HIP_TRY(c, hipEventRecord(c->comm.ev_packed, c->stream));
     // exchange stream: collective + de-slab, overlapping the next frame's kernels on the render stream
     HIP_TRY(c, hipStreamWaitEvent(c->comm.stream, c->comm.ev_packed, 0));
-    const size_t slab_bytes = ((size_t)c->comm.slab_w * c->H + SLAB_FLAG_WORDS) * 4;
+    const size_t slab_bytes = c->comm.slab_bytes(c->H);
     if (c->comm.fn) {
         if (const int r = c->comm.fn(c->comm.fn_user, c->comm.slab, c->comm.gathered, (uint64_t)slab_bytes, (void*)c->comm.stream))
             return fail(c, GSR_ERR_COMM, "the custom all-gather returned %d", r);
@@ -224,16 +249,19 @@ int gsr_allgather_frame_async(gsr_ctx* c)
     }
     HIP_TRY(c, hipEventRecord(c->comm.ev_slab_free, c->comm.stream));
     launch_unpack_slabs_rgba8(c->comm.gathered, c->comm.frame8, c->W, c->H, c->comm.slab_w, c->comm.world, c->comm.edges, c->comm.stream,
-                              c->comm.frame8 + (size_t)c->W * c->H);
+                              c->comm.frame8 + (size_t)c->W * c->H, dx.on() ? slab_bytes / 4 : 0);
+    if (dx.on())
+        launch_unpack_slabs_depth(dx.format, reinterpret_cast<const uint8_t*>(c->comm.gathered.p), dx.plane, dx.Wd, dx.Hd, slab_bytes, dx.offset, dx.stride,
+                                  c->comm.world, dx.edges, c->comm.stream);
     HIP_TRY(c, hipGetLastError());
     c->comm.frame8_valid = true;
     return GSR_OK;
 }
 
-int gsr_read_frame_rgba8(gsr_ctx* c, uint8_t* out)
+// gsr_read_frame_rgba8 / gsr_read_frame_depth: `bytes` at `src` of what the last gsr_allgather_frame_async left, unless that
+// gathered frame holds a stale band
+static int read_gathered(gsr_ctx* c, void* out, const void* src, size_t bytes)
 {
-    if (!c || !out) return c ? fail(c, GSR_ERR_ARG, "out is NULL") : GSR_ERR_ARG;
-    if (!c->comm.frame8_valid) return fail(c, GSR_ERR_ARG, "gsr_read_frame_rgba8: no gathered frame yet (gsr_allgather_frame_async)");
     HIP_TRY(c, hipSetDevice(c->device));
     // A band of the gathered frame may have been packed right behind a frame whose bin lists did not fit: that frame was not
     // composited and the band is the preceding image.  WHICH gathered frame that concerns is decided on the device and seen by
@@ -245,7 +273,7 @@ int gsr_read_frame_rgba8(gsr_ctx* c, uint8_t* out)
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (overflow_pending(c)) { if (int r = sync_and_repair(c)) return r; }
     uint32_t stale = 0;
-    HIP_TRY(c, hipMemcpyAsync(out, c->comm.frame8, (size_t)c->W * c->H * 4, hipMemcpyDeviceToHost, c->comm.stream));
+    HIP_TRY(c, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, c->comm.stream));
     HIP_TRY(c, hipMemcpyAsync(&stale, c->comm.frame8 + (size_t)c->W * c->H, 4, hipMemcpyDeviceToHost, c->comm.stream));
     HIP_TRY(c, hipStreamSynchronize(c->comm.stream));
     if (stale) {
@@ -257,6 +285,79 @@ int gsr_read_frame_rgba8(gsr_ctx* c, uint8_t* out)
     return GSR_OK;
 }
 
+int gsr_read_frame_rgba8(gsr_ctx* c, uint8_t* out)
+{
+    if (!c || !out) return c ? fail(c, GSR_ERR_ARG, "out is NULL") : GSR_ERR_ARG;
+    if (!c->comm.frame8_valid) return fail(c, GSR_ERR_ARG, "gsr_read_frame_rgba8: no gathered frame yet (gsr_allgather_frame_async)");
+    return read_gathered(c, out, c->comm.frame8, (size_t)c->W * c->H * 4);
+}
+
+int gsr_comm_set_depth(gsr_ctx* c, const gsr_depth_delivery_options* depth)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (!c->comm.joined()) return fail(c, GSR_ERR_ARG, "gsr_comm_set_depth: this context is not in a group (gsr_comm_init, gsr_comm_share)");
+    if (depth && depth->format == GSR_DEPTH_NONE) depth = nullptr;
+    if (depth) { if (int r = depth_options_check(c, "gsr_comm_set_depth", depth)) return r; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->comm.stream));
+    gsr_ctx::Comm::DepthExchange& dx = c->comm.depth;
+    dx.reset();
+    c->comm.frame8_valid = false;   // the slabs change: what was gathered under the old contract is gone
+    if (depth) {
+        const int st = depth->step, world = c->comm.world;
+        dx.format = depth->format; dx.step = st;
+        dx.near = depth->format == GSR_DEPTH_U16 ? depth->near : 0.0f;
+        dx.W = c->W; dx.H = c->H;
+        dx.Wd = (c->W + st - 1) / st; dx.Hd = (c->H + st - 1) / st;
+        // band edges are multiples of 32 (the last may be the image's width): x0 / step is exact, the bands are disjoint and cover Wd
+        for (int q = 0; q < world; q++) { dx.edges.x0[q] = c->comm.edges.x0[q] / st; dx.edges.x1[q] = (c->comm.edges.x1[q] + st - 1) / st; }
+        dx.stride = ((c->comm.slab_w + st - 1) / st + 7) & ~7;
+        dx.offset = ((((size_t)c->comm.slab_w * c->H + SLAB_FLAG_WORDS) * 4) + 15) & ~(size_t)15;
+        dx.slab_bytes = dx.offset + (size_t)dx.Hd * dx.stride * dx.sample_bytes();
+        const size_t np = (size_t)dx.Wd * dx.Hd;
+        const size_t plane_words = (dx.plane_bytes() + 15) / 16 * 4;
+        int r = dx.hit.alloc(c, np);
+        if (!r && st == 1) { r = dx.mean.alloc(c, np); if (!r) r = dx.index.alloc(c, np); }
+        if (!r) r = dx.invalid.alloc(c, 1);
+        if (!r) r = dx.plane.alloc(c, plane_words);
+        if (!r) r = alloc_slabs(c, world);
+        if (r) { dx.reset(); (void)alloc_slabs(c, world); return r; }   // (colour only again)
+        // (a frame that never fits leaves the plane unwritten: +infinity rather than whatever the allocation held)
+        HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)dx.hit.p, 0x7f800000, np, c->stream));
+        HIP_TRY(c, hipMemsetAsync(dx.plane, 0, plane_words * 4, c->stream));
+        return GSR_OK;
+    }
+    return alloc_slabs(c, c->comm.world);
+}
+
+int gsr_frame_depth_layout(gsr_ctx* c, gsr_depth_layout* out)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (!out) return fail(c, GSR_ERR_ARG, "gsr_frame_depth_layout: out is NULL");
+    const gsr_ctx::Comm::DepthExchange& dx = c->comm.depth;
+    if (!c->comm.joined() || !dx.on()) return fail(c, GSR_ERR_ARG, "gsr_frame_depth_layout: this context exchanges no depth (gsr_comm_set_depth)");
+    *out = gsr_depth_layout{};
+    out->format = dx.format; out->step = dx.step; out->width = dx.Wd; out->height = dx.Hd;
+    out->stride = (int32_t)(dx.Wd * dx.sample_bytes());
+    out->offset = 0;
+    out->bytes = dx.plane_bytes();
+    out->near = dx.near;
+    return GSR_OK;
+}
+
+int gsr_read_frame_depth(gsr_ctx* c, void* out, uint64_t out_bytes)
+{
+    if (!c || !out) return c ? fail(c, GSR_ERR_ARG, "out is NULL") : GSR_ERR_ARG;
+    const gsr_ctx::Comm::DepthExchange& dx = c->comm.depth;
+    if (!c->comm.joined() || !dx.on()) return fail(c, GSR_ERR_ARG, "gsr_read_frame_depth: this context exchanges no depth (gsr_comm_set_depth)");
+    if (!c->comm.frame8_valid) return fail(c, GSR_ERR_ARG, "gsr_read_frame_depth: no gathered frame yet (gsr_allgather_frame_async)");
+    if (out_bytes < dx.plane_bytes())
+        return fail(c, GSR_ERR_ARG, "gsr_read_frame_depth: %llu bytes, the plane has %zu", (unsigned long long)out_bytes, dx.plane_bytes());
+    return read_gathered(c, out, dx.plane, dx.plane_bytes());
+}
+
+void* gsr_frame_depth_device_ptr(gsr_ctx* c) { return c && c->comm.depth.on() ? (void*)c->comm.depth.plane : nullptr; }
 void* gsr_frame8_device_ptr(gsr_ctx* c) { return c ? (void*)c->comm.frame8 : nullptr; }
 void* gsr_comm_stream_handle(gsr_ctx* c) { return c ? (void*)c->comm.stream : nullptr; }
 

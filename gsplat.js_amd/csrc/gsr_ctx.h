@@ -260,6 +260,31 @@ struct gsr_ctx {
         gsr::SlabEdges edges{};
         bool frame8_valid = false;
         bool joined() const { return nccl || fn; }
+        // depth beside the colour (gsr_comm_set_depth): the band's hit samples travel in a depth section behind the slab's pixels and
+        // flag words, and one de-slab step leaves the gathered plane on every rank.  Nothing below is allocated, and the slab is
+        // the colour slab byte for byte, until a context opts in; the pass has planes of its own, like a depth ring's.
+        struct DepthExchange {
+            int format = GSR_DEPTH_NONE;    // GSR_DEPTH_*; NONE: colour only
+            int step = 1;
+            float near = 0.0f;              // GSR_DEPTH_U16
+            int W = 0, H = 0;               // the size the buffers and the layout were made for
+            int Wd = 0, Hd = 0;             // ceil(W / step), ceil(H / step)
+            int stride = 0;                 // samples per row of a slab's depth section: the widest band's, rounded up to 8
+            size_t offset = 0;              // of the section in a slab: behind pixels and flag words, at the next multiple of 16
+            size_t slab_bytes = 0;          // offset + Hd * stride * sample size: what one rank hands to the collective
+            gsr::SlabEdges edges{};         // the bands in samples: [x0 / step, ceil(x1 / step))
+            gsr::DevBuf<float> hit;         // Wd x Hd: what the pass writes (this rank's columns) and the band pack reads
+            gsr::DevBuf<float> mean;        // step 1 only: the full pass writes three planes; these two are scratch
+            gsr::DevBuf<uint32_t> index;
+            gsr::DevBuf<uint32_t> invalid;  // the pass's "refused an unfit frame" word (never read by the host: the slab's flag decides)
+            gsr::DevBuf<uint32_t> plane;    // the gathered plane [Hd][Wd], f32 or u16, in whole 16 bytes (the rest zero)
+            bool on() const { return format != GSR_DEPTH_NONE; }
+            size_t sample_bytes() const { return format == GSR_DEPTH_U16 ? 2 : 4; }
+            size_t plane_bytes() const { return (size_t)Wd * Hd * sample_bytes(); }
+            void reset() { format = GSR_DEPTH_NONE; hit.reset(); mean.reset(); index.reset(); invalid.reset(); plane.reset(); W = H = Wd = Hd = stride = 0; offset = slab_bytes = 0; }
+        } depth;
+        // what one rank hands to the collective
+        size_t slab_bytes(int H) const { return depth.on() ? depth.slab_bytes : ((size_t)slab_w * H + gsr::SLAB_FLAG_WORDS) * 4; }
     } comm;
 
     // depth planes and picking (gsr_depth.cpp); nothing is allocated until the first call that needs it
@@ -346,8 +371,12 @@ void comm_release(gsr_ctx* c);
 // enqueued); enqueue: the planes pass into the ring's own plane(s) on the render stream (launch errors are left for hipGetLastError)
 int delivery_depth_check(gsr_ctx* c, const char* who);
 int delivery_depth_enqueue(gsr_ctx* c);
+// the same pass for a group's depth exchange (gsr_comm_set_depth), into the exchange's own plane(s)
+void comm_depth_enqueue(gsr_ctx* c);
 // gsr_delivery.cpp
 int delivery_alloc(gsr_ctx* c, int slots);
+// what gsr_delivery_open_depth demands of depth options other than GSR_DEPTH_NONE (GSR_ERR_ARG, `who` in front of the message)
+int depth_options_check(gsr_ctx* c, const char* who, const gsr_depth_delivery_options* depth);
 void delivery_free(gsr_ctx* c);
 bool delivery_frame_held(const gsr_ctx* c);
 

@@ -114,6 +114,30 @@ static DeliverySlot* find_slot(gsr_ctx* c, uint64_t serial, DeliverySlot::State 
     return found;
 }
 
+int gsr::depth_options_check(gsr_ctx* c, const char* who, const gsr_depth_delivery_options* depth)
+{
+    if (depth->format != GSR_DEPTH_F32 && depth->format != GSR_DEPTH_U16)
+        return fail(c, GSR_ERR_ARG, "%s: unknown depth format %d (GSR_DEPTH_NONE, GSR_DEPTH_F32, GSR_DEPTH_U16)", who, depth->format);
+    if (depth->step != 1 && depth->step != 2) return fail(c, GSR_ERR_ARG, "%s: depth step %d (1 or 2)", who, depth->step);
+    if (depth->format == GSR_DEPTH_U16 && !(depth->near > 0.0f && std::isfinite(depth->near)))
+        return fail(c, GSR_ERR_ARG, "%s: GSR_DEPTH_U16 needs a finite near > 0, not %g", who, (double)depth->near);
+    if (depth->reserved) return fail(c, GSR_ERR_ARG, "%s: gsr_depth_delivery_options.reserved must be 0", who);
+    return GSR_OK;
+}
+
+// a depth ring on a context whose group exchanges depth: format, step and near must be the exchange's (GSR_ERR_ARG names the first that is not)
+static int exchange_mismatch(gsr_ctx* c, const char* who, int format, int step, float near)
+{
+    const gsr_ctx::Comm::DepthExchange& dx = c->comm.depth;
+    if (format != dx.format)
+        return fail(c, GSR_ERR_ARG, "%s: the ring's depth format (%d) is not the one the group exchanges (%d, gsr_comm_set_depth)", who, format, dx.format);
+    if (step != dx.step) return fail(c, GSR_ERR_ARG, "%s: the ring's depth step (%d) is not the one the group exchanges (%d, gsr_comm_set_depth)", who, step, dx.step);
+    if (c->W != dx.W || c->H != dx.H) return fail(c, GSR_ERR_ARG, "%s: the size changed since gsr_comm_set_depth: join the group again", who);
+    if (near != dx.near)
+        return fail(c, GSR_ERR_ARG, "%s: the ring's depth near (%g) is not the one the group exchanges (%g, gsr_comm_set_depth)", who, (double)near, (double)dx.near);
+    return GSR_OK;
+}
+
 extern "C" {
 
 static int delivery_open_checked(gsr_ctx* c, const char* who, int32_t slots)
@@ -141,14 +165,11 @@ static int delivery_open_options(gsr_ctx* c, const char* who, const gsr_delivery
     if (opt->format != GSR_FORMAT_RGBA8 && opt->format != GSR_FORMAT_NV12 && opt->format != GSR_FORMAT_I420)
         return fail(c, GSR_ERR_ARG, "%s: unknown format %d (GSR_FORMAT_RGBA8, GSR_FORMAT_NV12, GSR_FORMAT_I420)", who, opt->format);
     if (depth) {
-        if (depth->format != GSR_DEPTH_F32 && depth->format != GSR_DEPTH_U16)
-            return fail(c, GSR_ERR_ARG, "%s: unknown depth format %d (GSR_DEPTH_NONE, GSR_DEPTH_F32, GSR_DEPTH_U16)", who, depth->format);
-        if (depth->step != 1 && depth->step != 2) return fail(c, GSR_ERR_ARG, "%s: depth step %d (1 or 2)", who, depth->step);
-        if (depth->format == GSR_DEPTH_U16 && !(depth->near > 0.0f && std::isfinite(depth->near)))
-            return fail(c, GSR_ERR_ARG, "%s: GSR_DEPTH_U16 needs a finite near > 0, not %g", who, (double)depth->near);
-        if (depth->reserved) return fail(c, GSR_ERR_ARG, "%s: gsr_depth_delivery_options.reserved must be 0", who);
-        if (c->comm.joined())
+        if (int r = depth_options_check(c, who, depth)) return r;
+        if (c->comm.joined() && !c->comm.depth.on())
             return fail(c, GSR_ERR_ARG, "%s: this context is in a group: depth is not exchanged between ranks, so a gathered frame has no depth plane to deliver", who);
+        // a group that exchanges depth (gsr_comm_set_depth) delivers the gathered plane as it is: the ring's options must be the exchange's
+        if (c->comm.joined()) { if (int r = exchange_mismatch(c, who, depth->format, depth->step, depth->format == GSR_DEPTH_U16 ? depth->near : 0.0f)) return r; }
     }
     if (!c->delivery.ring.empty()) return fail(c, GSR_ERR_ARG, "%s: a delivery ring is open (gsr_delivery_close first)", who);
     if (int r = delivery_open_checked(c, who, opt->slots)) return r;
@@ -232,13 +253,20 @@ int gsr_deliver_frame_async(gsr_ctx* c, uint64_t* serial)
     if (c->delivery.ring.empty()) return fail(c, GSR_ERR_ARG, "gsr_deliver_frame_async: no delivery ring (gsr_delivery_open)");
     const bool group = c->comm.joined();
     const bool depth = ring_has_depth(c);
-    if (depth && group)   // (refused before anything else is looked at: nothing enqueued, no slot taken)
+    if (depth && group && !c->comm.depth.on())   // (refused before anything else is looked at: nothing enqueued, no slot taken)
         return fail(c, GSR_ERR_ARG, "gsr_deliver_frame_async: this context joined a group after it opened a depth ring: depth is not exchanged "
                                     "between ranks, so a gathered frame has no depth plane to deliver (gsr_delivery_close, then a ring without depth)");
+    if (depth && group) {   // the group exchanges depth: the gathered plane is delivered as it is, so the ring must have been opened for it
+        const gsr_ctx::Delivery::DepthPlane& dp = c->delivery.depth;
+        if (int r = exchange_mismatch(c, "gsr_deliver_frame_async", dp.format, dp.step, dp.near)) return r;
+        if (dp.Wd != c->comm.depth.Wd || dp.Hd != c->comm.depth.Hd)
+            return fail(c, GSR_ERR_ARG, "gsr_deliver_frame_async: the size changed since gsr_comm_set_depth: join the group again");
+    }
     if (group ? !c->comm.frame8_valid : !c->have_frame)
         return fail(c, GSR_ERR_ARG, group ? "gsr_deliver_frame_async: no gathered frame yet (gsr_allgather_frame_async)" : "gsr_deliver_frame_async: nothing rendered yet");
     // a depth ring needs what gsr_depth_async needs of the frame; refused before a slot is looked for: nothing enqueued, no slot taken
-    if (depth) { if (int r = delivery_depth_check(c, "gsr_deliver_frame_async (depth ring)")) return r; }
+    // (in a group the pass ran with the exchange: gsr_allgather_frame_async has asked the same of the frame it gathered)
+    if (depth && !group) { if (int r = delivery_depth_check(c, "gsr_deliver_frame_async (depth ring)")) return r; }
     DeliverySlot* sl = nullptr;
     const int slots = (int)c->delivery.ring.size();
     for (int k = 0; k < slots && !sl; k++) {
@@ -251,7 +279,24 @@ int gsr_deliver_frame_async(gsr_ctx* c, uint64_t* serial)
     const size_t bytes = ring_slot_bytes(c);
     const bool yuv = c->delivery.format != GSR_FORMAT_RGBA8;
     hipError_t e;
-    if (group && yuv) {
+    if (group && depth) {
+        // exchange stream, behind the de-slab steps and in front of the next ones: the gathered colour into the slot's staging (a plain
+        // copy, or the conversion), the gathered plane as it is behind it with THE trailer (the stale mask its first word), then the
+        // slot's one copy to the host.  No depth pass: gsr_allgather_frame_async ran it for the frame it gathered.
+        const gsr_ctx::Comm::DepthExchange& dx = c->comm.depth;
+        const uint32_t* stale = c->comm.frame8 + (size_t)c->W * c->H;
+        e = hipSuccess;
+        if (yuv)
+            launch_deliver_yuv(c->delivery.format, nullptr, c->comm.frame8, reinterpret_cast<uint8_t*>(sl->staging.p), bytes, c->W, c->H, c->delivery.yuv, k, stale,
+                               c->comm.stream);
+        else
+            e = hipMemcpyAsync(sl->staging, c->comm.frame8, (size_t)c->W * c->H * 4, hipMemcpyDeviceToDevice, c->comm.stream);
+        launch_deliver_gathered_depth(dx.plane, (uint32_t)((dx.plane_bytes() + 3) / 4), reinterpret_cast<uint8_t*>(sl->staging.p), ring_depth_offset(c),
+                                      ring_trailer_offset(c), c->W, c->H, k, stale, c->comm.stream);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(sl->host, sl->staging, bytes, hipMemcpyDeviceToHost, c->comm.stream);
+        if (e == hipSuccess) e = hipEventRecord(sl->done, c->comm.stream);
+    } else if (group && yuv) {
         // exchange stream, where the plain copy of an RGBA8 ring sits: the conversion reads the gathered frame behind its de-slab
         // kernel and in front of the next one (its stale mask becomes the trailer's first word), the copy follows it there
         launch_deliver_yuv(c->delivery.format, nullptr, c->comm.frame8, reinterpret_cast<uint8_t*>(sl->staging.p), bytes, c->W, c->H, c->delivery.yuv, k,

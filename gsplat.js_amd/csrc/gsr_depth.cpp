@@ -112,6 +112,14 @@ int gsr::delivery_depth_enqueue(gsr_ctx* c)
     return GSR_OK;
 }
 
+// The pass of a group's depth exchange (gsr_comm_set_depth): the same launch behind the frame on the render stream, into the
+// exchange's plane(s).  Only this rank's bin columns are written and only they are packed, so nothing is filled beside them.
+void gsr::comm_depth_enqueue(gsr_ctx* c)
+{
+    gsr_ctx::Comm::DepthExchange& d = c->comm.depth;
+    launch_depth_planes(buffers(c, d.invalid, d.mean, d.hit, d.index), make_grid(c), c->cam_frame, c->knobs.depth_skip, d.step, c->stream);
+}
+
 extern "C" {
 
 int gsr_set_hit_alpha(gsr_ctx* c, float a)

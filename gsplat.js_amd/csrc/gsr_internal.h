@@ -379,6 +379,18 @@ struct SlabEdges { int32_t x0[MAX_SLABS], x1[MAX_SLABS]; };
 constexpr int SLAB_FLAG_WORDS = 4;   // one flag, padded to 16 bytes
 void launch_pack_band_rgba8(const float4* fb, uint32_t* slab, int W, int H, int x0, int x1, int slab_w, hipStream_t s, const uint32_t* overflow = nullptr);
 void launch_unpack_slabs_rgba8(const uint32_t* gathered, uint32_t* image, int W, int H, int slab_w, int world,
-                               const SlabEdges& e, hipStream_t s, uint32_t* stale = nullptr);
+                               const SlabEdges& e, hipStream_t s, uint32_t* stale = nullptr, size_t slab_stride = 0);
+// Depth beside the colour (gsr_comm_set_depth; k_deliver.hip, beside the one statement of the 16-bit quantiser).  A slab's depth
+// section: Hd rows of `stride` samples (a multiple of 8: every row starts on 16 bytes), f32 or u16, the band's samples
+// [xd0, xd1) of the Wd x Hd hit plane at the front of every row and zeros behind them.
+void launch_pack_band_depth(int format, const float* plane, uint8_t* section, int Wd, int Hd, int xd0, int xd1, int stride, float near, hipStream_t s);
+// [world] slabs of slab_bytes, their depth sections at `offset` -> the gathered plane [Hd][Wd] in whole 16 bytes (the rest zero);
+// `e`: the bands in samples
+void launch_unpack_slabs_depth(int format, const uint8_t* gathered, uint32_t* plane, int Wd, int Hd, size_t slab_bytes, size_t offset, int stride,
+                               int world, const SlabEdges& e, hipStream_t s);
+// a gathered plane of `words` words as it is into a delivery slot's staging at `depth_offset`, and the slot's trailer ([0] the
+// gathered frame's stale mask) at `trailer_offset`: launch_deliver_depth's kernel on words that are final already
+void launch_deliver_gathered_depth(const uint32_t* plane, uint32_t words, uint8_t* staging, size_t depth_offset, size_t trailer_offset, int32_t W, int32_t H,
+                                   uint64_t serial, const uint32_t* stale, hipStream_t s);
 
 }  // namespace gsr

@@ -767,10 +767,12 @@ void launch_pack_band_rgba8(const float4* fb, uint32_t* slab, int W, int H, int 
 // Receiver side: the gathered slabs [world][H][slab_w] -> one row-major [H][W] image.
 // `stale` (may be null; then the slabs carry no flag words): out, one bit per rank whose band was not composited (see
 // k_pack_band_rgba8) -- the same word on every rank of the group.
+// `slab_stride` (words; 0: pixels and flag words and nothing else): from one rank's slab to the next, where the slabs carry a
+// depth section behind the flag words (gsr_comm_set_depth).
 __global__ void k_unpack_slabs_rgba8(const uint32_t* __restrict__ gathered, uint32_t* __restrict__ image, int W, int H,
-                                     int slab_w, int world, SlabEdges e, uint32_t* __restrict__ stale)
+                                     int slab_w, int world, SlabEdges e, uint32_t* __restrict__ stale, size_t slab_stride)
 {
-    const size_t slab_words = (size_t)H * slab_w + (stale ? SLAB_FLAG_WORDS : 0);
+    const size_t slab_words = slab_stride ? slab_stride : (size_t)H * slab_w + (stale ? SLAB_FLAG_WORDS : 0);
     if (stale && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
         uint32_t bits = 0;
         for (int q = 0; q < world; q++)
@@ -786,10 +788,10 @@ __global__ void k_unpack_slabs_rgba8(const uint32_t* __restrict__ gathered, uint
 }
 
 void launch_unpack_slabs_rgba8(const uint32_t* gathered, uint32_t* image, int W, int H, int slab_w, int world,
-                               const SlabEdges& e, hipStream_t s, uint32_t* stale)
+                               const SlabEdges& e, hipStream_t s, uint32_t* stale, size_t slab_stride)
 {
     if (W <= 0 || H <= 0) return;
-    hipLaunchKernelGGL(k_unpack_slabs_rgba8, dim3((W + 255) / 256, H), dim3(256), 0, s, gathered, image, W, H, slab_w, world, e, stale);
+    hipLaunchKernelGGL(k_unpack_slabs_rgba8, dim3((W + 255) / 256, H), dim3(256), 0, s, gathered, image, W, H, slab_w, world, e, stale, slab_stride);
 }
 
 void launch_to_rgba8(const float4* fb, uint32_t* out, uint32_t npix, hipStream_t s)

@@ -48,7 +48,8 @@ void launch_deliver_rgba8(const float4* fb, uint32_t* staging, int32_t W, int32_
 // 4:2:0 Y'CbCr (NV12 / I420) for video encoders: the definition is DESIGN.md section 4, "Frame delivery in Y'CbCr".
 // ---------------------------------------------------------------------------------------------------------
 GSR_BOUNDS_DECL(deliver)   // sites: 0 source pixel, 1 byte of the Y plane, 2 byte of the chroma planes, 3 trailer inside the staging buffer,
-                           // 4 word of the depth plane
+                           // 4 word of the depth plane, 5 sample of the hit plane a band pack reads, 6 sample of a slab's depth section
+                           // (written by the pack, read by the de-slab), 7 sample of the gathered plane
 
 constexpr int YUV_STRIP = 8;   // pixels of a row a lane owns (two rows of them)
 
@@ -267,6 +268,98 @@ void launch_deliver_depth(int format, const float* plane, uint8_t* staging, size
     else
         hipLaunchKernelGGL(k_deliver_depth<DELIVER_DEPTH_U16>, grid, block, 0, s, plane, out, n, near, trailer, dims, (uint32_t)serial, (uint32_t)(serial >> 32),
                            overflow, out_words);
+}
+
+void launch_deliver_gathered_depth(const uint32_t* plane, uint32_t words, uint8_t* staging, size_t depth_offset, size_t trailer_offset, int32_t W, int32_t H,
+                                   uint64_t serial, const uint32_t* stale, hipStream_t s)
+{
+    const uint32_t lanes = (words + 3u) / 4u;
+    hipLaunchKernelGGL(k_deliver_depth<DELIVER_DEPTH_F32>, dim3(std::max(1u, (lanes + DELIVER_THREADS - 1) / DELIVER_THREADS)), dim3(DELIVER_THREADS), 0, s,
+                       reinterpret_cast<const float*>(plane), reinterpret_cast<uint32_t*>(staging + depth_offset), words, 0.0f,
+                       reinterpret_cast<uint32_t*>(staging + trailer_offset), (uint32_t)W | ((uint32_t)H << 16), (uint32_t)serial, (uint32_t)(serial >> 32), stale,
+                       (uint32_t)((trailer_offset - depth_offset) / 4));
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Depth in a group (gsr_comm_set_depth): the band's samples of the exchange's hit plane into the slab's depth
+// section, and the gathered sections into one plane.  Pure data movement, a few megabytes at most: what counts is that there is
+// ONE launch each.  Threads run along a row; a pack lane owns four samples of a section row (rows start on 16 bytes and hold a
+// multiple of 8 samples: one 16-byte store as f32, one 8-byte store as u16), a de-slab lane 16 bytes of the gathered plane.
+// Loads are single samples -- a plane row starts wherever y * Wd puts it -- and neighbouring lanes read neighbouring addresses.
+// ---------------------------------------------------------------------------------------------------------
+template <int Format>
+__global__ __launch_bounds__(DELIVER_THREADS) void k_pack_band_depth(const float* __restrict__ plane, uint8_t* __restrict__ section, int Wd,
+                                                                     [[maybe_unused]] int Hd, int xd0, int xd1, int stride, float near)
+{
+    const int s = (blockIdx.x * DELIVER_THREADS + threadIdx.x) * 4, y = blockIdx.y;
+    if (s >= stride) return;
+    const float* row = plane + (size_t)y * Wd;
+    uint32_t v[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int x = xd0 + s + i;
+        v[i] = 0u;   // behind the band's last sample: a narrower band than the widest, and the row's padding
+        if (x < xd1) {
+            GSR_BOUND(deliver, 5, (size_t)y * Wd + x, (size_t)Wd * Hd);
+            v[i] = Format == DELIVER_DEPTH_F32 ? __float_as_uint(row[x]) : depth_u16(row[x], near);
+        }
+    }
+    const size_t at = (size_t)y * stride + s;
+    GSR_BOUND(deliver, 6, at + 3, (size_t)Hd * stride);
+    if (Format == DELIVER_DEPTH_F32) *reinterpret_cast<uint4*>(section + at * 4) = make_uint4(v[0], v[1], v[2], v[3]);
+    else *reinterpret_cast<uint2*>(section + at * 2) = make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
+}
+
+void launch_pack_band_depth(int format, const float* plane, uint8_t* section, int Wd, int Hd, int xd0, int xd1, int stride, float near, hipStream_t s)
+{
+    if (stride <= 0 || Hd <= 0) return;
+    const dim3 grid((stride / 4 + DELIVER_THREADS - 1) / DELIVER_THREADS, Hd), block(DELIVER_THREADS);
+    if (format == DELIVER_DEPTH_F32) hipLaunchKernelGGL(k_pack_band_depth<DELIVER_DEPTH_F32>, grid, block, 0, s, plane, section, Wd, Hd, xd0, xd1, stride, near);
+    else hipLaunchKernelGGL(k_pack_band_depth<DELIVER_DEPTH_U16>, grid, block, 0, s, plane, section, Wd, Hd, xd0, xd1, stride, near);
+}
+
+template <int Format>
+__global__ __launch_bounds__(DELIVER_THREADS) void k_unpack_slabs_depth(const uint8_t* __restrict__ gathered, uint32_t* __restrict__ plane, int Wd, uint32_t n,
+                                                                        size_t slab_bytes, size_t offset, int stride, int world, SlabEdges e)
+{
+    constexpr uint32_t PER_LANE = Format == DELIVER_DEPTH_F32 ? 4u : 8u;
+    const uint32_t s = (blockIdx.x * DELIVER_THREADS + threadIdx.x) * PER_LANE;
+    if (s >= n) return;
+    int y = (int)(s / (uint32_t)Wd), x = (int)(s - (uint32_t)y * (uint32_t)Wd);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};   // (samples behind the plane's last one stay zero: the padding a delivery slot takes with the plane)
+#pragma unroll
+    for (uint32_t i = 0; i < PER_LANE; i++) {
+        if (s + i < n) {
+            uint32_t v = 0u;
+            for (int q = 0; q < world; q++) {
+                if (x >= e.x0[q] && x < e.x1[q]) {
+                    const size_t at = (size_t)y * stride + (x - e.x0[q]);
+                    GSR_BOUND(deliver, 6, offset + (at + 1) * (Format == DELIVER_DEPTH_F32 ? 4 : 2) - 1, slab_bytes);
+                    const uint8_t* sec = gathered + (size_t)q * slab_bytes + offset;
+                    v = Format == DELIVER_DEPTH_F32 ? reinterpret_cast<const uint32_t*>(sec)[at] : (uint32_t)reinterpret_cast<const uint16_t*>(sec)[at];
+                }
+            }
+            if (Format == DELIVER_DEPTH_F32) w[i] = v;
+            else w[i >> 1] |= v << (16u * (i & 1u));
+        }
+        if (++x == Wd) { x = 0; y++; }
+    }
+    GSR_BOUND(deliver, 7, s / PER_LANE, (n + PER_LANE - 1u) / PER_LANE);
+    *reinterpret_cast<uint4*>(plane + s / PER_LANE * 4u) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+void launch_unpack_slabs_depth(int format, const uint8_t* gathered, uint32_t* plane, int Wd, int Hd, size_t slab_bytes, size_t offset, int stride,
+                               int world, const SlabEdges& e, hipStream_t s)
+{
+    if (Wd <= 0 || Hd <= 0) return;
+    const uint32_t n = (uint32_t)Wd * (uint32_t)Hd;   // (Wd, Hd <= 8192)
+    const uint32_t per_lane = format == DELIVER_DEPTH_F32 ? 4u : 8u;
+    const uint32_t lanes = (n + per_lane - 1u) / per_lane;
+    const dim3 grid((lanes + DELIVER_THREADS - 1) / DELIVER_THREADS), block(DELIVER_THREADS);
+    if (format == DELIVER_DEPTH_F32)
+        hipLaunchKernelGGL(k_unpack_slabs_depth<DELIVER_DEPTH_F32>, grid, block, 0, s, gathered, plane, Wd, n, slab_bytes, offset, stride, world, e);
+    else
+        hipLaunchKernelGGL(k_unpack_slabs_depth<DELIVER_DEPTH_U16>, grid, block, 0, s, gathered, plane, Wd, n, slab_bytes, offset, stride, world, e);
 }
 
 template <class Src>

@@ -177,7 +177,13 @@ export class HIPRenderer {
     /** multi-GPU, one process per GPU. Collective: same id (createGroupId() on rank 0), world and edges on every rank.
      *  Afterwards render() draws this rank's tile-column band and all-gathers the RGBA8 frame over xGMI inside the
      *  library (RCCL); readPixels() returns the whole frame on every rank. */
-    joinGroup(group: { id: Uint8Array; rank: number; world: number; edges: Array<[number, number]> }): void;
+    joinGroup(group: { id: Uint8Array; rank: number; world: number; edges: Array<[number, number]>; depth?: DepthDeliveryOptions }): void;
+    /** Depth in a group: every rank exchanges its band's hit depth beside the colour slab (the same options on every rank and sharer;
+     *  null switches it off).  openDelivery(n, { depth }) with these options then works in the group. */
+    setGroupDepth(depth: DepthDeliveryOptions | null): void;
+    /** the gathered plane of the last frame, frameDepthLayout().width x .height samples, row 0 = top */
+    readFrameDepth(): Uint16Array | Float32Array;
+    frameDepthLayout(): DepthLayout;
     /** Another renderer of the same rank (frames in flight) joins the group `leader` has joined: one communicator and one
      *  exchange stream per rank (gsr_comm_share).  Leave (or dispose) it before the leader. */
     shareGroup(leader: HIPRenderer): void;

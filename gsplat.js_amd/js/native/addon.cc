@@ -499,6 +499,59 @@ napi_value ReadFrame(napi_env env, napi_callback_info info)
     return rc ? throw_gsr(env, c, rc, "gsr_read_frame_rgba8") : undefined(env);
 }
 
+// ---- depth in a group (gsr_comm_set_depth) ----
+// commSetDepth(handle, format 0 | 1 | 2, step, near): 0 switches the option off
+napi_value CommSetDepth(napi_env env, napi_callback_info info)
+{
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    int32_t format, step;
+    double near;
+    if (!c || !get_i32(env, argv[1], &format) || !get_i32(env, argv[2], &step)) return nullptr;
+    if (!get_f64(env, argv[3], &near)) { napi_throw_type_error(env, nullptr, "commSetDepth: near must be a number"); return nullptr; }
+    const gsr_depth_delivery_options d{format, step, (float)near, 0};
+    const int rc = gsr_comm_set_depth(c, format == GSR_DEPTH_NONE ? nullptr : &d);
+    return rc ? throw_gsr(env, c, rc, "gsr_comm_set_depth") : undefined(env);
+}
+
+// frameDepthLayout(handle) -> depthLayout's object for the gathered plane (offset 0)
+napi_value FrameDepthLayout(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    if (!c) return nullptr;
+    gsr_depth_layout dl;
+    const int rc = gsr_frame_depth_layout(c, &dl);
+    if (rc) return throw_gsr(env, c, rc, "gsr_frame_depth_layout");
+    auto set = [&](napi_value obj, const char* key, double value) {
+        napi_value v;
+        return napi_create_double(env, value, &v) == napi_ok && napi_set_named_property(env, obj, key, v) == napi_ok;
+    };
+    napi_value out;
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    if (!(set(out, "format", dl.format) && set(out, "step", dl.step) && set(out, "width", dl.width) && set(out, "height", dl.height) &&
+          set(out, "stride", dl.stride) && set(out, "offset", (double)dl.offset) && set(out, "bytes", (double)dl.bytes) && set(out, "near", dl.near))) {
+        napi_throw_error(env, nullptr, "frameDepthLayout: building the result failed");
+        return nullptr;
+    }
+    return out;
+}
+
+// readFrameDepth(handle, Uint8Array out): the gathered plane's bytes
+napi_value ReadFrameDepth(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    void* out;
+    size_t len;
+    if (!c || !get_typed(env, argv[1], napi_uint8_array, &out, &len)) return nullptr;
+    const int rc = gsr_read_frame_depth(c, out, (uint64_t)len);
+    return rc ? throw_gsr(env, c, rc, "gsr_read_frame_depth") : undefined(env);
+}
+
 // ---- frame delivery (gsr_delivery_*): the ring's pinned blocks as external ArrayBuffers, wrapped ONCE per slot ----
 // An ArrayBuffer must never outlive the block it views.  Two guards: (1) every ArrayBuffer holds a reference to the renderer
 // handle until it is collected, so a renderer that is merely dropped keeps its context (and ring) alive as long as any
@@ -837,6 +890,7 @@ napi_value Init(napi_env env, napi_value exports)
         {"openDelivery", OpenDelivery}, {"closeDelivery", Call0<gsr_delivery_close>}, {"deliverySlots", DeliverySlots}, {"detachBuffers", DetachBuffers},
         {"openDeliveryEx", OpenDeliveryEx}, {"deliveryLayout", DeliveryLayout},
         {"openDeliveryDepth", OpenDeliveryDepth}, {"depthLayout", DepthLayout},
+        {"commSetDepth", CommSetDepth}, {"frameDepthLayout", FrameDepthLayout}, {"readFrameDepth", ReadFrameDepth},
         {"deliverFrame", DeliverFrame}, {"frameReady", FrameReady}, {"acquireFrame", AcquireFrame}, {"releaseFrame", ReleaseFrame},
         {"setHitAlpha", SetHitAlpha}, {"depthAsync", Call0<gsr_depth_async>}, {"readDepth", ReadDepth}, {"pick", Pick},
     };

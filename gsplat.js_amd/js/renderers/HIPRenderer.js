@@ -206,6 +206,29 @@ class HIPRenderer {
             for (let q = 0; q < g.world; q++) { x0[q] = g.edges[q][0]; x1[q] = g.edges[q][1]; }
             this._n.commInit(this._h, g.id, g.rank, g.world, x0, x1);
             group = { rank: g.rank, world: g.world };
+            if (g.depth) this.setGroupDepth(g.depth);
+        };
+        // Depth in a group (gsr_comm_set_depth): setGroupDepth({ format: "u16" | "f32", step: 1 | 2, near: 0.1 }) -- or joinGroup({ ..., depth })
+        // -- makes every rank exchange its band's hit depth beside the colour slab: readFrameDepth() returns the gathered plane of the
+        // last frame (frameDepthLayout(): width x height samples), and openDelivery(n, { depth }) with the same options works in the
+        // group: f.depth and f.depthLayout as on a single renderer.  Every rank (and every sharer) passes the same options; null
+        // switches it off again.
+        this.setGroupDepth = (depth) => {
+            if (!depth) { this._n.commSetDepth(this._h, 0, 1, 0); return; }
+            const format = DEPTH_FORMATS.indexOf(depth.format === undefined ? "u16" : depth.format);
+            if (format < 1) throw new Error("setGroupDepth: depth.format must be one of f32, u16");
+            this._n.commSetDepth(this._h, format, (depth.step === undefined ? 1 : depth.step) | 0, +(depth.near === undefined ? 0.1 : depth.near));
+        };
+        this.frameDepthLayout = () => {
+            const d = this._n.frameDepthLayout(this._h);
+            d.format = DEPTH_FORMATS[d.format];
+            return d;
+        };
+        this.readFrameDepth = () => {
+            const d = this._n.frameDepthLayout(this._h);
+            const bytes = new Uint8Array(d.bytes);
+            this._n.readFrameDepth(this._h, bytes);
+            return DEPTH_FORMATS[d.format] === "u16" ? new Uint16Array(bytes.buffer, 0, d.width * d.height) : new Float32Array(bytes.buffer, 0, d.width * d.height);
         };
         // A second renderer of the SAME rank (frames in flight with renderAsync) joins through the first one: it shares the
         // communicator and the exchange stream, so the rank's collectives go out in frame order (gsr_comm_share).

@@ -103,6 +103,7 @@ EXPORTS = [
     "gsr_delivery_open_depth", "gsr_delivery_depth_layout",
     "gsr_set_hit_alpha", "gsr_depth_async", "gsr_read_depth", "gsr_depth_device_ptr", "gsr_pick",
     "gsr_set_scene_arrays",
+    "gsr_comm_set_depth", "gsr_frame_depth_layout", "gsr_read_frame_depth", "gsr_frame_depth_device_ptr",
 ]
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p)
 GSR_COMM_ID_BYTES = 128
@@ -224,6 +225,11 @@ def load_library(path=None):
     L.gsr_depth_device_ptr.argtypes = [vp, ctypes.c_int32]
     L.gsr_depth_device_ptr.restype = vp
     L.gsr_pick.argtypes = [vp, vp, ctypes.c_uint32, vp]
+    L.gsr_comm_set_depth.argtypes = [vp, ctypes.POINTER(GsrDepthDeliveryOptions)]
+    L.gsr_frame_depth_layout.argtypes = [vp, ctypes.POINTER(GsrDepthLayout)]
+    L.gsr_read_frame_depth.argtypes = [vp, vp, ctypes.c_uint64]
+    L.gsr_frame_depth_device_ptr.argtypes = [vp]
+    L.gsr_frame_depth_device_ptr.restype = vp
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int and name not in ("gsplat_sort_host",):
@@ -810,6 +816,41 @@ class HIPRenderer:
 
     def frame8_ptr(self):
         return self._L.gsr_frame8_device_ptr(self._ctx)
+
+    # -- depth in a group (gsr_comm_set_depth): the ranks exchange depth slabs beside the colour slabs --
+    def set_group_depth(self, depth="u16", depth_step=1, near=0.1):
+        """Opt this context, which has joined a group, into exchanging depth: every allgather_frame_async() then also leaves the
+        frame's gathered hit plane on every rank -- read_frame_depth(), or the depth of acquire() on a ring opened with
+        open_delivery_depth(depth=..., depth_step=..., depth_near=near) -- bit for bit the plane a depth ring with these options
+        delivers on one context rendering the whole image.  `depth`: "u16", "f32", or None to switch it off again.  Every rank and
+        every sharer passes the same options."""
+        if depth is None:
+            self._check(self._L.gsr_comm_set_depth(self._ctx, None))
+            return
+        if depth not in DEPTH_DELIVERY_FORMATS:
+            raise ValueError("depth must be None or one of %s" % ", ".join(sorted(DEPTH_DELIVERY_FORMATS)))
+        dopt = GsrDepthDeliveryOptions(DEPTH_DELIVERY_FORMATS[depth], int(depth_step), float(near), 0)
+        self._check(self._L.gsr_comm_set_depth(self._ctx, ctypes.byref(dopt)))
+
+    def frame_depth_layout(self):
+        """The gathered plane (gsr_frame_depth_layout): depth_layout()'s fields, offset 0."""
+        lay = GsrDepthLayout()
+        self._check(self._L.gsr_frame_depth_layout(self._ctx, ctypes.byref(lay)))
+        names = {v: k for k, v in DEPTH_DELIVERY_FORMATS.items()}
+        return {"format": names[lay.format], "step": lay.step, "width": lay.width, "height": lay.height, "stride": lay.stride,
+                "offset": int(lay.offset), "bytes": int(lay.bytes), "near": float(lay.near)}
+
+    def read_frame_depth(self):
+        """The gathered plane of the last allgather_frame_async(), [Hd, Wd] float32 or uint16; waits like read_frame() and refuses
+        a gathered frame with a stale band like it (GSR_ERR_OVERFLOW on every rank: render and gather again)."""
+        lay = GsrDepthLayout()
+        self._check(self._L.gsr_frame_depth_layout(self._ctx, ctypes.byref(lay)))
+        out = np.empty((lay.height, lay.width), dtype=np.float32 if lay.format == GSR_DEPTH_F32 else np.uint16)
+        self._check(self._L.gsr_read_frame_depth(self._ctx, out.ctypes.data, out.nbytes))
+        return out
+
+    def frame_depth_ptr(self):
+        return self._L.gsr_frame_depth_device_ptr(self._ctx)
 
 
 def new_group_id():

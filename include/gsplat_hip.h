@@ -363,8 +363,9 @@ int gsr_delivery_layout(gsr_ctx *ctx, gsr_frame_layout *out);
  * is refused by gsr_acquire_frame with GSR_ERR_OVERFLOW (the depth pass wrote nothing for it) and its slot is freed.
  * gsr_deliver_frame_async on a depth ring needs what gsr_depth_async needs -- a render frame; scene, size, band and list
  * buffers unchanged since -- and otherwise returns GSR_ERR_ARG, enqueues nothing and takes no slot.
- * Groups: depth is not exchanged between ranks.  gsr_delivery_open_depth with a depth format on a context in a group returns
- * GSR_ERR_ARG, and so does gsr_deliver_frame_async on a context that joined a group after it opened a depth ring.
+ * Groups: depth is not exchanged between ranks unless the context opts in (gsr_comm_set_depth, "depth in a group" below).  Without
+ * that, gsr_delivery_open_depth with a depth format on a context in a group returns GSR_ERR_ARG, and so does
+ * gsr_deliver_frame_async on a context that joined a group after it opened a depth ring.
  * A context that never opens a depth ring allocates and launches nothing of this. */
 #define GSR_DEPTH_NONE 0
 #define GSR_DEPTH_F32  1
@@ -385,10 +386,49 @@ typedef struct gsr_depth_layout {
 } gsr_depth_layout;
 /* Colour as gsr_delivery_open_ex(ctx, opt) would deliver it, plus the depth plane.  depth == NULL or format GSR_DEPTH_NONE:
  * exactly gsr_delivery_open_ex.  GSR_ERR_ARG: what gsr_delivery_open_ex refuses; an unknown depth format, a step other than 1
- * or 2, GSR_DEPTH_U16 with a near that is not finite and > 0, reserved != 0, a context in a group. */
+ * or 2, GSR_DEPTH_U16 with a near that is not finite and > 0, reserved != 0, a context in a group that exchanges no depth or
+ * exchanges it with other options. */
 int gsr_delivery_open_depth(gsr_ctx *ctx, const gsr_delivery_options *opt, const gsr_depth_delivery_options *depth);
 /* The depth plane of the open ring's frames at the current size; GSR_ERR_ARG: no ring, or a ring without depth. */
 int gsr_delivery_depth_layout(gsr_ctx *ctx, gsr_depth_layout *out);
+
+/* ---- depth in a group: ranks exchange depth slabs beside the colour slabs ----
+ * Opt-in per context.  A context that has joined a group and calls gsr_comm_set_depth with a depth format exchanges, with every
+ * gsr_allgather_frame_async, the frame's hit plane beside its colour.  The call then also enqueues, on the render stream behind
+ * the frame and the colour pack, the hit-plane pass over this rank's bin columns (the pass and the hit_alpha rule of a depth
+ * ring, into a plane the exchange owns: gsr_read_depth, gsr_depth_device_ptr and gsr_pick answer as before) and a pack of the
+ * band's samples into a depth section of the slab; ONE collective carries colour pixels, flag words and depth section, and one
+ * more de-slab step on the exchange stream leaves the gathered plane on every rank.  No host wait is added.  With the option on,
+ * gsr_allgather_frame_async needs what gsr_depth_async needs of the frame and otherwise returns GSR_ERR_ARG and enqueues nothing.
+ * The gathered plane [Hd][Wd], Wd = ceil(width / step), Hd = ceil(height / step), sample (i, j) = pixel (step * i, step * j), is
+ * bit for bit the plane a depth ring with the same options delivers for the same frame on one context rendering the whole image.
+ * Band edges are multiples of 32, so rank q owns the plane's columns [x0[q] / step, ceil(x1[q] / step)): disjoint, covering Wd.
+ * A slab: pixels and flag words where they are without the option; the depth section at the next multiple of 16 bytes: Hd rows
+ * of S samples (f32 or u16), S = ceil(widest band / step) rounded up to a multiple of 8, the band's samples at the front of a row
+ * and zeros behind them.  bytes_per_rank of a custom collective grows by the padding and Hd * S * sample size.
+ * Overflow: a band packed behind a frame whose lists did not fit carries no valid depth; the slab's flag makes every rank refuse
+ * that gathered frame -- gsr_read_frame_depth like gsr_read_frame_rgba8, gsr_acquire_frame likewise: GSR_ERR_OVERFLOW on every
+ * rank alike -- and the group renders and gathers it again.
+ * Delivery: on such a context gsr_delivery_open_depth accepts depth options equal to the exchange's in format, step and near
+ * (GSR_ERR_ARG names the first that differs), and gsr_deliver_frame_async delivers the gathered colour (RGBA8, NV12 or I420) and
+ * the gathered plane of the last gsr_allgather_frame_async, on the exchange stream, without a depth pass of its own: serial k
+ * carries colour and depth of gathered frame k.  Slot layout, trailer, gsr_delivery_layout and gsr_delivery_depth_layout are a
+ * depth ring's; one device-to-host copy per frame.  A ring opened before the context joined works once the options match at
+ * the time of gsr_deliver_frame_async.
+ * The option is part of the group's contract like the band edges: every rank, and every sharer (gsr_comm_share), passes the same
+ * options before its next gsr_allgather_frame_async.  It goes with the group: gsr_comm_destroy, gsr_destroy, joining anew and a
+ * gsr_resize that drops the group clear it.  A context that never opts in allocates and launches nothing of this, and its slab
+ * is the colour slab byte for byte.  Not exchanged: the mean and index planes; gsr_pick answers for this rank's band only. */
+/* Opt a context that has joined a group into exchanging depth.  `depth` has the meaning it has for
+ * gsr_delivery_open_depth (format F32 | U16, step 1 | 2, near, reserved 0); NULL or GSR_DEPTH_NONE
+ * switches it off again.  Part of the group's contract like the band edges: every rank, and every
+ * sharer (gsr_comm_share), passes the same options before its next gsr_allgather_frame_async.
+ * GSR_ERR_ARG: a context that is in no group; options gsr_delivery_open_depth refuses.  Waits for the render and exchange
+ * streams, reallocates the exchange buffers and drops the gathered frame (gather again before reading or delivering). */
+int gsr_comm_set_depth(gsr_ctx *ctx, const gsr_depth_delivery_options *depth);
+int gsr_frame_depth_layout(gsr_ctx *ctx, gsr_depth_layout *out);          /* offset 0: the gathered plane */
+int gsr_read_frame_depth(gsr_ctx *ctx, void *out, uint64_t out_bytes);    /* blocking; beside gsr_read_frame_rgba8 */
+void *gsr_frame_depth_device_ptr(gsr_ctx *ctx);                           /* [Hd][Wd] f32 or u16 on the device */
 
 /* ---- depth and pick: per-pixel depth planes of the last rendered frame, and the splat under a pixel ----
  * No interface of the reference stands behind this section (its renderer returns colour only, WebGLRenderer.ts:241-296): it
