@@ -165,7 +165,24 @@ struct gsr_ctx {
         uint32_t sh_count = 0;
         int32_t band[3] = {-1, -1, -1};
         gsr::SceneSoA soa() const { return gsr::SceneSoA{arr.px, arr.py, arr.pz, arr.cov0, arr.cov1, arr.cov2, arr.rgba, sh_r, sh_g, sh_b, shcol}; }
-        void drop_sh() { sh_count = 0; band[0] = band[1] = band[2] = -1; sh_r.reset(); sh_g.reset(); sh_b.reset(); shcol.reset(); }
+        // The SH frame: the inverse of the linear part of every rotate / scale since the coefficients were
+        // supplied, row-major; the projection takes SH directions through it.  Kept up by gsr_scene_rotate / _scale while sh_follow
+        // is set; the identity takes the projection's frameless path.
+        bool sh_follow = false;
+        // the other set of SH textures a followed gsr_scene_limit_box compacts into (then the two sets change places): allocated by
+        // the first such call, kept until the SH state goes; sh_rows / sh_spare_rows: the rows each set was allocated for
+        gsr::DevBuf<uint32_t> sh_spare[3];
+        uint32_t sh_rows = 0, sh_spare_rows = 0;
+        double sh_frame[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        void reset_sh_frame() { for (int k = 0; k < 9; k++) sh_frame[k] = (k % 4 == 0) ? 1.0 : 0.0; }
+        bool sh_frame_is_identity() const
+        {
+            for (int k = 0; k < 9; k++) if (sh_frame[k] != ((k % 4 == 0) ? 1.0 : 0.0)) return false;
+            return true;
+        }
+        void drop_sh() { sh_count = 0; band[0] = band[1] = band[2] = -1; sh_r.reset(); sh_g.reset(); sh_b.reset(); shcol.reset(); reset_sh_frame();
+                         for (auto& b : sh_spare) b.reset();
+                         sh_rows = sh_spare_rows = 0; }
     } scene;
 
     struct Sort {    // per splat and frame: what the projection writes and the sort permutes; sized by alloc_scene

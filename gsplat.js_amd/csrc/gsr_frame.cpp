@@ -461,6 +461,10 @@ int enqueue_frame(gsr_ctx* c, bool render)
     c->cam.band_px1 = a.grid.bx_hi * BIN_PX;
     c->cam.sh_on = c->scene.sh_count ? 1 : 0;
     c->cam.band[0] = c->scene.band[0]; c->cam.band[1] = c->scene.band[1]; c->cam.band[2] = c->scene.band[2];
+    // the SH frame travels in the camera block: the one argument a graph replay rewrites, so a changed frame reaches the
+    // projection like a changed camera.  The identity (every context that never opted in) takes the frameless path.
+    c->cam.sh_frame = (c->scene.sh_count && !c->scene.sh_frame_is_identity()) ? 1 : 0;
+    for (int k = 0; k < 9; k++) c->cam.shm[k] = c->cam.sh_frame ? (float)c->scene.sh_frame[k] : 0.0f;
     if (render) c->cam_frame = c->cam;   // (gsr_read_records projects once more for this camera to get the pixel boxes)
     // No kernel in front of the frame: the camera is an argument of the projection kernel (k_project_key; k_depth_key in a
     // sort-only frame), the frame slots are left clean by their last reader, the frame words are stored, not accumulated

@@ -30,6 +30,8 @@ struct CamParams {
     int32_t band_px0, band_px1;  // pixel columns [x0, x1) this context composites (multi-GPU band; whole image otherwise)
     int32_t use_fade;       // u_useDepthFade
     float fade;             // u_depthFade
+    int32_t sh_frame;       // the SH frame is not the identity: SH directions go through shm first ("SH frame")
+    float shm[9];           // the frame, row-major, rounded once from the host's f64 (read only where sh_frame is set)
 };
 
 // 32-byte projected record consumed by the tile compositor (image coordinates, row 0 = top).
@@ -81,6 +83,11 @@ void launch_scene_rotate(uint32_t n, const SceneDev& sc, const double* q_xyzw, h
 void launch_scene_scale(uint32_t n, const SceneDev& sc, const double* sv, hipStream_t s);
 void launch_scene_limit_box(uint32_t n, const SceneDev& src, const SceneDev& dst, const double* box, uint32_t* block_count,
                             uint32_t* total, hipStream_t s);
+// limitBox of a scene whose SH colour follows it, enqueued behind launch_scene_limit_box while `src` still holds the source
+// positions: count[1..3] <- the kept splats in front of bandsIndices[k] + 1 (count[0]: the total the scan left there), and the
+// 8-word rows of the kept SH splats of sh_in[0..2], in order, into sh_out[0..2] (sh_count rows each).
+void launch_scene_limit_box_sh(uint32_t n, const SceneDev& src, const double* box, const uint32_t* block_off, uint32_t* count,
+                               const int32_t* band, uint32_t sh_count, const uint32_t* const* sh_in, uint32_t* const* sh_out, hipStream_t s);
 // Scene.scales (3 f32 per splat, device memory) -> scl; and the scene back into the layouts of Scene.data (8 words per splat,
 // 16-byte aligned), positions and scales (3 f32 per splat): a null output is skipped.  Rotations need neither: `rot` IS
 // Scene.rotations' layout.

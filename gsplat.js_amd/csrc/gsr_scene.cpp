@@ -2,6 +2,8 @@
 // scenes that carry rotations and scales, spherical harmonics, and the scene's read-back.  alloc_scene sizes everything that holds one entry per splat.
 #include "gsr_ctx.h"
 
+#include <cmath>
+
 using namespace gsr;
 
 // (re)allocate everything sized by the splat count; clears SH and per-frame state
@@ -138,15 +140,35 @@ int gsr_scene_rotate(gsr_ctx* c, const double* q)
     if (int r = need_rows(c)) return r;
     launch_scene_rotate(c->n, c->scene.arr.view(), q, c->stream);
     HIP_TRY(c, hipGetLastError());
+    if (c->scene.sh_follow && c->scene.sh_count) {   // Linv <- Linv . R(q)^T, R as k_scene_rotate builds it (the frame belongs to an SH state)
+        const double x = q[0], y = q[1], z = q[2], w = q[3];
+        const double R[9] = {1 - 2 * y * y - 2 * z * z, 2 * x * y - 2 * z * w, 2 * x * z + 2 * y * w,
+                             2 * x * y + 2 * z * w, 1 - 2 * x * x - 2 * z * z, 2 * y * z - 2 * x * w,
+                             2 * x * z - 2 * y * w, 2 * y * z + 2 * x * w, 1 - 2 * x * x - 2 * y * y};
+        double* L = c->scene.sh_frame;
+        double out[9];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) out[3 * i + j] = (L[3 * i] * R[3 * j] + L[3 * i + 1] * R[3 * j + 1]) + L[3 * i + 2] * R[3 * j + 2];
+        for (int k = 0; k < 9; k++) L[k] = out[k];
+    }
     return GSR_OK;
 }
 
 int gsr_scene_scale(gsr_ctx* c, const double* sv)
 {
     if (!c || !sv) return GSR_ERR_ARG;
+    if (c->scene.sh_follow)   // the frame is the inverse of the edits: there is none of a scale by 0
+        for (int k = 0; k < 3; k++)
+            if (!(std::isfinite(sv[k]) && sv[k] != 0.0))
+                return fail(c, GSR_ERR_ARG, "scale component %d is %g: with gsr_set_sh_follow on, a scale must be finite and not 0", k, sv[k]);
     if (int r = need_rows(c)) return r;
     launch_scene_scale(c->n, c->scene.arr.view(), sv, c->stream);
     HIP_TRY(c, hipGetLastError());
+    if (c->scene.sh_follow && c->scene.sh_count) {   // Linv <- Linv . diag(1 / sx, 1 / sy, 1 / sz)
+        double* L = c->scene.sh_frame;
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) L[3 * i + j] = L[3 * i + j] * (1.0 / sv[j]);
+    }
     return GSR_OK;
 }
 
@@ -160,26 +182,50 @@ int gsr_scene_limit_box(gsr_ctx* c, const double* box, uint32_t* new_count)
     const uint32_t n = c->n;
     uint32_t kept = 0;
     if (n) {
+        gsr_ctx::Scene& sc = c->scene;
+        const bool follow = sc.sh_follow && sc.sh_count;   // the SH textures are compacted with the scene
         SceneArrays dst;   // the kept splats are compacted into a second set of arrays, which then becomes the scene
-        DevBuf<uint32_t> block_count, total;
+        DevBuf<uint32_t> block_count, count;   // count: [0] kept splats, [1..3] those in front of bandsIndices[k] + 1 (follow)
+        uint32_t counts[4] = {0, 0, 0, 0};
         int r;
-        if ((r = dst.alloc(c, n, true)) || (r = block_count.alloc(c, (n + 1023) / 1024)) || (r = total.alloc(c, 1))) return r;
-        launch_scene_limit_box(n, c->scene.arr.view(), dst.view(), box, block_count, total, c->stream);
-        hipError_t e1 = hipMemcpyAsync(&kept, total, 4, hipMemcpyDeviceToHost, c->stream);
+        if ((r = dst.alloc(c, n, true)) || (r = block_count.alloc(c, (n + 1023) / 1024)) || (r = count.alloc(c, 4))) return r;
+        launch_scene_limit_box(n, sc.arr.view(), dst.view(), box, block_count, count, c->stream);
+        if (follow) {
+            if (sc.sh_spare_rows < sc.sh_count) {   // the second set of textures: allocated on first use, then the two sets take turns
+                for (auto& b : sc.sh_spare)
+                    if ((r = b.alloc(c, (size_t)sc.sh_count * 8))) { sc.sh_spare_rows = 0; return r; }
+                sc.sh_spare_rows = sc.sh_count;
+            }
+            const uint32_t* in[3] = {sc.sh_r, sc.sh_g, sc.sh_b};
+            uint32_t* out[3] = {sc.sh_spare[0], sc.sh_spare[1], sc.sh_spare[2]};
+            launch_scene_limit_box_sh(n, sc.arr.view(), box, block_count, count, sc.band, sc.sh_count, in, out, c->stream);
+        }
+        hipError_t e1 = hipMemcpyAsync(counts, count, follow ? 16 : 4, hipMemcpyDeviceToHost, c->stream);
         hipError_t e2 = hipStreamSynchronize(c->stream);
         for (hipError_t e : {e1, e2, hipGetLastError()})
             if (e != hipSuccess) return fail(c, GSR_ERR_HIP, "limitBox failed: %s", hipGetErrorString(e));
-        std::swap(c->scene.arr, dst);
+        kept = counts[0];
+        std::swap(sc.arr, dst);
         c->n = kept;   // arrays keep their old capacity; per-frame buffers sized for the old count still fit
         c->sort.blocks = (kept + c->sort.kpb - 1) / c->sort.kpb;
         // The compaction renumbers the splats, so SH rows (indexed by splat - (bandsIndices[0] + 1)) and the band
-        // thresholds no longer belong to them: the SH state is dropped and the scene falls back to its rgba8 colours
-        // until gsr_set_scene_sh is called again.  (Scene.limitBox, Scene.ts:307-366, leaves shs_rgb / bandsIndices
-        // untouched, i.e. stale; a host that wants SH after limitBox re-packs them for the kept splats.)
-        c->scene.drop_sh();
+        // thresholds no longer belong to them.  With gsr_set_sh_follow on they were renumbered with the scene: the kept rows
+        // are in sh_dst, bandsIndices'[k] = (kept splats with index <= bandsIndices[k]) - 1, and the frame stays.  Otherwise
+        // the SH state is dropped and the scene falls back to its rgba8 colours until gsr_set_scene_sh is called again.
+        // (Scene.limitBox, Scene.ts:307-366, leaves shs_rgb / bandsIndices untouched, i.e. stale.)
+        const bool sh_kept = follow && kept > counts[1];
+        if (sh_kept) {
+            std::swap(sc.sh_r, sc.sh_spare[0]); std::swap(sc.sh_g, sc.sh_spare[1]); std::swap(sc.sh_b, sc.sh_spare[2]);
+            std::swap(sc.sh_rows, sc.sh_spare_rows);
+            sc.sh_count = kept - counts[1];
+            for (int k = 0; k < 3; k++) sc.band[k] = (int32_t)counts[1 + k] - 1;
+        }
+        else sc.drop_sh();   // (no SH splat survived: cleared, as gsr_set_scene_sh with sh_count 0 clears it)
         // the binning's plan for the new count (plan_bins): fewer splats can mean fewer rounds and so MORE table rows, which
         // alloc_bins regrows; like every alloc_bins it drops what the last frame left in the lists (they index the old numbering)
         if ((r = alloc_bins(c))) return r;
+        // (last: the context is whole whatever this returns) evaluated colours of the old numbering go, as gsr_set_scene_sh leaves them
+        if (sh_kept) HIP_TRY(c, hipMemsetAsync(sc.shcol, 0, (size_t)kept * sizeof(float4), c->stream));
     }
     if (new_count) *new_count = kept;
     return GSR_OK;
@@ -227,6 +273,7 @@ int gsr_set_scene_sh(gsr_ctx* c, const uint32_t* sh_r, const uint32_t* sh_g, con
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     gsr_ctx::Scene& sc = c->scene;
     sc.sh_count = 0; sc.band[0] = sc.band[1] = sc.band[2] = -1;
+    sc.reset_sh_frame();   // new coefficients are in the scene's frame as it stands
     c->have_frame = false;
     if (!sh_count) return GSR_OK;
     if (!sh_r || !sh_g || !sh_b || !band_index) return fail(c, GSR_ERR_ARG, "SH texture or band_index pointer is NULL");
@@ -243,7 +290,52 @@ int gsr_set_scene_sh(gsr_ctx* c, const uint32_t* sh_r, const uint32_t* sh_g, con
     HIP_TRY(c, hipMemsetAsync(sc.shcol, 0, (size_t)c->n * sizeof(float4), c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     sc.sh_count = sh_count;
+    sc.sh_rows = sh_count;
     sc.band[0] = band_index[0]; sc.band[1] = band_index[1]; sc.band[2] = band_index[2];
+    return GSR_OK;
+}
+
+int gsr_set_sh_follow(gsr_ctx* c, int32_t on)
+{
+    if (!c) return GSR_ERR_ARG;
+    c->scene.sh_follow = on != 0;
+    return GSR_OK;
+}
+
+int gsr_set_sh_frame(gsr_ctx* c, const double* linv)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (!c->scene.sh_count) return fail(c, GSR_ERR_ARG, "gsr_set_sh_frame: the scene has no SH state (call gsr_set_scene_sh first)");
+    if (linv)
+        for (int k = 0; k < 9; k++)
+            if (!std::isfinite(linv[k])) return fail(c, GSR_ERR_ARG, "gsr_set_sh_frame: entry %d is not finite", k);
+    if (linv) for (int k = 0; k < 9; k++) c->scene.sh_frame[k] = linv[k];
+    else c->scene.reset_sh_frame();
+    c->have_frame = false;   // (the evaluated colours of the last frame are another frame's)
+    return GSR_OK;
+}
+
+int gsr_get_sh_frame(gsr_ctx* c, double* linv, int32_t* follow)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (linv) for (int k = 0; k < 9; k++) linv[k] = c->scene.sh_frame[k];
+    if (follow) *follow = c->scene.sh_follow ? 1 : 0;
+    return GSR_OK;
+}
+
+int gsr_read_scene_sh(gsr_ctx* c, uint32_t* sh_r, uint32_t* sh_g, uint32_t* sh_b, uint32_t* sh_count, int32_t* band_index)
+{
+    if (!c) return GSR_ERR_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const gsr_ctx::Scene& sc = c->scene;
+    if (sh_count) *sh_count = sc.sh_count;
+    if (band_index) for (int k = 0; k < 3; k++) band_index[k] = sc.band[k];
+    if (!sc.sh_count || (!sh_r && !sh_g && !sh_b)) return GSR_OK;
+    const size_t bytes = (size_t)sc.sh_count * 32;
+    if (sh_r) HIP_TRY(c, hipMemcpyAsync(sh_r, sc.sh_r, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (sh_g) HIP_TRY(c, hipMemcpyAsync(sh_g, sc.sh_g, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (sh_b) HIP_TRY(c, hipMemcpyAsync(sh_b, sc.sh_b, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return GSR_OK;
 }
 

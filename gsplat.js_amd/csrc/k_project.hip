@@ -295,7 +295,13 @@ __global__ __launch_bounds__(PROJ_THREADS) void k_project_key(SceneSoA sc, uint3
                         t = t + cam.view[q * 4 + 2] * cam.view[14];
                         cp[q] = -t;
                     }
-                    const float dvx = x - cp[0], dvy = y - cp[1], dvz = z - cp[2];
+                    float dvx = x - cp[0], dvy = y - cp[1], dvz = z - cp[2];
+                    if (cam.sh_frame) {   // (uniform) the scene was rotated / scaled under its coefficients: the direction in THEIR frame
+                        const float e0 = (cam.shm[0] * dvx + cam.shm[1] * dvy) + cam.shm[2] * dvz;
+                        const float e1 = (cam.shm[3] * dvx + cam.shm[4] * dvy) + cam.shm[5] * dvz;
+                        const float e2 = (cam.shm[6] * dvx + cam.shm[7] * dvy) + cam.shm[8] * dvz;
+                        dvx = e0; dvy = e1; dvz = e2;
+                    }
                     const float dl = sqrtf((dvx * dvx + dvy * dvy) + dvz * dvz);
                     const float dxn = dvx / dl, dyn = dvy / dl, dzn = dvz / dl;
                     const uint32_t t = i - (uint32_t)(cam.band[0] + 1);

@@ -4,6 +4,8 @@
 // file is compiled with -ffp-contract=off, so every word matches the JavaScript result bit for bit.
 #include "gsr_internal.h"
 
+#include <algorithm>
+
 namespace gsr {
 
 // src/utils.ts:16-43 floatToHalf: truncating; JS `>>` takes the shift count modulo 32
@@ -196,6 +198,63 @@ __global__ __launch_bounds__(BOX_THREADS) void k_box_compact(uint32_t n, SceneDe
     dst.rot[o] = src.rot[i]; dst.scl[o] = src.scl[i];
 }
 
+// ---- limitBox on a scene whose SH colour follows it (gsr_set_sh_follow): the SH textures are compacted with the scene ----
+GSR_BOUNDS_DECL(scene_sh)   // sites: 0 source splat of k_box_thresholds, 1 SH row read by k_box_compact_sh, 2 SH row it stores
+
+// The three kept-prefix counts the new band thresholds come from: count[1 + k] = kept splats with index < at[k] (at[k] =
+// bandsIndices[k] + 1 clamped to [0, n], by the host), beside the total k_box_scan left in count[0]: the exclusive offset at at[k].
+// One workgroup per threshold; it recounts the part of the threshold's block in front of it.
+struct BoxThresholds { uint32_t at[3]; };
+
+__global__ __launch_bounds__(BOX_THREADS) void k_box_thresholds(uint32_t n, SceneDev sc, Box box, const uint32_t* __restrict__ block_off,
+                                                                BoxThresholds th, uint32_t* __restrict__ count)
+{
+    __shared__ uint32_t s_w[BOX_THREADS / WAVE];
+    const uint32_t at = th.at[blockIdx.x];   // <= n
+    const uint32_t block = at / BOX_THREADS, i = block * BOX_THREADS + threadIdx.x;
+    const bool keep = i < at && in_box(sc, i, box.v);   // (i < at <= n)
+    if (keep) GSR_BOUND(scene_sh, 0, i, n);
+    const uint64_t m = __ballot(keep);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = at < n ? block_off[block] : count[0];   // (at == n: everything kept lies in front of it)
+        if (at < n)
+            for (int w = 0; w < BOX_THREADS / WAVE; w++) t += s_w[w];
+        count[1 + blockIdx.x] = t;
+    }
+}
+
+// k_box_compact's mask and offsets once more, for the SH rows: splat i > band0 owns row i - (band0 + 1) of each texture, 8 words
+// = two uint4; kept splat number o owns row o - count[1] of the compacted ones (count[1]: the kept splats without SH, above).
+// 96 bytes per kept SH splat, whole uint4 loads and stores.
+__global__ __launch_bounds__(BOX_THREADS) void k_box_compact_sh(uint32_t n, SceneDev src, Box box, const uint32_t* __restrict__ block_off,
+                                                                const uint32_t* __restrict__ count, int32_t band0, uint32_t sh_count,
+                                                                const uint4* __restrict__ r_in, const uint4* __restrict__ g_in,
+                                                                const uint4* __restrict__ b_in, uint4* __restrict__ r_out,
+                                                                uint4* __restrict__ g_out, uint4* __restrict__ b_out)
+{
+    __shared__ uint32_t s_w[BOX_THREADS / WAVE];
+    const uint32_t i = blockIdx.x * BOX_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool keep = i < n && in_box(src, i, box.v);
+    const uint64_t m = __ballot(keep);
+    if (lane == 0) s_w[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t off = block_off[blockIdx.x];
+    for (int w = 0; w < wave; w++) off += s_w[w];
+    if (!keep || (int32_t)i <= band0) return;
+    const uint32_t o = off + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    const size_t t = i - (uint32_t)(band0 + 1), u = o - count[1];   // (every kept splat in front of an SH splat is counted in o)
+    GSR_BOUND(scene_sh, 1, t, sh_count);
+    GSR_BOUND(scene_sh, 2, u, sh_count);
+    if (t >= sh_count || u >= sh_count) return;
+    const uint4 r0 = r_in[2 * t], r1 = r_in[2 * t + 1], g0 = g_in[2 * t], g1 = g_in[2 * t + 1], b0 = b_in[2 * t], b1 = b_in[2 * t + 1];
+    r_out[2 * u] = r0; r_out[2 * u + 1] = r1;
+    g_out[2 * u] = g0; g_out[2 * u + 1] = g1;
+    b_out[2 * u] = b0; b_out[2 * u + 1] = b1;
+}
+
 // ---- a scene from the Scene's own arrays, and the scene back into them (gsr_set_scene_arrays / gsr_read_scene) ----
 // Neither does arithmetic: words move between the SoA scene and the layouts of Scene.data / positions / rotations / scales.
 // Scene.rotations is (w, x, y, z) per splat, byte for byte what `rot` holds, so rotations are copied straight in and out and
@@ -290,6 +349,20 @@ void launch_scene_limit_box(uint32_t n, const SceneDev& src, const SceneDev& dst
     hipLaunchKernelGGL(k_box_count, dim3(nblocks), dim3(BOX_THREADS), 0, s, n, src, b, block_count);
     hipLaunchKernelGGL(k_box_scan, dim3(1), dim3(BOX_THREADS), 0, s, block_count, nblocks, total);
     hipLaunchKernelGGL(k_box_compact, dim3(nblocks), dim3(BOX_THREADS), 0, s, n, src, dst, b, (const uint32_t*)block_count);
+}
+
+void launch_scene_limit_box_sh(uint32_t n, const SceneDev& src, const double* box, const uint32_t* block_off, uint32_t* count,
+                               const int32_t* band, uint32_t sh_count, const uint32_t* const* sh_in, uint32_t* const* sh_out, hipStream_t s)
+{
+    if (!n) return;
+    Box b;
+    for (int k = 0; k < 6; k++) b.v[k] = box[k];
+    BoxThresholds th;
+    for (int k = 0; k < 3; k++) th.at[k] = (uint32_t)std::min<int64_t>(std::max<int64_t>((int64_t)band[k] + 1, 0), (int64_t)n);
+    const uint32_t nblocks = (n + BOX_THREADS - 1) / BOX_THREADS;
+    hipLaunchKernelGGL(k_box_thresholds, dim3(3), dim3(BOX_THREADS), 0, s, n, src, b, block_off, th, count);
+    hipLaunchKernelGGL(k_box_compact_sh, dim3(nblocks), dim3(BOX_THREADS), 0, s, n, src, b, block_off, (const uint32_t*)count, band[0], sh_count,
+                       (const uint4*)sh_in[0], (const uint4*)sh_in[1], (const uint4*)sh_in[2], (uint4*)sh_out[0], (uint4*)sh_out[1], (uint4*)sh_out[2]);
 }
 
 void launch_scene_import(const float* scales, uint32_t n, float4* scl, hipStream_t s)

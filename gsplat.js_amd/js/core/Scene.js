@@ -40,6 +40,12 @@ class Scene extends EventDispatcher {
         this._diverged = false;        // a plain setter replaced a buffer: the device copies are behind until the next "change"
         this._editOnDevice = false;    // true while the "change" of an edit the devices have applied is dispatched
         this._shDroppedOnDevice = false;
+        // SH colour that follows the transforms (opt-in; DESIGN.md section 4, "SH frame"): shFrame is the inverse of the linear part
+        // of every rotate / scale since setData, row-major; with the option on, limitBox compacts shs_rgb and recounts bandsIndices
+        // (on the device while attached: the three then are mirrors like the four arrays, refreshed on first read).
+        this._shFollowsTransforms = false;
+        this._shFrame = new Float64Array([1, 0, 0, 0, 1, 0, 0, 0, 1]);
+        this._shStale = false;         // the device compacted the SH state and shs_rgb / shHeight / bandsIndices have not seen it
         // A "change" that is not a device edit's (setData, an edit that ran here, one the caller dispatched after writing into
         // the arrays) makes every attached renderer upload the host's arrays: afterwards the device copies are current again.
         const dispatch = this.dispatchEvent;
@@ -50,12 +56,16 @@ class Scene extends EventDispatcher {
     }
 
     // ---- binding to device scenes ----
-    attachDevice(dev) { if (!this._devices.includes(dev)) this._devices.push(dev); }
+    attachDevice(dev) {
+        if (this._devices.includes(dev)) return;
+        this._devices.push(dev);
+        if (dev.setShFollow) dev.setShFollow(this._shFollowsTransforms);
+    }
     // The last device scene to go hands its edits back first, so the scene never loses one.
     detachDevice(dev) {
         const k = this._devices.indexOf(dev);
         if (k < 0) return;
-        if (this._devices.length === 1) { this._refresh(); this._diverged = false; }
+        if (this._devices.length === 1) { this._refresh(); this._refreshSh(); this._diverged = false; }
         this._devices.splice(k, 1);
     }
     // true inside the "change" of an edit every attached device scene has applied already: a renderer has nothing to upload
@@ -78,11 +88,51 @@ class Scene extends EventDispatcher {
         this._stale = false;
     }
 
+    // The SH mirrors after a limitBox the devices followed: 8 * shCount words per texture in front, zeros behind, as the loop
+    // in limitBox leaves them.
+    _refreshSh() {
+        if (!this._shStale) return;
+        this._shStale = false;
+        const band = new Int32Array(3);
+        const count = this._devices[0].readSh(null, band);
+        this._shHeight = Math.ceil((2 * count) / this._width);
+        this._shs_rgb = [0, 1, 2].map(() => new Uint32Array(this._width * this._shHeight * 4));
+        if (count) this._devices[0].readSh(this._shs_rgb, band);
+        this._bandsIndices = band;
+    }
+
+    get shFollowsTransforms() { return this._shFollowsTransforms; }
+    set shFollowsTransforms(on) {
+        this._shFollowsTransforms = !!on;
+        for (const d of this._devices) if (d.setShFollow) d.setShFollow(this._shFollowsTransforms);
+    }
+    get shFrame() { return this._shFrame; }
+
+    // shFrame <- shFrame . R(q)^T, R as rotate builds it; every entry (a * b + c * d) + e * f
+    _frameRotate(q) {
+        const x = q.x, y = q.y, z = q.z, w = q.w, L = this._shFrame, out = new Float64Array(9);
+        const R = [1 - 2 * y * y - 2 * z * z, 2 * x * y - 2 * z * w, 2 * x * z + 2 * y * w,
+                   2 * x * y + 2 * z * w, 1 - 2 * x * x - 2 * z * z, 2 * y * z - 2 * x * w,
+                   2 * x * z - 2 * y * w, 2 * y * z + 2 * x * w, 1 - 2 * x * x - 2 * y * y];
+        for (let i = 0; i < 3; i++)
+            for (let j = 0; j < 3; j++) out[3 * i + j] = (L[3 * i] * R[3 * j] + L[3 * i + 1] * R[3 * j + 1]) + L[3 * i + 2] * R[3 * j + 2];
+        L.set(out);
+    }
+    // shFrame <- shFrame . diag(1 / sx, 1 / sy, 1 / sz)
+    _frameScale(f) {
+        const L = this._shFrame;
+        for (let i = 0; i < 3; i++)
+            for (let j = 0; j < 3; j++) L[3 * i + j] = L[3 * i + j] * (1 / f[j]);
+    }
+
     // kind: 0 translate (x, y, z), 1 rotate (x, y, z, w), 2 scale (x, y, z), 3 limitBox (xMin, xMax, yMin, yMax, zMin, zMax).
     // false: the edit has to run here (nothing attached, a host-only device scene among them, or buffers set by hand).
     _editDevices(kind, args) {
-        if (!this._devices.length || this._diverged || this._devices.some((d) => d.hostOnly)) {
+        // (a device scene that cannot follow SH -- no setShFollow / readSh -- counts as host-only while the option is on)
+        const cannotFollow = this._shFollowsTransforms && this._devices.some((d) => !d.setShFollow || !d.readSh);
+        if (!this._devices.length || this._diverged || cannotFollow || this._devices.some((d) => d.hostOnly)) {
             this._refresh();
+            this._refreshSh();
             return false;
         }
         const f = new Float64Array(args);
@@ -95,7 +145,10 @@ class Scene extends EventDispatcher {
         this._vertexCount = count;
         this._height = Math.ceil((2 * count) / this._width);
         this._stale = true;
-        if (kind === 3) this._shDroppedOnDevice = true;
+        if (kind === 3) {
+            if (this._shFollowsTransforms) this._shStale = this._shStale || this._shHeight > 0;   // compacted with the scene over there
+            else this._shDroppedOnDevice = true;
+        }
         this._editOnDevice = true;
         try { this.dispatchEvent({ type: "change" }); } finally { this._editOnDevice = false; }
         return true;
@@ -126,6 +179,8 @@ class Scene extends EventDispatcher {
         const n = data.length / ROW;
         this._stale = false;            // the host is the truth again: whatever the devices hold is replaced by the upload
         this._shDroppedOnDevice = false;
+        this._shStale = false;
+        this._shFrame.set([1, 0, 0, 0, 1, 0, 0, 0, 1]);
         this._vertexCount = n;
         this._height = Math.ceil((2 * n) / this._width);
         this._data = new Uint32Array(this._width * this._height * 4);
@@ -170,6 +225,7 @@ class Scene extends EventDispatcher {
     }
 
     rotate(rotation) {
+        if (this._shFollowsTransforms) this._frameRotate(rotation);   // (the devices keep their own: gsr_set_sh_follow)
         if (this._editDevices(1, [rotation.x, rotation.y, rotation.z, rotation.w])) return;
         const R = Matrix3.RotationFromQuaternion(rotation).buffer;
         const p = this._positions, r = this._rotations;
@@ -188,6 +244,10 @@ class Scene extends EventDispatcher {
 
     scale(s) {
         const f = [s.x, s.y, s.z];
+        if (this._shFollowsTransforms) {
+            for (const v of f) if (!(Number.isFinite(v) && v !== 0)) throw new Error("scale component " + v + ": with shFollowsTransforms a scale must be finite and not 0");
+            this._frameScale(f);
+        }
         if (this._editDevices(2, f)) return;
         for (let i = 0; i < this._vertexCount; i++) {
             for (let k = 0; k < 3; k++) {
@@ -206,10 +266,21 @@ class Scene extends EventDispatcher {
         if (zMin >= zMax) throw new Error("zMin (" + zMin + ") must be smaller than zMax (" + zMax + ")");
         if (this._editDevices(3, [xMin, xMax, yMin, yMax, zMin, zMax])) return;
         const p = this._positions;
-        let kept = 0;
+        // with shFollowsTransforms the SH rows of the kept splats move up with them, and bandsIndices'[k] = (kept splats with
+        // index <= bandsIndices[k]) - 1
+        const follow = this._shFollowsTransforms && this._shHeight > 0;
+        const band = this._bandsIndices, first = band[0] + 1, below = [0, 0, 0], sh = this._shs_rgb;
+        let kept = 0, shKept = 0;
         for (let i = 0; i < this._vertexCount; i++) {
             const x = p[3 * i], y = p[3 * i + 1], z = p[3 * i + 2];
             if (!(x >= xMin && x <= xMax && y >= yMin && y <= yMax && z >= zMin && z <= zMax)) continue;
+            if (follow) {
+                for (let k = 0; k < 3; k++) if (i <= band[k]) below[k]++;
+                if (i >= first) {
+                    for (let c = 0; c < 3; c++) sh[c].copyWithin(8 * shKept, 8 * (i - first), 8 * (i - first) + 8);
+                    shKept++;
+                }
+            }
             this._data.copyWithin(8 * kept, 8 * i, 8 * i + 8);
             this._positions.copyWithin(3 * kept, 3 * i, 3 * i + 3);
             this._rotations.copyWithin(4 * kept, 4 * i, 4 * i + 4);
@@ -222,6 +293,11 @@ class Scene extends EventDispatcher {
         this._positions = new Float32Array(this._positions.buffer, 0, 3 * kept);
         this._rotations = new Float32Array(this._rotations.buffer, 0, 4 * kept);
         this._scales = new Float32Array(this._scales.buffer, 0, 3 * kept);
+        if (follow) {   // (no SH splat kept: the cleared state, as after a setData without shs)
+            this._shHeight = Math.ceil((2 * shKept) / this._width);
+            this._shs_rgb = sh.map((t) => { const o = new Uint32Array(this._width * this._shHeight * 4); o.set(t.subarray(0, 8 * shKept)); return o; });
+            this._bandsIndices = shKept ? new Int32Array([below[0] - 1, below[1] - 1, below[2] - 1]) : new Int32Array([-1, -1, -1]);
+        }
         this.dispatchEvent({ type: "change" });
     }
 
@@ -252,13 +328,14 @@ class Scene extends EventDispatcher {
 // plain accessors, as in Scene.ts:414-508.  Reading one of the four mirrors refreshes them first; assigning a buffer or a count
 // makes the host the truth (the mirrors are refreshed first, so no edit is lost) and takes the scene off the device path until
 // the next "change" has made the attached renderers upload it.
-const MIRRORS = ["data", "positions", "rotations", "scales"], UPLOADED = MIRRORS.concat(["vertexCount", "height"]);
+const MIRRORS = ["data", "positions", "rotations", "scales"], SH_MIRRORS = ["shs_rgb", "shHeight", "bandsIndices"], UPLOADED = MIRRORS.concat(["vertexCount", "height"]);
 for (const k of ["data", "vertexCount", "width", "height", "positions", "rotations", "scales", "shs", "shs_rgb", "shHeight",
                  "g0bands", "bandsIndices"]) {
-    const mirror = MIRRORS.includes(k), uploaded = UPLOADED.includes(k);
+    const mirror = MIRRORS.includes(k), uploaded = UPLOADED.includes(k), shMirror = SH_MIRRORS.includes(k);
     Object.defineProperty(Scene.prototype, k, {
-        get() { if (mirror) this._refresh(); return this["_" + k]; },
+        get() { if (mirror) this._refresh(); if (shMirror) this._refreshSh(); return this["_" + k]; },
         set(v) {
+            if (shMirror) this._refreshSh();
             if (uploaded) { this._refresh(); this._diverged = this._devices.length > 0; }
             this["_" + k] = v;
         },

@@ -54,6 +54,12 @@ export interface DeviceScene {
     transform(kind: number, args: Float64Array): number;
     /** fills the first 8 / 3 / 4 / 3 words per splat of the four arrays */
     read(out: { data: Uint32Array; positions: Float32Array; rotations: Float32Array; scales: Float32Array }): void;
+    /** optional: Scene.shFollowsTransforms, told on attach and on every change of the option.  While the option is on, a device scene
+     *  without setShFollow and readSh is treated like a host-only one: the edits run in JavaScript and every renderer uploads. */
+    setShFollow?(on: boolean): void;
+    /** needed with setShFollow: the SH state after a followed limitBox; fills `textures` (8 * shCount words each; null: none) and
+     *  `band` (bandsIndices), returns shCount */
+    readSh?(textures: [Uint32Array, Uint32Array, Uint32Array] | null, band: Int32Array): number;
 }
 export class Scene {
     static RowLength: number;
@@ -82,6 +88,13 @@ export class Scene {
     readonly deviceEditApplied: boolean;
     /** limitBox ran on the device, which drops the SH state there: the SH textures are not sent again before the next setData */
     readonly shDroppedOnDevice: boolean;
+    /** SH colour follows rotate / scale / limitBox (default false: the reference's behaviour).  On: rotate / scale keep `shFrame` up
+     *  and the renderer evaluates SH for the direction in the coefficients' own frame; limitBox compacts `shs_rgb` and recounts
+     *  `bandsIndices` (on the device while attached: the three are then mirrors, like the four arrays), `shDroppedOnDevice` stays
+     *  false; a scale with a component that is 0 or not finite throws. */
+    shFollowsTransforms: boolean;
+    /** 3x3 row-major: the inverse of the linear part of every rotate / scale since setData (the identity after setData) */
+    readonly shFrame: Float64Array;
 }
 export class Camera {
     position: Vector3; rotation: Quaternion;

@@ -284,6 +284,77 @@ napi_value ReadSceneArrays(napi_env env, napi_callback_info info)
     return n;
 }
 
+// setShFollow(handle, on)
+napi_value SetShFollow(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    int32_t on;
+    if (!c || !get_i32(env, argv[1], &on)) return nullptr;
+    const int rc = gsr_set_sh_follow(c, on);
+    return rc ? throw_gsr(env, c, rc, "gsr_set_sh_follow") : undefined(env);
+}
+
+// setShFrame(handle, Float64Array(9) | null)
+napi_value SetShFrame(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    void* m;
+    size_t len;
+    if (!c || !get_typed(env, argv[1], napi_float64_array, &m, &len, true)) return nullptr;
+    if (m && len < 9) { napi_throw_range_error(env, nullptr, "the SH frame has 9 entries"); return nullptr; }
+    const int rc = gsr_set_sh_frame(c, (const double*)m);
+    return rc ? throw_gsr(env, c, rc, "gsr_set_sh_frame") : undefined(env);
+}
+
+// getShFrame(handle, Float64Array(9) out) -> follow (0 / 1)
+napi_value GetShFrame(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    void* m;
+    size_t len;
+    if (!c || !get_typed(env, argv[1], napi_float64_array, &m, &len)) return nullptr;
+    if (len < 9) { napi_throw_range_error(env, nullptr, "the SH frame has 9 entries"); return nullptr; }
+    int32_t follow = 0;
+    const int rc = gsr_get_sh_frame(c, (double*)m, &follow);
+    if (rc) return throw_gsr(env, c, rc, "gsr_get_sh_frame");
+    napi_value n;
+    napi_create_int32(env, follow, &n);
+    return n;
+}
+
+// readSceneSh(handle, Uint32Array r | null, Uint32Array g | null, Uint32Array b | null, Int32Array(3) bandsIndices) -> shCount
+napi_value ReadSceneSh(napi_env env, napi_callback_info info)
+{
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    void *t[3], *band;
+    size_t len[3], nb;
+    if (!c) return nullptr;
+    for (int k = 0; k < 3; k++)
+        if (!get_typed(env, argv[1 + k], napi_uint32_array, &t[k], &len[k], true)) return nullptr;
+    if (!get_typed(env, argv[4], napi_int32_array, &band, &nb)) return nullptr;
+    uint32_t count = 0;
+    int rc = gsr_read_scene_sh(c, nullptr, nullptr, nullptr, &count, nullptr);
+    if (!rc) {
+        if (nb < 3 || (t[0] && len[0] < (size_t)count * 8) || (t[1] && len[1] < (size_t)count * 8) || (t[2] && len[2] < (size_t)count * 8)) {
+            napi_throw_range_error(env, nullptr, "output arrays are smaller than the SH state");
+            return nullptr;
+        }
+        rc = gsr_read_scene_sh(c, (uint32_t*)t[0], (uint32_t*)t[1], (uint32_t*)t[2], &count, (int32_t*)band);
+    }
+    if (rc) return throw_gsr(env, c, rc, "gsr_read_scene_sh");
+    napi_value n;
+    napi_create_uint32(env, count, &n);
+    return n;
+}
+
 napi_value SetDepthFade(napi_env env, napi_callback_info info)
 {
     napi_value argv[3];
@@ -879,7 +950,7 @@ napi_value Pick(napi_env env, napi_callback_info info)
 napi_value Init(napi_env env, napi_value exports)
 {
     struct { const char* name; napi_callback fn; } fns[] = {
-        {"create", Create}, {"destroy", Destroy}, {"setScene", SetScene}, {"setSceneSh", SetSceneSh}, {"setDepthFade", SetDepthFade}, {"setSceneRows", SetSceneRows},
+        {"create", Create}, {"destroy", Destroy}, {"setScene", SetScene}, {"setSceneSh", SetSceneSh}, {"setShFollow", SetShFollow}, {"setShFrame", SetShFrame}, {"getShFrame", GetShFrame}, {"readSceneSh", ReadSceneSh}, {"setDepthFade", SetDepthFade}, {"setSceneRows", SetSceneRows},
         {"sceneTransform", SceneTransform}, {"readScene", ReadScene}, {"setSceneArrays", SetSceneArrays}, {"readSceneArrays", ReadSceneArrays}, {"resize", Resize}, {"setBand", SetBand},
         {"setCamera", SetCamera}, {"sort", Call0<gsr_sort>}, {"render", Call0<gsr_render>},
         {"renderAsync", Call0<gsr_render_async>}, {"sync", Call0<gsr_sync>}, {"resetTimings", Call0<gsr_reset_timings>},

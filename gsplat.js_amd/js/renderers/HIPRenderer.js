@@ -48,9 +48,13 @@ class HIPRenderer {
             hostOnly: false,             // the last upload could not carry rotations / scales: edits run in JavaScript and upload
             transform: (kind, f64) => (vertexCount = this._n.sceneTransform(this._h, kind, f64)),
             read: (out) => this._n.readSceneArrays(this._h, out.data, out.positions, out.rotations, out.scales),
+            // SH colour that follows the transforms (Scene.shFollowsTransforms): the context keeps frame and textures up itself
+            setShFollow: (on) => this._n.setShFollow(this._h, on ? 1 : 0),
+            readSh: (textures, band) => this._n.readSceneSh(this._h, textures ? textures[0] : null, textures ? textures[1] : null, textures ? textures[2] : null, band),
         };
         const upload = () => {   // initWebGL's scene part: worker init + texImage2D (WebGLRenderer.ts:105-110,185-195)
             const s = activeScene, n = s.vertexCount, positions = s.positions, rotations = s.rotations, scales = s.scales;
+            void s.shs_rgb;              // (SH mirrors of a followed limitBox are read back before the upload clears the context's SH state)
             vertexCount = n;
             // a Scene whose buffers were assigned one by one (Scene.ts:474-496) may carry no rotations or scales
             device.hostOnly = !(positions.length === 3 * n && rotations.length === 4 * n && scales.length === 3 * n);
@@ -191,7 +195,10 @@ class HIPRenderer {
             if (!activeScene || !activeScene.shHeight || activeScene.shDroppedOnDevice) return;
             const band = activeScene.bandsIndices;
             const t = activeScene.shs_rgb;
-            this._n.setSceneSh(this._h, t[0], t[1], t[2], activeScene.vertexCount - (band[0] + 1), band);
+            const count = activeScene.vertexCount - (band[0] + 1);
+            this._n.setSceneSh(this._h, t[0], t[1], t[2], count, band);
+            // a re-upload hands the frame back: the scene has kept it through its rotate / scale (gsr_set_scene_sh resets it)
+            if (count > 0 && activeScene.shFrame) this._n.setShFrame(this._h, activeScene.shFrame);
         };
 
         // ---- multi-GPU (one process per GPU): joinGroup() is collective -- every rank calls it with the same id

@@ -104,6 +104,7 @@ EXPORTS = [
     "gsr_set_hit_alpha", "gsr_depth_async", "gsr_read_depth", "gsr_depth_device_ptr", "gsr_pick",
     "gsr_set_scene_arrays",
     "gsr_comm_set_depth", "gsr_frame_depth_layout", "gsr_read_frame_depth", "gsr_frame_depth_device_ptr",
+    "gsr_set_sh_follow", "gsr_set_sh_frame", "gsr_get_sh_frame", "gsr_read_scene_sh",
 ]
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p)
 GSR_COMM_ID_BYTES = 128
@@ -230,6 +231,10 @@ def load_library(path=None):
     L.gsr_read_frame_depth.argtypes = [vp, vp, ctypes.c_uint64]
     L.gsr_frame_depth_device_ptr.argtypes = [vp]
     L.gsr_frame_depth_device_ptr.restype = vp
+    L.gsr_set_sh_follow.argtypes = [vp, ctypes.c_int32]
+    L.gsr_set_sh_frame.argtypes = [vp, vp]
+    L.gsr_get_sh_frame.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int32)]
+    L.gsr_read_scene_sh.argtypes = [vp, vp, vp, vp, ctypes.POINTER(ctypes.c_uint32), vp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int and name not in ("gsplat_sort_host",):
@@ -408,6 +413,38 @@ class HIPRenderer:
         out = np.empty((self._n, 4), dtype=np.float32)
         self._check(self._L.gsr_read_sh_colors(self._ctx, out.ctypes.data))
         return out
+
+    # -- SH colour that follows the scene's transforms (gsr_set_sh_follow) --
+    def set_sh_follow(self, on):
+        """While on, scene_rotate / scene_scale keep the SH frame up and scene_limit_box compacts the SH textures with the scene."""
+        self._check(self._L.gsr_set_sh_follow(self._ctx, 1 if on else 0))
+
+    def set_sh_frame(self, linv=None):
+        """The SH frame (3x3 row-major float64; None: the identity) of the SH state set_sh uploaded."""
+        if linv is None:
+            self._check(self._L.gsr_set_sh_frame(self._ctx, None))
+            return
+        m = np.ascontiguousarray(linv, dtype=np.float64).reshape(-1)
+        if m.size != 9:
+            raise ValueError("the SH frame is 3x3")
+        self._check(self._L.gsr_set_sh_frame(self._ctx, m.ctypes.data))
+
+    def sh_frame(self):
+        """(frame float64[3, 3], follow bool)"""
+        m = np.zeros(9, dtype=np.float64)
+        follow = ctypes.c_int32(0)
+        self._check(self._L.gsr_get_sh_frame(self._ctx, m.ctypes.data, ctypes.byref(follow)))
+        return m.reshape(3, 3), bool(follow.value)
+
+    def read_scene_sh(self):
+        """([sh_r, sh_g, sh_b] uint32[8 * sh_count] each, bandsIndices int32[3]) as the device holds them; sh_count 0: no SH state."""
+        count = ctypes.c_uint32(0)
+        band = np.zeros(3, dtype=np.int32)
+        self._check(self._L.gsr_read_scene_sh(self._ctx, None, None, None, ctypes.byref(count), band.ctypes.data))
+        tex = [np.zeros(8 * count.value, dtype=np.uint32) for _ in range(3)]
+        if count.value:
+            self._check(self._L.gsr_read_scene_sh(self._ctx, tex[0].ctypes.data, tex[1].ctypes.data, tex[2].ctypes.data, None, None))
+        return tex, band
 
     # -- on-device scene build and transforms (Scene.ts:58-366 as kernels) --
     def set_scene_rows(self, rows):

@@ -132,9 +132,27 @@ int gsr_scene_count(gsr_ctx *ctx, uint32_t *count); /* splats in the device scen
  * band_index = Scene.bandsIndices (uniform u_bandIndex, WebGLRenderer.ts:209-211): splat i > band_index[0] takes its
  * colour from eval_sh_rgb (vertex.glsl.ts:57-104,180-204) with degree 1/2/3 by band_index[1], band_index[2].
  * sh_count must be n - (band_index[0] + 1).  Call after gsr_set_scene (which clears any SH state); sh_count 0 clears.
- * gsr_scene_limit_box renumbers the splats and therefore also clears the SH state. */
+ * gsr_scene_limit_box renumbers the splats and therefore also clears the SH state (unless gsr_set_sh_follow is on, below). */
 int gsr_set_scene_sh(gsr_ctx *ctx, const uint32_t *sh_r, const uint32_t *sh_g, const uint32_t *sh_b, uint32_t sh_count,
                      const int32_t *band_index /* 3 */);
+/* SH colour that follows the scene through gsr_scene_rotate / _scale / _limit_box (opt-in; the reference's Scene never touches
+ * shs_rgb or bandsIndices, Scene.ts:197-366, so after a rotate its highlights stay where they were and after a limitBox its
+ * textures belong to other splats).  An SH state carries a frame: linv, 3x3 row-major f64, the inverse of the linear part of
+ * every rotate / scale since the coefficients were supplied; gsr_set_scene* and gsr_set_scene_sh reset it to the identity.
+ * While follow is on and an SH state exists, gsr_scene_rotate(q) makes it linv . R(q)^T, gsr_scene_scale(s) linv . diag(1/sx, 1/sy, 1/sz) (a component
+ * that is 0 or not finite: GSR_ERR_ARG, nothing changed), and gsr_scene_limit_box compacts the SH textures with the scene:
+ * the rows of the kept SH splats in order, band_index'[k] = (kept splats with index <= band_index[k]) - 1, and the SH state
+ * cleared when no SH splat is kept.  A frame that is not the identity makes the projection evaluate eval_sh_rgb for
+ * normalize(linv . (p - camera)) in f32 -- the direction the scene as supplied would have been seen from; the identity costs
+ * nothing and yields the bits it always did.  on: default 0; legal at any time; does not alter the frame. */
+int gsr_set_sh_follow(gsr_ctx *ctx, int32_t on);
+/* Hand a frame to the SH state, for a host that keeps it itself and re-uploads (linv: 9, row-major; NULL = the identity).  Call
+ * after gsr_set_scene_sh; GSR_ERR_ARG when there is no SH state or an entry is not finite (nothing changed). */
+int gsr_set_sh_frame(gsr_ctx *ctx, const double *linv /* 9 */);
+int gsr_get_sh_frame(gsr_ctx *ctx, double *linv /* 9 */, int32_t *follow); /* either may be NULL; no copy, no wait */
+/* The SH state as the device holds it (after a followed gsr_scene_limit_box: the compacted one).  The textures take 8 * sh_count
+ * words each and may be NULL; sh_count 0 and band_index -1, -1, -1: no SH state. */
+int gsr_read_scene_sh(gsr_ctx *ctx, uint32_t *sh_r, uint32_t *sh_g, uint32_t *sh_b, uint32_t *sh_count, int32_t *band_index /* 3 */);
 
 /* ---- per resize / per frame ---- */
 int gsr_resize(gsr_ctx *ctx, int32_t width, int32_t height);
