@@ -105,6 +105,9 @@ int gsr_create(gsr_ctx** out, const gsr_options* opt)
     if (!(o.early_out_eps >= 0.0f && o.early_out_eps < 1.0f)) return fail(nullptr, GSR_ERR_ARG, "early_out_eps must be in [0,1)");
     gsr_ctx* c = new gsr_ctx();
     c->device = o.device;
+    c->scene = new SharedScene();
+    c->scene->members.push_back(c);
+    c->scene_gen = c->scene->generation;
     c->opt = o;
     c->knobs = knobs;
     c->graph.enabled = c->knobs.graphs;
@@ -163,6 +166,8 @@ int gsr_destroy(gsr_ctx* c)
     comm_release(c);
     delivery_free(c);
     drop_graph(c);
+    scene_release(c);   // (the last member of a scene frees it; the others keep rendering it)
+    if (c->share_ev) (void)hipEventDestroy(c->share_ev);
     for (auto& set : c->timing.evring)
         for (auto& e : set) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->link_ev) if (e) (void)hipEventDestroy(e);
@@ -305,7 +310,7 @@ int gsr_reset_timings(gsr_ctx* c)
     const uint64_t v = tm.visible, b = tm.bin_entries, d = tm.tile_entries;
     tm = gsr_timings{};
     HIP_TRY(c, hipMemsetAsync(c->words.accum, 0, 4 * sizeof(uint64_t), c->stream));
-    tm.visible = v; tm.bin_entries = b; tm.tile_entries = d; tm.n = c->n;
+    tm.visible = v; tm.bin_entries = b; tm.tile_entries = d; tm.n = c->scene->n;
     c->timing.frame_no = 0;  // the sampling restarts: the next frame carries the stage events
     return GSR_OK;
 }
@@ -347,10 +352,10 @@ void gsplat_sort_host(const float* viewProj, uint32_t vertexCount, const float* 
     }
     gsr_ctx* c = ctx;
     if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return failed("device unavailable");
-    if (vertexCount != c->n || !c->scene.arr.px) {
+    if (vertexCount != c->scene->n || !c->scene->arr.px) {
         if (vertexCount > 0x7fffffffu / 8) return failed("too many splats");
         if (alloc_scene(c, vertexCount, false) != GSR_OK) return failed(gsr_last_error(c));
-        c->n = vertexCount;
+        c->scene->n = vertexCount;
     }
     c->have_sort = false; c->have_frame = false;
     // What the call keeps between calls is memory of its own, never the caller's data: the device staging buffer for the
@@ -365,7 +370,7 @@ void gsplat_sort_host(const float* viewProj, uint32_t vertexCount, const float* 
             if (stage_pos.alloc(c, (size_t)vertexCount * 3) != GSR_OK) { stage_cap = 0; return failed(gsr_last_error(c)); }
             stage_cap = (size_t)vertexCount * 3;
         }
-        const gsr::SceneArrays& sa = c->scene.arr;
+        const gsr::SceneArrays& sa = c->scene->arr;
         hipError_t e1 = hipMemcpyAsync(stage_pos, fBuffer, (size_t)vertexCount * 12, hipMemcpyHostToDevice, c->stream);
         launch_repack_positions(stage_pos, vertexCount, sa.px, sa.py, sa.pz, c->stream);
         for (hipError_t e : {e1, hipGetLastError()})

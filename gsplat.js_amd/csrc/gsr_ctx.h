@@ -112,6 +112,50 @@ struct SceneArrays {
     SceneDev view() const { return SceneDev{px, py, pz, cov0, cov1, cov2, rgba, rot, scl}; }
 };
 
+// The scene state its members hold once (DESIGN.md section 2, and section 4 "Shared scenes"): the per-splat arrays, the SH textures and their spare set, the SH
+// frame and the splat count.  It owns these buffers; the contexts that render it are listed in `members` (no leader: the last one
+// to go frees it).  Everything a frame writes, `shcol` included, stays with the context.
+struct SharedScene {
+    SceneArrays arr;
+    uint32_t n = 0;                   // splats of the scene
+    uint32_t arr_rows = 0;            // rows the arrays were allocated for (gsr_scene_limit_box lowers n, not this)
+    bool have_rows = false;
+    bool given = false;               // a gsr_set_scene* call has supplied a scene (of any count, 0 included)
+    std::vector<gsr_ctx*> members;
+    // moves whenever the arrays, the count or the SH textures are replaced: a member whose scene_gen differs re-sizes its per-splat
+    // buffers where its next frame is enqueued (adopt_scene)
+    uint64_t generation = 1;
+    // spherical harmonics (optional)
+    DevBuf<uint32_t> sh_r, sh_g, sh_b;
+    uint32_t sh_count = 0;
+    int32_t band[3] = {-1, -1, -1};
+    SceneSoA soa(float4* shcol) const { return SceneSoA{arr.px, arr.py, arr.pz, arr.cov0, arr.cov1, arr.cov2, arr.rgba, sh_r, sh_g, sh_b, shcol}; }
+    // The SH frame: the inverse of the linear part of every rotate / scale since the coefficients were
+    // supplied, row-major; the projection takes SH directions through it.  Kept up by gsr_scene_rotate / _scale while sh_follow
+    // is set; the identity takes the projection's frameless path.
+    bool sh_follow = false;
+    // the other set of SH textures a followed gsr_scene_limit_box compacts into (then the two sets change places): allocated by
+    // the first such call, kept until the SH state goes; sh_rows / sh_spare_rows: the rows each set was allocated for
+    DevBuf<uint32_t> sh_spare[3];
+    uint32_t sh_rows = 0, sh_spare_rows = 0;
+    double sh_frame[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    void reset_sh_frame() { for (int k = 0; k < 9; k++) sh_frame[k] = (k % 4 == 0) ? 1.0 : 0.0; }
+    bool sh_frame_is_identity() const
+    {
+        for (int k = 0; k < 9; k++) if (sh_frame[k] != ((k % 4 == 0) ? 1.0 : 0.0)) return false;
+        return true;
+    }
+    // (the members' evaluated colours, shcol, go with it: the caller resets its own, the other members' go in adopt_scene)
+    void drop_sh() { sh_count = 0; band[0] = band[1] = band[2] = -1; sh_r.reset(); sh_g.reset(); sh_b.reset(); reset_sh_frame();
+                     for (auto& b : sh_spare) b.reset();
+                     sh_rows = sh_spare_rows = 0; }
+    // device bytes of the state the members hold once
+    uint64_t bytes() const
+    {
+        return (uint64_t)arr_rows * (7 * 4 + (arr.rot ? 32 : 0)) + ((uint64_t)sh_rows + sh_spare_rows) * 3 * 32;
+    }
+};
+
 // k_project_key's arguments but the splat count and the camera (ProjectLaunch without what changes from frame to frame)
 struct ProjectArgs {
     SceneSoA sc;
@@ -148,7 +192,6 @@ struct gsr_ctx {
     gsr::Knobs knobs;
     int W = 0, H = 0;
     int band_x0 = 0, band_x1 = 0;
-    uint32_t n = 0;                   // splats of the scene
     gsr::CamParams cam{};
     gsr::CamParams cam_frame{};       // the camera of the last rendered frame
     bool have_cam = false, have_frame = false, have_sort = false;
@@ -156,34 +199,13 @@ struct gsr_ctx {
     bool frame_lists = false;         // the last render frame's bin lists are still what the bin buffers hold (alloc_bins drops it)
     hipEvent_t link_ev[2] = {nullptr, nullptr};  // gsr_stream_order
 
-    struct Scene {   // gsr_scene.cpp
-        gsr::SceneArrays arr;
-        bool have_rows = false;
-        // spherical harmonics (optional)
-        gsr::DevBuf<uint32_t> sh_r, sh_g, sh_b;
-        gsr::DevBuf<float4> shcol;
-        uint32_t sh_count = 0;
-        int32_t band[3] = {-1, -1, -1};
-        gsr::SceneSoA soa() const { return gsr::SceneSoA{arr.px, arr.py, arr.pz, arr.cov0, arr.cov1, arr.cov2, arr.rgba, sh_r, sh_g, sh_b, shcol}; }
-        // The SH frame: the inverse of the linear part of every rotate / scale since the coefficients were
-        // supplied, row-major; the projection takes SH directions through it.  Kept up by gsr_scene_rotate / _scale while sh_follow
-        // is set; the identity takes the projection's frameless path.
-        bool sh_follow = false;
-        // the other set of SH textures a followed gsr_scene_limit_box compacts into (then the two sets change places): allocated by
-        // the first such call, kept until the SH state goes; sh_rows / sh_spare_rows: the rows each set was allocated for
-        gsr::DevBuf<uint32_t> sh_spare[3];
-        uint32_t sh_rows = 0, sh_spare_rows = 0;
-        double sh_frame[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        void reset_sh_frame() { for (int k = 0; k < 9; k++) sh_frame[k] = (k % 4 == 0) ? 1.0 : 0.0; }
-        bool sh_frame_is_identity() const
-        {
-            for (int k = 0; k < 9; k++) if (sh_frame[k] != ((k % 4 == 0) ? 1.0 : 0.0)) return false;
-            return true;
-        }
-        void drop_sh() { sh_count = 0; band[0] = band[1] = band[2] = -1; sh_r.reset(); sh_g.reset(); sh_b.reset(); shcol.reset(); reset_sh_frame();
-                         for (auto& b : sh_spare) b.reset();
-                         sh_rows = sh_spare_rows = 0; }
-    } scene;
+    // The scene the context renders (gsr_scene.cpp): never null.  A context is the only member of its scene until gsr_share_scene
+    // makes it a member of another context's; `scene_gen` is the scene's generation this context's per-splat buffers were last sized for.
+    gsr::SharedScene* scene = nullptr;
+    uint64_t scene_gen = 0;
+    gsr::DevBuf<float4> shcol;        // the SH colours the projection evaluates for this context's camera (one per splat, while the scene has SH)
+    hipEvent_t share_ev = nullptr;    // orders this context's stream against the other members' around an edit (created by the first share)
+    gsr::SceneSoA scene_soa() const { return scene->soa(shcol); }
 
     struct Sort {    // per splat and frame: what the projection writes and the sort permutes; sized by alloc_scene
         gsr::DevBuf<int32_t> depth;
@@ -197,6 +219,7 @@ struct gsr_ctx {
         gsr::DevBuf<uint32_t> rect_tmp;    // the rectangles between the two LSD passes (rect_carry)
         gsr::DevBuf<uint32_t> chunk_tab;   // bucket order: k_local_sort's work list
         uint32_t blocks = 0, kpb = 0;
+        uint32_t rows = 0;                 // splats the buffers above were allocated for
         int parity = 0;                    // which of the two sort-only slot sets the next sort-only frame uses
         bool culled = false;               // the last sort kept only the band's survivors (depth_index / keys are partial)
     } sort;
@@ -382,6 +405,10 @@ int sync_and_repair(gsr_ctx* c);
 void drop_graph(gsr_ctx* c);
 // gsr_scene.cpp
 int alloc_scene(gsr_ctx* c, uint32_t n, bool with_rows);
+// the context's per-splat buffers follow a scene another member replaced (nothing to do while scene_gen is the scene's generation)
+int adopt_scene(gsr_ctx* c);
+// the context leaves its scene (the last member frees it); c->scene is null afterwards
+void scene_release(gsr_ctx* c);
 // gsr_comm.cpp
 void comm_release(gsr_ctx* c);
 // gsr_depth.cpp: a depth ring's pass for the frame enqueued last.  check: what gsr_depth_async demands of the frame (GSR_ERR_ARG, nothing

@@ -33,12 +33,12 @@ DepthBuffers buffers(gsr_ctx* c, uint32_t* invalid, float* mean, float* hit, uin
     b.bin_start = c->bin.start;
     b.list = c->bin.list;
     b.rec = c->sort.rec;
-    b.px = c->scene.arr.px; b.py = c->scene.arr.py; b.pz = c->scene.arr.pz;
+    b.px = c->scene->arr.px; b.py = c->scene->arr.py; b.pz = c->scene->arr.pz;
     b.overflow = &c->words.fstate->overflow;
     b.invalid = invalid;
     b.mean = mean; b.hit = hit; b.index = index;
     b.capacity = c->bin.capacity;
-    b.nsplats = std::max(c->n, 1u);
+    b.nsplats = std::max(c->scene->n, 1u);
     b.hit_alpha = c->depth.hit_alpha;
     return b;
 }

@@ -67,7 +67,7 @@ constexpr uint32_t LONG_TILES_X2_THROUGHPUT = 6;   // with frames in flight: 3 (
 inline bool use_bucket_order(const gsr_ctx* c)
 {
     if (c->knobs.sort_order >= 0) return c->knobs.sort_order == 1;
-    if (c->n > BUCKET_ORDER_MAX_N) return false;
+    if (c->scene->n > BUCKET_ORDER_MAX_N) return false;
     const uint32_t largest = reinterpret_cast<volatile const uint32_t*>(c->words.mailbox)[2];   // low half of mailbox[1]
     return largest <= LOCAL_BUCKET_LIMIT;   // 0xffffffff until a frame of this scene has reported
 }
@@ -86,18 +86,18 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
     const bool cull = render && band_is_partial(g);
     FrameState* fs = c->words.fstate;
     a.render = render;
-    a.n = c->n;
+    a.n = c->scene->n;
     a.grid = g;
     a.early_out_eps = c->opt.early_out_eps;
     a.front_waves = front_waves_of(c);   // (the launchers keep the wide forms off the one-level 1080p chain)
-    a.sort_culled = cull && c->n;   // (an empty frame sorts nothing, so nothing of it is partial)
+    a.sort_culled = cull && c->scene->n;   // (an empty frame sorts nothing, so nothing of it is partial)
 
     // a sort-only frame has its own slots (sets 1 and 2 in turn; set 0 belongs to the render frames and k_begin_frame)
     const size_t slot_set = (size_t)FRAME_SLOTS * FRAME_SLOT_WORDS;
     int32_t* slots_now = render ? c->words.slots.p : c->words.slots + (size_t)(1 + c->sort.parity) * slot_set;
     a.slots_next = render ? nullptr : c->words.slots + (size_t)(2 - c->sort.parity) * slot_set;
 
-    a.proj.sc = c->scene.soa();
+    a.proj.sc = c->scene_soa();
     a.proj.depth = c->sort.depth;
     a.proj.slots = slots_now;
     if (render) {
@@ -140,7 +140,7 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
     bb.slots = c->words.slots;
     bb.rect_idx = c->sort.rect_idx;
     bb.rects = c->sort.rects;
-    bb.rects_sorted = (c->n && sb.rects_out) ? 1u : 0u;
+    bb.rects_sorted = (c->scene->n && sb.rects_out) ? 1u : 0u;
     bb.bin_total = c->bin.total;
     bb.bin_start = c->bin.start;
     bb.bin_start_pre = c->bin.start_pre;
@@ -179,7 +179,7 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
     bb.cell_wcnt = c->bin.cell_wcnt;
     bb.cell_table2 = c->bin.cell_table2;
     bb.band = band_is_partial(g) ? 1u : 0u;
-    bb.n_max = c->n;
+    bb.n_max = c->scene->n;
 
     BlendBuffers& bl = a.blend;
     bl.items = c->bin.items;
@@ -188,7 +188,7 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
     bl.list = c->bin.list;
     bl.rec = c->sort.rec;
     bl.bbox = nullptr;   // (nothing on the frame path reads the pixel boxes)
-    bl.shcol = c->scene.shcol;
+    bl.shcol = c->shcol;
     bl.fb = c->out.fb;
     bl.partial = c->bin.partial;
     bl.queue = &fs->queue;
@@ -196,7 +196,7 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
     bl.seg_len_dev = &fs->seg_len;
     bl.grid = queue_start;
     bl.capacity = c->bin.capacity;
-    bl.nsplats = std::max(c->n, 1u);
+    bl.nsplats = std::max(c->scene->n, 1u);
     bl.bin_mask = c->bin.mask;
     bl.saturate = c->knobs.saturate ? 1u : 0u;
     bl.sub = c->bin.blend_sub;
@@ -309,7 +309,7 @@ int check_frame_words(gsr_ctx* c, bool* overflowed)
     tm.visible = host->visible;
     tm.tile_entries = host->tile_entries;
     tm.bin_entries = (uint32_t)host->report[5];
-    tm.n = c->n;
+    tm.n = c->scene->n;
     *overflowed = host->overflow != 0;
     return GSR_OK;
 }
@@ -351,8 +351,8 @@ int alloc_bins(gsr_ctx* c)
     const Knobs& k = c->knobs;
     const BinGrid g = make_grid(c);
     // the binning's form, grids and table shape for this grid, scene and list (plan_bins, k_bin.hip): the buffers follow it
-    const uint64_t capacity = b.capacity ? b.capacity : std::max<uint64_t>(6ull * c->n + (1u << 20), 1u << 22);   // (a new scene's list, allocated below)
-    b.plan = plan_bins(g, c->n, capacity, c->cu_count, front_waves_of(c), BinKnobs{k.bin_two_level, k.bin_big, k.bin_rounds, k.cell_grid});
+    const uint64_t capacity = b.capacity ? b.capacity : std::max<uint64_t>(6ull * c->scene->n + (1u << 20), 1u << 22);   // (a new scene's list, allocated below)
+    b.plan = plan_bins(g, c->scene->n, capacity, c->cu_count, front_waves_of(c), BinKnobs{k.bin_two_level, k.bin_big, k.bin_rounds, k.cell_grid});
     const BinPlan& p = b.plan;
     const uint32_t nbins = (uint32_t)p.nbins;
     const size_t table = (size_t)p.table_rows * p.table_cols;
@@ -436,6 +436,7 @@ int enqueue_frame(gsr_ctx* c, bool render)
     if (!c->have_cam) return fail(c, GSR_ERR_ARG, "gsr_set_camera has not been called");
     if (render && (!c->W || !c->H)) return fail(c, GSR_ERR_ARG, "framebuffer size is 0");
     hipStream_t s = c->stream;
+    if (int r = adopt_scene(c)) return r;   // (the scene was replaced through another member: this context's buffers follow)
     if (render && overflow_pending(c)) {
         // an earlier asynchronous frame did not fit: regrow before this one is enqueued.  The frames that overflowed
         // are lost (later frames were already behind them); gsr_sync reports how many.
@@ -459,12 +460,12 @@ int enqueue_frame(gsr_ctx* c, bool render)
     c->cam.W = c->W; c->cam.H = c->H;
     c->cam.band_px0 = a.grid.bx_lo * BIN_PX;
     c->cam.band_px1 = a.grid.bx_hi * BIN_PX;
-    c->cam.sh_on = c->scene.sh_count ? 1 : 0;
-    c->cam.band[0] = c->scene.band[0]; c->cam.band[1] = c->scene.band[1]; c->cam.band[2] = c->scene.band[2];
+    c->cam.sh_on = c->scene->sh_count ? 1 : 0;
+    c->cam.band[0] = c->scene->band[0]; c->cam.band[1] = c->scene->band[1]; c->cam.band[2] = c->scene->band[2];
     // the SH frame travels in the camera block: the one argument a graph replay rewrites, so a changed frame reaches the
     // projection like a changed camera.  The identity (every context that never opted in) takes the frameless path.
-    c->cam.sh_frame = (c->scene.sh_count && !c->scene.sh_frame_is_identity()) ? 1 : 0;
-    for (int k = 0; k < 9; k++) c->cam.shm[k] = c->cam.sh_frame ? (float)c->scene.sh_frame[k] : 0.0f;
+    c->cam.sh_frame = (c->scene->sh_count && !c->scene->sh_frame_is_identity()) ? 1 : 0;
+    for (int k = 0; k < 9; k++) c->cam.shm[k] = c->cam.sh_frame ? (float)c->scene->sh_frame[k] : 0.0f;
     if (render) c->cam_frame = c->cam;   // (gsr_read_records projects once more for this camera to get the pixel boxes)
     // No kernel in front of the frame: the camera is an argument of the projection kernel (k_project_key; k_depth_key in a
     // sort-only frame), the frame slots are left clean by their last reader, the frame words are stored, not accumulated

@@ -17,7 +17,7 @@ int gsr_read_depth_index(gsr_ctx* c, uint32_t* out)
         if (int r = enqueue_frame(c, false)) return r;
         if (int r = finish_frame(c)) return r;
     }
-    HIP_TRY(c, hipMemcpyAsync(out, c->sort.depth_index, (size_t)c->n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out, c->sort.depth_index, (size_t)c->scene->n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return GSR_OK;
 }
@@ -51,7 +51,7 @@ int gsr_read_keys(gsr_ctx* c, uint32_t* keys, int32_t* minmax)
         if (int r = enqueue_frame(c, false)) return r;
         if (int r = finish_frame(c)) return r;
     }
-    if (keys) HIP_TRY(c, hipMemcpyAsync(keys, c->sort.keys, (size_t)c->n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (keys) HIP_TRY(c, hipMemcpyAsync(keys, c->sort.keys, (size_t)c->scene->n * 4, hipMemcpyDeviceToHost, c->stream));
     if (minmax) HIP_TRY(c, hipMemcpyAsync(minmax, c->words.fstate->minmax, 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return GSR_OK;
@@ -62,28 +62,28 @@ int gsr_read_records(gsr_ctx* c, float* rec, int32_t* bbox)
     if (!c) return GSR_ERR_ARG;
     if (!c->have_frame) return fail(c, GSR_ERR_ARG, "no frame has been rendered yet");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (rec) HIP_TRY(c, hipMemcpyAsync(rec, c->sort.rec, (size_t)c->n * 32, hipMemcpyDeviceToHost, c->stream));
+    if (rec) HIP_TRY(c, hipMemcpyAsync(rec, c->sort.rec, (size_t)c->scene->n * 32, hipMemcpyDeviceToHost, c->stream));
     std::vector<uint2> tmp;
     if (bbox) {
         // the pixel boxes are not part of a frame (no kernel reads them): project once more for the frame's camera, records and
         // boxes only (k_project_key, do_project == 2: the same arithmetic, so the same records)
-        tmp.resize(c->n);
-        if (c->n) {
+        tmp.resize(c->scene->n);
+        if (c->scene->n) {
             DevBuf<uint2> boxes;
-            if (int r = boxes.alloc(c, c->n)) return r;
+            if (int r = boxes.alloc(c, c->scene->n)) return r;
             ProjectLaunch again{};   // (kept / kept_lane null: no packing)
-            again.sc = c->scene.soa(); again.n = c->n; again.cam = c->cam_frame; again.do_project = 2;
+            again.sc = c->scene_soa(); again.n = c->scene->n; again.cam = c->cam_frame; again.do_project = 2;
             again.depth = c->sort.depth; again.slots = c->words.slots; again.rec = c->sort.rec; again.bbox = boxes;
             again.rect = c->sort.rect_idx; again.overflow = &c->words.fstate->overflow;
             launch_project_key(again, c->stream);
             HIP_TRY(c, hipGetLastError());
-            HIP_TRY(c, hipMemcpyAsync(tmp.data(), boxes, (size_t)c->n * 8, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(tmp.data(), boxes, (size_t)c->scene->n * 8, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(c, hipStreamSynchronize(c->stream));
         }
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (bbox)
-        for (uint32_t i = 0; i < c->n; i++) {
+        for (uint32_t i = 0; i < c->scene->n; i++) {
             bbox[4 * (size_t)i + 0] = (int32_t)(tmp[i].x & 0xffff);
             bbox[4 * (size_t)i + 1] = (int32_t)(tmp[i].y & 0xffff);
             bbox[4 * (size_t)i + 2] = (int32_t)(tmp[i].x >> 16);
@@ -95,9 +95,9 @@ int gsr_read_records(gsr_ctx* c, float* rec, int32_t* bbox)
 int gsr_read_sh_colors(gsr_ctx* c, float* rgba)
 {
     if (!c || !rgba) return c ? fail(c, GSR_ERR_ARG, "out is NULL") : GSR_ERR_ARG;
-    if (!c->have_frame || !c->scene.sh_count) return fail(c, GSR_ERR_ARG, "no frame rendered with SH colours yet");
+    if (!c->have_frame || !c->scene->sh_count) return fail(c, GSR_ERR_ARG, "no frame rendered with SH colours yet");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(rgba, c->scene.shcol, (size_t)c->n * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(rgba, c->shcol, (size_t)c->scene->n * 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return GSR_OK;
 }

@@ -10,7 +10,9 @@
 // scales}), hostOnly } -- instead of the loops below, nothing is uploaded, and the four arrays become mirrors that are
 // refreshed from the first device scene the next time they are read.  The Scene knows nothing else of a renderer, so
 // the protocol runs against a stub as well (tests/test_scene_binding.py).  DESIGN.md section 4, "Scene transforms on
-// the device".
+// the device".  Device scenes that carry the same `share` token (an object identity; renderers whose contexts share one
+// device copy, gsr_share_scene) are one scene: an edit or an option is issued once per distinct token, through the
+// first of them in attach order; a device scene without a token counts singly.
 const { EventDispatcher } = require("./EventDispatcher");
 const { Matrix3 } = require("../math/Matrix3");
 const { Quaternion } = require("../math/Quaternion");
@@ -61,6 +63,18 @@ class Scene extends EventDispatcher {
         this._devices.push(dev);
         if (dev.setShFollow) dev.setShFollow(this._shFollowsTransforms);
     }
+    // one device scene per distinct device copy, in attach order
+    _distinctDevices() {
+        const seen = new Set();
+        return this._devices.filter((d) => {
+            if (!d.share) return true;
+            if (seen.has(d.share)) return false;
+            seen.add(d.share);
+            return true;
+        });
+    }
+    // (for the renderers) false while a plain setter has replaced a buffer and no "change" has made the attached renderers upload it yet
+    get _devicesCurrent() { return !this._diverged; }
     // The last device scene to go hands its edits back first, so the scene never loses one.
     detachDevice(dev) {
         const k = this._devices.indexOf(dev);
@@ -104,7 +118,7 @@ class Scene extends EventDispatcher {
     get shFollowsTransforms() { return this._shFollowsTransforms; }
     set shFollowsTransforms(on) {
         this._shFollowsTransforms = !!on;
-        for (const d of this._devices) if (d.setShFollow) d.setShFollow(this._shFollowsTransforms);
+        for (const d of this._distinctDevices()) if (d.setShFollow) d.setShFollow(this._shFollowsTransforms);
     }
     get shFrame() { return this._shFrame; }
 
@@ -137,7 +151,7 @@ class Scene extends EventDispatcher {
         }
         const f = new Float64Array(args);
         let count = -1;
-        for (const d of this._devices) {
+        for (const d of this._distinctDevices()) {
             const c = d.transform(kind, f);
             if (count >= 0 && c !== count) throw new Error("device scenes disagree on vertexCount (" + count + " and " + c + ")");
             count = c;

@@ -48,6 +48,10 @@ export interface SceneEvent { type: string }
 /** What a renderer hands a Scene while the Scene is its active scene: the Scene's transforms run through it instead of the
  *  JavaScript loops, and the Scene reads its arrays back through it when they are next asked for. */
 export interface DeviceScene {
+    /** optional: an object identity that is equal for device scenes that are one device copy (renderers whose contexts share a
+     *  scene).  The Scene issues every edit and option once per distinct token, through the first such device scene in attach
+     *  order; without a token a device scene counts singly. */
+    readonly share?: object | null;
     /** the last upload carried no rotations / scales: the Scene's edits run in JavaScript and are uploaded again */
     hostOnly: boolean;
     /** kind 0 translate (x, y, z), 1 rotate (x, y, z, w), 2 scale (x, y, z), 3 limitBox (xMin, xMax, yMin, yMax, zMin, zMax); returns vertexCount */
@@ -123,6 +127,10 @@ export interface HIPRendererOptions {
     timing?: boolean;
     /** several renderers keep frames in flight on one device (GSR_FLAG_THROUGHPUT): longer compositor work items */
     throughput?: boolean;
+    /** another renderer of the same device: when render / renderAsync attaches a Scene that renderer has attached (its device copy
+     *  current), this one shares that device copy (gsr_share_scene) instead of uploading the scene again.  A "change" that makes the
+     *  renderers upload (setData, a buffer assigned by hand) is uploaded once, by that renderer, and shared again by this one. */
+    shareSceneWith?: HIPRenderer;
 }
 export interface FrameStats {
     msProjectKey: number; msSort: number; msBin: number; msBlend: number; msCombine: number; msTotal: number;
@@ -219,6 +227,11 @@ export class HIPRenderer {
     sceneLimitBox(xMin: number, xMax: number, yMin: number, yMax: number, zMin: number, zMax: number): void;
     readSceneData(): { data: Uint32Array; positions: Float32Array; vertexCount: number };
     renderDeviceScene(camera: Camera): void;
+    /** give up this renderer's scene and render `other`'s device scene from now on: nothing is copied or uploaded; edits through
+     *  either renderer (or the Scene) change the one copy.  setSceneRows, or a Scene that is uploaded, takes the renderer out again. */
+    shareScene(other: HIPRenderer): void;
+    /** renderers that render this renderer's device scene (1: not shared) and the device bytes they hold once */
+    sceneSharing(): { members: number; sceneBytes: number };
     dispose(): void;
     /** RGBA8, row 0 = top, round(clamp(x,0,1)*255), premultiplied alpha */
     /** RGBA8, row 0 = top; pass an array of width*height*4 elements to have it filled and returned (no allocation per frame). */

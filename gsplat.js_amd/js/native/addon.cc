@@ -555,6 +555,43 @@ napi_value CommShare(napi_env env, napi_callback_info info)
     return rc ? throw_gsr(env, c, rc, "gsr_comm_share") : undefined(env);
 }
 
+// shareScene(handle, fromHandle) -> vertexCount: gsr_share_scene, then the shared scene's count
+napi_value ShareScene(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    gsr_ctx* from = get_ctx(env, argv[1]);
+    if (!c || !from) return nullptr;
+    const int rc = gsr_share_scene(c, from);
+    if (rc) return throw_gsr(env, c, rc, "gsr_share_scene");
+    uint32_t count = 0;
+    gsr_scene_count(c, &count);
+    napi_value n;
+    napi_create_uint32(env, count, &n);
+    return n;
+}
+
+// sceneSharing(handle) -> { members, sceneBytes }
+napi_value SceneSharing(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    if (!c) return nullptr;
+    int32_t members = 0;
+    uint64_t bytes = 0;
+    const int rc = gsr_scene_sharing(c, &members, &bytes);
+    if (rc) return throw_gsr(env, c, rc, "gsr_scene_sharing");
+    napi_value o, m, b;
+    napi_create_object(env, &o);
+    napi_create_int32(env, members, &m);
+    napi_create_double(env, (double)bytes, &b);
+    napi_set_named_property(env, o, "members", m);
+    napi_set_named_property(env, o, "sceneBytes", b);
+    return o;
+}
+
 // readFrame(handle, Uint8Array out, width, height): the gathered RGBA8 frame
 napi_value ReadFrame(napi_env env, napi_callback_info info)
 {
@@ -964,6 +1001,7 @@ napi_value Init(napi_env env, napi_value exports)
         {"commSetDepth", CommSetDepth}, {"frameDepthLayout", FrameDepthLayout}, {"readFrameDepth", ReadFrameDepth},
         {"deliverFrame", DeliverFrame}, {"frameReady", FrameReady}, {"acquireFrame", AcquireFrame}, {"releaseFrame", ReleaseFrame},
         {"setHitAlpha", SetHitAlpha}, {"depthAsync", Call0<gsr_depth_async>}, {"readDepth", ReadDepth}, {"pick", Pick},
+        {"shareScene", ShareScene}, {"sceneSharing", SceneSharing},
     };
     for (auto& f : fns) {
         napi_value fn;

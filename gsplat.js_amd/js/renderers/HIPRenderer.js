@@ -28,6 +28,7 @@ class HIPRenderer {
     //   canvasLike: anything with numeric width/height (stands in for the HTMLCanvasElement of WebGLRenderer.ts:23)
     //   options: { width, height, device, earlyOutEps, band: [x0, x1], timing, throughput }
     //   (throughput: several renderers keep frames in flight on one device; see GSR_FLAG_THROUGHPUT)
+    //   (shareSceneWith: another HIPRenderer of the same device; a Scene that one has attached is shared with it, not uploaded again)
     constructor(target, optionalShaderPasses) {
         const o = target || {};
         this._n = loadNative();
@@ -44,7 +45,12 @@ class HIPRenderer {
         // While a Scene is this renderer's active scene, the renderer is one of its device scenes (Scene.attachDevice): the
         // Scene's transforms run here as kernels on this context's stream, behind whatever frames it has in flight, and the
         // Scene reads its arrays back from here when somebody asks for them.  DESIGN.md section 4, "Scene transforms on the device".
+        // Shared scenes (gsr_share_scene): renderers whose contexts render one device copy carry the same token, and the Scene
+        // issues an edit once per token.  null: this renderer's scene is its own.
+        this._shareToken = null;
+        const self = this;
         const device = {
+            get share() { return self._shareToken; },
             hostOnly: false,             // the last upload could not carry rotations / scales: edits run in JavaScript and upload
             transform: (kind, f64) => (vertexCount = this._n.sceneTransform(this._h, kind, f64)),
             read: (out) => this._n.readSceneArrays(this._h, out.data, out.positions, out.rotations, out.scales),
@@ -60,15 +66,44 @@ class HIPRenderer {
             device.hostOnly = !(positions.length === 3 * n && rotations.length === 4 * n && scales.length === 3 * n);
             if (device.hostOnly) this._n.setScene(this._h, s.data, positions, n);
             else this._n.setSceneArrays(this._h, s.data, positions, rotations, scales, n);
+            this._shareToken = null;     // (an upload takes the context out of a share: the scene is its own again)
             this.setShTextures();
             for (const p of passes) p.init(this, null);
             initialized = true;
         };
-        const onSceneChange = () => {           // WebGLRenderer.ts:234-239
-            if (!activeScene.deviceEditApplied) return upload();
+        const onSceneChange = (e) => {          // WebGLRenderer.ts:234-239
+            if (!activeScene.deviceEditApplied) {
+                // the re-upload is made once per device copy too: the renderer named in shareSceneWith uploads, this one shares again
+                if (shareAttached(e)) return;
+                upload();
+                uploadedFor = e;
+                return;
+            }
             vertexCount = activeScene.vertexCount;   // the edit ran here already: nothing to upload; the passes start over as after an upload
             for (const p of passes) p.init(this, null);
         };
+        // { shareSceneWith: other }: a Scene `other` has attached, with its device copy current, is shared instead of uploaded
+        const shareFrom = (other) => {
+            vertexCount = this._n.shareScene(this._h, other._h);
+            this._shareToken = other._shareToken || (other._shareToken = {});
+        };
+        // `forEvent`: inside a "change" that makes the renderers upload -- then only behind `other`'s upload for this very event
+        // (whichever order the listeners run in, this renderer never shares a copy that is about to be replaced)
+        let uploadedFor = null;
+        const shareAttached = (forEvent) => {
+            const other = o.shareSceneWith;
+            if (!other || !other._h || !other._attached) return false;
+            const st = other._attached();
+            if (st.scene !== activeScene || st.hostOnly) return false;
+            if (forEvent ? st.uploadedFor !== forEvent : !activeScene._devicesCurrent) return false;
+            shareFrom(other);
+            device.hostOnly = false;
+            if (!this._n.readSceneSh(this._h, null, null, null, new Int32Array(3))) this.setShTextures();   // (only if the share carried no SH)
+            for (const p of passes) p.init(this, null);
+            initialized = true;
+            return true;
+        };
+        this._attached = () => ({ scene: activeScene, hostOnly: device.hostOnly, uploadedFor: uploadedFor });
         const detach = () => {
             if (!activeScene) return;
             activeScene.removeEventListener("change", onSceneChange);
@@ -80,7 +115,7 @@ class HIPRenderer {
             detach();
             activeScene = scene;
             scene.addEventListener("change", onSceneChange);
-            upload();
+            if (!shareAttached()) upload();
             scene.attachDevice(device);
         };
 
@@ -294,10 +329,21 @@ class HIPRenderer {
         this.setSceneRows = (rows) => {
             detach();
             this._n.setSceneRows(this._h, rows);
+            this._shareToken = null;
             vertexCount = rows.length / 32;
             for (const p of passes) p.init(this, null);
             initialized = true;
         };
+        // Shared scenes for callers who manage it themselves: this renderer gives up its scene and renders `other`'s device scene
+        // (edit it with scene* through either; setSceneRows or a Scene takes this renderer out again).  sceneSharing(): how many
+        // renderers render this renderer's scene (1: not shared) and the device bytes they hold once.
+        this.shareScene = (other) => {
+            detach();
+            shareFrom(other);
+            for (const p of passes) p.init(this, null);
+            initialized = true;
+        };
+        this.sceneSharing = () => this._n.sceneSharing(this._h);
         const xf = (kind, args) => { vertexCount = this._n.sceneTransform(this._h, kind, new Float64Array(args)); };
         this.sceneTranslate = (v) => xf(0, [v.x, v.y, v.z]);
         this.sceneRotate = (q) => xf(1, [q.x, q.y, q.z, q.w]);

@@ -105,6 +105,7 @@ EXPORTS = [
     "gsr_set_scene_arrays",
     "gsr_comm_set_depth", "gsr_frame_depth_layout", "gsr_read_frame_depth", "gsr_frame_depth_device_ptr",
     "gsr_set_sh_follow", "gsr_set_sh_frame", "gsr_get_sh_frame", "gsr_read_scene_sh",
+    "gsr_share_scene", "gsr_scene_sharing",
 ]
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p)
 GSR_COMM_ID_BYTES = 128
@@ -235,6 +236,8 @@ def load_library(path=None):
     L.gsr_set_sh_frame.argtypes = [vp, vp]
     L.gsr_get_sh_frame.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int32)]
     L.gsr_read_scene_sh.argtypes = [vp, vp, vp, vp, ctypes.POINTER(ctypes.c_uint32), vp]
+    L.gsr_share_scene.argtypes = [vp, vp]
+    L.gsr_scene_sharing.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int and name not in ("gsplat_sort_host",):
@@ -367,6 +370,7 @@ class HIPRenderer:
         self._n = 0
         self._slot_views = {}   # delivery slot -> [H, W, 4] uint8 view of its pinned block (a depth ring: that and the depth view)
         self._depth_ring = False
+        self._shared = False    # this renderer has shared a scene: the count can change through another member (_count)
         self._on_change = lambda _e: self._upload(self._scene)
 
     # -- helpers --
@@ -404,13 +408,13 @@ class HIPRenderer:
 
     def set_sh(self, shs_rgb, bands_indices):
         band = np.ascontiguousarray(bands_indices, dtype=np.int32)
-        count = self._n - (int(band[0]) + 1)
+        count = self._count() - (int(band[0]) + 1)
         tex = [np.ascontiguousarray(t, dtype=np.uint32) for t in shs_rgb]
         self._check(self._L.gsr_set_scene_sh(self._ctx, tex[0].ctypes.data, tex[1].ctypes.data, tex[2].ctypes.data, count,
                                              band.ctypes.data))
 
     def read_sh_colors(self):
-        out = np.empty((self._n, 4), dtype=np.float32)
+        out = np.empty((self._count(), 4), dtype=np.float32)
         self._check(self._L.gsr_read_sh_colors(self._ctx, out.ctypes.data))
         return out
 
@@ -445,6 +449,30 @@ class HIPRenderer:
         if count.value:
             self._check(self._L.gsr_read_scene_sh(self._ctx, tex[0].ctypes.data, tex[1].ctypes.data, tex[2].ctypes.data, None, None))
         return tex, band
+
+    # -- shared scenes (gsr_share_scene): several renderers of one GPU render from one device copy --
+    def share_scene(self, other):
+        """Give up this renderer's scene and render `other`'s from now on: the same device arrays, nothing copied or uploaded.
+        Edits (scene_*), SH state and the count are then the members' together; set_scene_rows / set_raw_scene / set_scene_arrays
+        take a renderer out of the share again."""
+        self._check(self._L.gsr_share_scene(self._ctx, other._ctx))
+        self._shared = other._shared = True
+        if self._scene is not None:
+            self._scene.removeEventListener("change", self._on_change)
+            self._scene = None
+        self._n = self.scene_count()
+
+    def scene_sharing(self):
+        """(members, scene_bytes): renderers that render this renderer's scene (1: not shared) and the device bytes they hold once."""
+        members, nbytes = ctypes.c_int32(0), ctypes.c_uint64(0)
+        self._check(self._L.gsr_scene_sharing(self._ctx, ctypes.byref(members), ctypes.byref(nbytes)))
+        return members.value, int(nbytes.value)
+
+    def _count(self):
+        """The splat count read-backs are sized by: this renderer's own record, or the shared scene's (another member may have cut it)."""
+        if self._shared and self._ctx:
+            self._n = self.scene_count()
+        return self._n
 
     # -- on-device scene build and transforms (Scene.ts:58-366 as kernels) --
     def set_scene_rows(self, rows):
@@ -487,7 +515,7 @@ class HIPRenderer:
 
     def read_scene(self, with_rows=True):
         """(data u32[8n], positions f32[3n], rotations f32[4n] | None, scales f32[3n] | None)"""
-        n = self._n
+        n = self._count()
         data = np.zeros(8 * n, dtype=np.uint32)
         pos = np.zeros(3 * n, dtype=np.float32)
         rot = np.zeros(4 * n, dtype=np.float32) if with_rows else None
@@ -562,7 +590,7 @@ class HIPRenderer:
 
     # -- results --
     def lastDepthIndex(self):
-        out = np.empty(self._n, dtype=np.uint32)
+        out = np.empty(self._count(), dtype=np.uint32)
         self._check(self._L.gsr_read_depth_index(self._ctx, out.ctypes.data))
         return out
 
@@ -732,13 +760,13 @@ class HIPRenderer:
         return out[:len(xy)]
 
     def read_keys(self):
-        keys = np.empty(self._n, dtype=np.uint32)
+        keys = np.empty(self._count(), dtype=np.uint32)
         mm = np.zeros(2, dtype=np.int32)
         self._check(self._L.gsr_read_keys(self._ctx, keys.ctypes.data, mm.ctypes.data))
         return keys, (int(mm[0]), int(mm[1]))
 
     def read_records(self):
-        rec = np.empty((self._n, 8), dtype=np.float32)
+        rec = np.empty((self._count(), 8), dtype=np.float32)
         bbox = np.empty((self._n, 4), dtype=np.int32)
         self._check(self._L.gsr_read_records(self._ctx, rec.ctypes.data, bbox.ctypes.data))
         return rec, bbox

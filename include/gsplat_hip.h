@@ -6,7 +6,8 @@
  * (0 = ok, <0 = error, text via gsr_last_error).  No function throws, aborts
  * or keeps a caller's pointer after it returns (inputs are copied to the
  * device during the call).  A context is bound to one host thread at a time;
- * distinct contexts are independent.
+ * distinct contexts are independent -- except the contexts that share a scene
+ * (gsr_share_scene): those are bound to one host thread at a time together.
  *
  * Reference interfaces replaced (paths relative to the reference tree):
  *   wasm `sort(...)`                 wasm/wasm.cpp:8-13, called at
@@ -153,6 +154,42 @@ int gsr_get_sh_frame(gsr_ctx *ctx, double *linv /* 9 */, int32_t *follow); /* ei
 /* The SH state as the device holds it (after a followed gsr_scene_limit_box: the compacted one).  The textures take 8 * sh_count
  * words each and may be NULL; sh_count 0 and band_index -1, -1, -1: no SH state. */
 int gsr_read_scene_sh(gsr_ctx *ctx, uint32_t *sh_r, uint32_t *sh_g, uint32_t *sh_b, uint32_t *sh_count, int32_t *band_index /* 3 */);
+
+/* ---- shared scenes: contexts of one GPU render from one device copy ----
+ * One context per frame in flight (GSR_FLAG_THROUGHPUT) or per viewer would otherwise hold one copy of the scene each.
+ * gsr_share_scene makes ctx give up the scene it has and from now on render the scene `from` renders: the same device arrays,
+ * nothing copied or uploaded.  A context that never calls it allocates, launches and returns exactly what it always did.
+ *   What the members of a scene hold once: the per-splat arrays (positions, covariance words, colours, rotations / scales and
+ * whether the scene has them), the SH textures and their spare set with sh_count, band_index, the SH frame and the follow
+ * switch, and the splat count.  Membership is symmetric and counted: there is no leader, gsr_destroy of any member in any order
+ * leaves the others rendering, the last member to go frees the arrays.
+ *   What stays with each context: everything a frame writes -- the sort's, the binning's and the compositor's buffers, the frame
+ * words, framebuffer, depth planes, delivery ring, group exchange, the HIP graph, and the SH colours the projection evaluates
+ * for this context's camera.  Members may differ in size, band, flags, camera, depth fade, hit alpha, early-out, ring and group.
+ *   Leaving: gsr_set_scene / _rows / _arrays on a member take that member out of the share; it then owns the new scene alone and
+ * the others keep the old one untouched.  A refused upload (GSR_ERR_SCENE) leaves the member where it was, still sharing.
+ *   SH: gsr_set_scene_sh, gsr_set_sh_follow and gsr_set_sh_frame act on the shared scene (they are per-scene state): every
+ * member's later frames use them; gsr_get_sh_frame and gsr_read_scene_sh answer alike through any member.  gsr_set_scene_sh
+ * waits for every member's stream, as it waits for its own.
+ *   Edits: gsr_scene_translate / _rotate / _scale / _limit_box through any member edit the one copy, once, between frames: every
+ * frame, depth pass, pick or depth-ring pass any member enqueued before the call sees the scene as it was, everything enqueued
+ * afterwards on any member sees the edited scene.  Translate, rotate and scale add no host wait: the editing context's stream
+ * waits on one event per other member (recorded on that member's render stream), the kernel runs on the editing context's stream,
+ * and every other member's stream then waits on one event recorded behind it (the events are the contexts', none is created per
+ * edit).  gsr_scene_limit_box blocks as it always did and replaces the arrays: it also waits for every member's stream, and every
+ * member's frame state is then invalid as if it had run the call itself; each re-sizes its per-splat buffers for the new count
+ * where its next frame is enqueued.  The rules that hold "since the frame" hold for edits that arrive through another member:
+ * gsr_depth_async, gsr_pick and a depth ring's gsr_deliver_frame_async return GSR_ERR_ARG when the scene was edited behind the
+ * last frame, exactly as after an edit on the context itself.  The overflow repair of gsr_sync (the last frame rendered again)
+ * renders the scene as it stands then, edits included -- as it does after an edit on the context itself.
+ *   Reads: gsr_read_scene and gsr_scene_count through any member return the one scene.
+ *   GSR_ERR_ARG, nothing changed: ctx == from or either NULL; contexts on different devices; a `from` that has never been given
+ * a scene; a ctx that holds a delivered frame (gsr_release_frame first, as for gsr_resize).  Sharing the scene ctx already
+ * shares: GSR_OK, nothing changes.  The call waits for ctx's own stream (its frames in flight read the scene it gives up). */
+int gsr_share_scene(gsr_ctx *ctx, gsr_ctx *from);
+/* members: contexts that render this context's scene (1: not shared); scene_bytes: device bytes of the scene state that members
+ * hold once (SoA arrays, rotations / scales, SH textures and their spare set); either may be NULL; no copy, no wait. */
+int gsr_scene_sharing(gsr_ctx *ctx, int32_t *members, uint64_t *scene_bytes);
 
 /* ---- per resize / per frame ---- */
 int gsr_resize(gsr_ctx *ctx, int32_t width, int32_t height);

@@ -3,7 +3,7 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--pick X,Y] [--scene-arrays] [--scene-edit rotate]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--share-scene]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
@@ -18,6 +18,9 @@
 // --scene-arrays builds every context's scene through gsr_set_scene_arrays instead of gsr_set_scene_rows, from the four arrays
 // gsr_read_scene returns for the rows (same scene, same hashes); --scene-edit rotate adds a last leg with a gsr_scene_rotate by one
 // degree about y in front of every frame (a turntable: the scene is edited on the device, nothing is uploaded) and reports its rate.
+// --share-scene: with --in-flight k, contexts 2..k call gsr_share_scene(ctx, first) instead of uploading: one device copy of the
+// scene for all of them.  The report carries scene_sharing (members, bytes held once) and setup_ms, the wall time from the first
+// gsr_create to the last scene being ready, with and without the flag.
 //
 // Scene: the seeded synthetic generator of gsplat_hip/synth.py (mulberry32 counter PRNG, 24 draws per splat) written
 // out again in C++; log/exp/cos come from libm here and from numpy there, so a byte may differ in a rare rounding --
@@ -139,7 +142,7 @@ int main(int argc, char** argv)
     std::string deliver_depth = "none";
     int depth_step = 1;
     float depth_near = 0.1f;
-    bool depth = false, pick = false, scene_arrays = false;
+    bool depth = false, pick = false, scene_arrays = false, share_scene = false;
     std::string scene_edit = "none";
     int32_t pick_xy[2] = {0, 0};
     for (int i = 1; i < argc; i++) {
@@ -159,8 +162,9 @@ int main(int argc, char** argv)
         else if (a == "--depth") depth = true;
         else if (a == "--scene-arrays") scene_arrays = true;
         else if (a == "--scene-edit") scene_edit = next();
+        else if (a == "--share-scene") share_scene = true;
         else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--pick X,Y] [--scene-arrays] [--scene-edit rotate]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--share-scene]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
@@ -188,6 +192,7 @@ int main(int argc, char** argv)
 
     gsr_ctx* ctx0 = nullptr;
     std::vector<gsr_ctx*> ctx(in_flight, nullptr);
+    const auto setup0 = std::chrono::steady_clock::now();
     for (int c = 0; c < in_flight; c++) {
         gsr_options o{};
         o.device = 0; o.width = cfg->w; o.height = cfg->h;
@@ -195,15 +200,25 @@ int main(int argc, char** argv)
         const int rc = gsr_create(&ctx[c], &o);
         if (rc) { std::fprintf(stderr, "gsr_create failed (%d): %s\n", rc, gsr_last_error(nullptr)); return 1; }
         ctx0 = ctx[c];
-        CHECK(gsr_set_scene_rows(ctx[c], rows.data(), n));
+        if (share_scene && c > 0) CHECK(gsr_share_scene(ctx[c], ctx[0]));
+        else CHECK(gsr_set_scene_rows(ctx[c], rows.data(), n));
     }
     if (scene_arrays) {   // the same scene once more, as a host that holds a Scene's four arrays hands it over
         std::vector<uint32_t> data((size_t)n * 8);
         std::vector<float> positions((size_t)n * 3), rotations((size_t)n * 4), scales((size_t)n * 3);
         ctx0 = ctx[0];
         CHECK(gsr_read_scene(ctx[0], data.data(), positions.data(), rotations.data(), scales.data(), nullptr));
-        for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_set_scene_arrays(c, data.data(), positions.data(), rotations.data(), scales.data(), n)); }
+        for (gsr_ctx* c : ctx) {
+            ctx0 = c;
+            if (share_scene && c != ctx[0]) CHECK(gsr_share_scene(c, ctx[0]));
+            else CHECK(gsr_set_scene_arrays(c, data.data(), positions.data(), rotations.data(), scales.data(), n));
+        }
     }
+    const double setup_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - setup0).count() * 1e3;
+    int32_t share_members = 0;
+    uint64_t share_bytes = 0;
+    ctx0 = ctx[in_flight - 1];
+    CHECK(gsr_scene_sharing(ctx[in_flight - 1], &share_members, &share_bytes));
     std::vector<Cam> poses(120);
     for (int k = 0; k < 120; k++) poses[k] = orbit_camera(k, 120, cfg->w, cfg->h, cfg->fx);
 
@@ -363,6 +378,8 @@ int main(int argc, char** argv)
     if (depth)
         std::printf(", \"frames_per_sec_plain\": %.1f, \"frames_per_sec_with_depth\": %.1f, \"depth_legs\": 3",
                     3.0 * frames / depth_sec[0], 3.0 * frames / depth_sec[1]);
+    std::printf(", \"share_scene\": %s, \"scene_sharing\": {\"members\": %d, \"bytes\": %llu}, \"setup_ms\": %.2f",
+                share_scene ? "true" : "false", share_members, (unsigned long long)share_bytes, setup_ms);
     if (scene_arrays) std::printf(", \"scene_from\": \"gsr_set_scene_arrays\"");
     if (scene_edit == "rotate") std::printf(", \"scene_edit\": \"rotate\", \"frames_per_sec_scene_edit\": %.1f", frames / edit_sec);
     if (pick)
