@@ -214,14 +214,14 @@ int gsr_allgather_frame_async(gsr_ctx* c)
     if (dx.on()) {
         if (dx.W != c->W || dx.H != c->H)
             return fail(c, GSR_ERR_ARG, "gsr_allgather_frame_async: the size changed since gsr_comm_set_depth (%dx%d, now %dx%d): join the group again", dx.W, dx.H, c->W, c->H);
-        if (int r = delivery_depth_check(c, "gsr_allgather_frame_async (depth exchange)")) return r;
+        if (int r = depth_frame_check(c, "gsr_allgather_frame_async (depth exchange)")) return r;
     }
     HIP_TRY(c, hipSetDevice(c->device));
     // never ship a band the compositor did not draw: if the device has reported a list overflow, regrow and render
     // the frame again first (lost earlier frames stay counted and are reported by the next gsr_sync)
     if (overflow_pending(c)) {
         if (int r = sync_and_repair(c)) return r;
-        if (dx.on()) { if (int r = delivery_depth_check(c, "gsr_allgather_frame_async (depth exchange)")) return r; }   // (a regrowth may have taken the lists)
+        if (dx.on()) { if (int r = depth_frame_check(c, "gsr_allgather_frame_async (depth exchange)")) return r; }   // (a regrowth may have taken the lists)
     }
     const BinGrid g = make_grid(c);
     const int x0 = g.bx_lo * BIN_PX, x1 = std::min(g.bx_hi * BIN_PX, c->W);
@@ -233,9 +233,10 @@ int gsr_allgather_frame_async(gsr_ctx* c)
     if (dx.on()) {
         // the frame's hit plane on this rank's bin columns (the pass of a depth ring, the same hit_alpha rule), then the band's samples
         // into the slab's depth section.  A frame whose lists did not fit leaves the plane as it was: the slab's flag says so.
-        comm_depth_enqueue(c);
-        launch_pack_band_depth(dx.format, dx.hit, reinterpret_cast<uint8_t*>(c->comm.slab.p) + dx.offset, dx.Wd, dx.Hd, dx.edges.x0[c->comm.rank],
-                               dx.edges.x1[c->comm.rank], dx.stride, dx.near, c->stream);
+        // Only this rank's bin columns are written and only they are packed, so nothing is filled beside them.
+        if (int r = depth_enqueue(c, dx.planes, dx.spec.step, DEPTH_FILL_NOTHING)) return r;
+        launch_pack_band_depth(dx.spec.format, dx.planes.hit, reinterpret_cast<uint8_t*>(c->comm.slab.p) + dx.offset, dx.planes.Wd, dx.planes.Hd,
+                               dx.edges.x0[c->comm.rank], dx.edges.x1[c->comm.rank], dx.stride, dx.spec.near, c->stream);
     }
     HIP_TRY(c, hipEventRecord(c->comm.ev_packed, c->stream));
     // exchange stream: collective + de-slab, overlapping the next frame's kernels on the render stream
@@ -251,8 +252,8 @@ int gsr_allgather_frame_async(gsr_ctx* c)
     launch_unpack_slabs_rgba8(c->comm.gathered, c->comm.frame8, c->W, c->H, c->comm.slab_w, c->comm.world, c->comm.edges, c->comm.stream,
                               c->comm.frame8 + (size_t)c->W * c->H, dx.on() ? slab_bytes / 4 : 0);
     if (dx.on())
-        launch_unpack_slabs_depth(dx.format, reinterpret_cast<const uint8_t*>(c->comm.gathered.p), dx.plane, dx.Wd, dx.Hd, slab_bytes, dx.offset, dx.stride,
-                                  c->comm.world, dx.edges, c->comm.stream);
+        launch_unpack_slabs_depth(dx.spec.format, reinterpret_cast<const uint8_t*>(c->comm.gathered.p), dx.plane, dx.planes.Wd, dx.planes.Hd, slab_bytes, dx.offset,
+                                  dx.stride, c->comm.world, dx.edges, c->comm.stream);
     HIP_TRY(c, hipGetLastError());
     c->comm.frame8_valid = true;
     return GSR_OK;
@@ -296,35 +297,30 @@ int gsr_comm_set_depth(gsr_ctx* c, const gsr_depth_delivery_options* depth)
 {
     if (!c) return GSR_ERR_ARG;
     if (!c->comm.joined()) return fail(c, GSR_ERR_ARG, "gsr_comm_set_depth: this context is not in a group (gsr_comm_init, gsr_comm_share)");
-    if (depth && depth->format == GSR_DEPTH_NONE) depth = nullptr;
-    if (depth) { if (int r = depth_options_check(c, "gsr_comm_set_depth", depth)) return r; }
+    const DepthSpec spec = DepthSpec::from(depth);
+    if (spec.on()) { if (int r = depth_options_check(c, "gsr_comm_set_depth", depth)) return r; }
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->comm.stream));
     gsr_ctx::Comm::DepthExchange& dx = c->comm.depth;
     dx.reset();
     c->comm.frame8_valid = false;   // the slabs change: what was gathered under the old contract is gone
-    if (depth) {
-        const int st = depth->step, world = c->comm.world;
-        dx.format = depth->format; dx.step = st;
-        dx.near = depth->format == GSR_DEPTH_U16 ? depth->near : 0.0f;
+    if (spec.on()) {
+        const int st = spec.step, world = c->comm.world;
+        int r = dx.planes.alloc(c, c->W, c->H, st);   // (first: the layout below is in its Wd, Hd)
+        dx.spec = spec;
         dx.W = c->W; dx.H = c->H;
-        dx.Wd = (c->W + st - 1) / st; dx.Hd = (c->H + st - 1) / st;
         // band edges are multiples of 32 (the last may be the image's width): x0 / step is exact, the bands are disjoint and cover Wd
         for (int q = 0; q < world; q++) { dx.edges.x0[q] = c->comm.edges.x0[q] / st; dx.edges.x1[q] = (c->comm.edges.x1[q] + st - 1) / st; }
         dx.stride = ((c->comm.slab_w + st - 1) / st + 7) & ~7;
         dx.offset = ((((size_t)c->comm.slab_w * c->H + SLAB_FLAG_WORDS) * 4) + 15) & ~(size_t)15;
-        dx.slab_bytes = dx.offset + (size_t)dx.Hd * dx.stride * dx.sample_bytes();
-        const size_t np = (size_t)dx.Wd * dx.Hd;
+        dx.slab_bytes = dx.offset + (size_t)dx.planes.Hd * dx.stride * spec.sample_bytes();
         const size_t plane_words = (dx.plane_bytes() + 15) / 16 * 4;
-        int r = dx.hit.alloc(c, np);
-        if (!r && st == 1) { r = dx.mean.alloc(c, np); if (!r) r = dx.index.alloc(c, np); }
-        if (!r) r = dx.invalid.alloc(c, 1);
         if (!r) r = dx.plane.alloc(c, plane_words);
         if (!r) r = alloc_slabs(c, world);
         if (r) { dx.reset(); (void)alloc_slabs(c, world); return r; }   // (colour only again)
         // (a frame that never fits leaves the plane unwritten: +infinity rather than whatever the allocation held)
-        HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)dx.hit.p, 0x7f800000, np, c->stream));
+        HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)dx.planes.hit.p, 0x7f800000, (size_t)dx.planes.Wd * dx.planes.Hd, c->stream));
         HIP_TRY(c, hipMemsetAsync(dx.plane, 0, plane_words * 4, c->stream));
         return GSR_OK;
     }
@@ -337,12 +333,7 @@ int gsr_frame_depth_layout(gsr_ctx* c, gsr_depth_layout* out)
     if (!out) return fail(c, GSR_ERR_ARG, "gsr_frame_depth_layout: out is NULL");
     const gsr_ctx::Comm::DepthExchange& dx = c->comm.depth;
     if (!c->comm.joined() || !dx.on()) return fail(c, GSR_ERR_ARG, "gsr_frame_depth_layout: this context exchanges no depth (gsr_comm_set_depth)");
-    *out = gsr_depth_layout{};
-    out->format = dx.format; out->step = dx.step; out->width = dx.Wd; out->height = dx.Hd;
-    out->stride = (int32_t)(dx.Wd * dx.sample_bytes());
-    out->offset = 0;
-    out->bytes = dx.plane_bytes();
-    out->near = dx.near;
+    *out = dx.spec.layout(dx.planes.Wd, dx.planes.Hd, 0);
     return GSR_OK;
 }
 

@@ -181,6 +181,61 @@ struct FrameArgs {
 };
 static_assert(std::is_trivially_copyable<FrameArgs>::value, "FrameArgs is compared and copied as bytes");
 
+// What a depth plane that leaves the pass's own buffers holds -- a depth ring's (gsr_delivery_open_depth), a group's exchanged one
+// (gsr_comm_set_depth): the sample format, every step-th pixel in both directions and, for U16, the near plane.
+struct DepthSpec {
+    int format = GSR_DEPTH_NONE;   // GSR_DEPTH_*; NONE: no depth plane
+    int step = 1;                  // 1 or 2: sample (i, j) is pixel (step * i, step * j)
+    float near = 0.0f;             // GSR_DEPTH_U16; 0 otherwise
+    // of options depth_options_check has accepted; NULL or GSR_DEPTH_NONE: off, whatever else the struct holds
+    static DepthSpec from(const gsr_depth_delivery_options* o)
+    {
+        if (!o || o->format == GSR_DEPTH_NONE) return {};
+        return {o->format, o->step, o->format == GSR_DEPTH_U16 ? o->near : 0.0f};
+    }
+    bool on() const { return format != GSR_DEPTH_NONE; }
+    size_t sample_bytes() const { return format == GSR_DEPTH_U16 ? 2 : 4; }
+    bool operator==(const DepthSpec& o) const { return format == o.format && step == o.step && near == o.near; }
+    // a plane of Wd x Hd samples, rows packed; the layout of one that lies `offset` bytes into what the caller reads
+    size_t plane_bytes(int Wd, int Hd) const { return (size_t)Wd * Hd * sample_bytes(); }
+    gsr_depth_layout layout(int Wd, int Hd, uint64_t offset) const
+    {
+        gsr_depth_layout l{};
+        l.format = format; l.step = step; l.width = Wd; l.height = Hd;
+        l.stride = (int32_t)plane_bytes(Wd, 1);
+        l.offset = offset;
+        l.bytes = plane_bytes(Wd, Hd);
+        l.near = near;
+        return l;
+    }
+};
+
+// What one user of the depth pass (k_depth.hip) has it write: the context's planes (gsr_depth_async / gsr_read_depth), a depth ring's,
+// a group's depth exchange.  Each user has a set of its own, so none disturbs what another reads; gsr_depth.cpp's depth_enqueue fills any.
+struct DepthPlanes {
+    DevBuf<float> hit;             // Wd x Hd
+    DevBuf<float> mean;            // step 1 only (k_depth_planes<.., 1> writes all three planes); scratch for every user but the context
+    DevBuf<uint32_t> index;
+    DevBuf<uint32_t> invalid;      // one word, stored by every pass: 1 = it refused a frame whose lists did not fit and wrote nothing
+    int Wd = 0, Hd = 0;            // ceil(W / step), ceil(H / step): the extent in use, not the capacity (the context's planes only grow
+                                   // and hold a smaller image at their front; a ring's and the exchange's are allocated for exactly this)
+    int fill_key[4] = {0, 0, 0, 0};   // band contexts: W, H and bin columns the columns outside the band were last filled for
+    int alloc(gsr_ctx* c, int W, int H, int step)
+    {
+        reset();
+        Wd = (W + step - 1) / step; Hd = (H + step - 1) / step;
+        const size_t np = (size_t)Wd * Hd;
+        int r = hit.alloc(c, np);
+        if (!r && step == 1) { r = mean.alloc(c, np); if (!r) r = index.alloc(c, np); }
+        if (!r) r = invalid.alloc(c, 1);
+        if (r) reset();
+        return r;
+    }
+    void reset() { hit.reset(); mean.reset(); index.reset(); invalid.reset(); Wd = Hd = 0; std::fill(fill_key, fill_key + 4, 0); }
+};
+// what a user of the pass has in the columns outside a band context's bins, which the pass does not write
+enum DepthFill { DEPTH_FILL_NOTHING, DEPTH_FILL_HIT /* hit: +inf */, DEPTH_FILL_PLANES /* mean, hit, index: 0, +inf, none */ };
+
 }  // namespace gsr
 
 struct gsr_ctx {
@@ -302,26 +357,19 @@ struct gsr_ctx {
         bool joined() const { return nccl || fn; }
         // depth beside the colour (gsr_comm_set_depth): the band's hit samples travel in a depth section behind the slab's pixels and
         // flag words, and one de-slab step leaves the gathered plane on every rank.  Nothing below is allocated, and the slab is
-        // the colour slab byte for byte, until a context opts in; the pass has planes of its own, like a depth ring's.
+        // the colour slab byte for byte, until a context opts in.
         struct DepthExchange {
-            int format = GSR_DEPTH_NONE;    // GSR_DEPTH_*; NONE: colour only
-            int step = 1;
-            float near = 0.0f;              // GSR_DEPTH_U16
+            gsr::DepthSpec spec;            // off: colour only
+            gsr::DepthPlanes planes;        // the pass writes this rank's columns of hit, the band pack reads them (`invalid` is never read: the slab's flag decides)
             int W = 0, H = 0;               // the size the buffers and the layout were made for
-            int Wd = 0, Hd = 0;             // ceil(W / step), ceil(H / step)
             int stride = 0;                 // samples per row of a slab's depth section: the widest band's, rounded up to 8
             size_t offset = 0;              // of the section in a slab: behind pixels and flag words, at the next multiple of 16
             size_t slab_bytes = 0;          // offset + Hd * stride * sample size: what one rank hands to the collective
             gsr::SlabEdges edges{};         // the bands in samples: [x0 / step, ceil(x1 / step))
-            gsr::DevBuf<float> hit;         // Wd x Hd: what the pass writes (this rank's columns) and the band pack reads
-            gsr::DevBuf<float> mean;        // step 1 only: the full pass writes three planes; these two are scratch
-            gsr::DevBuf<uint32_t> index;
-            gsr::DevBuf<uint32_t> invalid;  // the pass's "refused an unfit frame" word (never read by the host: the slab's flag decides)
             gsr::DevBuf<uint32_t> plane;    // the gathered plane [Hd][Wd], f32 or u16, in whole 16 bytes (the rest zero)
-            bool on() const { return format != GSR_DEPTH_NONE; }
-            size_t sample_bytes() const { return format == GSR_DEPTH_U16 ? 2 : 4; }
-            size_t plane_bytes() const { return (size_t)Wd * Hd * sample_bytes(); }
-            void reset() { format = GSR_DEPTH_NONE; hit.reset(); mean.reset(); index.reset(); invalid.reset(); plane.reset(); W = H = Wd = Hd = stride = 0; offset = slab_bytes = 0; }
+            bool on() const { return spec.on(); }
+            size_t plane_bytes() const { return spec.plane_bytes(planes.Wd, planes.Hd); }
+            void reset() { spec = {}; planes.reset(); plane.reset(); W = H = stride = 0; offset = slab_bytes = 0; }
         } depth;
         // what one rank hands to the collective
         size_t slab_bytes(int H) const { return depth.on() ? depth.slab_bytes : ((size_t)slab_w * H + gsr::SLAB_FLAG_WORDS) * 4; }
@@ -329,15 +377,13 @@ struct gsr_ctx {
 
     // depth planes and picking (gsr_depth.cpp); nothing is allocated until the first call that needs it
     struct Depth {
-        gsr::DevBuf<float> mean, hit;
-        gsr::DevBuf<uint32_t> index;
-        size_t pixels = 0;                  // pixels the planes hold
+        gsr::DepthPlanes planes;            // what gsr_read_depth returns: W x H of the last pass in front of `pixels` allocated (they only grow)
+        size_t pixels = 0;
         gsr::DevBuf<int32_t> query;         // gsr_pick: MAX_PICKS (x, y) pairs
         gsr::DevBuf<gsr::PickResult> result;
-        gsr::DevBuf<uint32_t> invalid;      // [0] the planes pass, [1] the pick pass: 1 = it refused a frame whose lists did not fit
+        gsr::DevBuf<uint32_t> pick_invalid; // the pick pass's word, as planes.invalid is the planes pass's
         float hit_alpha = 0.5f;
         uint64_t planes_serial = 0;         // frame_serial of the frame the planes were enqueued behind (0: none, or hit_alpha changed)
-        int fill_key[4] = {0, 0, 0, 0};     // band contexts: W, H and bin columns the planes' other columns were last filled for
     } depth;
 
     // frame delivery (gsr_delivery_open): a ring of pinned host blocks, each with its device staging and "copy done" event
@@ -357,19 +403,19 @@ struct gsr_ctx {
         gsr::YuvParams yuv{};               // NV12 / I420: the coefficient set and the background
         int next = 0;                       // where the search for a free slot starts: the slots are used in turn
         uint64_t serial = 0;                // the last serial handed out; never restarts
-        // a depth ring (gsr_delivery_open_depth): every delivered frame carries its hit plane behind the colour payload.  The pass has
-        // buffers of its own -- nothing of gsr_ctx::Depth but hit_alpha is read, nothing of it written -- allocated with the ring.
+        // a depth ring (gsr_delivery_open_depth): every delivered frame carries its hit plane behind the colour payload.  Nothing of
+        // gsr_ctx::Depth but hit_alpha is read, nothing of it written.
         struct DepthPlane {
-            int format = GSR_DEPTH_NONE;    // GSR_DEPTH_*; NONE: a ring as it was before depth rings existed, nothing below is allocated
-            int step = 1;                   // 1 or 2: sample (i, j) is pixel (step * i, step * j)
-            float near = 0.0f;              // GSR_DEPTH_U16
-            int Wd = 0, Hd = 0;             // ceil(W / step), ceil(H / step)
-            gsr::DevBuf<float> hit;         // Wd x Hd: what the pass writes and k_deliver_depth reads; reused by every delivery (in-order on the render stream)
-            gsr::DevBuf<float> mean;        // step 1 only: k_depth_planes<.., 1> writes three planes; these two are scratch
-            gsr::DevBuf<uint32_t> index;
-            gsr::DevBuf<uint32_t> invalid;  // the pass's "refused an unfit frame" word: a third one, beside the planes' and the pick's
-            int fill_key[4] = {0, 0, 0, 0}; // band contexts: W, H and bin columns the hit plane's other columns were last filled for
+            gsr::DepthSpec spec;            // off: a ring as it was before depth rings existed, nothing below is allocated
+            gsr::DepthPlanes planes;        // allocated with the ring: the pass writes hit, k_deliver_depth reads it; reused by every delivery (in-order on the render stream)
         } depth;
+        // a slot's layout: the frame's payload in the ring's format; in a depth ring the plane behind it at the next multiple of 16; the
+        // trailer behind the plane at the next multiple of 16 (without depth: behind the payload at the next whole word)
+        size_t pixel_bytes() const { return format == GSR_FORMAT_RGBA8 ? (size_t)W * H * 4 : gsr::yuv420_bytes(W, H); }
+        size_t depth_offset() const { return (pixel_bytes() + 15) & ~(size_t)15; }
+        size_t depth_bytes() const { return depth.spec.plane_bytes(depth.planes.Wd, depth.planes.Hd); }
+        size_t trailer_offset() const { return depth.spec.on() ? (depth_offset() + depth_bytes() + 15) & ~(size_t)15 : (pixel_bytes() + 3) & ~(size_t)3; }
+        size_t slot_bytes() const { return trailer_offset() + gsr::DELIVER_TRAILER_WORDS * 4; }
     } delivery;
 };
 
@@ -411,12 +457,11 @@ int adopt_scene(gsr_ctx* c);
 void scene_release(gsr_ctx* c);
 // gsr_comm.cpp
 void comm_release(gsr_ctx* c);
-// gsr_depth.cpp: a depth ring's pass for the frame enqueued last.  check: what gsr_depth_async demands of the frame (GSR_ERR_ARG, nothing
-// enqueued); enqueue: the planes pass into the ring's own plane(s) on the render stream (launch errors are left for hipGetLastError)
-int delivery_depth_check(gsr_ctx* c, const char* who);
-int delivery_depth_enqueue(gsr_ctx* c);
-// the same pass for a group's depth exchange (gsr_comm_set_depth), into the exchange's own plane(s)
-void comm_depth_enqueue(gsr_ctx* c);
+// gsr_depth.cpp: the depth pass for the frame enqueued last.  depth_frame_check: what every pass demands of that frame (GSR_ERR_ARG,
+// `who` in front of the message; nothing enqueued); depth_enqueue: the pass into `p` behind the frame on the render stream (launch
+// errors are left for the caller's hipGetLastError)
+int depth_frame_check(gsr_ctx* c, const char* who);
+int depth_enqueue(gsr_ctx* c, DepthPlanes& p, int step, DepthFill fill);
 // gsr_delivery.cpp
 int delivery_alloc(gsr_ctx* c, int slots);
 // what gsr_delivery_open_depth demands of depth options other than GSR_DEPTH_NONE (GSR_ERR_ARG, `who` in front of the message)

@@ -15,24 +15,6 @@ using namespace gsr;
 
 using DeliverySlot = gsr_ctx::Delivery::Slot;
 
-// the payload of one frame in the ring's format, and where the trailer lies behind it
-static inline size_t ring_pixel_bytes(const gsr_ctx* c)
-{
-    const gsr_ctx::Delivery& d = c->delivery;
-    return d.format == GSR_FORMAT_RGBA8 ? (size_t)d.W * d.H * 4 : yuv420_bytes(d.W, d.H);
-}
-// a depth ring: the plane behind the payload at the next multiple of 16, the trailer behind the plane at the next multiple of 16
-static inline bool ring_has_depth(const gsr_ctx* c) { return c->delivery.depth.format != GSR_DEPTH_NONE; }
-static inline size_t ring_depth_offset(const gsr_ctx* c) { return (ring_pixel_bytes(c) + 15) & ~(size_t)15; }
-static inline size_t ring_depth_stride(const gsr_ctx* c) { return (size_t)c->delivery.depth.Wd * (c->delivery.depth.format == GSR_DEPTH_U16 ? 2 : 4); }
-static inline size_t ring_depth_bytes(const gsr_ctx* c) { return ring_depth_stride(c) * c->delivery.depth.Hd; }
-static inline size_t ring_trailer_offset(const gsr_ctx* c)
-{
-    if (ring_has_depth(c)) return (ring_depth_offset(c) + ring_depth_bytes(c) + 15) & ~(size_t)15;
-    return (ring_pixel_bytes(c) + 3) & ~(size_t)3;
-}
-static inline size_t ring_slot_bytes(const gsr_ctx* c) { return ring_trailer_offset(c) + DELIVER_TRAILER_WORDS * 4; }
-
 // BT.709 in 1/256: every chroma row sums to zero, the full-range luma row to 256, so greys are neutral exactly
 static YuvParams yuv_params(bool full_range, const uint8_t* bg)
 {
@@ -68,10 +50,7 @@ void gsr::delivery_free(gsr_ctx* c)
     c->delivery.copy_stream = nullptr;
     c->delivery.W = c->delivery.H = 0;
     c->delivery.next = 0;
-    gsr_ctx::Delivery::DepthPlane& dp = c->delivery.depth;   // (format, step and near stay: gsr_resize reallocates for them)
-    dp.hit.reset(); dp.mean.reset(); dp.index.reset(); dp.invalid.reset();
-    dp.Wd = dp.Hd = 0;
-    std::fill(dp.fill_key, dp.fill_key + 4, 0);
+    c->delivery.depth.planes.reset();   // (the spec stays: gsr_resize reallocates for it)
 }
 
 // (re)allocates the ring for the context's current size; frames in flight are waited for and dropped
@@ -80,17 +59,9 @@ int gsr::delivery_alloc(gsr_ctx* c, int slots)
     delivery_free(c);
     c->delivery.W = c->W; c->delivery.H = c->H;
     gsr_ctx::Delivery::DepthPlane& dp = c->delivery.depth;
-    if (ring_has_depth(c)) { dp.Wd = (c->W + dp.step - 1) / dp.step; dp.Hd = (c->H + dp.step - 1) / dp.step; }
-    const size_t bytes = ring_slot_bytes(c);
     auto bail = [c](int code) { delivery_free(c); return code; };
-    if (ring_has_depth(c)) {
-        // the pass's own plane(s): the hit plane k_deliver_depth reads; at step 1 the full pass also writes mean and index
-        const size_t np = (size_t)dp.Wd * dp.Hd;
-        int r = dp.hit.alloc(c, np);
-        if (!r && dp.step == 1) { r = dp.mean.alloc(c, np); if (!r) r = dp.index.alloc(c, np); }
-        if (!r) r = dp.invalid.alloc(c, 1);
-        if (r) return bail(r);
-    }
+    if (dp.spec.on()) { if (int r = dp.planes.alloc(c, c->W, c->H, dp.spec.step)) return bail(r); }
+    const size_t bytes = c->delivery.slot_bytes();
     hipError_t e = hipStreamCreateWithFlags(&c->delivery.copy_stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->delivery.ev_staged, hipEventDisableTiming);
     c->delivery.ring.resize((size_t)slots);
@@ -125,17 +96,17 @@ int gsr::depth_options_check(gsr_ctx* c, const char* who, const gsr_depth_delive
     return GSR_OK;
 }
 
-// a depth ring on a context whose group exchanges depth: format, step and near must be the exchange's (GSR_ERR_ARG names the first that is not)
-static int exchange_mismatch(gsr_ctx* c, const char* who, int format, int step, float near)
+// a depth ring on a context whose group exchanges depth: the ring's spec must be the exchange's (GSR_ERR_ARG names the first field that is not)
+static int exchange_mismatch(gsr_ctx* c, const char* who, const DepthSpec& ring)
 {
     const gsr_ctx::Comm::DepthExchange& dx = c->comm.depth;
-    if (format != dx.format)
-        return fail(c, GSR_ERR_ARG, "%s: the ring's depth format (%d) is not the one the group exchanges (%d, gsr_comm_set_depth)", who, format, dx.format);
-    if (step != dx.step) return fail(c, GSR_ERR_ARG, "%s: the ring's depth step (%d) is not the one the group exchanges (%d, gsr_comm_set_depth)", who, step, dx.step);
+    const DepthSpec& ex = dx.spec;
+    if (ring == ex && c->W == dx.W && c->H == dx.H) return GSR_OK;
+    if (ring.format != ex.format)
+        return fail(c, GSR_ERR_ARG, "%s: the ring's depth format (%d) is not the one the group exchanges (%d, gsr_comm_set_depth)", who, ring.format, ex.format);
+    if (ring.step != ex.step) return fail(c, GSR_ERR_ARG, "%s: the ring's depth step (%d) is not the one the group exchanges (%d, gsr_comm_set_depth)", who, ring.step, ex.step);
     if (c->W != dx.W || c->H != dx.H) return fail(c, GSR_ERR_ARG, "%s: the size changed since gsr_comm_set_depth: join the group again", who);
-    if (near != dx.near)
-        return fail(c, GSR_ERR_ARG, "%s: the ring's depth near (%g) is not the one the group exchanges (%g, gsr_comm_set_depth)", who, (double)near, (double)dx.near);
-    return GSR_OK;
+    return fail(c, GSR_ERR_ARG, "%s: the ring's depth near (%g) is not the one the group exchanges (%g, gsr_comm_set_depth)", who, (double)ring.near, (double)ex.near);
 }
 
 extern "C" {
@@ -154,7 +125,7 @@ int gsr_delivery_open(gsr_ctx* c, int32_t slots)
     if (int r = delivery_open_checked(c, "gsr_delivery_open", slots)) return r;
     HIP_TRY(c, hipSetDevice(c->device));
     c->delivery.format = GSR_FORMAT_RGBA8;
-    c->delivery.depth.format = GSR_DEPTH_NONE;
+    c->delivery.depth.spec = {};
     return delivery_alloc(c, slots);
 }
 
@@ -164,22 +135,20 @@ static int delivery_open_options(gsr_ctx* c, const char* who, const gsr_delivery
     if (!opt) return fail(c, GSR_ERR_ARG, "%s: options are NULL", who);
     if (opt->format != GSR_FORMAT_RGBA8 && opt->format != GSR_FORMAT_NV12 && opt->format != GSR_FORMAT_I420)
         return fail(c, GSR_ERR_ARG, "%s: unknown format %d (GSR_FORMAT_RGBA8, GSR_FORMAT_NV12, GSR_FORMAT_I420)", who, opt->format);
-    if (depth) {
+    const DepthSpec spec = DepthSpec::from(depth);
+    if (spec.on()) {
         if (int r = depth_options_check(c, who, depth)) return r;
         if (c->comm.joined() && !c->comm.depth.on())
             return fail(c, GSR_ERR_ARG, "%s: this context is in a group: depth is not exchanged between ranks, so a gathered frame has no depth plane to deliver", who);
         // a group that exchanges depth (gsr_comm_set_depth) delivers the gathered plane as it is: the ring's options must be the exchange's
-        if (c->comm.joined()) { if (int r = exchange_mismatch(c, who, depth->format, depth->step, depth->format == GSR_DEPTH_U16 ? depth->near : 0.0f)) return r; }
+        if (c->comm.joined()) { if (int r = exchange_mismatch(c, who, spec)) return r; }
     }
     if (!c->delivery.ring.empty()) return fail(c, GSR_ERR_ARG, "%s: a delivery ring is open (gsr_delivery_close first)", who);
     if (int r = delivery_open_checked(c, who, opt->slots)) return r;
     HIP_TRY(c, hipSetDevice(c->device));
     c->delivery.format = opt->format;
     c->delivery.yuv = yuv_params(opt->full_range != 0, opt->background);
-    gsr_ctx::Delivery::DepthPlane& dp = c->delivery.depth;
-    dp.format = depth ? depth->format : GSR_DEPTH_NONE;
-    dp.step = depth ? depth->step : 1;
-    dp.near = depth && depth->format == GSR_DEPTH_U16 ? depth->near : 0.0f;
+    c->delivery.depth.spec = spec;
     return delivery_alloc(c, opt->slots);
 }
 
@@ -192,7 +161,7 @@ int gsr_delivery_open_ex(gsr_ctx* c, const gsr_delivery_options* opt)
 int gsr_delivery_open_depth(gsr_ctx* c, const gsr_delivery_options* opt, const gsr_depth_delivery_options* depth)
 {
     if (!c) return GSR_ERR_ARG;
-    return delivery_open_options(c, "gsr_delivery_open_depth", opt, depth && depth->format != GSR_DEPTH_NONE ? depth : nullptr);
+    return delivery_open_options(c, "gsr_delivery_open_depth", opt, depth);
 }
 
 int gsr_delivery_depth_layout(gsr_ctx* c, gsr_depth_layout* out)
@@ -200,14 +169,9 @@ int gsr_delivery_depth_layout(gsr_ctx* c, gsr_depth_layout* out)
     if (!c) return GSR_ERR_ARG;
     if (!out) return fail(c, GSR_ERR_ARG, "gsr_delivery_depth_layout: out is NULL");
     if (c->delivery.ring.empty()) return fail(c, GSR_ERR_ARG, "gsr_delivery_depth_layout: no delivery ring (gsr_delivery_open_depth)");
-    if (!ring_has_depth(c)) return fail(c, GSR_ERR_ARG, "gsr_delivery_depth_layout: the ring was opened without a depth plane (gsr_delivery_open_depth)");
     const gsr_ctx::Delivery::DepthPlane& dp = c->delivery.depth;
-    *out = gsr_depth_layout{};
-    out->format = dp.format; out->step = dp.step; out->width = dp.Wd; out->height = dp.Hd;
-    out->stride = (int32_t)ring_depth_stride(c);
-    out->offset = ring_depth_offset(c);
-    out->bytes = ring_depth_bytes(c);
-    out->near = dp.near;
+    if (!dp.spec.on()) return fail(c, GSR_ERR_ARG, "gsr_delivery_depth_layout: the ring was opened without a depth plane (gsr_delivery_open_depth)");
+    *out = dp.spec.layout(dp.planes.Wd, dp.planes.Hd, c->delivery.depth_offset());
     return GSR_OK;
 }
 
@@ -220,7 +184,7 @@ int gsr_delivery_layout(gsr_ctx* c, gsr_frame_layout* out)
     const int32_t W = d.W, H = d.H, Wc = (W + 1) / 2, Hc = (H + 1) / 2;
     *out = gsr_frame_layout{};
     out->format = d.format; out->width = W; out->height = H;
-    out->bytes = ring_pixel_bytes(c);
+    out->bytes = d.pixel_bytes();
     out->stride[0] = W; out->rows[0] = H;
     if (d.format == GSR_FORMAT_RGBA8) {
         out->planes = 1;
@@ -243,7 +207,7 @@ int gsr_delivery_close(gsr_ctx* c)
     if (delivery_frame_held(c)) return fail(c, GSR_ERR_ARG, "gsr_delivery_close: a delivered frame is held (gsr_release_frame first): its pixels would be freed");
     HIP_TRY(c, hipSetDevice(c->device));
     delivery_free(c);
-    c->delivery.depth.format = GSR_DEPTH_NONE;
+    c->delivery.depth.spec = {};
     return GSR_OK;
 }
 
@@ -251,92 +215,76 @@ int gsr_deliver_frame_async(gsr_ctx* c, uint64_t* serial)
 {
     if (!c) return GSR_ERR_ARG;
     if (c->delivery.ring.empty()) return fail(c, GSR_ERR_ARG, "gsr_deliver_frame_async: no delivery ring (gsr_delivery_open)");
+    gsr_ctx::Delivery& dl = c->delivery;
     const bool group = c->comm.joined();
-    const bool depth = ring_has_depth(c);
+    const bool depth = dl.depth.spec.on();
     if (depth && group && !c->comm.depth.on())   // (refused before anything else is looked at: nothing enqueued, no slot taken)
         return fail(c, GSR_ERR_ARG, "gsr_deliver_frame_async: this context joined a group after it opened a depth ring: depth is not exchanged "
                                     "between ranks, so a gathered frame has no depth plane to deliver (gsr_delivery_close, then a ring without depth)");
     if (depth && group) {   // the group exchanges depth: the gathered plane is delivered as it is, so the ring must have been opened for it
-        const gsr_ctx::Delivery::DepthPlane& dp = c->delivery.depth;
-        if (int r = exchange_mismatch(c, "gsr_deliver_frame_async", dp.format, dp.step, dp.near)) return r;
-        if (dp.Wd != c->comm.depth.Wd || dp.Hd != c->comm.depth.Hd)
+        if (int r = exchange_mismatch(c, "gsr_deliver_frame_async", dl.depth.spec)) return r;
+        if (dl.depth.planes.Wd != c->comm.depth.planes.Wd || dl.depth.planes.Hd != c->comm.depth.planes.Hd)
             return fail(c, GSR_ERR_ARG, "gsr_deliver_frame_async: the size changed since gsr_comm_set_depth: join the group again");
     }
     if (group ? !c->comm.frame8_valid : !c->have_frame)
         return fail(c, GSR_ERR_ARG, group ? "gsr_deliver_frame_async: no gathered frame yet (gsr_allgather_frame_async)" : "gsr_deliver_frame_async: nothing rendered yet");
     // a depth ring needs what gsr_depth_async needs of the frame; refused before a slot is looked for: nothing enqueued, no slot taken
     // (in a group the pass ran with the exchange: gsr_allgather_frame_async has asked the same of the frame it gathered)
-    if (depth && !group) { if (int r = delivery_depth_check(c, "gsr_deliver_frame_async (depth ring)")) return r; }
+    if (depth && !group) { if (int r = depth_frame_check(c, "gsr_deliver_frame_async (depth ring)")) return r; }
     DeliverySlot* sl = nullptr;
-    const int slots = (int)c->delivery.ring.size();
+    const int slots = (int)dl.ring.size();
     for (int k = 0; k < slots && !sl; k++) {
-        DeliverySlot& cand = c->delivery.ring[(size_t)((c->delivery.next + k) % slots)];
+        DeliverySlot& cand = dl.ring[(size_t)((dl.next + k) % slots)];
         if (cand.state == DeliverySlot::FREE) sl = &cand;
     }
     if (!sl) return fail(c, GSR_ERR_BUSY, "gsr_deliver_frame_async: all %d delivery slots are in flight or held (gsr_acquire_frame / gsr_release_frame)", slots);
     HIP_TRY(c, hipSetDevice(c->device));
-    const uint64_t k = c->delivery.serial + 1;
-    const size_t bytes = ring_slot_bytes(c);
-    const bool yuv = c->delivery.format != GSR_FORMAT_RGBA8;
-    hipError_t e;
-    if (group && depth) {
-        // exchange stream, behind the de-slab steps and in front of the next ones: the gathered colour into the slot's staging (a plain
-        // copy, or the conversion), the gathered plane as it is behind it with THE trailer (the stale mask its first word), then the
-        // slot's one copy to the host.  No depth pass: gsr_allgather_frame_async ran it for the frame it gathered.
-        const gsr_ctx::Comm::DepthExchange& dx = c->comm.depth;
-        const uint32_t* stale = c->comm.frame8 + (size_t)c->W * c->H;
-        e = hipSuccess;
-        if (yuv)
-            launch_deliver_yuv(c->delivery.format, nullptr, c->comm.frame8, reinterpret_cast<uint8_t*>(sl->staging.p), bytes, c->W, c->H, c->delivery.yuv, k, stale,
-                               c->comm.stream);
-        else
-            e = hipMemcpyAsync(sl->staging, c->comm.frame8, (size_t)c->W * c->H * 4, hipMemcpyDeviceToDevice, c->comm.stream);
-        launch_deliver_gathered_depth(dx.plane, (uint32_t)((dx.plane_bytes() + 3) / 4), reinterpret_cast<uint8_t*>(sl->staging.p), ring_depth_offset(c),
-                                      ring_trailer_offset(c), c->W, c->H, k, stale, c->comm.stream);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(sl->host, sl->staging, bytes, hipMemcpyDeviceToHost, c->comm.stream);
-        if (e == hipSuccess) e = hipEventRecord(sl->done, c->comm.stream);
-    } else if (group && yuv) {
-        // exchange stream, where the plain copy of an RGBA8 ring sits: the conversion reads the gathered frame behind its de-slab
-        // kernel and in front of the next one (its stale mask becomes the trailer's first word), the copy follows it there
-        launch_deliver_yuv(c->delivery.format, nullptr, c->comm.frame8, reinterpret_cast<uint8_t*>(sl->staging.p), bytes, c->W, c->H, c->delivery.yuv, k,
-                           c->comm.frame8 + (size_t)c->W * c->H, c->comm.stream);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(sl->host, sl->staging, bytes, hipMemcpyDeviceToHost, c->comm.stream);
-        if (e == hipSuccess) e = hipEventRecord(sl->done, c->comm.stream);
-    } else if (group) {
-        // the gathered frame and the word behind it (one bit per rank whose band is stale) are what k_unpack_slabs_rgba8 left on the
-        // exchange stream; the copy goes behind it there, in front of the next frame's de-slab
+    const uint64_t k = dl.serial + 1;
+    const size_t bytes = dl.slot_bytes();
+    const bool yuv = dl.format != GSR_FORMAT_RGBA8;
+    // The source.  The context's own frame: fb and the frame's overflow word; the work goes on the render stream (it has read fb, lists
+    // and records before the next frame's chain, which follows there, overwrites them), the copy on the copy stream behind ev_staged.
+    // A group's gathered frame: frame8 and the word behind it (one bit per rank whose band is stale), as the de-slab steps left them
+    // on the exchange stream; work and copy both go there, in front of the next frame's de-slab.
+    const float4* fb = group ? nullptr : c->out.fb.p;
+    const uint32_t* frame8 = group ? c->comm.frame8.p : nullptr;
+    const uint32_t* flag = group ? frame8 + (size_t)c->W * c->H : &c->words.fstate->overflow;
+    const hipStream_t work = group ? c->comm.stream : c->stream, copy = group ? c->comm.stream : dl.copy_stream;
+    uint8_t* const staging = reinterpret_cast<uint8_t*>(sl->staging.p);
+    const void* payload = staging;   // what the copy reads
+    hipError_t e = hipSuccess;
+    // 1. colour into the slot's staging, with a trailer (flag word, serial, size) behind it
+    if (yuv) {
+        launch_deliver_yuv(dl.format, fb, frame8, staging, bytes, c->W, c->H, dl.yuv, k, flag, work);
+    } else if (!group) {
+        launch_deliver_rgba8(fb, sl->staging, c->W, c->H, k, flag, work);
+    } else if (depth) {   // gathered pixels are RGBA8 already: a plain copy
+        e = hipMemcpyAsync(staging, frame8, (size_t)c->W * c->H * 4, hipMemcpyDeviceToDevice, work);
+    } else {              // and without a plane behind them the frame and its flag words are the slot, byte for byte: no staging
         static_assert(SLAB_FLAG_WORDS == DELIVER_TRAILER_WORDS, "the gathered frame's flag words are the delivered frame's trailer");
-        e = hipMemcpyAsync(sl->host, c->comm.frame8, bytes, hipMemcpyDeviceToHost, c->comm.stream);
-        if (e == hipSuccess) e = hipEventRecord(sl->done, c->comm.stream);
-    } else {
-        // render stream: the conversion only (it has read fb before the next frame's compositor starts); copy stream: the copy
-        if (yuv)
-            launch_deliver_yuv(c->delivery.format, c->out.fb, nullptr, reinterpret_cast<uint8_t*>(sl->staging.p), bytes, c->W, c->H, c->delivery.yuv, k,
-                               &c->words.fstate->overflow, c->stream);
-        else
-            launch_deliver_rgba8(c->out.fb, sl->staging, c->W, c->H, k, &c->words.fstate->overflow, c->stream);
-        if (depth) {
-            // behind the conversion, in front of ev_staged: the frame's depth pass into the ring's plane, then the plane into the slot and
-            // THE trailer behind it (the one the conversion wrote at the end of the colour payload lies under the padding and the plane).
-            // The next frame's chain follows on this stream, so lists, records and the ring's plane are read before they are overwritten.
-            const gsr_ctx::Delivery::DepthPlane& dp = c->delivery.depth;
-            if (int r = delivery_depth_enqueue(c)) return r;
-            launch_deliver_depth(dp.format, dp.hit, reinterpret_cast<uint8_t*>(sl->staging.p), ring_depth_offset(c), ring_trailer_offset(c), dp.Wd, dp.Hd,
-                                 dp.near, c->W, c->H, k, &c->words.fstate->overflow, c->stream);
-        }
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(c->delivery.ev_staged, c->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(c->delivery.copy_stream, c->delivery.ev_staged, 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(sl->host, sl->staging, bytes, hipMemcpyDeviceToHost, c->delivery.copy_stream);
-        if (e == hipSuccess) e = hipEventRecord(sl->done, c->delivery.copy_stream);
+        payload = frame8;
     }
+    // 2. the plane behind it, and THE trailer behind the plane (the one step 1 wrote lies under the padding and the plane)
+    if (depth && group) {   // (no pass: gsr_allgather_frame_async ran it for the frame it gathered)
+        const gsr_ctx::Comm::DepthExchange& dx = c->comm.depth;
+        launch_deliver_gathered_depth(dx.plane, (uint32_t)((dx.plane_bytes() + 3) / 4), staging, dl.depth_offset(), dl.trailer_offset(), c->W, c->H, k, flag, work);
+    } else if (depth) {     // the frame's pass into the ring's plane, then the plane into the slot
+        gsr_ctx::Delivery::DepthPlane& dp = dl.depth;
+        if (int r = depth_enqueue(c, dp.planes, dp.spec.step, DEPTH_FILL_HIT)) return r;
+        launch_deliver_depth(dp.spec.format, dp.planes.hit, staging, dl.depth_offset(), dl.trailer_offset(), dp.planes.Wd, dp.planes.Hd, dp.spec.near, c->W, c->H, k,
+                             flag, work);
+    }
+    // 3. the slot's one copy to the host, and `done` behind it
+    if (e == hipSuccess && payload == staging) e = hipGetLastError();   // (nothing was launched for a frame that goes as it is)
+    if (e == hipSuccess && copy != work) e = hipEventRecord(dl.ev_staged, work);
+    if (e == hipSuccess && copy != work) e = hipStreamWaitEvent(copy, dl.ev_staged, 0);
+    if (e == hipSuccess) e = hipMemcpyAsync(sl->host, payload, bytes, hipMemcpyDeviceToHost, copy);
+    if (e == hipSuccess) e = hipEventRecord(sl->done, copy);
     if (e != hipSuccess)   // (the slot was never marked taken: it is still on the free list)
         return fail(c, GSR_ERR_HIP, "gsr_deliver_frame_async: frame %llu: %s", (unsigned long long)k, hipGetErrorString(e));
-    sl->serial = c->delivery.serial = k;
+    sl->serial = dl.serial = k;
     sl->state = DeliverySlot::IN_FLIGHT;
-    c->delivery.next = (int)(sl - c->delivery.ring.data() + 1) % slots;
+    dl.next = (int)(sl - dl.ring.data() + 1) % slots;
     if (serial) *serial = k;
     return GSR_OK;
 }
@@ -368,7 +316,7 @@ int gsr_acquire_frame(gsr_ctx* c, uint64_t serial, gsr_frame* out)
         return fail(c, GSR_ERR_HIP, "gsr_acquire_frame: frame %llu: %s", (unsigned long long)sl->serial, hipGetErrorString(e));
     }
     uint32_t flag;   // the frame's overflow word; in a group: the ranks whose band is stale
-    memcpy(&flag, sl->host + ring_trailer_offset(c), 4);
+    memcpy(&flag, sl->host + c->delivery.trailer_offset(), 4);
     if (flag) {
         sl->state = DeliverySlot::FREE;
         return fail(c, GSR_ERR_OVERFLOW, "delivered frame %llu was not composited (flags 0x%x): its bin lists did not fit and the framebuffer kept "
@@ -397,7 +345,7 @@ void* gsr_delivery_slot_ptr(gsr_ctx* c, int32_t slot, uint64_t* bytes)
 {
     if (bytes) *bytes = 0;
     if (!c || slot < 0 || (size_t)slot >= c->delivery.ring.size()) return nullptr;
-    if (bytes) *bytes = ring_pixel_bytes(c);
+    if (bytes) *bytes = c->delivery.pixel_bytes();
     return c->delivery.ring[(size_t)slot].host;
 }
 

@@ -7,14 +7,8 @@
 
 using namespace gsr;
 
-namespace {
-
-constexpr uint32_t MAX_PICKS = 4096;
-static_assert(sizeof(PickResult) == sizeof(gsr_pick_result) && offsetof(PickResult, alpha) == offsetof(gsr_pick_result, alpha),
-              "the kernel's result is the header's");
-
 // the last enqueued frame can be walked: a render frame whose scene, size, band and lists are still the context's
-int check_frame(gsr_ctx* c, const char* who)
+int gsr::depth_frame_check(gsr_ctx* c, const char* who)
 {
     if (!c->have_frame) return fail(c, GSR_ERR_ARG, "%s: no frame has been rendered yet (or the scene or the size changed since the last one)", who);
     if (!c->timing.render) return fail(c, GSR_ERR_ARG, "%s: the last frame was sort-only: it has no bin lists", who);
@@ -25,8 +19,13 @@ int check_frame(gsr_ctx* c, const char* who)
     return GSR_OK;
 }
 
-// the frame's lists, records and positions, and the planes a pass writes: the context's (gsr_depth_async / gsr_read_depth), a
-// delivery ring's own (delivery_depth_enqueue), or none (gsr_pick)
+namespace {
+
+constexpr uint32_t MAX_PICKS = 4096;
+static_assert(sizeof(PickResult) == sizeof(gsr_pick_result) && offsetof(PickResult, alpha) == offsetof(gsr_pick_result, alpha),
+              "the kernel's result is the header's");
+
+// the frame's lists, records and positions, and the planes a pass writes (none: gsr_pick)
 DepthBuffers buffers(gsr_ctx* c, uint32_t* invalid, float* mean, float* hit, uint32_t* index)
 {
     DepthBuffers b{};
@@ -43,40 +42,18 @@ DepthBuffers buffers(gsr_ctx* c, uint32_t* invalid, float* mean, float* hit, uin
     return b;
 }
 
-int alloc_planes(gsr_ctx* c)
+// the context's planes pass behind whatever the stream holds; the planes are then those of the last enqueued frame
+int enqueue_planes(gsr_ctx* c)
 {
     gsr_ctx::Depth& d = c->depth;
     const size_t np = (size_t)c->W * c->H;
-    if (!d.invalid) {
-        if (int r = d.invalid.alloc(c, 2)) return r;
-        HIP_TRY(c, hipMemsetAsync(d.invalid, 0, 8, c->stream));
-    }
-    if (np > d.pixels || !d.mean) {
-        if (int r = d.mean.alloc(c, np)) return r;
-        if (int r = d.hit.alloc(c, np)) return r;
-        if (int r = d.index.alloc(c, np)) return r;
+    if (np > d.pixels || !d.planes.hit) {
+        if (int r = d.planes.alloc(c, c->W, c->H, 1)) return r;
         d.pixels = np;
-        d.fill_key[0] = 0;
         d.planes_serial = 0;
     }
-    return GSR_OK;
-}
-
-// the planes pass behind whatever the stream holds; the planes are then those of the last enqueued frame
-int enqueue_planes(gsr_ctx* c)
-{
-    if (int r = alloc_planes(c)) return r;
-    gsr_ctx::Depth& d = c->depth;
-    const BinGrid g = make_grid(c);
-    // a band context's bins do not cover the image: the other columns hold 0 / +inf / none, written when the planes, the
-    // size or the band are new (the pass itself writes the band's columns only)
-    const bool whole = g.bx_lo == 0 && g.bx_hi == g.nbx;
-    const int key[4] = {c->W, c->H, g.bx_lo, g.bx_hi};
-    if (!std::equal(key, key + 4, d.fill_key)) {
-        if (!whole) launch_depth_fill(d.mean, d.hit, d.index, (uint32_t)((size_t)c->W * c->H), c->stream);
-        std::copy(key, key + 4, d.fill_key);
-    }
-    launch_depth_planes(buffers(c, d.invalid, d.mean, d.hit, d.index), g, c->cam_frame, c->knobs.depth_skip, 1, c->stream);
+    d.planes.Wd = c->W; d.planes.Hd = c->H;   // (a smaller image than they were allocated for lies at their front)
+    if (int r = depth_enqueue(c, d.planes, 1, DEPTH_FILL_PLANES)) return r;
     HIP_TRY(c, hipGetLastError());
     d.planes_serial = c->frame_serial;
     return GSR_OK;
@@ -85,39 +62,29 @@ int enqueue_planes(gsr_ctx* c)
 // what gsr_sync does for the frame (a frame that did not fit is rendered again with regrown lists), then the frame's checks again
 int settle_frame(gsr_ctx* c, const char* who)
 {
-    if (int r = check_frame(c, who)) return r;
+    if (int r = depth_frame_check(c, who)) return r;
     if (int r = sync_and_repair(c)) return r;
-    return check_frame(c, who);   // (a regrowth for earlier frames may have taken the lists with it)
+    return depth_frame_check(c, who);   // (a regrowth for earlier frames may have taken the lists with it)
 }
 
 }  // namespace
 
-int gsr::delivery_depth_check(gsr_ctx* c, const char* who) { return check_frame(c, who); }
-
-// The pass of a depth ring, behind the frame on the render stream: the frame's lists with the frame's camera and the context's
-// hit_alpha of this moment, into the ring's own plane(s).  c->depth (the planes gsr_read_depth caches, planes_serial) is not touched.
-int gsr::delivery_depth_enqueue(gsr_ctx* c)
+// One pass for every user: the frame's lists with the frame's camera and the context's hit_alpha of this moment, into `p`.  A band
+// context's bins do not cover the image and the pass writes the band's columns only: what the user has in the others (`fill`) is
+// written when the planes, the size or the band are new.
+int gsr::depth_enqueue(gsr_ctx* c, DepthPlanes& p, int step, DepthFill fill)
 {
-    gsr_ctx::Delivery::DepthPlane& d = c->delivery.depth;
     const BinGrid g = make_grid(c);
-    // a band context's bins do not cover the image: the other columns' samples are +inf, written when the plane, the size or the
-    // band are new (the pass writes the band's columns only; step 1's scratch planes are never read)
-    const bool whole = g.bx_lo == 0 && g.bx_hi == g.nbx;
     const int key[4] = {c->W, c->H, g.bx_lo, g.bx_hi};
-    if (!std::equal(key, key + 4, d.fill_key)) {
-        if (!whole) HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)d.hit.p, 0x7f800000, (size_t)d.Wd * d.Hd, c->stream));
-        std::copy(key, key + 4, d.fill_key);
+    if (fill != DEPTH_FILL_NOTHING && !std::equal(key, key + 4, p.fill_key)) {
+        const bool whole = g.bx_lo == 0 && g.bx_hi == g.nbx;   // the bins cover the image: no other columns
+        const size_t np = (size_t)p.Wd * p.Hd;
+        if (!whole && fill == DEPTH_FILL_PLANES) launch_depth_fill(p.mean, p.hit, p.index, (uint32_t)np, c->stream);
+        if (!whole && fill == DEPTH_FILL_HIT) HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)p.hit.p, 0x7f800000, np, c->stream));
+        std::copy(key, key + 4, p.fill_key);
     }
-    launch_depth_planes(buffers(c, d.invalid, d.mean, d.hit, d.index), g, c->cam_frame, c->knobs.depth_skip, d.step, c->stream);
+    launch_depth_planes(buffers(c, p.invalid, p.mean, p.hit, p.index), g, c->cam_frame, c->knobs.depth_skip, step, c->stream);
     return GSR_OK;
-}
-
-// The pass of a group's depth exchange (gsr_comm_set_depth): the same launch behind the frame on the render stream, into the
-// exchange's plane(s).  Only this rank's bin columns are written and only they are packed, so nothing is filled beside them.
-void gsr::comm_depth_enqueue(gsr_ctx* c)
-{
-    gsr_ctx::Comm::DepthExchange& d = c->comm.depth;
-    launch_depth_planes(buffers(c, d.invalid, d.mean, d.hit, d.index), make_grid(c), c->cam_frame, c->knobs.depth_skip, d.step, c->stream);
 }
 
 extern "C" {
@@ -134,7 +101,7 @@ int gsr_set_hit_alpha(gsr_ctx* c, float a)
 int gsr_depth_async(gsr_ctx* c)
 {
     if (!c) return GSR_ERR_ARG;
-    if (int r = check_frame(c, "gsr_depth_async")) return r;
+    if (int r = depth_frame_check(c, "gsr_depth_async")) return r;
     HIP_TRY(c, hipSetDevice(c->device));
     return enqueue_planes(c);
 }
@@ -145,20 +112,20 @@ int gsr_read_depth(gsr_ctx* c, float* mean, float* hit, uint32_t* index)
     HIP_TRY(c, hipSetDevice(c->device));
     if (int r = settle_frame(c, "gsr_read_depth")) return r;
     gsr_ctx::Depth& d = c->depth;
-    if (!d.mean || d.planes_serial != c->frame_serial) {   // (a repaired frame has a new serial: a pass behind the unfit one is redone)
+    if (!d.planes.hit || d.planes_serial != c->frame_serial) {   // (a repaired frame has a new serial: a pass behind the unfit one is redone)
         if (int r = enqueue_planes(c)) return r;
     }
     uint32_t invalid = 0;
     const size_t np = (size_t)c->W * c->H;
-    HIP_TRY(c, hipMemcpyAsync(&invalid, d.invalid, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&invalid, d.planes.invalid, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (invalid) {   // never returned as data
         d.planes_serial = 0;
         return fail(c, GSR_ERR_OVERFLOW, "gsr_read_depth: the frame's bin lists did not fit: the planes are not valid");
     }
-    if (mean) HIP_TRY(c, hipMemcpyAsync(mean, d.mean, np * 4, hipMemcpyDeviceToHost, c->stream));
-    if (hit) HIP_TRY(c, hipMemcpyAsync(hit, d.hit, np * 4, hipMemcpyDeviceToHost, c->stream));
-    if (index) HIP_TRY(c, hipMemcpyAsync(index, d.index, np * 4, hipMemcpyDeviceToHost, c->stream));
+    if (mean) HIP_TRY(c, hipMemcpyAsync(mean, d.planes.mean, np * 4, hipMemcpyDeviceToHost, c->stream));
+    if (hit) HIP_TRY(c, hipMemcpyAsync(hit, d.planes.hit, np * 4, hipMemcpyDeviceToHost, c->stream));
+    if (index) HIP_TRY(c, hipMemcpyAsync(index, d.planes.index, np * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return GSR_OK;
 }
@@ -166,7 +133,8 @@ int gsr_read_depth(gsr_ctx* c, float* mean, float* hit, uint32_t* index)
 void* gsr_depth_device_ptr(gsr_ctx* c, int32_t plane)
 {
     if (!c) return nullptr;
-    return plane == 0 ? (void*)c->depth.mean : plane == 1 ? (void*)c->depth.hit : plane == 2 ? (void*)c->depth.index : nullptr;
+    const DepthPlanes& p = c->depth.planes;
+    return plane == 0 ? (void*)p.mean : plane == 1 ? (void*)p.hit : plane == 2 ? (void*)p.index : nullptr;
 }
 
 int gsr_pick(gsr_ctx* c, const int32_t* xy, uint32_t count, gsr_pick_result* out)
@@ -174,7 +142,7 @@ int gsr_pick(gsr_ctx* c, const int32_t* xy, uint32_t count, gsr_pick_result* out
     if (!c) return GSR_ERR_ARG;
     if (!xy || !out) return fail(c, GSR_ERR_ARG, "gsr_pick: xy or out is NULL");
     if (!count || count > MAX_PICKS) return fail(c, GSR_ERR_ARG, "gsr_pick: count must be 1..%u, not %u", MAX_PICKS, count);
-    if (int r = check_frame(c, "gsr_pick")) return r;
+    if (int r = depth_frame_check(c, "gsr_pick")) return r;
     const BinGrid g = make_grid(c);
     const int xlo = g.bx_lo * BIN_PX, xhi = std::min(g.bx_hi * BIN_PX, c->W);
     for (uint32_t k = 0; k < count; k++) {
@@ -185,19 +153,17 @@ int gsr_pick(gsr_ctx* c, const int32_t* xy, uint32_t count, gsr_pick_result* out
     HIP_TRY(c, hipSetDevice(c->device));
     if (int r = settle_frame(c, "gsr_pick")) return r;
     gsr_ctx::Depth& d = c->depth;
-    if (!d.invalid) {
-        if (int r = d.invalid.alloc(c, 2)) return r;
-        HIP_TRY(c, hipMemsetAsync(d.invalid, 0, 8, c->stream));
-    }
-    if (!d.query) {
+    if (!d.result) {
+        if (int r = d.pick_invalid.alloc(c, 1)) return r;
+        HIP_TRY(c, hipMemsetAsync(d.pick_invalid, 0, 4, c->stream));
         if (int r = d.query.alloc(c, (size_t)MAX_PICKS * 2)) return r;
         if (int r = d.result.alloc(c, MAX_PICKS)) return r;
     }
     HIP_TRY(c, hipMemcpyAsync(d.query, xy, (size_t)count * 8, hipMemcpyHostToDevice, c->stream));
-    launch_pick(buffers(c, d.invalid + 1, nullptr, nullptr, nullptr), g, c->cam_frame, d.query, count, d.result, c->stream);
+    launch_pick(buffers(c, d.pick_invalid, nullptr, nullptr, nullptr), g, c->cam_frame, d.query, count, d.result, c->stream);
     HIP_TRY(c, hipGetLastError());
     uint32_t invalid = 0;
-    HIP_TRY(c, hipMemcpyAsync(&invalid, d.invalid + 1, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&invalid, d.pick_invalid, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (invalid) return fail(c, GSR_ERR_OVERFLOW, "gsr_pick: the frame's bin lists did not fit: nothing was picked");
     HIP_TRY(c, hipMemcpyAsync(out, d.result, (size_t)count * sizeof(gsr_pick_result), hipMemcpyDeviceToHost, c->stream));

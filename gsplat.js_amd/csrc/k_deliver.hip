@@ -215,7 +215,7 @@ __global__ __launch_bounds__(DELIVER_THREADS) void k_deliver_depth(const float* 
                                                                    const uint32_t* __restrict__ overflow, [[maybe_unused]] uint32_t out_words)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        *reinterpret_cast<uint4*>(trailer) = make_uint4(*overflow, dims, serial_lo, serial_hi);   // (16-byte aligned: see ring_trailer_offset)
+        *reinterpret_cast<uint4*>(trailer) = make_uint4(*overflow, dims, serial_lo, serial_hi);   // (16-byte aligned: see gsr_ctx::Delivery::trailer_offset)
     }
     constexpr uint32_t PER_LANE = Format == DELIVER_DEPTH_F32 ? 4u : 8u;
     const uint32_t s = (blockIdx.x * DELIVER_THREADS + threadIdx.x) * PER_LANE;

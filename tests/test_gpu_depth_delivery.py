@@ -244,6 +244,44 @@ def test_band_context_delivers_its_columns_and_nothing_outside(gh, scenes):
     full.dispose(); band.dispose()
 
 
+def test_band_moves_under_an_open_ring(gh, scenes):
+    """The band moves while the ring -- and the context's own planes -- stay as they are: the columns the band left hold "nothing" again,
+    in the delivered plane (+inf, or 0 as u16) and in read_depth() (0, +inf, none: what test_gpu_depth.py::test_band_context asserts)."""
+    W, H = 192, 96
+    rows, data, pos = scenes(4000, 21)
+    cam = gh.orbit_camera(3, width=W, height=H)
+    full = gh.HIPRenderer(W, H)
+    full.set_raw_scene(data, pos)
+    full.set_camera(cam)
+    full.render_async()
+    planes = full.read_depth()
+    hit = planes[1]
+    bands = [(32, 96), (96, 160), (0, 0)]
+    assert all(np.isfinite(hit[:, x0:x1]).any() and np.isinf(hit[:, x0:x1]).any() for x0, x1 in bands[:2])
+    none = (np.float32(0).view(np.uint32), np.float32(np.inf).view(np.uint32), np.uint32(0xFFFFFFFF))
+    for fmt, step, empty in (("f32", 1, np.float32(np.inf)), ("u16", 2, np.uint16(0))):
+        band = gh.HIPRenderer(W, H, band=bands[0])
+        band.set_raw_scene(data, pos)
+        band.set_camera(cam)
+        band.open_delivery_depth(2, depth=fmt, depth_step=step, depth_near=0.5)      # one ring, open throughout
+        want = _want(hit, fmt, step, 0.5)
+        for j, (x0, x1) in enumerate(bands):
+            if j:
+                band.set_band(x0, x1)
+            s, _, depth = _deliver_one(band)
+            inside = np.zeros(W, bool)
+            inside[x0:x1 or W] = True
+            assert s == j + 1 and depth.shape == want.shape
+            assert np.array_equal(_bits(depth[:, inside[::step]]), _bits(want[:, inside[::step]])), (fmt, step, x0, x1)
+            assert (depth[:, ~inside[::step]] == empty).all(), (fmt, step, x0, x1)
+            for got, ref, rest in zip(band.read_depth(), planes, none):
+                assert np.array_equal(got.view(np.uint32)[:, inside], ref.view(np.uint32)[:, inside]), (fmt, step, x0, x1)
+                assert (got.view(np.uint32)[:, ~inside] == rest).all(), (fmt, step, x0, x1)
+        band.close_delivery()
+        band.dispose()
+    full.dispose()
+
+
 # ---- 8. the ring's promises ----
 def test_busy_release_resize_close_reopen(gh, scenes):
     r, cfg, W, H = _renderer(gh, scenes, "C1")
