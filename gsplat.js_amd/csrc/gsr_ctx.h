@@ -175,9 +175,7 @@ struct FrameArgs {
     BlendBuffers blend;
     float early_out_eps;
     uint32_t n;
-    uint32_t front_waves;    // waves per workgroup of the heavy front-end kernels: FRONT_WAVES_WIDE, or FRONT_WAVES_NARROW (gsr_internal.h)
     bool render;             // false: a sort-only frame (depth key + sort)
-    bool sort_culled;        // the sort keeps only the band's survivors (depth_index / keys are partial)
 };
 static_assert(std::is_trivially_copyable<FrameArgs>::value, "FrameArgs is compared and copied as bytes");
 
@@ -271,12 +269,12 @@ struct gsr_ctx {
         gsr::DevBuf<gsr::Record> rec;
         gsr::DevBuf<uint32_t> rect_idx;    // per splat: packed bin rectangle (k_project_key); rects holds them in depth order
         gsr::DevBuf<uint32_t> rects;
-        gsr::DevBuf<uint32_t> rect_tmp;    // the rectangles between the two LSD passes (rect_carry)
+        gsr::DevBuf<uint32_t> rect_tmp;    // the rectangles between the sort's two passes, where they are carried (SortPlan::carry)
         gsr::DevBuf<uint32_t> chunk_tab;   // bucket order: k_local_sort's work list
-        uint32_t blocks = 0, kpb = 0;
         uint32_t rows = 0;                 // splats the buffers above were allocated for
         int parity = 0;                    // which of the two sort-only slot sets the next sort-only frame uses
-        bool culled = false;               // the last sort kept only the band's survivors (depth_index / keys are partial)
+        gsr::SortPlan plan{};              // what the last enqueued frame's sort was launched from (plan_sort; valid while have_sort);
+                                           // plan.band: it kept only the band's survivors (depth_index / keys are partial)
     } sort;
 
     struct Bin {     // bin lists and compositor work items; sized by alloc_bins (gsr_frame.cpp)
@@ -441,6 +439,11 @@ inline BinGrid make_grid(const gsr_ctx* c)
 inline uint32_t front_waves_of(const gsr_ctx* c)
 {
     return c->knobs.front_waves ? c->knobs.front_waves : (c->opt.flags & GSR_FLAG_THROUGHPUT) ? FRONT_WAVES_NARROW : FRONT_WAVES_WIDE;
+}
+
+inline SortKnobs sort_knobs_of(const gsr_ctx* c)
+{
+    return SortKnobs{c->knobs.sort_order, c->knobs.sort_kpb, c->knobs.rect_carry ? 1u : 0u, c->knobs.rect_carry_bucket ? 1u : 0u};
 }
 
 // gsr_frame.cpp

@@ -32,14 +32,6 @@ constexpr uint32_t BLEND_WG_PER_CU_SUB2 = 3;
 constexpr uint32_t SUB2_MAX_BINS = 4096, SEG_LEN_MIN_SUB2 = 1024;
 constexpr uint32_t SEG_LEN_WHOLE_BIN = 0x7fffff00u;
 
-// Sort order.  Up to BUCKET_ORDER_MAX_N splats the radix sort runs high digit first with one workgroup per bucket
-// (four launches, k_sort.hip) -- unless the last sorted frame reported a bucket above LOCAL_BUCKET_LIMIT keys: depth
-// outliers stretch the key range and can put most of a scene into one bucket, which would serialise in its workgroup.
-// Then, for the first frame of a scene, and above BUCKET_ORDER_MAX_N (the average bucket alone needs several chunks)
-// it runs the LSD order (six launches).  Same permutation either way.  GSR_SORT_ORDER=lsd|bucket pins it.
-constexpr uint32_t BUCKET_ORDER_MAX_N = 3u << 20;
-constexpr uint32_t LOCAL_BUCKET_LIMIT = 48u << 10;
-
 // Work-item length.  With the saturation skip of k_blend a work item ends as soon as nothing it could still add can change
 // a bit of its pixels, and that needs the item to contain the splats that saturate it: a bin cut into 512-entry segments
 // never saturates inside one of them (every segment starts from transmittance 1), a bin processed as one item stops
@@ -64,13 +56,9 @@ constexpr uint32_t LONG_TILES_X2_EXACT = 9;   // one frame at a time: and at lea
 constexpr uint32_t LONG_TILES_X2_THROUGHPUT = 6;   // with frames in flight: 3 (scripts/policy_check.py: 2 M tiny splats, 1.9 tiles each, tau 264:
                                                    // long items -26 %; the C2 generator, 3.6 tiles each: +10 % at the same tau)
 
-inline bool use_bucket_order(const gsr_ctx* c)
-{
-    if (c->knobs.sort_order >= 0) return c->knobs.sort_order == 1;
-    if (c->scene->n > BUCKET_ORDER_MAX_N) return false;
-    const uint32_t largest = reinterpret_cast<volatile const uint32_t*>(c->words.mailbox)[2];   // low half of mailbox[1]
-    return largest <= LOCAL_BUCKET_LIMIT;   // 0xffffffff until a frame of this scene has reported
-}
+// keys in the largest high-digit bucket of the last sorted frame (the low half of mailbox[1]; 0xffffffff until a frame of this
+// scene has reported): what plan_sort picks the sort order from
+inline uint32_t largest_bucket_reported(const gsr_ctx* c) { return reinterpret_cast<volatile const uint32_t*>(c->words.mailbox)[2]; }
 
 bool band_is_partial(const BinGrid& g) { return g.bx_lo > 0 || g.bx_hi < g.nbx; }
 
@@ -80,17 +68,16 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
     memset(&a, 0, sizeof a);
     const BinGrid g = make_grid(c);
     const bool throughput = (c->opt.flags & GSR_FLAG_THROUGHPUT) != 0;
-    const bool bucket_order = use_bucket_order(c);
+    // the sort's form for this frame (plan_sort, k_sort.hip): the order, the width, whether the rectangles travel with the keys and
+    // whether the frame runs on a band's survivors; every pointer below that depends on one of them follows it.
     // band mode (a context that composites only part of the screen): the projection's workgroups pack their survivors (see
     // k_project_key) and only those are sorted and binned; the full depthIndex is produced on demand (gsr_read_depth_index)
-    const bool cull = render && band_is_partial(g);
+    const SortPlan sp = plan_sort(c->scene->n, c->sort.rows, front_waves_of(c), render, band_is_partial(g), largest_bucket_reported(c), sort_knobs_of(c));
     FrameState* fs = c->words.fstate;
     a.render = render;
     a.n = c->scene->n;
     a.grid = g;
     a.early_out_eps = c->opt.early_out_eps;
-    a.front_waves = front_waves_of(c);   // (the launchers keep the wide forms off the one-level 1080p chain)
-    a.sort_culled = cull && c->scene->n;   // (an empty frame sorts nothing, so nothing of it is partial)
 
     // a sort-only frame has its own slots (sets 1 and 2 in turn; set 0 belongs to the render frames and k_begin_frame)
     const size_t slot_set = (size_t)FRAME_SLOTS * FRAME_SLOT_WORDS;
@@ -104,8 +91,8 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
         a.proj.rec = c->sort.rec;
         a.proj.rect = c->sort.rect_idx;
         a.proj.overflow = &fs->overflow;
-        a.proj.kept = cull ? c->sort.kept.p : nullptr;
-        a.proj.kept_lane = cull ? c->sort.kept_lane.p : nullptr;
+        a.proj.kept = sp.band ? c->sort.kept.p : nullptr;
+        a.proj.kept_lane = sp.band ? c->sort.kept_lane.p : nullptr;
     }
 
     SortBuffers& sb = a.sort;
@@ -121,15 +108,13 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
     sb.rect = c->sort.rect_idx;
     sb.kept = c->sort.kept;
     sb.kept_lane = c->sort.kept_lane;
-    sb.koff = cull ? c->sort.koff.p : nullptr;
+    sb.koff = sp.band ? c->sort.koff.p : nullptr;
     sb.count = &fs->sorted_count;
-    sb.keys_per_block = c->sort.kpb;
-    sb.nblocks = c->sort.blocks;
-    sb.bucket_order = bucket_order ? 1 : 0;
+    sb.plan = sp;
     sb.max_bucket = reinterpret_cast<uint32_t*>(c->words.mailbox_dev + 1);
     sb.chunk_tab = c->sort.chunk_tab;
     sb.rect_tmp = c->sort.rect_tmp;
-    sb.rects_out = (render && c->knobs.rect_carry && (c->knobs.rect_carry_bucket || !bucket_order)) ? c->sort.rects.p : nullptr;
+    sb.rects_out = sp.carry ? c->sort.rects.p : nullptr;
     if (!render) return;
 
     const uint32_t queue_start = std::min<uint32_t>(c->bin.max_items, c->bin.blend_grid);
@@ -140,7 +125,7 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
     bb.slots = c->words.slots;
     bb.rect_idx = c->sort.rect_idx;
     bb.rects = c->sort.rects;
-    bb.rects_sorted = (c->scene->n && sb.rects_out) ? 1u : 0u;
+    bb.rects_sorted = sp.carry;
     bb.bin_total = c->bin.total;
     bb.bin_start = c->bin.start;
     bb.bin_start_pre = c->bin.start_pre;
@@ -238,7 +223,7 @@ int enqueue_chain(gsr_ctx* c, const FrameArgs& a, bool timing)
         HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)&a.sort.minmax[1], (int)0x80000000u, 1, s));
     }
     if (timing) HIP_TRY(c, hipEventRecord(ev[EV_PROJECT], s));
-    launch_sort(a.sort, a.n, s, a.front_waves);
+    launch_sort(a.sort, a.n, s);
     if (timing) HIP_TRY(c, hipEventRecord(ev[EV_SORT], s));
     if (a.render) {
         if (!a.n) {
@@ -503,7 +488,7 @@ int enqueue_frame(gsr_ctx* c, bool render)
     // (the parity names the slot set the last k_depth_key reset for its successor: it moves only when that kernel ran, which it
     // does not for an empty scene -- nothing else ever cleans the sort-only frames' two sets)
     if (!render && a.n) c->sort.parity ^= 1;
-    c->sort.culled = a.sort_culled;
+    c->sort.plan = a.sort.plan;
     if (timing) t.pending++;
     t.recorded = timing;
     t.render = render;
@@ -572,3 +557,13 @@ int sync_and_repair(gsr_ctx* c)
 }
 
 }  // namespace gsr
+
+// The plan the context's last enqueued frame sorted from, for tests (tests/test_gpu_sort_plan.py compares it with what
+// gsr_debug_sort_plan answers for the context's inputs).  GSR_ERR_ARG before a first frame.  Not part of the ABI.
+extern "C" int gsr_debug_last_sort_plan(gsr_ctx* c, SortPlan* out)
+{
+    if (!c || !out) return GSR_ERR_ARG;
+    if (!c->have_sort) return fail(c, GSR_ERR_ARG, "no sort has run yet");
+    *out = c->sort.plan;
+    return GSR_OK;
+}

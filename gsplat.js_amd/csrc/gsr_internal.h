@@ -50,8 +50,9 @@ constexpr uint32_t BBOX_INVISIBLE_Y = 1u;
 
 // Bin rectangle of a splat's pixel box inside a context's band of bin columns [bx_lo, bx_hi), packed in 4 bytes:
 // x0 | x1 << 8 | y0 << 16 | y1 << 24 (inclusive bin coordinates, x relative to the band; at most 256 bins per axis);
-// 1 = nothing to draw.  Written once per splat by k_project_key.  In the LSD sort order they travel through the radix passes
-// with the keys (SortBuffers::rects_out); in the bucket order k_bin_count gathers them into depth order (4-byte gathers).
+// 1 = nothing to draw.  Written once per splat by k_project_key.  Where the sort plan says so (SortPlan::carry: the LSD order,
+// the bucket order only with GSR_RECT_CARRY=2) they travel through the sort's passes with the keys (SortBuffers::rects_out);
+// otherwise k_bin_count gathers them into depth order (4-byte gathers).
 constexpr uint32_t RECT_NONE = 1u;
 __host__ __device__ inline uint32_t pack_bin_rect(uint32_t bbx, uint32_t bby, int bx_lo, int bx_hi)
 {
@@ -174,9 +175,42 @@ void launch_project_key(ProjectLaunch& a, hipStream_t s);
 
 // Waves per workgroup of the four heavy front-end kernels of the one-level 1080p chain (k_scatter's bucket-order pass, k_local_sort,
 // k_bin_count, k_bin_scatter): WIDE everywhere, NARROW in throughput contexts, where a front-end workgroup has to fit the wave
-// slots and registers that retiring compositor workgroups of the other frames free on a CU (FrameArgs::front_waves).  A
+// slots and registers that retiring compositor workgroups of the other frames free on a CU (SortPlan::waves, BinPlan::form).  A
 // workgroup owns the same keys / ranks and the same table row at either width, and both widths write the same bits.
 constexpr uint32_t FRONT_WAVES_WIDE = 16, FRONT_WAVES_NARROW = 8;
+
+// The sort plan: which of k_sort.hip's forms a frame runs, on what, with what grids and LDS sizes.  plan_sort (k_sort.hip) is
+// the one place that decides it; alloc_sort sizes the buffers from sort_sizes, build_frame_args asks plan_sort once per frame
+// (the order depends on the bucket size the last frame reported) and takes every pointer that depends on the form from the
+// answer, launch_sort launches from it, and -- being part of SortBuffers, hence of FrameArgs -- a captured graph is dropped
+// exactly when it changes.  Trivially copyable, filled by name into zeroed storage (FrameArgs is compared as bytes).
+enum SortForm : uint32_t {
+    SORT_NONE = 0,            // a scene without splats: no launch
+    SORT_LSD,                 // low digit, then high digit: k_quantise_hist, scan, k_scatter<8>, k_hist_hi, scan, k_scatter<9> (6 launches)
+    SORT_BUCKET_WIDE,         // high digit first, then one workgroup per bucket chunk: k_quantise_hist, scan, k_scatter<9>, k_local_sort<16> (4 launches)
+    SORT_BUCKET_NARROW,       // the same at FRONT_WAVES_NARROW (throughput contexts): k_scatter<9, .., 8>, k_local_sort<8>
+};
+struct SortPlan {
+    uint32_t form;               // SortForm
+    uint32_t carry;              // 1: the packed bin rectangles travel with the keys (SortBuffers::rects_out is set)
+    uint32_t band;               // 1: the kernels run on the band's survivors (SortBuffers::koff is set)
+    uint32_t keys_per_block;     // keys of a radix workgroup: 2048, 4096 or 8192
+    uint32_t blocks;             // radix workgroups = rows of block_hist in use: ceil(n / keys_per_block)
+    uint32_t waves;              // waves per workgroup of k_scatter and k_local_sort: FRONT_WAVES_WIDE, or _NARROW in the narrow form
+    uint32_t lds_first, lds_last;   // dynamic LDS bytes of the first and the last k_scatter pass (bucket forms: one pass, lds_last = 0)
+    uint32_t local_grid;         // bucket forms: the grid of k_local_sort (at least the frame's bucket chunks)
+    uint32_t proj_blocks;        // blocks of k_project_key: the `nb` of k_kept_scan and k_band_gather (band frames)
+};
+struct SortSizes {               // what the per-splat allocation of `rows` splats needs beside its n-word buffers, in words
+    uint32_t keys_per_block;
+    size_t block_hist, chunk_tab, kept, koff;
+};
+struct SortKnobs { int32_t sort_order; uint32_t sort_kpb, rect_carry, rect_carry_bucket; };   // Knobs::sort_order, sort_kpb, rect_carry, rect_carry_bucket
+// (n: the scene's splats; rows: the splats the buffers were allocated for, which picked the keys per block; front_waves:
+//  FRONT_WAVES_WIDE or _NARROW; cull: the frame composites a band; largest_bucket: the word the last sorted frame left in the
+//  mailbox, 0xffffffff before a scene's first.  No HIP call, no environment.)
+SortPlan plan_sort(uint32_t n, uint32_t rows, uint32_t front_waves, bool render, bool cull, uint32_t largest_bucket, const SortKnobs& k);
+SortSizes sort_sizes(uint32_t rows, const SortKnobs& k);
 
 // radix sort of the 17-bit keys; see k_sort.hip
 struct SortBuffers {
@@ -187,22 +221,21 @@ struct SortBuffers {
     uint32_t* keys_tmp;        // n   keys after pass 1
     uint32_t* idx_tmp;         // n   indices after pass 1
     uint32_t* depth_index;     // n   result
-    uint32_t* block_hist;      // nblocks * RADIX_HI_BINS
+    uint32_t* block_hist;      // plan.blocks rows of RADIX_HI_BINS (SortSizes::block_hist)
     uint32_t* digit_total;     // RADIX_LO_BINS + RADIX_HI_BINS
     const uint32_t* rect;      // per splat: packed bin rectangle of the projection (carried with the keys when rects_out is set)
     const uint32_t* kept;      // band mode (koff set): per 256 splats, the survivors k_project_key packed to the front of their
     const uint8_t* kept_lane;  //   depth slots, and the lane each came from: everybody else is absent from the sort
-    uint32_t* koff;            // band mode: n / 256 + 2 words: the survivors in front of every block (k_kept_scan); null otherwise
+    uint32_t* koff;            // band mode (plan.band): SortSizes::koff words: the survivors in front of every block (k_kept_scan); null otherwise
     uint32_t* count;           // out: keys the first pass kept (n, or the band's survivors) = entries of depth_index
-    uint32_t keys_per_block;
-    uint32_t nblocks;
-    int bucket_order;          // 1: high digit first + one workgroup per bucket (4 launches); 0: LSD (6 launches); see k_sort.hip
+    SortPlan plan;             // the form and its launch shapes (plan_sort)
     uint32_t* max_bucket;      // out: keys in the frame's largest high-digit bucket (host-mapped word)
-    uint32_t* chunk_tab;       // bucket order: 4 x (1 + n / 4096 + 258) words: k_local_sort's work list (k_scatter's first workgroup writes it)
-    uint32_t* rect_tmp;        // LSD order with rects_out: the rectangles after the first pass
-    uint32_t* rects_out;       // LSD order: out: the packed bin rectangles in depth order (null: not carried; the binning gathers them)
+    uint32_t* chunk_tab;       // bucket forms: SortSizes::chunk_tab words: k_local_sort's work list (k_scatter's first workgroup writes it)
+    uint32_t* rect_tmp;        // with rects_out, in either order: the rectangles after the first pass
+    uint32_t* rects_out;       // plan.carry: out: the packed bin rectangles in depth order -- in the LSD order by default, in the bucket order
+                               // too with GSR_RECT_CARRY=2 (null: not carried; the binning gathers them)
 };
-void launch_sort(const SortBuffers& b, uint32_t n, hipStream_t s, uint32_t front_waves = FRONT_WAVES_WIDE);
+void launch_sort(const SortBuffers& b, uint32_t n, hipStream_t s);
 // column scan (k_sort.hip), shared with the binning
 // (live: the frame holds *live keys or ranks, live_unit of them per table row: the rows behind are neither written nor scanned)
 void launch_column_scan(uint32_t* table, uint32_t* total, int ncols, uint32_t nrows, hipStream_t s, const uint32_t* live = nullptr, uint32_t live_unit = 1);

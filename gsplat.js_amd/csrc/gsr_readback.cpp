@@ -13,7 +13,7 @@ int gsr_read_depth_index(gsr_ctx* c, uint32_t* out)
     if (!c || !out) return c ? fail(c, GSR_ERR_ARG, "out is NULL") : GSR_ERR_ARG;
     if (!c->have_sort) return fail(c, GSR_ERR_ARG, "no sort has run yet");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (c->sort.culled) {  // the band's frame sorted only its survivors: the caller wants the whole permutation
+    if (c->sort.plan.band) {  // the band's frame sorted only its survivors: the caller wants the whole permutation
         if (int r = enqueue_frame(c, false)) return r;
         if (int r = finish_frame(c)) return r;
     }
@@ -47,7 +47,7 @@ int gsr_read_keys(gsr_ctx* c, uint32_t* keys, int32_t* minmax)
     if (!c) return GSR_ERR_ARG;
     if (!c->have_sort) return fail(c, GSR_ERR_ARG, "no sort has run yet");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (c->sort.culled) {
+    if (c->sort.plan.band) {
         if (int r = enqueue_frame(c, false)) return r;
         if (int r = finish_frame(c)) return r;
     }

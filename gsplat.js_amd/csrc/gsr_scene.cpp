@@ -13,21 +13,14 @@ int alloc_sort(gsr_ctx* c, uint32_t n)
 {
     gsr_ctx::Sort& so = c->sort;
     so.rows = 0;
+    const SortSizes z = sort_sizes(n, sort_knobs_of(c));   // (k_sort.hip: what the sort's tables need for n rows)
     int r;
     if ((r = so.depth.alloc(c, n)) || (r = so.keys.alloc(c, n)) ||
         (r = so.keys_tmp.alloc(c, n)) || (r = so.idx_tmp.alloc(c, n)) || (r = so.depth_index.alloc(c, n)) || (r = so.rec.alloc(c, n)) ||
         (r = so.rects.alloc(c, n)) || (r = so.rect_idx.alloc(c, n)) || (r = so.rect_tmp.alloc(c, n)) ||
-        (r = so.chunk_tab.alloc(c, 4 * ((size_t)n / 4096 + 260))) ||
-        (r = so.kept.alloc(c, (size_t)n / PROJ_THREADS + 1)) || (r = so.kept_lane.alloc(c, n)) ||
-        (r = so.koff.alloc(c, (size_t)n / PROJ_THREADS + 2)))
+        (r = so.chunk_tab.alloc(c, z.chunk_tab)) || (r = so.kept.alloc(c, z.kept)) || (r = so.kept_lane.alloc(c, n)) ||
+        (r = so.koff.alloc(c, z.koff)) || (r = so.block_hist.alloc(c, z.block_hist)))
         return r;
-    // keys per radix workgroup: the scatter stores runs of keys_per_block / 2^bits keys, so larger scenes take larger
-    // blocks (longer runs) while small ones keep enough workgroups to fill the chip.  Measured at 20 M splats, the two
-    // scatters: 135 + 126 us with 2048 keys, 99 + 98 us with 4096, 113 + 116 us with 8192 (96 KiB of LDS: one
-    // workgroup per CU, nothing overlaps its load and store phases).
-    so.kpb = c->knobs.sort_kpb ? c->knobs.sort_kpb : n <= (3u << 20) ? 2048 : 4096;
-    so.blocks = (n + so.kpb - 1) / so.kpb;
-    if ((r = so.block_hist.alloc(c, (size_t)std::max(so.blocks, 1u) * RADIX_HI_BINS))) return r;
     so.rows = n;
     return GSR_OK;
 }
@@ -111,14 +104,13 @@ void gsr::scene_release(gsr_ctx* c)
 }
 
 // A member whose scene was replaced through another one (limitBox, new SH textures) does here, before its next frame, what the
-// call did for the context it ran on: the sort's blocks for the new count, the evaluated colours, the binning's plan and buffers.
+// call did for the context it ran on: the sort's buffers where the new count needs larger ones, the evaluated colours, the binning's plan and buffers.
 int gsr::adopt_scene(gsr_ctx* c)
 {
     SharedScene& sc = *c->scene;
     if (c->scene_gen == sc.generation) return GSR_OK;
     c->have_frame = false; c->have_sort = false;
     if (sc.n > c->sort.rows) { if (int r = alloc_sort(c, sc.n)) return r; }
-    else c->sort.blocks = (sc.n + c->sort.kpb - 1) / c->sort.kpb;
     if (int r = alloc_bins(c)) return r;
     if (sc.sh_count) {
         if (int r = c->shcol.alloc(c, sc.n)) return r;
@@ -317,7 +309,6 @@ int gsr_scene_limit_box(gsr_ctx* c, const double* box, uint32_t* new_count)
         sc.arr_rows = n;   // (what `dst` was allocated for)
         sc.n = kept;   // arrays keep their old capacity; per-frame buffers sized for the old count still fit
         c->scene_gen = ++sc.generation;   // (this context follows below; the other members in adopt_scene, before their next frame)
-        c->sort.blocks = (kept + c->sort.kpb - 1) / c->sort.kpb;
         // The compaction renumbers the splats, so SH rows (indexed by splat - (bandsIndices[0] + 1)) and the band
         // thresholds no longer belong to them.  With gsr_set_sh_follow on they were renumbered with the scene: the kept rows
         // are in sh_dst, bandsIndices'[k] = (kept splats with index <= bandsIndices[k]) - 1, and the frame stays.  Otherwise

@@ -12,6 +12,8 @@
 // must match the reference bit for bit).
 #include "gsr_internal.h"
 
+#include <algorithm>
+#include <cstring>
 #include <mutex>
 
 namespace gsr {
@@ -337,7 +339,7 @@ void launch_column_scan(uint32_t* table, uint32_t* total, int ncols, uint32_t nr
 //   phase 3  rank with ballot matching and write (key, index) into LDS at the local position
 //   phase 4  stream the LDS image out: consecutive lanes hold consecutive local positions, so within a digit they store
 //            to consecutive addresses.
-// WAVES (16, or 8: the narrow form of throughput contexts, launch_sort) is the workgroup's width, not what it owns: the
+// WAVES (16, or 8: the narrow form of throughput contexts, plan_sort) is the workgroup's width, not what it owns: the
 // same keys_per_block keys, the same table row, each wave a contiguous WAVES-th of them in twice as many steps -- the
 // order above is the input order either way, so both widths write the same bits.
 // Phase 4 is what the pass is about.  Storing straight from phase 3 gave every lane of a wave its own destination
@@ -345,7 +347,7 @@ void launch_column_scan(uint32_t* table, uint32_t* total, int ncols, uint32_t nr
 // stamps on C3: 4.4 of a workgroup's 7.1 us in the rank-and-store phase; at 20 M splats the pass reached 15 % of the
 // HBM roofline).  Staged, a store instruction covers one run per digit present among its 64 local positions:
 // keys_per_block / 2^BITS keys per run on average (8 for 2048 keys and 8 bits, 32 for 8192).  Larger scenes take
-// larger blocks (launch_sort) so that the runs are whole cache lines.
+// larger blocks (plan_sort) so that the runs are whole cache lines.
 // ---------------------------------------------------------------------------
 constexpr int SCAT_THREADS = 1024;
 constexpr int SCAT_WAVES = SCAT_THREADS / WAVE;
@@ -358,10 +360,9 @@ constexpr int scat_max_steps(int waves) { return waves == SCAT_WAVES ? SCAT_MAX_
 // (the bucket order's second kernel, k_local_sort below: one workgroup per LOCAL_CHUNK keys of a bucket)
 constexpr uint32_t LOCAL_CHUNK = 4096;                            // keys per workgroup: 16 waves x 4 steps of 64 keys, or 8 x 8
 
-template <int BITS>
-constexpr size_t scatter_lds_bytes(uint32_t keys_per_block, int waves = SCAT_WAVES)
+constexpr size_t scatter_lds_bytes(int bits, uint32_t keys_per_block, int waves = SCAT_WAVES)
 {
-    return (size_t)(waves * (1 << BITS) + 2 * (1 << BITS) + 3 * ((1 << BITS) / WAVE) + 2 * keys_per_block) * sizeof(uint32_t);
+    return (size_t)(waves * (1 << bits) + 2 * (1 << bits) + 3 * ((1 << bits) / WAVE) + 2 * keys_per_block) * sizeof(uint32_t);
 }
 
 // PAY: one more word per key travels with it (the splat's packed bin rectangle, from rect order to depth order in the two
@@ -561,7 +562,7 @@ __global__ __launch_bounds__(WAVES * WAVE) void k_scatter(const uint32_t* __rest
 // inside every digit) -- a redundant read of the bucket, which sits in L2 -- then ranks its chunk exactly like
 // k_scatter does and places it.  The redundant counting is quadratic in the bucket size, so a bucket holding most of
 // the scene (depth outliers stretch the key range) is slow this way: every frame reports its largest bucket to the
-// host, which falls back to the LSD order while that exceeds LOCAL_BUCKET_LIMIT (gsr_frame.cpp).
+// host, which falls back to the LSD order while that exceeds LOCAL_BUCKET_LIMIT (plan_sort).
 // ---------------------------------------------------------------------------
 inline uint32_t local_sort_grid(uint32_t n) { return (n + LOCAL_CHUNK - 1) / LOCAL_CHUNK + RADIX_HI_BINS / 2 + 1; }   // >= sum over buckets of ceil(size / chunk)
 // (a 2-D grid -- chunk x bucket, bucket starts handed over by the partition pass, no search -- was measured slower:
@@ -669,99 +670,170 @@ __global__ __launch_bounds__(WAVES * WAVE) void k_local_sort(const uint32_t* __r
     }
 }
 
-void launch_sort(const SortBuffers& b, uint32_t n, hipStream_t s, uint32_t front_waves)
+// ---------------------------------------------------------------------------
+// The plan: every choice between the forms above and every size that follows from it (SortPlan, gsr_internal.h).  The
+// thresholds live here and nowhere else; alloc_sort allocates by sort_sizes, build_frame_args asks plan_sort for every frame
+// and launch_sort launches by the answer.
+// ---------------------------------------------------------------------------
+// Keys per radix workgroup: the scatter stores runs of keys_per_block / 2^bits keys, so larger scenes take larger blocks
+// (longer runs) while small ones keep enough workgroups to fill the chip.  Measured at 20 M splats, the two scatters:
+// 135 + 126 us with 2048 keys, 99 + 98 us with 4096, 113 + 116 us with 8192 (96 KiB of LDS: one workgroup per CU, nothing
+// overlaps its load and store phases).  Chosen for the rows the buffers were allocated for; GSR_SORT_KPB pins it.
+constexpr uint32_t KPB_SMALL = 2048, KPB_LARGE = 4096, KPB_SMALL_MAX_ROWS = 3u << 20;
+// Sort order.  Up to BUCKET_ORDER_MAX_N splats the radix sort runs high digit first with one workgroup per bucket chunk
+// (four launches) -- unless the last sorted frame reported a bucket above LOCAL_BUCKET_LIMIT keys: depth outliers stretch
+// the key range and can put most of a scene into one bucket, which would serialise in its workgroups.  Then, for the first
+// frame of a scene (the word reads 0xffffffff), and above BUCKET_ORDER_MAX_N (the average bucket alone needs several
+// chunks) it runs the LSD order (six launches).  Same permutation either way.  GSR_SORT_ORDER=lsd|bucket pins it.
+constexpr uint32_t BUCKET_ORDER_MAX_N = 3u << 20;
+constexpr uint32_t LOCAL_BUCKET_LIMIT = 48u << 10;
+constexpr uint32_t CHUNK_TAB_SPARE = 2;   // entries of chunk_tab behind its header and one per workgroup of k_local_sort
+
+inline uint32_t keys_per_block_of(uint32_t rows, const SortKnobs& k) { return k.sort_kpb ? k.sort_kpb : rows <= KPB_SMALL_MAX_ROWS ? KPB_SMALL : KPB_LARGE; }
+inline uint32_t ceil_div(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a + b - 1u) / b); }
+
+SortSizes sort_sizes(uint32_t rows, const SortKnobs& k)
 {
-    if (!n) return;
-    const dim3 grid(b.nblocks), block(SORT_THREADS);
+    SortSizes z;
+    z.keys_per_block = keys_per_block_of(rows, k);
+    z.block_hist = (size_t)std::max(ceil_div(rows, z.keys_per_block), 1u) * RADIX_HI_BINS;
+    z.chunk_tab = 4 * ((size_t)1 + local_sort_grid(rows) + CHUNK_TAB_SPARE);   // uint4 entries: [0] the number of chunks, then one per chunk
+    z.kept = (size_t)ceil_div(rows, PROJ_THREADS) + 1;
+    z.koff = (size_t)ceil_div(rows, PROJ_THREADS) + 2;
+    return z;
+}
+
+SortPlan plan_sort(uint32_t n, uint32_t rows, uint32_t front_waves, bool render, bool cull, uint32_t largest_bucket, const SortKnobs& k)
+{
+    SortPlan p;
+    memset(&p, 0, sizeof p);
+    p.keys_per_block = keys_per_block_of(rows, k);
+    if (!n) return p;   // SORT_NONE (an empty frame sorts nothing, so nothing of it is carried or partial)
+    const bool bucket = k.sort_order >= 0 ? k.sort_order == 1 : (n <= BUCKET_ORDER_MAX_N && largest_bucket <= LOCAL_BUCKET_LIMIT);
+    // the narrow forms: same grid, same blocks, same table rows, half the waves per workgroup
+    const bool narrow = bucket && front_waves == FRONT_WAVES_NARROW && p.keys_per_block == NARROW_KEYS_PER_BLOCK;
+    p.form = !bucket ? SORT_LSD : narrow ? SORT_BUCKET_NARROW : SORT_BUCKET_WIDE;
+    p.waves = narrow ? FRONT_WAVES_NARROW : FRONT_WAVES_WIDE;
+    // carried in the LSD order; in the bucket order what k_bin_count saves, the two sort kernels pay (GSR_RECT_CARRY=2 asks for it)
+    p.carry = (render && k.rect_carry && (k.rect_carry_bucket || !bucket)) ? 1u : 0u;
+    p.band = (render && cull) ? 1u : 0u;
+    p.blocks = ceil_div(n, p.keys_per_block);
+    p.proj_blocks = ceil_div(n, PROJ_THREADS);
+    if (bucket) {
+        p.lds_first = (uint32_t)scatter_lds_bytes(RADIX_HI_BITS, p.keys_per_block, (int)p.waves);
+        p.local_grid = local_sort_grid(n);
+    } else {
+        p.lds_first = (uint32_t)scatter_lds_bytes(RADIX_LO_BITS, p.keys_per_block, (int)p.waves);
+        p.lds_last = (uint32_t)scatter_lds_bytes(RADIX_HI_BITS, p.keys_per_block, (int)p.waves);
+    }
+    return p;
+}
+
+// The plan and the sizes for tests (tests/test_sort_plan.py): no context and no device, so they answer wherever the library
+// loads.  gsr_debug_sort_plan returns sizeof(SortPlan), for the caller to check its idea of the layout against;
+// gsr_debug_sort_sizes stores sort_sizes(rows) as five 64-bit words in the struct's order and returns their number.
+extern "C" int gsr_debug_sort_plan(unsigned int n, unsigned int rows, unsigned int front_waves, int render, int cull, unsigned int largest_bucket,
+                                    int sort_order, unsigned int sort_kpb, int rect_carry, int rect_carry_bucket, SortPlan* out)
+{
+    *out = plan_sort(n, rows, front_waves, render != 0, cull != 0, largest_bucket,
+                     SortKnobs{sort_order, sort_kpb, rect_carry ? 1u : 0u, rect_carry_bucket ? 1u : 0u});
+    return (int)sizeof(SortPlan);
+}
+extern "C" int gsr_debug_sort_sizes(unsigned int rows, unsigned int sort_kpb, unsigned long long* out)
+{
+    const SortSizes z = sort_sizes(rows, SortKnobs{-1, sort_kpb, 1u, 0u});
+    out[0] = z.keys_per_block; out[1] = z.block_hist; out[2] = z.chunk_tab; out[3] = z.kept; out[4] = z.koff;
+    return 5;
+}
+
+// Every instantiation of the two templated kernels, once: the attribute raise and the launches both walk these.
+using ScatterFn = void (*)(const uint32_t*, const uint32_t*, uint32_t, uint32_t*, uint32_t, const uint32_t*, const uint32_t*, uint32_t*, uint32_t*,
+                           uint32_t*, const uint32_t*, uint32_t*, uint4*);
+using LocalSortFn = void (*)(const uint32_t*, const uint32_t*, const uint4*, uint32_t*, const uint32_t*, uint32_t*);
+struct ScatterKernel { ScatterFn fn; uint32_t waves; int bits; bool first, pay; };
+static const ScatterKernel SCATTER_KERNELS[] = {
+    {k_scatter<RADIX_LO_BITS, 0, true>, FRONT_WAVES_WIDE, RADIX_LO_BITS, true, false},                                        // LSD, first pass
+    {k_scatter<RADIX_LO_BITS, 0, true, true>, FRONT_WAVES_WIDE, RADIX_LO_BITS, true, true},
+    {k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, false>, FRONT_WAVES_WIDE, RADIX_HI_BITS, false, false},                          // LSD, last pass
+    {k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, false, true>, FRONT_WAVES_WIDE, RADIX_HI_BITS, false, true},
+    {k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, true>, FRONT_WAVES_WIDE, RADIX_HI_BITS, true, false},                            // bucket order's partition
+    {k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, true, true>, FRONT_WAVES_WIDE, RADIX_HI_BITS, true, true},
+    {k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, true, false, FRONT_WAVES_NARROW>, FRONT_WAVES_NARROW, RADIX_HI_BITS, true, false},   // ... narrow
+    {k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, true, true, FRONT_WAVES_NARROW>, FRONT_WAVES_NARROW, RADIX_HI_BITS, true, true},
+};
+struct LocalSortKernel { LocalSortFn fn; uint32_t waves; };
+static const LocalSortKernel LOCAL_SORT_KERNELS[] = {{k_local_sort<SCAT_WAVES>, FRONT_WAVES_WIDE}, {k_local_sort<FRONT_WAVES_NARROW>, FRONT_WAVES_NARROW}};
+
+static const ScatterKernel& scatter_kernel(int bits, bool first, bool pay, uint32_t waves)
+{
+    for (const ScatterKernel& k : SCATTER_KERNELS)
+        if (k.bits == bits && k.first == first && k.pay == pay && k.waves == waves) return k;
+    return SCATTER_KERNELS[0];   // (unreachable: plan_sort asks for no other combination)
+}
+static LocalSortFn local_sort_kernel(uint32_t waves) { return LOCAL_SORT_KERNELS[waves == LOCAL_SORT_KERNELS[0].waves ? 0 : 1].fn; }
+
+// The last pass needs more than the default 48 KiB of dynamic LDS even at 2048 keys: raise the limit once per device (the
+// attribute belongs to the device's copy of the kernel), to what the largest block of the kernel's width needs.
+// (contexts on different host threads may arrive here together: one flag per device, set exactly once)
+static void raise_scatter_lds()
+{
+    static std::once_flag once[64];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::call_once(once[dev >= 0 && dev < 64 ? dev : 0], [] {
+        for (const ScatterKernel& k : SCATTER_KERNELS)
+            (void)hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)scatter_lds_bytes(k.bits, k.waves * WAVE * scat_max_steps((int)k.waves), (int)k.waves));
+        (void)hipGetLastError();   // a failure shows up as the launch error
+    });
+}
+
+void launch_sort(const SortBuffers& b, uint32_t n, hipStream_t s)
+{
+    const SortPlan& p = b.plan;
+    if (p.form == SORT_NONE) return;
+    raise_scatter_lds();
+    const dim3 grid(p.blocks), block(SORT_THREADS);
     uint32_t* total_lo = b.digit_total;
     uint32_t* total_hi = b.digit_total + RADIX_LO_BINS;
-    const size_t lds_lo = scatter_lds_bytes<RADIX_LO_BITS>(b.keys_per_block), lds_hi = scatter_lds_bytes<RADIX_HI_BITS>(b.keys_per_block);
-    {   // the last pass needs more than the default 48 KiB of dynamic LDS even at 2048 keys: raise the limit once per
-        // device (the attribute belongs to the device's copy of the kernel), to what the largest block size needs
-        // (contexts on different host threads may arrive here together: one flag per device, set exactly once)
-        static std::once_flag once[64];
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        std::call_once(once[dev >= 0 && dev < 64 ? dev : 0], [] {
-            (void)hipFuncSetAttribute((const void*)k_scatter<RADIX_LO_BITS, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)scatter_lds_bytes<RADIX_LO_BITS>(SCAT_THREADS * SCAT_MAX_STEPS));
-            (void)hipFuncSetAttribute((const void*)k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)scatter_lds_bytes<RADIX_HI_BITS>(SCAT_THREADS * SCAT_MAX_STEPS));
-            (void)hipFuncSetAttribute((const void*)k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)scatter_lds_bytes<RADIX_HI_BITS>(SCAT_THREADS * SCAT_MAX_STEPS));
-            (void)hipFuncSetAttribute((const void*)k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)scatter_lds_bytes<RADIX_HI_BITS>(SCAT_THREADS * SCAT_MAX_STEPS));
-            (void)hipFuncSetAttribute((const void*)k_scatter<RADIX_LO_BITS, 0, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)scatter_lds_bytes<RADIX_LO_BITS>(SCAT_THREADS * SCAT_MAX_STEPS));
-            (void)hipFuncSetAttribute((const void*)k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)scatter_lds_bytes<RADIX_HI_BITS>(SCAT_THREADS * SCAT_MAX_STEPS));
-            (void)hipFuncSetAttribute((const void*)k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, true, false, FRONT_WAVES_NARROW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)scatter_lds_bytes<RADIX_HI_BITS>(NARROW_KEYS_PER_BLOCK, FRONT_WAVES_NARROW));
-            (void)hipFuncSetAttribute((const void*)k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, true, true, FRONT_WAVES_NARROW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)scatter_lds_bytes<RADIX_HI_BITS>(NARROW_KEYS_PER_BLOCK, FRONT_WAVES_NARROW));
-            (void)hipGetLastError();   // a failure shows up as the launch error
-        });
-    }
     // band mode: the survivors' offsets from the projection's per-block counts, then their depths and original indices dense
     // in keys_tmp[] / depth_index[] (both free: the first radix pass writes the one, the last kernel of the sort the other)
-    uint32_t* band_idx = b.koff ? b.depth_index : nullptr;
-    const uint32_t* live = b.koff ? b.count : nullptr;
-    const int32_t* depth_in = b.koff ? reinterpret_cast<const int32_t*>(b.keys_tmp) : b.depth;
-    if (b.koff) {
-        const uint32_t nb = (n + PROJ_THREADS - 1u) / PROJ_THREADS;
+    uint32_t* band_idx = p.band ? b.depth_index : nullptr;
+    const uint32_t* live = p.band ? b.count : nullptr;
+    const int32_t* depth_in = p.band ? reinterpret_cast<const int32_t*>(b.keys_tmp) : b.depth;
+    if (p.band) {
+        const uint32_t nb = p.proj_blocks;
         hipLaunchKernelGGL(k_kept_scan, dim3(1), dim3(KS_THREADS), (size_t)((nb + WAVE - 1u) / WAVE) * sizeof(uint32_t), s, b.kept, nb, b.koff, b.count);
         hipLaunchKernelGGL(k_band_gather, dim3((nb + BG_BLOCKS - 1) / BG_BLOCKS), dim3(BG_BLOCKS * WAVE), 0, s, b.depth, b.kept_lane, b.kept,
                            (const uint32_t*)b.koff, n, nb, reinterpret_cast<int32_t*>(b.keys_tmp), band_idx);
     }
-    if (b.bucket_order) {
-        // bucket order: partition by the high 9 bits, then one workgroup per bucket sorts by the low 8 (k_local_sort)
-        hipLaunchKernelGGL(k_quantise_hist, grid, block, 0, s, depth_in, b.slots, b.minmax, n, b.keys_per_block,
-                           live, b.keys, b.block_hist, RADIX_LO_BITS, RADIX_HI_BINS);
-        launch_column_scan(b.block_hist, total_hi, RADIX_HI_BINS, b.nblocks, s, live, b.keys_per_block);
-        uint4* tab = reinterpret_cast<uint4*>(b.chunk_tab);   // k_local_sort's work list, written by the partition pass's first workgroup
-        // the narrow forms: same grid, same blocks, same table rows, half the waves per workgroup
-        const bool narrow = front_waves == FRONT_WAVES_NARROW && b.keys_per_block == NARROW_KEYS_PER_BLOCK;
-#define GSR_LAUNCH_PARTITION(PAY, W, PAY_IN, PAY_OUT)                                                                                          \
-    hipLaunchKernelGGL((k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, true, PAY, W>), grid, dim3(W * WAVE),                                          \
-                       scatter_lds_bytes<RADIX_HI_BITS>(b.keys_per_block, W), s, (const uint32_t*)b.keys, (const uint32_t*)band_idx, n, b.count, \
-                       b.keys_per_block, (const uint32_t*)b.block_hist, (const uint32_t*)total_hi, b.keys_tmp, b.idx_tmp, b.max_bucket,       \
-                       (const uint32_t*)(PAY_IN), (uint32_t*)(PAY_OUT), tab)
-        if (b.rects_out && narrow) GSR_LAUNCH_PARTITION(true, FRONT_WAVES_NARROW, b.rect, b.rect_tmp);
-        else if (b.rects_out) GSR_LAUNCH_PARTITION(true, SCAT_WAVES, b.rect, b.rect_tmp);
-        else if (narrow) GSR_LAUNCH_PARTITION(false, FRONT_WAVES_NARROW, nullptr, nullptr);
-        else GSR_LAUNCH_PARTITION(false, SCAT_WAVES, nullptr, nullptr);
-#undef GSR_LAUNCH_PARTITION
-        if (narrow)
-            hipLaunchKernelGGL(k_local_sort<FRONT_WAVES_NARROW>, dim3(local_sort_grid(n)), dim3(FRONT_WAVES_NARROW * WAVE), 0, s, (const uint32_t*)b.keys_tmp,
-                               (const uint32_t*)b.idx_tmp, (const uint4*)tab, b.depth_index, (const uint32_t*)b.rect_tmp, b.rects_out);
-        else
-            hipLaunchKernelGGL(k_local_sort<SCAT_WAVES>, dim3(local_sort_grid(n)), dim3(SCAT_THREADS), 0, s, (const uint32_t*)b.keys_tmp,
-                               (const uint32_t*)b.idx_tmp, (const uint4*)tab, b.depth_index, (const uint32_t*)b.rect_tmp, b.rects_out);
+    // the first pass of either order: from the keys in splat order (the band's survivors: band_idx) to keys_tmp / idx_tmp, the
+    // carried rectangles from rect to rect_tmp
+    const bool bucket = p.form != SORT_LSD;
+    const int bits = bucket ? RADIX_HI_BITS : RADIX_LO_BITS;
+    uint32_t* total = bucket ? total_hi : total_lo;
+    uint4* tab = bucket ? reinterpret_cast<uint4*>(b.chunk_tab) : nullptr;   // k_local_sort's work list, written by the partition pass's first workgroup
+    hipLaunchKernelGGL(k_quantise_hist, grid, block, 0, s, depth_in, b.slots, b.minmax, n, p.keys_per_block, live, b.keys, b.block_hist,
+                       bucket ? RADIX_LO_BITS : 0, 1 << bits);
+    launch_column_scan(b.block_hist, total, 1 << bits, p.blocks, s, live, p.keys_per_block);
+    const ScatterFn first = scatter_kernel(bits, true, p.carry, p.waves).fn;
+    hipLaunchKernelGGL(first, grid, dim3(p.waves * WAVE), p.lds_first, s, (const uint32_t*)b.keys,
+                       (const uint32_t*)band_idx, n, b.count, p.keys_per_block, (const uint32_t*)b.block_hist, (const uint32_t*)total, b.keys_tmp,
+                       b.idx_tmp, bucket ? b.max_bucket : nullptr, p.carry ? b.rect : nullptr, p.carry ? b.rect_tmp : nullptr, tab);
+    if (bucket) {
+        // bucket order: the partition by the high 9 bits is done; one workgroup per bucket chunk sorts by the low 8
+        const LocalSortFn local = local_sort_kernel(p.waves);
+        hipLaunchKernelGGL(local, dim3(p.local_grid), dim3(p.waves * WAVE), 0, s, (const uint32_t*)b.keys_tmp, (const uint32_t*)b.idx_tmp,
+                           (const uint4*)tab, b.depth_index, (const uint32_t*)b.rect_tmp, b.rects_out);
         return;
     }
-    hipLaunchKernelGGL(k_quantise_hist, grid, block, 0, s, depth_in, b.slots, b.minmax, n, b.keys_per_block,
-                       live, b.keys, b.block_hist, 0, RADIX_LO_BINS);
-    launch_column_scan(b.block_hist, total_lo, RADIX_LO_BINS, b.nblocks, s, live, b.keys_per_block);
-    const bool carry = b.rects_out != nullptr;   // the packed rectangles travel with the keys (k_scatter, PAY)
-    if (carry)
-        hipLaunchKernelGGL((k_scatter<RADIX_LO_BITS, 0, true, true>), grid, dim3(SCAT_THREADS), lds_lo, s, (const uint32_t*)b.keys,
-                           (const uint32_t*)band_idx, n, b.count, b.keys_per_block, (const uint32_t*)b.block_hist,
-                           (const uint32_t*)total_lo, b.keys_tmp, b.idx_tmp, (uint32_t*)nullptr, b.rect, b.rect_tmp);
-    else
-        hipLaunchKernelGGL((k_scatter<RADIX_LO_BITS, 0, true>), grid, dim3(SCAT_THREADS), lds_lo, s, (const uint32_t*)b.keys,
-                           (const uint32_t*)band_idx, n, b.count, b.keys_per_block, (const uint32_t*)b.block_hist,
-                           (const uint32_t*)total_lo, b.keys_tmp, b.idx_tmp, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-    hipLaunchKernelGGL(k_hist_hi, grid, block, 0, s, (const uint32_t*)b.keys_tmp, (const uint32_t*)b.count, b.keys_per_block,
-                       b.block_hist);
-    launch_column_scan(b.block_hist, total_hi, RADIX_HI_BINS, b.nblocks, s, live, b.keys_per_block);
-    if (carry)
-        hipLaunchKernelGGL((k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, false, true>), grid, dim3(SCAT_THREADS), lds_hi, s, (const uint32_t*)b.keys_tmp,
-                           (const uint32_t*)b.idx_tmp, n, b.count, b.keys_per_block, (const uint32_t*)b.block_hist,
-                           (const uint32_t*)total_hi, (uint32_t*)nullptr, b.depth_index, b.max_bucket, (const uint32_t*)b.rect_tmp, b.rects_out);
-    else
-        hipLaunchKernelGGL((k_scatter<RADIX_HI_BITS, RADIX_LO_BITS, false>), grid, dim3(SCAT_THREADS), lds_hi, s, (const uint32_t*)b.keys_tmp,
-                           (const uint32_t*)b.idx_tmp, n, b.count, b.keys_per_block, (const uint32_t*)b.block_hist,
-                           (const uint32_t*)total_hi, (uint32_t*)nullptr, b.depth_index, b.max_bucket, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+    // LSD order: the second histogram and scan, and the pass by the high 9 bits into depth_index / rects_out
+    hipLaunchKernelGGL(k_hist_hi, grid, block, 0, s, (const uint32_t*)b.keys_tmp, (const uint32_t*)b.count, p.keys_per_block, b.block_hist);
+    launch_column_scan(b.block_hist, total_hi, RADIX_HI_BINS, p.blocks, s, live, p.keys_per_block);
+    const ScatterFn last = scatter_kernel(RADIX_HI_BITS, false, p.carry, p.waves).fn;
+    hipLaunchKernelGGL(last, grid, dim3(p.waves * WAVE), p.lds_last, s, (const uint32_t*)b.keys_tmp,
+                       (const uint32_t*)b.idx_tmp, n, b.count, p.keys_per_block, (const uint32_t*)b.block_hist, (const uint32_t*)total_hi,
+                       (uint32_t*)nullptr, b.depth_index, b.max_bucket, p.carry ? (const uint32_t*)b.rect_tmp : nullptr, b.rects_out, (uint4*)nullptr);
 }
 
 }  // namespace gsr

@@ -34,7 +34,7 @@ bucket order, where k_bin_count gathers them through depthIndex; GSR_SORT_ORDER=
 order, GSR_RECT_CARRY=2 carries them through the bucket order's kernels.  So every context renders two poses or more.
 
 The sort's narrow kernels (throughput contexts, bucket order) exist for 2048 keys per workgroup only, which is what
-every scene of up to 3 << 20 splats gets (gsr_scene.cpp): all the ragged sizes below reach them."""
+every scene of up to 3 << 20 splats gets (plan_sort, k_sort.hip): all the ragged sizes below reach them."""
 import os
 
 import numpy as np

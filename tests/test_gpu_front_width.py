@@ -1,4 +1,4 @@
-"""Front-end workgroup width (GSR_FRONT_WAVES, FrameArgs::front_waves): throughput contexts run the four heavy front-end
+"""Front-end workgroup width (GSR_FRONT_WAVES; SortPlan::waves and BinPlan::form in FrameArgs): throughput contexts run the four heavy front-end
 kernels of the one-level 1080p chain -- the bucket order's partition pass and k_local_sort, k_bin_count, k_bin_scatter --
 as 8-wave workgroups, default contexts as 16-wave ones.  A workgroup owns the same keys / ranks and the same table row at
 either width, so everything a frame leaves behind must be the same bits: depthIndex, every bin's start and entries, the
