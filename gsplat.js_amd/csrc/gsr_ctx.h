@@ -149,10 +149,23 @@ struct SharedScene {
     void drop_sh() { sh_count = 0; band[0] = band[1] = band[2] = -1; sh_r.reset(); sh_g.reset(); sh_b.reset(); reset_sh_frame();
                      for (auto& b : sh_spare) b.reset();
                      sh_rows = sh_spare_rows = 0; }
+    // The selection (gsr_select.cpp; DESIGN.md section 4, "Selection"): one bit per splat of THIS copy, so the members have one
+    // together.  Nothing is allocated until the first call that selects; a scene without buffers reads as all zeros.
+    struct Selection {
+        DevBuf<uint32_t> mask, scratch;   // `words` words each: the selection, and the picked set of the call in progress
+        DevBuf<uint32_t> counters;        // [0] the bits set after the last fold, [1] a picker's `invalid` word, [2..] per-workgroup sums
+        DevBuf<uint8_t> region;           // the region bytes of gsr_select_region: grows on demand
+        uint32_t words = 0;               // words `mask` and `scratch` were allocated for (even, >= ceil(n / 32))
+        uint32_t counter_words = 0;
+        size_t region_bytes = 0;
+        uint32_t count = 0;               // bits set: every call is blocking and returns with it final
+        void reset() { mask.reset(); scratch.reset(); counters.reset(); region.reset(); words = counter_words = 0; region_bytes = 0; count = 0; }
+        uint64_t bytes() const { return (uint64_t)words * 8 + (uint64_t)counter_words * 4 + region_bytes; }
+    } sel;
     // device bytes of the state the members hold once
     uint64_t bytes() const
     {
-        return (uint64_t)arr_rows * (7 * 4 + (arr.rot ? 32 : 0)) + ((uint64_t)sh_rows + sh_spare_rows) * 3 * 32;
+        return (uint64_t)arr_rows * (7 * 4 + (arr.rot ? 32 : 0)) + ((uint64_t)sh_rows + sh_spare_rows) * 3 * 32 + sel.bytes();
     }
 };
 
@@ -458,6 +471,10 @@ int alloc_scene(gsr_ctx* c, uint32_t n, bool with_rows);
 int adopt_scene(gsr_ctx* c);
 // the context leaves its scene (the last member frees it); c->scene is null afterwards
 void scene_release(gsr_ctx* c);
+// gsr_scene_limit_box from need_rows on, for either predicate (gsr_scene_erase_selected is the other caller): the kept splats, in
+// order, become the scene; SH state, generation, bins and the members' frame state as the header says of limitBox; the selection is
+// empty afterwards.  `what` names the caller in a HIP error.
+int scene_compact(gsr_ctx* c, const ScenePred& p, const char* what, uint32_t* kept_out);
 // gsr_comm.cpp
 void comm_release(gsr_ctx* c);
 // gsr_depth.cpp: the depth pass for the frame enqueued last.  depth_frame_check: what every pass demands of that frame (GSR_ERR_ARG,
@@ -465,6 +482,11 @@ void comm_release(gsr_ctx* c);
 // errors are left for the caller's hipGetLastError)
 int depth_frame_check(gsr_ctx* c, const char* who);
 int depth_enqueue(gsr_ctx* c, DepthPlanes& p, int step, DepthFill fill);
+// what gsr_pick and gsr_read_depth do first: gsr_sync's work for the frame (one that did not fit is rendered again), then the checks again
+int depth_settle_frame(gsr_ctx* c, const char* who);
+// gsr_read_depth up to its copies: the context's planes are the settled frame's (the pass is run if they are not) and final on the
+// device; GSR_ERR_OVERFLOW for planes a pass marked invalid
+int depth_planes_current(gsr_ctx* c, const char* who);
 // gsr_delivery.cpp
 int delivery_alloc(gsr_ctx* c, int slots);
 // what gsr_delivery_open_depth demands of depth options other than GSR_DEPTH_NONE (GSR_ERR_ARG, `who` in front of the message)

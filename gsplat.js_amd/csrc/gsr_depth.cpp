@@ -59,15 +59,32 @@ int enqueue_planes(gsr_ctx* c)
     return GSR_OK;
 }
 
+}  // namespace
+
 // what gsr_sync does for the frame (a frame that did not fit is rendered again with regrown lists), then the frame's checks again
-int settle_frame(gsr_ctx* c, const char* who)
+int gsr::depth_settle_frame(gsr_ctx* c, const char* who)
 {
     if (int r = depth_frame_check(c, who)) return r;
     if (int r = sync_and_repair(c)) return r;
     return depth_frame_check(c, who);   // (a regrowth for earlier frames may have taken the lists with it)
 }
 
-}  // namespace
+int gsr::depth_planes_current(gsr_ctx* c, const char* who)
+{
+    if (int r = depth_settle_frame(c, who)) return r;
+    gsr_ctx::Depth& d = c->depth;
+    if (!d.planes.hit || d.planes_serial != c->frame_serial) {   // (a repaired frame has a new serial: a pass behind the unfit one is redone)
+        if (int r = enqueue_planes(c)) return r;
+    }
+    uint32_t invalid = 0;
+    HIP_TRY(c, hipMemcpyAsync(&invalid, d.planes.invalid, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (invalid) {   // never returned as data
+        d.planes_serial = 0;
+        return fail(c, GSR_ERR_OVERFLOW, "%s: the frame's bin lists did not fit: the planes are not valid", who);
+    }
+    return GSR_OK;
+}
 
 // One pass for every user: the frame's lists with the frame's camera and the context's hit_alpha of this moment, into `p`.  A band
 // context's bins do not cover the image and the pass writes the band's columns only: what the user has in the others (`fill`) is
@@ -110,19 +127,9 @@ int gsr_read_depth(gsr_ctx* c, float* mean, float* hit, uint32_t* index)
 {
     if (!c) return GSR_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (int r = settle_frame(c, "gsr_read_depth")) return r;
+    if (int r = depth_planes_current(c, "gsr_read_depth")) return r;
     gsr_ctx::Depth& d = c->depth;
-    if (!d.planes.hit || d.planes_serial != c->frame_serial) {   // (a repaired frame has a new serial: a pass behind the unfit one is redone)
-        if (int r = enqueue_planes(c)) return r;
-    }
-    uint32_t invalid = 0;
     const size_t np = (size_t)c->W * c->H;
-    HIP_TRY(c, hipMemcpyAsync(&invalid, d.planes.invalid, 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (invalid) {   // never returned as data
-        d.planes_serial = 0;
-        return fail(c, GSR_ERR_OVERFLOW, "gsr_read_depth: the frame's bin lists did not fit: the planes are not valid");
-    }
     if (mean) HIP_TRY(c, hipMemcpyAsync(mean, d.planes.mean, np * 4, hipMemcpyDeviceToHost, c->stream));
     if (hit) HIP_TRY(c, hipMemcpyAsync(hit, d.planes.hit, np * 4, hipMemcpyDeviceToHost, c->stream));
     if (index) HIP_TRY(c, hipMemcpyAsync(index, d.planes.index, np * 4, hipMemcpyDeviceToHost, c->stream));
@@ -151,7 +158,7 @@ int gsr_pick(gsr_ctx* c, const int32_t* xy, uint32_t count, gsr_pick_result* out
         if (x < xlo || x >= xhi) return fail(c, GSR_ERR_ARG, "gsr_pick: pixel (%d, %d) is outside this context's band [%d, %d)", x, y, xlo, xhi);
     }
     HIP_TRY(c, hipSetDevice(c->device));
-    if (int r = settle_frame(c, "gsr_pick")) return r;
+    if (int r = depth_settle_frame(c, "gsr_pick")) return r;
     gsr_ctx::Depth& d = c->depth;
     if (!d.result) {
         if (int r = d.pick_invalid.alloc(c, 1)) return r;

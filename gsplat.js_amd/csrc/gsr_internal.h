@@ -82,13 +82,16 @@ void launch_build_scene(const uint8_t* rows, uint32_t n, const SceneDev& sc, hip
 void launch_scene_translate(uint32_t n, const SceneDev& sc, const double* t, hipStream_t s);
 void launch_scene_rotate(uint32_t n, const SceneDev& sc, const double* q_xyzw, hipStream_t s);
 void launch_scene_scale(uint32_t n, const SceneDev& sc, const double* sv, hipStream_t s);
-void launch_scene_limit_box(uint32_t n, const SceneDev& src, const SceneDev& dst, const double* box, uint32_t* block_count,
-                            uint32_t* total, hipStream_t s);
-// limitBox of a scene whose SH colour follows it, enqueued behind launch_scene_limit_box while `src` still holds the source
+// The order-preserving compaction (Scene.limitBox, gsr_scene_erase_selected) and which splats stay: those inside `box` (six f64,
+// limitBox's comparisons), or, with box null, those whose bit of the selection words `mask` equals `keep`.
+struct ScenePred { const double* box; const uint32_t* mask; uint32_t keep; };
+void launch_scene_compact(uint32_t n, const SceneDev& src, const SceneDev& dst, const ScenePred& p, uint32_t* block_count,
+                          uint32_t* total, hipStream_t s);
+// The compaction of a scene whose SH colour follows it, enqueued behind launch_scene_compact while `src` still holds the source
 // positions: count[1..3] <- the kept splats in front of bandsIndices[k] + 1 (count[0]: the total the scan left there), and the
 // 8-word rows of the kept SH splats of sh_in[0..2], in order, into sh_out[0..2] (sh_count rows each).
-void launch_scene_limit_box_sh(uint32_t n, const SceneDev& src, const double* box, const uint32_t* block_off, uint32_t* count,
-                               const int32_t* band, uint32_t sh_count, const uint32_t* const* sh_in, uint32_t* const* sh_out, hipStream_t s);
+void launch_scene_compact_sh(uint32_t n, const SceneDev& src, const ScenePred& p, const uint32_t* block_off, uint32_t* count,
+                             const int32_t* band, uint32_t sh_count, const uint32_t* const* sh_in, uint32_t* const* sh_out, hipStream_t s);
 // Scene.scales (3 f32 per splat, device memory) -> scl; and the scene back into the layouts of Scene.data (8 words per splat,
 // 16-byte aligned), positions and scales (3 f32 per splat): a null output is skipped.  Rotations need neither: `rot` IS
 // Scene.rotations' layout.
@@ -411,6 +414,35 @@ struct PickResult { uint32_t index; float depth, mean, alpha; };   // gsr_pick_r
 void launch_depth_planes(const DepthBuffers& b, const BinGrid& g, const CamParams& cam, bool skip, int step, hipStream_t s);
 void launch_pick(const DepthBuffers& b, const BinGrid& g, const CamParams& cam, const int32_t* xy, uint32_t count, PickResult* out, hipStream_t s);
 void launch_depth_fill(float* mean, float* hit, uint32_t* index, uint32_t npix, hipStream_t s);
+
+// Selection (k_select.hip; DESIGN.md section 4, "Selection"): one bit per splat of a scene, bit i & 31 of word i >> 5, bits at and
+// above n always 0.  The pickers set the picked splats' bits in a zeroed scratch mask; launch_select_apply folds it into the selection.
+constexpr int SELECT_CENTRE = 0, SELECT_HIT = 1;                                            // (GSR_SELECT_*)
+constexpr int SELOP_REPLACE = 0, SELOP_ADD = 1, SELOP_SUBTRACT = 2, SELOP_INTERSECT = 3,   // (GSR_SELOP_*)
+              SELOP_INVERT = 4;                                                             // gsr_selection_invert: S = ~S, the picked set is not read
+constexpr uint32_t SELECT_APPLY_THREADS = 256;   // words per workgroup of k_select_apply = words one entry of `block_sums` counts
+struct SelectRegion {
+    int32_t x0, y0, x1, y1;      // the pixel rectangle [x0, x1) x [y0, y1), inside the image and the context's band
+    const uint8_t* bytes;        // one byte per pixel of the rectangle, non-zero = inside; null: the whole rectangle
+    int32_t stride;              // bytes per row (>= x1 - x0)
+    uint32_t nbytes;             // what `bytes` holds: (y1 - y0 - 1) * stride + (x1 - x0)
+};
+struct SelectBuffers {
+    const uint32_t* bin_start;   // nbins + 1      (SELECT_CENTRE: the frame's lists and records, as DepthBuffers holds them)
+    const uint32_t* list;
+    const Record* rec;
+    const uint32_t* overflow;    // the frame's overflow word: non-zero = its lists did not fit, nothing of it may be walked
+    const uint32_t* index;       // SELECT_HIT: the hit-index plane, W x H
+    uint32_t* invalid;           // out: 1 when the picker refused the frame (nothing set), 0 otherwise
+    uint32_t* scratch;           // nwords, zeroed by the caller
+    uint32_t capacity;           // entries the list can hold
+    uint32_t nsplats, nwords;
+};
+void launch_select_region(int mode, const SelectBuffers& b, const BinGrid& g, const SelectRegion& r, hipStream_t s);
+// scratch <- the splats inside `box` (in_box of k_scene.hip): every word of it is stored, no zeroing needed
+void launch_select_box(uint32_t n, const float* px, const float* py, const float* pz, const double* box, uint32_t* scratch, uint32_t nwords, hipStream_t s);
+// sel <- sel (op) scratch, bits at and above n dropped; *count <- the bits set afterwards (block_sums: ceil(nwords / SELECT_APPLY_THREADS) words)
+void launch_select_apply(int op, uint32_t* sel, const uint32_t* scratch, uint32_t n, uint32_t nwords, uint32_t* block_sums, uint32_t* count, hipStream_t s);
 
 // multi-GPU exchange helpers (RGBA8 slabs of the all-gather)
 constexpr int MAX_SLABS = 16;

@@ -87,6 +87,7 @@ int gsr::alloc_scene(gsr_ctx* c, uint32_t n, bool with_rows)
     c->bin.plan.form = BIN_FINALIZE_ONLY;   // (no splats until the caller's alloc_bins plans for the new count: a frame in between only finalizes)
     if (c->words.mailbox) reinterpret_cast<volatile uint32_t*>(c->words.mailbox)[2] = 0xffffffffu;   // a new scene: LSD order until a frame reports
     sc.drop_sh();
+    sc.sel.reset();   // a new scene: the empty selection
     c->shcol.reset();
     int r;
     if ((r = sc.arr.alloc(c, n, with_rows)) || (r = alloc_sort(c, n))) return r;
@@ -175,6 +176,66 @@ int upload_scene(gsr_ctx* c, const uint32_t* data, const float* positions, const
 }
 
 }  // namespace
+
+// gsr_scene_limit_box and gsr_scene_erase_selected: the splats `p` keeps, in order, become the scene
+int gsr::scene_compact(gsr_ctx* c, const ScenePred& p, const char* what, uint32_t* kept_out)
+{
+    if (int r = need_rows(c)) return r;
+    const uint32_t n = c->scene->n;
+    uint32_t kept = 0;
+    if (n) {
+        SharedScene& sc = *c->scene;
+        if (int r = sync_members(c)) return r;   // the arrays are replaced: nothing of any member reads the old ones any more
+        if (int r = adopt_scene(c)) return r;    // (as in gsr_set_scene_sh: the generation below is the next one, never a skipped one)
+        const bool follow = sc.sh_follow && sc.sh_count;   // the SH textures are compacted with the scene
+        SceneArrays dst;   // the kept splats are compacted into a second set of arrays, which then becomes the scene
+        DevBuf<uint32_t> block_count, count;   // count: [0] kept splats, [1..3] those in front of bandsIndices[k] + 1 (follow)
+        uint32_t counts[4] = {0, 0, 0, 0};
+        int r;
+        if ((r = dst.alloc(c, n, true)) || (r = block_count.alloc(c, (n + 1023) / 1024)) || (r = count.alloc(c, 4))) return r;
+        launch_scene_compact(n, sc.arr.view(), dst.view(), p, block_count, count, c->stream);
+        if (follow) {
+            if (sc.sh_spare_rows < sc.sh_count) {   // the second set of textures: allocated on first use, then the two sets take turns
+                for (auto& b : sc.sh_spare)
+                    if ((r = b.alloc(c, (size_t)sc.sh_count * 8))) { sc.sh_spare_rows = 0; return r; }
+                sc.sh_spare_rows = sc.sh_count;
+            }
+            const uint32_t* in[3] = {sc.sh_r, sc.sh_g, sc.sh_b};
+            uint32_t* out[3] = {sc.sh_spare[0], sc.sh_spare[1], sc.sh_spare[2]};
+            launch_scene_compact_sh(n, sc.arr.view(), p, block_count, count, sc.band, sc.sh_count, in, out, c->stream);
+        }
+        hipError_t e1 = hipMemcpyAsync(counts, count, follow ? 16 : 4, hipMemcpyDeviceToHost, c->stream);
+        hipError_t e2 = hipStreamSynchronize(c->stream);
+        for (hipError_t e : {e1, e2, hipGetLastError()})
+            if (e != hipSuccess) return fail(c, GSR_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+        kept = counts[0];
+        std::swap(sc.arr, dst);
+        sc.arr_rows = n;   // (what `dst` was allocated for)
+        sc.n = kept;   // arrays keep their old capacity; per-frame buffers sized for the old count still fit
+        sc.sel.reset();   // the selection's bits are indices of the old numbering: the scene is left with the empty one (nothing is in flight)
+        c->scene_gen = ++sc.generation;   // (this context follows below; the other members in adopt_scene, before their next frame)
+        // The compaction renumbers the splats, so SH rows (indexed by splat - (bandsIndices[0] + 1)) and the band
+        // thresholds no longer belong to them.  With gsr_set_sh_follow on they were renumbered with the scene: the kept rows
+        // are in sh_dst, bandsIndices'[k] = (kept splats with index <= bandsIndices[k]) - 1, and the frame stays.  Otherwise
+        // the SH state is dropped and the scene falls back to its rgba8 colours until gsr_set_scene_sh is called again.
+        // (Scene.limitBox, Scene.ts:307-366, leaves shs_rgb / bandsIndices untouched, i.e. stale.)
+        const bool sh_kept = follow && kept > counts[1];
+        if (sh_kept) {
+            std::swap(sc.sh_r, sc.sh_spare[0]); std::swap(sc.sh_g, sc.sh_spare[1]); std::swap(sc.sh_b, sc.sh_spare[2]);
+            std::swap(sc.sh_rows, sc.sh_spare_rows);
+            sc.sh_count = kept - counts[1];
+            for (int k = 0; k < 3; k++) sc.band[k] = (int32_t)counts[1 + k] - 1;
+        }
+        else { sc.drop_sh(); c->shcol.reset(); }   // (no SH splat survived: cleared, as gsr_set_scene_sh with sh_count 0 clears it)
+        // the binning's plan for the new count (plan_bins): fewer splats can mean fewer rounds and so MORE table rows, which
+        // alloc_bins regrows; like every alloc_bins it drops what the last frame left in the lists (they index the old numbering)
+        if ((r = alloc_bins(c))) return r;
+        // (last: the context is whole whatever this returns) evaluated colours of the old numbering go, as gsr_set_scene_sh leaves them
+        if (sh_kept) HIP_TRY(c, hipMemsetAsync(c->shcol, 0, (size_t)kept * sizeof(float4), c->stream));
+    }
+    if (kept_out) *kept_out = kept;
+    return GSR_OK;
+}
 
 extern "C" {
 
@@ -276,60 +337,7 @@ int gsr_scene_limit_box(gsr_ctx* c, const double* box, uint32_t* new_count)
     if (box[0] >= box[1]) return fail(c, GSR_ERR_ARG, "xMin (%g) must be smaller than xMax (%g)", box[0], box[1]);   // Scene.ts:308-316
     if (box[2] >= box[3]) return fail(c, GSR_ERR_ARG, "yMin (%g) must be smaller than yMax (%g)", box[2], box[3]);
     if (box[4] >= box[5]) return fail(c, GSR_ERR_ARG, "zMin (%g) must be smaller than zMax (%g)", box[4], box[5]);
-    if (int r = need_rows(c)) return r;
-    const uint32_t n = c->scene->n;
-    uint32_t kept = 0;
-    if (n) {
-        SharedScene& sc = *c->scene;
-        if (int r = sync_members(c)) return r;   // the arrays are replaced: nothing of any member reads the old ones any more
-        if (int r = adopt_scene(c)) return r;    // (as in gsr_set_scene_sh: the generation below is the next one, never a skipped one)
-        const bool follow = sc.sh_follow && sc.sh_count;   // the SH textures are compacted with the scene
-        SceneArrays dst;   // the kept splats are compacted into a second set of arrays, which then becomes the scene
-        DevBuf<uint32_t> block_count, count;   // count: [0] kept splats, [1..3] those in front of bandsIndices[k] + 1 (follow)
-        uint32_t counts[4] = {0, 0, 0, 0};
-        int r;
-        if ((r = dst.alloc(c, n, true)) || (r = block_count.alloc(c, (n + 1023) / 1024)) || (r = count.alloc(c, 4))) return r;
-        launch_scene_limit_box(n, sc.arr.view(), dst.view(), box, block_count, count, c->stream);
-        if (follow) {
-            if (sc.sh_spare_rows < sc.sh_count) {   // the second set of textures: allocated on first use, then the two sets take turns
-                for (auto& b : sc.sh_spare)
-                    if ((r = b.alloc(c, (size_t)sc.sh_count * 8))) { sc.sh_spare_rows = 0; return r; }
-                sc.sh_spare_rows = sc.sh_count;
-            }
-            const uint32_t* in[3] = {sc.sh_r, sc.sh_g, sc.sh_b};
-            uint32_t* out[3] = {sc.sh_spare[0], sc.sh_spare[1], sc.sh_spare[2]};
-            launch_scene_limit_box_sh(n, sc.arr.view(), box, block_count, count, sc.band, sc.sh_count, in, out, c->stream);
-        }
-        hipError_t e1 = hipMemcpyAsync(counts, count, follow ? 16 : 4, hipMemcpyDeviceToHost, c->stream);
-        hipError_t e2 = hipStreamSynchronize(c->stream);
-        for (hipError_t e : {e1, e2, hipGetLastError()})
-            if (e != hipSuccess) return fail(c, GSR_ERR_HIP, "limitBox failed: %s", hipGetErrorString(e));
-        kept = counts[0];
-        std::swap(sc.arr, dst);
-        sc.arr_rows = n;   // (what `dst` was allocated for)
-        sc.n = kept;   // arrays keep their old capacity; per-frame buffers sized for the old count still fit
-        c->scene_gen = ++sc.generation;   // (this context follows below; the other members in adopt_scene, before their next frame)
-        // The compaction renumbers the splats, so SH rows (indexed by splat - (bandsIndices[0] + 1)) and the band
-        // thresholds no longer belong to them.  With gsr_set_sh_follow on they were renumbered with the scene: the kept rows
-        // are in sh_dst, bandsIndices'[k] = (kept splats with index <= bandsIndices[k]) - 1, and the frame stays.  Otherwise
-        // the SH state is dropped and the scene falls back to its rgba8 colours until gsr_set_scene_sh is called again.
-        // (Scene.limitBox, Scene.ts:307-366, leaves shs_rgb / bandsIndices untouched, i.e. stale.)
-        const bool sh_kept = follow && kept > counts[1];
-        if (sh_kept) {
-            std::swap(sc.sh_r, sc.sh_spare[0]); std::swap(sc.sh_g, sc.sh_spare[1]); std::swap(sc.sh_b, sc.sh_spare[2]);
-            std::swap(sc.sh_rows, sc.sh_spare_rows);
-            sc.sh_count = kept - counts[1];
-            for (int k = 0; k < 3; k++) sc.band[k] = (int32_t)counts[1 + k] - 1;
-        }
-        else { sc.drop_sh(); c->shcol.reset(); }   // (no SH splat survived: cleared, as gsr_set_scene_sh with sh_count 0 clears it)
-        // the binning's plan for the new count (plan_bins): fewer splats can mean fewer rounds and so MORE table rows, which
-        // alloc_bins regrows; like every alloc_bins it drops what the last frame left in the lists (they index the old numbering)
-        if ((r = alloc_bins(c))) return r;
-        // (last: the context is whole whatever this returns) evaluated colours of the old numbering go, as gsr_set_scene_sh leaves them
-        if (sh_kept) HIP_TRY(c, hipMemsetAsync(c->shcol, 0, (size_t)kept * sizeof(float4), c->stream));
-    }
-    if (new_count) *new_count = kept;
-    return GSR_OK;
+    return scene_compact(c, ScenePred{box, nullptr, 0u}, "limitBox", new_count);
 }
 
 int gsr_share_scene(gsr_ctx* c, gsr_ctx* from)

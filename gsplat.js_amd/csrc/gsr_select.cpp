@@ -1,0 +1,184 @@
+// Selection: one bit per splat of a scene, held with the scene (SharedScene::sel), changed by screen regions of the last rendered
+// frame, world boxes and the host's own words, and applied by gsr_scene_erase_selected, which compacts the scene exactly as
+// gsr_scene_limit_box does (scene_compact, gsr_scene.cpp).  Kernels: k_select.hip.  Every call is blocking and ends with a wait
+// for the context's stream, so the selection is final on the device when it returns -- which is also why the members of a shared
+// scene need no events between their calls.  A context that never calls these allocates nothing.
+#include "gsr_ctx.h"
+
+using namespace gsr;
+
+namespace {
+
+uint32_t words_of(uint32_t n) { return (n + 31u) / 32u; }
+
+// the selection's buffers for the scene's count, allocated (the mask zeroed) by the first call that needs them
+int ensure_selection(gsr_ctx* c)
+{
+    SharedScene& sc = *c->scene;
+    SharedScene::Selection& sel = sc.sel;
+    const uint32_t need = std::max((words_of(sc.n) + 1u) & ~1u, 2u);   // even: a wave's ballot is two whole words (k_select_box)
+    if (sel.words >= need && sel.mask) return GSR_OK;
+    // (the count only shrinks under a selection -- a new scene or a compaction resets it -- so there are no bits to carry over)
+    sel.reset();
+    const uint32_t cw = 2u + (need + SELECT_APPLY_THREADS - 1u) / SELECT_APPLY_THREADS;
+    int r;
+    if ((r = sel.mask.alloc(c, need)) || (r = sel.scratch.alloc(c, need)) || (r = sel.counters.alloc(c, cw))) { sel.reset(); return r; }
+    sel.words = need; sel.counter_words = cw;
+    HIP_TRY(c, hipMemsetAsync(sel.mask, 0, (size_t)need * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(sel.counters, 0, (size_t)cw * 4, c->stream));
+    return GSR_OK;
+}
+
+// selection <- selection (op) scratch on the device, its count back to the host: the end of every call that changes it
+int fold_and_count(gsr_ctx* c, int op, uint32_t* selected)
+{
+    SharedScene::Selection& sel = c->scene->sel;
+    launch_select_apply(op, sel.mask, sel.scratch, c->scene->n, sel.words, sel.counters + 2, sel.counters, c->stream);
+    uint32_t count = 0;
+    hipError_t e1 = hipMemcpyAsync(&count, sel.counters, 4, hipMemcpyDeviceToHost, c->stream);
+    hipError_t e2 = hipStreamSynchronize(c->stream);
+    for (hipError_t e : {e1, e2, hipGetLastError()})
+        if (e != hipSuccess) return fail(c, GSR_ERR_HIP, "selection update failed: %s", hipGetErrorString(e));
+    sel.count = count;
+    if (selected) *selected = count;
+    return GSR_OK;
+}
+
+bool op_ok(int32_t op) { return op >= GSR_SELOP_REPLACE && op <= GSR_SELOP_INTERSECT; }
+
+}  // namespace
+
+extern "C" {
+
+int gsr_select_region(gsr_ctx* c, const gsr_region* region, int32_t mode, int32_t op, uint32_t* selected)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (!region) return fail(c, GSR_ERR_ARG, "gsr_select_region: region is NULL");
+    const gsr_region& q = *region;
+    if (mode != GSR_SELECT_CENTRE && mode != GSR_SELECT_HIT) return fail(c, GSR_ERR_ARG, "gsr_select_region: unknown mode %d", mode);
+    if (!op_ok(op)) return fail(c, GSR_ERR_ARG, "gsr_select_region: unknown op %d", op);
+    if (q.reserved != 0) return fail(c, GSR_ERR_ARG, "gsr_select_region: reserved must be 0");
+    if (int r = depth_frame_check(c, "gsr_select_region")) return r;
+    if (!(0 <= q.x0 && q.x0 < q.x1 && q.x1 <= c->W && 0 <= q.y0 && q.y0 < q.y1 && q.y1 <= c->H))
+        return fail(c, GSR_ERR_ARG, "gsr_select_region: the rectangle [%d, %d) x [%d, %d) is empty or outside the %dx%d image", q.x0, q.x1, q.y0, q.y1,
+                    c->W, c->H);
+    const int w = q.x1 - q.x0, h = q.y1 - q.y0;
+    if (q.mask && q.mask_stride < w) return fail(c, GSR_ERR_ARG, "gsr_select_region: mask_stride (%d) is smaller than the rectangle's width (%d)", q.mask_stride, w);
+    const BinGrid g = make_grid(c);
+    const int xlo = g.bx_lo * BIN_PX, xhi = std::min(g.bx_hi * BIN_PX, c->W);
+    if (q.x0 < xlo || q.x1 > xhi)
+        return fail(c, GSR_ERR_ARG, "gsr_select_region: the rectangle's columns [%d, %d) are outside this context's band [%d, %d)", q.x0, q.x1, xlo, xhi);
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the frame as gsr_pick / gsr_read_depth have it: settled (one that did not fit is rendered again), in HIT mode with its planes
+    if (mode == GSR_SELECT_HIT) { if (int r = depth_planes_current(c, "gsr_select_region")) return r; }
+    else if (int r = depth_settle_frame(c, "gsr_select_region")) return r;
+    SharedScene& sc = *c->scene;
+    if (!sc.n) { if (selected) *selected = 0; return GSR_OK; }
+    if (int r = ensure_selection(c)) return r;
+    SharedScene::Selection& sel = sc.sel;
+
+    SelectRegion reg{q.x0, q.y0, q.x1, q.y1, nullptr, 0, 0u};
+    if (q.mask) {
+        const size_t nbytes = (size_t)(h - 1) * (size_t)q.mask_stride + (size_t)w;
+        if (nbytes > 0xffffffffull) return fail(c, GSR_ERR_ARG, "gsr_select_region: the region's bytes do not fit 32 bits");
+        if (nbytes > sel.region_bytes || !sel.region) {
+            sel.region_bytes = 0;
+            if (int r = sel.region.alloc(c, nbytes)) return r;
+            sel.region_bytes = nbytes;
+        }
+        HIP_TRY(c, hipMemcpyAsync(sel.region, q.mask, nbytes, hipMemcpyHostToDevice, c->stream));
+        reg.bytes = sel.region; reg.stride = q.mask_stride; reg.nbytes = (uint32_t)nbytes;
+    }
+    SelectBuffers b{};
+    b.bin_start = c->bin.start; b.list = c->bin.list; b.rec = c->sort.rec;
+    b.overflow = &c->words.fstate->overflow;
+    b.index = mode == GSR_SELECT_HIT ? (const uint32_t*)c->depth.planes.index : nullptr;
+    b.invalid = sel.counters + 1;
+    b.scratch = sel.scratch;
+    b.capacity = c->bin.capacity;
+    b.nsplats = sc.n; b.nwords = sel.words;
+    HIP_TRY(c, hipMemsetAsync(sel.scratch, 0, (size_t)sel.words * 4, c->stream));
+    launch_select_region(mode, b, g, reg, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    uint32_t invalid = 0;
+    HIP_TRY(c, hipMemcpyAsync(&invalid, sel.counters + 1, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (invalid) return fail(c, GSR_ERR_OVERFLOW, "gsr_select_region: the frame's bin lists did not fit: nothing was selected");
+    return fold_and_count(c, op, selected);
+}
+
+int gsr_select_box(gsr_ctx* c, const double* box, int32_t op, uint32_t* selected)
+{
+    if (!c || !box) return GSR_ERR_ARG;
+    if (!op_ok(op)) return fail(c, GSR_ERR_ARG, "gsr_select_box: unknown op %d", op);
+    if (box[0] >= box[1]) return fail(c, GSR_ERR_ARG, "xMin (%g) must be smaller than xMax (%g)", box[0], box[1]);   // as gsr_scene_limit_box
+    if (box[2] >= box[3]) return fail(c, GSR_ERR_ARG, "yMin (%g) must be smaller than yMax (%g)", box[2], box[3]);
+    if (box[4] >= box[5]) return fail(c, GSR_ERR_ARG, "zMin (%g) must be smaller than zMax (%g)", box[4], box[5]);
+    HIP_TRY(c, hipSetDevice(c->device));
+    SharedScene& sc = *c->scene;
+    if (!sc.n) { if (selected) *selected = 0; return GSR_OK; }
+    if (int r = ensure_selection(c)) return r;
+    launch_select_box(sc.n, sc.arr.px, sc.arr.py, sc.arr.pz, box, sc.sel.scratch, sc.sel.words, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return fold_and_count(c, op, selected);
+}
+
+int gsr_selection_set(gsr_ctx* c, const uint32_t* words, uint32_t nwords, int32_t op, uint32_t* selected)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (!op_ok(op)) return fail(c, GSR_ERR_ARG, "gsr_selection_set: unknown op %d", op);
+    SharedScene& sc = *c->scene;
+    const uint32_t need = words_of(sc.n);
+    if (words && nwords < need) return fail(c, GSR_ERR_ARG, "gsr_selection_set: nwords (%u) is smaller than ceil(%u / 32) = %u", nwords, sc.n, need);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!sc.n) { if (selected) *selected = 0; return GSR_OK; }
+    if (int r = ensure_selection(c)) return r;
+    HIP_TRY(c, hipMemsetAsync(sc.sel.scratch, 0, (size_t)sc.sel.words * 4, c->stream));
+    if (words) HIP_TRY(c, hipMemcpyAsync(sc.sel.scratch, words, (size_t)need * 4, hipMemcpyHostToDevice, c->stream));
+    return fold_and_count(c, op, selected);   // (host bits at and above n are dropped there)
+}
+
+int gsr_selection_invert(gsr_ctx* c, uint32_t* selected)
+{
+    if (!c) return GSR_ERR_ARG;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->scene->n) { if (selected) *selected = 0; return GSR_OK; }
+    if (int r = ensure_selection(c)) return r;
+    return fold_and_count(c, SELOP_INVERT, selected);
+}
+
+int gsr_read_selection(gsr_ctx* c, uint32_t* words, uint32_t nwords, uint32_t* selected)
+{
+    if (!c) return GSR_ERR_ARG;
+    const SharedScene& sc = *c->scene;
+    const uint32_t need = words_of(sc.n);
+    if (words && nwords < need) return fail(c, GSR_ERR_ARG, "gsr_read_selection: nwords (%u) is smaller than ceil(%u / 32) = %u", nwords, sc.n, need);
+    if (selected) *selected = sc.sel.mask ? sc.sel.count : 0u;
+    if (!words || !need) return GSR_OK;
+    if (!sc.sel.mask) {   // never selected in: all zeros
+        std::fill(words, words + need, 0u);
+        return GSR_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(words, sc.sel.mask, (size_t)need * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return GSR_OK;
+}
+
+int gsr_scene_erase_selected(gsr_ctx* c, int32_t keep_selected, uint32_t* new_count)
+{
+    if (!c) return GSR_ERR_ARG;
+    SharedScene& sc = *c->scene;
+    if (!sc.have_rows) return fail(c, GSR_ERR_ARG, "scene transforms need a scene built with gsr_set_scene_rows or gsr_set_scene_arrays");
+    const uint32_t n = sc.n, count = sc.sel.mask ? sc.sel.count : 0u;
+    // nothing to remove: nothing changes, the last frame stays valid (the count is the one the last fold left: every call is blocking)
+    if (!n || (keep_selected ? count == n : count == 0u)) {
+        if (new_count) *new_count = n;
+        return GSR_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int r = ensure_selection(c)) return r;   // (keep_selected with no selection yet: the zeroed mask, everything goes)
+    return scene_compact(c, ScenePred{nullptr, sc.sel.mask, keep_selected ? 1u : 0u}, "gsr_scene_erase_selected", new_count);
+}
+
+}  // extern "C"

@@ -142,13 +142,24 @@ __device__ __forceinline__ bool in_box(const SceneDev& sc, uint32_t i, const dou
     return x >= box[0] && x <= box[1] && y >= box[2] && y <= box[3] && z >= box[4] && z <= box[5];
 }
 
-struct Box { double v[6]; };
+// The compaction's predicate, "splat i stays": the kernels below are templates over it.  Box: limitBox's six comparisons;
+// MaskKeep: one bit per splat of a selection (k_select.hip: bit i & 31 of word i >> 5), the splats whose bit equals `keep` stay
+// (gsr_scene_erase_selected).  Both are called for i < n only.
+struct Box {
+    double v[6];
+    __device__ __forceinline__ bool operator()(const SceneDev& sc, uint32_t i) const { return in_box(sc, i, v); }
+};
+struct MaskKeep {
+    const uint32_t* words; uint32_t keep;
+    __device__ __forceinline__ bool operator()(const SceneDev&, uint32_t i) const { return ((words[i >> 5] >> (i & 31u)) & 1u) == keep; }
+};
 
-__global__ __launch_bounds__(BOX_THREADS) void k_box_count(uint32_t n, SceneDev sc, Box box, uint32_t* __restrict__ block_count)
+template <class Pred>
+__global__ __launch_bounds__(BOX_THREADS) void k_box_count(uint32_t n, SceneDev sc, Pred box, uint32_t* __restrict__ block_count)
 {
     __shared__ uint32_t s_w[BOX_THREADS / WAVE];
     const uint32_t i = blockIdx.x * BOX_THREADS + threadIdx.x;
-    const bool keep = i < n && in_box(sc, i, box.v);
+    const bool keep = i < n && box(sc, i);
     const uint64_t m = __ballot(keep);
     if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = (uint32_t)__popcll(m);
     __syncthreads();
@@ -179,13 +190,14 @@ __global__ __launch_bounds__(BOX_THREADS) void k_box_scan(uint32_t* __restrict__
     for (uint32_t b = b0; b < b1; b++) { const uint32_t v = block_count[b]; block_count[b] = run; run += v; }
 }
 
-__global__ __launch_bounds__(BOX_THREADS) void k_box_compact(uint32_t n, SceneDev src, SceneDev dst, Box box,
+template <class Pred>
+__global__ __launch_bounds__(BOX_THREADS) void k_box_compact(uint32_t n, SceneDev src, SceneDev dst, Pred box,
                                                              const uint32_t* __restrict__ block_off)
 {
     __shared__ uint32_t s_w[BOX_THREADS / WAVE];
     const uint32_t i = blockIdx.x * BOX_THREADS + threadIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool keep = i < n && in_box(src, i, box.v);
+    const bool keep = i < n && box(src, i);
     const uint64_t m = __ballot(keep);
     if (lane == 0) s_w[wave] = (uint32_t)__popcll(m);
     __syncthreads();
@@ -206,13 +218,14 @@ GSR_BOUNDS_DECL(scene_sh)   // sites: 0 source splat of k_box_thresholds, 1 SH r
 // One workgroup per threshold; it recounts the part of the threshold's block in front of it.
 struct BoxThresholds { uint32_t at[3]; };
 
-__global__ __launch_bounds__(BOX_THREADS) void k_box_thresholds(uint32_t n, SceneDev sc, Box box, const uint32_t* __restrict__ block_off,
+template <class Pred>
+__global__ __launch_bounds__(BOX_THREADS) void k_box_thresholds(uint32_t n, SceneDev sc, Pred box, const uint32_t* __restrict__ block_off,
                                                                 BoxThresholds th, uint32_t* __restrict__ count)
 {
     __shared__ uint32_t s_w[BOX_THREADS / WAVE];
     const uint32_t at = th.at[blockIdx.x];   // <= n
     const uint32_t block = at / BOX_THREADS, i = block * BOX_THREADS + threadIdx.x;
-    const bool keep = i < at && in_box(sc, i, box.v);   // (i < at <= n)
+    const bool keep = i < at && box(sc, i);   // (i < at <= n)
     if (keep) GSR_BOUND(scene_sh, 0, i, n);
     const uint64_t m = __ballot(keep);
     if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = (uint32_t)__popcll(m);
@@ -228,7 +241,8 @@ __global__ __launch_bounds__(BOX_THREADS) void k_box_thresholds(uint32_t n, Scen
 // k_box_compact's mask and offsets once more, for the SH rows: splat i > band0 owns row i - (band0 + 1) of each texture, 8 words
 // = two uint4; kept splat number o owns row o - count[1] of the compacted ones (count[1]: the kept splats without SH, above).
 // 96 bytes per kept SH splat, whole uint4 loads and stores.
-__global__ __launch_bounds__(BOX_THREADS) void k_box_compact_sh(uint32_t n, SceneDev src, Box box, const uint32_t* __restrict__ block_off,
+template <class Pred>
+__global__ __launch_bounds__(BOX_THREADS) void k_box_compact_sh(uint32_t n, SceneDev src, Pred box, const uint32_t* __restrict__ block_off,
                                                                 const uint32_t* __restrict__ count, int32_t band0, uint32_t sh_count,
                                                                 const uint4* __restrict__ r_in, const uint4* __restrict__ g_in,
                                                                 const uint4* __restrict__ b_in, uint4* __restrict__ r_out,
@@ -237,7 +251,7 @@ __global__ __launch_bounds__(BOX_THREADS) void k_box_compact_sh(uint32_t n, Scen
     __shared__ uint32_t s_w[BOX_THREADS / WAVE];
     const uint32_t i = blockIdx.x * BOX_THREADS + threadIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool keep = i < n && in_box(src, i, box.v);
+    const bool keep = i < n && box(src, i);
     const uint64_t m = __ballot(keep);
     if (lane == 0) s_w[wave] = (uint32_t)__popcll(m);
     __syncthreads();
@@ -339,30 +353,52 @@ void launch_scene_scale(uint32_t n, const SceneDev& sc, const double* sv, hipStr
 {
     if (n) hipLaunchKernelGGL(k_scene_scale, dim3((n + 255) / 256), dim3(256), 0, s, n, sc, sv[0], sv[1], sv[2]);
 }
-void launch_scene_limit_box(uint32_t n, const SceneDev& src, const SceneDev& dst, const double* box, uint32_t* block_count,
-                            uint32_t* total, hipStream_t s)
+namespace {
+
+template <class Pred>
+void compact_with(uint32_t n, const SceneDev& src, const SceneDev& dst, const Pred& b, uint32_t* block_count, uint32_t* total, hipStream_t s)
 {
-    if (!n) return;
-    Box b;
-    for (int k = 0; k < 6; k++) b.v[k] = box[k];
     const uint32_t nblocks = (n + BOX_THREADS - 1) / BOX_THREADS;
-    hipLaunchKernelGGL(k_box_count, dim3(nblocks), dim3(BOX_THREADS), 0, s, n, src, b, block_count);
+    hipLaunchKernelGGL(k_box_count<Pred>, dim3(nblocks), dim3(BOX_THREADS), 0, s, n, src, b, block_count);
     hipLaunchKernelGGL(k_box_scan, dim3(1), dim3(BOX_THREADS), 0, s, block_count, nblocks, total);
-    hipLaunchKernelGGL(k_box_compact, dim3(nblocks), dim3(BOX_THREADS), 0, s, n, src, dst, b, (const uint32_t*)block_count);
+    hipLaunchKernelGGL(k_box_compact<Pred>, dim3(nblocks), dim3(BOX_THREADS), 0, s, n, src, dst, b, (const uint32_t*)block_count);
 }
 
-void launch_scene_limit_box_sh(uint32_t n, const SceneDev& src, const double* box, const uint32_t* block_off, uint32_t* count,
-                               const int32_t* band, uint32_t sh_count, const uint32_t* const* sh_in, uint32_t* const* sh_out, hipStream_t s)
+template <class Pred>
+void compact_sh_with(uint32_t n, const SceneDev& src, const Pred& b, const uint32_t* block_off, uint32_t* count, const int32_t* band,
+                     uint32_t sh_count, const uint32_t* const* sh_in, uint32_t* const* sh_out, hipStream_t s)
 {
-    if (!n) return;
-    Box b;
-    for (int k = 0; k < 6; k++) b.v[k] = box[k];
     BoxThresholds th;
     for (int k = 0; k < 3; k++) th.at[k] = (uint32_t)std::min<int64_t>(std::max<int64_t>((int64_t)band[k] + 1, 0), (int64_t)n);
     const uint32_t nblocks = (n + BOX_THREADS - 1) / BOX_THREADS;
-    hipLaunchKernelGGL(k_box_thresholds, dim3(3), dim3(BOX_THREADS), 0, s, n, src, b, block_off, th, count);
-    hipLaunchKernelGGL(k_box_compact_sh, dim3(nblocks), dim3(BOX_THREADS), 0, s, n, src, b, block_off, (const uint32_t*)count, band[0], sh_count,
+    hipLaunchKernelGGL(k_box_thresholds<Pred>, dim3(3), dim3(BOX_THREADS), 0, s, n, src, b, block_off, th, count);
+    hipLaunchKernelGGL(k_box_compact_sh<Pred>, dim3(nblocks), dim3(BOX_THREADS), 0, s, n, src, b, block_off, (const uint32_t*)count, band[0], sh_count,
                        (const uint4*)sh_in[0], (const uint4*)sh_in[1], (const uint4*)sh_in[2], (uint4*)sh_out[0], (uint4*)sh_out[1], (uint4*)sh_out[2]);
+}
+
+Box box_of(const double* box)
+{
+    Box b;
+    for (int k = 0; k < 6; k++) b.v[k] = box[k];
+    return b;
+}
+
+}  // namespace
+
+void launch_scene_compact(uint32_t n, const SceneDev& src, const SceneDev& dst, const ScenePred& p, uint32_t* block_count,
+                          uint32_t* total, hipStream_t s)
+{
+    if (!n) return;
+    if (p.box) compact_with(n, src, dst, box_of(p.box), block_count, total, s);
+    else compact_with(n, src, dst, MaskKeep{p.mask, p.keep}, block_count, total, s);
+}
+
+void launch_scene_compact_sh(uint32_t n, const SceneDev& src, const ScenePred& p, const uint32_t* block_off, uint32_t* count,
+                             const int32_t* band, uint32_t sh_count, const uint32_t* const* sh_in, uint32_t* const* sh_out, hipStream_t s)
+{
+    if (!n) return;
+    if (p.box) compact_sh_with(n, src, box_of(p.box), block_off, count, band, sh_count, sh_in, sh_out, s);
+    else compact_sh_with(n, src, MaskKeep{p.mask, p.keep}, block_off, count, band, sh_count, sh_in, sh_out, s);
 }
 
 void launch_scene_import(const float* scales, uint32_t n, float4* scl, hipStream_t s)

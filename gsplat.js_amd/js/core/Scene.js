@@ -139,27 +139,32 @@ class Scene extends EventDispatcher {
             for (let j = 0; j < 3; j++) L[3 * i + j] = L[3 * i + j] * (1 / f[j]);
     }
 
-    // kind: 0 translate (x, y, z), 1 rotate (x, y, z, w), 2 scale (x, y, z), 3 limitBox (xMin, xMax, yMin, yMax, zMin, zMax).
+    // kind: 0 translate (x, y, z), 1 rotate (x, y, z, w), 2 scale (x, y, z), 3 limitBox (xMin, xMax, yMin, yMax, zMin, zMax),
+    // 4 eraseSelection ({ mask, keep }: the mask is set on the device copy, then erased there).
     // false: the edit has to run here (nothing attached, a host-only device scene among them, or buffers set by hand).
     _editDevices(kind, args) {
-        // (a device scene that cannot follow SH -- no setShFollow / readSh -- counts as host-only while the option is on)
+        // (a device scene that cannot follow SH -- no setShFollow / readSh -- counts as host-only while the option is on; so does
+        //  one that cannot take a selection -- no setSelection / eraseSelected -- for an eraseSelection)
         const cannotFollow = this._shFollowsTransforms && this._devices.some((d) => !d.setShFollow || !d.readSh);
-        if (!this._devices.length || this._diverged || cannotFollow || this._devices.some((d) => d.hostOnly)) {
+        const cannotErase = kind === 4 && this._devices.some((d) => !d.setSelection || !d.eraseSelected);
+        if (!this._devices.length || this._diverged || cannotFollow || cannotErase || this._devices.some((d) => d.hostOnly)) {
             this._refresh();
             this._refreshSh();
             return false;
         }
-        const f = new Float64Array(args);
+        const f = kind === 4 ? null : new Float64Array(args);
         let count = -1;
         for (const d of this._distinctDevices()) {
-            const c = d.transform(kind, f);
+            let c;
+            if (kind === 4) { d.setSelection(args.mask); c = d.eraseSelected(args.keep); }
+            else c = d.transform(kind, f);
             if (count >= 0 && c !== count) throw new Error("device scenes disagree on vertexCount (" + count + " and " + c + ")");
             count = c;
         }
         this._vertexCount = count;
         this._height = Math.ceil((2 * count) / this._width);
         this._stale = true;
-        if (kind === 3) {
+        if (kind === 3 || (kind === 4 && args.removes)) {   // (an erase that removes nothing leaves the device's SH state alone)
             if (this._shFollowsTransforms) this._shStale = this._shStale || this._shHeight > 0;   // compacted with the scene over there
             else this._shDroppedOnDevice = true;
         }
@@ -280,14 +285,36 @@ class Scene extends EventDispatcher {
         if (zMin >= zMax) throw new Error("zMin (" + zMin + ") must be smaller than zMax (" + zMax + ")");
         if (this._editDevices(3, [xMin, xMax, yMin, yMax, zMin, zMax])) return;
         const p = this._positions;
-        // with shFollowsTransforms the SH rows of the kept splats move up with them, and bandsIndices'[k] = (kept splats with
-        // index <= bandsIndices[k]) - 1
+        this._compact((i) => {
+            const x = p[3 * i], y = p[3 * i + 1], z = p[3 * i + 2];
+            return x >= xMin && x <= xMax && y >= yMin && y <= yMax && z >= zMin && z <= zMax;
+        });
+    }
+
+    // Remove the splats whose bit of `mask` is set -- splat i is bit i & 31 of word i >>> 5, the layout of the renderer's
+    // readSelection() -- or, with { keep: true }, the others: order-preserving, with limitBox's bookkeeping (SH rows and
+    // bandsIndices follow with shFollowsTransforms).  While device scenes are attached the mask is set on every distinct device
+    // copy and erased there (gsr_selection_set, gsr_scene_erase_selected); otherwise the same loop runs here.  Fires "change".
+    eraseSelection(mask, options) {
+        const keep = !!(options && options.keep), n = this._vertexCount, words = Math.ceil(n / 32);
+        if (!(mask instanceof Uint32Array) || mask.length < words) throw new Error("eraseSelection: mask must be a Uint32Array of at least " + words + " words");
+        const bit = (i) => (mask[i >>> 5] >>> (i & 31)) & 1, want = keep ? 1 : 0;
+        let kept = 0;
+        for (let i = 0; i < n; i++) if (bit(i) === want) kept++;
+        if (this._editDevices(4, { mask: mask, keep: keep, removes: kept < n })) return;
+        if (kept < n) this._compact((i) => bit(i) === want);
+        else this.dispatchEvent({ type: "change" });
+    }
+
+    // limitBox's loop over its predicate: the splats `stays` keeps move to the front of the four arrays in order; with
+    // shFollowsTransforms the SH rows of the kept splats move up with them, and bandsIndices'[k] = (kept splats with index <=
+    // bandsIndices[k]) - 1
+    _compact(stays) {
         const follow = this._shFollowsTransforms && this._shHeight > 0;
         const band = this._bandsIndices, first = band[0] + 1, below = [0, 0, 0], sh = this._shs_rgb;
         let kept = 0, shKept = 0;
         for (let i = 0; i < this._vertexCount; i++) {
-            const x = p[3 * i], y = p[3 * i + 1], z = p[3 * i + 2];
-            if (!(x >= xMin && x <= xMax && y >= yMin && y <= yMax && z >= zMin && z <= zMax)) continue;
+            if (!stays(i)) continue;
             if (follow) {
                 for (let k = 0; k < 3; k++) if (i <= band[k]) below[k]++;
                 if (i >= first) {

@@ -64,7 +64,17 @@ export interface DeviceScene {
     /** needed with setShFollow: the SH state after a followed limitBox; fills `textures` (8 * shCount words each; null: none) and
      *  `band` (bandsIndices), returns shCount */
     readSh?(textures: [Uint32Array, Uint32Array, Uint32Array] | null, band: Int32Array): number;
+    /** optional, the two together: Scene.eraseSelection sets its mask as the device copy's selection (splat i = bit i & 31 of word
+     *  i >>> 5), then has the copy erase the selected splats (keep: the others) and return vertexCount.  A device scene without
+     *  them is treated like a host-only one for an eraseSelection. */
+    setSelection?(words: Uint32Array): void;
+    eraseSelected?(keep: boolean): number;
 }
+export type SelectMode = "centre" | "hit";
+export type SelectOp = "replace" | "add" | "subtract" | "intersect";
+/** A screen region: the pixels [x0, x1) x [y0, y1), optionally one byte per pixel of the rectangle (non-zero = inside; rows
+ *  `stride` >= x1 - x0 apart, default x1 - x0; row 0 is y0): a rasterised lasso or brush. */
+export interface SelectRegion { x0: number; y0: number; x1: number; y1: number; mask?: Uint8Array; stride?: number }
 export class Scene {
     static RowLength: number;
     constructor();
@@ -77,6 +87,10 @@ export class Scene {
     rotate(rotation: Quaternion): void;
     scale(scale: Vector3): void;
     limitBox(xMin: number, xMax: number, yMin: number, yMax: number, zMin: number, zMax: number): void;
+    /** Remove the splats whose bit of `mask` is set (HIPRenderer.readSelection()'s layout; at least ceil(vertexCount / 32) words),
+     *  or with { keep: true } the others: order-preserving, with limitBox's bookkeeping.  While device scenes are attached the mask
+     *  is set on every distinct device copy and erased there; otherwise the same loop runs here.  Fires "change". */
+    eraseSelection(mask: Uint32Array, options?: { keep?: boolean }): void;
     saveToFile(name: string): void;
     toSplatBytes(): Uint8Array;
     data: Uint32Array; vertexCount: number; width: number; height: number;
@@ -232,6 +246,18 @@ export class HIPRenderer {
     shareScene(other: HIPRenderer): void;
     /** renderers that render this renderer's device scene (1: not shared) and the device bytes they hold once */
     sceneSharing(): { members: number; sceneBytes: number };
+    /** Selection: one bit per splat of the device scene (renderers that share a scene have one together).  selectRegion picks by a
+     *  region of the last rendered frame -- "centre": the listed splats whose centre pixel lies in it; "hit": the splats that are the
+     *  hit of one of its pixels (readDepth().index) -- and folds the picked set into the selection with `op`; every call returns the
+     *  number of selected splats.  Scene.eraseSelection(renderer.readSelection()) then removes them everywhere. */
+    selectRegion(region: SelectRegion, options?: { mode?: SelectMode; op?: SelectOp }): number;
+    /** the splats inside [xMin, xMax, yMin, yMax, zMin, zMax]: limitBox's comparisons; needs no frame */
+    selectBox(box: ArrayLike<number>, options?: { op?: SelectOp }): number;
+    /** fold the host's own words into the selection (null: the empty set); bits at and above vertexCount are dropped */
+    setSelection(words: Uint32Array | null, op?: SelectOp): number;
+    invertSelection(): number;
+    /** ceil(vertexCount / 32) words: splat i is bit i & 31 of word i >>> 5 */
+    readSelection(): Uint32Array;
     dispose(): void;
     /** RGBA8, row 0 = top, round(clamp(x,0,1)*255), premultiplied alpha */
     /** RGBA8, row 0 = top; pass an array of width*height*4 elements to have it filled and returned (no allocation per frame). */

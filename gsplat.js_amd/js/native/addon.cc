@@ -984,6 +984,111 @@ napi_value Pick(napi_env env, napi_callback_info info)
     return rc ? throw_gsr(env, c, rc, "gsr_pick") : undefined(env);
 }
 
+// ---- selection (gsr_select_region / _box, gsr_selection_set / _invert, gsr_read_selection, gsr_scene_erase_selected) ----
+napi_value count_value(napi_env env, uint32_t count)
+{
+    napi_value n;
+    napi_create_uint32(env, count, &n);
+    return n;
+}
+
+// selectRegion(handle, Int32Array [x0, y0, x1, y1, stride, mode, op], Uint8Array mask | null) -> selected
+napi_value SelectRegion(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    void *a, *mask;
+    size_t na, nm;
+    if (!c || !get_typed(env, argv[1], napi_int32_array, &a, &na) || !get_typed(env, argv[2], napi_uint8_array, &mask, &nm, true)) return nullptr;
+    if (na < 7) { napi_throw_range_error(env, nullptr, "selectRegion takes [x0, y0, x1, y1, stride, mode, op]"); return nullptr; }
+    const int32_t* v = (const int32_t*)a;
+    gsr_region reg{v[0], v[1], v[2], v[3], (const uint8_t*)mask, mask ? v[4] : 0, 0};
+    // (the library reads (y1 - y0 - 1) * stride + (x1 - x0) bytes of a mask whose rectangle and stride it accepts)
+    if (mask && v[2] > v[0] && v[3] > v[1] && v[4] >= v[2] - v[0] && nm < (size_t)(v[3] - v[1] - 1) * (size_t)v[4] + (size_t)(v[2] - v[0])) {
+        napi_throw_range_error(env, nullptr, "mask is smaller than the rectangle and stride require");
+        return nullptr;
+    }
+    uint32_t count = 0;
+    const int rc = gsr_select_region(c, &reg, v[5], v[6], &count);
+    return rc ? throw_gsr(env, c, rc, "gsr_select_region") : count_value(env, count);
+}
+
+// selectBox(handle, Float64Array(6), op) -> selected
+napi_value SelectBox(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    void* box;
+    size_t len;
+    int32_t op;
+    if (!c || !get_typed(env, argv[1], napi_float64_array, &box, &len) || !get_i32(env, argv[2], &op)) return nullptr;
+    if (len < 6) { napi_throw_range_error(env, nullptr, "a box has 6 entries"); return nullptr; }
+    uint32_t count = 0;
+    const int rc = gsr_select_box(c, (const double*)box, op, &count);
+    return rc ? throw_gsr(env, c, rc, "gsr_select_box") : count_value(env, count);
+}
+
+// setSelection(handle, Uint32Array words | null, op) -> selected
+napi_value SetSelection(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    void* words;
+    size_t len;
+    int32_t op;
+    if (!c || !get_typed(env, argv[1], napi_uint32_array, &words, &len, true) || !get_i32(env, argv[2], &op)) return nullptr;
+    uint32_t count = 0;
+    const int rc = gsr_selection_set(c, (const uint32_t*)words, (uint32_t)len, op, &count);   // (null: the empty set)
+    return rc ? throw_gsr(env, c, rc, "gsr_selection_set") : count_value(env, count);
+}
+
+// invertSelection(handle) -> selected
+napi_value InvertSelection(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    if (!c) return nullptr;
+    uint32_t count = 0;
+    const int rc = gsr_selection_invert(c, &count);
+    return rc ? throw_gsr(env, c, rc, "gsr_selection_invert") : count_value(env, count);
+}
+
+// readSelection(handle) -> Uint32Array of ceil(n / 32) words
+napi_value ReadSelection(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    if (!c) return nullptr;
+    uint32_t n = 0;
+    int rc = gsr_scene_count(c, &n);
+    if (rc) return throw_gsr(env, c, rc, "gsr_scene_count");
+    const size_t nwords = ((size_t)n + 31) / 32;
+    void* data = nullptr;
+    napi_value ab, out;
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, nwords * 4, &data, &ab));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_uint32_array, nwords, ab, 0, &out));
+    rc = gsr_read_selection(c, nwords ? (uint32_t*)data : nullptr, (uint32_t)nwords, nullptr);
+    return rc ? throw_gsr(env, c, rc, "gsr_read_selection") : out;
+}
+
+// eraseSelected(handle, keep) -> new count
+napi_value EraseSelected(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    int32_t keep;
+    if (!c || !get_i32(env, argv[1], &keep)) return nullptr;
+    uint32_t count = 0;
+    const int rc = gsr_scene_erase_selected(c, keep, &count);
+    return rc ? throw_gsr(env, c, rc, "gsr_scene_erase_selected") : count_value(env, count);
+}
+
 napi_value Init(napi_env env, napi_value exports)
 {
     struct { const char* name; napi_callback fn; } fns[] = {
@@ -1002,6 +1107,8 @@ napi_value Init(napi_env env, napi_value exports)
         {"deliverFrame", DeliverFrame}, {"frameReady", FrameReady}, {"acquireFrame", AcquireFrame}, {"releaseFrame", ReleaseFrame},
         {"setHitAlpha", SetHitAlpha}, {"depthAsync", Call0<gsr_depth_async>}, {"readDepth", ReadDepth}, {"pick", Pick},
         {"shareScene", ShareScene}, {"sceneSharing", SceneSharing},
+        {"selectRegion", SelectRegion}, {"selectBox", SelectBox}, {"setSelection", SetSelection}, {"invertSelection", InvertSelection},
+        {"readSelection", ReadSelection}, {"eraseSelected", EraseSelected},
     };
     for (auto& f : fns) {
         napi_value fn;

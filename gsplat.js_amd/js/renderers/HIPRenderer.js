@@ -57,6 +57,9 @@ class HIPRenderer {
             // SH colour that follows the transforms (Scene.shFollowsTransforms): the context keeps frame and textures up itself
             setShFollow: (on) => this._n.setShFollow(this._h, on ? 1 : 0),
             readSh: (textures, band) => this._n.readSceneSh(this._h, textures ? textures[0] : null, textures ? textures[1] : null, textures ? textures[2] : null, band),
+            // Scene.eraseSelection: the mask becomes the device copy's selection, then the copy is compacted there
+            setSelection: (words) => this._n.setSelection(this._h, words, 0),
+            eraseSelected: (keep) => (vertexCount = this._n.eraseSelected(this._h, keep ? 1 : 0)),
         };
         const upload = () => {   // initWebGL's scene part: worker init + texImage2D (WebGLRenderer.ts:105-110,185-195)
             const s = activeScene, n = s.vertexCount, positions = s.positions, rotations = s.rotations, scales = s.scales;
@@ -403,6 +406,28 @@ class HIPRenderer {
             }
             return { index, depth, mean: pickOut[2], alpha: pickOut[3], point };
         };
+        // ---- selection (gsr_select_* / gsr_selection_*): one bit per splat of the device scene, splat i = bit i & 31 of word i >>> 5 ----
+        //   renderer.selectRegion({ x0, y0, x1, y1, mask?, stride? }, { mode: "centre" | "hit", op: "replace" | "add" | "subtract" | "intersect" })
+        //   scene.eraseSelection(renderer.readSelection(), { keep: false });   // on every device copy of the Scene, and in its mirrors
+        // mask: Uint8Array, one byte per pixel of the rectangle, non-zero = inside, rows `stride` (default x1 - x0) apart: a rasterised
+        // lasso or brush.  "centre": the last frame's listed splats whose centre pixel lies in the region; "hit": the splats that are
+        // the hit of one of its pixels (readDepth().index).  Every call returns the number of selected splats.
+        const MODES = { centre: 0, hit: 1 }, OPS = { replace: 0, add: 1, subtract: 2, intersect: 3 };
+        const code = (table, v, dflt, what) => {
+            const k = v === undefined ? dflt : v;
+            if (!(k in table)) throw new Error(what + " must be one of " + Object.keys(table).join(", "));
+            return table[k];
+        };
+        this.selectRegion = (region, options) => {
+            const r = region, o2 = options || {};
+            const stride = r.mask ? (r.stride === undefined ? r.x1 - r.x0 : r.stride) : 0;
+            return this._n.selectRegion(this._h, new Int32Array([r.x0, r.y0, r.x1, r.y1, stride, code(MODES, o2.mode, "centre", "mode"), code(OPS, o2.op, "replace", "op")]),
+                                        r.mask || null);
+        };
+        this.selectBox = (box, options) => this._n.selectBox(this._h, new Float64Array(box), code(OPS, (options || {}).op, "replace", "op"));
+        this.setSelection = (words, op) => this._n.setSelection(this._h, words || null, code(OPS, op, "replace", "op"));
+        this.invertSelection = () => this._n.invertSelection(this._h);
+        this.readSelection = () => this._n.readSelection(this._h);
         this.stats = () => this._n.getTimings(this._h);
         this.deviceInfo = () => this._n.deviceInfo(this._h);
         this.isInitialized = () => initialized;

@@ -61,6 +61,11 @@ class GsrDepthDeliveryOptions(ctypes.Structure):
     _fields_ = [("format", ctypes.c_int32), ("step", ctypes.c_int32), ("near", ctypes.c_float), ("reserved", ctypes.c_int32)]
 
 
+class GsrRegion(ctypes.Structure):
+    _fields_ = [("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("x1", ctypes.c_int32), ("y1", ctypes.c_int32), ("mask", ctypes.c_void_p),
+                ("mask_stride", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class GsrDepthLayout(ctypes.Structure):
     _fields_ = [("format", ctypes.c_int32), ("step", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
                 ("stride", ctypes.c_int32), ("reserved", ctypes.c_int32), ("offset", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
@@ -71,6 +76,8 @@ GSR_FORMAT_RGBA8, GSR_FORMAT_NV12, GSR_FORMAT_I420 = 0, 1, 2
 DELIVERY_FORMATS = {"rgba8": GSR_FORMAT_RGBA8, "nv12": GSR_FORMAT_NV12, "i420": GSR_FORMAT_I420}
 GSR_DEPTH_NONE, GSR_DEPTH_F32, GSR_DEPTH_U16 = 0, 1, 2
 DEPTH_DELIVERY_FORMATS = {"f32": GSR_DEPTH_F32, "u16": GSR_DEPTH_U16}
+SELECT_MODES = {"centre": 0, "hit": 1}                                     # GSR_SELECT_*
+SELECT_OPS = {"replace": 0, "add": 1, "subtract": 2, "intersect": 3}       # GSR_SELOP_*
 
 
 def edge_arrays(edges):
@@ -106,6 +113,7 @@ EXPORTS = [
     "gsr_comm_set_depth", "gsr_frame_depth_layout", "gsr_read_frame_depth", "gsr_frame_depth_device_ptr",
     "gsr_set_sh_follow", "gsr_set_sh_frame", "gsr_get_sh_frame", "gsr_read_scene_sh",
     "gsr_share_scene", "gsr_scene_sharing",
+    "gsr_select_region", "gsr_select_box", "gsr_selection_set", "gsr_selection_invert", "gsr_read_selection", "gsr_scene_erase_selected",
 ]
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p)
 GSR_COMM_ID_BYTES = 128
@@ -238,6 +246,13 @@ def load_library(path=None):
     L.gsr_read_scene_sh.argtypes = [vp, vp, vp, vp, ctypes.POINTER(ctypes.c_uint32), vp]
     L.gsr_share_scene.argtypes = [vp, vp]
     L.gsr_scene_sharing.argtypes = [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64)]
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    L.gsr_select_region.argtypes = [vp, ctypes.POINTER(GsrRegion), ctypes.c_int32, ctypes.c_int32, u32p]
+    L.gsr_select_box.argtypes = [vp, vp, ctypes.c_int32, u32p]
+    L.gsr_selection_set.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_int32, u32p]
+    L.gsr_selection_invert.argtypes = [vp, u32p]
+    L.gsr_read_selection.argtypes = [vp, vp, ctypes.c_uint32, u32p]
+    L.gsr_scene_erase_selected.argtypes = [vp, ctypes.c_int32, u32p]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int and name not in ("gsplat_sort_host",):
@@ -759,6 +774,88 @@ class HIPRenderer:
         self._check(self._L.gsr_pick(self._ctx, xy.ctypes.data, len(xy), out.ctypes.data))
         return out[:len(xy)]
 
+    # -- selection (gsr_select_* / gsr_selection_* / gsr_scene_erase_selected): one bit per splat, held with the device scene --
+    @staticmethod
+    def _select_code(table, name, what):
+        if isinstance(name, str):
+            if name not in table:
+                raise ValueError("%s must be one of %s" % (what, ", ".join(sorted(table))))
+            return table[name]
+        return int(name)   # (a raw code: the library judges it)
+
+    def select_region(self, rect, mask=None, mode="centre", op="replace"):
+        """Pick splats by a screen region of the last rendered frame and fold them into the selection; returns the selected count.
+        rect = (x0, y0, x1, y1): the pixels [x0, x1) x [y0, y1).  mask: optional [y1 - y0, stride] array (stride >= x1 - x0), non-zero =
+        inside (a rasterised lasso or brush; row 0 is y0).  mode "centre": the listed splats whose centre pixel lies in the region
+        ("select through"); "hit": the splats that are the hit of one or more of its pixels (read_depth()[2]; "select the
+        surface").  op: "replace", "add", "subtract", "intersect"."""
+        x0, y0, x1, y1 = (int(v) for v in rect)
+        reg = GsrRegion(x0, y0, x1, y1, None, 0, 0)
+        if mask is not None:
+            m = np.ascontiguousarray(mask)
+            if m.dtype != np.uint8:
+                m = (m != 0).astype(np.uint8)
+            if m.ndim != 2 or m.shape[0] < y1 - y0:
+                raise ValueError("mask must be [y1 - y0, stride]")
+            reg.mask, reg.mask_stride = m.ctypes.data, m.shape[1]
+        count = ctypes.c_uint32(0)
+        self._check(self._L.gsr_select_region(self._ctx, ctypes.byref(reg), self._select_code(SELECT_MODES, mode, "mode"),
+                                              self._select_code(SELECT_OPS, op, "op"), ctypes.byref(count)))
+        return count.value
+
+    def select_box(self, box, op="replace"):
+        """Pick the splats inside box = (xMin, xMax, yMin, yMax, zMin, zMax) -- scene_limit_box's comparisons; needs no frame."""
+        box = np.ascontiguousarray(box, dtype=np.float64)
+        count = ctypes.c_uint32(0)
+        self._check(self._L.gsr_select_box(self._ctx, box.ctypes.data, self._select_code(SELECT_OPS, op, "op"), ctypes.byref(count)))
+        return count.value
+
+    def set_selection(self, picked=None, op="replace", words=None):
+        """Fold a set of the host's into the selection: `picked` bool[n] (None: the empty set), or `words` uint32[>= ceil(n / 32)] as
+        selection_words() returns them (bits at and above n are dropped)."""
+        count = ctypes.c_uint32(0)
+        code = self._select_code(SELECT_OPS, op, "op")
+        if words is None and picked is not None:
+            b = np.ascontiguousarray(picked).reshape(-1) != 0
+            if b.size != self._count():
+                raise ValueError("picked must hold one entry per splat (%d)" % self._count())
+            words = pack_selection(b)
+        if words is None:
+            self._check(self._L.gsr_selection_set(self._ctx, None, 0, code, ctypes.byref(count)))
+        else:
+            w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+            self._check(self._L.gsr_selection_set(self._ctx, w.ctypes.data, w.size, code, ctypes.byref(count)))
+        return count.value
+
+    def invert_selection(self):
+        count = ctypes.c_uint32(0)
+        self._check(self._L.gsr_selection_invert(self._ctx, ctypes.byref(count)))
+        return count.value
+
+    def selection_words(self):
+        """The selection as the device holds it: uint32[ceil(n / 32)], splat i = bit i & 31 of word i >> 5."""
+        n = self._count()
+        w = np.zeros(-(-n // 32), dtype=np.uint32)
+        self._check(self._L.gsr_read_selection(self._ctx, w.ctypes.data if w.size else None, w.size, None))
+        return w
+
+    def selection_count(self):
+        count = ctypes.c_uint32(0)
+        self._check(self._L.gsr_read_selection(self._ctx, None, 0, ctypes.byref(count)))
+        return count.value
+
+    def selection(self):
+        """bool[n]: which splats are selected."""
+        return unpack_selection(self.selection_words(), self._count())
+
+    def scene_erase_selected(self, keep=False):
+        """Remove the selected splats (keep=True: the unselected ones) as scene_limit_box removes those outside its box; returns the new
+        count.  When nothing would be removed nothing changes and the last frame stays valid."""
+        n = ctypes.c_uint32(0)
+        self._check(self._L.gsr_scene_erase_selected(self._ctx, 1 if keep else 0, ctypes.byref(n)))
+        self._n = n.value
+        return n.value
+
     def read_keys(self):
         keys = np.empty(self._count(), dtype=np.uint32)
         mm = np.zeros(2, dtype=np.int32)
@@ -916,6 +1013,18 @@ class HIPRenderer:
 
     def frame_depth_ptr(self):
         return self._L.gsr_frame_depth_device_ptr(self._ctx)
+
+
+def pack_selection(picked):
+    """bool[n] -> uint32[ceil(n / 32)], splat i = bit i & 31 of word i >> 5 (the selection's layout)."""
+    b = np.ascontiguousarray(picked).reshape(-1) != 0
+    return np.packbits(np.concatenate([b, np.zeros(-b.size % 32, dtype=bool)]), bitorder="little").view(np.uint32).copy()
+
+
+def unpack_selection(words, n):
+    """uint32[>= ceil(n / 32)] -> bool[n]."""
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    return np.unpackbits(w.view(np.uint8), bitorder="little")[:n].astype(bool)
 
 
 def new_group_id():

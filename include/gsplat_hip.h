@@ -514,6 +514,61 @@ int gsr_read_depth(gsr_ctx *ctx, float *mean, float *hit, uint32_t *index);   /*
 void *gsr_depth_device_ptr(gsr_ctx *ctx, int32_t plane);      /* 0 mean, 1 hit, 2 index; NULL until the planes exist */
 int gsr_pick(gsr_ctx *ctx, const int32_t *xy /* count x (x, y) */, uint32_t count, gsr_pick_result *out);   /* blocking */
 
+/* ---- selection ---- screen regions and boxes select, erase compacts
+ * No interface of the reference stands behind this section either: it lies between gsr_pick (the splat under one pixel) and
+ * gsr_scene_limit_box (a world-axis crop), and is what a viewer that becomes a clean-up tool needs first: delete the floaters in
+ * front of the subject, keep only the object inside the lasso.
+ * A selection is one bit per splat of a scene, held on the device with the scene: nwords = ceil(n / 32) words of uint32_t, splat
+ * i is bit i & 31 of word i >> 5, bits at and above n are always 0, and a scene that has never been selected in reads as all
+ * zeros.  The members of a shared scene (gsr_share_scene) have ONE selection, because its bits are splat indices of the one copy.
+ * Definitions ("Selection"); P is the set a call picks, S the selection:
+ *   GSR_SELECT_CENTRE ("select through"): splat i is picked iff it is listed in the last rendered frame -- it passed the frame's
+ *     culls, i.e. it has a non-empty pixel box (on a band context: the box touches the band) -- and its centre pixel
+ *     X = (int)floorf(cx), Y = (int)floorf(cy) of the frame's record lies in the region (pixel centres are at +0.5).  A centre
+ *     outside the image never selects.
+ *   GSR_SELECT_HIT ("select the surface"): splat i is picked iff it is the value of the context's hit-index plane (plane 2 of
+ *     "depth and pick", at the context's hit_alpha of that moment, for the last rendered frame) at one or more pixels of the region.
+ *   Region: a pixel rectangle [x0, x1) x [y0, y1), 0 <= x0 < x1 <= width, 0 <= y0 < y1 <= height; optionally one byte per pixel of
+ *     the rectangle, non-zero meaning inside, row stride mask_stride >= x1 - x0, row 0 = y0 (the top): the host rasterises a lasso
+ *     or a brush into it.  On a band context the rectangle must lie inside the band's pixel columns, the rule gsr_pick has for a pixel.
+ *   gsr_select_box picks the splats inside the box: the same f64 comparisons on the same f32 positions as gsr_scene_limit_box,
+ *     with its min >= max refusals.  It needs no frame.
+ *   Ops: REPLACE S = P; ADD S = S | P; SUBTRACT S = S & ~P; INTERSECT S = S & P.
+ * Common to the calls: `selected` receives the number of set bits afterwards and may be NULL.  Every call is blocking and returns
+ * with the selection final on the device; because each call ends with a stream wait, the members of a shared scene may issue these
+ * calls in any order with no events between them (the "one host thread at a time, together" rule above covers the rest).
+ * gsr_select_region needs of the frame what gsr_pick needs, and first settles the frame as gsr_pick does (a frame whose lists
+ * did not fit is rendered again); HIT mode runs the planes pass if the planes are not this frame's, as gsr_read_depth does, and
+ * refuses planes a pass marked invalid with GSR_ERR_OVERFLOW.  It does not touch the frame, the framebuffer, the statistics or
+ * the planes' validity.  GSR_ERR_ARG, nothing changed: a bad rectangle or stride, an unknown mode or op, reserved != 0, a region
+ * outside the band, every frame condition gsr_pick refuses (no frame yet; scene, size, band or list buffers changed since the
+ * frame -- a gsr_scene_translate counts; a sort-only last frame).
+ * gsr_selection_set / gsr_read_selection need nwords >= ceil(n / 32), else GSR_ERR_ARG; host bits at or above n are dropped;
+ * gsr_selection_invert keeps the tail at 0.
+ * gsr_scene_erase_selected removes the selected splats, or with keep_selected != 0 the unselected ones.  Everything said of
+ * gsr_scene_limit_box holds: order-preserving; needs rotations / scales (a scene from rows or from the four arrays); waits for
+ * every member of a shared scene and invalidates their frame state; moves the generation; re-plans the bins; with
+ * gsr_set_sh_follow on, compacts the SH textures and recounts band_index, otherwise drops the SH state.  Exception: when nothing
+ * would be removed it returns GSR_OK with new_count = n and changes nothing -- the last frame stays valid and gsr_pick still
+ * answers.  After a removal the selection is empty.
+ * Where the selection is cleared or replaced: gsr_scene_limit_box and gsr_set_scene* also leave the scene with the empty
+ * selection (a selection does not survive a limitBox); translate, rotate and scale keep it; after gsr_share_scene, ctx has
+ * `from`'s selection; a member that leaves a share starts empty.  gsr_scene_sharing's scene_bytes counts the selection's buffers
+ * once they exist.  A context that never calls any of this allocates nothing and launches nothing. */
+#define GSR_SELECT_CENTRE 0
+#define GSR_SELECT_HIT    1
+#define GSR_SELOP_REPLACE 0
+#define GSR_SELOP_ADD 1
+#define GSR_SELOP_SUBTRACT 2
+#define GSR_SELOP_INTERSECT 3
+typedef struct gsr_region { int32_t x0, y0, x1, y1; const uint8_t *mask; int32_t mask_stride; int32_t reserved; } gsr_region;
+int gsr_select_region(gsr_ctx *ctx, const gsr_region *region, int32_t mode, int32_t op, uint32_t *selected);
+int gsr_select_box(gsr_ctx *ctx, const double *box /* 6 */, int32_t op, uint32_t *selected);
+int gsr_selection_set(gsr_ctx *ctx, const uint32_t *words, uint32_t nwords, int32_t op, uint32_t *selected); /* words NULL: the empty set */
+int gsr_selection_invert(gsr_ctx *ctx, uint32_t *selected);
+int gsr_read_selection(gsr_ctx *ctx, uint32_t *words, uint32_t nwords, uint32_t *selected);   /* words may be NULL: count only */
+int gsr_scene_erase_selected(gsr_ctx *ctx, int32_t keep_selected, uint32_t *new_count);
+
 /* ---- device interop (torch / RCCL plumbing in the harness) ---- */
 void *gsr_framebuffer_device_ptr(gsr_ctx *ctx); /* float4[h][w] on the device */
 void *gsr_stream_handle(gsr_ctx *ctx);          /* hipStream_t */
