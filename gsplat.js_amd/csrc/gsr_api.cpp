@@ -218,8 +218,7 @@ int gsr_set_list_capacity(gsr_ctx* c, uint32_t entries)
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->bin.capacity = std::max<uint32_t>(entries, 1024u);
     if (int r = c->bin.list.alloc(c, c->bin.capacity)) return r;
-    c->bin.max_items = 0;
-    return alloc_bins(c);
+    return alloc_bins(c, true);
 }
 
 int gsr_set_camera(gsr_ctx* c, const float* view, const float* proj, const float* vp, float fx, float fy)

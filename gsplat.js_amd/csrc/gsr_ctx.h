@@ -294,14 +294,13 @@ struct gsr_ctx {
         gsr::DevBuf<uint32_t> table, total, start, start_pre, list;
         gsr::DevBuf<uint32_t> cell_list, cell_total, cell_start, chunk_start, chunk_info, cell_table2, cell_wcnt;
         gsr::DevBuf<uint32_t> seg_start, items;
-        gsr::DevBuf<unsigned long long> mask;   // per-bin arrival masks of the compositor (null: separate k_combine launch)
+        gsr::DevBuf<unsigned long long> mask;   // per-bin arrival masks of the compositor (blend.fused; null otherwise)
         gsr::DevBuf<float4> partial;
         gsr::BinPlan plan{};               // the binning's form and launch shapes for the context as it stands (plan_bins)
+        gsr::BlendPlan blend{};            // the compositor's kernel, grid and work-item policy for the same (plan_blend);
+                                           // blend.max_items: what `items` was allocated for
         uint32_t cell_capacity_alloc = 0, cell_ncells_alloc = 0;
         uint32_t capacity = 0, table_elems = 0, nbins_alloc = 0;
-        uint32_t max_items = 0, seg_len = 0, blend_grid = 2048;
-        uint32_t seg_target_items = 5000;
-        uint32_t blend_sub = 1;            // compositor waves per 16x16 tile: 1 (k_blend) or 2 (k_blend2)
     } bin;
 
     struct Words {   // the small device words every frame shares, and what the host knows of them
@@ -460,7 +459,8 @@ inline SortKnobs sort_knobs_of(const gsr_ctx* c)
 }
 
 // gsr_frame.cpp
-int alloc_bins(gsr_ctx* c);
+// (fresh_items: the work items are sized afresh -- the list was replaced -- instead of only growing)
+int alloc_bins(gsr_ctx* c, bool fresh_items = false);
 int enqueue_frame(gsr_ctx* c, bool render);
 int finish_frame(gsr_ctx* c);
 int sync_and_repair(gsr_ctx* c);

@@ -1,6 +1,6 @@
 // The frame: what its launches are handed (build_frame_args), the chain itself, its capture and replay as a HIP graph,
 // stage timing, and the repair of frames whose bin lists did not fit.  Also the sizing of everything the binning and the
-// compositor use (alloc_bins), next to the policy constants it is sized by.
+// compositor use (alloc_bins), from the two stages' plans: plan_bins (k_bin.hip) and plan_blend (k_blend.hip) hold the policy.
 #include "gsr_ctx.h"
 
 #include <algorithm>
@@ -9,52 +9,6 @@
 using namespace gsr;
 
 namespace {
-
-// Compositor work-item granularity: list entries per (bin, segment) item.  0x7fffff00 = one item per
-// bin, which early termination needs (a segment cannot see whether earlier ones saturated the bin).
-constexpr uint32_t SEG_LEN_MIN = 512;            // shortest segment; k_bin_finalize lengthens it so that the frame is cut
-                                                 // into about SEG_TARGET_* full segments (multiples of 256 entries)
-constexpr uint32_t SEG_TARGET_EXACT = 5000;      // one frame at a time: concurrency from the frame's own segments (C3: 512)
-constexpr uint32_t SEG_TARGET_THROUGHPUT = 1300; // GSR_FLAG_THROUGHPUT: concurrency comes from the other frames in flight
-                                                 // (C3: 2048-entry segments; a 1/8-screen band stays at 512)
-// Persistent compositor workgroups per CU.  k_blend is built for 7 waves per SIMD (72 VGPRs), so 7 four-wave
-// workgroups are resident per CU and the grid must not exceed that: a workgroup that is not resident at launch still
-// owns its first work item by index (a heavy one: the queue is ordered heaviest first) and starts it only when a
-// resident workgroup exits.  With 8 per CU, one item in eight began at 222 us of a 270 us kernel (in-kernel stamps,
-// scripts/blend_stamps.py): k_blend 271 -> 252 us on C3 at 7 per CU.
-constexpr uint32_t BLEND_WG_PER_CU_EXACT = 7;
-// Contexts that overlap with others' kernels (GSR_FLAG_THROUGHPUT): 6 per CU left a wave slot per SIMD to the other
-// contexts and was best while the fold of the partials was a kernel of its own; with the fold inside k_blend 7 is
-// (bench.py, three frames in flight, C3: 3324 -> 3400 frames/s, reproducible; C2 -0.8 %, C4 and early-out unchanged).
-constexpr uint32_t BLEND_WG_PER_CU_THROUGHPUT = 7;
-// Two waves per tile (k_blend2, 512-thread workgroups): three workgroups per CU are resident (6 waves per SIMD).
-constexpr uint32_t BLEND_WG_PER_CU_SUB2 = 3;
-constexpr uint32_t SUB2_MAX_BINS = 4096, SEG_LEN_MIN_SUB2 = 1024;
-constexpr uint32_t SEG_LEN_WHOLE_BIN = 0x7fffff00u;
-
-// Work-item length.  With the saturation skip of k_blend a work item ends as soon as nothing it could still add can change
-// a bit of its pixels, and that needs the item to contain the splats that saturate it: a bin cut into 512-entry segments
-// never saturates inside one of them (every segment starts from transmittance 1), a bin processed as one item stops
-// after the few thousand entries that matter (C3: 3430 -> 4990 frames/s with three frames in flight, 2670 -> 2945 one at
-// a time; C4: 292 -> 856).  Where the scene does not saturate (C2: small splats, 9 % of the entries skipped against 53 %
-// on C3 and 85 % on C4; or any thin, low-opacity scene) long items only cost balance (C2: 6670 -> 2780 frames/s).
-// k_bin_finalize decides per frame, from a figure the projection already has: the frame's optical depth
-//     tau = sum over visible splats of opacity x (16x16 tiles its box overlaps) x 256 / pixels
-// (C1 14, C2 74, C3 362, C4 1090): items are at least SEG_LEN_LONG entries (in practice whole bins) from LONG_TAU_* on.
-// A function of the frame alone: no feedback from earlier frames, the same frame always takes the same path.
-// Where long items start to pay (scripts/tau_crossover.py: the C3 and C2 generators at 0.25 .. 1.6 M splats, 1080p): with
-// other frames' kernels filling the gaps, between tau 90 and 145 for both generators (tau 90: 10 390 -> 10 080 frames/s,
-// tau 145: 7350 -> 8640, tau 250: 4730 -> 6800); one frame at a time the few long items are the frame's tail and the
-// crossover depends on the scene (C3 generator: tau ~ 255, C3 itself +23 %; the C2 generator's small splats still lose
-// 8 % at tau 390), so the threshold there stays high.
-constexpr uint32_t SEG_LEN_LONG = 32768;   // (16384: C4 k_blend 437 instead of 405 us -- its heaviest bins hold 50-100 k entries; 65536 measures the same)
-constexpr uint32_t LONG_TAU_EXACT = 340, LONG_TAU_THROUGHPUT = 120;
-// a frame that is not dense as a whole: bins far past saturation become one item only where a list entry carries at least this
-// optical mass (pixels): C3 14, C2 8, 2 M tiny splats 1.9 -- one frame at a time a 3000-entry serial walk is the frame's tail
-constexpr uint32_t LONG_MASS_MIN_EXACT = 12, LONG_MASS_MIN_THROUGHPUT = 0;
-constexpr uint32_t LONG_TILES_X2_EXACT = 9;   // one frame at a time: and at least 4.5 tiles per visible splat (k_bin_finalize)
-constexpr uint32_t LONG_TILES_X2_THROUGHPUT = 6;   // with frames in flight: 3 (scripts/policy_check.py: 2 M tiny splats, 1.9 tiles each, tau 264:
-                                                   // long items -26 %; the C2 generator, 3.6 tiles each: +10 % at the same tau)
 
 // keys in the largest high-digit bucket of the last sorted frame (the low half of mailbox[1]; 0xffffffff until a frame of this
 // scene has reported): what plan_sort picks the sort order from
@@ -67,7 +21,6 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
 {
     memset(&a, 0, sizeof a);
     const BinGrid g = make_grid(c);
-    const bool throughput = (c->opt.flags & GSR_FLAG_THROUGHPUT) != 0;
     // the sort's form for this frame (plan_sort, k_sort.hip): the order, the width, whether the rectangles travel with the keys and
     // whether the frame runs on a band's survivors; every pointer below that depends on one of them follows it.
     // band mode (a context that composites only part of the screen): the projection's workgroups pack their survivors (see
@@ -117,7 +70,6 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
     sb.rects_out = sp.carry ? c->sort.rects.p : nullptr;
     if (!render) return;
 
-    const uint32_t queue_start = std::min<uint32_t>(c->bin.max_items, c->bin.blend_grid);
     BinBuffers& bb = a.bin;
     bb.depth_index = c->sort.depth_index;
     bb.count = &fs->sorted_count;
@@ -140,22 +92,9 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
     bb.mailbox = c->words.mailbox_dev;
     bb.report = fs->report;
     bb.capacity = c->bin.capacity;
-    bb.max_items = c->bin.max_items;
-    bb.seg_len = c->bin.seg_len;
     bb.seg_len_dev = &fs->seg_len;
-    // work items heaviest first (one frame at a time) or in raster order
-    bb.items_by_size = c->knobs.items_by_size >= 0 ? c->knobs.items_by_size : throughput ? 0 : 1;
     bb.queue = &fs->queue;
-    bb.queue_start = queue_start;
-    bb.seg_target_items = c->bin.seg_target_items;
     bb.bin_mask = c->bin.mask;
-    bb.long_policy = c->bin.seg_len == SEG_LEN_WHOLE_BIN ? 0 : c->knobs.long_items >= 0 ? c->knobs.long_items : c->knobs.saturate ? -1 : 0;
-    bb.seg_len_long = SEG_LEN_LONG;
-    bb.long_tau = throughput ? LONG_TAU_THROUGHPUT : LONG_TAU_EXACT;
-    bb.npix = (uint32_t)((g.bx_hi - g.bx_lo) * BIN_PX) * (uint32_t)c->H;
-    bb.long_tiles_x2 = throughput ? LONG_TILES_X2_THROUGHPUT : LONG_TILES_X2_EXACT;
-    bb.long_tau_bin = c->knobs.long_tau;
-    bb.long_mass_min = throughput ? LONG_MASS_MIN_THROUGHPUT : LONG_MASS_MIN_EXACT;
     bb.cell_list = c->bin.cell_list;
     bb.cell_total = c->bin.cell_total;
     bb.cell_start = c->bin.cell_start;
@@ -166,25 +105,22 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
     bb.band = band_is_partial(g) ? 1u : 0u;
     bb.n_max = c->scene->n;
 
+    // the compositor reads what the binning wrote; its kernel, grid and work-item policy are the context's plan (plan_blend)
     BlendBuffers& bl = a.blend;
-    bl.items = c->bin.items;
-    bl.seg_start = c->bin.seg_start;
-    bl.bin_start = c->bin.start;
-    bl.list = c->bin.list;
+    bl.items = bb.items;
+    bl.seg_start = bb.seg_start;
+    bl.bin_start = bb.bin_start;
+    bl.list = bb.list;
     bl.rec = c->sort.rec;
-    bl.bbox = nullptr;   // (nothing on the frame path reads the pixel boxes)
     bl.shcol = c->shcol;
     bl.fb = c->out.fb;
     bl.partial = c->bin.partial;
-    bl.queue = &fs->queue;
-    bl.seg_len = c->bin.seg_len;
-    bl.seg_len_dev = &fs->seg_len;
-    bl.grid = queue_start;
-    bl.capacity = c->bin.capacity;
+    bl.queue = bb.queue;
+    bl.seg_len_dev = bb.seg_len_dev;
+    bl.capacity = bb.capacity;
     bl.nsplats = std::max(c->scene->n, 1u);
-    bl.bin_mask = c->bin.mask;
-    bl.saturate = c->knobs.saturate ? 1u : 0u;
-    bl.sub = c->bin.blend_sub;
+    bl.bin_mask = bb.bin_mask;
+    bl.plan = c->bin.blend;
 }
 
 // the projection's launch of this frame: its arguments from `a`, the context's current camera
@@ -230,9 +166,9 @@ int enqueue_chain(gsr_ctx* c, const FrameArgs& a, bool timing)
             HIP_TRY(c, hipMemsetAsync(a.bin.bin_total, 0, sizeof(uint32_t) * a.bin.plan.nbins, s));
             HIP_TRY(c, hipMemsetAsync(a.bin.overflow, 0, sizeof(uint32_t), s));   // (k_project_key zeroes it otherwise)
         }
-        launch_bin(a.bin, a.grid, s);
+        launch_bin(a.bin, a.blend.plan, a.grid, s);
         if (timing) HIP_TRY(c, hipEventRecord(ev[EV_BIN], s));
-        launch_blend(a.blend, a.grid, a.early_out_eps, s, (timing && !a.blend.bin_mask) ? ev[EV_BLEND] : nullptr);
+        launch_blend(a.blend, a.grid, a.early_out_eps, s, (timing && !a.blend.plan.fused) ? ev[EV_BLEND] : nullptr);
         if (timing) HIP_TRY(c, hipEventRecord(ev[EV_COMBINE], s));
     }
     HIP_TRY(c, hipGetLastError());
@@ -320,15 +256,14 @@ int handle_overflow(gsr_ctx* c, uint64_t* newly)
         c->bin.capacity = (uint32_t)want;
         if (int r = c->bin.list.alloc(c, c->bin.capacity)) return r;
     }
-    c->bin.max_items = 0;
-    return alloc_bins(c);
+    return alloc_bins(c, true);
 }
 
 }  // namespace
 
 namespace gsr {
 
-int alloc_bins(gsr_ctx* c)
+int alloc_bins(gsr_ctx* c, bool fresh_items)
 {
     if (!c->W) return GSR_OK;
     c->frame_lists = false;   // (grid, lists or work items change: what the last frame left in them is not walked again)
@@ -340,27 +275,32 @@ int alloc_bins(gsr_ctx* c)
     b.plan = plan_bins(g, c->scene->n, capacity, c->cu_count, front_waves_of(c), BinKnobs{k.bin_two_level, k.bin_big, k.bin_rounds, k.cell_grid});
     const BinPlan& p = b.plan;
     const uint32_t nbins = (uint32_t)p.nbins;
+    // the compositor's kernel, grid and work items for the same (plan_blend, k_blend.hip).  The item table only grows, unless the
+    // bins or the list it is sized by are replaced below, or the caller has replaced the list
+    const bool items_afresh = fresh_items || nbins > b.nbins_alloc || !b.capacity;
+    const uint32_t items_alloc = items_afresh ? 0u : b.blend.max_items;
+    b.blend = plan_blend(nbins, (uint32_t)((g.bx_hi - g.bx_lo) * BIN_PX) * (uint32_t)c->H, (uint32_t)capacity, c->cu_count,
+                         (c->opt.flags & GSR_FLAG_THROUGHPUT) != 0, c->opt.early_out_eps > 0.0f, items_alloc,
+                         BlendKnobs{k.fuse_combine ? 1u : 0u, k.saturate ? 1u : 0u, k.items_by_size, k.long_items, k.long_tau, k.blend_sub, k.seg_target,
+                                    k.blend_grid, k.seg_len});
     const size_t table = (size_t)p.table_rows * p.table_cols;
     if (table > b.table_elems) {
         if (int r = b.table.alloc(c, table)) return r;
         b.table_elems = (uint32_t)table;
     }
-    bool items_dirty = false;
     if (nbins > b.nbins_alloc) {
         if (int r = b.total.alloc(c, nbins)) return r;
         if (int r = b.start.alloc(c, nbins + 1)) return r;
         if (int r = b.start_pre.alloc(c, nbins + 1)) return r;
         if (int r = b.seg_start.alloc(c, nbins + 1)) return r;
-        if (k.fuse_combine) {
+        if (b.blend.fused) {
             if (int r = b.mask.alloc(c, nbins)) return r;
         }
         b.nbins_alloc = nbins;
-        items_dirty = true;
     }
     if (!b.capacity) {
         b.capacity = (uint32_t)capacity;
         if (int r = b.list.alloc(c, b.capacity)) return r;
-        items_dirty = true;
     }
     if (p.form == BIN_TWO_LEVEL) {
         const uint32_t ncells = (uint32_t)p.ncells;
@@ -379,28 +319,10 @@ int alloc_bins(gsr_ctx* c)
             b.cell_capacity_alloc = b.capacity;
         }
     }
-    const bool throughput = (c->opt.flags & GSR_FLAG_THROUGHPUT) != 0;
-    b.seg_len = c->opt.early_out_eps > 0.0f ? SEG_LEN_WHOLE_BIN : SEG_LEN_MIN;
-    b.seg_target_items = k.seg_target ? k.seg_target : throughput ? SEG_TARGET_THROUGHPUT : SEG_TARGET_EXACT;
-    // Waves per tile.  Two (k_blend2) halve a wave's serial walk over a work item -- the pole of a frame rendered alone, where a
-    // wave needs ~560 cycles per entry visit whatever else the chip does -- and pay with occupancy (24 instead of 28 waves
-    // per CU) and saturation tests at chunk instead of 64-entry boundaries.  Measured one frame at a time: C3 k_blend 194 ->
-    // 147 us, C1 20 -> 15; C2 (short segments) 77 -> 86, with 1024-entry segments 80; C4, whose 8160 bins keep every slot
-    // busy: 412 -> 509; three frames in flight, C3: 5280 -> 4410 frames/s.  So: contexts that render one frame at a time, up
-    // to SUB2_MAX_BINS bins, with segments of at least 1024 entries.  (Leaving the choice to k_bin_finalize per frame --
-    // both kernels launched, the other one returning at once -- cost 4.5 us per frame for the idle launch.)
-    b.blend_sub = k.blend_sub ? (uint32_t)k.blend_sub : (!throughput && nbins <= SUB2_MAX_BINS) ? 2u : 1u;
-    if (b.blend_sub >= 2 && b.seg_len != SEG_LEN_WHOLE_BIN) b.seg_len = SEG_LEN_MIN_SUB2;
-    b.blend_grid = (b.blend_sub >= 2 ? BLEND_WG_PER_CU_SUB2 : throughput ? BLEND_WG_PER_CU_THROUGHPUT : BLEND_WG_PER_CU_EXACT) * (uint32_t)std::max(c->cu_count, 1);
-    if (k.blend_grid) b.blend_grid = k.blend_grid;
-    if (k.seg_len && b.seg_len != SEG_LEN_WHOLE_BIN) b.seg_len = k.seg_len;
-    // segments = work items (each may need a partial slot): one per bin plus one per seg_len entries
-    const uint32_t want_items = nbins + b.capacity / b.seg_len + 16;
-    if (items_dirty || want_items > b.max_items) {
-        b.max_items = want_items;
-        if (int r = b.items.alloc(c, (size_t)b.max_items * 4)) return r;   // (four words per work item: k_bin_finalize)
-        if (b.seg_len != SEG_LEN_WHOLE_BIN) {
-            if (int r = b.partial.alloc(c, (size_t)want_items * BIN_PX * BIN_PX)) return r;
+    if (b.blend.max_items > items_alloc) {
+        if (int r = b.items.alloc(c, (size_t)b.blend.max_items * 4)) return r;   // (four words per work item: k_bin_finalize)
+        if (b.blend.partial_slots) {
+            if (int r = b.partial.alloc(c, (size_t)b.blend.partial_slots * BIN_PX * BIN_PX)) return r;
         }
     }
     return GSR_OK;
@@ -511,7 +433,7 @@ int finish_frame(gsr_ctx* c)
         tot = a + b;
         if (render) {
             HIP_TRY(c, hipEventElapsedTime(&d, ev[EV_SORT], ev[EV_BIN]));
-            if (c->bin.mask) {   // the fold of multi-segment bins runs inside k_blend: one stage, no event in between
+            if (c->bin.blend.fused) {   // the fold of multi-segment bins runs inside k_blend: one stage, no event in between
                 HIP_TRY(c, hipEventElapsedTime(&e, ev[EV_BIN], ev[EV_COMBINE]));
             } else {
                 HIP_TRY(c, hipEventElapsedTime(&e, ev[EV_BIN], ev[EV_BLEND]));
@@ -565,5 +487,14 @@ extern "C" int gsr_debug_last_sort_plan(gsr_ctx* c, SortPlan* out)
     if (!c || !out) return GSR_ERR_ARG;
     if (!c->have_sort) return fail(c, GSR_ERR_ARG, "no sort has run yet");
     *out = c->sort.plan;
+    return GSR_OK;
+}
+
+// The compositor plan the context holds: what alloc_bins sized from and the next frame is launched from (tests/test_gpu_blend_plan.py
+// compares it with what gsr_debug_blend_plan answers for the context's inputs).  Not part of the ABI.
+extern "C" int gsr_debug_last_blend_plan(gsr_ctx* c, BlendPlan* out)
+{
+    if (!c || !out) return GSR_ERR_ARG;
+    *out = c->bin.blend;
     return GSR_OK;
 }

@@ -281,6 +281,48 @@ struct BinKnobs { int32_t two_level; uint32_t big; int64_t rounds; uint32_t cell
 // (capacity: entries of the list; cu_count: the device's compute units; front_waves: FRONT_WAVES_WIDE or _NARROW.  No HIP call.)
 BinPlan plan_bins(const BinGrid& g, uint32_t n, uint64_t capacity, int cu_count, uint32_t front_waves, const BinKnobs& k);
 
+// The whole-bin sentinel: a minimum segment length that makes every bin one compositor work item, which early termination needs
+// (a segment cannot see whether earlier ones saturated the bin).  The one statement of the value written and of how it is read,
+// for the host (plan_blend) and the device (k_bin_finalize) alike.
+constexpr uint32_t SEG_LEN_WHOLE_BIN = 0x7fffff00u;
+__host__ __device__ inline bool is_whole_bin(uint32_t seg_len) { return seg_len >= 0x40000000u; }
+
+// The compositor plan: which of k_blend.hip's four kernels a frame runs, on what grid, and how k_bin_finalize cuts the bin lists
+// into its work items.  plan_blend (k_blend.hip) is the one place that decides it; alloc_bins sizes the work items, the partials
+// and the arrival masks from it and keeps it, build_frame_args copies it, launch_bin hands k_bin_finalize its policy, launch_blend
+// launches from it, and -- being part of BlendBuffers, hence of FrameArgs -- a captured graph is dropped exactly when it changes.
+// Trivially copyable, filled by name into zeroed storage (FrameArgs is compared as bytes).
+struct BlendPlan {
+    uint32_t waves_per_tile;     // 1 (k_blend, 256-thread workgroups) or 2 (k_blend2: halves a wave's serial walk)
+    uint32_t fused;              // 1: the workgroup delivering a bin's last segment folds the bin inside the kernel (arrival masks)
+    uint32_t separate_fold;      // 1: k_combine is launched behind the compositor (not fused, and bins are cut into segments)
+    uint32_t whole_bin;          // 1: every bin is one work item (is_whole_bin(seg_len)): no partials, nothing to fold
+    uint32_t threads;            // per workgroup: BLEND_THREADS x waves_per_tile
+    uint32_t grid;               // persistent workgroups wanted: the per-CU figure x CUs (GSR_BLEND_GRID pins it)
+    uint32_t queue_start;        // min(max_items, grid): the workgroups launched -- each takes the work item of its own index first --
+                                 // and the value k_bin_finalize sets the work-item counter to
+    uint32_t seg_len;            // minimum list entries per work item (a multiple of 256), or SEG_LEN_WHOLE_BIN
+    uint32_t seg_target_items;   // full segments the frame should be cut into at least (long lists -> longer segments)
+    uint32_t max_items;          // work items the item table holds (four words each); only grows unless sized afresh
+    uint32_t partial_slots;      // per-segment partials to allocate (BIN_PX x BIN_PX float4 each): max_items, 0 for whole bins
+    // the work-item policy k_bin_finalize is handed
+    int32_t items_by_size;       // order the bins' last segments by size class (one frame at a time) or leave them in raster order
+    int32_t long_policy;         // work items of at least seg_len_long entries: 1 always, 0 never, -1 where the frame's optical depth >= long_tau
+    uint32_t seg_len_long, long_tau;
+    uint32_t long_tiles_x2;      // long work items also need this many 16x16 tiles per visible splat, times two (0: no such condition)
+    uint32_t long_tau_bin;       // 0: the built-in per-bin thresholds (k_bin_finalize); else: bins from this optical depth on are one item (GSR_LONG_TAU)
+    uint32_t long_mass_min;      // a frame that is not dense as a whole: its saturated bins become items only from this optical mass per list entry on (pixels)
+    uint32_t npix;               // pixels of this context's band (the optical depth is per pixel)
+    uint32_t saturate;           // 1: quadrants whose pixels can no longer change are skipped (bit-identical; k_blend); 0: A/B knob
+};
+// Knobs::fuse_combine, saturate, items_by_size, long_items, long_tau, blend_sub, seg_target, blend_grid, seg_len
+struct BlendKnobs { uint32_t fuse_combine, saturate; int32_t items_by_size, long_items; uint32_t long_tau; int32_t blend_sub; uint32_t seg_target, blend_grid, seg_len; };
+// (nbins: bins of the context's band; npix: its pixels; capacity: entries of the list; cu_count: the device's compute units;
+//  early_out: early termination is on; allocated_items: the work items the item table holds already, 0 = size afresh.
+//  No HIP call, no environment.)
+BlendPlan plan_blend(uint32_t nbins, uint32_t npix, uint32_t capacity, int cu_count, bool throughput, bool early_out, uint32_t allocated_items,
+                     const BlendKnobs& k);
+
 struct BinBuffers {
     const uint32_t* depth_index; // *count entries
     const uint32_t* count;       // ranks to bin (SortBuffers::count)
@@ -305,21 +347,10 @@ struct BinBuffers {
     uint64_t* mailbox;           // host-mapped word: accum[5] is stored here whenever it changes
     uint64_t* report;            // [6] per-frame copy for the host: accum[0..4] after this frame, [5] = this frame's bin entries
     uint32_t capacity;
-    uint32_t max_items;
-    uint32_t seg_len;            // minimum list entries per compositor work item (multiple of 256); k_bin_finalize
-                                 // raises it for long lists and publishes the frame's value in *seg_len_dev
-    uint32_t* seg_len_dev;       // [0] the frame's segment length, [1] its number of work items, [2] reserved (0)
-    int32_t items_by_size;       // order the bins' last segments by size class (one frame at a time) or leave them in raster order
-    uint32_t* queue;             // the compositor's work-item counter, set to queue_start (= its grid size) by k_bin_finalize
-    uint32_t queue_start;
-    uint32_t seg_target_items;   // full segments the frame should be cut into at least (long lists -> longer segments)
+    uint32_t* seg_len_dev;       // [0] the frame's segment length (k_bin_finalize raises BlendPlan::seg_len for long lists and publishes the
+                                 // frame's value here), [1] its number of work items, [2] reserved (0)
+    uint32_t* queue;             // the compositor's work-item counter, set to BlendPlan::queue_start (= its grid size) by k_bin_finalize
     unsigned long long* bin_mask; // nbins: the compositor's per-bin arrival masks (one bit per segment), zeroed by the finalize step (may be null)
-    int32_t long_policy;         // work items of at least seg_len_long entries: 1 always, 0 never, -1 where the frame's optical depth >= long_tau
-    uint32_t seg_len_long, long_tau;
-    uint32_t npix;               // pixels of this context's band (the optical depth is per pixel)
-    uint32_t long_tiles_x2;      // long work items also need this many 16x16 tiles per visible splat, times two (0: no such condition)
-    uint32_t long_tau_bin;       // 0: the built-in per-bin thresholds (k_bin_finalize); else: bins from this optical depth on are one item (GSR_LONG_TAU)
-    uint32_t long_mass_min;      // a frame that is not dense as a whole: its saturated bins become items only from this optical mass per list entry on (pixels)
     // two-level binning (launch_bin; large bin grids): cells of 4 x 4 bins first, then the cell lists' chunks into the bins
     uint32_t* cell_list;         // 2 x capacity words: (splat index, rectangle in bins) per cell-list entry
     uint32_t* cell_total;        // cells + 1: entries per cell; [cells] = list entries the frame needs
@@ -331,7 +362,8 @@ struct BinBuffers {
     uint32_t band;               // 1: a band context (the frame holds fewer ranks than the scene: scans and workgroups stop at *count's rows)
     uint32_t n_max;              // entries the rank-ordered buffers hold (the scene's splats): k_bin_count may load that far before it knows *count
 };
-void launch_bin(const BinBuffers& b, const BinGrid& g, hipStream_t s);
+// (bp: the compositor's plan, of which the finalize step is handed the work-item policy)
+void launch_bin(const BinBuffers& b, const BlendPlan& bp, const BinGrid& g, hipStream_t s);
 
 struct BlendBuffers {
     const uint32_t* items;      // work items, four words each (BinBuffers::items)
@@ -339,22 +371,17 @@ struct BlendBuffers {
     const uint32_t* bin_start;  // nbins + 1
     const uint32_t* list;
     const Record* rec;
-    const uint2* bbox;
     const float4* shcol;        // evaluated SH colours (may be null)
     float4* fb;
-    float4* partial;            // max_items * 1024 float4: per-segment (colour, transmittance), slot = seg_start[bin] + segment
-    uint32_t* queue;            // device-wide work-item counter, zero at frame start
-    uint32_t seg_len;           // host's minimum; >= 0x40000000: one item per bin (early termination mode)
+    float4* partial;            // plan.partial_slots * 1024 float4: per-segment (colour, transmittance), slot = seg_start[bin] + segment
+    uint32_t* queue;            // device-wide work-item counter (k_bin_finalize sets it to plan.queue_start)
     const uint32_t* seg_len_dev; // [0] the frame's segment length, [1] its number of work items (k_bin_finalize)
-    uint32_t grid;              // persistent workgroups launched
     uint32_t capacity;          // entries the list can hold
     uint32_t nsplats;
-    unsigned long long* bin_mask; // nbins arrival masks, zeroed by the finalize step: the workgroup delivering a bin's last
-                                // segment folds the bin inside k_blend; null = the separate k_combine launch does it
-    uint32_t saturate;          // 1: quadrants whose pixels can no longer change are skipped (bit-identical; k_blend); 0: A/B knob
-    uint32_t sub;               // waves per 16x16 tile: 1 (k_blend, 256-thread workgroups) or 2 (k_blend2: halves a wave's serial walk)
+    unsigned long long* bin_mask; // nbins arrival masks, zeroed by the finalize step (plan.fused; null otherwise)
+    BlendPlan plan;             // the kernel, its grid and the work-item policy (plan_blend)
 };
-// `between` (may be null) is recorded after k_blend and before k_combine
+// `between` (may be null) is recorded after the compositor and before k_combine
 void launch_blend(const BlendBuffers& b, const BinGrid& g, float early_out_eps, hipStream_t s, hipEvent_t between);
 void launch_clear_fb(float4* fb, int32_t W, int32_t H, hipStream_t s);
 void launch_to_rgba8(const float4* fb, uint32_t* out, uint32_t npix, hipStream_t s);

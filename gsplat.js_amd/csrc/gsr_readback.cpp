@@ -112,7 +112,7 @@ int gsr_read_work_items(gsr_ctx* c, uint32_t* out)
     HIP_TRY(c, hipMemcpyAsync(out, &c->words.fstate->seg_len, 12, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const BinGrid g = make_grid(c);
-    out[3] = std::min(c->bin.blend_sub, 2u);
+    out[3] = c->bin.blend.waves_per_tile;
     out[4] = (uint32_t)((g.bx_hi - g.bx_lo) * g.nby);
     return GSR_OK;
 }

@@ -303,7 +303,7 @@ __device__ __forceinline__ void bin_finalize_body(const FinalizeArgs& fa, uint32
     // 1.6 M splats: tau 394, 3.6 tiles per splat, long items 8 % slower; C3: 5.3 tiles per splat, 23 % faster)
     const bool dense = optical * (16u * 256u) >= (uint64_t)fa.long_tau * 255u * (uint64_t)fa.npix &&
                        (uint64_t)ctot.v[1] * 2u >= (uint64_t)fa.long_tiles_x2 * ctot.v[0];
-    // Which bins become ONE work item (gsr_frame.cpp, "Work-item length").  A whole-bin item stops where the bin saturates, which
+    // Which bins become ONE work item (k_blend.hip, "Work-item length").  A whole-bin item stops where the bin saturates, which
     // pays where the bin holds much more than it takes to saturate it -- and costs a serial pole as long as that takes; a bin cut
     // into segments is composited by several workgroups at once, every segment in full.  A frame can mix both kinds of bins (a
     // dense object in front of a sparse background), so the choice is made PER BIN, deterministically from figures of this
@@ -320,7 +320,7 @@ __device__ __forceinline__ void bin_finalize_body(const FinalizeArgs& fa, uint32
     // pays for; one frame at a time only).  long_policy 1 / 0 pin all / no bins.
     constexpr uint32_t LONG_TAU_B_LO = 8, LONG_TAU_B_HI = 60;
     uint32_t long_from = 0xffffffffu;                       // bins of at least this many entries are one work item
-    if (seg_len_min < 0x40000000u) {
+    if (!is_whole_bin(seg_len_min)) {
         if (fa.long_policy > 0) long_from = 0u;
         else if (fa.long_policy < 0 && mass > 0u) {
             const uint64_t E = ent_tot.v[0];
@@ -336,7 +336,7 @@ __device__ __forceinline__ void bin_finalize_body(const FinalizeArgs& fa, uint32
     // frames in flight, C3: 4970 -> 5310 frames/s); plain short segments in throughput contexts stay in raster order (C2: 11 550 vs 11 250)
     const bool by_size = fa.by_size != 0 || mxbin >= long_from;
     uint32_t seg_len = seg_min;
-    if (seg_min < 0x40000000u)
+    if (!is_whole_bin(seg_min))
         seg_len = min(max(ent_tot.v[0] / seg_target_items / 256u * 256u, seg_min), max(SEG_LEN_MAX, seg_min));
     // Items are emitted heaviest first -- by size class (whole bins, full segments, the bins' last segments alike), a counting
     // sort over FIN_CLASSES classes in LDS -- so the compositor's queue hands out the long items while the chip is still full
@@ -1130,21 +1130,21 @@ extern "C" int gsr_debug_bin_plan(int nbxb, int nby, unsigned int n, unsigned lo
     return (int)sizeof(BinPlan);
 }
 
-static FinalizeArgs make_finalize_args(const BinBuffers& b)
+// the finalize step's arguments: the binning's buffers and, from the compositor's plan (plan_blend, k_blend.hip), the work-item policy
+static FinalizeArgs make_finalize_args(const BinBuffers& b, const BlendPlan& bp)
 {
-    return FinalizeArgs{b.bin_total, b.plan.nbins, b.seg_len, b.seg_target_items, b.items_by_size, b.seg_len_dev, b.max_items, b.capacity,
+    return FinalizeArgs{b.bin_total, b.plan.nbins, bp.seg_len, bp.seg_target_items, bp.items_by_size, b.seg_len_dev, bp.max_items, b.capacity,
                         b.slots, b.plan.form != BIN_FINALIZE_ONLY ? 1u : 0u, b.bin_start, b.seg_start, b.items, b.overflow, b.visible, b.tile_entries, b.accum,
-                        b.report, b.queue, b.queue_start, b.mailbox, b.bin_mask, b.long_policy, b.seg_len_long, b.long_tau, b.npix, b.long_tiles_x2, b.long_tau_bin, b.long_mass_min};
+                        b.report, b.queue, bp.queue_start, b.mailbox, b.bin_mask, bp.long_policy, bp.seg_len_long, bp.long_tau, bp.npix, bp.long_tiles_x2, bp.long_tau_bin, bp.long_mass_min};
 }
 
 // Two levels (see "Two-level binning" above): count / scan / scatter over the cells, then count / scan / scatter of the
 // cell lists' chunks into the bins; the finalize step is the first workgroup of the last kernel.
-static void launch_bin_two_level(const BinBuffers& b, const BinGrid& g, hipStream_t s)
+static void launch_bin_two_level(const BinBuffers& b, const FinalizeArgs& fa, const BinGrid& g, hipStream_t s)
 {
     const BinPlan& p = b.plan;
     BinGrid gc = g;
     gc.nbx = p.ncx; gc.nby = p.ncy; gc.bx_lo = 0; gc.bx_hi = p.ncx;
-    const FinalizeArgs fa = make_finalize_args(b);
     const CellArgs ca{b.cell_start, b.chunk_start, reinterpret_cast<uint4*>(b.chunk_info), CELL_SHIFT};
     const uint4* ci = reinterpret_cast<const uint4*>(b.chunk_info);
     const CellGeom cg{p.ncx, p.ncells, g.bx_hi - g.bx_lo, g.nby};
@@ -1182,12 +1182,12 @@ static void launch_count_and_scan(const BinBuffers& b, const BinGrid& g, hipStre
     launch_column_scan(b.table, b.bin_total, p.nbins, p.blocks, s, b.band ? b.count : nullptr, p.rounds * BIN_RANKS_PER_BLOCK);
 }
 
-void launch_bin(const BinBuffers& b, const BinGrid& g, hipStream_t s)
+void launch_bin(const BinBuffers& b, const BlendPlan& bp, const BinGrid& g, hipStream_t s)
 {
     const BinPlan& p = b.plan;
     if (p.nbins <= 0) return;
     set_scatter_lds_attribute();
-    const FinalizeArgs fa = make_finalize_args(b);
+    const FinalizeArgs fa = make_finalize_args(b, bp);
 #define GSR_LAUNCH_SCATTER(K, THREADS, STARTS)                                                                                      \
     hipLaunchKernelGGL((K), dim3(p.blocks + p.extra_wg, p.slices.sx * p.slices.sy), dim3(THREADS), p.scatter_lds, s,               \
                        b.depth_index, (const uint32_t*)b.rects, b.count, g, p.slices,                                               \
@@ -1218,7 +1218,7 @@ void launch_bin(const BinBuffers& b, const BinGrid& g, hipStream_t s)
         else GSR_LAUNCH_SCATTER((k_bin_scatter_big<4, 2>), SCAT_THREADS, b.bin_start_pre);
         break;
     case BIN_TWO_LEVEL:
-        launch_bin_two_level(b, g, s);
+        launch_bin_two_level(b, fa, g, s);
         break;
     }
 #undef GSR_LAUNCH_SCATTER

@@ -36,6 +36,9 @@
 // so the coverage test (|vPosition|^2 <= 4) is bit-identical to the oracle's.
 #include "gsr_internal.h"
 
+#include <algorithm>
+#include <cstring>
+
 namespace gsr {
 
 GSR_BOUNDS_DECL(blend)   // sites: 0 work item's bin, 1 its segment, 2 list position, 3 splat index in the list, 4 item range inside the bin
@@ -665,8 +668,8 @@ extern "C" int gsr_debug_bin_info(unsigned int* out /* 16384*8 */)
 }
 #endif
 
-// Fold the per-segment partials of every multi-segment bin, front to back -- the stand-alone form (BlendBuffers::bin_mask
-// null); by default the fold runs inside k_blend and this kernel is not launched.  A thread folds its four
+// Fold the per-segment partials of every multi-segment bin, front to back -- the stand-alone form (BlendPlan::separate_fold);
+// by default the fold runs inside k_blend and this kernel is not launched.  A thread folds its four
 // pixels as four independent chains and the segment loop is unrolled, so 16 loads are in flight per
 // thread: the kernel is a latency-bound read of the partials (85 MB on C3 with 512-entry segments).
 __global__ __launch_bounds__(BLEND_THREADS) void k_combine(const uint32_t* __restrict__ seg_start,
@@ -703,20 +706,129 @@ __global__ __launch_bounds__(BLEND_THREADS) void k_combine(const uint32_t* __res
     }
 }
 
+// ---------------------------------------------------------------------------
+// The plan: which of the four kernels above a frame runs, on what grid, and how k_bin_finalize cuts the bin lists into its work
+// items (BlendPlan, gsr_internal.h).  Every threshold and per-kind figure lives here and nowhere else; alloc_bins allocates by
+// the answer, launch_bin hands k_bin_finalize its policy and launch_blend launches by it.
+// ---------------------------------------------------------------------------
+// Compositor work-item granularity: list entries per (bin, segment) item.  SEG_LEN_WHOLE_BIN (gsr_internal.h) = one item per
+// bin, which early termination needs (a segment cannot see whether earlier ones saturated the bin).
+constexpr uint32_t SEG_LEN_MIN = 512;            // shortest segment; k_bin_finalize lengthens it so that the frame is cut
+                                                 // into about SEG_TARGET_* full segments (multiples of 256 entries)
+constexpr uint32_t SEG_TARGET_EXACT = 5000;      // one frame at a time: concurrency from the frame's own segments (C3: 512)
+constexpr uint32_t SEG_TARGET_THROUGHPUT = 1300; // GSR_FLAG_THROUGHPUT: concurrency comes from the other frames in flight
+                                                 // (C3: 2048-entry segments; a 1/8-screen band stays at 512)
+// Persistent compositor workgroups per CU.  k_blend is built for 7 waves per SIMD (72 VGPRs), so 7 four-wave
+// workgroups are resident per CU and the grid must not exceed that: a workgroup that is not resident at launch still
+// owns its first work item by index (a heavy one: the queue is ordered heaviest first) and starts it only when a
+// resident workgroup exits.  With 8 per CU, one item in eight began at 222 us of a 270 us kernel (in-kernel stamps,
+// scripts/blend_stamps.py): k_blend 271 -> 252 us on C3 at 7 per CU.
+constexpr uint32_t BLEND_WG_PER_CU_EXACT = 7;
+// Contexts that overlap with others' kernels (GSR_FLAG_THROUGHPUT): 6 per CU left a wave slot per SIMD to the other
+// contexts and was best while the fold of the partials was a kernel of its own; with the fold inside k_blend 7 is
+// (bench.py, three frames in flight, C3: 3324 -> 3400 frames/s, reproducible; C2 -0.8 %, C4 and early-out unchanged).
+constexpr uint32_t BLEND_WG_PER_CU_THROUGHPUT = 7;
+// Two waves per tile (k_blend2, 512-thread workgroups): three workgroups per CU are resident (6 waves per SIMD).
+constexpr uint32_t BLEND_WG_PER_CU_SUB2 = 3;
+// Waves per tile.  Two (k_blend2) halve a wave's serial walk over a work item -- the pole of a frame rendered alone, where a
+// wave needs ~560 cycles per entry visit whatever else the chip does -- and pay with occupancy (24 instead of 28 waves
+// per CU) and saturation tests at chunk instead of 64-entry boundaries.  Measured one frame at a time: C3 k_blend 194 ->
+// 147 us, C1 20 -> 15; C2 (short segments) 77 -> 86, with 1024-entry segments 80; C4, whose 8160 bins keep every slot
+// busy: 412 -> 509; three frames in flight, C3: 5280 -> 4410 frames/s.  So: contexts that render one frame at a time, up
+// to SUB2_MAX_BINS bins, with segments of at least 1024 entries.  (Leaving the choice to k_bin_finalize per frame --
+// both kernels launched, the other one returning at once -- cost 4.5 us per frame for the idle launch.)
+constexpr uint32_t SUB2_MAX_BINS = 4096, SEG_LEN_MIN_SUB2 = 1024;
+
+// Work-item length.  With the saturation skip of k_blend a work item ends as soon as nothing it could still add can change
+// a bit of its pixels, and that needs the item to contain the splats that saturate it: a bin cut into 512-entry segments
+// never saturates inside one of them (every segment starts from transmittance 1), a bin processed as one item stops
+// after the few thousand entries that matter (C3: 3430 -> 4990 frames/s with three frames in flight, 2670 -> 2945 one at
+// a time; C4: 292 -> 856).  Where the scene does not saturate (C2: small splats, 9 % of the entries skipped against 53 %
+// on C3 and 85 % on C4; or any thin, low-opacity scene) long items only cost balance (C2: 6670 -> 2780 frames/s).
+// k_bin_finalize decides per frame, from a figure the projection already has: the frame's optical depth
+//     tau = sum over visible splats of opacity x (16x16 tiles its box overlaps) x 256 / pixels
+// (C1 14, C2 74, C3 362, C4 1090): items are at least SEG_LEN_LONG entries (in practice whole bins) from LONG_TAU_* on.
+// A function of the frame alone: no feedback from earlier frames, the same frame always takes the same path.
+// Where long items start to pay (scripts/tau_crossover.py: the C3 and C2 generators at 0.25 .. 1.6 M splats, 1080p): with
+// other frames' kernels filling the gaps, between tau 90 and 145 for both generators (tau 90: 10 390 -> 10 080 frames/s,
+// tau 145: 7350 -> 8640, tau 250: 4730 -> 6800); one frame at a time the few long items are the frame's tail and the
+// crossover depends on the scene (C3 generator: tau ~ 255, C3 itself +23 %; the C2 generator's small splats still lose
+// 8 % at tau 390), so the threshold there stays high.
+constexpr uint32_t SEG_LEN_LONG = 32768;   // (16384: C4 k_blend 437 instead of 405 us -- its heaviest bins hold 50-100 k entries; 65536 measures the same)
+constexpr uint32_t LONG_TAU_EXACT = 340, LONG_TAU_THROUGHPUT = 120;
+// a frame that is not dense as a whole: bins far past saturation become one item only where a list entry carries at least this
+// optical mass (pixels): C3 14, C2 8, 2 M tiny splats 1.9 -- one frame at a time a 3000-entry serial walk is the frame's tail
+constexpr uint32_t LONG_MASS_MIN_EXACT = 12, LONG_MASS_MIN_THROUGHPUT = 0;
+constexpr uint32_t LONG_TILES_X2_EXACT = 9;   // one frame at a time: and at least 4.5 tiles per visible splat (k_bin_finalize)
+constexpr uint32_t LONG_TILES_X2_THROUGHPUT = 6;   // with frames in flight: 3 (scripts/policy_check.py: 2 M tiny splats, 1.9 tiles each, tau 264:
+                                                   // long items -26 %; the C2 generator, 3.6 tiles each: +10 % at the same tau)
+
+BlendPlan plan_blend(uint32_t nbins, uint32_t npix, uint32_t capacity, int cu_count, bool throughput, bool early_out, uint32_t allocated_items,
+                     const BlendKnobs& k)
+{
+    BlendPlan p;
+    memset(&p, 0, sizeof p);
+    p.waves_per_tile = k.blend_sub >= 2 ? 2u : k.blend_sub == 1 ? 1u : (!throughput && nbins <= SUB2_MAX_BINS) ? 2u : 1u;
+    p.threads = (uint32_t)BLEND_THREADS * p.waves_per_tile;
+    const uint32_t wg_per_cu = p.waves_per_tile == 2 ? BLEND_WG_PER_CU_SUB2 : throughput ? BLEND_WG_PER_CU_THROUGHPUT : BLEND_WG_PER_CU_EXACT;
+    p.grid = k.blend_grid ? k.blend_grid : wg_per_cu * (uint32_t)std::max(cu_count, 1);
+    // early termination composites whole bins whatever GSR_SEG_LEN says
+    p.seg_len = early_out ? SEG_LEN_WHOLE_BIN : k.seg_len ? k.seg_len : p.waves_per_tile == 2 ? SEG_LEN_MIN_SUB2 : SEG_LEN_MIN;
+    p.whole_bin = is_whole_bin(p.seg_len) ? 1u : 0u;
+    p.seg_target_items = k.seg_target ? k.seg_target : throughput ? SEG_TARGET_THROUGHPUT : SEG_TARGET_EXACT;
+    // segments = work items (each may need a partial slot): one per bin plus one per seg_len entries
+    const uint32_t want_items = nbins + capacity / p.seg_len + 16;
+    p.max_items = allocated_items ? std::max(allocated_items, want_items) : want_items;
+    p.partial_slots = p.whole_bin ? 0u : p.max_items;
+    p.queue_start = std::min(p.max_items, p.grid);
+    p.fused = k.fuse_combine ? 1u : 0u;
+    p.separate_fold = (!p.fused && !p.whole_bin) ? 1u : 0u;
+    // work items heaviest first (one frame at a time) or in raster order
+    p.items_by_size = k.items_by_size >= 0 ? k.items_by_size : throughput ? 0 : 1;
+    p.long_policy = p.whole_bin ? 0 : k.long_items >= 0 ? k.long_items : k.saturate ? -1 : 0;
+    p.seg_len_long = SEG_LEN_LONG;
+    p.long_tau = throughput ? LONG_TAU_THROUGHPUT : LONG_TAU_EXACT;
+    p.long_tiles_x2 = throughput ? LONG_TILES_X2_THROUGHPUT : LONG_TILES_X2_EXACT;
+    p.long_tau_bin = k.long_tau;
+    p.long_mass_min = throughput ? LONG_MASS_MIN_THROUGHPUT : LONG_MASS_MIN_EXACT;
+    p.npix = npix;
+    p.saturate = k.saturate ? 1u : 0u;
+    return p;
+}
+
+// The plan for tests (tests/test_blend_plan.py): no context and no device, so it answers wherever the library loads.  Returns
+// sizeof(BlendPlan), for the caller to check its idea of the layout against.
+extern "C" int gsr_debug_blend_plan(unsigned int nbins, unsigned int npix, unsigned int capacity, int cu_count, int throughput, int early_out,
+                                     unsigned int allocated_items, int fuse_combine, int saturate, int items_by_size, int long_items, unsigned int long_tau,
+                                     int blend_sub, unsigned int seg_target, unsigned int blend_grid, unsigned int seg_len, BlendPlan* out)
+{
+    *out = plan_blend(nbins, npix, capacity, cu_count, throughput != 0, early_out != 0, allocated_items,
+                      BlendKnobs{fuse_combine ? 1u : 0u, saturate ? 1u : 0u, items_by_size, long_items, long_tau, blend_sub, seg_target, blend_grid, seg_len});
+    return (int)sizeof(BlendPlan);
+}
+
+// Every instantiation of the compositor, once: the launch walks this table.
+using BlendFn = void (*)(const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, const Record*, const float4*, float4*, float4*, uint32_t*,
+                         BinGrid, float, const uint32_t*, uint32_t, uint32_t, unsigned long long*, uint32_t);
+struct BlendKernel { BlendFn fn; uint32_t waves_per_tile; bool fused; uint32_t threads; };
+static const BlendKernel BLEND_KERNELS[] = {
+    {k_blend, 1, true, BLEND_THREADS},
+    {k_blend2, 2, true, 2 * BLEND_THREADS},
+    {k_blend_unfused, 1, false, BLEND_THREADS},
+    {k_blend2_unfused, 2, false, 2 * BLEND_THREADS},
+};
+
 void launch_blend(const BlendBuffers& b, const BinGrid& g, float early_out_eps, hipStream_t s, hipEvent_t between)
 {
+    const BlendPlan& p = b.plan;
     const int nbins = (g.bx_hi - g.bx_lo) * g.nby;
     if (nbins <= 0) return;
-#define GSR_LAUNCH_BLEND(K, THREADS)                                                                                      \
-    hipLaunchKernelGGL(K, dim3(b.grid), dim3(THREADS), 0, s, b.items, b.seg_start, b.bin_start, b.list, b.rec, b.shcol, b.fb, \
-                       b.partial, b.queue, g, early_out_eps, b.seg_len_dev, b.capacity, b.nsplats, b.bin_mask, b.saturate)
-    if (b.sub >= 2 && b.bin_mask) GSR_LAUNCH_BLEND(k_blend2, 2 * BLEND_THREADS);
-    else if (b.sub >= 2) GSR_LAUNCH_BLEND(k_blend2_unfused, 2 * BLEND_THREADS);
-    else if (b.bin_mask) GSR_LAUNCH_BLEND(k_blend, BLEND_THREADS);
-    else GSR_LAUNCH_BLEND(k_blend_unfused, BLEND_THREADS);
-#undef GSR_LAUNCH_BLEND
+    for (const BlendKernel& k : BLEND_KERNELS)
+        if (k.waves_per_tile == p.waves_per_tile && k.fused == (p.fused != 0u))
+            hipLaunchKernelGGL(k.fn, dim3(p.queue_start), dim3(k.threads), 0, s, b.items, b.seg_start, b.bin_start, b.list, b.rec, b.shcol, b.fb,
+                               b.partial, b.queue, g, early_out_eps, b.seg_len_dev, b.capacity, b.nsplats, b.bin_mask, p.saturate);
     if (between) (void)hipEventRecord(between, s);
-    if (b.seg_len < 0x40000000u && !b.bin_mask)
+    if (p.separate_fold)
         hipLaunchKernelGGL(k_combine, dim3(nbins), dim3(BLEND_THREADS), 0, s, b.seg_start, (const float4*)b.partial, b.fb, g);
 }
 
