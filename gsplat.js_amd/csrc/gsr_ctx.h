@@ -162,10 +162,23 @@ struct SharedScene {
         void reset() { mask.reset(); scratch.reset(); counters.reset(); region.reset(); words = counter_words = 0; region_bytes = 0; count = 0; }
         uint64_t bytes() const { return (uint64_t)words * 8 + (uint64_t)counter_words * 4 + region_bytes; }
     } sel;
+    // The contribution accumulators (gsr_contrib.cpp; DESIGN.md section 4, "Contribution"): per splat of THIS copy, so the members
+    // have one set together and their passes add into it with atomics that commute.  Nothing is allocated until the first reset or
+    // pass; without buffers the state is "never reset".  Dropped wherever the selection is emptied: the indices are the old numbering's.
+    struct Contrib {
+        DevBuf<unsigned long long> weight;   // `rows` each: sum of rintf(w * 2^24),
+        DevBuf<uint32_t> peak, pixels;       // max of w (bits of a non-negative f32), fragments modulo 2^32
+        DevBuf<uint32_t> counters;           // [0] frames: the passes that contributed since the last reset; [1] reserved (0)
+        uint32_t rows = 0;                   // splats the arrays were allocated for (the scene's count at the reset)
+        static constexpr uint32_t COUNTER_WORDS = 2;
+        bool live() const { return (bool)counters.p; }
+        void reset() { weight.reset(); peak.reset(); pixels.reset(); counters.reset(); rows = 0; }
+        uint64_t bytes() const { return live() ? (uint64_t)rows * 16 + COUNTER_WORDS * 4 : 0; }
+    } contrib;
     // device bytes of the state the members hold once
     uint64_t bytes() const
     {
-        return (uint64_t)arr_rows * (7 * 4 + (arr.rot ? 32 : 0)) + ((uint64_t)sh_rows + sh_spare_rows) * 3 * 32 + sel.bytes();
+        return (uint64_t)arr_rows * (7 * 4 + (arr.rot ? 32 : 0)) + ((uint64_t)sh_rows + sh_spare_rows) * 3 * 32 + sel.bytes() + contrib.bytes();
     }
 };
 
@@ -475,6 +488,10 @@ void scene_release(gsr_ctx* c);
 // order, become the scene; SH state, generation, bins and the members' frame state as the header says of limitBox; the selection is
 // empty afterwards.  `what` names the caller in a HIP error.
 int scene_compact(gsr_ctx* c, const ScenePred& p, const char* what, uint32_t* kept_out);
+// gsr_select.cpp: the selection's buffers for the scene's count, allocated (the mask zeroed) by the first call that needs them; and
+// the end of every call that changes the selection: selection <- selection (op) scratch on the device, its count back to the host
+int select_ensure(gsr_ctx* c);
+int select_fold_and_count(gsr_ctx* c, int op, uint32_t* selected);
 // gsr_comm.cpp
 void comm_release(gsr_ctx* c);
 // gsr_depth.cpp: the depth pass for the frame enqueued last.  depth_frame_check: what every pass demands of that frame (GSR_ERR_ARG,

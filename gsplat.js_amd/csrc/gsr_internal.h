@@ -471,6 +471,28 @@ void launch_select_box(uint32_t n, const float* px, const float* py, const float
 // sel <- sel (op) scratch, bits at and above n dropped; *count <- the bits set afterwards (block_sums: ceil(nwords / SELECT_APPLY_THREADS) words)
 void launch_select_apply(int op, uint32_t* sel, const uint32_t* scratch, uint32_t n, uint32_t nwords, uint32_t* block_sums, uint32_t* count, hipStream_t s);
 
+// Contribution (k_contrib.hip; DESIGN.md section 4, "Contribution"): the last frame's bin lists walked once more, the weight
+// w = T * B of every fragment kept per SPLAT and summed over pixels and passes into three accumulators held with the scene.
+struct ContribBuffers {
+    const uint32_t* bin_start;   // nbins + 1      (the frame's lists, records and positions, as DepthBuffers holds them)
+    const uint32_t* list;
+    const Record* rec;
+    const float *px, *py, *pz;
+    const uint32_t* overflow;    // the frame's overflow word: non-zero = its lists did not fit, nothing of it is walked or counted
+    unsigned long long* weight;  // rows: sum of rintf(w * 2^24) over the splat's fragments
+    uint32_t* peak;              // rows: max of w, as the bits of a non-negative f32
+    uint32_t* pixels;            // rows: the splat's fragments, modulo 2^32
+    uint32_t* frames;            // one word: passes that contributed
+    uint32_t capacity;           // entries the list can hold
+    uint32_t nsplats;
+    uint32_t rows;               // splats the accumulators were allocated for
+};
+constexpr int CONTRIB_WEIGHT = 0, CONTRIB_PEAK = 1, CONTRIB_PIXELS = 2;   // (GSR_CONTRIB_*)
+void launch_contrib(const ContribBuffers& b, const BinGrid& g, const CamParams& cam, bool skip, hipStream_t s);
+// scratch <- the splats i < n whose value (stat) is below `below`, compared in f64: every word of it is stored, no zeroing needed
+void launch_contrib_select(int stat, double below, uint32_t n, const unsigned long long* weight, const uint32_t* peak, const uint32_t* pixels,
+                           uint32_t* scratch, uint32_t nwords, hipStream_t s);
+
 // multi-GPU exchange helpers (RGBA8 slabs of the all-gather)
 constexpr int MAX_SLABS = 16;
 struct SlabEdges { int32_t x0[MAX_SLABS], x1[MAX_SLABS]; };

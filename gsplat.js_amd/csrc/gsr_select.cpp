@@ -11,8 +11,10 @@ namespace {
 
 uint32_t words_of(uint32_t n) { return (n + 31u) / 32u; }
 
+}  // namespace
+
 // the selection's buffers for the scene's count, allocated (the mask zeroed) by the first call that needs them
-int ensure_selection(gsr_ctx* c)
+int gsr::select_ensure(gsr_ctx* c)
 {
     SharedScene& sc = *c->scene;
     SharedScene::Selection& sel = sc.sel;
@@ -30,7 +32,7 @@ int ensure_selection(gsr_ctx* c)
 }
 
 // selection <- selection (op) scratch on the device, its count back to the host: the end of every call that changes it
-int fold_and_count(gsr_ctx* c, int op, uint32_t* selected)
+int gsr::select_fold_and_count(gsr_ctx* c, int op, uint32_t* selected)
 {
     SharedScene::Selection& sel = c->scene->sel;
     launch_select_apply(op, sel.mask, sel.scratch, c->scene->n, sel.words, sel.counters + 2, sel.counters, c->stream);
@@ -43,6 +45,8 @@ int fold_and_count(gsr_ctx* c, int op, uint32_t* selected)
     if (selected) *selected = count;
     return GSR_OK;
 }
+
+namespace {
 
 bool op_ok(int32_t op) { return op >= GSR_SELOP_REPLACE && op <= GSR_SELOP_INTERSECT; }
 
@@ -74,7 +78,7 @@ int gsr_select_region(gsr_ctx* c, const gsr_region* region, int32_t mode, int32_
     else if (int r = depth_settle_frame(c, "gsr_select_region")) return r;
     SharedScene& sc = *c->scene;
     if (!sc.n) { if (selected) *selected = 0; return GSR_OK; }
-    if (int r = ensure_selection(c)) return r;
+    if (int r = select_ensure(c)) return r;
     SharedScene::Selection& sel = sc.sel;
 
     SelectRegion reg{q.x0, q.y0, q.x1, q.y1, nullptr, 0, 0u};
@@ -104,7 +108,7 @@ int gsr_select_region(gsr_ctx* c, const gsr_region* region, int32_t mode, int32_
     HIP_TRY(c, hipMemcpyAsync(&invalid, sel.counters + 1, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (invalid) return fail(c, GSR_ERR_OVERFLOW, "gsr_select_region: the frame's bin lists did not fit: nothing was selected");
-    return fold_and_count(c, op, selected);
+    return select_fold_and_count(c, op, selected);
 }
 
 int gsr_select_box(gsr_ctx* c, const double* box, int32_t op, uint32_t* selected)
@@ -117,10 +121,10 @@ int gsr_select_box(gsr_ctx* c, const double* box, int32_t op, uint32_t* selected
     HIP_TRY(c, hipSetDevice(c->device));
     SharedScene& sc = *c->scene;
     if (!sc.n) { if (selected) *selected = 0; return GSR_OK; }
-    if (int r = ensure_selection(c)) return r;
+    if (int r = select_ensure(c)) return r;
     launch_select_box(sc.n, sc.arr.px, sc.arr.py, sc.arr.pz, box, sc.sel.scratch, sc.sel.words, c->stream);
     HIP_TRY(c, hipGetLastError());
-    return fold_and_count(c, op, selected);
+    return select_fold_and_count(c, op, selected);
 }
 
 int gsr_selection_set(gsr_ctx* c, const uint32_t* words, uint32_t nwords, int32_t op, uint32_t* selected)
@@ -132,10 +136,10 @@ int gsr_selection_set(gsr_ctx* c, const uint32_t* words, uint32_t nwords, int32_
     if (words && nwords < need) return fail(c, GSR_ERR_ARG, "gsr_selection_set: nwords (%u) is smaller than ceil(%u / 32) = %u", nwords, sc.n, need);
     HIP_TRY(c, hipSetDevice(c->device));
     if (!sc.n) { if (selected) *selected = 0; return GSR_OK; }
-    if (int r = ensure_selection(c)) return r;
+    if (int r = select_ensure(c)) return r;
     HIP_TRY(c, hipMemsetAsync(sc.sel.scratch, 0, (size_t)sc.sel.words * 4, c->stream));
     if (words) HIP_TRY(c, hipMemcpyAsync(sc.sel.scratch, words, (size_t)need * 4, hipMemcpyHostToDevice, c->stream));
-    return fold_and_count(c, op, selected);   // (host bits at and above n are dropped there)
+    return select_fold_and_count(c, op, selected);   // (host bits at and above n are dropped there)
 }
 
 int gsr_selection_invert(gsr_ctx* c, uint32_t* selected)
@@ -143,8 +147,8 @@ int gsr_selection_invert(gsr_ctx* c, uint32_t* selected)
     if (!c) return GSR_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     if (!c->scene->n) { if (selected) *selected = 0; return GSR_OK; }
-    if (int r = ensure_selection(c)) return r;
-    return fold_and_count(c, SELOP_INVERT, selected);
+    if (int r = select_ensure(c)) return r;
+    return select_fold_and_count(c, SELOP_INVERT, selected);
 }
 
 int gsr_read_selection(gsr_ctx* c, uint32_t* words, uint32_t nwords, uint32_t* selected)
@@ -177,7 +181,7 @@ int gsr_scene_erase_selected(gsr_ctx* c, int32_t keep_selected, uint32_t* new_co
         return GSR_OK;
     }
     HIP_TRY(c, hipSetDevice(c->device));
-    if (int r = ensure_selection(c)) return r;   // (keep_selected with no selection yet: the zeroed mask, everything goes)
+    if (int r = select_ensure(c)) return r;   // (keep_selected with no selection yet: the zeroed mask, everything goes)
     return scene_compact(c, ScenePred{nullptr, sc.sel.mask, keep_selected ? 1u : 0u}, "gsr_scene_erase_selected", new_count);
 }
 

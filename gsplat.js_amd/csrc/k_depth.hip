@@ -13,15 +13,12 @@
 // depth_accumulate below, and through nothing else, for a fragment.
 //
 // Compiled with -ffp-contract=off like the rest of the device code: the fused multiply-adds are the explicit ones.
-#include "gsr_internal.h"
+#include "k_depth_walk.h"   // DepthEntry, depth_entry, depth_weight, depth_row_u / _w, depth_tile_reach: shared with k_contrib.hip
 
 namespace gsr {
 
 GSR_BOUNDS_DECL(depth)   // sites: 0 bin -> bin_start, 1 list position, 2 splat index in the list, 3 LDS cell, 4 query pixel,
                          // 5 sample of a strided hit plane
-constexpr int DEPTH_THREADS = 256;
-constexpr int DEPTH_CHUNK = DEPTH_THREADS;
-constexpr float DEPTH_LOG2E = 1.4426950408889634f;
 constexpr uint32_t HIT_NONE = 0xffffffffu;
 
 struct DepthPixel {
@@ -33,57 +30,9 @@ __device__ __forceinline__ DepthPixel depth_pixel_start()
     return DepthPixel{1.0f, 0.0f, __uint_as_float(0x7f800000u), HIT_NONE};
 }
 
-// One entry as the walk reads it: the record folded to bin-relative form (k_blend's staging: o = centre of the bin's first pixel),
-// the splat's depth and its index.
-struct DepthEntry {
-    float ux, uy, ncu, wx, wy, ncw, la, z;
-    uint32_t index;
-};
-
-// z of a splat: w of projection * (view * (x, y, z, 1)), k_project_key's sums term by term
-__device__ __forceinline__ float depth_of(const CamParams& cam, float x, float y, float z)
-{
-    float camv[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        float s = cam.view[0 * 4 + r] * x;
-        s = s + cam.view[1 * 4 + r] * y;
-        s = s + cam.view[2 * 4 + r] * z;
-        s = s + cam.view[3 * 4 + r];
-        camv[r] = s;
-    }
-    float s = cam.proj[0 * 4 + 3] * camv[0];
-    s = s + cam.proj[1 * 4 + 3] * camv[1];
-    s = s + cam.proj[2 * 4 + 3] * camv[2];
-    s = s + cam.proj[3 * 4 + 3] * camv[3];
-    return s;
-}
-
-__device__ __forceinline__ DepthEntry depth_entry(const Record* __restrict__ rec, const float* __restrict__ px, const float* __restrict__ py,
-                                                  const float* __restrict__ pz, uint32_t i, const CamParams& cam, float bx0c, float by0c)
-{
-    const float4* rp = reinterpret_cast<const float4*>(rec + i);
-    const float4 ra = rp[0], rb = rp[1];   // (cx, cy, ux, uy), (wx, wy, la, rgb8)
-    const float cxr = ra.x - bx0c, cyr = ra.y - by0c;
-    DepthEntry e;
-    e.ux = ra.z; e.uy = ra.w; e.ncu = -__builtin_fmaf(ra.w, cyr, ra.z * cxr);
-    e.wx = rb.x; e.wy = rb.y; e.ncw = -__builtin_fmaf(rb.y, cyr, rb.x * cxr);
-    e.la = rb.z;
-    e.z = depth_of(cam, px[i], py[i], pz[i]);
-    e.index = i;
-    return e;
-}
-
-// THE per-fragment arithmetic, in two steps so that k_pick can evaluate the weights of 64 entries across its lanes and still
-// apply them one after the other: the weight B of an entry at the pixel (pxf, pyf) (bin-relative, small exact integers), or a
-// negative value where the fragment is discarded ...
-__device__ __forceinline__ float depth_weight(const DepthEntry& e, float pxf, float ur, float wr)
-{
-    const float vx = __builtin_fmaf(e.ux, pxf, ur), vy = __builtin_fmaf(e.wx, pxf, wr);
-    const float q = __builtin_fmaf(vy, vy, vx * vx);
-    return q <= 4.0f ? __builtin_amdgcn_exp2f(__builtin_fmaf(q, -DEPTH_LOG2E, e.la)) : -1.0f;
-}
-// ... and the recurrence
+// The per-fragment arithmetic is k_depth_walk.h's depth_weight (the weight B of an entry at a pixel, negative where the fragment is
+// discarded), in its own step so that k_pick can evaluate the weights of 64 entries across its lanes and still apply them one
+// after the other through the recurrence:
 __device__ __forceinline__ void depth_accumulate(DepthPixel& p, float B, float z, uint32_t index, float hit_alpha)
 {
     if (B >= 0.0f) {
@@ -93,10 +42,6 @@ __device__ __forceinline__ void depth_accumulate(DepthPixel& p, float B, float z
         if (p.hit == HIT_NONE && 1.0f - p.T >= hit_alpha) { p.hit = index; p.hit_z = z; }
     }
 }
-// the row terms of vPosition, shared by the pixels of a row: uy * py - dot(u, c), wy * py - dot(w, c)
-__device__ __forceinline__ float depth_row_u(const DepthEntry& e, float pyf) { return __builtin_fmaf(e.uy, pyf, e.ncu); }
-__device__ __forceinline__ float depth_row_w(const DepthEntry& e, float pyf) { return __builtin_fmaf(e.wy, pyf, e.ncw); }
-
 // SKIP: a wave leaves out the entries that provably cannot reach its 16x16 tile -- a conservative test at staging, k_blend's
 // quadrant test at tile size: the tile's pixel centres lie outside the oriented box |vPosition.x|, |vPosition.y| <= 2
 // (separating axes u and w), or farther from the centre than the longer semi-axis.  Every fragment left out has q > 4, so the
@@ -154,24 +99,7 @@ __global__ __launch_bounds__(DEPTH_THREADS) void k_depth_planes(DepthBuffers a, 
             s_a[threadIdx.x] = make_float4(en.ux, en.uy, en.ncu, en.wx);
             s_b[threadIdx.x] = make_float4(en.wy, en.ncw, en.la, en.z);
             s_idx[threadIdx.x] = en.index;
-            tiles = 0xfu;
-            if (SKIP) {
-                // vPosition at a tile's centre (pixel offset 7.5 from its first pixel centre) and how far it can move over the
-                // tile's pixel centres (7.5 each way); the slack covers the rounding of these sums
-                const float eu = 7.5f * (fabsf(en.ux) + fabsf(en.uy)) + 2.0005f;
-                const float ew = 7.5f * (fabsf(en.wx) + fabsf(en.wy)) + 2.0005f;
-                const float minlen2 = fminf(en.ux * en.ux + en.uy * en.uy, en.wx * en.wx + en.wy * en.wy);
-                const Record* r = a.rec + i;
-                tiles = 0;
-#pragma unroll
-                for (int t = 0; t < 4; t++) {
-                    const float dx = ((float)(binX0 + (t & 1) * TILE) + 8.0f) - r->cx, dy = ((float)(binY0 + (t >> 1) * TILE) + 8.0f) - r->cy;
-                    const float ddx = fmaxf(fabsf(dx) - 7.5f, 0.0f), ddy = fmaxf(fabsf(dy) - 7.5f, 0.0f);
-                    const bool reach = fabsf(en.ux * dx + en.uy * dy) <= eu && fabsf(en.wx * dx + en.wy * dy) <= ew &&
-                                       (ddx * ddx + ddy * ddy) * minlen2 <= 4.002f;
-                    if (reach) tiles |= 1u << t;
-                }
-            }
+            tiles = SKIP ? depth_tile_reach(en, a.rec + i, binX0, binY0) : 0xfu;
         }
         s_tiles[threadIdx.x] = tiles;
         __syncthreads();

@@ -72,6 +72,8 @@ export interface DeviceScene {
 }
 export type SelectMode = "centre" | "hit";
 export type SelectOp = "replace" | "add" | "subtract" | "intersect";
+export type ContribStat = "weight" | "peak" | "pixels";
+export interface Contribution { weight: BigUint64Array; peak: Float32Array; pixels: Uint32Array; frames: number }
 /** A screen region: the pixels [x0, x1) x [y0, y1), optionally one byte per pixel of the rectangle (non-zero = inside; rows
  *  `stride` >= x1 - x0 apart, default x1 - x0; row 0 is y0): a rasterised lasso or brush. */
 export interface SelectRegion { x0: number; y0: number; x1: number; y1: number; mask?: Uint8Array; stride?: number }
@@ -258,6 +260,16 @@ export class HIPRenderer {
     invertSelection(): number;
     /** ceil(vertexCount / 32) words: splat i is bit i & 31 of word i >>> 5 */
     readSelection(): Uint32Array;
+    /** Contribution: per splat of the device scene (renderers that share a scene have one set together), what it showed over the
+     *  frames of a tour.  resetContribution zeroes the accumulators (blocking); accumulateContribution enqueues the pass behind the
+     *  frame rendered last (no wait; a frame whose lists did not fit adds nothing); readContribution returns weight (sum of the
+     *  fragment weights in quanta of 2^-24), peak (the largest weight), pixels (the pixels covered, modulo 2^32) and frames (the
+     *  passes counted); selectContribution picks the splats whose value -- weight * 2^-24, peak or pixels -- is below `below` and
+     *  folds them into the selection with `op`, returning the number of selected splats.  It throws while no pass has contributed. */
+    resetContribution(): void;
+    accumulateContribution(): void;
+    readContribution(): Contribution;
+    selectContribution(options?: { stat?: ContribStat; below?: number; op?: SelectOp }): number;
     dispose(): void;
     /** RGBA8, row 0 = top, round(clamp(x,0,1)*255), premultiplied alpha */
     /** RGBA8, row 0 = top; pass an array of width*height*4 elements to have it filled and returned (no allocation per frame). */

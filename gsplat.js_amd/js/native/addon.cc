@@ -1089,6 +1089,51 @@ napi_value EraseSelected(napi_env env, napi_callback_info info)
     return rc ? throw_gsr(env, c, rc, "gsr_scene_erase_selected") : count_value(env, count);
 }
 
+// ---- contribution (gsr_contrib_reset / _accumulate_async, gsr_read_contrib, gsr_select_contrib) ----
+// readContrib(handle) -> { weight: BigUint64Array(n), peak: Float32Array(n), pixels: Uint32Array(n), frames }
+napi_value ReadContrib(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    if (!c) return nullptr;
+    uint32_t n = 0, frames = 0;
+    int rc = gsr_scene_count(c, &n);
+    if (rc) return throw_gsr(env, c, rc, "gsr_scene_count");
+    void *weight = nullptr, *peak = nullptr, *pixels = nullptr;
+    napi_value ab, out, w, p, x, f;
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, (size_t)n * 8, &weight, &ab));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_biguint64_array, n, ab, 0, &w));
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, (size_t)n * 4, &peak, &ab));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_float32_array, n, ab, 0, &p));
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, (size_t)n * 4, &pixels, &ab));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_uint32_array, n, ab, 0, &x));
+    rc = gsr_read_contrib(c, n ? (uint64_t*)weight : nullptr, n ? (float*)peak : nullptr, n ? (uint32_t*)pixels : nullptr, n, &frames);
+    if (rc) return throw_gsr(env, c, rc, "gsr_read_contrib");
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    NAPI_OK_OR_NULL(env, napi_create_uint32(env, frames, &f));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "weight", w));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "peak", p));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "pixels", x));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "frames", f));
+    return out;
+}
+
+// selectContrib(handle, stat, below, op) -> selected
+napi_value SelectContrib(napi_env env, napi_callback_info info)
+{
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    int32_t stat, op;
+    double below;
+    if (!c || !get_i32(env, argv[1], &stat) || !get_i32(env, argv[3], &op)) return nullptr;
+    if (!get_f64(env, argv[2], &below)) { napi_throw_type_error(env, nullptr, "selectContrib: below must be a number"); return nullptr; }
+    uint32_t count = 0;
+    const int rc = gsr_select_contrib(c, stat, below, op, &count);
+    return rc ? throw_gsr(env, c, rc, "gsr_select_contrib") : count_value(env, count);
+}
+
 napi_value Init(napi_env env, napi_value exports)
 {
     struct { const char* name; napi_callback fn; } fns[] = {
@@ -1109,6 +1154,8 @@ napi_value Init(napi_env env, napi_value exports)
         {"shareScene", ShareScene}, {"sceneSharing", SceneSharing},
         {"selectRegion", SelectRegion}, {"selectBox", SelectBox}, {"setSelection", SetSelection}, {"invertSelection", InvertSelection},
         {"readSelection", ReadSelection}, {"eraseSelected", EraseSelected},
+        {"contribReset", Call0<gsr_contrib_reset>}, {"contribAccumulate", Call0<gsr_contrib_accumulate_async>}, {"readContrib", ReadContrib},
+        {"selectContrib", SelectContrib},
     };
     for (auto& f : fns) {
         napi_value fn;

@@ -428,6 +428,21 @@ class HIPRenderer {
         this.setSelection = (words, op) => this._n.setSelection(this._h, words || null, code(OPS, op, "replace", "op"));
         this.invertSelection = () => this._n.invertSelection(this._h);
         this.readSelection = () => this._n.readSelection(this._h);
+        // ---- contribution (gsr_contrib_* / gsr_select_contrib): per splat of the device scene, what it showed over the frames of a tour ----
+        //   renderer.resetContribution(); for (const cam of tour) { renderer.render(scene, cam); renderer.accumulateContribution(); }
+        //   renderer.selectContribution({ stat: "pixels", below: 1 }); scene.eraseSelection(renderer.readSelection());   // what never showed
+        // weight[i] * 2^-24: the sum of splat i's fragment weights ("fully opaque pixels' worth"); peak[i]: its largest weight;
+        // pixels[i]: the pixels it covered; frames: the passes counted.  selectContribution picks the splats whose value is below
+        // `below` (f64, over all splats) and folds them into the selection; it throws while no pass has contributed.
+        const STATS = { weight: 0, peak: 1, pixels: 2 };
+        this.resetContribution = () => { this._n.contribReset(this._h); };
+        this.accumulateContribution = () => { this._n.contribAccumulate(this._h); };
+        this.readContribution = () => this._n.readContrib(this._h);
+        this.selectContribution = (options) => {
+            const o2 = options || {};
+            const below = o2.below === undefined ? 0 : Number(o2.below);
+            return this._n.selectContrib(this._h, code(STATS, o2.stat, "weight", "stat"), below, code(OPS, o2.op, "replace", "op"));
+        };
         this.stats = () => this._n.getTimings(this._h);
         this.deviceInfo = () => this._n.deviceInfo(this._h);
         this.isInitialized = () => initialized;

@@ -78,6 +78,7 @@ GSR_DEPTH_NONE, GSR_DEPTH_F32, GSR_DEPTH_U16 = 0, 1, 2
 DEPTH_DELIVERY_FORMATS = {"f32": GSR_DEPTH_F32, "u16": GSR_DEPTH_U16}
 SELECT_MODES = {"centre": 0, "hit": 1}                                     # GSR_SELECT_*
 SELECT_OPS = {"replace": 0, "add": 1, "subtract": 2, "intersect": 3}       # GSR_SELOP_*
+CONTRIB_STATS = {"weight": 0, "peak": 1, "pixels": 2}                      # GSR_CONTRIB_*
 
 
 def edge_arrays(edges):
@@ -114,6 +115,7 @@ EXPORTS = [
     "gsr_set_sh_follow", "gsr_set_sh_frame", "gsr_get_sh_frame", "gsr_read_scene_sh",
     "gsr_share_scene", "gsr_scene_sharing",
     "gsr_select_region", "gsr_select_box", "gsr_selection_set", "gsr_selection_invert", "gsr_read_selection", "gsr_scene_erase_selected",
+    "gsr_contrib_reset", "gsr_contrib_accumulate_async", "gsr_read_contrib", "gsr_select_contrib",
 ]
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p)
 GSR_COMM_ID_BYTES = 128
@@ -253,6 +255,10 @@ def load_library(path=None):
     L.gsr_selection_invert.argtypes = [vp, u32p]
     L.gsr_read_selection.argtypes = [vp, vp, ctypes.c_uint32, u32p]
     L.gsr_scene_erase_selected.argtypes = [vp, ctypes.c_int32, u32p]
+    L.gsr_contrib_reset.argtypes = [vp]
+    L.gsr_contrib_accumulate_async.argtypes = [vp]
+    L.gsr_read_contrib.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, u32p]
+    L.gsr_select_contrib.argtypes = [vp, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, u32p]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int and name not in ("gsplat_sort_host",):
@@ -855,6 +861,36 @@ class HIPRenderer:
         self._check(self._L.gsr_scene_erase_selected(self._ctx, 1 if keep else 0, ctypes.byref(n)))
         self._n = n.value
         return n.value
+
+    # -- contribution (gsr_contrib_* / gsr_read_contrib / gsr_select_contrib): per-splat weight, peak and pixel counts over views --
+    def contrib_reset(self):
+        """Zero the scene's contribution accumulators and the pass counter (allocates them on first use); blocking."""
+        self._check(self._L.gsr_contrib_reset(self._ctx))
+
+    def contrib_accumulate(self):
+        """Enqueue the contribution pass behind the frame enqueued last (no host wait): every fragment's weight w = T * B of that
+        frame is added to its splat's accumulators.  A frame whose lists did not fit adds nothing and is not counted."""
+        self._check(self._L.gsr_contrib_accumulate_async(self._ctx))
+
+    def read_contrib(self):
+        """(weight, peak, pixels, frames) accumulated since the last reset, one entry per splat.  weight (uint64): the sum over the
+        splat's fragments of rint(w * 2^24), i.e. weight * 2^-24 is "fully opaque pixels' worth"; peak (float32): the largest w;
+        pixels (uint32): the fragments (pixels the splat covered, whatever the weight; modulo 2^32); frames: the passes counted."""
+        n = self._count()
+        weight, peak, pixels = np.zeros(n, np.uint64), np.zeros(n, np.float32), np.zeros(n, np.uint32)
+        frames = ctypes.c_uint32(0)
+        self._check(self._L.gsr_read_contrib(self._ctx, weight.ctypes.data if n else None, peak.ctypes.data if n else None,
+                                             pixels.ctypes.data if n else None, n, ctypes.byref(frames)))
+        return weight, peak, pixels, frames.value
+
+    def select_contrib(self, stat="weight", below=0.0, op="replace"):
+        """Pick the splats whose accumulated value is below `below` (compared in f64 over ALL splats of the scene; one no frame
+        ever listed has value 0) and fold them into the selection; returns the selected count.  stat: "weight" (weight * 2^-24),
+        "peak" or "pixels".  Refused while no pass has contributed."""
+        count = ctypes.c_uint32(0)
+        self._check(self._L.gsr_select_contrib(self._ctx, self._select_code(CONTRIB_STATS, stat, "stat"), float(below),
+                                               self._select_code(SELECT_OPS, op, "op"), ctypes.byref(count)))
+        return count.value
 
     def read_keys(self):
         keys = np.empty(self._count(), dtype=np.uint32)

@@ -569,6 +569,53 @@ int gsr_selection_invert(gsr_ctx *ctx, uint32_t *selected);
 int gsr_read_selection(gsr_ctx *ctx, uint32_t *words, uint32_t nwords, uint32_t *selected);   /* words may be NULL: count only */
 int gsr_scene_erase_selected(gsr_ctx *ctx, int32_t keep_selected, uint32_t *new_count);
 
+/* ---- contribution ---- per-splat weight, peak and pixel counts over views
+ * No interface of the reference stands behind this section either.  Every selector above is geometric; this one answers "which
+ * splats never show" -- buried inside surfaces, hidden behind them, touching no pixel from any camera of a tour -- and with
+ * gsr_scene_erase_selected prunes a scene by rendered contribution, on the device, with no read-back of frames.
+ * Definition ("Contribution").  For the last rendered frame, a pixel's fragments, their weight B and the
+ * transmittance T are exactly those of "depth and pick": the entries of the pixel's bin list, in list order, that pass q <= 4;
+ * w = T * B, then T = T - w, in f32, with no early termination, no saturation skip and no segments.  For every splat i of the
+ * scene three accumulators are held on the device with the scene:
+ *   weight[i], uint64_t: the sum over the pixels where i is a fragment of (uint64_t)rintf(w * 16777216.0f) -- the fragment's
+ *     weight in quanta of 2^-24, ties to even; w <= 1, so one term is at most 2^24.  Integers make the sum independent of the
+ *     order in which tiles, bins, contexts and views arrive.
+ *   peak[i], float: the maximum over those pixels of w (w >= 0: taken on the bit patterns, exact and order-free).
+ *   pixels[i], uint32_t: the number of those pixels -- the fragments with q <= 4 whatever their weight.  It wraps modulo 2^32.
+ * and one word, frames: the passes that contributed since the last reset.  Only pixels of the image count (a partial last bin's
+ * other pixels have no fragments).  Accumulation continues across calls: sums add, peaks take the maximum.  A band context walks
+ * its own bin columns only; bands that partition the pixels on bin columns (multiples of 32) partition the fragments, and the
+ * host combines ranks by adding weight and pixels and taking the maximum of peak.
+ * gsr_contrib_reset allocates on first use (16 bytes per splat row plus the counter words, 8 bytes), zeroes the accumulators and
+ *   frames, and is blocking: it waits for every member's stream of a shared scene, as gsr_set_scene_sh does.
+ * gsr_contrib_accumulate_async enqueues the pass behind the last enqueued frame on the context's stream: no host wait, nothing
+ *   allocated after the first use.  It needs of the frame exactly what gsr_depth_async needs, otherwise GSR_ERR_ARG and nothing
+ *   is enqueued.  Without a prior reset the first call does what gsr_contrib_reset does first.  A frame whose lists did not fit
+ *   contributes nothing and does not bump frames (the pass reads the frame's overflow word on the device; render the pose again
+ *   after gsr_sync has regrown the lists).  The frame, the framebuffer, the statistics, the depth planes and their validity are
+ *   not touched.
+ * gsr_read_contrib is blocking: it settles the streams that may hold passes (of a shared scene: every member's), then copies the
+ *   accumulators.  Any output may be NULL.  n must equal the scene's count, else GSR_ERR_ARG; GSR_ERR_ARG also when nothing was
+ *   ever reset or accumulated.
+ * gsr_select_contrib picks P = { i in [0, n) : value_i < below }, compared in f64 on the device over ALL splats of the scene,
+ *   where value is (double)weight * 2^-24 ("fully opaque pixels' worth"), (double)peak or (double)pixels; a splat no frame ever
+ *   listed has value 0.  P is folded into the selection with `op` (GSR_SELOP_*) exactly as the selection calls fold theirs; it is
+ *   blocking, and `selected` means what it means everywhere else.  GSR_ERR_ARG, nothing changed: an unknown stat or op, a NaN
+ *   `below`, or frames == 0 -- the last refusal keeps an empty tour from selecting the whole scene.
+ * Where the state lives: with the scene, beside the selection.  The members of a shared scene have ONE set of accumulators and
+ * may run passes concurrently on their own streams: the updates are agent-scope integer atomics and commute.  gsr_scene_sharing's
+ * scene_bytes counts the buffers once they exist.  gsr_scene_translate, _rotate and _scale keep the accumulators (the indices
+ * still mean the same splats); gsr_scene_limit_box, an erase that removes something, gsr_set_scene, _arrays and _rows, and leaving
+ * a share drop them: back to "never reset".  After gsr_share_scene, ctx sees `from`'s accumulators.  A context that never calls
+ * any of this allocates nothing and launches nothing. */
+#define GSR_CONTRIB_WEIGHT 0   /* value = (double)weight * 2^-24: "fully opaque pixels' worth" */
+#define GSR_CONTRIB_PEAK   1   /* value = (double)peak */
+#define GSR_CONTRIB_PIXELS 2   /* value = (double)pixels */
+int gsr_contrib_reset(gsr_ctx *ctx);
+int gsr_contrib_accumulate_async(gsr_ctx *ctx);
+int gsr_read_contrib(gsr_ctx *ctx, uint64_t *weight, float *peak, uint32_t *pixels, uint32_t n, uint32_t *frames);
+int gsr_select_contrib(gsr_ctx *ctx, int32_t stat, double below, int32_t op, uint32_t *selected);
+
 /* ---- device interop (torch / RCCL plumbing in the harness) ---- */
 void *gsr_framebuffer_device_ptr(gsr_ctx *ctx); /* float4[h][w] on the device */
 void *gsr_stream_handle(gsr_ctx *ctx);          /* hipStream_t */

@@ -3,7 +3,7 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--share-scene]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--share-scene]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
@@ -11,6 +11,9 @@
 // ring is full) -- the header alone is enough to consume frames -- and reports its rate and the checksum of a delivered frame.
 // --deliver-format nv12|i420 (beside --deliver) opens the rings in 4:2:0 Y'CbCr instead of RGBA8 (gsr_delivery_open_ex, BT.709 limited
 // range, black background) and reports the checksum of the last frame's payload (gsr_delivery_layout gives its size).
+// --contrib adds legs in which gsr_contrib_accumulate_async is enqueued behind every frame, alternated with plain legs as --depth
+// does, then times the pass alone on sampled frames (host clock around the enqueue and the wait, the smallest of 20; beside --depth
+// the depth pass the same way) and reports `frames` and the FNV-1a of the three accumulator arrays.
 // --deliver-depth f32|u16 (beside --deliver) opens depth rings (gsr_delivery_open_depth): every delivered frame carries its hit
 // plane, at every --depth-step-th pixel (1, the default, or 2), as float or as 16-bit inverse depth against --depth-near (default
 // 0.1), and the checksum of the last frame's plane is reported (gsr_delivery_depth_layout says where it lies in the slot).
@@ -30,6 +33,7 @@
 // Build: gsplat.js_amd/csrc/Makefile (target bench_cabi), plain g++ against the header and the shared library.
 #include "../include/gsplat_hip.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -142,6 +146,7 @@ int main(int argc, char** argv)
     std::string deliver_depth = "none";
     int depth_step = 1;
     float depth_near = 0.1f;
+    bool contrib = false;
     bool depth = false, pick = false, scene_arrays = false, share_scene = false;
     std::string scene_edit = "none";
     int32_t pick_xy[2] = {0, 0};
@@ -160,11 +165,12 @@ int main(int argc, char** argv)
         else if (a == "--depth-step") depth_step = std::atoi(next());
         else if (a == "--depth-near") depth_near = (float)std::atof(next());
         else if (a == "--depth") depth = true;
+        else if (a == "--contrib") contrib = true;
         else if (a == "--scene-arrays") scene_arrays = true;
         else if (a == "--scene-edit") scene_edit = next();
         else if (a == "--share-scene") share_scene = true;
         else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--share-scene]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--share-scene]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
@@ -265,6 +271,50 @@ int main(int argc, char** argv)
             for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_sync(c)); }
             depth_sec[with] += std::chrono::duration<double>(std::chrono::steady_clock::now() - d0).count();
         }
+    }
+    // --contrib: the orbit again, three legs without and three with the contribution pass (gsr_contrib_accumulate_async) behind
+    // every frame, alternating; then the pass alone on a sampled frame of context 0 (and, with --depth, the depth pass on the same
+    // frame): the stream is drained, the pass enqueued and waited for, so the figure holds one launch's latency as well
+    double contrib_sec[2] = {0, 0}, contrib_pass_ms = 0, depth_pass_ms = 0;
+    uint32_t contrib_frames = 0;
+    unsigned long long contrib_hash[3] = {0, 0, 0};
+    if (contrib) {
+        ctx0 = ctx[0];
+        CHECK(gsr_contrib_reset(ctx[0]));
+        if (!share_scene) for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_contrib_reset(c)); }
+        for (int leg = 0; leg < 6; leg++) {
+            const bool with = leg & 1;
+            auto contrib_step = [&](int k) -> int {
+                if (int rc = step(k)) return rc;
+                return with ? gsr_contrib_accumulate_async(ctx[k % in_flight]) : 0;
+            };
+            for (int k = 0; k < warmup; k++) { ctx0 = ctx[k % in_flight]; CHECK(contrib_step(k)); }
+            for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_sync(c)); }
+            const auto d0 = std::chrono::steady_clock::now();
+            for (int k = 0; k < frames; k++) { ctx0 = ctx[(warmup + k) % in_flight]; CHECK(contrib_step(warmup + k)); }
+            for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_sync(c)); }
+            contrib_sec[with] += std::chrono::duration<double>(std::chrono::steady_clock::now() - d0).count();
+        }
+        ctx0 = ctx[0];
+        const int samples = 20;
+        for (int pass = 0; pass < (depth ? 2 : 1); pass++) {
+            double best = 1e30;
+            for (int k = 0; k < samples; k++) {
+                const Cam& p = poses[(7 * k) % 120];
+                CHECK(gsr_set_camera(ctx[0], p.view, p.proj, p.vp, (float)cfg->fx, (float)cfg->fx));
+                CHECK(gsr_render(ctx[0]));
+                const auto p0 = std::chrono::steady_clock::now();
+                CHECK(pass ? gsr_depth_async(ctx[0]) : gsr_contrib_accumulate_async(ctx[0]));
+                CHECK(gsr_sync(ctx[0]));
+                best = std::min(best, std::chrono::duration<double>(std::chrono::steady_clock::now() - p0).count() * 1e3);
+            }
+            (pass ? depth_pass_ms : contrib_pass_ms) = best;
+        }
+        std::vector<uint64_t> cw(n);
+        std::vector<float> cp(n);
+        std::vector<uint32_t> cx(n);
+        CHECK(gsr_read_contrib(ctx[0], cw.data(), cp.data(), cx.data(), n, &contrib_frames));
+        contrib_hash[0] = fnv1a(cw.data(), (size_t)n * 8); contrib_hash[1] = fnv1a(cp.data(), (size_t)n * 4); contrib_hash[2] = fnv1a(cx.data(), (size_t)n * 4);
     }
     gsr_pick_result picked{};
     if (pick) {
@@ -375,6 +425,12 @@ int main(int argc, char** argv)
         std::printf(", \"delivery_depth\": \"%s\", \"depth_step\": %d, \"depth_near\": %.9g, \"depth_width\": %d, \"depth_height\": %d, "
                     "\"depth_bytes\": %llu, \"delivered_depth_fnv1a\": \"%016llx\"",
                     deliver_depth.c_str(), dlay.step, (double)dlay.near, dlay.width, dlay.height, (unsigned long long)dlay.bytes, delivered_depth_hash);
+    if (contrib) {
+        std::printf(", \"frames_per_sec_without_contrib\": %.1f, \"frames_per_sec_with_contrib\": %.1f, \"contrib_legs\": 3, \"contrib_pass_ms\": %.4f, "
+                    "\"contrib_frames\": %u, \"contrib_weight_fnv1a\": \"%016llx\", \"contrib_peak_fnv1a\": \"%016llx\", \"contrib_pixels_fnv1a\": \"%016llx\"",
+                    3.0 * frames / contrib_sec[0], 3.0 * frames / contrib_sec[1], contrib_pass_ms, contrib_frames, contrib_hash[0], contrib_hash[1], contrib_hash[2]);
+        if (depth) std::printf(", \"depth_pass_ms\": %.4f", depth_pass_ms);
+    }
     if (depth)
         std::printf(", \"frames_per_sec_plain\": %.1f, \"frames_per_sec_with_depth\": %.1f, \"depth_legs\": 3",
                     3.0 * frames / depth_sec[0], 3.0 * frames / depth_sec[1]);
