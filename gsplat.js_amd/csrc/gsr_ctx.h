@@ -59,7 +59,9 @@ struct FrameState {  // small per-frame device words; initialised once (k_begin_
     uint32_t queue;   // compositor work-item counter
     uint64_t visible;
     uint64_t tile_entries;
-    uint64_t report[6];  // written by k_bin_finalize for the host: running sums accum[0..4], this frame's bin entries
+    uint64_t report[12]; // written by k_bin_finalize for the host: running sums accum[0..4], this frame's bin entries, and [6..11] what the
+                         // step saw and decided (gsr_debug_read_frame_figures): optical depth and raw optical mass sums of the frame slots,
+                         // list entries, the longest list, long_from, and dense | heavy << 1 | by_size << 2 | fits << 3
     uint32_t digit_total[RADIX_LO_BINS + RADIX_HI_BINS];
     uint32_t sorted_count;  // entries of depth_index: n, or the band's survivors (SortBuffers::count)
     uint32_t seg_len;       // the frame's compositor segment length (k_bin_finalize -> k_blend)

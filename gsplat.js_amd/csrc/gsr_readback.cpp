@@ -149,6 +149,49 @@ int gsr_read_bin_lists(gsr_ctx* c, uint32_t* starts, uint32_t* list, uint64_t li
     return GSR_OK;
 }
 
+// The work list k_bin_finalize published for the last render frame, for tests (tests/test_gpu_work_items.py compares it with
+// tests/work_items_reference.py): items[0 .. n_items) as four words each and seg_start[0 .. bins].  Returns n_items; GSR_ERR_ARG
+// where the frame cannot be walked (depth_frame_check) or a buffer is too small.  A frame whose lists did not fit is NOT
+// rendered again: the caller sees its n_items == 0, as the compositor did.  Not part of the ABI.
+int gsr_debug_read_work_list(gsr_ctx* c, uint32_t* items, uint64_t item_words, uint32_t* seg_start, uint64_t seg_words)
+{
+    if (!c || !items || !seg_start) return c ? fail(c, GSR_ERR_ARG, "gsr_debug_read_work_list: a buffer is NULL") : GSR_ERR_ARG;
+    if (int r = depth_frame_check(c, "gsr_debug_read_work_list")) return r;
+    const BinGrid g = make_grid(c);
+    const size_t nbins = (size_t)(g.bx_hi - g.bx_lo) * g.nby;
+    if (seg_words < nbins + 1) return fail(c, GSR_ERR_ARG, "gsr_debug_read_work_list: seg_start needs %zu words", nbins + 1);
+    HIP_TRY(c, hipSetDevice(c->device));
+    uint32_t n_items = 0;
+    HIP_TRY(c, hipMemcpyAsync(&n_items, &c->words.fstate->n_items, 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(seg_start, c->bin.seg_start, (nbins + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (n_items > c->bin.blend.max_items || (uint64_t)n_items * 4 > item_words)
+        return fail(c, GSR_ERR_ARG, "gsr_debug_read_work_list: the frame has %u work items", n_items);
+    if (n_items) {
+        HIP_TRY(c, hipMemcpyAsync(items, c->bin.items, (size_t)n_items * 16, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return (int)n_items;
+}
+
+// What the finalize step of the last render frame saw and decided (FrameState::report[6..11], with the frame's visible splats
+// and tile overlaps in front): out[8] = V, D, optical depth sum, raw optical mass sum, list entries, longest list, long_from,
+// dense | heavy << 1 | by_size << 2 | fits << 3.  The same checks, and no repair, as gsr_debug_read_work_list.  Not part of the ABI.
+int gsr_debug_read_frame_figures(gsr_ctx* c, uint64_t* out)
+{
+    if (!c || !out) return c ? fail(c, GSR_ERR_ARG, "gsr_debug_read_frame_figures: out is NULL") : GSR_ERR_ARG;
+    if (int r = depth_frame_check(c, "gsr_debug_read_frame_figures")) return r;
+    HIP_TRY(c, hipSetDevice(c->device));
+    static_assert(offsetof(FrameState, tile_entries) == offsetof(FrameState, visible) + 8 && offsetof(FrameState, report) == offsetof(FrameState, visible) + 16,
+                  "visible, tile_entries and report are read through one pointer");
+    uint64_t w[2 + 12];
+    HIP_TRY(c, hipMemcpyAsync(w, &c->words.fstate->visible, sizeof w, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    out[0] = w[0]; out[1] = w[1];
+    for (int k = 0; k < 6; k++) out[2 + k] = w[2 + 6 + k];
+    return GSR_OK;
+}
+
 int gsr_convert_rgba8_async(gsr_ctx* c)
 {
     if (!c) return GSR_ERR_ARG;

@@ -213,7 +213,7 @@ __device__ __forceinline__ UN<N> block_exclusive_scan(UN<N> x, uint32_t (*s_w)[F
 constexpr uint32_t SEG_LEN_MAX = 8192;
 
 // Size class of a bin's last (partial) segment of r entries -- with long work items: of the whole bin -- for the order of
-// the work items: 4 classes per power of two (r < 65536 -> 0 .. 63), larger = heavier.  The compositor draws the items of
+// the work items: 4 classes per power of two (r < 7 << 14 -> 0 .. 62, 63 from there on), larger = heavier.  The compositor draws the items of
 // the heaviest class first.  (With several frames in flight the tail of one frame's compositor is filled by the other
 // frames' kernels, and a tail made only of the lightest items was measured 2.5 % slower: then `by_size` is off and the
 // bins' last segments stay in raster order.)
@@ -320,12 +320,12 @@ __device__ __forceinline__ void bin_finalize_body(const FinalizeArgs& fa, uint32
     // pays for; one frame at a time only).  long_policy 1 / 0 pin all / no bins.
     constexpr uint32_t LONG_TAU_B_LO = 8, LONG_TAU_B_HI = 60;
     uint32_t long_from = 0xffffffffu;                       // bins of at least this many entries are one work item
+    const bool heavy = mass >= (uint64_t)fa.long_mass_min * ent_tot.v[0];
     if (!is_whole_bin(seg_len_min)) {
         if (fa.long_policy > 0) long_from = 0u;
         else if (fa.long_policy < 0 && mass > 0u) {
             const uint64_t E = ent_tot.v[0];
             const uint32_t tb = fa.long_tau_bin ? fa.long_tau_bin : dense ? LONG_TAU_B_LO : LONG_TAU_B_HI;
-            const bool heavy = mass >= (uint64_t)fa.long_mass_min * E;
             if (dense || heavy || fa.long_tau_bin)
                 long_from = (uint32_t)min((uint64_t)0xfffffff0u, ((uint64_t)tb * 1024u * E + mass - 1u) / mass);
         }
@@ -445,6 +445,9 @@ __device__ __forceinline__ void bin_finalize_body(const FinalizeArgs& fa, uint32
 #pragma unroll
         for (int k = 0; k < 5; k++) report[k] = accum[k];   // what the host reads at the next synchronisation: one copy
         report[5] = fits ? tot.v[0] : 0u;
+        // what this step saw and decided, for gsr_debug_read_frame_figures (the slots are reset above: nothing else keeps the sums)
+        report[6] = optical; report[7] = s_slot[1]; report[8] = ent_tot.v[0]; report[9] = mxbin; report[10] = long_from;
+        report[11] = (dense ? 1u : 0u) | (heavy ? 2u : 0u) | (by_size ? 4u : 0u) | (fits ? 8u : 0u);
     }
 }
 

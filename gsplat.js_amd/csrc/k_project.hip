@@ -340,7 +340,9 @@ __global__ __launch_bounds__(PROJ_THREADS) void k_project_key(SceneSoA sc, uint3
                 // opacity x tiles, /16 so that a slot's sum stays inside 32 bits (<= 255 * 4096 / 16 per splat): the frame's
                 // optical depth in the unit k_bin_finalize compares (FinalizeArgs::long_tau)
                 otiles += (op8 * min(nt, 4096u)) >> 4;
-                omass += (op8 * (uint32_t)area) >> 8;   // (<= 65280 per splat: a slot's sum stays inside 32 bits)
+                // (<= 65279 per splat, summed in 32 bits per slot: a slot wraps from 2^32 / 65279 = 65 794 splats of the largest footprint and
+                // full opacity on, the 64 slots together from about 4.2 M such splats; nothing detects it -- DESIGN.md section 5.9)
+                omass += (op8 * (uint32_t)area) >> 8;
             }
         }
     }

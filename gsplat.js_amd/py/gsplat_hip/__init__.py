@@ -942,6 +942,32 @@ class HIPRenderer:
         self._check(self._L.gsr_read_work_items(self._ctx, out.ctypes.data))
         return {"seg_len": int(out[0]), "items": int(out[1]), "speculative": bool(out[2]), "waves_per_tile": int(out[3]), "bins": int(out[4])}
 
+    def work_list(self, max_items):
+        """The last frame's compositor work list as k_bin_finalize published it (a test read-back, not part of the ABI):
+        (items [n_items, 4] -- bin | segment << 16, first entry, end, the bin's first partial slot | its segments << 25 --,
+        seg_start [bins + 1]).  `max_items`: the most items to expect (the compositor plan's max_items).  A frame whose lists
+        did not fit is not rendered again: it has no items."""
+        fn = self._L.gsr_debug_read_work_list
+        fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64]
+        items = np.zeros((max(int(max_items), 1), 4), dtype=np.uint32)
+        seg_start = np.zeros(self.work_items()["bins"] + 1, dtype=np.uint32)
+        n = fn(self._ctx, items.ctypes.data, items.size, seg_start.ctypes.data, seg_start.size)
+        if n < 0:
+            self._check(n)
+        return items[:n].copy(), seg_start
+
+    def frame_figures(self):
+        """What the finalize step of the last frame saw and decided (a test read-back, not part of the ABI): the projection's
+        four sums (visible splats, 16x16 tile overlaps, optical depth over the boxes, raw optical mass), the list entries, the
+        longest list, the entries from which a bin is one work item, and the decisions."""
+        fn = self._L.gsr_debug_read_frame_figures
+        fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]
+        w = np.zeros(8, dtype=np.uint64)
+        self._check(fn(self._ctx, w.ctypes.data))
+        out = {k: int(w[i]) for i, k in enumerate(("visible", "tiles", "otiles", "omass", "entries", "mxbin", "long_from"))}
+        out.update({k: bool(int(w[7]) >> i & 1) for i, k in enumerate(("dense", "heavy", "by_size", "fits"))})
+        return out
+
     def set_timing_interval(self, every):
         """Record stage events only on every `every`-th frame (they cost command-processor time on short frames)."""
         self._check(self._L.gsr_set_timing_interval(self._ctx, every))

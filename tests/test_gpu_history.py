@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import history_trace as ht
+import work_items_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -91,6 +92,10 @@ def observe(r, state, points=None):
     starts, lst = r.bin_lists()
     o["bin starts"], o["bin list entries"] = starts, lst
     o["work_items()"] = r.work_items()
+    # the work list itself: the order inside a size class is the atomics' (k_bin_finalize), everything else is the frame's
+    items, seg_start = r.work_list(max(o["work_items()"]["items"], 1))
+    o["work list (items sorted inside their class)"], o["seg_start"] = work_items_reference.canonical(items), seg_start
+    o["frame figures"] = tuple(sorted(r.frame_figures().items()))
     rec, bbox = r.read_records()
     o["pixel boxes"] = bbox
     # (a record is defined for the splats the projection draws: k_project_key writes nothing for a culled splat, and nothing reads it)
