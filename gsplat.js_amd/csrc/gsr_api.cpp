@@ -49,6 +49,7 @@ Knobs read_knobs(std::string& bad)
         else bad = std::string("GSR_FRONT_WAVES must be ") + std::to_string(FRONT_WAVES_NARROW) + " or " + std::to_string(FRONT_WAVES_WIDE) + ", not \"" + e + "\"";
     }
     if (const char* e = getenv("GSR_DEPTH_SKIP")) k.depth_skip = atoi(e) != 0;
+    if (const char* e = getenv("GSR_OVERLAY_TRIM")) k.overlay_trim = atoi(e) != 0;
     return k;
 }
 
@@ -253,6 +254,7 @@ int gsr_sync(gsr_ctx* c)
     if (!c) return GSR_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     if (int r = sync_and_repair(c)) return r;
+    c->overlay.in_flight = false;   // (the render stream is idle: no overlay pass of this context reads the selection any more)
     if (c->comm.stream) HIP_TRY(c, hipStreamSynchronize(c->comm.stream));                 // the frame exchange, if one is in flight
     if (c->delivery.copy_stream) HIP_TRY(c, hipStreamSynchronize(c->delivery.copy_stream));   // frame deliveries in flight
     if (c->words.dropped_unreported) {

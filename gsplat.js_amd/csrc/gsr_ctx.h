@@ -94,6 +94,7 @@ struct Knobs {
     uint32_t sort_kpb = 0;       // GSR_SORT_KPB: keys per radix workgroup, 2048, 4096 or 8192 (0: by the scene's size)
     uint32_t front_waves = 0;    // GSR_FRONT_WAVES=8|16: waves per workgroup of the heavy front-end kernels (0: by the kind of context)
     bool depth_skip = true;      // GSR_DEPTH_SKIP=0: the depth pass visits every entry in every tile (no skip of entries that cannot reach a tile)
+    bool overlay_trim = true;    // GSR_OVERLAY_TRIM=0: the overlay pass walks every list to its end (no stop behind the last selected entry)
 };
 
 // The scene's per-splat arrays: everything the on-device build, the transforms and the compaction move together.
@@ -164,6 +165,9 @@ struct SharedScene {
         void reset() { mask.reset(); scratch.reset(); counters.reset(); region.reset(); words = counter_words = 0; region_bytes = 0; count = 0; }
         uint64_t bytes() const { return (uint64_t)words * 8 + (uint64_t)counter_words * 4 + region_bytes; }
     } sel;
+    // Moves with every call that changes the selection's bits (the folds of gsr_select.cpp) or drops them (a new scene, a compaction):
+    // a member's overlay image (gsr_overlay.cpp) is the selection's while the version it was enqueued for is this one.
+    uint64_t sel_version = 1;
     // The contribution accumulators (gsr_contrib.cpp; DESIGN.md section 4, "Contribution"): per splat of THIS copy, so the members
     // have one set together and their passes add into it with atomics that commute.  Nothing is allocated until the first reset or
     // pass; without buffers the state is "never reset".  Dropped wherever the selection is emptied: the indices are the old numbering's.
@@ -411,6 +415,22 @@ struct gsr_ctx {
         uint64_t planes_serial = 0;         // frame_serial of the frame the planes were enqueued behind (0: none, or hit_alpha changed)
     } depth;
 
+    // selection overlay (gsr_overlay.cpp); nothing is allocated until gsr_set_overlay supplies options
+    struct Overlay {
+        bool on = false;                    // options are set
+        float tint[3] = {0.0f, 0.0f, 0.0f}, mix = 0.0f;
+        gsr::DevBuf<float4> image;          // W x H in front of `pixels` allocated (they only grow): the frame with the selected splats tinted
+        gsr::DevBuf<float> cover;           // likewise: the selected splats' share of the pixel's alpha
+        gsr::DevBuf<uint32_t> image8;       // gsr_read_overlay_rgba8's conversion of `image`, allocated by its first call
+        gsr::DevBuf<uint32_t> invalid;      // one word, stored by every pass: 1 = it refused a frame whose lists did not fit and wrote nothing
+        size_t pixels = 0;
+        // what the image was enqueued for: the frame (frame_serial; 0: nothing), the scene's sel_version, the options (a count of the
+        // gsr_set_overlay calls that changed them)
+        uint64_t serial = 0, sel_version = 0, opt_version = 0, image_opt_version = 0;
+        bool in_flight = false;             // a pass has been enqueued since the last gsr_sync: calls that change the mask wait for this stream first
+        void reset() { on = false; image.reset(); cover.reset(); image8.reset(); invalid.reset(); pixels = 0; serial = 0; }
+    } overlay;
+
     // frame delivery (gsr_delivery_open): a ring of pinned host blocks, each with its device staging and "copy done" event
     struct Delivery {
         struct Slot {
@@ -434,6 +454,7 @@ struct gsr_ctx {
             gsr::DepthSpec spec;            // off: a ring as it was before depth rings existed, nothing below is allocated
             gsr::DepthPlanes planes;        // allocated with the ring: the pass writes hit, k_deliver_depth reads it; reused by every delivery (in-order on the render stream)
         } depth;
+        bool overlay = false;               // gsr_delivery_set_overlay: the conversion reads the overlay image in place of the framebuffer
         // a slot's layout: the frame's payload in the ring's format; in a depth ring the plane behind it at the next multiple of 16; the
         // trailer behind the plane at the next multiple of 16 (without depth: behind the payload at the next whole word)
         size_t pixel_bytes() const { return format == GSR_FORMAT_RGBA8 ? (size_t)W * H * 4 : gsr::yuv420_bytes(W, H); }
@@ -506,6 +527,13 @@ int depth_settle_frame(gsr_ctx* c, const char* who);
 // gsr_read_depth up to its copies: the context's planes are the settled frame's (the pass is run if they are not) and final on the
 // device; GSR_ERR_OVERFLOW for planes a pass marked invalid
 int depth_planes_current(gsr_ctx* c, const char* who);
+// gsr_overlay.cpp: the overlay image is the last enqueued frame's, the selection's and the options' -- the pass is enqueued behind the
+// frame on the render stream if it is not (launch errors are left for the caller's hipGetLastError); the caller has run
+// depth_frame_check and knows that options are set
+int overlay_enqueue(gsr_ctx* c);
+// what every call that changes the selection's bits does first: waits for the members' streams that may hold an overlay pass, and
+// moves the scene's sel_version
+int overlay_before_selection_change(gsr_ctx* c);
 // gsr_delivery.cpp
 int delivery_alloc(gsr_ctx* c, int slots);
 // what gsr_delivery_open_depth demands of depth options other than GSR_DEPTH_NONE (GSR_ERR_ARG, `who` in front of the message)

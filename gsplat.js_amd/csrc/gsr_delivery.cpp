@@ -126,6 +126,7 @@ int gsr_delivery_open(gsr_ctx* c, int32_t slots)
     HIP_TRY(c, hipSetDevice(c->device));
     c->delivery.format = GSR_FORMAT_RGBA8;
     c->delivery.depth.spec = {};
+    c->delivery.overlay = false;
     return delivery_alloc(c, slots);
 }
 
@@ -149,6 +150,7 @@ static int delivery_open_options(gsr_ctx* c, const char* who, const gsr_delivery
     c->delivery.format = opt->format;
     c->delivery.yuv = yuv_params(opt->full_range != 0, opt->background);
     c->delivery.depth.spec = spec;
+    c->delivery.overlay = false;
     return delivery_alloc(c, opt->slots);
 }
 
@@ -208,6 +210,18 @@ int gsr_delivery_close(gsr_ctx* c)
     HIP_TRY(c, hipSetDevice(c->device));
     delivery_free(c);
     c->delivery.depth.spec = {};
+    c->delivery.overlay = false;
+    return GSR_OK;
+}
+
+int gsr_delivery_set_overlay(gsr_ctx* c, int32_t on)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (c->delivery.ring.empty()) return fail(c, GSR_ERR_ARG, "gsr_delivery_set_overlay: no delivery ring (gsr_delivery_open)");
+    if (on && c->comm.joined())
+        return fail(c, GSR_ERR_ARG, "gsr_delivery_set_overlay: this context is in a group: the gathered frame is RGBA8 of other ranks, which the overlay cannot tint");
+    if (on && !c->overlay.on) return fail(c, GSR_ERR_ARG, "gsr_delivery_set_overlay: no overlay options (gsr_set_overlay first)");
+    c->delivery.overlay = on != 0;
     return GSR_OK;
 }
 
@@ -226,11 +240,19 @@ int gsr_deliver_frame_async(gsr_ctx* c, uint64_t* serial)
         if (dl.depth.planes.Wd != c->comm.depth.planes.Wd || dl.depth.planes.Hd != c->comm.depth.planes.Hd)
             return fail(c, GSR_ERR_ARG, "gsr_deliver_frame_async: the size changed since gsr_comm_set_depth: join the group again");
     }
+    if (dl.overlay && group)   // (likewise refused before anything else is looked at)
+        return fail(c, GSR_ERR_ARG, "gsr_deliver_frame_async: this context joined a group after gsr_delivery_set_overlay: the gathered frame is RGBA8 of "
+                                    "other ranks, which the overlay cannot tint (gsr_delivery_set_overlay(ctx, 0))");
     if (group ? !c->comm.frame8_valid : !c->have_frame)
         return fail(c, GSR_ERR_ARG, group ? "gsr_deliver_frame_async: no gathered frame yet (gsr_allgather_frame_async)" : "gsr_deliver_frame_async: nothing rendered yet");
     // a depth ring needs what gsr_depth_async needs of the frame; refused before a slot is looked for: nothing enqueued, no slot taken
     // (in a group the pass ran with the exchange: gsr_allgather_frame_async has asked the same of the frame it gathered)
     if (depth && !group) { if (int r = depth_frame_check(c, "gsr_deliver_frame_async (depth ring)")) return r; }
+    // an overlay ring likewise, and it needs options
+    if (dl.overlay) {
+        if (!c->overlay.on) return fail(c, GSR_ERR_ARG, "gsr_deliver_frame_async: the ring delivers the overlay, but the options are off (gsr_set_overlay)");
+        if (int r = depth_frame_check(c, "gsr_deliver_frame_async (overlay ring)")) return r;
+    }
     DeliverySlot* sl = nullptr;
     const int slots = (int)dl.ring.size();
     for (int k = 0; k < slots && !sl; k++) {
@@ -246,7 +268,10 @@ int gsr_deliver_frame_async(gsr_ctx* c, uint64_t* serial)
     // and records before the next frame's chain, which follows there, overwrites them), the copy on the copy stream behind ev_staged.
     // A group's gathered frame: frame8 and the word behind it (one bit per rank whose band is stale), as the de-slab steps left them
     // on the exchange stream; work and copy both go there, in front of the next frame's de-slab.
-    const float4* fb = group ? nullptr : c->out.fb.p;
+    // An overlay ring: the overlay pass behind the frame on the render stream, and its image in place of the framebuffer.  One image
+    // per context suffices for the reason one framebuffer does: the conversion reads it on the render stream in front of the next pass.
+    if (dl.overlay) { if (int r = overlay_enqueue(c)) return r; }
+    const float4* fb = group ? nullptr : dl.overlay ? c->overlay.image.p : c->out.fb.p;
     const uint32_t* frame8 = group ? c->comm.frame8.p : nullptr;
     const uint32_t* flag = group ? frame8 + (size_t)c->W * c->H : &c->words.fstate->overflow;
     const hipStream_t work = group ? c->comm.stream : c->stream, copy = group ? c->comm.stream : dl.copy_stream;

@@ -493,6 +493,29 @@ void launch_contrib(const ContribBuffers& b, const BinGrid& g, const CamParams& 
 void launch_contrib_select(int stat, double below, uint32_t n, const unsigned long long* weight, const uint32_t* peak, const uint32_t* pixels,
                            uint32_t* scratch, uint32_t nwords, hipStream_t s);
 
+// Selection overlay (k_overlay.hip; DESIGN.md section 4, "Selection overlay"): the last frame's bin lists walked once more, the
+// weight w = T * B of every fragment of a SELECTED splat summed per pixel (cover) and, with the splat's colour, turned into the
+// frame with those splats tinted (overlay).  Reads the framebuffer, never writes it.
+struct OverlayBuffers {
+    const uint32_t* bin_start;   // nbins + 1      (the frame's lists, records and positions, as DepthBuffers holds them)
+    const uint32_t* list;
+    const Record* rec;
+    const float *px, *py, *pz;
+    const float4* shcol;         // this frame's evaluated SH colours (null without SH)
+    const uint32_t* sel;         // the selection words (null: a scene never selected in, the empty selection)
+    const uint32_t* overflow;    // the frame's overflow word: non-zero = its lists did not fit, nothing of it may be walked
+    uint32_t* invalid;           // out: 1 when the pass refused the frame (nothing written), 0 otherwise
+    const float4* fb;            // the frame's framebuffer, W x H
+    float4* overlay;             // out, W x H
+    float* cover;                // out, W x H
+    uint32_t capacity;           // entries the list can hold
+    uint32_t nsplats, nwords;    // splats of the scene, words `sel` holds
+    float tint[3], mix;
+};
+// skip: entries that cannot reach a tile are left out (GSR_DEPTH_SKIP); trim: the walk ends behind the list's last selected entry
+// (GSR_OVERLAY_TRIM); the same bits in all four forms
+void launch_overlay(const OverlayBuffers& b, const BinGrid& g, const CamParams& cam, bool skip, bool trim, hipStream_t s);
+
 // multi-GPU exchange helpers (RGBA8 slabs of the all-gather)
 constexpr int MAX_SLABS = 16;
 struct SlabEdges { int32_t x0[MAX_SLABS], x1[MAX_SLABS]; };

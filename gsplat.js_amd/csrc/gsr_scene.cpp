@@ -88,6 +88,7 @@ int gsr::alloc_scene(gsr_ctx* c, uint32_t n, bool with_rows)
     if (c->words.mailbox) reinterpret_cast<volatile uint32_t*>(c->words.mailbox)[2] = 0xffffffffu;   // a new scene: LSD order until a frame reports
     sc.drop_sh();
     sc.sel.reset();   // a new scene: the empty selection
+    sc.sel_version++;   // (and every member's overlay image is stale)
     sc.contrib.reset();   // and no contribution: "never reset"
     c->shcol.reset();
     int r;
@@ -214,6 +215,7 @@ int gsr::scene_compact(gsr_ctx* c, const ScenePred& p, const char* what, uint32_
         sc.arr_rows = n;   // (what `dst` was allocated for)
         sc.n = kept;   // arrays keep their old capacity; per-frame buffers sized for the old count still fit
         sc.sel.reset();   // the selection's bits are indices of the old numbering: the scene is left with the empty one (nothing is in flight)
+        sc.sel_version++;   // (and every member's overlay image is stale)
         sc.contrib.reset();   // the contribution accumulators likewise
         c->scene_gen = ++sc.generation;   // (this context follows below; the other members in adopt_scene, before their next frame)
         // The compaction renumbers the splats, so SH rows (indexed by splat - (bandsIndices[0] + 1)) and the band

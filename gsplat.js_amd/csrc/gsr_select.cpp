@@ -35,6 +35,7 @@ int gsr::select_ensure(gsr_ctx* c)
 int gsr::select_fold_and_count(gsr_ctx* c, int op, uint32_t* selected)
 {
     SharedScene::Selection& sel = c->scene->sel;
+    if (int r = overlay_before_selection_change(c)) return r;   // the members' overlay passes in flight read the mask as it was
     launch_select_apply(op, sel.mask, sel.scratch, c->scene->n, sel.words, sel.counters + 2, sel.counters, c->stream);
     uint32_t count = 0;
     hipError_t e1 = hipMemcpyAsync(&count, sel.counters, 4, hipMemcpyDeviceToHost, c->stream);

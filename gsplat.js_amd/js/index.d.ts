@@ -162,6 +162,8 @@ export interface DeliveryOptions {
     background?: [number, number, number];
     /** a depth plane beside every frame, for a client that reprojects between server frames (not in a group) */
     depth?: DepthDeliveryOptions;
+    /** deliver the selection overlay (setSelectionOverlay first) in place of the frame; default false (not in a group) */
+    overlay?: boolean;
 }
 export type DepthDeliveryFormat = "f32" | "u16";
 export interface DepthDeliveryOptions {
@@ -273,6 +275,14 @@ export class HIPRenderer {
     dispose(): void;
     /** RGBA8, row 0 = top, round(clamp(x,0,1)*255), premultiplied alpha */
     /** RGBA8, row 0 = top; pass an array of width*height*4 elements to have it filled and returned (no allocation per frame). */
+    /** Selection overlay: the frame rendered last with the selected splats drawn in lerp(colour, tint, mix) (tint [r, g, b] as
+     *  the framebuffer's channels, mix in [0, 1]; null: off, the buffers are freed).  readOverlay returns the image (premultiplied
+     *  RGBA float32, width * height * 4) and cover (width * height: the share of the pixel's alpha that selected splats supply);
+     *  readPixels({ overlay: true }) returns the image as RGBA8, and openDelivery(n, { overlay: true }) delivers it in place of
+     *  the frame.  Refused in a group. */
+    setSelectionOverlay(options: { tint?: [number, number, number]; mix?: number } | null): void;
+    readOverlay(): { rgba: Float32Array; cover: Float32Array };
+    readPixels(options: { overlay?: boolean; out?: Uint8Array }): Uint8Array;
     readPixels(out?: Uint8Array): Uint8Array;
     readPixelsFloat(out?: Float32Array): Float32Array;
     /** Depth planes of the last rendered frame, width*height each, row 0 = top; pass arrays to have them filled (like

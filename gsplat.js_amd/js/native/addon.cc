@@ -1134,6 +1134,75 @@ napi_value SelectContrib(napi_env env, napi_callback_info info)
     return rc ? throw_gsr(env, c, rc, "gsr_select_contrib") : count_value(env, count);
 }
 
+// ---- selection overlay (gsr_set_overlay / gsr_overlay_async / gsr_read_overlay* / gsr_delivery_set_overlay) ----
+// setOverlay(handle, on, r, g, b, mix): on = 0 switches the overlay off (the other arguments are not read)
+napi_value SetOverlay(napi_env env, napi_callback_info info)
+{
+    napi_value argv[6];
+    if (!get_args(env, info, 6, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    int32_t on;
+    if (!c || !get_i32(env, argv[1], &on)) return nullptr;
+    if (!on) { const int rc = gsr_set_overlay(c, nullptr); return rc ? throw_gsr(env, c, rc, "gsr_set_overlay") : undefined(env); }
+    double v[4];
+    for (int k = 0; k < 4; k++)
+        if (!get_f64(env, argv[2 + k], &v[k])) { napi_throw_type_error(env, nullptr, "setOverlay(handle, on, r, g, b, mix): numbers"); return nullptr; }
+    gsr_overlay_options o{};
+    o.tint[0] = (float)v[0]; o.tint[1] = (float)v[1]; o.tint[2] = (float)v[2]; o.mix = (float)v[3];
+    const int rc = gsr_set_overlay(c, &o);
+    return rc ? throw_gsr(env, c, rc, "gsr_set_overlay") : undefined(env);
+}
+
+// readOverlay(handle, width, height) -> { rgba: Float32Array(w * h * 4), cover: Float32Array(w * h) }
+napi_value ReadOverlay(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    int32_t w, h;
+    if (!c || !get_i32(env, argv[1], &w) || !get_i32(env, argv[2], &h)) return nullptr;
+    const size_t np = (size_t)w * h;
+    void *rgba = nullptr, *cover = nullptr;
+    napi_value ab, out, a, b;
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, np * 16, &rgba, &ab));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_float32_array, np * 4, ab, 0, &a));
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, np * 4, &cover, &ab));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_float32_array, np, ab, 0, &b));
+    const int rc = gsr_read_overlay(c, (float*)rgba, (float*)cover);
+    if (rc) return throw_gsr(env, c, rc, "gsr_read_overlay");
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "rgba", a));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "cover", b));
+    return out;
+}
+
+// readOverlayPixels(handle, out, width, height): out is a Uint8Array of width * height * 4 (the overlay as RGBA8)
+napi_value ReadOverlayPixels(napi_env env, napi_callback_info info)
+{
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    void* out;
+    size_t len;
+    int32_t w, h;
+    if (!c || !get_typed(env, argv[1], napi_uint8_array, &out, &len) || !get_i32(env, argv[2], &w) || !get_i32(env, argv[3], &h)) return nullptr;
+    if (len < (size_t)w * h * 4) { napi_throw_range_error(env, nullptr, "output array is smaller than width*height*4"); return nullptr; }
+    const int rc = gsr_read_overlay_rgba8(c, (uint8_t*)out);
+    return rc ? throw_gsr(env, c, rc, "gsr_read_overlay_rgba8") : undefined(env);
+}
+
+// deliverySetOverlay(handle, on)
+napi_value DeliverySetOverlay(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    int32_t on;
+    if (!c || !get_i32(env, argv[1], &on)) return nullptr;
+    const int rc = gsr_delivery_set_overlay(c, on);
+    return rc ? throw_gsr(env, c, rc, "gsr_delivery_set_overlay") : undefined(env);
+}
+
 napi_value Init(napi_env env, napi_value exports)
 {
     struct { const char* name; napi_callback fn; } fns[] = {
@@ -1156,6 +1225,8 @@ napi_value Init(napi_env env, napi_value exports)
         {"readSelection", ReadSelection}, {"eraseSelected", EraseSelected},
         {"contribReset", Call0<gsr_contrib_reset>}, {"contribAccumulate", Call0<gsr_contrib_accumulate_async>}, {"readContrib", ReadContrib},
         {"selectContrib", SelectContrib},
+        {"setOverlay", SetOverlay}, {"readOverlay", ReadOverlay}, {"readOverlayPixels", ReadOverlayPixels},
+        {"deliverySetOverlay", DeliverySetOverlay},
     };
     for (auto& f : fns) {
         napi_value fn;

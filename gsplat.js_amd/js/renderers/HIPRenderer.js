@@ -188,6 +188,7 @@ class HIPRenderer {
                 const buffers = this._n.openDeliveryEx(this._h, n, format, o.fullRange ? 1 : 0, bg[0] | 0, bg[1] | 0, bg[2] | 0);
                 wrapSlots(buffers);
             }
+            if (o.overlay) this._n.deliverySetOverlay(this._h, 1);   // the ring delivers the selection overlay (setSelectionOverlay first)
         };
         this.closeDelivery = () => {
             refuseWhileHeld("closeDelivery");
@@ -370,7 +371,14 @@ class HIPRenderer {
         // array (width*height*4 elements) and gets it back filled; without one a fresh array is allocated per call, which
         // costs more than the copy itself (8 MB of zeroed pages at 1080p: 583 -> frames/s with a reused array in
         // tools/bench_node.js).
+        // readPixels({ overlay: true, out? }): the selection overlay (setSelectionOverlay) as RGBA8 instead of the frame.
         this.readPixels = (out) => {
+            if (out && !ArrayBuffer.isView(out) && out.overlay) {
+                const o = out.out || new Uint8Array(this.width * this.height * 4);
+                this._n.readOverlayPixels(this._h, o, this.width, this.height);
+                return o;
+            }
+            if (out && !ArrayBuffer.isView(out)) out = out.out;
             const a = out || new Uint8Array(this.width * this.height * 4);
             if (group) this._n.readFrame(this._h, a, this.width, this.height);   // the gathered frame of all ranks
             else this._n.readPixels(this._h, a, this.width, this.height);
@@ -443,6 +451,18 @@ class HIPRenderer {
             const below = o2.below === undefined ? 0 : Number(o2.below);
             return this._n.selectContrib(this._h, code(STATS, o2.stat, "weight", "stat"), below, code(OPS, o2.op, "replace", "op"));
         };
+        // ---- selection overlay (gsr_set_overlay / gsr_read_overlay*): the last frame with the selected splats tinted ----
+        //   renderer.setSelectionOverlay({ tint: [1, 0.5, 0], mix: 0.5 }); renderer.render(scene, cam);
+        //   const { rgba, cover } = renderer.readOverlay();   // or readPixels({ overlay: true }), or openDelivery(n, { overlay: true })
+        // Selected splats are drawn with lerp(colour, tint, mix); cover[p] is the share of pixel p's alpha they supply (outlines are
+        // drawn from it).  null switches it off and frees its buffers.
+        this.setSelectionOverlay = (options) => {
+            if (options === null || options === undefined) { this._n.setOverlay(this._h, 0, 0, 0, 0, 0); return; }
+            const t = options.tint === undefined ? [1, 0.5, 0] : options.tint, mix = options.mix === undefined ? 0.5 : options.mix;
+            if (!t || t.length !== 3) throw new Error("setSelectionOverlay: tint must be [r, g, b]");
+            this._n.setOverlay(this._h, 1, +t[0], +t[1], +t[2], +mix);
+        };
+        this.readOverlay = () => this._n.readOverlay(this._h, this.width, this.height);
         this.stats = () => this._n.getTimings(this._h);
         this.deviceInfo = () => this._n.deviceInfo(this._h);
         this.isInitialized = () => initialized;

@@ -66,6 +66,10 @@ class GsrRegion(ctypes.Structure):
                 ("mask_stride", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class GsrOverlayOptions(ctypes.Structure):
+    _fields_ = [("tint", ctypes.c_float * 3), ("mix", ctypes.c_float), ("reserved", ctypes.c_int32 * 4)]
+
+
 class GsrDepthLayout(ctypes.Structure):
     _fields_ = [("format", ctypes.c_int32), ("step", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
                 ("stride", ctypes.c_int32), ("reserved", ctypes.c_int32), ("offset", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
@@ -116,6 +120,7 @@ EXPORTS = [
     "gsr_share_scene", "gsr_scene_sharing",
     "gsr_select_region", "gsr_select_box", "gsr_selection_set", "gsr_selection_invert", "gsr_read_selection", "gsr_scene_erase_selected",
     "gsr_contrib_reset", "gsr_contrib_accumulate_async", "gsr_read_contrib", "gsr_select_contrib",
+    "gsr_set_overlay", "gsr_overlay_async", "gsr_read_overlay", "gsr_read_overlay_rgba8", "gsr_overlay_device_ptr", "gsr_delivery_set_overlay",
 ]
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p)
 GSR_COMM_ID_BYTES = 128
@@ -259,6 +264,13 @@ def load_library(path=None):
     L.gsr_contrib_accumulate_async.argtypes = [vp]
     L.gsr_read_contrib.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, u32p]
     L.gsr_select_contrib.argtypes = [vp, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, u32p]
+    L.gsr_set_overlay.argtypes = [vp, ctypes.POINTER(GsrOverlayOptions)]
+    L.gsr_overlay_async.argtypes = [vp]
+    L.gsr_read_overlay.argtypes = [vp, vp, vp]
+    L.gsr_read_overlay_rgba8.argtypes = [vp, vp]
+    L.gsr_overlay_device_ptr.argtypes = [vp, ctypes.c_int32]
+    L.gsr_overlay_device_ptr.restype = vp
+    L.gsr_delivery_set_overlay.argtypes = [vp, ctypes.c_int32]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is ctypes.c_int and name not in ("gsplat_sort_host",):
@@ -637,7 +649,8 @@ class HIPRenderer:
     def open_delivery(self, slots=3, format="rgba8", full_range=False, background=(0, 0, 0)):
         """A ring of `slots` (2..8) pinned frames for deliver() / acquire() / release().  `format`: "rgba8", or 4:2:0 Y'CbCr for a
         video encoder, "nv12" / "i420" (BT.709; `full_range`: 0..255 instead of 16..235 / 16..240; `background`: the (R, G, B) the
-        premultiplied frame is laid over, Y'CbCr having no alpha).  A Y'CbCr ring is opened only when none is open."""
+        premultiplied frame is laid over, Y'CbCr having no alpha).  A Y'CbCr ring is opened only when none is open.
+        delivery_set_overlay() then makes the ring deliver the selection overlay in place of the frame."""
         if format not in DELIVERY_FORMATS:
             raise ValueError("format must be one of %s" % ", ".join(sorted(DELIVERY_FORMATS)))
         self._slot_views = {}
@@ -891,6 +904,45 @@ class HIPRenderer:
         self._check(self._L.gsr_select_contrib(self._ctx, self._select_code(CONTRIB_STATS, stat, "stat"), float(below),
                                                self._select_code(SELECT_OPS, op, "op"), ctypes.byref(count)))
         return count.value
+
+    # -- selection overlay (gsr_set_overlay / gsr_overlay_async / gsr_read_overlay*): the selected splats tinted --
+    def set_overlay(self, tint=(1.0, 0.5, 0.0), mix=0.5):
+        """The overlay's options: selected splats are drawn with lerp(colour, tint, mix); tint (r, g, b) as the framebuffer's
+        channels, mix in [0, 1].  tint=None: off, the overlay's buffers are freed."""
+        if tint is None:
+            self._check(self._L.gsr_set_overlay(self._ctx, None))
+            return
+        t = [float(v) for v in tint]
+        if len(t) != 3:
+            raise ValueError("tint must be three values (r, g, b)")
+        opt = GsrOverlayOptions((ctypes.c_float * 3)(*t), float(mix), (ctypes.c_int32 * 4)())
+        self._check(self._L.gsr_set_overlay(self._ctx, ctypes.byref(opt)))
+
+    def overlay_async(self):
+        """Enqueue the overlay pass behind the frame enqueued last (no host wait)."""
+        self._check(self._L.gsr_overlay_async(self._ctx))
+
+    def read_overlay(self):
+        """(rgba, cover) of the last rendered frame: rgba float32 [H, W, 4], the frame with the selected splats tinted, premultiplied
+        like readPixelsFloat(); cover float32 [H, W], the share of the pixel's alpha that selected splats supply.  Waits for the frame
+        (one that did not fit its lists is rendered again first) and runs the pass if the image is not the one of this frame, this
+        selection and these options."""
+        rgba = np.empty((self.height, self.width, 4), np.float32)
+        cover = np.empty((self.height, self.width), np.float32)
+        self._check(self._L.gsr_read_overlay(self._ctx, rgba.ctypes.data, cover.ctypes.data))
+        return rgba, cover
+
+    def read_overlay_rgba8(self):
+        """read_overlay()[0] as RGBA8 [H, W, 4], by the rule of readPixels()."""
+        out = np.empty((self.height, self.width, 4), np.uint8)
+        self._check(self._L.gsr_read_overlay_rgba8(self._ctx, out.ctypes.data))
+        return out
+
+    def delivery_set_overlay(self, on=True):
+        """The open ring (open_delivery / open_delivery_depth) delivers the selection overlay in place of the frame from now on
+        (needs set_overlay; refused in a group); on=False: the frame again.  A newly opened ring starts with it off.  (A method
+        of its own, as the C ABI has an entry point of its own: open_delivery keeps the signature its callers know.)"""
+        self._check(self._L.gsr_delivery_set_overlay(self._ctx, 1 if on else 0))
 
     def read_keys(self):
         keys = np.empty(self._count(), dtype=np.uint32)

@@ -616,6 +616,56 @@ int gsr_contrib_accumulate_async(gsr_ctx *ctx);
 int gsr_read_contrib(gsr_ctx *ctx, uint64_t *weight, float *peak, uint32_t *pixels, uint32_t n, uint32_t *frames);
 int gsr_select_contrib(gsr_ctx *ctx, int32_t stat, double below, int32_t op, uint32_t *selected);
 
+/* ---- selection overlay ---- the selected splats tinted, in read-backs and in delivered frames
+ * No interface of the reference stands behind this section either.  gsr_read_selection returns bits; this shows them: a second
+ * image beside the frame in which the selected splats carry a tint, and per pixel how much of it they are.
+ * Definition ("Selection overlay").  For the last rendered frame, a pixel's fragments, their weight B and the
+ * transmittance T are exactly those of "depth and pick": the entries of the pixel's bin list, in list order, that pass q <= 4, with
+ * no early termination, no saturation skip and no segments.  A splat's colour c = (cr, cg, cb) is the compositor's:
+ * (float)byte * (1.0f / 255.0f) of the record's colour bytes, or the frame's evaluated SH colour for an SH-coloured splat.  From
+ * T = 1, S = 0, C = (0, 0, 0), in f32:  w = T * B; T = T - w; and if the splat is selected: S = S + w; Cr = fma(w, cr, Cr), Cg and
+ * Cb likewise.  Two results, both W x H with row 0 at the top:
+ *   cover, float: S, the share of the pixel's alpha that selected splats supply (a host draws outlines from it).
+ *   overlay, float4, premultiplied like the framebuffer: with fb the frame's framebuffer value at the pixel,
+ *     out.r = fma(mix, fma(tint[0], S, -Cr), fb.r), g and b likewise; out.a = fb.a.  This is the frame rendered with every selected
+ *     splat's colour replaced by lerp(c, tint, mix).  mix == 0, or a pixel with no selected fragment, gives fb bit for bit.
+ *     Nothing is clamped here; the RGBA8 and Y'CbCr conversions clamp as they always do.
+ * A band context defines both on its own bin columns; elsewhere cover is 0 and overlay is whatever the framebuffer holds.  The pass
+ * reads the framebuffer and never writes it: the frame, its statistics, the depth planes and their validity are not touched.
+ * gsr_set_overlay supplies the options and allocates the two images (20 bytes per pixel, the context's: gsr_scene_sharing's
+ *   scene_bytes does not change); it makes no host wait beyond what allocating needs.  tint and mix must be finite, mix in [0, 1],
+ *   reserved 0, else GSR_ERR_ARG and nothing changes.  NULL: off, the buffers are freed.
+ * gsr_overlay_async enqueues the pass behind the last enqueued frame on the context's stream: no host wait.  It needs of the frame
+ *   exactly what gsr_depth_async needs, otherwise GSR_ERR_ARG and nothing is enqueued; GSR_ERR_ARG also without options.  A scene
+ *   never selected in has the empty selection: no mask is allocated, cover is 0 and overlay equals the framebuffer.  A frame whose
+ *   lists did not fit is not walked (the pass reads the frame's overflow word on the device) and nothing of it is ever returned as data.
+ * gsr_read_overlay and gsr_read_overlay_rgba8 are blocking: they settle the frame as gsr_read_depth does (one that did not fit is
+ *   rendered again), run the pass if the image is not the one of this frame, this selection and these options, refuse an invalid pass
+ *   with GSR_ERR_OVERFLOW, then copy.  rgba: w * h * 4 floats; cover: w * h floats; either may be NULL.  _rgba8: the overlay through
+ *   the framebuffer's RGBA8 rule, round(clamp(x, 0, 1) * 255), w * h * 4 bytes (its first call allocates 4 more bytes per pixel).
+ * gsr_overlay_device_ptr: plane 0 the overlay (float4[h][w]), 1 cover (float[h][w]); NULL before gsr_set_overlay.
+ * gsr_delivery_set_overlay(ctx, 1) on an open ring: gsr_deliver_frame_async enqueues the pass behind the frame and converts the
+ *   overlay image in place of the framebuffer, RGBA8 or Y'CbCr alike; serials, GSR_ERR_BUSY, the overflow refusal, resize and close
+ *   behave as before, and a depth ring's plane is still the frame's.  It needs options (GSR_ERR_ARG without) and an open ring.  On
+ *   a context in a group it returns GSR_ERR_ARG: the gathered frame is RGBA8 of other ranks, which nothing here can tint.  Off --
+ *   the default, and the state of every newly opened ring -- the ring does byte for byte what it does without this call.
+ * Shared scenes: the selection belongs to the scene, the images to the context, and passes run on each member's stream.  A context
+ * notes that it has a pass in flight (gsr_sync clears the note); every call that changes the selection first waits for the streams
+ * of the members with such a note, so a pass already enqueued never sees the change and every later one does.  A changed selection,
+ * changed options, a new frame, gsr_scene_limit_box, an erase and gsr_set_scene* make the image stale: the next read runs the pass
+ * again (or, without a valid frame, returns GSR_ERR_ARG).  A context that never calls any of this allocates nothing and launches nothing. */
+typedef struct gsr_overlay_options {
+    float tint[3];        /* the colour selected splats are drawn towards, as the framebuffer's channels (not clamped) */
+    float mix;            /* 0: the frame as it is; 1: the tint alone; in [0, 1] */
+    int32_t reserved[4];  /* 0 */
+} gsr_overlay_options;
+int gsr_set_overlay(gsr_ctx *ctx, const gsr_overlay_options *options);   /* NULL: off, buffers freed */
+int gsr_overlay_async(gsr_ctx *ctx);
+int gsr_read_overlay(gsr_ctx *ctx, float *rgba /* w*h*4 */, float *cover /* w*h */);   /* either NULL; blocking */
+int gsr_read_overlay_rgba8(gsr_ctx *ctx, uint8_t *out);
+void *gsr_overlay_device_ptr(gsr_ctx *ctx, int32_t plane);   /* 0 overlay, 1 cover */
+int gsr_delivery_set_overlay(gsr_ctx *ctx, int32_t on);
+
 /* ---- device interop (torch / RCCL plumbing in the harness) ---- */
 void *gsr_framebuffer_device_ptr(gsr_ctx *ctx); /* float4[h][w] on the device */
 void *gsr_stream_handle(gsr_ctx *ctx);          /* hipStream_t */

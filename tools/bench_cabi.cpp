@@ -3,7 +3,7 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--share-scene]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--share-scene]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
@@ -11,6 +11,9 @@
 // ring is full) -- the header alone is enough to consume frames -- and reports its rate and the checksum of a delivered frame.
 // --deliver-format nv12|i420 (beside --deliver) opens the rings in 4:2:0 Y'CbCr instead of RGBA8 (gsr_delivery_open_ex, BT.709 limited
 // range, black background) and reports the checksum of the last frame's payload (gsr_delivery_layout gives its size).
+// --overlay FRACTION selects that fraction of the splats (scattered over the indices) through gsr_selection_set and adds legs in which
+// gsr_overlay_async is enqueued behind every frame, alternated with plain legs as --depth does; then the pass alone on sampled frames
+// (overlay_pass_us; with --depth the depth pass on the same frames, depth_pass_us) and the hashes of the overlay's RGBA8 and cover.
 // --contrib adds legs in which gsr_contrib_accumulate_async is enqueued behind every frame, alternated with plain legs as --depth
 // does, then times the pass alone on sampled frames (host clock around the enqueue and the wait, the smallest of 20; beside --depth
 // the depth pass the same way) and reports `frames` and the FNV-1a of the three accumulator arrays.
@@ -147,6 +150,7 @@ int main(int argc, char** argv)
     int depth_step = 1;
     float depth_near = 0.1f;
     bool contrib = false;
+    double overlay_fraction = -1.0;   // < 0: off
     bool depth = false, pick = false, scene_arrays = false, share_scene = false;
     std::string scene_edit = "none";
     int32_t pick_xy[2] = {0, 0};
@@ -166,11 +170,12 @@ int main(int argc, char** argv)
         else if (a == "--depth-near") depth_near = (float)std::atof(next());
         else if (a == "--depth") depth = true;
         else if (a == "--contrib") contrib = true;
+        else if (a == "--overlay" && i + 1 < argc) { overlay_fraction = std::atof(argv[++i]); if (!(overlay_fraction >= 0.0 && overlay_fraction <= 1.0)) { std::fprintf(stderr, "--overlay FRACTION must be in [0, 1]\n"); return 2; } }
         else if (a == "--scene-arrays") scene_arrays = true;
         else if (a == "--scene-edit") scene_edit = next();
         else if (a == "--share-scene") share_scene = true;
         else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--share-scene]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--share-scene]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
@@ -316,6 +321,58 @@ int main(int argc, char** argv)
         CHECK(gsr_read_contrib(ctx[0], cw.data(), cp.data(), cx.data(), n, &contrib_frames));
         contrib_hash[0] = fnv1a(cw.data(), (size_t)n * 8); contrib_hash[1] = fnv1a(cp.data(), (size_t)n * 4); contrib_hash[2] = fnv1a(cx.data(), (size_t)n * 4);
     }
+    // --overlay: the orbit again, three legs without and three with the overlay pass (gsr_overlay_async) behind every frame,
+    // alternating; then the pass alone on sampled frames of context 0, measured as --contrib measures its pass
+    double overlay_sec[2] = {0, 0}, overlay_pass_us = 0, overlay_depth_pass_us = 0;
+    uint32_t overlay_selected = 0;
+    unsigned long long overlay_hash[2] = {0, 0};
+    if (overlay_fraction >= 0.0) {
+        ctx0 = ctx[0];
+        std::vector<uint32_t> words((n + 31) / 32, 0u);
+        const uint64_t limit = (uint64_t)(overlay_fraction * 4294967296.0);
+        for (uint32_t i = 0; i < n; i++)
+            if ((uint64_t)(i * 2654435761u) < limit) words[i >> 5] |= 1u << (i & 31);
+        CHECK(gsr_selection_set(ctx[0], words.data(), (uint32_t)words.size(), GSR_SELOP_REPLACE, &overlay_selected));
+        if (!share_scene) for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_selection_set(c, words.data(), (uint32_t)words.size(), GSR_SELOP_REPLACE, nullptr)); }
+        gsr_overlay_options oo{};
+        oo.tint[0] = 1.0f; oo.tint[1] = 0.5f; oo.tint[2] = 0.0f; oo.mix = 0.5f;
+        for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_set_overlay(c, &oo)); }
+        for (int leg = 0; leg < 6; leg++) {
+            const bool with = leg & 1;
+            auto overlay_step = [&](int k) -> int {
+                if (int rc = step(k)) return rc;
+                return with ? gsr_overlay_async(ctx[k % in_flight]) : 0;
+            };
+            for (int k = 0; k < warmup; k++) { ctx0 = ctx[k % in_flight]; CHECK(overlay_step(k)); }
+            for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_sync(c)); }
+            const auto d0 = std::chrono::steady_clock::now();
+            for (int k = 0; k < frames; k++) { ctx0 = ctx[(warmup + k) % in_flight]; CHECK(overlay_step(warmup + k)); }
+            for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_sync(c)); }
+            overlay_sec[with] += std::chrono::duration<double>(std::chrono::steady_clock::now() - d0).count();
+        }
+        ctx0 = ctx[0];
+        const int samples = 20;
+        for (int pass = 0; pass < (depth ? 2 : 1); pass++) {
+            double best = 1e30;
+            for (int k = 0; k < samples; k++) {
+                const Cam& p = poses[(7 * k) % 120];
+                CHECK(gsr_set_camera(ctx[0], p.view, p.proj, p.vp, (float)cfg->fx, (float)cfg->fx));
+                CHECK(gsr_render(ctx[0]));
+                const auto p0 = std::chrono::steady_clock::now();
+                CHECK(pass ? gsr_depth_async(ctx[0]) : gsr_overlay_async(ctx[0]));
+                CHECK(gsr_sync(ctx[0]));
+                best = std::min(best, std::chrono::duration<double>(std::chrono::steady_clock::now() - p0).count() * 1e6);
+            }
+            (pass ? overlay_depth_pass_us : overlay_pass_us) = best;
+        }
+        CHECK(gsr_set_camera(ctx[0], poses[0].view, poses[0].proj, poses[0].vp, (float)cfg->fx, (float)cfg->fx));
+        CHECK(gsr_render(ctx[0]));
+        std::vector<uint8_t> o8((size_t)cfg->w * cfg->h * 4);
+        std::vector<float> cov((size_t)cfg->w * cfg->h);
+        CHECK(gsr_read_overlay_rgba8(ctx[0], o8.data()));
+        CHECK(gsr_read_overlay(ctx[0], nullptr, cov.data()));
+        overlay_hash[0] = fnv1a(o8.data(), o8.size()); overlay_hash[1] = fnv1a(cov.data(), cov.size() * 4);
+    }
     gsr_pick_result picked{};
     if (pick) {
         ctx0 = ctx[0];
@@ -425,6 +482,12 @@ int main(int argc, char** argv)
         std::printf(", \"delivery_depth\": \"%s\", \"depth_step\": %d, \"depth_near\": %.9g, \"depth_width\": %d, \"depth_height\": %d, "
                     "\"depth_bytes\": %llu, \"delivered_depth_fnv1a\": \"%016llx\"",
                     deliver_depth.c_str(), dlay.step, (double)dlay.near, dlay.width, dlay.height, (unsigned long long)dlay.bytes, delivered_depth_hash);
+    if (overlay_fraction >= 0.0) {
+        std::printf(", \"overlay_fraction\": %g, \"overlay_selected\": %u, \"frames_per_sec_without_overlay\": %.1f, \"frames_per_sec_with_overlay\": %.1f, "
+                    "\"overlay_legs\": 3, \"overlay_pass_us\": %.1f, \"overlay_rgba8_fnv1a\": \"%016llx\", \"overlay_cover_fnv1a\": \"%016llx\"",
+                    overlay_fraction, overlay_selected, 3.0 * frames / overlay_sec[0], 3.0 * frames / overlay_sec[1], overlay_pass_us, overlay_hash[0], overlay_hash[1]);
+        if (depth) std::printf(", \"depth_pass_us\": %.1f", overlay_depth_pass_us);
+    }
     if (contrib) {
         std::printf(", \"frames_per_sec_without_contrib\": %.1f, \"frames_per_sec_with_contrib\": %.1f, \"contrib_legs\": 3, \"contrib_pass_ms\": %.4f, "
                     "\"contrib_frames\": %u, \"contrib_weight_fnv1a\": \"%016llx\", \"contrib_peak_fnv1a\": \"%016llx\", \"contrib_pixels_fnv1a\": \"%016llx\"",
