@@ -132,7 +132,12 @@ struct SharedScene {
     DevBuf<uint32_t> sh_r, sh_g, sh_b;
     uint32_t sh_count = 0;
     int32_t band[3] = {-1, -1, -1};
-    SceneSoA soa(float4* shcol) const { return SceneSoA{arr.px, arr.py, arr.pz, arr.cov0, arr.cov1, arr.cov2, arr.rgba, sh_r, sh_g, sh_b, shcol}; }
+    // (hidden: the mask only while a bit is set -- with nothing hidden the projection is handed null and the frame path is the one
+    // of a scene that never hid, buffers allocated or not)
+    SceneSoA soa(float4* shcol) const
+    {
+        return SceneSoA{arr.px, arr.py, arr.pz, arr.cov0, arr.cov1, arr.cov2, arr.rgba, sh_r, sh_g, sh_b, shcol, hid.count ? hid.mask.p : nullptr};
+    }
     // The SH frame: the inverse of the linear part of every rotate / scale since the coefficients were
     // supplied, row-major; the projection takes SH directions through it.  Kept up by gsr_scene_rotate / _scale while sh_follow
     // is set; the identity takes the projection's frameless path.
@@ -165,6 +170,19 @@ struct SharedScene {
         void reset() { mask.reset(); scratch.reset(); counters.reset(); region.reset(); words = counter_words = 0; region_bytes = 0; count = 0; }
         uint64_t bytes() const { return (uint64_t)words * 8 + (uint64_t)counter_words * 4 + region_bytes; }
     } sel;
+    // The hidden set (gsr_hidden.cpp; DESIGN.md section 4, "Hidden splats"): one bit per splat of THIS copy, the selection's layout,
+    // so the members have one together.  A hidden splat fails the projection's culls (k_project_key reads `mask` while count != 0).
+    // Nothing is allocated until the first call that hides; a scene without buffers reads as all zeros.  Unlike the selection it
+    // survives a compaction: scene_compact carries it into `spare` (k_box_compact_bits), then the two change places.
+    struct Hidden {
+        DevBuf<uint32_t> mask, spare, scratch;   // `words` words each: the set, the other buffer of a compaction, the folded set of the call in progress
+        DevBuf<uint32_t> counters;               // [0] the bits set after the last fold, [1] reserved, [2..] per-workgroup sums
+        uint32_t words = 0;                      // words the three were allocated for (even, >= ceil(n / 32))
+        uint32_t counter_words = 0;
+        uint32_t count = 0;                      // bits set: every call is blocking and returns with it final
+        void reset() { mask.reset(); spare.reset(); scratch.reset(); counters.reset(); words = counter_words = 0; count = 0; }
+        uint64_t bytes() const { return (uint64_t)words * 12 + (uint64_t)counter_words * 4; }
+    } hid;
     // Moves with every call that changes the selection's bits (the folds of gsr_select.cpp) or drops them (a new scene, a compaction):
     // a member's overlay image (gsr_overlay.cpp) is the selection's while the version it was enqueued for is this one.
     uint64_t sel_version = 1;
@@ -184,7 +202,7 @@ struct SharedScene {
     // device bytes of the state the members hold once
     uint64_t bytes() const
     {
-        return (uint64_t)arr_rows * (7 * 4 + (arr.rot ? 32 : 0)) + ((uint64_t)sh_rows + sh_spare_rows) * 3 * 32 + sel.bytes() + contrib.bytes();
+        return (uint64_t)arr_rows * (7 * 4 + (arr.rot ? 32 : 0)) + ((uint64_t)sh_rows + sh_spare_rows) * 3 * 32 + sel.bytes() + contrib.bytes() + hid.bytes();
     }
 };
 
@@ -511,6 +529,15 @@ void scene_release(gsr_ctx* c);
 // order, become the scene; SH state, generation, bins and the members' frame state as the header says of limitBox; the selection is
 // empty afterwards.  `what` names the caller in a HIP error.
 int scene_compact(gsr_ctx* c, const ScenePred& p, const char* what, uint32_t* kept_out);
+// Device-side order around an edit of a shared scene that arrives through `c` (translate, rotate, scale, a change of the hidden
+// set), no host wait: edit_begin makes c's stream wait for what every other member has enqueued, edit_end makes whatever the
+// others enqueue from now on wait for the edit; invalidate_members marks every member's frame state as edited (lists: the sorted
+// order went too)
+int edit_begin(gsr_ctx* c);
+int edit_end(gsr_ctx* c);
+void invalidate_members(gsr_ctx* c, bool lists);
+// gsr_hidden.cpp: the hidden set's buffers for the scene's count, allocated (the mask zeroed) by the first call that needs them
+int hidden_ensure(gsr_ctx* c);
 // gsr_select.cpp: the selection's buffers for the scene's count, allocated (the mask zeroed) by the first call that needs them; and
 // the end of every call that changes the selection: selection <- selection (op) scratch on the device, its count back to the host
 int select_ensure(gsr_ctx* c);

@@ -37,7 +37,8 @@ void build_frame_args(const gsr_ctx* c, bool render, FrameArgs& a)
     int32_t* slots_now = render ? c->words.slots.p : c->words.slots + (size_t)(1 + c->sort.parity) * slot_set;
     a.slots_next = render ? nullptr : c->words.slots + (size_t)(2 - c->sort.parity) * slot_set;
 
-    a.proj.sc = c->scene_soa();
+    a.proj.sc = c->scene_soa();   // (with the hidden set while a bit of it is set, null otherwise: a change of that re-captures the graph)
+    if (!render) a.proj.sc.hidden = nullptr;   // gsr_sort does not look at it: the depth key and the order are the whole scene's
     a.proj.depth = c->sort.depth;
     a.proj.slots = slots_now;
     if (render) {

@@ -69,6 +69,8 @@ struct SceneSoA {
     const uint32_t *cov0, *cov1, *cov2, *rgba;
     const uint32_t *sh_r, *sh_g, *sh_b;  // 8 u32 per SH-carrying splat and channel (null without SH)
     float4* shcol;                       // out: evaluated SH colour per splat (null without SH)
+    const uint32_t* hidden;              // the scene's hidden set, one bit per splat (null while nothing is hidden: the frame path as it
+                                         // was before hidden splats existed); read by k_project_key's projection only
 };
 
 // mutable device scene for the on-device build / transforms (k_scene.hip)
@@ -92,6 +94,10 @@ void launch_scene_compact(uint32_t n, const SceneDev& src, const SceneDev& dst, 
 // 8-word rows of the kept SH splats of sh_in[0..2], in order, into sh_out[0..2] (sh_count rows each).
 void launch_scene_compact_sh(uint32_t n, const SceneDev& src, const ScenePred& p, const uint32_t* block_off, uint32_t* count,
                              const int32_t* band, uint32_t sh_count, const uint32_t* const* sh_in, uint32_t* const* sh_out, hipStream_t s);
+// A one-bit-per-splat set through the same compaction (the hidden set), enqueued behind launch_scene_compact while `src` still
+// holds the source: out[new index of i] = in[i] for every kept i; `out` (nwords_out words) has been zeroed by the caller.
+void launch_scene_compact_bits(uint32_t n, const SceneDev& src, const ScenePred& p, const uint32_t* block_off, const uint32_t* in,
+                               uint32_t nwords_in, uint32_t* out, uint32_t nwords_out, hipStream_t s);
 // Scene.scales (3 f32 per splat, device memory) -> scl; and the scene back into the layouts of Scene.data (8 words per splat,
 // 16-byte aligned), positions and scales (3 f32 per splat): a null output is skipped.  Rotations need neither: `rot` IS
 // Scene.rotations' layout.

@@ -37,8 +37,18 @@ void leave_share(gsr_ctx* c)
     c->scene_gen = c->scene->generation;
 }
 
+// blocking calls that replace what the members read (limitBox, new SH textures): nothing of any member is in flight afterwards
+int sync_members(gsr_ctx* c)
+{
+    for (gsr_ctx* m : c->scene->members)
+        if (m != c) HIP_TRY(c, hipStreamSynchronize(m->stream));
+    return GSR_OK;
+}
+
+}  // namespace
+
 // the other members' frame state after an edit that arrived through `c`: as if each had run the call itself
-void invalidate_members(gsr_ctx* c, bool lists)
+void gsr::invalidate_members(gsr_ctx* c, bool lists)
 {
     for (gsr_ctx* m : c->scene->members) {
         m->have_frame = false;
@@ -46,9 +56,9 @@ void invalidate_members(gsr_ctx* c, bool lists)
     }
 }
 
-// Device-side order around an edit of a shared scene (translate, rotate, scale), no host wait: the editing context's stream waits for
+// Device-side order around an edit of a shared scene (translate, rotate, scale, a change of the hidden set), no host wait: the editing context's stream waits for
 // what every other member has enqueued (one event per member, recorded on its render stream) ...
-int edit_begin(gsr_ctx* c)
+int gsr::edit_begin(gsr_ctx* c)
 {
     for (gsr_ctx* m : c->scene->members) {
         if (m == c) continue;
@@ -59,7 +69,7 @@ int edit_begin(gsr_ctx* c)
 }
 
 // ... and whatever the others enqueue from now on waits for the edit (one event behind the kernel)
-int edit_end(gsr_ctx* c)
+int gsr::edit_end(gsr_ctx* c)
 {
     if (c->scene->members.size() < 2) return GSR_OK;
     HIP_TRY(c, hipEventRecord(c->share_ev, c->stream));
@@ -67,16 +77,6 @@ int edit_end(gsr_ctx* c)
         if (m != c) HIP_TRY(c, hipStreamWaitEvent(m->stream, c->share_ev, 0));
     return GSR_OK;
 }
-
-// blocking calls that replace what the members read (limitBox, new SH textures): nothing of any member is in flight afterwards
-int sync_members(gsr_ctx* c)
-{
-    for (gsr_ctx* m : c->scene->members)
-        if (m != c) HIP_TRY(c, hipStreamSynchronize(m->stream));
-    return GSR_OK;
-}
-
-}  // namespace
 
 // (re)allocate everything sized by the splat count; clears SH and per-frame state.  A member of a shared scene leaves it here.
 int gsr::alloc_scene(gsr_ctx* c, uint32_t n, bool with_rows)
@@ -90,6 +90,7 @@ int gsr::alloc_scene(gsr_ctx* c, uint32_t n, bool with_rows)
     sc.sel.reset();   // a new scene: the empty selection
     sc.sel_version++;   // (and every member's overlay image is stale)
     sc.contrib.reset();   // and no contribution: "never reset"
+    sc.hid.reset();   // and nothing hidden
     c->shcol.reset();
     int r;
     if ((r = sc.arr.alloc(c, n, with_rows)) || (r = alloc_sort(c, n))) return r;
@@ -206,11 +207,25 @@ int gsr::scene_compact(gsr_ctx* c, const ScenePred& p, const char* what, uint32_
             uint32_t* out[3] = {sc.sh_spare[0], sc.sh_spare[1], sc.sh_spare[2]};
             launch_scene_compact_sh(n, sc.arr.view(), p, block_count, count, sc.band, sc.sh_count, in, out, c->stream);
         }
+        // the hidden set keeps naming the same splats: H'[new index of i] = H[i] for every kept i, into the zeroed other buffer, and
+        // its count again (an empty fold: H' |= nothing).  Only while something is hidden: an empty set stays the zeros it is.
+        SharedScene::Hidden& hid = sc.hid;
+        const bool carry = hid.mask && hid.count;
+        uint32_t hidden_kept = 0;
+        hipError_t e0 = hipSuccess, e3 = hipSuccess, e4 = hipSuccess;
+        if (carry) {
+            e0 = hipMemsetAsync(hid.spare, 0, (size_t)hid.words * 4, c->stream);
+            launch_scene_compact_bits(n, sc.arr.view(), p, block_count, hid.mask, hid.words, hid.spare, hid.words, c->stream);
+            e3 = hipMemsetAsync(hid.scratch, 0, (size_t)hid.words * 4, c->stream);
+            launch_select_apply(SELOP_ADD, hid.spare, hid.scratch, n, hid.words, hid.counters + 2, hid.counters, c->stream);
+            e4 = hipMemcpyAsync(&hidden_kept, hid.counters, 4, hipMemcpyDeviceToHost, c->stream);
+        }
         hipError_t e1 = hipMemcpyAsync(counts, count, follow ? 16 : 4, hipMemcpyDeviceToHost, c->stream);
         hipError_t e2 = hipStreamSynchronize(c->stream);
-        for (hipError_t e : {e1, e2, hipGetLastError()})
+        for (hipError_t e : {e0, e1, e2, e3, e4, hipGetLastError()})
             if (e != hipSuccess) return fail(c, GSR_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
         kept = counts[0];
+        if (carry) { std::swap(hid.mask, hid.spare); hid.count = hidden_kept; }
         std::swap(sc.arr, dst);
         sc.arr_rows = n;   // (what `dst` was allocated for)
         sc.n = kept;   // arrays keep their old capacity; per-frame buffers sized for the old count still fit

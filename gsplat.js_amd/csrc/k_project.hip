@@ -186,6 +186,12 @@ __global__ __launch_bounds__(PROJ_THREADS) void k_project_key(SceneSoA sc, uint3
             uint32_t op8 = 0;   // the splat's opacity byte (for the frame's optical-depth figure below)
             float area = 0.0f;  // its footprint: the integral of exp(-|vPosition|^2) over the |vPosition| <= 2 ellipse, in pixels
             do {
+                // a hidden splat ("Hidden splats") fails the culls as if its pixel box were empty: no record, no
+                // rectangle, nothing counted; its depth key above is the one it always had.  (uniform) null while nothing is hidden.
+                // A wave reads two consecutive words, a workgroup eight: one line of the vector cache.
+                if (sc.hidden) {
+                    if ((sc.hidden[i >> 5] >> (i & 31u)) & 1u) break;
+                }
                 // :133-136  cam = view * vec4(p,1); pos2d = projection * cam
                 float camv[4], pos2d[4];
 #pragma unroll

@@ -213,6 +213,55 @@ __global__ __launch_bounds__(BOX_THREADS) void k_box_compact(uint32_t n, SceneDe
 // ---- limitBox on a scene whose SH colour follows it (gsr_set_sh_follow): the SH textures are compacted with the scene ----
 GSR_BOUNDS_DECL(scene_sh)   // sites: 0 source splat of k_box_thresholds, 1 SH row read by k_box_compact_sh, 2 SH row it stores
 
+GSR_BOUNDS_DECL(scene)   // sites: 0 word of Scene.scales read by k_scene_import, 1 its LDS cell, 2 float4 it stores,
+                         //        3 row of Scene.data stored by k_scene_export, 4 its LDS cell, 5 word of positions / scales it stores,
+                         //        6 word of the bit set k_box_compact_bits reads, 7 word it stores
+
+// k_box_compact's mask and offsets once more, for a one-bit-per-splat set that has to keep naming the same splats (the hidden set,
+// DESIGN.md section 4 "Hidden splats"): out[new index of i] = in[i] for every kept i, in order, into a ZEROED `out` of nwords_out
+// words.  A wave's kept lanes take the consecutive new indices [off, off + popcount): at most 64 bits from bit off & 31 of word
+// off >> 5 on, so at most three words.  Every lane places its bit in the word of the three it falls into, an OR across the wave
+// assembles them, and lane 0 ORs the non-zero ones into `out` (atomically: the run's edge words are shared with the waves
+// before and behind; bits of different waves never coincide).
+template <class Pred>
+__global__ __launch_bounds__(BOX_THREADS) void k_box_compact_bits(uint32_t n, SceneDev src, Pred box, const uint32_t* __restrict__ block_off,
+                                                                  const uint32_t* __restrict__ in, uint32_t nwords_in,
+                                                                  uint32_t* __restrict__ out, uint32_t nwords_out)
+{
+    __shared__ uint32_t s_w[BOX_THREADS / WAVE];
+    const uint32_t i = blockIdx.x * BOX_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool keep = i < n && box(src, i);
+    const uint64_t m = __ballot(keep);
+    if (lane == 0) s_w[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t off = block_off[blockIdx.x];
+    for (int w = 0; w < wave; w++) off += s_w[w];
+    bool bit = false;
+    if (keep) {
+        const uint32_t wi = i >> 5;
+        GSR_BOUND(scene, 6, wi, nwords_in);
+        bit = wi < nwords_in && ((in[wi] >> (i & 31u)) & 1u) != 0u;
+    }
+    const uint32_t o = off + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    const uint32_t w0 = off >> 5, k = (o >> 5) - w0, b = bit ? 1u << (o & 31u) : 0u;   // (k is 0, 1 or 2 for a kept lane)
+    uint32_t v0 = k == 0u ? b : 0u, v1 = k == 1u ? b : 0u, v2 = k == 2u ? b : 0u;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        v0 |= __shfl_xor(v0, d);
+        v1 |= __shfl_xor(v1, d);
+        v2 |= __shfl_xor(v2, d);
+    }
+    if (lane != 0) return;
+    const uint32_t v[3] = {v0, v1, v2};
+#pragma unroll
+    for (uint32_t j = 0; j < 3; j++) {
+        if (!v[j]) continue;
+        GSR_BOUND(scene, 7, w0 + j, nwords_out);
+        if (w0 + j < nwords_out) atomicOr(&out[w0 + j], v[j]);
+    }
+}
+
 // The three kept-prefix counts the new band thresholds come from: count[1 + k] = kept splats with index < at[k] (at[k] =
 // bandsIndices[k] + 1 clamped to [0, n], by the host), beside the total k_box_scan left in count[0]: the exclusive offset at at[k].
 // One workgroup per threshold; it recounts the part of the threshold's block in front of it.
@@ -274,9 +323,7 @@ __global__ __launch_bounds__(BOX_THREADS) void k_box_compact_sh(uint32_t n, Scen
 // Scene.rotations is (w, x, y, z) per splat, byte for byte what `rot` holds, so rotations are copied straight in and out and
 // no kernel touches them.  The three-float arrays go through LDS, so that a wave loads and stores whole consecutive lines on
 // both sides: 256 splats = 768 consecutive words outside, one splat per lane (stride 3 words: no bank conflict) inside.
-constexpr int XFER_THREADS = 256;
-GSR_BOUNDS_DECL(scene)   // sites: 0 word of Scene.scales read by k_scene_import, 1 its LDS cell, 2 float4 it stores,
-                         //        3 row of Scene.data stored by k_scene_export, 4 its LDS cell, 5 word of positions / scales it stores
+constexpr int XFER_THREADS = 256;   // (their bounds sites: `scene` 0..5, declared in front of k_box_compact_bits)
 
 // Scene.scales (3 f32 per splat) -> scl (float4 per splat, w = 0 as k_build_scene leaves it)
 __global__ __launch_bounds__(XFER_THREADS) void k_scene_import(const float* __restrict__ scales, uint32_t n, float4* __restrict__ scl)
@@ -399,6 +446,15 @@ void launch_scene_compact_sh(uint32_t n, const SceneDev& src, const ScenePred& p
     if (!n) return;
     if (p.box) compact_sh_with(n, src, box_of(p.box), block_off, count, band, sh_count, sh_in, sh_out, s);
     else compact_sh_with(n, src, MaskKeep{p.mask, p.keep}, block_off, count, band, sh_count, sh_in, sh_out, s);
+}
+
+void launch_scene_compact_bits(uint32_t n, const SceneDev& src, const ScenePred& p, const uint32_t* block_off, const uint32_t* in,
+                               uint32_t nwords_in, uint32_t* out, uint32_t nwords_out, hipStream_t s)
+{
+    if (!n) return;
+    const uint32_t nblocks = (n + BOX_THREADS - 1) / BOX_THREADS;
+    if (p.box) hipLaunchKernelGGL(k_box_compact_bits<Box>, dim3(nblocks), dim3(BOX_THREADS), 0, s, n, src, box_of(p.box), block_off, in, nwords_in, out, nwords_out);
+    else hipLaunchKernelGGL(k_box_compact_bits<MaskKeep>, dim3(nblocks), dim3(BOX_THREADS), 0, s, n, src, MaskKeep{p.mask, p.keep}, block_off, in, nwords_in, out, nwords_out);
 }
 
 void launch_scene_import(const float* scales, uint32_t n, float4* scl, hipStream_t s)

@@ -306,6 +306,21 @@ class Scene extends EventDispatcher {
         else this.dispatchEvent({ type: "change" });
     }
 
+    // Hide the splats whose bit of `mask` is set (the layout of the renderer's readHidden() / readSelection()); null shows all.
+    // The hidden set exists on the device copies only -- the four arrays do not change and no "change" fires -- so the set is
+    // issued once per distinct device copy (gsr_hidden_set), as eraseSelection issues its mask, and the call throws when there is
+    // no copy, when the copies are behind the arrays (an upload leaves nothing hidden), or when one cannot take it.
+    setHidden(mask) {
+        const words = Math.ceil(this._vertexCount / 32);
+        if (mask !== null && (!(mask instanceof Uint32Array) || mask.length < words)) throw new Error("setHidden: mask must be null or a Uint32Array of at least " + words + " words");
+        if (!this._devices.length) throw new Error("setHidden: no renderer holds this scene (the hidden set lives on the device copies)");
+        if (this._diverged) throw new Error("setHidden: the device copies are behind the scene's arrays (dispatch 'change' first)");
+        if (this._devices.some((d) => !d.setHidden)) throw new Error("setHidden: a device scene cannot take a hidden set");
+        let count = -1;
+        for (const d of this._distinctDevices()) count = d.setHidden(mask);
+        return count;
+    }
+
     // limitBox's loop over its predicate: the splats `stays` keeps move to the front of the four arrays in order; with
     // shFollowsTransforms the SH rows of the kept splats move up with them, and bandsIndices'[k] = (kept splats with index <=
     // bandsIndices[k]) - 1

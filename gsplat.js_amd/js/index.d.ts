@@ -69,6 +69,9 @@ export interface DeviceScene {
      *  them is treated like a host-only one for an eraseSelection. */
     setSelection?(words: Uint32Array): void;
     eraseSelected?(keep: boolean): number;
+    /** optional: Scene.setHidden sets its mask (the selection's layout; null: nothing hidden) as the device copy's hidden set and
+     *  returns the number of hidden splats.  Scene.setHidden throws when an attached device scene has none. */
+    setHidden?(words: Uint32Array | null): number;
 }
 export type SelectMode = "centre" | "hit";
 export type SelectOp = "replace" | "add" | "subtract" | "intersect";
@@ -93,6 +96,11 @@ export class Scene {
      *  or with { keep: true } the others: order-preserving, with limitBox's bookkeeping.  While device scenes are attached the mask
      *  is set on every distinct device copy and erased there; otherwise the same loop runs here.  Fires "change". */
     eraseSelection(mask: Uint32Array, options?: { keep?: boolean }): void;
+    /** Hide the splats whose bit of `mask` is set (HIPRenderer.readHidden()'s layout; at least ceil(vertexCount / 32) words); null
+     *  shows all.  The hidden set exists on the device copies only: it is set once on every distinct device copy, the arrays do not
+     *  change and no "change" fires.  Throws when no renderer holds the scene, when the copies are behind the arrays, or when a
+     *  device scene cannot take it.  Returns the number of hidden splats. */
+    setHidden(mask: Uint32Array | null): number;
     saveToFile(name: string): void;
     toSplatBytes(): Uint8Array;
     data: Uint32Array; vertexCount: number; width: number; height: number;
@@ -262,6 +270,19 @@ export class HIPRenderer {
     invertSelection(): number;
     /** ceil(vertexCount / 32) words: splat i is bit i & 31 of word i >>> 5 */
     readSelection(): Uint32Array;
+    /** Hidden splats: one more bit per splat of the device scene (renderers that share a scene have one set together).  A hidden
+     *  splat is in no list of the frames rendered from now on -- not drawn, not picked, no depth, no contribution, no overlay -- and
+     *  nothing is erased: the splats keep their numbers, and the set survives limitBox / eraseSelection of other splats.
+     *  hideSelection folds the selection into the hidden set (default "add": hide; "subtract": show; "replace"; "intersect"), showAll
+     *  empties it, setHidden folds the host's own words (null: the empty set), selectHidden folds the hidden set into the selection.
+     *  A change is a scene edit: pick, selectRegion and readDepth need a new frame.  Each returns the number of hidden (selectHidden:
+     *  selected) splats. */
+    hideSelection(options?: { op?: SelectOp }): number;
+    showAll(): number;
+    setHidden(words: Uint32Array | null, options?: { op?: SelectOp }): number;
+    /** ceil(vertexCount / 32) words: splat i is bit i & 31 of word i >>> 5 */
+    readHidden(): Uint32Array;
+    selectHidden(options?: { op?: SelectOp }): number;
     /** Contribution: per splat of the device scene (renderers that share a scene have one set together), what it showed over the
      *  frames of a tour.  resetContribution zeroes the accumulators (blocking); accumulateContribution enqueues the pass behind the
      *  frame rendered last (no wait; a frame whose lists did not fit adds nothing); readContribution returns weight (sum of the

@@ -1089,6 +1089,67 @@ napi_value EraseSelected(napi_env env, napi_callback_info info)
     return rc ? throw_gsr(env, c, rc, "gsr_scene_erase_selected") : count_value(env, count);
 }
 
+// ---- hidden splats (gsr_hide_selected, gsr_hidden_set, gsr_read_hidden, gsr_select_hidden) ----
+// hideSelected(handle, op) -> hidden
+napi_value HideSelected(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    int32_t op;
+    if (!c || !get_i32(env, argv[1], &op)) return nullptr;
+    uint32_t count = 0;
+    const int rc = gsr_hide_selected(c, op, &count);
+    return rc ? throw_gsr(env, c, rc, "gsr_hide_selected") : count_value(env, count);
+}
+
+// setHidden(handle, Uint32Array words | null, op) -> hidden
+napi_value SetHidden(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    void* words;
+    size_t len;
+    int32_t op;
+    if (!c || !get_typed(env, argv[1], napi_uint32_array, &words, &len, true) || !get_i32(env, argv[2], &op)) return nullptr;
+    uint32_t count = 0;
+    const int rc = gsr_hidden_set(c, (const uint32_t*)words, (uint32_t)len, op, &count);   // (null: the empty set)
+    return rc ? throw_gsr(env, c, rc, "gsr_hidden_set") : count_value(env, count);
+}
+
+// readHidden(handle) -> Uint32Array of ceil(n / 32) words
+napi_value ReadHidden(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    if (!c) return nullptr;
+    uint32_t n = 0;
+    int rc = gsr_scene_count(c, &n);
+    if (rc) return throw_gsr(env, c, rc, "gsr_scene_count");
+    const size_t nwords = ((size_t)n + 31) / 32;
+    void* data = nullptr;
+    napi_value ab, out;
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, nwords * 4, &data, &ab));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_uint32_array, nwords, ab, 0, &out));
+    rc = gsr_read_hidden(c, nwords ? (uint32_t*)data : nullptr, (uint32_t)nwords, nullptr);
+    return rc ? throw_gsr(env, c, rc, "gsr_read_hidden") : out;
+}
+
+// selectHidden(handle, op) -> selected
+napi_value SelectHidden(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    int32_t op;
+    if (!c || !get_i32(env, argv[1], &op)) return nullptr;
+    uint32_t count = 0;
+    const int rc = gsr_select_hidden(c, op, &count);
+    return rc ? throw_gsr(env, c, rc, "gsr_select_hidden") : count_value(env, count);
+}
+
 // ---- contribution (gsr_contrib_reset / _accumulate_async, gsr_read_contrib, gsr_select_contrib) ----
 // readContrib(handle) -> { weight: BigUint64Array(n), peak: Float32Array(n), pixels: Uint32Array(n), frames }
 napi_value ReadContrib(napi_env env, napi_callback_info info)
@@ -1223,6 +1284,7 @@ napi_value Init(napi_env env, napi_value exports)
         {"shareScene", ShareScene}, {"sceneSharing", SceneSharing},
         {"selectRegion", SelectRegion}, {"selectBox", SelectBox}, {"setSelection", SetSelection}, {"invertSelection", InvertSelection},
         {"readSelection", ReadSelection}, {"eraseSelected", EraseSelected},
+        {"hideSelected", HideSelected}, {"setHidden", SetHidden}, {"readHidden", ReadHidden}, {"selectHidden", SelectHidden},
         {"contribReset", Call0<gsr_contrib_reset>}, {"contribAccumulate", Call0<gsr_contrib_accumulate_async>}, {"readContrib", ReadContrib},
         {"selectContrib", SelectContrib},
         {"setOverlay", SetOverlay}, {"readOverlay", ReadOverlay}, {"readOverlayPixels", ReadOverlayPixels},

@@ -60,6 +60,8 @@ class HIPRenderer {
             // Scene.eraseSelection: the mask becomes the device copy's selection, then the copy is compacted there
             setSelection: (words) => this._n.setSelection(this._h, words, 0),
             eraseSelected: (keep) => (vertexCount = this._n.eraseSelected(this._h, keep ? 1 : 0)),
+            // Scene.setHidden: the mask becomes the device copy's hidden set (null: nothing hidden)
+            setHidden: (words) => this._n.setHidden(this._h, words, 0),
         };
         const upload = () => {   // initWebGL's scene part: worker init + texImage2D (WebGLRenderer.ts:105-110,185-195)
             const s = activeScene, n = s.vertexCount, positions = s.positions, rotations = s.rotations, scales = s.scales;
@@ -436,6 +438,19 @@ class HIPRenderer {
         this.setSelection = (words, op) => this._n.setSelection(this._h, words || null, code(OPS, op, "replace", "op"));
         this.invertSelection = () => this._n.invertSelection(this._h);
         this.readSelection = () => this._n.readSelection(this._h);
+        // ---- hidden splats (gsr_hide_selected / gsr_hidden_set / gsr_read_hidden / gsr_select_hidden): hide without erasing ----
+        //   renderer.selectRegion(lasso); renderer.hideSelection();            // the floaters are out of the way: not drawn, not picked
+        //   renderer.invertSelection(); renderer.hideSelection({ op: "replace" });   // isolate what was selected
+        //   renderer.showAll();                                                 // undo
+        // A hidden splat is in no list of the frames rendered from now on; nothing is erased and the splats keep their numbers.  The
+        // set belongs to the device copy (one for the renderers of a shared scene) and survives limitBox / eraseSelection of other
+        // splats; Scene.setHidden(mask) sets it on every device copy of a Scene.  A change is a scene edit: pick, selectRegion and
+        // readDepth need a new frame afterwards.  Every call returns the number of hidden (selectHidden: selected) splats.
+        this.hideSelection = (options) => this._n.hideSelected(this._h, code(OPS, (options || {}).op, "add", "op"));
+        this.showAll = () => this._n.setHidden(this._h, null, OPS.replace);
+        this.setHidden = (words, options) => this._n.setHidden(this._h, words || null, code(OPS, (options || {}).op, "replace", "op"));
+        this.readHidden = () => this._n.readHidden(this._h);
+        this.selectHidden = (options) => this._n.selectHidden(this._h, code(OPS, (options || {}).op, "replace", "op"));
         // ---- contribution (gsr_contrib_* / gsr_select_contrib): per splat of the device scene, what it showed over the frames of a tour ----
         //   renderer.resetContribution(); for (const cam of tour) { renderer.render(scene, cam); renderer.accumulateContribution(); }
         //   renderer.selectContribution({ stat: "pixels", below: 1 }); scene.eraseSelection(renderer.readSelection());   // what never showed

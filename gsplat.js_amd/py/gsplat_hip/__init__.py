@@ -119,6 +119,7 @@ EXPORTS = [
     "gsr_set_sh_follow", "gsr_set_sh_frame", "gsr_get_sh_frame", "gsr_read_scene_sh",
     "gsr_share_scene", "gsr_scene_sharing",
     "gsr_select_region", "gsr_select_box", "gsr_selection_set", "gsr_selection_invert", "gsr_read_selection", "gsr_scene_erase_selected",
+    "gsr_hide_selected", "gsr_hidden_set", "gsr_read_hidden", "gsr_select_hidden",
     "gsr_contrib_reset", "gsr_contrib_accumulate_async", "gsr_read_contrib", "gsr_select_contrib",
     "gsr_set_overlay", "gsr_overlay_async", "gsr_read_overlay", "gsr_read_overlay_rgba8", "gsr_overlay_device_ptr", "gsr_delivery_set_overlay",
 ]
@@ -260,6 +261,10 @@ def load_library(path=None):
     L.gsr_selection_invert.argtypes = [vp, u32p]
     L.gsr_read_selection.argtypes = [vp, vp, ctypes.c_uint32, u32p]
     L.gsr_scene_erase_selected.argtypes = [vp, ctypes.c_int32, u32p]
+    L.gsr_hide_selected.argtypes = [vp, ctypes.c_int32, u32p]
+    L.gsr_hidden_set.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_int32, u32p]
+    L.gsr_read_hidden.argtypes = [vp, vp, ctypes.c_uint32, u32p]
+    L.gsr_select_hidden.argtypes = [vp, ctypes.c_int32, u32p]
     L.gsr_contrib_reset.argtypes = [vp]
     L.gsr_contrib_accumulate_async.argtypes = [vp]
     L.gsr_read_contrib.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, u32p]
@@ -874,6 +879,60 @@ class HIPRenderer:
         self._check(self._L.gsr_scene_erase_selected(self._ctx, 1 if keep else 0, ctypes.byref(n)))
         self._n = n.value
         return n.value
+
+    # -- hidden splats (gsr_hide_selected / gsr_hidden_set / gsr_read_hidden / gsr_select_hidden): hide without erasing, show again --
+    def hide_selected(self, op="add"):
+        """Fold the selection into the hidden set: H = H op S -- "add" hides the selected splats, "subtract" shows them, "replace"
+        hides exactly them, "intersect" keeps hidden only what is also selected; returns the hidden count.  A hidden splat is in no
+        list of the frames rendered from now on (not drawn, not picked, no depth, no contribution); nothing is erased.  A scene
+        edit like scene_translate: the next pick / select_region / read_depth needs a new frame."""
+        count = ctypes.c_uint32(0)
+        self._check(self._L.gsr_hide_selected(self._ctx, self._select_code(SELECT_OPS, op, "op"), ctypes.byref(count)))
+        return count.value
+
+    def set_hidden(self, hidden=None, op="replace", words=None):
+        """Fold a set of the host's into the hidden set: `hidden` bool[n] (None: the empty set, so set_hidden(None) shows
+        everything), or uint32 words as hidden_words() returns them (`words=`, or a uint32 array; bits at and above n are dropped)."""
+        count = ctypes.c_uint32(0)
+        code = self._select_code(SELECT_OPS, op, "op")
+        if words is None and hidden is not None:
+            a = np.ascontiguousarray(hidden)
+            if a.dtype == np.uint32:
+                words = a
+            else:
+                b = a.reshape(-1) != 0
+                if b.size != self._count():
+                    raise ValueError("hidden must hold one entry per splat (%d)" % self._count())
+                words = pack_selection(b)
+        if words is None:
+            self._check(self._L.gsr_hidden_set(self._ctx, None, 0, code, ctypes.byref(count)))
+        else:
+            w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+            self._check(self._L.gsr_hidden_set(self._ctx, w.ctypes.data, w.size, code, ctypes.byref(count)))
+        return count.value
+
+    def hidden_words(self):
+        """The hidden set as the device holds it: uint32[ceil(n / 32)], splat i = bit i & 31 of word i >> 5."""
+        n = self._count()
+        w = np.zeros(-(-n // 32), dtype=np.uint32)
+        self._check(self._L.gsr_read_hidden(self._ctx, w.ctypes.data if w.size else None, w.size, None))
+        return w
+
+    def hidden_count(self):
+        count = ctypes.c_uint32(0)
+        self._check(self._L.gsr_read_hidden(self._ctx, None, 0, ctypes.byref(count)))
+        return count.value
+
+    def hidden(self):
+        """bool[n]: which splats are hidden."""
+        return unpack_selection(self.hidden_words(), self._count())
+
+    def select_hidden(self, op="replace"):
+        """Fold the hidden set into the selection (S = S op H), a picker like select_box; returns the selected count.
+        select_hidden() + scene_erase_selected() erases the hidden splats for good."""
+        count = ctypes.c_uint32(0)
+        self._check(self._L.gsr_select_hidden(self._ctx, self._select_code(SELECT_OPS, op, "op"), ctypes.byref(count)))
+        return count.value
 
     # -- contribution (gsr_contrib_* / gsr_read_contrib / gsr_select_contrib): per-splat weight, peak and pixel counts over views --
     def contrib_reset(self):

@@ -569,6 +569,49 @@ int gsr_selection_invert(gsr_ctx *ctx, uint32_t *selected);
 int gsr_read_selection(gsr_ctx *ctx, uint32_t *words, uint32_t nwords, uint32_t *selected);   /* words may be NULL: count only */
 int gsr_scene_erase_selected(gsr_ctx *ctx, int32_t keep_selected, uint32_t *new_count);
 
+/* ---- hidden splats ---- hide the selection without erasing it, show it again
+ * No interface of the reference stands behind this section either: its Scene has limitBox and nothing softer
+ * (src/core/Scene.ts:307-366).  Between "tinted" (the overlay) and "gone for good" (gsr_scene_erase_selected) lies the step every
+ * splat editor has: hide.  It is non-destructive -- undo is "show" -- and isolating an object is gsr_selection_invert + hide.
+ * The hidden set H is one bit per splat of a scene, held on the device with the scene, in the selection's layout: ceil(n / 32)
+ * words, splat i is bit i & 31 of word i >> 5, bits at and above n are always 0, and a scene that never hid anything reads as all
+ * zeros -- such a scene has allocated nothing and gsr_scene_sharing's scene_bytes is unchanged.  The members of a shared scene
+ * have ONE hidden set.
+ * The frame ("Hidden splats"): a hidden splat fails the frame's culls, as if its pixel box were empty.  It
+ *   gets no record and no bin rectangle, is in no bin list, does not count in gsr_timings.visible / bin_entries / tile_entries
+ *   nor in the optical-mass words the work-item cut reads, on a band context it is not a survivor, and gsr_read_records reports it
+ *   as it reports a culled splat (x0 > x1).  It is still sorted: its depth key, the frame's min / max and gsr_read_depth_index are
+ *   bit for bit what they are with nothing hidden, and gsr_sort does not look at H.  Everything downstream follows from the
+ *   lists: the compositor, the depth planes and gsr_pick see through it, gsr_select_region does not pick it in either mode, the
+ *   contribution pass gives it no weight, the overlay does not draw it; none of them got a new argument.  With H empty the frame
+ *   path is exactly the one of a scene that never hid -- the projection is handed a null pointer, not an all-zero mask -- also
+ *   after "show all" while the buffers stay allocated.
+ * Calls; S is the selection, P a set of the host's:
+ *   gsr_hide_selected: H = H op S -- REPLACE H = S; ADD H = H | S (hide); SUBTRACT H = H & ~S (show); INTERSECT H = H & S.
+ *   gsr_hidden_set: H = H op P; words NULL is the empty set, so (NULL, 0, GSR_SELOP_REPLACE) is "show all".
+ *   gsr_read_hidden: the words and the count; words may be NULL: count only.
+ *   gsr_select_hidden: S = S op H, an ordinary picker: it does not touch H or any frame.
+ *   op is GSR_SELOP_*; `hidden` / `selected` receive the bit count afterwards and may be NULL; gsr_hidden_set / gsr_read_hidden
+ *   need nwords >= ceil(n / 32), else GSR_ERR_ARG, and host bits at or above n are dropped.  A refused call (GSR_ERR_ARG: nwords,
+ *   an unknown op, a NULL ctx) changes nothing.
+ * A change of H is a scene edit, ordered like gsr_scene_translate, but it needs no rotations / scales: a scene from gsr_set_scene
+ *   can hide.  It marks every member's frame state as edited: gsr_depth_async, gsr_pick, gsr_select_region and a depth ring's
+ *   gsr_deliver_frame_async return GSR_ERR_ARG until the next frame, exactly as after a translate.  Frames any member enqueued
+ *   before the call see the old H, frames enqueued afterwards, on any member, see the new one; there is no host wait on other
+ *   members' streams, the call waits for its own stream to return the count.  A call that would change no bit still counts as
+ *   an edit.  A captured graph is re-captured when H goes from empty to non-empty or back.
+ * Compaction: gsr_scene_limit_box and a removing gsr_scene_erase_selected carry H through: H'[new index of i] = H[i] for every
+ *   kept i, in order; the tail is 0 and the count is recomputed (the selection and the contribution state are still dropped
+ *   there).  Erasing the hidden splats for good is gsr_select_hidden(REPLACE) + gsr_scene_erase_selected(0); afterwards H is empty.
+ * Where H is replaced: gsr_set_scene* leaves nothing hidden; after gsr_share_scene, ctx has `from`'s H; a member that leaves a
+ *   share starts with nothing hidden.
+ * Interplay: gsr_select_box and gsr_select_contrib range over all splats, hidden ones included; a splat hidden during a tour
+ *   accumulates nothing, so `below` picks it -- a host that does not want that folds gsr_select_hidden(SUBTRACT) behind it. */
+int gsr_hide_selected(gsr_ctx *ctx, int32_t op, uint32_t *hidden);
+int gsr_hidden_set(gsr_ctx *ctx, const uint32_t *words, uint32_t nwords, int32_t op, uint32_t *hidden);   /* words NULL: the empty set */
+int gsr_read_hidden(gsr_ctx *ctx, uint32_t *words, uint32_t nwords, uint32_t *hidden);   /* words may be NULL: count only */
+int gsr_select_hidden(gsr_ctx *ctx, int32_t op, uint32_t *selected);
+
 /* ---- contribution ---- per-splat weight, peak and pixel counts over views
  * No interface of the reference stands behind this section either.  Every selector above is geometric; this one answers "which
  * splats never show" -- buried inside surfaces, hidden behind them, touching no pixel from any camera of a tour -- and with

@@ -3,7 +3,7 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--share-scene]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--share-scene]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
@@ -27,6 +27,10 @@
 // --share-scene: with --in-flight k, contexts 2..k call gsr_share_scene(ctx, first) instead of uploading: one device copy of the
 // scene for all of them.  The report carries scene_sharing (members, bytes held once) and setup_ms, the wall time from the first
 // gsr_create to the last scene being ready, with and without the flag.
+// --hide FRACTION hides that fraction of the splats (scattered over the indices) through gsr_hidden_set on every device copy before
+// the first frame, so every timed frame is one of the scene with those out of the way; the report carries `hidden` and the call's
+// wall time.  --hide 0 is the run to compare with: nothing hidden, the projection handed no mask.  --hide-edits adds, at the very
+// end, the wall time of one gsr_hide_selected and of one gsr_scene_erase_selected with and without a hidden set to carry along.
 //
 // Scene: the seeded synthetic generator of gsplat_hip/synth.py (mulberry32 counter PRNG, 24 draws per splat) written
 // out again in C++; log/exp/cos come from libm here and from numpy there, so a byte may differ in a rare rounding --
@@ -153,6 +157,8 @@ int main(int argc, char** argv)
     double overlay_fraction = -1.0;   // < 0: off
     bool depth = false, pick = false, scene_arrays = false, share_scene = false;
     std::string scene_edit = "none";
+    double hide_fraction = -1.0;   // < 0: off
+    bool hide_edits = false;
     int32_t pick_xy[2] = {0, 0};
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -171,6 +177,8 @@ int main(int argc, char** argv)
         else if (a == "--depth") depth = true;
         else if (a == "--contrib") contrib = true;
         else if (a == "--overlay" && i + 1 < argc) { overlay_fraction = std::atof(argv[++i]); if (!(overlay_fraction >= 0.0 && overlay_fraction <= 1.0)) { std::fprintf(stderr, "--overlay FRACTION must be in [0, 1]\n"); return 2; } }
+        else if (a == "--hide" && i + 1 < argc) { hide_fraction = std::atof(argv[++i]); if (!(hide_fraction >= 0.0 && hide_fraction <= 1.0)) { std::fprintf(stderr, "--hide FRACTION must be in [0, 1]\n"); return 2; } }
+        else if (a == "--hide-edits") hide_edits = true;
         else if (a == "--scene-arrays") scene_arrays = true;
         else if (a == "--scene-edit") scene_edit = next();
         else if (a == "--share-scene") share_scene = true;
@@ -232,6 +240,21 @@ int main(int argc, char** argv)
     CHECK(gsr_scene_sharing(ctx[in_flight - 1], &share_members, &share_bytes));
     std::vector<Cam> poses(120);
     for (int k = 0; k < 120; k++) poses[k] = orbit_camera(k, 120, cfg->w, cfg->h, cfg->fx);
+    // --hide: a seeded fraction of the splats (scattered over the indices, the hash --overlay uses, another seed) is hidden on every
+    // device copy before any frame is enqueued: every frame below, warm-up included, is a frame of the scene with those out of the way
+    uint32_t hidden = 0;
+    double hidden_set_ms = 0;
+    if (hide_fraction >= 0.0) {
+        std::vector<uint32_t> words((n + 31) / 32, 0u);
+        const uint64_t limit = (uint64_t)(hide_fraction * 4294967296.0);
+        for (uint32_t i = 0; i < n; i++)
+            if ((uint64_t)((i + 0x9e3779b9u) * 2654435761u) < limit) words[i >> 5] |= 1u << (i & 31);
+        const auto h0 = std::chrono::steady_clock::now();
+        ctx0 = ctx[0];
+        CHECK(gsr_hidden_set(ctx[0], words.data(), (uint32_t)words.size(), GSR_SELOP_REPLACE, &hidden));
+        hidden_set_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - h0).count() * 1e3;
+        if (!share_scene) for (gsr_ctx* c : ctx) { ctx0 = c; if (c != ctx[0]) CHECK(gsr_hidden_set(c, words.data(), (uint32_t)words.size(), GSR_SELOP_REPLACE, nullptr)); }
+    }
 
     auto step = [&](int k) -> int {
         gsr_ctx* c = ctx[k % in_flight];
@@ -461,6 +484,33 @@ int main(int argc, char** argv)
         for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_sync(c)); }
         edit_sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - e0).count();
     }
+    // --hide-edits (last: it removes splats): the wall time of one gsr_hide_selected that hides a fifth of the scene, and of one
+    // gsr_scene_erase_selected of another fifth while those are hidden (the compaction carries the hidden set: k_box_compact_bits)
+    double hide_selected_ms = 0, erase_hidden_ms = 0, erase_plain_ms = 0;
+    uint32_t edits_hidden = 0, edits_kept = 0;
+    if (hide_edits) {
+        ctx0 = ctx[0];
+        std::vector<uint32_t> words((n + 31) / 32, 0u);
+        auto fifth = [&](uint32_t r) { std::fill(words.begin(), words.end(), 0u); for (uint32_t i = 0; i < n; i++) if (i % 5u == r) words[i >> 5] |= 1u << (i & 31); };
+        auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count() * 1e3; };
+        CHECK(gsr_hidden_set(ctx[0], nullptr, 0, GSR_SELOP_REPLACE, nullptr));
+        fifth(0);
+        CHECK(gsr_selection_set(ctx[0], words.data(), (uint32_t)words.size(), GSR_SELOP_REPLACE, nullptr));
+        auto t = std::chrono::steady_clock::now();
+        CHECK(gsr_scene_erase_selected(ctx[0], 0, nullptr));                       // nothing hidden: the compaction as it was
+        erase_plain_ms = ms_since(t);
+        fifth(1);
+        CHECK(gsr_selection_set(ctx[0], words.data(), (uint32_t)words.size(), GSR_SELOP_REPLACE, nullptr));
+        t = std::chrono::steady_clock::now();
+        CHECK(gsr_hide_selected(ctx[0], GSR_SELOP_ADD, &edits_hidden));
+        hide_selected_ms = ms_since(t);
+        fifth(2);
+        CHECK(gsr_selection_set(ctx[0], words.data(), (uint32_t)words.size(), GSR_SELOP_REPLACE, nullptr));
+        t = std::chrono::steady_clock::now();
+        CHECK(gsr_scene_erase_selected(ctx[0], 0, &edits_kept));                   // with the hidden set carried through
+        erase_hidden_ms = ms_since(t);
+        CHECK(gsr_read_hidden(ctx[0], nullptr, 0, &edits_hidden));
+    }
     char name[128] = "";
     int32_t cus = 0, khz = 0;
     (void)gsr_device_info(ctx[0], name, (int32_t)sizeof name, &cus, &khz);
@@ -499,6 +549,10 @@ int main(int argc, char** argv)
                     3.0 * frames / depth_sec[0], 3.0 * frames / depth_sec[1]);
     std::printf(", \"share_scene\": %s, \"scene_sharing\": {\"members\": %d, \"bytes\": %llu}, \"setup_ms\": %.2f",
                 share_scene ? "true" : "false", share_members, (unsigned long long)share_bytes, setup_ms);
+    if (hide_fraction >= 0.0) std::printf(", \"hide_fraction\": %g, \"hidden\": %u, \"hidden_set_ms\": %.3f", hide_fraction, hidden, hidden_set_ms);
+    if (hide_edits)
+        std::printf(", \"hide_edits\": {\"hide_selected_ms\": %.3f, \"erase_ms\": %.3f, \"erase_with_hidden_ms\": %.3f, \"hidden_after\": %u, \"kept\": %u}",
+                    hide_selected_ms, erase_plain_ms, erase_hidden_ms, edits_hidden, edits_kept);
     if (scene_arrays) std::printf(", \"scene_from\": \"gsr_set_scene_arrays\"");
     if (scene_edit == "rotate") std::printf(", \"scene_edit\": \"rotate\", \"frames_per_sec_scene_edit\": %.1f", frames / edit_sec);
     if (pick)
