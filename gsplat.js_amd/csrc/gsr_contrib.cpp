@@ -62,14 +62,7 @@ int gsr_contrib_accumulate_async(gsr_ctx* c)
     SharedScene& sc = *c->scene;
     if (!sc.contrib.live()) { if (int r = reset_accumulators(c)) return r; }   // the first use: what gsr_contrib_reset does
     const SharedScene::Contrib& k = sc.contrib;
-    ContribBuffers b{};
-    b.bin_start = c->bin.start; b.list = c->bin.list; b.rec = c->sort.rec;
-    b.px = sc.arr.px; b.py = sc.arr.py; b.pz = sc.arr.pz;
-    b.overflow = &c->words.fstate->overflow;
-    b.weight = k.weight; b.peak = k.peak; b.pixels = k.pixels; b.frames = k.counters;
-    b.capacity = c->bin.capacity;
-    b.nsplats = std::max(sc.n, 1u);
-    b.rows = k.rows;
+    const ContribBuffers b{frame_lists(c), k.weight, k.peak, k.pixels, k.counters, k.rows};
     launch_contrib(b, make_grid(c), c->cam_frame, c->knobs.depth_skip, c->stream);
     HIP_TRY(c, hipGetLastError());
     return GSR_OK;

@@ -548,6 +548,8 @@ void comm_release(gsr_ctx* c);
 // `who` in front of the message; nothing enqueued); depth_enqueue: the pass into `p` behind the frame on the render stream (launch
 // errors are left for the caller's hipGetLastError)
 int depth_frame_check(gsr_ctx* c, const char* who);
+// the lists of that frame as every pass behind it walks them (depth, contribution, overlay): the one place that fills FrameLists
+FrameLists frame_lists(const gsr_ctx* c);
 int depth_enqueue(gsr_ctx* c, DepthPlanes& p, int step, DepthFill fill);
 // what gsr_pick and gsr_read_depth do first: gsr_sync's work for the frame (one that did not fit is rendered again), then the checks again
 int depth_settle_frame(gsr_ctx* c, const char* who);

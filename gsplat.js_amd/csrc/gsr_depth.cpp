@@ -19,27 +19,27 @@ int gsr::depth_frame_check(gsr_ctx* c, const char* who)
     return GSR_OK;
 }
 
+FrameLists gsr::frame_lists(const gsr_ctx* c)
+{
+    FrameLists f{};
+    f.bin_start = c->bin.start; f.list = c->bin.list; f.rec = c->sort.rec;
+    f.px = c->scene->arr.px; f.py = c->scene->arr.py; f.pz = c->scene->arr.pz;
+    f.overflow = &c->words.fstate->overflow;
+    f.capacity = c->bin.capacity;
+    f.nsplats = std::max(c->scene->n, 1u);   // (the walk clamps a list entry to nsplats - 1)
+    return f;
+}
+
 namespace {
 
 constexpr uint32_t MAX_PICKS = 4096;
 static_assert(sizeof(PickResult) == sizeof(gsr_pick_result) && offsetof(PickResult, alpha) == offsetof(gsr_pick_result, alpha),
               "the kernel's result is the header's");
 
-// the frame's lists, records and positions, and the planes a pass writes (none: gsr_pick)
+// the frame's lists and the planes a pass writes (none: gsr_pick)
 DepthBuffers buffers(gsr_ctx* c, uint32_t* invalid, float* mean, float* hit, uint32_t* index)
 {
-    DepthBuffers b{};
-    b.bin_start = c->bin.start;
-    b.list = c->bin.list;
-    b.rec = c->sort.rec;
-    b.px = c->scene->arr.px; b.py = c->scene->arr.py; b.pz = c->scene->arr.pz;
-    b.overflow = &c->words.fstate->overflow;
-    b.invalid = invalid;
-    b.mean = mean; b.hit = hit; b.index = index;
-    b.capacity = c->bin.capacity;
-    b.nsplats = std::max(c->scene->n, 1u);
-    b.hit_alpha = c->depth.hit_alpha;
-    return b;
+    return DepthBuffers{frame_lists(c), invalid, mean, hit, index, c->depth.hit_alpha};
 }
 
 // the context's planes pass behind whatever the stream holds; the planes are then those of the last enqueued frame

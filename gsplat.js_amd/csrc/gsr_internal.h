@@ -429,17 +429,22 @@ constexpr int DELIVER_DEPTH_F32 = 1, DELIVER_DEPTH_U16 = 2;   // (GSR_DEPTH_F32 
 void launch_deliver_depth(int format, const float* plane, uint8_t* staging, size_t depth_offset, size_t trailer_offset, int32_t Wd, int32_t Hd, float near,
                           int32_t W, int32_t H, uint64_t serial, const uint32_t* overflow, hipStream_t s);
 
-// Depth planes and picking (k_depth.hip): the last frame's bin lists walked once more for depth instead of colour.
-struct DepthBuffers {
+// The last frame's lists as the passes behind the frame walk them once more (k_depth_walk.h: depth planes and picking, contribution,
+// selection overlay): filled in one place, frame_lists of gsr_depth.cpp.
+struct FrameLists {
     const uint32_t* bin_start;   // nbins + 1
     const uint32_t* list;
     const Record* rec;
     const float *px, *py, *pz;   // the scene's positions (a splat's depth is computed from them and the frame's camera)
     const uint32_t* overflow;    // the frame's overflow word: non-zero = its lists did not fit, nothing of it may be walked
+    uint32_t capacity;           // entries the list can hold
+    uint32_t nsplats;            // splats of the scene, at least 1 (the walk clamps a list entry to nsplats - 1)
+};
+
+// Depth planes and picking (k_depth.hip): the lists walked for depth instead of colour.
+struct DepthBuffers : FrameLists {
     uint32_t* invalid;           // out: 1 when the pass refused the frame (nothing written), 0 otherwise
     float* mean; float* hit; uint32_t* index;   // the planes, W x H each (null for k_pick)
-    uint32_t capacity;           // entries the list can hold
-    uint32_t nsplats;
     float hit_alpha;
 };
 struct PickResult { uint32_t index; float depth, mean, alpha; };   // gsr_pick_result
@@ -479,18 +484,11 @@ void launch_select_apply(int op, uint32_t* sel, const uint32_t* scratch, uint32_
 
 // Contribution (k_contrib.hip; DESIGN.md section 4, "Contribution"): the last frame's bin lists walked once more, the weight
 // w = T * B of every fragment kept per SPLAT and summed over pixels and passes into three accumulators held with the scene.
-struct ContribBuffers {
-    const uint32_t* bin_start;   // nbins + 1      (the frame's lists, records and positions, as DepthBuffers holds them)
-    const uint32_t* list;
-    const Record* rec;
-    const float *px, *py, *pz;
-    const uint32_t* overflow;    // the frame's overflow word: non-zero = its lists did not fit, nothing of it is walked or counted
+struct ContribBuffers : FrameLists {   // (a frame that did not fit is neither walked nor counted)
     unsigned long long* weight;  // rows: sum of rintf(w * 2^24) over the splat's fragments
     uint32_t* peak;              // rows: max of w, as the bits of a non-negative f32
     uint32_t* pixels;            // rows: the splat's fragments, modulo 2^32
     uint32_t* frames;            // one word: passes that contributed
-    uint32_t capacity;           // entries the list can hold
-    uint32_t nsplats;
     uint32_t rows;               // splats the accumulators were allocated for
 };
 constexpr int CONTRIB_WEIGHT = 0, CONTRIB_PEAK = 1, CONTRIB_PIXELS = 2;   // (GSR_CONTRIB_*)
@@ -502,20 +500,14 @@ void launch_contrib_select(int stat, double below, uint32_t n, const unsigned lo
 // Selection overlay (k_overlay.hip; DESIGN.md section 4, "Selection overlay"): the last frame's bin lists walked once more, the
 // weight w = T * B of every fragment of a SELECTED splat summed per pixel (cover) and, with the splat's colour, turned into the
 // frame with those splats tinted (overlay).  Reads the framebuffer, never writes it.
-struct OverlayBuffers {
-    const uint32_t* bin_start;   // nbins + 1      (the frame's lists, records and positions, as DepthBuffers holds them)
-    const uint32_t* list;
-    const Record* rec;
-    const float *px, *py, *pz;
+struct OverlayBuffers : FrameLists {
     const float4* shcol;         // this frame's evaluated SH colours (null without SH)
     const uint32_t* sel;         // the selection words (null: a scene never selected in, the empty selection)
-    const uint32_t* overflow;    // the frame's overflow word: non-zero = its lists did not fit, nothing of it may be walked
     uint32_t* invalid;           // out: 1 when the pass refused the frame (nothing written), 0 otherwise
     const float4* fb;            // the frame's framebuffer, W x H
     float4* overlay;             // out, W x H
     float* cover;                // out, W x H
-    uint32_t capacity;           // entries the list can hold
-    uint32_t nsplats, nwords;    // splats of the scene, words `sel` holds
+    uint32_t nwords;             // words `sel` holds
     float tint[3], mix;
 };
 // skip: entries that cannot reach a tile are left out (GSR_DEPTH_SKIP); trim: the walk ends behind the list's last selected entry

@@ -69,16 +69,11 @@ int gsr::overlay_enqueue(gsr_ctx* c)
         HIP_TRY(c, hipMemcpyAsync(o.image, c->out.fb, np * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(c, hipMemsetAsync(o.cover, 0, np * sizeof(float), c->stream));
     }
-    OverlayBuffers b{};
-    b.bin_start = c->bin.start; b.list = c->bin.list; b.rec = c->sort.rec;
-    b.px = sc.arr.px; b.py = sc.arr.py; b.pz = sc.arr.pz;
+    OverlayBuffers b{frame_lists(c)};
     b.shcol = c->shcol;
     b.sel = sc.sel.mask;            // (null: never selected in)
-    b.overflow = &c->words.fstate->overflow;
     b.invalid = o.invalid;
     b.fb = c->out.fb; b.overlay = o.image; b.cover = o.cover;
-    b.capacity = c->bin.capacity;
-    b.nsplats = std::max(sc.n, 1u);
     b.nwords = sc.sel.mask ? sc.sel.words : 0u;
     for (int k = 0; k < 3; k++) b.tint[k] = o.tint[k];
     b.mix = o.mix;

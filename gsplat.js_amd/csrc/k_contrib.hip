@@ -9,21 +9,25 @@
 //     pixels[i] += 1                             whatever the weight; modulo 2^32
 // Integers and a maximum: the result does not depend on the order in which tiles, bins, contexts and views arrive.
 //
-// k_contrib keeps the shape of k_depth_planes<SKIP, 1>: one 256-thread workgroup per bin, chunks of 256 entries staged into LDS,
-// one wave per 16x16 tile, four pixels per lane, the ballot over s_tiles gives list order.  On top of it every chunk cell has
-// three LDS accumulators.  Per visited entry a wave counts its covered pixels with four ballots, reduces its lanes' sums and
-// maxima across lanes (16-lane rows in 32 bits: a lane's sum is at most 2^26, a row's 2^30; the four row totals are added in 64
-// bits, since the wave's sum reaches 2^32 when every pixel has w = 1) and ONE lane updates the cell -- never 64 LDS atomics on
-// one address, which serialise.  After the chunk, thread t flushes cell t with three return-less global atomics, if any pixel
-// was covered: a splat occurs once in a bin's list, so global atomics number three per (bin, covering entry).
+// k_contrib walks a bin the way k_depth_walk.h's skeleton does (a 256-thread workgroup per bin, chunks of 256 entries staged into LDS,
+// one wave per 16x16 tile, four pixels per lane, the ballot over s_tiles gives list order) but keeps its own loop, as k_pick does, over
+// the skeleton's helpers: through walk_bin_list it measured 2.8 % longer (profiles/second_walk_ab.txt, section 6).  No barrier at the
+// loop's top: the one in front of the flush does that job, and a thread restages no cell but the one it flushes.  Every chunk cell has
+// three LDS accumulators.  Per visited entry a wave counts its covered pixels with four ballots, reduces its lanes' sums and maxima
+// across lanes (16-lane rows in 32 bits: a lane's sum is at most 2^26, a row's 2^30; the four row totals are added in 64 bits, since
+// the wave's sum reaches 2^32 when every pixel has w = 1) and ONE lane updates the cell -- never 64 LDS atomics on one address, which
+// serialise.  After the chunk, thread t flushes cell t with three return-less global atomics, if any pixel was covered: a splat
+// occurs once in a bin's list, so global atomics number three per (bin, covering entry).
 //
 // Compiled with -ffp-contract=off like the rest of the device code: the fused multiply-adds are the explicit ones.
 #include "k_depth_walk.h"
 
 namespace gsr {
 
-GSR_BOUNDS_DECL(contrib)   // sites: 0 bin -> bin_start, 1 list position, 2 splat index in the list, 3 LDS cell, 4 accumulator index,
-                           //        5 selection word
+GSR_BOUNDS_DECL(contrib)   // sites: 0 - 3 the walk's (WALK_SITE_*: 0 - 2 in its helpers, 3 here), 4 accumulator index, 5 selection word
+struct ContribBounds {
+    static __device__ __forceinline__ void bound(int site, unsigned long long idx, unsigned long long limit) { GSR_BOUND(contrib, site, idx, limit); }
+};
 constexpr int CONTRIB_SELECT_THREADS = 256;
 constexpr float CONTRIB_QUANTA = 16777216.0f;   // 2^24
 
@@ -54,24 +58,14 @@ __global__ __launch_bounds__(DEPTH_THREADS) void k_contrib(ContribBuffers a, Bin
     if (*a.overflow != 0u) return;
     if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_fetch_add(a.frames, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
-    const int nbxb = g.bx_hi - g.bx_lo;
-    const int bin = blockIdx.x;
-    GSR_BOUND(contrib, 0, bin, nbxb * g.nby);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lx = lane & 7, ly = lane >> 3;
-    const int by = bin / nbxb, bxl = bin - by * nbxb;
-    const int binX0 = (g.bx_lo + bxl) * BIN_PX, binY0 = by * BIN_PX;
-    const int ox = (wave & 1) * TILE, oy = (wave >> 1) * TILE;
-    const float pxf0 = (float)(ox + lx), pxf1 = pxf0 + 8.0f;
-    const float pyf0 = (float)(oy + ly), pyf1 = pyf0 + 8.0f;
-    const float bx0c = (float)binX0 + 0.5f, by0c = (float)binY0 + 0.5f;
+    const WalkBin w = walk_bin<ContribBounds>(a, g, blockIdx.x);
+    const int lane = w.lane, wave = w.wave;
+    const float pxf0 = (float)(w.ox + w.lx), pxf1 = pxf0 + 8.0f;
+    const float pyf0 = (float)(w.oy + w.ly), pyf1 = pyf0 + 8.0f;
     // the lane's pixels (x + 8i, y + 8j) that are pixels of the image: a partial last bin's other pixels have no fragments
-    const bool inx0 = binX0 + ox + lx < g.W, inx1 = binX0 + ox + lx + 8 < g.W;
-    const bool iny0 = binY0 + oy + ly < g.H, iny1 = binY0 + oy + ly + 8 < g.H;
-
-    const uint32_t end = min(a.bin_start[bin + 1], a.capacity), begin = min(a.bin_start[bin], end);
-    GSR_BOUND(contrib, 1, a.bin_start[bin + 1], (unsigned long long)a.capacity + 1ull);
-    GSR_BOUND(contrib, 1, a.bin_start[bin], (unsigned long long)a.bin_start[bin + 1] + 1ull);
+    const int x = w.binX0 + w.ox + w.lx, y = w.binY0 + w.oy + w.ly;
+    const bool inx0 = x < g.W, inx1 = x + 8 < g.W, iny0 = y < g.H, iny1 = y + 8 < g.H;
+    const uint32_t begin = w.begin, end = w.end;
 
     float T00 = 1.0f, T10 = 1.0f, T01 = 1.0f, T11 = 1.0f;   // Tij: pixel (x + 8i, y + 8j)
 
@@ -80,14 +74,12 @@ __global__ __launch_bounds__(DEPTH_THREADS) void k_contrib(ContribBuffers a, Bin
         const uint32_t e = base + threadIdx.x;
         uint32_t tiles = 0;
         if (e < end) {
-            GSR_BOUND(contrib, 1, e, a.capacity);
-            GSR_BOUND(contrib, 2, a.list[e], a.nsplats);
-            const uint32_t i = min(a.list[e], a.nsplats - 1u);
-            const DepthEntry en = depth_entry(a.rec, a.px, a.py, a.pz, i, cam, bx0c, by0c);
+            const uint32_t i = walk_list_entry<ContribBounds>(a, e);
+            const DepthEntry en = depth_entry(a.rec, a.px, a.py, a.pz, i, cam, w.bx0c, w.by0c);
             s_a[threadIdx.x] = make_float4(en.ux, en.uy, en.ncu, en.wx);
             s_b[threadIdx.x] = make_float4(en.wy, en.ncw, en.la, 0.0f);
             s_idx[threadIdx.x] = en.index;
-            tiles = SKIP ? depth_tile_reach(en, a.rec + i, binX0, binY0) : 0xfu;
+            tiles = SKIP ? depth_tile_reach(en, a.rec[i].cx, a.rec[i].cy, w.binX0, w.binY0) : 0xfu;
         }
         s_tiles[threadIdx.x] = tiles;
         s_sum[threadIdx.x] = 0ull; s_cnt[threadIdx.x] = 0u; s_peak[threadIdx.x] = 0u;
@@ -100,7 +92,7 @@ __global__ __launch_bounds__(DEPTH_THREADS) void k_contrib(ContribBuffers a, Bin
             while (bal) {
                 const uint32_t cell = c0 + (uint32_t)__builtin_ctzll(bal);
                 bal &= bal - 1ull;
-                GSR_BOUND(contrib, 3, cell, DEPTH_CHUNK);
+                GSR_BOUND(contrib, WALK_SITE_CELL, cell, DEPTH_CHUNK);
                 const float4 ra = s_a[cell], rb = s_b[cell];   // the same address in every lane: a broadcast
                 DepthEntry en;
                 en.ux = ra.x; en.uy = ra.y; en.ncu = ra.z; en.wx = ra.w; en.wy = rb.x; en.ncw = rb.y; en.la = rb.z; en.z = 0.0f;
@@ -177,11 +169,7 @@ __global__ __launch_bounds__(CONTRIB_SELECT_THREADS) void k_contrib_select(int s
 
 void launch_contrib(const ContribBuffers& b, const BinGrid& g, const CamParams& cam, bool skip, hipStream_t s)
 {
-    const int nbins = (g.bx_hi - g.bx_lo) * g.nby;
-    if (nbins <= 0) return;
-    const dim3 grid(nbins), block(DEPTH_THREADS);
-    if (skip) hipLaunchKernelGGL((k_contrib<true>), grid, block, 0, s, b, g, cam);
-    else hipLaunchKernelGGL((k_contrib<false>), grid, block, 0, s, b, g, cam);
+    walk_launch(skip ? k_contrib<true> : k_contrib<false>, b, g, cam, s);
 }
 
 void launch_contrib_select(int stat, double below, uint32_t n, const unsigned long long* weight, const uint32_t* peak, const uint32_t* pixels,

@@ -6,6 +6,8 @@ import os
 import re
 import subprocess
 
+from walk_source import walk_is_stated_once, walk_sites_are_checked
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "gsplat_hip.h")
 CSRC = os.path.join(ROOT, "gsplat.js_amd", "csrc")
@@ -75,20 +77,13 @@ def test_sources_are_wired_into_every_build():
     assert "make" in exp and "OUT=../lib_exp/$name" in exp
     src = open(os.path.join(CSRC, "k_contrib.hip")).read()
     assert "GSR_BOUNDS_DECL(contrib)" in src
-    for site in range(6):                                               # bin, list position, splat index, LDS cell, accumulator index, selection word
+    walk_sites_are_checked(src, "contrib", "ContribBounds", None)   # bin, list position, splat index: in the walk's helpers; LDS cell: in the unit's own loop
+    for site in (4, 5):                                                 # accumulator index, selection word: the unit's own
         assert re.search(r"GSR_BOUND\(contrib, %d," % site, src), site
 
 
 def test_the_walk_arithmetic_is_stated_once():
-    walk = open(os.path.join(CSRC, "k_depth_walk.h")).read()
-    for fn in ("struct DepthEntry", "DepthEntry depth_entry(", "float depth_weight(", "float depth_row_u(", "float depth_row_w(", "uint32_t depth_tile_reach("):
-        assert fn in walk, fn
-    for name in ("k_depth.hip", "k_contrib.hip"):
-        src = open(os.path.join(CSRC, name)).read()
-        assert '#include "k_depth_walk.h"' in src, name
-        for fn in ("depth_entry(", "depth_weight(", "depth_row_u(", "depth_row_w(", "depth_tile_reach("):
-            assert fn in src, (name, fn)
-        assert "exp2f" not in src and "struct DepthEntry" not in src, name          # used, never restated
+    walk_is_stated_once()
     src = open(os.path.join(CSRC, "k_contrib.hip")).read()
     assert "asm" not in re.sub(r"//.*", "", src)                         # vector stores and HIP atomics only
     for word in ("__hip_atomic_fetch_add", "__hip_atomic_fetch_max", "__HIP_MEMORY_SCOPE_AGENT", "__ATOMIC_RELAXED", "__shfl_xor", "rintf("):

@@ -125,3 +125,12 @@ def test_knob_and_kernels_are_in_the_library():
     out = subprocess.run(["strings", "-a", gh.LIB_PATH], capture_output=True, text=True).stdout
     for s in ("k_depth_planes", "k_pick", "GSR_DEPTH_SKIP"):
         assert s in out, s
+
+
+def test_depth_unit_instantiates_the_walk_and_keeps_its_check_sites():
+    from walk_source import CSRC, walk_sites_are_checked
+    src = open(os.path.join(CSRC, "k_depth.hip")).read()
+    assert "GSR_BOUNDS_DECL(depth)" in src
+    walk_sites_are_checked(src, "depth", "DepthBounds", "DepthPass")    # bin, list position, splat index, LDS cell: in the walk the unit instantiates
+    for site in (4, 5):                                                 # query pixel, sample of a strided hit plane: the unit's own
+        assert re.search(r"GSR_BOUND\(depth, %d," % site, src), site

@@ -9,7 +9,9 @@ import os
 import numpy as np
 import pytest
 
+import blend_reference as BR
 import depth_reference as DR
+from test_oracle_render import make_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -46,14 +48,24 @@ class Ref:
 
     def __init__(self, oracle, gh, name, data, pos, k, hit_alpha=0.5, fade=None):
         cfg = gh.synth.CONFIGS[name]
-        self.W, self.H = cfg["width"], cfg["height"]
-        cam = _cam(gh, name, k)
+        self.evaluate(oracle, _cam(gh, name, k), data, pos, cfg["width"], cfg["height"], _window(name, gh), hit_alpha, fade)
+
+    @classmethod
+    def of_scene(cls, oracle, cam, data, pos, W, H, hit_alpha):
+        """the reference of a scene that is no named configuration, over the whole W x H image"""
+        ref = cls.__new__(cls)
+        ref.cam, ref.data, ref.pos = cam, data, pos
+        ref.evaluate(oracle, cam, data, pos, W, H, (0, 0, W, H), hit_alpha)
+        return ref
+
+    def evaluate(self, oracle, cam, data, pos, W, H, window, hit_alpha, fade=None):
+        self.W, self.H = W, H
         v, p, vp = cam.f32()
         kw = {} if fade is None else {"fade": fade}
         self.rec, self.bbox, raw = oracle.project(data, v, p, cam.fx, cam.fy, self.W, self.H, **kw)
         self.z = np.ascontiguousarray(raw[:, 10])
         self.order = oracle.sort(vp, pos)[0]
-        self.window = _window(name, gh)
+        self.window = window
         self.planes = DR.depth_planes_reference(self.rec, self.bbox, self.z, self.order, self.W, self.H, self.window, hit_alpha)
         vis = (self.bbox[:, 0] <= self.bbox[:, 2]) & (self.bbox[:, 1] <= self.bbox[:, 3])
         self.zmin, self.zmax = float(self.z[vis].min()), float(self.z[vis].max())
@@ -265,11 +277,8 @@ def test_hit_alpha(gh, monkeypatch, scenes, refs):
 
 
 # 8 -------------------------------------------------------------------------------------------------------------------
-def _pick_equals_planes(gh, r, planes, seed=8):
-    W, H = r.width, r.height
-    rng = np.random.default_rng(seed)
-    pts = np.stack([rng.integers(0, W, 512), rng.integers(0, H, 512)], axis=1)
-    pts = np.concatenate([pts, [(0, 0), (W - 1, 0), (0, H - 1), (W - 1, H - 1)]])
+def _pick_at(r, planes, pts):
+    pts = np.asarray(pts)
     res = r.pick(pts)
     mean, hit, index = planes
     ys, xs = pts[:, 1], pts[:, 0]
@@ -277,6 +286,15 @@ def _pick_equals_planes(gh, r, planes, seed=8):
     assert np.array_equal(res["depth"].view(np.uint32), hit[ys, xs].view(np.uint32))
     assert np.array_equal(res["mean"].view(np.uint32), mean[ys, xs].view(np.uint32))
     assert np.abs(res["alpha"].astype(np.float64) - r.readPixelsFloat()[ys, xs, 3]).max() <= 2e-6
+    return res
+
+
+def _pick_equals_planes(gh, r, planes, seed=8):
+    W, H = r.width, r.height
+    rng = np.random.default_rng(seed)
+    pts = np.stack([rng.integers(0, W, 512), rng.integers(0, H, 512)], axis=1)
+    pts = np.concatenate([pts, [(0, 0), (W - 1, 0), (0, H - 1), (W - 1, H - 1)]])
+    res = _pick_at(r, planes, pts)
     assert (res["index"] != NONE).any()
     return res
 
@@ -391,3 +409,70 @@ def test_skip_changes_no_bit(gh, monkeypatch, scenes):
         assert (got[0][2] != NONE).any()
         for a, b in zip(*got):
             assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), name
+
+
+# 11 ------------------------------------------------------------------------------------------------------------------
+# The walk at its chunk edges (chunks of 256 entries): L - 1 faint co-located splats over the whole 96 x 96 frame (3 x 3 bins) and one
+# opaque splat behind them, so that every bin's list has exactly L entries, every entry adds a term to the mean plane and, at
+# hit_alpha 0.9, the only possible hit is the list's last entry.  (At 0.5 the reference's own knife-edge mask is 4.6 % to 15.8 %
+# of these frames; at 0.9 it is at most 0.0009, far inside the 1 % Ref.check allows.)
+STACK_LENGTHS = (1, 255, 256, 257, 512, 513)
+STACK_HIT_ALPHA = 0.9
+
+
+@pytest.fixture(scope="module")
+def stack_refs(oracle):
+    """length -> the scene and its reference planes: computed once, shared with the bounds twin, dropped with the module"""
+    cache = {}
+
+    def get(length):
+        if length not in cache:
+            W, H = BR.STACK_FRAME
+            cam, to_world = BR.front_view(W, H)
+            splats = BR.stack(to_world, 48, 48, length - 1, 100.0, (90, 160, 220, 1)) + BR.stack(to_world, 48, 48, 1, 100.0, (255, 230, 40, 255), dz0=1.0)
+            cache[length] = Ref.of_scene(oracle, cam, *make_scene(oracle, splats), W, H, STACK_HIT_ALPHA)
+            assert np.array_equal(cache[length].order, np.arange(length))
+        return cache[length]
+
+    yield get
+    cache.clear()
+
+
+def _stack_at_the_chunk_edges(gh, ref, monkeypatch, length, lib_path=None):
+    W, H = BR.STACK_FRAME
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    kw = {} if lib_path is None else {"lib_path": lib_path}
+    r = gh.HIPRenderer(W, H, **kw)
+    r.set_raw_scene(ref.data, ref.pos)
+    r.set_hit_alpha(STACK_HIT_ALPHA)
+    r.set_camera(ref.cam)
+    r.render_async()
+    r.sync()
+    assert r.stats()["bin_entries"] == 9 * length and r.stats()["overflow_frames"] == 0
+    planes = r.read_depth()
+    ref.check(planes, ("stack", length, lib_path is not None))
+    mean, hit, index = planes
+    assert (index == length - 1).any() and np.all((index == length - 1) | (index == NONE) | ref.planes["mask"])
+    # pick: the centre, a corner and one pixel of each bin
+    _pick_at(r, planes, [(48, 48), (W - 1, 0)] + [(32 * bx + 5 + 7 * by, 32 * by + 11 + 6 * bx) for by in range(3) for bx in range(3)])
+    # the strided pass: the samples of a depth ring (f32, step 2) are the hit plane at (2i, 2j)
+    r.open_delivery_depth(2, depth="f32", depth_step=2)
+    r.render_async()
+    s, _, depth = r.acquire(r.deliver())
+    want = np.ascontiguousarray(hit[::2, ::2])
+    assert depth.shape == want.shape and np.array_equal(depth.view(np.uint32), want.view(np.uint32)), (length, "strided pass")
+    r.release(s)
+    r.close_delivery()
+    return r
+
+
+@pytest.mark.parametrize("length", STACK_LENGTHS)
+def test_depth_at_the_chunk_edges(gh, stack_refs, monkeypatch, length):
+    ref = stack_refs(length)
+    _stack_at_the_chunk_edges(gh, ref, monkeypatch, length).dispose()
+    if length in (256, 257):
+        assert os.path.exists(BOUNDS_LIB), "the bounds-checked build is missing: run python -c 'import __graft_entry__ as g; g.build()'"
+        r = _stack_at_the_chunk_edges(gh, ref, monkeypatch, length, lib_path=BOUNDS_LIB)
+        _bounds_zero(r, ("bounds", "stack", length))
+        r.dispose()

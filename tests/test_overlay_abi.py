@@ -6,6 +6,8 @@ import os
 import re
 import subprocess
 
+from walk_source import walk_is_stated_once, walk_sites_are_checked
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "gsplat_hip.h")
 CSRC = os.path.join(ROOT, "gsplat.js_amd", "csrc")
@@ -85,8 +87,10 @@ def test_sources_are_wired_into_every_build():
     assert '"bounds", "-DGSR_BOUNDS"' in entry and '"cppwalk", "-DGSR_CPP_WALK"' in entry
     src = open(os.path.join(CSRC, "k_overlay.hip")).read()
     assert "GSR_BOUNDS_DECL(overlay)" in src
-    for site in range(6):                                               # bin, list position, splat index, mask word, LDS cell, pixel
+    walk_sites_are_checked(src, "overlay", "OverlayBounds", "OverlayPass")   # bin, list position, splat index, LDS cell: in the walk the unit instantiates
+    for site in (4, 5):                                                 # mask word, pixel: the unit's own
         assert re.search(r"GSR_BOUND\(overlay, %d," % site, src), site
+    assert "walk_list_entry<OverlayBounds>(a, e)" in src                # the TRIM pass over the list reads it through the same checks
     api = open(os.path.join(CSRC, "gsr_api.cpp")).read()
     assert 'getenv("GSR_OVERLAY_TRIM")' in api and 'getenv("GSR_DEPTH_SKIP")' in api       # read once, where a context is created
 
@@ -94,8 +98,9 @@ def test_sources_are_wired_into_every_build():
 def test_the_walk_arithmetic_is_shared_and_the_frame_chain_is_not_touched():
     src = open(os.path.join(CSRC, "k_overlay.hip")).read()
     assert '#include "k_depth_walk.h"' in src
-    for fn in ("depth_entry(", "depth_weight(", "depth_row_u(", "depth_row_w(", "depth_tile_reach("):
+    for fn in ("depth_weight(", "depth_row_u(", "depth_row_w(", "walk_bin_list<SKIP>(st, a, w, cam, w.begin, end, pass)", "walk_frame_unfit(a.overflow, a.invalid)"):
         assert fn in src, fn
+    walk_is_stated_once()                           # depth_entry and depth_tile_reach: in the walk's skeleton, for all three units
     assert "exp2f" not in src and "struct DepthEntry" not in src        # used, never restated
     code = re.sub(r"//.*", "", src)
     assert "asm" not in code  and "atomicAdd" not in code         # plain vector stores; the one LDS maximum is a HIP atomic
