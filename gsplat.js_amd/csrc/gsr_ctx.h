@@ -536,6 +536,9 @@ int scene_compact(gsr_ctx* c, const ScenePred& p, const char* what, uint32_t* ke
 int edit_begin(gsr_ctx* c);
 int edit_end(gsr_ctx* c);
 void invalidate_members(gsr_ctx* c, bool lists);
+// GSR_ERR_ARG with the message unless the scene carries rotations and scales (built from rows or from the four arrays): what the
+// transforms, the compactions and the edits of the selection all demand first
+int require_rows(gsr_ctx* c);
 // gsr_hidden.cpp: the hidden set's buffers for the scene's count, allocated (the mask zeroed) by the first call that needs them
 int hidden_ensure(gsr_ctx* c);
 // gsr_select.cpp: the selection's buffers for the scene's count, allocated (the mask zeroed) by the first call that needs them; and

@@ -482,6 +482,22 @@ void launch_select_box(uint32_t n, const float* px, const float* py, const float
 // sel <- sel (op) scratch, bits at and above n dropped; *count <- the bits set afterwards (block_sums: ceil(nwords / SELECT_APPLY_THREADS) words)
 void launch_select_apply(int op, uint32_t* sel, const uint32_t* scratch, uint32_t n, uint32_t nwords, uint32_t* block_sums, uint32_t* count, hipStream_t s);
 
+// Editing the selection (k_edit.hip; DESIGN.md section 4, "Editing the selection"): Scene.translate / rotate / scale on the splats
+// whose bit of `words` (nwords of them, the selection's layout) is set, as a Scene holding only them would be left; no other splat
+// is written.  pivot (3 f64, may be null): translate(-pivot), the operation, translate(+pivot), each step rounded to f32 as the
+// reference's stores round, fused into one read and one write per selected splat.
+void launch_edit_translate(uint32_t n, const SceneDev& sc, const uint32_t* words, uint32_t nwords, const double* t, hipStream_t s);
+void launch_edit_rotate(uint32_t n, const SceneDev& sc, const uint32_t* words, uint32_t nwords, const double* q_xyzw, const double* pivot, hipStream_t s);
+void launch_edit_scale(uint32_t n, const SceneDev& sc, const uint32_t* words, uint32_t nwords, const double* sv, const double* pivot, hipStream_t s);
+// rgba[i] = (rgba[i] & ~byte_mask) | (rgba & byte_mask) for the selected i
+void launch_edit_rgba(uint32_t n, const SceneDev& sc, const uint32_t* words, uint32_t nwords, uint32_t rgba, uint32_t byte_mask, hipStream_t s);
+// The selected splats' count and the box of their centres: out[0] = count, out[1..3] = min, out[4..6] = max (f32 bits), out[7] = 0.
+// partial: edit_bounds_blocks(n) x EDIT_PARTIAL_WORDS words of scratch; out: EDIT_PARTIAL_WORDS words.  n >= 1.
+constexpr uint32_t EDIT_PARTIAL_WORDS = 8;
+uint32_t edit_bounds_blocks(uint32_t n);
+void launch_edit_bounds(uint32_t n, const float* px, const float* py, const float* pz, const uint32_t* words, uint32_t nwords, uint32_t* partial,
+                        uint32_t* out, hipStream_t s);
+
 // Contribution (k_contrib.hip; DESIGN.md section 4, "Contribution"): the last frame's bin lists walked once more, the weight
 // w = T * B of every fragment kept per SPLAT and summed over pixels and passes into three accumulators held with the scene.
 struct ContribBuffers : FrameLists {   // (a frame that did not fit is neither walked nor counted)

@@ -47,6 +47,13 @@ int sync_members(gsr_ctx* c)
 
 }  // namespace
 
+// what every transform, compaction and edit of the selection demands of the scene: rotations and scales (the one statement of the refusal)
+int gsr::require_rows(gsr_ctx* c)
+{
+    if (!c->scene->have_rows) return fail(c, GSR_ERR_ARG, "scene transforms need a scene built with gsr_set_scene_rows or gsr_set_scene_arrays");
+    return GSR_OK;
+}
+
 // the other members' frame state after an edit that arrived through `c`: as if each had run the call itself
 void gsr::invalidate_members(gsr_ctx* c, bool lists)
 {
@@ -129,7 +136,7 @@ namespace {
 
 int need_rows(gsr_ctx* c)
 {
-    if (!c->scene->have_rows) return fail(c, GSR_ERR_ARG, "scene transforms need a scene built with gsr_set_scene_rows or gsr_set_scene_arrays");
+    if (int r = require_rows(c)) return r;
     HIP_TRY(c, hipSetDevice(c->device));
     invalidate_members(c, true);
     return GSR_OK;

@@ -174,7 +174,7 @@ int gsr_scene_erase_selected(gsr_ctx* c, int32_t keep_selected, uint32_t* new_co
 {
     if (!c) return GSR_ERR_ARG;
     SharedScene& sc = *c->scene;
-    if (!sc.have_rows) return fail(c, GSR_ERR_ARG, "scene transforms need a scene built with gsr_set_scene_rows or gsr_set_scene_arrays");
+    if (int r = require_rows(c)) return r;
     const uint32_t n = sc.n, count = sc.sel.mask ? sc.sel.count : 0u;
     // nothing to remove: nothing changes, the last frame stays valid (the count is the one the last fold left: every call is blocking)
     if (!n || (keep_selected ? count == n : count == 0u)) {

@@ -140,23 +140,32 @@ class Scene extends EventDispatcher {
     }
 
     // kind: 0 translate (x, y, z), 1 rotate (x, y, z, w), 2 scale (x, y, z), 3 limitBox (xMin, xMax, yMin, yMax, zMin, zMax),
-    // 4 eraseSelection ({ mask, keep }: the mask is set on the device copy, then erased there).
+    // 4 eraseSelection ({ mask, keep }: the mask is set on the device copy, then erased there),
+    // 5 translateSelection, 6 rotateSelection, 7 scaleSelection ({ mask, values, pivot }), 8 paintSelection ({ mask, rgba, byteMask }):
+    // the mask is set on the device copy, then the splats it selects are edited there.
     // false: the edit has to run here (nothing attached, a host-only device scene among them, or buffers set by hand).
     _editDevices(kind, args) {
         // (a device scene that cannot follow SH -- no setShFollow / readSh -- counts as host-only while the option is on; so does
         //  one that cannot take a selection -- no setSelection / eraseSelected -- for an eraseSelection)
         const cannotFollow = this._shFollowsTransforms && this._devices.some((d) => !d.setShFollow || !d.readSh);
         const cannotErase = kind === 4 && this._devices.some((d) => !d.setSelection || !d.eraseSelected);
-        if (!this._devices.length || this._diverged || cannotFollow || cannotErase || this._devices.some((d) => d.hostOnly)) {
+        const cannotEdit = kind >= 5 && this._devices.some((d) => !d.setSelection || !d.editSelected || !d.paintSelected);
+        if (!this._devices.length || this._diverged || cannotFollow || cannotErase || cannotEdit || this._devices.some((d) => d.hostOnly)) {
             this._refresh();
             this._refreshSh();
             return false;
         }
-        const f = kind === 4 ? null : new Float64Array(args);
+        const f = kind >= 4 ? null : new Float64Array(args);
         let count = -1;
         for (const d of this._distinctDevices()) {
             let c;
             if (kind === 4) { d.setSelection(args.mask); c = d.eraseSelected(args.keep); }
+            else if (kind >= 5) {   // the mask first, then the edit of what it selects; the count stays
+                d.setSelection(args.mask);
+                if (kind === 8) d.paintSelected(args.rgba, args.byteMask);
+                else d.editSelected(kind - 5, new Float64Array(args.values), args.pivot ? new Float64Array(args.pivot) : null);
+                c = this._vertexCount;
+            }
             else c = d.transform(kind, f);
             if (count >= 0 && c !== count) throw new Error("device scenes disagree on vertexCount (" + count + " and " + c + ")");
             count = c;
@@ -189,6 +198,35 @@ class Scene extends EventDispatcher {
         f[8 * i] = this._positions[3 * i];
         f[8 * i + 1] = this._positions[3 * i + 1];
         f[8 * i + 2] = this._positions[3 * i + 2];
+    }
+
+    // One splat of translate / rotate / scale (Scene.ts:182-305), for the selection's edits below: the bodies of the whole-scene
+    // loops, which stay exactly as they were.  Held to the same reference bit for bit by tests/test_edit_binding.py.
+    // R: Matrix3.RotationFromQuaternion(rotation).buffer; f: [sx, sy, sz].
+    _translateOne(i, x, y, z) {
+        this._positions[3 * i] += x;
+        this._positions[3 * i + 1] += y;
+        this._positions[3 * i + 2] += z;
+        this._writePosition(i);
+    }
+    _rotateOne(i, R, rotation) {
+        const p = this._positions, r = this._rotations;
+        const x = p[3 * i], y = p[3 * i + 1], z = p[3 * i + 2];
+        p[3 * i] = R[0] * x + R[1] * y + R[2] * z;
+        p[3 * i + 1] = R[3] * x + R[4] * y + R[5] * z;
+        p[3 * i + 2] = R[6] * x + R[7] * y + R[8] * z;
+        this._writePosition(i);
+        const q = rotation.multiply(new Quaternion(r[4 * i + 1], r[4 * i + 2], r[4 * i + 3], r[4 * i]));
+        r[4 * i + 1] = q.x; r[4 * i + 2] = q.y; r[4 * i + 3] = q.z; r[4 * i] = q.w;
+        this._packCovariance(i);
+    }
+    _scaleOne(i, f) {
+        for (let k = 0; k < 3; k++) {
+            this._positions[3 * i + k] *= f[k];
+            this._scales[3 * i + k] *= f[k];
+        }
+        this._writePosition(i);
+        this._packCovariance(i);
     }
 
     // data: Uint8Array of 32-byte rows [pos f32x3 | scale f32x3 | rgba u8x4 | rot u8x4 (w,x,y,z)].
@@ -304,6 +342,68 @@ class Scene extends EventDispatcher {
         if (this._editDevices(4, { mask: mask, keep: keep, removes: kept < n })) return;
         if (kept < n) this._compact((i) => bit(i) === want);
         else this.dispatchEvent({ type: "change" });
+    }
+
+    // ---- editing a selection: translate, rotate, scale and recolour the splats whose bit of `mask` is set, and nothing else ----
+    // The result is what translate / rotate / scale would leave in a Scene that held only those splats; with { pivot } (a
+    // Vector3 or [x, y, z]) the operation is the three steps translate(-pivot), the operation, translate(+pivot) on them, each
+    // rounded to f32 by the arrays it is stored into.  While device scenes are attached the mask is set on every distinct device
+    // copy and the edit runs there (gsr_selection_set, gsr_scene_*_selected); otherwise the loops run here over the masked
+    // indices.  Fires "change".  rotateSelection / scaleSelection throw while shFollowsTransforms is on and the scene has SH rows:
+    // the SH frame is one per scene, and a partial rotation has none.
+    _selectionArgs(what, mask, options, linear) {
+        const n = this._vertexCount, words = Math.ceil(n / 32);
+        if (!(mask instanceof Uint32Array) || mask.length < words) throw new Error(what + ": mask must be a Uint32Array of at least " + words + " words");
+        if (linear && this._shFollowsTransforms && this.shHeight > 0)
+            throw new Error(what + ": with shFollowsTransforms on and SH rows present a selection cannot be rotated or scaled (the SH frame is one per scene)");
+        const p = options && options.pivot;
+        return p ? (Array.isArray(p) || ArrayBuffer.isView(p) ? [p[0], p[1], p[2]] : [p.x, p.y, p.z]) : null;
+    }
+    // the host loop of an edit: `one(i)` on the masked splats, between the two translate steps when there is a pivot
+    _editMasked(mask, pivot, one) {
+        const n = this._vertexCount, bit = (i) => (mask[i >>> 5] >>> (i & 31)) & 1;
+        if (pivot) for (let i = 0; i < n; i++) if (bit(i)) this._translateOne(i, -pivot[0], -pivot[1], -pivot[2]);
+        for (let i = 0; i < n; i++) if (bit(i)) one(i);
+        if (pivot) for (let i = 0; i < n; i++) if (bit(i)) this._translateOne(i, pivot[0], pivot[1], pivot[2]);
+        this.dispatchEvent({ type: "change" });
+    }
+    translateSelection(mask, v) {
+        this._selectionArgs("translateSelection", mask, null, false);
+        if (this._editDevices(5, { mask: mask, values: [v.x, v.y, v.z], pivot: null })) return;
+        this._editMasked(mask, null, (i) => this._translateOne(i, v.x, v.y, v.z));
+    }
+    rotateSelection(mask, q, options) {
+        const pivot = this._selectionArgs("rotateSelection", mask, options, true);
+        if (this._editDevices(6, { mask: mask, values: [q.x, q.y, q.z, q.w], pivot: pivot })) return;
+        const R = Matrix3.RotationFromQuaternion(q).buffer;
+        this._editMasked(mask, pivot, (i) => this._rotateOne(i, R, q));
+    }
+    scaleSelection(mask, s, options) {
+        const pivot = this._selectionArgs("scaleSelection", mask, options, true), f = [s.x, s.y, s.z];
+        for (const v of f) if (!Number.isFinite(v)) throw new Error("scaleSelection: scale component " + v + " must be finite");
+        if (this._editDevices(7, { mask: mask, values: f, pivot: pivot })) return;
+        this._editMasked(mask, pivot, (i) => this._scaleOne(i, f));
+    }
+    // rgba: { r, g, b, a } bytes 0..255; absent channels are left alone.  The word is data[8i + 7]: r, g, b in the low three bytes,
+    // opacity in the top one (splats that take their colour from SH show only the opacity).
+    paintSelection(mask, rgba) {
+        this._selectionArgs("paintSelection", mask, null, false);
+        const [value, byteMask] = Scene.rgbaWord(rgba);
+        if (this._editDevices(8, { mask: mask, rgba: value, byteMask: byteMask })) return;
+        const d = this._data;
+        this._editMasked(mask, null, (i) => { d[8 * i + 7] = (d[8 * i + 7] & ~byteMask) | value; });
+    }
+    // { r, g, b, a } -> [word with the present channels' bytes, mask of their bytes]
+    static rgbaWord(rgba) {
+        let value = 0, byteMask = 0;
+        ["r", "g", "b", "a"].forEach((ch, k) => {
+            const v = rgba ? rgba[ch] : undefined;
+            if (v === undefined || v === null) return;
+            if (!Number.isInteger(v) || v < 0 || v > 255) throw new Error("paintSelection: " + ch + " must be an integer in 0..255");
+            value |= v << (8 * k);
+            byteMask |= 0xff << (8 * k);
+        });
+        return [value >>> 0, byteMask >>> 0];
     }
 
     // Hide the splats whose bit of `mask` is set (the layout of the renderer's readHidden() / readSelection()); null shows all.

@@ -72,7 +72,17 @@ export interface DeviceScene {
     /** optional: Scene.setHidden sets its mask (the selection's layout; null: nothing hidden) as the device copy's hidden set and
      *  returns the number of hidden splats.  Scene.setHidden throws when an attached device scene has none. */
     setHidden?(words: Uint32Array | null): number;
+    /** optional, the two together with setSelection: Scene.translateSelection / rotateSelection / scaleSelection / paintSelection set
+     *  their mask as the device copy's selection, then have the copy edit the selected splats.  kind 0 translate (x, y, z), 1 rotate
+     *  (x, y, z, w), 2 scale (x, y, z); pivot (x, y, z) or null.  A device scene without them is treated like a host-only one for
+     *  these edits. */
+    editSelected?(kind: number, args: Float64Array, pivot: Float64Array | null): void;
+    paintSelected?(rgba: number, byteMask: number): void;
 }
+/** Bytes 0..255; absent channels are left alone. */
+export interface PaintChannels { r?: number; g?: number; b?: number; a?: number }
+export type Vec3Like = Vector3 | [number, number, number] | Float64Array | Float32Array;
+export interface SelectionBounds { count: number; min: Float32Array; max: Float32Array }
 export type SelectMode = "centre" | "hit";
 export type SelectOp = "replace" | "add" | "subtract" | "intersect";
 export type ContribStat = "weight" | "peak" | "pixels";
@@ -101,6 +111,17 @@ export class Scene {
      *  change and no "change" fires.  Throws when no renderer holds the scene, when the copies are behind the arrays, or when a
      *  device scene cannot take it.  Returns the number of hidden splats. */
     setHidden(mask: Uint32Array | null): number;
+    /** Edit the splats whose bit of `mask` is set (HIPRenderer.readSelection()'s layout) and nothing else: what translate / rotate /
+     *  scale would leave in a Scene holding only them.  { pivot }: translate(-pivot), the operation, translate(+pivot) on them, each
+     *  step rounded to f32.  While device scenes are attached the mask is set on every distinct device copy and the edit runs
+     *  there; otherwise the loops run here over the masked indices.  Fires "change".  rotateSelection / scaleSelection throw while
+     *  shFollowsTransforms is on and the scene has SH rows. */
+    translateSelection(mask: Uint32Array, v: Vector3): void;
+    rotateSelection(mask: Uint32Array, q: Quaternion, options?: { pivot?: Vec3Like }): void;
+    scaleSelection(mask: Uint32Array, s: Vector3, options?: { pivot?: Vec3Like }): void;
+    /** data[8i + 7] of the masked splats: r, g, b in the low three bytes, opacity in the top one; absent channels are left alone */
+    paintSelection(mask: Uint32Array, rgba: PaintChannels): void;
+    static rgbaWord(rgba: PaintChannels): [number, number];
     saveToFile(name: string): void;
     toSplatBytes(): Uint8Array;
     data: Uint32Array; vertexCount: number; width: number; height: number;
@@ -283,6 +304,18 @@ export class HIPRenderer {
     /** ceil(vertexCount / 32) words: splat i is bit i & 31 of word i >>> 5 */
     readHidden(): Uint32Array;
     selectHidden(options?: { op?: SelectOp }): number;
+    /** Editing the selection on THIS renderer's device copy (a Scene attached to it does not learn of it: Scene.translateSelection
+     *  and its kin edit every copy and the Scene's arrays).  selectionBounds: the selected splats' count and the box of their centres
+     *  (nothing selected: 0, +Infinity, -Infinity; a NaN coordinate is counted and never enters the box).  The edits leave what
+     *  Scene.translate / rotate / scale would leave in a Scene holding only the selected splats; { pivot }: translate(-pivot), the
+     *  operation, translate(+pivot).  paintSelection writes the given channels' bytes.  Each is a scene edit: pick, selectRegion and
+     *  readDepth need a new frame; selection, hidden set and contribution state stay.  rotate / scale throw while SH follows the
+     *  transforms and the scene has SH rows. */
+    selectionBounds(): SelectionBounds;
+    translateSelection(v: Vec3Like): void;
+    rotateSelection(q: Quaternion | [number, number, number, number] | Float64Array, options?: { pivot?: Vec3Like }): void;
+    scaleSelection(s: Vec3Like, options?: { pivot?: Vec3Like }): void;
+    paintSelection(rgba: PaintChannels): void;
     /** Contribution: per splat of the device scene (renderers that share a scene have one set together), what it showed over the
      *  frames of a tour.  resetContribution zeroes the accumulators (blocking); accumulateContribution enqueues the pass behind the
      *  frame rendered last (no wait; a frame whose lists did not fit adds nothing); readContribution returns weight (sum of the

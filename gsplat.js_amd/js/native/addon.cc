@@ -1150,6 +1150,59 @@ napi_value SelectHidden(napi_env env, napi_callback_info info)
     return rc ? throw_gsr(env, c, rc, "gsr_select_hidden") : count_value(env, count);
 }
 
+// ---- editing the selection (gsr_selection_bounds, gsr_scene_*_selected) ----
+// selectionBounds(handle, Float32Array(6) out: min xyz, max xyz) -> count
+napi_value SelectionBounds(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    void* out;
+    size_t len;
+    if (!c || !get_typed(env, argv[1], napi_float32_array, &out, &len)) return nullptr;
+    if (len < 6) { napi_throw_range_error(env, nullptr, "the box has 6 entries"); return nullptr; }
+    struct gsr_selection_bounds b;
+    const int rc = gsr_selection_bounds(c, &b);
+    if (rc) return throw_gsr(env, c, rc, "gsr_selection_bounds");
+    for (int k = 0; k < 3; k++) { ((float*)out)[k] = b.min[k]; ((float*)out)[3 + k] = b.max[k]; }
+    return count_value(env, b.count);
+}
+
+// editSelected(handle, kind, Float64Array args, Float64Array pivot | null): kind 0 translate (3), 1 rotate (4: x, y, z, w), 2 scale (3)
+napi_value EditSelected(napi_env env, napi_callback_info info)
+{
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    int32_t kind;
+    void *args, *pivot;
+    size_t len, plen;
+    if (!c || !get_i32(env, argv[1], &kind) || !get_typed(env, argv[2], napi_float64_array, &args, &len) ||
+        !get_typed(env, argv[3], napi_float64_array, &pivot, &plen, true))
+        return nullptr;
+    if (kind < 0 || kind > 2 || len < (kind == 1 ? 4u : 3u) || (pivot && plen < 3)) {
+        napi_throw_range_error(env, nullptr, "editSelected: kind 0..2, 3 (rotate: 4) values, a pivot of 3");
+        return nullptr;
+    }
+    const int rc = kind == 0 ? gsr_scene_translate_selected(c, (const double*)args)
+                 : kind == 1 ? gsr_scene_rotate_selected(c, (const double*)args, (const double*)pivot)
+                             : gsr_scene_scale_selected(c, (const double*)args, (const double*)pivot);
+    return rc ? throw_gsr(env, c, rc, kind == 0 ? "gsr_scene_translate_selected" : kind == 1 ? "gsr_scene_rotate_selected" : "gsr_scene_scale_selected")
+              : undefined(env);
+}
+
+// paintSelected(handle, rgba, byteMask)
+napi_value PaintSelected(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    uint32_t rgba, mask;
+    if (!c || napi_get_value_uint32(env, argv[1], &rgba) != napi_ok || napi_get_value_uint32(env, argv[2], &mask) != napi_ok) return nullptr;
+    const int rc = gsr_scene_set_rgba_selected(c, rgba, mask);
+    return rc ? throw_gsr(env, c, rc, "gsr_scene_set_rgba_selected") : undefined(env);
+}
+
 // ---- contribution (gsr_contrib_reset / _accumulate_async, gsr_read_contrib, gsr_select_contrib) ----
 // readContrib(handle) -> { weight: BigUint64Array(n), peak: Float32Array(n), pixels: Uint32Array(n), frames }
 napi_value ReadContrib(napi_env env, napi_callback_info info)
@@ -1285,6 +1338,7 @@ napi_value Init(napi_env env, napi_value exports)
         {"selectRegion", SelectRegion}, {"selectBox", SelectBox}, {"setSelection", SetSelection}, {"invertSelection", InvertSelection},
         {"readSelection", ReadSelection}, {"eraseSelected", EraseSelected},
         {"hideSelected", HideSelected}, {"setHidden", SetHidden}, {"readHidden", ReadHidden}, {"selectHidden", SelectHidden},
+        {"selectionBounds", SelectionBounds}, {"editSelected", EditSelected}, {"paintSelected", PaintSelected},
         {"contribReset", Call0<gsr_contrib_reset>}, {"contribAccumulate", Call0<gsr_contrib_accumulate_async>}, {"readContrib", ReadContrib},
         {"selectContrib", SelectContrib},
         {"setOverlay", SetOverlay}, {"readOverlay", ReadOverlay}, {"readOverlayPixels", ReadOverlayPixels},

@@ -9,6 +9,7 @@
 const path = require("path");
 const { FadeInPass } = require("./FadeInPass");
 const { Vector3 } = require("../math/Vector3");
+const { Scene } = require("../core/Scene");
 
 let native = null;
 function loadNative() {
@@ -62,6 +63,10 @@ class HIPRenderer {
             eraseSelected: (keep) => (vertexCount = this._n.eraseSelected(this._h, keep ? 1 : 0)),
             // Scene.setHidden: the mask becomes the device copy's hidden set (null: nothing hidden)
             setHidden: (words) => this._n.setHidden(this._h, words, 0),
+            // Scene.translateSelection / rotateSelection / scaleSelection / paintSelection: the mask becomes the device copy's
+            // selection (setSelection), then the selected splats are edited there; kind 0 translate, 1 rotate, 2 scale
+            editSelected: (kind, f64, pivot) => this._n.editSelected(this._h, kind, f64, pivot),
+            paintSelected: (rgba, byteMask) => this._n.paintSelected(this._h, rgba, byteMask),
         };
         const upload = () => {   // initWebGL's scene part: worker init + texImage2D (WebGLRenderer.ts:105-110,185-195)
             const s = activeScene, n = s.vertexCount, positions = s.positions, rotations = s.rotations, scales = s.scales;
@@ -451,6 +456,27 @@ class HIPRenderer {
         this.setHidden = (words, options) => this._n.setHidden(this._h, words || null, code(OPS, (options || {}).op, "replace", "op"));
         this.readHidden = () => this._n.readHidden(this._h);
         this.selectHidden = (options) => this._n.selectHidden(this._h, code(OPS, (options || {}).op, "replace", "op"));
+        // ---- editing the selection (gsr_selection_bounds / gsr_scene_*_selected): the selected splats and nothing else ----
+        //   renderer.selectRegion(lasso); const { min, max } = renderer.selectionBounds();
+        //   renderer.rotateSelection(q, { pivot: [(min[0] + max[0]) / 2, (min[1] + max[1]) / 2, (min[2] + max[2]) / 2] });
+        //   renderer.paintSelection({ a: 0 });                                  // transparent; absent channels are left alone
+        // What Scene.translate / rotate / scale would leave in a Scene holding only the selected splats; a pivot is translate(-pivot),
+        // the operation, translate(+pivot).  These edit THIS renderer's device copy only: a Scene attached to it does not learn of
+        // them -- Scene.translateSelection(mask, v) and its kin edit every device copy and keep the Scene's arrays right.  A scene
+        // edit: pick, selectRegion and readDepth need a new frame afterwards; selection, hidden set and contribution state stay.
+        const vec = (v, k) => (Array.isArray(v) || ArrayBuffer.isView(v) ? new Float64Array(v) : new Float64Array(k === 4 ? [v.x, v.y, v.z, v.w] : [v.x, v.y, v.z]));
+        const pivotOf = (options) => (options && options.pivot ? vec(options.pivot, 3) : null);
+        this.selectionBounds = () => {
+            const box = new Float32Array(6), count = this._n.selectionBounds(this._h, box);
+            return { count, min: box.slice(0, 3), max: box.slice(3, 6) };
+        };
+        this.translateSelection = (v) => this._n.editSelected(this._h, 0, vec(v, 3), null);
+        this.rotateSelection = (q, options) => this._n.editSelected(this._h, 1, vec(q, 4), pivotOf(options));
+        this.scaleSelection = (s, options) => this._n.editSelected(this._h, 2, vec(s, 3), pivotOf(options));
+        this.paintSelection = (rgba) => {
+            const [value, byteMask] = Scene.rgbaWord(rgba);
+            this._n.paintSelected(this._h, value, byteMask);
+        };
         // ---- contribution (gsr_contrib_* / gsr_select_contrib): per splat of the device scene, what it showed over the frames of a tour ----
         //   renderer.resetContribution(); for (const cam of tour) { renderer.render(scene, cam); renderer.accumulateContribution(); }
         //   renderer.selectContribution({ stat: "pixels", below: 1 }); scene.eraseSelection(renderer.readSelection());   // what never showed

@@ -66,6 +66,10 @@ class GsrRegion(ctypes.Structure):
                 ("mask_stride", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class GsrSelectionBounds(ctypes.Structure):
+    _fields_ = [("count", ctypes.c_uint32), ("min", ctypes.c_float * 3), ("max", ctypes.c_float * 3)]
+
+
 class GsrOverlayOptions(ctypes.Structure):
     _fields_ = [("tint", ctypes.c_float * 3), ("mix", ctypes.c_float), ("reserved", ctypes.c_int32 * 4)]
 
@@ -120,6 +124,7 @@ EXPORTS = [
     "gsr_share_scene", "gsr_scene_sharing",
     "gsr_select_region", "gsr_select_box", "gsr_selection_set", "gsr_selection_invert", "gsr_read_selection", "gsr_scene_erase_selected",
     "gsr_hide_selected", "gsr_hidden_set", "gsr_read_hidden", "gsr_select_hidden",
+    "gsr_selection_bounds", "gsr_scene_translate_selected", "gsr_scene_rotate_selected", "gsr_scene_scale_selected", "gsr_scene_set_rgba_selected",
     "gsr_contrib_reset", "gsr_contrib_accumulate_async", "gsr_read_contrib", "gsr_select_contrib",
     "gsr_set_overlay", "gsr_overlay_async", "gsr_read_overlay", "gsr_read_overlay_rgba8", "gsr_overlay_device_ptr", "gsr_delivery_set_overlay",
 ]
@@ -265,6 +270,11 @@ def load_library(path=None):
     L.gsr_hidden_set.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_int32, u32p]
     L.gsr_read_hidden.argtypes = [vp, vp, ctypes.c_uint32, u32p]
     L.gsr_select_hidden.argtypes = [vp, ctypes.c_int32, u32p]
+    L.gsr_selection_bounds.argtypes = [vp, ctypes.POINTER(GsrSelectionBounds)]
+    L.gsr_scene_translate_selected.argtypes = [vp, vp]
+    L.gsr_scene_rotate_selected.argtypes = [vp, vp, vp]
+    L.gsr_scene_scale_selected.argtypes = [vp, vp, vp]
+    L.gsr_scene_set_rgba_selected.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32]
     L.gsr_contrib_reset.argtypes = [vp]
     L.gsr_contrib_accumulate_async.argtypes = [vp]
     L.gsr_read_contrib.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, u32p]
@@ -933,6 +943,51 @@ class HIPRenderer:
         count = ctypes.c_uint32(0)
         self._check(self._L.gsr_select_hidden(self._ctx, self._select_code(SELECT_OPS, op, "op"), ctypes.byref(count)))
         return count.value
+
+    # -- editing the selection (gsr_selection_bounds / gsr_scene_*_selected): the selected splats and nothing else --
+    def selection_bounds(self):
+        """(count, min f32[3], max f32[3]): the selected splats and the axis-aligned box of their centres, reduced on the device.
+        Nothing selected: (0, +inf, -inf); a NaN coordinate is counted and never enters the box."""
+        b = GsrSelectionBounds()
+        self._check(self._L.gsr_selection_bounds(self._ctx, ctypes.byref(b)))
+        return int(b.count), np.array(b.min, dtype=np.float32), np.array(b.max, dtype=np.float32)
+
+    @staticmethod
+    def _pivot(pivot):
+        return None if pivot is None else np.ascontiguousarray(pivot, dtype=np.float64).reshape(3)
+
+    def scene_translate_selected(self, t):
+        """scene_translate on the selected splats only: what Scene.translate would leave in a Scene holding only them.  A scene edit:
+        the next pick / select_region / overlay needs a new frame; selection, hidden set and contribution state stay."""
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+        self._check(self._L.gsr_scene_translate_selected(self._ctx, t.ctypes.data))
+
+    def scene_rotate_selected(self, q_xyzw, pivot=None):
+        """scene_rotate on the selected splats only; pivot (x, y, z): translate(-pivot), rotate, translate(+pivot), each step rounded
+        to f32.  None is the rotation alone (not a pivot of zero).  Refused while set_sh_follow is on and the scene has SH rows."""
+        q = np.ascontiguousarray(q_xyzw, dtype=np.float64).reshape(4)
+        p = self._pivot(pivot)
+        self._check(self._L.gsr_scene_rotate_selected(self._ctx, q.ctypes.data, None if p is None else p.ctypes.data))
+
+    def scene_scale_selected(self, s, pivot=None):
+        """scene_scale on the selected splats only; pivot as in scene_rotate_selected.  Components must be finite; 0 is allowed."""
+        s = np.ascontiguousarray(s, dtype=np.float64).reshape(3)
+        p = self._pivot(pivot)
+        self._check(self._L.gsr_scene_scale_selected(self._ctx, s.ctypes.data, None if p is None else p.ctypes.data))
+
+    def scene_set_rgba_selected(self, rgba, channels="rgba"):
+        """Paint the selected splats: rgba = (r, g, b, a) bytes or the packed word r | g << 8 | b << 16 | a << 24; channels: which of
+        "r", "g", "b", "a" are written (or a raw byte mask).  SH-coloured splats show only the opacity byte."""
+        if isinstance(channels, str):
+            if not channels or set(channels) - set("rgba"):
+                raise ValueError('channels must be made of "r", "g", "b", "a"')
+            mask = sum(0xff << (8 * "rgba".index(ch)) for ch in set(channels))
+        else:
+            mask = int(channels) & 0xffffffff
+        if np.ndim(rgba):
+            r, g, b, a = (int(v) & 0xff for v in rgba)
+            rgba = r | g << 8 | b << 16 | a << 24
+        self._check(self._L.gsr_scene_set_rgba_selected(self._ctx, int(rgba) & 0xffffffff, mask))
 
     # -- contribution (gsr_contrib_* / gsr_read_contrib / gsr_select_contrib): per-splat weight, peak and pixel counts over views --
     def contrib_reset(self):

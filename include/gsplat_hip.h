@@ -612,6 +612,50 @@ int gsr_hidden_set(gsr_ctx *ctx, const uint32_t *words, uint32_t nwords, int32_t
 int gsr_read_hidden(gsr_ctx *ctx, uint32_t *words, uint32_t nwords, uint32_t *hidden);   /* words may be NULL: count only */
 int gsr_select_hidden(gsr_ctx *ctx, int32_t op, uint32_t *selected);
 
+/* ---- editing the selection ---- move, rotate, scale and recolour the selected splats and nothing else
+ * The reference's Scene.translate / rotate / scale (src/core/Scene.ts:182-305) move the whole scene, and so do gsr_scene_translate /
+ * _rotate / _scale.  These calls change the selected splats only -- straighten a tilted object, move a floater cluster back, shrink
+ * a blown-up region, make a selection transparent or paint it -- on the device, with no gsr_read_scene / gsr_set_scene_arrays round
+ * trip (which re-allocates, drops the selection, the hidden set and the accumulators, and takes the context out of a shared scene).
+ * S is the selection (one bit per splat, the section above "hidden splats").
+ * Transforms ("Editing the selection"): for every splat i whose selection bit is set, the calls leave the
+ *   scene's positions, rotations, scales, covariance words and rgba of i holding exactly what the reference's loops would leave in
+ *   a Scene that held only the selected splats: f64 arithmetic in the reference's order, rounded to f32 wherever the reference
+ *   stores into a Float32Array, the covariance re-packed as Scene.setData packs it.  Every other splat is not written at all.  With
+ *   the whole scene selected and no pivot the result equals gsr_scene_translate / _rotate / _scale bit for bit.  q is (x, y, z, w).
+ * Pivot: a pivot is defined as the three-step sequence on that sub-scene, translate(-pivot), the operation, translate(+pivot), each
+ *   step rounding to f32 as the reference's stores do (the kernel fuses the three steps: one read and one write per selected
+ *   splat).  pivot == NULL means the operation alone, with no translate steps; this is not the same as a pivot of zero, which
+ *   turns -0.0 into +0.0.
+ * Recolour: gsr_scene_set_rgba_selected does rgba[i] = (rgba[i] & ~byte_mask) | (rgba & byte_mask) for selected i; the word is
+ *   data[8i+7]: r, g, b in the low three bytes, opacity in the top byte (0xff000000: opacity only; 0x00ffffff: colour only).  For
+ *   splats that take their colour from SH (index > bandsIndices[0]) the projection reads only the opacity byte.
+ * Bounds: gsr_selection_bounds returns the number of selected splats and the axis-aligned box of their centres as f32.  A value
+ *   enters min only through x < min and max only through x > max, so a NaN coordinate is counted but never enters the box; with
+ *   nothing selected count is 0, min is +inf and max is -inf; hidden splats that are selected count like any other.  The result is
+ *   order-free, so it is exact (compare values, not bits: which of -0.0 and +0.0 a bound holds is not defined).  It is reduced on
+ *   the device and 28 bytes are copied back: no host loop over n.  Blocking; it is no edit and touches no frame state.
+ * Ordering: an edit is a scene edit, ordered like gsr_scene_translate.  It runs on the context's stream, with no host wait on
+ *   other members' streams: frames that other members of a shared scene enqueued before it read the old scene, frames enqueued
+ *   behind it read the new scene.  It marks every member's frame and sorted order as edited: gsr_select_region, gsr_pick,
+ *   gsr_depth_async, gsr_contrib_accumulate_async and gsr_overlay_async return GSR_ERR_ARG until the next frame.  A call that
+ *   would change no bit still counts as an edit.  With no selection buffers (the scene was never selected in) no kernel is
+ *   launched.
+ * State that survives: the selection, the hidden set and the contribution accumulators are untouched and indices do not move; the
+ *   accumulators then describe the old geometry (gsr_contrib_reset starts a new tour).  The context stays in its shared scene.
+ * Requirements and refusals (GSR_ERR_ARG with a message, nothing touched): edits require a scene with rotations / scales (from rows
+ *   or from the four arrays), as the whole-scene transforms do.  gsr_scene_rotate_selected and gsr_scene_scale_selected are refused
+ *   while gsr_set_sh_follow is on and the scene has SH rows: the SH frame is one per scene and a partial rotation has none;
+ *   translate and set_rgba are allowed in that state.  Each scale component must be finite; zero is allowed, because there is no
+ *   frame to invert here.  A NULL ctx or a NULL required pointer returns GSR_ERR_ARG with nothing touched.
+ * (struct gsr_selection_bounds has no typedef: C keeps a struct tag and a function of one name apart, a typedef it would not.) */
+struct gsr_selection_bounds { uint32_t count; float min[3]; float max[3]; };
+int gsr_selection_bounds(gsr_ctx *ctx, struct gsr_selection_bounds *out);                       /* blocking */
+int gsr_scene_translate_selected(gsr_ctx *ctx, const double *t /* 3 */);
+int gsr_scene_rotate_selected(gsr_ctx *ctx, const double *q /* 4: x, y, z, w */, const double *pivot /* 3, or NULL */);
+int gsr_scene_scale_selected(gsr_ctx *ctx, const double *s /* 3 */, const double *pivot /* 3, or NULL */);
+int gsr_scene_set_rgba_selected(gsr_ctx *ctx, uint32_t rgba, uint32_t byte_mask);
+
 /* ---- contribution ---- per-splat weight, peak and pixel counts over views
  * No interface of the reference stands behind this section either.  Every selector above is geometric; this one answers "which
  * splats never show" -- buried inside surfaces, hidden behind them, touching no pixel from any camera of a tour -- and with

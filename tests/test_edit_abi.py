@@ -1,0 +1,115 @@
+"""Editing the selection, the part that needs no GPU: the five entry points are exported by the library, prototyped by the Python
+host and documented in include/gsplat_hip.h rule by rule, the way tests/test_hide_abi.py holds the hidden set to the header."""
+import ctypes
+import glob
+import inspect
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "gsplat_hip.h")
+CSRC = os.path.join(ROOT, "gsplat.js_amd", "csrc")
+NAMES = ("gsr_selection_bounds", "gsr_scene_translate_selected", "gsr_scene_rotate_selected", "gsr_scene_scale_selected",
+         "gsr_scene_set_rgba_selected")
+
+
+def test_symbols_are_exported_and_prototyped():
+    import gsplat_hip as gh
+    lib = gh.load_library()
+    for n in NAMES:
+        assert hasattr(lib, n), "libgsplat_hip.so does not export %s" % n
+        assert n in gh.EXPORTS
+        assert getattr(lib, n).restype is ctypes.c_int
+    vp, u32 = ctypes.c_void_p, ctypes.c_uint32
+    assert lib.gsr_selection_bounds.argtypes == [vp, ctypes.POINTER(gh.GsrSelectionBounds)]
+    assert ctypes.sizeof(gh.GsrSelectionBounds) == 28
+    assert lib.gsr_scene_translate_selected.argtypes == [vp, vp]
+    assert lib.gsr_scene_rotate_selected.argtypes == [vp, vp, vp]
+    assert lib.gsr_scene_scale_selected.argtypes == [vp, vp, vp]
+    assert lib.gsr_scene_set_rgba_selected.argtypes == [vp, u32, u32]
+    # a NULL context is refused by every one of them, with nothing touched
+    v = (ctypes.c_double * 4)(0, 0, 0, 1)
+    b = gh.GsrSelectionBounds()
+    for call in (lambda: lib.gsr_selection_bounds(None, ctypes.byref(b)), lambda: lib.gsr_scene_translate_selected(None, ctypes.addressof(v)),
+                 lambda: lib.gsr_scene_rotate_selected(None, ctypes.addressof(v), None), lambda: lib.gsr_scene_scale_selected(None, ctypes.addressof(v), None),
+                 lambda: lib.gsr_scene_set_rgba_selected(None, 0, 0)):
+        assert call() == -1
+
+
+def test_header_declares_and_documents_them():
+    src = open(HEADER).read()
+    code = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    flat = " ".join(code.split())
+    for decl in ("struct gsr_selection_bounds { uint32_t count; float min[3]; float max[3]; };",
+                 "int gsr_selection_bounds(gsr_ctx *ctx, struct gsr_selection_bounds *out);",
+                 "int gsr_scene_translate_selected(gsr_ctx *ctx, const double *t );",
+                 "int gsr_scene_rotate_selected(gsr_ctx *ctx, const double *q , const double *pivot );",
+                 "int gsr_scene_scale_selected(gsr_ctx *ctx, const double *s , const double *pivot );",
+                 "int gsr_scene_set_rgba_selected(gsr_ctx *ctx, uint32_t rgba, uint32_t byte_mask);"):
+        assert decl in flat, decl
+    assert src.index("/* ---- hidden splats ----") < src.index("/* ---- editing the selection ----") < src.index("/* ---- contribution ----")
+    m = re.search(r"/\* ---- editing the selection ----.*?\*/", src, flags=re.S)
+    assert m, "the header has no section on editing the selection"
+    doc = " ".join(m.group(0).replace(" * ", " ").split())
+    # transforms; pivot; recolour; bounds; ordering; what survives; requirements and refusals
+    for words in ("src/core/Scene.ts:182-305", "a Scene that held only the selected splats", "f64 arithmetic in the reference's order",
+                  "wherever the reference stores into a Float32Array", "Every other splat is not written at all",
+                  "equals gsr_scene_translate / _rotate / _scale bit for bit", "translate(-pivot), the operation, translate(+pivot)",
+                  "each step rounding to f32", "one read and one write per selected splat", "pivot == NULL means the operation alone",
+                  "not the same as a pivot of zero", "turns -0.0 into +0.0",
+                  "rgba[i] = (rgba[i] & ~byte_mask) | (rgba & byte_mask)", "data[8i+7]", "opacity in the top byte",
+                  "(index > bandsIndices[0]) the projection reads only the opacity byte",
+                  "axis-aligned box of their centres as f32", "enters min only through x < min", "max only through x > max",
+                  "a NaN coordinate is counted but never enters the box", "count is 0, min is +inf and max is -inf",
+                  "hidden splats that are selected count like any other", "order-free, so it is exact", "28 bytes are copied back", "no host loop over n",
+                  "ordered like gsr_scene_translate", "no host wait on other members' streams", "read the old scene", "read the new scene",
+                  "every member's frame and sorted order as edited", "gsr_select_region, gsr_pick, gsr_depth_async, gsr_contrib_accumulate_async and gsr_overlay_async",
+                  "GSR_ERR_ARG until the next frame", "would change no bit still counts as an edit", "no kernel is launched",
+                  "the selection, the hidden set and the contribution accumulators are untouched", "indices do not move",
+                  "the accumulators then describe the old geometry", "require a scene with rotations / scales",
+                  "refused while gsr_set_sh_follow is on and the scene has SH rows", "the SH frame is one per scene and a partial rotation has none",
+                  "translate and set_rgba are allowed in that state", "Each scale component must be finite", "zero is allowed",
+                  "A NULL ctx or a NULL required pointer returns GSR_ERR_ARG with nothing touched"):
+        assert words in doc, words
+
+
+def test_python_host_has_the_methods():
+    import gsplat_hip as gh
+    for name in ("selection_bounds", "scene_translate_selected", "scene_rotate_selected", "scene_scale_selected", "scene_set_rgba_selected"):
+        assert callable(getattr(gh.HIPRenderer, name)), name
+    sig = lambda name: inspect.signature(getattr(gh.HIPRenderer, name)).parameters
+    assert list(sig("selection_bounds")) == ["self"]
+    assert list(sig("scene_translate_selected")) == ["self", "t"]
+    assert list(sig("scene_rotate_selected")) == ["self", "q_xyzw", "pivot"] and sig("scene_rotate_selected")["pivot"].default is None
+    assert list(sig("scene_scale_selected")) == ["self", "s", "pivot"] and sig("scene_scale_selected")["pivot"].default is None
+    assert list(sig("scene_set_rgba_selected")) == ["self", "rgba", "channels"] and sig("scene_set_rgba_selected")["channels"].default == "rgba"
+
+
+def test_sources_are_wired_into_every_build():
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    srcs = re.search(r"^SRCS := (.*)$", mk, flags=re.M).group(1).split()
+    for f in ("gsr_edit.cpp", "k_edit.hip"):
+        assert f in srcs and os.path.exists(os.path.join(CSRC, f)), f   # SRCS feeds the objects, the build id and the bounds build
+    build_id = re.search(r"^BUILD_ID := (.*)$", mk, flags=re.M).group(1)
+    assert "$(SRCS)" in build_id and "k_pack_cov.h" in build_id
+    assert re.search(r"^\$\(OUT\)/%\.o: %\.hip .*k_pack_cov\.h", mk, flags=re.M), "the .hip rule does not depend on the shared header"
+    edit = open(os.path.join(CSRC, "gsr_edit.cpp")).read()
+    for word in ("edit_begin(c)", "edit_end(c)", "invalidate_members(c", "launch_edit_translate(", "launch_edit_rotate(", "launch_edit_scale(",
+                 "launch_edit_rgba(", "launch_edit_bounds("):
+        assert word in edit, word
+    kern = open(os.path.join(CSRC, "k_edit.hip")).read()
+    for word in ("GSR_BOUNDS_DECL(edit)", "GSR_BOUND(edit, 0,", "GSR_BOUND(edit, 1,", "GSR_BOUND(edit, 2,", "k_edit_translate", "k_edit_rotate", "k_edit_scale",
+                 "k_edit_rgba", "k_edit_bounds", "template <bool PIVOT>", "__popc(", "__shfl_xor(", '#include "k_pack_cov.h"'):
+        assert word in kern, word
+
+
+def test_the_covariance_arithmetic_exists_once():
+    defs = {}
+    for path in sorted(glob.glob(os.path.join(CSRC, "*"))):
+        if os.path.isfile(path):
+            text = open(path, errors="replace").read()
+            for fn in ("pack_cov", "pack_half2", "float_to_half_trunc"):
+                if re.search(r"__device__[^;{]*\b%s\(" % fn, text):
+                    defs.setdefault(fn, []).append(os.path.basename(path))
+    assert defs == {"pack_cov": ["k_pack_cov.h"], "pack_half2": ["k_pack_cov.h"], "float_to_half_trunc": ["k_pack_cov.h"]}, defs
+    assert '#include "k_pack_cov.h"' in open(os.path.join(CSRC, "k_scene.hip")).read()

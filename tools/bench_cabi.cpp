@@ -3,7 +3,7 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--share-scene]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--share-scene]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
@@ -31,6 +31,9 @@
 // the first frame, so every timed frame is one of the scene with those out of the way; the report carries `hidden` and the call's
 // wall time.  --hide 0 is the run to compare with: nothing hidden, the projection handed no mask.  --hide-edits adds, at the very
 // end, the wall time of one gsr_hide_selected and of one gsr_scene_erase_selected with and without a hidden set to carry along.
+// --edit-selected FRACTION selects that fraction of the splats (scattered over the indices) through gsr_selection_set on every device
+// copy and adds a leg with a gsr_scene_rotate_selected by one degree about y, pivoted, behind every frame: only the selection turns.
+// The report carries the leg's rate and `edit_ms`, the wall time a frame of that leg takes beyond a frame of the plain timed loop.
 //
 // Scene: the seeded synthetic generator of gsplat_hip/synth.py (mulberry32 counter PRNG, 24 draws per splat) written
 // out again in C++; log/exp/cos come from libm here and from numpy there, so a byte may differ in a rare rounding --
@@ -159,6 +162,7 @@ int main(int argc, char** argv)
     std::string scene_edit = "none";
     double hide_fraction = -1.0;   // < 0: off
     bool hide_edits = false;
+    double edit_fraction = -1.0;   // < 0: off
     int32_t pick_xy[2] = {0, 0};
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -179,11 +183,12 @@ int main(int argc, char** argv)
         else if (a == "--overlay" && i + 1 < argc) { overlay_fraction = std::atof(argv[++i]); if (!(overlay_fraction >= 0.0 && overlay_fraction <= 1.0)) { std::fprintf(stderr, "--overlay FRACTION must be in [0, 1]\n"); return 2; } }
         else if (a == "--hide" && i + 1 < argc) { hide_fraction = std::atof(argv[++i]); if (!(hide_fraction >= 0.0 && hide_fraction <= 1.0)) { std::fprintf(stderr, "--hide FRACTION must be in [0, 1]\n"); return 2; } }
         else if (a == "--hide-edits") hide_edits = true;
+        else if (a == "--edit-selected" && i + 1 < argc) { edit_fraction = std::atof(argv[++i]); if (!(edit_fraction >= 0.0 && edit_fraction <= 1.0)) { std::fprintf(stderr, "--edit-selected FRACTION must be in [0, 1]\n"); return 2; } }
         else if (a == "--scene-arrays") scene_arrays = true;
         else if (a == "--scene-edit") scene_edit = next();
         else if (a == "--share-scene") share_scene = true;
         else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--share-scene]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--share-scene]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
@@ -484,6 +489,30 @@ int main(int argc, char** argv)
         for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_sync(c)); }
         edit_sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - e0).count();
     }
+    // --edit-selected: the orbit once more with the selected splats turned about a pivot on the device behind every frame
+    double edit_selected_sec = 0;
+    uint32_t edit_selected = 0;
+    if (edit_fraction >= 0.0) {
+        std::vector<uint32_t> words((n + 31) / 32, 0u);
+        const uint64_t limit = (uint64_t)(edit_fraction * 4294967296.0);
+        for (uint32_t i = 0; i < n; i++)
+            if ((uint64_t)((i + 0x85ebca6bu) * 2654435761u) < limit) words[i >> 5] |= 1u << (i & 31);
+        for (gsr_ctx* c : ctx) {   // (the members of a shared scene have one selection: the first call sets it)
+            ctx0 = c;
+            if (c == ctx[0] || !share_scene) CHECK(gsr_selection_set(c, words.data(), (uint32_t)words.size(), GSR_SELOP_REPLACE, &edit_selected));
+        }
+        const double half = 0.5 * 3.14159265358979323846 / 180.0, dq[4] = {0.0, std::sin(half), 0.0, std::cos(half)}, pivot[3] = {0.5, 0.0, -0.5};
+        auto edit_step = [&](int k) -> int {
+            if (int rc = step(k)) return rc;
+            return gsr_scene_rotate_selected(ctx[k % in_flight], dq, pivot);
+        };
+        for (int k = 0; k < warmup; k++) { ctx0 = ctx[k % in_flight]; CHECK(edit_step(k)); }
+        for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_sync(c)); }
+        const auto e0 = std::chrono::steady_clock::now();
+        for (int k = 0; k < frames; k++) { ctx0 = ctx[(warmup + k) % in_flight]; CHECK(edit_step(warmup + k)); }
+        for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_sync(c)); }
+        edit_selected_sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - e0).count();
+    }
     // --hide-edits (last: it removes splats): the wall time of one gsr_hide_selected that hides a fifth of the scene, and of one
     // gsr_scene_erase_selected of another fifth while those are hidden (the compaction carries the hidden set: k_box_compact_bits)
     double hide_selected_ms = 0, erase_hidden_ms = 0, erase_plain_ms = 0;
@@ -555,6 +584,9 @@ int main(int argc, char** argv)
                     hide_selected_ms, erase_plain_ms, erase_hidden_ms, edits_hidden, edits_kept);
     if (scene_arrays) std::printf(", \"scene_from\": \"gsr_set_scene_arrays\"");
     if (scene_edit == "rotate") std::printf(", \"scene_edit\": \"rotate\", \"frames_per_sec_scene_edit\": %.1f", frames / edit_sec);
+    if (edit_fraction >= 0.0)
+        std::printf(", \"edit_selected_fraction\": %g, \"edit_selected\": %u, \"frames_per_sec_edit_selected\": %.1f, \"edit_ms\": %.4f", edit_fraction,
+                    edit_selected, frames / edit_selected_sec, (edit_selected_sec - sec) / frames * 1e3);
     if (pick)
         std::printf(", \"pick\": {\"x\": %d, \"y\": %d, \"index\": %u, \"depth\": %s, \"mean\": %.9g, \"alpha\": %.9g}",
                     pick_xy[0], pick_xy[1], picked.index, picked.index == 0xffffffffu ? "null" : std::to_string(picked.depth).c_str(), (double)picked.mean, (double)picked.alpha);
