@@ -32,7 +32,7 @@ int reset_accumulators(gsr_ctx* c)
         int r;
         if ((r = k.weight.alloc(c, sc.n)) || (r = k.peak.alloc(c, sc.n)) || (r = k.pixels.alloc(c, sc.n)) ||
             (r = k.counters.alloc(c, SharedScene::Contrib::COUNTER_WORDS))) { k.reset(); return r; }
-        k.rows = sc.n;
+        k.rows = k.alloc_rows = sc.n;
     }
     const size_t rows = std::max(k.rows, 1u);
     HIP_TRY(c, hipMemsetAsync(k.weight, 0, rows * 8, c->stream));

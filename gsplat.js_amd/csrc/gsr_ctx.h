@@ -193,11 +193,13 @@ struct SharedScene {
         DevBuf<unsigned long long> weight;   // `rows` each: sum of rintf(w * 2^24),
         DevBuf<uint32_t> peak, pixels;       // max of w (bits of a non-negative f32), fragments modulo 2^32
         DevBuf<uint32_t> counters;           // [0] frames: the passes that contributed since the last reset; [1] reserved (0)
-        uint32_t rows = 0;                   // splats the arrays were allocated for (the scene's count at the reset)
+        uint32_t rows = 0;                   // splats the accumulators describe (the scene's count at the reset, or since it grew)
+        uint32_t alloc_rows = 0;             // rows the arrays were allocated for: `rows`, or more where the scene's capacity was
+                                             // reserved (gsr_append.cpp); the rows at and above `rows` are zero
         static constexpr uint32_t COUNTER_WORDS = 2;
         bool live() const { return (bool)counters.p; }
-        void reset() { weight.reset(); peak.reset(); pixels.reset(); counters.reset(); rows = 0; }
-        uint64_t bytes() const { return live() ? (uint64_t)rows * 16 + COUNTER_WORDS * 4 : 0; }
+        void reset() { weight.reset(); peak.reset(); pixels.reset(); counters.reset(); rows = alloc_rows = 0; }
+        uint64_t bytes() const { return live() ? (uint64_t)alloc_rows * 16 + COUNTER_WORDS * 4 : 0; }
     } contrib;
     // device bytes of the state the members hold once
     uint64_t bytes() const
@@ -525,6 +527,8 @@ int alloc_scene(gsr_ctx* c, uint32_t n, bool with_rows);
 int adopt_scene(gsr_ctx* c);
 // the context leaves its scene (the last member frees it); c->scene is null afterwards
 void scene_release(gsr_ctx* c);
+// what the blocking scene replacements do first (limitBox, erase, new SH textures, growth): waits for every other member's stream
+int sync_members(gsr_ctx* c);
 // gsr_scene_limit_box from need_rows on, for either predicate (gsr_scene_erase_selected is the other caller): the kept splats, in
 // order, become the scene; SH state, generation, bins and the members' frame state as the header says of limitBox; the selection is
 // empty afterwards.  `what` names the caller in a HIP error.

@@ -498,6 +498,16 @@ uint32_t edit_bounds_blocks(uint32_t n);
 void launch_edit_bounds(uint32_t n, const float* px, const float* py, const float* pz, const uint32_t* words, uint32_t nwords, uint32_t* partial,
                         uint32_t* out, hipStream_t s);
 
+// Growing the scene (k_append.hip; DESIGN.md section 4, "Growing the scene"): the splats of `src` (n_src of them) whose bit of
+// `words` (nwords of them, the selection's layout; bits at and above n_src are not read) is set, in ascending order, copied bit for
+// bit into the rows dst_first, dst_first + 1, ... of `dst`, which holds dst_rows rows.  src and dst may be the same arrays (the
+// rows read lie below dst_first).  block_sums: append_blocks(n_src) + 1 words of scratch (the scanned per-workgroup counts, then the total).
+uint32_t append_blocks(uint32_t n_src);
+void launch_append_gather(uint32_t n_src, const SceneDev& src, const SceneDev& dst, uint32_t dst_first, uint32_t dst_rows, const uint32_t* words,
+                          uint32_t nwords, uint32_t* block_sums, hipStream_t s);
+// words[0 .. nwords) <- exactly the bits [first, first + count); *total <- count
+void launch_append_select_range(uint32_t* words, uint32_t nwords, uint32_t first, uint32_t count, uint32_t* total, hipStream_t s);
+
 // Contribution (k_contrib.hip; DESIGN.md section 4, "Contribution"): the last frame's bin lists walked once more, the weight
 // w = T * B of every fragment kept per SPLAT and summed over pixels and passes into three accumulators held with the scene.
 struct ContribBuffers : FrameLists {   // (a frame that did not fit is neither walked nor counted)

@@ -37,15 +37,15 @@ void leave_share(gsr_ctx* c)
     c->scene_gen = c->scene->generation;
 }
 
-// blocking calls that replace what the members read (limitBox, new SH textures): nothing of any member is in flight afterwards
-int sync_members(gsr_ctx* c)
+}  // namespace
+
+// blocking calls that replace what the members read (limitBox, new SH textures, growth): nothing of any other member is in flight afterwards
+int gsr::sync_members(gsr_ctx* c)
 {
     for (gsr_ctx* m : c->scene->members)
         if (m != c) HIP_TRY(c, hipStreamSynchronize(m->stream));
     return GSR_OK;
 }
-
-}  // namespace
 
 // what every transform, compaction and edit of the selection demands of the scene: rotations and scales (the one statement of the refusal)
 int gsr::require_rows(gsr_ctx* c)

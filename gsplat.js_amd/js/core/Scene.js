@@ -142,15 +142,18 @@ class Scene extends EventDispatcher {
     // kind: 0 translate (x, y, z), 1 rotate (x, y, z, w), 2 scale (x, y, z), 3 limitBox (xMin, xMax, yMin, yMax, zMin, zMax),
     // 4 eraseSelection ({ mask, keep }: the mask is set on the device copy, then erased there),
     // 5 translateSelection, 6 rotateSelection, 7 scaleSelection ({ mask, values, pivot }), 8 paintSelection ({ mask, rgba, byteMask }):
-    // the mask is set on the device copy, then the splats it selects are edited there.
+    // the mask is set on the device copy, then the splats it selects are edited there;
+    // 9 duplicateSelection ({ mask, count }: the mask is set on the device copy, then the splats it selects are copied behind the last one there),
+    // 10 append ({ data, positions, rotations, scales, count }: the rows go to the device copy through the upload's repack).
     // false: the edit has to run here (nothing attached, a host-only device scene among them, or buffers set by hand).
     _editDevices(kind, args) {
         // (a device scene that cannot follow SH -- no setShFollow / readSh -- counts as host-only while the option is on; so does
         //  one that cannot take a selection -- no setSelection / eraseSelected -- for an eraseSelection)
         const cannotFollow = this._shFollowsTransforms && this._devices.some((d) => !d.setShFollow || !d.readSh);
         const cannotErase = kind === 4 && this._devices.some((d) => !d.setSelection || !d.eraseSelected);
-        const cannotEdit = kind >= 5 && this._devices.some((d) => !d.setSelection || !d.editSelected || !d.paintSelected);
-        if (!this._devices.length || this._diverged || cannotFollow || cannotErase || cannotEdit || this._devices.some((d) => d.hostOnly)) {
+        const cannotEdit = kind >= 5 && kind <= 8 && this._devices.some((d) => !d.setSelection || !d.editSelected || !d.paintSelected);
+        const cannotGrow = kind >= 9 && this._devices.some((d) => !d.setSelection || !d.duplicateSelected || !d.appendArrays);
+        if (!this._devices.length || this._diverged || cannotFollow || cannotErase || cannotEdit || cannotGrow || this._devices.some((d) => d.hostOnly)) {
             this._refresh();
             this._refreshSh();
             return false;
@@ -160,6 +163,8 @@ class Scene extends EventDispatcher {
         for (const d of this._distinctDevices()) {
             let c;
             if (kind === 4) { d.setSelection(args.mask); c = d.eraseSelected(args.keep); }
+            else if (kind === 9) { d.setSelection(args.mask); c = d.duplicateSelected(); }   // (the copies are the copy's selection afterwards)
+            else if (kind === 10) c = d.appendArrays(args.data, args.positions, args.rotations, args.scales, args.count);
             else if (kind >= 5) {   // the mask first, then the edit of what it selects; the count stays
                 d.setSelection(args.mask);
                 if (kind === 8) d.paintSelected(args.rgba, args.byteMask);
@@ -393,6 +398,52 @@ class Scene extends EventDispatcher {
         const d = this._data;
         this._editMasked(mask, null, (i) => { d[8 * i + 7] = (d[8 * i + 7] & ~byteMask) | value; });
     }
+    // ---- growing the scene: copies of the masked splats, or another Scene's splats, behind the last one ----
+    // duplicateSelection(mask): the splats whose bit of `mask` is set, in ascending order, copied bit for bit behind the last splat;
+    // append(other): all of another Scene's splats likewise (its SH rows are not carried: the copies keep their rgba word).  Existing
+    // indices do not move.  While device scenes are attached the call is issued once per distinct device copy (gsr_selection_set +
+    // gsr_scene_duplicate_selected, gsr_scene_append_arrays), where the new splats become the selection; otherwise the four arrays are
+    // concatenated here.  Both return { first, count }, fire "change", and throw while the scene has SH rows: SH rows are indexed by
+    // splat order, and a splat appended at the tail would have none to read.
+    duplicateSelection(mask) {
+        const n = this._vertexCount, words = Math.ceil(n / 32);
+        if (!(mask instanceof Uint32Array) || mask.length < words) throw new Error("duplicateSelection: mask must be a Uint32Array of at least " + words + " words");
+        if (this.shHeight > 0) throw new Error("duplicateSelection: the scene has SH rows (a splat appended at the tail would have no SH row)");
+        const idx = [];
+        for (let i = 0; i < n; i++) if ((mask[i >>> 5] >>> (i & 31)) & 1) idx.push(i);
+        if (!this._editDevices(9, { mask: mask, count: idx.length })) this._appendRows(this._data, this._positions, this._rotations, this._scales, idx);
+        return { first: n, count: idx.length };
+    }
+    append(other) {
+        if (!(other instanceof Scene) || other === this) throw new Error("append: another Scene is needed");
+        if (this.shHeight > 0) throw new Error("append: the scene has SH rows (a splat appended at the tail would have no SH row)");
+        const m = other.vertexCount, data = other.data, positions = other.positions, rotations = other.rotations, scales = other.scales;
+        if (data.length < 8 * m || positions.length !== 3 * m || rotations.length !== 4 * m || scales.length !== 3 * m)
+            throw new Error("append: the other scene needs positions, rotations and scales of its vertexCount");
+        const n = this._vertexCount, idx = [];
+        for (let i = 0; i < m; i++) idx.push(i);
+        if (!this._editDevices(10, { data: data, positions: positions, rotations: rotations, scales: scales, count: m })) this._appendRows(data, positions, rotations, scales, idx);
+        return { first: n, count: m };
+    }
+    // the host loop of both: rows idx of the given arrays behind this scene's last row.  Rows travel through set() between arrays of
+    // one type, which copies bytes: a NaN keeps its payload.
+    _appendRows(data, positions, rotations, scales, idx) {
+        const n = this._vertexCount, total = n + idx.length, height = Math.ceil((2 * total) / this._width);
+        const grow = (T, old, len, keep) => { const a = new T(len); a.set(old.subarray(0, keep)); return a; };
+        const d = grow(Uint32Array, this._data, this._width * height * 4, 8 * n), p = grow(Float32Array, this._positions, 3 * total, 3 * n);
+        const r = grow(Float32Array, this._rotations, 4 * total, 4 * n), s = grow(Float32Array, this._scales, 3 * total, 3 * n);
+        idx.forEach((i, j) => {
+            d.set(data.subarray(8 * i, 8 * i + 8), 8 * (n + j));
+            p.set(positions.subarray(3 * i, 3 * i + 3), 3 * (n + j));
+            r.set(rotations.subarray(4 * i, 4 * i + 4), 4 * (n + j));
+            s.set(scales.subarray(3 * i, 3 * i + 3), 3 * (n + j));
+        });
+        this._data = d; this._positions = p; this._rotations = r; this._scales = s;
+        this._vertexCount = total;
+        this._height = height;
+        this.dispatchEvent({ type: "change" });
+    }
+
     // { r, g, b, a } -> [word with the present channels' bytes, mask of their bytes]
     static rgbaWord(rgba) {
         let value = 0, byteMask = 0;

@@ -78,7 +78,14 @@ export interface DeviceScene {
      *  these edits. */
     editSelected?(kind: number, args: Float64Array, pivot: Float64Array | null): void;
     paintSelected?(rgba: number, byteMask: number): void;
+    /** optional, the two together with setSelection: Scene.duplicateSelection sets its mask as the device copy's selection, then has
+     *  the copy duplicate the selected splats behind its last one; Scene.append hands it another Scene's four arrays (m splats).  Both
+     *  return vertexCount.  A device scene without them is treated like a host-only one for these calls. */
+    duplicateSelected?(): number;
+    appendArrays?(data: Uint32Array, positions: Float32Array, rotations: Float32Array, scales: Float32Array, m: number): number;
 }
+/** The new splats of a growing call: [first, first + count). */
+export interface GrownRange { first: number; count: number }
 /** Bytes 0..255; absent channels are left alone. */
 export interface PaintChannels { r?: number; g?: number; b?: number; a?: number }
 export type Vec3Like = Vector3 | [number, number, number] | Float64Array | Float32Array;
@@ -121,6 +128,12 @@ export class Scene {
     scaleSelection(mask: Uint32Array, s: Vector3, options?: { pivot?: Vec3Like }): void;
     /** data[8i + 7] of the masked splats: r, g, b in the low three bytes, opacity in the top one; absent channels are left alone */
     paintSelection(mask: Uint32Array, rgba: PaintChannels): void;
+    /** Grow the scene: the splats whose bit of `mask` is set, in ascending order, copied bit for bit behind the last splat
+     *  (duplicateSelection), or all of another Scene's splats (append; its SH rows are not carried).  Existing indices do not move.
+     *  While device scenes are attached the call is issued once per distinct device copy, where the new splats become the
+     *  selection; otherwise the four arrays are concatenated here.  Fires "change".  Both throw while the scene has SH rows. */
+    duplicateSelection(mask: Uint32Array): GrownRange;
+    append(other: Scene): GrownRange;
     static rgbaWord(rgba: PaintChannels): [number, number];
     saveToFile(name: string): void;
     toSplatBytes(): Uint8Array;
@@ -316,6 +329,17 @@ export class HIPRenderer {
     rotateSelection(q: Quaternion | [number, number, number, number] | Float64Array, options?: { pivot?: Vec3Like }): void;
     scaleSelection(s: Vec3Like, options?: { pivot?: Vec3Like }): void;
     paintSelection(rgba: PaintChannels): void;
+    /** Growing THIS renderer's device copy (Scene.duplicateSelection / Scene.append grow every copy and the Scene's arrays).
+     *  duplicateSelection copies the selected splats bit for bit behind the last splat; appendSelectionFrom copies the splats selected
+     *  in another renderer of the same GPU, device to device (that renderer is not changed, its SH rows are not carried).  The new
+     *  splats [first, first + count) become the selection; existing indices, the hidden set and the contribution state stay.  With
+     *  nothing selected nothing changes and the last frame stays valid.  reserveScene makes the device arrays hold at least `rows`
+     *  splats, so that copies up to that count re-allocate nothing; sceneCapacity returns what they hold.  The growing calls throw
+     *  while the device scene has SH rows. */
+    reserveScene(rows: number): void;
+    sceneCapacity(): number;
+    duplicateSelection(): GrownRange;
+    appendSelectionFrom(other: HIPRenderer): GrownRange;
     /** Contribution: per splat of the device scene (renderers that share a scene have one set together), what it showed over the
      *  frames of a tour.  resetContribution zeroes the accumulators (blocking); accumulateContribution enqueues the pass behind the
      *  frame rendered last (no wait; a frame whose lists did not fit adds nothing); readContribution returns weight (sum of the

@@ -1203,6 +1203,89 @@ napi_value PaintSelected(napi_env env, napi_callback_info info)
     return rc ? throw_gsr(env, c, rc, "gsr_scene_set_rgba_selected") : undefined(env);
 }
 
+// ---- growing the scene (gsr_scene_reserve / _capacity / _duplicate_selected / _append_selected / _append_arrays) ----
+napi_value first_count(napi_env env, uint32_t first, uint32_t count)
+{
+    napi_value o, f, k;
+    napi_create_object(env, &o);
+    napi_create_uint32(env, first, &f);
+    napi_create_uint32(env, count, &k);
+    napi_set_named_property(env, o, "first", f);
+    napi_set_named_property(env, o, "count", k);
+    return o;
+}
+
+// reserveScene(handle, rows)
+napi_value ReserveScene(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    uint32_t rows;
+    if (!c || napi_get_value_uint32(env, argv[1], &rows) != napi_ok) return nullptr;
+    const int rc = gsr_scene_reserve(c, rows);
+    return rc ? throw_gsr(env, c, rc, "gsr_scene_reserve") : undefined(env);
+}
+
+// sceneCapacity(handle) -> rows
+napi_value SceneCapacity(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    if (!c) return nullptr;
+    uint32_t rows = 0;
+    const int rc = gsr_scene_capacity(c, &rows);
+    return rc ? throw_gsr(env, c, rc, "gsr_scene_capacity") : count_value(env, rows);
+}
+
+// duplicateSelected(handle) -> { first, count }
+napi_value DuplicateSelected(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    if (!c) return nullptr;
+    uint32_t first = 0, count = 0;
+    const int rc = gsr_scene_duplicate_selected(c, &first, &count);
+    return rc ? throw_gsr(env, c, rc, "gsr_scene_duplicate_selected") : first_count(env, first, count);
+}
+
+// appendSelected(handle, from handle) -> { first, count }
+napi_value AppendSelected(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    gsr_ctx* from = c ? get_ctx(env, argv[1]) : nullptr;
+    if (!c || !from) return nullptr;
+    uint32_t first = 0, count = 0;
+    const int rc = gsr_scene_append_selected(c, from, &first, &count);
+    return rc ? throw_gsr(env, c, rc, "gsr_scene_append_selected") : first_count(env, first, count);
+}
+
+// appendArrays(handle, Uint32Array data, Float32Array positions, rotations, scales, m) -> { first, count }
+napi_value AppendArrays(napi_env env, napi_callback_info info)
+{
+    napi_value argv[6];
+    if (!get_args(env, info, 6, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    if (!c) return nullptr;
+    void *data, *pos, *rot, *scl;
+    size_t nd, np, nr, ns;
+    int32_t m;
+    if (!get_typed(env, argv[1], napi_uint32_array, &data, &nd) || !get_typed(env, argv[2], napi_float32_array, &pos, &np) ||
+        !get_typed(env, argv[3], napi_float32_array, &rot, &nr) || !get_typed(env, argv[4], napi_float32_array, &scl, &ns) || !get_i32(env, argv[5], &m))
+        return nullptr;
+    if (m < 0 || nd < (size_t)m * 8 || np < (size_t)m * 3 || nr < (size_t)m * 4 || ns < (size_t)m * 3) {
+        napi_throw_range_error(env, nullptr, "scene buffers are smaller than the appended count requires");
+        return nullptr;
+    }
+    uint32_t first = 0;
+    const int rc = gsr_scene_append_arrays(c, (const uint32_t*)data, (const float*)pos, (const float*)rot, (const float*)scl, (uint32_t)m, &first);
+    return rc ? throw_gsr(env, c, rc, "gsr_scene_append_arrays") : first_count(env, first, (uint32_t)m);
+}
+
 // ---- contribution (gsr_contrib_reset / _accumulate_async, gsr_read_contrib, gsr_select_contrib) ----
 // readContrib(handle) -> { weight: BigUint64Array(n), peak: Float32Array(n), pixels: Uint32Array(n), frames }
 napi_value ReadContrib(napi_env env, napi_callback_info info)
@@ -1339,6 +1422,8 @@ napi_value Init(napi_env env, napi_value exports)
         {"readSelection", ReadSelection}, {"eraseSelected", EraseSelected},
         {"hideSelected", HideSelected}, {"setHidden", SetHidden}, {"readHidden", ReadHidden}, {"selectHidden", SelectHidden},
         {"selectionBounds", SelectionBounds}, {"editSelected", EditSelected}, {"paintSelected", PaintSelected},
+        {"reserveScene", ReserveScene}, {"sceneCapacity", SceneCapacity}, {"duplicateSelected", DuplicateSelected}, {"appendSelected", AppendSelected},
+        {"appendArrays", AppendArrays},
         {"contribReset", Call0<gsr_contrib_reset>}, {"contribAccumulate", Call0<gsr_contrib_accumulate_async>}, {"readContrib", ReadContrib},
         {"selectContrib", SelectContrib},
         {"setOverlay", SetOverlay}, {"readOverlay", ReadOverlay}, {"readOverlayPixels", ReadOverlayPixels},

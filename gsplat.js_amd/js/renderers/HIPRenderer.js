@@ -67,7 +67,12 @@ class HIPRenderer {
             // selection (setSelection), then the selected splats are edited there; kind 0 translate, 1 rotate, 2 scale
             editSelected: (kind, f64, pivot) => this._n.editSelected(this._h, kind, f64, pivot),
             paintSelected: (rgba, byteMask) => this._n.paintSelected(this._h, rgba, byteMask),
+            // Scene.duplicateSelection / Scene.append: the mask becomes the device copy's selection and the selected splats are copied
+            // behind the last one there; another Scene's four arrays are appended through the upload's repack.  Both return the new count.
+            duplicateSelected: () => grown(this._n.duplicateSelected(this._h)),
+            appendArrays: (data, positions, rotations, scales, m) => grown(this._n.appendArrays(this._h, data, positions, rotations, scales, m)),
         };
+        const grown = (r) => (vertexCount = r.first + r.count);
         const upload = () => {   // initWebGL's scene part: worker init + texImage2D (WebGLRenderer.ts:105-110,185-195)
             const s = activeScene, n = s.vertexCount, positions = s.positions, rotations = s.rotations, scales = s.scales;
             void s.shs_rgb;              // (SH mirrors of a followed limitBox are read back before the upload clears the context's SH state)
@@ -477,6 +482,18 @@ class HIPRenderer {
             const [value, byteMask] = Scene.rgbaWord(rgba);
             this._n.paintSelected(this._h, value, byteMask);
         };
+        // ---- growing the scene (gsr_scene_reserve / _capacity / _duplicate_selected / _append_selected): copies and pasted splats ----
+        //   renderer.selectRegion(lasso); const { first, count } = renderer.duplicateSelection();   // the copies are now the selection ...
+        //   renderer.translateSelection([1, 0, 0]);                                                  // ... so this moves them
+        //   renderer.reserveScene(renderer.sceneCapacity() * 2);    // a host that will copy many times: nothing is re-allocated until then
+        // The selected splats are copied bit for bit behind the scene's last splat -- appendSelectionFrom(other): the splats selected
+        // in another renderer of the same GPU, device to device -- and become the selection; existing indices, the hidden set and the
+        // contribution state stay.  These act on THIS renderer's device copy only: Scene.duplicateSelection(mask) / Scene.append(other)
+        // grow every device copy and keep the Scene's arrays right.  Refused while the device scene has SH rows.
+        this.reserveScene = (rows) => { this._n.reserveScene(this._h, rows); };
+        this.sceneCapacity = () => this._n.sceneCapacity(this._h);
+        this.duplicateSelection = () => { const r = this._n.duplicateSelected(this._h); grown(r); return r; };
+        this.appendSelectionFrom = (other) => { const r = this._n.appendSelected(this._h, other._h); grown(r); return r; };
         // ---- contribution (gsr_contrib_* / gsr_select_contrib): per splat of the device scene, what it showed over the frames of a tour ----
         //   renderer.resetContribution(); for (const cam of tour) { renderer.render(scene, cam); renderer.accumulateContribution(); }
         //   renderer.selectContribution({ stat: "pixels", below: 1 }); scene.eraseSelection(renderer.readSelection());   // what never showed

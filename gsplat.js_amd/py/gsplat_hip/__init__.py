@@ -125,6 +125,7 @@ EXPORTS = [
     "gsr_select_region", "gsr_select_box", "gsr_selection_set", "gsr_selection_invert", "gsr_read_selection", "gsr_scene_erase_selected",
     "gsr_hide_selected", "gsr_hidden_set", "gsr_read_hidden", "gsr_select_hidden",
     "gsr_selection_bounds", "gsr_scene_translate_selected", "gsr_scene_rotate_selected", "gsr_scene_scale_selected", "gsr_scene_set_rgba_selected",
+    "gsr_scene_reserve", "gsr_scene_capacity", "gsr_scene_duplicate_selected", "gsr_scene_append_selected", "gsr_scene_append_arrays",
     "gsr_contrib_reset", "gsr_contrib_accumulate_async", "gsr_read_contrib", "gsr_select_contrib",
     "gsr_set_overlay", "gsr_overlay_async", "gsr_read_overlay", "gsr_read_overlay_rgba8", "gsr_overlay_device_ptr", "gsr_delivery_set_overlay",
 ]
@@ -275,6 +276,11 @@ def load_library(path=None):
     L.gsr_scene_rotate_selected.argtypes = [vp, vp, vp]
     L.gsr_scene_scale_selected.argtypes = [vp, vp, vp]
     L.gsr_scene_set_rgba_selected.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32]
+    L.gsr_scene_reserve.argtypes = [vp, ctypes.c_uint32]
+    L.gsr_scene_capacity.argtypes = [vp, u32p]
+    L.gsr_scene_duplicate_selected.argtypes = [vp, u32p, u32p]
+    L.gsr_scene_append_selected.argtypes = [vp, vp, u32p, u32p]
+    L.gsr_scene_append_arrays.argtypes = [vp, vp, vp, vp, vp, ctypes.c_uint32, u32p]
     L.gsr_contrib_reset.argtypes = [vp]
     L.gsr_contrib_accumulate_async.argtypes = [vp]
     L.gsr_read_contrib.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, u32p]
@@ -988,6 +994,51 @@ class HIPRenderer:
             r, g, b, a = (int(v) & 0xff for v in rgba)
             rgba = r | g << 8 | b << 16 | a << 24
         self._check(self._L.gsr_scene_set_rgba_selected(self._ctx, int(rgba) & 0xffffffff, mask))
+
+    # -- growing the scene (gsr_scene_reserve / _capacity / _duplicate_selected / _append_selected / _append_arrays) --
+    def scene_reserve(self, rows):
+        """Make the device scene's arrays hold at least `rows` splats, so that duplicates and appends up to that count re-allocate
+        nothing and copy no old row.  Never shrinks; changes no splat and no frame state."""
+        self._check(self._L.gsr_scene_reserve(self._ctx, int(rows)))
+
+    def scene_capacity(self):
+        """Rows the device scene's arrays hold (at least scene_count())."""
+        rows = ctypes.c_uint32(0)
+        self._check(self._L.gsr_scene_capacity(self._ctx, ctypes.byref(rows)))
+        return rows.value
+
+    def scene_duplicate_selected(self):
+        """Copy the selected splats, in order and bit for bit, behind the scene's last splat; returns (first, count): the copies
+        are the splats [first, first + count) and become the selection, so scene_translate_selected moves them next.  Existing
+        indices, the hidden set and the contribution accumulators stay.  Nothing selected: (n, 0), nothing touched."""
+        first, count = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        self._check(self._L.gsr_scene_duplicate_selected(self._ctx, ctypes.byref(first), ctypes.byref(count)))
+        self._n = first.value + count.value
+        return first.value, count.value
+
+    def scene_append_selected(self, other):
+        """scene_duplicate_selected with the rows read from `other`'s device scene and its selection (same GPU, device to device;
+        `other` is not changed and its SH rows are not carried); returns (first, count)."""
+        first, count = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        self._check(self._L.gsr_scene_append_selected(self._ctx, other._ctx, ctypes.byref(first), ctypes.byref(count)))
+        self._n = first.value + count.value
+        return first.value, count.value
+
+    def scene_append_arrays(self, data, positions, rotations, scales):
+        """Append rows given as set_scene_arrays takes them (the same repack and check); returns the index of the first new
+        splat.  The new rows become the selection."""
+        data = np.ascontiguousarray(data, dtype=np.uint32).reshape(-1)
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1)
+        rot = np.ascontiguousarray(rotations, dtype=np.float32).reshape(-1)
+        scl = np.ascontiguousarray(scales, dtype=np.float32).reshape(-1)
+        m = pos.size // 3
+        if data.size < 8 * m or rot.size != 4 * m or scl.size != 3 * m:
+            raise ValueError("data / rotations / scales do not hold %d splats" % m)
+        first = ctypes.c_uint32(0)
+        self._check(self._L.gsr_scene_append_arrays(self._ctx, data.ctypes.data, pos.ctypes.data, rot.ctypes.data, scl.ctypes.data, m, ctypes.byref(first)))
+        self._n = first.value + m
+        self._scene = None if m else self._scene
+        return first.value
 
     # -- contribution (gsr_contrib_* / gsr_read_contrib / gsr_select_contrib): per-splat weight, peak and pixel counts over views --
     def contrib_reset(self):

@@ -656,6 +656,53 @@ int gsr_scene_rotate_selected(gsr_ctx *ctx, const double *q /* 4: x, y, z, w */,
 int gsr_scene_scale_selected(gsr_ctx *ctx, const double *s /* 3 */, const double *pivot /* 3, or NULL */);
 int gsr_scene_set_rgba_selected(gsr_ctx *ctx, uint32_t rgba, uint32_t byte_mask);
 
+/* ---- growing the scene ---- duplicate the selection, append another scene's selected splats or rows from the host, reserve capacity
+ * Every call above keeps the splat count or lowers it.  These raise it on the device: copy an object, paste one capture's splats
+ * into another scene, add rows -- with no gsr_read_scene / host loop / gsr_set_scene_arrays round trip (which re-uploads and
+ * re-allocates the whole scene, drops the selection, the hidden set and the accumulators, and takes the context out of a shared
+ * scene).  n is the count before the call ("Growing the scene").
+ * Duplicate: with idx the selected indices in ascending order and k their number, gsr_scene_duplicate_selected leaves a scene of
+ *   n + k splats.  Rows [0, n) are not written at all.  Row n + j holds the bits of row idx[j] in every per-splat array
+ *   (positions, covariance words, rgba, rotations, scales): the copy is bit for bit, NaNs and -0.0 included, with no arithmetic
+ *   and no re-packing of the covariance.  *first = n, *count = k (either pointer may be NULL).  k is the selection's count, which the
+ *   host already knows: nothing is read back to learn it.  With k == 0 the call returns GSR_OK with count 0, touches nothing and is
+ *   not an edit: the last frame stays valid.
+ * Append selected: gsr_scene_append_selected is duplicate with the rows read from `from`'s scene and `from`'s selection.  `from`
+ *   must be on the same device and its scene must have rotations / scales.  from == ctx, or a member of the same shared scene, is
+ *   exactly duplicate.  `from`'s scene, selection and frame state are not changed; its stream is waited for on the device, not on
+ *   the host.  `from`'s SH rows are not carried: the copies keep their rgba word.
+ * Append arrays: the m rows of gsr_scene_append_arrays go through the same repack and check as gsr_set_scene_arrays, into rows
+ *   [n, n + m); no new arithmetic.  A refused upload (GSR_ERR_SCENE: positions differ from data words 0..2) leaves everything as it
+ *   was, the count and the capacity included.  Rows [0, n) are not written.  A scene with no splats and no rotations / scales
+ *   accepts the call and becomes a scene with them.  *first = n (may be NULL); m == 0 touches nothing.
+ * State afterwards: the selection becomes exactly the new rows [first, first + count) -- a REPLACE, so the next
+ *   gsr_scene_translate_selected moves the copies -- and its version moves; the bits are set on the device, no upload proportional to
+ *   n is made.  The hidden set keeps its bits; new rows are visible, and so is the copy of a hidden selected splat.  The
+ *   contribution accumulators, if live, keep the old rows' values and `frames`; new rows start at zero (if never reset they stay
+ *   "never reset").  Indices of existing splats do not move.  The context stays in its shared scene.
+ * Capacity: the scene arrays hold gsr_scene_capacity rows, at least the count.  If n + k <= capacity nothing of the scene arrays is
+ *   re-allocated and no old row is copied.  Otherwise the arrays grow to max(n + k, capacity + capacity / 2), capped by the upload's
+ *   limit of 0x7fffffff / 8 splats, and the old rows are carried by device copies.  The selection, hidden and contribution buffers
+ *   grow with the capacity where they exist.  gsr_scene_reserve performs the growth alone, to exactly `rows`, for a host that will
+ *   copy an object many times: capacity >= rows afterwards, it never shrinks, no splat changes and no frame state changes.
+ *   gsr_scene_sharing's scene_bytes reports the capacity.  gsr_scene_limit_box and gsr_scene_erase_selected keep their behaviour
+ *   (the compacted arrays hold the old count's rows).
+ * Ordering: the calls are blocking scene replacements like gsr_scene_limit_box: the other members' streams are waited for, the work
+ *   runs on the context's stream, and every member re-sizes its per-splat buffers before its next frame.  They mark every member's
+ *   frame and sorted order as edited: gsr_select_region, gsr_pick, gsr_depth_async, gsr_contrib_accumulate_async and
+ *   gsr_overlay_async return GSR_ERR_ARG until the next frame.
+ * Refusals (GSR_ERR_ARG with a message, nothing touched): a NULL ctx; a NULL `from`; a NULL data / positions / rotations / scales
+ *   with m > 0; a destination without rotations / scales (but the empty scene of append arrays above); a `from` on another device or
+ *   without rotations / scales; n + k above the upload's limit; and a destination that has SH rows (sh_count != 0): SH rows are
+ *   indexed by splat order and the bands are index thresholds, so a row appended at the tail would fall into the top band and has no
+ *   SH row to read. */
+int gsr_scene_reserve(gsr_ctx *ctx, uint32_t rows);          /* capacity >= rows; never shrinks; no splat changes */
+int gsr_scene_capacity(gsr_ctx *ctx, uint32_t *rows);        /* no copy, no wait */
+int gsr_scene_duplicate_selected(gsr_ctx *ctx, uint32_t *first, uint32_t *count);
+int gsr_scene_append_selected(gsr_ctx *ctx, gsr_ctx *from, uint32_t *first, uint32_t *count);
+int gsr_scene_append_arrays(gsr_ctx *ctx, const uint32_t *data, const float *positions, const float *rotations,
+                            const float *scales, uint32_t m, uint32_t *first);
+
 /* ---- contribution ---- per-splat weight, peak and pixel counts over views
  * No interface of the reference stands behind this section either.  Every selector above is geometric; this one answers "which
  * splats never show" -- buried inside surfaces, hidden behind them, touching no pixel from any camera of a tour -- and with

@@ -91,6 +91,30 @@ def main():
                 wall.append((time.perf_counter() - t0) * 1e3)
             assert count == int(sel.sum())
             out["selection_bounds_wall"][key] = summary(wall)
+    # the duplicate leg (last: it grows the scene): the wall time of the blocking gsr_scene_duplicate_selected at the same fractions
+    # (random bits), on a scene uploaded afresh for every call, without and with gsr_scene_reserve making room first -- reserved,
+    # the call re-allocates nothing of the scene arrays and copies no old row
+    out["duplicate_wall"] = {}
+    rows = gh.synth.config_rows(args.config)
+    for frac in FRACTIONS:
+        k = int(round(frac * n))
+        sel = np.zeros(n, dtype=bool)
+        sel[rng.permutation(n)[:k]] = True
+        leg = {"count": k}
+        for form in ("plain", "reserved"):
+            wall = []
+            for _ in range(min(args.repeats, 5)):
+                r.set_scene_rows(rows)
+                assert r.set_selection(sel) == k
+                if form == "reserved":
+                    r.scene_reserve(n + k)
+                r.sync()
+                t0 = time.perf_counter()
+                first, count = r.scene_duplicate_selected()
+                wall.append((time.perf_counter() - t0) * 1e3)
+                assert (first, count) == (n, k) and r.scene_capacity() == (n if not k else n + k if form == "reserved" else max(n + k, n + n // 2))
+            leg[form] = summary(wall)
+        out["duplicate_wall"]["%g" % frac] = leg
     r.dispose()
     path = args.out or os.path.join(ROOT, "profiles", "edit_bench_%s.json" % out["build_id"])
     os.makedirs(os.path.dirname(path), exist_ok=True)

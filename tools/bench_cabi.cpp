@@ -3,7 +3,7 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--share-scene]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--share-scene]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
@@ -34,6 +34,10 @@
 // --edit-selected FRACTION selects that fraction of the splats (scattered over the indices) through gsr_selection_set on every device
 // copy and adds a leg with a gsr_scene_rotate_selected by one degree about y, pivoted, behind every frame: only the selection turns.
 // The report carries the leg's rate and `edit_ms`, the wall time a frame of that leg takes beyond a frame of the plain timed loop.
+// --duplicate FRACTION (last of all: it grows the scene) selects that fraction of the splats through gsr_selection_set and calls
+// gsr_scene_duplicate_selected twice -- the second call copies the first one's copies, the same count -- and reports the wall time
+// of either (`duplicate_ms`, `duplicate_again_ms`), the count and the capacity.  With --reserve, gsr_scene_reserve makes room for
+// both first (`reserve_ms`), so neither call re-allocates the scene arrays or copies an old row.
 //
 // Scene: the seeded synthetic generator of gsplat_hip/synth.py (mulberry32 counter PRNG, 24 draws per splat) written
 // out again in C++; log/exp/cos come from libm here and from numpy there, so a byte may differ in a rare rounding --
@@ -163,6 +167,8 @@ int main(int argc, char** argv)
     double hide_fraction = -1.0;   // < 0: off
     bool hide_edits = false;
     double edit_fraction = -1.0;   // < 0: off
+    double duplicate_fraction = -1.0;   // < 0: off
+    bool reserve = false;
     int32_t pick_xy[2] = {0, 0};
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -184,11 +190,13 @@ int main(int argc, char** argv)
         else if (a == "--hide" && i + 1 < argc) { hide_fraction = std::atof(argv[++i]); if (!(hide_fraction >= 0.0 && hide_fraction <= 1.0)) { std::fprintf(stderr, "--hide FRACTION must be in [0, 1]\n"); return 2; } }
         else if (a == "--hide-edits") hide_edits = true;
         else if (a == "--edit-selected" && i + 1 < argc) { edit_fraction = std::atof(argv[++i]); if (!(edit_fraction >= 0.0 && edit_fraction <= 1.0)) { std::fprintf(stderr, "--edit-selected FRACTION must be in [0, 1]\n"); return 2; } }
+        else if (a == "--duplicate" && i + 1 < argc) { duplicate_fraction = std::atof(argv[++i]); if (!(duplicate_fraction >= 0.0 && duplicate_fraction <= 1.0)) { std::fprintf(stderr, "--duplicate FRACTION must be in [0, 1]\n"); return 2; } }
+        else if (a == "--reserve") reserve = true;
         else if (a == "--scene-arrays") scene_arrays = true;
         else if (a == "--scene-edit") scene_edit = next();
         else if (a == "--share-scene") share_scene = true;
         else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--share-scene]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--share-scene]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
@@ -540,6 +548,29 @@ int main(int argc, char** argv)
         erase_hidden_ms = ms_since(t);
         CHECK(gsr_read_hidden(ctx[0], nullptr, 0, &edits_hidden));
     }
+    // --duplicate (last of all: it grows the scene): the selection duplicated on the device, twice
+    double duplicate_ms = 0, duplicate_again_ms = 0, reserve_ms = 0;
+    uint32_t dup_selected = 0, dup_first = 0, dup_count = 0, dup_capacity = 0, dup_n = 0;
+    if (duplicate_fraction >= 0.0) {
+        ctx0 = ctx[0];
+        CHECK(gsr_scene_count(ctx[0], &dup_n));
+        std::vector<uint32_t> words((dup_n + 31) / 32, 0u);
+        const uint64_t limit = (uint64_t)(duplicate_fraction * 4294967296.0);
+        for (uint32_t i = 0; i < dup_n; i++)
+            if ((uint64_t)((i + 0x85ebca6bu) * 2654435761u) < limit) words[i >> 5] |= 1u << (i & 31);
+        auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count() * 1e3; };
+        CHECK(gsr_selection_set(ctx[0], words.data(), (uint32_t)words.size(), GSR_SELOP_REPLACE, &dup_selected));
+        auto t = std::chrono::steady_clock::now();
+        if (reserve) { CHECK(gsr_scene_reserve(ctx[0], dup_n + 2 * dup_selected)); reserve_ms = ms_since(t); }
+        t = std::chrono::steady_clock::now();
+        CHECK(gsr_scene_duplicate_selected(ctx[0], &dup_first, &dup_count));
+        duplicate_ms = ms_since(t);
+        t = std::chrono::steady_clock::now();
+        CHECK(gsr_scene_duplicate_selected(ctx[0], nullptr, nullptr));
+        duplicate_again_ms = ms_since(t);
+        CHECK(gsr_scene_capacity(ctx[0], &dup_capacity));
+        CHECK(gsr_scene_count(ctx[0], &dup_n));
+    }
     char name[128] = "";
     int32_t cus = 0, khz = 0;
     (void)gsr_device_info(ctx[0], name, (int32_t)sizeof name, &cus, &khz);
@@ -587,6 +618,10 @@ int main(int argc, char** argv)
     if (edit_fraction >= 0.0)
         std::printf(", \"edit_selected_fraction\": %g, \"edit_selected\": %u, \"frames_per_sec_edit_selected\": %.1f, \"edit_ms\": %.4f", edit_fraction,
                     edit_selected, frames / edit_selected_sec, (edit_selected_sec - sec) / frames * 1e3);
+    if (duplicate_fraction >= 0.0)
+        std::printf(", \"duplicate_fraction\": %g, \"duplicate_first\": %u, \"duplicate_count\": %u, \"duplicate_reserved\": %s, \"reserve_ms\": %.4f, "
+                    "\"duplicate_ms\": %.4f, \"duplicate_again_ms\": %.4f, \"count_after\": %u, \"capacity_after\": %u",
+                    duplicate_fraction, dup_first, dup_count, reserve ? "true" : "false", reserve_ms, duplicate_ms, duplicate_again_ms, dup_n, dup_capacity);
     if (pick)
         std::printf(", \"pick\": {\"x\": %d, \"y\": %d, \"index\": %u, \"depth\": %s, \"mean\": %.9g, \"alpha\": %.9g}",
                     pick_xy[0], pick_xy[1], picked.index, picked.index == 0xffffffffu ? "null" : std::to_string(picked.depth).c_str(), (double)picked.mean, (double)picked.alpha);
