@@ -14,11 +14,6 @@ namespace {
 
 constexpr uint32_t MAX_ROWS = 0x7fffffffu / 8;   // the upload's limit (gsr_set_scene*)
 
-uint32_t words_of(uint32_t n) { return (n + 31u) / 32u; }
-// words select_ensure / hidden_ensure allocate at least for n splats
-uint32_t fold_words(uint32_t n) { return std::max((words_of(n) + 1u) & ~1u, 2u); }
-uint32_t counter_words(uint32_t words) { return 2u + (words + SELECT_APPLY_THREADS - 1u) / SELECT_APPLY_THREADS; }
-
 // the capacity a scene of `capacity` rows takes when it has to hold `need`
 uint32_t grown_rows(uint32_t capacity, uint32_t need)
 {
@@ -52,19 +47,20 @@ int grown_arrays(gsr_ctx* c, uint32_t rows, SceneArrays& dst)
 {
     const SharedScene& sc = *c->scene;
     if (int r = dst.alloc(c, rows, true)) return r;
-    const size_t n = sc.n;
-    if (!n) return GSR_OK;
-    const SceneArrays& a = sc.arr;
-    hipStream_t s = c->stream;
-    HIP_TRY(c, hipMemcpyAsync(dst.px, a.px, n * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(dst.py, a.py, n * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(dst.pz, a.pz, n * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(dst.cov0, a.cov0, n * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(dst.cov1, a.cov1, n * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(dst.cov2, a.cov2, n * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(dst.rgba, a.rgba, n * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(dst.rot, a.rot, n * 16, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(dst.scl, a.scl, n * 16, hipMemcpyDeviceToDevice, s));
+    return sc.n ? sc.arr.copy_rows(c, dst, sc.n, c->stream) : GSR_OK;
+}
+
+// a set that exists and holds less than `need` words regrown, its bits kept (scratch and spare are not carried, the counters' two
+// leading words are); old[0..3] take what it held
+int regrow_set(gsr_ctx* c, SplatSet& s, DevBuf<uint32_t>* spare, uint32_t need, DevBuf<uint32_t>* old)
+{
+    if (!s.mask || s.words >= need) return GSR_OK;
+    const uint32_t cw = counter_words(need);
+    int r;
+    if ((r = regrow(c, s.mask, s.words, need, old[0])) || (spare && (r = regrow(c, *spare, 0, need, old[3]))) ||
+        (r = regrow(c, s.scratch, 0, need, old[1])) || (r = regrow(c, s.counters, std::min<size_t>(s.counter_words, 2), cw, old[2])))
+        return r;
+    s.words = need; s.counter_words = cw;
     return GSR_OK;
 }
 
@@ -73,23 +69,9 @@ int grown_arrays(gsr_ctx* c, uint32_t rows, SceneArrays& dst)
 int grow_side_buffers(gsr_ctx* c, uint32_t rows, Retired& old)
 {
     SharedScene& sc = *c->scene;
-    const uint32_t need = fold_words(rows), cw = counter_words(need);
-    SharedScene::Selection& sel = sc.sel;
-    if (sel.mask && sel.words < need) {
-        int r;
-        if ((r = regrow(c, sel.mask, sel.words, need, old.words[0])) || (r = regrow(c, sel.scratch, 0, need, old.words[1])) ||
-            (r = regrow(c, sel.counters, std::min<size_t>(sel.counter_words, 2), cw, old.words[2])))
-            return r;
-        sel.words = need; sel.counter_words = cw;
-    }
-    SharedScene::Hidden& hid = sc.hid;
-    if (hid.mask && hid.words < need) {
-        int r;
-        if ((r = regrow(c, hid.mask, hid.words, need, old.words[3])) || (r = regrow(c, hid.spare, 0, need, old.words[4])) ||
-            (r = regrow(c, hid.scratch, 0, need, old.words[5])) || (r = regrow(c, hid.counters, std::min<size_t>(hid.counter_words, 2), cw, old.words[6])))
-            return r;
-        hid.words = need; hid.counter_words = cw;
-    }
+    const uint32_t need = fold_words(rows);
+    if (int r = regrow_set(c, sc.sel, nullptr, need, old.words)) return r;
+    if (int r = regrow_set(c, sc.hid, &sc.hid.spare, need, old.words + 3)) return r;
     SharedScene::Contrib& k = sc.contrib;
     if (k.live() && k.alloc_rows < rows) {
         int r;
@@ -145,13 +127,8 @@ int grow_commit(gsr_ctx* c, const char* who, uint32_t k, Retired& old)
     const uint32_t n = sc.n;
     if (int r = overlay_before_selection_change(c)) return r;   // the members' overlay passes in flight read the mask as it was
     SharedScene::Selection& sel = sc.sel;
-    if (!sel.mask) {   // never selected in (rows from the host, or from another scene): the buffers, for the capacity
-        const uint32_t need = fold_words(sc.arr_rows), cw = counter_words(need);
-        int r;
-        if ((r = sel.mask.alloc(c, need)) || (r = sel.scratch.alloc(c, need)) || (r = sel.counters.alloc(c, cw))) { sel.reset(); return r; }
-        sel.words = need; sel.counter_words = cw;
-        HIP_TRY(c, hipMemsetAsync(sel.counters, 0, (size_t)cw * 4, c->stream));
-    }
+    // never selected in (rows from the host, or from another scene): the buffers, for the capacity; every word of the mask is stored below
+    if (int r = set_ensure(c, sel, nullptr, sc.arr_rows, false)) return r;
     launch_append_select_range(sel.mask, sel.words, n, k, sel.counters, c->stream);
     hipError_t e0 = hipGetLastError();
     hipError_t e1 = hipStreamSynchronize(c->stream);
@@ -251,7 +228,7 @@ int gsr_scene_append_arrays(gsr_ctx* c, const uint32_t* data, const float* posit
     if (first) *first = n;
     if (!m) return GSR_OK;
     if (int r = grow_enter(c)) return r;
-    // The rows go through gsr_set_scene_arrays' repack and check into views offset by n -- of the scene's arrays where they hold
+    // The rows go through gsr_set_scene_arrays' repack and check (upload_rows, gsr_scene.cpp) into views offset by n -- of the scene's arrays where they hold
     // n + m rows, of larger ones filled beside them otherwise, which become the scene only once the upload is accepted: a refused
     // one (GSR_ERR_SCENE) leaves everything as it was, the capacity included.  Rows [0, n) are not written either way.
     const bool grow = n + m > sc.arr_rows || !sc.arr.rot;
@@ -259,26 +236,9 @@ int gsr_scene_append_arrays(gsr_ctx* c, const uint32_t* data, const float* posit
     SceneArrays fresh;
     if (grow) { if (int r = grown_arrays(c, rows, fresh)) return r; }
     const SceneDev v = grow ? fresh.view() : sc.arr.view();
-    {
-        DevBuf<uint32_t> d_data, d_flag;
-        DevBuf<float> d_pos, d_scl;
-        int r;
-        if ((r = d_data.alloc(c, (size_t)m * 8)) || (r = d_pos.alloc(c, (size_t)m * 3)) || (r = d_scl.alloc(c, (size_t)m * 3)) || (r = d_flag.alloc(c, 1))) return r;
-        hipStream_t s = c->stream;
-        hipError_t e1 = hipMemcpyAsync(d_data, data, (size_t)m * 32, hipMemcpyHostToDevice, s);
-        hipError_t e2 = hipMemcpyAsync(d_pos, positions, (size_t)m * 12, hipMemcpyHostToDevice, s);
-        hipError_t e3 = hipMemsetAsync(d_flag, 0, 4, s);
-        launch_repack_scene(d_data, d_pos, m, v.px + n, v.py + n, v.pz + n, v.cov0 + n, v.cov1 + n, v.cov2 + n, v.rgba + n, d_flag, s);
-        hipError_t e4 = hipMemcpyAsync(v.rot + n, rotations, (size_t)m * 16, hipMemcpyHostToDevice, s);   // rotations are `rot`'s bytes already
-        hipError_t e5 = hipMemcpyAsync(d_scl, scales, (size_t)m * 12, hipMemcpyHostToDevice, s);
-        launch_scene_import(d_scl, m, v.scl + n, s);
-        uint32_t flag = 0;
-        hipError_t e6 = hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s);
-        hipError_t e7 = hipStreamSynchronize(s);
-        for (hipError_t e : {e1, e2, e3, e4, e5, e6, e7, hipGetLastError()})
-            if (e != hipSuccess) return fail(c, GSR_ERR_HIP, "%s failed: %s", who, hipGetErrorString(e));
-        if (flag) return fail(c, GSR_ERR_SCENE, "%s: positions differ from data words 0..2 (Scene.ts:141-143 keeps them equal)", who);
-    }
+    uint32_t flag = 0;
+    if (int r = upload_rows(c, who, v, n, m, data, positions, rotations, scales, &flag)) return r;
+    if (flag) return fail(c, GSR_ERR_SCENE, "%s: positions differ from data words 0..2 (Scene.ts:141-143 keeps them equal)", who);
     Retired old;
     if (grow) {
         std::swap(sc.arr, fresh);

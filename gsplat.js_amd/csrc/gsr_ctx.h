@@ -102,18 +102,62 @@ struct SceneArrays {
     DevBuf<float> px, py, pz;
     DevBuf<uint32_t> cov0, cov1, cov2, rgba;
     DevBuf<float4> rot, scl;   // rotations / scales, only for scenes built on the device from .splat rows
-    int alloc(gsr_ctx* c, size_t n, bool with_rows)
+    // the one list of the arrays (view() beside it names them in SceneDev's order): f(a's array, b's, whether it is one of the
+    // two that only scenes with rotations and scales have), until one returns non-zero
+    template <class A, class B, class F>
+    static int each(A& a, B& b, F f)
     {
         int r;
-        if ((r = px.alloc(c, n)) || (r = py.alloc(c, n)) || (r = pz.alloc(c, n)) || (r = cov0.alloc(c, n)) || (r = cov1.alloc(c, n)) ||
-            (r = cov2.alloc(c, n)) || (r = rgba.alloc(c, n)))
+        if ((r = f(a.px, b.px, false)) || (r = f(a.py, b.py, false)) || (r = f(a.pz, b.pz, false)) || (r = f(a.cov0, b.cov0, false)) ||
+            (r = f(a.cov1, b.cov1, false)) || (r = f(a.cov2, b.cov2, false)) || (r = f(a.rgba, b.rgba, false)) ||
+            (r = f(a.rot, b.rot, true)) || (r = f(a.scl, b.scl, true)))
             return r;
-        rot.reset(); scl.reset();
-        if (with_rows && ((r = rot.alloc(c, n)) || (r = scl.alloc(c, n)))) return r;
         return GSR_OK;
+    }
+    int alloc(gsr_ctx* c, size_t n, bool with_rows)
+    {
+        return each(*this, *this, [&](auto& buf, auto&, bool rows_only) -> int {
+            if (rows_only && !with_rows) { buf.reset(); return GSR_OK; }
+            return buf.alloc(c, n);
+        });
+    }
+    // the first n rows of every array into dst's, device to device on `s` (both sets with rotations and scales)
+    int copy_rows(gsr_ctx* c, SceneArrays& dst, size_t n, hipStream_t s) const
+    {
+        return each(*this, dst, [&](const auto& from, auto& to, bool) -> int {
+            HIP_TRY(c, hipMemcpyAsync(to, from, n * sizeof(*from.p), hipMemcpyDeviceToDevice, s));
+            return GSR_OK;
+        });
+    }
+    // bytes of one row over the arrays that are allocated
+    size_t row_bytes() const
+    {
+        size_t t = 0;
+        each(*this, *this, [&](const auto& buf, const auto&, bool) -> int { if (buf) t += sizeof(*buf.p); return GSR_OK; });
+        return t;
     }
     SceneDev view() const { return SceneDev{px, py, pz, cov0, cov1, cov2, rgba, rot, scl}; }
 };
+
+// A set of splats, one bit per splat of a scene: bit i & 31 of word i >> 5, bits at and above the scene's count always 0
+// (k_splat_ops.h has the device's side of the layout).  The selection and the hidden set are one each; the functions that size,
+// allocate, fold, read back and regrow them are declared below (set_*, gsr_select.cpp).
+struct SplatSet {
+    DevBuf<uint32_t> mask, scratch;   // `words` words each: the set, and the picked / folded set of the call in progress
+    DevBuf<uint32_t> counters;        // [0] the bits set after the last fold, [1] a picker's `invalid` word, [2..] per-workgroup sums
+    uint32_t words = 0;               // words the word buffers were allocated for (even, >= ceil(n / 32))
+    uint32_t counter_words = 0;
+    uint32_t count = 0;               // bits set: every call is blocking and returns with it final
+    void reset() { mask.reset(); scratch.reset(); counters.reset(); words = counter_words = 0; count = 0; }
+    uint64_t bytes() const { return (uint64_t)words * 8 + (uint64_t)counter_words * 4; }
+};
+// The sizes, each stated once.  words_of: the words that hold n splats' bits.  fold_words: the words a set is allocated with and a
+// fold runs over for `rows` splats (even, as the box picker's ballots store whole pairs; the count only shrinks under a set, so
+// one allocated for more holds these).  counter_words: the counters of a set of that many words.  op_ok: the ops a caller may name.
+inline uint32_t words_of(uint32_t n) { return (n + 31u) / 32u; }
+inline uint32_t fold_words(uint32_t rows) { return std::max((words_of(rows) + 1u) & ~1u, 2u); }
+inline uint32_t counter_words(uint32_t words) { return 2u + (words + SELECT_APPLY_THREADS - 1u) / SELECT_APPLY_THREADS; }
+inline bool op_ok(int32_t op) { return op >= GSR_SELOP_REPLACE && op <= GSR_SELOP_INTERSECT; }
 
 // The scene state its members hold once (DESIGN.md section 2, and section 4 "Shared scenes"): the per-splat arrays, the SH textures and their spare set, the SH
 // frame and the splat count.  It owns these buffers; the contexts that render it are listed in `members` (no leader: the last one
@@ -159,29 +203,20 @@ struct SharedScene {
                      sh_rows = sh_spare_rows = 0; }
     // The selection (gsr_select.cpp; DESIGN.md section 4, "Selection"): one bit per splat of THIS copy, so the members have one
     // together.  Nothing is allocated until the first call that selects; a scene without buffers reads as all zeros.
-    struct Selection {
-        DevBuf<uint32_t> mask, scratch;   // `words` words each: the selection, and the picked set of the call in progress
-        DevBuf<uint32_t> counters;        // [0] the bits set after the last fold, [1] a picker's `invalid` word, [2..] per-workgroup sums
+    struct Selection : SplatSet {
         DevBuf<uint8_t> region;           // the region bytes of gsr_select_region: grows on demand
-        uint32_t words = 0;               // words `mask` and `scratch` were allocated for (even, >= ceil(n / 32))
-        uint32_t counter_words = 0;
         size_t region_bytes = 0;
-        uint32_t count = 0;               // bits set: every call is blocking and returns with it final
-        void reset() { mask.reset(); scratch.reset(); counters.reset(); region.reset(); words = counter_words = 0; region_bytes = 0; count = 0; }
-        uint64_t bytes() const { return (uint64_t)words * 8 + (uint64_t)counter_words * 4 + region_bytes; }
+        void reset() { SplatSet::reset(); region.reset(); region_bytes = 0; }
+        uint64_t bytes() const { return SplatSet::bytes() + region_bytes; }
     } sel;
-    // The hidden set (gsr_hidden.cpp; DESIGN.md section 4, "Hidden splats"): one bit per splat of THIS copy, the selection's layout,
-    // so the members have one together.  A hidden splat fails the projection's culls (k_project_key reads `mask` while count != 0).
-    // Nothing is allocated until the first call that hides; a scene without buffers reads as all zeros.  Unlike the selection it
-    // survives a compaction: scene_compact carries it into `spare` (k_box_compact_bits), then the two change places.
-    struct Hidden {
-        DevBuf<uint32_t> mask, spare, scratch;   // `words` words each: the set, the other buffer of a compaction, the folded set of the call in progress
-        DevBuf<uint32_t> counters;               // [0] the bits set after the last fold, [1] reserved, [2..] per-workgroup sums
-        uint32_t words = 0;                      // words the three were allocated for (even, >= ceil(n / 32))
-        uint32_t counter_words = 0;
-        uint32_t count = 0;                      // bits set: every call is blocking and returns with it final
-        void reset() { mask.reset(); spare.reset(); scratch.reset(); counters.reset(); words = counter_words = 0; count = 0; }
-        uint64_t bytes() const { return (uint64_t)words * 12 + (uint64_t)counter_words * 4; }
+    // The hidden set (gsr_hidden.cpp; DESIGN.md section 4, "Hidden splats"): one bit per splat of THIS copy, so the members have
+    // one together.  A hidden splat fails the projection's culls (k_project_key reads `mask` while count != 0).  Nothing is
+    // allocated until the first call that hides; a scene without buffers reads as all zeros.  Unlike the selection it survives
+    // a compaction: scene_compact carries it into `spare` (k_box_compact_bits), then the two change places.
+    struct Hidden : SplatSet {
+        DevBuf<uint32_t> spare;           // `words` words: the other buffer of a compaction
+        void reset() { SplatSet::reset(); spare.reset(); }
+        uint64_t bytes() const { return SplatSet::bytes() + (uint64_t)words * 4; }
     } hid;
     // Moves with every call that changes the selection's bits (the folds of gsr_select.cpp) or drops them (a new scene, a compaction):
     // a member's overlay image (gsr_overlay.cpp) is the selection's while the version it was enqueued for is this one.
@@ -204,7 +239,7 @@ struct SharedScene {
     // device bytes of the state the members hold once
     uint64_t bytes() const
     {
-        return (uint64_t)arr_rows * (7 * 4 + (arr.rot ? 32 : 0)) + ((uint64_t)sh_rows + sh_spare_rows) * 3 * 32 + sel.bytes() + contrib.bytes() + hid.bytes();
+        return (uint64_t)arr_rows * arr.row_bytes() + ((uint64_t)sh_rows + sh_spare_rows) * 3 * 32 + sel.bytes() + contrib.bytes() + hid.bytes();
     }
 };
 
@@ -533,6 +568,10 @@ int sync_members(gsr_ctx* c);
 // order, become the scene; SH state, generation, bins and the members' frame state as the header says of limitBox; the selection is
 // empty afterwards.  `what` names the caller in a HIP error.
 int scene_compact(gsr_ctx* c, const ScenePred& p, const char* what, uint32_t* kept_out);
+// the host upload path of gsr_set_scene / gsr_set_scene_arrays and gsr_scene_append_arrays: m host rows staged, repacked and checked
+// into rows [at, at + m) of `v` (rotations / scales null: a scene without them); *mismatch: positions differ from data words 0..2
+int upload_rows(gsr_ctx* c, const char* what, const SceneDev& v, uint32_t at, uint32_t m, const uint32_t* data, const float* positions,
+                const float* rotations, const float* scales, uint32_t* mismatch);
 // Device-side order around an edit of a shared scene that arrives through `c` (translate, rotate, scale, a change of the hidden
 // set), no host wait: edit_begin makes c's stream wait for what every other member has enqueued, edit_end makes whatever the
 // others enqueue from now on wait for the edit; invalidate_members marks every member's frame state as edited (lists: the sorted
@@ -543,10 +582,20 @@ void invalidate_members(gsr_ctx* c, bool lists);
 // GSR_ERR_ARG with the message unless the scene carries rotations and scales (built from rows or from the four arrays): what the
 // transforms, the compactions and the edits of the selection all demand first
 int require_rows(gsr_ctx* c);
-// gsr_hidden.cpp: the hidden set's buffers for the scene's count, allocated (the mask zeroed) by the first call that needs them
+// gsr_select.cpp, for either set (`spare`: the hidden set's third word buffer, null for the selection).
+// set_ensure: the buffers for `rows` splats, allocated by the first call that needs them -- nothing happens while the set holds
+// that many; the counters are zeroed, and the mask unless the caller stores every word of it (zero_mask false).
+int set_ensure(gsr_ctx* c, SplatSet& s, DevBuf<uint32_t>* spare, uint32_t rows, bool zero_mask = true);
+// set_count: the end of every fold of a set (launch_select_apply, which leaves the bits set in the set's counters): that count to
+// the host and into s.count -- the copy, the wait for the stream, and "<what> failed: .." for an error of either or of a launch
+// in front of them.  The launch stays with the callers: what lies between it and the copy differs (nothing for the selection,
+// edit_end for the hidden set, the compaction's other counts for scene_compact's carry).
+int set_count(gsr_ctx* c, SplatSet& s, const char* what);
+// gsr_read_selection / gsr_read_hidden (`who`): the count and ceil(n / 32) words, zeros from a set never allocated
+int set_read(gsr_ctx* c, const SplatSet& s, const char* who, uint32_t* words, uint32_t nwords, uint32_t* count);
+// the two sets for the scene's count (set_ensure), and the end of every call that changes the selection:
+// selection <- selection (op) scratch on the device, its count back to the host
 int hidden_ensure(gsr_ctx* c);
-// gsr_select.cpp: the selection's buffers for the scene's count, allocated (the mask zeroed) by the first call that needs them; and
-// the end of every call that changes the selection: selection <- selection (op) scratch on the device, its count back to the host
 int select_ensure(gsr_ctx* c);
 int select_fold_and_count(gsr_ctx* c, int op, uint32_t* selected);
 // gsr_comm.cpp

@@ -11,12 +11,6 @@ using namespace gsr;
 
 namespace {
 
-uint32_t words_of(uint32_t n) { return (n + 31u) / 32u; }
-// words a fold runs over for n splats: what select_ensure and hidden_ensure allocate at least (even, as the box picker's ballots
-// store whole pairs), so both masks hold this many whatever count they were allocated for (the count only shrinks under them)
-uint32_t fold_words(uint32_t n) { return std::max((words_of(n) + 1u) & ~1u, 2u); }
-bool op_ok(int32_t op) { return op >= GSR_SELOP_REPLACE && op <= GSR_SELOP_INTERSECT; }
-
 // H <- H (op) P as a scene edit; P: `dev` (device words, at least fold_words(n) of them), or `host` (ceil(n / 32) words), or the empty set
 int hidden_fold(gsr_ctx* c, const uint32_t* dev, const uint32_t* host, int op, uint32_t* hidden)
 {
@@ -36,34 +30,14 @@ int hidden_fold(gsr_ctx* c, const uint32_t* dev, const uint32_t* host, int op, u
     launch_select_apply(op, hid.mask, dev, sc.n, nw, hid.counters + 2, hid.counters, c->stream);   // (host bits at and above n are dropped there)
     HIP_TRY(c, hipGetLastError());
     if (int r = edit_end(c)) return r;
-    uint32_t count = 0;
-    hipError_t e1 = hipMemcpyAsync(&count, hid.counters, 4, hipMemcpyDeviceToHost, c->stream);
-    hipError_t e2 = hipStreamSynchronize(c->stream);
-    for (hipError_t e : {e1, e2, hipGetLastError()})
-        if (e != hipSuccess) return fail(c, GSR_ERR_HIP, "hidden set update failed: %s", hipGetErrorString(e));
-    hid.count = count;
-    if (hidden) *hidden = count;
+    if (int r = set_count(c, hid, "hidden set update")) return r;
+    if (hidden) *hidden = hid.count;
     return GSR_OK;
 }
 
 }  // namespace
 
-int gsr::hidden_ensure(gsr_ctx* c)
-{
-    SharedScene& sc = *c->scene;
-    SharedScene::Hidden& hid = sc.hid;
-    const uint32_t need = fold_words(sc.n);
-    if (hid.words >= need && hid.mask) return GSR_OK;
-    // (the count only shrinks under a hidden set -- a new scene resets it, a compaction keeps the buffers -- so there are no bits to carry over)
-    hid.reset();
-    const uint32_t cw = 2u + (need + SELECT_APPLY_THREADS - 1u) / SELECT_APPLY_THREADS;
-    int r;
-    if ((r = hid.mask.alloc(c, need)) || (r = hid.spare.alloc(c, need)) || (r = hid.scratch.alloc(c, need)) || (r = hid.counters.alloc(c, cw))) { hid.reset(); return r; }
-    hid.words = need; hid.counter_words = cw;
-    HIP_TRY(c, hipMemsetAsync(hid.mask, 0, (size_t)need * 4, c->stream));
-    HIP_TRY(c, hipMemsetAsync(hid.counters, 0, (size_t)cw * 4, c->stream));
-    return GSR_OK;
-}
+int gsr::hidden_ensure(gsr_ctx* c) { return set_ensure(c, c->scene->hid, &c->scene->hid.spare, c->scene->n); }
 
 extern "C" {
 
@@ -87,19 +61,7 @@ int gsr_hidden_set(gsr_ctx* c, const uint32_t* words, uint32_t nwords, int32_t o
 int gsr_read_hidden(gsr_ctx* c, uint32_t* words, uint32_t nwords, uint32_t* hidden)
 {
     if (!c) return GSR_ERR_ARG;
-    const SharedScene& sc = *c->scene;
-    const uint32_t need = words_of(sc.n);
-    if (words && nwords < need) return fail(c, GSR_ERR_ARG, "gsr_read_hidden: nwords (%u) is smaller than ceil(%u / 32) = %u", nwords, sc.n, need);
-    if (hidden) *hidden = sc.hid.mask ? sc.hid.count : 0u;
-    if (!words || !need) return GSR_OK;
-    if (!sc.hid.mask) {   // never hid anything: all zeros
-        std::fill(words, words + need, 0u);
-        return GSR_OK;
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(words, sc.hid.mask, (size_t)need * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return GSR_OK;
+    return set_read(c, c->scene->hid, "gsr_read_hidden", words, nwords, hidden);
 }
 
 // a picker like the others: P = H into the selection's scratch, then the selection's own fold (which waits for overlay passes in

@@ -85,8 +85,9 @@ void launch_scene_translate(uint32_t n, const SceneDev& sc, const double* t, hip
 void launch_scene_rotate(uint32_t n, const SceneDev& sc, const double* q_xyzw, hipStream_t s);
 void launch_scene_scale(uint32_t n, const SceneDev& sc, const double* sv, hipStream_t s);
 // The order-preserving compaction (Scene.limitBox, gsr_scene_erase_selected) and which splats stay: those inside `box` (six f64,
-// limitBox's comparisons), or, with box null, those whose bit of the selection words `mask` equals `keep`.
-struct ScenePred { const double* box; const uint32_t* mask; uint32_t keep; };
+// limitBox's comparisons), or, with box null, those whose bit of the mask_words selection words `mask` equals `keep` (a word
+// behind them reads as zero).
+struct ScenePred { const double* box; const uint32_t* mask; uint32_t keep; uint32_t mask_words; };
 void launch_scene_compact(uint32_t n, const SceneDev& src, const SceneDev& dst, const ScenePred& p, uint32_t* block_count,
                           uint32_t* total, hipStream_t s);
 // The compaction of a scene whose SH colour follows it, enqueued behind launch_scene_compact while `src` still holds the source

@@ -1,6 +1,7 @@
 // The scene on the device: upload (packed words, the Scene's four arrays or .splat rows), the transforms and the compaction of
 // scenes that carry rotations and scales, spherical harmonics, and the scene's read-back.  alloc_scene sizes everything that holds one entry per splat.
 #include "gsr_ctx.h"
+#include "k_splat_ops.h"
 
 #include <cmath>
 
@@ -132,6 +133,38 @@ int gsr::adopt_scene(gsr_ctx* c)
     return GSR_OK;
 }
 
+// The host upload path, for a new scene (rows from 0) and for rows appended behind a scene's last (gsr_append.cpp): m rows of
+// Scene.data and Scene.positions staged and repacked into rows [at, at + m) of `v` with the repack's check, and, when given,
+// rotations (`rot`'s bytes already) and scales beside them; *mismatch <- the check's flag; waits for the stream.  An error of a
+// copy, the wait or a launch is "<what> failed: ..".  Covariance words and colours stay the caller's.
+int gsr::upload_rows(gsr_ctx* c, const char* what, const SceneDev& v, uint32_t at, uint32_t m, const uint32_t* data, const float* positions,
+                     const float* rotations, const float* scales, uint32_t* mismatch)
+{
+    DevBuf<uint32_t> d_data, d_flag;
+    DevBuf<float> d_pos, d_scl;
+    int r;
+    if ((r = d_data.alloc(c, (size_t)m * 8)) || (r = d_pos.alloc(c, (size_t)m * 3)) || (r = d_flag.alloc(c, 1)) ||
+        (rotations && (r = d_scl.alloc(c, (size_t)m * 3))))
+        return r;
+    hipStream_t s = c->stream;
+    hipError_t e[8] = {};   // (hipSuccess)
+    e[0] = hipMemcpyAsync(d_data, data, (size_t)m * 32, hipMemcpyHostToDevice, s);
+    e[1] = hipMemcpyAsync(d_pos, positions, (size_t)m * 12, hipMemcpyHostToDevice, s);
+    e[2] = hipMemsetAsync(d_flag, 0, 4, s);
+    launch_repack_scene(d_data, d_pos, m, v.px + at, v.py + at, v.pz + at, v.cov0 + at, v.cov1 + at, v.cov2 + at, v.rgba + at, d_flag, s);
+    if (rotations) {
+        e[3] = hipMemcpyAsync(v.rot + at, rotations, (size_t)m * 16, hipMemcpyHostToDevice, s);
+        e[4] = hipMemcpyAsync(d_scl, scales, (size_t)m * 12, hipMemcpyHostToDevice, s);
+        launch_scene_import(d_scl, m, v.scl + at, s);
+    }
+    e[5] = hipMemcpyAsync(mismatch, d_flag, 4, hipMemcpyDeviceToHost, s);
+    e[6] = hipStreamSynchronize(s);
+    e[7] = hipGetLastError();
+    for (hipError_t x : e)
+        if (x != hipSuccess) return fail(c, GSR_ERR_HIP, "%s failed: %s", what, hipGetErrorString(x));
+    return GSR_OK;
+}
+
 namespace {
 
 int need_rows(gsr_ctx* c)
@@ -155,25 +188,8 @@ int upload_scene(gsr_ctx* c, const uint32_t* data, const float* positions, const
     // has, its SH state and its last frame as they were.  The arrays are filled beside the old ones and swapped in afterwards.
     SceneArrays sa;
     if (n) {
-        DevBuf<uint32_t> d_data, d_flag;
-        DevBuf<float> d_pos, d_scl;
-        if ((r = sa.alloc(c, n, with_rows)) || (r = d_data.alloc(c, (size_t)n * 8)) || (r = d_pos.alloc(c, (size_t)n * 3)) || (r = d_flag.alloc(c, 1))) return r;
-        hipError_t e1 = hipMemcpyAsync(d_data, data, (size_t)n * 32, hipMemcpyHostToDevice, c->stream);
-        hipError_t e2 = hipMemcpyAsync(d_pos, positions, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
-        hipError_t e3 = hipMemsetAsync(d_flag, 0, 4, c->stream);
-        launch_repack_scene(d_data, d_pos, n, sa.px, sa.py, sa.pz, sa.cov0, sa.cov1, sa.cov2, sa.rgba, d_flag, c->stream);
-        hipError_t e6 = hipSuccess, e7 = hipSuccess;
-        if (with_rows) {   // covariance words and colours stay the caller's; rotations are `rot`'s bytes already
-            if ((r = d_scl.alloc(c, (size_t)n * 3))) return r;
-            e6 = hipMemcpyAsync(sa.rot, rotations, (size_t)n * 16, hipMemcpyHostToDevice, c->stream);
-            e7 = hipMemcpyAsync(d_scl, scales, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
-            launch_scene_import(d_scl, n, sa.scl, c->stream);
-        }
         uint32_t flag = 0;
-        hipError_t e4 = hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, c->stream);
-        hipError_t e5 = hipStreamSynchronize(c->stream);
-        for (hipError_t e : {e1, e2, e3, e4, e5, e6, e7, hipGetLastError()})
-            if (e != hipSuccess) return fail(c, GSR_ERR_HIP, "scene upload failed: %s", hipGetErrorString(e));
+        if ((r = sa.alloc(c, n, with_rows)) || (r = upload_rows(c, "scene upload", sa.view(), 0, n, data, positions, rotations, scales, &flag))) return r;
         if (flag) return fail(c, GSR_ERR_SCENE, "positions differ from data words 0..2 (Scene.ts:141-143 keeps them equal)");
     }
     if ((r = alloc_scene(c, n, with_rows))) return r;
@@ -218,21 +234,22 @@ int gsr::scene_compact(gsr_ctx* c, const ScenePred& p, const char* what, uint32_
         // its count again (an empty fold: H' |= nothing).  Only while something is hidden: an empty set stays the zeros it is.
         SharedScene::Hidden& hid = sc.hid;
         const bool carry = hid.mask && hid.count;
-        uint32_t hidden_kept = 0;
-        hipError_t e0 = hipSuccess, e3 = hipSuccess, e4 = hipSuccess;
+        hipError_t e0 = hipSuccess, e2 = hipSuccess, e3 = hipSuccess;
         if (carry) {
             e0 = hipMemsetAsync(hid.spare, 0, (size_t)hid.words * 4, c->stream);
             launch_scene_compact_bits(n, sc.arr.view(), p, block_count, hid.mask, hid.words, hid.spare, hid.words, c->stream);
             e3 = hipMemsetAsync(hid.scratch, 0, (size_t)hid.words * 4, c->stream);
             launch_select_apply(SELOP_ADD, hid.spare, hid.scratch, n, hid.words, hid.counters + 2, hid.counters, c->stream);
-            e4 = hipMemcpyAsync(&hidden_kept, hid.counters, 4, hipMemcpyDeviceToHost, c->stream);
         }
         hipError_t e1 = hipMemcpyAsync(counts, count, follow ? 16 : 4, hipMemcpyDeviceToHost, c->stream);
-        hipError_t e2 = hipStreamSynchronize(c->stream);
-        for (hipError_t e : {e0, e1, e2, e3, e4, hipGetLastError()})
+        if (carry) {   // (its count back: the call's one wait)
+            if ((r = set_count(c, hid, what))) return r;
+            std::swap(hid.mask, hid.spare);
+        }
+        else e2 = hipStreamSynchronize(c->stream);
+        for (hipError_t e : {e0, e1, e2, e3, hipGetLastError()})
             if (e != hipSuccess) return fail(c, GSR_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
         kept = counts[0];
-        if (carry) { std::swap(hid.mask, hid.spare); hid.count = hidden_kept; }
         std::swap(sc.arr, dst);
         sc.arr_rows = n;   // (what `dst` was allocated for)
         sc.n = kept;   // arrays keep their old capacity; per-frame buffers sized for the old count still fit
@@ -323,11 +340,9 @@ int gsr_scene_rotate(gsr_ctx* c, const double* q)
     launch_scene_rotate(c->scene->n, c->scene->arr.view(), q, c->stream);
     HIP_TRY(c, hipGetLastError());
     if (int r = edit_end(c)) return r;
-    if (c->scene->sh_follow && c->scene->sh_count) {   // Linv <- Linv . R(q)^T, R as k_scene_rotate builds it (the frame belongs to an SH state)
-        const double x = q[0], y = q[1], z = q[2], w = q[3];
-        const double R[9] = {1 - 2 * y * y - 2 * z * z, 2 * x * y - 2 * z * w, 2 * x * z + 2 * y * w,
-                             2 * x * y + 2 * z * w, 1 - 2 * x * x - 2 * z * z, 2 * y * z - 2 * x * w,
-                             2 * x * z - 2 * y * w, 2 * y * z + 2 * x * w, 1 - 2 * x * x - 2 * y * y};
+    if (c->scene->sh_follow && c->scene->sh_count) {   // Linv <- Linv . R(q)^T, R as the kernels build it (k_splat_ops.h) (the frame belongs to an SH state)
+        double R[9];
+        quat_matrix(q[0], q[1], q[2], q[3], R);
         double* L = c->scene->sh_frame;
         double out[9];
         for (int i = 0; i < 3; i++)
@@ -363,7 +378,7 @@ int gsr_scene_limit_box(gsr_ctx* c, const double* box, uint32_t* new_count)
     if (box[0] >= box[1]) return fail(c, GSR_ERR_ARG, "xMin (%g) must be smaller than xMax (%g)", box[0], box[1]);   // Scene.ts:308-316
     if (box[2] >= box[3]) return fail(c, GSR_ERR_ARG, "yMin (%g) must be smaller than yMax (%g)", box[2], box[3]);
     if (box[4] >= box[5]) return fail(c, GSR_ERR_ARG, "zMin (%g) must be smaller than zMax (%g)", box[4], box[5]);
-    return scene_compact(c, ScenePred{box, nullptr, 0u}, "limitBox", new_count);
+    return scene_compact(c, ScenePred{box, nullptr, 0u, 0u}, "limitBox", new_count);
 }
 
 int gsr_share_scene(gsr_ctx* c, gsr_ctx* from)

@@ -7,29 +7,56 @@
 
 using namespace gsr;
 
-namespace {
-
-uint32_t words_of(uint32_t n) { return (n + 31u) / 32u; }
-
-}  // namespace
-
-// the selection's buffers for the scene's count, allocated (the mask zeroed) by the first call that needs them
-int gsr::select_ensure(gsr_ctx* c)
+// ---- what the selection and the hidden set share (gsr_ctx.h, SplatSet) ----
+int gsr::set_ensure(gsr_ctx* c, SplatSet& s, DevBuf<uint32_t>* spare, uint32_t rows, bool zero_mask)
 {
-    SharedScene& sc = *c->scene;
-    SharedScene::Selection& sel = sc.sel;
-    const uint32_t need = std::max((words_of(sc.n) + 1u) & ~1u, 2u);   // even: a wave's ballot is two whole words (k_select_box)
-    if (sel.words >= need && sel.mask) return GSR_OK;
-    // (the count only shrinks under a selection -- a new scene or a compaction resets it -- so there are no bits to carry over)
-    sel.reset();
-    const uint32_t cw = 2u + (need + SELECT_APPLY_THREADS - 1u) / SELECT_APPLY_THREADS;
+    const uint32_t need = fold_words(rows), cw = counter_words(need);
+    if (s.words >= need && s.mask) return GSR_OK;
+    // (the count only shrinks under a set -- a new scene resets it, a compaction drops the selection and keeps the hidden set's
+    // buffers, growth regrows them first -- so there are no bits to carry over)
+    s.reset();
+    if (spare) spare->reset();
     int r;
-    if ((r = sel.mask.alloc(c, need)) || (r = sel.scratch.alloc(c, need)) || (r = sel.counters.alloc(c, cw))) { sel.reset(); return r; }
-    sel.words = need; sel.counter_words = cw;
-    HIP_TRY(c, hipMemsetAsync(sel.mask, 0, (size_t)need * 4, c->stream));
-    HIP_TRY(c, hipMemsetAsync(sel.counters, 0, (size_t)cw * 4, c->stream));
+    if ((r = s.mask.alloc(c, need)) || (spare && (r = spare->alloc(c, need))) || (r = s.scratch.alloc(c, need)) || (r = s.counters.alloc(c, cw))) {
+        s.reset();
+        if (spare) spare->reset();
+        return r;
+    }
+    s.words = need; s.counter_words = cw;
+    if (zero_mask) HIP_TRY(c, hipMemsetAsync(s.mask, 0, (size_t)need * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(s.counters, 0, (size_t)cw * 4, c->stream));
     return GSR_OK;
 }
+
+int gsr::set_count(gsr_ctx* c, SplatSet& s, const char* what)
+{
+    uint32_t count = 0;
+    hipError_t e1 = hipMemcpyAsync(&count, s.counters, 4, hipMemcpyDeviceToHost, c->stream);
+    hipError_t e2 = hipStreamSynchronize(c->stream);
+    for (hipError_t e : {e1, e2, hipGetLastError()})
+        if (e != hipSuccess) return fail(c, GSR_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+    s.count = count;
+    return GSR_OK;
+}
+
+int gsr::set_read(gsr_ctx* c, const SplatSet& s, const char* who, uint32_t* words, uint32_t nwords, uint32_t* count)
+{
+    const uint32_t n = c->scene->n, need = words_of(n);
+    if (words && nwords < need) return fail(c, GSR_ERR_ARG, "%s: nwords (%u) is smaller than ceil(%u / 32) = %u", who, nwords, n, need);
+    if (count) *count = s.mask ? s.count : 0u;
+    if (!words || !need) return GSR_OK;
+    if (!s.mask) {   // never allocated: all zeros
+        std::fill(words, words + need, 0u);
+        return GSR_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(words, s.mask, (size_t)need * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return GSR_OK;
+}
+
+// the selection's buffers for the scene's count, allocated (the mask zeroed) by the first call that needs them
+int gsr::select_ensure(gsr_ctx* c) { return set_ensure(c, c->scene->sel, nullptr, c->scene->n); }
 
 // selection <- selection (op) scratch on the device, its count back to the host: the end of every call that changes it
 int gsr::select_fold_and_count(gsr_ctx* c, int op, uint32_t* selected)
@@ -37,21 +64,10 @@ int gsr::select_fold_and_count(gsr_ctx* c, int op, uint32_t* selected)
     SharedScene::Selection& sel = c->scene->sel;
     if (int r = overlay_before_selection_change(c)) return r;   // the members' overlay passes in flight read the mask as it was
     launch_select_apply(op, sel.mask, sel.scratch, c->scene->n, sel.words, sel.counters + 2, sel.counters, c->stream);
-    uint32_t count = 0;
-    hipError_t e1 = hipMemcpyAsync(&count, sel.counters, 4, hipMemcpyDeviceToHost, c->stream);
-    hipError_t e2 = hipStreamSynchronize(c->stream);
-    for (hipError_t e : {e1, e2, hipGetLastError()})
-        if (e != hipSuccess) return fail(c, GSR_ERR_HIP, "selection update failed: %s", hipGetErrorString(e));
-    sel.count = count;
-    if (selected) *selected = count;
+    if (int r = set_count(c, sel, "selection update")) return r;
+    if (selected) *selected = sel.count;
     return GSR_OK;
 }
-
-namespace {
-
-bool op_ok(int32_t op) { return op >= GSR_SELOP_REPLACE && op <= GSR_SELOP_INTERSECT; }
-
-}  // namespace
 
 extern "C" {
 
@@ -155,19 +171,7 @@ int gsr_selection_invert(gsr_ctx* c, uint32_t* selected)
 int gsr_read_selection(gsr_ctx* c, uint32_t* words, uint32_t nwords, uint32_t* selected)
 {
     if (!c) return GSR_ERR_ARG;
-    const SharedScene& sc = *c->scene;
-    const uint32_t need = words_of(sc.n);
-    if (words && nwords < need) return fail(c, GSR_ERR_ARG, "gsr_read_selection: nwords (%u) is smaller than ceil(%u / 32) = %u", nwords, sc.n, need);
-    if (selected) *selected = sc.sel.mask ? sc.sel.count : 0u;
-    if (!words || !need) return GSR_OK;
-    if (!sc.sel.mask) {   // never selected in: all zeros
-        std::fill(words, words + need, 0u);
-        return GSR_OK;
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(words, sc.sel.mask, (size_t)need * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return GSR_OK;
+    return set_read(c, c->scene->sel, "gsr_read_selection", words, nwords, selected);
 }
 
 int gsr_scene_erase_selected(gsr_ctx* c, int32_t keep_selected, uint32_t* new_count)
@@ -183,7 +187,7 @@ int gsr_scene_erase_selected(gsr_ctx* c, int32_t keep_selected, uint32_t* new_co
     }
     HIP_TRY(c, hipSetDevice(c->device));
     if (int r = select_ensure(c)) return r;   // (keep_selected with no selection yet: the zeroed mask, everything goes)
-    return scene_compact(c, ScenePred{nullptr, sc.sel.mask, keep_selected ? 1u : 0u}, "gsr_scene_erase_selected", new_count);
+    return scene_compact(c, ScenePred{nullptr, sc.sel.mask, keep_selected ? 1u : 0u, sc.sel.words}, "gsr_scene_erase_selected", new_count);
 }
 
 }  // extern "C"

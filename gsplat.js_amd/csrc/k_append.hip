@@ -8,6 +8,7 @@
 // n / 8 bytes, not a pass over the scene (k_edit.hip's rule).  The selected lanes of a wave write consecutive rows.
 // Bits at and above n_src are masked in both kernels alike, whatever the words hold there.
 #include "gsr_internal.h"
+#include "k_splat_ops.h"
 
 #include <algorithm>
 
@@ -24,11 +25,8 @@ constexpr uint32_t APPEND_BLOCK_WORDS = APPEND_THREADS / 32;   // its selection 
 // selection word wi with the bits at and above n_src dropped (a word behind the mask's end reads as zero)
 __device__ __forceinline__ uint32_t append_word(const uint32_t* __restrict__ words, uint32_t nwords, uint32_t n_src, uint32_t wi)
 {
-    if ((uint64_t)wi * 32u >= n_src) return 0u;
-    GSR_BOUND(append, 0, wi, nwords);
-    if (wi >= nwords) return 0u;
-    const uint32_t rest = n_src - wi * 32u;
-    return words[wi] & (rest >= 32u ? 0xffffffffu : (1u << rest) - 1u);
+    if ((uint64_t)wi * 32u < n_src) GSR_BOUND(append, 0, wi, nwords);
+    return set_word(words, nwords, n_src, wi);
 }
 
 // one thread per gather workgroup: the selected splats among its 256
@@ -102,17 +100,7 @@ __global__ __launch_bounds__(APPEND_THREADS) void k_append_gather(uint32_t n_src
     const uint64_t row = (uint64_t)dst_first + block_off[blockIdx.x] + rank;
     GSR_BOUND(append, 2, row, dst_rows);
     if (row >= dst_rows) return;   // (never: the host sized the destination for dst_first + the selection's count)
-    const uint32_t o = (uint32_t)row;
-    // words, not floats: the bits travel as they are (NaN payloads, -0.0)
-    reinterpret_cast<uint32_t*>(dst.px)[o] = reinterpret_cast<const uint32_t*>(src.px)[i];
-    reinterpret_cast<uint32_t*>(dst.py)[o] = reinterpret_cast<const uint32_t*>(src.py)[i];
-    reinterpret_cast<uint32_t*>(dst.pz)[o] = reinterpret_cast<const uint32_t*>(src.pz)[i];
-    dst.cov0[o] = src.cov0[i];
-    dst.cov1[o] = src.cov1[i];
-    dst.cov2[o] = src.cov2[i];
-    dst.rgba[o] = src.rgba[i];
-    reinterpret_cast<uint4*>(dst.rot)[o] = reinterpret_cast<const uint4*>(src.rot)[i];
-    reinterpret_cast<uint4*>(dst.scl)[o] = reinterpret_cast<const uint4*>(src.scl)[i];
+    copy_splat_row(dst, (uint32_t)row, src, i);   // words: the bits travel as they are
 }
 
 // the selection becomes exactly [first, first + count): every one of the nwords words is stored (a REPLACE); *total <- count

@@ -7,6 +7,7 @@
 // n / 8 bytes, not a pass over the scene.
 #include "gsr_internal.h"
 #include "k_pack_cov.h"
+#include "k_splat_ops.h"
 
 #include <algorithm>
 
@@ -24,76 +25,36 @@ constexpr uint32_t BOUNDS_MAX_BLOCKS = 1024;   // partials of k_edit_bounds: a g
 __device__ __forceinline__ bool edit_selected(const uint32_t* __restrict__ words, uint32_t nwords, uint32_t n, uint32_t i)
 {
     if (i >= n) return false;
-    const uint32_t wi = i >> 5;
-    GSR_BOUND(edit, 0, wi, nwords);
-    if (wi >= nwords) return false;
+    GSR_BOUND(edit, 0, i >> 5, nwords);
     GSR_BOUND(edit, 1, i, n);
-    return ((words[wi] >> (i & 31u)) & 1u) != 0u;
+    return set_bit(words, nwords, i);
 }
 
-// Scene.translate (Scene.ts:182-195) on the selected splats
+// Scene.translate / rotate / scale (Scene.ts:182-305) on the selected splats: k_splat_ops.h's arithmetic behind the selection test
 __global__ __launch_bounds__(EDIT_THREADS) void k_edit_translate(uint32_t n, SceneDev sc, const uint32_t* __restrict__ words, uint32_t nwords,
                                                                  double tx, double ty, double tz)
 {
     const uint32_t i = blockIdx.x * EDIT_THREADS + threadIdx.x;
-    if (!edit_selected(words, nwords, n, i)) return;
-    sc.px[i] = (float)((double)sc.px[i] + tx);
-    sc.py[i] = (float)((double)sc.py[i] + ty);
-    sc.pz[i] = (float)((double)sc.pz[i] + tz);
+    if (edit_selected(words, nwords, n, i)) splat_translate(sc, i, tx, ty, tz);
 }
 
-// Scene.rotate (Scene.ts:197-257), q = (x, y, z, w), on the selected splats.  PIVOT: translate(-pivot), rotate, translate(+pivot)
-// fused in registers -- every (float) below is a store of the reference's into positions; m = -pivot, p = pivot.
+// q = (x, y, z, w); PIVOT, m = -pivot and p = pivot as SplatPivot has them
 template <bool PIVOT>
 __global__ __launch_bounds__(EDIT_THREADS) void k_edit_rotate(uint32_t n, SceneDev sc, const uint32_t* __restrict__ words, uint32_t nwords,
                                                               double x, double y, double z, double w, double mx, double my, double mz,
                                                               double px_, double py_, double pz_)
 {
     const uint32_t i = blockIdx.x * EDIT_THREADS + threadIdx.x;
-    if (!edit_selected(words, nwords, n, i)) return;
-    const double R[9] = {1 - 2 * y * y - 2 * z * z, 2 * x * y - 2 * z * w, 2 * x * z + 2 * y * w,
-                         2 * x * y + 2 * z * w, 1 - 2 * x * x - 2 * z * z, 2 * y * z - 2 * x * w,
-                         2 * x * z - 2 * y * w, 2 * y * z + 2 * x * w, 1 - 2 * x * x - 2 * y * y};
-    double px = sc.px[i], py = sc.py[i], pz = sc.pz[i];
-    if (PIVOT) { px = (float)(px + mx); py = (float)(py + my); pz = (float)(pz + mz); }
-    float ox = (float)(R[0] * px + R[1] * py + R[2] * pz);
-    float oy = (float)(R[3] * px + R[4] * py + R[5] * pz);
-    float oz = (float)(R[6] * px + R[7] * py + R[8] * pz);
-    if (PIVOT) { ox = (float)((double)ox + px_); oy = (float)((double)oy + py_); oz = (float)((double)oz + pz_); }
-    sc.px[i] = ox; sc.py[i] = oy; sc.pz[i] = oz;
-    const float4 r = sc.rot[i];  // (w, x, y, z)
-    // rotation.multiply(Quaternion(r1, r2, r3, r0)), Quaternion.ts:39-55
-    const double w1 = w, x1 = x, y1 = y, z1 = z, w2 = r.x, x2 = r.y, y2 = r.z, z2 = r.w;
-    float4 nr;
-    nr.y = (float)(w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2);
-    nr.z = (float)(w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2);
-    nr.w = (float)(w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2);
-    nr.x = (float)(w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2);
-    sc.rot[i] = nr;
-    uint32_t c0, c1, c2;
-    pack_cov(nr, sc.scl[i], c0, c1, c2);
-    sc.cov0[i] = c0; sc.cov1[i] = c1; sc.cov2[i] = c2;
+    if (edit_selected(words, nwords, n, i)) splat_rotate<PIVOT>(sc, i, x, y, z, w, SplatPivot{mx, my, mz, px_, py_, pz_});
 }
 
-// Scene.scale (Scene.ts:259-305) on the selected splats; PIVOT as in k_edit_rotate
 template <bool PIVOT>
 __global__ __launch_bounds__(EDIT_THREADS) void k_edit_scale(uint32_t n, SceneDev sc, const uint32_t* __restrict__ words, uint32_t nwords,
                                                              double sx, double sy, double sz, double mx, double my, double mz,
                                                              double px_, double py_, double pz_)
 {
     const uint32_t i = blockIdx.x * EDIT_THREADS + threadIdx.x;
-    if (!edit_selected(words, nwords, n, i)) return;
-    double px = sc.px[i], py = sc.py[i], pz = sc.pz[i];
-    if (PIVOT) { px = (float)(px + mx); py = (float)(py + my); pz = (float)(pz + mz); }
-    float ox = (float)(px * sx), oy = (float)(py * sy), oz = (float)(pz * sz);
-    if (PIVOT) { ox = (float)((double)ox + px_); oy = (float)((double)oy + py_); oz = (float)((double)oz + pz_); }
-    sc.px[i] = ox; sc.py[i] = oy; sc.pz[i] = oz;
-    float4 s = sc.scl[i];
-    s.x = (float)((double)s.x * sx); s.y = (float)((double)s.y * sy); s.z = (float)((double)s.z * sz);
-    sc.scl[i] = s;
-    uint32_t c0, c1, c2;
-    pack_cov(sc.rot[i], s, c0, c1, c2);
-    sc.cov0[i] = c0; sc.cov1[i] = c1; sc.cov2[i] = c2;
+    if (edit_selected(words, nwords, n, i)) splat_scale<PIVOT>(sc, i, sx, sy, sz, SplatPivot{mx, my, mz, px_, py_, pz_});
 }
 
 // rgba[i] = (rgba[i] & ~byte_mask) | (value & byte_mask) on the selected splats (value arrives masked)
@@ -164,12 +125,10 @@ __global__ __launch_bounds__(BOUNDS_THREADS) void k_edit_bounds(uint32_t n, cons
     __shared__ EditBox s_box[BOUNDS_THREADS / WAVE];
     EditBox b = box_empty();
     const uint32_t t = blockIdx.x * BOUNDS_THREADS + threadIdx.x, stride = gridDim.x * BOUNDS_THREADS;
-    const uint32_t live = (n + 31u) >> 5;   // words that hold a splat; the last one masked to the bits below n
+    const uint32_t live = (n + 31u) >> 5;   // words that hold a splat
     for (uint32_t wi = t; wi < live; wi += stride) {
         GSR_BOUND(edit, 0, wi, nwords);
-        if (wi >= nwords) break;
-        const uint32_t rest = n - (wi << 5);
-        b.count += (uint32_t)__popc(words[wi] & (rest >= 32u ? 0xffffffffu : (1u << rest) - 1u));
+        b.count += (uint32_t)__popc(set_word(words, nwords, n, wi));
     }
     for (uint32_t i = t; i < n; i += stride) {   // (i + stride wraps only for n > 2^32 - stride: gsr_set_scene* refuses far less)
         if (!edit_selected(words, nwords, n, i)) continue;

@@ -4,6 +4,7 @@
 // file is compiled with -ffp-contract=off, so every word matches the JavaScript result bit for bit.
 #include "gsr_internal.h"
 #include "k_pack_cov.h"
+#include "k_splat_ops.h"
 
 #include <algorithm>
 
@@ -28,56 +29,23 @@ __global__ __launch_bounds__(256) void k_build_scene(const uint4* __restrict__ r
     sc.cov0[i] = c0; sc.cov1[i] = c1; sc.cov2[i] = c2;
 }
 
-// Scene.translate (Scene.ts:182-195)
+// Scene.translate / rotate / scale (Scene.ts:182-305) on every splat: k_splat_ops.h's arithmetic, no pivot
 __global__ __launch_bounds__(256) void k_scene_translate(uint32_t n, SceneDev sc, double tx, double ty, double tz)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    sc.px[i] = (float)((double)sc.px[i] + tx);
-    sc.py[i] = (float)((double)sc.py[i] + ty);
-    sc.pz[i] = (float)((double)sc.pz[i] + tz);
+    if (i < n) splat_translate(sc, i, tx, ty, tz);
 }
 
-// Scene.rotate (Scene.ts:197-257), q = (x, y, z, w)
-__global__ __launch_bounds__(256) void k_scene_rotate(uint32_t n, SceneDev sc, double x, double y, double z, double w)
+__global__ __launch_bounds__(256) void k_scene_rotate(uint32_t n, SceneDev sc, double x, double y, double z, double w)   // q = (x, y, z, w)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double R[9] = {1 - 2 * y * y - 2 * z * z, 2 * x * y - 2 * z * w, 2 * x * z + 2 * y * w,
-                         2 * x * y + 2 * z * w, 1 - 2 * x * x - 2 * z * z, 2 * y * z - 2 * x * w,
-                         2 * x * z - 2 * y * w, 2 * y * z + 2 * x * w, 1 - 2 * x * x - 2 * y * y};
-    const double px = sc.px[i], py = sc.py[i], pz = sc.pz[i];
-    sc.px[i] = (float)(R[0] * px + R[1] * py + R[2] * pz);
-    sc.py[i] = (float)(R[3] * px + R[4] * py + R[5] * pz);
-    sc.pz[i] = (float)(R[6] * px + R[7] * py + R[8] * pz);
-    const float4 r = sc.rot[i];  // (w, x, y, z)
-    // rotation.multiply(Quaternion(r1, r2, r3, r0)), Quaternion.ts:39-55
-    const double w1 = w, x1 = x, y1 = y, z1 = z, w2 = r.x, x2 = r.y, y2 = r.z, z2 = r.w;
-    float4 nr;
-    nr.y = (float)(w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2);
-    nr.z = (float)(w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2);
-    nr.w = (float)(w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2);
-    nr.x = (float)(w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2);
-    sc.rot[i] = nr;
-    uint32_t c0, c1, c2;
-    pack_cov(nr, sc.scl[i], c0, c1, c2);
-    sc.cov0[i] = c0; sc.cov1[i] = c1; sc.cov2[i] = c2;
+    if (i < n) splat_rotate<false>(sc, i, x, y, z, w, SplatPivot{});
 }
 
-// Scene.scale (Scene.ts:259-305)
 __global__ __launch_bounds__(256) void k_scene_scale(uint32_t n, SceneDev sc, double sx, double sy, double sz)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    sc.px[i] = (float)((double)sc.px[i] * sx);
-    sc.py[i] = (float)((double)sc.py[i] * sy);
-    sc.pz[i] = (float)((double)sc.pz[i] * sz);
-    float4 s = sc.scl[i];
-    s.x = (float)((double)s.x * sx); s.y = (float)((double)s.y * sy); s.z = (float)((double)s.z * sz);
-    sc.scl[i] = s;
-    uint32_t c0, c1, c2;
-    pack_cov(sc.rot[i], s, c0, c1, c2);
-    sc.cov0[i] = c0; sc.cov1[i] = c1; sc.cov2[i] = c2;
+    if (i < n) splat_scale<false>(sc, i, sx, sy, sz, SplatPivot{});
 }
 
 // ---- Scene.limitBox (Scene.ts:307-366): order-preserving compaction ----
@@ -90,26 +58,45 @@ __device__ __forceinline__ bool in_box(const SceneDev& sc, uint32_t i, const dou
 }
 
 // The compaction's predicate, "splat i stays": the kernels below are templates over it.  Box: limitBox's six comparisons;
-// MaskKeep: one bit per splat of a selection (k_select.hip: bit i & 31 of word i >> 5), the splats whose bit equals `keep` stay
+// MaskKeep: one bit per splat of a selection of nwords words (k_splat_ops.h's set layout), the splats whose bit equals `keep` stay
 // (gsr_scene_erase_selected).  Both are called for i < n only.
 struct Box {
     double v[6];
     __device__ __forceinline__ bool operator()(const SceneDev& sc, uint32_t i) const { return in_box(sc, i, v); }
 };
 struct MaskKeep {
-    const uint32_t* words; uint32_t keep;
-    __device__ __forceinline__ bool operator()(const SceneDev&, uint32_t i) const { return ((words[i >> 5] >> (i & 31u)) & 1u) == keep; }
+    const uint32_t* words; uint32_t nwords, keep;
+    __device__ __forceinline__ bool operator()(const SceneDev&, uint32_t i) const { return (set_bit(words, nwords, i) ? 1u : 0u) == keep; }
 };
+
+// The compaction's prologue.  wave_counts: the wave's ballot of `keep`, its popcount into s_w[wave], and THE barrier (every thread calls
+// it).  compact_slot, on top of it: the wave's first output index (the workgroup's offset + the earlier waves' counts) and the lane's.
+struct CompactSlot { uint32_t off, o; };
+
+__device__ __forceinline__ uint64_t wave_counts(bool keep, uint32_t* s_w)
+{
+    const uint64_t m = __ballot(keep);
+    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+    __syncthreads();
+    return m;
+}
+
+__device__ __forceinline__ CompactSlot compact_slot(bool keep, const uint32_t* __restrict__ block_off, uint32_t* s_w)
+{
+    const uint64_t m = wave_counts(keep, s_w);
+    CompactSlot c;
+    c.off = block_off[blockIdx.x];
+    for (int w = 0; w < (int)(threadIdx.x >> 6); w++) c.off += s_w[w];
+    c.o = c.off + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    return c;
+}
 
 template <class Pred>
 __global__ __launch_bounds__(BOX_THREADS) void k_box_count(uint32_t n, SceneDev sc, Pred box, uint32_t* __restrict__ block_count)
 {
     __shared__ uint32_t s_w[BOX_THREADS / WAVE];
     const uint32_t i = blockIdx.x * BOX_THREADS + threadIdx.x;
-    const bool keep = i < n && box(sc, i);
-    const uint64_t m = __ballot(keep);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = (uint32_t)__popcll(m);
-    __syncthreads();
+    wave_counts(i < n && box(sc, i), s_w);
     if (threadIdx.x == 0) {
         uint32_t t = 0;
         for (int w = 0; w < BOX_THREADS / WAVE; w++) t += s_w[w];
@@ -143,18 +130,9 @@ __global__ __launch_bounds__(BOX_THREADS) void k_box_compact(uint32_t n, SceneDe
 {
     __shared__ uint32_t s_w[BOX_THREADS / WAVE];
     const uint32_t i = blockIdx.x * BOX_THREADS + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool keep = i < n && box(src, i);
-    const uint64_t m = __ballot(keep);
-    if (lane == 0) s_w[wave] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t off = block_off[blockIdx.x];
-    for (int w = 0; w < wave; w++) off += s_w[w];
-    if (!keep) return;
-    const uint32_t o = off + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    dst.px[o] = src.px[i]; dst.py[o] = src.py[i]; dst.pz[o] = src.pz[i];
-    dst.cov0[o] = src.cov0[i]; dst.cov1[o] = src.cov1[i]; dst.cov2[o] = src.cov2[i]; dst.rgba[o] = src.rgba[i];
-    dst.rot[o] = src.rot[i]; dst.scl[o] = src.scl[i];
+    const CompactSlot c = compact_slot(keep, block_off, s_w);
+    if (keep) copy_splat_row(dst, c.o, src, i);
 }
 
 // ---- limitBox on a scene whose SH colour follows it (gsr_set_sh_follow): the SH textures are compacted with the scene ----
@@ -177,21 +155,14 @@ __global__ __launch_bounds__(BOX_THREADS) void k_box_compact_bits(uint32_t n, Sc
 {
     __shared__ uint32_t s_w[BOX_THREADS / WAVE];
     const uint32_t i = blockIdx.x * BOX_THREADS + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool keep = i < n && box(src, i);
-    const uint64_t m = __ballot(keep);
-    if (lane == 0) s_w[wave] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t off = block_off[blockIdx.x];
-    for (int w = 0; w < wave; w++) off += s_w[w];
+    const CompactSlot c = compact_slot(keep, block_off, s_w);
     bool bit = false;
     if (keep) {
-        const uint32_t wi = i >> 5;
-        GSR_BOUND(scene, 6, wi, nwords_in);
-        bit = wi < nwords_in && ((in[wi] >> (i & 31u)) & 1u) != 0u;
+        GSR_BOUND(scene, 6, i >> 5, nwords_in);
+        bit = set_bit(in, nwords_in, i);
     }
-    const uint32_t o = off + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    const uint32_t w0 = off >> 5, k = (o >> 5) - w0, b = bit ? 1u << (o & 31u) : 0u;   // (k is 0, 1 or 2 for a kept lane)
+    const uint32_t o = c.o, w0 = c.off >> 5, k = (o >> 5) - w0, b = bit ? 1u << (o & 31u) : 0u;   // (k is 0, 1 or 2 for a kept lane)
     uint32_t v0 = k == 0u ? b : 0u, v1 = k == 1u ? b : 0u, v2 = k == 2u ? b : 0u;
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) {
@@ -199,7 +170,7 @@ __global__ __launch_bounds__(BOX_THREADS) void k_box_compact_bits(uint32_t n, Sc
         v1 |= __shfl_xor(v1, d);
         v2 |= __shfl_xor(v2, d);
     }
-    if (lane != 0) return;
+    if ((threadIdx.x & 63) != 0) return;
     const uint32_t v[3] = {v0, v1, v2};
 #pragma unroll
     for (uint32_t j = 0; j < 3; j++) {
@@ -223,9 +194,7 @@ __global__ __launch_bounds__(BOX_THREADS) void k_box_thresholds(uint32_t n, Scen
     const uint32_t block = at / BOX_THREADS, i = block * BOX_THREADS + threadIdx.x;
     const bool keep = i < at && box(sc, i);   // (i < at <= n)
     if (keep) GSR_BOUND(scene_sh, 0, i, n);
-    const uint64_t m = __ballot(keep);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = (uint32_t)__popcll(m);
-    __syncthreads();
+    wave_counts(keep, s_w);
     if (threadIdx.x == 0) {
         uint32_t t = at < n ? block_off[block] : count[0];   // (at == n: everything kept lies in front of it)
         if (at < n)
@@ -246,16 +215,10 @@ __global__ __launch_bounds__(BOX_THREADS) void k_box_compact_sh(uint32_t n, Scen
 {
     __shared__ uint32_t s_w[BOX_THREADS / WAVE];
     const uint32_t i = blockIdx.x * BOX_THREADS + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool keep = i < n && box(src, i);
-    const uint64_t m = __ballot(keep);
-    if (lane == 0) s_w[wave] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t off = block_off[blockIdx.x];
-    for (int w = 0; w < wave; w++) off += s_w[w];
+    const CompactSlot c = compact_slot(keep, block_off, s_w);
     if (!keep || (int32_t)i <= band0) return;
-    const uint32_t o = off + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    const size_t t = i - (uint32_t)(band0 + 1), u = o - count[1];   // (every kept splat in front of an SH splat is counted in o)
+    const size_t t = i - (uint32_t)(band0 + 1), u = c.o - count[1];   // (every kept splat in front of an SH splat is counted in o)
     GSR_BOUND(scene_sh, 1, t, sh_count);
     GSR_BOUND(scene_sh, 2, u, sh_count);
     if (t >= sh_count || u >= sh_count) return;
@@ -384,7 +347,7 @@ void launch_scene_compact(uint32_t n, const SceneDev& src, const SceneDev& dst, 
 {
     if (!n) return;
     if (p.box) compact_with(n, src, dst, box_of(p.box), block_count, total, s);
-    else compact_with(n, src, dst, MaskKeep{p.mask, p.keep}, block_count, total, s);
+    else compact_with(n, src, dst, MaskKeep{p.mask, p.mask_words, p.keep}, block_count, total, s);
 }
 
 void launch_scene_compact_sh(uint32_t n, const SceneDev& src, const ScenePred& p, const uint32_t* block_off, uint32_t* count,
@@ -392,7 +355,7 @@ void launch_scene_compact_sh(uint32_t n, const SceneDev& src, const ScenePred& p
 {
     if (!n) return;
     if (p.box) compact_sh_with(n, src, box_of(p.box), block_off, count, band, sh_count, sh_in, sh_out, s);
-    else compact_sh_with(n, src, MaskKeep{p.mask, p.keep}, block_off, count, band, sh_count, sh_in, sh_out, s);
+    else compact_sh_with(n, src, MaskKeep{p.mask, p.mask_words, p.keep}, block_off, count, band, sh_count, sh_in, sh_out, s);
 }
 
 void launch_scene_compact_bits(uint32_t n, const SceneDev& src, const ScenePred& p, const uint32_t* block_off, const uint32_t* in,
@@ -401,7 +364,7 @@ void launch_scene_compact_bits(uint32_t n, const SceneDev& src, const ScenePred&
     if (!n) return;
     const uint32_t nblocks = (n + BOX_THREADS - 1) / BOX_THREADS;
     if (p.box) hipLaunchKernelGGL(k_box_compact_bits<Box>, dim3(nblocks), dim3(BOX_THREADS), 0, s, n, src, box_of(p.box), block_off, in, nwords_in, out, nwords_out);
-    else hipLaunchKernelGGL(k_box_compact_bits<MaskKeep>, dim3(nblocks), dim3(BOX_THREADS), 0, s, n, src, MaskKeep{p.mask, p.keep}, block_off, in, nwords_in, out, nwords_out);
+    else hipLaunchKernelGGL(k_box_compact_bits<MaskKeep>, dim3(nblocks), dim3(BOX_THREADS), 0, s, n, src, MaskKeep{p.mask, p.mask_words, p.keep}, block_off, in, nwords_in, out, nwords_out);
 }
 
 void launch_scene_import(const float* scales, uint32_t n, float4* scl, hipStream_t s)

@@ -6,6 +6,7 @@
 //
 // A bit set is order-independent, so the atomic ORs of the two region pickers give an exact result whatever order they land in.
 #include "gsr_internal.h"
+#include "k_splat_ops.h"
 
 #include <algorithm>
 
@@ -121,8 +122,7 @@ __global__ __launch_bounds__(SELECT_APPLY_THREADS) void k_select_apply(int op, u
         GSR_BOUND(select, 5, w, nwords);
         const uint32_t s = sel[w], p = op == SELOP_INVERT ? 0u : scratch[w];
         uint32_t v = op == SELOP_REPLACE ? p : op == SELOP_ADD ? (s | p) : op == SELOP_SUBTRACT ? (s & ~p) : op == SELOP_INTERSECT ? (s & p) : ~s;
-        const uint32_t live = n - min(n, w * 32u);   // splats from this word's first bit on
-        if (live < 32u) v &= (1u << live) - 1u;      // (live == 0: the word lies behind the last splat)
+        v &= set_live_bits(n, w);   // (0: the word lies behind the last splat)
         sel[w] = v;
         bits = (uint32_t)__popc(v);
     }

@@ -144,8 +144,15 @@ def test_sources_are_wired_into_every_build():
     assert "$(SRCS)" in build_id
     host = open(os.path.join(CSRC, "gsr_append.cpp")).read()
     for word in ("sync_members(c)", "adopt_scene(c)", "++sc.generation", "invalidate_members(c, true)", "overlay_before_selection_change(c)", "require_rows(c)",
-                 "launch_append_gather(", "launch_append_select_range(", "launch_repack_scene(", "launch_scene_import(", "sc.sh_count", "hipStreamWaitEvent(c->stream"):
+                 "launch_append_gather(", "launch_append_select_range(", "upload_rows(c, who, v, n, m,", "sc.sh_count", "hipStreamWaitEvent(c->stream"):
         assert word in host, word
+    # the repack and its check are the upload's own (one hop further: the helper gsr_set_scene_arrays goes through)
+    scene = open(os.path.join(CSRC, "gsr_scene.cpp")).read()
+    helper = re.search(r"^int gsr::upload_rows\(.*?^}", scene, flags=re.S | re.M)
+    assert helper, "gsr_scene.cpp does not define upload_rows"
+    for word in ("launch_repack_scene(", "launch_scene_import("):
+        assert word in helper.group(0), word
+    assert scene.count("upload_rows(") == 2 and "launch_repack_scene(" not in scene.replace(helper.group(0), "")   # defined once, called by the upload
     internal = open(os.path.join(CSRC, "gsr_internal.h")).read()
     for word in ("void launch_append_gather(", "void launch_append_select_range(", "uint32_t append_blocks("):
         assert word in internal, word

@@ -113,3 +113,40 @@ def test_the_covariance_arithmetic_exists_once():
                     defs.setdefault(fn, []).append(os.path.basename(path))
     assert defs == {"pack_cov": ["k_pack_cov.h"], "pack_half2": ["k_pack_cov.h"], "float_to_half_trunc": ["k_pack_cov.h"]}, defs
     assert '#include "k_pack_cov.h"' in open(os.path.join(CSRC, "k_scene.hip")).read()
+
+
+def _csrc_files_with(pattern):
+    """the files of csrc/ whose text matches `pattern`, comments included"""
+    return [os.path.basename(p) for p in sorted(glob.glob(os.path.join(CSRC, "*")))
+            if os.path.isfile(p) and re.search(pattern, open(p, errors="replace").read())]
+
+
+def test_the_transform_arithmetic_exists_once():
+    """Scene.rotate's matrix and quaternion product are written in one file (pack_cov's own matrix is of another quaternion and
+    names its entries qx..qw), and the three units that need them include it."""
+    assert _csrc_files_with(re.escape("1 - 2 * y * y - 2 * z * z")) == ["k_splat_ops.h"]
+    assert _csrc_files_with(re.escape("w1 * x2 + x1 * w2")) == ["k_splat_ops.h"]
+    for f in ("k_scene.hip", "k_edit.hip", "gsr_scene.cpp"):
+        assert '#include "k_splat_ops.h"' in open(os.path.join(CSRC, f)).read(), f
+    for fn in ("quat_matrix", "splat_translate", "splat_rotate", "splat_scale", "copy_splat_row", "set_live_bits", "set_word", "set_bit"):
+        assert _csrc_files_with(r"__device__[^;{]*\b%s\(" % fn) == ["k_splat_ops.h"], fn
+    # the tail mask of a set's last word and the bit test are spelled out nowhere else
+    assert _csrc_files_with(re.escape("(1u << rest) - 1u")) == ["k_splat_ops.h"]
+    # (the frame path's two readers, k_project.hip and k_overlay.hip, are not the editing layer's)
+    assert _csrc_files_with(r">> \(i & 31u\)\) & 1u") == ["k_overlay.hip", "k_project.hip", "k_splat_ops.h"]
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    assert "k_splat_ops.h" in re.search(r"^BUILD_ID := (.*)$", mk, flags=re.M).group(1)
+    assert re.search(r"^\$\(OUT\)/%\.o: %\.hip .*k_splat_ops\.h", mk, flags=re.M), "the .hip rule does not depend on the shared header"
+    assert re.search(r"^\$\(OUT\)/gsr_%\.o: gsr_%\.cpp .*k_splat_ops\.h", mk, flags=re.M), "the host rule does not depend on the shared header"
+
+
+def test_the_splat_set_is_sized_and_allocated_once():
+    """the sizes of a one-bit-per-splat set are defined in one file, and neither set allocates for itself"""
+    for fn in ("words_of", "fold_words", "counter_words", "op_ok"):
+        assert _csrc_files_with(r"\b(uint32_t|bool) %s\([^;{)]*\)\s*\{" % fn) == ["gsr_ctx.h"], fn
+    for path, fn in (("gsr_select.cpp", "select_ensure"), ("gsr_hidden.cpp", "hidden_ensure")):
+        body = re.search(r"^int gsr::%s\(gsr_ctx\* c\)\s*\{.*?\}\s*$" % fn, open(os.path.join(CSRC, path)).read(), flags=re.S | re.M)
+        assert body and "set_ensure(" in body.group(0) and ".alloc(" not in body.group(0), fn
+    assert _csrc_files_with(r"(?m)^int gsr::set_ensure\(") == ["gsr_select.cpp"]
+    append = open(os.path.join(CSRC, "gsr_append.cpp")).read()
+    assert "set_ensure(c, sel, nullptr, sc.arr_rows" in append and "sel.mask.alloc(" not in append   # an append sizes for the capacity

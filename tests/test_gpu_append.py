@@ -12,6 +12,7 @@ import pytest
 import append_reference as ar
 import contrib_reference as CR
 import edit_reference as er
+import hide_reference as hr
 
 pytestmark = pytest.mark.gpu
 
@@ -503,6 +504,69 @@ def test_bounds_twin_counts_nothing_over_the_same_walk(oracle):
         _walk(oracle, n, lib_path=BOUNDS_LIB)   # every size, every selection, the frames at 20000 included
     _refusals(oracle, lib_path=BOUNDS_LIB)
     for name in ("gsr_debug_bounds_append", "gsr_debug_bounds_scene", "gsr_debug_bounds_edit", "gsr_debug_bounds_select"):
+        buf = (ctypes.c_uint32 * 8)()
+        assert getattr(L, name)(buf) == 0
+        assert list(buf) == [0] * 8, name
+
+
+SET_COUNTS = (1, 63, 65, 8191, 8193)   # a word is 32 splats, a wave's ballot 64, one k_select_apply workgroup 256 words = 8192 splats
+
+
+def _set_layout_bytes(capacity, with_rows=True):
+    """scene_bytes of a scene with both sets allocated, no region bytes, no SH and no contribution accumulators, from the documented
+    layout: 7 (15 with rotations / scales) words per capacity row; the selection's two and the hidden set's three word buffers of
+    the capacity's fold words (even, at least 2); for each set two counter words and one per 256 words"""
+    fold = max((-(-capacity // 32) + 1) & ~1, 2)
+    counters = 2 + -(-fold // 256)
+    return 4 * (capacity * (15 if with_rows else 7) + (2 + 3) * fold + 2 * counters)
+
+
+def _sets_through_growth(oracle, n, lib_path=None):
+    import gsplat_hip as gh
+    mix = (np.arange(n, dtype=np.uint64) * 2654435761 % 2 ** 32) >> 7   # fixed pseudo-random thirds; splat 0 is selected
+    sel, third, hid = mix % 3 == 0, mix % 3 == 1, np.zeros(n, dtype=bool)   # (sel, hid: what the device is expected to hold)
+    st = _state(oracle, n)
+    r = gh.HIPRenderer(W, H, lib_path=lib_path)
+
+    def same(what):
+        assert np.array_equal(r.selection_words(), hr.pack(sel)) and r.selection_count() == int(sel.sum()), (what, n, "selection")   # (pack: tail bits zero)
+        assert np.array_equal(r.hidden_words(), hr.pack(hid)) and r.hidden_count() == int(hid.sum()), (what, n, "hidden set")
+
+    try:
+        r.set_scene_arrays(st.data, st.positions, st.rotations, st.scales)
+        assert r.set_selection(sel) == int(sel.sum())
+        same("select")
+        hid = hr.hidden_set(hid, third)
+        assert r.set_hidden(third) == int(hid.sum())
+        same("hide")
+        got = r.scene_duplicate_selected()   # past the allocated words at the small sizes, past one apply workgroup at 8191
+        want = ar.duplicate(st, sel)
+        assert tuple(got) == tuple(want) == (n, int(sel.sum()))
+        sel, hid = ar.selection_after(st.n, *want), ar.hidden_after(hid, want[1])   # the new rows selected and not hidden
+        same("duplicate")
+        capacity = ar.capacity_after(n, st.n)
+        assert r.scene_capacity() == capacity and r.scene_count() == st.n
+        sel = ~sel
+        assert r.invert_selection() == int(sel.sum())
+        same("invert")
+        hid = hr.hide_selected(hid, sel, "add")
+        assert r.hide_selected("add") == int(hid.sum())
+        same("hide_selected")
+        assert r.scene_sharing() == (1, _set_layout_bytes(capacity))
+    finally:
+        r.dispose()
+
+
+@pytest.mark.parametrize("n", SET_COUNTS)
+def test_the_sets_survive_growth_across_word_and_workgroup_edges(oracle, n):
+    """select a third, hide another third, duplicate, invert, hide the selection: both sets word for word and both counts after every
+    step, and the scene's bytes from the documented layout -- on the shipped build and on the bounds-checked twin, which counts nothing"""
+    import gsplat_hip as gh
+    _sets_through_growth(oracle, n)
+    assert os.path.exists(BOUNDS_LIB), "the bounds-checked build is missing: run python -c 'import __graft_entry__ as g; g.build()'"
+    L = gh.load_library(BOUNDS_LIB)
+    _sets_through_growth(oracle, n, lib_path=BOUNDS_LIB)
+    for name in ("gsr_debug_bounds_append", "gsr_debug_bounds_select", "gsr_debug_bounds_scene", "gsr_debug_bounds_edit"):
         buf = (ctypes.c_uint32 * 8)()
         assert getattr(L, name)(buf) == 0
         assert list(buf) == [0] * 8, name
