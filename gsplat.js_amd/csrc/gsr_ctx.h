@@ -483,7 +483,16 @@ struct gsr_ctx {
         // gsr_set_overlay calls that changed them)
         uint64_t serial = 0, sel_version = 0, opt_version = 0, image_opt_version = 0;
         bool in_flight = false;             // a pass has been enqueued since the last gsr_sync: calls that change the mask wait for this stream first
-        void reset() { on = false; image.reset(); cover.reset(); image8.reset(); invalid.reset(); pixels = 0; serial = 0; }
+        // the selection's outline (gsr_set_overlay_outline): drawn into `image` behind the pass; off, nothing is allocated or launched
+        struct Outline {
+            bool on = false;
+            float rgb[3] = {0.0f, 0.0f, 0.0f}, alpha = 0.0f, threshold = 0.0f;
+            int32_t width = 0, side = 0;
+            gsr::DevBuf<unsigned long long> bits;   // the bit plane of k_outline_bits, H x outline_words(W) in front of `words` allocated (they only grow)
+            size_t words = 0;
+            void reset() { on = false; bits.reset(); words = 0; }
+        } outline;
+        void reset() { on = false; image.reset(); cover.reset(); image8.reset(); invalid.reset(); pixels = 0; serial = 0; outline.reset(); }
     } overlay;
 
     // frame delivery (gsr_delivery_open): a ring of pinned host blocks, each with its device staging and "copy done" event

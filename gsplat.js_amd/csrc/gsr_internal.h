@@ -540,6 +540,22 @@ struct OverlayBuffers : FrameLists {
 // skip: entries that cannot reach a tile are left out (GSR_DEPTH_SKIP); trim: the walk ends behind the list's last selected entry
 // (GSR_OVERLAY_TRIM); the same bits in all four forms
 void launch_overlay(const OverlayBuffers& b, const BinGrid& g, const CamParams& cam, bool skip, bool trim, hipStream_t s);
+// Selection outline (k_overlay.hip; DESIGN.md section 4, "Selection overlay"): the edge of { cover >= threshold } drawn into the
+// overlay image behind launch_overlay, in place.  The domain is the grid's band columns inside the image, every row.
+constexpr int OUTLINE_MAX_WIDTH = 16;                      // one neighbour word on each side of a 64-pixel word suffices
+constexpr int OUTLINE_OUTER = 0, OUTLINE_INNER = 1;        // (gsr_outline_options.side)
+struct OutlineArgs {
+    const float* cover;          // W x H, read, never written
+    float4* overlay;             // W x H: only edge pixels are read and rewritten
+    unsigned long long* bits;    // H x outline_words(W) words of scratch: bit x & 63 of word (y, x >> 6) = pixel (x, y) is a source of the dilation
+    const uint32_t* invalid;     // the overlay pass's word: non-zero = it refused the frame, nothing is drawn
+    int32_t W, H, x_lo, x_hi;    // the image and the domain's columns [x_lo, x_hi), 0 <= x_lo <= x_hi <= W
+    int32_t width, side;
+    float rgb[3], alpha, threshold;
+    uint8_t hw[OUTLINE_MAX_WIDTH + 1];   // hw[d] = floor(sqrt(width^2 - d^2)) for d <= width: the disc's half-width d rows from its centre
+};
+inline size_t outline_words(int32_t W) { return ((size_t)W + 63) / 64; }
+void launch_outline(const OutlineArgs& a, hipStream_t s);
 
 // multi-GPU exchange helpers (RGBA8 slabs of the all-gather)
 constexpr int MAX_SLABS = 16;

@@ -4,8 +4,11 @@
 // frame left on the device, the scene's selection words and the framebuffer, which it reads and never writes.  The image and the
 // cover plane are the context's; the selection is the scene's, so a context notes that it has a pass in flight and the calls that
 // change the mask wait for the noted members first.  A context that never calls gsr_set_overlay allocates nothing and launches nothing.
+// gsr_set_overlay_outline adds the selection's outline: two more launches behind the pass, which draw the edge of { cover >= threshold }
+// into the image in place; without it nothing here differs by a launch.
 #include "gsr_ctx.h"
 
+#include <algorithm>
 #include <cmath>
 
 using namespace gsr;
@@ -53,6 +56,39 @@ int image_final(gsr_ctx* c, const char* who)
     return GSR_OK;
 }
 
+// the outline's bit plane for this size: the one step of the outline that can fail, taken before anything of the pass is enqueued
+int outline_ensure(gsr_ctx* c)
+{
+    gsr_ctx::Overlay::Outline& ol = c->overlay.outline;
+    const size_t words = outline_words(c->W) * (size_t)c->H;
+    if (words > ol.words || !ol.bits) {
+        ol.words = 0;
+        if (int r = ol.bits.alloc(c, words)) return r;   // (hipFree waits for what still reads the old plane)
+        ol.words = words;
+    }
+    return GSR_OK;
+}
+
+// the outline behind the pass just launched: the edge of { cover >= threshold } into the image, in place
+void outline_enqueue(gsr_ctx* c, const BinGrid& g)
+{
+    gsr_ctx::Overlay& o = c->overlay;
+    gsr_ctx::Overlay::Outline& ol = o.outline;
+    OutlineArgs a{};
+    a.cover = o.cover; a.overlay = o.image; a.bits = ol.bits; a.invalid = o.invalid;
+    a.W = c->W; a.H = c->H;
+    a.x_lo = std::min(g.bx_lo * BIN_PX, c->W); a.x_hi = std::min(g.bx_hi * BIN_PX, c->W);   // the band's bin columns inside the image
+    a.width = ol.width; a.side = ol.side;
+    for (int k = 0; k < 3; k++) a.rgb[k] = ol.rgb[k];
+    a.alpha = ol.alpha; a.threshold = ol.threshold;
+    // the disc's half-widths, in integers: the largest h with h * h <= width^2 - d^2
+    for (int d = 0, h = ol.width; d <= ol.width; d++) {
+        while (h * h > ol.width * ol.width - d * d) h--;
+        a.hw[d] = (uint8_t)h;
+    }
+    launch_outline(a, c->stream);
+}
+
 }  // namespace
 
 int gsr::overlay_enqueue(gsr_ctx* c)
@@ -63,6 +99,8 @@ int gsr::overlay_enqueue(gsr_ctx* c)
     const SharedScene& sc = *c->scene;
     const BinGrid g = make_grid(c);
     const size_t np = (size_t)c->W * c->H;
+    const bool outline = o.outline.on && sc.sel.mask;   // (a scene never selected in: nothing is inside, either side's edge is empty)
+    if (outline) { if (int r = outline_ensure(c)) return r; }
     // A band context's bins do not cover the image and the pass writes the band's columns only: elsewhere cover is 0 and the overlay
     // is whatever the framebuffer holds.
     if (!(g.bx_lo == 0 && g.bx_hi == g.nbx)) {
@@ -78,6 +116,7 @@ int gsr::overlay_enqueue(gsr_ctx* c)
     for (int k = 0; k < 3; k++) b.tint[k] = o.tint[k];
     b.mix = o.mix;
     launch_overlay(b, g, c->cam_frame, c->knobs.depth_skip, c->knobs.overlay_trim, c->stream);
+    if (outline) outline_enqueue(c, g);
     o.serial = c->frame_serial; o.sel_version = sc.sel_version; o.image_opt_version = o.opt_version;
     o.in_flight = true;
     return GSR_OK;
@@ -124,6 +163,41 @@ int gsr_set_overlay(gsr_ctx* c, const gsr_overlay_options* opt)
     for (int k = 0; k < 3; k++) o.tint[k] = opt->tint[k];
     o.mix = opt->mix;
     o.on = true;
+    return GSR_OK;
+}
+
+int gsr_set_overlay_outline(gsr_ctx* c, const gsr_outline_options* opt)
+{
+    if (!c) return GSR_ERR_ARG;
+    gsr_ctx::Overlay& o = c->overlay;
+    gsr_ctx::Overlay::Outline& ol = o.outline;
+    if (opt && !o.on) return fail(c, GSR_ERR_ARG, "gsr_set_overlay_outline: no overlay options (gsr_set_overlay first)");
+    if (!opt) {   // off: the bit plane goes (nothing of it is in flight afterwards: the wait is the free's)
+        if (ol.on) o.opt_version++;
+        if (ol.bits) {
+            HIP_TRY(c, hipSetDevice(c->device));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+        }
+        ol.reset();
+        return GSR_OK;
+    }
+    for (int k = 0; k < 3; k++)
+        if (!std::isfinite(opt->rgb[k])) return fail(c, GSR_ERR_ARG, "gsr_set_overlay_outline: rgb[%d] is not finite", k);
+    if (!(opt->alpha >= 0.0f && opt->alpha <= 1.0f)) return fail(c, GSR_ERR_ARG, "gsr_set_overlay_outline: alpha must be in [0, 1], not %g", (double)opt->alpha);
+    if (!(std::isfinite(opt->threshold) && opt->threshold > 0.0f))
+        return fail(c, GSR_ERR_ARG, "gsr_set_overlay_outline: threshold must be finite and > 0, not %g", (double)opt->threshold);
+    if (opt->width < 1 || opt->width > OUTLINE_MAX_WIDTH)
+        return fail(c, GSR_ERR_ARG, "gsr_set_overlay_outline: width must be in 1 .. %d, not %d", OUTLINE_MAX_WIDTH, (int)opt->width);
+    if (opt->side != GSR_OUTLINE_OUTER && opt->side != GSR_OUTLINE_INNER)
+        return fail(c, GSR_ERR_ARG, "gsr_set_overlay_outline: side must be GSR_OUTLINE_OUTER or GSR_OUTLINE_INNER, not %d", (int)opt->side);
+    for (int k = 0; k < 5; k++)
+        if (opt->reserved[k]) return fail(c, GSR_ERR_ARG, "gsr_set_overlay_outline: gsr_outline_options.reserved must be 0");
+    const bool same = ol.on && ol.alpha == opt->alpha && ol.threshold == opt->threshold && ol.width == opt->width && ol.side == opt->side &&
+                      ol.rgb[0] == opt->rgb[0] && ol.rgb[1] == opt->rgb[1] && ol.rgb[2] == opt->rgb[2];
+    if (!same) o.opt_version++;
+    for (int k = 0; k < 3; k++) ol.rgb[k] = opt->rgb[k];
+    ol.alpha = opt->alpha; ol.threshold = opt->threshold; ol.width = opt->width; ol.side = opt->side;
+    ol.on = true;
     return GSR_OK;
 }
 

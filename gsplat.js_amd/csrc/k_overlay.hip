@@ -22,7 +22,7 @@
 
 namespace gsr {
 
-GSR_BOUNDS_DECL(overlay)   // sites: 0 - 3 the walk's (WALK_SITE_*), 4 selection word, 5 pixel
+GSR_BOUNDS_DECL(overlay)   // sites: 0 - 3 the walk's (WALK_SITE_*), 4 selection word, 5 pixel; the outline's: 6 bit-plane word, 7 pixel
 struct OverlayBounds {
     static __device__ __forceinline__ void bound(int site, unsigned long long idx, unsigned long long limit) { GSR_BOUND(overlay, site, idx, limit); }
 };
@@ -146,6 +146,107 @@ void launch_overlay(const OverlayBuffers& b, const BinGrid& g, const CamParams& 
 {
     if (skip) walk_launch(trim ? k_overlay<true, true> : k_overlay<true, false>, b, g, cam, s);
     else walk_launch(trim ? k_overlay<false, true> : k_overlay<false, false>, b, g, cam, s);
+}
+
+// ---- selection outline --------------------------------------------------------------------------------------------------------
+// The edge of inside = { cover >= threshold } within the domain (the band's columns inside the image, every row), drawn into the
+// overlay image behind k_overlay, in place ("Selection overlay"):
+//     outer: edge(p) = !inside(p), and a q of the domain with inside(q) lies within (qx - px)^2 + (qy - py)^2 <= width^2
+//     inner: the same with inside and !inside exchanged
+//     at an edge pixel, k = 1 - alpha:  out.rgb = fma(ov.rgb, k, rgb * alpha),  out.a = fma(ov.a, k, alpha)
+// Both sides are one dilation: with SOURCE = inside (outer) or domain & !inside (inner), edge = domain & !SOURCE & dilate(SOURCE).
+// k_outline_bits ballots SOURCE into a bit plane, one 64-bit word per 64 pixels of a row (bit x & 63 of word (y, x >> 6); columns
+// outside the domain give 0).  k_outline_apply, one wave per word, folds the rows y - width .. y + width around it from the centre
+// outwards -- F_0 = row y, F_d = dilate(F_{d-1}, hw[d-1] - hw[d]) | row (y + d) | row (y - d), so that a row d away ends up
+// spread by hw[d], the disc's half-width there -- on three wave-uniform words (wx - 1, wx, wx + 1: width <= 16 never reaches past
+// them), and only the lanes whose edge bit is set read and rewrite their pixel.  An edge bit depends on cover alone, so writing
+// the image in place is safe.  A pass that refused its frame (the invalid word) draws nothing.
+constexpr int OUTLINE_THREADS = 256, OUTLINE_WAVES = OUTLINE_THREADS / WAVE;   // sites: 6 a word of the bit plane, 7 a pixel
+
+// the domain's bits of word wx: the columns [x_lo, x_hi) that fall into [64 wx, 64 wx + 64)
+__device__ __forceinline__ uint64_t outline_domain(const OutlineArgs& a, int wx)
+{
+    const int lo = max(a.x_lo - wx * 64, 0), hi = min(a.x_hi - wx * 64, 64);
+    if (hi <= lo) return 0ull;
+    return (hi >= 64 ? ~0ull : (1ull << hi) - 1ull) & ~((1ull << lo) - 1ull);
+}
+
+// the word this wave owns (uniform), false behind the plane's last one
+__device__ __forceinline__ bool outline_word(const OutlineArgs& a, int& nw, uint32_t& word)
+{
+    nw = (a.W + 63) >> 6;
+    word = blockIdx.x * (uint32_t)OUTLINE_WAVES + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    return word < (uint32_t)nw * (uint32_t)a.H;
+}
+
+__global__ __launch_bounds__(OUTLINE_THREADS) void k_outline_bits(OutlineArgs a)
+{
+    if (*a.invalid != 0u) return;
+    int nw; uint32_t word;
+    if (!outline_word(a, nw, word)) return;
+    const int y = (int)(word / (uint32_t)nw), wx = (int)word - y * nw, lane = threadIdx.x & 63, x = wx * 64 + lane;
+    bool source = false;
+    if (x >= a.x_lo && x < a.x_hi) {
+        const size_t o = (size_t)y * a.W + x;
+        GSR_BOUND(overlay, 7, o, (size_t)a.W * a.H);
+        const bool inside = a.cover[o] >= a.threshold;   // (a NaN is not inside)
+        source = inside != (a.side == OUTLINE_INNER);
+    }
+    const uint64_t bal = __ballot(source);
+    if (lane == 0) {
+        GSR_BOUND(overlay, 6, word, (size_t)nw * a.H);
+        a.bits[word] = bal;
+    }
+}
+
+__global__ __launch_bounds__(OUTLINE_THREADS) void k_outline_apply(OutlineArgs a)
+{
+    if (*a.invalid != 0u) return;
+    int nw; uint32_t word;
+    if (!outline_word(a, nw, word)) return;
+    const int y = (int)(word / (uint32_t)nw), wx = (int)word - y * nw, lane = threadIdx.x & 63;
+    uint64_t l = 0ull, c = 0ull, r = 0ull;   // F of the words wx - 1, wx, wx + 1
+    auto fold_row = [&](int yy) {            // rows outside the image are outside the domain
+        if (yy < 0 || yy >= a.H) return;
+        const size_t at = (size_t)yy * nw + wx;
+        GSR_BOUND(overlay, 6, at, (size_t)nw * a.H);
+        c |= a.bits[at];
+        if (wx > 0) l |= a.bits[at - 1];
+        if (wx + 1 < nw) r |= a.bits[at + 1];
+    };
+    fold_row(y);
+    const uint64_t own = c;
+    for (int d = 1; d <= a.width; d++) {
+        for (int s = (int)a.hw[d - 1] - (int)a.hw[d]; s > 0; s--) {   // one column to either side per step
+            const uint64_t nl = l | (l << 1) | (l >> 1) | (c << 63);
+            const uint64_t nc = c | (c << 1) | (c >> 1) | (l >> 63) | (r << 63);
+            const uint64_t nr = r | (r << 1) | (r >> 1) | (c >> 63);
+            l = nl; c = nc; r = nr;
+        }
+        fold_row(y + d);
+        fold_row(y - d);
+    }
+    const uint64_t edge = outline_domain(a, wx) & ~own & c;
+    if ((edge >> lane) & 1ull) {
+        const size_t o = (size_t)y * a.W + (size_t)(wx * 64 + lane);
+        GSR_BOUND(overlay, 7, o, (size_t)a.W * a.H);
+        float4 v = a.overlay[o];
+        const float k = 1.0f - a.alpha;
+        v.x = __builtin_fmaf(v.x, k, a.rgb[0] * a.alpha);
+        v.y = __builtin_fmaf(v.y, k, a.rgb[1] * a.alpha);
+        v.z = __builtin_fmaf(v.z, k, a.rgb[2] * a.alpha);
+        v.w = __builtin_fmaf(v.w, k, a.alpha);
+        a.overlay[o] = v;
+    }
+}
+
+void launch_outline(const OutlineArgs& a, hipStream_t s)
+{
+    const size_t words = outline_words(a.W) * (size_t)a.H;
+    if (!words) return;
+    const uint32_t blocks = (uint32_t)((words + OUTLINE_WAVES - 1) / OUTLINE_WAVES);
+    k_outline_bits<<<blocks, OUTLINE_THREADS, 0, s>>>(a);
+    k_outline_apply<<<blocks, OUTLINE_THREADS, 0, s>>>(a);
 }
 
 }  // namespace gsr

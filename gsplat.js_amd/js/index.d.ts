@@ -360,6 +360,12 @@ export class HIPRenderer {
      *  the frame.  Refused in a group. */
     setSelectionOverlay(options: { tint?: [number, number, number]; mix?: number } | null): void;
     readOverlay(): { rgba: Float32Array; cover: Float32Array };
+    /** Selection outline: the overlay image with the selection's edge drawn into it (needs setSelectionOverlay; null: off).  A pixel
+     *  is inside where cover >= threshold (> 0); side "outer" draws the pixels around the selection within `width` (1 .. 16) of an
+     *  inside pixel, "inner" the inside pixels within `width` of one that is not.  An edge pixel becomes lerp(overlay, color, alpha),
+     *  its alpha lerp(a, 1, alpha).  readOverlay, readPixels({ overlay: true }) and an overlay ring all show it; cover is unchanged.
+     *  Defaults: color [1, 1, 1], alpha 1, threshold 0.5, width 2, side "outer". */
+    setSelectionOutline(options: { color?: [number, number, number]; alpha?: number; threshold?: number; width?: number; side?: "outer" | "inner" } | null): void;
     readPixels(options: { overlay?: boolean; out?: Uint8Array }): Uint8Array;
     readPixels(out?: Uint8Array): Uint8Array;
     readPixelsFloat(out?: Float32Array): Float32Array;

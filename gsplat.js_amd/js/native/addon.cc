@@ -1350,6 +1350,25 @@ napi_value SetOverlay(napi_env env, napi_callback_info info)
     return rc ? throw_gsr(env, c, rc, "gsr_set_overlay") : undefined(env);
 }
 
+// setOutline(handle, on, r, g, b, alpha, threshold, width, side): on = 0 switches the outline off (the other arguments are not read)
+napi_value SetOutline(napi_env env, napi_callback_info info)
+{
+    napi_value argv[9];
+    if (!get_args(env, info, 9, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    int32_t on;
+    if (!c || !get_i32(env, argv[1], &on)) return nullptr;
+    if (!on) { const int rc = gsr_set_overlay_outline(c, nullptr); return rc ? throw_gsr(env, c, rc, "gsr_set_overlay_outline") : undefined(env); }
+    double v[5];
+    for (int k = 0; k < 5; k++)
+        if (!get_f64(env, argv[2 + k], &v[k])) { napi_throw_type_error(env, nullptr, "setOutline(handle, on, r, g, b, alpha, threshold, width, side): numbers"); return nullptr; }
+    gsr_outline_options o{};
+    o.rgb[0] = (float)v[0]; o.rgb[1] = (float)v[1]; o.rgb[2] = (float)v[2]; o.alpha = (float)v[3]; o.threshold = (float)v[4];
+    if (!get_i32(env, argv[7], &o.width) || !get_i32(env, argv[8], &o.side)) return nullptr;
+    const int rc = gsr_set_overlay_outline(c, &o);
+    return rc ? throw_gsr(env, c, rc, "gsr_set_overlay_outline") : undefined(env);
+}
+
 // readOverlay(handle, width, height) -> { rgba: Float32Array(w * h * 4), cover: Float32Array(w * h) }
 napi_value ReadOverlay(napi_env env, napi_callback_info info)
 {
@@ -1427,7 +1446,7 @@ napi_value Init(napi_env env, napi_value exports)
         {"contribReset", Call0<gsr_contrib_reset>}, {"contribAccumulate", Call0<gsr_contrib_accumulate_async>}, {"readContrib", ReadContrib},
         {"selectContrib", SelectContrib},
         {"setOverlay", SetOverlay}, {"readOverlay", ReadOverlay}, {"readOverlayPixels", ReadOverlayPixels},
-        {"deliverySetOverlay", DeliverySetOverlay},
+        {"deliverySetOverlay", DeliverySetOverlay}, {"setOutline", SetOutline},
     };
     for (auto& f : fns) {
         napi_value fn;

@@ -521,6 +521,20 @@ class HIPRenderer {
             this._n.setOverlay(this._h, 1, +t[0], +t[1], +t[2], +mix);
         };
         this.readOverlay = () => this._n.readOverlay(this._h, this.width, this.height);
+        // ---- selection outline (gsr_set_overlay_outline): the overlay image with the selection's edge drawn into it ----
+        //   renderer.setSelectionOutline({ color: [1, 1, 1], alpha: 1, threshold: 0.5, width: 2, side: "outer" });
+        // A pixel is inside where cover >= threshold; "outer" draws the pixels around the selection within `width` (1 .. 16) of an
+        // inside pixel, "inner" the inside pixels within `width` of one that is not.  Needs setSelectionOverlay; null switches it off.
+        const SIDES = { outer: 0, inner: 1 };
+        this.setSelectionOutline = (options) => {
+            if (options === null || options === undefined) { this._n.setOutline(this._h, 0, 0, 0, 0, 0, 0, 0, 0); return; }
+            const t = options.color === undefined ? [1, 1, 1] : options.color;
+            if (!t || t.length !== 3) throw new Error("setSelectionOutline: color must be [r, g, b]");
+            const alpha = options.alpha === undefined ? 1 : options.alpha, threshold = options.threshold === undefined ? 0.5 : options.threshold;
+            const width = options.width === undefined ? 2 : options.width;
+            if (!Number.isInteger(width)) throw new Error("setSelectionOutline: width must be an integer");
+            this._n.setOutline(this._h, 1, +t[0], +t[1], +t[2], +alpha, +threshold, width, code(SIDES, options.side, "outer", "side"));
+        };
         this.stats = () => this._n.getTimings(this._h);
         this.deviceInfo = () => this._n.deviceInfo(this._h);
         this.isInitialized = () => initialized;

@@ -74,6 +74,11 @@ class GsrOverlayOptions(ctypes.Structure):
     _fields_ = [("tint", ctypes.c_float * 3), ("mix", ctypes.c_float), ("reserved", ctypes.c_int32 * 4)]
 
 
+class GsrOutlineOptions(ctypes.Structure):
+    _fields_ = [("rgb", ctypes.c_float * 3), ("alpha", ctypes.c_float), ("threshold", ctypes.c_float), ("width", ctypes.c_int32),
+                ("side", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
+
+
 class GsrDepthLayout(ctypes.Structure):
     _fields_ = [("format", ctypes.c_int32), ("step", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
                 ("stride", ctypes.c_int32), ("reserved", ctypes.c_int32), ("offset", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
@@ -84,6 +89,7 @@ GSR_FORMAT_RGBA8, GSR_FORMAT_NV12, GSR_FORMAT_I420 = 0, 1, 2
 DELIVERY_FORMATS = {"rgba8": GSR_FORMAT_RGBA8, "nv12": GSR_FORMAT_NV12, "i420": GSR_FORMAT_I420}
 GSR_DEPTH_NONE, GSR_DEPTH_F32, GSR_DEPTH_U16 = 0, 1, 2
 DEPTH_DELIVERY_FORMATS = {"f32": GSR_DEPTH_F32, "u16": GSR_DEPTH_U16}
+OUTLINE_SIDES = {"outer": 0, "inner": 1}                                   # GSR_OUTLINE_*
 SELECT_MODES = {"centre": 0, "hit": 1}                                     # GSR_SELECT_*
 SELECT_OPS = {"replace": 0, "add": 1, "subtract": 2, "intersect": 3}       # GSR_SELOP_*
 CONTRIB_STATS = {"weight": 0, "peak": 1, "pixels": 2}                      # GSR_CONTRIB_*
@@ -128,6 +134,7 @@ EXPORTS = [
     "gsr_scene_reserve", "gsr_scene_capacity", "gsr_scene_duplicate_selected", "gsr_scene_append_selected", "gsr_scene_append_arrays",
     "gsr_contrib_reset", "gsr_contrib_accumulate_async", "gsr_read_contrib", "gsr_select_contrib",
     "gsr_set_overlay", "gsr_overlay_async", "gsr_read_overlay", "gsr_read_overlay_rgba8", "gsr_overlay_device_ptr", "gsr_delivery_set_overlay",
+    "gsr_set_overlay_outline",
 ]
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p)
 GSR_COMM_ID_BYTES = 128
@@ -286,6 +293,7 @@ def load_library(path=None):
     L.gsr_read_contrib.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, u32p]
     L.gsr_select_contrib.argtypes = [vp, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, u32p]
     L.gsr_set_overlay.argtypes = [vp, ctypes.POINTER(GsrOverlayOptions)]
+    L.gsr_set_overlay_outline.argtypes = [vp, ctypes.POINTER(GsrOutlineOptions)]
     L.gsr_overlay_async.argtypes = [vp]
     L.gsr_read_overlay.argtypes = [vp, vp, vp]
     L.gsr_read_overlay_rgba8.argtypes = [vp, vp]
@@ -1082,6 +1090,22 @@ class HIPRenderer:
             raise ValueError("tint must be three values (r, g, b)")
         opt = GsrOverlayOptions((ctypes.c_float * 3)(*t), float(mix), (ctypes.c_int32 * 4)())
         self._check(self._L.gsr_set_overlay(self._ctx, ctypes.byref(opt)))
+
+    def set_overlay_outline(self, rgb=(1.0, 1.0, 1.0), alpha=1.0, threshold=0.5, width=2, side="outer"):
+        """The selection's outline, drawn into the overlay image behind every pass (needs set_overlay): a pixel is inside where
+        cover >= threshold; side "outer" draws the pixels around the selection within `width` (1 .. 16) of an inside pixel, "inner"
+        the inside pixels within `width` of one that is not.  An edge pixel becomes lerp(overlay, rgb, alpha), its alpha
+        lerp(a, 1, alpha).  rgb=None: off.  Everything that shows the overlay -- read_overlay*, a ring with delivery_set_overlay --
+        shows the outline; cover does not change."""
+        if rgb is None:
+            self._check(self._L.gsr_set_overlay_outline(self._ctx, None))
+            return
+        t = [float(v) for v in rgb]
+        if len(t) != 3:
+            raise ValueError("rgb must be three values (r, g, b)")
+        opt = GsrOutlineOptions((ctypes.c_float * 3)(*t), float(alpha), float(threshold), int(width),
+                                self._select_code(OUTLINE_SIDES, side, "side"), (ctypes.c_int32 * 5)())
+        self._check(self._L.gsr_set_overlay_outline(self._ctx, ctypes.byref(opt)))
 
     def overlay_async(self):
         """Enqueue the overlay pass behind the frame enqueued last (no host wait)."""

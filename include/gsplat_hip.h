@@ -759,7 +759,7 @@ int gsr_select_contrib(gsr_ctx *ctx, int32_t stat, double below, int32_t op, uin
  * (float)byte * (1.0f / 255.0f) of the record's colour bytes, or the frame's evaluated SH colour for an SH-coloured splat.  From
  * T = 1, S = 0, C = (0, 0, 0), in f32:  w = T * B; T = T - w; and if the splat is selected: S = S + w; Cr = fma(w, cr, Cr), Cg and
  * Cb likewise.  Two results, both W x H with row 0 at the top:
- *   cover, float: S, the share of the pixel's alpha that selected splats supply (a host draws outlines from it).
+ *   cover, float: S, the share of the pixel's alpha that selected splats supply (gsr_set_overlay_outline draws the selection's edge from it).
  *   overlay, float4, premultiplied like the framebuffer: with fb the frame's framebuffer value at the pixel,
  *     out.r = fma(mix, fma(tint[0], S, -Cr), fb.r), g and b likewise; out.a = fb.a.  This is the frame rendered with every selected
  *     splat's colour replaced by lerp(c, tint, mix).  mix == 0, or a pixel with no selected fragment, gives fb bit for bit.
@@ -799,6 +799,40 @@ int gsr_read_overlay(gsr_ctx *ctx, float *rgba /* w*h*4 */, float *cover /* w*h 
 int gsr_read_overlay_rgba8(gsr_ctx *ctx, uint8_t *out);
 void *gsr_overlay_device_ptr(gsr_ctx *ctx, int32_t plane);   /* 0 overlay, 1 cover */
 int gsr_delivery_set_overlay(gsr_ctx *ctx, int32_t on);
+
+/* ---- selection outline ---- the overlay draws the edge of the selection
+ * An editor shows a selection by its outline.  With outline options set, every overlay pass is followed by a step that draws the
+ * edge of the selected region into the overlay image, so everything that consumes that image -- gsr_read_overlay,
+ * gsr_read_overlay_rgba8, gsr_overlay_device_ptr(ctx, 0) and a ring switched with gsr_delivery_set_overlay, RGBA8 and Y'CbCr
+ * alike -- gets the outlined image with no further change.  cover is never changed.
+ * Definition ("Selection overlay").  The domain is the pixels the pass defines: the whole image, or for a band
+ * context the pixels of its own bin columns that lie inside the image.  For p in the domain, inside(p) = (cover[p] >= threshold),
+ * an f32 compare: a NaN is not inside.  Pixels outside the domain are neither inside nor outside: the neighbourhood ignores them
+ * and they are never written.  With r = width, in integers:
+ *   side GSR_OUTLINE_OUTER: edge(p) = !inside(p) and there is a q in the domain with inside(q) and (qx-px)^2 + (qy-py)^2 <= r*r;
+ *   side GSR_OUTLINE_INNER: the same with inside and !inside exchanged.
+ * With ov the overlay value the pass produced, where edge(p), in f32:  k = 1.0f - alpha;  out.c = fma(ov.c, k, rgb[c] * alpha) for
+ * c = r, g, b;  out.a = fma(ov.a, k, alpha).  Everywhere else out = ov bit for bit.  Nothing is clamped here.
+ * A pass whose frame did not fit draws nothing.  A scene never selected in has an empty outline on either side.
+ * gsr_set_overlay_outline needs overlay options (gsr_set_overlay first); rgb must be finite, alpha in [0, 1], threshold finite
+ *   and > 0, width in 1 .. 16, side GSR_OUTLINE_OUTER or GSR_OUTLINE_INNER, reserved 0, else GSR_ERR_ARG and nothing changes.
+ *   NULL: off (always accepted); like gsr_set_overlay(ctx, NULL) it waits for the context's stream when it frees the bit plane.
+ *   Setting options makes no host wait; one bit per pixel is allocated by the first pass that draws (and again when the image
+ *   grows, where freeing the smaller plane waits for what still reads it).
+ *   Changed outline options make the image stale exactly as changed overlay options do; equal options do not.
+ *   gsr_set_overlay(ctx, NULL) clears the outline too.  Off -- the default -- the overlay is bit for bit and launch for launch
+ *   what it is without this call. */
+#define GSR_OUTLINE_OUTER 0
+#define GSR_OUTLINE_INNER 1
+typedef struct gsr_outline_options {
+    float rgb[3];         /* the outline's colour, as the framebuffer's channels (not clamped) */
+    float alpha;          /* how much of the pixel the outline replaces; in [0, 1] */
+    float threshold;      /* a pixel is inside the selection where cover >= threshold; finite, > 0 */
+    int32_t width;        /* the outline's width in pixels: the radius of the disc; 1 .. 16 */
+    int32_t side;         /* GSR_OUTLINE_OUTER: on the pixels around the selection; GSR_OUTLINE_INNER: on its own border pixels */
+    int32_t reserved[5];  /* 0 */
+} gsr_outline_options;
+int gsr_set_overlay_outline(gsr_ctx *ctx, const gsr_outline_options *options);   /* NULL: off */
 
 /* ---- device interop (torch / RCCL plumbing in the harness) ---- */
 void *gsr_framebuffer_device_ptr(gsr_ctx *ctx); /* float4[h][w] on the device */

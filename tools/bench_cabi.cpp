@@ -3,7 +3,7 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--share-scene]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--share-scene]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
@@ -14,6 +14,8 @@
 // --overlay FRACTION selects that fraction of the splats (scattered over the indices) through gsr_selection_set and adds legs in which
 // gsr_overlay_async is enqueued behind every frame, alternated with plain legs as --depth does; then the pass alone on sampled frames
 // (overlay_pass_us; with --depth the depth pass on the same frames, depth_pass_us) and the hashes of the overlay's RGBA8 and cover.
+// --outline WIDTH (with --overlay) also sets the selection's outline (gsr_set_overlay_outline: white, outer, threshold 0.5), so that
+// every overlay pass counted above draws it: overlay_pass_us with and without it is the outline step's cost.
 // --contrib adds legs in which gsr_contrib_accumulate_async is enqueued behind every frame, alternated with plain legs as --depth
 // does, then times the pass alone on sampled frames (host clock around the enqueue and the wait, the smallest of 20; beside --depth
 // the depth pass the same way) and reports `frames` and the FNV-1a of the three accumulator arrays.
@@ -162,6 +164,7 @@ int main(int argc, char** argv)
     float depth_near = 0.1f;
     bool contrib = false;
     double overlay_fraction = -1.0;   // < 0: off
+    int outline_width = 0;            // 0: off
     bool depth = false, pick = false, scene_arrays = false, share_scene = false;
     std::string scene_edit = "none";
     double hide_fraction = -1.0;   // < 0: off
@@ -186,6 +189,7 @@ int main(int argc, char** argv)
         else if (a == "--depth-near") depth_near = (float)std::atof(next());
         else if (a == "--depth") depth = true;
         else if (a == "--contrib") contrib = true;
+        else if (a == "--outline" && i + 1 < argc) { outline_width = std::atoi(argv[++i]); if (outline_width < 1 || outline_width > 16) { std::fprintf(stderr, "--outline WIDTH must be in 1 .. 16\n"); return 2; } }
         else if (a == "--overlay" && i + 1 < argc) { overlay_fraction = std::atof(argv[++i]); if (!(overlay_fraction >= 0.0 && overlay_fraction <= 1.0)) { std::fprintf(stderr, "--overlay FRACTION must be in [0, 1]\n"); return 2; } }
         else if (a == "--hide" && i + 1 < argc) { hide_fraction = std::atof(argv[++i]); if (!(hide_fraction >= 0.0 && hide_fraction <= 1.0)) { std::fprintf(stderr, "--hide FRACTION must be in [0, 1]\n"); return 2; } }
         else if (a == "--hide-edits") hide_edits = true;
@@ -196,7 +200,7 @@ int main(int argc, char** argv)
         else if (a == "--scene-edit") scene_edit = next();
         else if (a == "--share-scene") share_scene = true;
         else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--share-scene]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--share-scene]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
@@ -207,6 +211,7 @@ int main(int argc, char** argv)
     if (depth_format == GSR_DEPTH_NONE && deliver_depth != "none") { std::fprintf(stderr, "--deliver-depth f32|u16\n"); return 2; }
     if (scene_edit != "none" && scene_edit != "rotate") { std::fprintf(stderr, "--scene-edit rotate\n"); return 2; }
     if (depth_format != GSR_DEPTH_NONE && !deliver) { std::fprintf(stderr, "--deliver-depth goes beside --deliver\n"); return 2; }
+    if (outline_width && overlay_fraction < 0.0) { std::fprintf(stderr, "--outline WIDTH goes beside --overlay FRACTION\n"); return 2; }
 
     std::vector<uint8_t> rows;
     if (!rows_path.empty()) {
@@ -373,6 +378,11 @@ int main(int argc, char** argv)
         gsr_overlay_options oo{};
         oo.tint[0] = 1.0f; oo.tint[1] = 0.5f; oo.tint[2] = 0.0f; oo.mix = 0.5f;
         for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_set_overlay(c, &oo)); }
+        if (outline_width) {   // the selection's outline behind every overlay pass: the legs, the pass and the hashes below include it
+            gsr_outline_options ol{};
+            ol.rgb[0] = ol.rgb[1] = ol.rgb[2] = 1.0f; ol.alpha = 1.0f; ol.threshold = 0.5f; ol.width = outline_width; ol.side = GSR_OUTLINE_OUTER;
+            for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_set_overlay_outline(c, &ol)); }
+        }
         for (int leg = 0; leg < 6; leg++) {
             const bool with = leg & 1;
             auto overlay_step = [&](int k) -> int {
@@ -596,6 +606,7 @@ int main(int argc, char** argv)
         std::printf(", \"overlay_fraction\": %g, \"overlay_selected\": %u, \"frames_per_sec_without_overlay\": %.1f, \"frames_per_sec_with_overlay\": %.1f, "
                     "\"overlay_legs\": 3, \"overlay_pass_us\": %.1f, \"overlay_rgba8_fnv1a\": \"%016llx\", \"overlay_cover_fnv1a\": \"%016llx\"",
                     overlay_fraction, overlay_selected, 3.0 * frames / overlay_sec[0], 3.0 * frames / overlay_sec[1], overlay_pass_us, overlay_hash[0], overlay_hash[1]);
+        if (outline_width) std::printf(", \"outline_width\": %d", outline_width);
         if (depth) std::printf(", \"depth_pass_us\": %.1f", overlay_depth_pass_us);
     }
     if (contrib) {
