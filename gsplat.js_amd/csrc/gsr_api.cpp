@@ -50,6 +50,8 @@ Knobs read_knobs(std::string& bad)
     }
     if (const char* e = getenv("GSR_DEPTH_SKIP")) k.depth_skip = atoi(e) != 0;
     if (const char* e = getenv("GSR_OVERLAY_TRIM")) k.overlay_trim = atoi(e) != 0;
+    if (const char* e = getenv("GSR_ATTR_HIST")) k.attr_hist_peel = strcmp(e, "peel") == 0;
+    if (const char* e = getenv("GSR_ATTR_HIST_GRID")) k.attr_hist_grid = (uint32_t)std::min(std::max(atol(e), 0l), 65535l);
     return k;
 }
 

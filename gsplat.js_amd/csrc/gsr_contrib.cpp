@@ -11,14 +11,14 @@
 
 using namespace gsr;
 
-namespace {
-
 // nothing of any member is in flight afterwards: the streams that may hold passes
-int settle_members(gsr_ctx* c)
+int gsr::settle_members(gsr_ctx* c)
 {
     for (gsr_ctx* m : c->scene->members) HIP_TRY(c, hipStreamSynchronize(m->stream));
     return GSR_OK;
 }
+
+namespace {
 
 // gsr_contrib_reset: the accumulators for the scene's count, allocated by the first call, zeroed and final on the device
 int reset_accumulators(gsr_ctx* c)

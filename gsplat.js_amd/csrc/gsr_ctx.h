@@ -95,6 +95,8 @@ struct Knobs {
     uint32_t front_waves = 0;    // GSR_FRONT_WAVES=8|16: waves per workgroup of the heavy front-end kernels (0: by the kind of context)
     bool depth_skip = true;      // GSR_DEPTH_SKIP=0: the depth pass visits every entry in every tile (no skip of entries that cannot reach a tile)
     bool overlay_trim = true;    // GSR_OVERLAY_TRIM=0: the overlay pass walks every list to its end (no stop behind the last selected entry)
+    bool attr_hist_peel = false; // GSR_ATTR_HIST=peel: k_attr_hist peels the bin of each wave's first lane before the LDS atomics (the same counts; measured slower)
+    uint32_t attr_hist_grid = 0; // GSR_ATTR_HIST_GRID: workgroups of k_attr_hist (0: by the device)
 };
 
 // The scene's per-splat arrays: everything the on-device build, the transforms and the compaction move together.
@@ -495,6 +497,12 @@ struct gsr_ctx {
         void reset() { on = false; image.reset(); cover.reset(); image8.reset(); invalid.reset(); pixels = 0; serial = 0; outline.reset(); }
     } overlay;
 
+    // splat data (gsr_attr.cpp): the device words of gsr_attr_stats / gsr_attr_histogram, the context's own; nothing is allocated
+    // until the first such call
+    struct Attr {
+        gsr::DevBuf<uint32_t> words;        // ATTR_HIST_WORDS histogram counters, then ATTR_MAX_GRID + 1 AttrStats (the partials, the result)
+    } attr;
+
     // frame delivery (gsr_delivery_open): a ring of pinned host blocks, each with its device staging and "copy done" event
     struct Delivery {
         struct Slot {
@@ -607,6 +615,9 @@ int set_read(gsr_ctx* c, const SplatSet& s, const char* who, uint32_t* words, ui
 int hidden_ensure(gsr_ctx* c);
 int select_ensure(gsr_ctx* c);
 int select_fold_and_count(gsr_ctx* c, int op, uint32_t* selected);
+// gsr_contrib.cpp: what the blocking calls that read per-splat state of a scene do first: waits for every member's stream, so
+// that nothing of any member (a contribution pass, an edit) is in flight afterwards
+int settle_members(gsr_ctx* c);
 // gsr_comm.cpp
 void comm_release(gsr_ctx* c);
 // gsr_depth.cpp: the depth pass for the frame enqueued last.  depth_frame_check: what every pass demands of that frame (GSR_ERR_ARG,

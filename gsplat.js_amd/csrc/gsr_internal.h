@@ -524,6 +524,49 @@ void launch_contrib(const ContribBuffers& b, const BinGrid& g, const CamParams& 
 void launch_contrib_select(int stat, double below, uint32_t n, const unsigned long long* weight, const uint32_t* peak, const uint32_t* pixels,
                            uint32_t* scratch, uint32_t nwords, hipStream_t s);
 
+// Splat data (k_attr.hip; DESIGN.md section 4, "Splat data"): the scene's own attributes reduced, binned and picked by range.
+// The value of attribute `attr` of splat i is attr_value (k_attr.h), an f64; the codes are GSR_ATTR_*.
+constexpr int ATTR_X = 0, ATTR_Y = 1, ATTR_Z = 2, ATTR_DISTANCE = 3, ATTR_RED = 4, ATTR_GREEN = 5, ATTR_BLUE = 6, ATTR_OPACITY = 7,
+              ATTR_SCALE_X = 8, ATTR_SCALE_Y = 9, ATTR_SCALE_Z = 10, ATTR_SCALE_MIN = 11, ATTR_SCALE_MAX = 12,
+              ATTR_CONTRIB_WEIGHT = 13, ATTR_CONTRIB_PEAK = 14, ATTR_CONTRIB_PIXELS = 15, ATTR_COUNT = 16;
+static_assert(ATTR_CONTRIB_PEAK == ATTR_CONTRIB_WEIGHT + CONTRIB_PEAK && ATTR_CONTRIB_PIXELS == ATTR_CONTRIB_WEIGHT + CONTRIB_PIXELS,
+              "the contribution attributes are GSR_CONTRIB_* behind ATTR_CONTRIB_WEIGHT");
+// where the values come from; a kernel reads only the arrays its attribute names (the others may be null)
+struct AttrSource {
+    const float *px, *py, *pz;
+    const uint32_t* rgba;                  // r | g << 8 | b << 16 | opacity << 24 (gsr_scene_set_rgba_selected's numbering)
+    const float4* scl;                     // Scene._scales
+    const unsigned long long* weight;      // the contribution accumulators (ContribBuffers)
+    const uint32_t* peak;
+    const uint32_t* pixels;
+    double ox, oy, oz;                     // ATTR_DISTANCE: the origin
+};
+constexpr uint32_t ATTR_SCOPE_SELECTED = 1u, ATTR_SCOPE_VISIBLE = 2u;   // (GSR_SCOPE_*)
+struct AttrScope {
+    uint32_t flags;                        // ATTR_SCOPE_*; 0: every splat
+    const uint32_t* sel; uint32_t sel_words;   // the selection's words (null: never selected in, nothing is in a SELECTED scope)
+    const uint32_t* hid; uint32_t hid_words;   // the hidden set's words (null: nothing is hidden)
+};
+struct AttrStats { uint32_t count, nan; double mn, mx; };   // splats in scope, those with a NaN value, min / max of the others ((+inf, -inf): none)
+constexpr uint32_t ATTR_MAX_BINS = 4096;                    // bins + 3 counters of 4 bytes: an LDS histogram of 16 KB
+constexpr uint32_t ATTR_MAX_GRID = 1024;                    // workgroups of a reduction at most = partials of k_attr_stats
+struct AttrRange { double lo, hi, w; uint32_t bins; };      // [lo, hi) in `bins` bins of w = (hi - lo) / (double)bins
+constexpr int ATTR_HIST_PLAIN = 0, ATTR_HIST_PEEL = 1;     // k_attr_hist's forms (Knobs::attr_hist_peel)
+// Workgroups of a reduction over n splats: per_cu per compute unit -- from the device, not from n -- at most ATTR_MAX_GRID and
+// never more than ceil(n / 256).  k_attr_stats takes four per compute unit; k_attr_hist two, because every workgroup ends with
+// one global atomic per non-zero counter and same-address atomics of many workgroups queue up (512
+// workgroups measured fastest, 1024 a third slower, one per 256 splats nearly four times slower).
+constexpr uint32_t ATTR_STATS_WG_PER_CU = 4, ATTR_HIST_WG_PER_CU = 2;
+uint32_t attr_grid(uint32_t n, int cu_count, uint32_t per_cu);
+// partial: attr_grid(n, cu_count, ATTR_STATS_WG_PER_CU) entries of scratch; *out: the result.  n >= 1.
+void launch_attr_stats(int attr, const AttrSource& src, const AttrScope& sc, uint32_t n, int cu_count, AttrStats* partial, AttrStats* out, hipStream_t s);
+// counters[0 .. bins) += the bins, [bins] += values below lo, [bins + 1] += at or above hi, [bins + 2] += NaN: zeroed by the caller.  n >= 1.
+// (blocks: any number of workgroups gives the same counters; attr_grid unless GSR_ATTR_HIST_GRID pins it)
+void launch_attr_hist(int attr, const AttrSource& src, const AttrScope& sc, uint32_t n, uint32_t blocks, const AttrRange& r, int form, uint32_t* counters,
+                      hipStream_t s);
+// scratch <- the splats i < n with lo <= value < hi: every word of it is stored, no zeroing needed
+void launch_attr_select(int attr, const AttrSource& src, uint32_t n, double lo, double hi, uint32_t* scratch, uint32_t nwords, hipStream_t s);
+
 // Selection overlay (k_overlay.hip; DESIGN.md section 4, "Selection overlay"): the last frame's bin lists walked once more, the
 // weight w = T * B of every fragment of a SELECTED splat summed per pixel (cover) and, with the splat's colour, turned into the
 // frame with those splats tinted (overlay).  Reads the framebuffer, never writes it.

@@ -20,6 +20,7 @@
 // occurs once in a bin's list, so global atomics number three per (bin, covering entry).
 //
 // Compiled with -ffp-contract=off like the rest of the device code: the fused multiply-adds are the explicit ones.
+#include "k_attr.h"
 #include "k_depth_walk.h"
 
 namespace gsr {
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(DEPTH_THREADS) void k_contrib(ContribBuffers a, Bin
     }
 }
 
-// gsr_select_contrib.  One thread per splat: its value in f64, compared with `below`.  A wave's 64-bit ballot IS two whole words
+// gsr_select_contrib.  One thread per splat: its value in f64 (attr_value, k_attr.h), compared with `below`.  A wave's 64-bit ballot IS two whole words
 // of the mask (k_select_box): lane 0 stores them, no atomics, and every word of the mask is stored (splats at and above n vote 0).
 __global__ __launch_bounds__(CONTRIB_SELECT_THREADS) void k_contrib_select(int stat, double below, uint32_t n, const unsigned long long* __restrict__ weight,
                                                                            const uint32_t* __restrict__ peak, const uint32_t* __restrict__ pixels,
@@ -156,8 +157,8 @@ __global__ __launch_bounds__(CONTRIB_SELECT_THREADS) void k_contrib_select(int s
     const uint32_t i = blockIdx.x * CONTRIB_SELECT_THREADS + threadIdx.x;
     bool in = false;
     if (i < n) {
-        const double v = stat == CONTRIB_WEIGHT ? (double)weight[i] * (1.0 / 16777216.0) : stat == CONTRIB_PEAK ? (double)__uint_as_float(peak[i]) : (double)pixels[i];
-        in = v < below;
+        const AttrSource src{nullptr, nullptr, nullptr, nullptr, nullptr, weight, peak, pixels, 0.0, 0.0, 0.0};
+        in = attr_value(ATTR_CONTRIB_WEIGHT + stat, src, i) < below;   // (the one statement of the value: k_attr.h)
     }
     const uint64_t m = __ballot(in);
     if ((threadIdx.x & 63u) == 0u) {

@@ -93,6 +93,11 @@ export interface SelectionBounds { count: number; min: Float32Array; max: Float3
 export type SelectMode = "centre" | "hit";
 export type SelectOp = "replace" | "add" | "subtract" | "intersect";
 export type ContribStat = "weight" | "peak" | "pixels";
+export type SplatAttribute = "x" | "y" | "z" | "distance" | "red" | "green" | "blue" | "opacity" | "scale_x" | "scale_y" | "scale_z" | "scale_min" | "scale_max" |
+    "contrib_weight" | "contrib_peak" | "contrib_pixels";
+export interface SplatScope { origin?: ArrayLike<number> | { x: number; y: number; z: number } | null; selected?: boolean; visible?: boolean }
+export interface SplatStats { count: number; nan: number; min: number; max: number }
+export interface SplatHistogram { counts: Uint32Array; below: number; above: number; nan: number; edges: Float64Array }
 export interface Contribution { weight: BigUint64Array; peak: Float32Array; pixels: Uint32Array; frames: number }
 /** A screen region: the pixels [x0, x1) x [y0, y1), optionally one byte per pixel of the rectangle (non-zero = inside; rows
  *  `stride` >= x1 - x0 apart, default x1 - x0; row 0 is y0): a rasterised lasso or brush. */
@@ -350,6 +355,19 @@ export class HIPRenderer {
     accumulateContribution(): void;
     readContribution(): Contribution;
     selectContribution(options?: { stat?: ContribStat; below?: number; op?: SelectOp }): number;
+    /** Splat data: how an attribute of the splats themselves is distributed over the device scene, and a range of it as a picker.
+     *  splatStats: the splats in scope (selected: only the selection; visible: only what is not hidden), how many have a NaN value,
+     *  and min / max of the others (Infinity, -Infinity when there are none).  splatHistogram: the values in [lo, hi) in `bins` bins
+     *  (1 .. 4096, default 64) by the edge rule of HIPRenderer.attrEdges -- a value's bin is the last one whose edge is <= it -- plus
+     *  the splats in scope below lo, at or above hi, and NaN.  selectAttribute picks lo <= value < hi over every splat (defaults
+     *  -Infinity, Infinity; never a NaN) and folds them into the selection with `op`, returning the number of selected splats:
+     *  selectAttribute(attr, { lo: edges[a], hi: edges[b] }) selects exactly the splats an unscoped histogram counts in bins a .. b - 1.
+     *  origin is what "distance" is measured from.  Scale attributes need a scene with rotations / scales, contribution attributes a
+     *  tour; unknown names throw. */
+    splatStats(attr: SplatAttribute, options?: SplatScope): SplatStats;
+    splatHistogram(attr: SplatAttribute, options: SplatScope & { lo: number; hi: number; bins?: number }): SplatHistogram;
+    selectAttribute(attr: SplatAttribute, options?: { lo?: number; hi?: number; origin?: SplatScope["origin"]; op?: SelectOp }): number;
+    static attrEdges(lo: number, hi: number, bins: number): Float64Array;
     dispose(): void;
     /** RGBA8, row 0 = top, round(clamp(x,0,1)*255), premultiplied alpha */
     /** RGBA8, row 0 = top; pass an array of width*height*4 elements to have it filled and returned (no allocation per frame). */

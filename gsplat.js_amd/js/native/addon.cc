@@ -1331,6 +1331,99 @@ napi_value SelectContrib(napi_env env, napi_callback_info info)
     return rc ? throw_gsr(env, c, rc, "gsr_select_contrib") : count_value(env, count);
 }
 
+// ---- splat data (gsr_attr_stats / gsr_attr_histogram / gsr_select_attr) ----
+// the optional origin (Float64Array(3) or null) of the calls below; false: a type error is pending
+bool get_origin(napi_env env, napi_value v, const double** origin)
+{
+    void* data = nullptr;
+    size_t len = 0;
+    if (!get_typed(env, v, napi_float64_array, &data, &len, true)) return false;
+    if (data && len < 3) { napi_throw_range_error(env, nullptr, "origin must hold 3 values"); return false; }
+    *origin = (const double*)data;
+    return true;
+}
+
+napi_value set_u32(napi_env env, napi_value o, const char* name, uint32_t v)
+{
+    napi_value x;
+    NAPI_OK_OR_NULL(env, napi_create_uint32(env, v, &x));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, o, name, x));
+    return o;
+}
+
+napi_value set_f64(napi_env env, napi_value o, const char* name, double v)
+{
+    napi_value x;
+    NAPI_OK_OR_NULL(env, napi_create_double(env, v, &x));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, o, name, x));
+    return o;
+}
+
+// attrStats(handle, attr, origin | null, scope) -> { count, nan, min, max }
+napi_value AttrStats(napi_env env, napi_callback_info info)
+{
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    int32_t attr;
+    uint32_t scope;
+    const double* origin = nullptr;
+    if (!c || !get_i32(env, argv[1], &attr) || !get_origin(env, argv[2], &origin) || napi_get_value_uint32(env, argv[3], &scope) != napi_ok) return nullptr;
+    uint32_t count = 0, nan = 0;
+    double mn = 0, mx = 0;
+    const int rc = gsr_attr_stats(c, attr, origin, scope, &count, &nan, &mn, &mx);
+    if (rc) return throw_gsr(env, c, rc, "gsr_attr_stats");
+    napi_value out;
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    if (!set_u32(env, out, "count", count) || !set_u32(env, out, "nan", nan) || !set_f64(env, out, "min", mn) || !set_f64(env, out, "max", mx)) return nullptr;
+    return out;
+}
+
+// attrHistogram(handle, attr, origin | null, scope, lo, hi, bins) -> { counts: Uint32Array(bins), below, above, nan }
+napi_value AttrHistogram(napi_env env, napi_callback_info info)
+{
+    napi_value argv[7];
+    if (!get_args(env, info, 7, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    int32_t attr;
+    uint32_t scope, bins;
+    double lo, hi;
+    const double* origin = nullptr;
+    if (!c || !get_i32(env, argv[1], &attr) || !get_origin(env, argv[2], &origin) || napi_get_value_uint32(env, argv[3], &scope) != napi_ok) return nullptr;
+    if (!get_f64(env, argv[4], &lo) || !get_f64(env, argv[5], &hi) || napi_get_value_uint32(env, argv[6], &bins) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "attrHistogram: lo, hi and bins must be numbers");
+        return nullptr;
+    }
+    if (bins < 1 || bins > 4096) { napi_throw_range_error(env, nullptr, "attrHistogram: bins must be in 1 .. 4096"); return nullptr; }
+    void* counts = nullptr;
+    napi_value ab, arr, out;
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, (size_t)bins * 4, &counts, &ab));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_uint32_array, bins, ab, 0, &arr));
+    uint32_t outside[3] = {0, 0, 0};
+    const int rc = gsr_attr_histogram(c, attr, origin, scope, lo, hi, bins, (uint32_t*)counts, outside);
+    if (rc) return throw_gsr(env, c, rc, "gsr_attr_histogram");
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "counts", arr));
+    if (!set_u32(env, out, "below", outside[0]) || !set_u32(env, out, "above", outside[1]) || !set_u32(env, out, "nan", outside[2])) return nullptr;
+    return out;
+}
+
+// selectAttr(handle, attr, origin | null, lo, hi, op) -> selected
+napi_value SelectAttr(napi_env env, napi_callback_info info)
+{
+    napi_value argv[6];
+    if (!get_args(env, info, 6, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    int32_t attr, op;
+    double lo, hi;
+    const double* origin = nullptr;
+    if (!c || !get_i32(env, argv[1], &attr) || !get_origin(env, argv[2], &origin) || !get_i32(env, argv[5], &op)) return nullptr;
+    if (!get_f64(env, argv[3], &lo) || !get_f64(env, argv[4], &hi)) { napi_throw_type_error(env, nullptr, "selectAttr: lo and hi must be numbers"); return nullptr; }
+    uint32_t count = 0;
+    const int rc = gsr_select_attr(c, attr, origin, lo, hi, op, &count);
+    return rc ? throw_gsr(env, c, rc, "gsr_select_attr") : count_value(env, count);
+}
+
 // ---- selection overlay (gsr_set_overlay / gsr_overlay_async / gsr_read_overlay* / gsr_delivery_set_overlay) ----
 // setOverlay(handle, on, r, g, b, mix): on = 0 switches the overlay off (the other arguments are not read)
 napi_value SetOverlay(napi_env env, napi_callback_info info)
@@ -1445,6 +1538,7 @@ napi_value Init(napi_env env, napi_value exports)
         {"appendArrays", AppendArrays},
         {"contribReset", Call0<gsr_contrib_reset>}, {"contribAccumulate", Call0<gsr_contrib_accumulate_async>}, {"readContrib", ReadContrib},
         {"selectContrib", SelectContrib},
+        {"attrStats", AttrStats}, {"attrHistogram", AttrHistogram}, {"selectAttr", SelectAttr},
         {"setOverlay", SetOverlay}, {"readOverlay", ReadOverlay}, {"readOverlayPixels", ReadOverlayPixels},
         {"deliverySetOverlay", DeliverySetOverlay}, {"setOutline", SetOutline},
     };

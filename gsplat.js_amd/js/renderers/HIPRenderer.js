@@ -509,6 +509,35 @@ class HIPRenderer {
             const below = o2.below === undefined ? 0 : Number(o2.below);
             return this._n.selectContrib(this._h, code(STATS, o2.stat, "weight", "stat"), below, code(OPS, o2.op, "replace", "op"));
         };
+        // ---- splat data (gsr_attr_stats / gsr_attr_histogram / gsr_select_attr): an attribute's distribution, a range of it as a picker ----
+        //   const { min, max } = renderer.splatStats("scale_max");
+        //   const h = renderer.splatHistogram("scale_max", { lo: min, hi: max * (1 + 1e-12), bins: 64 });   // h.counts, h.edges
+        //   renderer.selectAttribute("scale_max", { lo: h.edges[48] });        // the huge ones: exactly the splats of bins 48 .. 63
+        // attr: x, y, z, distance (from `origin`), red, green, blue, opacity (bytes, 0 .. 255), scale_x / _y / _z / _min / _max,
+        // contrib_weight / _peak / _pixels (selectContribution's values).  selected / visible restrict the statistics to the selection /
+        // to what is not hidden; selectAttribute ranges over every splat and picks lo <= value < hi (never a NaN).  The histogram's
+        // edges are HIPRenderer.attrEdges(lo, hi, bins): selectAttribute(attr, { lo: edges[a], hi: edges[b] }) selects exactly the
+        // splats an unscoped histogram counts in bins a .. b - 1.
+        const ATTRS = { x: 0, y: 1, z: 2, distance: 3, red: 4, green: 5, blue: 6, opacity: 7, scale_x: 8, scale_y: 9, scale_z: 10,
+                        scale_min: 11, scale_max: 12, contrib_weight: 13, contrib_peak: 14, contrib_pixels: 15 };
+        const originOf = (o) => (o.origin === undefined || o.origin === null ? null : vec(o.origin, 3));
+        const scopeOf = (o) => (o.selected ? 1 : 0) | (o.visible ? 2 : 0);
+        this.splatStats = (attr, options) => {
+            const o2 = options || {};
+            return this._n.attrStats(this._h, code(ATTRS, attr, undefined, "attr"), originOf(o2), scopeOf(o2));
+        };
+        this.splatHistogram = (attr, options) => {
+            const o2 = options || {}, lo = Number(o2.lo), hi = Number(o2.hi), bins = o2.bins === undefined ? 64 : o2.bins;
+            const a = code(ATTRS, attr, undefined, "attr");
+            if (!Number.isInteger(bins) || bins < 1 || bins > 4096) throw new Error("bins must be an integer in 1 .. 4096");
+            const h = this._n.attrHistogram(this._h, a, originOf(o2), scopeOf(o2), lo, hi, bins);
+            return { counts: h.counts, below: h.below, above: h.above, nan: h.nan, edges: HIPRenderer.attrEdges(lo, hi, bins) };
+        };
+        this.selectAttribute = (attr, options) => {
+            const o2 = options || {};
+            const lo = o2.lo === undefined ? -Infinity : Number(o2.lo), hi = o2.hi === undefined ? Infinity : Number(o2.hi);
+            return this._n.selectAttr(this._h, code(ATTRS, attr, undefined, "attr"), originOf(o2), lo, hi, code(OPS, o2.op, "replace", "op"));
+        };
         // ---- selection overlay (gsr_set_overlay / gsr_read_overlay*): the last frame with the selected splats tinted ----
         //   renderer.setSelectionOverlay({ tint: [1, 0.5, 0], mix: 0.5 }); renderer.render(scene, cam);
         //   const { rgba, cover } = renderer.readOverlay();   // or readPixels({ overlay: true }), or openDelivery(n, { overlay: true })
@@ -546,6 +575,13 @@ HIPRenderer.createGroupId = () => loadNative().commUniqueId();
 HIPRenderer.bandEdges = (width, world) => {
     const nbx = Math.ceil(width / 32), per = Math.ceil(nbx / world), e = [];
     for (let q = 0; q < world; q++) e.push([Math.min(q * per * 32, width), Math.min((q + 1) * per * 32, width)]);
+    return e;
+};
+// the bins + 1 edges of splatHistogram, by gsr_attr_histogram's f64 rule: w = (hi - lo) / bins, edge(k) = min(lo + k * w, hi), edge(bins) = hi
+HIPRenderer.attrEdges = (lo, hi, bins) => {
+    const e = new Float64Array(bins + 1), w = (hi - lo) / bins;
+    for (let k = 0; k < bins; k++) e[k] = Math.min(lo + k * w, hi);
+    e[bins] = hi;
     return e;
 };
 

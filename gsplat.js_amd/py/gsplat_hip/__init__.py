@@ -93,6 +93,20 @@ OUTLINE_SIDES = {"outer": 0, "inner": 1}                                   # GSR
 SELECT_MODES = {"centre": 0, "hit": 1}                                     # GSR_SELECT_*
 SELECT_OPS = {"replace": 0, "add": 1, "subtract": 2, "intersect": 3}       # GSR_SELOP_*
 CONTRIB_STATS = {"weight": 0, "peak": 1, "pixels": 2}                      # GSR_CONTRIB_*
+ATTRS = {"x": 0, "y": 1, "z": 2, "distance": 3, "red": 4, "green": 5, "blue": 6, "opacity": 7, "scale_x": 8, "scale_y": 9, "scale_z": 10,
+         "scale_min": 11, "scale_max": 12, "contrib_weight": 13, "contrib_peak": 14, "contrib_pixels": 15}   # GSR_ATTR_*
+SCOPES = {"selected": 1, "visible": 2}                                     # GSR_SCOPE_*
+ATTR_MAX_BINS = 4096
+
+
+def attr_edges(lo, hi, bins):
+    """The bins + 1 edges of gsr_attr_histogram, by the header's f64 rule: w = (hi - lo) / bins, edge(k) = min(lo + k * w, hi) and
+    edge(bins) = hi.  select_attr(attr, edges[a], edges[b]) selects exactly sum(counts[a:b]) splats."""
+    lo, hi = np.float64(lo), np.float64(hi)
+    w = (hi - lo) / np.float64(bins)
+    e = np.minimum(lo + np.arange(bins + 1, dtype=np.float64) * w, hi)
+    e[bins] = hi
+    return e
 
 
 def edge_arrays(edges):
@@ -133,6 +147,7 @@ EXPORTS = [
     "gsr_selection_bounds", "gsr_scene_translate_selected", "gsr_scene_rotate_selected", "gsr_scene_scale_selected", "gsr_scene_set_rgba_selected",
     "gsr_scene_reserve", "gsr_scene_capacity", "gsr_scene_duplicate_selected", "gsr_scene_append_selected", "gsr_scene_append_arrays",
     "gsr_contrib_reset", "gsr_contrib_accumulate_async", "gsr_read_contrib", "gsr_select_contrib",
+    "gsr_attr_stats", "gsr_attr_histogram", "gsr_select_attr",
     "gsr_set_overlay", "gsr_overlay_async", "gsr_read_overlay", "gsr_read_overlay_rgba8", "gsr_overlay_device_ptr", "gsr_delivery_set_overlay",
     "gsr_set_overlay_outline",
 ]
@@ -292,6 +307,10 @@ def load_library(path=None):
     L.gsr_contrib_accumulate_async.argtypes = [vp]
     L.gsr_read_contrib.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, u32p]
     L.gsr_select_contrib.argtypes = [vp, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, u32p]
+    f64p = ctypes.POINTER(ctypes.c_double)
+    L.gsr_attr_stats.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_uint32, u32p, u32p, f64p, f64p]
+    L.gsr_attr_histogram.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_uint32, vp, vp]
+    L.gsr_select_attr.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_double, ctypes.c_double, ctypes.c_int32, u32p]
     L.gsr_set_overlay.argtypes = [vp, ctypes.POINTER(GsrOverlayOptions)]
     L.gsr_set_overlay_outline.argtypes = [vp, ctypes.POINTER(GsrOutlineOptions)]
     L.gsr_overlay_async.argtypes = [vp]
@@ -1076,6 +1095,47 @@ class HIPRenderer:
         count = ctypes.c_uint32(0)
         self._check(self._L.gsr_select_contrib(self._ctx, self._select_code(CONTRIB_STATS, stat, "stat"), float(below),
                                                self._select_code(SELECT_OPS, op, "op"), ctypes.byref(count)))
+        return count.value
+
+    # -- splat data (gsr_attr_stats / gsr_attr_histogram / gsr_select_attr): an attribute's distribution, and a range of it as a picker --
+    @staticmethod
+    def _origin(origin):
+        return None if origin is None else np.ascontiguousarray(origin, dtype=np.float64).reshape(3)
+
+    @staticmethod
+    def _scope(selected, visible):
+        return (SCOPES["selected"] if selected else 0) | (SCOPES["visible"] if visible else 0)
+
+    def attr_stats(self, attr, origin=None, selected=False, visible=False):
+        """(count, nan, min, max) of an attribute (ATTRS: "opacity", "scale_max", "distance", ...) over the splats in scope --
+        selected=True: only the selection; visible=True: only what is not hidden.  nan: values that are NaN; min / max over the
+        others (+inf, -inf when there are none).  origin (x, y, z): what "distance" is measured from."""
+        o = self._origin(origin)
+        count, nan, mn, mx = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_double(0), ctypes.c_double(0)
+        self._check(self._L.gsr_attr_stats(self._ctx, self._select_code(ATTRS, attr, "attr"), None if o is None else o.ctypes.data,
+                                           self._scope(selected, visible), ctypes.byref(count), ctypes.byref(nan), ctypes.byref(mn), ctypes.byref(mx)))
+        return count.value, nan.value, mn.value, mx.value
+
+    def attr_histogram(self, attr, lo, hi, bins, origin=None, selected=False, visible=False):
+        """(counts uint32[bins], (below, above, nan), edges float64[bins + 1]): the attribute's values in [lo, hi) binned by the
+        header's edge rule (attr_edges), and the splats in scope below lo, at or above hi, and NaN.
+        select_attr(attr, edges[a], edges[b]) selects exactly counts[a:b].sum() splats of an unscoped histogram."""
+        bins = int(bins)
+        if not 1 <= bins <= ATTR_MAX_BINS:
+            raise ValueError("bins must be in 1 .. %d" % ATTR_MAX_BINS)
+        o = self._origin(origin)
+        counts, outside = np.zeros(bins, np.uint32), np.zeros(3, np.uint32)
+        self._check(self._L.gsr_attr_histogram(self._ctx, self._select_code(ATTRS, attr, "attr"), None if o is None else o.ctypes.data,
+                                               self._scope(selected, visible), float(lo), float(hi), bins, counts.ctypes.data, outside.ctypes.data))
+        return counts, (int(outside[0]), int(outside[1]), int(outside[2])), attr_edges(lo, hi, bins)
+
+    def select_attr(self, attr, lo=-np.inf, hi=np.inf, origin=None, op="replace"):
+        """Pick the splats with lo <= value < hi (all splats, hidden ones included; a NaN value is never picked) and fold them into
+        the selection; returns the selected count."""
+        o = self._origin(origin)
+        count = ctypes.c_uint32(0)
+        self._check(self._L.gsr_select_attr(self._ctx, self._select_code(ATTRS, attr, "attr"), None if o is None else o.ctypes.data,
+                                            float(lo), float(hi), self._select_code(SELECT_OPS, op, "op"), ctypes.byref(count)))
         return count.value
 
     # -- selection overlay (gsr_set_overlay / gsr_overlay_async / gsr_read_overlay*): the selected splats tinted --

@@ -750,6 +750,77 @@ int gsr_contrib_accumulate_async(gsr_ctx *ctx);
 int gsr_read_contrib(gsr_ctx *ctx, uint64_t *weight, float *peak, uint32_t *pixels, uint32_t n, uint32_t *frames);
 int gsr_select_contrib(gsr_ctx *ctx, int32_t stat, double below, int32_t op, uint32_t *selected);
 
+/* ---- splat data ---- attribute statistics, histograms and range selection on the device
+ * No interface of the reference stands behind this section either.  Every picker above asks where a splat is on the screen, in a
+ * box, or how much it showed; these ask about the splats themselves -- how opacity, size, colour and distance from a point are
+ * distributed in a scene, and which splats lie in a range of one of them (the near-transparent, the huge, everything farther than
+ * r from here) -- with no gsr_read_scene of the whole scene and no host loop.  They also show where the mass of the contribution
+ * accumulators lies before gsr_select_contrib is handed a threshold.
+ * The value of attribute a of splat i is a double ("Splat data"; stated once on the device, in f64, in the
+ * written order, uncontracted):
+ *   GSR_ATTR_X, _Y, _Z               (double)position component
+ *   GSR_ATTR_DISTANCE                dx = (double)x - origin[0], dy and dz likewise; sqrt((dx*dx + dy*dy) + dz*dz), the square root
+ *                                    correctly rounded
+ *   GSR_ATTR_RED, _GREEN, _BLUE, _OPACITY   that byte of the colour word, 0 .. 255, numbered as gsr_scene_set_rgba_selected numbers
+ *                                    them: r, g, b the low three bytes, opacity the top byte
+ *   GSR_ATTR_SCALE_X, _Y, _Z         (double)scale component
+ *   GSR_ATTR_SCALE_MIN, _MAX         NaN if any scale component is NaN; otherwise the smallest / largest of the three
+ *   GSR_ATTR_CONTRIB_WEIGHT, _PEAK, _PIXELS   exactly the value gsr_select_contrib compares: (double)weight * 2^-24, (double)peak,
+ *                                    (double)pixels (one function on the device serves both calls)
+ * `origin` (3 doubles) is read for GSR_ATTR_DISTANCE only and ignored otherwise.
+ * Scope: GSR_SCOPE_SELECTED counts only splats in the selection, GSR_SCOPE_VISIBLE only splats not in the hidden set; the flags
+ *   combine, 0 is every splat.  A scene never selected in has the empty selection, one that never hid has nothing hidden.  A run of
+ *   64 splats with none in scope costs its set words and no read of the scene.
+ * gsr_attr_stats: count = the splats in scope; nan = those whose value is NaN; min / max over the others, infinities included
+ *   (compared as values: -0.0 and 0.0 are equal, and which of them a bound holds is not defined).  With no non-NaN value min is +inf
+ *   and max is -inf.  Any out pointer may be NULL.  An empty scene returns zeros and that empty box.
+ * gsr_attr_histogram needs 1 <= bins <= 4096, lo < hi, both finite, hi - lo finite.  The edge rule, in f64:
+ *     w = (hi - lo) / (double)bins;   edge(k) = k == bins ? hi : min(lo + (double)k * w, hi)
+ *   The edges are nondecreasing and edge(0) == lo.  A value v is in range iff lo <= v && v < hi, and its bin is the largest b < bins
+ *   with edge(b) <= v -- decided by comparisons against the edges, not by floor((v - lo) / w), which disagrees at the edges.
+ *   counts[bins] receives the bins; outside[3] the splats in scope with v < lo, with v >= hi, and with a NaN value, so
+ *   sum(counts) + sum(outside) == count of gsr_attr_stats.  Either pointer may be NULL.
+ * gsr_select_attr picks P = { i in [0, n) : lo <= v_i && v_i < hi } over ALL splats of the scene, hidden ones included; a NaN value
+ *   is never picked.  lo and hi may be infinite (lo = -inf: "below hi"); lo == hi picks nothing.  P is folded into the selection
+ *   with `op` (GSR_SELOP_*) exactly as the selection calls fold theirs, and `selected` means what it means everywhere else.
+ * The consistency guarantee: for 0 <= a < b <= bins, gsr_select_attr(attr, origin, edge(a), edge(b), GSR_SELOP_REPLACE) selects
+ *   exactly sum(counts[a .. b-1]) splats of a scope-0 gsr_attr_histogram over the same [lo, hi) and bins: what the histogram
+ *   shows is what the range selects.  A host computes edge(k) with the f64 formula above.
+ * All three are blocking and ordered like gsr_select_contrib: they wait for every member's stream of a shared scene first.  They
+ *   read the scene and write none of it: no frame state changes.  Counts are integers and min / max commute, so every result is
+ *   exact and independent of the order of arrival.
+ * Refusals (GSR_ERR_ARG with a message, nothing touched, the selection and its count included): an unknown attribute code, scope
+ *   flag or op; for GSR_ATTR_DISTANCE a NULL origin or a non-finite origin component; the scale attributes on a scene without
+ *   rotations / scales (as gsr_scene_scale_selected refuses); the contribution attributes while nothing was ever reset or
+ *   accumulated or frames == 0 (as gsr_select_contrib refuses); bins, lo or hi outside what the histogram needs; a NaN bound or
+ *   lo > hi for gsr_select_attr.
+ * The device words the reductions need (a few tens of KB) belong to the context and are allocated by the first call; a context
+ * that never calls any of this allocates nothing and launches nothing. */
+#define GSR_ATTR_X 0
+#define GSR_ATTR_Y 1
+#define GSR_ATTR_Z 2
+#define GSR_ATTR_DISTANCE 3         /* from `origin` */
+#define GSR_ATTR_RED 4
+#define GSR_ATTR_GREEN 5
+#define GSR_ATTR_BLUE 6
+#define GSR_ATTR_OPACITY 7
+#define GSR_ATTR_SCALE_X 8
+#define GSR_ATTR_SCALE_Y 9
+#define GSR_ATTR_SCALE_Z 10
+#define GSR_ATTR_SCALE_MIN 11
+#define GSR_ATTR_SCALE_MAX 12
+#define GSR_ATTR_CONTRIB_WEIGHT 13
+#define GSR_ATTR_CONTRIB_PEAK 14
+#define GSR_ATTR_CONTRIB_PIXELS 15
+#define GSR_SCOPE_SELECTED 1u   /* only splats in the selection */
+#define GSR_SCOPE_VISIBLE  2u   /* only splats not in the hidden set */   /* 0: every splat; flags combine */
+int gsr_attr_stats(gsr_ctx *ctx, int32_t attr, const double *origin, uint32_t scope,
+                   uint32_t *count, uint32_t *nan, double *min, double *max);
+int gsr_attr_histogram(gsr_ctx *ctx, int32_t attr, const double *origin, uint32_t scope,
+                       double lo, double hi, uint32_t bins, uint32_t *counts, uint32_t *outside);
+int gsr_select_attr(gsr_ctx *ctx, int32_t attr, const double *origin, double lo, double hi,
+                    int32_t op, uint32_t *selected);
+
 /* ---- selection overlay ---- the selected splats tinted, in read-backs and in delivered frames
  * No interface of the reference stands behind this section either.  gsr_read_selection returns bits; this shows them: a second
  * image beside the frame in which the selected splats carry a tint, and per pixel how much of it they are.

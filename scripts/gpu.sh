@@ -5,6 +5,9 @@
 #   ab ARGS...                scripts/ab_bench.py ARGS (variants "base@ENV=v,ENV2=v" or lib_exp names) -> gpurun_out/ab.log
 #   py SCRIPT [ARGS]          python SCRIPT ARGS
 #   trace NAME [BENCH_ARGS]   rocprofv3 --kernel-trace --stats of `bench.py --timed-only BENCH_ARGS` -> gpurun_out/trace_NAME/
+#   pytrace DIR SCRIPT [ARGS]   the trace task's profiler run around `python SCRIPT ARGS` (SCRIPT relative to the repository) -> DIR/ (pass a
+#                             directory under the runner's output directory), the script's own output in DIR/script.log
+#                             (scripts/bench_attr.py prints its plan there)
 #   copytrace DIR [ARGS]   the trace task's profiler run with --memory-copy-trace added, around `scripts/bench_delivery.py --timed-only ARGS`:
 #                             kernels AND copies on one timeline (the delivery ring's device-to-host copies under the next frames'
 #                             kernels; no counters in this run) -> DIR/ (pass a directory under the runner's output directory);
@@ -29,6 +32,9 @@ run_task() {
     trace) local name=$1; shift; rm -rf gpurun_out/trace_$name
            (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/trace_$name -- \
               python3 $R/bench.py --timed-only --no-cpu-baseline "$@" > $R/gpurun_out/trace_$name.log 2>&1) ;;
+    pytrace) local dir=$R/$1 script=$2; shift 2; rm -rf "$dir"; mkdir -p "$dir"
+           (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$dir" -- \
+              python3 $R/$script "$@" > "$dir/script.log" 2>&1) ;;
     copytrace) local dir=$R/$1; shift; rm -rf "$dir"; mkdir -p "$dir"
            (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d "$dir" -- \
               python3 $R/scripts/bench_delivery.py --timed-only "$@" > "$dir/bench_delivery.log" 2>&1) ;;

@@ -3,7 +3,7 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--share-scene]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--share-scene]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
@@ -36,6 +36,10 @@
 // --edit-selected FRACTION selects that fraction of the splats (scattered over the indices) through gsr_selection_set on every device
 // copy and adds a leg with a gsr_scene_rotate_selected by one degree about y, pivoted, behind every frame: only the selection turns.
 // The report carries the leg's rate and `edit_ms`, the wall time a frame of that leg takes beyond a frame of the plain timed loop.
+// --histogram ATTR[:BINS] (x, y, z, distance, red, green, blue, opacity, scale_x .. scale_max, contrib_weight .. contrib_pixels; 256
+// bins unless given; the contribution attributes go beside --contrib) asks the scene about itself: gsr_attr_stats, a
+// gsr_attr_histogram over [min, max] and a gsr_select_attr of the middle half of the bins, [edge(bins / 4), edge(bins - bins / 4)).
+// The report carries the three blocking times (the best of five each) and the check sum(counts[a .. b-1]) == selected.
 // --duplicate FRACTION (last of all: it grows the scene) selects that fraction of the splats through gsr_selection_set and calls
 // gsr_scene_duplicate_selected twice -- the second call copies the first one's copies, the same count -- and reports the wall time
 // of either (`duplicate_ms`, `duplicate_again_ms`), the count and the capacity.  With --reserve, gsr_scene_reserve makes room for
@@ -172,6 +176,8 @@ int main(int argc, char** argv)
     double edit_fraction = -1.0;   // < 0: off
     double duplicate_fraction = -1.0;   // < 0: off
     bool reserve = false;
+    std::string histogram_attr;         // empty: off
+    uint32_t histogram_bins = 256;
     int32_t pick_xy[2] = {0, 0};
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -194,13 +200,19 @@ int main(int argc, char** argv)
         else if (a == "--hide" && i + 1 < argc) { hide_fraction = std::atof(argv[++i]); if (!(hide_fraction >= 0.0 && hide_fraction <= 1.0)) { std::fprintf(stderr, "--hide FRACTION must be in [0, 1]\n"); return 2; } }
         else if (a == "--hide-edits") hide_edits = true;
         else if (a == "--edit-selected" && i + 1 < argc) { edit_fraction = std::atof(argv[++i]); if (!(edit_fraction >= 0.0 && edit_fraction <= 1.0)) { std::fprintf(stderr, "--edit-selected FRACTION must be in [0, 1]\n"); return 2; } }
+        else if (a == "--histogram" && i + 1 < argc) {
+            histogram_attr = argv[++i];
+            const size_t colon = histogram_attr.find(':');
+            if (colon != std::string::npos) { histogram_bins = (uint32_t)std::atoi(histogram_attr.c_str() + colon + 1); histogram_attr.resize(colon); }
+            if (histogram_bins < 1 || histogram_bins > 4096) { std::fprintf(stderr, "--histogram ATTR[:BINS]: BINS must be in 1 .. 4096\n"); return 2; }
+        }
         else if (a == "--duplicate" && i + 1 < argc) { duplicate_fraction = std::atof(argv[++i]); if (!(duplicate_fraction >= 0.0 && duplicate_fraction <= 1.0)) { std::fprintf(stderr, "--duplicate FRACTION must be in [0, 1]\n"); return 2; } }
         else if (a == "--reserve") reserve = true;
         else if (a == "--scene-arrays") scene_arrays = true;
         else if (a == "--scene-edit") scene_edit = next();
         else if (a == "--share-scene") share_scene = true;
         else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--share-scene]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--share-scene]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
@@ -558,6 +570,39 @@ int main(int argc, char** argv)
         erase_hidden_ms = ms_since(t);
         CHECK(gsr_read_hidden(ctx[0], nullptr, 0, &edits_hidden));
     }
+    // --histogram: the scene asked about itself -- statistics, a histogram over [min, max], the middle half of its bins selected
+    int32_t hist_attr = -1;
+    uint32_t hist_count = 0, hist_nan = 0, hist_outside[3] = {0, 0, 0}, hist_selected = 0, hist_a = 0, hist_b = 0;
+    unsigned long long hist_sum = 0, hist_peak = 0;
+    double hist_min = 0, hist_max = 0, hist_lo = 0, hist_hi = 1, hist_ms[3] = {0, 0, 0};
+    if (!histogram_attr.empty()) {
+        static const char* const ATTR_NAMES[16] = {"x", "y", "z", "distance", "red", "green", "blue", "opacity", "scale_x", "scale_y", "scale_z",
+                                                   "scale_min", "scale_max", "contrib_weight", "contrib_peak", "contrib_pixels"};   // GSR_ATTR_*
+        for (int k = 0; k < 16; k++) if (histogram_attr == ATTR_NAMES[k]) hist_attr = k;
+        if (hist_attr < 0) { std::fprintf(stderr, "--histogram: unknown attribute %s\n", histogram_attr.c_str()); return 2; }
+        const double origin[3] = {0.0, 0.0, 0.0};
+        const uint32_t bins = histogram_bins;
+        std::vector<uint32_t> counts(bins);
+        auto best_of = [&](auto call, double& ms) -> int {
+            ms = 1e30;
+            for (int t = 0; t < 5; t++) {
+                const auto t0 = std::chrono::steady_clock::now();
+                if (int rc = call()) return rc;
+                ms = std::min(ms, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3);
+            }
+            return 0;
+        };
+        ctx0 = ctx[0];
+        CHECK(best_of([&] { return gsr_attr_stats(ctx[0], hist_attr, origin, 0, &hist_count, &hist_nan, &hist_min, &hist_max); }, hist_ms[0]));
+        if (std::isfinite(hist_min) && std::isfinite(hist_max)) { hist_lo = hist_min; hist_hi = std::nextafter(hist_max, INFINITY); }   // the maximum is in range
+        CHECK(best_of([&] { return gsr_attr_histogram(ctx[0], hist_attr, origin, 0, hist_lo, hist_hi, bins, counts.data(), hist_outside); }, hist_ms[1]));
+        // the edges, by the header's f64 rule
+        const double w = (hist_hi - hist_lo) / (double)bins;
+        auto edge = [&](uint32_t k) { return k == bins ? hist_hi : std::min(hist_lo + (double)k * w, hist_hi); };
+        hist_a = bins / 4; hist_b = bins - bins / 4;
+        CHECK(best_of([&] { return gsr_select_attr(ctx[0], hist_attr, origin, edge(hist_a), edge(hist_b), GSR_SELOP_REPLACE, &hist_selected); }, hist_ms[2]));
+        for (uint32_t k = 0; k < bins; k++) { hist_peak = std::max<unsigned long long>(hist_peak, counts[k]); if (k >= hist_a && k < hist_b) hist_sum += counts[k]; }
+    }
     // --duplicate (last of all: it grows the scene): the selection duplicated on the device, twice
     double duplicate_ms = 0, duplicate_again_ms = 0, reserve_ms = 0;
     uint32_t dup_selected = 0, dup_first = 0, dup_count = 0, dup_capacity = 0, dup_n = 0;
@@ -629,6 +674,17 @@ int main(int argc, char** argv)
     if (edit_fraction >= 0.0)
         std::printf(", \"edit_selected_fraction\": %g, \"edit_selected\": %u, \"frames_per_sec_edit_selected\": %.1f, \"edit_ms\": %.4f", edit_fraction,
                     edit_selected, frames / edit_selected_sec, (edit_selected_sec - sec) / frames * 1e3);
+    auto json_num = [](double v) -> std::string {   // (an empty box is (+inf, -inf): not JSON numbers)
+        char buf[40];
+        std::snprintf(buf, sizeof buf, "%.17g", v);
+        return std::isfinite(v) ? std::string(buf) : std::string("null");
+    };
+    if (hist_attr >= 0)
+        std::printf(", \"histogram\": {\"attr\": \"%s\", \"bins\": %u, \"count\": %u, \"nan\": %u, \"min\": %s, \"max\": %s, \"lo\": %.17g, \"hi\": %.17g, "
+                    "\"below\": %u, \"above\": %u, \"nan_in_scope\": %u, \"largest_bin\": %llu, \"attr_stats_ms\": %.4f, \"attr_histogram_ms\": %.4f, "
+                    "\"select_attr_ms\": %.4f, \"range\": [%u, %u], \"sum_counts\": %llu, \"selected\": %u, \"histogram_equals_selection\": %s}",
+                    histogram_attr.c_str(), histogram_bins, hist_count, hist_nan, json_num(hist_min).c_str(), json_num(hist_max).c_str(), hist_lo, hist_hi, hist_outside[0], hist_outside[1], hist_outside[2],
+                    hist_peak, hist_ms[0], hist_ms[1], hist_ms[2], hist_a, hist_b, hist_sum, hist_selected, hist_sum == hist_selected ? "true" : "false");
     if (duplicate_fraction >= 0.0)
         std::printf(", \"duplicate_fraction\": %g, \"duplicate_first\": %u, \"duplicate_count\": %u, \"duplicate_reserved\": %s, \"reserve_ms\": %.4f, "
                     "\"duplicate_ms\": %.4f, \"duplicate_again_ms\": %.4f, \"count_after\": %u, \"capacity_after\": %u",
