@@ -4,7 +4,17 @@ frame, bit for bit, with the frame of a context created a moment ago from the St
 
 Pure Python and numpy: building and folding a trace needs no GPU (tests/test_history_trace.py); only `apply` and `build`
 touch a renderer.  An operation is a tuple (kind, *arguments); a trace is a list of Step(op, check): after a checked step the
-test renders the State's pose on both contexts and compares, an unchecked step is followed directly by the next operation."""
+test renders the State's pose on both contexts and compares, an unchecked step is followed directly by the next operation.
+
+The editing layer -- selection, hidden set, edits of the selection, growth and erasure, overlay, contribution -- is part of the State
+as a RECIPE (State.edits): `materialise` evaluates it on the CPU with the specifications the feature suites already have
+(edit_reference, append_reference, hide_reference, select_reference, attr_reference over oracle.SceneState), and `build` uploads the
+result, so the fresh context has a capacity equal to its count, never ran an edit kernel and never grew.  KINDS, REFUSALS, tour() and
+the walks over KINDS keep their exact content (tests/test_history_trace.py pins a digest); the new operations are EDIT_KINDS and
+EDIT_REFUSALS, the new fixed trace editing_tour(), the new pairs EDIT_RISKY_PAIRS, and walk(..., kinds=KINDS + EDIT_KINDS).
+HIT-mode region selection stays out of the traces: its result is defined by the device's own index plane, so it has no pure fold;
+tests/test_gpu_select.py covers it.  gsr_select_contrib is folded at the two thresholds whose set needs no frame (below = +inf:
+every splat, below = 0: none); the accumulators themselves are compared through read_contrib()."""
 import os
 import random
 from collections import namedtuple
@@ -33,6 +43,12 @@ class State:
     hit_alpha: float = 0.5
     ring: tuple = None               # (format, full_range, depth format | None, depth step): the open delivery ring
     pose: int = 0                    # camera k of the 120-frame orbit at this size
+    # the editing layer, as a recipe (materialise evaluates it on the CPU)
+    edits: tuple = ()                # the ordered scene-changing operations since the scene was set: pickers, hides, edits of the selection,
+    #                                  growth, erasure -- and, once there is one, the whole-scene transforms behind it (("transform", name, values))
+    overlay: tuple = None            # (tint, mix, outline options (rgb, alpha, threshold, width, side) | None), None: off
+    ring_overlay: bool = False       # the open ring delivers the overlay in place of the frame
+    contrib: tuple = None            # the passes since the last reset, (pose, W, H, band, fade, len(edits) at the pass) each; None: never reset
 
 
 # Read-backs that must not disturb anything, and calls that are refused and must change nothing.
@@ -44,6 +60,20 @@ KINDS = ("camera", "same_pose", "burst", "sort_only", "readback", "scene", "resi
 # operations after which the last frame's lists, records and planes are still the context's: only these may go unchecked
 # (an unchecked step is followed directly by the next operation, which may be a read-back of that frame)
 KEEPS_FRAME = ("camera", "same_pose", "burst", "sort_only", "readback", "fade", "hit_alpha", "timing_interval", "deliver", "depth_async")
+
+# The editing layer's operations (KINDS itself stays: tour() and the seeded walks over it keep their exact content).
+SELECT_KINDS = ("select_box", "select_region", "set_selection", "invert_selection", "select_attr", "select_hidden", "select_contrib")
+EDIT_KINDS = SELECT_KINDS + ("hide", "set_hidden", "edit", "reserve", "duplicate", "append_arrays", "erase", "overlay", "ring_overlay",
+                             "contrib_reset", "contrib_pass")
+# refused calls of the editing layer (REFUSALS stays as it is, like KINDS): an edit and an erase on a raw scene, growth with SH rows,
+# rotate-selected with SH follow on, append_arrays whose positions differ from its data
+EDIT_REFUSALS = ("edit_raw", "erase_raw", "grow_with_sh", "rotate_selected_sh_follow", "append_positions_differ")
+# of the new kinds only the pickers, a contribution pass and the overlay's option calls keep the frame: edits, hides and growth invalidate it
+EDIT_KEEPS_FRAME = SELECT_KINDS + ("contrib_pass", "overlay")
+# operations that move splats or change which are listed while the indices stay: live accumulators then describe frames no State can
+# render again, so the traces reset the accumulators in front of them (walk() does it itself)
+MOVES_GEOMETRY = ("rotate", "translate", "scale", "edit")
+MAX_GROWN = 40000                     # no trace grows a scene beyond this
 
 # Ordered pairs of neighbours the tour must visit (tags as `tags` gives them), and why each is risky.
 RISKY_PAIRS = (
@@ -79,6 +109,48 @@ RISKY_PAIRS = (
     ("refused", "camera", "a call that failed must have changed nothing the next frame reads"),
 )
 
+# The same for the editing layer (editing_tour visits them).  Tags: "select" for every picker, "hide:on" for a hide that adds or
+# replaces, "hide:off" for show-all, "duplicate:fit" / "duplicate:grow" for a duplicate inside / beyond the capacity, "overlay:on" / ":off".
+EDIT_RISKY_PAIRS = (
+    ("hide:on", "same_pose", "the hidden mask arrives in FrameArgs: the graph captured without it must not be replayed"),
+    ("hide:on", "hide:off", "the null pointer returns while the buffers stay allocated, and the graph is dropped again"),
+    ("hide:on", "band:on", "a hidden splat is no survivor: the pack path of k_project_key reads the mask"),
+    ("band:on", "hide:on", "survivor slots and rectangles of the frame before belong to splats that are hidden now"),
+    ("hide:on", "overflow_sync", "the frame rendered again by the repair must hide what the first attempt hid"),
+    ("hide:on", "overflow_async", "dropped frames, regrown lists, and a mask that arrived between captures"),
+    ("hide:on", "sort_only", "gsr_sort does not look at the mask: the render frame behind it must"),
+    ("hide:on", "scene", "gsr_set_scene* leaves nothing hidden: the pointer is null again though the buffers were sized for the old scene"),
+    ("scene", "hide:on", "the first hide of a scene allocates the mask for this count"),
+    ("hide:on", "erase", "the compaction carries H to the new numbering"),
+    ("hide:on", "limit_box", "... and so does gsr_scene_limit_box, which drops the selection"),
+    ("duplicate:grow", "same_pose", "the arrays are new, generation moved: a replayed graph would read the freed ones"),
+    ("duplicate:fit", "same_pose", "nothing re-allocated, but n is a kernel argument of every node"),
+    ("reserve", "same_pose", "capacity above n: the rows behind n are stale and the arrays moved under a captured graph"),
+    ("duplicate", "burst", "three frames in flight over per-splat buffers sized a moment ago"),
+    ("duplicate", "band:on", "survivor buffers sized by the old count"),
+    ("duplicate", "resize", "a new bin grid and new per-splat buffers at once"),
+    ("duplicate", "erase", "the compaction reads n rows of arrays that hold capacity rows"),
+    ("erase", "duplicate", "the copies land on rows the compaction left stale"),
+    ("duplicate:grow", "sort_only", "alloc_sort runs only when n > sort.rows: past it and past a keys-per-block multiple"),
+    ("append_arrays", "limit_box", "the compaction of a scene whose tail was uploaded, not built"),
+    ("edit", "same_pose", "an edit changes no argument: the replayed graph must still read the edited rows"),
+    ("edit", "sort_only", "the sorted order of the frame before is marked edited"),
+    ("edit", "readback:pick", "a pick behind an edit needs the new frame"),
+    ("select", "limit_box", "a selection does not survive a limitBox"),
+    ("select", "scene", "nor a new scene"),
+    ("overlay:on", "resize", "the overlay's images follow the size"),
+    ("overlay:on", "hide:on", "the pass walks this frame's lists: a hidden selected splat tints nothing"),
+    ("overlay:on", "duplicate", "the selection mask grew with the capacity and holds exactly the copies"),
+    ("overlay:on", "band:on", "the pass and the outline are defined on the band's columns"),
+    ("ring_overlay", "deliver", "the ring converts the overlay image in place of the framebuffer"),
+    ("ring_overlay", "resize", "the ring survives the resize with its overlay flag; the images are new"),
+    ("ring_overlay", "overlay:off", "the switch is the ring's and stays when the options go: deliveries are refused until they return"),
+    ("erase", "band:on", "a band frame behind a compaction must not read a rectangle of the old numbering"),
+    ("contrib_pass", "duplicate", "the accumulators grow with zeros behind the old rows' values"),
+    ("contrib_pass", "erase", "a compaction drops the accumulators: never reset again"),
+    ("contrib_pass", "scene", "and so does a new scene"),
+) + tuple(("refused:" + w, "camera", "a refused call of the editing layer must have changed nothing the next frame reads") for w in EDIT_REFUSALS)
+
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # State arithmetic (pure)
@@ -103,28 +175,61 @@ def fold(state, op):
         return replace(state, pose=a[-1])
     if kind == "overflow_async":
         return replace(state, pose=a[-1])
-    if kind == "scene":
-        return replace(state, scene=a[0], transforms=(), sh=None)
+    if kind == "scene":    # (selection, hidden set and accumulators are the scene's: gone with it)
+        return replace(state, scene=a[0], transforms=(), sh=None, edits=(), contrib=None)
     if kind == "resize":
-        return replace(state, W=a[0], H=a[1], band=None)          # (gsr_resize drops the band)
+        return replace(state, W=a[0], H=a[1], band=None)          # (gsr_resize drops the band; ring and overlay follow the size)
     if kind == "band":
         return replace(state, band=None if a == (0, 0) else (a[0], min(a[1], state.W)))
     if kind == "sh":
         return replace(state, sh=a[0])
-    if kind == "limit_box":
-        return replace(state, transforms=state.transforms + (("limit_box", a[0]),), sh=None)   # (the compaction drops the SH state)
+    if kind == "limit_box":    # (the compaction drops the SH state, the selection and the accumulators, and carries the hidden set)
+        if state.edits:
+            return replace(state, edits=state.edits + (("transform", kind, a[0]),), sh=None, contrib=None)
+        return replace(state, transforms=state.transforms + (("limit_box", a[0]),), sh=None, contrib=None)
     if kind in ("rotate", "translate", "scale"):
+        if state.edits:        # (behind an edit the order matters: the transform joins the recipe)
+            return replace(state, edits=state.edits + (("transform", kind, a[0]),))
         return replace(state, transforms=state.transforms + ((kind, a[0]),))
     if kind == "fade":
         return replace(state, fade=(bool(a[0]), float(a[1])))
     if kind == "hit_alpha":
         return replace(state, hit_alpha=float(a[0]))
-    if kind == "ring_open":
-        return replace(state, ring=tuple(a))
+    if kind == "ring_open":    # (a newly opened ring delivers the frame)
+        return replace(state, ring=tuple(a), ring_overlay=False)
     if kind == "ring_close":
-        return replace(state, ring=None)
-    assert kind in KINDS, op
-    return state      # same_pose, sort_only, readback, depth_async, timing_interval, overflow_sync, deliver, refused
+        return replace(state, ring=None, ring_overlay=False)
+    # -- the editing layer
+    if kind == "select_region":    # a region picks from a frame: the op records the frame it was made under
+        return replace(state, edits=state.edits + ((kind,) + a + (frame_of(state),),))
+    if kind in SELECT_KINDS or kind in ("hide", "set_hidden", "edit", "append_arrays"):
+        return replace(state, edits=state.edits + (op,))
+    if kind == "duplicate":        # (its argument is the trace's expectation "fit" / "grow" / None, no part of the recipe)
+        return replace(state, edits=state.edits + ((kind,),))
+    if kind == "erase":            # (a removing erase drops the SH state and the accumulators; the traces' erases all remove)
+        return replace(state, edits=state.edits + (op,), sh=None, contrib=None)
+    if kind == "overlay":          # (the ring's switch is the ring's: it stays when the options go, see overlay_ring_refuses)
+        return replace(state, overlay=None if a[0] is None else tuple(a))
+    if kind == "ring_overlay":
+        return replace(state, ring_overlay=bool(a[0]))
+    if kind == "contrib_reset":
+        return replace(state, contrib=())
+    if kind == "contrib_pass":     # (without a prior reset the first pass resets first)
+        return replace(state, contrib=(state.contrib or ()) + (frame_of(state) + (len(state.edits),),))
+    assert kind in KINDS or kind == "reserve", op
+    return state      # same_pose, sort_only, readback, depth_async, timing_interval, overflow_sync, deliver, refused, reserve
+
+
+def overlay_ring_refuses(state):
+    """The one State in which a delivery is refused by design: the ring was switched to the overlay and the overlay's options were
+    taken away afterwards.  The switch stays (options set again, the ring delivers the overlay again); until then
+    gsr_deliver_frame_async returns GSR_ERR_ARG ("the options are off") and takes no slot."""
+    return state.ring is not None and state.ring_overlay and state.overlay is None
+
+
+def frame_of(state):
+    """what a frame's lists depend on besides the scene: (pose, W, H, band, fade)"""
+    return (state.pose, state.W, state.H, state.band, state.fade)
 
 
 def fold_all(state, trace):
@@ -159,16 +264,35 @@ def tags(op, before):
         out.add("fade:on" if a[0] else "fade:off")
     elif kind in ("readback", "refused"):
         out.add(kind + ":" + a[0])
+    elif kind in SELECT_KINDS:
+        out.add("select")
+    elif kind == "hide":
+        if a[0] in ("add", "replace"):
+            out.add("hide:on")
+    elif kind == "set_hidden":
+        if a[0] is None and a[1] == "replace":
+            out.update(("hide", "hide:off"))
+        elif a[0] is not None and a[1] in ("add", "replace"):
+            out.update(("hide", "hide:on"))
+    elif kind == "duplicate":
+        if a[0]:
+            out.add("duplicate:" + a[0])
+    elif kind == "overlay":
+        out.add("overlay:off" if a[0] is None else "overlay:on")
     return out
 
 
 def pairs_in(state, trace):
-    """every (tag, tag) of two neighbouring operations of the trace"""
-    seen, prev = set(), None
+    """every (tag, tag) of two neighbouring operations of the trace.  A picker that goes unchecked touches no frame and no scene
+    array, and some neighbours need one between them (an erase leaves the empty selection, a duplicate needs one): the operation
+    in front of such a picker also counts as the neighbour of the one behind it."""
+    seen, prev, through = set(), None, None
     for st in trace:
         t = tags(st.op, state)
-        if prev is not None:
-            seen.update((x, y) for x in prev for y in t)
+        for p in (prev, through):
+            if p is not None:
+                seen.update((x, y) for x in p for y in t)
+        through = (through or prev) if (st.op[0] in SELECT_KINDS and not st.check) else None
         prev, state = t, fold(state, st.op)
     return seen
 
@@ -185,6 +309,206 @@ def bins_of(W, H, band=None):
     if band:
         return (min(-(-band[1] // 32), nbx) - band[0] // 32) * nby
     return nbx * nby
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The recipe, evaluated on the CPU (pure: the oracle and the feature suites' specifications, no renderer)
+# ---------------------------------------------------------------------------------------------------------------------------
+Materialised = namedtuple("Materialised", "data positions rotations scales n selection_words hidden_words")
+_mat_cache = {}
+_MAT_CACHE_MAX = 24
+
+
+def _refs():
+    import append_reference, attr_reference, edit_reference, hide_reference, select_reference
+    return edit_reference, append_reference, hide_reference, select_reference, attr_reference
+
+
+def recipe_rows(recipe):
+    from gsplat_hip import synth
+    return synth.config_rows(recipe[1]) if recipe[0] == "config" else synth.synth_rows(recipe[1], recipe[2])
+
+
+def spec_set(spec, n):
+    """the host's set of a set_selection / set_hidden operation: None (the empty set) or (seed, density) -> bool[n]"""
+    if spec is None:
+        return np.zeros(n, dtype=bool)
+    return np.random.default_rng(spec[0]).random(n) < spec[1]
+
+
+def mask_of(mspec):
+    """the byte mask of a select_region operation: None, or ("disc", cx, cy, radius, stride_pad) -> select_reference.disc's mask"""
+    if mspec is None:
+        return None
+    return _refs()[3].disc(*mspec[1:])[1]
+
+
+def disc_rect(mspec):
+    return _refs()[3].disc(*mspec[1:])[0]
+
+
+def band_columns(W, band):
+    """the pixel columns of a band context's whole bins (None: the whole frame)"""
+    return None if band is None else (band[0] // 32 * 32, min(-(-band[1] // 32) * 32, -(-W // 32) * 32))
+
+
+def project_frame(oracle, data, frame, hidden):
+    """(rec, bbox) of the ORACLE for a frame (pose, W, H, band, fade) of `data`, the members of `hidden` with the invisible box"""
+    import gsplat_hip as gh
+    pose, W, H, band, fade = frame
+    cam = gh.orbit_camera(pose, 120, W, H, fx=0.59 * W)
+    v, p, _ = cam.f32()
+    rec, bbox, _ = oracle.project(data, v, p, cam.fx, cam.fy, W, H, fade=fade[1] if fade[0] else None)
+    return rec, _refs()[2].hide_bbox(bbox, hidden)
+
+
+def listed_in(oracle, data, frame, hidden):
+    """bool[n]: the splats the frame lists"""
+    _, bbox = project_frame(oracle, data, frame, hidden)
+    return _refs()[3].listed(bbox, band_columns(frame[1], frame[3]))
+
+
+def picked_by(oracle, st, S, H, e):
+    """bool[n]: the set P a picker of the recipe picks from the scene `st` (selection S, hidden set H)"""
+    er, ar, hr, sr, at = _refs()
+    kind = e[0]
+    if kind == "select_box":
+        return sr.box_pick(st.positions, e[1])
+    if kind == "select_region":
+        rect, mspec, frame = e[1], e[2], e[4]
+        rec, bbox = project_frame(oracle, st.data[:8 * st.n], frame, H)
+        return sr.centre_pick(rec, bbox, rect, mask_of(mspec), band=band_columns(frame[1], frame[3]))
+    if kind == "set_selection":
+        return spec_set(e[1], st.n)
+    if kind == "select_attr":
+        v = at.attr_value(e[1], data=st.data[:8 * st.n], positions=st.positions, scales=st.scales, origin=e[4])
+        return at.select(v, e[2], e[3])
+    if kind == "select_hidden":
+        return H.copy()
+    if kind == "select_contrib":     # value < below over all splats: everything at +inf, nothing at 0 (values are >= 0)
+        assert e[2] in (np.inf, 0.0), e
+        return np.full(st.n, e[2] == np.inf)
+    raise AssertionError(e)
+
+
+def _apply_edit(oracle, st, S, H, e):
+    """one entry of State.edits on (SceneState, selection bool[n], hidden bool[n]); returns the new (S, H)"""
+    er, ar, hr, sr, at = _refs()
+    kind = e[0]
+    if kind == "invert_selection":
+        return ~S, H
+    if kind in SELECT_KINDS:
+        return sr.apply_op(S, picked_by(oracle, st, S, H, e), e[-2] if kind == "select_region" else e[-1]), H
+    if kind == "hide":
+        return S, hr.hide_selected(H, S, e[1])
+    if kind == "set_hidden":
+        return S, hr.hidden_set(H, spec_set(e[1], st.n) if e[1] is not None else None, e[2])
+    if kind == "edit":
+        what, args, pivot = e[1], e[2], e[3]
+        if what == "rgba":
+            er.paint(st, S, args[0], args[1])
+        else:
+            er.apply(st, S, what, np.asarray(args, dtype=np.float64), pivot)
+        return S, H
+    if kind == "duplicate":
+        if not S.any():                 # nothing selected: nothing touched, the selection included
+            return S, H
+        first, count = ar.duplicate(st, S)
+        return ar.selection_after(st.n, first, count), ar.hidden_after(H, count)
+    if kind == "append_arrays":
+        add = oracle.SceneState(recipe_rows(("synth", e[1], e[2], "rows")))
+        first, count = ar.append_arrays(st, add.data, add.positions, add.rotations, add.scales)
+        return ar.selection_after(st.n, first, count), ar.hidden_after(H, count)
+    if kind == "erase":
+        gone = ~S if e[1] else S
+        if not gone.any():              # nothing would be removed: nothing changes
+            return S, H
+        ar.erase(st, gone)
+        return np.zeros(st.n, dtype=bool), hr.compact(H, ~gone)
+    if kind == "transform":
+        name, values = e[1], e[2]
+        if name == "limit_box":
+            keep = sr.box_pick(st.positions, values)
+            st.limit_box(values)
+            assert st.n == int(keep.sum())
+            return np.zeros(st.n, dtype=bool), hr.compact(H, keep)
+        getattr(st, name)(values)
+        return S, H
+    raise AssertionError(e)
+
+
+def _evaluate(state, oracle):
+    """(SceneState, S, H) of the State's recipe; memoised on the recipe's prefixes (the caller copies before it changes anything)"""
+    import copy
+    base = (state.scene, state.transforms)
+    k = len(state.edits)
+    while k > 0 and base + (state.edits[:k],) not in _mat_cache:
+        k -= 1
+    if base + (state.edits[:k],) in _mat_cache:
+        st, S, H = _mat_cache[base + (state.edits[:k],)]
+        st = copy.deepcopy(st)
+    else:
+        st = oracle.SceneState(recipe_rows(state.scene))
+        for name, values in state.transforms:
+            getattr(st, name)(values)
+        S, H = np.zeros(st.n, dtype=bool), np.zeros(st.n, dtype=bool)
+    for j in range(k, len(state.edits)):
+        S, H = _apply_edit(oracle, st, S, H, state.edits[j])
+        assert S.size == st.n and H.size == st.n
+    key = base + (state.edits,)
+    if key not in _mat_cache:
+        if len(_mat_cache) >= _MAT_CACHE_MAX:
+            _mat_cache.pop(next(iter(_mat_cache)))
+        _mat_cache[key] = (copy.deepcopy(st), S.copy(), H.copy())
+    return st, S, H
+
+
+def materialise(state, oracle):
+    """The scene, the selection and the hidden set the State's recipe leaves, evaluated on the CPU only: oracle.SceneState(rows),
+    state.transforms with the oracle, state.edits with edit_reference, append_reference, hide_reference, select_reference and
+    attr_reference.  Arrays hold exactly n rows."""
+    st, S, H = _evaluate(state, oracle)
+    sr = _refs()[3]
+    return Materialised(st.data[:8 * st.n].copy(), st.positions[:3 * st.n].copy(), st.rotations[:4 * st.n].copy(),
+                        st.scales[:3 * st.n].copy(), st.n, sr.pack(S), sr.pack(H))
+
+
+def vacuous(state, op, oracle):
+    """Why `op`, performed from `state`, would check nothing (None: it checks something).  The conditions of the issue: a hide hides
+    a listed splat and leaves one listed; a region or box selection picks more than none and fewer than all listed; an erase removes
+    more than 0 and fewer than n; a contribution pass lists a selected and an unselected splat; nothing grows beyond MAX_GROWN."""
+    kind = op[0]
+    if kind not in ("hide", "set_hidden", "select_box", "select_region", "erase", "contrib_pass", "duplicate", "append_arrays", "edit"):
+        return None
+    st, S, H = _evaluate(state, oracle)
+    data = st.data[:8 * st.n]
+    if kind == "edit":
+        return None if S.any() else "nothing selected"
+    if kind in ("hide", "set_hidden"):
+        if "hide:on" not in tags(op, state):
+            return None
+        _, H1 = _apply_edit(oracle, st, S, H, op)
+        before, after = listed_in(oracle, data, frame_of(state), H), listed_in(oracle, data, frame_of(state), H1)
+        if not (before & H1 & ~H).any():
+            return "hides no listed splat"
+        return None if after.any() else "leaves nothing listed"
+    if kind in ("select_box", "select_region"):
+        e = fold(state, op).edits[-1]
+        P = picked_by(oracle, st, S, H, e)
+        L = listed_in(oracle, data, frame_of(state), H)
+        if not P.any():
+            return "picks nothing"
+        return None if (L & ~P).any() else "picks every listed splat"
+    if kind == "erase":
+        gone = int((~S if op[1] else S).sum())
+        return None if 0 < gone < st.n else "removes %d of %d" % (gone, st.n)
+    if kind == "contrib_pass":
+        L = listed_in(oracle, data, frame_of(state), H)
+        return None if (L & S).any() and (L & ~S).any() else "lists no selected or no unselected splat"
+    grown = st.n + (int(S.sum()) if kind == "duplicate" else op[1])
+    if kind == "duplicate" and not S.any():
+        return "nothing selected"
+    return None if grown <= MAX_GROWN else "grows to %d" % grown
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -350,6 +674,215 @@ def tour(band_context=False):
     return t
 
 
+SELOPS = ("replace", "add", "subtract", "intersect")
+ALL = (1, 2.0)                          # a set_selection / set_hidden spec that names every splat
+RECT = (224, 120, 416, 360)             # inside the band (192, 448) of a 640 x 480 frame
+DISC = ("disc", 320.5, 240.5, 90.0, 5)  # select_reference.disc: rows 5 bytes longer than the rectangle, the padding non-zero
+PIVOT = (0.25, -0.5, 0.125)
+OUTLINE_OUTER = ((1.0, 1.0, 1.0), 1.0, 0.5, 2, "outer")
+OUTLINE_INNER = ((0.0, 1.0, 0.25), 0.75, 0.25, 5, "inner")
+
+
+def editing_tour(band_context=False):
+    """The fixed trace of the editing layer: every kind of EDIT_KINDS, every refusal of EDIT_REFUSALS, every pair of EDIT_RISKY_PAIRS,
+    on small scenes (1, 33, 2049 and 20 000 splats built from rows, growing to at most MAX_GROWN) and small frames (at most
+    900 x 700, and one size above 4096 bins for two-level binning).  It starts from State()'s raw scene, where hiding and selecting
+    work and editing is refused.  band_context: as in tour()."""
+    C, N = True, False
+    t = []
+
+    def add(*op, check=C):
+        t.append(Step(tuple(op), check))
+
+    def size(W, H):
+        add("resize", W, H)
+        if band_context:
+            add("band", *_band_for(W))
+
+    def band_off():
+        add("band", 0, 0)
+        if band_context:
+            add("band", 192, 448)
+
+    def box(f):
+        return tuple(v * f for v in BOX)
+
+    # a raw scene: pickers and hides work, edits and erases are refused
+    add("set_selection", (3, 0.5), "replace", check=N)
+    add("refused", "edit_raw")
+    add("camera", 60)
+    add("refused", "erase_raw")
+    add("camera", 61)
+    add("hide", "add")
+    add("same_pose")                                    # the graph captured without a mask is not replayed
+    add("set_hidden", (5, 0.4), "replace")
+    add("set_hidden", None, "replace")                  # show all: the null pointer again, the buffers stay
+    add("same_pose")
+    add("hide", "add")
+    add("band", 192, 448)
+    add("set_hidden", (6, 0.5), "add")
+    add("overflow_sync", 2048)
+    add("set_hidden", (7, 0.3), "add")
+    add("overflow_async", 1024, 40, 41, 42)
+    add("set_hidden", (8, 0.2), "add")
+    add("sort_only", 1, 30)
+    add("readback", "records", check=N)
+    add("hide", "subtract")                             # show the selected ones
+    band_off()
+    add("set_hidden", (9, 0.5), "replace")
+    add("scene", ("synth", 33, 2, "rows"))              # nothing hidden again
+    add("set_hidden", (10, 0.5), "replace")
+    add("select_hidden", "replace", check=N)
+    add("edit", "translate", (0.25, 0.0, -0.125), None)
+    # one splat
+    add("scene", ("synth", 1, 3, "rows"))
+    add("set_selection", ALL, "replace", check=N)
+    add("edit", "scale", (1.5, 1.0, 0.5), None)
+    add("duplicate", "grow")
+    add("edit", "translate", (0.0, 0.25, 0.0), None)
+    # edits of the selection
+    add("scene", ("synth", 2049, 5, "rows"))
+    add("select_box", box(0.5), "replace", check=N)
+    add("edit", "translate", (0.5, -0.25, 0.125), None)
+    add("same_pose")
+    add("edit", "rotate", QUAT, None)
+    add("sort_only", 1, 31)
+    add("edit", "rotate", QUAT, PIVOT)
+    add("readback", "pick", check=N)
+    add("camera", 62)
+    add("edit", "scale", (1.25, 0.75, 1.0), None)
+    add("edit", "scale", (0.5, 1.0, 2.0), PIVOT)
+    add("edit", "rgba", (0x00c08040, 0x00ffffff), None)
+    add("edit", "rgba", (0x60000000, 0xff000000), None)
+    # pickers: a rectangle and a byte mask, all four fold ops
+    add("select_region", RECT, None, "replace", check=N)
+    add("camera", 63)
+    add("select_region", disc_rect(DISC), DISC, "add")
+    add("select_region", (256, 200, 352, 300), None, "subtract", check=N)
+    add("select_region", disc_rect(DISC), DISC, "intersect")
+    add("invert_selection")
+    add("select_attr", "opacity", 0.0, 128.0, None, "replace", check=N)
+    add("select_attr", "distance", 0.0, 1.5, (0.5, 0.0, -0.25), "add")
+    add("select_attr", "scale_max", 0.0, 0.05, None, "subtract")
+    add("set_hidden", (11, 0.3), "replace")
+    add("select_hidden", "add", check=N)
+    add("select_box", box(1.0), "intersect")
+    add("limit_box", BOX)                               # the selection does not survive, the hidden set is carried
+    add("select_box", box(0.5), "replace", check=N)
+    add("hide", "add")
+    add("limit_box", box(0.75))
+    add("set_selection", (16, 0.3), "replace", check=N)
+    add("hide", "replace")
+    add("erase", False)                                 # the hidden selected splats go; H is carried
+    add("set_selection", (12, 0.5), "replace", check=N)
+    add("erase", True)
+    add("select_box", box(0.3), "replace")
+    add("scene", ("synth", 2049, 5, "rows"))
+    # growth: beyond the capacity, inside it, inside a reserve
+    add("set_selection", ALL, "replace", check=N)
+    add("duplicate", "grow")                            # 2049 -> 4098: past sort.rows and past two blocks of 2048 keys
+    add("sort_only", 1, 32)
+    add("set_selection", (2, 0.1), "replace", check=N)
+    add("duplicate", "grow")                            # capacity 4098 -> 6147
+    add("same_pose")
+    add("set_selection", (3, 0.1), "replace", check=N)
+    add("duplicate", "fit")
+    add("same_pose")
+    add("reserve", 20000)
+    add("same_pose")
+    add("duplicate", "fit")
+    add("burst", 64, 65, 66)
+    add("edit", "translate", (0.0, 0.5, 0.0), None)     # the copies move
+    add("duplicate", "fit")
+    add("band", 192, 448)
+    band_off()
+    add("duplicate", "fit")
+    size(333, 219)
+    size(640, 480)
+    add("duplicate", "fit")
+    add("erase", False)                                 # the copies go again
+    add("set_selection", (4, 0.05), "replace", check=N)
+    add("duplicate", "fit")                             # onto the rows the compaction left stale
+    add("append_arrays", 500, 21)
+    add("limit_box", BOX)
+    add("append_arrays", 33, 22)
+    add("invert_selection")
+    add("erase", True)                                  # only the appended rows' complement stays selected: keep it
+    add("band", 192, 448)
+    band_off()
+    # the overlay
+    add("scene", ("synth", 20000, 9, "rows"))
+    add("select_box", box(0.5), "replace", check=N)
+    add("overlay", (1.0, 0.5, 0.0), 0.5, None, check=N)
+    add("resize", 801, 601)
+    if band_context:
+        add("band", *_band_for(801))
+    size(640, 480)
+    add("overlay", (0.0, 0.5, 1.0), 0.75, OUTLINE_OUTER)
+    add("set_hidden", (13, 0.4), "add")
+    add("overlay", (0.0, 0.5, 1.0), 0.75, None)
+    add("duplicate", "grow")
+    add("overlay", (1.0, 0.0, 0.0), 1.0, OUTLINE_INNER)
+    add("band", 192, 448)
+    band_off()
+    add("ring_open", "rgba8", False, None, 1)
+    add("ring_overlay", True)
+    add("deliver")
+    add("ring_overlay", True)
+    add("resize", 512, 384)
+    add("deliver")
+    if band_context:
+        add("band", *_band_for(512))
+    add("ring_close")
+    add("ring_open", "nv12", False, "u16", 2)
+    add("ring_overlay", True)
+    size(640, 480)
+    add("deliver")
+    add("ring_overlay", True)
+    add("overlay", None)                                # off under a ring that delivers it: deliveries are refused, no slot is taken
+    add("deliver")
+    add("overlay", (1.0, 0.5, 0.0), 0.5, None)          # options again: the ring's switch stayed, it delivers the overlay again
+    add("deliver", check=N)
+    add("ring_overlay", True)
+    add("ring_overlay", False)
+    add("overlay", None)
+    add("ring_close")
+    # two-level binning (above 4096 bins) with a hidden set and a grown scene
+    size(2080, 2048)
+    add("set_hidden", (14, 0.5), "replace")
+    add("select_box", box(0.3), "replace", check=N)
+    add("duplicate", "fit")
+    size(640, 480)
+    # contribution
+    add("scene", ("synth", 2049, 5, "rows"))
+    add("select_box", box(0.5), "replace", check=N)
+    add("contrib_reset")
+    add("contrib_pass", check=N)
+    add("camera", 67)
+    add("contrib_pass")
+    add("select_contrib", "weight", np.inf, "intersect", check=N)
+    add("contrib_pass", check=N)
+    add("duplicate", "grow")                            # the accumulators grow with zeros
+    add("contrib_pass", check=N)
+    add("erase", False)                                 # ... and are dropped
+    add("select_box", box(0.5), "replace", check=N)
+    add("contrib_pass")                                 # never reset: the first pass resets first
+    add("select_contrib", "pixels", 0.0, "subtract")
+    add("contrib_pass", check=N)
+    add("scene", ("synth", 2049, 6, "rows"))
+    # refusals that need SH rows, and an upload that contradicts itself
+    add("set_selection", (15, 0.5), "replace", check=N)
+    add("sh", (11, 0.0, 0.25, 0.5))
+    add("refused", "grow_with_sh")
+    add("camera", 68)
+    add("refused", "rotate_selected_sh_follow")
+    add("camera", 69)
+    add("sh", None)
+    add("refused", "append_positions_differ")
+    add("camera", 70)
+    return t
+
+
 WALK_SIZES = ((640, 480), (333, 219), (900, 700), (64, 64), (801, 601), (512, 384), (160, 96))
 WALK_SCENES = (0, 1, 63, 2049, 20000, 7000, 300, 12000)
 WALK_RINGS = (("rgba8", False, None, 1), ("nv12", False, None, 1), ("i420", True, None, 1), ("rgba8", False, "u16", 1),
@@ -418,18 +951,149 @@ def _gen(kind, s, rng):
     raise AssertionError(kind)
 
 
-def walk(seed, steps, start=State()):
+def _picker(s, rng):
+    """one picker that needs nothing but a scene (a region picks from the frame of the State's pose)"""
+    selop = rng.choice(SELOPS)
+    kind = rng.choice(("select_box", "select_region", "select_region", "set_selection", "select_attr"))
+    if kind == "select_box":
+        f = rng.choice((0.3, 0.5, 0.75))
+        return ("select_box", tuple(v * f for v in BOX), selop)
+    if kind == "select_region":
+        x0, x1 = s.band if s.band is not None else (0, s.W)
+        w = x1 - x0
+        if rng.random() < 0.5 and min(w, s.H) >= 12:
+            mspec = ("disc", x0 + w / 2.0, s.H / 2.0, float(min(w, s.H) // 3), rng.choice((0, 3)))
+            return ("select_region", disc_rect(mspec), mspec, selop)
+        return ("select_region", (x0 + w // 4, s.H // 4, x0 + max(w // 4 + 1, 3 * w // 4), max(s.H // 4 + 1, 3 * s.H // 4)), None, selop)
+    if kind == "set_selection":
+        return ("set_selection", (rng.randrange(1, 99), rng.choice((0.1, 0.5))), selop)
+    attr = rng.choice(("x", "opacity", "distance") + (("scale_max",) if scene_form(s.scene) == "rows" else ()))
+    lo, hi, origin = {"x": (-0.5, 0.75, None), "opacity": (0.0, 128.0, None), "distance": (0.0, 1.5, (0.5, 0.0, -0.25)),
+                      "scale_max": (0.0, 0.05, None)}[attr]
+    return ("select_attr", attr, lo, hi, origin, selop)
+
+
+def _gen_edit(kind, s, rng):
+    """_gen for the kinds of EDIT_KINDS and ("refused_edit",): the operations, preludes included.  Which splats a step touches depends
+    on the scene: walk() asks `vacuous` and draws again."""
+    rows_scene = ("scene", ("synth", rng.choice((2049, 7000, 20000)), rng.randrange(1, 50), "rows"))
+    small = scene_n(s.scene) < 33
+    need_scene = [rows_scene] if small else []
+    need_rows = [rows_scene] if small or scene_form(s.scene) != "rows" else []
+    sh_now = None if need_rows else s.sh
+    picker = [_picker(fold_ops(s, need_rows), rng)] if rng.random() < 0.5 else []
+    no_sh = [("sh", None)] if sh_now is not None else []
+    # (what a region picks and what a pass lists depends on the pose: some of the draws move the camera first)
+    cam = [("camera", rng.randrange(120))] if rng.random() < 0.5 else []
+    if kind in ("select_box", "select_region", "set_selection", "select_attr"):
+        while True:
+            op = _picker(fold_ops(s, need_scene), rng)
+            if op[0] == kind:
+                return need_scene + (cam if kind == "select_region" else []) + [op]
+    if kind == "invert_selection":
+        return need_scene + [("invert_selection",)]
+    if kind == "select_hidden":
+        return need_scene + [("select_hidden", rng.choice(SELOPS))]
+    if kind == "select_contrib":
+        pre = [] if s.contrib and not need_scene else cam + [("set_selection", (rng.randrange(1, 99), 0.5), "replace"), ("contrib_pass",)]
+        return need_scene + pre + [("select_contrib", rng.choice(("weight", "peak", "pixels")), rng.choice((np.inf, 0.0)), rng.choice(SELOPS))]
+    if kind == "hide":
+        return need_scene + ([_picker(fold_ops(s, need_scene), rng)] if picker else []) + [("hide", rng.choice(SELOPS))]
+    if kind == "set_hidden":
+        if rng.random() < 0.25:
+            return need_scene + [("set_hidden", None, "replace")]
+        return need_scene + [("set_hidden", (rng.randrange(1, 99), rng.choice((0.2, 0.5))), rng.choice(SELOPS))]
+    if kind == "edit":
+        what = rng.choice(("translate", "rotate", "scale", "rgba"))
+        pivot = None if what in ("translate", "rgba") or rng.random() < 0.5 else PIVOT
+        args = {"translate": tuple(rng.choice((-0.5, -0.125, 0.0, 0.25)) for _ in range(3)), "rotate": QUAT,
+                "scale": tuple(rng.choice((0.5, 1.0, 1.25)) for _ in range(3)),
+                "rgba": (rng.randrange(1 << 32), rng.choice((0x00ffffff, 0xff000000, 0xffffffff, 0x0000ff00)))}[what]
+        return need_rows + picker + [("edit", what, args, pivot)]
+    if kind == "reserve":
+        return need_rows + no_sh + [("reserve", rng.choice((1000, 25000, 30000, 40000)))]
+    if kind == "duplicate":
+        return need_rows + no_sh + picker + [("duplicate", None)]
+    if kind == "append_arrays":
+        return need_rows + no_sh + [("append_arrays", rng.choice((1, 33, 500)), rng.randrange(1, 50))]
+    if kind == "erase":
+        return need_rows + no_sh + picker + [("erase", rng.random() < 0.5)]
+    if kind == "overlay":
+        if s.overlay is not None and rng.random() < 0.3:
+            return [("overlay", None)]
+        tint = tuple(rng.choice((0.0, 0.5, 1.0)) for _ in range(3))
+        return [("overlay", tint, rng.choice((0.25, 0.5, 1.0)), rng.choice((None, OUTLINE_OUTER, OUTLINE_INNER)))]
+    if kind == "ring_overlay":
+        if s.ring_overlay:
+            return [("ring_overlay", False)]
+        return (([] if s.ring else [("ring_open",) + rng.choice(WALK_RINGS)]) +
+                ([] if s.overlay else [("overlay", (1.0, 0.5, 0.0), 0.5, OUTLINE_OUTER)]) + [("ring_overlay", True), ("deliver",)])
+    if kind == "contrib_reset":
+        return [("contrib_reset",)]
+    if kind == "contrib_pass":
+        half = [("set_selection", (rng.randrange(1, 99), 0.5), "replace")] if rng.random() < 0.6 else []
+        return need_scene + cam + half + [("contrib_pass",)]
+    if kind == "refused_edit":
+        which = rng.choice(EDIT_REFUSALS)
+        some = ("set_selection", (rng.randrange(1, 99), 0.5), "replace")
+        if which in ("edit_raw", "erase_raw"):
+            raw = [] if scene_form(s.scene) == "raw" and not small else [("scene", ("synth", rng.choice((2049, 7000)), rng.randrange(1, 50), "raw"))]
+            return raw + [some, ("refused", which)]
+        if which == "append_positions_differ":
+            return need_rows + no_sh + [("refused", which)]
+        return need_rows + ([] if sh_now is not None else [("sh", (rng.randrange(1, 99), 0.0, 0.25, 0.5))]) + [some, ("refused", which)]
+    raise AssertionError(kind)
+
+
+def fold_ops(state, ops):
+    for op in ops:
+        state = fold(state, op)
+    return state
+
+
+def walk(seed, steps, start=State(), kinds=KINDS, oracle=None):
     """A seeded random walk over the same operations with cheap States (<= 20 000 splats, <= 900 x 700).  The kinds are dealt like
     cards -- one shuffled deck after another -- so that a walk of twice as many steps as there are kinds and preludes holds every
-    kind; walk(seed, k) is the first k steps of walk(seed, k + 1), so a failure at step k replays as walk(seed, k + 1)."""
+    kind; walk(seed, k) is the first k steps of walk(seed, k + 1), so a failure at step k replays as walk(seed, k + 1).
+    kinds: KINDS (the walks as they always were), or KINDS + EDIT_KINDS: the editing layer's kinds and its refusals join the deck
+    (scenes then grow to at most MAX_GROWN splats).  Those steps depend on the scene -- a hide must hide something that shows --,
+    so the walk needs the `oracle` (CPU) to ask `vacuous`, draws a kind's operations again up to eight times and leaves the kind
+    to the next deck if all of them would check nothing."""
     rng = random.Random(seed)
     t, s = [], start
+    if kinds is KINDS or tuple(kinds) == KINDS:
+        while len(t) < steps:
+            deck = list(KINDS)
+            rng.shuffle(deck)
+            for kind in deck:
+                for op in _gen(kind, s, rng):
+                    check = not (op[0] in KEEPS_FRAME and rng.random() < 0.3)
+                    t.append(Step(op, check))
+                    s = fold(s, op)
+        return t[:steps]
+    assert oracle is not None, "a walk over the editing layer asks the oracle which steps check something"
     while len(t) < steps:
-        deck = list(KINDS)
+        deck = list(kinds) + ["refused_edit"]
         rng.shuffle(deck)
         for kind in deck:
-            for op in _gen(kind, s, rng):
-                check = not (op[0] in KEEPS_FRAME and rng.random() < 0.3)
+            for _ in range(8):
+                ops = _gen(kind, s, rng) if kind in KINDS else _gen_edit(kind, s, rng)
+                s1, out = s, []
+                for op in ops:
+                    if s1.contrib and op[0] in MOVES_GEOMETRY:
+                        out.append(("contrib_reset",))   # (the accumulators describe frames of splats that are about to move)
+                        s1 = fold(s1, out[-1])
+                    if vacuous(s1, op, oracle) is not None:
+                        out = None
+                        break
+                    out.append(op)
+                    s1 = fold(s1, op)
+                if out is not None:
+                    break
+            if out is None:
+                continue
+            for op in out:
+                check = not ((op[0] in KEEPS_FRAME or op[0] in EDIT_KEEPS_FRAME) and rng.random() < 0.3)
                 t.append(Step(op, check))
                 s = fold(s, op)
     return t[:steps]
@@ -523,18 +1187,112 @@ def build(gh, state, lib_path=None):
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
-    _load_scene(gh, r, state.scene)
-    for name, values in state.transforms:
-        _transform(r, name, values)
-    if state.sh is not None:
-        _set_sh(gh, r, state.sh)
-    if state.fade != (False, 0.0):
-        r.set_depth_fade(*state.fade)
-    if state.hit_alpha != 0.5:
-        r.set_hit_alpha(state.hit_alpha)
-    if state.ring is not None:
-        _open_ring(r, state.ring)
+    try:
+        _build_scene(gh, r, state)
+        if state.sh is not None:
+            _set_sh(gh, r, state.sh)
+        if state.fade != (False, 0.0):
+            r.set_depth_fade(*state.fade)
+        if state.hit_alpha != 0.5:
+            r.set_hit_alpha(state.hit_alpha)
+        if state.overlay is not None:
+            _set_overlay(r, state.overlay)
+        if state.ring is not None:
+            _open_ring(r, state.ring)
+        if state.ring_overlay:      # (the switch needs options when it is thrown; it stays when they go)
+            if state.overlay is None:
+                r.set_overlay((1.0, 0.5, 0.0), 0.5)
+            r.delivery_set_overlay(True)
+            if state.overlay is None:
+                r.set_overlay(None)
+    except Exception:
+        r.dispose()
+        raise
     return r
+
+
+def _oracle():
+    from oracle import oracle as O
+    O.lib()
+    return O
+
+
+def _build_scene(gh, r, state):
+    """The State's scene on a fresh context.  Without edits: the upload and the device's transforms, as ever.  With edits: the
+    materialised arrays, selection and hidden words -- a capacity equal to n, no edit kernel, no growth -- and the contribution
+    passes rendered again."""
+    if not state.edits and state.contrib is None:
+        _load_scene(gh, r, state.scene)
+        for name, values in state.transforms:
+            _transform(r, name, values)
+        return
+    O = _oracle()
+    if not state.edits:
+        _load_scene(gh, r, state.scene)
+        for name, values in state.transforms:
+            _transform(r, name, values)
+        m = None
+    else:
+        m = materialise(state, O)
+        if scene_form(state.scene) == "rows" and m.n:
+            r.set_scene_arrays(m.data, m.positions, m.rotations, m.scales)
+        else:                       # (a raw scene takes pickers and hides only: its arrays are the upload's)
+            _load_scene(gh, r, state.scene)
+            assert r.scene_count() == m.n
+        if m.selection_words.any():
+            r.set_selection(words=m.selection_words)
+    if state.contrib is not None:
+        _replay_contrib(gh, r, state, O)
+    if m is not None and m.hidden_words.any():
+        r.set_hidden(words=m.hidden_words)
+
+
+def _replay_contrib(gh, r, state, O):
+    """The accumulators of the State: every pass since the last reset rendered again under its pose, size, band and fade.  Rows
+    appended since a pass did not exist for it: they are hidden while it is rendered again (a hidden splat is in no list, and the
+    order of the others does not depend on it), and so is what was hidden then."""
+    n = r.scene_count()
+    r.contrib_reset()
+    hid_any, cur_band, cur_fade = False, state.band, (False, 0.0)
+
+    def frame_like(W, H, band, fade):
+        nonlocal cur_band, cur_fade
+        if (r.width, r.height) != (W, H):
+            r.setSize(W, H)
+            cur_band = None                     # (gsr_resize drops the band)
+        if band != cur_band:
+            r.set_band(*(band if band is not None else (0, 0)))
+            cur_band = band
+        if fade != cur_fade:
+            r.set_depth_fade(*fade)
+            cur_fade = fade
+
+    for pose, W, H, band, fade, at in state.contrib:
+        frame_like(W, H, band, fade)
+        then = materialise(replace(state, edits=state.edits[:at]), O)
+        assert then.n <= n
+        hid = np.ones(n, dtype=bool)
+        hid[:then.n] = _refs()[3].unpack(then.hidden_words, then.n)
+        if hid.any() or hid_any:
+            r.set_hidden(hid)
+            hid_any = True
+        r.set_camera(gh.orbit_camera(pose, 120, W, H, fx=0.59 * W))
+        r.render_async()
+        r.contrib_accumulate()
+    r.sync()
+    frame_like(state.W, state.H, state.band, (False, 0.0))
+    if hid_any:
+        r.set_hidden(None)
+
+
+def _set_overlay(r, overlay):
+    tint, mix, outline = overlay
+    r.set_overlay(tint, mix)
+    if outline is None:
+        r.set_overlay_outline(None)
+    else:
+        rgb, alpha, threshold, width, side = outline
+        r.set_overlay_outline(rgb, alpha, threshold, width, side)
 
 
 def _frame(gh, r, state, pose=None, sync=False):
@@ -553,6 +1311,20 @@ def _refuse(gh, r, state, which):
             r.setSize(0, 10)
         elif which == "timing_interval_zero":
             r.set_timing_interval(0)
+        elif which == "edit_raw":                        # (edits need rotations / scales)
+            r.scene_translate_selected((0.5, 0.0, 0.0))
+        elif which == "erase_raw":
+            r.scene_erase_selected()
+        elif which == "rotate_selected_sh_follow":       # (the SH frame is one per scene: a partial rotation has none)
+            r.set_sh_follow(True)
+            try:
+                r.scene_rotate_selected(QUAT)
+            finally:
+                r.set_sh_follow(False)
+        elif which in ("grow_with_sh", "append_positions_differ"):
+            add = _oracle().SceneState(gh.synth.synth_rows(3, 78))
+            pos = add.positions + np.float32(1.0) if which == "append_positions_differ" else add.positions
+            r.scene_append_arrays(add.data, pos, add.rotations, add.scales)
         else:
             rows = gh.synth.synth_rows(500, 77)
             sc = gh.Scene()
@@ -563,9 +1335,20 @@ def _refuse(gh, r, state, which):
     raise AssertionError("the library accepted %s" % which)
 
 
-def apply(gh, r, op, before):
+def deliver_refused(gh, r):
+    """gsr_deliver_frame_async in a State of overlay_ring_refuses: refused, and only in that way; returns the message"""
+    try:
+        r.deliver()
+    except gh.GsplatError as e:
+        assert e.code == GSR_ERR_ARG and "the options are off" in str(e), str(e)
+        return str(e).split(": ", 1)[-1]
+    raise AssertionError("the ring delivered an overlay without options")
+
+
+def apply(gh, r, op, before, edited=False):
     """Perform `op` on the renderer, which is in State `before`.  Returns a dict of what the operation itself observed
-    ({"overflowed": bool} for the overflow operations)."""
+    ({"overflowed": bool} for the overflow operations).  edited: the scene was edited since the renderer's last frame (a read-back
+    of planes or picks is then refused, and only then)."""
     kind, a = op[0], op[1:]
     out = {}
     if kind == "camera":
@@ -600,9 +1383,13 @@ def apply(gh, r, op, before):
             else:
                 r.stats()
         except gh.GsplatError as e:
-            # the one documented refusal: planes and picks of a frame need its bin lists, and the frame enqueued last was sort-only
-            # (gsr_sort, or the whole permutation a band context sorts on demand for gsr_read_depth_index / gsr_read_keys)
-            assert which in ("read_depth", "pick") and e.code == GSR_ERR_ARG and "sort-only" in str(e), (which, str(e))
+            # the documented refusals: planes and picks of a frame need its bin lists, and the frame enqueued last was sort-only
+            # (gsr_sort, or the whole permutation a band context sorts on demand for gsr_read_depth_index / gsr_read_keys); or, with
+            # `edited` (the caller knows that the scene was edited since the last frame, through this context or another member
+            # of its shared scene), the frame is gone until the next one is rendered
+            ok = "sort-only" in str(e) or (edited and "no frame has been rendered yet" in str(e))
+            assert which in ("read_depth", "pick") and e.code == GSR_ERR_ARG and ok, (which, str(e))
+            out["refused"] = str(e)
     elif kind == "scene":
         _load_scene(gh, r, a[0])
     elif kind == "resize":
@@ -646,6 +1433,9 @@ def apply(gh, r, op, before):
         r.close_delivery()
     elif kind == "deliver":
         _frame(gh, r, before)
+        if overlay_ring_refuses(before):
+            out["refused"] = deliver_refused(gh, r)
+            return out
         k = r.deliver()
         got = r.acquire(k)
         assert got[0] == k
@@ -653,5 +1443,66 @@ def apply(gh, r, op, before):
     elif kind == "refused":
         out["code"] = _refuse(gh, r, before, a[0])
     else:
-        raise AssertionError(op)
+        _apply_editing(gh, r, op, before, out)
     return out
+
+
+def _apply_editing(gh, r, op, before, out):
+    kind, a = op[0], op[1:]
+    if kind == "select_box":
+        r.select_box(a[0], a[1])
+    elif kind == "select_region":                         # centre mode, from the frame of the State's pose
+        _frame(gh, r, before)
+        r.select_region(a[0], mask_of(a[1]), "centre", a[2])
+    elif kind == "set_selection":
+        r.set_selection(None if a[0] is None else spec_set(a[0], r._count()), a[1])
+    elif kind == "invert_selection":
+        r.invert_selection()
+    elif kind == "select_attr":
+        r.select_attr(a[0], a[1], a[2], a[3], a[4])
+    elif kind == "select_hidden":
+        r.select_hidden(a[0])
+    elif kind == "select_contrib":
+        r.select_contrib(a[0], a[1], a[2])
+    elif kind == "hide":
+        r.hide_selected(a[0])
+    elif kind == "set_hidden":
+        r.set_hidden(None if a[0] is None else spec_set(a[0], r._count()), a[1])
+    elif kind == "edit":
+        what, args, pivot = a
+        if what == "translate":
+            r.scene_translate_selected(args)
+        elif what == "rgba":
+            r.scene_set_rgba_selected(args[0], args[1])
+        else:
+            getattr(r, "scene_%s_selected" % what)(args, pivot)
+    elif kind == "reserve":
+        r.scene_reserve(a[0])
+    elif kind == "duplicate":
+        cap = r.scene_capacity()
+        first, count = r.scene_duplicate_selected()
+        out["count"] = count
+        if a[0]:                                          # the trace says on which side of the capacity this copy falls
+            assert count and (r.scene_capacity() == cap) == (a[0] == "fit"), (op, cap, r.scene_capacity(), first, count)
+    elif kind == "append_arrays":
+        add = _oracle().SceneState(recipe_rows(("synth", a[0], a[1], "rows")))
+        r.scene_append_arrays(add.data, add.positions, add.rotations, add.scales)
+    elif kind == "erase":
+        n0 = r.scene_count()
+        n1 = r.scene_erase_selected(keep=a[0])
+        assert 0 < n1 < n0, (op, n0, n1)                  # (the traces' erases all remove something and leave something)
+    elif kind == "overlay":
+        if a[0] is None:
+            r.set_overlay(None)
+        else:
+            _set_overlay(r, a)
+    elif kind == "ring_overlay":
+        r.delivery_set_overlay(a[0])
+    elif kind == "contrib_reset":
+        r.contrib_reset()
+    elif kind == "contrib_pass":
+        r.set_camera(camera_of(gh, before))
+        r._check(r._L.gsr_render(r._ctx))                 # the blocking entry point: a frame that did not fit is rendered again
+        r.contrib_accumulate()
+    else:
+        raise AssertionError(op)

@@ -10,11 +10,14 @@ is compared BIT FOR BIT.  No tolerance: a wrong entry in one bin list shows.  (V
 random walks also meet the CPU oracle every tenth step.)"""
 import ctypes
 import os
+from dataclasses import replace
 
 import numpy as np
 import pytest
 
+import hide_reference
 import history_trace as ht
+import select_reference
 import work_items_reference
 
 pytestmark = pytest.mark.gpu
@@ -30,6 +33,11 @@ FRAME_STATS = ("visible", "bin_entries", "tile_entries", "n")
 #   a delivered frame's trailer is (overflow word, dims, serial low, serial high): the serial counts deliveries
 TRAILER_FRAME_WORDS = 2
 #   and the serial gsr_deliver_frame_async / gsr_acquire_frame return (never compared)
+#   scene_capacity() and the byte count of scene_sharing() depend on the context's life BY RULE ("Growing the scene"): the
+#   arrays grow to max(need, capacity + capacity / 2) and never shrink, a compaction keeps the old count's rows, and the selection,
+#   hidden and contribution buffers are counted once they exist -- a veteran that grew, reserved or showed everything again holds
+#   more than a context that was handed the final scene
+NOT_COMPARED = ("scene_capacity()", "scene_sharing() bytes")
 
 
 @pytest.fixture(scope="module")
@@ -76,7 +84,10 @@ def observe(r, state, points=None):
     """Everything the finished frame can be asked, in an order every answer survives (a band context sorts the whole permutation on
     demand for keys / depthIndex, which makes the frame enqueued last a sort-only one: planes and picks are asked first)."""
     o = {}
-    if state.ring is not None:
+    if ht.overlay_ring_refuses(state):       # (the one delivery that is refused by design: it takes no slot, and says why)
+        import gsplat_hip
+        o["delivery refused"] = ht.deliver_refused(gsplat_hip, r)
+    elif state.ring is not None:
         o["delivered payload"], o["delivered depth plane"], o["delivered trailer (overflow word, dims)"] = _deliver(r)
     img = r.readPixelsFloat()
     o["f32 image"] = img
@@ -89,6 +100,9 @@ def observe(r, state, points=None):
         points = [ht.into_band(state, x, y) for x, y in points]
     o["pick points"] = points
     o["pick()"] = r.pick(points)
+    if state.overlay is not None:       # (the pass walks this frame's lists: asked while the frame enqueued last is a render frame)
+        o["read_overlay() (rgba, cover)"] = r.read_overlay()
+        o["read_overlay_rgba8()"] = r.read_overlay_rgba8()
     starts, lst = r.bin_lists()
     o["bin starts"], o["bin list entries"] = starts, lst
     o["work_items()"] = r.work_items()
@@ -105,6 +119,17 @@ def observe(r, state, points=None):
     keys, mm = r.read_keys()
     o["keys"], o["key (min, max)"] = keys, mm
     o["depthIndex"] = r.lastDepthIndex()
+    # the scene and the sets that are held with it
+    o["scene_count()"] = r.scene_count()
+    o["read_scene() (data, positions, rotations, scales)"] = r.read_scene(with_rows=ht.scene_form(state.scene) == "rows")
+    o["selection words"], o["selection count"] = r.selection_words(), r.selection_count()
+    o["hidden words"], o["hidden count"] = r.hidden_words(), r.hidden_count()
+    count, lo, hi = r.selection_bounds()         # (values, not bits: which of -0.0 and +0.0 a bound holds is not defined)
+    o["selection_bounds()"] = (count, tuple(float(v) for v in lo), tuple(float(v) for v in hi))
+    if state.contrib is not None:
+        o["read_contrib() (weight, peak, pixels, frames)"] = r.read_contrib()
+    o["attr_histogram(opacity, visible and selected)"] = r.attr_histogram("opacity", 0.0, 256.0, 16, selected=True, visible=True)[:2]
+    o["attr_stats(opacity, visible and selected)"] = r.attr_stats("opacity", selected=True, visible=True)
     return o
 
 
@@ -142,9 +167,21 @@ def compare_with_fresh(gh, vet, state, where, lib_path=None):
 
 
 def meet_oracle(gh, O, vet, state, a, where):
-    """depthIndex exact, the band's columns of the image within TOL_EXACT: veteran and fresh are not wrong together"""
-    data, pos, _, _ = vet.read_scene(with_rows=False)
+    """depthIndex exact, the band's columns of the image within TOL_EXACT: veteran and fresh are not wrong together.  And the scene,
+    the selection and the hidden set the veteran holds are the recipe's, evaluated on the CPU: bit for bit."""
+    rows = ht.scene_form(state.scene) == "rows"
+    data, pos, rot, scl = a["read_scene() (data, positions, rotations, scales)"]
     n = pos.size // 3
+    m = ht.materialise(state, O)
+    assert n == m.n == a["scene_count()"], "%s: %d splats, the recipe leaves %d" % (where(), n, m.n)
+    want = (m.data, m.positions, m.rotations, m.scales)
+    if not rows:      # (a raw scene takes pickers and hides only: its arrays are the upload's)
+        _, up_data, up_pos = ht.scene_arrays(gh, state.scene)
+        want = (np.ascontiguousarray(up_data[:8 * n]), np.ascontiguousarray(up_pos[:3 * n]), None, None)
+    for name, x, y in zip(("data", "positions", "rotations", "scales"), (data, pos, rot, scl), want):
+        assert _same(x, y), "%s: the veteran's %s differ from the recipe's" % (where(), name)
+    assert _same(a["selection words"], m.selection_words), "%s: the selection differs from the recipe's" % where()
+    assert _same(a["hidden words"], m.hidden_words), "%s: the hidden set differs from the recipe's" % where()
     cam = ht.camera_of(gh, state)
     v, p, vp = cam.f32()
     sh = bidx = None
@@ -152,8 +189,11 @@ def meet_oracle(gh, O, vet, state, a, where):
         tex, b = ht.sh_arrays(gh, state.sh, n)
         if n - (int(b[0]) + 1) > 0:
             sh, bidx = tex, b
-    oimg, odi, _, _ = O.render_scene(data, pos, v, p, vp, cam.fx, cam.fy, state.W, state.H, mode=1, sh=sh, band=bidx,
-                                     fade=state.fade[1] if state.fade[0] else None)
+    # the oracle's frame with the hidden splats' boxes made invisible (hide_reference: they are still sorted)
+    odi, _, _ = O.sort(vp, pos)
+    rec, bbox, raw = O.project(data, v, p, cam.fx, cam.fy, state.W, state.H, sh, bidx, state.fade[1] if state.fade[0] else None)
+    bbox = hide_reference.hide_bbox(bbox, select_reference.unpack(m.hidden_words, n))
+    oimg = O.render(odi, raw, rec, bbox, state.W, state.H, 1)
     assert np.array_equal(a["depthIndex"], odi), "%s: depthIndex differs from the oracle" % where()
     x0, x1 = (state.band[0] // 32 * 32, min(-(-state.band[1] // 32) * 32, state.W)) if state.band else (0, state.W)
     img = a["f32 image"]
@@ -271,6 +311,163 @@ def test_a_refused_call_changes_nothing(gh):
         r.dispose()
     assert codes == {"band_off_boundary": ht.GSR_ERR_ARG, "size_zero": ht.GSR_ERR_ARG, "positions_differ": ht.GSR_ERR_SCENE,
                      "timing_interval_zero": ht.GSR_ERR_ARG}
+
+
+def _bounds_counts(L, units):
+    bad = {}
+    for unit in units:
+        buf = (ctypes.c_uint32 * 8)()
+        assert getattr(L, "gsr_debug_bounds_" + unit)(buf) == 0
+        bad.update({(unit, site): v for site, v in enumerate(buf) if v})
+    return bad
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The editing layer: selection, hidden set, edits of the selection, growth and erasure, overlay, contribution (history_trace's
+# State.edits / overlay / ring_overlay / contrib).  The fresh context gets the recipe evaluated on the CPU: it never ran an edit
+# kernel and never grew, and its capacity equals its count.
+# ---------------------------------------------------------------------------------------------------------------------------
+EDIT_BOUNDS_UNITS = ("blend", "bin", "sort", "depth", "deliver", "scene", "scene_sh", "select", "edit", "append", "contrib", "overlay", "attr")
+ALL_KINDS = ht.KINDS + ht.EDIT_KINDS
+
+
+def test_editing_tour_on_a_default_context(gh):
+    t = ht.editing_tour()
+    checked, _ = run_trace(gh, t, ht.State(kind="default"), "editing tour, default context")
+    assert checked == sum(st.check for st in t)
+
+
+def test_editing_tour_on_a_throughput_context(gh):
+    """(with stage events on every other frame: the others are graph replays)"""
+    t = [ht.Step(("timing_interval", 2), True)] + ht.editing_tour()
+    checked, _ = run_trace(gh, t, ht.State(kind="throughput", timing=True), "editing tour, throughput context")
+    assert checked == sum(st.check for st in t)
+
+
+def test_editing_tour_on_a_band_context(gh):
+    t = ht.editing_tour(band_context=True)
+    checked, _ = run_trace(gh, t, ht.State(kind="throughput", band=(192, 448)), "editing tour, band context")
+    assert checked == sum(st.check for st in t)
+
+
+def test_editing_tour_on_the_bounds_checked_build(gh):
+    """a stale row behind n, a selection word of the old capacity, a rectangle of the old numbering: indices into the wrong data,
+    counted by the build that checks every index derived from device data"""
+    assert os.path.exists(BOUNDS_LIB), "the bounds-checked build is missing: run python -c 'import __graft_entry__ as g; g.build()'"
+    t = ht.editing_tour(band_context=True)
+    _, L = run_trace(gh, t, ht.State(kind="default", band=(192, 448)), "editing tour, bounds-checked build", lib_path=BOUNDS_LIB)
+    bad = _bounds_counts(L, EDIT_BOUNDS_UNITS)
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("kind", ["default", "throughput"])
+@pytest.mark.parametrize("seed", [11, 22, 33])
+def test_editing_walks(gh, oracle, seed, kind):
+    """random walks over the old and the new kinds together (tests/test_history_trace.py: each holds every kind, no step is vacuous)"""
+    start = ht.State(kind=kind, timing=bool(seed & 1))
+    t = ht.walk(seed, 150, start, kinds=ALL_KINDS, oracle=oracle)
+    run_trace(gh, t, start, "walk(%d, 150, kinds=KINDS + EDIT_KINDS), %s context" % (seed, kind), oracle=oracle)
+
+
+SHARED_FIELDS = ("scene", "transforms", "sh", "edits", "contrib")      # what the members of a shared scene have together
+
+
+def test_two_veterans_share_one_scene(gh, oracle):
+    """A default context and a throughput context of another size render one device scene.  Operations arrive through either member
+    in turn while a frame of the other is in flight; after each, every member's frame is the frame of a fresh context of its kind
+    built from the same State, a pick through the member that did not act is refused exactly when the operation was an edit, and
+    selection and hidden set read the same through both."""
+    box = tuple(v * 0.5 for v in ht.BOX)
+    ops = [("select_box", box, "replace"), ("hide", "add"), ("set_selection", (3, 0.3), "replace"), ("edit", "translate", (0.25, -0.5, 0.0), None),
+           ("duplicate", "grow"), ("edit", "rotate", ht.QUAT, ht.PIVOT), ("set_hidden", (5, 0.3), "add"), ("select_region", (80, 50, 250, 170), None, "replace"),
+           ("edit", "rgba", (0x80ff2010, 0xffffffff), None), ("select_attr", "opacity", 0.0, 128.0, None, "add"), ("duplicate", None), ("erase", False),
+           ("select_region", ht.RECT, None, "replace"), ("reserve", 9000), ("duplicate", "fit"), ("rotate", ht.QUAT), ("set_hidden", None, "replace"),
+           ("invert_selection",), ("append_arrays", 33, 4), ("limit_box", ht.BOX), ("set_selection", (6, 0.5), "replace"), ("erase", True)]
+    scene = ("synth", 2049, 5, "rows")
+    states = [ht.State(kind="default", scene=scene), ht.State(kind="throughput", timing=True, W=333, H=219, scene=scene)]
+    vets = [ht.build(gh, s) for s in states]
+    k = -1
+
+    def where(j):
+        return lambda: "shared scene, operation %d (%s) through member %d, seen by member %d" % (k, " ".join(str(v) for v in ops[k]) if k >= 0 else "none", k % 2, j)
+
+    try:
+        vets[1].share_scene(vets[0])
+        for j in (0, 1):
+            compare_with_fresh(gh, vets[j], states[j], where(j))
+        for k, op in enumerate(ops):
+            actor, other = k % 2, 1 - k % 2
+            assert ht.vacuous(states[actor], op, oracle) is None, (k, op)
+            states[other] = ht.fold(states[other], ("camera", (7 * k + 3) % 120))
+            ht._frame(gh, vets[other], states[other])                       # in flight: the operation does not wait for it
+            ht.apply(gh, vets[actor], op, states[actor])
+            after = ht.fold(states[actor], op)
+            states = [replace(s, **{f: getattr(after, f) for f in SHARED_FIELDS}) for s in states]
+            edit = op[0] not in ht.SELECT_KINDS and op[0] != "reserve"
+            got = ht.apply(gh, vets[other], ("readback", "pick"), states[other], edited=edit)
+            assert ("refused" in got) == edit, (k, op, got)
+            seen = [compare_with_fresh(gh, vets[j], states[j], where(j)) for j in (0, 1)]
+            for name in ("scene_count()", "selection words", "selection count", "hidden words", "hidden count", "selection_bounds()"):
+                assert _same(seen[0][name], seen[1][name]), "%s: the members disagree on %s" % (where(1)(), name)
+            m = ht.materialise(states[0], oracle)
+            assert _same(seen[0]["selection words"], m.selection_words) and _same(seen[0]["hidden words"], m.hidden_words), where(0)()
+        assert vets[0].scene_sharing()[0] == 2
+    finally:
+        for vet in vets:
+            vet.dispose()
+
+
+def test_frames_in_flight_with_edits_have_no_memory(gh):
+    """test_frames_in_flight_have_no_memory with hides, duplicates and erases between the frames"""
+    pick = [("set_selection", (3, 0.3), "replace"), ("set_selection", (4, 0.1), "replace"), ("select_box", tuple(v * 0.5 for v in ht.BOX), "replace")]
+    plans = [
+        {1: [pick[0], ("hide", "add")], 3: [("duplicate", None)], 5: [("erase", False)], 6: [("set_hidden", None, "replace")], 7: [pick[1], ("duplicate", None)]},
+        {0: [("resize", 333, 219)], 2: [pick[2], ("duplicate", None)], 3: [("hide", "add")], 4: [("resize", 801, 601)], 5: [pick[1], ("erase", False)],
+         7: [("band", 256, 512)]},
+        {1: [pick[1], ("duplicate", None)], 2: [("duplicate", None)], 4: [("set_hidden", (5, 0.5), "replace")], 5: [pick[0], ("erase", True)], 6: [("set_hidden", (6, 0.5), "add")],
+         8: [("timing_interval", 2)]},
+    ]
+    states = [ht.State(kind="throughput", timing=True, scene=("synth", 20000, 9 + j, "rows")) for j in range(3)]
+    vets = [ht.build(gh, s) for s in states]
+    try:
+        for k in range(9):
+            for j, vet in enumerate(vets):
+                for op in plans[j].get(k, ()):
+                    ht.apply(gh, vet, op, states[j])
+                    states[j] = ht.fold(states[j], op)
+                states[j] = ht.fold(states[j], ("camera", (7 * k + 11 * j) % 120))
+                ht._frame(gh, vet, states[j])            # no wait: the next context's frame is issued behind it
+        for vet in vets:
+            vet.sync()
+        for j, vet in enumerate(vets):
+            assert states[j].edits and vet.scene_count() not in (0, 20000)
+            compare_with_fresh(gh, vet, states[j], lambda: "frames in flight with edits, context %d, plan %r" % (j, plans[j]))
+    finally:
+        for vet in vets:
+            vet.dispose()
+
+
+def test_the_editing_refusals_change_nothing_and_say_why(gh):
+    """the codes of EDIT_REFUSALS, each from the State it needs (the editing tour walks them with a frame behind each)"""
+    raw = ht.State(kind="default", scene=("synth", 2049, 5, "raw"))
+    rows = ht.State(kind="default", scene=("synth", 2049, 5, "rows"))
+    some = ("set_selection", (3, 0.5), "replace")
+    cases = {"edit_raw": (raw, [some], ht.GSR_ERR_ARG), "erase_raw": (raw, [some], ht.GSR_ERR_ARG),
+             "grow_with_sh": (rows, [("sh", (11, 0.0, 0.25, 0.5))], ht.GSR_ERR_ARG),
+             "rotate_selected_sh_follow": (rows, [some, ("sh", (11, 0.0, 0.25, 0.5))], ht.GSR_ERR_ARG),
+             "append_positions_differ": (rows, [], ht.GSR_ERR_SCENE)}
+    assert set(cases) == set(ht.EDIT_REFUSALS)
+    for which, (start, prelude, code) in cases.items():
+        r, s = ht.build(gh, start), start
+        try:
+            for op in prelude:
+                ht.apply(gh, r, op, s)
+                s = ht.fold(s, op)
+            cap = r.scene_capacity()
+            assert ht.apply(gh, r, ("refused", which), s)["code"] == code, which
+            assert (r.scene_count(), r.scene_capacity()) == (2049, cap) and r.sh_frame()[1] is False
+        finally:
+            r.dispose()
 
 
 def test_tour_on_the_bounds_checked_build(gh):

@@ -1,8 +1,15 @@
 """The traces of tests/history_trace.py, checked without a GPU: the builders are deterministic, the tour holds every operation,
 read-back, refusal and risky pair, every random walk the GPU tests use holds every kind of operation, and the State a trace ends
-in is the fold of its operations."""
+in is the fold of its operations.  The same for the editing layer's tour and walks -- and, through the oracle on the CPU, that none of
+their steps is vacuous (a hide hides something that shows, a region picks some but not all listed splats, an erase removes some but
+not all), that duplicates fall on both sides of the capacity, and that `materialise` is the references' chain."""
+import hashlib
+from dataclasses import replace
+
+import numpy as np
 import pytest
 
+import append_reference
 import history_trace as ht
 
 WALKS = [(seed, kind) for seed in (101, 202, 303) for kind in ("default", "throughput")]   # tests/test_gpu_history.py::test_random_walks
@@ -69,6 +76,243 @@ def test_every_walk_holds_every_kind_and_stays_cheap(seed, kind):
         s = ht.fold(s, st.op)
         assert ht.scene_n(s.scene) <= 20000 and s.W <= 900 and s.H <= 700
         assert s.band is None or (s.band[0] % 32 == 0 and s.band[0] < s.band[1] <= s.W)
+
+
+def _digest(trace):
+    return hashlib.sha256(ht.describe(trace).encode()).hexdigest()[:16]
+
+
+def test_the_old_traces_are_unchanged():
+    """describe() of tour() and of the walks over KINDS, digested on the commit before the editing layer joined the module"""
+    assert (_digest(ht.tour()), _digest(ht.tour(True))) == ("3adedddaafc32c89", "b067c35df2a4aac9")
+    want = {101: "d419ffae3778d0f8", 202: "5ae363d8e129a2d3", 303: "11d8bc4105fe7223"}
+    for seed, kind in WALKS:
+        assert _digest(ht.walk(seed, WALK_STEPS, _start(kind, seed))) == want[seed], (seed, kind)
+        assert ht.walk(seed, WALK_STEPS, _start(kind, seed), kinds=ht.KINDS) == ht.walk(seed, WALK_STEPS, _start(kind, seed))
+    assert ht.KINDS[0] == "camera" and ht.KINDS[-1] == "refused" and len(ht.KINDS) == 23 and len(ht.REFUSALS) == 4
+    assert not set(ht.KINDS) & set(ht.EDIT_KINDS) and not set(ht.REFUSALS) & set(ht.EDIT_REFUSALS)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the editing layer
+# ---------------------------------------------------------------------------------------------------------------------------
+EDIT_WALKS = [(seed, kind) for seed in (11, 22, 33) for kind in ("default", "throughput")]   # tests/test_gpu_history.py::test_editing_walks
+EDIT_WALK_STEPS = 150
+ALL_KINDS = ht.KINDS + ht.EDIT_KINDS
+_edit_walks = {}
+
+
+def _edit_walk(oracle, seed, kind):
+    if (seed, kind) not in _edit_walks:
+        _edit_walks[seed, kind] = ht.walk(seed, EDIT_WALK_STEPS, _start(kind, seed), kinds=ALL_KINDS, oracle=oracle)
+    return _edit_walks[seed, kind]
+
+
+def _capacities(start, trace, oracle):
+    """[(step, n before, capacity before, n after)] of the trace's duplicates, by the capacity rule of append_reference:
+    a scene's capacity is its count when it is set, the old count after a compaction, never shrinks otherwise"""
+    out, s, cap = [], start, None
+    for i, st in enumerate(trace):
+        n0 = ht.materialise(s, oracle).n
+        cap = n0 if cap is None else cap
+        s = ht.fold(s, st.op)
+        n1 = ht.materialise(s, oracle).n
+        kind = st.op[0]
+        if kind == "duplicate":
+            out.append((i, n0, cap, n1))
+        if kind == "scene":
+            cap = n1
+        elif kind in ("limit_box", "erase"):
+            cap = n0 if n1 < n0 else cap
+        elif kind == "reserve":
+            cap = max(cap, st.op[1])
+        elif kind in ("duplicate", "append_arrays"):
+            cap = append_reference.capacity_after(cap, n1)
+    return out
+
+
+def _assert_nothing_vacuous(start, trace, oracle):
+    s = start
+    for i, st in enumerate(trace):
+        why = ht.vacuous(s, st.op, oracle)
+        assert why is None, "step %d (%s) %s" % (i, " ".join(str(v) for v in st.op), why)
+        s = ht.fold(s, st.op)
+        if s.contrib:      # live accumulators: nothing moved the splats they describe
+            assert st.op[0] not in ht.MOVES_GEOMETRY, i
+        assert ht.materialise(s, oracle).n <= ht.MAX_GROWN
+        if s.edits and ht.scene_form(s.scene) == "raw":      # a raw scene takes pickers and hides only
+            assert {e[0] for e in s.edits} <= set(ht.SELECT_KINDS) | {"hide", "set_hidden"}
+        if s.ring_overlay:
+            assert s.ring is not None
+        if st.op[0] in ("duplicate", "append_arrays", "reserve"):
+            assert s.sh is None and ht.scene_form(s.scene) == "rows"
+
+
+def test_the_editing_builders_are_deterministic(oracle):
+    assert ht.editing_tour() == ht.editing_tour() and ht.editing_tour(True) == ht.editing_tour(True)
+    for seed, kind in EDIT_WALKS[:2]:
+        a = _edit_walk(oracle, seed, kind)
+        assert len(a) == EDIT_WALK_STEPS and a == ht.walk(seed, EDIT_WALK_STEPS, _start(kind, seed), kinds=ALL_KINDS, oracle=oracle)
+        assert ht.walk(seed, 41, _start(kind, seed), kinds=ALL_KINDS, oracle=oracle) == a[:41]
+    assert _edit_walk(oracle, 11, "default") != _edit_walk(oracle, 22, "default")
+
+
+@pytest.mark.parametrize("band_context", [False, True])
+def test_the_editing_tour_holds_every_kind_refusal_and_pair(oracle, band_context):
+    start = ht.State(band=(192, 448) if band_context else None)
+    t = ht.editing_tour(band_context)
+    kinds = {st.op[0] for st in t}
+    assert set(ht.EDIT_KINDS) <= kinds <= set(ALL_KINDS), set(ht.EDIT_KINDS) - kinds
+    assert {st.op[1] for st in t if st.op[0] == "refused"} == set(ht.EDIT_REFUSALS)
+    seen = ht.pairs_in(start, t)
+    for a, b, why in ht.EDIT_RISKY_PAIRS:
+        assert why
+        assert (a, b) in seen, (a, b)     # (on a band context too: the band is set again BEHIND a resize, which stays the neighbour)
+    # what the issue asks of the operations: both keep values, all four fold ops on a rectangle and on a byte mask, every kind of
+    # edit with and without a pivot, show-all, overlay on / other options / outline on and off / off
+    assert {st.op[1] for st in t if st.op[0] == "erase"} == {False, True}
+    regions = {(st.op[2] is not None, st.op[3]) for st in t if st.op[0] == "select_region"}
+    assert {op for _, op in regions} == set(ht.SELOPS) and {m for m, _ in regions} == {False, True}
+    edits = {(st.op[1], st.op[3] is not None) for st in t if st.op[0] == "edit"}
+    assert edits >= {("translate", False), ("rotate", False), ("rotate", True), ("scale", False), ("scale", True), ("rgba", False)}
+    assert {st.op[1] for st in t if st.op[0] == "hide"} >= {"add", "subtract"}
+    assert ("set_hidden", None, "replace") in [st.op for st in t]
+    overlays = [st.op for st in t if st.op[0] == "overlay"]
+    assert ("overlay", None) in overlays and {o[3] is not None for o in overlays if o[1] is not None} == {False, True}
+    assert len({o[1:3] for o in overlays if o[1] is not None}) > 1
+    # sizes and scenes stay small: four scene sizes from rows, at most 900 x 700 and one size above 4096 bins
+    ns = {ht.scene_n(st.op[1]) for st in t if st.op[0] == "scene"}
+    assert ns == {1, 33, 2049, 20000} and all(ht.scene_form(st.op[1]) == "rows" for st in t if st.op[0] == "scene")
+    sizes = {(st.op[1], st.op[2]) for st in t if st.op[0] == "resize"}
+    big = {z for z in sizes if z[0] > 900 or z[1] > 700}
+    assert len(big) == 1 and ht.bins_of(*next(iter(big))) > 4096
+    # unchecked steps keep the frame
+    assert all(st.check or st.op[0] in ht.KEEPS_FRAME + ht.EDIT_KEEPS_FRAME for st in t)
+    _assert_nothing_vacuous(start, t, oracle)
+    # the one delivery that is refused by design is asked for, and one behind it is delivered again
+    s, refused = start, []
+    for st in t:
+        if st.op[0] == "deliver":
+            refused.append(ht.overlay_ring_refuses(s))
+        s = ht.fold(s, st.op)
+    assert True in refused and refused[refused.index(True) + 1] is False
+    # duplicates on both sides of the capacity, and each on the side the trace says
+    dups = _capacities(start, t, oracle)
+    said = {i: st.op[1] for i, st in enumerate(t) if st.op[0] == "duplicate"}
+    for i, n0, cap, n1 in dups:
+        assert n1 > n0 and said[i] == ("fit" if n1 <= cap else "grow"), (i, n0, cap, n1, said[i])
+    assert {"fit", "grow"} <= set(said.values())
+    # past sort.rows (the largest count since the scene was set) and past a multiple of the 2048 keys of a radix block
+    i = next(i for i, st in enumerate(t) if st.op[0] == "duplicate" and t[i + 1].op[0] == "sort_only")
+    _, n0, _, n1 = next(d for d in dups if d[0] == i)
+    assert n1 > n0 and n1 // 2048 > n0 // 2048 and n0 % 2048 and n1 % 2048
+
+
+@pytest.mark.parametrize("seed,kind", EDIT_WALKS)
+def test_every_editing_walk_holds_every_kind_and_stays_cheap(oracle, seed, kind):
+    start = _start(kind, seed)
+    t = _edit_walk(oracle, seed, kind)
+    assert {st.op[0] for st in t} == set(ALL_KINDS), set(ALL_KINDS) ^ {st.op[0] for st in t}
+    assert {st.op[1] for st in t if st.op[0] == "refused"} & set(ht.EDIT_REFUSALS)
+    s = start
+    for st in t:
+        assert st.check or st.op[0] in ht.KEEPS_FRAME + ht.EDIT_KEEPS_FRAME
+        if st.op[0] == "ring_overlay" and st.op[1]:
+            assert s.ring is not None and s.overlay is not None
+        if st.op[0] == "select_contrib":
+            assert s.contrib                       # only where a pass has contributed
+        s = ht.fold(s, st.op)
+        assert s.W <= 900 and s.H <= 700
+    _assert_nothing_vacuous(start, t, oracle)
+
+
+def test_fold_is_pure_and_the_editing_tour_ends_where_it_says():
+    s0 = ht.State(kind="throughput")
+    t = ht.editing_tour()
+    s = ht.fold_all(s0, t)
+    assert ht.fold_all(s0, t) == s and s0 == ht.State(kind="throughput") and hash(s) == hash(ht.fold_all(s0, t))
+    # by hand, for the tail: the last scene, a selection set on it, SH on and off again, three refusals and their cameras
+    assert s.scene == ("synth", 2049, 6, "rows") and s.transforms == () and s.sh is None and s.pose == 70
+    assert s.edits == (("set_selection", (15, 0.5), "replace"),)
+    assert s.contrib is None and s.overlay is None and s.ring is None and s.ring_overlay is False and (s.W, s.H) == (640, 480)
+    # the rules of the fold, one by one
+    e = ("select_box", ht.BOX, "add")
+    assert ht.fold(s, e).edits == s.edits + (e,)
+    r = ht.fold(s, ("select_region", ht.RECT, None, "replace"))
+    assert r.edits[-1] == ("select_region", ht.RECT, None, "replace", (70, 640, 480, None, (False, 0.0)))
+    assert ht.fold(s, ("duplicate", "grow")).edits[-1] == ("duplicate",)
+    assert ht.fold(s, ("reserve", 5000)) == s and ht.fold(s, ("refused", "edit_raw")) == s
+    assert ht.fold(s, ("rotate", ht.QUAT)).edits[-1] == ("transform", "rotate", ht.QUAT) and ht.fold(s, ("rotate", ht.QUAT)).transforms == ()
+    assert ht.fold(replace(s, edits=()), ("rotate", ht.QUAT)).transforms == (("rotate", ht.QUAT),)
+    c = ht.fold(ht.fold(s, ("contrib_pass",)), ("contrib_pass",))
+    assert c.contrib == ((70, 640, 480, None, (False, 0.0), 1),) * 2 and ht.fold(c, ("contrib_reset",)).contrib == ()
+    for op in (("erase", False), ("limit_box", ht.BOX), ("scene", ("synth", 33, 1, "rows"))):
+        assert ht.fold(c, op).contrib is None
+    assert ht.fold(c, ("scene", ("synth", 33, 1, "rows"))).edits == ()
+    o = ht.fold(s, ("overlay", (1.0, 0.5, 0.0), 0.5, None))
+    assert o.overlay == ((1.0, 0.5, 0.0), 0.5, None) and ht.fold(o, ("overlay", None)).overlay is None
+    g = ht.fold(ht.fold(o, ("ring_open", "rgba8", False, None, 1)), ("ring_overlay", True))
+    assert g.ring_overlay and ht.fold(g, ("resize", 320, 200)).ring_overlay and not ht.fold(g, ("ring_close",)).ring_overlay
+    # the ring's switch stays when the options go: the one State whose deliveries are refused, until options return
+    off = ht.fold(g, ("overlay", None))
+    assert off.ring_overlay and off.overlay is None and ht.overlay_ring_refuses(off) and not ht.overlay_ring_refuses(g)
+    assert not ht.overlay_ring_refuses(ht.fold(off, ("overlay", (0.0, 0.0, 1.0), 1.0, None))) and not ht.overlay_ring_refuses(ht.fold(off, ("ring_overlay", False)))
+    assert ht.fold(ht.fold(s, ("sh", (1, 0.0, 0.5, 0.5))), ("erase", True)).sh is None
+
+
+def test_materialise_agrees_with_the_references_by_hand(oracle):
+    import gsplat_hip as gh
+    import edit_reference as er
+    import hide_reference as hr
+    import select_reference as sr
+    import attr_reference as at
+    s = ht.State(scene=("synth", 300, 7, "rows"), transforms=(("translate", (0.25, 0.0, -0.5)),), pose=9)
+    ops = [("select_box", tuple(v * 0.5 for v in ht.BOX), "replace"), ("edit", "rotate", ht.QUAT, ht.PIVOT), ("hide", "add"),
+           ("select_attr", "opacity", 0.0, 128.0, None, "replace"), ("select_region", ht.RECT, None, "add"), ("duplicate", None),
+           ("edit", "rgba", (0x11223344, 0x00ff00ff), None), ("append_arrays", 5, 3), ("invert_selection",), ("scale", (1.0, 2.0, 1.0)),
+           ("erase", True), ("set_hidden", (4, 0.5), "subtract"), ("select_hidden", "replace")]
+    m = ht.materialise(ht.fold_ops(s, ops), oracle)
+    # the same chain, written out
+    st = oracle.SceneState(gh.synth.synth_rows(300, 7))
+    st.translate((0.25, 0.0, -0.5))
+    S = sr.box_pick(st.positions, tuple(v * 0.5 for v in ht.BOX))
+    assert 0 < S.sum() < 300
+    er.apply(st, S, "rotate", ht.QUAT, ht.PIVOT)
+    H = hr.hide_selected(np.zeros(300, bool), S, "add")
+    S = at.select(at.attr_value("opacity", data=st.data), 0.0, 128.0)
+    cam = gh.orbit_camera(9, 120, 640, 480, fx=0.59 * 640)
+    v, p, _ = cam.f32()
+    rec, bbox, _ = oracle.project(st.data, v, p, cam.fx, cam.fy, 640, 480)
+    P = sr.centre_pick(rec, hr.hide_bbox(bbox, H), ht.RECT)
+    assert P.any() and not (P & H).any()
+    S = S | P
+    k = int(S.sum())
+    first, count = append_reference.duplicate(st, S)
+    assert (first, count) == (300, k)
+    S, H = append_reference.selection_after(st.n, first, count), append_reference.hidden_after(H, count)
+    er.paint(st, S, 0x11223344, 0x00ff00ff)
+    add = oracle.SceneState(gh.synth.synth_rows(5, 3))
+    first, count = append_reference.append_arrays(st, add.data, add.positions, add.rotations, add.scales)
+    S, H = append_reference.selection_after(st.n, first, count), append_reference.hidden_after(H, count)
+    S = ~S
+    st.scale((1.0, 2.0, 1.0))
+    H = hr.compact(H, S)
+    append_reference.erase(st, ~S)
+    S = np.zeros(st.n, bool)
+    H = hr.hidden_set(H, np.random.default_rng(4).random(st.n) < 0.5, "subtract")
+    S = hr.select_hidden(S, H, "replace")
+    assert st.n == 300 + k and m.n == st.n and H.any()
+    for name in ("data", "positions", "rotations", "scales"):
+        a, b = getattr(m, name), getattr(st, name)
+        assert a.dtype == b.dtype and np.array_equal(a.view(np.uint32), b.view(np.uint32)), name
+    assert np.array_equal(m.selection_words, sr.pack(S)) and np.array_equal(m.hidden_words, sr.pack(H))
+    # memoised on the prefixes: a longer recipe starts from this one, and the cached value is not the caller's to change
+    m.data[:] = 0
+    assert np.array_equal(ht.materialise(ht.fold_ops(s, ops), oracle).data.view(np.uint32), st.data.view(np.uint32))
+    # without edits: the scene as it is set
+    m0 = ht.materialise(ht.State(scene=("synth", 33, 2, "rows")), oracle)
+    assert m0.n == 33 and not m0.selection_words.any() and not m0.hidden_words.any()
+    assert np.array_equal(m0.data, oracle.SceneState(gh.synth.synth_rows(33, 2)).data)
 
 
 def test_the_final_state_is_the_fold_of_the_operations():
