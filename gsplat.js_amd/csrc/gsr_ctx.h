@@ -503,6 +503,20 @@ struct gsr_ctx {
         gsr::DevBuf<uint32_t> words;        // ATTR_HIST_WORDS histogram counters, then ATTR_MAX_GRID + 1 AttrStats (the partials, the result)
     } attr;
 
+    // neighbours (gsr_neighbours.cpp): the device scratch of gsr_neighbours / gsr_select_neighbours, the context's own; the first
+    // call allocates it, it only grows, and the context's end frees it
+    struct Neighbours {
+        gsr::DevBuf<uint32_t> words;            // NB_INFO_WORDS of NbInfo, then NB_MAX_CAP + 1 histogram counters
+        gsr::DevBuf<uint32_t> table;            // 2 words per bucket
+        uint64_t buckets = 0;                   // buckets `table` was allocated for
+        gsr::DevBuf<uint4> entry;               // `rows` each: the index's entries, their cell keys, the counts by splat
+        gsr::DevBuf<unsigned long long> key;
+        gsr::DevBuf<uint32_t> counts;
+        uint32_t rows = 0;
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // in front of the build, behind the bound, behind the count
+        float build_ms = 0.0f, count_ms = 0.0f;           // of the last call that ran both (gsr_debug_neighbour_times)
+    } nb;
+
     // frame delivery (gsr_delivery_open): a ring of pinned host blocks, each with its device staging and "copy done" event
     struct Delivery {
         struct Slot {

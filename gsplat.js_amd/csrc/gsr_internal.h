@@ -567,6 +567,40 @@ void launch_attr_hist(int attr, const AttrSource& src, const AttrScope& sc, uint
 // scratch <- the splats i < n with lo <= value < hi: every word of it is stored, no zeroing needed
 void launch_attr_select(int attr, const AttrSource& src, uint32_t n, double lo, double hi, uint32_t* scratch, uint32_t nwords, hipStream_t s);
 
+// Neighbours (k_neighbours.hip; DESIGN.md section 4, "Neighbours"): for every splat in scope, how many others in scope lie within
+// `radius` of it, through a hashed uniform grid built on the device for the one call.  Cell side h = radius * (1 + 2^-10); a cell
+// coordinate is floor((double)x * inv_h) clamped to [-NB_CELL_HALF, NB_CELL_HALF); three of them pack into the 63-bit cell key.
+constexpr uint32_t NB_MAX_CAP = 4095;                       // GSR_NEIGHBOUR_MAX_CAP: cap + 1 LDS counters of 4 bytes, 16 KB at most
+constexpr int32_t NB_CELL_HALF = 1 << 20;                   // 21 bits per axis
+constexpr uint32_t NB_WG_PER_CU = 8;                        // workgroups of the walks (bound, count) per compute unit
+constexpr uint32_t NB_MAX_GRID = 4096;                      // and at most
+// the device words of one call: zeroed by the host in front of the build
+struct NbInfo {
+    uint32_t in_scope, nonfinite;          // splats in scope; of those, with a NaN or infinite position component
+    uint32_t indexed, pad;                 // the index's entries (k_nb_offsets' cursor): in_scope - nonfinite
+    unsigned long long pair_bound;         // k_nb_bound's sum
+};
+struct NbIndex {
+    uint32_t* table;                       // 2 * buckets words: [2b] the bucket's population, [2b + 1] its cursor -- the bucket's first
+                                           // entry after k_nb_offsets, one behind its last after k_nb_scatter
+    uint32_t bucket_mask;                  // buckets - 1, a power of two >= 2 n
+    uint4* entry;                          // n: (bits of x, y, z, the splat's index), bucket by bucket
+    unsigned long long* key;               // n: the entry's cell key
+    NbInfo* info;
+    double inv_h, r2;
+};
+// the index of the splats in scope with finite positions, info->in_scope / nonfinite / indexed, and hist0 += nonfinite (null: no
+// histogram); table and *info zeroed by the caller.  n >= 1.
+void launch_nb_build(const NbIndex& ix, const float* px, const float* py, const float* pz, const AttrScope& sc, uint32_t n, int cu_count, uint32_t* hist0,
+                     hipStream_t s);
+// info->pair_bound += for every entry the populations of the 27 buckets the count pass walks for it
+void launch_nb_bound(const NbIndex& ix, uint32_t n, int cu_count, hipStream_t s);
+// counts[index] = min(cap, neighbours) for every entry (the other words are the caller's zeros); hist (null: none), cap + 1 words
+// zeroed by the caller but for hist0's share, += the entries by their count.  indexed: info->indexed as the host read it; n: the splats.
+void launch_nb_count(const NbIndex& ix, uint32_t indexed, uint32_t n, uint32_t cap, uint32_t* counts, uint32_t* hist, int cu_count, hipStream_t s);
+// scratch <- the splats i < n in scope with lo <= counts[i] < hi: every word of it is stored, no zeroing needed
+void launch_nb_select(const uint32_t* counts, const AttrScope& sc, uint32_t n, uint32_t lo, uint32_t hi, uint32_t* scratch, uint32_t nwords, hipStream_t s);
+
 // Selection overlay (k_overlay.hip; DESIGN.md section 4, "Selection overlay"): the last frame's bin lists walked once more, the
 // weight w = T * B of every fragment of a SELECTED splat summed per pixel (cover) and, with the splat's colour, turned into the
 // frame with those splats tinted (overlay).  Reads the framebuffer, never writes it.

@@ -97,6 +97,9 @@ export type SplatAttribute = "x" | "y" | "z" | "distance" | "red" | "green" | "b
     "contrib_weight" | "contrib_peak" | "contrib_pixels";
 export interface SplatScope { origin?: ArrayLike<number> | { x: number; y: number; z: number } | null; selected?: boolean; visible?: boolean }
 export interface SplatStats { count: number; nan: number; min: number; max: number }
+export type NeighbourScope = "selected" | "visible";
+export interface NeighbourOptions { cap?: number; scope?: NeighbourScope | NeighbourScope[]; budget?: number }
+export interface SplatNeighbours { counts: Uint32Array; hist: Uint32Array; inScope: number; nonfinite: number; pairBound: number }
 export interface SplatHistogram { counts: Uint32Array; below: number; above: number; nan: number; edges: Float64Array }
 export interface Contribution { weight: BigUint64Array; peak: Float32Array; pixels: Uint32Array; frames: number }
 /** A screen region: the pixels [x0, x1) x [y0, y1), optionally one byte per pixel of the rectangle (non-zero = inside; rows
@@ -368,6 +371,17 @@ export class HIPRenderer {
     splatHistogram(attr: SplatAttribute, options: SplatScope & { lo: number; hi: number; bins?: number }): SplatHistogram;
     selectAttribute(attr: SplatAttribute, options?: { lo?: number; hi?: number; origin?: SplatScope["origin"]; op?: SelectOp }): number;
     static attrEdges(lo: number, hi: number, bins: number): Float64Array;
+    /** Neighbours: for every splat in scope (scope: "selected", "visible" or both; none: every splat) the number of OTHER splats in
+     *  scope within `radius` of it -- f64, distance exactly radius counts, a splat never counts itself -- at most `cap` (1 .. 4095,
+     *  default 64); 0 outside the scope.  splatNeighbours: counts per splat, hist[k] = the splats in scope with k neighbours
+     *  (hist[cap]: cap or more; the histogram sums to inScope), nonfinite = splats in scope with a NaN or infinite position (count 0),
+     *  pairBound = the most pair tests the count pass makes.  selectNeighbours picks lo <= count < hi (below: { lo: 0, hi: below };
+     *  default hi cap + 1) and folds them into the selection with `op`, returning the number of selected splats: with "replace"
+     *  exactly hist.slice(lo, hi) summed.  selectNeighbours(r, { below: k }) then Scene.eraseSelection(readSelection()) is the radius
+     *  outlier filter.  Both index the device scene as it is now.  budget: the most pair tests a call may make (default 2^34, at
+     *  most 2^38); a radius that needs more throws before the count pass runs, with both numbers in the message. */
+    splatNeighbours(radius: number, options?: NeighbourOptions): SplatNeighbours;
+    selectNeighbours(radius: number, options?: NeighbourOptions & { below?: number; lo?: number; hi?: number; op?: SelectOp }): number;
     dispose(): void;
     /** RGBA8, row 0 = top, round(clamp(x,0,1)*255), premultiplied alpha */
     /** RGBA8, row 0 = top; pass an array of width*height*4 elements to have it filled and returned (no allocation per frame). */

@@ -1424,6 +1424,72 @@ napi_value SelectAttr(napi_env env, napi_callback_info info)
     return rc ? throw_gsr(env, c, rc, "gsr_select_attr") : count_value(env, count);
 }
 
+// ---- neighbours (gsr_neighbours / gsr_select_neighbours) ----
+// radius, cap, scope and budget of the two calls below (argv[1 .. 4]; the budget a number, 0: the library's default); false: an
+// error is pending
+bool get_neighbour_args(napi_env env, napi_value* argv, double* radius, uint32_t* cap, uint32_t* scope, uint64_t* budget)
+{
+    double b;
+    if (!get_f64(env, argv[1], radius) || napi_get_value_uint32(env, argv[2], cap) != napi_ok || napi_get_value_uint32(env, argv[3], scope) != napi_ok ||
+        !get_f64(env, argv[4], &b)) {
+        napi_throw_type_error(env, nullptr, "neighbours: radius, cap, scope and budget must be numbers");
+        return false;
+    }
+    if (*cap < 1 || *cap > GSR_NEIGHBOUR_MAX_CAP) { napi_throw_range_error(env, nullptr, "neighbours: cap must be in 1 .. 4095"); return false; }
+    if (!(b >= 0.0 && b <= 18446744073709549568.0)) { napi_throw_range_error(env, nullptr, "neighbours: budget must be a non-negative number"); return false; }
+    *budget = (uint64_t)b;
+    return true;
+}
+
+// neighbours(handle, radius, cap, scope, budget) -> { counts: Uint32Array(n), hist: Uint32Array(cap + 1), inScope, nonfinite, pairBound, budget }
+napi_value Neighbours(napi_env env, napi_callback_info info)
+{
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    double radius;
+    uint32_t cap, scope, n = 0;
+    uint64_t budget;
+    if (!c || !get_neighbour_args(env, argv, &radius, &cap, &scope, &budget)) return nullptr;
+    int rc = gsr_scene_count(c, &n);
+    if (rc) return throw_gsr(env, c, rc, "gsr_scene_count");
+    void *counts = nullptr, *hist = nullptr;
+    napi_value cb, carr, hb, harr, out;
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, (size_t)n * 4, &counts, &cb));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_uint32_array, n, cb, 0, &carr));
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, ((size_t)cap + 1) * 4, &hist, &hb));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_uint32_array, (size_t)cap + 1, hb, 0, &harr));
+    gsr_neighbour_info ni{};
+    rc = gsr_neighbours(c, radius, cap, scope, budget, n ? (uint32_t*)counts : nullptr, n, (uint32_t*)hist, &ni);
+    if (rc) return throw_gsr(env, c, rc, "gsr_neighbours");
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "counts", carr));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "hist", harr));
+    if (!set_u32(env, out, "inScope", ni.in_scope) || !set_u32(env, out, "nonfinite", ni.nonfinite) || !set_f64(env, out, "pairBound", (double)ni.pair_bound) ||
+        !set_f64(env, out, "budget", (double)ni.budget)) return nullptr;
+    return out;
+}
+
+// selectNeighbours(handle, radius, cap, scope, budget, lo, hi, op) -> selected
+napi_value SelectNeighbours(napi_env env, napi_callback_info info)
+{
+    napi_value argv[8];
+    if (!get_args(env, info, 8, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    double radius;
+    uint32_t cap, scope, lo, hi;
+    uint64_t budget;
+    int32_t op;
+    if (!c || !get_neighbour_args(env, argv, &radius, &cap, &scope, &budget)) return nullptr;
+    if (napi_get_value_uint32(env, argv[5], &lo) != napi_ok || napi_get_value_uint32(env, argv[6], &hi) != napi_ok || !get_i32(env, argv[7], &op)) {
+        napi_throw_type_error(env, nullptr, "selectNeighbours: lo, hi and op must be numbers");
+        return nullptr;
+    }
+    uint32_t count = 0;
+    const int rc = gsr_select_neighbours(c, radius, cap, scope, budget, lo, hi, op, &count, nullptr);
+    return rc ? throw_gsr(env, c, rc, "gsr_select_neighbours") : count_value(env, count);
+}
+
 // ---- selection overlay (gsr_set_overlay / gsr_overlay_async / gsr_read_overlay* / gsr_delivery_set_overlay) ----
 // setOverlay(handle, on, r, g, b, mix): on = 0 switches the overlay off (the other arguments are not read)
 napi_value SetOverlay(napi_env env, napi_callback_info info)
@@ -1539,6 +1605,7 @@ napi_value Init(napi_env env, napi_value exports)
         {"contribReset", Call0<gsr_contrib_reset>}, {"contribAccumulate", Call0<gsr_contrib_accumulate_async>}, {"readContrib", ReadContrib},
         {"selectContrib", SelectContrib},
         {"attrStats", AttrStats}, {"attrHistogram", AttrHistogram}, {"selectAttr", SelectAttr},
+        {"neighbours", Neighbours}, {"selectNeighbours", SelectNeighbours},
         {"setOverlay", SetOverlay}, {"readOverlay", ReadOverlay}, {"readOverlayPixels", ReadOverlayPixels},
         {"deliverySetOverlay", DeliverySetOverlay}, {"setOutline", SetOutline},
     };

@@ -538,6 +538,37 @@ class HIPRenderer {
             const lo = o2.lo === undefined ? -Infinity : Number(o2.lo), hi = o2.hi === undefined ? Infinity : Number(o2.hi);
             return this._n.selectAttr(this._h, code(ATTRS, attr, undefined, "attr"), originOf(o2), lo, hi, code(OPS, o2.op, "replace", "op"));
         };
+        // ---- neighbours (gsr_neighbours / gsr_select_neighbours): how many other splats lie within a radius of each ----
+        //   renderer.selectNeighbours(0.05, { below: 3 }); scene.eraseSelection(renderer.readSelection());   // floaters: fewer than 3 neighbours within 0.05
+        //   const { counts, hist } = renderer.splatNeighbours(0.05, { cap: 64 });       // hist[k]: splats with k neighbours, hist[cap]: cap or more
+        // A splat's count is the number of OTHER splats in scope within `radius` of it (f64, distance exactly radius counts), at most
+        // `cap` (1 .. 4095, default 64); scope: "selected", "visible" or both -- counted among and reported for those only.
+        // selectNeighbours picks lo <= count < hi (below: hi with lo 0; default hi cap + 1) and returns the selected count; with op
+        // "replace" exactly hist.slice(lo, hi) summed.  Both index the device scene as it is now.  budget: the most pair tests the
+        // call may make (default 2^34); a radius that would need more throws before the count pass runs.
+        const NB_SCOPES = { selected: 1, visible: 2 };
+        const nbScope = (o) => {
+            const names = o.scope === undefined || o.scope === null ? [] : (typeof o.scope === "string" ? [o.scope] : Array.from(o.scope));
+            return names.reduce((m, name) => m | code(NB_SCOPES, name, undefined, "scope"), 0);
+        };
+        const nbArgs = (radius, o) => {
+            const cap = o.cap === undefined ? 64 : o.cap, budget = o.budget === undefined || o.budget === null ? 0 : Number(o.budget);
+            if (!Number.isInteger(cap) || cap < 1 || cap > 4095) throw new Error("cap must be an integer in 1 .. 4095");
+            if (!(budget >= 0)) throw new Error("budget must be a non-negative number");
+            return [Number(radius), cap, nbScope(o), budget];
+        };
+        this.splatNeighbours = (radius, options) => {
+            const o2 = options || {};
+            const r = this._n.neighbours(this._h, ...nbArgs(radius, o2));
+            return { counts: r.counts, hist: r.hist, inScope: r.inScope, nonfinite: r.nonfinite, pairBound: r.pairBound };
+        };
+        this.selectNeighbours = (radius, options) => {
+            const o2 = options || {}, args = nbArgs(radius, o2), cap = args[1];
+            const lo = o2.lo === undefined ? 0 : o2.lo, hi = o2.below !== undefined ? o2.below : o2.hi === undefined ? cap + 1 : o2.hi;
+            if (o2.below !== undefined && (o2.hi !== undefined || o2.lo !== undefined)) throw new Error("selectNeighbours: below goes alone (it is { lo: 0, hi: below })");
+            if (!Number.isInteger(lo) || !Number.isInteger(hi) || lo < 0 || lo > hi || hi > cap + 1) throw new Error("selectNeighbours: 0 <= lo <= hi <= cap + 1 must hold");
+            return this._n.selectNeighbours(this._h, ...args, lo, hi, code(OPS, o2.op, "replace", "op"));
+        };
         // ---- selection overlay (gsr_set_overlay / gsr_read_overlay*): the last frame with the selected splats tinted ----
         //   renderer.setSelectionOverlay({ tint: [1, 0.5, 0], mix: 0.5 }); renderer.render(scene, cam);
         //   const { rgba, cover } = renderer.readOverlay();   // or readPixels({ overlay: true }), or openDelivery(n, { overlay: true })

@@ -79,6 +79,13 @@ class GsrOutlineOptions(ctypes.Structure):
                 ("side", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
 
 
+class GsrNeighbourInfo(ctypes.Structure):
+    _fields_ = [("in_scope", ctypes.c_uint32), ("nonfinite", ctypes.c_uint32), ("pair_bound", ctypes.c_uint64), ("budget", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class GsrDepthLayout(ctypes.Structure):
     _fields_ = [("format", ctypes.c_int32), ("step", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
                 ("stride", ctypes.c_int32), ("reserved", ctypes.c_int32), ("offset", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
@@ -97,6 +104,8 @@ ATTRS = {"x": 0, "y": 1, "z": 2, "distance": 3, "red": 4, "green": 5, "blue": 6,
          "scale_min": 11, "scale_max": 12, "contrib_weight": 13, "contrib_peak": 14, "contrib_pixels": 15}   # GSR_ATTR_*
 SCOPES = {"selected": 1, "visible": 2}                                     # GSR_SCOPE_*
 ATTR_MAX_BINS = 4096
+NEIGHBOUR_MAX_CAP = 4095                                                   # GSR_NEIGHBOUR_MAX_CAP
+NEIGHBOUR_DEFAULT_BUDGET, NEIGHBOUR_MAX_BUDGET = 1 << 34, 1 << 38          # GSR_NEIGHBOUR_*_BUDGET
 
 
 def attr_edges(lo, hi, bins):
@@ -148,6 +157,7 @@ EXPORTS = [
     "gsr_scene_reserve", "gsr_scene_capacity", "gsr_scene_duplicate_selected", "gsr_scene_append_selected", "gsr_scene_append_arrays",
     "gsr_contrib_reset", "gsr_contrib_accumulate_async", "gsr_read_contrib", "gsr_select_contrib",
     "gsr_attr_stats", "gsr_attr_histogram", "gsr_select_attr",
+    "gsr_neighbours", "gsr_select_neighbours",
     "gsr_set_overlay", "gsr_overlay_async", "gsr_read_overlay", "gsr_read_overlay_rgba8", "gsr_overlay_device_ptr", "gsr_delivery_set_overlay",
     "gsr_set_overlay_outline",
 ]
@@ -311,6 +321,10 @@ def load_library(path=None):
     L.gsr_attr_stats.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_uint32, u32p, u32p, f64p, f64p]
     L.gsr_attr_histogram.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_uint32, vp, vp]
     L.gsr_select_attr.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_double, ctypes.c_double, ctypes.c_int32, u32p]
+    u64 = ctypes.c_uint64
+    L.gsr_neighbours.argtypes = [vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, vp, ctypes.c_uint32, vp, ctypes.POINTER(GsrNeighbourInfo)]
+    L.gsr_select_neighbours.argtypes = [vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, u32p,
+                                        ctypes.POINTER(GsrNeighbourInfo)]
     L.gsr_set_overlay.argtypes = [vp, ctypes.POINTER(GsrOverlayOptions)]
     L.gsr_set_overlay_outline.argtypes = [vp, ctypes.POINTER(GsrOutlineOptions)]
     L.gsr_overlay_async.argtypes = [vp]
@@ -1137,6 +1151,63 @@ class HIPRenderer:
         self._check(self._L.gsr_select_attr(self._ctx, self._select_code(ATTRS, attr, "attr"), None if o is None else o.ctypes.data,
                                             float(lo), float(hi), self._select_code(SELECT_OPS, op, "op"), ctypes.byref(count)))
         return count.value
+
+    # -- neighbours (gsr_neighbours / gsr_select_neighbours): how many other splats lie within a radius of each; floaters have none --
+    @staticmethod
+    def _scope_flags(scope):
+        names = (scope,) if isinstance(scope, str) else tuple(scope)
+        for name in names:
+            if name not in SCOPES:
+                raise ValueError("unknown scope %r (one of %s)" % (name, ", ".join(SCOPES)))
+        return sum(SCOPES[name] for name in set(names))
+
+    @staticmethod
+    def _neighbour_args(radius, cap, budget):
+        cap = int(cap)
+        if not 1 <= cap <= NEIGHBOUR_MAX_CAP:
+            raise ValueError("cap must be in 1 .. %d" % NEIGHBOUR_MAX_CAP)
+        budget = 0 if budget is None else int(budget)
+        if budget < 0:
+            raise ValueError("budget must not be negative")
+        return float(radius), cap, budget
+
+    def neighbours(self, radius, cap=64, scope=(), budget=None, counts=True, hist=True):
+        """(counts uint32[n], hist uint32[cap + 1], info): for every splat in scope -- scope: any of "selected", "visible"; () is
+        every splat -- the number of OTHER splats in scope within `radius` of it (f64, distance exactly radius counts), at most
+        `cap`; 0 outside the scope.  hist[k]: the splats in scope with count == k, hist[cap] "cap or more"; hist.sum() ==
+        info["in_scope"].  counts=False / hist=False: None in its place, nothing copied.  info: in_scope, nonfinite, pair_bound,
+        budget.  budget=None is the library's default; a call whose pair_bound lies above it is refused (GsplatError) before
+        the count pass runs, and the error carries `info`."""
+        radius, cap, budget = self._neighbour_args(radius, cap, budget)
+        n = self._count()
+        c = np.zeros(n, np.uint32) if counts else None
+        h = np.zeros(cap + 1, np.uint32) if hist else None
+        info = GsrNeighbourInfo()
+        self._check_neighbours(self._L.gsr_neighbours(self._ctx, radius, cap, self._scope_flags(scope), budget, c.ctypes.data if counts and n else None, n if counts else 0,
+                                                      h.ctypes.data if hist else None, ctypes.byref(info)), info)
+        return c, h, info.as_dict()
+
+    def select_neighbours(self, radius, lo=0, hi=None, cap=64, scope=(), op="replace", budget=None):
+        """(selected, info): pick the splats in scope with lo <= count < hi (hi=None: cap + 1, "lo or more") and fold them into the
+        selection; counts as neighbours() gives them.  select_neighbours(r, hi=k) then scene_erase_selected() is the radius
+        outlier filter: every splat with fewer than k neighbours within r goes.  With op "replace" it selects exactly
+        hist[lo:hi].sum() splats of neighbours(radius, cap, scope)."""
+        radius, cap, budget = self._neighbour_args(radius, cap, budget)
+        hi = cap + 1 if hi is None else int(hi)
+        lo = int(lo)
+        if not 0 <= lo <= hi <= cap + 1:
+            raise ValueError("lo <= hi <= cap + 1 must hold")
+        count, info = ctypes.c_uint32(0), GsrNeighbourInfo()
+        self._check_neighbours(self._L.gsr_select_neighbours(self._ctx, radius, cap, self._scope_flags(scope), budget, lo, hi, self._select_code(SELECT_OPS, op, "op"),
+                                                             ctypes.byref(count), ctypes.byref(info)), info)
+        return count.value, info.as_dict()
+
+    def _check_neighbours(self, rc, info):
+        try:
+            self._check(rc)
+        except GsplatError as e:
+            e.info = info.as_dict()   # (a call refused for its budget has filled it)
+            raise
 
     # -- selection overlay (gsr_set_overlay / gsr_overlay_async / gsr_read_overlay*): the selected splats tinted --
     def set_overlay(self, tint=(1.0, 0.5, 0.0), mix=0.5):

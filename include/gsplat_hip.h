@@ -821,6 +821,63 @@ int gsr_attr_histogram(gsr_ctx *ctx, int32_t attr, const double *origin, uint32_
 int gsr_select_attr(gsr_ctx *ctx, int32_t attr, const double *origin, double lo, double hi,
                     int32_t op, uint32_t *selected);
 
+/* ---- neighbours ---- how many other splats lie within a radius of each splat: floaters found by local density
+ * No interface of the reference stands behind this section either.  Every picker above judges a splat alone; the clean-up every
+ * captured scene needs first is floaters -- isolated splats hanging in empty space -- and what marks a floater is no attribute of
+ * its own: it has no neighbours.  Point-cloud tools call the operation radius outlier removal: count the points within r of each
+ * point and drop those with fewer than k.  These two calls do it on the device, with no gsr_read_scene and no spatial index on
+ * the host:  gsr_select_neighbours(ctx, r, cap, 0, 0, 0, k, GSR_SELOP_REPLACE, ..) then gsr_scene_erase_selected.
+ * Definition ("Neighbours").  Scope S is the GSR_SCOPE_SELECTED | GSR_SCOPE_VISIBLE flags of "splat data",
+ * with the same meaning; 0 is every splat.  For splats i, j of the scene, in f64, in the written order, uncontracted:
+ *     dx = (double)x_i - (double)x_j;  dy, dz likewise
+ *     d2(i,j) = (dx*dx + dy*dy) + dz*dz
+ *     r2 = radius * radius                      (computed once on the host)
+ *     near(i,j)  :=  i != j  &&  d2(i,j) <= r2
+ *     count_i = min(cap, #{ j in S : near(i,j) })   for i in S;      count_i = 0   for i not in S
+ *   d2 is symmetric.  Distance exactly radius counts.  Coincident splats count each other.  A splat does not count itself.  A NaN
+ *   or infinite position component needs no special case: the comparison is false, so such a splat has count 0 and is nobody's
+ *   neighbour (it is kept out of the index).  Counts are integers decided by f64 comparisons, so every result is exact and
+ *   independent of the order of arrival.
+ * gsr_neighbours: counts is n words or NULL; a non-NULL counts with n not equal to the scene's count is refused.  hist is cap + 1
+ *   words or NULL: hist[k] is the number of splats in S with count == k, so hist[cap] means "cap or more", and
+ *   sum(hist) == info->in_scope.  info may be NULL.  An empty scene, or an empty scope, returns zeros.
+ * gsr_select_neighbours picks P = { i in S : lo <= count_i && count_i < hi }, with lo <= hi <= cap + 1, and folds P into the
+ *   selection with `op` (GSR_SELOP_*) exactly as the selection calls fold theirs; `selected` means what it means everywhere else.
+ *   lo == hi picks nothing.
+ * The consistency guarantee: with GSR_SELOP_REPLACE it selects exactly sum(hist[lo .. hi-1]) splats of a gsr_neighbours call with
+ *   the same radius, cap and scope: what the histogram shows is what the range selects.
+ * info: in_scope = the splats in S; nonfinite = those of them with a NaN or infinite position component (count 0, in hist[0]);
+ *   pair_bound and budget as below.
+ * The work budget.  These machines are shared and a radius that puts the whole scene into one cell is an O(n^2) kernel.  Both calls
+ *   build the index first -- a hashed uniform grid of cells a little wider than radius -- and a cheap pass then computes pair_bound:
+ *   for every indexed splat, the sum of the populations of the 27 hash buckets the count pass walks for it, i.e. the pair tests the
+ *   count pass makes at most (no early exit), as the implementation counts them; it is never below the exact 27-cell neighbourhood
+ *   sum.  If pair_bound > budget the call returns GSR_ERR_ARG with a message naming both numbers; it fills info and launches no
+ *   count kernel.  budget == 0 means GSR_NEIGHBOUR_DEFAULT_BUDGET; a budget above GSR_NEIGHBOUR_MAX_BUDGET is refused.
+ * Both calls are blocking and stateless: they index the scene as it is now, so nothing can go stale after an edit.  They are
+ *   ordered like gsr_select_attr: they wait for every member's stream of a shared scene first.  They read the scene and write none
+ *   of it: no frame state changes.
+ * Refusals (GSR_ERR_ARG with a message, nothing touched, the selection and its count included): a NULL ctx; a radius that is not
+ *   finite, not > 0, or with radius * radius or 1 / radius not finite and normal; cap outside 1 .. 4095; unknown scope flags or op;
+ *   lo > hi or hi > cap + 1; a budget above the maximum; a bound above the budget.
+ * The device scratch belongs to the context: the index (8 bytes per hash bucket, a power of two of at least twice the scene's
+ *   count, and 24 bytes per splat), the counts (4 bytes per splat) and a histogram of at most 4096 counters.  The first call
+ *   allocates it, it only grows, and gsr_destroy frees it; a context that never calls any of this allocates nothing and launches
+ *   nothing. */
+typedef struct gsr_neighbour_info {
+    uint32_t in_scope;      /* splats in S */
+    uint32_t nonfinite;     /* of those, with a NaN or infinite position component */
+    uint64_t pair_bound;    /* pair tests the count pass makes at most (no early exit), as the implementation counts them */
+    uint64_t budget;        /* the budget that applied */
+} gsr_neighbour_info;
+#define GSR_NEIGHBOUR_MAX_CAP 4095u
+#define GSR_NEIGHBOUR_DEFAULT_BUDGET (1ull << 34)   /* about 43 ms of count pass at the 4.0e11 pair tests per second measured on one MI355X */
+#define GSR_NEIGHBOUR_MAX_BUDGET     (1ull << 38)   /* about 0.7 s at that rate */
+int gsr_neighbours(gsr_ctx *ctx, double radius, uint32_t cap, uint32_t scope, uint64_t budget,
+                   uint32_t *counts, uint32_t n, uint32_t *hist, gsr_neighbour_info *info);
+int gsr_select_neighbours(gsr_ctx *ctx, double radius, uint32_t cap, uint32_t scope, uint64_t budget,
+                          uint32_t lo, uint32_t hi, int32_t op, uint32_t *selected, gsr_neighbour_info *info);
+
 /* ---- selection overlay ---- the selected splats tinted, in read-backs and in delivered frames
  * No interface of the reference stands behind this section either.  gsr_read_selection returns bits; this shows them: a second
  * image beside the frame in which the selected splats carry a tint, and per pixel how much of it they are.

@@ -3,7 +3,7 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--share-scene]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--share-scene]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
@@ -40,6 +40,10 @@
 // bins unless given; the contribution attributes go beside --contrib) asks the scene about itself: gsr_attr_stats, a
 // gsr_attr_histogram over [min, max] and a gsr_select_attr of the middle half of the bins, [edge(bins / 4), edge(bins - bins / 4)).
 // The report carries the three blocking times (the best of five each) and the check sum(counts[a .. b-1]) == selected.
+// --neighbours RADIUS[:CAP] (cap 64 unless given) counts every splat's neighbours within RADIUS: five gsr_neighbours calls, the best
+// wall time, and by the library's events on the stream the index build (with its bound) and the count pass apart; pair_bound and
+// the pair tests per second it means for the count pass, the median count, the splats with fewer than three neighbours, and the
+// check that gsr_select_neighbours(lo 0, hi 3) selects exactly hist[0] + hist[1] + hist[2].
 // --duplicate FRACTION (last of all: it grows the scene) selects that fraction of the splats through gsr_selection_set and calls
 // gsr_scene_duplicate_selected twice -- the second call copies the first one's copies, the same count -- and reports the wall time
 // of either (`duplicate_ms`, `duplicate_again_ms`), the count and the capacity.  With --reserve, gsr_scene_reserve makes room for
@@ -149,6 +153,8 @@ uint64_t fnv1a(const void* p, size_t bytes)
     return h;
 }
 
+extern "C" int gsr_debug_neighbour_times(gsr_ctx* ctx, float* out /* build_ms, count_ms */);   // not part of the ABI (gsr_neighbours.cpp)
+
 #define CHECK(call)                                                                                     \
     do {                                                                                                \
         const int rc_ = (call);                                                                         \
@@ -178,6 +184,8 @@ int main(int argc, char** argv)
     bool reserve = false;
     std::string histogram_attr;         // empty: off
     uint32_t histogram_bins = 256;
+    double nb_radius = 0.0;             // 0: off
+    uint32_t nb_cap = 64;
     int32_t pick_xy[2] = {0, 0};
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -206,13 +214,20 @@ int main(int argc, char** argv)
             if (colon != std::string::npos) { histogram_bins = (uint32_t)std::atoi(histogram_attr.c_str() + colon + 1); histogram_attr.resize(colon); }
             if (histogram_bins < 1 || histogram_bins > 4096) { std::fprintf(stderr, "--histogram ATTR[:BINS]: BINS must be in 1 .. 4096\n"); return 2; }
         }
+        else if (a == "--neighbours" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            const size_t colon = v.find(':');
+            nb_radius = std::atof(v.c_str());
+            if (colon != std::string::npos) nb_cap = (uint32_t)std::atoi(v.c_str() + colon + 1);
+            if (!(nb_radius > 0.0) || nb_cap < 1 || nb_cap > GSR_NEIGHBOUR_MAX_CAP) { std::fprintf(stderr, "--neighbours RADIUS[:CAP]: RADIUS > 0, CAP in 1 .. 4095\n"); return 2; }
+        }
         else if (a == "--duplicate" && i + 1 < argc) { duplicate_fraction = std::atof(argv[++i]); if (!(duplicate_fraction >= 0.0 && duplicate_fraction <= 1.0)) { std::fprintf(stderr, "--duplicate FRACTION must be in [0, 1]\n"); return 2; } }
         else if (a == "--reserve") reserve = true;
         else if (a == "--scene-arrays") scene_arrays = true;
         else if (a == "--scene-edit") scene_edit = next();
         else if (a == "--share-scene") share_scene = true;
         else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--share-scene]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--share-scene]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
@@ -603,6 +618,30 @@ int main(int argc, char** argv)
         CHECK(best_of([&] { return gsr_select_attr(ctx[0], hist_attr, origin, edge(hist_a), edge(hist_b), GSR_SELOP_REPLACE, &hist_selected); }, hist_ms[2]));
         for (uint32_t k = 0; k < bins; k++) { hist_peak = std::max<unsigned long long>(hist_peak, counts[k]); if (k >= hist_a && k < hist_b) hist_sum += counts[k]; }
     }
+    // --neighbours: every splat's neighbour count within the radius, the stages timed apart, the floater pick checked against the histogram
+    gsr_neighbour_info nb_info{};
+    double nb_ms = 1e30, nb_build_ms = 1e30, nb_count_ms = 1e30, nb_select_ms = 0;
+    uint32_t nb_median = 0, nb_selected = 0, nb_n = 0;
+    unsigned long long nb_few = 0;
+    if (nb_radius > 0.0) {
+        ctx0 = ctx[0];
+        CHECK(gsr_scene_count(ctx[0], &nb_n));
+        std::vector<uint32_t> counts(nb_n), hist(nb_cap + 1u);
+        for (int t = 0; t < 5; t++) {
+            const auto t0 = std::chrono::steady_clock::now();
+            CHECK(gsr_neighbours(ctx[0], nb_radius, nb_cap, 0, 0, counts.data(), nb_n, hist.data(), &nb_info));
+            nb_ms = std::min(nb_ms, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3);
+            float stage[2] = {0, 0};
+            CHECK(gsr_debug_neighbour_times(ctx[0], stage));
+            nb_build_ms = std::min(nb_build_ms, (double)stage[0]); nb_count_ms = std::min(nb_count_ms, (double)stage[1]);
+        }
+        unsigned long long seen = 0;
+        for (uint32_t k = 0; k <= nb_cap; k++) { seen += hist[k]; if (2 * seen >= nb_info.in_scope) { nb_median = k; break; } }
+        for (uint32_t k = 0; k < 3 && k <= nb_cap; k++) nb_few += hist[k];
+        const auto t0 = std::chrono::steady_clock::now();
+        CHECK(gsr_select_neighbours(ctx[0], nb_radius, nb_cap, 0, 0, 0, std::min(3u, nb_cap + 1u), GSR_SELOP_REPLACE, &nb_selected, nullptr));
+        nb_select_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3;
+    }
     // --duplicate (last of all: it grows the scene): the selection duplicated on the device, twice
     double duplicate_ms = 0, duplicate_again_ms = 0, reserve_ms = 0;
     uint32_t dup_selected = 0, dup_first = 0, dup_count = 0, dup_capacity = 0, dup_n = 0;
@@ -685,6 +724,13 @@ int main(int argc, char** argv)
                     "\"select_attr_ms\": %.4f, \"range\": [%u, %u], \"sum_counts\": %llu, \"selected\": %u, \"histogram_equals_selection\": %s}",
                     histogram_attr.c_str(), histogram_bins, hist_count, hist_nan, json_num(hist_min).c_str(), json_num(hist_max).c_str(), hist_lo, hist_hi, hist_outside[0], hist_outside[1], hist_outside[2],
                     hist_peak, hist_ms[0], hist_ms[1], hist_ms[2], hist_a, hist_b, hist_sum, hist_selected, hist_sum == hist_selected ? "true" : "false");
+    if (nb_radius > 0.0)
+        std::printf(", \"neighbours\": {\"radius\": %.17g, \"cap\": %u, \"n\": %u, \"in_scope\": %u, \"nonfinite\": %u, \"pair_bound\": %llu, \"budget\": %llu, "
+                    "\"neighbours_ms\": %.4f, \"index_build_ms\": %.4f, \"count_ms\": %.4f, \"pair_tests_per_s\": %.4g, \"median_count\": %u, "
+                    "\"fewer_than_3\": %llu, \"select_neighbours_ms\": %.4f, \"selected\": %u, \"histogram_equals_selection\": %s}",
+                    nb_radius, nb_cap, nb_n, nb_info.in_scope, nb_info.nonfinite, (unsigned long long)nb_info.pair_bound, (unsigned long long)nb_info.budget, nb_ms,
+                    nb_build_ms, nb_count_ms, nb_count_ms > 0 ? (double)nb_info.pair_bound / (nb_count_ms * 1e-3) : 0.0, nb_median, nb_few, nb_select_ms, nb_selected,
+                    nb_few == nb_selected ? "true" : "false");
     if (duplicate_fraction >= 0.0)
         std::printf(", \"duplicate_fraction\": %g, \"duplicate_first\": %u, \"duplicate_count\": %u, \"duplicate_reserved\": %s, \"reserve_ms\": %.4f, "
                     "\"duplicate_ms\": %.4f, \"duplicate_again_ms\": %.4f, \"count_after\": %u, \"capacity_after\": %u",
