@@ -601,6 +601,34 @@ void launch_nb_count(const NbIndex& ix, uint32_t indexed, uint32_t n, uint32_t c
 // scratch <- the splats i < n in scope with lo <= counts[i] < hi: every word of it is stored, no zeroing needed
 void launch_nb_select(const uint32_t* counts, const AttrScope& sc, uint32_t n, uint32_t lo, uint32_t hi, uint32_t* scratch, uint32_t nwords, hipStream_t s);
 
+// Clusters (k_clusters.hip; DESIGN.md section 4, "Clusters"): the connected islands of the splats in scope at a linking radius, over
+// the index above.  A label is the smallest splat index of its cluster; CL_NONE is "in no cluster".
+constexpr uint32_t CL_NONE = 0xffffffffu;                   // GSR_CLUSTER_NONE
+constexpr uint32_t CL_INFO_WORDS = 8;
+// the device words of one call: zeroed by the host in front of the walks
+struct ClInfo {
+    uint32_t core, border;                 // splats that are core; non-core splats that took a core neighbour's label
+    uint32_t clusters, fault;              // roots; non-zero when a find or a hook ran into its step limit or met parent[x] > x
+    unsigned long long largest;            // max over roots of size << 32 | ~label (0: no cluster)
+};
+struct ClArrays {
+    uint32_t* label;                       // n: parent[] while the union runs, every splat's label afterwards (CL_NONE: none)
+    uint32_t* size;                        // n: size[l] = the splats labelled l (zeroed by the caller)
+    uint32_t* sizes;                       // n: every splat's size[label] (0: no label)
+    ClInfo* info;
+};
+// label[i] = i for every core entry (counts[i] >= min_pts), CL_NONE for every other splat; info->core.  indexed, n as launch_nb_count's.
+void launch_cl_seed(const NbIndex& ix, uint32_t indexed, uint32_t n, const uint32_t* counts, uint32_t min_pts, const ClArrays& a, int cu_count, hipStream_t s);
+// the union over every near pair of core entries, then label[i] = its root for every core entry, size[root] and info->clusters
+void launch_cl_union(const NbIndex& ix, uint32_t indexed, uint32_t n, const uint32_t* counts, uint32_t min_pts, const ClArrays& a, int cu_count, hipStream_t s);
+// label[i] = the smallest label among the near core entries of every non-core entry that has one; size[] and info->border
+void launch_cl_border(const NbIndex& ix, uint32_t indexed, uint32_t n, const uint32_t* counts, uint32_t min_pts, const ClArrays& a, int cu_count, hipStream_t s);
+// sizes[i] for every splat and info->largest
+void launch_cl_sizes(uint32_t n, const ClArrays& a, int cu_count, hipStream_t s);
+// scratch <- the splats i < n in scope with lo <= sizes[i] < hi / with label[i] == target (CL_NONE: nobody): every word of it is stored
+void launch_cl_select_sizes(const uint32_t* sizes, const AttrScope& sc, uint32_t n, uint32_t lo, uint32_t hi, uint32_t* scratch, uint32_t nwords, hipStream_t s);
+void launch_cl_select_label(const uint32_t* label, uint32_t n, uint32_t target, uint32_t* scratch, uint32_t nwords, hipStream_t s);
+
 // Selection overlay (k_overlay.hip; DESIGN.md section 4, "Selection overlay"): the last frame's bin lists walked once more, the
 // weight w = T * B of every fragment of a SELECTED splat summed per pixel (cover) and, with the splat's colour, turned into the
 // frame with those splats tinted (overlay).  Reads the framebuffer, never writes it.

@@ -22,27 +22,24 @@ static_assert(sizeof(NbInfo) <= NB_INFO_WORDS * 4, "NbInfo fits its words");
 static_assert(NB_MAX_CAP == GSR_NEIGHBOUR_MAX_CAP, "the header's cap");
 constexpr uint32_t NB_MAX_ROWS = 1u << 29;            // twice as many buckets still index with 32 bits
 
-struct NbCall {
-    AttrScope sc;
-    NbIndex ix;
-    uint32_t n, indexed;
-    uint32_t* hist;                                   // the device counters (null: the call wants none)
-};
+}  // namespace
 
-// The refusals both calls share, in the header's order.  Nothing is touched by a refused call.
-int nb_check(gsr_ctx* c, const char* who, double radius, uint32_t cap, uint32_t scope, uint64_t budget)
+// The refusals every call over the index shares, in the header's order.  Nothing is touched by a refused call.
+int gsr::nb_check(gsr_ctx* c, const char* who, double radius, uint32_t cap, uint32_t scope, uint64_t budget, uint32_t cap_min, const char* cap_name)
 {
     if (!(std::isfinite(radius) && radius > 0.0)) return fail(c, GSR_ERR_ARG, "%s: radius (%g) must be finite and > 0", who, radius);
     const double r2 = radius * radius, inv = 1.0 / radius, inv_h = 1.0 / (radius * (1.0 + 1.0 / 1024.0));
     if (!(std::isnormal(r2) && std::isnormal(inv) && std::isnormal(inv_h)))
         return fail(c, GSR_ERR_ARG, "%s: radius (%g): radius * radius and 1 / radius must be finite and normal", who, radius);
-    if (cap < 1u || cap > GSR_NEIGHBOUR_MAX_CAP) return fail(c, GSR_ERR_ARG, "%s: cap (%u) must be in 1 .. %u", who, cap, GSR_NEIGHBOUR_MAX_CAP);
+    if (cap < cap_min || cap > GSR_NEIGHBOUR_MAX_CAP) return fail(c, GSR_ERR_ARG, "%s: %s (%u) must be in %u .. %u", who, cap_name, cap, cap_min, GSR_NEIGHBOUR_MAX_CAP);
     if (scope & ~(ATTR_SCOPE_SELECTED | ATTR_SCOPE_VISIBLE)) return fail(c, GSR_ERR_ARG, "%s: unknown scope flags 0x%x", who, scope);
     if (budget > GSR_NEIGHBOUR_MAX_BUDGET)
         return fail(c, GSR_ERR_ARG, "%s: budget (%llu) is above GSR_NEIGHBOUR_MAX_BUDGET (%llu)", who, (unsigned long long)budget,
                     (unsigned long long)GSR_NEIGHBOUR_MAX_BUDGET);
     return GSR_OK;
 }
+
+namespace {
 
 // the context's scratch for n splats: allocated by the first call, only ever grown
 int nb_ensure(gsr_ctx* c, uint32_t n, uint64_t buckets)
@@ -64,9 +61,11 @@ int nb_ensure(gsr_ctx* c, uint32_t n, uint64_t buckets)
     return GSR_OK;
 }
 
+}  // namespace
+
 // Everything up to the count pass: the index, its bound against the budget, *info.  GSR_ERR_ARG (with *info filled) when the
 // bound is above the budget: no count kernel has been launched.  n >= 1; the device is current and no member's stream holds work.
-int nb_index(gsr_ctx* c, const char* who, double radius, uint32_t cap, uint32_t scope, uint64_t budget, bool want_hist, NbCall* call, gsr_neighbour_info* info)
+int gsr::nb_index(gsr_ctx* c, const char* who, double radius, uint32_t cap, uint32_t scope, uint64_t budget, bool want_hist, NbCall* call, gsr_neighbour_info* info)
 {
     SharedScene& sc = *c->scene;
     const uint32_t n = sc.n;
@@ -104,6 +103,8 @@ int nb_index(gsr_ctx* c, const char* who, double radius, uint32_t cap, uint32_t 
                     who, (unsigned long long)got.pair_bound, (unsigned long long)budget, radius);
     return GSR_OK;
 }
+
+namespace {
 
 // the two stages' times of a call that ran both, by the events around them (bench_cabi --neighbours)
 void nb_times(gsr_ctx* c)

@@ -31,13 +31,13 @@
 #include "gsr_internal.h"
 #include "k_splat_ops.h"
 
-#include <algorithm>
+namespace gsr {
+GSR_BOUNDS_DECL(neighbours)   // sites: 0 set word, 1 splat index, 2 bucket, 3 entry slot, 4 LDS counter, 5 global counter, 6 selection word, 7 counts word
+}
+#define NB_BOUND_BUCKET(idx, limit) GSR_BOUND(neighbours, 2, idx, limit)
+#include "k_neighbours.h"   // the key, the bucket and the 27-cell walk, shared with k_clusters.hip
 
 namespace gsr {
-
-GSR_BOUNDS_DECL(neighbours)   // sites: 0 set word, 1 splat index, 2 bucket, 3 entry slot, 4 LDS counter, 5 global counter, 6 selection word, 7 counts word
-
-constexpr int NB_THREADS = 256;
 
 // the bits of word wi whose splats are in scope (the rule of k_attr.hip's attr_scope_word: below n, selected, not hidden)
 __device__ __forceinline__ uint32_t nb_scope_word(const AttrScope& sc, uint32_t n, uint32_t wi)
@@ -72,41 +72,6 @@ __device__ __forceinline__ int32_t nb_cell(float v, double inv_h)
     t = t < -(double)NB_CELL_HALF ? -(double)NB_CELL_HALF : t;
     t = t > (double)(NB_CELL_HALF - 1) ? (double)(NB_CELL_HALF - 1) : t;
     return (int32_t)t;
-}
-
-__device__ __forceinline__ unsigned long long nb_key(int32_t cx, int32_t cy, int32_t cz)
-{
-    return (unsigned long long)(uint32_t)(cx + NB_CELL_HALF) | (unsigned long long)(uint32_t)(cy + NB_CELL_HALF) << 21 |
-           (unsigned long long)(uint32_t)(cz + NB_CELL_HALF) << 42;
-}
-
-__device__ __forceinline__ uint32_t nb_bucket(unsigned long long k, uint32_t mask)
-{
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
-    k ^= k >> 33;
-    return (uint32_t)k & mask;
-}
-
-// f(key, bucket) for each of the 27 cells around the cell of key k that lie inside the clamp, while f returns true
-template <class F>
-__device__ __forceinline__ void nb_each_cell(unsigned long long k, uint32_t mask, F f)
-{
-    const int32_t cx = (int32_t)((uint32_t)k & 0x1fffffu) - NB_CELL_HALF, cy = (int32_t)((uint32_t)(k >> 21) & 0x1fffffu) - NB_CELL_HALF,
-                  cz = (int32_t)((uint32_t)(k >> 42) & 0x1fffffu) - NB_CELL_HALF;
-    for (int32_t z = cz - 1; z <= cz + 1; z++) {
-        if (z < -NB_CELL_HALF || z >= NB_CELL_HALF) continue;
-        for (int32_t y = cy - 1; y <= cy + 1; y++) {
-            if (y < -NB_CELL_HALF || y >= NB_CELL_HALF) continue;
-            for (int32_t x = cx - 1; x <= cx + 1; x++) {
-                if (x < -NB_CELL_HALF || x >= NB_CELL_HALF) continue;
-                const unsigned long long nk = nb_key(x, y, z);
-                const uint32_t b = nb_bucket(nk, mask);
-                GSR_BOUND(neighbours, 2, b, (uint64_t)mask + 1u);
-                if (!f(nk, b)) return;
-            }
-        }
-    }
 }
 
 // ---- the index ----
@@ -267,12 +232,6 @@ __global__ __launch_bounds__(NB_THREADS) void k_nb_select(const uint32_t* __rest
 }
 
 // ---- launchers ----
-static uint32_t nb_grid(uint64_t work, int cu_count)
-{
-    const uint32_t most = std::min<uint32_t>(NB_WG_PER_CU * (uint32_t)std::max(cu_count, 1), NB_MAX_GRID);
-    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((work + NB_THREADS - 1) / NB_THREADS, 1u), most);
-}
-
 void launch_nb_build(const NbIndex& ix, const float* px, const float* py, const float* pz, const AttrScope& sc, uint32_t n, int cu_count, uint32_t* hist0,
                      hipStream_t s)
 {

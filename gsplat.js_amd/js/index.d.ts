@@ -100,6 +100,9 @@ export interface SplatStats { count: number; nan: number; min: number; max: numb
 export type NeighbourScope = "selected" | "visible";
 export interface NeighbourOptions { cap?: number; scope?: NeighbourScope | NeighbourScope[]; budget?: number }
 export interface SplatNeighbours { counts: Uint32Array; hist: Uint32Array; inScope: number; nonfinite: number; pairBound: number }
+export interface ClusterOptions { minPts?: number; scope?: NeighbourScope | NeighbourScope[]; budget?: number }
+export interface SplatClusters { labels: Uint32Array; sizes: Uint32Array; inScope: number; nonfinite: number; pairBound: number; core: number; border: number;
+    noise: number; clusters: number; largestLabel: number; largestSize: number }
 export interface SplatHistogram { counts: Uint32Array; below: number; above: number; nan: number; edges: Float64Array }
 export interface Contribution { weight: BigUint64Array; peak: Float32Array; pixels: Uint32Array; frames: number }
 /** A screen region: the pixels [x0, x1) x [y0, y1), optionally one byte per pixel of the rectangle (non-zero = inside; rows
@@ -382,6 +385,20 @@ export class HIPRenderer {
      *  most 2^38); a radius that needs more throws before the count pass runs, with both numbers in the message. */
     splatNeighbours(radius: number, options?: NeighbourOptions): SplatNeighbours;
     selectNeighbours(radius: number, options?: NeighbourOptions & { below?: number; lo?: number; hi?: number; op?: SelectOp }): number;
+    /** Clusters: the connected islands of the splats in scope at the linking radius `radius` (f64, distance exactly radius links).
+     *  minPts (0 .. 4095, default 0: plain connected components) makes it DBSCAN: a splat with minPts or more others within radius is
+     *  core, core splats within radius of each other share a cluster, a non-core splat beside a core one takes the smallest such
+     *  label (border), the rest is noise.  splatClusters: labels[i] = the smallest splat index of i's cluster (0xffffffff: noise, not
+     *  finite, outside the scope), sizes[i] = the splats labelled like i (0 without a label), and the counts: inScope == core + border +
+     *  noise, clusters, largestLabel / largestSize (ties: the smallest label; 0xffffffff / 0 without a cluster).  selectClusters picks
+     *  the splats in scope with atLeast <= size < below (defaults 0 and no upper end) and folds them into the selection with `op`,
+     *  returning the number of selected splats: selectClusters(r, { below: k }) then Scene.eraseSelection(readSelection()) removes noise
+     *  and every island smaller than k.  selectClusterAt picks the cluster of splat `seed` (pick(x, y).index: the island under the
+     *  cursor) or, with largest: true, the largest one; a seed that is noise or outside the scope picks nothing.  All index the device
+     *  scene as it is now; budget as splatNeighbours takes it, for each of up to three walks. */
+    splatClusters(radius: number, options?: ClusterOptions): SplatClusters;
+    selectClusters(radius: number, options?: ClusterOptions & { below?: number; atLeast?: number; op?: SelectOp }): number;
+    selectClusterAt(radius: number, options: ClusterOptions & { seed?: number; largest?: boolean; op?: SelectOp }): number;
     dispose(): void;
     /** RGBA8, row 0 = top, round(clamp(x,0,1)*255), premultiplied alpha */
     /** RGBA8, row 0 = top; pass an array of width*height*4 elements to have it filled and returned (no allocation per frame). */

@@ -1490,6 +1490,100 @@ napi_value SelectNeighbours(napi_env env, napi_callback_info info)
     return rc ? throw_gsr(env, c, rc, "gsr_select_neighbours") : count_value(env, count);
 }
 
+// ---- clusters (gsr_clusters / gsr_select_clusters / gsr_select_cluster_at) ----
+// radius, min_pts, scope and budget of the three calls below (argv[1 .. 4]; the budget a number, 0: the library's default); false:
+// an error is pending
+bool get_cluster_args(napi_env env, napi_value* argv, double* radius, uint32_t* min_pts, uint32_t* scope, uint64_t* budget)
+{
+    double b;
+    if (!get_f64(env, argv[1], radius) || napi_get_value_uint32(env, argv[2], min_pts) != napi_ok || napi_get_value_uint32(env, argv[3], scope) != napi_ok ||
+        !get_f64(env, argv[4], &b)) {
+        napi_throw_type_error(env, nullptr, "clusters: radius, minPts, scope and budget must be numbers");
+        return false;
+    }
+    if (*min_pts > GSR_NEIGHBOUR_MAX_CAP) { napi_throw_range_error(env, nullptr, "clusters: minPts must be in 0 .. 4095"); return false; }
+    if (!(b >= 0.0 && b <= 18446744073709549568.0)) { napi_throw_range_error(env, nullptr, "clusters: budget must be a non-negative number"); return false; }
+    *budget = (uint64_t)b;
+    return true;
+}
+
+bool set_cluster_info(napi_env env, napi_value out, const gsr_cluster_info& ci)
+{
+    return set_u32(env, out, "inScope", ci.in_scope) && set_u32(env, out, "nonfinite", ci.nonfinite) && set_f64(env, out, "pairBound", (double)ci.pair_bound) &&
+           set_f64(env, out, "budget", (double)ci.budget) && set_u32(env, out, "core", ci.core) && set_u32(env, out, "border", ci.border) &&
+           set_u32(env, out, "noise", ci.noise) && set_u32(env, out, "clusters", ci.clusters) && set_u32(env, out, "largestLabel", ci.largest_label) &&
+           set_u32(env, out, "largestSize", ci.largest_size);
+}
+
+// clusters(handle, radius, minPts, scope, budget) -> { labels: Uint32Array(n), sizes: Uint32Array(n), inScope, nonfinite, pairBound, budget, core, border, noise,
+// clusters, largestLabel, largestSize }
+napi_value Clusters(napi_env env, napi_callback_info info)
+{
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    double radius;
+    uint32_t min_pts, scope, n = 0;
+    uint64_t budget;
+    if (!c || !get_cluster_args(env, argv, &radius, &min_pts, &scope, &budget)) return nullptr;
+    int rc = gsr_scene_count(c, &n);
+    if (rc) return throw_gsr(env, c, rc, "gsr_scene_count");
+    void *labels = nullptr, *sizes = nullptr;
+    napi_value lb, larr, sb, sarr, out;
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, (size_t)n * 4, &labels, &lb));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_uint32_array, n, lb, 0, &larr));
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, (size_t)n * 4, &sizes, &sb));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_uint32_array, n, sb, 0, &sarr));
+    gsr_cluster_info ci{};
+    rc = gsr_clusters(c, radius, min_pts, scope, budget, n ? (uint32_t*)labels : nullptr, n ? (uint32_t*)sizes : nullptr, n, &ci);
+    if (rc) return throw_gsr(env, c, rc, "gsr_clusters");
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "labels", larr));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "sizes", sarr));
+    if (!set_cluster_info(env, out, ci)) return nullptr;
+    return out;
+}
+
+// selectClusters(handle, radius, minPts, scope, budget, lo, hi, op) -> selected
+napi_value SelectClusters(napi_env env, napi_callback_info info)
+{
+    napi_value argv[8];
+    if (!get_args(env, info, 8, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    double radius;
+    uint32_t min_pts, scope, lo, hi;
+    uint64_t budget;
+    int32_t op;
+    if (!c || !get_cluster_args(env, argv, &radius, &min_pts, &scope, &budget)) return nullptr;
+    if (napi_get_value_uint32(env, argv[5], &lo) != napi_ok || napi_get_value_uint32(env, argv[6], &hi) != napi_ok || !get_i32(env, argv[7], &op)) {
+        napi_throw_type_error(env, nullptr, "selectClusters: lo, hi and op must be numbers");
+        return nullptr;
+    }
+    uint32_t count = 0;
+    const int rc = gsr_select_clusters(c, radius, min_pts, scope, budget, lo, hi, op, &count, nullptr);
+    return rc ? throw_gsr(env, c, rc, "gsr_select_clusters") : count_value(env, count);
+}
+
+// selectClusterAt(handle, radius, minPts, scope, budget, seed, op) -> selected   (seed 0xffffffff: the largest cluster)
+napi_value SelectClusterAt(napi_env env, napi_callback_info info)
+{
+    napi_value argv[7];
+    if (!get_args(env, info, 7, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    double radius;
+    uint32_t min_pts, scope, seed;
+    uint64_t budget;
+    int32_t op;
+    if (!c || !get_cluster_args(env, argv, &radius, &min_pts, &scope, &budget)) return nullptr;
+    if (napi_get_value_uint32(env, argv[5], &seed) != napi_ok || !get_i32(env, argv[6], &op)) {
+        napi_throw_type_error(env, nullptr, "selectClusterAt: seed and op must be numbers");
+        return nullptr;
+    }
+    uint32_t count = 0;
+    const int rc = gsr_select_cluster_at(c, radius, min_pts, scope, budget, seed, op, &count, nullptr);
+    return rc ? throw_gsr(env, c, rc, "gsr_select_cluster_at") : count_value(env, count);
+}
+
 // ---- selection overlay (gsr_set_overlay / gsr_overlay_async / gsr_read_overlay* / gsr_delivery_set_overlay) ----
 // setOverlay(handle, on, r, g, b, mix): on = 0 switches the overlay off (the other arguments are not read)
 napi_value SetOverlay(napi_env env, napi_callback_info info)
@@ -1606,6 +1700,7 @@ napi_value Init(napi_env env, napi_value exports)
         {"selectContrib", SelectContrib},
         {"attrStats", AttrStats}, {"attrHistogram", AttrHistogram}, {"selectAttr", SelectAttr},
         {"neighbours", Neighbours}, {"selectNeighbours", SelectNeighbours},
+        {"clusters", Clusters}, {"selectClusters", SelectClusters}, {"selectClusterAt", SelectClusterAt},
         {"setOverlay", SetOverlay}, {"readOverlay", ReadOverlay}, {"readOverlayPixels", ReadOverlayPixels},
         {"deliverySetOverlay", DeliverySetOverlay}, {"setOutline", SetOutline},
     };

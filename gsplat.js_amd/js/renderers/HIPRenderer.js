@@ -569,6 +569,40 @@ class HIPRenderer {
             if (!Number.isInteger(lo) || !Number.isInteger(hi) || lo < 0 || lo > hi || hi > cap + 1) throw new Error("selectNeighbours: 0 <= lo <= hi <= cap + 1 must hold");
             return this._n.selectNeighbours(this._h, ...args, lo, hi, code(OPS, o2.op, "replace", "op"));
         };
+        // ---- clusters (gsr_clusters / gsr_select_clusters / gsr_select_cluster_at): the connected islands of splats at a linking radius ----
+        //   const p = renderer.pick(x, y); renderer.selectClusterAt(0.05, { seed: p.index });        // the island under the cursor
+        //   renderer.selectClusters(0.05, { below: 50 }); scene.eraseSelection(renderer.readSelection());   // noise and every island of fewer than 50 splats
+        //   renderer.selectClusterAt(0.05, { largest: true }); renderer.invertSelection();            // everything but the largest island
+        // Two splats within `radius` of each other (f64, distance exactly radius links) share a cluster; minPts (0 .. 4095, default 0)
+        // makes it DBSCAN: only a splat with minPts or more others within radius links, a splat beside such a one takes the smallest
+        // such label, the rest is noise.  labels[i]: the smallest splat index of i's cluster, 0xffffffff for noise and outside the
+        // scope; sizes[i]: the splats labelled like i.  selectClusters picks the splats whose cluster has atLeast <= size < below
+        // splats (noise has size 0); selectClusterAt the cluster of splat `seed`, or the largest one.  scope and budget as splatNeighbours.
+        const CLUSTER_LARGEST = 0xffffffff;
+        const clArgs = (radius, o) => {
+            const minPts = o.minPts === undefined ? 0 : o.minPts, budget = o.budget === undefined || o.budget === null ? 0 : Number(o.budget);
+            if (!Number.isInteger(minPts) || minPts < 0 || minPts > 4095) throw new Error("minPts must be an integer in 0 .. 4095");
+            if (!(budget >= 0)) throw new Error("budget must be a non-negative number");
+            return [Number(radius), minPts, nbScope(o), budget];
+        };
+        this.splatClusters = (radius, options) => {
+            const o2 = options || {};
+            const r = this._n.clusters(this._h, ...clArgs(radius, o2));
+            return { labels: r.labels, sizes: r.sizes, inScope: r.inScope, nonfinite: r.nonfinite, pairBound: r.pairBound, core: r.core, border: r.border,
+                     noise: r.noise, clusters: r.clusters, largestLabel: r.largestLabel, largestSize: r.largestSize };
+        };
+        this.selectClusters = (radius, options) => {
+            const o2 = options || {}, args = clArgs(radius, o2);
+            const lo = o2.atLeast === undefined ? 0 : o2.atLeast, hi = o2.below === undefined ? CLUSTER_LARGEST : o2.below;
+            if (!Number.isInteger(lo) || !Number.isInteger(hi) || lo < 0 || lo > hi || hi > CLUSTER_LARGEST) throw new Error("selectClusters: 0 <= atLeast <= below < 2^32 must hold");
+            return this._n.selectClusters(this._h, ...args, lo, hi, code(OPS, o2.op, "replace", "op"));
+        };
+        this.selectClusterAt = (radius, options) => {
+            const o2 = options || {}, args = clArgs(radius, o2);
+            if ((o2.largest === true) === (o2.seed !== undefined)) throw new Error("selectClusterAt: give either seed (a splat index) or largest: true");
+            if (o2.seed !== undefined && (!Number.isInteger(o2.seed) || o2.seed < 0 || o2.seed >= CLUSTER_LARGEST)) throw new Error("selectClusterAt: seed must be a splat index");
+            return this._n.selectClusterAt(this._h, ...args, o2.largest === true ? CLUSTER_LARGEST : o2.seed, code(OPS, o2.op, "replace", "op"));
+        };
         // ---- selection overlay (gsr_set_overlay / gsr_read_overlay*): the last frame with the selected splats tinted ----
         //   renderer.setSelectionOverlay({ tint: [1, 0.5, 0], mix: 0.5 }); renderer.render(scene, cam);
         //   const { rgba, cover } = renderer.readOverlay();   // or readPixels({ overlay: true }), or openDelivery(n, { overlay: true })

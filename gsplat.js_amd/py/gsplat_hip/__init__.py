@@ -86,6 +86,15 @@ class GsrNeighbourInfo(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class GsrClusterInfo(ctypes.Structure):
+    _fields_ = [("in_scope", ctypes.c_uint32), ("nonfinite", ctypes.c_uint32), ("pair_bound", ctypes.c_uint64), ("budget", ctypes.c_uint64),
+                ("core", ctypes.c_uint32), ("border", ctypes.c_uint32), ("noise", ctypes.c_uint32), ("clusters", ctypes.c_uint32),
+                ("largest_label", ctypes.c_uint32), ("largest_size", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class GsrDepthLayout(ctypes.Structure):
     _fields_ = [("format", ctypes.c_int32), ("step", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
                 ("stride", ctypes.c_int32), ("reserved", ctypes.c_int32), ("offset", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
@@ -106,6 +115,7 @@ SCOPES = {"selected": 1, "visible": 2}                                     # GSR
 ATTR_MAX_BINS = 4096
 NEIGHBOUR_MAX_CAP = 4095                                                   # GSR_NEIGHBOUR_MAX_CAP
 NEIGHBOUR_DEFAULT_BUDGET, NEIGHBOUR_MAX_BUDGET = 1 << 34, 1 << 38          # GSR_NEIGHBOUR_*_BUDGET
+CLUSTER_NONE = CLUSTER_LARGEST = 0xffffffff                                # GSR_CLUSTER_NONE (a label), GSR_CLUSTER_LARGEST (a seed)
 
 
 def attr_edges(lo, hi, bins):
@@ -158,6 +168,7 @@ EXPORTS = [
     "gsr_contrib_reset", "gsr_contrib_accumulate_async", "gsr_read_contrib", "gsr_select_contrib",
     "gsr_attr_stats", "gsr_attr_histogram", "gsr_select_attr",
     "gsr_neighbours", "gsr_select_neighbours",
+    "gsr_clusters", "gsr_select_clusters", "gsr_select_cluster_at",
     "gsr_set_overlay", "gsr_overlay_async", "gsr_read_overlay", "gsr_read_overlay_rgba8", "gsr_overlay_device_ptr", "gsr_delivery_set_overlay",
     "gsr_set_overlay_outline",
 ]
@@ -325,6 +336,10 @@ def load_library(path=None):
     L.gsr_neighbours.argtypes = [vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, vp, ctypes.c_uint32, vp, ctypes.POINTER(GsrNeighbourInfo)]
     L.gsr_select_neighbours.argtypes = [vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, u32p,
                                         ctypes.POINTER(GsrNeighbourInfo)]
+    ci = ctypes.POINTER(GsrClusterInfo)
+    L.gsr_clusters.argtypes = [vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, vp, vp, ctypes.c_uint32, ci]
+    L.gsr_select_clusters.argtypes = [vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, u32p, ci]
+    L.gsr_select_cluster_at.argtypes = [vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, ctypes.c_uint32, ctypes.c_int32, u32p, ci]
     L.gsr_set_overlay.argtypes = [vp, ctypes.POINTER(GsrOverlayOptions)]
     L.gsr_set_overlay_outline.argtypes = [vp, ctypes.POINTER(GsrOutlineOptions)]
     L.gsr_overlay_async.argtypes = [vp]
@@ -1208,6 +1223,69 @@ class HIPRenderer:
         except GsplatError as e:
             e.info = info.as_dict()   # (a call refused for its budget has filled it)
             raise
+
+    # -- clusters (gsr_clusters / gsr_select_clusters / gsr_select_cluster_at): the connected islands of splats at a linking radius --
+    @staticmethod
+    def _cluster_args(radius, min_pts, budget):
+        min_pts = int(min_pts)
+        if not 0 <= min_pts <= NEIGHBOUR_MAX_CAP:
+            raise ValueError("min_pts must be in 0 .. %d" % NEIGHBOUR_MAX_CAP)
+        budget = 0 if budget is None else int(budget)
+        if budget < 0:
+            raise ValueError("budget must not be negative")
+        return float(radius), min_pts, budget
+
+    def clusters(self, radius, min_pts=0, scope=(), budget=None, labels=True, sizes=True):
+        """(labels uint32[n], sizes uint32[n], info): the clusters of the splats in scope -- scope: any of "selected", "visible"; ()
+        is every splat -- at the linking radius `radius` (f64, distance exactly radius links).  min_pts=0: connected components;
+        min_pts=k: DBSCAN, a splat with k or more others within radius is core, core splats within radius of each other share a
+        cluster, a non-core splat near a core one takes the smallest such label (border), the rest is noise.  labels[i]: the smallest
+        splat index of i's cluster, CLUSTER_NONE for noise and outside the scope; sizes[i]: the splats labelled like i, 0 without a
+        label.  labels=False / sizes=False: None in its place, nothing copied.  info: in_scope, nonfinite, pair_bound, budget, core,
+        border, noise, clusters, largest_label, largest_size.  budget as neighbours() takes it: a call whose pair_bound lies above
+        it is refused (GsplatError carrying `info`) before any walk runs."""
+        radius, min_pts, budget = self._cluster_args(radius, min_pts, budget)
+        n = self._count()
+        lab = np.zeros(n, np.uint32) if labels else None
+        siz = np.zeros(n, np.uint32) if sizes else None
+        info = GsrClusterInfo()
+        self._check_neighbours(self._L.gsr_clusters(self._ctx, radius, min_pts, self._scope_flags(scope), budget, lab.ctypes.data if labels and n else None,
+                                                    siz.ctypes.data if sizes and n else None, n if labels or sizes else 0, ctypes.byref(info)), info)
+        return lab, siz, info.as_dict()
+
+    def select_clusters(self, radius, lo=0, hi=None, min_pts=0, scope=(), op="replace", budget=None):
+        """(selected, info): pick the splats in scope whose cluster has lo <= size < hi splats (hi=None: no upper end; noise has
+        size 0) and fold them into the selection.  select_clusters(r, hi=k) then scene_erase_selected() removes noise and every
+        island smaller than k.  With op "replace" it selects exactly the splats in scope whose sizes[i] of clusters(radius,
+        min_pts, scope) lies in the range."""
+        radius, min_pts, budget = self._cluster_args(radius, min_pts, budget)
+        hi = 0xffffffff if hi is None else int(hi)
+        lo = int(lo)
+        if not 0 <= lo <= hi <= 0xffffffff:
+            raise ValueError("0 <= lo <= hi < 2^32 must hold")
+        count, info = ctypes.c_uint32(0), GsrClusterInfo()
+        self._check_neighbours(self._L.gsr_select_clusters(self._ctx, radius, min_pts, self._scope_flags(scope), budget, lo, hi, self._select_code(SELECT_OPS, op, "op"),
+                                                           ctypes.byref(count), ctypes.byref(info)), info)
+        return count.value, info.as_dict()
+
+    def select_cluster_at(self, radius, seed, min_pts=0, scope=(), op="replace", budget=None):
+        """(selected, info): pick the cluster of splat `seed` -- an index, such as pick()'s, or "largest" for the largest cluster (ties:
+        the smallest label) -- and fold it into the selection: the flood select.  A seed that is noise or outside the scope, or
+        "largest" without a cluster, picks the empty set.  select_cluster_at(r, "largest"), invert_selection(),
+        scene_erase_selected() keeps the largest island."""
+        radius, min_pts, budget = self._cluster_args(radius, min_pts, budget)
+        if isinstance(seed, str):
+            if seed != "largest":
+                raise ValueError("seed must be a splat index or \"largest\"")
+            seed = CLUSTER_LARGEST
+        else:
+            seed = int(seed)
+            if not 0 <= seed < CLUSTER_LARGEST:
+                raise ValueError("seed must be a splat index or \"largest\"")
+        count, info = ctypes.c_uint32(0), GsrClusterInfo()
+        self._check_neighbours(self._L.gsr_select_cluster_at(self._ctx, radius, min_pts, self._scope_flags(scope), budget, seed, self._select_code(SELECT_OPS, op, "op"),
+                                                             ctypes.byref(count), ctypes.byref(info)), info)
+        return count.value, info.as_dict()
 
     # -- selection overlay (gsr_set_overlay / gsr_overlay_async / gsr_read_overlay*): the selected splats tinted --
     def set_overlay(self, tint=(1.0, 0.5, 0.0), mix=0.5):

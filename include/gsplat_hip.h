@@ -878,6 +878,80 @@ int gsr_neighbours(gsr_ctx *ctx, double radius, uint32_t cap, uint32_t scope, ui
 int gsr_select_neighbours(gsr_ctx *ctx, double radius, uint32_t cap, uint32_t scope, uint64_t budget,
                           uint32_t lo, uint32_t hi, int32_t op, uint32_t *selected, gsr_neighbour_info *info);
 
+/* ---- clusters ---- connected islands of splats labelled, sized and selected
+ * No interface of the reference stands behind this section either.  A neighbour count finds thin floaters; it cannot find a dense
+ * blob of a few hundred splats hanging in mid-air, or a second object beside the one the user wants: inside such a blob every
+ * splat has plenty of neighbours.  Point-cloud tools answer with clustering -- connected components at a linking radius, or DBSCAN
+ * with a core threshold -- and two operations rest on it: "remove every island smaller than k splats" / "keep only the largest
+ * island", and "select the island under the cursor", the flood select that goes with gsr_pick.  These calls do it on the device,
+ * over the index of "neighbours", with no gsr_read_scene and no spatial index on the host.
+ * Definition ("Clusters").  Scope S, near(i,j) and the treatment of non-finite rows are exactly those of
+ *   "neighbours": the same f64 expression, in the written order, uncontracted, and a distance of exactly radius counts; a splat with
+ *   a NaN or infinite position component is in scope, is never indexed and is nobody's neighbour.  With min_pts in
+ *   0 .. GSR_NEIGHBOUR_MAX_CAP:
+ *     deg_i   = #{ j in S : near(i,j) }                 (only deg_i >= min_pts is ever needed: the count may stop at min_pts)
+ *     core_i  := i in S, finite, deg_i >= min_pts       (min_pts == 0: every finite splat in scope is core: plain connected components)
+ *     i ~ j   := core_i && core_j && near(i,j);   clusters = the classes of the transitive closure of ~ over core splats
+ *     label_i = the smallest splat index in i's class                           for a core splat
+ *     label_i = min{ label_j : core_j && near(i,j) }                            for a non-core finite splat in S with such a j ("border")
+ *     label_i = GSR_CLUSTER_NONE                                                otherwise (noise, non-finite, out of scope)
+ *     size_i  = #{ k : label_k == label_i }  if label_i != GSR_CLUSTER_NONE, else 0
+ *   A border splat never joins two clusters: it takes the smaller label, so the result does not depend on any visiting order.  The
+ *   largest cluster is the one of greatest size, ties going to the smallest label.  All results are integers decided by f64
+ *   comparisons: the same scene, scope, radius and min_pts give the same words on every run, in every context form and through
+ *   every member of a shared scene.
+ * gsr_clusters: labels and sizes are n words each, or NULL; a non-NULL pointer with n not equal to the scene's count is refused.
+ *   sizes is per splat: sizes[i] = size_i.  info may be NULL.  An empty scene, or an empty scope, returns zeros (largest_label
+ *   GSR_CLUSTER_NONE).
+ * gsr_select_clusters picks P = { i in S : size_lo <= size_i && size_i < size_hi }, with size_lo <= size_hi, and folds P into the
+ *   selection with `op` (GSR_SELOP_*) exactly as the selection calls fold theirs; `selected` means what it means everywhere else.
+ *   size_lo == size_hi picks nothing.  Noise and non-finite splats in S have size 0.
+ * The consistency guarantee: with GSR_SELOP_REPLACE it selects exactly the number of splats in S whose sizes[i] from a gsr_clusters
+ *   call with the same radius, min_pts and scope lies in the range.  gsr_select_clusters(.., 0, k, ..) then gsr_scene_erase_selected
+ *   removes noise and every island smaller than k.
+ * gsr_select_cluster_at picks P = { i : label_i == label_seed && label_seed != GSR_CLUSTER_NONE } and folds it the same way.  seed
+ *   is a splat index below the scene's count, or GSR_CLUSTER_LARGEST for the largest cluster.  A seed that is noise or out of
+ *   scope, or GSR_CLUSTER_LARGEST when there is no cluster, picks the empty set: the fold still happens.  "Keep the largest
+ *   island" is gsr_select_cluster_at(.., GSR_CLUSTER_LARGEST, GSR_SELOP_REPLACE, ..), gsr_selection_invert, gsr_scene_erase_selected.
+ * info: in_scope, nonfinite, pair_bound and budget as in gsr_neighbour_info; core, border and noise count the splats in S by kind,
+ *   noise including the non-finite ones, so in_scope == core + border + noise; clusters is the number of clusters; largest_label
+ *   and largest_size name the largest one (GSR_CLUSTER_NONE and 0 when there is no cluster).
+ * The work budget is the neighbour budget, with the same constants and the same pair_bound, checked before any walk is launched:
+ *   if pair_bound > budget the call returns GSR_ERR_ARG with a message naming both numbers, fills info's first four fields and
+ *   launches no walk.  A call makes up to three 27-cell walks -- the core test (none for min_pts == 0), the union and the border pass
+ *   (none for min_pts == 0) -- each of at most pair_bound pair tests: the budget bounds each walk, not their sum.
+ * All three calls are blocking and stateless: they index the scene as it is now, so nothing can go stale after an edit.  They are
+ *   ordered like gsr_select_attr: they wait for every member's stream of a shared scene first.  They read the scene and write none
+ *   of it: no frame state changes.
+ * Refusals (GSR_ERR_ARG with a message, nothing touched, the selection and its count included): a NULL ctx; a radius that is not
+ *   finite, not > 0, or with radius * radius or 1 / radius not finite and normal; min_pts above 4095; unknown scope flags or op;
+ *   size_lo > size_hi; a seed that is neither below the scene's count nor GSR_CLUSTER_LARGEST; a wrong n; a budget above the
+ *   maximum; a bound above the budget.  GSR_ERR_HIP, should the union ever meet an inconsistent parent word or exceed its step limit
+ *   of n: the call ends instead of occupying the device.
+ * The device scratch belongs to the context: the scratch of "neighbours" and 12 bytes per splat (parent / label, size by label,
+ *   size by splat).  The first cluster call allocates it, it only grows, and gsr_destroy frees it; a context that never calls any of
+ *   this allocates nothing and launches nothing. */
+typedef struct gsr_cluster_info {
+    uint32_t in_scope;      /* splats in S */
+    uint32_t nonfinite;     /* of those, with a NaN or infinite position component (noise) */
+    uint64_t pair_bound;    /* pair tests ONE walk makes at most, as the implementation counts them */
+    uint64_t budget;        /* the budget that applied */
+    uint32_t core;          /* splats in S that are core */
+    uint32_t border;        /* non-core splats in S labelled by a core neighbour */
+    uint32_t noise;         /* the rest of S, the non-finite ones included */
+    uint32_t clusters;      /* number of clusters */
+    uint32_t largest_label; /* label of the largest cluster (ties: the smallest label); GSR_CLUSTER_NONE: there is none */
+    uint32_t largest_size;  /* its size; 0: there is none */
+} gsr_cluster_info;
+#define GSR_CLUSTER_NONE    0xffffffffu   /* a label: in no cluster */
+#define GSR_CLUSTER_LARGEST 0xffffffffu   /* a seed: the largest cluster */
+int gsr_clusters(gsr_ctx *ctx, double radius, uint32_t min_pts, uint32_t scope, uint64_t budget,
+                 uint32_t *labels, uint32_t *sizes, uint32_t n, gsr_cluster_info *info);
+int gsr_select_clusters(gsr_ctx *ctx, double radius, uint32_t min_pts, uint32_t scope, uint64_t budget,
+                        uint32_t size_lo, uint32_t size_hi, int32_t op, uint32_t *selected, gsr_cluster_info *info);
+int gsr_select_cluster_at(gsr_ctx *ctx, double radius, uint32_t min_pts, uint32_t scope, uint64_t budget,
+                          uint32_t seed, int32_t op, uint32_t *selected, gsr_cluster_info *info);
+
 /* ---- selection overlay ---- the selected splats tinted, in read-backs and in delivered frames
  * No interface of the reference stands behind this section either.  gsr_read_selection returns bits; this shows them: a second
  * image beside the frame in which the selected splats carry a tint, and per pixel how much of it they are.

@@ -3,7 +3,7 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--share-scene]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--clusters RADIUS[:MIN_PTS]] [--share-scene]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
@@ -44,6 +44,10 @@
 // wall time, and by the library's events on the stream the index build (with its bound) and the count pass apart; pair_bound and
 // the pair tests per second it means for the count pass, the median count, the splats with fewer than three neighbours, and the
 // check that gsr_select_neighbours(lo 0, hi 3) selects exactly hist[0] + hist[1] + hist[2].
+// --clusters RADIUS[:MIN_PTS] (min_pts 0 unless given) labels the islands of the scene at the linking radius: five gsr_clusters calls,
+// the best wall time, and by the library's events on the stream the stages apart -- the index with its bound, the core test with the
+// seed, union with flatten, border with sizes; clusters, largest_size and noise, and the check that gsr_select_clusters(0, 10)
+// selects exactly the splats whose sizes[i] is below 10 (`sizes_equal_selection`).
 // --duplicate FRACTION (last of all: it grows the scene) selects that fraction of the splats through gsr_selection_set and calls
 // gsr_scene_duplicate_selected twice -- the second call copies the first one's copies, the same count -- and reports the wall time
 // of either (`duplicate_ms`, `duplicate_again_ms`), the count and the capacity.  With --reserve, gsr_scene_reserve makes room for
@@ -154,6 +158,7 @@ uint64_t fnv1a(const void* p, size_t bytes)
 }
 
 extern "C" int gsr_debug_neighbour_times(gsr_ctx* ctx, float* out /* build_ms, count_ms */);   // not part of the ABI (gsr_neighbours.cpp)
+extern "C" int gsr_debug_cluster_times(gsr_ctx* ctx, float* out /* index_ms, core_ms, union_ms, border_ms */);   // not part of the ABI (gsr_clusters.cpp)
 
 #define CHECK(call)                                                                                     \
     do {                                                                                                \
@@ -186,6 +191,8 @@ int main(int argc, char** argv)
     uint32_t histogram_bins = 256;
     double nb_radius = 0.0;             // 0: off
     uint32_t nb_cap = 64;
+    double cl_radius = 0.0;             // 0: off
+    uint32_t cl_min_pts = 0;
     int32_t pick_xy[2] = {0, 0};
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -221,13 +228,21 @@ int main(int argc, char** argv)
             if (colon != std::string::npos) nb_cap = (uint32_t)std::atoi(v.c_str() + colon + 1);
             if (!(nb_radius > 0.0) || nb_cap < 1 || nb_cap > GSR_NEIGHBOUR_MAX_CAP) { std::fprintf(stderr, "--neighbours RADIUS[:CAP]: RADIUS > 0, CAP in 1 .. 4095\n"); return 2; }
         }
+        else if (a == "--clusters" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            const size_t colon = v.find(':');
+            cl_radius = std::atof(v.c_str());
+            int mp = colon != std::string::npos ? std::atoi(v.c_str() + colon + 1) : 0;
+            if (!(cl_radius > 0.0) || mp < 0 || mp > (int)GSR_NEIGHBOUR_MAX_CAP) { std::fprintf(stderr, "--clusters RADIUS[:MIN_PTS]: RADIUS > 0, MIN_PTS in 0 .. 4095\n"); return 2; }
+            cl_min_pts = (uint32_t)mp;
+        }
         else if (a == "--duplicate" && i + 1 < argc) { duplicate_fraction = std::atof(argv[++i]); if (!(duplicate_fraction >= 0.0 && duplicate_fraction <= 1.0)) { std::fprintf(stderr, "--duplicate FRACTION must be in [0, 1]\n"); return 2; } }
         else if (a == "--reserve") reserve = true;
         else if (a == "--scene-arrays") scene_arrays = true;
         else if (a == "--scene-edit") scene_edit = next();
         else if (a == "--share-scene") share_scene = true;
         else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--share-scene]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--clusters RADIUS[:MIN_PTS]] [--share-scene]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
@@ -642,6 +657,28 @@ int main(int argc, char** argv)
         CHECK(gsr_select_neighbours(ctx[0], nb_radius, nb_cap, 0, 0, 0, std::min(3u, nb_cap + 1u), GSR_SELOP_REPLACE, &nb_selected, nullptr));
         nb_select_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3;
     }
+    // --clusters: the islands at the linking radius, the stages timed apart, the small-island pick checked against the sizes
+    gsr_cluster_info cl_info{};
+    double cl_ms = 1e30, cl_stage_ms[4] = {1e30, 1e30, 1e30, 1e30}, cl_select_ms = 0;
+    uint32_t cl_selected = 0, cl_n = 0;
+    unsigned long long cl_small = 0;
+    if (cl_radius > 0.0) {
+        ctx0 = ctx[0];
+        CHECK(gsr_scene_count(ctx[0], &cl_n));
+        std::vector<uint32_t> labels(cl_n), sizes(cl_n);
+        for (int t = 0; t < 5; t++) {
+            const auto t0 = std::chrono::steady_clock::now();
+            CHECK(gsr_clusters(ctx[0], cl_radius, cl_min_pts, 0, 0, labels.data(), sizes.data(), cl_n, &cl_info));
+            cl_ms = std::min(cl_ms, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3);
+            float stage[4] = {0, 0, 0, 0};
+            CHECK(gsr_debug_cluster_times(ctx[0], stage));
+            for (int k = 0; k < 4; k++) cl_stage_ms[k] = std::min(cl_stage_ms[k], (double)stage[k]);
+        }
+        for (uint32_t i = 0; i < cl_n; i++) cl_small += sizes[i] < 10u;
+        const auto t0 = std::chrono::steady_clock::now();
+        CHECK(gsr_select_clusters(ctx[0], cl_radius, cl_min_pts, 0, 0, 0, 10, GSR_SELOP_REPLACE, &cl_selected, nullptr));
+        cl_select_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3;
+    }
     // --duplicate (last of all: it grows the scene): the selection duplicated on the device, twice
     double duplicate_ms = 0, duplicate_again_ms = 0, reserve_ms = 0;
     uint32_t dup_selected = 0, dup_first = 0, dup_count = 0, dup_capacity = 0, dup_n = 0;
@@ -731,6 +768,14 @@ int main(int argc, char** argv)
                     nb_radius, nb_cap, nb_n, nb_info.in_scope, nb_info.nonfinite, (unsigned long long)nb_info.pair_bound, (unsigned long long)nb_info.budget, nb_ms,
                     nb_build_ms, nb_count_ms, nb_count_ms > 0 ? (double)nb_info.pair_bound / (nb_count_ms * 1e-3) : 0.0, nb_median, nb_few, nb_select_ms, nb_selected,
                     nb_few == nb_selected ? "true" : "false");
+    if (cl_radius > 0.0)
+        std::printf(", \"clusters\": {\"radius\": %.17g, \"min_pts\": %u, \"n\": %u, \"in_scope\": %u, \"nonfinite\": %u, \"pair_bound\": %llu, \"budget\": %llu, "
+                    "\"clusters_ms\": %.4f, \"index_ms\": %.4f, \"core_ms\": %.4f, \"union_ms\": %.4f, \"border_ms\": %.4f, \"core\": %u, \"border\": %u, "
+                    "\"noise\": %u, \"clusters\": %u, \"largest_label\": %u, \"largest_size\": %u, \"smaller_than_10\": %llu, \"select_clusters_ms\": %.4f, "
+                    "\"selected\": %u, \"sizes_equal_selection\": %s}",
+                    cl_radius, cl_min_pts, cl_n, cl_info.in_scope, cl_info.nonfinite, (unsigned long long)cl_info.pair_bound, (unsigned long long)cl_info.budget, cl_ms,
+                    cl_stage_ms[0], cl_stage_ms[1], cl_stage_ms[2], cl_stage_ms[3], cl_info.core, cl_info.border, cl_info.noise, cl_info.clusters, cl_info.largest_label,
+                    cl_info.largest_size, cl_small, cl_select_ms, cl_selected, cl_small == cl_selected ? "true" : "false");
     if (duplicate_fraction >= 0.0)
         std::printf(", \"duplicate_fraction\": %g, \"duplicate_first\": %u, \"duplicate_count\": %u, \"duplicate_reserved\": %s, \"reserve_ms\": %.4f, "
                     "\"duplicate_ms\": %.4f, \"duplicate_again_ms\": %.4f, \"count_after\": %u, \"capacity_after\": %u",
