@@ -529,6 +529,20 @@ struct gsr_ctx {
         float ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};           // index, core, union + flatten, border + sizes of the last call (gsr_debug_cluster_times)
     } cl;
 
+    // k nearest neighbours (gsr_knn.cpp): what gsr_knn / gsr_select_knn hold beside the neighbour scratch, the context's own; the
+    // first such call allocates it, it only grows, and the context's end frees it
+    struct Knn {
+        gsr::DevBuf<uint32_t> words;            // KNN_INFO_WORDS of KnnInfo
+        gsr::DevBuf<uint32_t> found;            // `rows` each: the lists' lengths and the values by splat
+        gsr::DevBuf<double> values;
+        uint32_t rows = 0;
+        gsr::DevBuf<uint32_t> idx;              // `slots` each (rows * k of the calls that asked for lists): indices and squared distances
+        gsr::DevBuf<double> d2;
+        uint64_t slots = 0;
+        hipEvent_t ev = nullptr;                // behind the walk
+        float ms[2] = {0.0f, 0.0f};             // index with its bound, fill and walk of the last call (gsr_debug_knn_times)
+    } knn;
+
     // frame delivery (gsr_delivery_open): a ring of pinned host blocks, each with its device staging and "copy done" event
     struct Delivery {
         struct Slot {
@@ -641,9 +655,9 @@ int set_read(gsr_ctx* c, const SplatSet& s, const char* who, uint32_t* words, ui
 int hidden_ensure(gsr_ctx* c);
 int select_ensure(gsr_ctx* c);
 int select_fold_and_count(gsr_ctx* c, int op, uint32_t* selected);
-// gsr_neighbours.cpp, for the calls that walk the spatial index (neighbours, clusters).  NbCall: one call's scope and index.
-// nb_check: the refusals they share, in the header's order, with `cap` in cap_min .. GSR_NEIGHBOUR_MAX_CAP under the name
-// cap_name; nothing is touched.  nb_index: everything up to the first walk -- the context's scratch (allocated by the first call,
+// gsr_neighbours.cpp, for the calls that walk the spatial index (neighbours, clusters, k nearest neighbours).  NbCall: one call's scope and index.
+// nb_check: the refusals they share, in the header's order, with `cap` in cap_min .. cap_max under the name cap_name; nothing is
+// touched.  nb_index: everything up to the first walk -- the context's scratch (allocated by the first call,
 // only grown), the index, its bound against the budget, *info.  GSR_ERR_ARG (with *info filled) when the bound is above the
 // budget: no walk has been launched.  n >= 1; the device is current and no member's stream holds work.
 struct NbCall {
@@ -652,7 +666,8 @@ struct NbCall {
     uint32_t n, indexed;
     uint32_t* hist;                                   // the device counters (null: the call wants none)
 };
-int nb_check(gsr_ctx* c, const char* who, double radius, uint32_t cap, uint32_t scope, uint64_t budget, uint32_t cap_min = 1u, const char* cap_name = "cap");
+int nb_check(gsr_ctx* c, const char* who, double radius, uint32_t cap, uint32_t scope, uint64_t budget, uint32_t cap_min = 1u, const char* cap_name = "cap",
+             uint32_t cap_max = GSR_NEIGHBOUR_MAX_CAP);
 int nb_index(gsr_ctx* c, const char* who, double radius, uint32_t cap, uint32_t scope, uint64_t budget, bool want_hist, NbCall* call, gsr_neighbour_info* info);
 // gsr_contrib.cpp: what the blocking calls that read per-splat state of a scene do first: waits for every member's stream, so
 // that nothing of any member (a contribution pass, an edit) is in flight afterwards

@@ -629,6 +629,36 @@ void launch_cl_sizes(uint32_t n, const ClArrays& a, int cu_count, hipStream_t s)
 void launch_cl_select_sizes(const uint32_t* sizes, const AttrScope& sc, uint32_t n, uint32_t lo, uint32_t hi, uint32_t* scratch, uint32_t nwords, hipStream_t s);
 void launch_cl_select_label(const uint32_t* label, uint32_t n, uint32_t target, uint32_t* scratch, uint32_t nwords, hipStream_t s);
 
+// k nearest neighbours (k_knn.hip; DESIGN.md section 4, "k nearest neighbours"): for every splat in scope the k nearest others in
+// scope within `radius`, ordered by (d2, index), over the index above; a per-splat value (distance to the k-th, or the mean
+// distance to those found) and the splats of a value range as a picker.
+constexpr uint32_t KNN_MAX_K = 32;                          // GSR_KNN_MAX_K
+constexpr uint32_t KNN_NONE = 0xffffffffu;                  // GSR_KNN_NONE: an empty list slot
+constexpr int KNN_KTH = 0, KNN_MEAN = 1;                    // GSR_KNN_KTH / GSR_KNN_MEAN
+constexpr uint32_t KNN_LDS_BYTES = 48u * 1024u;             // the lists of one workgroup at most: three workgroups in a CU's 160 KiB
+// the device words of one call, zeroed by the host in front of the walk.  The values are non-negative doubles, so their bit
+// patterns order as unsigned integers: vmax is the largest pattern, nvmin the largest COMPLEMENT of one (0: no finite value).
+struct KnnInfo {
+    uint32_t complete, finite_values;      // entries with a full list; entries with a finite value
+    unsigned long long nvmin, vmax;
+};
+struct KnnArrays {
+    uint32_t* found;                       // n
+    double* values;                        // n
+    uint32_t* idx;                         // n * k (null: no lists)
+    double* d2;                            // n * k
+    KnnInfo* info;
+};
+// lanes of a workgroup of the walk for this k: the most of 256, 128, 64 whose lists (12 bytes per lane and slot) fit KNN_LDS_BYTES
+inline uint32_t knn_threads(uint32_t k) { return k * 12u * 256u <= KNN_LDS_BYTES ? 256u : k * 12u * 128u <= KNN_LDS_BYTES ? 128u : 64u; }
+// every row as a splat outside the index has it: found 0, value +inf in scope and NaN outside, the slots KNN_NONE and +inf
+void launch_knn_fill(const AttrScope& sc, uint32_t n, uint32_t k, const KnnArrays& a, int cu_count, hipStream_t s);
+// the walk: found, value and (a.idx) the k slots of every entry at its splat's row; hist (k + 1 words, zeroed by the caller but for
+// hist0's share) += the entries by found; a.info += complete, finite_values, min and max.  indexed, n as launch_nb_count's.
+void launch_knn(const NbIndex& ix, uint32_t indexed, uint32_t n, uint32_t k, int stat, const KnnArrays& a, uint32_t* hist, int cu_count, hipStream_t s);
+// scratch <- the splats i < n in scope with lo <= values[i] && (values[i] < hi || open_hi): every word of it is stored
+void launch_knn_select(const double* values, const AttrScope& sc, uint32_t n, double lo, double hi, bool open_hi, uint32_t* scratch, uint32_t nwords, hipStream_t s);
+
 // Selection overlay (k_overlay.hip; DESIGN.md section 4, "Selection overlay"): the last frame's bin lists walked once more, the
 // weight w = T * B of every fragment of a SELECTED splat summed per pixel (cover) and, with the splat's colour, turned into the
 // frame with those splats tinted (overlay).  Reads the framebuffer, never writes it.

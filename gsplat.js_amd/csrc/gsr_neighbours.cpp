@@ -25,13 +25,14 @@ constexpr uint32_t NB_MAX_ROWS = 1u << 29;            // twice as many buckets s
 }  // namespace
 
 // The refusals every call over the index shares, in the header's order.  Nothing is touched by a refused call.
-int gsr::nb_check(gsr_ctx* c, const char* who, double radius, uint32_t cap, uint32_t scope, uint64_t budget, uint32_t cap_min, const char* cap_name)
+int gsr::nb_check(gsr_ctx* c, const char* who, double radius, uint32_t cap, uint32_t scope, uint64_t budget, uint32_t cap_min, const char* cap_name,
+                  uint32_t cap_max)
 {
     if (!(std::isfinite(radius) && radius > 0.0)) return fail(c, GSR_ERR_ARG, "%s: radius (%g) must be finite and > 0", who, radius);
     const double r2 = radius * radius, inv = 1.0 / radius, inv_h = 1.0 / (radius * (1.0 + 1.0 / 1024.0));
     if (!(std::isnormal(r2) && std::isnormal(inv) && std::isnormal(inv_h)))
         return fail(c, GSR_ERR_ARG, "%s: radius (%g): radius * radius and 1 / radius must be finite and normal", who, radius);
-    if (cap < cap_min || cap > GSR_NEIGHBOUR_MAX_CAP) return fail(c, GSR_ERR_ARG, "%s: %s (%u) must be in %u .. %u", who, cap_name, cap, cap_min, GSR_NEIGHBOUR_MAX_CAP);
+    if (cap < cap_min || cap > cap_max) return fail(c, GSR_ERR_ARG, "%s: %s (%u) must be in %u .. %u", who, cap_name, cap, cap_min, cap_max);
     if (scope & ~(ATTR_SCOPE_SELECTED | ATTR_SCOPE_VISIBLE)) return fail(c, GSR_ERR_ARG, "%s: unknown scope flags 0x%x", who, scope);
     if (budget > GSR_NEIGHBOUR_MAX_BUDGET)
         return fail(c, GSR_ERR_ARG, "%s: budget (%llu) is above GSR_NEIGHBOUR_MAX_BUDGET (%llu)", who, (unsigned long long)budget,

@@ -103,6 +103,10 @@ export interface SplatNeighbours { counts: Uint32Array; hist: Uint32Array; inSco
 export interface ClusterOptions { minPts?: number; scope?: NeighbourScope | NeighbourScope[]; budget?: number }
 export interface SplatClusters { labels: Uint32Array; sizes: Uint32Array; inScope: number; nonfinite: number; pairBound: number; core: number; border: number;
     noise: number; clusters: number; largestLabel: number; largestSize: number }
+export type KnnStat = "kth" | "mean";
+export interface KnnOptions { k?: number; stat?: KnnStat; scope?: NeighbourScope | NeighbourScope[]; budget?: number }
+export interface SplatKnn { found: Uint32Array; values: Float64Array; hist: Uint32Array; idx?: Uint32Array; d2?: Float64Array; inScope: number; nonfinite: number;
+    pairBound: number; complete: number; finiteValues: number; valueMin: number; valueMax: number }
 export interface SplatHistogram { counts: Uint32Array; below: number; above: number; nan: number; edges: Float64Array }
 export interface Contribution { weight: BigUint64Array; peak: Float32Array; pixels: Uint32Array; frames: number }
 /** A screen region: the pixels [x0, x1) x [y0, y1), optionally one byte per pixel of the rectangle (non-zero = inside; rows
@@ -399,6 +403,19 @@ export class HIPRenderer {
     splatClusters(radius: number, options?: ClusterOptions): SplatClusters;
     selectClusters(radius: number, options?: ClusterOptions & { below?: number; atLeast?: number; op?: SelectOp }): number;
     selectClusterAt(radius: number, options: ClusterOptions & { seed?: number; largest?: boolean; op?: SelectOp }): number;
+    /** k nearest neighbours: for every splat in scope the k (1 .. 32, default 8) nearest OTHER splats in scope within `radius`,
+     *  ascending by (squared distance, index), equal distances to the smaller index.  splatKnn: found[i] = how many there are;
+     *  with lists: true, idx and d2 hold their indices and squared distances, row i at [i * k], padded with 0xffffffff / Infinity;
+     *  values[i] = the distance to the k-th (stat "kth"; Infinity without one) or the mean distance to those found (stat "mean",
+     *  the default; Infinity with none), NaN outside the scope; hist[t] = the splats in scope with found == t; complete = those
+     *  with k; finiteValues, valueMin / valueMax over the finite values.  selectKnn picks lo <= value < hi (hi undefined or
+     *  Infinity: no upper end, the Infinity values included) and folds them into the selection with `op`, returning the number of
+     *  selected splats.  selectStatisticalOutliers is statistical outlier removal: it picks value >= threshold = mean + stdRatio
+     *  (default 2) * sample standard deviation of the finite mean distances, the splats without a neighbour included; then
+     *  Scene.eraseSelection(readSelection()) removes them.  All index the device scene as it is now; budget as splatNeighbours. */
+    splatKnn(radius: number, options?: KnnOptions & { lists?: boolean }): SplatKnn;
+    selectKnn(radius: number, options?: KnnOptions & { lo?: number; hi?: number; op?: SelectOp }): number;
+    selectStatisticalOutliers(radius: number, options?: { k?: number; stdRatio?: number; scope?: NeighbourScope | NeighbourScope[]; budget?: number; op?: SelectOp }): { selected: number; threshold: number };
     dispose(): void;
     /** RGBA8, row 0 = top, round(clamp(x,0,1)*255), premultiplied alpha */
     /** RGBA8, row 0 = top; pass an array of width*height*4 elements to have it filled and returned (no allocation per frame). */

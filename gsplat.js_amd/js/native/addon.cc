@@ -1584,6 +1584,88 @@ napi_value SelectClusterAt(napi_env env, napi_callback_info info)
     return rc ? throw_gsr(env, c, rc, "gsr_select_cluster_at") : count_value(env, count);
 }
 
+// ---- k nearest neighbours (gsr_knn / gsr_select_knn) ----
+// radius, k, scope, budget and stat of the two calls below (argv[1 .. 5]; the budget a number, 0: the library's default); false: an
+// error is pending
+bool get_knn_args(napi_env env, napi_value* argv, double* radius, uint32_t* k, uint32_t* scope, uint64_t* budget, int32_t* stat)
+{
+    double b;
+    if (!get_f64(env, argv[1], radius) || napi_get_value_uint32(env, argv[2], k) != napi_ok || napi_get_value_uint32(env, argv[3], scope) != napi_ok ||
+        !get_f64(env, argv[4], &b) || napi_get_value_int32(env, argv[5], stat) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "knn: radius, k, scope, budget and stat must be numbers");
+        return false;
+    }
+    if (*k < 1 || *k > GSR_KNN_MAX_K) { napi_throw_range_error(env, nullptr, "knn: k must be in 1 .. 32"); return false; }
+    if (!(b >= 0.0 && b <= 18446744073709549568.0)) { napi_throw_range_error(env, nullptr, "knn: budget must be a non-negative number"); return false; }
+    *budget = (uint64_t)b;
+    return true;
+}
+
+// knn(handle, radius, k, scope, budget, stat, lists) -> { found: Uint32Array(n), values: Float64Array(n), hist: Uint32Array(k + 1), and with lists != 0
+// idx: Uint32Array(n * k), d2: Float64Array(n * k); inScope, nonfinite, pairBound, budget, complete, finiteValues, valueMin, valueMax }
+napi_value Knn(napi_env env, napi_callback_info info)
+{
+    napi_value argv[7];
+    if (!get_args(env, info, 7, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    double radius;
+    uint32_t k, scope, n = 0;
+    uint64_t budget;
+    int32_t stat, lists;
+    if (!c || !get_knn_args(env, argv, &radius, &k, &scope, &budget, &stat) || !get_i32(env, argv[6], &lists)) return nullptr;
+    int rc = gsr_scene_count(c, &n);
+    if (rc) return throw_gsr(env, c, rc, "gsr_scene_count");
+    const size_t slots = lists ? (size_t)n * k : 0;
+    void *found = nullptr, *values = nullptr, *hist = nullptr, *idx = nullptr, *d2 = nullptr;
+    napi_value fb, farr, vb, varr, hb, harr, ib, iarr, db, darr, out;
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, (size_t)n * 4, &found, &fb));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_uint32_array, n, fb, 0, &farr));
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, (size_t)n * 8, &values, &vb));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_float64_array, n, vb, 0, &varr));
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, ((size_t)k + 1) * 4, &hist, &hb));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_uint32_array, (size_t)k + 1, hb, 0, &harr));
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, slots * 4, &idx, &ib));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_uint32_array, slots, ib, 0, &iarr));
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, slots * 8, &d2, &db));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_float64_array, slots, db, 0, &darr));
+    gsr_knn_info ki{};
+    rc = gsr_knn(c, radius, k, scope, budget, stat, n ? (uint32_t*)found : nullptr, slots ? (uint32_t*)idx : nullptr, slots ? (double*)d2 : nullptr,
+                 n ? (double*)values : nullptr, n, (uint32_t*)hist, &ki);
+    if (rc) return throw_gsr(env, c, rc, "gsr_knn");
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "found", farr));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "values", varr));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "hist", harr));
+    if (lists) {
+        NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "idx", iarr));
+        NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "d2", darr));
+    }
+    if (!set_u32(env, out, "inScope", ki.in_scope) || !set_u32(env, out, "nonfinite", ki.nonfinite) || !set_f64(env, out, "pairBound", (double)ki.pair_bound) ||
+        !set_f64(env, out, "budget", (double)ki.budget) || !set_u32(env, out, "complete", ki.complete) || !set_u32(env, out, "finiteValues", ki.finite_values) ||
+        !set_f64(env, out, "valueMin", ki.value_min) || !set_f64(env, out, "valueMax", ki.value_max)) return nullptr;
+    return out;
+}
+
+// selectKnn(handle, radius, k, scope, budget, stat, lo, hi, op) -> selected   (hi +Infinity: no upper end)
+napi_value SelectKnn(napi_env env, napi_callback_info info)
+{
+    napi_value argv[9];
+    if (!get_args(env, info, 9, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    double radius, lo, hi;
+    uint32_t k, scope;
+    uint64_t budget;
+    int32_t stat, op;
+    if (!c || !get_knn_args(env, argv, &radius, &k, &scope, &budget, &stat)) return nullptr;
+    if (!get_f64(env, argv[6], &lo) || !get_f64(env, argv[7], &hi) || !get_i32(env, argv[8], &op)) {
+        napi_throw_type_error(env, nullptr, "selectKnn: lo, hi and op must be numbers");
+        return nullptr;
+    }
+    uint32_t count = 0;
+    const int rc = gsr_select_knn(c, radius, k, scope, budget, stat, lo, hi, op, &count, nullptr);
+    return rc ? throw_gsr(env, c, rc, "gsr_select_knn") : count_value(env, count);
+}
+
 // ---- selection overlay (gsr_set_overlay / gsr_overlay_async / gsr_read_overlay* / gsr_delivery_set_overlay) ----
 // setOverlay(handle, on, r, g, b, mix): on = 0 switches the overlay off (the other arguments are not read)
 napi_value SetOverlay(napi_env env, napi_callback_info info)
@@ -1701,6 +1783,7 @@ napi_value Init(napi_env env, napi_value exports)
         {"attrStats", AttrStats}, {"attrHistogram", AttrHistogram}, {"selectAttr", SelectAttr},
         {"neighbours", Neighbours}, {"selectNeighbours", SelectNeighbours},
         {"clusters", Clusters}, {"selectClusters", SelectClusters}, {"selectClusterAt", SelectClusterAt},
+        {"knn", Knn}, {"selectKnn", SelectKnn},
         {"setOverlay", SetOverlay}, {"readOverlay", ReadOverlay}, {"readOverlayPixels", ReadOverlayPixels},
         {"deliverySetOverlay", DeliverySetOverlay}, {"setOutline", SetOutline},
     };

@@ -603,6 +603,52 @@ class HIPRenderer {
             if (o2.seed !== undefined && (!Number.isInteger(o2.seed) || o2.seed < 0 || o2.seed >= CLUSTER_LARGEST)) throw new Error("selectClusterAt: seed must be a splat index");
             return this._n.selectClusterAt(this._h, ...args, o2.largest === true ? CLUSTER_LARGEST : o2.seed, code(OPS, o2.op, "replace", "op"));
         };
+        // ---- k nearest neighbours (gsr_knn / gsr_select_knn): per-splat neighbour lists, and statistical outlier removal ----
+        //   renderer.selectStatisticalOutliers(0.1, { k: 8, stdRatio: 2 }); scene.eraseSelection(renderer.readSelection());
+        //   const { found, idx, d2, values } = renderer.splatKnn(0.1, { k: 8, lists: true });   // row i of idx / d2 at [i * k]
+        // For every splat in scope the k (1 .. 32, default 8) nearest OTHER splats in scope within `radius`, ascending by (squared
+        // distance, index): found[i] how many there are, idx / d2 (lists: true) their indices and squared distances, padded with
+        // 0xffffffff / Infinity.  values[i]: stat "kth", the distance to the k-th (Infinity without one); "mean" (the default), the mean
+        // distance to those found (Infinity with none); NaN outside the scope.  hist[t]: the splats in scope with found == t.
+        // selectKnn picks lo <= value < hi (hi undefined or Infinity: no upper end, the Infinity values included).
+        // selectStatisticalOutliers picks value >= mean + stdRatio * (sample standard deviation) of the finite values and returns
+        // { selected, threshold }.  scope and budget as splatNeighbours.
+        const KNN_STATS = { kth: 0, mean: 1 };
+        const knnArgs = (radius, o) => {
+            const k = o.k === undefined ? 8 : o.k, budget = o.budget === undefined || o.budget === null ? 0 : Number(o.budget);
+            if (!Number.isInteger(k) || k < 1 || k > 32) throw new Error("k must be an integer in 1 .. 32");
+            if (!(budget >= 0)) throw new Error("budget must be a non-negative number");
+            return [Number(radius), k, nbScope(o), budget, code(KNN_STATS, o.stat, "mean", "stat")];
+        };
+        this.splatKnn = (radius, options) => {
+            const o2 = options || {};
+            const r = this._n.knn(this._h, ...knnArgs(radius, o2), o2.lists ? 1 : 0);
+            const out = { found: r.found, values: r.values, hist: r.hist, inScope: r.inScope, nonfinite: r.nonfinite, pairBound: r.pairBound, complete: r.complete,
+                          finiteValues: r.finiteValues, valueMin: r.valueMin, valueMax: r.valueMax };
+            if (o2.lists) { out.idx = r.idx; out.d2 = r.d2; }
+            return out;
+        };
+        this.selectKnn = (radius, options) => {
+            const o2 = options || {}, args = knnArgs(radius, o2);
+            const lo = o2.lo === undefined ? 0 : Number(o2.lo), hi = o2.hi === undefined || o2.hi === null ? Infinity : Number(o2.hi);
+            if (Number.isNaN(lo) || Number.isNaN(hi) || lo > hi) throw new Error("selectKnn: lo <= hi must hold, neither a NaN");
+            return this._n.selectKnn(this._h, ...args, lo, hi, code(OPS, o2.op, "replace", "op"));
+        };
+        this.selectStatisticalOutliers = (radius, options) => {
+            const o2 = options || {}, stdRatio = o2.stdRatio === undefined ? 2 : Number(o2.stdRatio);
+            const o3 = { k: o2.k, scope: o2.scope, budget: o2.budget, stat: "mean" };
+            const values = this.splatKnn(radius, o3).values;
+            let count = 0, sum = 0;
+            for (let i = 0; i < values.length; i++) if (Number.isFinite(values[i])) { count++; sum += values[i]; }
+            let threshold = Infinity;   // fewer than two finite values: only the splats without a neighbour
+            if (count >= 2) {
+                const mu = sum / count;
+                let sq = 0;
+                for (let i = 0; i < values.length; i++) if (Number.isFinite(values[i])) sq += (values[i] - mu) * (values[i] - mu);
+                threshold = mu + stdRatio * Math.sqrt(sq / (count - 1));
+            }
+            return { selected: this.selectKnn(radius, { ...o3, lo: threshold, op: o2.op }), threshold };
+        };
         // ---- selection overlay (gsr_set_overlay / gsr_read_overlay*): the last frame with the selected splats tinted ----
         //   renderer.setSelectionOverlay({ tint: [1, 0.5, 0], mix: 0.5 }); renderer.render(scene, cam);
         //   const { rgba, cover } = renderer.readOverlay();   // or readPixels({ overlay: true }), or openDelivery(n, { overlay: true })

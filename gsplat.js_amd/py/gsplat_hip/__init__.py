@@ -95,6 +95,14 @@ class GsrClusterInfo(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class GsrKnnInfo(ctypes.Structure):
+    _fields_ = [("in_scope", ctypes.c_uint32), ("nonfinite", ctypes.c_uint32), ("pair_bound", ctypes.c_uint64), ("budget", ctypes.c_uint64),
+                ("complete", ctypes.c_uint32), ("finite_values", ctypes.c_uint32), ("value_min", ctypes.c_double), ("value_max", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: (float if t is ctypes.c_double else int)(getattr(self, k)) for k, t in self._fields_}
+
+
 class GsrDepthLayout(ctypes.Structure):
     _fields_ = [("format", ctypes.c_int32), ("step", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
                 ("stride", ctypes.c_int32), ("reserved", ctypes.c_int32), ("offset", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
@@ -115,7 +123,19 @@ SCOPES = {"selected": 1, "visible": 2}                                     # GSR
 ATTR_MAX_BINS = 4096
 NEIGHBOUR_MAX_CAP = 4095                                                   # GSR_NEIGHBOUR_MAX_CAP
 NEIGHBOUR_DEFAULT_BUDGET, NEIGHBOUR_MAX_BUDGET = 1 << 34, 1 << 38          # GSR_NEIGHBOUR_*_BUDGET
+KNN_MAX_K, KNN_NONE = 32, 0xffffffff                                       # GSR_KNN_MAX_K, GSR_KNN_NONE (an empty list slot)
+KNN_STATS = {"kth": 0, "mean": 1}                                          # GSR_KNN_*
 CLUSTER_NONE = CLUSTER_LARGEST = 0xffffffff                                # GSR_CLUSTER_NONE (a label), GSR_CLUSTER_LARGEST (a seed)
+
+
+def knn_outlier_threshold(values, std_ratio):
+    """The threshold of select_statistical_outliers, in f64: mu + std_ratio * sigma over the finite values, sigma the sample
+    standard deviation (n - 1); +inf with fewer than two finite values."""
+    v = np.asarray(values, dtype=np.float64)
+    v = v[np.isfinite(v)]
+    if v.size < 2:
+        return float("inf")
+    return float(np.mean(v) + np.float64(std_ratio) * np.std(v, ddof=1))
 
 
 def attr_edges(lo, hi, bins):
@@ -169,6 +189,7 @@ EXPORTS = [
     "gsr_attr_stats", "gsr_attr_histogram", "gsr_select_attr",
     "gsr_neighbours", "gsr_select_neighbours",
     "gsr_clusters", "gsr_select_clusters", "gsr_select_cluster_at",
+    "gsr_knn", "gsr_select_knn",
     "gsr_set_overlay", "gsr_overlay_async", "gsr_read_overlay", "gsr_read_overlay_rgba8", "gsr_overlay_device_ptr", "gsr_delivery_set_overlay",
     "gsr_set_overlay_outline",
 ]
@@ -340,6 +361,9 @@ def load_library(path=None):
     L.gsr_clusters.argtypes = [vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, vp, vp, ctypes.c_uint32, ci]
     L.gsr_select_clusters.argtypes = [vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, u32p, ci]
     L.gsr_select_cluster_at.argtypes = [vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, ctypes.c_uint32, ctypes.c_int32, u32p, ci]
+    ki = ctypes.POINTER(GsrKnnInfo)
+    L.gsr_knn.argtypes = [vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, ctypes.c_int32, vp, vp, vp, vp, ctypes.c_uint32, vp, ki]
+    L.gsr_select_knn.argtypes = [vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32, u32p, ki]
     L.gsr_set_overlay.argtypes = [vp, ctypes.POINTER(GsrOverlayOptions)]
     L.gsr_set_overlay_outline.argtypes = [vp, ctypes.POINTER(GsrOutlineOptions)]
     L.gsr_overlay_async.argtypes = [vp]
@@ -1286,6 +1310,64 @@ class HIPRenderer:
         self._check_neighbours(self._L.gsr_select_cluster_at(self._ctx, radius, min_pts, self._scope_flags(scope), budget, seed, self._select_code(SELECT_OPS, op, "op"),
                                                              ctypes.byref(count), ctypes.byref(info)), info)
         return count.value, info.as_dict()
+
+    # -- k nearest neighbours (gsr_knn / gsr_select_knn): per-splat neighbour lists, and statistical outlier removal --
+    @staticmethod
+    def _knn_args(radius, k, stat, budget):
+        k = int(k)
+        if not 1 <= k <= KNN_MAX_K:
+            raise ValueError("k must be in 1 .. %d" % KNN_MAX_K)
+        if stat not in KNN_STATS:
+            raise ValueError("unknown stat %r (one of %s)" % (stat, ", ".join(KNN_STATS)))
+        budget = 0 if budget is None else int(budget)
+        if budget < 0:
+            raise ValueError("budget must not be negative")
+        return float(radius), k, KNN_STATS[stat], budget
+
+    def knn(self, radius, k=8, stat="mean", scope=(), budget=None, found=True, idx=False, d2=False, values=True, hist=True):
+        """(found uint32[n], idx uint32[n, k], d2 float64[n, k], values float64[n], hist uint32[k + 1], info): for every splat in
+        scope -- scope: any of "selected", "visible"; () is every splat -- the k nearest OTHER splats in scope within `radius`,
+        ascending by (squared distance, index): found[i] how many there are, idx / d2 their indices and squared distances, padded
+        with KNN_NONE / +inf.  values[i]: stat "kth", the distance to the k-th (+inf without one); "mean", the mean distance to
+        those found (+inf with none); NaN outside the scope.  hist[t]: the splats in scope with found == t.  A False argument:
+        None in its place, nothing copied, and without idx and d2 the lists are not stored at all.  info: in_scope, nonfinite,
+        pair_bound, budget, complete, finite_values, value_min, value_max.  budget as neighbours() takes it."""
+        radius, k, stat, budget = self._knn_args(radius, k, stat, budget)
+        n = self._count()
+        f = np.zeros(n, np.uint32) if found else None
+        i = np.full((n, k), KNN_NONE, np.uint32) if idx else None
+        d = np.full((n, k), np.inf, np.float64) if d2 else None
+        v = np.full(n, np.nan, np.float64) if values else None
+        h = np.zeros(k + 1, np.uint32) if hist else None
+        info = GsrKnnInfo()
+        ptr = lambda a: a.ctypes.data if a is not None and n else None
+        self._check_neighbours(self._L.gsr_knn(self._ctx, radius, k, self._scope_flags(scope), budget, stat, ptr(f), ptr(i), ptr(d), ptr(v),
+                                               n if found or idx or d2 or values else 0, h.ctypes.data if hist else None, ctypes.byref(info)), info)
+        return f, i, d, v, h, info.as_dict()
+
+    def select_knn(self, radius, k=8, stat="mean", lo=0.0, hi=None, scope=(), op="replace", budget=None):
+        """(selected, info): pick the splats in scope with lo <= value < hi (hi=None or +inf: no upper end, the +inf values
+        included) and fold them into the selection; values as knn() gives them.  With op "replace" it selects exactly the
+        splats in scope whose values[i] of knn(radius, k, stat, scope) satisfy the rule."""
+        radius, k, stat, budget = self._knn_args(radius, k, stat, budget)
+        lo, hi = float(lo), float("inf") if hi is None else float(hi)
+        if lo != lo or hi != hi or lo > hi:
+            raise ValueError("lo <= hi must hold, neither a NaN")
+        count, info = ctypes.c_uint32(0), GsrKnnInfo()
+        self._check_neighbours(self._L.gsr_select_knn(self._ctx, radius, k, self._scope_flags(scope), budget, stat, lo, hi, self._select_code(SELECT_OPS, op, "op"),
+                                                      ctypes.byref(count), ctypes.byref(info)), info)
+        return count.value, info.as_dict()
+
+    def select_statistical_outliers(self, radius, k=8, std_ratio=2.0, scope=(), op="replace"):
+        """(selected, threshold, info): statistical outlier removal.  The mean distance of every splat in scope to its k nearest
+        within `radius` is read back; mu and the sample standard deviation sigma (n - 1) of the finite ones are taken in f64, and
+        the splats with value >= threshold = mu + std_ratio * sigma -- those without a neighbour included -- are folded into the
+        selection.  With fewer than two finite values only the splats without a neighbour are picked (threshold +inf).
+        scene_erase_selected() then removes them."""
+        values = self.knn(radius, k=k, stat="mean", scope=scope, found=False, hist=False)[3]
+        threshold = knn_outlier_threshold(values, std_ratio)
+        selected, info = self.select_knn(radius, k=k, stat="mean", lo=threshold, hi=None, scope=scope, op=op)
+        return selected, threshold, info
 
     # -- selection overlay (gsr_set_overlay / gsr_overlay_async / gsr_read_overlay*): the selected splats tinted --
     def set_overlay(self, tint=(1.0, 0.5, 0.0), mix=0.5):

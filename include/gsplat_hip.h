@@ -952,6 +952,74 @@ int gsr_select_clusters(gsr_ctx *ctx, double radius, uint32_t min_pts, uint32_t 
 int gsr_select_cluster_at(gsr_ctx *ctx, double radius, uint32_t min_pts, uint32_t scope, uint64_t budget,
                           uint32_t seed, int32_t op, uint32_t *selected, gsr_cluster_info *info);
 
+/* ---- k nearest neighbours ---- per-splat neighbour lists, and statistical outlier removal
+ * No interface of the reference stands behind this section either.  A radius count needs the user to know the scene's density in
+ * advance and misjudges a capture whose density varies from the subject to the background.  "Mean distance to the k nearest,
+ * against the scene's own distribution of that value" adapts by itself: point-cloud tools call the filter statistical outlier
+ * removal.  The lists themselves -- indices and squared distances in a defined order -- are what normals, smoothing and
+ * density-aware pruning start from.  These calls make them on the device, over the index of "neighbours", with no gsr_read_scene
+ * and no spatial index on the host.
+ * Definition ("k nearest neighbours").  Scope S, d2(i,j), r2, near(i,j) and the treatment of non-finite rows
+ *   are exactly those of "neighbours": the same f64 expression, in the written order, uncontracted, and a distance of exactly radius
+ *   counts; a splat with a NaN or infinite position component is in scope, is never indexed and is nobody's neighbour.  The search
+ *   is the hybrid form, the k nearest WITHIN radius.  With 1 <= k <= GSR_KNN_MAX_K:
+ *     N_i    = { j in S : near(i,j) }, ordered ascending by the pair (d2(i,j), j): equal distances go to the smaller index
+ *     m_i    = min(k, |N_i|)   for i in S and finite;   0 otherwise                        ("found")
+ *     nn_i[t], dd_i[t] = index and d2 of the t-th element of that order, t < m_i;
+ *                        GSR_KNN_NONE and +inf for m_i <= t < k
+ *     value_i (GSR_KNN_KTH)  = m_i == k ? sqrt(dd_i[k-1]) : +inf        (sqrt correctly rounded, as GSR_ATTR_DISTANCE states it)
+ *     value_i (GSR_KNN_MEAN) = m_i == 0 ? +inf : ( ..((sqrt(dd_i[0]) + sqrt(dd_i[1])) + sqrt(dd_i[2])) .. ) / (double)m_i
+ *                              (f64, summed in ascending t, uncontracted)
+ *     value_i = NaN (0x7ff8000000000000) for i not in S
+ *   A non-finite splat in S has m_i = 0 and value +inf.  The order is total, so the lists do not depend on any visiting order;
+ *   every value is a sequence of correctly rounded f64 operations in a stated order: the same scene, scope, radius, k and stat give
+ *   the same bits on every run, in every context form and through every member of a shared scene.
+ * gsr_knn: found is n words, idx n * k words, d2 n * k doubles, values n doubles, row i of a list at [i * k]; any out pointer may
+ *   be NULL; a non-NULL per-splat pointer with n not equal to the scene's count is refused.  Rows outside S hold found = 0,
+ *   GSR_KNN_NONE, +inf and NaN.  hist is k + 1 words or NULL: hist[t] is the number of splats in S with m_i == t, so
+ *   sum(hist) == info->in_scope.  info may be NULL.  An empty scene, or an empty scope, returns zeros (value_min +inf, value_max -inf).
+ * info: in_scope, nonfinite, pair_bound and budget as in gsr_neighbour_info; complete = the splats with m_i == k; finite_values =
+ *   the splats in S with a finite value_i; value_min / value_max over those finite values, +inf / -inf when there is none, as in
+ *   gsr_attr_stats.  Every field is an integer or a min / max, so every field is exact.
+ * gsr_select_knn picks P = { i in S : lo <= value_i && (value_i < hi || hi == +inf) } and folds P into the selection with `op`
+ *   (GSR_SELOP_*) exactly as the selection calls fold theirs; `selected` means what it means everywhere else.  +inf is a value
+ *   splats really have here -- "no k-th neighbour within radius" -- so hi = +inf means "no upper end": the one difference from
+ *   gsr_select_attr.  lo == hi (both finite) picks nothing.  Statistical outlier removal: read values, take the mean mu and the
+ *   standard deviation sigma of the finite ones on the host, gsr_select_knn(.., lo = mu + ratio * sigma, hi = +inf, ..), then
+ *   gsr_scene_erase_selected.
+ * The consistency guarantee: with GSR_SELOP_REPLACE it selects exactly the splats of S whose values[i], from a gsr_knn call with
+ *   the same radius, k, scope and stat, satisfy the rule.
+ * The work budget is the neighbour budget, with the same constants and the same pair_bound, checked before the walk is launched:
+ *   if pair_bound > budget the call returns GSR_ERR_ARG with a message naming both numbers, fills info's first four fields and
+ *   launches no walk.  A call makes one 27-cell walk of at most pair_bound pair tests.
+ * Both calls are blocking and stateless: they index the scene as it is now, so nothing can go stale after an edit.  They are
+ *   ordered like gsr_select_attr: they wait for every member's stream of a shared scene first.  They read the scene and write none
+ *   of it: no frame state changes.
+ * Refusals (GSR_ERR_ARG with a message, nothing touched, the selection and its count included): a NULL ctx; a radius that is not
+ *   finite, not > 0, or with radius * radius or 1 / radius not finite and normal; k outside 1 .. 32; unknown scope flags, stat or
+ *   op; a NaN bound or lo > hi; a wrong n; a budget above the maximum; a bound above the budget.
+ * The device scratch belongs to the context: the scratch of "neighbours", 4 + 8 bytes per splat for found and values, and 12 bytes
+ *   per splat per k for the lists, only when idx or d2 is asked for.  The first call allocates it, it only grows, and gsr_destroy
+ *   frees it; a context that never calls any of this allocates nothing and launches nothing. */
+typedef struct gsr_knn_info {
+    uint32_t in_scope;      /* splats in S */
+    uint32_t nonfinite;     /* of those, with a NaN or infinite position component (found 0, value +inf) */
+    uint64_t pair_bound;    /* pair tests the walk makes at most, as the implementation counts them */
+    uint64_t budget;        /* the budget that applied */
+    uint32_t complete;      /* splats in S with a full list: m_i == k */
+    uint32_t finite_values; /* splats in S with a finite value */
+    double value_min;       /* over the finite values; +inf: there is none */
+    double value_max;       /* over the finite values; -inf: there is none */
+} gsr_knn_info;
+#define GSR_KNN_MAX_K 32u
+#define GSR_KNN_NONE  0xffffffffu   /* an empty list slot */
+#define GSR_KNN_KTH  0              /* value: the distance to the k-th nearest */
+#define GSR_KNN_MEAN 1              /* value: the mean distance to those found */
+int gsr_knn(gsr_ctx *ctx, double radius, uint32_t k, uint32_t scope, uint64_t budget, int32_t stat,
+            uint32_t *found, uint32_t *idx, double *d2, double *values, uint32_t n, uint32_t *hist, gsr_knn_info *info);
+int gsr_select_knn(gsr_ctx *ctx, double radius, uint32_t k, uint32_t scope, uint64_t budget, int32_t stat,
+                   double lo, double hi, int32_t op, uint32_t *selected, gsr_knn_info *info);
+
 /* ---- selection overlay ---- the selected splats tinted, in read-backs and in delivered frames
  * No interface of the reference stands behind this section either.  gsr_read_selection returns bits; this shows them: a second
  * image beside the frame in which the selected splats carry a tint, and per pixel how much of it they are.

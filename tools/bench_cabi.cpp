@@ -3,7 +3,7 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--clusters RADIUS[:MIN_PTS]] [--share-scene]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--share-scene]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
@@ -48,6 +48,11 @@
 // the best wall time, and by the library's events on the stream the stages apart -- the index with its bound, the core test with the
 // seed, union with flatten, border with sizes; clusters, largest_size and noise, and the check that gsr_select_clusters(0, 10)
 // selects exactly the splats whose sizes[i] is below 10 (`sizes_equal_selection`).
+// --knn RADIUS:K[:kth|mean] (mean unless given) finds every splat's K nearest neighbours within RADIUS: five gsr_knn calls without
+// the lists and five with them, the best wall time of either, and by the library's events on the stream the index build (with its
+// bound) and the walk (with its fill) apart; pair_bound and the pair tests per second it means for the walk, complete,
+// finite_values, the value range, and the check that gsr_select_knn(lo = the mean of the finite values, hi = +inf) selects exactly
+// the splats whose values[i] is at or above it (`values_equal_selection`).
 // --duplicate FRACTION (last of all: it grows the scene) selects that fraction of the splats through gsr_selection_set and calls
 // gsr_scene_duplicate_selected twice -- the second call copies the first one's copies, the same count -- and reports the wall time
 // of either (`duplicate_ms`, `duplicate_again_ms`), the count and the capacity.  With --reserve, gsr_scene_reserve makes room for
@@ -158,6 +163,7 @@ uint64_t fnv1a(const void* p, size_t bytes)
 }
 
 extern "C" int gsr_debug_neighbour_times(gsr_ctx* ctx, float* out /* build_ms, count_ms */);   // not part of the ABI (gsr_neighbours.cpp)
+extern "C" int gsr_debug_knn_times(gsr_ctx* ctx, float* out /* index_ms, walk_ms */);   // not part of the ABI (gsr_knn.cpp)
 extern "C" int gsr_debug_cluster_times(gsr_ctx* ctx, float* out /* index_ms, core_ms, union_ms, border_ms */);   // not part of the ABI (gsr_clusters.cpp)
 
 #define CHECK(call)                                                                                     \
@@ -193,6 +199,9 @@ int main(int argc, char** argv)
     uint32_t nb_cap = 64;
     double cl_radius = 0.0;             // 0: off
     uint32_t cl_min_pts = 0;
+    double knn_radius = 0.0;            // 0: off
+    uint32_t knn_k = 8;
+    int32_t knn_stat = GSR_KNN_MEAN;
     int32_t pick_xy[2] = {0, 0};
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -236,13 +245,22 @@ int main(int argc, char** argv)
             if (!(cl_radius > 0.0) || mp < 0 || mp > (int)GSR_NEIGHBOUR_MAX_CAP) { std::fprintf(stderr, "--clusters RADIUS[:MIN_PTS]: RADIUS > 0, MIN_PTS in 0 .. 4095\n"); return 2; }
             cl_min_pts = (uint32_t)mp;
         }
+        else if (a == "--knn" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            const size_t colon = v.find(':'), colon2 = colon == std::string::npos ? colon : v.find(':', colon + 1);
+            knn_radius = std::atof(v.c_str());
+            const int k = colon != std::string::npos ? std::atoi(v.c_str() + colon + 1) : 0;
+            const std::string stat = colon2 != std::string::npos ? v.substr(colon2 + 1) : "mean";
+            if (!(knn_radius > 0.0) || k < 1 || k > (int)GSR_KNN_MAX_K || (stat != "kth" && stat != "mean")) { std::fprintf(stderr, "--knn RADIUS:K[:kth|mean]: RADIUS > 0, K in 1 .. 32\n"); return 2; }
+            knn_k = (uint32_t)k; knn_stat = stat == "kth" ? GSR_KNN_KTH : GSR_KNN_MEAN;
+        }
         else if (a == "--duplicate" && i + 1 < argc) { duplicate_fraction = std::atof(argv[++i]); if (!(duplicate_fraction >= 0.0 && duplicate_fraction <= 1.0)) { std::fprintf(stderr, "--duplicate FRACTION must be in [0, 1]\n"); return 2; } }
         else if (a == "--reserve") reserve = true;
         else if (a == "--scene-arrays") scene_arrays = true;
         else if (a == "--scene-edit") scene_edit = next();
         else if (a == "--share-scene") share_scene = true;
         else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--clusters RADIUS[:MIN_PTS]] [--share-scene]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--share-scene]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
@@ -679,6 +697,34 @@ int main(int argc, char** argv)
         CHECK(gsr_select_clusters(ctx[0], cl_radius, cl_min_pts, 0, 0, 0, 10, GSR_SELOP_REPLACE, &cl_selected, nullptr));
         cl_select_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3;
     }
+    // --knn: every splat's k nearest within the radius, without and with the lists, the stages timed apart, the pick checked against the values
+    gsr_knn_info knn_info{};
+    double knn_ms[2] = {1e30, 1e30}, knn_index_ms[2] = {1e30, 1e30}, knn_walk_ms[2] = {1e30, 1e30}, knn_select_ms = 0, knn_lo = 0;
+    uint32_t knn_selected = 0, knn_n = 0;
+    unsigned long long knn_above = 0;
+    if (knn_radius > 0.0) {
+        ctx0 = ctx[0];
+        CHECK(gsr_scene_count(ctx[0], &knn_n));
+        std::vector<uint32_t> found(knn_n), idx((size_t)knn_n * knn_k), hist(knn_k + 1u);
+        std::vector<double> d2((size_t)knn_n * knn_k), values(knn_n);
+        for (int lists = 0; lists < 2; lists++)
+            for (int t = 0; t < 5; t++) {
+                const auto t0 = std::chrono::steady_clock::now();
+                CHECK(gsr_knn(ctx[0], knn_radius, knn_k, 0, 0, knn_stat, found.data(), lists ? idx.data() : nullptr, lists ? d2.data() : nullptr, values.data(), knn_n,
+                              hist.data(), &knn_info));
+                knn_ms[lists] = std::min(knn_ms[lists], std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3);
+                float stage[2] = {0, 0};
+                CHECK(gsr_debug_knn_times(ctx[0], stage));
+                knn_index_ms[lists] = std::min(knn_index_ms[lists], (double)stage[0]); knn_walk_ms[lists] = std::min(knn_walk_ms[lists], (double)stage[1]);
+            }
+        double sum = 0;
+        for (uint32_t i = 0; i < knn_n; i++) if (std::isfinite(values[i])) sum += values[i];
+        knn_lo = knn_info.finite_values ? sum / (double)knn_info.finite_values : 0.0;
+        for (uint32_t i = 0; i < knn_n; i++) knn_above += values[i] >= knn_lo;
+        const auto t0 = std::chrono::steady_clock::now();
+        CHECK(gsr_select_knn(ctx[0], knn_radius, knn_k, 0, 0, knn_stat, knn_lo, HUGE_VAL, GSR_SELOP_REPLACE, &knn_selected, nullptr));
+        knn_select_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3;
+    }
     // --duplicate (last of all: it grows the scene): the selection duplicated on the device, twice
     double duplicate_ms = 0, duplicate_again_ms = 0, reserve_ms = 0;
     uint32_t dup_selected = 0, dup_first = 0, dup_count = 0, dup_capacity = 0, dup_n = 0;
@@ -776,6 +822,15 @@ int main(int argc, char** argv)
                     cl_radius, cl_min_pts, cl_n, cl_info.in_scope, cl_info.nonfinite, (unsigned long long)cl_info.pair_bound, (unsigned long long)cl_info.budget, cl_ms,
                     cl_stage_ms[0], cl_stage_ms[1], cl_stage_ms[2], cl_stage_ms[3], cl_info.core, cl_info.border, cl_info.noise, cl_info.clusters, cl_info.largest_label,
                     cl_info.largest_size, cl_small, cl_select_ms, cl_selected, cl_small == cl_selected ? "true" : "false");
+    if (knn_radius > 0.0)
+        std::printf(", \"knn\": {\"radius\": %.17g, \"k\": %u, \"stat\": \"%s\", \"n\": %u, \"in_scope\": %u, \"nonfinite\": %u, \"pair_bound\": %llu, \"budget\": %llu, "
+                    "\"knn_ms\": %.4f, \"index_build_ms\": %.4f, \"walk_ms\": %.4f, \"pair_tests_per_s\": %.4g, \"knn_lists_ms\": %.4f, \"lists_index_build_ms\": %.4f, "
+                    "\"lists_walk_ms\": %.4f, \"complete\": %u, \"finite_values\": %u, \"value_min\": %s, \"value_max\": %s, \"select_lo\": %.17g, "
+                    "\"at_or_above\": %llu, \"select_knn_ms\": %.4f, \"selected\": %u, \"values_equal_selection\": %s}",
+                    knn_radius, knn_k, knn_stat == GSR_KNN_KTH ? "kth" : "mean", knn_n, knn_info.in_scope, knn_info.nonfinite, (unsigned long long)knn_info.pair_bound,
+                    (unsigned long long)knn_info.budget, knn_ms[0], knn_index_ms[0], knn_walk_ms[0], knn_walk_ms[0] > 0 ? (double)knn_info.pair_bound / (knn_walk_ms[0] * 1e-3) : 0.0,
+                    knn_ms[1], knn_index_ms[1], knn_walk_ms[1], knn_info.complete, knn_info.finite_values, json_num(knn_info.value_min).c_str(),
+                    json_num(knn_info.value_max).c_str(), knn_lo, knn_above, knn_select_ms, knn_selected, knn_above == knn_selected ? "true" : "false");
     if (duplicate_fraction >= 0.0)
         std::printf(", \"duplicate_fraction\": %g, \"duplicate_first\": %u, \"duplicate_count\": %u, \"duplicate_reserved\": %s, \"reserve_ms\": %.4f, "
                     "\"duplicate_ms\": %.4f, \"duplicate_again_ms\": %.4f, \"count_after\": %u, \"capacity_after\": %u",
