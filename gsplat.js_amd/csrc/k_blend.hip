@@ -315,9 +315,26 @@ __device__ __forceinline__ void blend_body(const uint32_t* __restrict__ items,
 #endif
             // ---- stage one entry per thread: record, unpacked colour, and a 16-bit mask of the bin's
             //      8x8-pixel quadrants the splat can touch (bit = tile*4 + quadrant).  The mask is a
-            //      conservative cull only: a quadrant is dropped when it lies outside the oriented box
-            //      |vPosition.x|,|vPosition.y| <= 2 (separating axes u, w) or farther from the centre than the
-            //      longer semi-axis.  Pixels that pass are still tested exactly (q <= 4) below. ----
+            //      conservative cull only: pixels that pass are still tested exactly (q <= 4) below, and a
+            //      quadrant without a covered pixel changes no accumulator, so a tighter mask changes no bit.
+            //      A quadrant is dropped when a separating axis lies between its pixel centres and the disc
+            //      |vPosition| <= 2.  With (vxc, vyc) = vPosition at the quadrant's centre, whose pixel centres
+            //      lie within 3.5 px of it in x and in y, a covered centre implies along the axis n:
+            //        n = u:                  |vxc|        <= 2        + 3.5 (|ux| + |uy|)
+            //        n = w:                  |vyc|        <= 2        + 3.5 (|wx| + |wy|)
+            //        n = (u +- w) / sqrt 2:  |vxc +- vyc| <= 2 sqrt 2 + 3.5 (|ux +- wx| + |uy +- wy|)
+            //      and every quadrant farther from the centre than the longer semi-axis (the bounding circle) is
+            //      dropped as well.  u and w alone bound the disc by its square, and the square's corners are where
+            //      most of the visited quadrants without a covered pixel came from; one wave per tile (k_blend,
+            //      k_blend_unfused) tests all four axes, the octagon (counts: DESIGN 8.1).  The slack: 2.0005f allows
+            //      5e-4 for the rounding of the sums here (products rounded one by one, about the quadrant's centre)
+            //      against the walk's fused ones; a diagonal carries the allowances of both sums, q <= 4 in f32
+            //      holds |vx +- vy| to 2 sqrt 2 (1 + 2^-23) = 2.8284275, and |vxc +- vyc| and ep / em are one more
+            //      f32 addition each, of values of a few tens at most (under 1e-5 together):
+            //      2.8284275 + 2 * 5e-4 + 1e-5 < 2.8295f.
+            //      Two waves per tile (k_blend2) keeps u, w and the circle: it cuts every chunk between its two
+            //      waves by COUNTING mask hits, so a tighter mask would move that cut and with it the f32
+            //      association of its images. ----
             // (two waves per tile: two threads per entry, thread t and t + 256, each testing two of the four quadrant rows
             //  -- one byte of the mask -- and writing its share of the record)
             const uint32_t slot = threadIdx.x & (CHUNK - 1), half = SUB == 2 ? threadIdx.x >> 8 : 0u;
@@ -329,13 +346,25 @@ __device__ __forceinline__ void blend_body(const uint32_t* __restrict__ items,
                 const uint32_t i = min(list[e], nsplats - 1u);
                 const float4* rp = reinterpret_cast<const float4*>(rec + i);
                 const float4 ra = rp[0], rb = rp[1];
+                constexpr bool DIAG = SUB == 1;
                 const float eu = 3.5f * (fabsf(ra.z) + fabsf(ra.w)) + 2.0005f;
                 const float ew = 3.5f * (fabsf(rb.x) + fabsf(rb.y)) + 2.0005f;
+                float ep = 0.f, em = 0.f;
+                if constexpr (DIAG) {
+                    ep = 3.5f * (fabsf(ra.z + rb.x) + fabsf(ra.w + rb.y)) + 2.8295f;
+                    em = 3.5f * (fabsf(ra.z - rb.x) + fabsf(ra.w - rb.y)) + 2.8295f;
+                }
                 const float minlen2 = fminf(ra.z * ra.z + ra.w * ra.w, rb.x * rb.x + rb.y * rb.y);
+                // the quadrant centres of the bin, (float)(binX0 + 8 k + 4) and rows alike.  One wave per tile converts them from
+                // the scalar origin again in every chunk (eight v_cvt a wave): as values of the work item they held eight of
+                // the 72 vector registers of seven waves per SIMD across the walk, other values of the item went to scratch for
+                // them, and the four-axis staging spilled on top (20 bytes of scratch a lane instead of 40)
+                int qx0 = binX0 + 4, qy0 = binY0 + 4;
+                if constexpr (DIAG) asm volatile("" : "+s"(qx0), "+s"(qy0));
                 float ucol[4], wcol[4], dcol[4];
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
-                    const float dc = (float)(binX0 + 8 * k + 4) - ra.x;
+                    const float dc = (float)(qx0 + 8 * k) - ra.x;
                     ucol[k] = ra.z * dc; wcol[k] = rb.x * dc;
                     const float dd = fmaxf(fabsf(dc) - 3.5f, 0.0f);
                     dcol[k] = dd * dd;
@@ -344,13 +373,16 @@ __device__ __forceinline__ void blend_body(const uint32_t* __restrict__ items,
                 for (int rr = 0; rr < 4 / SUB; rr++) {
                     // quadrant row r of the bin: all four (one wave per tile), or rows 2*half, 2*half + 1 (two threads per entry)
                     const int r = SUB == 2 ? (int)(2u * half) + rr : rr;
-                    const float dc = (float)(binY0 + 8 * r + 4) - ra.y;
+                    const float dc = (float)(qy0 + 8 * r) - ra.y;
                     const float ur = ra.w * dc, wr = rb.y * dc;
                     const float dd = fmaxf(fabsf(dc) - 3.5f, 0.0f);
                     const float d2 = dd * dd;
 #pragma unroll
                     for (int k = 0; k < 4; k++) {
-                        const bool hit = fabsf(ucol[k] + ur) <= eu && fabsf(wcol[k] + wr) <= ew && (dcol[k] + d2) * minlen2 <= 4.002f;
+                        const float vxc = ucol[k] + ur, vyc = wcol[k] + wr;
+                        bool hit = fabsf(vxc) <= eu && fabsf(vyc) <= ew;
+                        if constexpr (DIAG) hit = hit && fabsf(vxc + vyc) <= ep && fabsf(vxc - vyc) <= em;
+                        hit = hit && (dcol[k] + d2) * minlen2 <= 4.002f;
                         // quadrant (k, r) of the bin -> tile (k>>1, r>>1), quadrant (k&1, r&1): bit tile*4 + quadrant (SUB == 2: of
                         // this thread's byte, which holds the tile row r>>1 = half)
                         if (hit) mask |= 1u << (((((SUB == 2 ? 0 : rr >> 1) * 2) + (k >> 1)) << 2) + ((rr & 1) * 2 + (k & 1)));
