@@ -543,6 +543,20 @@ struct gsr_ctx {
         float ms[2] = {0.0f, 0.0f};             // index with its bound, fill and walk of the last call (gsr_debug_knn_times)
     } knn;
 
+    // merging cells (gsr_merge.cpp): what gsr_cells / gsr_scene_merge_cells hold beside the neighbour scratch, the context's own; the
+    // first such call allocates it, it only grows, and the context's end frees it
+    struct Merge {
+        gsr::DevBuf<uint32_t> words;            // MG_INFO_WORDS of MgInfo
+        gsr::DevBuf<uint32_t> cand;             // `mask_words` words: the candidate mask
+        gsr::DevBuf<uint32_t> leader, count, rank;   // `rows` each
+        uint32_t rows = 0, mask_words = 0;
+        // the edit only
+        gsr::DevBuf<uint32_t> slice, member;    // `edit_rows` each
+        gsr::DevBuf<uint2> cells;               // edit_rows / 2 + 1
+        gsr::DevBuf<uint32_t> remove, merged, carried;   // `edit_words` words each: the compaction's predicate, the merged rows before and after it
+        uint32_t edit_rows = 0, edit_words = 0;
+    } mg;
+
     // frame delivery (gsr_delivery_open): a ring of pinned host blocks, each with its device staging and "copy done" event
     struct Delivery {
         struct Slot {
@@ -624,7 +638,10 @@ int sync_members(gsr_ctx* c);
 // gsr_scene_limit_box from need_rows on, for either predicate (gsr_scene_erase_selected is the other caller): the kept splats, in
 // order, become the scene; SH state, generation, bins and the members' frame state as the header says of limitBox; the selection is
 // empty afterwards.  `what` names the caller in a HIP error.
-int scene_compact(gsr_ctx* c, const ScenePred& p, const char* what, uint32_t* kept_out);
+// carry (null: none): one more set that keeps naming the same splats, as the hidden set does: out[new index of i] = in[i] for every
+// kept i, into `out`, nwords_out words zeroed by the caller (gsr_scene_merge_cells: the merged rows, its selection afterwards)
+struct SetCarry { const uint32_t* in; uint32_t nwords_in; uint32_t* out; uint32_t nwords_out; };
+int scene_compact(gsr_ctx* c, const ScenePred& p, const char* what, uint32_t* kept_out, const SetCarry* carry = nullptr);
 // the host upload path of gsr_set_scene / gsr_set_scene_arrays and gsr_scene_append_arrays: m host rows staged, repacked and checked
 // into rows [at, at + m) of `v` (rotations / scales null: a scene without them); *mismatch: positions differ from data words 0..2
 int upload_rows(gsr_ctx* c, const char* what, const SceneDev& v, uint32_t at, uint32_t m, const uint32_t* data, const float* positions,
@@ -669,6 +686,9 @@ struct NbCall {
 int nb_check(gsr_ctx* c, const char* who, double radius, uint32_t cap, uint32_t scope, uint64_t budget, uint32_t cap_min = 1u, const char* cap_name = "cap",
              uint32_t cap_max = GSR_NEIGHBOUR_MAX_CAP);
 int nb_index(gsr_ctx* c, const char* who, double radius, uint32_t cap, uint32_t scope, uint64_t budget, bool want_hist, NbCall* call, gsr_neighbour_info* info);
+// nb_index's first step, for a caller with cells of its own (gsr_merge.cpp): the context's scratch for the scene's n splats, *ix
+// over it with the given inv_h and r2, the words of NbInfo and cap + 1 histogram counters (*hist) and the table zeroed on the stream
+int nb_prepare(gsr_ctx* c, const char* who, uint32_t cap, double inv_h, double r2, NbIndex* ix, uint32_t** hist);
 // gsr_contrib.cpp: what the blocking calls that read per-splat state of a scene do first: waits for every member's stream, so
 // that nothing of any member (a contribution pass, an edit) is in flight afterwards
 int settle_members(gsr_ctx* c);

@@ -659,6 +659,45 @@ void launch_knn(const NbIndex& ix, uint32_t indexed, uint32_t n, uint32_t k, int
 // scratch <- the splats i < n in scope with lo <= values[i] && (values[i] < hi || open_hi): every word of it is stored
 void launch_knn_select(const double* values, const AttrScope& sc, uint32_t n, double lo, double hi, bool open_hi, uint32_t* scratch, uint32_t nwords, hipStream_t s);
 
+// Merging cells (k_merge.hip; DESIGN.md section 4, "Merging cells"): the candidates of every cell of a uniform grid -- the splats
+// in scope whose ten floats are finite -- found through the index above with inv_h = 1 / cell, and every cell of two or more merged
+// into one splat by moment matching, written at its leader's row (the smallest member index).
+constexpr uint32_t MG_NONE = 0xffffffffu;                   // GSR_CELL_NONE: a leader word of a splat that is no candidate
+constexpr uint32_t MG_INFO_WORDS = 8;
+// the device words of one call: zeroed by the host in front of the candidate mask
+struct MgInfo {
+    uint32_t in_scope;                     // splats in scope (k_mg_candidates)
+    uint32_t cells, merged_cells;          // cells with a member; with two or more: the cursor of `cells` below
+    uint32_t merged_members;               // members of those: the cursor of the member list
+    uint32_t largest, fault;               // the largest cell; non-zero when a slice or an index read back from the arrays lay outside them
+    unsigned long long pair_bound;         // the sum over the buckets of population^2: what the walk tests at most
+};
+struct MgArrays {
+    uint32_t* cand;                        // words: the candidate mask (the selection's layout)
+    uint32_t words;
+    uint32_t* leader;                      // n: the smallest member index of the splat's cell (MG_NONE: no candidate)
+    uint32_t* count;                       // n: the members of the splat's cell (0: no candidate)
+    uint32_t* rank;                        // n: the members of it with a smaller index
+    // the edit only (null in the report: the walk then hands out slices and stores none)
+    uint32_t* slice;                       // n: at a leader of a merged cell, the cell's first slot of the member list
+    uint32_t* member;                      // n: the merged cells' members, a slice per cell, ascending inside it
+    uint2* cells;                          // n / 2: (first slot, members) of every merged cell, in no particular order
+    uint32_t* remove;                      // words: member of a merged cell and not its leader
+    uint32_t* merged;                      // words: leader of a merged cell
+    MgInfo* info;
+};
+// a.cand <- the splats in `sc` with finite position, rotation and scale: every word of it is stored; info->in_scope.  n >= 1.
+void launch_mg_candidates(const SceneDev& scene, const AttrScope& sc, uint32_t n, const MgArrays& a, hipStream_t s);
+// info->pair_bound from the built index's populations
+void launch_mg_bound(const NbIndex& ix, const MgArrays& a, int cu_count, hipStream_t s);
+// leader, count and rank of every splat; hist (null: none; cap + 1 words zeroed by the caller) += the cells by min(members, cap);
+// info->cells, merged_cells, merged_members, largest; a.slice and a.cells for the merged cells.  indexed: info->indexed as the host read it.
+void launch_mg_walk(const NbIndex& ix, uint32_t indexed, uint32_t n, uint32_t cap, const MgArrays& a, uint32_t* hist, int cu_count, hipStream_t s);
+// a.member, a.remove and a.merged (every word stored) from leader, count, rank and slice
+void launch_mg_members(uint32_t n, uint32_t merged_members, const MgArrays& a, hipStream_t s);
+// every merged cell reduced and written at its leader's row of `scene`
+void launch_mg_reduce(const SceneDev& scene, uint32_t n, uint32_t merged_cells, uint32_t merged_members, const MgArrays& a, hipStream_t s);
+
 // Selection overlay (k_overlay.hip; DESIGN.md section 4, "Selection overlay"): the last frame's bin lists walked once more, the
 // weight w = T * B of every fragment of a SELECTED splat summed per pixel (cover) and, with the splat's colour, turned into the
 // frame with those splats tinted (overlay).  Reads the framebuffer, never writes it.

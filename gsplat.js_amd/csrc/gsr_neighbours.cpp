@@ -64,25 +64,35 @@ int nb_ensure(gsr_ctx* c, uint32_t n, uint64_t buckets)
 
 }  // namespace
 
-// Everything up to the count pass: the index, its bound against the budget, *info.  GSR_ERR_ARG (with *info filled) when the
+// nb_prepare: the scratch, the index's description and its zeroed words and table.  nb_index: on top of it,
+// everything up to the count pass: the index, its bound against the budget, *info.  GSR_ERR_ARG (with *info filled) when the
 // bound is above the budget: no count kernel has been launched.  n >= 1; the device is current and no member's stream holds work.
-int gsr::nb_index(gsr_ctx* c, const char* who, double radius, uint32_t cap, uint32_t scope, uint64_t budget, bool want_hist, NbCall* call, gsr_neighbour_info* info)
+int gsr::nb_prepare(gsr_ctx* c, const char* who, uint32_t cap, double inv_h, double r2, NbIndex* ix, uint32_t** hist)
 {
-    SharedScene& sc = *c->scene;
-    const uint32_t n = sc.n;
+    const uint32_t n = c->scene->n;
     if (n > NB_MAX_ROWS) return fail(c, GSR_ERR_ARG, "%s: the scene has %u splats; at most %u are indexed", who, n, NB_MAX_ROWS);
     uint64_t buckets = 256;   // a power of two, a multiple of k_nb_offsets' workgroup, at least twice the splats
     while (buckets < 2ull * n) buckets <<= 1;
     if (int r = nb_ensure(c, n, buckets)) return r;
     gsr_ctx::Neighbours& nb = c->nb;
-    NbCall k{};
-    k.sc = AttrScope{scope, sc.sel.mask, sc.sel.words, sc.hid.mask, sc.hid.words};
-    k.n = n;
-    k.hist = want_hist ? nb.words + NB_INFO_WORDS : nullptr;
-    const double h = radius * (1.0 + 1.0 / 1024.0);
-    k.ix = NbIndex{nb.table, (uint32_t)(buckets - 1u), nb.entry, nb.key, reinterpret_cast<NbInfo*>(nb.words.p), 1.0 / h, radius * radius};
+    *hist = nb.words + NB_INFO_WORDS;
+    *ix = NbIndex{nb.table, (uint32_t)(buckets - 1u), nb.entry, nb.key, reinterpret_cast<NbInfo*>(nb.words.p), inv_h, r2};
     HIP_TRY(c, hipMemsetAsync(nb.words, 0, (size_t)(NB_INFO_WORDS + cap + 1u) * 4, c->stream));
     HIP_TRY(c, hipMemsetAsync(nb.table, 0, (size_t)buckets * 8, c->stream));
+    return GSR_OK;
+}
+
+int gsr::nb_index(gsr_ctx* c, const char* who, double radius, uint32_t cap, uint32_t scope, uint64_t budget, bool want_hist, NbCall* call, gsr_neighbour_info* info)
+{
+    SharedScene& sc = *c->scene;
+    const uint32_t n = sc.n;
+    NbCall k{};
+    uint32_t* hist = nullptr;
+    if (int r = nb_prepare(c, who, cap, 1.0 / (radius * (1.0 + 1.0 / 1024.0)), radius * radius, &k.ix, &hist)) return r;
+    gsr_ctx::Neighbours& nb = c->nb;
+    k.sc = AttrScope{scope, sc.sel.mask, sc.sel.words, sc.hid.mask, sc.hid.words};
+    k.n = n;
+    k.hist = want_hist ? hist : nullptr;
     HIP_TRY(c, hipMemsetAsync(nb.counts, 0, (size_t)n * 4, c->stream));
     HIP_TRY(c, hipEventRecord(nb.ev[0], c->stream));
     launch_nb_build(k.ix, sc.arr.px, sc.arr.py, sc.arr.pz, k.sc, n, c->cu_count, k.hist, c->stream);

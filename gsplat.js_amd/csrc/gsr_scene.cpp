@@ -204,7 +204,7 @@ int upload_scene(gsr_ctx* c, const uint32_t* data, const float* positions, const
 }  // namespace
 
 // gsr_scene_limit_box and gsr_scene_erase_selected: the splats `p` keeps, in order, become the scene
-int gsr::scene_compact(gsr_ctx* c, const ScenePred& p, const char* what, uint32_t* kept_out)
+int gsr::scene_compact(gsr_ctx* c, const ScenePred& p, const char* what, uint32_t* kept_out, const SetCarry* also)
 {
     if (int r = need_rows(c)) return r;
     const uint32_t n = c->scene->n;
@@ -241,6 +241,8 @@ int gsr::scene_compact(gsr_ctx* c, const ScenePred& p, const char* what, uint32_
             e3 = hipMemsetAsync(hid.scratch, 0, (size_t)hid.words * 4, c->stream);
             launch_select_apply(SELOP_ADD, hid.spare, hid.scratch, n, hid.words, hid.counters + 2, hid.counters, c->stream);
         }
+        // (the caller's set goes the same way, into the caller's zeroed words)
+        if (also) launch_scene_compact_bits(n, sc.arr.view(), p, block_count, also->in, also->nwords_in, also->out, also->nwords_out, c->stream);
         hipError_t e1 = hipMemcpyAsync(counts, count, follow ? 16 : 4, hipMemcpyDeviceToHost, c->stream);
         if (carry) {   // (its count back: the call's one wait)
             if ((r = set_count(c, hid, what))) return r;

@@ -107,6 +107,10 @@ export type KnnStat = "kth" | "mean";
 export interface KnnOptions { k?: number; stat?: KnnStat; scope?: NeighbourScope | NeighbourScope[]; budget?: number }
 export interface SplatKnn { found: Uint32Array; values: Float64Array; hist: Uint32Array; idx?: Uint32Array; d2?: Float64Array; inScope: number; nonfinite: number;
     pairBound: number; complete: number; finiteValues: number; valueMin: number; valueMax: number }
+export interface CellOptions { scope?: NeighbourScope | NeighbourScope[]; budget?: number }
+export interface CellInfo { inScope: number; candidates: number; cells: number; mergedCells: number; mergedMembers: number; largest: number; rowsAfter: number;
+    pairBound: number }
+export interface SplatCells extends CellInfo { hist: Uint32Array; leader?: Uint32Array }
 export interface SplatHistogram { counts: Uint32Array; below: number; above: number; nan: number; edges: Float64Array }
 export interface Contribution { weight: BigUint64Array; peak: Float32Array; pixels: Uint32Array; frames: number }
 /** A screen region: the pixels [x0, x1) x [y0, y1), optionally one byte per pixel of the rectangle (non-zero = inside; rows
@@ -416,6 +420,16 @@ export class HIPRenderer {
     splatKnn(radius: number, options?: KnnOptions & { lists?: boolean }): SplatKnn;
     selectKnn(radius: number, options?: KnnOptions & { lo?: number; hi?: number; op?: SelectOp }): number;
     selectStatisticalOutliers(radius: number, options?: { k?: number; stdRatio?: number; scope?: NeighbourScope | NeighbourScope[]; budget?: number; op?: SelectOp }): { selected: number; threshold: number };
+    /** Merging cells: voxel simplification of this renderer's device copy.  The candidates -- the splats in scope with finite
+     *  position, rotation and scale -- fall into the cells of a grid of side `cell`.  splatCells is the report: hist[k] = the cells
+     *  with k members (hist[cap]: cap or more; cap 1 .. 4095, default 64), with leaders: true leader[i] = the smallest candidate
+     *  index of i's cell (0xffffffff: no candidate), rowsAfter = the rows mergeCells would leave.  mergeCells replaces every cell of
+     *  two or more by one splat -- the opacity x volume weighted mean, the covariance of the mixture, a rotation and scale from its
+     *  eigen-decomposition -- at the smallest member's row and removes the other members in order; count === rowsAfter of the
+     *  report, and the selection becomes exactly the merged rows.  Nothing to merge: nothing changes.  It acts on the device copy
+     *  like rotateSelection; a scene with SH rows is refused; budget as splatNeighbours. */
+    splatCells(cell: number, options?: CellOptions & { cap?: number; leaders?: boolean }): SplatCells;
+    mergeCells(cell: number, options?: CellOptions): CellInfo & { count: number };
     dispose(): void;
     /** RGBA8, row 0 = top, round(clamp(x,0,1)*255), premultiplied alpha */
     /** RGBA8, row 0 = top; pass an array of width*height*4 elements to have it filled and returned (no allocation per frame). */

@@ -1666,6 +1666,80 @@ napi_value SelectKnn(napi_env env, napi_callback_info info)
     return rc ? throw_gsr(env, c, rc, "gsr_select_knn") : count_value(env, count);
 }
 
+// ---- merging cells (gsr_cells / gsr_scene_merge_cells) ----
+// cell, scope and budget of the two calls below (the budget a number, 0: the library's default); false: an error is pending
+bool get_cell_args(napi_env env, napi_value cell_v, napi_value scope_v, napi_value budget_v, double* cell, uint32_t* scope, uint64_t* budget)
+{
+    double b;
+    if (!get_f64(env, cell_v, cell) || napi_get_value_uint32(env, scope_v, scope) != napi_ok || !get_f64(env, budget_v, &b)) {
+        napi_throw_type_error(env, nullptr, "cells: cell, scope and budget must be numbers");
+        return false;
+    }
+    if (!(b >= 0.0 && b <= 18446744073709549568.0)) { napi_throw_range_error(env, nullptr, "cells: budget must be a non-negative number"); return false; }
+    *budget = (uint64_t)b;
+    return true;
+}
+
+bool set_cell_info(napi_env env, napi_value out, const gsr_cell_info& ci)
+{
+    return set_u32(env, out, "inScope", ci.in_scope) && set_u32(env, out, "candidates", ci.candidates) && set_u32(env, out, "cells", ci.cells) &&
+           set_u32(env, out, "mergedCells", ci.merged_cells) && set_u32(env, out, "mergedMembers", ci.merged_members) && set_u32(env, out, "largest", ci.largest) &&
+           set_u32(env, out, "rowsAfter", ci.rows_after) && set_f64(env, out, "pairBound", (double)ci.pair_bound) && set_f64(env, out, "budget", (double)ci.budget);
+}
+
+// cells(handle, cell, cap, scope, budget, leaders) -> { hist: Uint32Array(cap + 1), and with leaders != 0 leader: Uint32Array(n); inScope,
+// candidates, cells, mergedCells, mergedMembers, largest, rowsAfter, pairBound, budget }
+napi_value Cells(napi_env env, napi_callback_info info)
+{
+    napi_value argv[6];
+    if (!get_args(env, info, 6, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    double cell;
+    uint32_t cap, scope, n = 0;
+    uint64_t budget;
+    int32_t leaders;
+    if (!c || !get_cell_args(env, argv[1], argv[3], argv[4], &cell, &scope, &budget)) return nullptr;
+    if (napi_get_value_uint32(env, argv[2], &cap) != napi_ok || !get_i32(env, argv[5], &leaders)) {
+        napi_throw_type_error(env, nullptr, "cells: cap and leaders must be numbers");
+        return nullptr;
+    }
+    if (cap < 1 || cap > GSR_NEIGHBOUR_MAX_CAP) { napi_throw_range_error(env, nullptr, "cells: cap must be in 1 .. 4095"); return nullptr; }
+    int rc = gsr_scene_count(c, &n);
+    if (rc) return throw_gsr(env, c, rc, "gsr_scene_count");
+    const size_t rows = leaders ? n : 0;
+    void *leader = nullptr, *hist = nullptr;
+    napi_value lb, larr, hb, harr, out;
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, rows * 4, &leader, &lb));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_uint32_array, rows, lb, 0, &larr));
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, ((size_t)cap + 1) * 4, &hist, &hb));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_uint32_array, (size_t)cap + 1, hb, 0, &harr));
+    gsr_cell_info ci{};
+    rc = gsr_cells(c, cell, cap, scope, budget, rows ? (uint32_t*)leader : nullptr, rows ? n : 0, (uint32_t*)hist, &ci);
+    if (rc) return throw_gsr(env, c, rc, "gsr_cells");
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "hist", harr));
+    if (leaders) NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "leader", larr));
+    return set_cell_info(env, out, ci) ? out : nullptr;
+}
+
+// mergeCells(handle, cell, scope, budget) -> { count, and gsr_cell_info's fields as cells() names them }
+napi_value MergeCells(napi_env env, napi_callback_info info)
+{
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    double cell;
+    uint32_t scope, count = 0;
+    uint64_t budget;
+    if (!c || !get_cell_args(env, argv[1], argv[2], argv[3], &cell, &scope, &budget)) return nullptr;
+    gsr_cell_info ci{};
+    const int rc = gsr_scene_merge_cells(c, cell, scope, budget, &count, &ci);
+    if (rc) return throw_gsr(env, c, rc, "gsr_scene_merge_cells");
+    napi_value out;
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    return set_u32(env, out, "count", count) && set_cell_info(env, out, ci) ? out : nullptr;
+}
+
 // ---- selection overlay (gsr_set_overlay / gsr_overlay_async / gsr_read_overlay* / gsr_delivery_set_overlay) ----
 // setOverlay(handle, on, r, g, b, mix): on = 0 switches the overlay off (the other arguments are not read)
 napi_value SetOverlay(napi_env env, napi_callback_info info)
@@ -1784,6 +1858,7 @@ napi_value Init(napi_env env, napi_value exports)
         {"neighbours", Neighbours}, {"selectNeighbours", SelectNeighbours},
         {"clusters", Clusters}, {"selectClusters", SelectClusters}, {"selectClusterAt", SelectClusterAt},
         {"knn", Knn}, {"selectKnn", SelectKnn},
+        {"cells", Cells}, {"mergeCells", MergeCells},
         {"setOverlay", SetOverlay}, {"readOverlay", ReadOverlay}, {"readOverlayPixels", ReadOverlayPixels},
         {"deliverySetOverlay", DeliverySetOverlay}, {"setOutline", SetOutline},
     };

@@ -649,6 +649,37 @@ class HIPRenderer {
             }
             return { selected: this.selectKnn(radius, { ...o3, lo: threshold, op: o2.op }), threshold };
         };
+        // ---- merging cells (gsr_cells / gsr_scene_merge_cells): voxel simplification of this renderer's copy ----
+        //   const { rowsAfter, hist } = renderer.splatCells(0.05); renderer.mergeCells(0.05);   // the report, then the edit it announced
+        // The candidates -- the splats in scope with finite position, rotation and scale -- fall into the cells of a grid of side
+        // `cell`.  splatCells reports them: hist[k] the cells with k members (hist[cap]: cap or more; cap 1 .. 4095, default 64),
+        // leader[i] (leaders: true) the smallest candidate index of i's cell, 0xffffffff for a splat that is no candidate, and
+        // rowsAfter, the rows mergeCells would leave.  mergeCells replaces every cell of two or more by one splat, by moment matching
+        // (opacity x volume weighted mean, the mixture's covariance, rotation and scale from its eigen-decomposition), at the smallest
+        // member's row, removes the other members as eraseSelection removes, and returns { count, ... }; afterwards the selection is
+        // exactly the merged rows.  Like rotateSelection it acts on the device copy: the Scene object's arrays are not changed.  scope
+        // and budget as splatNeighbours.  A scene with SH rows is refused.
+        const cellBudget = (o) => {
+            const budget = o.budget === undefined || o.budget === null ? 0 : Number(o.budget);
+            if (!(budget >= 0)) throw new Error("budget must be a non-negative number");
+            return budget;
+        };
+        const cellInfo = (r) => ({ inScope: r.inScope, candidates: r.candidates, cells: r.cells, mergedCells: r.mergedCells, mergedMembers: r.mergedMembers,
+                                   largest: r.largest, rowsAfter: r.rowsAfter, pairBound: r.pairBound });
+        this.splatCells = (cell, options) => {
+            const o2 = options || {}, cap = o2.cap === undefined ? 64 : o2.cap;
+            if (!Number.isInteger(cap) || cap < 1 || cap > 4095) throw new Error("cap must be an integer in 1 .. 4095");
+            const r = this._n.cells(this._h, Number(cell), cap, nbScope(o2), cellBudget(o2), o2.leaders ? 1 : 0);
+            const out = { hist: r.hist, ...cellInfo(r) };
+            if (o2.leaders) out.leader = r.leader;
+            return out;
+        };
+        this.mergeCells = (cell, options) => {
+            const o2 = options || {};
+            const r = this._n.mergeCells(this._h, Number(cell), nbScope(o2), cellBudget(o2));
+            vertexCount = r.count;   // (the device copy's: readSceneData and lastDepthIndex are sized by it)
+            return { count: r.count, ...cellInfo(r) };
+        };
         // ---- selection overlay (gsr_set_overlay / gsr_read_overlay*): the last frame with the selected splats tinted ----
         //   renderer.setSelectionOverlay({ tint: [1, 0.5, 0], mix: 0.5 }); renderer.render(scene, cam);
         //   const { rgba, cover } = renderer.readOverlay();   // or readPixels({ overlay: true }), or openDelivery(n, { overlay: true })

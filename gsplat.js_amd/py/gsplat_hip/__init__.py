@@ -103,6 +103,15 @@ class GsrKnnInfo(ctypes.Structure):
         return {k: (float if t is ctypes.c_double else int)(getattr(self, k)) for k, t in self._fields_}
 
 
+class GsrCellInfo(ctypes.Structure):
+    _fields_ = [("in_scope", ctypes.c_uint32), ("candidates", ctypes.c_uint32), ("cells", ctypes.c_uint32), ("merged_cells", ctypes.c_uint32),
+                ("merged_members", ctypes.c_uint32), ("largest", ctypes.c_uint32), ("rows_after", ctypes.c_uint32), ("pad", ctypes.c_uint32),
+                ("pair_bound", ctypes.c_uint64), ("budget", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
+
+
 class GsrDepthLayout(ctypes.Structure):
     _fields_ = [("format", ctypes.c_int32), ("step", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
                 ("stride", ctypes.c_int32), ("reserved", ctypes.c_int32), ("offset", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
@@ -125,6 +134,7 @@ NEIGHBOUR_MAX_CAP = 4095                                                   # GSR
 NEIGHBOUR_DEFAULT_BUDGET, NEIGHBOUR_MAX_BUDGET = 1 << 34, 1 << 38          # GSR_NEIGHBOUR_*_BUDGET
 KNN_MAX_K, KNN_NONE = 32, 0xffffffff                                       # GSR_KNN_MAX_K, GSR_KNN_NONE (an empty list slot)
 KNN_STATS = {"kth": 0, "mean": 1}                                          # GSR_KNN_*
+CELL_NONE = 0xffffffff                                                     # GSR_CELL_NONE (a leader: the splat is no candidate)
 CLUSTER_NONE = CLUSTER_LARGEST = 0xffffffff                                # GSR_CLUSTER_NONE (a label), GSR_CLUSTER_LARGEST (a seed)
 
 
@@ -190,6 +200,7 @@ EXPORTS = [
     "gsr_neighbours", "gsr_select_neighbours",
     "gsr_clusters", "gsr_select_clusters", "gsr_select_cluster_at",
     "gsr_knn", "gsr_select_knn",
+    "gsr_cells", "gsr_scene_merge_cells",
     "gsr_set_overlay", "gsr_overlay_async", "gsr_read_overlay", "gsr_read_overlay_rgba8", "gsr_overlay_device_ptr", "gsr_delivery_set_overlay",
     "gsr_set_overlay_outline",
 ]
@@ -364,6 +375,9 @@ def load_library(path=None):
     ki = ctypes.POINTER(GsrKnnInfo)
     L.gsr_knn.argtypes = [vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, ctypes.c_int32, vp, vp, vp, vp, ctypes.c_uint32, vp, ki]
     L.gsr_select_knn.argtypes = [vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32, u32p, ki]
+    gi = ctypes.POINTER(GsrCellInfo)
+    L.gsr_cells.argtypes = [vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, vp, ctypes.c_uint32, vp, gi]
+    L.gsr_scene_merge_cells.argtypes = [vp, ctypes.c_double, ctypes.c_uint32, u64, u32p, gi]
     L.gsr_set_overlay.argtypes = [vp, ctypes.POINTER(GsrOverlayOptions)]
     L.gsr_set_overlay_outline.argtypes = [vp, ctypes.POINTER(GsrOutlineOptions)]
     L.gsr_overlay_async.argtypes = [vp]
@@ -1368,6 +1382,44 @@ class HIPRenderer:
         threshold = knn_outlier_threshold(values, std_ratio)
         selected, info = self.select_knn(radius, k=k, stat="mean", lo=threshold, hi=None, scope=scope, op=op)
         return selected, threshold, info
+
+    # -- merging cells (gsr_cells / gsr_scene_merge_cells): voxel simplification of the scene --
+    @staticmethod
+    def _cell_args(cell, cap, budget):
+        cap = int(cap)
+        if not 1 <= cap <= NEIGHBOUR_MAX_CAP:
+            raise ValueError("cap must be in 1 .. %d" % NEIGHBOUR_MAX_CAP)
+        budget = 0 if budget is None else int(budget)
+        if budget < 0:
+            raise ValueError("budget must not be negative")
+        return float(cell), cap, budget
+
+    def cells(self, cell, cap=64, scope=(), leaders=False, budget=None):
+        """(leader uint32[n] or None, hist uint32[cap + 1], info): the report of scene_merge_cells(cell, scope).  The candidates
+        -- the splats in scope (any of "selected", "visible"; () is every splat) whose position, rotation and scale are finite --
+        fall into the cells of a grid of side `cell`; leader[i] (leaders=True) is the smallest candidate index of i's cell,
+        CELL_NONE for a splat that is no candidate; hist[k] the cells with k members, hist[cap] "cap or more".  info: in_scope,
+        candidates, cells, merged_cells, merged_members, largest, rows_after, pair_bound, budget.  budget as neighbours() takes it."""
+        cell, cap, budget = self._cell_args(cell, cap, budget)
+        n = self._count()
+        lead = np.full(n, CELL_NONE, np.uint32) if leaders else None
+        h = np.zeros(cap + 1, np.uint32)
+        info = GsrCellInfo()
+        self._check_neighbours(self._L.gsr_cells(self._ctx, cell, cap, self._scope_flags(scope), budget, lead.ctypes.data if leaders and n else None,
+                                                 n if leaders else 0, h.ctypes.data, ctypes.byref(info)), info)
+        return lead, h, info.as_dict()
+
+    def scene_merge_cells(self, cell, scope=(), budget=None):
+        """(new_count, info): every grid cell of side `cell` that holds two or more candidates becomes one splat, by moment matching
+        -- the opacity x volume weighted mean, the covariance of the mixture, a rotation and scale from its eigen-decomposition --
+        written at the smallest member's row; the other members are removed as scene_erase_selected() removes.  new_count equals
+        cells(cell, scope=scope)[2]["rows_after"]; afterwards the selection is exactly the merged rows.  Nothing to merge: nothing
+        changes.  A scene with SH rows is refused."""
+        cell, _, budget = self._cell_args(cell, 1, budget)
+        count, info = ctypes.c_uint32(0), GsrCellInfo()
+        self._check_neighbours(self._L.gsr_scene_merge_cells(self._ctx, cell, self._scope_flags(scope), budget, ctypes.byref(count), ctypes.byref(info)), info)
+        self._n = count.value
+        return count.value, info.as_dict()
 
     # -- selection overlay (gsr_set_overlay / gsr_overlay_async / gsr_read_overlay*): the selected splats tinted --
     def set_overlay(self, tint=(1.0, 0.5, 0.0), mix=0.5):

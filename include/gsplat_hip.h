@@ -1020,6 +1020,88 @@ int gsr_knn(gsr_ctx *ctx, double radius, uint32_t k, uint32_t scope, uint64_t bu
 int gsr_select_knn(gsr_ctx *ctx, double radius, uint32_t k, uint32_t scope, uint64_t budget, int32_t stat,
                    double lo, double hi, int32_t op, uint32_t *selected, gsr_knn_info *info);
 
+/* ---- merging cells ---- voxel simplification: the splats of every grid cell merged into one by moment matching
+ * No interface of the reference stands behind this section either.  The calls above prune a scene -- by contribution, outliers or
+ * islands -- and none of them makes it coarser.  Point-cloud tools call the operation voxel down-sampling; for Gaussians it is not
+ * "keep one point per cell": the splats of a cell are merged into one whose mass, mean and covariance are those of the mixture.
+ * gsr_cells is the read-only report, gsr_scene_merge_cells the edit that does exactly what the report announced, on the device,
+ * over the index of "neighbours", with no gsr_read_scene.
+ * Definition ("Merging cells").  Scope S is the GSR_SCOPE_SELECTED | GSR_SCOPE_VISIBLE flags of "splat data",
+ *   with the same meaning; 0 is every splat.
+ *   Candidate: splat i is a candidate iff it is in S and all ten floats (position, rotation, scale) are finite.
+ *   Cell: inv = 1.0 / cell, computed once on the host; per axis the coordinate is floor((double)x * inv) clamped to [-2^20, 2^20),
+ *     the cell coordinate of "neighbours" with no slack, because no radius is involved.  Everything at or beyond the clamp shares
+ *     the boundary cell.
+ *   Members: the members of a cell are its candidates; m is their number; the leader is the smallest member index.
+ * gsr_cells: leader is n words or NULL (a non-NULL leader with n not equal to the scene's count is refused): leader[i] is the leader
+ *   of i's cell for a candidate and GSR_CELL_NONE otherwise.  hist is cap + 1 words or NULL, cap in 1 .. 4095: hist[k], for
+ *   1 <= k <= cap, is the number of cells with k members, hist[cap] means "cap or more", hist[0] is 0.  info may be NULL.  An
+ *   empty scene, or an empty scope, returns zeros (rows_after = the scene's count).
+ * info: in_scope = the splats in S; candidates = those of them that are candidates; cells = the occupied cells; merged_cells =
+ *   the cells with m >= 2; merged_members = the sum of m over those; largest = the largest m; rows_after = n - merged_members +
+ *   merged_cells; pair_bound and budget as below.  Every field is an integer, so every field is exact.
+ * gsr_scene_merge_cells: a cell with m == 1, and every non-candidate, is left bit for bit.  A cell with m >= 2 is replaced by one
+ *   row, written at its leader's index; its other members are removed by the order-preserving compaction gsr_scene_erase_selected
+ *   uses.  The consistency guarantee: *new_count == info->rows_after of a gsr_cells call with the same cell, scope and budget.
+ * The merged row.  All arithmetic is f64, uncontracted; every sum runs over the members in ascending index order; division and
+ *   square root are correctly rounded.
+ *    1. a_i = the opacity byte;  v_i = (fabs(sx) * fabs(sy)) * fabs(sz);  m_i = a_i * v_i;  M = sum m_i.
+ *    2. If M > 0: w_i = m_i, W = M.  Otherwise w_i = 1, W = (double)m.
+ *    3. mu_k = (sum w_i * p_ik) / W; the stored position is (float)mu_k.
+ *    4. S_i = the six sums of the covariance R^T diag(s^2) R of member i, from its stored rotation and scale exactly as the packed
+ *       covariance words are computed from them, before the factor 4 and the halves.
+ *    5. d_i = p_i - mu, mu unrounded;  C_ab = (sum w_i * (S_i,ab + d_ia * d_ib)) / W  for ab = 00, 01, 02, 11, 12, 22.
+ *    6. Cyclic Jacobi, exactly 6 sweeps over the pairs (p, q) = (0,1), (0,2), (1,2) on A = C, V = I, r = 3 - p - q.  A pair with
+ *       A_pq == 0 is skipped.  th = (A_qq - A_pp) / (2.0 * A_pq);  t = 1.0 / (fabs(th) + sqrt(th * th + 1.0)), negated if th < 0;
+ *       cs = 1.0 / sqrt(t * t + 1.0);  sn = t * cs.  From the old values: A_pp = app - t * apq;  A_qq = aqq + t * apq;
+ *       A_pq = 0;  A_rp = cs * arp - sn * arq;  A_rq = sn * arp + cs * arq;  for k = 0..2: V_kp = cs * vkp - sn * vkq,
+ *       V_kq = sn * vkp + cs * vkq.  lam_k = A_kk, not sorted.
+ *    7. The stored scale is (float)sqrt(lam_k > 0 ? lam_k : 0.0).
+ *    8. The renderer's covariance is R^T diag(s^2) R with R built from (x, y, z, w) = (r1, r2, r3, -r0), so R = V^T: row k is
+ *       eigenvector k.
+ *    9. (x, y, z, w) from R by Shepperd's four branches, in this order: tr = (R00 + R11) + R22 > 0: s = sqrt(tr + 1.0) * 2.0,
+ *       w = 0.25 * s, x = (R21 - R12) / s, y = (R02 - R20) / s, z = (R10 - R01) / s;  else R00 > R11 && R00 > R22:
+ *       s = sqrt(((1.0 + R00) - R11) - R22) * 2.0, w = (R21 - R12) / s, x = 0.25 * s, y = (R01 + R10) / s, z = (R02 + R20) / s;
+ *       else R11 > R22: s = sqrt(((1.0 + R11) - R00) - R22) * 2.0, w = (R02 - R20) / s, x = (R01 + R10) / s, y = 0.25 * s,
+ *       z = (R12 + R21) / s;  else: s = sqrt(((1.0 + R22) - R00) - R11) * 2.0, w = (R10 - R01) / s, x = (R02 + R20) / s,
+ *       y = (R12 + R21) / s, z = 0.25 * s.  The stored rotation is (r0, r1, r2, r3) = ((float)(-w), (float)x, (float)y, (float)z).
+ *   10. The covariance words are those of the stored f32 rotation and scale.
+ *   11. Each colour byte is floor((sum w_i * c_i) / W + 0.5).
+ *   12. Opacity conserves opacity x volume: v' = (s'x * s'y) * s'z from the stored f32 scales as doubles; if v' > 0: o = M / v',
+ *       the byte is 255 if o >= 255, else floor(o + 0.5); otherwise the byte is the largest a_i.
+ *   13. Data word 3 stays the leader's.
+ *   Every value is a sequence of correctly rounded f64 operations in a stated order: the same scene, cell and scope give the same
+ *   bits on every run, in every context form and through every member of a shared scene.
+ * State.  The edit is a blocking scene replacement, like a removing gsr_scene_erase_selected: it waits for every member of a
+ *   shared scene, invalidates the members' frame state, moves the generation and re-plans the bins; the capacity is kept.  The
+ *   hidden set is carried through the compaction, a merged row has its leader's bit; the contribution accumulators are treated
+ *   exactly as a removing erase treats them; the selection becomes exactly the merged rows, so the overlay shows what was merged.
+ *   Nothing to merge: if no cell has two members the call returns GSR_OK with new_count = n and changes nothing; the last frame
+ *   stays valid, and so does the selection.  gsr_cells reads the scene and writes none of it; it is ordered like gsr_neighbours.
+ * The work budget is the neighbour budget, with the same constants: pair_bound is the sum, over the indexed candidates, of the
+ *   population of the candidate's own hash bucket, i.e. the key tests the walk makes.  budget == 0 means
+ *   GSR_NEIGHBOUR_DEFAULT_BUDGET; a budget above GSR_NEIGHBOUR_MAX_BUDGET is refused; if pair_bound > budget the call returns
+ *   GSR_ERR_ARG with a message naming both numbers, fills info (in_scope, candidates, pair_bound, budget) and launches no walk.
+ * Refusals (GSR_ERR_ARG with a message, nothing touched): a NULL ctx; a cell that is not finite, not > 0, or with 1 / cell not
+ *   finite and normal; cap outside 1 .. 4095; unknown scope flags; a budget above the maximum; a non-NULL leader with the wrong n;
+ *   a scene without rotations / scales; for the edit, a scene with SH rows (sh_count != 0): a mixture's SH colour is not defined
+ *   here, while gsr_cells answers for such a scene; a bound above the budget.
+ * The device scratch belongs to the context: the scratch of "neighbours", a mask and 12 bytes per splat for the report, 12 more
+ *   bytes per splat and three masks for the edit.  The first call allocates it, it only grows, and gsr_destroy frees it; a context
+ *   that never calls any of this allocates nothing and launches nothing. */
+#define GSR_CELL_NONE 0xffffffffu   /* a leader: the splat is no candidate */
+typedef struct gsr_cell_info {
+    uint32_t in_scope, candidates;       /* splats in S; of those, mergeable */
+    uint32_t cells, merged_cells;        /* occupied cells; cells with >= 2 members */
+    uint32_t merged_members, largest;    /* sum of m over merged cells; the largest m */
+    uint32_t rows_after, pad;            /* n - merged_members + merged_cells */
+    uint64_t pair_bound, budget;
+} gsr_cell_info;
+int gsr_cells(gsr_ctx *ctx, double cell, uint32_t cap, uint32_t scope, uint64_t budget,
+              uint32_t *leader /* n or NULL */, uint32_t n, uint32_t *hist /* cap + 1 or NULL */, gsr_cell_info *info);
+int gsr_scene_merge_cells(gsr_ctx *ctx, double cell, uint32_t scope, uint64_t budget,
+                          uint32_t *new_count, gsr_cell_info *info);
+
 /* ---- selection overlay ---- the selected splats tinted, in read-backs and in delivered frames
  * No interface of the reference stands behind this section either.  gsr_read_selection returns bits; this shows them: a second
  * image beside the frame in which the selected splats carry a tint, and per pixel how much of it they are.

@@ -3,7 +3,7 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--share-scene]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--merge CELL] [--share-scene]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
@@ -53,6 +53,9 @@
 // bound) and the walk (with its fill) apart; pair_bound and the pair tests per second it means for the walk, complete,
 // finite_values, the value range, and the check that gsr_select_knn(lo = the mean of the finite values, hi = +inf) selects exactly
 // the splats whose values[i] is at or above it (`values_equal_selection`).
+// --merge CELL (behind everything else: it replaces the scene) merges the cells of a grid of side CELL: three gsr_cells calls, the
+// best wall time of the report, then the one gsr_scene_merge_cells call it announced: the blocking time, the rows before and after,
+// the members per cell, and the check that the edit left the announced rows with exactly the merged rows selected (`report_equals_edit`).
 // --duplicate FRACTION (last of all: it grows the scene) selects that fraction of the splats through gsr_selection_set and calls
 // gsr_scene_duplicate_selected twice -- the second call copies the first one's copies, the same count -- and reports the wall time
 // of either (`duplicate_ms`, `duplicate_again_ms`), the count and the capacity.  With --reserve, gsr_scene_reserve makes room for
@@ -200,6 +203,7 @@ int main(int argc, char** argv)
     double cl_radius = 0.0;             // 0: off
     uint32_t cl_min_pts = 0;
     double knn_radius = 0.0;            // 0: off
+    double merge_cell = 0.0;            // 0: off
     uint32_t knn_k = 8;
     int32_t knn_stat = GSR_KNN_MEAN;
     int32_t pick_xy[2] = {0, 0};
@@ -254,13 +258,14 @@ int main(int argc, char** argv)
             if (!(knn_radius > 0.0) || k < 1 || k > (int)GSR_KNN_MAX_K || (stat != "kth" && stat != "mean")) { std::fprintf(stderr, "--knn RADIUS:K[:kth|mean]: RADIUS > 0, K in 1 .. 32\n"); return 2; }
             knn_k = (uint32_t)k; knn_stat = stat == "kth" ? GSR_KNN_KTH : GSR_KNN_MEAN;
         }
+        else if (a == "--merge" && i + 1 < argc) { merge_cell = std::atof(argv[++i]); if (!(merge_cell > 0.0)) { std::fprintf(stderr, "--merge CELL: CELL > 0\n"); return 2; } }
         else if (a == "--duplicate" && i + 1 < argc) { duplicate_fraction = std::atof(argv[++i]); if (!(duplicate_fraction >= 0.0 && duplicate_fraction <= 1.0)) { std::fprintf(stderr, "--duplicate FRACTION must be in [0, 1]\n"); return 2; } }
         else if (a == "--reserve") reserve = true;
         else if (a == "--scene-arrays") scene_arrays = true;
         else if (a == "--scene-edit") scene_edit = next();
         else if (a == "--share-scene") share_scene = true;
         else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--share-scene]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--merge CELL] [--share-scene]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
@@ -748,6 +753,23 @@ int main(int argc, char** argv)
         CHECK(gsr_scene_capacity(ctx[0], &dup_capacity));
         CHECK(gsr_scene_count(ctx[0], &dup_n));
     }
+    // --merge (after everything else: it replaces the scene): the report three times, then the one blocking edit it announced
+    gsr_cell_info mg_report{}, mg_info{};
+    double mg_cells_ms = 1e30, mg_merge_ms = 0;
+    uint32_t mg_before = 0, mg_after = 0, mg_selected = 0;
+    if (merge_cell > 0.0) {
+        ctx0 = ctx[0];
+        CHECK(gsr_scene_count(ctx[0], &mg_before));
+        for (int t = 0; t < 3; t++) {
+            const auto t0 = std::chrono::steady_clock::now();
+            CHECK(gsr_cells(ctx[0], merge_cell, 64, 0, 0, nullptr, 0, nullptr, &mg_report));
+            mg_cells_ms = std::min(mg_cells_ms, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3);
+        }
+        const auto t0 = std::chrono::steady_clock::now();
+        CHECK(gsr_scene_merge_cells(ctx[0], merge_cell, 0, 0, &mg_after, &mg_info));
+        mg_merge_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3;
+        CHECK(gsr_read_selection(ctx[0], nullptr, 0, &mg_selected));
+    }
     char name[128] = "";
     int32_t cus = 0, khz = 0;
     (void)gsr_device_info(ctx[0], name, (int32_t)sizeof name, &cus, &khz);
@@ -835,6 +857,14 @@ int main(int argc, char** argv)
         std::printf(", \"duplicate_fraction\": %g, \"duplicate_first\": %u, \"duplicate_count\": %u, \"duplicate_reserved\": %s, \"reserve_ms\": %.4f, "
                     "\"duplicate_ms\": %.4f, \"duplicate_again_ms\": %.4f, \"count_after\": %u, \"capacity_after\": %u",
                     duplicate_fraction, dup_first, dup_count, reserve ? "true" : "false", reserve_ms, duplicate_ms, duplicate_again_ms, dup_n, dup_capacity);
+    if (merge_cell > 0.0)
+        std::printf(", \"merge\": {\"cell\": %.17g, \"rows_before\": %u, \"rows_after\": %u, \"rows_announced\": %u, \"in_scope\": %u, \"candidates\": %u, "
+                    "\"cells\": %u, \"merged_cells\": %u, \"merged_members\": %u, \"largest\": %u, \"members_per_cell\": %.3f, \"pair_bound\": %llu, \"budget\": %llu, "
+                    "\"cells_ms\": %.4f, \"merge_blocking_ms\": %.4f, \"selected_after\": %u, \"report_equals_edit\": %s}",
+                    merge_cell, mg_before, mg_after, mg_report.rows_after, mg_info.in_scope, mg_info.candidates, mg_info.cells, mg_info.merged_cells, mg_info.merged_members,
+                    mg_info.largest, mg_info.cells ? (double)mg_info.candidates / mg_info.cells : 0.0, (unsigned long long)mg_info.pair_bound,
+                    (unsigned long long)mg_info.budget, mg_cells_ms, mg_merge_ms, mg_selected,
+                    mg_after == mg_report.rows_after && mg_selected == mg_info.merged_cells ? "true" : "false");
     if (pick)
         std::printf(", \"pick\": {\"x\": %d, \"y\": %d, \"index\": %u, \"depth\": %s, \"mean\": %.9g, \"alpha\": %.9g}",
                     pick_xy[0], pick_xy[1], picked.index, picked.index == 0xffffffffu ? "null" : std::to_string(picked.depth).c_str(), (double)picked.mean, (double)picked.alpha);
