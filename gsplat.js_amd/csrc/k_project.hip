@@ -129,6 +129,32 @@ __device__ __forceinline__ float eval_sh_texture(const uint32_t* __restrict__ te
 }
 
 // ---------------------------------------------------------------------------
+// A wave's total of a per-lane 32-bit value (min, max or sum), returned wave-uniform, with DPP row operations instead of six
+// ds_bpermute_b32 steps (each of which also cost a lane xor, a compare, a select and a shift for the permute address): two quad
+// permutes and the two row mirrors leave a row's total in each of its 16 lanes, row broadcasts 15 and 31 carry it into the rows
+// behind, lane 63 then holds the wave's and one v_readlane fetches it.  A lane that a step does not write (row_mask) takes the
+// operation's identity, and the compiler folds the DPP move into the operation.  Integer min, max and add are associative and
+// commutative (the sums wrap modulo 2^32): the same number in whatever order.  Every lane of the wave must be active.
+enum class Fold { Min, Max, Add };
+template <Fold F> __device__ __forceinline__ int32_t fold_two(int32_t a, int32_t b)
+{
+    return F == Fold::Min ? min(a, b) : F == Fold::Max ? max(a, b) : (int32_t)((uint32_t)a + (uint32_t)b);
+}
+template <Fold F> __device__ __forceinline__ int32_t wave_total(int32_t v)
+{
+    constexpr int32_t ID = F == Fold::Min ? 0x7fffffff : F == Fold::Max ? (int32_t)0x80000000 : 0;
+    constexpr int QUAD_1032 = 0xB1, QUAD_2301 = 0x4E, ROW_HALF_MIRROR = 0x141, ROW_MIRROR = 0x140, ROW_BCAST15 = 0x142, ROW_BCAST31 = 0x143;
+    v = fold_two<F>(v, __builtin_amdgcn_update_dpp(ID, v, QUAD_1032, 0xf, 0xf, false));
+    v = fold_two<F>(v, __builtin_amdgcn_update_dpp(ID, v, QUAD_2301, 0xf, 0xf, false));
+    v = fold_two<F>(v, __builtin_amdgcn_update_dpp(ID, v, ROW_HALF_MIRROR, 0xf, 0xf, false));
+    v = fold_two<F>(v, __builtin_amdgcn_update_dpp(ID, v, ROW_MIRROR, 0xf, 0xf, false));
+    v = fold_two<F>(v, __builtin_amdgcn_update_dpp(ID, v, ROW_BCAST15, 0xa, 0xf, false));   // rows 1 and 3 += rows 0 and 2
+    v = fold_two<F>(v, __builtin_amdgcn_update_dpp(ID, v, ROW_BCAST31, 0xc, 0xf, false));   // rows 2 and 3 += rows 0 + 1
+    return __builtin_amdgcn_readlane(v, 63);
+}
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return (uint32_t)wave_total<Fold::Add>((int32_t)v); }
+
+// ---------------------------------------------------------------------------
 // One thread per splat, original order (fully coalesced SoA reads).
 //   A1  depth key + min/max        wasm/wasm.cpp:14-31
 //   B1-B6 projection               vertex.glsl.ts:130-231 (non-SH colour branch, scalingFactor 1)
@@ -164,7 +190,8 @@ __global__ __launch_bounds__(PROJ_THREADS) void k_project_key(SceneSoA sc, uint3
     int32_t mydepth = 0;
     bool keep = false;
     int32_t dmin = 0x7fffffff, dmax = (int32_t)0x80000000;
-    uint32_t vis = 0, tiles = 0;   // this thread's visible splats and the 16x16 tiles their boxes overlap (V and D of the byte model)
+    bool visible = false;          // this thread's splat has a pixel box: counted per wave below (V of the byte model)
+    uint32_t tiles = 0;            // the 16x16 tiles its box overlaps (D of the byte model)
     uint32_t otiles = 0;           // sum of opacity byte x tiles / 16 over them
     uint32_t omass = 0;            // sum of opacity byte x footprint in pixels / 256 over them (below)
     const int bx_lo = cam.band_px0 / BIN_PX, bx_hi = (cam.band_px1 + BIN_PX - 1) / BIN_PX;   // this context's band of bin columns
@@ -339,7 +366,7 @@ __global__ __launch_bounds__(PROJ_THREADS) void k_project_key(SceneSoA sc, uint3
                 if (!pack || keep) rect[i] = rv;
             }
             if ((bb.x & 0xffffu) <= (bb.x >> 16)) {
-                vis++;
+                visible = true;
                 const int tx0 = max((int)(bb.x & 0xffffu) / TILE, bx_lo * BIN_TILES), tx1 = min((int)(bb.x >> 16) / TILE, bx_hi * BIN_TILES - 1);
                 const uint32_t nt = (uint32_t)((tx1 - tx0 + 1) * ((int)(bb.y >> 16) / TILE - (int)(bb.y & 0xffffu) / TILE + 1));
                 tiles += nt;
@@ -354,15 +381,13 @@ __global__ __launch_bounds__(PROJ_THREADS) void k_project_key(SceneSoA sc, uint3
     }
 
     // ---- workgroup totals, folded into this workgroup's frame slot (see FRAME_SLOTS in gsr_internal.h) ----
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        dmin = min(dmin, __shfl_xor(dmin, off));
-        dmax = max(dmax, __shfl_xor(dmax, off));
-        vis += __shfl_xor(vis, off);
-        tiles += __shfl_xor(tiles, off);
-        otiles += __shfl_xor(otiles, off);
-        omass += __shfl_xor(omass, off);
-    }
+    // (the wave's totals, uniform: the visible count is a population count of a predicate, the rest wave_total above)
+    const uint32_t vis = (uint32_t)__popcll(__ballot(visible));
+    dmin = wave_total<Fold::Min>(dmin);
+    dmax = wave_total<Fold::Max>(dmax);
+    tiles = wave_sum(tiles);
+    otiles = wave_sum(otiles);
+    omass = wave_sum(omass);
     const int wave = threadIdx.x >> 6;
     uint32_t keep_rank = 0;
     if (pack) {
@@ -433,11 +458,8 @@ __global__ __launch_bounds__(PROJ_THREADS) void k_depth_key(SceneSoA sc, uint32_
             dmin = min(dmin, d); dmax = max(dmax, d);
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        dmin = min(dmin, __shfl_xor(dmin, off));
-        dmax = max(dmax, __shfl_xor(dmax, off));
-    }
+    dmin = wave_total<Fold::Min>(dmin);
+    dmax = wave_total<Fold::Max>(dmax);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) { s_min[wave] = dmin; s_max[wave] = dmax; }
     __syncthreads();
