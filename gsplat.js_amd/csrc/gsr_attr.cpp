@@ -51,14 +51,6 @@ int attr_enter(gsr_ctx* c, const char* who, int32_t attr, const double* origin, 
     return GSR_OK;
 }
 
-int scope_of(gsr_ctx* c, const char* who, uint32_t scope, AttrScope* out)
-{
-    if (scope & ~(ATTR_SCOPE_SELECTED | ATTR_SCOPE_VISIBLE)) return fail(c, GSR_ERR_ARG, "%s: unknown scope flags 0x%x", who, scope);
-    const SharedScene& sc = *c->scene;
-    *out = AttrScope{scope, sc.sel.mask, sc.sel.words, sc.hid.mask, sc.hid.words};
-    return GSR_OK;
-}
-
 // the context's device words, allocated by the first call that needs them
 int attr_ensure(gsr_ctx* c)
 {
@@ -68,14 +60,23 @@ int attr_ensure(gsr_ctx* c)
 
 }  // namespace
 
+int gsr::scope_check(gsr_ctx* c, const char* who, uint32_t scope, uint64_t budget)
+{
+    if (scope & ~(ATTR_SCOPE_SELECTED | ATTR_SCOPE_VISIBLE)) return fail(c, GSR_ERR_ARG, "%s: unknown scope flags 0x%x", who, scope);
+    if (budget > GSR_NEIGHBOUR_MAX_BUDGET)
+        return fail(c, GSR_ERR_ARG, "%s: budget (%llu) is above GSR_NEIGHBOUR_MAX_BUDGET (%llu)", who, (unsigned long long)budget,
+                    (unsigned long long)GSR_NEIGHBOUR_MAX_BUDGET);
+    return GSR_OK;
+}
+
 extern "C" {
 
 int gsr_attr_stats(gsr_ctx* c, int32_t attr, const double* origin, uint32_t scope, uint32_t* count, uint32_t* nan, double* min, double* max)
 {
     if (!c) return GSR_ERR_ARG;
     AttrSource src;
-    AttrScope sc;
-    if (int r = scope_of(c, "gsr_attr_stats", scope, &sc)) return r;
+    if (int r = scope_check(c, "gsr_attr_stats", scope)) return r;
+    const AttrScope sc = scene_scope(*c->scene, scope);
     if (int r = attr_enter(c, "gsr_attr_stats", attr, origin, &src)) return r;
     AttrStats got{0u, 0u, std::numeric_limits<double>::infinity(), -std::numeric_limits<double>::infinity()};
     if (const uint32_t n = c->scene->n) {
@@ -104,8 +105,8 @@ int gsr_attr_histogram(gsr_ctx* c, int32_t attr, const double* origin, uint32_t 
     if (!(std::isfinite(lo) && std::isfinite(hi) && lo < hi && std::isfinite(hi - lo)))
         return fail(c, GSR_ERR_ARG, "gsr_attr_histogram: [%g, %g) must be finite, of finite width, with lo < hi", lo, hi);
     AttrSource src;
-    AttrScope sc;
-    if (int r = scope_of(c, "gsr_attr_histogram", scope, &sc)) return r;
+    if (int r = scope_check(c, "gsr_attr_histogram", scope)) return r;
+    const AttrScope sc = scene_scope(*c->scene, scope);
     if (int r = attr_enter(c, "gsr_attr_histogram", attr, origin, &src)) return r;
     const uint32_t ncounters = bins + 3u;
     uint32_t got[ATTR_MAX_BINS + 3u];

@@ -672,6 +672,11 @@ int set_read(gsr_ctx* c, const SplatSet& s, const char* who, uint32_t* words, ui
 int hidden_ensure(gsr_ctx* c);
 int select_ensure(gsr_ctx* c);
 int select_fold_and_count(gsr_ctx* c, int op, uint32_t* selected);
+// The scope of an analysis call (splat data, neighbours, clusters, k nearest neighbours, merging cells).  scope_check (gsr_attr.cpp):
+// the two refusals those calls share, in the header's order -- flags outside GSR_SCOPE_*, a budget above GSR_NEIGHBOUR_MAX_BUDGET (a
+// call without a budget passes 0); nothing is touched.  scene_scope: the scope as the kernels take it, over the scene's sets as they are.
+int scope_check(gsr_ctx* c, const char* who, uint32_t scope, uint64_t budget = 0);
+inline AttrScope scene_scope(const SharedScene& sc, uint32_t flags) { return AttrScope{flags, sc.sel.mask, sc.sel.words, sc.hid.mask, sc.hid.words}; }
 // gsr_neighbours.cpp, for the calls that walk the spatial index (neighbours, clusters, k nearest neighbours).  NbCall: one call's scope and index.
 // nb_check: the refusals they share, in the header's order, with `cap` in cap_min .. cap_max under the name cap_name; nothing is
 // touched.  nb_index: everything up to the first walk -- the context's scratch (allocated by the first call,

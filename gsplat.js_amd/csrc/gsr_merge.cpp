@@ -30,11 +30,7 @@ int mg_check(gsr_ctx* c, const char* who, double cell, uint32_t cap, uint32_t sc
     if (!(std::isfinite(cell) && cell > 0.0)) return fail(c, GSR_ERR_ARG, "%s: cell (%g) must be finite and > 0", who, cell);
     if (!std::isnormal(1.0 / cell)) return fail(c, GSR_ERR_ARG, "%s: cell (%g): 1 / cell must be finite and normal", who, cell);
     if (cap < 1u || cap > GSR_NEIGHBOUR_MAX_CAP) return fail(c, GSR_ERR_ARG, "%s: cap (%u) must be in 1 .. %u", who, cap, GSR_NEIGHBOUR_MAX_CAP);
-    if (scope & ~(ATTR_SCOPE_SELECTED | ATTR_SCOPE_VISIBLE)) return fail(c, GSR_ERR_ARG, "%s: unknown scope flags 0x%x", who, scope);
-    if (budget > GSR_NEIGHBOUR_MAX_BUDGET)
-        return fail(c, GSR_ERR_ARG, "%s: budget (%llu) is above GSR_NEIGHBOUR_MAX_BUDGET (%llu)", who, (unsigned long long)budget,
-                    (unsigned long long)GSR_NEIGHBOUR_MAX_BUDGET);
-    return GSR_OK;
+    return scope_check(c, who, scope, budget);
 }
 
 // the context's scratch for n splats, with the edit's share when `edit`: allocated by the first call, only ever grown
@@ -93,7 +89,7 @@ int mg_run(gsr_ctx* c, const char* who, double cell, uint32_t cap, uint32_t scop
     HIP_TRY(c, hipMemsetAsync(mg.words, 0, MG_INFO_WORDS * 4, c->stream));
     HIP_TRY(c, hipMemsetAsync(mg.leader, 0xff, (size_t)n * 4, c->stream));   // MG_NONE and 0 for every splat the walk does not reach
     HIP_TRY(c, hipMemsetAsync(mg.count, 0, (size_t)n * 4, c->stream));
-    launch_mg_candidates(scene, AttrScope{scope, sc.sel.mask, sc.sel.words, sc.hid.mask, sc.hid.words}, n, a, c->stream);
+    launch_mg_candidates(scene, scene_scope(sc, scope), n, a, c->stream);
     // the index of the candidates: the mask is the scope, a grid cell is an index cell
     launch_nb_build(ix, scene.px, scene.py, scene.pz, AttrScope{ATTR_SCOPE_SELECTED, a.cand, a.words, nullptr, 0u}, n, c->cu_count, nullptr, c->stream);
     launch_mg_bound(ix, a, c->cu_count, c->stream);

@@ -33,11 +33,7 @@ int gsr::nb_check(gsr_ctx* c, const char* who, double radius, uint32_t cap, uint
     if (!(std::isnormal(r2) && std::isnormal(inv) && std::isnormal(inv_h)))
         return fail(c, GSR_ERR_ARG, "%s: radius (%g): radius * radius and 1 / radius must be finite and normal", who, radius);
     if (cap < cap_min || cap > cap_max) return fail(c, GSR_ERR_ARG, "%s: %s (%u) must be in %u .. %u", who, cap_name, cap, cap_min, cap_max);
-    if (scope & ~(ATTR_SCOPE_SELECTED | ATTR_SCOPE_VISIBLE)) return fail(c, GSR_ERR_ARG, "%s: unknown scope flags 0x%x", who, scope);
-    if (budget > GSR_NEIGHBOUR_MAX_BUDGET)
-        return fail(c, GSR_ERR_ARG, "%s: budget (%llu) is above GSR_NEIGHBOUR_MAX_BUDGET (%llu)", who, (unsigned long long)budget,
-                    (unsigned long long)GSR_NEIGHBOUR_MAX_BUDGET);
-    return GSR_OK;
+    return scope_check(c, who, scope, budget);
 }
 
 namespace {
@@ -90,7 +86,7 @@ int gsr::nb_index(gsr_ctx* c, const char* who, double radius, uint32_t cap, uint
     uint32_t* hist = nullptr;
     if (int r = nb_prepare(c, who, cap, 1.0 / (radius * (1.0 + 1.0 / 1024.0)), radius * radius, &k.ix, &hist)) return r;
     gsr_ctx::Neighbours& nb = c->nb;
-    k.sc = AttrScope{scope, sc.sel.mask, sc.sel.words, sc.hid.mask, sc.hid.words};
+    k.sc = scene_scope(sc, scope);
     k.n = n;
     k.hist = want_hist ? hist : nullptr;
     HIP_TRY(c, hipMemsetAsync(nb.counts, 0, (size_t)n * 4, c->stream));

@@ -4,17 +4,16 @@
 // are compiled with -ffp-contract=off.  include/gsplat_hip.h ("splat data") has the table the host sees.
 #pragma once
 #include "gsr_internal.h"
+#include "k_splat_ops.h"
 
 namespace gsr {
-
-__device__ __forceinline__ double attr_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 // the smallest (MAX false) / largest of a splat's three scales; NaN if any of them is
 template <bool MAX>
 __device__ __forceinline__ double attr_scale_extreme(const float4 s)
 {
     const double x = (double)s.x, y = (double)s.y, z = (double)s.z;
-    if (x != x || y != y || z != z) return attr_nan();
+    if (x != x || y != y || z != z) return f64_nan();
     double m = x;
     if (MAX ? y > m : y < m) m = y;
     if (MAX ? z > m : z < m) m = z;

@@ -3,13 +3,12 @@
 // (k_attr_select).  The value of attribute a of splat i is k_attr.h's attr_value, f64; nothing here states one of its own.
 //
 // The two reductions are grid-stride loops over runs of 64 splats, one per wave and step, on a grid sized from the device's
-// compute units (attr_grid).  A lane's scope bit comes from the scene's set words (set_word, k_splat_ops.h): the selection word and the
-// hidden word of i >> 5 are the same over each half of a wave64, so a wave whose 64 splats are all out of scope has no lane
-// left behind the test and loads nothing of the scene (k_edit.hip's idiom): a 1 % selection costs the words' n / 8 bytes.
+// compute units (attr_grid).  A lane's scope bit is in_scope's (k_splat_ops.h), so a wave whose 64 splats are all out of scope has
+// no lane left behind the test and loads nothing of the scene: a 1 % selection costs the words' n / 8 bytes.
 // Counts are integers, minimum and maximum commute: no result depends on the grid or on the order of arrival.
 //
 // The histogram is a per-workgroup LDS histogram of bins + 3 counters (below, at or above hi, NaN behind the bins): one LDS atomic
-// per lane in scope, and at the end one relaxed agent-scope add per non-zero counter.  The case to fear was every splat in one
+// per lane in scope, and at the end one relaxed agent-scope add per non-zero counter (lds_counters_*, k_splat_ops.h).  The case to fear was every splat in one
 // bin -- opacity 255 everywhere, pixels == 0 after a short tour -- where 64 lanes of every wave meet in one LDS address.
 // Measured it is the FASTEST case: the LDS serves a wave's 64 same-address adds in well under the time
 // its loads take, and a workgroup then flushes one counter instead of hundreds.  What costs is the flush: same-address global
@@ -30,30 +29,12 @@ GSR_BOUNDS_DECL(attr)   // sites: 0 set word, 1 splat index, 2 LDS counter, 3 gl
 
 constexpr int ATTR_THREADS = 256;
 
-// the bits of word wi whose splats are in scope: below n, selected (ATTR_SCOPE_SELECTED; no words: nothing is), not hidden
-// (ATTR_SCOPE_VISIBLE; no words: nothing is hidden)
-__device__ __forceinline__ uint32_t attr_scope_word(const AttrScope& sc, uint32_t n, uint32_t wi)
-{
-    uint32_t m = set_live_bits(n, wi);
-    if (!m) return 0u;
-    if (sc.flags & ATTR_SCOPE_SELECTED) {
-        if (!sc.sel) return 0u;
-        GSR_BOUND(attr, 0, wi, sc.sel_words);
-        m &= set_word(sc.sel, sc.sel_words, n, wi);
-    }
-    if (m && (sc.flags & ATTR_SCOPE_VISIBLE) && sc.hid) {
-        GSR_BOUND(attr, 0, wi, sc.hid_words);
-        m &= ~set_word(sc.hid, sc.hid_words, n, wi);
-    }
-    return m;
-}
-
-// is splat i (any i: at and above n never) in scope?
-__device__ __forceinline__ bool attr_in_scope(const AttrScope& sc, uint32_t n, uint64_t i)
-{
-    if (i >= n) return false;
-    return (attr_scope_word(sc, n, (uint32_t)(i >> 5)) & (1u << ((uint32_t)i & 31u))) != 0u;
-}
+// the sites of the shared helpers (k_splat_ops.h)
+struct attr_sites {
+    static __device__ __forceinline__ void bound_set_word(unsigned long long idx, unsigned long long limit) { GSR_BOUND(attr, 0, idx, limit); }
+    static __device__ __forceinline__ void bound_counter(unsigned long long idx, unsigned long long limit) { GSR_BOUND(attr, 3, idx, limit); }
+    static __device__ __forceinline__ void bound_mask_word(unsigned long long idx, unsigned long long limit) { GSR_BOUND(attr, 5, idx, limit); }
+};
 
 // ---- count, NaNs, minimum, maximum ----
 // A value enters min only through `v < min` and max only through `v > max`, in a thread's fold, across lanes, waves and partials
@@ -69,7 +50,7 @@ __device__ __forceinline__ AttrStats stats_empty()
 {
     AttrStats a;
     a.count = 0u; a.nan = 0u;
-    a.mn = __longlong_as_double(0x7ff0000000000000ll); a.mx = __longlong_as_double((long long)0xfff0000000000000ull);
+    a.mn = f64_inf(); a.mx = -f64_inf();
     return a;
 }
 
@@ -95,7 +76,7 @@ __global__ __launch_bounds__(ATTR_THREADS) void k_attr_stats(int attr, AttrSourc
     AttrStats a = stats_empty();
     const uint64_t stride = (uint64_t)gridDim.x * ATTR_THREADS, end = ((uint64_t)n + 63u) & ~63ull;   // whole waves step together
     for (uint64_t i = (uint64_t)blockIdx.x * ATTR_THREADS + threadIdx.x; i < end; i += stride) {
-        if (!attr_in_scope(sc, n, i)) continue;
+        if (!in_scope<attr_sites>(sc, n, i)) continue;
         GSR_BOUND(attr, 1, i, n);
         const double v = attr_value(attr, src, (uint32_t)i);
         if (v != v) stats_take(a, 1u, 1u, a.mn, a.mx);
@@ -149,13 +130,12 @@ __global__ __launch_bounds__(ATTR_THREADS) void k_attr_hist(int attr, AttrSource
 {
     extern __shared__ uint32_t s_hist[];   // bins + 3
     const uint32_t ncounters = r.bins + 3u;
-    for (uint32_t k = threadIdx.x; k < ncounters; k += ATTR_THREADS) s_hist[k] = 0u;
-    __syncthreads();
+    lds_counters_zero(s_hist, ncounters, ATTR_THREADS);
 
     const int lane = threadIdx.x & 63;
     const uint64_t stride = (uint64_t)gridDim.x * ATTR_THREADS, end = ((uint64_t)n + 63u) & ~63ull;   // whole waves step together
     for (uint64_t i = (uint64_t)blockIdx.x * ATTR_THREADS + threadIdx.x; i < end; i += stride) {
-        const bool in = attr_in_scope(sc, n, i);
+        const bool in = in_scope<attr_sites>(sc, n, i);
         uint32_t b = 0u;
         if (in) {
             GSR_BOUND(attr, 1, i, n);
@@ -176,21 +156,12 @@ __global__ __launch_bounds__(ATTR_THREADS) void k_attr_hist(int attr, AttrSource
         }
         if (mine) __hip_atomic_fetch_add(&s_hist[b], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
-    __syncthreads();   // the workgroup's counters are final
-
-    // relaxed, agent scope, results unused (return-less atomics); a counter nobody touched costs nothing
-    for (uint32_t k = threadIdx.x; k < ncounters; k += ATTR_THREADS) {
-        const uint32_t c = s_hist[k];
-        if (!c) continue;
-        GSR_BOUND(attr, 3, k, ATTR_MAX_BINS + 3u);
-        __hip_atomic_fetch_add(&counters[k], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    lds_counters_flush<attr_sites>(s_hist, ncounters, ATTR_THREADS, counters, ATTR_MAX_BINS + 3u);
 }
 
 // ---- the range picker ----
-// gsr_select_attr.  One thread per bit of the mask: lo <= v && v < hi, so a NaN is never picked.  A wave's 64-bit ballot IS two
-// whole words of the mask (k_contrib_select, k_select_box): lane 0 stores them, no atomics, and every word of the mask is stored
-// (splats at and above n vote 0).
+// gsr_select_attr.  One thread per bit of the mask: lo <= v && v < hi, so a NaN is never picked.  A wave's ballot is two
+// whole words of the mask (mask_store_ballot, k_splat_ops.h): every word is stored (splats at and above n vote 0).
 __global__ __launch_bounds__(ATTR_THREADS) void k_attr_select(int attr, AttrSource src, uint32_t n, double lo, double hi, uint32_t* __restrict__ scratch,
                                                               uint32_t nwords)
 {
@@ -201,12 +172,7 @@ __global__ __launch_bounds__(ATTR_THREADS) void k_attr_select(int attr, AttrSour
         const double v = attr_value(attr, src, i);
         in = lo <= v && v < hi;
     }
-    const uint64_t m = __ballot(in);
-    if ((threadIdx.x & 63u) == 0u) {
-        const uint32_t w = i >> 5;   // (i is a multiple of 64: w is even)
-        if (w < nwords) { GSR_BOUND(attr, 5, w, nwords); scratch[w] = (uint32_t)m; }
-        if (w + 1u < nwords) { GSR_BOUND(attr, 5, w + 1u, nwords); scratch[w + 1u] = (uint32_t)(m >> 32); }
-    }
+    mask_store_ballot<attr_sites>(scratch, nwords, i, __ballot(in));
 }
 
 // ---- launchers ----
@@ -237,9 +203,7 @@ void launch_attr_hist(int attr, const AttrSource& src, const AttrScope& sc, uint
 void launch_attr_select(int attr, const AttrSource& src, uint32_t n, double lo, double hi, uint32_t* scratch, uint32_t nwords, hipStream_t s)
 {
     if (!nwords) return;
-    // one lane per bit of the mask, so that every word is stored
-    const uint32_t blocks = (uint32_t)(((uint64_t)nwords * 32u + ATTR_THREADS - 1) / ATTR_THREADS);
-    hipLaunchKernelGGL(k_attr_select, dim3(blocks), dim3(ATTR_THREADS), 0, s, attr, src, n, lo, hi, scratch, nwords);
+    hipLaunchKernelGGL(k_attr_select, dim3(mask_blocks(nwords, ATTR_THREADS)), dim3(ATTR_THREADS), 0, s, attr, src, n, lo, hi, scratch, nwords);
 }
 
 }  // namespace gsr

@@ -1,8 +1,8 @@
 // Clusters ("Clusters"): the connected islands of the splats in scope at a linking radius -- connected
 // components, or DBSCAN with a core threshold -- labelled, sized and picked.  The second operation that relates splats to each
-// other; it walks the index k_neighbours.hip builds (k_neighbours.h: the same keys, buckets and 27 cells) with the same pair test:
-// near(i, j) := i != j && (dx*dx + dy*dy) + dz*dz <= r2 in f64, in the written order, uncontracted, the stored cell key compared
-// before any f64 arithmetic.
+// other; it walks the index k_neighbours.hip builds through k_neighbours.h's nb_each_near: the same keys, buckets, 27 cells and pair
+// test, near(i, j) := i != j && (dx*dx + dy*dy) + dz*dz <= r2 in f64, in the written order, uncontracted, the stored cell key
+// compared before any f64 arithmetic.
 //
 // Stages, one launch each, so that what a stage reads is final:
 //   core     launch_nb_count with cap = min_pts (k_neighbours.hip): core_i := counts[i] >= min_pts.  Skipped for min_pts == 0.
@@ -13,7 +13,7 @@
 //   border   a non-core entry takes the smallest label among its near core entries (their labels are final: another launch).
 //   sizes    sizes[i] = size[label[i]] per splat; the largest cluster as one 64-bit maximum of size << 32 | ~label, which makes the
 //            tie go to the smallest label.
-//   pick     k_nb_select's form: a wave's ballot stored as two whole words into the selection's scratch.
+//   pick     a wave's ballot stored as two whole words into the selection's scratch (mask_store_ballot, k_splat_ops.h).
 //
 // The union is lock-free hooking in ECL-CC's form.  INVARIANT: parent[x] <= x at every instant (CL_NONE words are never followed:
 // only core splats are linked, and theirs are seeded).  It holds after the seed (parent[x] == x); a hook is ONE
@@ -35,30 +35,19 @@
 #include "gsr_internal.h"
 #include "k_splat_ops.h"
 
-namespace gsr {
-GSR_BOUNDS_DECL(clusters)   // sites: 0 set word, 1 entry slot, 2 bucket, 3 parent / label word, 4 size word, 5 selection word, 6 counts word, 7 sizes word
-}
-#define NB_BOUND_BUCKET(idx, limit) GSR_BOUND(clusters, 2, idx, limit)
 #include "k_neighbours.h"
 
 namespace gsr {
 
-// the bits of word wi whose splats are in scope (the rule of k_attr.hip's attr_scope_word: below n, selected, not hidden)
-__device__ __forceinline__ uint32_t cl_scope_word(const AttrScope& sc, uint32_t n, uint32_t wi)
-{
-    uint32_t m = set_live_bits(n, wi);
-    if (!m) return 0u;
-    if (sc.flags & ATTR_SCOPE_SELECTED) {
-        if (!sc.sel) return 0u;
-        GSR_BOUND(clusters, 0, wi, sc.sel_words);
-        m &= set_word(sc.sel, sc.sel_words, n, wi);
-    }
-    if (m && (sc.flags & ATTR_SCOPE_VISIBLE) && sc.hid) {
-        GSR_BOUND(clusters, 0, wi, sc.hid_words);
-        m &= ~set_word(sc.hid, sc.hid_words, n, wi);
-    }
-    return m;
-}
+GSR_BOUNDS_DECL(clusters)   // sites: 0 set word, 1 entry slot, 2 bucket, 3 parent / label word, 4 size word, 5 selection word, 6 counts word, 7 sizes word
+
+// the sites of the shared helpers (k_splat_ops.h, k_neighbours.h)
+struct cl_sites {
+    static __device__ __forceinline__ void bound_set_word(unsigned long long idx, unsigned long long limit) { GSR_BOUND(clusters, 0, idx, limit); }
+    static __device__ __forceinline__ void bound_entry(unsigned long long idx, unsigned long long limit) { GSR_BOUND(clusters, 1, idx, limit); }
+    static __device__ __forceinline__ void bound_bucket(unsigned long long idx, unsigned long long limit) { GSR_BOUND(clusters, 2, idx, limit); }
+    static __device__ __forceinline__ void bound_mask_word(unsigned long long idx, unsigned long long limit) { GSR_BOUND(clusters, 5, idx, limit); }
+};
 
 __device__ __forceinline__ uint32_t cl_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void cl_store(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -98,28 +87,6 @@ __device__ __forceinline__ uint32_t cl_unite(uint32_t* parent, uint32_t from, ui
         a = cl_find<true>(parent, old, n, info); b = small;            // strictly below big
     }
     return a == CL_NONE ? from : a;
-}
-
-// f(j) for every other entry within the radius of entry s (splat index j) that passes pre(j), while f returns true; k_nb_count's
-// walk: per cell the bucket's range, the key compare first, then pre, then the f64 pair test
-template <class P, class F>
-__device__ __forceinline__ void cl_each_near(const NbIndex& ix, uint32_t m, uint32_t s, const uint4& me, P pre, F f)
-{
-    const uint2* __restrict__ table = reinterpret_cast<const uint2*>(ix.table);   // (population, one behind the last entry)
-    const double x = (double)__uint_as_float(me.x), y = (double)__uint_as_float(me.y), z = (double)__uint_as_float(me.z);
-    nb_each_cell(ix.key[s], ix.bucket_mask, [&](unsigned long long nk, uint32_t b) {
-        const uint2 t = table[b];
-        GSR_BOUND(clusters, 1, t.y, (uint64_t)m + 1u);
-        if (t.y > m || t.x > t.y) return true;   // (never: a range of the entry array)
-        for (uint32_t e = t.y - t.x; e < t.y; e++) {
-            if (ix.key[e] != nk || e == s) continue;
-            const uint4 o = ix.entry[e];
-            if (!pre(o.w)) continue;
-            const double ex = x - (double)__uint_as_float(o.x), ey = y - (double)__uint_as_float(o.y), ez = z - (double)__uint_as_float(o.z);
-            if ((ex * ex + ey * ey) + ez * ez <= ix.r2 && !f(o.w)) return false;
-        }
-        return true;
-    });
 }
 
 // is splat j (an entry's index) core?  counts[] is launch_nb_count's with cap = min_pts (all zero for min_pts == 0)
@@ -177,7 +144,7 @@ __global__ __launch_bounds__(NB_THREADS) void k_cl_union(NbIndex ix, uint32_t m,
         const uint32_t i = me.w;
         if (!cl_core(counts, i, n, min_pts)) continue;
         uint32_t at = i;   // a node of i's tree, at or near its root
-        cl_each_near(ix, m, (uint32_t)s, me, [&](uint32_t j) { return j < i; }, [&](uint32_t j) {
+        nb_each_near<cl_sites>(ix, m, (uint32_t)s, me, [&](uint32_t j) { return j < i; }, [&](uint32_t j) {
             if (cl_core(counts, j, n, min_pts)) at = cl_unite(a.label, at, j, n, a.info);
             return true;
         });
@@ -221,7 +188,7 @@ __global__ __launch_bounds__(NB_THREADS) void k_cl_border(NbIndex ix, uint32_t m
             const uint4 me = ix.entry[s];
             i = me.w;
             if (i < n && !cl_core(counts, i, n, min_pts)) {
-                cl_each_near(ix, m, (uint32_t)s, me, [&](uint32_t) { return true; }, [&](uint32_t j) {
+                nb_each_near<cl_sites>(ix, m, (uint32_t)s, me, [&](uint32_t) { return true; }, [&](uint32_t j) {
                     if (cl_core(counts, j, n, min_pts)) label = min(label, a.label[j]);   // (a core entry's word: final, not written here)
                     return true;
                 });
@@ -258,29 +225,19 @@ __global__ __launch_bounds__(NB_THREADS) void k_cl_sizes(uint32_t n, ClArrays a)
 }
 
 // ---- the pickers ----
-// One thread per bit of the mask; a wave's ballot is two whole words (k_nb_select): every word of the mask is stored.
-__device__ __forceinline__ void cl_store_ballot(bool in, uint32_t i, uint32_t* __restrict__ scratch, uint32_t nwords)
-{
-    const uint64_t m = __ballot(in);
-    if ((threadIdx.x & 63u) == 0u) {
-        const uint32_t w = i >> 5;   // (i is a multiple of 64: w is even)
-        if (w < nwords) { GSR_BOUND(clusters, 5, w, nwords); scratch[w] = (uint32_t)m; }
-        if (w + 1u < nwords) { GSR_BOUND(clusters, 5, w + 1u, nwords); scratch[w + 1u] = (uint32_t)(m >> 32); }
-    }
-}
-
+// One thread per bit of the mask; a wave's ballot is two whole words (mask_store_ballot): every word of the mask is stored.
 // gsr_select_clusters: in scope and lo <= size < hi (noise and non-finite splats in scope have size 0)
 __global__ __launch_bounds__(NB_THREADS) void k_cl_select_sizes(const uint32_t* __restrict__ sizes, AttrScope sc, uint32_t n, uint32_t lo, uint32_t hi,
                                                                 uint32_t* __restrict__ scratch, uint32_t nwords)
 {
     const uint32_t i = blockIdx.x * NB_THREADS + threadIdx.x;
     bool in = false;
-    if (i < n && (cl_scope_word(sc, n, i >> 5) & (1u << (i & 31u))) != 0u) {
+    if (in_scope<cl_sites>(sc, n, i)) {
         GSR_BOUND(clusters, 7, i, n);
         const uint32_t c = sizes[i];
         in = lo <= c && c < hi;
     }
-    cl_store_ballot(in, i, scratch, nwords);
+    mask_store_ballot<cl_sites>(scratch, nwords, i, __ballot(in));
 }
 
 // gsr_select_cluster_at: label == target (a labelled splat is in scope; CL_NONE picks nobody)
@@ -293,7 +250,7 @@ __global__ __launch_bounds__(NB_THREADS) void k_cl_select_label(const uint32_t* 
         GSR_BOUND(clusters, 7, i, n);
         in = label[i] == target;
     }
-    cl_store_ballot(in, i, scratch, nwords);
+    mask_store_ballot<cl_sites>(scratch, nwords, i, __ballot(in));
 }
 
 // ---- launchers ----
@@ -323,18 +280,16 @@ void launch_cl_sizes(uint32_t n, const ClArrays& a, int cu_count, hipStream_t s)
     hipLaunchKernelGGL(k_cl_sizes, dim3(nb_grid(n, cu_count)), dim3(NB_THREADS), 0, s, n, a);
 }
 
-static uint32_t cl_mask_blocks(uint32_t nwords) { return (uint32_t)(((uint64_t)nwords * 32u + NB_THREADS - 1) / NB_THREADS); }   // one lane per bit of the mask
-
 void launch_cl_select_sizes(const uint32_t* sizes, const AttrScope& sc, uint32_t n, uint32_t lo, uint32_t hi, uint32_t* scratch, uint32_t nwords, hipStream_t s)
 {
     if (!nwords) return;
-    hipLaunchKernelGGL(k_cl_select_sizes, dim3(cl_mask_blocks(nwords)), dim3(NB_THREADS), 0, s, sizes, sc, n, lo, hi, scratch, nwords);
+    hipLaunchKernelGGL(k_cl_select_sizes, dim3(mask_blocks(nwords, NB_THREADS)), dim3(NB_THREADS), 0, s, sizes, sc, n, lo, hi, scratch, nwords);
 }
 
 void launch_cl_select_label(const uint32_t* label, uint32_t n, uint32_t target, uint32_t* scratch, uint32_t nwords, hipStream_t s)
 {
     if (!nwords) return;
-    hipLaunchKernelGGL(k_cl_select_label, dim3(cl_mask_blocks(nwords)), dim3(NB_THREADS), 0, s, label, n, target, scratch, nwords);
+    hipLaunchKernelGGL(k_cl_select_label, dim3(mask_blocks(nwords, NB_THREADS)), dim3(NB_THREADS), 0, s, label, n, target, scratch, nwords);
 }
 
 }  // namespace gsr

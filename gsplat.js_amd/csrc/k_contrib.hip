@@ -22,12 +22,14 @@
 // Compiled with -ffp-contract=off like the rest of the device code: the fused multiply-adds are the explicit ones.
 #include "k_attr.h"
 #include "k_depth_walk.h"
+#include "k_splat_ops.h"
 
 namespace gsr {
 
 GSR_BOUNDS_DECL(contrib)   // sites: 0 - 3 the walk's (WALK_SITE_*: 0 - 2 in its helpers, 3 here), 4 accumulator index, 5 selection word
 struct ContribBounds {
     static __device__ __forceinline__ void bound(int site, unsigned long long idx, unsigned long long limit) { GSR_BOUND(contrib, site, idx, limit); }
+    static __device__ __forceinline__ void bound_mask_word(unsigned long long idx, unsigned long long limit) { GSR_BOUND(contrib, 5, idx, limit); }   // (k_splat_ops.h)
 };
 constexpr int CONTRIB_SELECT_THREADS = 256;
 constexpr float CONTRIB_QUANTA = 16777216.0f;   // 2^24
@@ -148,8 +150,8 @@ __global__ __launch_bounds__(DEPTH_THREADS) void k_contrib(ContribBuffers a, Bin
     }
 }
 
-// gsr_select_contrib.  One thread per splat: its value in f64 (attr_value, k_attr.h), compared with `below`.  A wave's 64-bit ballot IS two whole words
-// of the mask (k_select_box): lane 0 stores them, no atomics, and every word of the mask is stored (splats at and above n vote 0).
+// gsr_select_contrib.  One thread per splat: its value in f64 (attr_value, k_attr.h), compared with `below`.  A wave's ballot is two whole words
+// of the mask (mask_store_ballot, k_splat_ops.h): every word of the mask is stored (splats at and above n vote 0).
 __global__ __launch_bounds__(CONTRIB_SELECT_THREADS) void k_contrib_select(int stat, double below, uint32_t n, const unsigned long long* __restrict__ weight,
                                                                            const uint32_t* __restrict__ peak, const uint32_t* __restrict__ pixels,
                                                                            uint32_t* __restrict__ scratch, uint32_t nwords)
@@ -160,12 +162,7 @@ __global__ __launch_bounds__(CONTRIB_SELECT_THREADS) void k_contrib_select(int s
         const AttrSource src{nullptr, nullptr, nullptr, nullptr, nullptr, weight, peak, pixels, 0.0, 0.0, 0.0};
         in = attr_value(ATTR_CONTRIB_WEIGHT + stat, src, i) < below;   // (the one statement of the value: k_attr.h)
     }
-    const uint64_t m = __ballot(in);
-    if ((threadIdx.x & 63u) == 0u) {
-        const uint32_t w = i >> 5;   // (i is a multiple of 64: w is even)
-        if (w < nwords) { GSR_BOUND(contrib, 5, w, nwords); scratch[w] = (uint32_t)m; }
-        if (w + 1u < nwords) { GSR_BOUND(contrib, 5, w + 1u, nwords); scratch[w + 1u] = (uint32_t)(m >> 32); }
-    }
+    mask_store_ballot<ContribBounds>(scratch, nwords, i, __ballot(in));
 }
 
 void launch_contrib(const ContribBuffers& b, const BinGrid& g, const CamParams& cam, bool skip, hipStream_t s)
@@ -177,9 +174,7 @@ void launch_contrib_select(int stat, double below, uint32_t n, const unsigned lo
                            uint32_t* scratch, uint32_t nwords, hipStream_t s)
 {
     if (!nwords) return;
-    // one lane per bit of the mask, so that every word is stored
-    const uint32_t blocks = (uint32_t)(((uint64_t)nwords * 32u + CONTRIB_SELECT_THREADS - 1) / CONTRIB_SELECT_THREADS);
-    hipLaunchKernelGGL(k_contrib_select, dim3(blocks), dim3(CONTRIB_SELECT_THREADS), 0, s, stat, below, n, weight, peak, pixels, scratch, nwords);
+    hipLaunchKernelGGL(k_contrib_select, dim3(mask_blocks(nwords, CONTRIB_SELECT_THREADS)), dim3(CONTRIB_SELECT_THREADS), 0, s, stat, below, n, weight, peak, pixels, scratch, nwords);
 }
 
 }  // namespace gsr

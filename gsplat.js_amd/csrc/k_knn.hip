@@ -3,7 +3,7 @@
 // list: the distance to the k-th, or the mean distance to those found.  Statistical outlier removal is a picker on that value.
 // The index is k_neighbours.hip's, as it is: scope, cells, the pair test and the treatment of non-finite rows are its own.
 //
-// The walk.  k_knn takes the ENTRIES in index order, one per lane, grid-stride, and visits the 27 cells as k_nb_count does: one
+// The walk.  k_knn takes the ENTRIES in index order, one per lane, grid-stride, and visits the 27 cells (nb_each_cell): one
 // 8-byte (population, end) load per cell, the stored cell key compared BEFORE any f64 arithmetic, so that an entry is met once
 // however the cells hash.  What is new is that every lane keeps a sorted list.  A register array indexed by a loop variable
 // becomes scratch memory, so the list lives in LDS, lane-strided: slot t of lane l at [t * blockDim + l], a column of d2 and a
@@ -15,47 +15,26 @@
 //
 // The workgroup is sized by k (knn_threads): 12 bytes per lane and slot, 48 KiB of lists at most, so that three workgroups fit a
 // CU's 160 KiB at k = 32.  At the end a lane computes its value from its own column in ascending slot order, stores found, the value
-// and (LISTS) its k slots at the splat's row, and adds to the workgroup's LDS histogram of k + 1 counters, flushed as k_nb_count's.
+// and (LISTS) its k slots at the splat's row, and adds to the workgroup's LDS histogram of k + 1 counters (lds_counters_*, k_splat_ops.h).
 // complete, finite_values, min and max are reduced over the wave and cost one atomic each per wave: the values are
 // non-negative doubles, so min and max go through their bit patterns as 64-bit unsigned maxima (KnnInfo).
 //
 // Compiled with -ffp-contract=off like the rest of the device code.
 #include "gsr_internal.h"
 #include "k_splat_ops.h"
-
-namespace gsr {
-GSR_BOUNDS_DECL(knn)   // sites: 0 set word, 1 entry slot, 2 bucket, 3 LDS list slot, 4 LDS counter, 5 global counter, 6 selection word, 7 splat row
-}
-#define NB_BOUND_BUCKET(idx, limit) GSR_BOUND(knn, 2, idx, limit)
 #include "k_neighbours.h"   // the key, the bucket and the 27-cell walk
 
 namespace gsr {
 
-// the bits of word wi whose splats are in scope (the rule of k_attr.hip's attr_scope_word: below n, selected, not hidden)
-__device__ __forceinline__ uint32_t knn_scope_word(const AttrScope& sc, uint32_t n, uint32_t wi)
-{
-    uint32_t m = set_live_bits(n, wi);
-    if (!m) return 0u;
-    if (sc.flags & ATTR_SCOPE_SELECTED) {
-        if (!sc.sel) return 0u;
-        GSR_BOUND(knn, 0, wi, sc.sel_words);
-        m &= set_word(sc.sel, sc.sel_words, n, wi);
-    }
-    if (m && (sc.flags & ATTR_SCOPE_VISIBLE) && sc.hid) {
-        GSR_BOUND(knn, 0, wi, sc.hid_words);
-        m &= ~set_word(sc.hid, sc.hid_words, n, wi);
-    }
-    return m;
-}
+GSR_BOUNDS_DECL(knn)   // sites: 0 set word, 1 entry slot, 2 bucket, 3 LDS list slot, 4 LDS counter, 5 global counter, 6 selection word, 7 splat row
 
-__device__ __forceinline__ bool knn_in_scope(const AttrScope& sc, uint32_t n, uint64_t i)
-{
-    if (i >= n) return false;
-    return (knn_scope_word(sc, n, (uint32_t)(i >> 5)) & (1u << ((uint32_t)i & 31u))) != 0u;
-}
-
-__device__ __forceinline__ double knn_inf() { return __longlong_as_double(0x7ff0000000000000ll); }
-__device__ __forceinline__ double knn_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
+// the sites of the shared helpers (k_splat_ops.h, k_neighbours.h)
+struct knn_sites {
+    static __device__ __forceinline__ void bound_set_word(unsigned long long idx, unsigned long long limit) { GSR_BOUND(knn, 0, idx, limit); }
+    static __device__ __forceinline__ void bound_bucket(unsigned long long idx, unsigned long long limit) { GSR_BOUND(knn, 2, idx, limit); }
+    static __device__ __forceinline__ void bound_counter(unsigned long long idx, unsigned long long limit) { GSR_BOUND(knn, 5, idx, limit); }
+    static __device__ __forceinline__ void bound_mask_word(unsigned long long idx, unsigned long long limit) { GSR_BOUND(knn, 6, idx, limit); }
+};
 
 // ---- the rows the walk does not reach ----
 // Every row as a splat outside the index has it; the walk then overwrites the rows of its entries.
@@ -64,13 +43,13 @@ __global__ __launch_bounds__(NB_THREADS) void k_knn_fill(AttrScope sc, uint32_t 
     const uint64_t stride = (uint64_t)gridDim.x * NB_THREADS, first = (uint64_t)blockIdx.x * NB_THREADS + threadIdx.x;
     for (uint64_t i = first; i < n; i += stride) {
         a.found[i] = 0u;
-        a.values[i] = knn_in_scope(sc, n, i) ? knn_inf() : knn_nan();
+        a.values[i] = in_scope<knn_sites>(sc, n, i) ? f64_inf() : f64_nan();
     }
     if (!a.idx) return;
     const uint64_t slots = (uint64_t)n * k;
     for (uint64_t t = first; t < slots; t += stride) {
         a.idx[t] = KNN_NONE;
-        a.d2[t] = knn_inf();
+        a.d2[t] = f64_inf();
     }
 }
 
@@ -85,8 +64,7 @@ __global__ __launch_bounds__(NB_THREADS) void k_knn(NbIndex ix, uint32_t m /* en
     double* const s_d2 = reinterpret_cast<double*>(s_knn);
     uint32_t* const s_j = reinterpret_cast<uint32_t*>(s_d2 + slots);
     uint32_t* const s_hist = s_j + slots;
-    for (uint32_t t = threadIdx.x; t <= k; t += T) s_hist[t] = 0u;
-    __syncthreads();
+    lds_counters_zero(s_hist, k + 1u, T);
     double* const my_d2 = s_d2 + threadIdx.x;     // this lane's columns: slot t at [t * T]
     uint32_t* const my_j = s_j + threadIdx.x;
     const uint2* __restrict__ table = reinterpret_cast<const uint2*>(ix.table);   // (population, one behind the last entry)
@@ -99,13 +77,13 @@ __global__ __launch_bounds__(NB_THREADS) void k_knn(NbIndex ix, uint32_t m /* en
         const double x = (double)__uint_as_float(me.x), y = (double)__uint_as_float(me.y), z = (double)__uint_as_float(me.z);
         uint32_t found = 0u, wj = 0u;   // the list's length; (wd, wj): its last pair once it is full
         double wd = 0.0;
-        nb_each_cell(ix.key[s], ix.bucket_mask, [&](unsigned long long nk, uint32_t b) {
+        nb_each_cell<knn_sites>(ix.key[s], ix.bucket_mask, [&](unsigned long long nk, uint32_t b) {
             const uint2 t = table[b];
             GSR_BOUND(knn, 1, t.y, (uint64_t)m + 1u);
             if (t.y > m || t.x > t.y) return true;   // (never: a range of the entry array)
-            // KNN_BATCH candidates at a time, their keys and entries loaded together in front of any use: with the few waves the lists
-            // leave room for, nothing else hides the latency of a load that waits for the one before it (a slot behind the range's
-            // end repeats the last one and is skipped below)
+            // Not nb_each_near's loop: KNN_BATCH candidates at a time, their keys and entries loaded together in front of any use.
+            // With the few waves the lists leave room for, nothing else hides the latency of a load that waits for the one before
+            // it (a slot behind the range's end repeats the last one and is skipped below)
             for (uint32_t e0 = t.y - t.x; e0 < t.y; e0 += KNN_BATCH) {
                 unsigned long long ck[KNN_BATCH];
                 uint4 co[KNN_BATCH];
@@ -146,7 +124,7 @@ __global__ __launch_bounds__(NB_THREADS) void k_knn(NbIndex ix, uint32_t m /* en
             return true;
         });
         // the value, from the lane's own column in ascending slot order
-        double value = knn_inf();
+        double value = f64_inf();
         if (STAT == KNN_KTH) {
             if (found == k) value = __dsqrt_rn(wd);
         } else if (found) {
@@ -162,7 +140,7 @@ __global__ __launch_bounds__(NB_THREADS) void k_knn(NbIndex ix, uint32_t m /* en
                 const uint64_t row = (uint64_t)me.w * k;
                 for (uint32_t t = 0u; t < k; t++) {
                     a.idx[row + t] = t < found ? my_j[t * T] : KNN_NONE;
-                    a.d2[row + t] = t < found ? my_d2[t * T] : knn_inf();
+                    a.d2[row + t] = t < found ? my_d2[t * T] : f64_inf();
                 }
             }
         }
@@ -192,34 +170,23 @@ __global__ __launch_bounds__(NB_THREADS) void k_knn(NbIndex ix, uint32_t m /* en
             __hip_atomic_fetch_max(&a.info->nvmin, nvmin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
-    __syncthreads();   // the workgroup's counters are final
-    for (uint32_t t = threadIdx.x; t <= k; t += T) {
-        const uint32_t c = s_hist[t];
-        if (!c) continue;
-        GSR_BOUND(knn, 5, t, KNN_MAX_K + 1u);
-        __hip_atomic_fetch_add(&hist[t], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    lds_counters_flush<knn_sites>(s_hist, k + 1u, T, hist, KNN_MAX_K + 1u);
 }
 
 // ---- the picker ----
 // gsr_select_knn.  One thread per bit of the mask: in scope, lo <= value && (value < hi || hi is +inf).  A wave's ballot is two
-// whole words (k_nb_select): every word of the mask is stored.
+// whole words (mask_store_ballot): every word of the mask is stored.
 __global__ __launch_bounds__(NB_THREADS) void k_knn_select(const double* __restrict__ values, AttrScope sc, uint32_t n, double lo, double hi, uint32_t open_hi,
                                                            uint32_t* __restrict__ scratch, uint32_t nwords)
 {
     const uint32_t i = blockIdx.x * NB_THREADS + threadIdx.x;
     bool in = false;
-    if (knn_in_scope(sc, n, i)) {
+    if (in_scope<knn_sites>(sc, n, i)) {
         GSR_BOUND(knn, 7, i, n);
         const double v = values[i];
         in = lo <= v && (v < hi || open_hi != 0u);
     }
-    const uint64_t m = __ballot(in);
-    if ((threadIdx.x & 63u) == 0u) {
-        const uint32_t w = i >> 5;   // (i is a multiple of 64: w is even)
-        if (w < nwords) { GSR_BOUND(knn, 6, w, nwords); scratch[w] = (uint32_t)m; }
-        if (w + 1u < nwords) { GSR_BOUND(knn, 6, w + 1u, nwords); scratch[w + 1u] = (uint32_t)(m >> 32); }
-    }
+    mask_store_ballot<knn_sites>(scratch, nwords, i, __ballot(in));
 }
 
 // ---- launchers ----
@@ -242,9 +209,7 @@ void launch_knn(const NbIndex& ix, uint32_t indexed, uint32_t n, uint32_t k, int
 void launch_knn_select(const double* values, const AttrScope& sc, uint32_t n, double lo, double hi, bool open_hi, uint32_t* scratch, uint32_t nwords, hipStream_t s)
 {
     if (!nwords) return;
-    // one lane per bit of the mask, so that every word is stored
-    const uint32_t blocks = (uint32_t)(((uint64_t)nwords * 32u + NB_THREADS - 1) / NB_THREADS);
-    hipLaunchKernelGGL(k_knn_select, dim3(blocks), dim3(NB_THREADS), 0, s, values, sc, n, lo, hi, open_hi ? 1u : 0u, scratch, nwords);
+    hipLaunchKernelGGL(k_knn_select, dim3(mask_blocks(nwords, NB_THREADS)), dim3(NB_THREADS), 0, s, values, sc, n, lo, hi, open_hi ? 1u : 0u, scratch, nwords);
 }
 
 }  // namespace gsr

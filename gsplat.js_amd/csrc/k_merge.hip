@@ -8,7 +8,7 @@
 // k_mg_bound       the sum over the buckets of population^2: what the walk tests at most, checked against the budget first.
 // k_mg_walk        one entry per lane, in index order.  The lane walks its OWN bucket and compares the stored key in front of
 //                  anything else: it ends with its cell's smallest member index (the leader), the members and its rank among
-//                  them.  A leader counts its cell (histogram through LDS counters, as k_nb_count) and, for two or more members,
+//                  them.  A leader counts its cell (histogram through LDS counters: lds_counters_*, k_splat_ops.h) and, for two or more members,
 //                  takes a slice of the member list and a cell record.  Slices and records are handed out per WAVE: a scan of the
 //                  wave's sizes and two atomics by its first lane, so the cursors see one atomic per 64 entries.  Where a slice
 //                  lies decides nothing: a cell reads only its own.
@@ -23,59 +23,35 @@
 // All arithmetic of the merged row is f64 in the header's order; compiled with -ffp-contract=off like the rest of the device code.
 #include "gsr_internal.h"
 #include "k_splat_ops.h"
-
-namespace gsr {
-GSR_BOUNDS_DECL(merge)   // sites: 0 set word, 1 splat index, 2 bucket, 3 entry slot, 4 LDS counter, 5 cell record, 6 mask word stored, 7 member slot
-}
-#define NB_BOUND_BUCKET(idx, limit) GSR_BOUND(merge, 2, idx, limit)
 #include "k_neighbours.h"   // the key and the bucket
 
 namespace gsr {
 
-// the bits of word wi whose splats are in scope (the rule of k_attr.hip's attr_scope_word: below n, selected, not hidden)
-__device__ __forceinline__ uint32_t mg_scope_word(const AttrScope& sc, uint32_t n, uint32_t wi)
-{
-    uint32_t m = set_live_bits(n, wi);
-    if (!m) return 0u;
-    if (sc.flags & ATTR_SCOPE_SELECTED) {
-        if (!sc.sel) return 0u;
-        GSR_BOUND(merge, 0, wi, sc.sel_words);
-        m &= set_word(sc.sel, sc.sel_words, n, wi);
-    }
-    if (m && (sc.flags & ATTR_SCOPE_VISIBLE) && sc.hid) {
-        GSR_BOUND(merge, 0, wi, sc.hid_words);
-        m &= ~set_word(sc.hid, sc.hid_words, n, wi);
-    }
-    return m;
-}
+GSR_BOUNDS_DECL(merge)   // sites: 0 set word, 1 splat index, 2 bucket, 3 entry slot, 4 LDS counter, 5 cell record, 6 mask word stored, 7 member slot
 
-__device__ __forceinline__ bool mg_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-// a wave's ballot as the two words of a mask it covers (i: the first lane's bit, a multiple of 64)
-__device__ __forceinline__ void mg_store_ballot(uint32_t* __restrict__ words, uint32_t nwords, uint32_t i, uint64_t m)
-{
-    if ((threadIdx.x & 63u) != 0u) return;
-    const uint32_t w = i >> 5;
-    if (w < nwords) { GSR_BOUND(merge, 6, w, nwords); words[w] = (uint32_t)m; }
-    if (w + 1u < nwords) { GSR_BOUND(merge, 6, w + 1u, nwords); words[w + 1u] = (uint32_t)(m >> 32); }
-}
+// the sites of the shared helpers (k_splat_ops.h)
+struct mg_sites {
+    static __device__ __forceinline__ void bound_set_word(unsigned long long idx, unsigned long long limit) { GSR_BOUND(merge, 0, idx, limit); }
+    static __device__ __forceinline__ void bound_counter(unsigned long long idx, unsigned long long limit) { GSR_BOUND(merge, 4, idx, limit); }
+    static __device__ __forceinline__ void bound_mask_word(unsigned long long idx, unsigned long long limit) { GSR_BOUND(merge, 6, idx, limit); }
+};
 
 // ---- the candidates ----
 __global__ __launch_bounds__(NB_THREADS) void k_mg_candidates(SceneDev scene, AttrScope sc, uint32_t n, MgArrays a)
 {
     __shared__ uint32_t s_w[NB_THREADS / WAVE];
     const uint32_t i = blockIdx.x * NB_THREADS + threadIdx.x;
-    const bool in = i < n && (mg_scope_word(sc, n, i >> 5) & (1u << (i & 31u))) != 0u;
+    const bool in = in_scope<mg_sites>(sc, n, i);
     bool cand = false;
     if (in) {
         GSR_BOUND(merge, 1, i, n);
         const float x = scene.px[i], y = scene.py[i], z = scene.pz[i];
         const float4 r = scene.rot[i], s = scene.scl[i];
-        cand = mg_finite(x) && mg_finite(y) && mg_finite(z) && mg_finite(r.x) && mg_finite(r.y) && mg_finite(r.z) && mg_finite(r.w) && mg_finite(s.x) &&
-               mg_finite(s.y) && mg_finite(s.z);
+        cand = f32_finite(x) && f32_finite(y) && f32_finite(z) && f32_finite(r.x) && f32_finite(r.y) && f32_finite(r.z) && f32_finite(r.w) && f32_finite(s.x) &&
+               f32_finite(s.y) && f32_finite(s.z);
     }
     const uint64_t ms = __ballot(in), mc = __ballot(cand);
-    mg_store_ballot(a.cand, a.words, i & ~63u, mc);
+    mask_store_ballot<mg_sites>(a.cand, a.words, i, mc);
     if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = (uint32_t)__popcll(ms);
     __syncthreads();
     if (threadIdx.x != 0u) return;
@@ -88,7 +64,6 @@ __global__ __launch_bounds__(NB_THREADS) void k_mg_candidates(SceneDev scene, At
 // An entry walks its own bucket: population tests for each of the bucket's population entries.
 __global__ __launch_bounds__(NB_THREADS) void k_mg_bound(NbIndex ix, MgArrays a)
 {
-    __shared__ unsigned long long s_part[NB_THREADS / WAVE];
     const uint64_t buckets = (uint64_t)ix.bucket_mask + 1u, stride = (uint64_t)gridDim.x * NB_THREADS;
     unsigned long long sum = 0ull;
     for (uint64_t b = (uint64_t)blockIdx.x * NB_THREADS + threadIdx.x; b < buckets; b += stride) {
@@ -96,13 +71,7 @@ __global__ __launch_bounds__(NB_THREADS) void k_mg_bound(NbIndex ix, MgArrays a)
         const unsigned long long p = ix.table[2ull * b];
         sum += p * p;
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
-    if ((threadIdx.x & 63u) == 0u) s_part[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x != 0u) return;
-    for (int w = 1; w < NB_THREADS / WAVE; w++) sum += s_part[w];
-    if (sum) __hip_atomic_fetch_add(&a.info->pair_bound, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    workgroup_sum_u64<NB_THREADS>(sum, &a.info->pair_bound);
 }
 
 // ---- the walk ----
@@ -111,10 +80,7 @@ __global__ __launch_bounds__(NB_THREADS) void k_mg_walk(NbIndex ix, uint32_t m /
                                                         uint32_t* __restrict__ hist)
 {
     extern __shared__ uint32_t s_hist[];   // cap + 1 (HIST)
-    if (HIST) {
-        for (uint32_t k = threadIdx.x; k <= cap; k += NB_THREADS) s_hist[k] = 0u;
-        __syncthreads();
-    }
+    if (HIST) lds_counters_zero(s_hist, cap + 1u, NB_THREADS);
     const uint2* __restrict__ table = reinterpret_cast<const uint2*>(ix.table);   // (population, one behind the last entry)
     const uint32_t lane = threadIdx.x & 63u, max_cells = n / 2u + 1u;
     uint32_t cells = 0u, largest = 0u;
@@ -184,14 +150,7 @@ __global__ __launch_bounds__(NB_THREADS) void k_mg_walk(NbIndex ix, uint32_t m /
         __hip_atomic_fetch_add(&a.info->cells, cells, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_fetch_max(&a.info->largest, largest, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (!HIST) return;
-    __syncthreads();   // the workgroup's counters are final
-    for (uint32_t k = threadIdx.x; k <= cap; k += NB_THREADS) {
-        const uint32_t c = s_hist[k];
-        if (!c) continue;
-        GSR_BOUND(merge, 4, k, NB_MAX_CAP + 1u);
-        __hip_atomic_fetch_add(&hist[k], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (HIST) lds_counters_flush<mg_sites>(s_hist, cap + 1u, NB_THREADS, hist, NB_MAX_CAP + 1u);
 }
 
 // ---- the member lists and the compaction's masks ----
@@ -210,8 +169,8 @@ __global__ __launch_bounds__(NB_THREADS) void k_mg_members(uint32_t n, uint32_t 
         else __hip_atomic_fetch_add(&a.info->fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     const uint64_t br = __ballot(rem), bg = __ballot(mrg);
-    mg_store_ballot(a.remove, a.words, i & ~63u, br);
-    mg_store_ballot(a.merged, a.words, i & ~63u, bg);
+    mask_store_ballot<mg_sites>(a.remove, a.words, i, br);
+    mask_store_ballot<mg_sites>(a.merged, a.words, i, bg);
 }
 
 // ---- the reduction ----
@@ -328,9 +287,7 @@ __global__ __launch_bounds__(NB_THREADS) void k_mg_reduce(SceneDev scene, uint32
 // ---- launchers ----
 void launch_mg_candidates(const SceneDev& scene, const AttrScope& sc, uint32_t n, const MgArrays& a, hipStream_t s)
 {
-    // one lane per bit of the mask, so that every word is stored
-    const uint32_t blocks = (uint32_t)(((uint64_t)a.words * 32u + NB_THREADS - 1) / NB_THREADS);
-    hipLaunchKernelGGL(k_mg_candidates, dim3(blocks), dim3(NB_THREADS), 0, s, scene, sc, n, a);
+    hipLaunchKernelGGL(k_mg_candidates, dim3(mask_blocks(a.words, NB_THREADS)), dim3(NB_THREADS), 0, s, scene, sc, n, a);
 }
 
 void launch_mg_bound(const NbIndex& ix, const MgArrays& a, int cu_count, hipStream_t s)
@@ -348,8 +305,7 @@ void launch_mg_walk(const NbIndex& ix, uint32_t indexed, uint32_t n, uint32_t ca
 
 void launch_mg_members(uint32_t n, uint32_t merged_members, const MgArrays& a, hipStream_t s)
 {
-    const uint32_t blocks = (uint32_t)(((uint64_t)a.words * 32u + NB_THREADS - 1) / NB_THREADS);
-    hipLaunchKernelGGL(k_mg_members, dim3(blocks), dim3(NB_THREADS), 0, s, n, merged_members, a);
+    hipLaunchKernelGGL(k_mg_members, dim3(mask_blocks(a.words, NB_THREADS)), dim3(NB_THREADS), 0, s, n, merged_members, a);
 }
 
 void launch_mg_reduce(const SceneDev& scene, uint32_t n, uint32_t merged_cells, uint32_t merged_members, const MgArrays& a, hipStream_t s)

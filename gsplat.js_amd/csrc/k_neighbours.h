@@ -1,18 +1,13 @@
 // The device side of the spatial index (k_neighbours.hip builds it; DESIGN.md section 3, "Neighbours") for the kernels that walk
-// it: k_neighbours.hip's own and k_clusters.hip's.  The cell key, its hash bucket and the 27-cell walk are stated here once, so
-// that every walk over the index visits the cells the build made.  (What only the build needs -- a position's cell, the scope of a
-// call -- stays in k_neighbours.hip.)
+// it: k_neighbours.hip's own, k_clusters.hip's, k_knn.hip's and k_merge.hip's.  The cell key, its hash bucket, the 27-cell walk and
+// the walk over the entries near one are stated here once, so that every walk over the index visits the cells the build made and
+// tests pairs the same way.  (What only the build needs -- a position's cell -- stays in k_neighbours.hip.)
 //
-// The bounds twin counts per translation unit, so the includer names its own site in front of the include:
-//     NB_BOUND_BUCKET(idx, limit)   a bucket of the table
+// Sites: the includer's bounds sites (k_splat_ops.h): bound_bucket (a bucket of the table), bound_entry (a slot of the entry array).
 #pragma once
 #include "gsr_internal.h"
 
 #include <algorithm>
-
-#ifndef NB_BOUND_BUCKET
-#error "define NB_BOUND_BUCKET (the translation unit's GSR_BOUND site for a bucket) in front of k_neighbours.h"
-#endif
 
 namespace gsr {
 
@@ -33,7 +28,7 @@ __device__ __forceinline__ uint32_t nb_bucket(unsigned long long k, uint32_t mas
 }
 
 // f(key, bucket) for each of the 27 cells around the cell of key k that lie inside the clamp, while f returns true
-template <class F>
+template <class Sites, class F>
 __device__ __forceinline__ void nb_each_cell(unsigned long long k, uint32_t mask, F f)
 {
     const int32_t cx = (int32_t)((uint32_t)k & 0x1fffffu) - NB_CELL_HALF, cy = (int32_t)((uint32_t)(k >> 21) & 0x1fffffu) - NB_CELL_HALF,
@@ -46,11 +41,36 @@ __device__ __forceinline__ void nb_each_cell(unsigned long long k, uint32_t mask
                 if (x < -NB_CELL_HALF || x >= NB_CELL_HALF) continue;
                 const unsigned long long nk = nb_key(x, y, z);
                 const uint32_t b = nb_bucket(nk, mask);
-                NB_BOUND_BUCKET(b, (uint64_t)mask + 1u);
+                Sites::bound_bucket(b, (uint64_t)mask + 1u);
                 if (!f(nk, b)) return;
             }
         }
     }
+}
+
+// f(j) for every OTHER entry within the radius of entry s (`me`; j: the other's splat index) that passes pre(j), while f returns
+// true.  Per cell the bucket's (population, end) pair and its range of the entry array; the stored cell key is compared BEFORE
+// anything else -- two of the 27 cells that hash to one bucket are walked twice and each pass takes only its own cell's entries --
+// then pre, then the pair test: near(i, j) := i != j && (dx*dx + dy*dy) + dz*dz <= r2 in f64, in the written order, uncontracted.
+// An entry IS a splat, so "i != j" is "another slot".  m: the entries.
+template <class Sites, class P, class F>
+__device__ __forceinline__ void nb_each_near(const NbIndex& ix, uint32_t m, uint32_t s, const uint4& me, P pre, F f)
+{
+    const uint2* __restrict__ table = reinterpret_cast<const uint2*>(ix.table);   // (population, one behind the last entry)
+    const double x = (double)__uint_as_float(me.x), y = (double)__uint_as_float(me.y), z = (double)__uint_as_float(me.z);
+    nb_each_cell<Sites>(ix.key[s], ix.bucket_mask, [&](unsigned long long nk, uint32_t b) {
+        const uint2 t = table[b];
+        Sites::bound_entry(t.y, (uint64_t)m + 1u);
+        if (t.y > m || t.x > t.y) return true;   // (never: a range of the entry array)
+        for (uint32_t e = t.y - t.x; e < t.y; e++) {
+            if (ix.key[e] != nk || e == s) continue;
+            const uint4 o = ix.entry[e];
+            if (!pre(o.w)) continue;
+            const double ex = x - (double)__uint_as_float(o.x), ey = y - (double)__uint_as_float(o.y), ez = z - (double)__uint_as_float(o.z);
+            if ((ex * ex + ey * ey) + ez * ez <= ix.r2 && !f(o.w)) return false;
+        }
+        return true;
+    });
 }
 
 // the grid of a grid-stride kernel over `work` items: NB_WG_PER_CU workgroups per compute unit, NB_MAX_GRID at most

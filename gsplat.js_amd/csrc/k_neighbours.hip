@@ -17,54 +17,34 @@
 // workgroup: the ranges are disjoint and dense but in no particular order across workgroups, which nothing needs -- every
 // result below is a count, independent of where an entry sits -- and it saves the second and third pass of a global scan.
 // Splats out of scope or with a NaN / infinite component are counted (NbInfo) and never indexed; a run of 64 splats out of scope
-// costs its set words and no read of the scene (k_attr.hip's idiom).
+// costs its set words and no read of the scene (in_scope, k_splat_ops.h).
 //
 // Walks.  k_nb_bound and k_nb_count take the ENTRIES in index order, one per lane, so that the lanes of a wave that share a
 // bucket share its 27 neighbours.  For each of the 27 cells (those outside the clamp hold nothing and are skipped) the lane reads
-// the bucket's (population, end) pair; k_nb_bound adds the population, k_nb_count walks the bucket's entries and compares the
-// stored cell key BEFORE any f64 arithmetic -- two of the 27 cells that hash to one bucket are walked twice and counted once
-// each, because each pass takes only its own cell's entries.  The pair test is the header's, in f64, in the written order,
-// uncontracted; a lane stops at `cap`.  Counts go to counts[index] with ordinary stores; the histogram goes through per-workgroup
-// LDS counters and one relaxed agent-scope add per non-zero counter, as k_attr_hist does.
+// the bucket's (population, end) pair; k_nb_bound adds the population, k_nb_count walks the entries near its own (nb_each_near,
+// k_neighbours.h: the stored cell key compared BEFORE any f64 arithmetic, the pair test in f64, in the written order,
+// uncontracted); a lane stops at `cap`.  Counts go to counts[index] with ordinary stores; the histogram goes through per-workgroup
+// LDS counters and one relaxed agent-scope add per non-zero counter (lds_counters_*, k_splat_ops.h).
 //
 // Compiled with -ffp-contract=off like the rest of the device code.
 #include "gsr_internal.h"
 #include "k_splat_ops.h"
+#include "k_neighbours.h"   // the key, the bucket, the 27-cell walk and the near walk, shared with the other units over the index
 
 namespace gsr {
+
 GSR_BOUNDS_DECL(neighbours)   // sites: 0 set word, 1 splat index, 2 bucket, 3 entry slot, 4 LDS counter, 5 global counter, 6 selection word, 7 counts word
-}
-#define NB_BOUND_BUCKET(idx, limit) GSR_BOUND(neighbours, 2, idx, limit)
-#include "k_neighbours.h"   // the key, the bucket and the 27-cell walk, shared with k_clusters.hip
 
-namespace gsr {
-
-// the bits of word wi whose splats are in scope (the rule of k_attr.hip's attr_scope_word: below n, selected, not hidden)
-__device__ __forceinline__ uint32_t nb_scope_word(const AttrScope& sc, uint32_t n, uint32_t wi)
-{
-    uint32_t m = set_live_bits(n, wi);
-    if (!m) return 0u;
-    if (sc.flags & ATTR_SCOPE_SELECTED) {
-        if (!sc.sel) return 0u;
-        GSR_BOUND(neighbours, 0, wi, sc.sel_words);
-        m &= set_word(sc.sel, sc.sel_words, n, wi);
-    }
-    if (m && (sc.flags & ATTR_SCOPE_VISIBLE) && sc.hid) {
-        GSR_BOUND(neighbours, 0, wi, sc.hid_words);
-        m &= ~set_word(sc.hid, sc.hid_words, n, wi);
-    }
-    return m;
-}
-
-__device__ __forceinline__ bool nb_in_scope(const AttrScope& sc, uint32_t n, uint64_t i)
-{
-    if (i >= n) return false;
-    return (nb_scope_word(sc, n, (uint32_t)(i >> 5)) & (1u << ((uint32_t)i & 31u))) != 0u;
-}
+// the sites of the shared helpers (k_splat_ops.h, k_neighbours.h)
+struct nb_sites {
+    static __device__ __forceinline__ void bound_set_word(unsigned long long idx, unsigned long long limit) { GSR_BOUND(neighbours, 0, idx, limit); }
+    static __device__ __forceinline__ void bound_bucket(unsigned long long idx, unsigned long long limit) { GSR_BOUND(neighbours, 2, idx, limit); }
+    static __device__ __forceinline__ void bound_entry(unsigned long long idx, unsigned long long limit) { GSR_BOUND(neighbours, 3, idx, limit); }
+    static __device__ __forceinline__ void bound_counter(unsigned long long idx, unsigned long long limit) { GSR_BOUND(neighbours, 5, idx, limit); }
+    static __device__ __forceinline__ void bound_mask_word(unsigned long long idx, unsigned long long limit) { GSR_BOUND(neighbours, 6, idx, limit); }
+};
 
 // ---- cells ----
-__device__ __forceinline__ bool nb_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
 // floor, not truncation; the clamp in f64, in front of the conversion
 __device__ __forceinline__ int32_t nb_cell(float v, double inv_h)
 {
@@ -81,14 +61,14 @@ template <bool SCATTER>
 __global__ __launch_bounds__(NB_THREADS) void k_nb_cells(const float* __restrict__ px, const float* __restrict__ py, const float* __restrict__ pz, AttrScope sc,
                                                          uint32_t n, NbIndex ix, uint32_t* __restrict__ hist0)
 {
-    uint32_t in_scope = 0u, nonfinite = 0u;
+    uint32_t scoped = 0u, nonfinite = 0u;   // splats in scope; of those, non-finite
     const uint64_t stride = (uint64_t)gridDim.x * NB_THREADS, end = ((uint64_t)n + 63u) & ~63ull;   // whole waves step together
     for (uint64_t i = (uint64_t)blockIdx.x * NB_THREADS + threadIdx.x; i < end; i += stride) {
-        if (!nb_in_scope(sc, n, i)) continue;
+        if (!in_scope<nb_sites>(sc, n, i)) continue;
         GSR_BOUND(neighbours, 1, i, n);
         const float x = px[i], y = py[i], z = pz[i];
-        in_scope++;
-        if (!(nb_finite(x) && nb_finite(y) && nb_finite(z))) { nonfinite++; continue; }
+        scoped++;
+        if (!(f32_finite(x) && f32_finite(y) && f32_finite(z))) { nonfinite++; continue; }
         const unsigned long long k = nb_key(nb_cell(x, ix.inv_h), nb_cell(y, ix.inv_h), nb_cell(z, ix.inv_h));
         const uint32_t b = nb_bucket(k, ix.bucket_mask);
         GSR_BOUND(neighbours, 2, b, (uint64_t)ix.bucket_mask + 1u);
@@ -105,9 +85,9 @@ __global__ __launch_bounds__(NB_THREADS) void k_nb_cells(const float* __restrict
     }
     if (SCATTER) return;
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { in_scope += __shfl_xor(in_scope, d); nonfinite += __shfl_xor(nonfinite, d); }
+    for (int d = 32; d > 0; d >>= 1) { scoped += __shfl_xor(scoped, d); nonfinite += __shfl_xor(nonfinite, d); }
     if ((threadIdx.x & 63u) != 0u) return;
-    if (in_scope) __hip_atomic_fetch_add(&ix.info->in_scope, in_scope, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (scoped) __hip_atomic_fetch_add(&ix.info->in_scope, scoped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (nonfinite) {
         __hip_atomic_fetch_add(&ix.info->nonfinite, nonfinite, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (hist0) __hip_atomic_fetch_add(hist0, nonfinite, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -145,22 +125,14 @@ __global__ __launch_bounds__(NB_THREADS) void k_nb_offsets(NbIndex ix)
 // twice, as the walk visits it twice.  64-bit sums, reduced per workgroup, one atomic per workgroup.
 __global__ __launch_bounds__(NB_THREADS) void k_nb_bound(NbIndex ix, uint32_t n)
 {
-    __shared__ unsigned long long s_part[NB_THREADS / WAVE];
     const uint32_t m = min(ix.info->indexed, n);
     unsigned long long sum = 0ull;
     const uint64_t stride = (uint64_t)gridDim.x * NB_THREADS;
     for (uint64_t s = (uint64_t)blockIdx.x * NB_THREADS + threadIdx.x; s < m; s += stride) {
         GSR_BOUND(neighbours, 3, s, n);
-        nb_each_cell(ix.key[s], ix.bucket_mask, [&](unsigned long long, uint32_t b) { sum += ix.table[2ull * b]; return true; });
+        nb_each_cell<nb_sites>(ix.key[s], ix.bucket_mask, [&](unsigned long long, uint32_t b) { sum += ix.table[2ull * b]; return true; });
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) s_part[wave] = sum;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    for (int w = 1; w < NB_THREADS / WAVE; w++) sum += s_part[w];
-    if (sum) __hip_atomic_fetch_add(&ix.info->pair_bound, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    workgroup_sum_u64<NB_THREADS>(sum, &ix.info->pair_bound);
 }
 
 // ---- the count ----
@@ -170,29 +142,13 @@ __global__ __launch_bounds__(NB_THREADS) void k_nb_count(NbIndex ix, uint32_t m 
                                                          uint32_t* __restrict__ hist)
 {
     extern __shared__ uint32_t s_hist[];   // cap + 1 (HIST)
-    if (HIST) {
-        for (uint32_t k = threadIdx.x; k <= cap; k += NB_THREADS) s_hist[k] = 0u;
-        __syncthreads();
-    }
-    const uint2* __restrict__ table = reinterpret_cast<const uint2*>(ix.table);   // (population, one behind the last entry)
+    if (HIST) lds_counters_zero(s_hist, cap + 1u, NB_THREADS);
     const uint64_t stride = (uint64_t)gridDim.x * NB_THREADS;
     for (uint64_t s = (uint64_t)blockIdx.x * NB_THREADS + threadIdx.x; s < m; s += stride) {
         GSR_BOUND(neighbours, 3, s, m);
         const uint4 me = ix.entry[s];
-        const double x = (double)__uint_as_float(me.x), y = (double)__uint_as_float(me.y), z = (double)__uint_as_float(me.z);
         uint32_t count = 0u;
-        nb_each_cell(ix.key[s], ix.bucket_mask, [&](unsigned long long nk, uint32_t b) {
-            const uint2 t = table[b];
-            GSR_BOUND(neighbours, 3, t.y, (uint64_t)m + 1u);
-            if (t.y > m || t.x > t.y) return true;   // (never: a range of the entry array)
-            for (uint32_t e = t.y - t.x; e < t.y; e++) {
-                if (ix.key[e] != nk || e == (uint32_t)s) continue;
-                const uint4 o = ix.entry[e];
-                const double ex = x - (double)__uint_as_float(o.x), ey = y - (double)__uint_as_float(o.y), ez = z - (double)__uint_as_float(o.z);
-                if ((ex * ex + ey * ey) + ez * ez <= ix.r2 && ++count >= cap) return false;
-            }
-            return true;
-        });
+        nb_each_near<nb_sites>(ix, m, (uint32_t)s, me, [](uint32_t) { return true; }, [&](uint32_t) { return ++count < cap; });
         GSR_BOUND(neighbours, 7, me.w, n);
         if (me.w < n) counts[me.w] = count;
         if (HIST) {
@@ -200,35 +156,23 @@ __global__ __launch_bounds__(NB_THREADS) void k_nb_count(NbIndex ix, uint32_t m 
             __hip_atomic_fetch_add(&s_hist[count < cap ? count : cap], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     }
-    if (!HIST) return;
-    __syncthreads();   // the workgroup's counters are final
-    for (uint32_t k = threadIdx.x; k <= cap; k += NB_THREADS) {
-        const uint32_t c = s_hist[k];
-        if (!c) continue;
-        GSR_BOUND(neighbours, 5, k, NB_MAX_CAP + 1u);
-        __hip_atomic_fetch_add(&hist[k], c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (HIST) lds_counters_flush<nb_sites>(s_hist, cap + 1u, NB_THREADS, hist, NB_MAX_CAP + 1u);
 }
 
 // ---- the picker ----
 // gsr_select_neighbours.  One thread per bit of the mask: in scope, lo <= count && count < hi (a splat in scope that is not
-// indexed has the caller's zero).  A wave's ballot is two whole words (k_attr_select): every word of the mask is stored.
+// indexed has the caller's zero).  A wave's ballot is two whole words (mask_store_ballot): every word of the mask is stored.
 __global__ __launch_bounds__(NB_THREADS) void k_nb_select(const uint32_t* __restrict__ counts, AttrScope sc, uint32_t n, uint32_t lo, uint32_t hi,
                                                           uint32_t* __restrict__ scratch, uint32_t nwords)
 {
     const uint32_t i = blockIdx.x * NB_THREADS + threadIdx.x;
     bool in = false;
-    if (nb_in_scope(sc, n, i)) {
+    if (in_scope<nb_sites>(sc, n, i)) {
         GSR_BOUND(neighbours, 7, i, n);
         const uint32_t c = counts[i];
         in = lo <= c && c < hi;
     }
-    const uint64_t m = __ballot(in);
-    if ((threadIdx.x & 63u) == 0u) {
-        const uint32_t w = i >> 5;   // (i is a multiple of 64: w is even)
-        if (w < nwords) { GSR_BOUND(neighbours, 6, w, nwords); scratch[w] = (uint32_t)m; }
-        if (w + 1u < nwords) { GSR_BOUND(neighbours, 6, w + 1u, nwords); scratch[w + 1u] = (uint32_t)(m >> 32); }
-    }
+    mask_store_ballot<nb_sites>(scratch, nwords, i, __ballot(in));
 }
 
 // ---- launchers ----
@@ -259,9 +203,7 @@ void launch_nb_count(const NbIndex& ix, uint32_t indexed, uint32_t n, uint32_t c
 void launch_nb_select(const uint32_t* counts, const AttrScope& sc, uint32_t n, uint32_t lo, uint32_t hi, uint32_t* scratch, uint32_t nwords, hipStream_t s)
 {
     if (!nwords) return;
-    // one lane per bit of the mask, so that every word is stored
-    const uint32_t blocks = (uint32_t)(((uint64_t)nwords * 32u + NB_THREADS - 1) / NB_THREADS);
-    hipLaunchKernelGGL(k_nb_select, dim3(blocks), dim3(NB_THREADS), 0, s, counts, sc, n, lo, hi, scratch, nwords);
+    hipLaunchKernelGGL(k_nb_select, dim3(mask_blocks(nwords, NB_THREADS)), dim3(NB_THREADS), 0, s, counts, sc, n, lo, hi, scratch, nwords);
 }
 
 }  // namespace gsr

@@ -16,6 +16,11 @@ GSR_BOUNDS_DECL(select)   // sites: 0 bin -> bin_start, 1 list position, 2 splat
                           //        4 plane pixel, 5 selection word
 constexpr int SELECT_THREADS = 256;
 
+// the site of the shared mask store (k_splat_ops.h)
+struct select_sites {
+    static __device__ __forceinline__ void bound_mask_word(unsigned long long idx, unsigned long long limit) { GSR_BOUND(select, 5, idx, limit); }
+};
+
 // the region byte of pixel (x, y) of the rectangle: true without bytes
 __device__ __forceinline__ bool region_has(const SelectRegion& r, int x, int y)
 {
@@ -89,7 +94,7 @@ __global__ __launch_bounds__(SELECT_THREADS) void k_select_hit(SelectBuffers a, 
 }
 
 // gsr_select_box.  in_box of k_scene.hip per splat -- the same f64 comparisons on the same f32 positions as limitBox's
-// compaction.  A wave's 64-bit ballot IS two whole words of the mask: lane 0 stores them, no atomics, and every word of the
+// compaction.  A wave's ballot is two whole words of the mask (mask_store_ballot, k_splat_ops.h): every word of the
 // mask is stored (splats at and above n vote 0), so the caller need not zero it.
 struct SelectBox { double v[6]; };
 __global__ __launch_bounds__(SELECT_THREADS) void k_select_box(uint32_t n, const float* __restrict__ px, const float* __restrict__ py,
@@ -102,12 +107,7 @@ __global__ __launch_bounds__(SELECT_THREADS) void k_select_box(uint32_t n, const
         const double x = px[i], y = py[i], z = pz[i];
         in = x >= box.v[0] && x <= box.v[1] && y >= box.v[2] && y <= box.v[3] && z >= box.v[4] && z <= box.v[5];
     }
-    const uint64_t m = __ballot(in);
-    if ((threadIdx.x & 63u) == 0u) {
-        const uint32_t w = i >> 5;   // (i is a multiple of 64: w is even)
-        if (w < nwords) { GSR_BOUND(select, 5, w, nwords); scratch[w] = (uint32_t)m; }
-        if (w + 1u < nwords) { GSR_BOUND(select, 5, w + 1u, nwords); scratch[w + 1u] = (uint32_t)(m >> 32); }
-    }
+    mask_store_ballot<select_sites>(scratch, nwords, i, __ballot(in));
 }
 
 // sel <- sel (op) scratch word by word, the bits at and above n dropped from the result, and the popcount of the result: one sum
@@ -176,9 +176,7 @@ void launch_select_box(uint32_t n, const float* px, const float* py, const float
     if (!nwords) return;
     SelectBox b;
     for (int k = 0; k < 6; k++) b.v[k] = box[k];
-    // one lane per bit of the mask, so that every word is stored
-    const uint32_t blocks = (uint32_t)(((uint64_t)nwords * 32u + SELECT_THREADS - 1) / SELECT_THREADS);
-    hipLaunchKernelGGL(k_select_box, dim3(blocks), dim3(SELECT_THREADS), 0, s, n, px, py, pz, b, scratch, nwords);
+    hipLaunchKernelGGL(k_select_box, dim3(mask_blocks(nwords, SELECT_THREADS)), dim3(SELECT_THREADS), 0, s, n, px, py, pz, b, scratch, nwords);
 }
 
 void launch_select_apply(int op, uint32_t* sel, const uint32_t* scratch, uint32_t n, uint32_t nwords, uint32_t* block_sums, uint32_t* count, hipStream_t s)

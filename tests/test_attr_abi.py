@@ -71,6 +71,12 @@ def test_hosts_have_the_methods():
         assert name in dts, name
 
 
+def _ops_body(start, end):
+    """k_splat_ops.h between two of its functions' names, comments dropped"""
+    ops = re.sub(r"//.*", "", open(os.path.join(CSRC, "k_splat_ops.h")).read())
+    return ops[ops.index(start):ops.index(end)]
+
+
 def test_sources_are_wired_into_every_build():
     mk = open(os.path.join(CSRC, "Makefile")).read()
     srcs = re.search(r"^SRCS := (.*)$", mk, flags=re.M).group(1).split()
@@ -84,8 +90,12 @@ def test_sources_are_wired_into_every_build():
         assert re.search(r"GSR_BOUND\(attr, %d," % site, src), site
     code = re.sub(r"//.*", "", src)
     assert "asm" not in code                                            # vector stores and HIP atomics only
-    for word in ("__hip_atomic_fetch_add", "__HIP_MEMORY_SCOPE_AGENT", "__HIP_MEMORY_SCOPE_WORKGROUP", "__ATOMIC_RELAXED", "__ballot", "set_word(", "extern __shared__"):
+    for word in ("__hip_atomic_fetch_add", "lds_counters_flush<attr_sites>(", "__HIP_MEMORY_SCOPE_WORKGROUP", "__ATOMIC_RELAXED", "__ballot", "in_scope<attr_sites>(",
+                 "extern __shared__"):
         assert word in code, word
+    # the scope reads the sets through set_word and the flush is agent-scope atomics: k_splat_ops.h, for every unit
+    assert "set_word(" in _ops_body("uint32_t scope_word(", "bool in_scope(")
+    assert "__HIP_MEMORY_SCOPE_AGENT" in _ops_body("void lds_counters_flush(", "void workgroup_sum_u64(")
     assert "atomicAdd(" not in code and not re.search(r"atomic\w*\([^;]*(float|double)", code)    # integer atomics only; min / max go through partials
 
 

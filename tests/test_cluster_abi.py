@@ -94,9 +94,9 @@ def test_sources_are_wired_into_every_build():
     # the key, the bucket and the 27-cell walk are stated once, for both users
     for f in ("k_clusters.hip", "k_neighbours.hip"):
         assert '#include "k_neighbours.h"' in files[f], f
-        for helper in ("nb_key(", "nb_bucket(", "nb_each_cell("):
+        for helper in ("nb_key(", "nb_bucket(", "nb_each_cell(", "nb_each_near("):
             assert not re.search(r"__device__[^;{]*\b" + re.escape(helper), files[f]), (f, helper)
-    for helper in ("nb_key(", "nb_bucket(", "nb_each_cell("):
+    for helper in ("nb_key(", "nb_bucket(", "nb_each_cell(", "nb_each_near("):
         assert re.search(r"__device__[^;{]*\b" + re.escape(helper), files["k_neighbours.h"]), helper
     src = files["k_clusters.hip"]
     assert "GSR_BOUNDS_DECL(clusters)" in src
@@ -105,8 +105,10 @@ def test_sources_are_wired_into_every_build():
     code = re.sub(r"//.*", "", src)
     assert "asm" not in code                                              # ordinary vector stores and HIP atomics only
     for word in ("atomicCAS(&parent[big], big, small)", "__hip_atomic_load", "__hip_atomic_fetch_max", "__hip_atomic_fetch_add", "__HIP_MEMORY_SCOPE_AGENT",
-                 "__ATOMIC_RELAXED", "__ballot", "nb_each_cell(", "cl_fault("):
+                 "__ATOMIC_RELAXED", "__ballot", "nb_each_near<cl_sites>(", "cl_fault("):
         assert word in code, word
+    near = re.sub(r"//.*", "", files["k_neighbours.h"])
+    assert "nb_each_cell<Sites>(" in near[near.index("void nb_each_near("):]     # the near walk is the 27-cell walk
     assert code.count("atomicCAS(") == 1                                  # a hook is ONE compare-and-swap
     assert not re.search(r"while\s*\(\s*(true|1)\s*\)", code) and "__builtin_amdgcn_s_sleep" not in code     # no lane waits for another
     assert not re.search(r"atomic\w*\([^;]*(float|double)", code)         # integer atomics only

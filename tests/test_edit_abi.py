@@ -140,6 +140,42 @@ def test_the_transform_arithmetic_exists_once():
     assert re.search(r"^\$\(OUT\)/gsr_%\.o: gsr_%\.cpp .*k_splat_ops\.h", mk, flags=re.M), "the host rule does not depend on the shared header"
 
 
+def test_the_analysis_helpers_exist_once():
+    """The scope of an analysis call, a picker's mask store, the workgroup reductions, the near walk and the host's scope are each
+    defined in one file of csrc/, the copies they replaced are defined nowhere, and a unit names its bounds sites through a struct
+    of its own instead of a define in front of an include."""
+    for fn in ("scope_word", "in_scope", "mask_store_ballot", "lds_counters_zero", "lds_counters_flush", "workgroup_sum_u64", "f32_finite", "f64_nan", "f64_inf"):
+        assert _csrc_files_with(r"__device__[^;{]*\b%s\(" % fn) == ["k_splat_ops.h"], fn
+    assert _csrc_files_with(r"\buint32_t mask_blocks\(uint32_t nwords, uint32_t threads\)\s*\{") == ["k_splat_ops.h"]
+    assert _csrc_files_with(r"__device__[^;{]*\bnb_each_near\(") == ["k_neighbours.h"]
+    assert _csrc_files_with(r"(?m)^int gsr::scope_check\(") == ["gsr_attr.cpp"]
+    assert _csrc_files_with(r"\bAttrScope scene_scope\([^;{)]*\)\s*\{") == ["gsr_ctx.h"]
+    for old in ("attr_scope_word", "nb_scope_word", "knn_scope_word", "cl_scope_word", "mg_scope_word", "nb_in_scope", "knn_in_scope", "attr_in_scope",
+                "cl_store_ballot", "mg_store_ballot", "cl_each_near", "nb_finite", "mg_finite", "knn_nan", "knn_inf", "attr_nan", "cl_mask_blocks"):
+        assert _csrc_files_with(r"\b%s\b" % old) == [], old
+    # the store of a ballot's two words, the scope's flag test and the scope's assembly on the host are spelled out once each
+    assert _csrc_files_with(re.escape("[w + 1u] = (uint32_t)(m >> 32)")) == ["k_splat_ops.h"]
+    assert _csrc_files_with(re.escape("sc.flags & ATTR_SCOPE_SELECTED")) == ["k_splat_ops.h"]
+    assert _csrc_files_with(re.escape("* 32u + ")) == ["k_splat_ops.h"]                          # "one lane per bit of the mask"
+    assert _csrc_files_with(re.escape("sel.mask, sc.sel.words, sc.hid.mask, sc.hid.words}")) == ["gsr_ctx.h"]
+    assert _csrc_files_with(re.escape("unknown scope flags")) == ["gsr_attr.cpp"]
+    # every picker stores its mask through the one helper, launched with the one grid
+    for f, stores in (("k_attr.hip", 1), ("k_neighbours.hip", 1), ("k_knn.hip", 1), ("k_clusters.hip", 2), ("k_merge.hip", 3), ("k_contrib.hip", 1), ("k_select.hip", 1)):
+        text = open(os.path.join(CSRC, f)).read()
+        assert '#include "k_splat_ops.h"' in text, f
+        assert len(re.findall(r"\bmask_store_ballot<\w+>\(", text)) == stores, f
+        assert text.count("dim3(mask_blocks(") == (2 if f in ("k_clusters.hip", "k_merge.hip") else 1), f
+    for f in ("k_attr.hip", "k_neighbours.hip", "k_knn.hip", "k_merge.hip"):                     # the four LDS histograms
+        text = open(os.path.join(CSRC, f)).read()
+        assert "lds_counters_zero(s_hist, " in text and re.search(r"lds_counters_flush<\w+_sites>\(s_hist, ", text), f
+    # no site is named by a define in front of an include: k_neighbours.h is an ordinary header
+    assert _csrc_files_with(r"NB_BOUND_BUCKET") == []
+    assert "#error" not in open(os.path.join(CSRC, "k_neighbours.h")).read()
+    for f in ("k_neighbours.hip", "k_knn.hip", "k_clusters.hip", "k_merge.hip"):
+        text = open(os.path.join(CSRC, f)).read()
+        assert text.index('#include "k_neighbours.h"') < text.index("GSR_BOUNDS_DECL("), f
+
+
 def test_the_splat_set_is_sized_and_allocated_once():
     """the sizes of a one-bit-per-splat set are defined in one file, and neither set allocates for itself"""
     for fn in ("words_of", "fold_words", "counter_words", "op_ok"):

@@ -494,3 +494,52 @@ def test_bounds_twin(gh, monkeypatch, scenes, proj):
     assert band.tolist() == [int(want[:100].sum()) - 1, int(want[:401].sum()) - 1, int(want[:701].sum()) - 1]
     _bounds_zero(r, "box and SH")
     r.dispose()
+
+
+# 14 ------------------------------------------------------------------------------------------------------------------
+# The contract every picker's kernel shares (mask_store_ballot, k_splat_ops.h): EVERY word of the scratch mask is written, so no
+# picker zeroes it first.  n = 33: one wave, the second word partial; 65: the second wave stores one word and must not store a
+# second; 257: a second workgroup.  Each picker first takes everything -- behind the previous picker's empty mask, so every word
+# must have been written with its bits -- then nothing, behind its own full mask, so every word must have been written with zeros.
+# (The two masks k_merge.hip stores the same way are test_gpu_merge.py's, on both builds.)
+EVERY = (-1e9, 1e9, -1e9, 1e9, -1e9, 1e9)
+FAR = (1e8, 1e9, 1e8, 1e9, 1e8, 1e9)
+LINK = 32.0                                       # synth positions lie in [-6, 6]^3: every splat is within LINK of every other
+
+
+def _pickers(r):
+    """(name, take everything, take nothing): each returns the selected count of a REPLACE"""
+    return [("gsr_select_attr", lambda: r.select_attr("x"), lambda: r.select_attr("x", lo=0.0, hi=0.0)),
+            ("gsr_select_neighbours", lambda: r.select_neighbours(LINK)[0], lambda: r.select_neighbours(LINK, lo=0, hi=0)[0]),
+            ("gsr_select_knn", lambda: r.select_knn(LINK)[0], lambda: r.select_knn(LINK, lo=0.0, hi=0.0)[0]),
+            ("gsr_select_clusters", lambda: r.select_clusters(LINK)[0], lambda: r.select_clusters(LINK, lo=0, hi=0)[0]),
+            # one island at LINK; at a radius nobody has a neighbour within and min_pts = 1 the seed is noise: the empty set
+            ("gsr_select_cluster_at", lambda: r.select_cluster_at(LINK, "largest")[0], lambda: r.select_cluster_at(1e-6, 0, min_pts=1)[0]),
+            ("gsr_select_contrib", lambda: r.select_contrib("pixels", below=np.inf), lambda: r.select_contrib("pixels", below=0.0)),
+            ("gsr_select_box", lambda: r.select_box(EVERY), lambda: r.select_box(FAR))]
+
+
+@pytest.mark.parametrize("build", ["shipped", "bounds twin"])
+@pytest.mark.parametrize("n", [33, 65, 257])
+def test_every_picker_stores_every_word(gh, monkeypatch, scenes, n, build):
+    if build != "shipped":
+        assert os.path.exists(BOUNDS_LIB), "the bounds-checked build is missing: run python -c 'import __graft_entry__ as g; g.build()'"
+    r = _context(gh, monkeypatch, scenes, name=n, seed=7, **({} if build == "shipped" else {"lib_path": BOUNDS_LIB}))
+    assert r.scene_count() == n
+    _frame(gh, r, POSES[0])                       # the contribution picker needs a pass
+    r.contrib_reset()
+    r.contrib_accumulate()
+    r.sync()
+    everything, nothing = np.ones(n, bool), np.zeros(n, bool)
+    for name, take_all, take_none in _pickers(r):
+        assert take_all() == n, (n, name)
+        _is(r, everything, (n, name, "everything"))
+        assert take_none() == 0, (n, name)
+        _is(r, nothing, (n, name, "nothing"))
+        assert not r.selection_words().any(), (n, name)
+    if build != "shipped":
+        for unit in ("attr", "neighbours", "knn", "clusters", "contrib", "select"):
+            buf = (ctypes.c_uint32 * 8)()
+            assert getattr(r._L, "gsr_debug_bounds_" + unit)(buf) == 0
+            assert not any(buf), (n, unit, list(buf))
+    r.dispose()

@@ -89,7 +89,7 @@ def test_sources_are_wired_into_every_build():
         assert re.search(r"GSR_BOUND\(knn, %d," % site, src), site
     code = re.sub(r"//.*", "", src)
     assert "asm" not in code                                              # plain HIP: ordinary vector stores and HIP atomics only
-    for word in ("nb_each_cell(", "nb_grid(", "__hip_atomic_fetch_add", "__hip_atomic_fetch_max", "__HIP_MEMORY_SCOPE_AGENT", "__HIP_MEMORY_SCOPE_WORKGROUP", "__ATOMIC_RELAXED",
+    for word in ("nb_each_cell<knn_sites>(", "nb_grid(", "__hip_atomic_fetch_add", "__hip_atomic_fetch_max", "__HIP_MEMORY_SCOPE_AGENT", "__HIP_MEMORY_SCOPE_WORKGROUP", "__ATOMIC_RELAXED",
                  "__ballot", "__shfl_xor", "extern __shared__", "__dsqrt_rn(", "!(d <= ix.r2)"):
         assert word in code, word
     assert "atomicAdd(" not in code and not re.search(r"atomic\w*\([^;]*(float|double)\b\*", code)       # integer atomics only

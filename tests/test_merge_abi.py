@@ -100,8 +100,9 @@ def test_sources_are_wired_into_every_build():
     assert cov.count("M[0] * M[0] + M[3] * M[3] + M[6] * M[6]") == 1 and "splat_cov(rot, scl, s);" in cov      # the six sums stated once, pack_cov on top of them
     host = open(os.path.join(CSRC, "gsr_merge.cpp")).read()
     for word in ("settle_members(c)", "require_rows(c)", "select_ensure(c)", "select_fold_and_count(c, SELOP_REPLACE, nullptr)", "scene_compact(c, ScenePred{nullptr, a.remove, 0u, a.words}",
-                 "nb_prepare(c, who, cap, 1.0 / cell", "launch_nb_build(", "GSR_NEIGHBOUR_DEFAULT_BUDGET", "GSR_NEIGHBOUR_MAX_BUDGET", "sc.sh_count"):
+                 "nb_prepare(c, who, cap, 1.0 / cell", "launch_nb_build(", "GSR_NEIGHBOUR_DEFAULT_BUDGET", "scope_check(c, who, scope, budget)", "sc.sh_count"):
         assert word in host, word
+    assert "GSR_NEIGHBOUR_MAX_BUDGET" in open(os.path.join(CSRC, "gsr_attr.cpp")).read()           # scope_check's refusal, shared with gsr_neighbours.cpp
     scene = open(os.path.join(CSRC, "gsr_scene.cpp")).read()
     assert "also->in, also->nwords_in, also->out, also->nwords_out" in scene      # the merged rows ride the compaction the hidden set rides
 

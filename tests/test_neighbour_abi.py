@@ -83,14 +83,17 @@ def test_sources_are_wired_into_every_build():
         assert re.search(r"GSR_BOUND\(neighbours, %d," % site, src), site
     code = re.sub(r"//.*", "", src)
     assert "asm" not in code                                              # ordinary vector stores and HIP atomics only
-    for word in ("__hip_atomic_fetch_add", "__HIP_MEMORY_SCOPE_AGENT", "__HIP_MEMORY_SCOPE_WORKGROUP", "__ATOMIC_RELAXED", "__ballot", "set_word(", "extern __shared__",
+    for word in ("__hip_atomic_fetch_add", "__HIP_MEMORY_SCOPE_AGENT", "__HIP_MEMORY_SCOPE_WORKGROUP", "__ATOMIC_RELAXED", "__ballot", "in_scope<nb_sites>(", "extern __shared__",
                  "floor("):
         assert word in code, word
+    ops = re.sub(r"//.*", "", open(os.path.join(CSRC, "k_splat_ops.h")).read())
+    assert "set_word(" in ops[ops.index("uint32_t scope_word("):ops.index("bool in_scope(")]       # the scope reads the sets through set_word, for every unit
     assert "atomicAdd(" not in code and not re.search(r"atomic\w*\([^;]*(float|double)", code)      # integer atomics only
     assert "trunc" not in code                                            # floor, not truncation
     host = open(os.path.join(CSRC, "gsr_neighbours.cpp")).read()
-    for word in ("settle_members(c)", "select_ensure(c)", "select_fold_and_count(c, op, selected)", "GSR_NEIGHBOUR_DEFAULT_BUDGET", "GSR_NEIGHBOUR_MAX_BUDGET"):
+    for word in ("settle_members(c)", "select_ensure(c)", "select_fold_and_count(c, op, selected)", "GSR_NEIGHBOUR_DEFAULT_BUDGET", "scope_check(c, who, scope, budget)"):
         assert word in host, word
+    assert "GSR_NEIGHBOUR_MAX_BUDGET" in open(os.path.join(CSRC, "gsr_attr.cpp")).read()           # scope_check's refusal, shared with gsr_merge.cpp
 
 
 def test_library_holds_the_kernels():
