@@ -14,7 +14,16 @@ the walks over KINDS keep their exact content (tests/test_history_trace.py pins 
 EDIT_REFUSALS, the new fixed trace editing_tour(), the new pairs EDIT_RISKY_PAIRS, and walk(..., kinds=KINDS + EDIT_KINDS).
 HIT-mode region selection stays out of the traces: its result is defined by the device's own index plane, so it has no pure fold;
 tests/test_gpu_select.py covers it.  gsr_select_contrib is folded at the two thresholds whose set needs no frame (below = +inf:
-every splat, below = 0: none); the accumulators themselves are compared through read_contrib()."""
+every splat, below = 0: none); the accumulators themselves are compared through read_contrib().
+
+The analysis layer -- neighbour counts, clusters, k nearest neighbours, merge cells -- joins the same way: its pickers and the merge
+are entries of State.edits, evaluated by neighbour_reference, cluster_reference, knn_reference and merge_reference under scope masks
+computed from the recipe's own selection and hidden set; its read-only calls are ("report", ...) operations that fold to the same
+State.  ANALYSIS_KINDS, ANALYSIS_REFUSALS, analysis_tour(), ANALYSIS_RISKY_PAIRS and walk(..., kinds=KINDS + EDIT_KINDS +
+ANALYSIS_KINDS) are new; editing_tour() and the walks over KINDS + EDIT_KINDS keep their exact content (a second digest pins them).
+The fresh context is still uploaded from CPU-evaluated arrays and never ran an analysis kernel before its own observables: the
+feature suites pin every one of these calls to its reference exactly.  No threshold is computed from device values inside a trace:
+the statistical outlier filter is select_knn with a constant lower end, followed by erase."""
 import os
 import random
 from collections import namedtuple
@@ -74,6 +83,36 @@ EDIT_KEEPS_FRAME = SELECT_KINDS + ("contrib_pass", "overlay")
 # render again, so the traces reset the accumulators in front of them (walk() does it itself)
 MOVES_GEOMETRY = ("rotate", "translate", "scale", "edit")
 MAX_GROWN = 40000                     # no trace grows a scene beyond this
+
+# The analysis layer: neighbour counts, clusters, k nearest neighbours and merge cells (KINDS, EDIT_KINDS and the traces over them stay).
+# The four pickers join State.edits like select_attr and keep the frame; merge_cells is an edit that removes rows from the inside;
+# ("report", which, ...) are the read-only calls gsr_neighbours / gsr_clusters / gsr_knn / gsr_cells.  Operations:
+#   ("select_neighbours", radius, lo, hi, cap, scope, op)          ("select_clusters", radius, lo, hi, min_pts, scope, op)
+#   ("select_cluster_at", radius, seed, min_pts, scope, op)        ("select_knn", radius, k, stat, lo, hi, scope, op)
+#   ("merge_cells", cell, scope)
+#   ("report", "neighbours", radius, cap, scope) | ("report", "clusters", radius, min_pts, scope) | ("report", "knn", radius, k, stat, scope)
+#       | ("report", "cells", cell, cap, scope)
+# scope: a tuple of "selected" / "visible"; hi None: no upper end; seed: an index or "largest".
+ANALYSIS_PICKERS = ("select_neighbours", "select_clusters", "select_cluster_at", "select_knn")
+ANALYSIS_KINDS = ANALYSIS_PICKERS + ("merge_cells", "report")
+REPORTS = ("neighbours", "clusters", "knn", "cells")
+SCOPES = ((), ("selected",), ("visible",), ("selected", "visible"))
+ANALYSIS_KEEPS_FRAME = ANALYSIS_PICKERS + ("report",)
+# refused calls of the analysis layer, and a piece of the message each must carry (the library's texts: gsr_merge.cpp, gsr_neighbours.cpp,
+# gsr_scene.cpp).  budget_of_one is the first picker, gsr_select_neighbours, with a budget of 1: refused before any walk, selection untouched.
+ANALYSIS_REFUSAL_TEXTS = {
+    "merge_raw": "need a scene built with gsr_set_scene_rows or gsr_set_scene_arrays",
+    "merge_with_sh": "SH rows: the SH colour of a mixture is not defined",
+    "budget_of_one": "above the budget of 1 (radius",
+    "cell_not_finite": "gsr_scene_merge_cells: cell (inf) must be finite and > 0",
+    "cell_not_positive": "gsr_cells: cell (0) must be finite and > 0",
+    "radius_not_finite": "gsr_select_knn: radius (nan) must be finite and > 0",
+    "radius_not_positive": "gsr_select_clusters: radius (-0.25) must be finite and > 0",
+    "cap_out_of_range": "gsr_select_neighbours: cap (4096) must be in 1 .. 4095",
+    "k_out_of_range": "gsr_knn: k (33) must be in 1 .. 32",
+}
+ANALYSIS_REFUSALS = tuple(ANALYSIS_REFUSAL_TEXTS)
+MAX_ANALYSED = 8192                   # the references are blocked brute force: no trace holds an analysis operation on a larger scene
 
 # Ordered pairs of neighbours the tour must visit (tags as `tags` gives them), and why each is risky.
 RISKY_PAIRS = (
@@ -151,6 +190,56 @@ EDIT_RISKY_PAIRS = (
     ("contrib_pass", "scene", "and so does a new scene"),
 ) + tuple(("refused:" + w, "camera", "a refused call of the editing layer must have changed nothing the next frame reads") for w in EDIT_REFUSALS)
 
+# The same for the analysis layer (analysis_tour visits them).  Tags: "merge" for merge_cells, "select" and the kind for every picker,
+# "report" and "report:<which>" for the read-only calls.  All four features share one neighbour scratch and one hashed index per context
+# (nb_prepare / launch_nb_build, gsr_neighbours.cpp), rebuilt by each call with its own cell side; the merge's own scratch is sized by
+# mg.rows and mg.edit_rows (mg_ensure, gsr_merge.cpp).
+ANALYSIS_RISKY_PAIRS = (
+    # merge in front of a later frame, buffer or edit
+    ("merge", "same_pose", "rows were rewritten in place and compacted: the graph captured over the old count must not be replayed"),
+    ("merge", "sort_only", "the sorted order of the frame before numbers rows that are gone"),
+    ("merge", "burst", "three frames in flight over per-splat buffers whose tail is the old scene's"),
+    ("merge", "band:on", "a band frame behind the merge must not read a rectangle or a survivor slot of the old numbering"),
+    ("band:on", "merge", "survivor slots of the band frame before belong to rows the merge removes"),
+    ("merge", "resize", "a new bin grid over a scene whose count just moved"),
+    ("overflow_async", "merge", "dropped frames and a sticky device counter, then the rows move under the regrown lists"),
+    ("burst", "merge", "the merge waits for three frames in flight before it writes their rows in place"),
+    ("merge", "readback:records", "k_project_key runs a second time over the merged rows and the live rec / rect buffers"),
+    ("merge", "erase", "a second compaction over the first one's stale tail, the selection being exactly the merged rows"),
+    # merge and the hidden set, in both scopes
+    ("hide:on", "merge", "the compaction carries H to the new numbering; under scope visible a hidden member stays out of its cell"),
+    ("merge", "hide:off", "the null pointer returns behind a carried set"),
+    # merge and capacity above n
+    ("duplicate:grow", "merge", "the arrays are new and the copies sit exactly on their originals: every copy merges with its original"),
+    ("duplicate:fit", "merge", "the merge reads n rows of arrays that hold capacity rows"),
+    ("reserve", "merge", "capacity above n: the rows behind n are stale, and the scratch is sized by n"),
+    ("merge", "duplicate", "the copies land on rows the merge's compaction left stale"),
+    ("append_arrays", "merge", "the merge of a scene whose tail was uploaded, not built"),
+    # merge and the layers that follow the selection
+    ("contrib_pass", "merge", "the accumulators are dropped as a removing erase drops them: never reset again"),
+    ("overlay:on", "merge", "the selection becomes the merged rows: the overlay tints exactly those"),
+    ("ring_overlay", "merge", "the ring delivers the overlay of a selection the merge replaces ..."),
+    ("merge", "deliver", "... and the first delivery behind it shows the merged rows"),
+    # merge and the scratch sizing paths
+    ("merge", "merge", "a larger cell over the rows the first merge wrote: scratch, index and carried masks of the larger count stay behind"),
+    ("scene:grow", "merge", "mg.rows < n and mg.edit_rows < n: both shares of the scratch are allocated anew"),
+    ("scene:shrink", "merge", "scratch larger than the scene: masks and tables of the old count behind the words in use"),
+    ("report:cells", "merge", "the report grew its own share of the scratch only: the edit's share is behind (mg.edit_rows < n)"),
+    # different features back to back over the one index and scratch, a different radius each time
+    ("select_neighbours", "select_knn", "the index of the call before has another cell side"),
+    ("select_knn", "select_clusters", "... and another"),
+    ("select_clusters", "merge", "the merge indexes cells of its own side over the clusters' table"),
+    ("merge", "select_neighbours", "the index of the merge holds the old numbering's entries"),
+    # a picker behind a change of positions, numbering or hidden set
+    ("edit", "select_neighbours", "the selected splats moved: an index kept from before would count the old places"),
+    ("translate", "select_knn", "every position changed"),
+    ("limit_box", "select_clusters", "the compaction renumbered the splats: labels are indices"),
+    ("erase", "select_cluster_at", "the seed is an index of the new numbering"),
+    ("hide:on", "select_neighbours", "under scope visible the hidden splats are no neighbours"),
+) + tuple(("report:" + w, "same_pose", "a report disturbs no frame: the next one is a graph replay") for w in REPORTS) + tuple(
+    ("report:" + w, "readback:bin_lists", "... and the last frame's lists are still there to be read") for w in REPORTS) + tuple(
+    ("refused:" + w, "camera", "a refused call of the analysis layer must have changed nothing the next frame reads") for w in ANALYSIS_REFUSALS)
+
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # State arithmetic (pure)
@@ -216,8 +305,13 @@ def fold(state, op):
         return replace(state, contrib=())
     if kind == "contrib_pass":     # (without a prior reset the first pass resets first)
         return replace(state, contrib=(state.contrib or ()) + (frame_of(state) + (len(state.edits),),))
-    assert kind in KINDS or kind == "reserve", op
-    return state      # same_pose, sort_only, readback, depth_async, timing_interval, overflow_sync, deliver, refused, reserve
+    # -- the analysis layer
+    if kind in ANALYSIS_PICKERS:
+        return replace(state, edits=state.edits + (op,))
+    if kind == "merge_cells":      # (a merge that merges something drops the SH state and the accumulators, as a removing erase does; the traces' merges all merge)
+        return replace(state, edits=state.edits + (op,), sh=None, contrib=None)
+    assert kind in KINDS or kind in ("reserve", "report"), op
+    return state      # same_pose, sort_only, readback, depth_async, timing_interval, overflow_sync, deliver, refused, reserve, report
 
 
 def overlay_ring_refuses(state):
@@ -279,6 +373,12 @@ def tags(op, before):
             out.add("duplicate:" + a[0])
     elif kind == "overlay":
         out.add("overlay:off" if a[0] is None else "overlay:on")
+    elif kind in ANALYSIS_PICKERS:
+        out.add("select")
+    elif kind == "merge_cells":
+        out.add("merge")
+    elif kind == "report":
+        out.add("report:" + a[0])
     return out
 
 
@@ -292,7 +392,7 @@ def pairs_in(state, trace):
         for p in (prev, through):
             if p is not None:
                 seen.update((x, y) for x in p for y in t)
-        through = (through or prev) if (st.op[0] in SELECT_KINDS and not st.check) else None
+        through = (through or prev) if (st.op[0] in SELECT_KINDS + ANALYSIS_PICKERS and not st.check) else None
         prev, state = t, fold(state, st.op)
     return seen
 
@@ -388,7 +488,52 @@ def picked_by(oracle, st, S, H, e):
     if kind == "select_contrib":     # value < below over all splats: everything at +inf, nothing at 0 (values are >= 0)
         assert e[2] in (np.inf, 0.0), e
         return np.full(st.n, e[2] == np.inf)
+    if kind in ANALYSIS_PICKERS:
+        return analysis_pick(st, scope_mask(e[-2], S, H), e)
     raise AssertionError(e)
+
+
+def _analysis_refs():
+    import cluster_reference, knn_reference, merge_reference, neighbour_reference
+    return neighbour_reference, cluster_reference, knn_reference, merge_reference
+
+
+def scope_mask(scope, S, H):
+    """bool[n]: the splats in scope -- "selected": S, "visible": not H, both: the intersection, (): every splat"""
+    assert set(scope) <= {"selected", "visible"}, scope
+    m = np.ones(S.size, dtype=bool)
+    if "selected" in scope:
+        m &= S
+    if "visible" in scope:
+        m &= ~H
+    return m
+
+
+def analysis_pick(st, mask, e):
+    """bool[n]: what one of ANALYSIS_PICKERS picks from the scene `st` under the scope mask, by the feature suites' specifications"""
+    nr, cr, kr, _ = _analysis_refs()
+    kind, pos = e[0], st.positions[:3 * st.n]
+    if kind == "select_neighbours":
+        radius, lo, hi, cap = e[1:5]
+        return nr.select(nr.counts(pos, radius, cap, mask), lo, cap + 1 if hi is None else hi, mask)
+    if kind == "select_clusters":
+        radius, lo, hi, min_pts = e[1:5]
+        return cr.select(cr.Clusters(pos, radius, min_pts, mask).sizes, lo, 0xffffffff if hi is None else hi, mask)
+    if kind == "select_cluster_at":
+        radius, seed, min_pts = e[1:4]
+        c = cr.Clusters(pos, radius, min_pts, mask)
+        return cr.select_at(c.labels, cr.LARGEST if seed == "largest" else seed, c.info["largest_label"])
+    if kind == "select_knn":
+        radius, k, stat, lo, hi = e[1:6]
+        found, _, d2 = kr.lists(pos, radius, k, mask)
+        return kr.select(kr.values(found, d2, k, stat, mask), lo, np.inf if hi is None else hi, mask)
+    raise AssertionError(e)
+
+
+def merge_of(st, S, H, e):
+    """merge_reference.merge of a ("merge_cells", cell, scope) entry on the scene `st`: the dict of the scene that is left"""
+    n = st.n
+    return _analysis_refs()[3].merge(st.data[:8 * n], st.positions[:3 * n], st.rotations[:4 * n], st.scales[:3 * n], e[1], scope_mask(e[2], S, H), H)
 
 
 def _apply_edit(oracle, st, S, H, e):
@@ -397,8 +542,16 @@ def _apply_edit(oracle, st, S, H, e):
     kind = e[0]
     if kind == "invert_selection":
         return ~S, H
-    if kind in SELECT_KINDS:
+    if kind in SELECT_KINDS or kind in ANALYSIS_PICKERS:
         return sr.apply_op(S, picked_by(oracle, st, S, H, e), e[-2] if kind == "select_region" else e[-1]), H
+    if kind == "merge_cells":
+        out = merge_of(st, S, H, e)
+        if not out["info"]["merged_cells"]:      # nothing to merge: nothing changes, the selection included
+            return S, H
+        for name in ("data", "positions", "rotations", "scales"):
+            setattr(st, name, np.ascontiguousarray(out[name]).reshape(-1))
+        st.n = int(out["keep"].sum())
+        return out["merged"].copy(), out["hidden"].copy()       # the selection becomes exactly the merged rows; H is carried
     if kind == "hide":
         return S, hr.hide_selected(H, S, e[1])
     if kind == "set_hidden":
@@ -465,8 +618,9 @@ def _evaluate(state, oracle):
 
 def materialise(state, oracle):
     """The scene, the selection and the hidden set the State's recipe leaves, evaluated on the CPU only: oracle.SceneState(rows),
-    state.transforms with the oracle, state.edits with edit_reference, append_reference, hide_reference, select_reference and
-    attr_reference.  Arrays hold exactly n rows."""
+    state.transforms with the oracle, state.edits with edit_reference, append_reference, hide_reference, select_reference,
+    attr_reference and, for the analysis layer, neighbour_reference, cluster_reference, knn_reference and merge_reference (a merge
+    hands over the merged arrays, the merged rows as the selection and the carried hidden set).  Arrays hold exactly n rows."""
     st, S, H = _evaluate(state, oracle)
     sr = _refs()[3]
     return Materialised(st.data[:8 * st.n].copy(), st.positions[:3 * st.n].copy(), st.rotations[:4 * st.n].copy(),
@@ -476,8 +630,11 @@ def materialise(state, oracle):
 def vacuous(state, op, oracle):
     """Why `op`, performed from `state`, would check nothing (None: it checks something).  The conditions of the issue: a hide hides
     a listed splat and leaves one listed; a region or box selection picks more than none and fewer than all listed; an erase removes
-    more than 0 and fewer than n; a contribution pass lists a selected and an unselected splat; nothing grows beyond MAX_GROWN."""
+    more than 0 and fewer than n; a contribution pass lists a selected and an unselected splat; nothing grows beyond MAX_GROWN.
+    ANALYSIS_KINDS: _vacuous_analysis."""
     kind = op[0]
+    if kind in ANALYSIS_KINDS:
+        return _vacuous_analysis(state, op, oracle)
     if kind not in ("hide", "set_hidden", "select_box", "select_region", "erase", "contrib_pass", "duplicate", "append_arrays", "edit"):
         return None
     st, S, H = _evaluate(state, oracle)
@@ -509,6 +666,56 @@ def vacuous(state, op, oracle):
     if kind == "duplicate" and not S.any():
         return "nothing selected"
     return None if grown <= MAX_GROWN else "grows to %d" % grown
+
+
+def _vacuous_analysis(state, op, oracle):
+    """`vacuous` for ANALYSIS_KINDS.  A picker with "replace" picks a listed splat and leaves a listed one unpicked; an index seed of
+    select_cluster_at is in scope and not noise; a merge merges a cell with a listed member, leaves a candidate unmerged and
+    2 <= rows_after < n, and under scope "visible" a hidden splat sits in a cell that would merge without that scope; a merge and the
+    cells report need a scene built from rows, a merge one without SH; nothing is analysed above MAX_ANALYSED splats."""
+    kind = op[0]
+    st, S, H = _evaluate(state, oracle)
+    if st.n > MAX_ANALYSED:
+        return "too large for the CPU fold"
+    needs_rows = kind == "merge_cells" or (kind == "report" and op[1] == "cells")
+    if needs_rows and st.n and scene_form(state.scene) != "rows":
+        return "needs a scene built from rows"
+    if kind == "report":
+        return None
+    nr, cr, kr, mr = _analysis_refs()
+    n = st.n
+    L = listed_in(oracle, st.data[:8 * n], frame_of(state), H) if n else np.zeros(0, dtype=bool)
+    if kind in ANALYSIS_PICKERS:
+        mask = scope_mask(op[-2], S, H)
+        if kind == "select_cluster_at" and op[2] != "largest":
+            if not (0 <= op[2] < n and mask[op[2]]):
+                return "the seed is out of scope"
+            if int(cr.Clusters(st.positions[:3 * n], op[1], op[3], mask).labels[op[2]]) == cr.NONE:
+                return "the seed is noise"
+        if op[-1] != "replace":
+            return None
+        P = analysis_pick(st, mask, op)
+        if not (L & P).any():
+            return "picks no listed splat"
+        return None if (L & ~P).any() else "picks every listed splat"
+    if state.sh is not None:
+        return "SH rows present"
+    cell, scope = op[1], op[2]
+    arrays = (st.positions[:3 * n], st.rotations[:4 * n], st.scales[:3 * n])
+    cand, _, members = mr.cells_of(*arrays, cell, scope_mask(scope, S, H))
+    merging = [i for idx in members.values() if len(idx) >= 2 for i in idx]
+    if not L[merging].any():
+        return "merges no cell with a listed member"
+    if len(merging) >= int(cand.sum()):
+        return "leaves no candidate unmerged"
+    rows_after = n - len(merging) + sum(len(idx) >= 2 for idx in members.values())
+    if not 2 <= rows_after < n:
+        return "leaves %d of %d rows" % (rows_after, n)
+    if "visible" in scope:      # a hidden splat in a cell that would otherwise merge: the scope keeps something out
+        _, _, wider = mr.cells_of(*arrays, cell, scope_mask(tuple(x for x in scope if x != "visible"), S, H))
+        if not any(len(idx) >= 2 and H[idx].any() for idx in wider.values()):
+            return "no hidden splat in a cell that would otherwise merge"
+    return None
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -883,6 +1090,169 @@ def editing_tour(band_context=False):
     return t
 
 
+def analysis_spacing(n):
+    """The radius at which a splat in the middle of a synth scene of n splats has about three neighbours.  The scenes of every trace
+    are gsplat_hip.synth's: positions drawn from a gaussian of standard deviation 1.5 per axis, so the density in the middle is
+    n / ((2 pi)^1.5 * 1.5^3) = n / 53.2 per unit volume, and 4/3 pi r^3 of it holds three at r = 3.4 * n^(-1/3) (0.27 at 2049 splats).
+    Radii and cell sides of the traces and of the observables are small multiples of it."""
+    return 3.4 * max(int(n), 1) ** (-1.0 / 3.0)
+
+
+COINCIDENT = 2.0 ** -10     # a cell side at which, in these scenes, little but a copy and its original share a cell
+CLUSTER_SEED = 0            # an index that is labelled where analysis_tour seeds select_cluster_at (tests/test_history_trace.py asks `vacuous`)
+
+
+def analysis_tour(band_context=False):
+    """The fixed trace of the analysis layer: every kind of ANALYSIS_KINDS with every scope and every fold op, every refusal of
+    ANALYSIS_REFUSALS, every pair of ANALYSIS_RISKY_PAIRS, on rows scenes of 2049, 4099, 2601 and 6001 splats (more than one
+    workgroup of 256 and a partial last wave each; merges shrink them, duplicates grow them past the scratch of the scene before) at
+    640 x 480 and one other size.  It starts from State()'s raw scene, where the pickers work and a merge is refused.  Every radius
+    differs from the one of the call before.  band_context: as in tour()."""
+    C, N = True, False
+    t = []
+    h = analysis_spacing(2049)
+
+    def add(*op, check=C):
+        t.append(Step(tuple(op), check))
+
+    def size(W, H):
+        add("resize", W, H)
+        if band_context:
+            add("band", *_band_for(W))
+
+    def band_off():
+        add("band", 0, 0)
+        if band_context:
+            add("band", 192, 448)
+
+    sel, vis, both = ("selected",), ("visible",), ("selected", "visible")
+    # a raw scene: the pickers and three of the reports work on positions alone, a merge is refused
+    add("refused", "merge_raw")
+    add("camera", 60)
+    add("select_neighbours", 1.1 * h, 1, None, 8, (), "replace")
+    add("report", "knn", 1.3 * h, 4, "kth", (), check=N)
+    add("same_pose")
+    # different features back to back over the one index, a different radius each time
+    add("scene", ("synth", 2049, 5, "rows"))
+    add("select_neighbours", 1.2 * h, 1, None, 16, (), "replace", check=N)
+    add("select_knn", 1.6 * h, 4, "mean", 0.0, 1.2 * h, (), "add")
+    add("select_clusters", 0.9 * h, 2, None, 0, (), "intersect")
+    add("merge_cells", 0.5 * h, ())
+    add("select_neighbours", 1.4 * h, 0, 1, 8, (), "replace")          # the floaters of the merged scene
+    add("merge_cells", 0.7 * h, ())
+    add("merge_cells", 0.9 * h, ())                                     # a larger cell over the rows the merge before wrote
+    add("same_pose")
+    # the statistical outlier filter: the threshold is a constant of the trace
+    add("select_knn", 2.0 * h, 8, "mean", 1.5 * h, None, (), "replace")
+    add("erase", False)
+    add("select_cluster_at", 1.5 * h, "largest", 0, (), "replace")
+    add("select_cluster_at", 1.25 * h, CLUSTER_SEED, 1, (), "add")
+    add("select_clusters", 1.0 * h, 0, 3, 2, (), "subtract")
+    # merge and the hidden set, in both scopes; scopes of the pickers
+    add("scene", ("synth", 2049, 5, "rows"))
+    add("set_hidden", (21, 0.3), "replace")
+    add("merge_cells", 0.6 * h, ())                                     # hidden members merge, H is carried with the leaders
+    add("sort_only", 1, 30)
+    add("set_hidden", (22, 0.3), "add")
+    add("select_neighbours", 1.3 * h, 1, None, 4, vis, "replace")
+    add("merge_cells", 0.8 * h, vis)                                    # a hidden member stays out of its cell
+    add("set_hidden", None, "replace")                                  # show all
+    add("set_selection", (23, 0.6), "replace", check=N)
+    add("select_knn", 1.7 * h, 2, "kth", 0.0, 1.1 * h, sel, "intersect")
+    add("select_clusters", 1.2 * h, 2, None, 1, sel, "replace")
+    add("set_selection", (24, 0.7), "replace", check=N)
+    add("merge_cells", 1.0 * h, sel)
+    add("burst", 64, 65, 66)
+    add("set_hidden", (25, 0.25), "replace")
+    add("set_selection", (26, 0.7), "replace", check=N)
+    add("select_cluster_at", 1.6 * h, "largest", 0, both, "intersect")
+    add("select_knn", 1.4 * h, 3, "mean", 0.0, 1.0 * h, both, "add")
+    add("select_neighbours", 1.9 * h, 2, 5, 4, both, "subtract")
+    add("select_clusters", 1.3 * h, 0, 2, 0, vis, "add")
+    add("set_selection", (27, 0.7), "replace", check=N)
+    add("merge_cells", 1.2 * h, both)
+    add("readback", "records", check=N)
+    add("camera", 61)
+    add("set_hidden", None, "replace")
+    # reports disturb neither frame nor scene
+    for which, args in (("neighbours", (1.1 * h, 16, ())), ("clusters", (1.4 * h, 2, vis)), ("knn", (1.7 * h, 8, "mean", sel)), ("cells", (0.9 * h, 8, both))):
+        add("report", which, *args, check=N)
+        add("same_pose")
+        add("report", which, *args, check=N)
+        add("readback", "bin_lists", check=N)
+    # the same radius twice in a row under another scope: an index kept for its radius alone would hold the wrong splats
+    add("set_selection", (29, 0.5), "replace", check=N)
+    add("report", "neighbours", 1.2 * h, 8, (), check=N)
+    add("select_neighbours", 1.2 * h, 1, None, 8, sel, "replace")
+    # scratch sizing: a larger scene, a smaller one, a report in front of the edit
+    add("scene", ("synth", 4099, 7, "rows"))
+    add("merge_cells", 0.6 * h, ())                                     # both shares of the merge scratch grow
+    add("band", 192, 448)
+    add("merge_cells", 0.8 * h, ())                                     # behind a band frame
+    add("band", 320, 600)
+    band_off()
+    add("merge_cells", 1.0 * h, ())
+    size(333, 219)
+    size(640, 480)
+    add("scene", ("synth", 2601, 8, "rows"))
+    add("merge_cells", 0.5 * h, ())                                     # scratch larger than the scene
+    # capacity above n: the copies merge with their originals
+    add("set_selection", (28, 0.65), "replace", check=N)
+    add("duplicate", "grow")                                            # past the 4099 rows the scratch was sized for
+    add("merge_cells", COINCIDENT, ())
+    add("duplicate", "fit")                                             # the merged rows again, onto the rows the compaction left stale
+    add("merge_cells", COINCIDENT, ())
+    add("reserve", 9000)
+    add("merge_cells", 0.7 * h, ())
+    add("append_arrays", 500, 21)
+    add("merge_cells", 0.9 * h, ())
+    add("erase", False)                                                 # the merged rows go
+    add("select_cluster_at", 1.5 * h, CLUSTER_SEED, 0, (), "replace")
+    add("scene", ("synth", 6001, 9, "rows"))
+    add("report", "cells", 0.4 * h, 4, (), check=N)                     # the report's share of the scratch only
+    add("merge_cells", 0.4 * h, ())
+    # frames in flight and regrown lists in front of the merge
+    add("burst", 67, 68, 69, check=N)
+    add("merge_cells", 0.5 * h, ())
+    add("overflow_async", 1024, 40, 41, 42)
+    add("merge_cells", 0.6 * h, ())
+    # pickers behind a change of positions, numbering or hidden set
+    add("scene", ("synth", 2049, 5, "rows"))
+    add("select_box", tuple(v * 0.5 for v in BOX), "replace", check=N)
+    add("edit", "translate", (0.5, -0.25, 0.125), None)
+    add("select_neighbours", 1.2 * h, 1, None, 8, (), "replace")
+    add("translate", (0.25, -0.125, 0.5))
+    add("select_knn", 1.5 * h, 4, "kth", 0.0, 1.25 * h, (), "replace")
+    add("limit_box", BOX)
+    add("select_clusters", 1.1 * h, 2, None, 0, (), "replace")
+    add("hide", "add")
+    add("select_neighbours", 1.3 * h, 0, 1, 8, vis, "replace")
+    add("set_hidden", None, "replace")
+    # the layers that follow the selection
+    add("select_box", tuple(v * 0.5 for v in BOX), "replace", check=N)
+    add("contrib_reset")
+    add("contrib_pass", check=N)
+    add("merge_cells", 0.5 * h, ())                                     # the accumulators are dropped
+    add("overlay", (1.0, 0.5, 0.0), 0.5, OUTLINE_OUTER, check=N)
+    add("merge_cells", 0.7 * h, ())                                     # the overlay tints the merged rows
+    add("ring_open", "rgba8", False, None, 1)
+    add("ring_overlay", True)
+    add("merge_cells", 0.9 * h, ())
+    add("deliver")
+    add("ring_overlay", False)
+    add("overlay", None)
+    add("ring_close")
+    # refusals
+    for which in ANALYSIS_REFUSALS:
+        if which == "merge_raw":
+            continue                                                    # (at the head of the trace, on the raw scene)
+        if which == "merge_with_sh":
+            add("sh", (11, 0.0, 0.25, 0.5))
+        add("refused", which)
+        add("camera", 70 + ANALYSIS_REFUSALS.index(which))
+    return t
+
+
 WALK_SIZES = ((640, 480), (333, 219), (900, 700), (64, 64), (801, 601), (512, 384), (160, 96))
 WALK_SCENES = (0, 1, 63, 2049, 20000, 7000, 300, 12000)
 WALK_RINGS = (("rgba8", False, None, 1), ("nv12", False, None, 1), ("i420", True, None, 1), ("rgba8", False, "u16", 1),
@@ -1045,6 +1415,68 @@ def _gen_edit(kind, s, rng):
     raise AssertionError(kind)
 
 
+def _gen_analysis(kind, s, rng, oracle):
+    """_gen for the kinds of ANALYSIS_KINDS and ("refused_analysis",).  The CPU fold of these is blocked brute force, so they are
+    generated on rows scenes of 33 .. MAX_ANALYSED splats only: a scene that is raw, smaller or has grown beyond that is replaced first.
+    Radii and cell sides are multiples of the scene's own spacing (analysis_spacing); what a step picks or merges depends on the
+    scene: walk() asks `vacuous` and draws again."""
+    rows_scene = ("scene", ("synth", rng.choice((2049, 3000, 4100)), rng.randrange(1, 50), "rows"))
+    n_now = _evaluate(s, oracle)[0].n
+    fits = scene_form(s.scene) == "rows" and 33 <= n_now <= MAX_ANALYSED
+    pre = [] if fits else [rows_scene]
+    n = n_now if fits else rows_scene[1][1]
+    sh_now = s.sh if fits else None
+    h = analysis_spacing(n)
+    some = ("set_selection", (rng.randrange(1, 99), rng.choice((0.5, 0.7))), "replace")
+    if kind == "refused_analysis":
+        which = rng.choice(ANALYSIS_REFUSALS)
+        if which == "merge_raw":
+            raw = scene_form(s.scene) == "raw" and scene_n(s.scene) >= 33
+            return ([] if raw else [("scene", ("synth", rng.choice((2049, 7000)), rng.randrange(1, 50), "raw"))]) + [("refused", which)]
+        if which == "merge_with_sh":
+            return pre + ([] if sh_now is not None else [("sh", (rng.randrange(1, 99), 0.0, 0.25, 0.5))]) + [("refused", which)]
+        return pre + [("refused", which)]
+    scope = rng.choice(SCOPES)
+    if "selected" in scope and rng.random() < 0.7:
+        pre = pre + [some]
+    if "visible" in scope and rng.random() < 0.7:
+        pre = pre + [("set_hidden", (rng.randrange(1, 99), rng.choice((0.2, 0.4))), "replace")]
+    radius = h * rng.choice((0.8, 1.0, 1.3, 1.7))
+    selop = rng.choice(SELOPS)
+    if kind == "select_neighbours":
+        lo, hi, cap = rng.choice(((0, 1, 4), (1, None, 16), (2, None, 64), (1, 3, 2)))
+        return pre + [(kind, radius, lo, hi, cap, scope, selop)]
+    if kind == "select_clusters":
+        lo, hi = rng.choice(((0, 2), (2, None), (3, None), (1, 4)))
+        return pre + [(kind, radius, lo, hi, rng.choice((0, 1, 3)), scope, selop)]
+    if kind == "select_cluster_at":
+        min_pts = rng.choice((0, 1, 2))
+        seed = "largest"
+        if rng.random() < 0.6:          # an index seed: a labelled splat of the scene as it will be, from the reference
+            st, S, H = _evaluate(fold_ops(s, pre), oracle)
+            lab = _analysis_refs()[1].Clusters(st.positions[:3 * st.n], radius, min_pts, scope_mask(scope, S, H)).labels
+            labelled = np.flatnonzero(lab != 0xffffffff)
+            if labelled.size:
+                seed = int(labelled[rng.randrange(labelled.size)])
+        return pre + [(kind, radius, seed, min_pts, scope, selop)]
+    if kind == "select_knn":
+        k, stat = rng.choice((1, 4, 8)), rng.choice(("kth", "mean"))
+        if rng.random() < 0.3:          # the statistical outlier filter, its threshold a constant of the operation
+            return pre + ([("sh", None)] if sh_now is not None else []) + [(kind, radius, k, "mean", 0.75 * radius, None, scope, "replace"), ("erase", False)]
+        return pre + [(kind, radius, k, stat, 0.0, radius * rng.choice((0.6, 0.8)), scope, selop)]
+    if kind == "merge_cells":
+        no_sh = [("sh", None)] if sh_now is not None else []
+        if rng.random() < 0.3:          # copies sit exactly on their originals: the most natural merge there is
+            return pre + no_sh + [("set_selection", (rng.randrange(1, 99), 0.2), "replace"), ("duplicate", None), (kind, COINCIDENT, tuple(x for x in scope if x != "selected"))]
+        return pre + no_sh + [(kind, h * rng.choice((0.5, 0.8, 1.2, 1.6)), scope)]
+    if kind == "report":
+        which = rng.choice(REPORTS)
+        args = {"neighbours": (radius, rng.choice((4, 64)), scope), "clusters": (radius, rng.choice((0, 2)), scope),
+                "knn": (radius, rng.choice((1, 8)), rng.choice(("kth", "mean")), scope), "cells": (radius, rng.choice((1, 8)), scope)}[which]
+        return pre + [("report", which) + args]
+    raise AssertionError(kind)
+
+
 def fold_ops(state, ops):
     for op in ops:
         state = fold(state, op)
@@ -1058,7 +1490,9 @@ def walk(seed, steps, start=State(), kinds=KINDS, oracle=None):
     kinds: KINDS (the walks as they always were), or KINDS + EDIT_KINDS: the editing layer's kinds and its refusals join the deck
     (scenes then grow to at most MAX_GROWN splats).  Those steps depend on the scene -- a hide must hide something that shows --,
     so the walk needs the `oracle` (CPU) to ask `vacuous`, draws a kind's operations again up to eight times and leaves the kind
-    to the next deck if all of them would check nothing."""
+    to the next deck if all of them would check nothing.  With kinds of ANALYSIS_KINDS among them the analysis layer's kinds and
+    refusals join the deck under the same rule (_gen_analysis: on rows scenes of at most MAX_ANALYSED splats), and the accumulators
+    are reset in front of a merge as in front of MOVES_GEOMETRY."""
     rng = random.Random(seed)
     t, s = [], start
     if kinds is KINDS or tuple(kinds) == KINDS:
@@ -1072,15 +1506,19 @@ def walk(seed, steps, start=State(), kinds=KINDS, oracle=None):
                     s = fold(s, op)
         return t[:steps]
     assert oracle is not None, "a walk over the editing layer asks the oracle which steps check something"
+    analysis = any(k in ANALYSIS_KINDS for k in kinds)      # (the analysis layer's kinds and its refusals join the deck as the editing layer's did)
     while len(t) < steps:
-        deck = list(kinds) + ["refused_edit"]
+        deck = list(kinds) + ["refused_edit"] + (["refused_analysis"] if analysis else [])
         rng.shuffle(deck)
         for kind in deck:
             for _ in range(8):
-                ops = _gen(kind, s, rng) if kind in KINDS else _gen_edit(kind, s, rng)
+                if kind in ANALYSIS_KINDS or kind == "refused_analysis":
+                    ops = _gen_analysis(kind, s, rng, oracle)
+                else:
+                    ops = _gen(kind, s, rng) if kind in KINDS else _gen_edit(kind, s, rng)
                 s1, out = s, []
                 for op in ops:
-                    if s1.contrib and op[0] in MOVES_GEOMETRY:
+                    if s1.contrib and op[0] in MOVES_GEOMETRY + ("merge_cells",):
                         out.append(("contrib_reset",))   # (the accumulators describe frames of splats that are about to move)
                         s1 = fold(s1, out[-1])
                     if vacuous(s1, op, oracle) is not None:
@@ -1093,7 +1531,7 @@ def walk(seed, steps, start=State(), kinds=KINDS, oracle=None):
             if out is None:
                 continue
             for op in out:
-                check = not ((op[0] in KEEPS_FRAME or op[0] in EDIT_KEEPS_FRAME) and rng.random() < 0.3)
+                check = not ((op[0] in KEEPS_FRAME or op[0] in EDIT_KEEPS_FRAME or op[0] in ANALYSIS_KEEPS_FRAME) and rng.random() < 0.3)
                 t.append(Step(op, check))
                 s = fold(s, op)
     return t[:steps]
@@ -1440,6 +1878,9 @@ def apply(gh, r, op, before, edited=False):
         got = r.acquire(k)
         assert got[0] == k
         r.release(k)
+    elif kind == "refused" and a[0] in ANALYSIS_REFUSAL_TEXTS:
+        out["code"], out["message"] = _refuse_analysis(gh, r, a[0])
+        assert out["code"] == GSR_ERR_ARG and ANALYSIS_REFUSAL_TEXTS[a[0]] in out["message"], (a[0], out)
     elif kind == "refused":
         out["code"] = _refuse(gh, r, before, a[0])
     else:
@@ -1504,5 +1945,65 @@ def _apply_editing(gh, r, op, before, out):
         r.set_camera(camera_of(gh, before))
         r._check(r._L.gsr_render(r._ctx))                 # the blocking entry point: a frame that did not fit is rendered again
         r.contrib_accumulate()
+    elif kind == "select_neighbours":
+        radius, lo, hi, cap, scope, selop = a
+        out["selected"], out["info"] = r.select_neighbours(radius, lo, hi, cap, scope, selop)
+    elif kind == "select_clusters":
+        radius, lo, hi, min_pts, scope, selop = a
+        out["selected"], out["info"] = r.select_clusters(radius, lo, hi, min_pts, scope, selop)
+    elif kind == "select_cluster_at":
+        radius, seed, min_pts, scope, selop = a
+        out["selected"], out["info"] = r.select_cluster_at(radius, seed, min_pts, scope, selop)
+    elif kind == "select_knn":
+        radius, k, stat, lo, hi, scope, selop = a
+        out["selected"], out["info"] = r.select_knn(radius, k, stat, lo, hi, scope, selop)
+    elif kind == "merge_cells":
+        n0 = r.scene_count()
+        n1, out["info"] = r.scene_merge_cells(a[0], a[1])
+        assert 2 <= n1 < n0 and n1 == r.scene_count(), (op, n0, n1)      # (the traces' merges all merge something and leave something)
+    elif kind == "report":
+        out["report"] = report(r, a)
     else:
         raise AssertionError(op)
+
+
+def report(r, a):
+    """one of the read-only calls, ("neighbours" | "clusters" | "knn" | "cells", arguments as the operation holds them): what it returned"""
+    which = a[0]
+    if which == "neighbours":
+        return r.neighbours(a[1], a[2], a[3])
+    if which == "clusters":
+        return r.clusters(a[1], a[2], a[3])
+    if which == "knn":
+        return r.knn(a[1], a[2], a[3], a[4])
+    if which == "cells":
+        return r.cells(a[1], a[2], a[3], leaders=True)
+    raise AssertionError(a)
+
+
+def _refuse_analysis(gh, r, which):
+    """one call of the analysis layer the library must refuse; returns (code, message).  The calls go to the C ABI where the Python
+    layer would stop them first (cap, k)."""
+    L, ctx = r._L, r._ctx
+    inf, nan = float("inf"), float("nan")
+    if which in ("merge_raw", "merge_with_sh"):
+        rc = L.gsr_scene_merge_cells(ctx, 0.25, 0, 0, None, None)
+    elif which == "budget_of_one":
+        rc = L.gsr_select_neighbours(ctx, 0.25, 8, 0, 1, 0, 9, 0, None, None)
+    elif which == "cell_not_finite":
+        rc = L.gsr_scene_merge_cells(ctx, inf, 0, 0, None, None)
+    elif which == "cell_not_positive":
+        rc = L.gsr_cells(ctx, 0.0, 8, 0, 0, None, 0, None, None)
+    elif which == "radius_not_finite":
+        rc = L.gsr_select_knn(ctx, nan, 4, 0, 0, 1, 0.0, 1.0, 0, None, None)
+    elif which == "radius_not_positive":
+        rc = L.gsr_select_clusters(ctx, -0.25, 0, 0, 0, 0, 4, 0, None, None)
+    elif which == "cap_out_of_range":
+        rc = L.gsr_select_neighbours(ctx, 0.25, 4096, 0, 0, 0, 1, 0, None, None)
+    elif which == "k_out_of_range":
+        rc = L.gsr_knn(ctx, 0.25, 33, 0, 0, 1, None, None, None, None, 0, None, None)
+    else:
+        raise AssertionError(which)
+    if rc == 0:
+        raise AssertionError("the library accepted %s" % which)
+    return rc, L.gsr_last_error(ctx).decode()

@@ -25,7 +25,8 @@ pytestmark = pytest.mark.gpu
 TOL_EXACT = 2e-4
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BOUNDS_LIB = os.path.join(ROOT, "gsplat.js_amd", "lib_exp", "bounds", "libgsplat_hip.so")
-BOUNDS_UNITS = ("blend", "bin", "sort", "depth", "deliver")
+ANALYSIS_UNITS = ("merge", "neighbours", "knn", "clusters", "attr")      # the observables run these kernels on every trace
+BOUNDS_UNITS = ("blend", "bin", "sort", "depth", "deliver") + ANALYSIS_UNITS
 
 # The only things a veteran and a fresh context may disagree on: what counts frames, deliveries or time.
 #   gsr_timings: everything but these four describes the context's life, not the frame
@@ -37,7 +38,15 @@ TRAILER_FRAME_WORDS = 2
 #   arrays grow to max(need, capacity + capacity / 2) and never shrink, a compaction keeps the old count's rows, and the selection,
 #   hidden and contribution buffers are counted once they exist -- a veteran that grew, reserved or showed everything again holds
 #   more than a context that was handed the final scene
-NOT_COMPARED = ("scene_capacity()", "scene_sharing() bytes")
+#   pair_bound of the four analysis infos is "the pair tests the walk makes at most, AS THE IMPLEMENTATION COUNTS THEM" (include/gsplat_hip.h,
+#   "neighbours": the populations of hash buckets, whose number the header leaves to the implementation): a context may size its table
+#   by its scratch, which only grows.  The feature suites bound it by an interval (pair_floor <= pair_bound <= budget); every other
+#   field of the infos is defined by the scene and the arguments and is compared
+NOT_COMPARED = ("scene_capacity()", "scene_sharing() bytes", "pair_bound")
+# The analysis observables are asked while the scene holds at most this many splats: every scene of the editing and analysis traces
+# (history_trace.MAX_GROWN) and of the walks.  tour()'s scenes of 70 000 .. 3.2 M splats are left to the observables they always had.
+ANALYSIS_OBSERVED_MAX = 40000
+assert ANALYSIS_OBSERVED_MAX >= ht.MAX_GROWN
 
 
 @pytest.fixture(scope="module")
@@ -130,7 +139,27 @@ def observe(r, state, points=None):
         o["read_contrib() (weight, peak, pixels, frames)"] = r.read_contrib()
     o["attr_histogram(opacity, visible and selected)"] = r.attr_histogram("opacity", 0.0, 256.0, 16, selected=True, visible=True)[:2]
     o["attr_stats(opacity, visible and selected)"] = r.attr_stats("opacity", selected=True, visible=True)
+    # the analysis calls, over the one neighbour scratch and index the veteran's earlier calls left behind: parameters from the scene's
+    # own spacing (history_trace.analysis_spacing), the scope that ties them to both sets wherever both are non-empty
+    n = o["scene_count()"]
+    if n <= ANALYSIS_OBSERVED_MAX:
+        h = ht.analysis_spacing(n)
+        scope = ("selected", "visible") if o["selection count"] and o["hidden count"] else ()
+        counts, hist, info = r.neighbours(1.1 * h, 16, scope)
+        o["neighbours() counts"], o["neighbours() hist"], o["neighbours() info"] = counts, hist, _info(info)
+        labels, sizes, info = r.clusters(1.3 * h, 2, scope)
+        o["clusters() labels"], o["clusters() sizes"], o["clusters() info"] = labels, sizes, _info(info)
+        found, _, _, values, _, info = r.knn(1.6 * h, 4, "mean", scope, hist=False)
+        o["knn() found"], o["knn() values"], o["knn() info"] = found, values, _info(info)
+        if ht.scene_form(state.scene) == "rows" or not n:       # (cells are of rotations and scales too: a raw scene has none)
+            leader, hist, info = r.cells(0.9 * h, 8, scope, leaders=True)
+            o["cells() leader"], o["cells() hist"], o["cells() info"] = leader, hist, _info(info)
     return o
+
+
+def _info(info):
+    """an analysis call's info without NOT_COMPARED's field"""
+    return tuple(sorted((k, v) for k, v in info.items() if k != "pair_bound"))
 
 
 def _render(gh, r, state):
@@ -327,7 +356,7 @@ def _bounds_counts(L, units):
 # State.edits / overlay / ring_overlay / contrib).  The fresh context gets the recipe evaluated on the CPU: it never ran an edit
 # kernel and never grew, and its capacity equals its count.
 # ---------------------------------------------------------------------------------------------------------------------------
-EDIT_BOUNDS_UNITS = ("blend", "bin", "sort", "depth", "deliver", "scene", "scene_sh", "select", "edit", "append", "contrib", "overlay", "attr")
+EDIT_BOUNDS_UNITS = ("blend", "bin", "sort", "depth", "deliver", "scene", "scene_sh", "select", "edit", "append", "contrib", "overlay") + ANALYSIS_UNITS
 ALL_KINDS = ht.KINDS + ht.EDIT_KINDS
 
 
@@ -382,7 +411,11 @@ def test_two_veterans_share_one_scene(gh, oracle):
            ("duplicate", "grow"), ("edit", "rotate", ht.QUAT, ht.PIVOT), ("set_hidden", (5, 0.3), "add"), ("select_region", (80, 50, 250, 170), None, "replace"),
            ("edit", "rgba", (0x80ff2010, 0xffffffff), None), ("select_attr", "opacity", 0.0, 128.0, None, "add"), ("duplicate", None), ("erase", False),
            ("select_region", ht.RECT, None, "replace"), ("reserve", 9000), ("duplicate", "fit"), ("rotate", ht.QUAT), ("set_hidden", None, "replace"),
-           ("invert_selection",), ("append_arrays", 33, 4), ("limit_box", ht.BOX), ("set_selection", (6, 0.5), "replace"), ("erase", True)]
+           ("invert_selection",), ("append_arrays", 33, 4), ("limit_box", ht.BOX), ("set_selection", (6, 0.5), "replace"), ("erase", True),
+           # the analysis layer: a merge through member 0, a picker and a report through member 1, frames of both in between
+           ("set_selection", (7, 0.3), "replace"), ("duplicate", None), ("merge_cells", ht.COINCIDENT, ()),
+           ("select_neighbours", 0.4, 1, None, 8, (), "replace"), ("set_hidden", (8, 0.3), "replace"), ("report", "clusters", 0.5, 1, ("visible",)),
+           ("merge_cells", 0.3, ("visible",)), ("select_knn", 0.6, 2, "kth", 0.0, 0.45, ("selected", "visible"), "add")]
     scene = ("synth", 2049, 5, "rows")
     states = [ht.State(kind="default", scene=scene), ht.State(kind="throughput", timing=True, W=333, H=219, scene=scene)]
     vets = [ht.build(gh, s) for s in states]
@@ -403,7 +436,7 @@ def test_two_veterans_share_one_scene(gh, oracle):
             ht.apply(gh, vets[actor], op, states[actor])
             after = ht.fold(states[actor], op)
             states = [replace(s, **{f: getattr(after, f) for f in SHARED_FIELDS}) for s in states]
-            edit = op[0] not in ht.SELECT_KINDS and op[0] != "reserve"
+            edit = op[0] not in ht.SELECT_KINDS + ht.ANALYSIS_KEEPS_FRAME and op[0] != "reserve"
             got = ht.apply(gh, vets[other], ("readback", "pick"), states[other], edited=edit)
             assert ("refused" in got) == edit, (k, op, got)
             seen = [compare_with_fresh(gh, vets[j], states[j], where(j)) for j in (0, 1)]
@@ -418,13 +451,14 @@ def test_two_veterans_share_one_scene(gh, oracle):
 
 
 def test_frames_in_flight_with_edits_have_no_memory(gh):
-    """test_frames_in_flight_have_no_memory with hides, duplicates and erases between the frames"""
+    """test_frames_in_flight_have_no_memory with hides, duplicates, erases and a merge between the frames"""
     pick = [("set_selection", (3, 0.3), "replace"), ("set_selection", (4, 0.1), "replace"), ("select_box", tuple(v * 0.5 for v in ht.BOX), "replace")]
     plans = [
         {1: [pick[0], ("hide", "add")], 3: [("duplicate", None)], 5: [("erase", False)], 6: [("set_hidden", None, "replace")], 7: [pick[1], ("duplicate", None)]},
         {0: [("resize", 333, 219)], 2: [pick[2], ("duplicate", None)], 3: [("hide", "add")], 4: [("resize", 801, 601)], 5: [pick[1], ("erase", False)],
          7: [("band", 256, 512)]},
         {1: [pick[1], ("duplicate", None)], 2: [("duplicate", None)], 4: [("set_hidden", (5, 0.5), "replace")], 5: [pick[0], ("erase", True)], 6: [("set_hidden", (6, 0.5), "add")],
+         7: [pick[1], ("duplicate", None), ("merge_cells", ht.COINCIDENT, ())],     # a merge between frames in flight: the copies merge with their originals
          8: [("timing_interval", 2)]},
     ]
     states = [ht.State(kind="throughput", timing=True, scene=("synth", 20000, 9 + j, "rows")) for j in range(3)]
@@ -466,6 +500,76 @@ def test_the_editing_refusals_change_nothing_and_say_why(gh):
             cap = r.scene_capacity()
             assert ht.apply(gh, r, ("refused", which), s)["code"] == code, which
             assert (r.scene_count(), r.scene_capacity()) == (2049, cap) and r.sh_frame()[1] is False
+        finally:
+            r.dispose()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The analysis layer: neighbour counts, clusters, k nearest neighbours and merge cells (history_trace's ANALYSIS_KINDS).  All four
+# share one neighbour scratch and one hashed index per context; a merge replaces the scene from the inside.  The fresh context gets
+# the recipe evaluated on the CPU by the feature suites' references: it never ran an analysis kernel before its own observables.
+# ---------------------------------------------------------------------------------------------------------------------------
+EVERY_KIND = ht.KINDS + ht.EDIT_KINDS + ht.ANALYSIS_KINDS
+ANALYSIS_WALK_STEPS = 180
+
+
+def test_analysis_tour_on_a_default_context(gh):
+    t = ht.analysis_tour()
+    checked, _ = run_trace(gh, t, ht.State(kind="default"), "analysis tour, default context")
+    assert checked == sum(st.check for st in t)
+
+
+def test_analysis_tour_on_a_throughput_context(gh):
+    """(with stage events on every other frame: the others are graph replays)"""
+    t = [ht.Step(("timing_interval", 2), True)] + ht.analysis_tour()
+    checked, _ = run_trace(gh, t, ht.State(kind="throughput", timing=True), "analysis tour, throughput context")
+    assert checked == sum(st.check for st in t)
+
+
+def test_analysis_tour_on_a_band_context(gh):
+    t = ht.analysis_tour(band_context=True)
+    checked, _ = run_trace(gh, t, ht.State(kind="throughput", band=(192, 448)), "analysis tour, band context")
+    assert checked == sum(st.check for st in t)
+
+
+def test_analysis_tour_on_the_bounds_checked_build(gh):
+    """a bucket of the table the call before sized, an entry of the old numbering, a mask word of the larger scene's scratch: indices
+    into the wrong data, counted by the build that checks every index derived from device data"""
+    assert os.path.exists(BOUNDS_LIB), "the bounds-checked build is missing: run python -c 'import __graft_entry__ as g; g.build()'"
+    t = ht.analysis_tour(band_context=True)
+    _, L = run_trace(gh, t, ht.State(kind="default", band=(192, 448)), "analysis tour, bounds-checked build", lib_path=BOUNDS_LIB)
+    bad = _bounds_counts(L, EDIT_BOUNDS_UNITS)
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("kind", ["default", "throughput"])
+@pytest.mark.parametrize("seed", [7, 14, 21])
+def test_analysis_walks(gh, oracle, seed, kind):
+    """random walks over all three kind sets together (tests/test_history_trace.py: each holds every kind, no step is vacuous)"""
+    start = ht.State(kind=kind, timing=bool(seed & 1))
+    t = ht.walk(seed, ANALYSIS_WALK_STEPS, start, kinds=EVERY_KIND, oracle=oracle)
+    run_trace(gh, t, start, "walk(%d, %d, kinds=KINDS + EDIT_KINDS + ANALYSIS_KINDS), %s context" % (seed, ANALYSIS_WALK_STEPS, kind), oracle=oracle)
+
+
+def test_the_analysis_refusals_change_nothing_and_say_why(gh):
+    """the codes and texts of ANALYSIS_REFUSALS, each from the State it needs (the analysis tour walks them with a frame behind each):
+    scene, selection and count stay, and a picker refused for its budget leaves the selection untouched"""
+    raw = ht.State(kind="default", scene=("synth", 2049, 5, "raw"))
+    rows = ht.State(kind="default", scene=("synth", 2049, 5, "rows"))
+    some = ("set_selection", (3, 0.5), "replace")
+    for which in ht.ANALYSIS_REFUSALS:
+        start = raw if which == "merge_raw" else rows
+        prelude = [some] + ([("sh", (11, 0.0, 0.25, 0.5))] if which == "merge_with_sh" else [])
+        r, s = ht.build(gh, start), start
+        try:
+            for op in prelude:
+                ht.apply(gh, r, op, s)
+                s = ht.fold(s, op)
+            scene, words, cap = r.read_scene(with_rows=which != "merge_raw"), r.selection_words().copy(), r.scene_capacity()
+            got = ht.apply(gh, r, ("refused", which), s)
+            assert got["code"] == ht.GSR_ERR_ARG and ht.ANALYSIS_REFUSAL_TEXTS[which] in got["message"], (which, got)
+            assert (r.scene_count(), r.scene_capacity()) == (2049, cap) and _same(r.selection_words(), words), which
+            assert _same(r.read_scene(with_rows=which != "merge_raw"), scene), which
         finally:
             r.dispose()
 
