@@ -557,6 +557,19 @@ struct gsr_ctx {
         uint32_t edit_rows = 0, edit_words = 0;
     } mg;
 
+    // planes (gsr_plane.cpp): the device scratch of gsr_fit_plane / gsr_plane_inliers, the context's own; the first such call
+    // allocates it, it only grows, and the context's end frees it
+    struct Plane {
+        gsr::DevBuf<uint32_t> words;            // PL_INFO_WORDS: the totals, then PlBest
+        gsr::DevBuf<uint32_t> cand, block;      // `rows` candidates; plane_blocks(rows) + 1 block sums
+        uint32_t rows = 0;
+        gsr::DevBuf<double4> planes;            // PLANE_MAX_HYPOTHESES each
+        gsr::DevBuf<uint4> triple;
+        gsr::DevBuf<uint32_t> scores;
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // in front of the candidates, behind them, behind the scores
+        float candidates_ms = 0.0f, score_ms = 0.0f;      // of the last call that ran both (gsr_debug_plane_times)
+    } pl;
+
     // frame delivery (gsr_delivery_open): a ring of pinned host blocks, each with its device staging and "copy done" event
     struct Delivery {
         struct Slot {

@@ -698,6 +698,45 @@ void launch_mg_members(uint32_t n, uint32_t merged_members, const MgArrays& a, h
 // every merged cell reduced and written at its leader's row of `scene`
 void launch_mg_reduce(const SceneDev& scene, uint32_t n, uint32_t merged_cells, uint32_t merged_members, const MgArrays& a, hipStream_t s);
 
+// Planes (k_plane.hip; DESIGN.md section 4, "Planes"): the dominant plane of the splats in scope by RANSAC -- hypotheses drawn by a
+// counter-based generator, every one scored against every candidate in f64 -- the scoring pass alone over planes of the host's, and
+// the splats whose signed distance from a plane lies in [lo, hi] as a picker.  A candidate is a splat in scope with a finite position.
+constexpr uint32_t PLANE_MAX_HYPOTHESES = 4096;             // GSR_PLANE_MAX_HYPOTHESES
+constexpr uint32_t PLANE_CHUNK = 512;                       // candidates a score workgroup stages at a time: 3 * 8 * 512 = 12 KB of LDS,
+                                                            // so eight 256-lane workgroups (a compute unit's 32 waves) hold 96 of its 160 KB
+constexpr uint32_t PLANE_MAX_CHUNK_GROUPS = 2048;           // the score grid's other dimension at most: a group walks chunks g, g + groups, ..
+constexpr uint32_t PLANE_THREADS = 256;                     // splats of a candidate workgroup: one entry of the block sums
+// what k_plane_best leaves for the host: behind the totals in the call's words
+struct PlBest {
+    uint32_t degenerate, found, best, triple[3], inliers, pad;
+    double plane[4];
+};
+struct PlArrays {
+    unsigned long long* totals;            // in_scope | nonfinite << 32 (zeroed by the caller)
+    PlBest* result;
+    uint32_t* block;                       // plane_blocks(n) + 1 words: the candidates per 256 splats, scanned in place; [blocks] their number
+    uint32_t* cand;                        // cand_rows: the candidates' splat indices, ascending
+    uint32_t cand_rows;
+    double4* planes;                       // PLANE_MAX_HYPOTHESES each: (a, b, c, d); the triple and, in .w, 1 for a degenerate hypothesis
+    uint4* triple;
+    uint32_t* scores;
+};
+inline uint32_t plane_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + PLANE_THREADS - 1u) / PLANE_THREADS); }
+// a.cand[0 .. m) <- the candidates in ascending index, a.block[plane_blocks(n)] <- m, *a.totals += in_scope | nonfinite << 32.  n >= 1.
+void launch_plane_candidates(const float* px, const float* py, const float* pz, const AttrScope& sc, uint32_t n, const PlArrays& a, hipStream_t s);
+// a.planes[h], a.triple[h] for h < hypotheses from the candidates' positions.  m >= 1.
+void launch_plane_hypotheses(const float* px, const float* py, const float* pz, uint32_t hypotheses, uint64_t seed, uint32_t m, uint32_t n, const PlArrays& a,
+                             hipStream_t s);
+// a.scores[h] (zeroed by the caller) += the candidates within `threshold` of a.planes[h], h < count; with `flagged` a hypothesis
+// whose a.triple[h].w is set is skipped.  m >= 1.
+void launch_plane_score(const float* px, const float* py, const float* pz, uint32_t count, uint32_t m, uint32_t n, double threshold, bool flagged, const PlArrays& a,
+                        hipStream_t s);
+// *a.result from the scores, the flags, the triples and the planes
+void launch_plane_best(uint32_t hypotheses, const PlArrays& a, hipStream_t s);
+// scratch <- the splats i < n with lo <= s_i && s_i <= hi: every word of it is stored, no zeroing needed
+void launch_plane_select(const float* px, const float* py, const float* pz, uint32_t n, double4 plane, double lo, double hi, uint32_t* scratch, uint32_t nwords,
+                         hipStream_t s);
+
 // Selection overlay (k_overlay.hip; DESIGN.md section 4, "Selection overlay"): the last frame's bin lists walked once more, the
 // weight w = T * B of every fragment of a SELECTED splat summed per pixel (cover) and, with the splat's colour, turned into the
 // frame with those splats tinted (overlay).  Reads the framebuffer, never writes it.

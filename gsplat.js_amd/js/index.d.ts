@@ -100,6 +100,10 @@ export interface SplatStats { count: number; nan: number; min: number; max: numb
 export type NeighbourScope = "selected" | "visible";
 export interface NeighbourOptions { cap?: number; scope?: NeighbourScope | NeighbourScope[]; budget?: number }
 export interface SplatNeighbours { counts: Uint32Array; hist: Uint32Array; inScope: number; nonfinite: number; pairBound: number }
+export type Plane = ArrayLike<number>;   // (a, b, c, d): a . x + b . y + c . z + d = 0
+export interface PlaneFitOptions { hypotheses?: number; seed?: number; scope?: NeighbourScope | NeighbourScope[]; budget?: number; scores?: boolean }
+export interface PlaneFit { plane: Float64Array | null; found: boolean; best: number; triple: Uint32Array; inliers: number; degenerate: number; inScope: number;
+    nonfinite: number; hypotheses: number; tests: number; scores?: Uint32Array }
 export interface ClusterOptions { minPts?: number; scope?: NeighbourScope | NeighbourScope[]; budget?: number }
 export interface SplatClusters { labels: Uint32Array; sizes: Uint32Array; inScope: number; nonfinite: number; pairBound: number; core: number; border: number;
     noise: number; clusters: number; largestLabel: number; largestSize: number }
@@ -393,6 +397,21 @@ export class HIPRenderer {
      *  most 2^38); a radius that needs more throws before the count pass runs, with both numbers in the message. */
     splatNeighbours(radius: number, options?: NeighbourOptions): SplatNeighbours;
     selectNeighbours(radius: number, options?: NeighbourOptions & { below?: number; lo?: number; hi?: number; op?: SelectOp }): number;
+    /** Planes: fitPlane finds the dominant plane of the splats in scope by RANSAC on the device -- `hypotheses` (1 .. 4096, default
+     *  512) planes through three splats each, drawn by a counter-based generator from `seed`, every one scored in f64 by the splats
+     *  within `threshold` of it (a distance of exactly threshold counts); the largest score wins, ties go to the smallest index.
+     *  plane: (nx, ny, nz, d) with a unit normal, null when every hypothesis was degenerate; scores: true adds every hypothesis's
+     *  score.  planeInliers scores up to 4096 planes of the host's, used as given.  selectPlane picks lo <= signed distance <= hi
+     *  over all splats (within: t is { lo: -t, hi: t }; a NaN distance is never picked) and folds them into the selection with `op`,
+     *  returning the number of selected splats: after an unscoped fit, selectPlane(plane, { within: threshold }) selects exactly
+     *  `inliers` splats, and selectPlane(plane, { hi: -t }) is everything under the floor.  planeAlignment returns the whole-scene
+     *  rotation and translation that take the plane to axis . p = 0 (axis: default +y): scene.rotate(rotation);
+     *  scene.translate(translation).  budget: the most tests (hypotheses x candidates) a call may make (default 2^34, at most 2^38);
+     *  more throws before the scoring pass runs, with both numbers in the message. */
+    fitPlane(threshold: number, options?: PlaneFitOptions): PlaneFit;
+    planeInliers(planes: ArrayLike<Plane>, threshold: number, options?: { scope?: NeighbourScope | NeighbourScope[]; budget?: number }): Uint32Array;
+    selectPlane(plane: Plane, options?: { within?: number; lo?: number; hi?: number; op?: SelectOp }): number;
+    planeAlignment(plane: Plane, options?: { axis?: ArrayLike<number> | Vector3 }): { rotation: Quaternion; translation: Vector3 };
     /** Clusters: the connected islands of the splats in scope at the linking radius `radius` (f64, distance exactly radius links).
      *  minPts (0 .. 4095, default 0: plain connected components) makes it DBSCAN: a splat with minPts or more others within radius is
      *  core, core splats within radius of each other share a cluster, a non-core splat beside a core one takes the smallest such

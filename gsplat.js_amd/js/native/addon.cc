@@ -1490,6 +1490,144 @@ napi_value SelectNeighbours(napi_env env, napi_callback_info info)
     return rc ? throw_gsr(env, c, rc, "gsr_select_neighbours") : count_value(env, count);
 }
 
+// ---- planes (gsr_fit_plane / gsr_plane_inliers / gsr_select_plane / gsr_plane_alignment) ----
+// threshold at argv[t], scope and budget at argv[sb], argv[sb + 1] (the budget a number, 0: the library's default); false: an error is pending
+bool get_plane_args(napi_env env, napi_value* argv, int t, int sb, double* threshold, uint32_t* scope, uint64_t* budget)
+{
+    double b;
+    if (!get_f64(env, argv[t], threshold) || napi_get_value_uint32(env, argv[sb], scope) != napi_ok || !get_f64(env, argv[sb + 1], &b)) {
+        napi_throw_type_error(env, nullptr, "planes: threshold, scope and budget must be numbers");
+        return false;
+    }
+    if (!(b >= 0.0 && b <= 18446744073709549568.0)) { napi_throw_range_error(env, nullptr, "planes: budget must be a non-negative number"); return false; }
+    *budget = (uint64_t)b;
+    return true;
+}
+
+// a Float64Array of at least `need` values
+bool get_f64_array(napi_env env, napi_value v, size_t need, const char* what, const double** out)
+{
+    void* data = nullptr;
+    size_t len = 0;
+    if (!get_typed(env, v, napi_float64_array, &data, &len)) return false;
+    if (!data || len < need) { napi_throw_range_error(env, nullptr, what); return false; }
+    *out = (const double*)data;
+    return true;
+}
+
+bool set_plane_info(napi_env env, napi_value out, const gsr_plane_info& pi)
+{
+    return set_u32(env, out, "inScope", pi.in_scope) && set_u32(env, out, "nonfinite", pi.nonfinite) && set_u32(env, out, "hypotheses", pi.hypotheses) &&
+           set_f64(env, out, "tests", (double)pi.tests) && set_f64(env, out, "budget", (double)pi.budget);
+}
+
+// fitPlane(handle, threshold, hypotheses, seed, scope, budget, wantScores) -> { found, plane: Float64Array(4), best, triple: Uint32Array(3), inliers,
+//   degenerate, inScope, nonfinite, hypotheses, tests, budget[, scores: Uint32Array(hypotheses)] }
+napi_value FitPlane(napi_env env, napi_callback_info info)
+{
+    napi_value argv[7];
+    if (!get_args(env, info, 7, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    double threshold, seed;
+    uint32_t hypotheses, scope;
+    uint64_t budget;
+    bool want = false;
+    if (!c || !get_plane_args(env, argv, 1, 4, &threshold, &scope, &budget)) return nullptr;
+    if (napi_get_value_uint32(env, argv[2], &hypotheses) != napi_ok || !get_f64(env, argv[3], &seed) || napi_get_value_bool(env, argv[6], &want) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "fitPlane: hypotheses and seed must be numbers, scores a boolean");
+        return nullptr;
+    }
+    if (hypotheses < 1 || hypotheses > GSR_PLANE_MAX_HYPOTHESES) { napi_throw_range_error(env, nullptr, "fitPlane: hypotheses must be in 1 .. 4096"); return nullptr; }
+    if (!(seed >= 0.0 && seed <= 9007199254740992.0)) { napi_throw_range_error(env, nullptr, "fitPlane: seed must be a non-negative integer"); return nullptr; }
+    void *scores = nullptr, *plane = nullptr, *triple = nullptr;
+    napi_value sb, sarr = nullptr, pb, parr, tb, tarr, out;
+    if (want) {
+        NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, (size_t)hypotheses * 4, &scores, &sb));
+        NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_uint32_array, hypotheses, sb, 0, &sarr));
+    }
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, 32, &plane, &pb));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_float64_array, 4, pb, 0, &parr));
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, 12, &triple, &tb));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_uint32_array, 3, tb, 0, &tarr));
+    gsr_plane_info pi{};
+    const int rc = gsr_fit_plane(c, threshold, hypotheses, (uint64_t)seed, scope, budget, (uint32_t*)scores, &pi);
+    if (rc) return throw_gsr(env, c, rc, "gsr_fit_plane");
+    std::memcpy(plane, pi.plane, 32);
+    std::memcpy(triple, pi.triple, 12);
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "plane", parr));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "triple", tarr));
+    if (want) NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "scores", sarr));
+    if (!set_u32(env, out, "found", pi.found) || !set_u32(env, out, "best", pi.best) || !set_u32(env, out, "inliers", pi.inliers) ||
+        !set_u32(env, out, "degenerate", pi.degenerate) || !set_plane_info(env, out, pi)) return nullptr;
+    return out;
+}
+
+// planeInliers(handle, planes: Float64Array(4 * count), count, threshold, scope, budget) -> { inliers: Uint32Array(count), inScope, nonfinite, hypotheses, tests, budget }
+napi_value PlaneInliers(napi_env env, napi_callback_info info)
+{
+    napi_value argv[6];
+    if (!get_args(env, info, 6, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    double threshold;
+    uint32_t count, scope;
+    uint64_t budget;
+    const double* planes = nullptr;
+    if (!c || !get_plane_args(env, argv, 3, 4, &threshold, &scope, &budget)) return nullptr;
+    if (napi_get_value_uint32(env, argv[2], &count) != napi_ok) { napi_throw_type_error(env, nullptr, "planeInliers: count must be a number"); return nullptr; }
+    if (count < 1 || count > GSR_PLANE_MAX_HYPOTHESES) { napi_throw_range_error(env, nullptr, "planeInliers: 1 .. 4096 planes"); return nullptr; }
+    if (!get_f64_array(env, argv[1], (size_t)count * 4, "planeInliers: planes must hold 4 values per plane", &planes)) return nullptr;
+    void* inl = nullptr;
+    napi_value ib, iarr, out;
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, (size_t)count * 4, &inl, &ib));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_uint32_array, count, ib, 0, &iarr));
+    gsr_plane_info pi{};
+    const int rc = gsr_plane_inliers(c, planes, count, threshold, scope, budget, (uint32_t*)inl, &pi);
+    if (rc) return throw_gsr(env, c, rc, "gsr_plane_inliers");
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "inliers", iarr));
+    if (!set_plane_info(env, out, pi)) return nullptr;
+    return out;
+}
+
+// selectPlane(handle, plane: Float64Array(4), lo, hi, op) -> selected
+napi_value SelectPlane(napi_env env, napi_callback_info info)
+{
+    napi_value argv[5];
+    if (!get_args(env, info, 5, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    const double* plane = nullptr;
+    double lo, hi;
+    int32_t op;
+    if (!c || !get_f64_array(env, argv[1], 4, "selectPlane: plane must hold 4 values", &plane) || !get_i32(env, argv[4], &op)) return nullptr;
+    if (!get_f64(env, argv[2], &lo) || !get_f64(env, argv[3], &hi)) { napi_throw_type_error(env, nullptr, "selectPlane: lo and hi must be numbers"); return nullptr; }
+    uint32_t count = 0;
+    const int rc = gsr_select_plane(c, plane, lo, hi, op, &count);
+    return rc ? throw_gsr(env, c, rc, "gsr_select_plane") : count_value(env, count);
+}
+
+// planeAlignment(plane: Float64Array(4), axis: Float64Array(3)) -> { q: Float64Array(4) (x, y, z, w), t: Float64Array(3) }   (no handle: a pure function)
+napi_value PlaneAlignment(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    const double *plane = nullptr, *axis = nullptr;
+    if (!get_f64_array(env, argv[0], 4, "planeAlignment: plane must hold 4 values", &plane) ||
+        !get_f64_array(env, argv[1], 3, "planeAlignment: axis must hold 3 values", &axis)) return nullptr;
+    void *q = nullptr, *t = nullptr;
+    napi_value qb, qarr, tb, tarr, out;
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, 32, &q, &qb));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_float64_array, 4, qb, 0, &qarr));
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, 24, &t, &tb));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_float64_array, 3, tb, 0, &tarr));
+    const int rc = gsr_plane_alignment(plane, axis, (double*)q, (double*)t);
+    if (rc) return throw_gsr(env, nullptr, rc, "gsr_plane_alignment");
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "q", qarr));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "t", tarr));
+    return out;
+}
+
 // ---- clusters (gsr_clusters / gsr_select_clusters / gsr_select_cluster_at) ----
 // radius, min_pts, scope and budget of the three calls below (argv[1 .. 4]; the budget a number, 0: the library's default); false:
 // an error is pending
@@ -1856,6 +1994,7 @@ napi_value Init(napi_env env, napi_value exports)
         {"selectContrib", SelectContrib},
         {"attrStats", AttrStats}, {"attrHistogram", AttrHistogram}, {"selectAttr", SelectAttr},
         {"neighbours", Neighbours}, {"selectNeighbours", SelectNeighbours},
+        {"fitPlane", FitPlane}, {"planeInliers", PlaneInliers}, {"selectPlane", SelectPlane}, {"planeAlignment", PlaneAlignment},
         {"clusters", Clusters}, {"selectClusters", SelectClusters}, {"selectClusterAt", SelectClusterAt},
         {"knn", Knn}, {"selectKnn", SelectKnn},
         {"cells", Cells}, {"mergeCells", MergeCells},

@@ -9,6 +9,7 @@
 const path = require("path");
 const { FadeInPass } = require("./FadeInPass");
 const { Vector3 } = require("../math/Vector3");
+const { Quaternion } = require("../math/Quaternion");
 const { Scene } = require("../core/Scene");
 
 let native = null;
@@ -568,6 +569,61 @@ class HIPRenderer {
             if (o2.below !== undefined && (o2.hi !== undefined || o2.lo !== undefined)) throw new Error("selectNeighbours: below goes alone (it is { lo: 0, hi: below })");
             if (!Number.isInteger(lo) || !Number.isInteger(hi) || lo < 0 || lo > hi || hi > cap + 1) throw new Error("selectNeighbours: 0 <= lo <= hi <= cap + 1 must hold");
             return this._n.selectNeighbours(this._h, ...args, lo, hi, code(OPS, o2.op, "replace", "op"));
+        };
+        // ---- planes (gsr_fit_plane / gsr_plane_inliers / gsr_select_plane / gsr_plane_alignment): the floor found, selected by, aligned to ----
+        //   const fit = renderer.fitPlane(0.01);                                           // RANSAC on the device: 512 hypotheses, every one scored in f64
+        //   renderer.selectPlane(fit.plane, { hi: -0.01 }); scene.eraseSelection(renderer.readSelection());   // everything under the floor
+        //   const { rotation, translation } = renderer.planeAlignment(fit.plane); scene.rotate(rotation); scene.translate(translation);   // the floor at y = 0
+        // fitPlane draws `hypotheses` (1 .. 4096, default 512) planes through three splats in scope each -- a counter-based generator
+        // from `seed` -- and scores each by the splats within `threshold` of it (a distance of exactly threshold counts); the largest
+        // score wins, ties go to the smallest index.  plane: Float64Array (nx, ny, nz, d), unit normal; null when nothing was found.
+        // planeInliers scores planes of the host's, used as given.  selectPlane picks lo <= distance <= hi over all splats (within: t is
+        // { lo: -t, hi: t }): after an unscoped fit, selectPlane(plane, { within: threshold }) selects exactly fit.inliers splats.
+        // budget: the most tests (hypotheses x candidates) a call may make (default 2^34); more throws before the scoring pass runs.
+        const planeOf = (plane, what) => {
+            const p = Float64Array.from(plane);
+            if (p.length !== 4) throw new Error(what + ": a plane is (a, b, c, d)");
+            return p;
+        };
+        const planeBudget = (o) => {
+            const budget = o.budget === undefined || o.budget === null ? 0 : Number(o.budget);
+            if (!(budget >= 0)) throw new Error("budget must be a non-negative number");
+            return budget;
+        };
+        this.fitPlane = (threshold, options) => {
+            const o2 = options || {};
+            const hypotheses = o2.hypotheses === undefined ? 512 : o2.hypotheses, seed = o2.seed === undefined ? 0 : o2.seed;
+            if (!Number.isInteger(hypotheses) || hypotheses < 1 || hypotheses > 4096) throw new Error("hypotheses must be an integer in 1 .. 4096");
+            if (!Number.isSafeInteger(seed) || seed < 0) throw new Error("seed must be a non-negative integer");
+            const r = this._n.fitPlane(this._h, Number(threshold), hypotheses, seed, nbScope(o2), planeBudget(o2), !!o2.scores);
+            const out = { plane: r.found ? r.plane : null, found: !!r.found, best: r.best, triple: r.triple, inliers: r.inliers, degenerate: r.degenerate,
+                          inScope: r.inScope, nonfinite: r.nonfinite, hypotheses: r.hypotheses, tests: r.tests };
+            if (o2.scores) out.scores = r.scores;
+            return out;
+        };
+        this.planeInliers = (planes, threshold, options) => {
+            const o2 = options || {};
+            const rows = Array.from(planes, (p) => planeOf(p, "planeInliers"));
+            if (rows.length < 1 || rows.length > 4096) throw new Error("planeInliers: 1 .. 4096 planes");
+            const flat = new Float64Array(4 * rows.length);
+            rows.forEach((p, k) => flat.set(p, 4 * k));
+            return this._n.planeInliers(this._h, flat, rows.length, Number(threshold), nbScope(o2), planeBudget(o2)).inliers;
+        };
+        this.selectPlane = (plane, options) => {
+            const o2 = options || {};
+            if (o2.within !== undefined && (o2.lo !== undefined || o2.hi !== undefined)) throw new Error("selectPlane: within goes alone (it is { lo: -within, hi: within })");
+            const lo = o2.within !== undefined ? -Number(o2.within) : o2.lo === undefined ? -Infinity : Number(o2.lo);
+            const hi = o2.within !== undefined ? Number(o2.within) : o2.hi === undefined ? Infinity : Number(o2.hi);
+            return this._n.selectPlane(this._h, planeOf(plane, "selectPlane"), lo, hi, code(OPS, o2.op, "replace", "op"));
+        };
+        // the whole-scene rotation and translation that take `plane` to axis . p = 0 (axis: default +y), by the library's one
+        // statement of it (a pure function: no device): scene.rotate(rotation); scene.translate(translation) acts on every device copy
+        this.planeAlignment = (plane, options) => {
+            const o2 = options || {}, a = o2.axis === undefined ? [0, 1, 0] : (Array.isArray(o2.axis) || ArrayBuffer.isView(o2.axis) ? o2.axis : [o2.axis.x, o2.axis.y, o2.axis.z]);
+            const axis = Float64Array.from(a);
+            if (axis.length !== 3) throw new Error("planeAlignment: axis is (x, y, z)");
+            const r = this._n.planeAlignment(planeOf(plane, "planeAlignment"), axis);
+            return { rotation: new Quaternion(r.q[0], r.q[1], r.q[2], r.q[3]), translation: new Vector3(r.t[0], r.t[1], r.t[2]) };
         };
         // ---- clusters (gsr_clusters / gsr_select_clusters / gsr_select_cluster_at): the connected islands of splats at a linking radius ----
         //   const p = renderer.pick(x, y); renderer.selectClusterAt(0.05, { seed: p.index });        // the island under the cursor

@@ -112,6 +112,18 @@ class GsrCellInfo(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "pad"}
 
 
+class GsrPlaneInfo(ctypes.Structure):
+    _fields_ = [("in_scope", ctypes.c_uint32), ("nonfinite", ctypes.c_uint32), ("hypotheses", ctypes.c_uint32), ("degenerate", ctypes.c_uint32),
+                ("found", ctypes.c_uint32), ("best", ctypes.c_uint32), ("triple", ctypes.c_uint32 * 3), ("inliers", ctypes.c_uint32),
+                ("tests", ctypes.c_uint64), ("budget", ctypes.c_uint64), ("plane", ctypes.c_double * 4)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k not in ("triple", "plane")}
+        d["triple"] = tuple(int(v) for v in self.triple)
+        d["plane"] = np.array(self.plane, dtype=np.float64)
+        return d
+
+
 class GsrDepthLayout(ctypes.Structure):
     _fields_ = [("format", ctypes.c_int32), ("step", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
                 ("stride", ctypes.c_int32), ("reserved", ctypes.c_int32), ("offset", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
@@ -134,6 +146,7 @@ NEIGHBOUR_MAX_CAP = 4095                                                   # GSR
 NEIGHBOUR_DEFAULT_BUDGET, NEIGHBOUR_MAX_BUDGET = 1 << 34, 1 << 38          # GSR_NEIGHBOUR_*_BUDGET
 KNN_MAX_K, KNN_NONE = 32, 0xffffffff                                       # GSR_KNN_MAX_K, GSR_KNN_NONE (an empty list slot)
 KNN_STATS = {"kth": 0, "mean": 1}                                          # GSR_KNN_*
+PLANE_MAX_HYPOTHESES = 4096                                               # GSR_PLANE_MAX_HYPOTHESES
 CELL_NONE = 0xffffffff                                                     # GSR_CELL_NONE (a leader: the splat is no candidate)
 CLUSTER_NONE = CLUSTER_LARGEST = 0xffffffff                                # GSR_CLUSTER_NONE (a label), GSR_CLUSTER_LARGEST (a seed)
 
@@ -146,6 +159,21 @@ def knn_outlier_threshold(values, std_ratio):
     if v.size < 2:
         return float("inf")
     return float(np.mean(v) + np.float64(std_ratio) * np.std(v, ddof=1))
+
+
+def plane_alignment(plane, axis=(0, 1, 0)):
+    """(q_xyzw float64[4], t float64[3]) of gsr_plane_alignment: the rotation and translation that take `plane` (a, b, c, d) to
+    axis . p = 0.  Needs the library, not a device."""
+    L = load_library()
+    p = np.ascontiguousarray(plane, dtype=np.float64).reshape(4)
+    a = np.ascontiguousarray(axis, dtype=np.float64).reshape(3)
+    q, t = np.zeros(4, np.float64), np.zeros(3, np.float64)
+    rc = L.gsr_plane_alignment(p.ctypes.data, a.ctypes.data, q.ctypes.data, t.ctypes.data)
+    if rc:
+        err = GsplatError("libgsplat_hip error %d: %s" % (rc, L.gsr_last_error(None).decode()))
+        err.code = rc
+        raise err
+    return q, t
 
 
 def attr_edges(lo, hi, bins):
@@ -201,6 +229,7 @@ EXPORTS = [
     "gsr_clusters", "gsr_select_clusters", "gsr_select_cluster_at",
     "gsr_knn", "gsr_select_knn",
     "gsr_cells", "gsr_scene_merge_cells",
+    "gsr_fit_plane", "gsr_plane_inliers", "gsr_select_plane", "gsr_plane_alignment",
     "gsr_set_overlay", "gsr_overlay_async", "gsr_read_overlay", "gsr_read_overlay_rgba8", "gsr_overlay_device_ptr", "gsr_delivery_set_overlay",
     "gsr_set_overlay_outline",
 ]
@@ -378,6 +407,11 @@ def load_library(path=None):
     gi = ctypes.POINTER(GsrCellInfo)
     L.gsr_cells.argtypes = [vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, vp, ctypes.c_uint32, vp, gi]
     L.gsr_scene_merge_cells.argtypes = [vp, ctypes.c_double, ctypes.c_uint32, u64, u32p, gi]
+    pi = ctypes.POINTER(GsrPlaneInfo)
+    L.gsr_fit_plane.argtypes = [vp, ctypes.c_double, ctypes.c_uint32, u64, ctypes.c_uint32, u64, vp, pi]
+    L.gsr_plane_inliers.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, u64, vp, pi]
+    L.gsr_select_plane.argtypes = [vp, vp, ctypes.c_double, ctypes.c_double, ctypes.c_int32, u32p]
+    L.gsr_plane_alignment.argtypes = [vp, vp, vp, vp]
     L.gsr_set_overlay.argtypes = [vp, ctypes.POINTER(GsrOverlayOptions)]
     L.gsr_set_overlay_outline.argtypes = [vp, ctypes.POINTER(GsrOutlineOptions)]
     L.gsr_overlay_async.argtypes = [vp]
@@ -1420,6 +1454,63 @@ class HIPRenderer:
         self._check_neighbours(self._L.gsr_scene_merge_cells(self._ctx, cell, self._scope_flags(scope), budget, ctypes.byref(count), ctypes.byref(info)), info)
         self._n = count.value
         return count.value, info.as_dict()
+
+    # -- planes (gsr_fit_plane / gsr_plane_inliers / gsr_select_plane / gsr_plane_alignment): the floor found, selected by, aligned to --
+    @staticmethod
+    def _plane_args(threshold, count, budget, what):
+        count = int(count)
+        if not 1 <= count <= PLANE_MAX_HYPOTHESES:
+            raise ValueError("%s must be in 1 .. %d" % (what, PLANE_MAX_HYPOTHESES))
+        budget = 0 if budget is None else int(budget)
+        if budget < 0:
+            raise ValueError("budget must not be negative")
+        return float(threshold), count, budget
+
+    def fit_plane(self, threshold, hypotheses=512, seed=0, scope=(), budget=0, scores=False):
+        """(plane, info[, scores]): the dominant plane of the splats in scope -- scope: any of "selected", "visible"; () is every
+        splat -- by RANSAC on the device: `hypotheses` planes through three candidates each, drawn by a counter-based generator
+        from `seed`, every one scored by the candidates within `threshold` of it (f64, a distance of exactly threshold counts);
+        the largest score wins, ties go to the smallest index.  plane: float64[4] (nx, ny, nz, d), unit normal, or None when
+        every hypothesis is degenerate.  info: in_scope, nonfinite, hypotheses, degenerate, found, best, triple, inliers, tests,
+        budget, plane.  scores=True: also uint32[hypotheses].  A call whose tests = hypotheses * candidates lie above the budget
+        (0: the library's default) is refused (GsplatError) before the scoring pass runs, and the error carries `info`."""
+        threshold, hypotheses, budget = self._plane_args(threshold, hypotheses, budget, "hypotheses")
+        sc = np.zeros(hypotheses, np.uint32) if scores else None
+        info = GsrPlaneInfo()
+        self._check_neighbours(self._L.gsr_fit_plane(self._ctx, threshold, hypotheses, int(seed) & 0xffffffffffffffff, self._scope_flags(scope), budget,
+                                                     sc.ctypes.data if scores else None, ctypes.byref(info)), info)
+        d = info.as_dict()
+        plane = d["plane"].copy() if d["found"] else None
+        return (plane, d, sc) if scores else (plane, d)
+
+    def plane_inliers(self, planes, threshold, scope=(), budget=0, info=False):
+        """uint32[K]: for each of the K planes (a, b, c, d) -- used as given, not normalised -- the splats in scope with a finite
+        position within `threshold` of it: fit_plane's scoring pass alone.  info=True: (inliers, info)."""
+        p = np.ascontiguousarray(planes, dtype=np.float64).reshape(-1, 4)
+        threshold, count, budget = self._plane_args(threshold, p.shape[0], budget, "the number of planes")
+        out = np.zeros(count, np.uint32)
+        got = GsrPlaneInfo()
+        self._check_neighbours(self._L.gsr_plane_inliers(self._ctx, p.ctypes.data, count, threshold, self._scope_flags(scope), budget, out.ctypes.data,
+                                                         ctypes.byref(got)), got)
+        return (out, got.as_dict()) if info else out
+
+    def select_plane(self, plane, lo=-np.inf, hi=np.inf, within=None, op="replace"):
+        """Pick the splats whose signed distance s from `plane` has lo <= s <= hi (all splats, hidden ones included; a NaN distance
+        is never picked) and fold them into the selection; returns the selected count.  within=t is lo=-t, hi=t: after a fit over
+        every splat, select_plane(plane, within=threshold) selects exactly info["inliers"] splats; select_plane(plane, hi=-t) is
+        "everything under the floor"."""
+        if within is not None:
+            lo, hi = -float(within), float(within)
+        p = np.ascontiguousarray(plane, dtype=np.float64).reshape(4)
+        count = ctypes.c_uint32(0)
+        self._check(self._L.gsr_select_plane(self._ctx, p.ctypes.data, float(lo), float(hi), self._select_code(SELECT_OPS, op, "op"), ctypes.byref(count)))
+        return count.value
+
+    @staticmethod
+    def plane_alignment(plane, axis=(0, 1, 0)):
+        """(q_xyzw float64[4], t float64[3]): the whole-scene rotation and translation that take `plane` to axis . p = 0 --
+        scene_rotate(q) then scene_translate(t) puts the floor at y = 0.  A pure function of the library's: no device."""
+        return plane_alignment(plane, axis)
 
     # -- selection overlay (gsr_set_overlay / gsr_overlay_async / gsr_read_overlay*): the selected splats tinted --
     def set_overlay(self, tint=(1.0, 0.5, 0.0), mix=0.5):

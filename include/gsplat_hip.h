@@ -1102,6 +1102,80 @@ int gsr_cells(gsr_ctx *ctx, double cell, uint32_t cap, uint32_t scope, uint64_t 
 int gsr_scene_merge_cells(gsr_ctx *ctx, double cell, uint32_t scope, uint64_t budget,
                           uint32_t *new_count, gsr_cell_info *info);
 
+/* ---- planes ---- the dominant plane fitted on the device, the splats near it selected, the scene aligned to it
+ * No interface of the reference stands behind this section either.  The calls above relate splats to each other; these relate
+ * them to a shape, and the first shape every capture needs is its floor, table top or wall: a captured scene arrives tilted and
+ * shifted, with floaters under the ground.  gsr_fit_plane finds the plane by RANSAC on the device, with no gsr_read_scene;
+ * gsr_select_plane picks by signed distance from it ("everything under the floor"); gsr_plane_alignment turns it into the
+ * arguments of gsr_scene_rotate and gsr_scene_translate that put it at axis . p = 0.
+ * Definition ("Planes").  All arithmetic is f64, in the written order, uncontracted; / and the square root
+ *   are correctly rounded.  Scope S is the GSR_SCOPE_SELECTED | GSR_SCOPE_VISIBLE flags of "splat data", with the same meaning; 0
+ *   is every splat.  A candidate is a splat in S whose three position floats are finite; the candidates in ascending index are
+ *   cand[0 .. m-1], and nonfinite = in_scope - m.  Rotation and scale are not read, so a scene without them is accepted.
+ *   Signed distance of a splat at f32 (x, y, z) from the plane (a, b, c, d):
+ *     s = ((a*(double)x + b*(double)y) + c*(double)z) + d
+ *   The plane is used as given: the two calls that take planes from the host do not normalise them.  A splat is within t of the
+ *   plane iff fabs(s) <= t: a distance of exactly t counts.
+ *   Hypothesis h of a fit, 0 <= h < H:
+ *     mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *             return z ^ (z >> 31)            (uint64, wrapping: the splitmix64 finaliser)
+ *     rank(h, j) = mulhi64(mix(seed + 3*h + j), m)   for j = 0, 1, 2     (the high 64 bits of the 128-bit product)
+ *     A, B, C = cand[rank(h, 0..2)];  e1 = B - A, e2 = C - A   (component-wise on the doubles)
+ *     N = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x);  l2 = (Nx*Nx + Ny*Ny) + Nz*Nz
+ *     degenerate if two ranks are equal, if l2 is not finite, or if l2 == 0;  otherwise n = N / sqrt(l2),
+ *     negated when nx < 0 || (nx == 0 && (ny < 0 || (ny == 0 && nz < 0))): the first of nx, ny, nz that is not zero is positive
+ *     (a -0.0 that this leaves behind is part of the result);  d = -((nx*Ax + ny*Ay) + nz*Az)
+ *   score(h) is the number of candidates within threshold of plane h; a degenerate hypothesis scores 0.  The best hypothesis has
+ *   the largest score; ties go to the smallest h.  found = 0 iff every hypothesis is degenerate, which covers m < 3; triple,
+ *   inliers, best and plane are then zeros.  Scores are integers decided by f64 comparisons, so every result is exact and
+ *   independent of the order of arrival.
+ * gsr_fit_plane: scores is `hypotheses` words or NULL; info is required.  tests = hypotheses * m.  An empty scene or an empty
+ *   scope returns GSR_OK with zeros (and the budget) and found = 0; a scope whose splats are all non-finite has hypotheses =
+ *   degenerate = H.
+ * gsr_plane_inliers scores up to 4096 planes of the caller's over the candidates: the scoring pass alone.  A host uses it to
+ *   check a plane it refined itself.  It fills in_scope, nonfinite, tests and budget of info, and hypotheses = count; info may be
+ *   NULL.
+ * gsr_select_plane picks P = { i in [0, n) : lo <= s_i && s_i <= hi } over all splats, hidden ones included -- what
+ *   gsr_select_attr does, but closed at both ends -- and folds P into the selection with `op` (GSR_SELOP_*) exactly as the
+ *   selection calls fold theirs; `selected` means what it means everywhere else.  A non-finite position gives a NaN or infinite
+ *   s; NaN is never picked.  lo and hi may be infinite: (-inf, -t) is "everything under the floor".  NaN or lo > hi is refused.
+ * The consistency guarantee: after a scope-0 fit with found, gsr_select_plane(info.plane, -threshold, threshold,
+ *   GSR_SELOP_REPLACE) selects exactly info.inliers splats; after a fit over GSR_SCOPE_SELECTED with nothing hidden, the same call
+ *   with GSR_SELOP_INTERSECT does too.
+ * gsr_plane_alignment is a pure function with no context: it runs on a machine without a GPU.  It returns the whole-scene
+ *   rotation q (x, y, z, w) and translation t that take the plane to axis . p = 0; the host then calls gsr_scene_rotate(q) and
+ *   gsr_scene_translate(t).  The plane and the axis are each normalised by their own length: n, d = plane / |normal|, a = axis /
+ *   |axis|.  With c = n . a, when c > -1 + 2^-20: v = n x a and q = (vx, vy, vz, 1 + c) divided by its length.  Otherwise q is a
+ *   half turn about n x e, normalised, with e the unit axis of n's smallest component in magnitude (ties go x before y before z)
+ *   and w = 0.  t = d * a.
+ * The work budget.  hypotheses x candidates is a dense kernel on a shared machine.  Both scoring calls list the candidates
+ *   first; if tests > budget the call returns GSR_ERR_ARG with a message naming both numbers; it fills info and launches no scoring
+ *   kernel.  budget == 0 means GSR_NEIGHBOUR_DEFAULT_BUDGET; a budget above GSR_NEIGHBOUR_MAX_BUDGET is refused.
+ * gsr_fit_plane and gsr_plane_inliers are blocking and stateless, and ordered like gsr_select_attr: they wait for every member's
+ *   stream of a shared scene first.  They read the scene and write none of it: no frame state and no selection changes.
+ * Refusals (GSR_ERR_ARG with a message, nothing touched, the selection and its count included): a NULL ctx; a threshold that is
+ *   not finite or < 0; hypotheses or count outside 1 .. 4096; unknown scope flags or op; a NULL required pointer; a supplied
+ *   plane with a non-finite entry or a zero normal; for the alignment, a non-finite entry or a zero plane normal or axis.
+ * The device scratch belongs to the context: the candidate list (4 bytes per splat and 4 per 256 splats), 4096 planes, triples
+ *   and scores, and an info block.  The first call allocates it, it only grows, and gsr_destroy frees it; a context that never
+ *   calls any of this allocates nothing and launches nothing. */
+typedef struct gsr_plane_info {
+    uint32_t in_scope, nonfinite;        /* candidates = in_scope - nonfinite */
+    uint32_t hypotheses, degenerate;
+    uint32_t found, best;                /* best: the winning h */
+    uint32_t triple[3];                  /* its three splat indices */
+    uint32_t inliers;                    /* its score */
+    uint64_t tests, budget;              /* tests = hypotheses * candidates */
+    double plane[4];                     /* (nx, ny, nz, d), unit normal */
+} gsr_plane_info;                        /* 88 bytes; tests at 40, plane at 56 */
+#define GSR_PLANE_MAX_HYPOTHESES 4096u
+int gsr_fit_plane(gsr_ctx *ctx, double threshold, uint32_t hypotheses, uint64_t seed, uint32_t scope,
+                  uint64_t budget, uint32_t *scores /* [hypotheses] or NULL */, gsr_plane_info *info);
+int gsr_plane_inliers(gsr_ctx *ctx, const double *planes /* [count][4] */, uint32_t count, double threshold,
+                      uint32_t scope, uint64_t budget, uint32_t *inliers /* [count] */, gsr_plane_info *info);
+int gsr_select_plane(gsr_ctx *ctx, const double *plane /* [4] */, double lo, double hi, int32_t op, uint32_t *selected);
+int gsr_plane_alignment(const double *plane, const double *axis /* [3] */, double *q_xyzw, double *t /* [3] */);
+
 /* ---- selection overlay ---- the selected splats tinted, in read-backs and in delivered frames
  * No interface of the reference stands behind this section either.  gsr_read_selection returns bits; this shows them: a second
  * image beside the frame in which the selected splats carry a tint, and per pixel how much of it they are.

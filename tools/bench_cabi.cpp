@@ -3,7 +3,7 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--merge CELL] [--share-scene]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--plane THRESHOLD[:HYPOTHESES]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--merge CELL] [--share-scene]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
@@ -44,6 +44,10 @@
 // wall time, and by the library's events on the stream the index build (with its bound) and the count pass apart; pair_bound and
 // the pair tests per second it means for the count pass, the median count, the splats with fewer than three neighbours, and the
 // check that gsr_select_neighbours(lo 0, hi 3) selects exactly hist[0] + hist[1] + hist[2].
+// --plane THRESHOLD[:HYPOTHESES] (512 hypotheses unless given) fits the scene's dominant plane: five gsr_fit_plane calls, the best
+// wall time, and by the library's events on the stream the candidate pass and the scoring pass apart; the tests and the tests per
+// second they mean for the scoring pass, the winner's inliers, and the check that gsr_select_plane(plane, -THRESHOLD, THRESHOLD)
+// selects exactly that many splats (`fit_equals_selection`).
 // --clusters RADIUS[:MIN_PTS] (min_pts 0 unless given) labels the islands of the scene at the linking radius: five gsr_clusters calls,
 // the best wall time, and by the library's events on the stream the stages apart -- the index with its bound, the core test with the
 // seed, union with flatten, border with sizes; clusters, largest_size and noise, and the check that gsr_select_clusters(0, 10)
@@ -166,6 +170,7 @@ uint64_t fnv1a(const void* p, size_t bytes)
 }
 
 extern "C" int gsr_debug_neighbour_times(gsr_ctx* ctx, float* out /* build_ms, count_ms */);   // not part of the ABI (gsr_neighbours.cpp)
+extern "C" int gsr_debug_plane_times(gsr_ctx* ctx, float* out /* candidates_ms, score_ms */);   // not part of the ABI (gsr_plane.cpp)
 extern "C" int gsr_debug_knn_times(gsr_ctx* ctx, float* out /* index_ms, walk_ms */);   // not part of the ABI (gsr_knn.cpp)
 extern "C" int gsr_debug_cluster_times(gsr_ctx* ctx, float* out /* index_ms, core_ms, union_ms, border_ms */);   // not part of the ABI (gsr_clusters.cpp)
 
@@ -200,6 +205,8 @@ int main(int argc, char** argv)
     uint32_t histogram_bins = 256;
     double nb_radius = 0.0;             // 0: off
     uint32_t nb_cap = 64;
+    double plane_threshold = -1.0;      // < 0: off
+    uint32_t plane_hypotheses = 512;
     double cl_radius = 0.0;             // 0: off
     uint32_t cl_min_pts = 0;
     double knn_radius = 0.0;            // 0: off
@@ -241,6 +248,13 @@ int main(int argc, char** argv)
             if (colon != std::string::npos) nb_cap = (uint32_t)std::atoi(v.c_str() + colon + 1);
             if (!(nb_radius > 0.0) || nb_cap < 1 || nb_cap > GSR_NEIGHBOUR_MAX_CAP) { std::fprintf(stderr, "--neighbours RADIUS[:CAP]: RADIUS > 0, CAP in 1 .. 4095\n"); return 2; }
         }
+        else if (a == "--plane" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            const size_t colon = v.find(':');
+            plane_threshold = std::atof(v.c_str());
+            if (colon != std::string::npos) plane_hypotheses = (uint32_t)std::atoi(v.c_str() + colon + 1);
+            if (!(plane_threshold >= 0.0) || plane_hypotheses < 1 || plane_hypotheses > GSR_PLANE_MAX_HYPOTHESES) { std::fprintf(stderr, "--plane THRESHOLD[:HYPOTHESES]: THRESHOLD >= 0, HYPOTHESES in 1 .. 4096\n"); return 2; }
+        }
         else if (a == "--clusters" && i + 1 < argc) {
             const std::string v = argv[++i];
             const size_t colon = v.find(':');
@@ -265,7 +279,7 @@ int main(int argc, char** argv)
         else if (a == "--scene-edit") scene_edit = next();
         else if (a == "--share-scene") share_scene = true;
         else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--merge CELL] [--share-scene]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--plane THRESHOLD[:HYPOTHESES]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--merge CELL] [--share-scene]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
@@ -680,6 +694,26 @@ int main(int argc, char** argv)
         CHECK(gsr_select_neighbours(ctx[0], nb_radius, nb_cap, 0, 0, 0, std::min(3u, nb_cap + 1u), GSR_SELOP_REPLACE, &nb_selected, nullptr));
         nb_select_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3;
     }
+    // --plane: the dominant plane, the stages timed apart, the winner's score checked against the picker
+    gsr_plane_info pl_info{};
+    double pl_ms = 1e30, pl_cand_ms = 1e30, pl_score_ms = 1e30, pl_select_ms = 0;
+    uint32_t pl_selected = 0;
+    if (plane_threshold >= 0.0) {
+        ctx0 = ctx[0];
+        for (int t = 0; t < 5; t++) {
+            const auto t0 = std::chrono::steady_clock::now();
+            CHECK(gsr_fit_plane(ctx[0], plane_threshold, plane_hypotheses, 0, 0, 0, nullptr, &pl_info));
+            pl_ms = std::min(pl_ms, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3);
+            float stage[2] = {0, 0};
+            CHECK(gsr_debug_plane_times(ctx[0], stage));
+            pl_cand_ms = std::min(pl_cand_ms, (double)stage[0]); pl_score_ms = std::min(pl_score_ms, (double)stage[1]);
+        }
+        if (pl_info.found) {
+            const auto t0 = std::chrono::steady_clock::now();
+            CHECK(gsr_select_plane(ctx[0], pl_info.plane, -plane_threshold, plane_threshold, GSR_SELOP_REPLACE, &pl_selected));
+            pl_select_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3;
+        }
+    }
     // --clusters: the islands at the linking radius, the stages timed apart, the small-island pick checked against the sizes
     gsr_cluster_info cl_info{};
     double cl_ms = 1e30, cl_stage_ms[4] = {1e30, 1e30, 1e30, 1e30}, cl_select_ms = 0;
@@ -829,6 +863,14 @@ int main(int argc, char** argv)
                     "\"select_attr_ms\": %.4f, \"range\": [%u, %u], \"sum_counts\": %llu, \"selected\": %u, \"histogram_equals_selection\": %s}",
                     histogram_attr.c_str(), histogram_bins, hist_count, hist_nan, json_num(hist_min).c_str(), json_num(hist_max).c_str(), hist_lo, hist_hi, hist_outside[0], hist_outside[1], hist_outside[2],
                     hist_peak, hist_ms[0], hist_ms[1], hist_ms[2], hist_a, hist_b, hist_sum, hist_selected, hist_sum == hist_selected ? "true" : "false");
+    if (plane_threshold >= 0.0)
+        std::printf(", \"plane\": {\"threshold\": %.17g, \"hypotheses\": %u, \"in_scope\": %u, \"nonfinite\": %u, \"degenerate\": %u, \"found\": %u, \"best\": %u, "
+                    "\"tests\": %llu, \"budget\": %llu, \"fit_plane_ms\": %.4f, \"candidates_ms\": %.4f, \"score_ms\": %.4f, \"tests_per_s\": %.4g, \"inliers\": %u, "
+                    "\"plane\": [%.17g, %.17g, %.17g, %.17g], \"select_plane_ms\": %.4f, \"selected\": %u, \"fit_equals_selection\": %s}",
+                    plane_threshold, plane_hypotheses, pl_info.in_scope, pl_info.nonfinite, pl_info.degenerate, pl_info.found, pl_info.best,
+                    (unsigned long long)pl_info.tests, (unsigned long long)pl_info.budget, pl_ms, pl_cand_ms, pl_score_ms,
+                    pl_score_ms > 0.0 ? (double)pl_info.tests / (pl_score_ms * 1e-3) : 0.0, pl_info.inliers, pl_info.plane[0], pl_info.plane[1], pl_info.plane[2],
+                    pl_info.plane[3], pl_select_ms, pl_selected, pl_info.found && pl_selected == pl_info.inliers ? "true" : "false");
     if (nb_radius > 0.0)
         std::printf(", \"neighbours\": {\"radius\": %.17g, \"cap\": %u, \"n\": %u, \"in_scope\": %u, \"nonfinite\": %u, \"pair_bound\": %llu, \"budget\": %llu, "
                     "\"neighbours_ms\": %.4f, \"index_build_ms\": %.4f, \"count_ms\": %.4f, \"pair_tests_per_s\": %.4g, \"median_count\": %u, "
