@@ -178,6 +178,7 @@ int gsr_destroy(gsr_ctx* c)
     for (auto& e : c->cl.ev) if (e) (void)hipEventDestroy(e);
     if (c->knn.ev) (void)hipEventDestroy(c->knn.ev);
     for (auto& e : c->pl.ev) if (e) (void)hipEventDestroy(e);
+    for (auto& e : c->mt.ev) if (e) (void)hipEventDestroy(e);
     if (c->words.fstate_host) (void)hipHostFree(c->words.fstate_host);
     if (c->words.mailbox) (void)hipHostFree(c->words.mailbox);
     if (c->stream) (void)hipStreamDestroy(c->stream);

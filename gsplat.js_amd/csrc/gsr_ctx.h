@@ -570,6 +570,21 @@ struct gsr_ctx {
         float candidates_ms = 0.0f, score_ms = 0.0f;      // of the last call that ran both (gsr_debug_plane_times)
     } pl;
 
+    // matching and registration (gsr_match.cpp): what gsr_match / gsr_select_match / gsr_register hold beside the neighbour scratch
+    // (which they size for the TARGET's count), the context's own; the first such call allocates it, it only grows, and the
+    // context's end frees it
+    struct Match {
+        gsr::DevBuf<uint32_t> words;            // MATCH_INFO_WORDS of MatchInfo
+        gsr::DevBuf<uint32_t> idx;              // `rows` each: the match and its squared distance by source splat
+        gsr::DevBuf<double> d2;
+        uint32_t rows = 0;
+        gsr::DevBuf<double> tree;               // `tree_rows` rows of MATCH_ROW doubles: the partial rows of every level (calls that ask for sums)
+        uint64_t tree_rows = 0;
+        hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // around the index; in front of a step's bound, behind it, behind the walk, the tree
+        float ms[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // of the last call: the index; bound, walk, tree of its last step; their sums over
+                                                                          // its steps; the steps (gsr_debug_match_times)
+    } mt;
+
     // frame delivery (gsr_delivery_open): a ring of pinned host blocks, each with its device staging and "copy done" event
     struct Delivery {
         struct Slot {
@@ -707,6 +722,9 @@ int nb_index(gsr_ctx* c, const char* who, double radius, uint32_t cap, uint32_t 
 // nb_index's first step, for a caller with cells of its own (gsr_merge.cpp): the context's scratch for the scene's n splats, *ix
 // over it with the given inv_h and r2, the words of NbInfo and cap + 1 histogram counters (*hist) and the table zeroed on the stream
 int nb_prepare(gsr_ctx* c, const char* who, uint32_t cap, double inv_h, double r2, NbIndex* ix, uint32_t** hist);
+// the same for n rows that need not be the context's own scene's (n >= 1): the caller names the arrays to index when it builds
+// (gsr_match.cpp indexes ANOTHER context's scene into this context's scratch)
+int nb_prepare_rows(gsr_ctx* c, const char* who, uint32_t n, uint32_t cap, double inv_h, double r2, NbIndex* ix, uint32_t** hist);
 // gsr_contrib.cpp: what the blocking calls that read per-splat state of a scene do first: waits for every member's stream, so
 // that nothing of any member (a contribution pass, an edit) is in flight afterwards
 int settle_members(gsr_ctx* c);

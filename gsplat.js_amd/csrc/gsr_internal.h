@@ -737,6 +737,48 @@ void launch_plane_best(uint32_t hypotheses, const PlArrays& a, hipStream_t s);
 void launch_plane_select(const float* px, const float* py, const float* pz, uint32_t n, double4 plane, double lo, double hi, uint32_t* scratch, uint32_t nwords,
                          hipStream_t s);
 
+// Matching and registration (k_match.hip; DESIGN.md section 4, "Matching and registration"): for every splat in scope of a SOURCE
+// scene under a trial transform, the nearest indexed splat of a TARGET scene within `radius`, by the pair (d2, index), over the
+// index above built on the target; the sums a rigid solve needs, by a fixed tree; and the splats of a distance range as a picker.
+constexpr uint32_t MATCH_NONE = 0xffffffffu;                // GSR_MATCH_NONE: an unmatched splat
+constexpr uint32_t MATCH_ROW = 16;                          // doubles of a row of sums: T, Q, T_a * Q_b for ab = 00 .. 22, d2
+constexpr uint32_t MATCH_GROUP = 256;                       // rows one workgroup of the tree reduces to one
+struct MatchXf { double m[12]; };                           // row-major 3 x 4 (R | t)
+// the source side of a call: the positions of its n splats, its scope and the trial transform
+struct MatchSource {
+    const float *px, *py, *pz;
+    AttrScope sc;
+    uint32_t n;
+    MatchXf xf;
+};
+// the device words of one step, zeroed by the host in front of the bound.  Squared distances are non-negative doubles, so their
+// bit patterns order as unsigned integers (KnnInfo): d2max is the largest pattern, nd2min the largest COMPLEMENT of one.
+struct MatchInfo {
+    uint32_t in_scope, nonfinite;          // source splats in scope; of those, with a non-finite position or transformed point
+    uint32_t matched, pad;
+    unsigned long long nd2min, d2max;
+    unsigned long long pair_bound;         // k_match_bound's sum
+};
+// rows of every level of the tree over n >= 1 rows: ceil(n / 256), ceil of that / 256, .. down to 1; the return value is their sum
+inline uint64_t match_tree_rows(uint32_t n)
+{
+    uint64_t total = 0, rows = n;
+    do { rows = (rows + MATCH_GROUP - 1u) / MATCH_GROUP; total += rows; } while (rows > 1u);
+    return total;
+}
+// info->in_scope, nonfinite, and pair_bound += for every query the populations of the 27 buckets the walk visits for it
+void launch_match_bound(const NbIndex& ix, const MatchSource& src, MatchInfo* info, int cu_count, hipStream_t s);
+// idx[i], d2[i] for every source splat: the match, (MATCH_NONE, +inf) without one, (MATCH_NONE, NaN) outside the scope;
+// info->matched, nd2min, d2max.  indexed: the target index's entries as the host read them.
+void launch_match(const NbIndex& ix, uint32_t indexed, const MatchSource& src, uint32_t* idx, double* d2, MatchInfo* info, int cu_count, hipStream_t s);
+// the tree: level 1 rebuilds every row from idx[] and d2[] (the transformed point again, the target's position gathered; tn: the
+// target's splats), every level reduces groups of MATCH_GROUP rows; partial: match_tree_rows(n) rows of MATCH_ROW doubles, the
+// levels one behind the other; the result is the last row.  n >= 1.
+void launch_match_tree(const MatchSource& src, const float* qx, const float* qy, const float* qz, uint32_t tn, const uint32_t* idx, const double* d2,
+                       double* partial, hipStream_t s);
+// scratch <- the source splats i < n in scope with lo <= sqrt(d2[i]) && (sqrt(d2[i]) < hi || open_hi): every word of it is stored
+void launch_match_select(const double* d2, const AttrScope& sc, uint32_t n, double lo, double hi, bool open_hi, uint32_t* scratch, uint32_t nwords, hipStream_t s);
+
 // Selection overlay (k_overlay.hip; DESIGN.md section 4, "Selection overlay"): the last frame's bin lists walked once more, the
 // weight w = T * B of every fragment of a SELECTED splat summed per pixel (cover) and, with the splat's colour, turned into the
 // frame with those splats tinted (overlay).  Reads the framebuffer, never writes it.

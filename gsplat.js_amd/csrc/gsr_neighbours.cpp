@@ -60,12 +60,17 @@ int nb_ensure(gsr_ctx* c, uint32_t n, uint64_t buckets)
 
 }  // namespace
 
-// nb_prepare: the scratch, the index's description and its zeroed words and table.  nb_index: on top of it,
+// nb_prepare_rows: the scratch for n rows (the scene's, or those of another scene that gsr_match.cpp indexes), the index's
+// description and its zeroed words and table; nb_prepare: the same for the context's own scene.  nb_index: on top of it,
 // everything up to the count pass: the index, its bound against the budget, *info.  GSR_ERR_ARG (with *info filled) when the
 // bound is above the budget: no count kernel has been launched.  n >= 1; the device is current and no member's stream holds work.
 int gsr::nb_prepare(gsr_ctx* c, const char* who, uint32_t cap, double inv_h, double r2, NbIndex* ix, uint32_t** hist)
 {
-    const uint32_t n = c->scene->n;
+    return nb_prepare_rows(c, who, c->scene->n, cap, inv_h, r2, ix, hist);
+}
+
+int gsr::nb_prepare_rows(gsr_ctx* c, const char* who, uint32_t n, uint32_t cap, double inv_h, double r2, NbIndex* ix, uint32_t** hist)
+{
     if (n > NB_MAX_ROWS) return fail(c, GSR_ERR_ARG, "%s: the scene has %u splats; at most %u are indexed", who, n, NB_MAX_ROWS);
     uint64_t buckets = 256;   // a power of two, a multiple of k_nb_offsets' workgroup, at least twice the splats
     while (buckets < 2ull * n) buckets <<= 1;

@@ -8,7 +8,9 @@
 // of +-1 cell would miss a pair the definition counts.  Multiplying by one constant, floor and the clamp are all monotone, and
 // 2^-10 of slack is far more than the product's rounding error anywhere inside the clamp (2^20 * 2^-53), so two splats within
 // `radius` of each other are never more than one cell apart on any axis: the 27-cell walk is complete.  Everything at or beyond
-// the clamp shares the boundary cell, which costs pair tests and no pair.
+// the clamp shares the boundary cell, which costs pair tests and no pair.  Nothing in the argument needs the multiplied value to
+// have been a float: it holds unchanged for a query point given as a double (nb_cell_query, k_neighbours.h), which is how
+// k_match.hip finds the cell of a splat of another scene under a trial transform.
 //
 // Index.  A hashed grid -- floaters are exactly what stretches a bounding box, so nothing dense -- built as a counting sort by
 // bucket: k_nb_cells<false> counts the splats of every bucket with one relaxed atomic each, k_nb_offsets gives every bucket its

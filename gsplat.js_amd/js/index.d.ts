@@ -104,6 +104,13 @@ export type Plane = ArrayLike<number>;   // (a, b, c, d): a . x + b . y + c . z 
 export interface PlaneFitOptions { hypotheses?: number; seed?: number; scope?: NeighbourScope | NeighbourScope[]; budget?: number; scores?: boolean }
 export interface PlaneFit { plane: Float64Array | null; found: boolean; best: number; triple: Uint32Array; inliers: number; degenerate: number; inScope: number;
     nonfinite: number; hypotheses: number; tests: number; scores?: Uint32Array }
+export type RigidTransform = ArrayLike<number>;   // 12 numbers, row-major 3 x 4 (R | t)
+export interface MatchOptions { transform?: RigidTransform | null; scope?: NeighbourScope | NeighbourScope[]; targetScope?: NeighbourScope | NeighbourScope[]; budget?: number }
+export interface SceneMatch { idx: Uint32Array; d2: Float64Array; inScope: number; nonfinite: number; targetIndexed: number; matched: number; pairBound: number;
+    d2Min: number; d2Max: number; pairs?: number; sums?: Float64Array }
+export type RegisterStatus = "converged" | "max_iterations" | "too_few";
+export interface Registration { transform: Float64Array; rotation: Quaternion; translation: Vector3; status: RegisterStatus; iterations: number; pairs: number;
+    rms: number; stepPairs?: Float64Array; stepRms?: Float64Array }
 export interface ClusterOptions { minPts?: number; scope?: NeighbourScope | NeighbourScope[]; budget?: number }
 export interface SplatClusters { labels: Uint32Array; sizes: Uint32Array; inScope: number; nonfinite: number; pairBound: number; core: number; border: number;
     noise: number; clusters: number; largestLabel: number; largestSize: number }
@@ -412,6 +419,21 @@ export class HIPRenderer {
     planeInliers(planes: ArrayLike<Plane>, threshold: number, options?: { scope?: NeighbourScope | NeighbourScope[]; budget?: number }): Uint32Array;
     selectPlane(plane: Plane, options?: { within?: number; lo?: number; hi?: number; op?: SelectOp }): number;
     planeAlignment(plane: Plane, options?: { axis?: ArrayLike<number> | Vector3 }): { rotation: Quaternion; translation: Vector3 };
+    /** Matching and registration: matchScene finds, for every splat in scope moved by `transform` (12 numbers, row-major 3 x 4
+     *  (R | t); default the identity), the nearest splat of `target`'s scene in targetScope within `radius` -- f64, smallest in
+     *  (squared distance, index), a distance of exactly radius counts: idx[i] its index (0xffffffff without one), d2[i] the squared
+     *  distance (Infinity without one, NaN outside the scope); sums: true adds pairs and the 16 sums a rigid solve takes.  selectMatch
+     *  picks lo <= distance < hi (hi undefined or Infinity: no upper end, the unmatched splats included) and folds them into the
+     *  selection with `op`: { hi: r } is what the other capture already has, { lo: r } what it lacks.  registerTo iterates match,
+     *  reduce and solve from `transform` and returns the rigid transform that takes this scene onto the target's, with its rotation
+     *  and translation: scene.rotate(rotation); scene.translate(translation).  It stops "converged" when a step moves no entry by more
+     *  than `tolerance` (default 2^-40), "too_few" when a step matches fewer than 3 splats, "max_iterations" after maxIterations
+     *  (1 .. 256, default 32) steps; history: true adds every step's pairs and rms.  Neither device scene is written, and the same
+     *  scenes give the same bits on every run.  rigidDecompose splits any such transform.  budget as splatNeighbours. */
+    matchScene(target: HIPRenderer, radius: number, options?: MatchOptions & { sums?: boolean }): SceneMatch;
+    selectMatch(target: HIPRenderer, radius: number, options?: MatchOptions & { lo?: number; hi?: number; op?: SelectOp }): number;
+    registerTo(target: HIPRenderer, radius: number, options?: MatchOptions & { maxIterations?: number; tolerance?: number; history?: boolean }): Registration;
+    rigidDecompose(transform: RigidTransform): { rotation: Quaternion; translation: Vector3 };
     /** Clusters: the connected islands of the splats in scope at the linking radius `radius` (f64, distance exactly radius links).
      *  minPts (0 .. 4095, default 0: plain connected components) makes it DBSCAN: a splat with minPts or more others within radius is
      *  core, core splats within radius of each other share a cluster, a non-core splat beside a core one takes the smallest such

@@ -1628,6 +1628,159 @@ napi_value PlaneAlignment(napi_env env, napi_callback_info info)
     return out;
 }
 
+// ---- matching and registration (gsr_match / gsr_select_match / gsr_register / gsr_rigid_decompose) ----
+// what the three calls share, at argv[1 .. 6]: the target's handle, the transform (Float64Array(12), or null for the identity),
+// radius, scope, target scope and budget (a number, 0: the library's default); false: an error is pending
+struct MatchArgs { gsr_ctx* target; const double* M; double radius; uint32_t scope, target_scope; uint64_t budget; };
+bool get_match_args(napi_env env, napi_value* argv, MatchArgs* a)
+{
+    a->target = get_ctx(env, argv[1]);
+    if (!a->target) return false;
+    void* data = nullptr;
+    size_t len = 0;
+    if (!get_typed(env, argv[2], napi_float64_array, &data, &len, true)) return false;
+    if (data && len < 12) { napi_throw_range_error(env, nullptr, "match: transform must hold 12 values"); return false; }
+    a->M = (const double*)data;
+    double b;
+    if (!get_f64(env, argv[3], &a->radius) || napi_get_value_uint32(env, argv[4], &a->scope) != napi_ok || napi_get_value_uint32(env, argv[5], &a->target_scope) != napi_ok ||
+        !get_f64(env, argv[6], &b)) {
+        napi_throw_type_error(env, nullptr, "match: radius, scope, targetScope and budget must be numbers");
+        return false;
+    }
+    if (!(b >= 0.0 && b <= 18446744073709549568.0)) { napi_throw_range_error(env, nullptr, "match: budget must be a non-negative number"); return false; }
+    a->budget = (uint64_t)b;
+    return true;
+}
+
+// a Float64Array of `count` values over a fresh buffer; *data: its storage
+napi_value new_f64_array(napi_env env, size_t count, void** data)
+{
+    napi_value ab, arr;
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, count * 8, data, &ab));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_float64_array, count, ab, 0, &arr));
+    return arr;
+}
+
+// matchScene(handle, target, transform | null, radius, scope, targetScope, budget, wantSums) -> { idx: Uint32Array(n), d2: Float64Array(n), inScope, nonfinite,
+//   targetIndexed, matched, pairBound, budget, d2Min, d2Max[, pairs, sums: Float64Array(16)] }
+napi_value MatchScene(napi_env env, napi_callback_info info)
+{
+    napi_value argv[8];
+    if (!get_args(env, info, 8, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    MatchArgs a;
+    bool want = false;
+    uint32_t n = 0;
+    if (!c || !get_match_args(env, argv, &a)) return nullptr;
+    if (napi_get_value_bool(env, argv[7], &want) != napi_ok) { napi_throw_type_error(env, nullptr, "matchScene: sums must be a boolean"); return nullptr; }
+    int rc = gsr_scene_count(c, &n);
+    if (rc) return throw_gsr(env, c, rc, "gsr_scene_count");
+    void *idx = nullptr, *d2 = nullptr, *sum = nullptr;
+    napi_value ib, iarr, darr, sarr = nullptr, out;
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, (size_t)n * 4, &idx, &ib));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_uint32_array, n, ib, 0, &iarr));
+    if (!(darr = new_f64_array(env, n, &d2))) return nullptr;
+    if (want && !(sarr = new_f64_array(env, 16, &sum))) return nullptr;
+    gsr_match_info mi{};
+    gsr_match_sums ms{};
+    rc = gsr_match(c, a.target, a.M, a.radius, a.scope, a.target_scope, a.budget, n ? (uint32_t*)idx : nullptr, n ? (double*)d2 : nullptr, n, want ? &ms : nullptr, &mi);
+    if (rc) return throw_gsr(env, c, rc, "gsr_match");
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "idx", iarr));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "d2", darr));
+    if (want) {
+        std::memcpy(sum, ms.sum, sizeof ms.sum);
+        NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "sums", sarr));
+        if (!set_f64(env, out, "pairs", (double)ms.pairs)) return nullptr;
+    }
+    if (!set_u32(env, out, "inScope", mi.in_scope) || !set_u32(env, out, "nonfinite", mi.nonfinite) || !set_u32(env, out, "targetIndexed", mi.target_indexed) ||
+        !set_u32(env, out, "matched", mi.matched) || !set_f64(env, out, "pairBound", (double)mi.pair_bound) || !set_f64(env, out, "budget", (double)mi.budget) ||
+        !set_f64(env, out, "d2Min", mi.d2_min) || !set_f64(env, out, "d2Max", mi.d2_max)) return nullptr;
+    return out;
+}
+
+// selectMatch(handle, target, transform | null, radius, scope, targetScope, budget, lo, hi, op) -> selected
+napi_value SelectMatch(napi_env env, napi_callback_info info)
+{
+    napi_value argv[10];
+    if (!get_args(env, info, 10, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    MatchArgs a;
+    double lo, hi;
+    int32_t op;
+    if (!c || !get_match_args(env, argv, &a)) return nullptr;
+    if (!get_f64(env, argv[7], &lo) || !get_f64(env, argv[8], &hi) || !get_i32(env, argv[9], &op)) {
+        napi_throw_type_error(env, nullptr, "selectMatch: lo, hi and op must be numbers");
+        return nullptr;
+    }
+    uint32_t count = 0;
+    const int rc = gsr_select_match(c, a.target, a.M, a.radius, a.scope, a.target_scope, a.budget, lo, hi, op, &count, nullptr);
+    return rc ? throw_gsr(env, c, rc, "gsr_select_match") : count_value(env, count);
+}
+
+// registerTo(handle, target, transform | null, radius, scope, targetScope, budget, maxIterations, tolerance, history) -> { transform: Float64Array(12),
+//   q: Float64Array(4) (x, y, z, w), t: Float64Array(3), status, iterations, pairs, rms, delta[, stepPairs: Float64Array, stepRms: Float64Array] }
+napi_value RegisterTo(napi_env env, napi_callback_info info)
+{
+    napi_value argv[10];
+    if (!get_args(env, info, 10, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    MatchArgs a;
+    uint32_t steps;
+    double tolerance;
+    bool history = false;
+    if (!c || !get_match_args(env, argv, &a)) return nullptr;
+    if (napi_get_value_uint32(env, argv[7], &steps) != napi_ok || !get_f64(env, argv[8], &tolerance) || napi_get_value_bool(env, argv[9], &history) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "registerTo: maxIterations and tolerance must be numbers, history a boolean");
+        return nullptr;
+    }
+    if (steps < 1 || steps > GSR_REGISTER_MAX_ITERATIONS_LIMIT) { napi_throw_range_error(env, nullptr, "registerTo: maxIterations must be in 1 .. 256"); return nullptr; }
+    void *M = nullptr, *q = nullptr, *t = nullptr;
+    napi_value marr, qarr, tarr, out;
+    if (!(marr = new_f64_array(env, 12, &M)) || !(qarr = new_f64_array(env, 4, &q)) || !(tarr = new_f64_array(env, 3, &t))) return nullptr;
+    uint64_t step_pairs[GSR_REGISTER_MAX_ITERATIONS_LIMIT];
+    double step_rms[GSR_REGISTER_MAX_ITERATIONS_LIMIT];
+    gsr_register_info ri{};
+    if (history) { ri.step_pairs = step_pairs; ri.step_rms = step_rms; ri.step_rows = steps; }
+    int rc = gsr_register(c, a.target, a.M, a.radius, a.scope, a.target_scope, a.budget, steps, tolerance, (double*)M, &ri);
+    if (rc) return throw_gsr(env, c, rc, "gsr_register");
+    rc = gsr_rigid_decompose((const double*)M, (double*)q, (double*)t);
+    if (rc) return throw_gsr(env, nullptr, rc, "gsr_rigid_decompose");
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "transform", marr));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "q", qarr));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "t", tarr));
+    if (history) {
+        void *sp = nullptr, *sr = nullptr;
+        napi_value sparr, srarr;
+        if (!(sparr = new_f64_array(env, ri.iterations, &sp)) || !(srarr = new_f64_array(env, ri.iterations, &sr))) return nullptr;
+        for (uint32_t k = 0; k < ri.iterations; k++) { ((double*)sp)[k] = (double)step_pairs[k]; ((double*)sr)[k] = step_rms[k]; }
+        NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "stepPairs", sparr));
+        NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "stepRms", srarr));
+    }
+    if (!set_u32(env, out, "status", (uint32_t)ri.status) || !set_u32(env, out, "iterations", ri.iterations) || !set_f64(env, out, "pairs", (double)ri.pairs) ||
+        !set_f64(env, out, "rms", ri.rms) || !set_f64(env, out, "delta", ri.delta)) return nullptr;
+    return out;
+}
+
+// rigidDecompose(transform: Float64Array(12)) -> { q: Float64Array(4) (x, y, z, w), t: Float64Array(3) }   (no handle: a pure function)
+napi_value RigidDecompose(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    const double* M = nullptr;
+    if (!get_f64_array(env, argv[0], 12, "rigidDecompose: transform must hold 12 values", &M)) return nullptr;
+    void *q = nullptr, *t = nullptr;
+    napi_value qarr, tarr, out;
+    if (!(qarr = new_f64_array(env, 4, &q)) || !(tarr = new_f64_array(env, 3, &t))) return nullptr;
+    const int rc = gsr_rigid_decompose(M, (double*)q, (double*)t);
+    if (rc) return throw_gsr(env, nullptr, rc, "gsr_rigid_decompose");
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "q", qarr));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "t", tarr));
+    return out;
+}
+
 // ---- clusters (gsr_clusters / gsr_select_clusters / gsr_select_cluster_at) ----
 // radius, min_pts, scope and budget of the three calls below (argv[1 .. 4]; the budget a number, 0: the library's default); false:
 // an error is pending
@@ -1995,6 +2148,7 @@ napi_value Init(napi_env env, napi_value exports)
         {"attrStats", AttrStats}, {"attrHistogram", AttrHistogram}, {"selectAttr", SelectAttr},
         {"neighbours", Neighbours}, {"selectNeighbours", SelectNeighbours},
         {"fitPlane", FitPlane}, {"planeInliers", PlaneInliers}, {"selectPlane", SelectPlane}, {"planeAlignment", PlaneAlignment},
+        {"matchScene", MatchScene}, {"selectMatch", SelectMatch}, {"registerTo", RegisterTo}, {"rigidDecompose", RigidDecompose},
         {"clusters", Clusters}, {"selectClusters", SelectClusters}, {"selectClusterAt", SelectClusterAt},
         {"knn", Knn}, {"selectKnn", SelectKnn},
         {"cells", Cells}, {"mergeCells", MergeCells},

@@ -625,6 +625,62 @@ class HIPRenderer {
             const r = this._n.planeAlignment(planeOf(plane, "planeAlignment"), axis);
             return { rotation: new Quaternion(r.q[0], r.q[1], r.q[2], r.q[3]), translation: new Vector3(r.t[0], r.t[1], r.t[2]) };
         };
+        // ---- matching and registration (gsr_match / gsr_select_match / gsr_register): this renderer's scene matched to another's, aligned with it ----
+        //   const fit = renderer.registerTo(other, 0.25); scene.rotate(fit.rotation); scene.translate(fit.translation);   // this capture onto the other one
+        //   renderer.selectMatch(other, 0.05, { lo: 0.05 });                                // what the other capture lacks: no splat of it within 0.05
+        //   const { idx, d2 } = renderer.matchScene(other, 0.05);                           // per splat: the nearest splat of `other`, 0xffffffff / Infinity without one
+        // For every splat in scope, moved by `transform` (12 numbers, row-major 3 x 4 (R | t); default the identity), the nearest splat of
+        // `target`'s scene in targetScope within `radius` (f64, smallest in (squared distance, index), a distance of exactly radius counts);
+        // NaN outside the scope.  sums: true adds { pairs, sums: Float64Array(16) }, what a rigid solve takes.  selectMatch picks
+        // lo <= distance < hi (hi undefined or Infinity: no upper end, the unmatched splats included).  registerTo iterates match, reduce
+        // and solve from `transform` and returns the rigid transform that takes this scene onto the target's -- status "converged",
+        // "max_iterations" or "too_few" -- with its rotation and translation; neither device scene is written.  scope, targetScope and
+        // budget as splatNeighbours.  `target` may be this renderer.
+        const REGISTER_STATUS = ["converged", "max_iterations", "too_few"];
+        const matchArgs = (target, radius, o) => {
+            if (!(target instanceof HIPRenderer) || !target._h) throw new Error("target must be a live HIPRenderer");
+            const budget = o.budget === undefined || o.budget === null ? 0 : Number(o.budget);
+            if (!(budget >= 0)) throw new Error("budget must be a non-negative number");
+            let m = null;
+            if (o.transform !== undefined && o.transform !== null) {
+                m = Float64Array.from(o.transform);
+                if (m.length !== 12) throw new Error("transform is 12 numbers, row-major 3 x 4 (R | t)");
+            }
+            return [target._h, m, Number(radius), nbScope(o), nbScope({ scope: o.targetScope }), budget];
+        };
+        this.matchScene = (target, radius, options) => {
+            const o2 = options || {};
+            const r = this._n.matchScene(this._h, ...matchArgs(target, radius, o2), !!o2.sums);
+            const out = { idx: r.idx, d2: r.d2, inScope: r.inScope, nonfinite: r.nonfinite, targetIndexed: r.targetIndexed, matched: r.matched, pairBound: r.pairBound,
+                          d2Min: r.d2Min, d2Max: r.d2Max };
+            if (o2.sums) { out.pairs = r.pairs; out.sums = r.sums; }
+            return out;
+        };
+        this.selectMatch = (target, radius, options) => {
+            const o2 = options || {}, args = matchArgs(target, radius, o2);
+            const lo = o2.lo === undefined ? 0 : Number(o2.lo), hi = o2.hi === undefined || o2.hi === null ? Infinity : Number(o2.hi);
+            if (Number.isNaN(lo) || Number.isNaN(hi) || lo > hi) throw new Error("selectMatch: lo <= hi must hold, neither a NaN");
+            return this._n.selectMatch(this._h, ...args, lo, hi, code(OPS, o2.op, "replace", "op"));
+        };
+        this.registerTo = (target, radius, options) => {
+            const o2 = options || {}, args = matchArgs(target, radius, o2);
+            const steps = o2.maxIterations === undefined ? 32 : o2.maxIterations, tolerance = o2.tolerance === undefined ? 2 ** -40 : Number(o2.tolerance);
+            if (!Number.isInteger(steps) || steps < 1 || steps > 256) throw new Error("maxIterations must be an integer in 1 .. 256");
+            if (!(tolerance >= 0)) throw new Error("tolerance must be a non-negative number");
+            const r = this._n.registerTo(this._h, ...args, steps, tolerance, !!o2.history);
+            const out = { transform: r.transform, rotation: new Quaternion(r.q[0], r.q[1], r.q[2], r.q[3]), translation: new Vector3(r.t[0], r.t[1], r.t[2]),
+                          status: REGISTER_STATUS[r.status], iterations: r.iterations, pairs: r.pairs, rms: r.rms };
+            if (o2.history) { out.stepPairs = r.stepPairs; out.stepRms = r.stepRms; }
+            return out;
+        };
+        // the rotation and translation of a transform (12 numbers), by the library's one statement of it (a pure function: no device):
+        // scene.rotate(rotation); scene.translate(translation) applies it to every device copy
+        this.rigidDecompose = (transform) => {
+            const m = Float64Array.from(transform);
+            if (m.length !== 12) throw new Error("rigidDecompose: transform is 12 numbers, row-major 3 x 4 (R | t)");
+            const r = this._n.rigidDecompose(m);
+            return { rotation: new Quaternion(r.q[0], r.q[1], r.q[2], r.q[3]), translation: new Vector3(r.t[0], r.t[1], r.t[2]) };
+        };
         // ---- clusters (gsr_clusters / gsr_select_clusters / gsr_select_cluster_at): the connected islands of splats at a linking radius ----
         //   const p = renderer.pick(x, y); renderer.selectClusterAt(0.05, { seed: p.index });        // the island under the cursor
         //   renderer.selectClusters(0.05, { below: 50 }); scene.eraseSelection(renderer.readSelection());   // noise and every island of fewer than 50 splats

@@ -124,6 +124,30 @@ class GsrPlaneInfo(ctypes.Structure):
         return d
 
 
+class GsrMatchInfo(ctypes.Structure):
+    _fields_ = [("in_scope", ctypes.c_uint32), ("nonfinite", ctypes.c_uint32), ("target_indexed", ctypes.c_uint32), ("matched", ctypes.c_uint32),
+                ("pair_bound", ctypes.c_uint64), ("budget", ctypes.c_uint64), ("d2_min", ctypes.c_double), ("d2_max", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: (float if t is ctypes.c_double else int)(getattr(self, k)) for k, t in self._fields_}
+
+
+class GsrMatchSums(ctypes.Structure):
+    _fields_ = [("pairs", ctypes.c_uint64), ("sum", ctypes.c_double * 16)]
+
+    def as_dict(self):
+        return {"pairs": int(self.pairs), "sum": np.array(self.sum, dtype=np.float64)}
+
+
+class GsrRegisterInfo(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("iterations", ctypes.c_uint32), ("pairs", ctypes.c_uint64), ("rms", ctypes.c_double), ("delta", ctypes.c_double),
+                ("step_pairs", ctypes.c_void_p), ("step_rms", ctypes.c_void_p), ("step_rows", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self):
+        return {"status": REGISTER_STATUS[self.status], "iterations": int(self.iterations), "pairs": int(self.pairs), "rms": float(self.rms),
+                "delta": float(self.delta)}
+
+
 class GsrDepthLayout(ctypes.Structure):
     _fields_ = [("format", ctypes.c_int32), ("step", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
                 ("stride", ctypes.c_int32), ("reserved", ctypes.c_int32), ("offset", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
@@ -147,6 +171,9 @@ NEIGHBOUR_DEFAULT_BUDGET, NEIGHBOUR_MAX_BUDGET = 1 << 34, 1 << 38          # GSR
 KNN_MAX_K, KNN_NONE = 32, 0xffffffff                                       # GSR_KNN_MAX_K, GSR_KNN_NONE (an empty list slot)
 KNN_STATS = {"kth": 0, "mean": 1}                                          # GSR_KNN_*
 PLANE_MAX_HYPOTHESES = 4096                                               # GSR_PLANE_MAX_HYPOTHESES
+MATCH_NONE = 0xffffffff                                                    # GSR_MATCH_NONE (an unmatched splat)
+REGISTER_STATUS = {0: "converged", 1: "max_iterations", 2: "too_few"}      # GSR_REGISTER_*
+REGISTER_MAX_ITERATIONS = 256                                              # GSR_REGISTER_MAX_ITERATIONS_LIMIT
 CELL_NONE = 0xffffffff                                                     # GSR_CELL_NONE (a leader: the splat is no candidate)
 CLUSTER_NONE = CLUSTER_LARGEST = 0xffffffff                                # GSR_CLUSTER_NONE (a label), GSR_CLUSTER_LARGEST (a seed)
 
@@ -173,6 +200,47 @@ def plane_alignment(plane, axis=(0, 1, 0)):
         err = GsplatError("libgsplat_hip error %d: %s" % (rc, L.gsr_last_error(None).decode()))
         err.code = rc
         raise err
+    return q, t
+
+
+def _pure(name, rc):
+    if rc:
+        err = GsplatError("libgsplat_hip error %d: %s" % (rc, load_library().gsr_last_error(None).decode()))
+        err.code = rc
+        raise err
+
+
+def _transform_arg(transform):
+    """a 3 x 4 transform (R | t) as twelve contiguous doubles, None for the identity"""
+    return None if transform is None else np.ascontiguousarray(transform, dtype=np.float64).reshape(12)
+
+
+def rigid_solve(sums):
+    """(D float64[3, 4], rms) of gsr_rigid_solve: the rigid motion that takes the matched source points closest to their targets
+    (Horn's closed form on match()'s sums, a dict with "pairs" and "sum").  Needs the library, not a device."""
+    L = load_library()
+    s = GsrMatchSums()
+    s.pairs = int(sums["pairs"])
+    s.sum[:] = [float(v) for v in np.asarray(sums["sum"], dtype=np.float64).reshape(16)]
+    D, rms = np.zeros(12, np.float64), ctypes.c_double(0.0)
+    _pure("gsr_rigid_solve", L.gsr_rigid_solve(ctypes.byref(s), D.ctypes.data, ctypes.byref(rms)))
+    return D.reshape(3, 4), rms.value
+
+
+def rigid_compose(D, M):
+    """float64[3, 4] of gsr_rigid_compose: D o M, "apply M, then D"."""
+    L = load_library()
+    d, m, out = _transform_arg(D), _transform_arg(M), np.zeros(12, np.float64)
+    _pure("gsr_rigid_compose", L.gsr_rigid_compose(d.ctypes.data, m.ctypes.data, out.ctypes.data))
+    return out.reshape(3, 4)
+
+
+def rigid_decompose(M):
+    """(q_xyzw float64[4], t float64[3]) of gsr_rigid_decompose: scene_rotate(q) then scene_translate(t) applies the transform M
+    to a scene."""
+    L = load_library()
+    m, q, t = _transform_arg(M), np.zeros(4, np.float64), np.zeros(3, np.float64)
+    _pure("gsr_rigid_decompose", L.gsr_rigid_decompose(m.ctypes.data, q.ctypes.data, t.ctypes.data))
     return q, t
 
 
@@ -230,6 +298,7 @@ EXPORTS = [
     "gsr_knn", "gsr_select_knn",
     "gsr_cells", "gsr_scene_merge_cells",
     "gsr_fit_plane", "gsr_plane_inliers", "gsr_select_plane", "gsr_plane_alignment",
+    "gsr_match", "gsr_select_match", "gsr_register", "gsr_rigid_solve", "gsr_rigid_compose", "gsr_rigid_decompose",
     "gsr_set_overlay", "gsr_overlay_async", "gsr_read_overlay", "gsr_read_overlay_rgba8", "gsr_overlay_device_ptr", "gsr_delivery_set_overlay",
     "gsr_set_overlay_outline",
 ]
@@ -412,6 +481,13 @@ def load_library(path=None):
     L.gsr_plane_inliers.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_double, ctypes.c_uint32, u64, vp, pi]
     L.gsr_select_plane.argtypes = [vp, vp, ctypes.c_double, ctypes.c_double, ctypes.c_int32, u32p]
     L.gsr_plane_alignment.argtypes = [vp, vp, vp, vp]
+    mi = ctypes.POINTER(GsrMatchInfo)
+    L.gsr_match.argtypes = [vp, vp, vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, vp, vp, ctypes.c_uint32, ctypes.POINTER(GsrMatchSums), mi]
+    L.gsr_select_match.argtypes = [vp, vp, vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, ctypes.c_double, ctypes.c_double, ctypes.c_int32, u32p, mi]
+    L.gsr_register.argtypes = [vp, vp, vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, ctypes.c_uint32, ctypes.c_double, vp, ctypes.POINTER(GsrRegisterInfo)]
+    L.gsr_rigid_solve.argtypes = [ctypes.POINTER(GsrMatchSums), vp, ctypes.POINTER(ctypes.c_double)]
+    L.gsr_rigid_compose.argtypes = [vp, vp, vp]
+    L.gsr_rigid_decompose.argtypes = [vp, vp, vp]
     L.gsr_set_overlay.argtypes = [vp, ctypes.POINTER(GsrOverlayOptions)]
     L.gsr_set_overlay_outline.argtypes = [vp, ctypes.POINTER(GsrOutlineOptions)]
     L.gsr_overlay_async.argtypes = [vp]
@@ -1511,6 +1587,77 @@ class HIPRenderer:
         """(q_xyzw float64[4], t float64[3]): the whole-scene rotation and translation that take `plane` to axis . p = 0 --
         scene_rotate(q) then scene_translate(t) puts the floor at y = 0.  A pure function of the library's: no device."""
         return plane_alignment(plane, axis)
+
+    # -- matching and registration (gsr_match / gsr_select_match / gsr_register): this scene matched to another one, aligned with it --
+    @staticmethod
+    def _match_args(target, radius, budget):
+        if not isinstance(target, HIPRenderer):
+            raise TypeError("target must be a HIPRenderer")
+        budget = 0 if budget is None else int(budget)
+        if budget < 0:
+            raise ValueError("budget must not be negative")
+        return float(radius), budget
+
+    def match(self, target, radius, transform=None, scope=(), target_scope=(), idx=True, d2=True, sums=False, budget=None):
+        """(idx uint32[n], d2 float64[n], sums, info): for every splat of this scene in `scope`, moved by `transform` (3 x 4, R | t;
+        None is the identity), the nearest splat of `target`'s scene in `target_scope` within `radius` -- smallest in (squared
+        distance, index), f64, a distance of exactly radius counting.  Unmatched: MATCH_NONE and +inf; outside the scope: MATCH_NONE
+        and NaN.  sums=True: {"pairs", "sum" float64[16]}, what rigid_solve takes -- the rows (T, Q, T_a * Q_b, d2) of the matched
+        splats summed by a fixed tree; otherwise None.  idx=False / d2=False: None in its place, nothing copied.  info: in_scope,
+        nonfinite, target_indexed, matched, pair_bound, budget, d2_min, d2_max.  budget as neighbours() takes it.  Neither scene
+        is written; `target` may be this renderer."""
+        radius, budget = self._match_args(target, radius, budget)
+        m = _transform_arg(transform)
+        n = self._count()
+        i = np.full(n, MATCH_NONE, np.uint32) if idx else None
+        d = np.full(n, np.nan, np.float64) if d2 else None
+        s = GsrMatchSums() if sums else None
+        info = GsrMatchInfo()
+        ptr = lambda a: a.ctypes.data if a is not None and n else None
+        self._check_neighbours(self._L.gsr_match(self._ctx, target._ctx, None if m is None else m.ctypes.data, radius, self._scope_flags(scope),
+                                                 self._scope_flags(target_scope), budget, ptr(i), ptr(d), n if idx or d2 else 0,
+                                                 ctypes.byref(s) if sums else None, ctypes.byref(info)), info)
+        return i, d, s.as_dict() if sums else None, info.as_dict()
+
+    def select_match(self, target, radius, lo=0.0, hi=None, transform=None, scope=(), target_scope=(), op="replace", budget=None):
+        """(selected, info): pick the splats in scope whose distance v to their match has lo <= v < hi (hi=None or +inf: no upper end,
+        the unmatched splats included) and fold them into the selection.  select_match(t, r, hi=r) is "what the other capture
+        already has", select_match(t, r, lo=r) "what it lacks".  With op "replace" it selects exactly the splats whose d2 of
+        match() with the same arguments satisfies the rule."""
+        radius, budget = self._match_args(target, radius, budget)
+        m = _transform_arg(transform)
+        lo, hi = float(lo), float("inf") if hi is None else float(hi)
+        if lo != lo or hi != hi or lo > hi:
+            raise ValueError("lo <= hi must hold, neither a NaN")
+        count, info = ctypes.c_uint32(0), GsrMatchInfo()
+        self._check_neighbours(self._L.gsr_select_match(self._ctx, target._ctx, None if m is None else m.ctypes.data, radius, self._scope_flags(scope),
+                                                        self._scope_flags(target_scope), budget, lo, hi, self._select_code(SELECT_OPS, op, "op"),
+                                                        ctypes.byref(count), ctypes.byref(info)), info)
+        return count.value, info.as_dict()
+
+    def register(self, target, radius, transform=None, max_iterations=32, tolerance=2.0 ** -40, history=False, scope=(), target_scope=(), budget=None):
+        """(M float64[3, 4], info): the rigid transform that takes this scene onto `target`'s, by iterating match, reduce and solve
+        from `transform` (None: the identity) -- the same bits on every run.  It stops with status "too_few" when a step matches
+        fewer than 3 splats, "converged" when a step's motion differs from the identity by at most `tolerance` in every entry,
+        "max_iterations" after that many steps (1 .. 256).  info: status, iterations, pairs and rms of the last step, delta;
+        history=True adds step_pairs and step_rms, one entry per step.  The scene is not written: rigid_decompose(M), then
+        scene_rotate and scene_translate, apply the result once."""
+        radius, budget = self._match_args(target, radius, budget)
+        max_iterations = int(max_iterations)
+        if not 1 <= max_iterations <= REGISTER_MAX_ITERATIONS:
+            raise ValueError("max_iterations must be in 1 .. %d" % REGISTER_MAX_ITERATIONS)
+        m = _transform_arg(transform)
+        out = np.zeros(12, np.float64)
+        info = GsrRegisterInfo()
+        sp, sr = np.zeros(max_iterations, np.uint64), np.zeros(max_iterations, np.float64)
+        if history:
+            info.step_pairs, info.step_rms, info.step_rows = sp.ctypes.data, sr.ctypes.data, max_iterations
+        self._check(self._L.gsr_register(self._ctx, target._ctx, None if m is None else m.ctypes.data, radius, self._scope_flags(scope),
+                                         self._scope_flags(target_scope), budget, max_iterations, float(tolerance), out.ctypes.data, ctypes.byref(info)))
+        d = info.as_dict()
+        if history:
+            d["step_pairs"], d["step_rms"] = sp[:info.iterations].copy(), sr[:info.iterations].copy()
+        return out.reshape(3, 4), d
 
     # -- selection overlay (gsr_set_overlay / gsr_overlay_async / gsr_read_overlay*): the selected splats tinted --
     def set_overlay(self, tint=(1.0, 0.5, 0.0), mix=0.5):

@@ -1176,6 +1176,131 @@ int gsr_plane_inliers(gsr_ctx *ctx, const double *planes /* [count][4] */, uint3
 int gsr_select_plane(gsr_ctx *ctx, const double *plane /* [4] */, double lo, double hi, int32_t op, uint32_t *selected);
 int gsr_plane_alignment(const double *plane, const double *axis /* [3] */, double *q_xyzw, double *t /* [3] */);
 
+/* ---- matching and registration ---- a scene matched to another one and aligned with it on the device
+ * No interface of the reference stands behind this section either.  gsr_scene_append_selected pastes the splats of another
+ * context's scene into this one; nothing above can say where they should go.  Two captures of one place come with different
+ * origins and orientations.  These calls are the first that relate two scenes: for every splat of this scene, moved by a trial
+ * transform, gsr_match finds the nearest splat of another scene.  That answer is data, a picker ("what does the other capture
+ * already have", "what changed") and the inner step of a rigid registration (gsr_register) whose result is the same bits on every
+ * run -- with no gsr_read_scene and no spatial index or ICP on the host.
+ * Definition ("Matching and registration").  All arithmetic is f64, in the written order, uncontracted; / and
+ *   the square root are correctly rounded.
+ *   Transform.  M is twelve doubles, row-major 3 x 4 (R | t): M[k][c] = M[4*k + c].  NULL is the identity.
+ *   Transformed source point of splat i of ctx, at the stored f32 position p as doubles:
+ *     T_k = ((M[k][0]*p_x + M[k][1]*p_y) + M[k][2]*p_z) + M[k][3]       k = 0, 1, 2
+ *   Scopes.  S (scope) and S' (target_scope) are the GSR_SCOPE_* flags of "splat data"; S is evaluated on ctx's selection and
+ *   hidden set, S' on target's.  A target splat is indexed iff it is in S' and its position is finite.  A source splat is a
+ *   query iff it is in S, its position is finite and all three T_k are finite; the others in S are `nonfinite` and unmatched.
+ *   Match.  For a query i and an indexed target splat j at the stored f32 position q:
+ *     e = T_i - (double)q_j;   d2(i,j) = (ex*ex + ey*ey) + ez*ez;   j is a candidate iff d2 <= radius*radius
+ *     match_i = the candidate smallest in the pair (d2, j): equal distances go to the smaller target index
+ *   An unmatched splat of S has GSR_MATCH_NONE and +inf; a splat outside S has GSR_MATCH_NONE and NaN (0x7ff8000000000000), which
+ *   is gsr_knn's convention.  There is no "other" exclusion: with target == ctx (or a member of the same shared scene) and the
+ *   identity every finite splat matches the smallest index among the splats coincident with it, with d2 == 0.
+ *   The index is that of "neighbours", built over the TARGET's positions and scope, with the same h = radius * (1 + 2^-10), key,
+ *   bucket and 27-cell walk; a query's cell coordinate is floor(T_k * inv_h), clamped as a stored position's is.
+ *   Sums.  A matched splat contributes the row of 16 doubles
+ *     (T_x, T_y, T_z, Q_x, Q_y, Q_z, T_a*Q_b for ab = 00, 01, 02, 10, 11, 12, 20, 21, 22, d2)      Q = (double)q_match
+ *   and every other splat sixteen +0.0.  The rows of splats 0 .. n-1 are summed by a fixed tree: groups of 256 consecutive rows, the
+ *   last group padded with +0.0; within a group, for s = 128, 64, .., 1: x[l] = x[l] + x[l + s] for l < s; the group results are
+ *   reduced the same way until one row is left.  f64 addition is commutative and no NaN can enter, so the tree decides the bits
+ *   and no visiting order does.  pairs is the integer count of matched splats.
+ * gsr_match: idx is n words and d2 n doubles, or NULL; a non-NULL one with n not equal to ctx's count is refused.  sums and info
+ *   may be NULL; the tree runs only when sums are asked for.  An empty source scene or scope, or an empty target (no splat, or
+ *   none indexed), returns GSR_OK with everything unmatched and zeros (d2_min +inf, d2_max -inf).
+ * info: in_scope and nonfinite count SOURCE splats; target_indexed the index's entries; matched = pairs; pair_bound and budget as
+ *   in gsr_neighbour_info; d2_min / d2_max over the matched splats, +inf / -inf with none.  Every field is an integer or a min /
+ *   max, so every field is exact.
+ * gsr_select_match picks P = { i in S : lo <= v_i && (v_i < hi || hi == +inf) } with v_i = sqrt(d2_i) (+inf when unmatched) and
+ *   folds P into ctx's selection with `op` exactly as gsr_select_knn folds its set.  (lo = 0, hi = r) is "what the other capture
+ *   already has within r", (lo = r, hi = +inf) "what it lacks".  The consistency guarantee: with GSR_SELOP_REPLACE it selects
+ *   exactly the splats whose d2 from gsr_match with the same arguments satisfies the rule.
+ * gsr_rigid_solve is a pure function with no context: Horn's closed form on the sums.  It returns D (3 x 4) with D(T) closest to
+ *   Q in the least-squares sense over the pairs, and rms (may be NULL).  With n = (double)pairs, inv = 1.0 / n:
+ *     mT_a = sum[a] * inv;  mQ_a = sum[3 + a] * inv;  S_ab = sum[6 + 3*a + b] * inv - mT_a * mQ_b       (x, y, z = 0, 1, 2)
+ *     N, symmetric 4 x 4 in the order (w, x, y, z):
+ *       N00 = (Sxx + Syy) + Szz;  N01 = Syz - Szy;  N02 = Szx - Sxz;  N03 = Sxy - Syx;  N11 = (Sxx - Syy) - Szz;
+ *       N12 = Sxy + Syx;  N13 = Szx + Sxz;  N22 = (Syy - Sxx) - Szz;  N23 = Syz + Szy;  N33 = (Szz - Sxx) - Syy
+ *     Cyclic Jacobi, exactly 8 sweeps over the pairs (p, q) = (0,1), (0,2), (0,3), (1,2), (1,3), (2,3) on A = N, V = I, with the
+ *     formulas of "merging cells", step 6: a pair with A_pq == 0 is skipped; th = (A_qq - A_pp) / (2.0 * A_pq);
+ *     t = 1.0 / (fabs(th) + sqrt(th * th + 1.0)), negated if th < 0;  cs = 1.0 / sqrt(t * t + 1.0);  sn = t * cs.  From the old
+ *     values: A_pp = app - t * apq;  A_qq = aqq + t * apq;  A_pq = 0;  for both r other than p, q: A_rp = cs * arp - sn * arq,
+ *     A_rq = sn * arp + cs * arq;  for k = 0..3: V_kp = cs * vkp - sn * vkq, V_kq = sn * vkp + cs * vkq.  lam_k = A_kk.
+ *     (w, x, y, z) = column k of V for the largest lam_k, ties to the smallest k, divided by sqrt(((w*w + x*x) + y*y) + z*z) and
+ *     negated if its first non-zero component is negative.
+ *     R00 = 1.0 - 2.0*(y*y + z*z);  R01 = 2.0*(x*y - z*w);  R02 = 2.0*(x*z + y*w);
+ *     R10 = 2.0*(x*y + z*w);  R11 = 1.0 - 2.0*(x*x + z*z);  R12 = 2.0*(y*z - x*w);
+ *     R20 = 2.0*(x*z - y*w);  R21 = 2.0*(y*z + x*w);  R22 = 1.0 - 2.0*(x*x + y*y)
+ *     t_k = mQ_k - ((R_k0*mT_0 + R_k1*mT_1) + R_k2*mT_2);   D = (R | t);   rms = sqrt(sum[15] * inv)
+ *   Refused (GSR_ERR_ARG): a NULL pointer, pairs < 3, a non-finite sum.  A degenerate (collinear) set of pairs gives SOME rotation
+ *   about the line and is not detected.  tests/register_reference.py restates this order; the result is bit for bit its result.
+ * gsr_rigid_compose: out = D o M (apply M, then D): out[k][c] = (D[k][0]*M[0][c] + D[k][1]*M[1][c]) + D[k][2]*M[2][c], plus
+ *   D[k][3] for c == 3.  out may be D or M.
+ * gsr_rigid_decompose: q (x, y, z, w) from the 3 x 3 part of M by Shepperd's four branches as "merging cells", step 9, states
+ *   them, and t = (M[0][3], M[1][3], M[2][3]).  gsr_scene_rotate(q) then gsr_scene_translate(t) applies M to the scene, once.
+ * gsr_register runs the loop on the host, from M_0 (NULL: the identity).  Step t matches under M_t and reduces; with pairs < 3 it
+ *   stops with GSR_REGISTER_TOO_FEW and M_t; otherwise it solves D_t and sets M_{t+1} = D_t o M_t; when the largest of the twelve
+ *   |D_t - (I | 0)| is <= tolerance it stops with GSR_REGISTER_CONVERGED; after max_iterations steps (1 .. 256) it stops with
+ *   GSR_REGISTER_MAX_ITERATIONS.  All three return GSR_OK.  info: status; iterations = the steps that ran; pairs and rms of the
+ *   last step's match (rms = sqrt(sum[15] * (1.0 / pairs)), +inf with no pair); delta = the last solved step's largest
+ *   |D - (I | 0)| (+inf with none).  info is in / out: step_pairs and step_rms are NULL or the caller's arrays of step_rows >=
+ *   max_iterations entries, which receive every step's pairs and rms.  M_out (twelve doubles) and info may be NULL.
+ *   The scene is never written: a trial transform is iterated, not the stored f32 positions, so positions and packed covariances
+ *   do not drift.  The target does not change between the steps, so its index is built once per call.  Rigid only.
+ * The work budget is the neighbour budget, with the same constants.  pair_bound is the sum, over the queries, of the populations of
+ *   the 27 buckets their walk visits; it is checked before the walk is launched, at every step of gsr_register: if pair_bound >
+ *   budget the call returns GSR_ERR_ARG with a message naming both numbers, with info's first fields filled, and launches no walk.
+ * gsr_match, gsr_select_match and gsr_register are blocking and stateless.  They wait for every member's stream of both contexts'
+ *   shared scenes first.  target must be on ctx's device.  target's scene, selection, hidden set and frame state are not changed;
+ *   ctx's scene is read and never written.
+ * Refusals (GSR_ERR_ARG with a message, nothing touched, the selection and its count included): a NULL ctx or target; another
+ *   device; the radius rules of "neighbours"; unknown scope flags or op; a NaN bound or lo > hi; a wrong n; a non-finite M; a
+ *   tolerance that is NaN or negative; iterations outside 1 .. 256; step arrays shorter than max_iterations; a budget above the
+ *   maximum; a bound above the budget.
+ * The device scratch belongs to ctx: the scratch of "neighbours" sized for the TARGET's count, 4 + 8 bytes per source splat for
+ *   idx and d2, and the tree's partial rows (128 bytes per 256 source splats and level) once sums are asked for.  The first call
+ *   allocates it, it only grows, and gsr_destroy frees it; a context that never calls any of this allocates nothing and launches
+ *   nothing. */
+typedef struct gsr_match_info {
+    uint32_t in_scope;        /* source splats in S */
+    uint32_t nonfinite;       /* of those, no query: a non-finite position or transformed point */
+    uint32_t target_indexed;  /* target splats in S' with a finite position */
+    uint32_t matched;
+    uint64_t pair_bound;      /* pair tests the walk makes at most, as the implementation counts them */
+    uint64_t budget;          /* the budget that applied */
+    double d2_min;            /* over the matched splats; +inf: there is none */
+    double d2_max;            /* over the matched splats; -inf: there is none */
+} gsr_match_info;             /* 48 bytes */
+typedef struct gsr_match_sums {
+    uint64_t pairs;
+    double sum[16];
+} gsr_match_sums;             /* 136 bytes */
+typedef struct gsr_register_info {
+    int32_t status;           /* GSR_REGISTER_* */
+    uint32_t iterations;
+    uint64_t pairs;
+    double rms, delta;
+    uint64_t *step_pairs;     /* in: NULL, or step_rows entries */
+    double *step_rms;         /* in: NULL, or step_rows entries */
+    uint32_t step_rows;       /* in */
+    uint32_t reserved;
+} gsr_register_info;          /* 56 bytes */
+#define GSR_MATCH_NONE 0xffffffffu   /* an unmatched splat */
+#define GSR_REGISTER_CONVERGED      0
+#define GSR_REGISTER_MAX_ITERATIONS 1
+#define GSR_REGISTER_TOO_FEW        2
+#define GSR_REGISTER_MAX_ITERATIONS_LIMIT 256u
+int gsr_match(gsr_ctx *ctx, gsr_ctx *target, const double *M /* [12] or NULL */, double radius, uint32_t scope,
+              uint32_t target_scope, uint64_t budget, uint32_t *idx, double *d2, uint32_t n, gsr_match_sums *sums,
+              gsr_match_info *info);
+int gsr_select_match(gsr_ctx *ctx, gsr_ctx *target, const double *M, double radius, uint32_t scope, uint32_t target_scope,
+                     uint64_t budget, double lo, double hi, int32_t op, uint32_t *selected, gsr_match_info *info);
+int gsr_register(gsr_ctx *ctx, gsr_ctx *target, const double *M0, double radius, uint32_t scope, uint32_t target_scope,
+                 uint64_t budget, uint32_t max_iterations, double tolerance, double *M_out /* [12] */, gsr_register_info *info);
+int gsr_rigid_solve(const gsr_match_sums *sums, double *D /* [12] */, double *rms);
+int gsr_rigid_compose(const double *D, const double *M, double *out /* [12] */);
+int gsr_rigid_decompose(const double *M, double *q_xyzw, double *t /* [3] */);
+
 /* ---- selection overlay ---- the selected splats tinted, in read-backs and in delivered frames
  * No interface of the reference stands behind this section either.  gsr_read_selection returns bits; this shows them: a second
  * image beside the frame in which the selected splats carry a tint, and per pixel how much of it they are.

@@ -3,7 +3,7 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--plane THRESHOLD[:HYPOTHESES]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--merge CELL] [--share-scene]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--plane THRESHOLD[:HYPOTHESES]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--register RADIUS[:ITERATIONS]] [--merge CELL] [--share-scene]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
@@ -57,6 +57,11 @@
 // bound) and the walk (with its fill) apart; pair_bound and the pair tests per second it means for the walk, complete,
 // finite_values, the value range, and the check that gsr_select_knn(lo = the mean of the finite values, hi = +inf) selects exactly
 // the splats whose values[i] is at or above it (`values_equal_selection`).
+// --register RADIUS[:ITERATIONS] (32 steps at most unless given) registers the scene to a copy of itself: a second context holds the
+// config's scene moved by a fixed small rigid motion (0.01 rad about (0.3, 0.9, 0.2), then (0.01, -0.005, 0.008)), so source and target
+// are one size; one gsr_register call from the identity at tolerance 2^-40: its blocking time, the status, every step's pairs and rms,
+// and by the library's events on the stream the target's index (built once per call) and, of the last step and summed over the
+// steps, the bound, the walk and the tree apart (gsr_debug_match_times).
 // --merge CELL (behind everything else: it replaces the scene) merges the cells of a grid of side CELL: three gsr_cells calls, the
 // best wall time of the report, then the one gsr_scene_merge_cells call it announced: the blocking time, the rows before and after,
 // the members per cell, and the check that the edit left the announced rows with exactly the merged rows selected (`report_equals_edit`).
@@ -172,6 +177,7 @@ uint64_t fnv1a(const void* p, size_t bytes)
 extern "C" int gsr_debug_neighbour_times(gsr_ctx* ctx, float* out /* build_ms, count_ms */);   // not part of the ABI (gsr_neighbours.cpp)
 extern "C" int gsr_debug_plane_times(gsr_ctx* ctx, float* out /* candidates_ms, score_ms */);   // not part of the ABI (gsr_plane.cpp)
 extern "C" int gsr_debug_knn_times(gsr_ctx* ctx, float* out /* index_ms, walk_ms */);   // not part of the ABI (gsr_knn.cpp)
+extern "C" int gsr_debug_match_times(gsr_ctx* ctx, float* out /* index_ms, the last step's bound_ms, walk_ms, tree_ms, the steps' sums of the three, steps */);   // not part of the ABI (gsr_match.cpp)
 extern "C" int gsr_debug_cluster_times(gsr_ctx* ctx, float* out /* index_ms, core_ms, union_ms, border_ms */);   // not part of the ABI (gsr_clusters.cpp)
 
 #define CHECK(call)                                                                                     \
@@ -211,6 +217,8 @@ int main(int argc, char** argv)
     uint32_t cl_min_pts = 0;
     double knn_radius = 0.0;            // 0: off
     double merge_cell = 0.0;            // 0: off
+    double reg_radius = 0.0;            // 0: off
+    uint32_t reg_steps = 32;
     uint32_t knn_k = 8;
     int32_t knn_stat = GSR_KNN_MEAN;
     int32_t pick_xy[2] = {0, 0};
@@ -272,6 +280,14 @@ int main(int argc, char** argv)
             if (!(knn_radius > 0.0) || k < 1 || k > (int)GSR_KNN_MAX_K || (stat != "kth" && stat != "mean")) { std::fprintf(stderr, "--knn RADIUS:K[:kth|mean]: RADIUS > 0, K in 1 .. 32\n"); return 2; }
             knn_k = (uint32_t)k; knn_stat = stat == "kth" ? GSR_KNN_KTH : GSR_KNN_MEAN;
         }
+        else if (a == "--register" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            const size_t colon = v.find(':');
+            reg_radius = std::atof(v.c_str());
+            const int steps = colon != std::string::npos ? std::atoi(v.c_str() + colon + 1) : 32;
+            if (!(reg_radius > 0.0) || steps < 1 || steps > (int)GSR_REGISTER_MAX_ITERATIONS_LIMIT) { std::fprintf(stderr, "--register RADIUS[:ITERATIONS]: RADIUS > 0, ITERATIONS in 1 .. 256\n"); return 2; }
+            reg_steps = (uint32_t)steps;
+        }
         else if (a == "--merge" && i + 1 < argc) { merge_cell = std::atof(argv[++i]); if (!(merge_cell > 0.0)) { std::fprintf(stderr, "--merge CELL: CELL > 0\n"); return 2; } }
         else if (a == "--duplicate" && i + 1 < argc) { duplicate_fraction = std::atof(argv[++i]); if (!(duplicate_fraction >= 0.0 && duplicate_fraction <= 1.0)) { std::fprintf(stderr, "--duplicate FRACTION must be in [0, 1]\n"); return 2; } }
         else if (a == "--reserve") reserve = true;
@@ -279,7 +295,7 @@ int main(int argc, char** argv)
         else if (a == "--scene-edit") scene_edit = next();
         else if (a == "--share-scene") share_scene = true;
         else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--plane THRESHOLD[:HYPOTHESES]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--merge CELL] [--share-scene]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--plane THRESHOLD[:HYPOTHESES]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--register RADIUS[:ITERATIONS]] [--merge CELL] [--share-scene]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
@@ -764,6 +780,35 @@ int main(int argc, char** argv)
         CHECK(gsr_select_knn(ctx[0], knn_radius, knn_k, 0, 0, knn_stat, knn_lo, HUGE_VAL, GSR_SELOP_REPLACE, &knn_selected, nullptr));
         knn_select_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3;
     }
+    // --register: the scene registered to a moved copy of itself in a second context, the stages timed apart
+    gsr_register_info reg_info{};
+    std::vector<uint64_t> reg_step_pairs(reg_steps, 0);
+    std::vector<double> reg_step_rms(reg_steps, 0.0);
+    double reg_ms = 0, reg_M[12] = {0};
+    float reg_stage[8] = {0};
+    uint32_t reg_n = 0, reg_target_n = 0;
+    if (reg_radius > 0.0) {
+        gsr_ctx* tgt = nullptr;
+        gsr_options o{};
+        o.device = 0; o.width = cfg->w; o.height = cfg->h;
+        const int rc = gsr_create(&tgt, &o);
+        if (rc) { std::fprintf(stderr, "gsr_create failed (%d): %s\n", rc, gsr_last_error(nullptr)); return 1; }
+        ctx0 = tgt;
+        CHECK(gsr_set_scene_rows(tgt, rows.data(), n));
+        const double half = 0.005, al = std::sqrt(0.3 * 0.3 + 0.9 * 0.9 + 0.2 * 0.2), sh = std::sin(half);
+        const double q[4] = {0.3 / al * sh, 0.9 / al * sh, 0.2 / al * sh, std::cos(half)}, tr[3] = {0.01, -0.005, 0.008};
+        CHECK(gsr_scene_rotate(tgt, q));
+        CHECK(gsr_scene_translate(tgt, tr));
+        CHECK(gsr_scene_count(tgt, &reg_target_n));
+        ctx0 = ctx[0];
+        CHECK(gsr_scene_count(ctx[0], &reg_n));
+        reg_info.step_pairs = reg_step_pairs.data(); reg_info.step_rms = reg_step_rms.data(); reg_info.step_rows = reg_steps;
+        const auto t0 = std::chrono::steady_clock::now();
+        CHECK(gsr_register(ctx[0], tgt, nullptr, reg_radius, 0, 0, 0, reg_steps, 1.0 / 1099511627776.0, reg_M, &reg_info));
+        reg_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3;
+        CHECK(gsr_debug_match_times(ctx[0], reg_stage));
+        gsr_destroy(tgt);
+    }
     // --duplicate (last of all: it grows the scene): the selection duplicated on the device, twice
     double duplicate_ms = 0, duplicate_again_ms = 0, reserve_ms = 0;
     uint32_t dup_selected = 0, dup_first = 0, dup_count = 0, dup_capacity = 0, dup_n = 0;
@@ -886,6 +931,21 @@ int main(int argc, char** argv)
                     cl_radius, cl_min_pts, cl_n, cl_info.in_scope, cl_info.nonfinite, (unsigned long long)cl_info.pair_bound, (unsigned long long)cl_info.budget, cl_ms,
                     cl_stage_ms[0], cl_stage_ms[1], cl_stage_ms[2], cl_stage_ms[3], cl_info.core, cl_info.border, cl_info.noise, cl_info.clusters, cl_info.largest_label,
                     cl_info.largest_size, cl_small, cl_select_ms, cl_selected, cl_small == cl_selected ? "true" : "false");
+    if (reg_radius > 0.0) {
+        std::printf(", \"register\": {\"radius\": %.17g, \"max_iterations\": %u, \"n\": %u, \"target_n\": %u, \"status\": \"%s\", \"iterations\": %u, \"pairs\": %llu, "
+                    "\"rms\": %s, \"delta\": %s, \"register_ms\": %.4f, \"index_build_ms\": %.4f, \"bound_ms\": %.4f, \"walk_ms\": %.4f, \"tree_ms\": %.4f, "
+                    "\"steps_bound_ms\": %.4f, \"steps_walk_ms\": %.4f, \"steps_tree_ms\": %.4f, \"transform\": [",
+                    reg_radius, reg_steps, reg_n, reg_target_n,
+                    reg_info.status == GSR_REGISTER_CONVERGED ? "converged" : reg_info.status == GSR_REGISTER_TOO_FEW ? "too_few" : "max_iterations", reg_info.iterations,
+                    (unsigned long long)reg_info.pairs, json_num(reg_info.rms).c_str(), json_num(reg_info.delta).c_str(), reg_ms, reg_stage[0], reg_stage[1], reg_stage[2],
+                    reg_stage[3], reg_stage[4], reg_stage[5], reg_stage[6]);
+        for (int k = 0; k < 12; k++) std::printf("%s%.17g", k ? ", " : "", reg_M[k]);
+        std::printf("], \"step_pairs\": [");
+        for (uint32_t k = 0; k < reg_info.iterations; k++) std::printf("%s%llu", k ? ", " : "", (unsigned long long)reg_step_pairs[k]);
+        std::printf("], \"step_rms\": [");
+        for (uint32_t k = 0; k < reg_info.iterations; k++) std::printf("%s%s", k ? ", " : "", json_num(reg_step_rms[k]).c_str());
+        std::printf("]}");
+    }
     if (knn_radius > 0.0)
         std::printf(", \"knn\": {\"radius\": %.17g, \"k\": %u, \"stat\": \"%s\", \"n\": %u, \"in_scope\": %u, \"nonfinite\": %u, \"pair_bound\": %llu, \"budget\": %llu, "
                     "\"knn_ms\": %.4f, \"index_build_ms\": %.4f, \"walk_ms\": %.4f, \"pair_tests_per_s\": %.4g, \"knn_lists_ms\": %.4f, \"lists_index_build_ms\": %.4f, "
