@@ -499,6 +499,17 @@ uint32_t edit_bounds_blocks(uint32_t n);
 void launch_edit_bounds(uint32_t n, const float* px, const float* py, const float* pz, const uint32_t* words, uint32_t nwords, uint32_t* partial,
                         uint32_t* out, hipStream_t s);
 
+// Rotating SH coefficients (k_sh_rotate.hip; DESIGN.md section 4, "Rotating SH coefficients"): the band matrices D_1, D_2, D_3 of
+// gsr_sh_rotation rounded once to f32, row-major; passed by value, so a wave reads them from scalar registers.
+struct ShRotation { float d1[9], d2[25], d3[49]; };
+// c' = D_l c per band, in place, on the rows of tex[0..2] (sh_count rows of 8 words each; row t belongs to splat first + t, and
+// n = first + sh_count): every row (words null), or the rows of the splats whose bit of `words` (nwords of them, the selection's
+// layout) is set.  counter (may be null): SH_ROTATE_COUNTERS slots of one word, SH_ROTATE_COUNTER_STRIDE words apart, zeroed by the
+// caller; the sum of the slots += the rows rotated.
+constexpr uint32_t SH_ROTATE_COUNTERS = 64, SH_ROTATE_COUNTER_STRIDE = 32;
+void launch_sh_rotate(uint32_t n, uint32_t first, uint32_t sh_count, uint32_t* const* tex, const uint32_t* words, uint32_t nwords,
+                      const ShRotation& M, uint32_t* counter, hipStream_t s);
+
 // Growing the scene (k_append.hip; DESIGN.md section 4, "Growing the scene"): the splats of `src` (n_src of them) whose bit of
 // `words` (nwords of them, the selection's layout; bits at and above n_src are not read) is set, in ascending order, copied bit for
 // bit into the rows dst_first, dst_first + 1, ... of `dst`, which holds dst_rows rows.  src and dst may be the same arrays (the

@@ -115,6 +115,13 @@ class Scene extends EventDispatcher {
         this._bandsIndices = band;
     }
 
+    // (for the renderers) a device copy rotated SH coefficients in place (rotateSH, rotateSelection { sh }, bakeSHFrame): shs_rgb is
+    // read back before its next use, as after a followed limitBox; baked: the frame went into the coefficients and is the identity
+    _deviceTurnedSh(baked) {
+        if (this._shHeight > 0) this._shStale = true;
+        if (baked) this._shFrame.set([1, 0, 0, 0, 1, 0, 0, 0, 1]);
+    }
+
     get shFollowsTransforms() { return this._shFollowsTransforms; }
     set shFollowsTransforms(on) {
         this._shFollowsTransforms = !!on;

@@ -356,9 +356,18 @@ export class HIPRenderer {
      *  transforms and the scene has SH rows. */
     selectionBounds(): SelectionBounds;
     translateSelection(v: Vec3Like): void;
-    rotateSelection(q: Quaternion | [number, number, number, number] | Float64Array, options?: { pivot?: Vec3Like }): void;
+    rotateSelection(q: Quaternion | [number, number, number, number] | Float64Array, options?: { pivot?: Vec3Like; sh?: boolean }): void;
     scaleSelection(s: Vec3Like, options?: { pivot?: Vec3Like }): void;
     paintSelection(rgba: PaintChannels): void;
+    /** Rotating SH coefficients on THIS renderer's device copy.  rotateSH rotates, in place, the coefficients of every SH row (or of
+     *  the selected splats' rows) by q and returns the rows rotated; the SH frame is neither read nor written.
+     *  rotateSelection(q, { pivot, sh: true }) turns the selected splats and their coefficients as one edit; it is allowed with
+     *  shFollowsTransforms on or off while the SH frame is the identity and throws otherwise -- bakeSHFrame() moves a frame that is
+     *  a rotation times a positive uniform scale into the coefficients (throws for any other frame) and returns the rotation it
+     *  used.  `sh` defaults to false: today's rotateSelection.  Each is a scene edit; an attached Scene's shs_rgb mirror is marked
+     *  stale and read back from the device on its next use. */
+    rotateSH(q: Quaternion | [number, number, number, number] | Float64Array, options?: { selected?: boolean }): number;
+    bakeSHFrame(): Quaternion;
     /** Growing THIS renderer's device copy (Scene.duplicateSelection / Scene.append grow every copy and the Scene's arrays).
      *  duplicateSelection copies the selected splats bit for bit behind the last splat; appendSelectionFrom copies the splats selected
      *  in another renderer of the same GPU, device to device (that renderer is not changed, its SH rows are not carried).  The new
@@ -555,5 +564,8 @@ export class OrbitControls {
     static applyPose(camera: Camera, alpha: number, beta: number, radius: number, target: Vector3): void;
 }
 /** Drop-in for the wasm export `sort` (wasm/wasm.cpp:8-13) on host typed arrays. */
+/** The band matrices [D_1 (3 x 3), D_2 (5 x 5), D_3 (7 x 7)], row-major, that rotate SH coefficients by q (finite, not zero;
+ *  normalised): c' = D_l c makes the colour seen from d the colour formerly seen from R(q)^T d.  A pure function: no device. */
+export function shRotation(q: Quaternion | [number, number, number, number] | Float64Array): [Float64Array, Float64Array, Float64Array];
 export function sortHost(viewProj: Float32Array, vertexCount: number, fBuffer: Float32Array,
                          depthBuffer: Uint32Array | null, depthIndex: Uint32Array): void;

@@ -1,7 +1,7 @@
 "use strict";
 // Public API: the export list of src/index.ts:1-12.  WebGLRenderer is the HIP renderer under the name callers of
 // the reference already use.
-const { HIPRenderer, sortHost } = require("./renderers/HIPRenderer");
+const { HIPRenderer, sortHost, shRotation } = require("./renderers/HIPRenderer");
 module.exports = {
     Camera: require("./cameras/Camera").Camera,
     Scene: require("./core/Scene").Scene,
@@ -17,4 +17,5 @@ module.exports = {
     ShaderPass: require("./renderers/ShaderPass").ShaderPass,
     FadeInPass: require("./renderers/FadeInPass").FadeInPass,
     sortHost: sortHost,
+    shRotation: shRotation,
 };

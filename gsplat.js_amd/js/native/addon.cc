@@ -1628,6 +1628,76 @@ napi_value PlaneAlignment(napi_env env, napi_callback_info info)
     return out;
 }
 
+// ---- rotating SH coefficients (gsr_sh_rotation, gsr_scene_rotate_sh, gsr_scene_rotate_selected_sh, gsr_scene_bake_sh_frame) ----
+napi_value f64_array(napi_env env, size_t count, double** data)
+{
+    void* p = nullptr;
+    napi_value buf, arr;
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, count * sizeof(double), &p, &buf));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_float64_array, count, buf, 0, &arr));
+    *data = (double*)p;
+    return arr;
+}
+
+// shRotation(q: Float64Array(4) (x, y, z, w)) -> Float64Array(83): D_1, D_2, D_3 row-major   (no handle: a pure function)
+napi_value ShRotation(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    const double* q = nullptr;
+    if (!get_f64_array(env, argv[0], 4, "shRotation: q must hold 4 values", &q)) return nullptr;
+    double* m = nullptr;
+    napi_value out = f64_array(env, 83, &m);
+    if (!out) return nullptr;
+    const int rc = gsr_sh_rotation(q, m);
+    return rc ? throw_gsr(env, nullptr, rc, "gsr_sh_rotation") : out;
+}
+
+// rotateSh(handle, q: Float64Array(4), scope: 0 every SH row | 1 the selected splats' rows) -> rows
+napi_value RotateSh(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    const double* q = nullptr;
+    int32_t scope;
+    if (!c || !get_f64_array(env, argv[1], 4, "rotateSh: q must hold 4 values", &q) || !get_i32(env, argv[2], &scope)) return nullptr;
+    uint32_t rows = 0;
+    const int rc = gsr_scene_rotate_sh(c, q, (uint32_t)scope, &rows);
+    return rc ? throw_gsr(env, c, rc, "gsr_scene_rotate_sh") : count_value(env, rows);
+}
+
+// rotateSelectedSh(handle, q: Float64Array(4), pivot: Float64Array(3) | null)
+napi_value RotateSelectedSh(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    const double* q = nullptr;
+    void* pivot;
+    size_t plen;
+    if (!c || !get_f64_array(env, argv[1], 4, "rotateSelectedSh: q must hold 4 values", &q) ||
+        !get_typed(env, argv[2], napi_float64_array, &pivot, &plen, true))
+        return nullptr;
+    if (pivot && plen < 3) { napi_throw_range_error(env, nullptr, "rotateSelectedSh: a pivot of 3"); return nullptr; }
+    const int rc = gsr_scene_rotate_selected_sh(c, q, (const double*)pivot);
+    return rc ? throw_gsr(env, c, rc, "gsr_scene_rotate_selected_sh") : undefined(env);
+}
+
+// bakeShFrame(handle) -> Float64Array(4): the quaternion (x, y, z, w) the coefficients were rotated by
+napi_value BakeShFrame(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    if (!c) return nullptr;
+    double* q = nullptr;
+    napi_value out = f64_array(env, 4, &q);
+    if (!out) return nullptr;
+    const int rc = gsr_scene_bake_sh_frame(c, q);
+    return rc ? throw_gsr(env, c, rc, "gsr_scene_bake_sh_frame") : out;
+}
+
 // ---- matching and registration (gsr_match / gsr_select_match / gsr_register / gsr_rigid_decompose) ----
 // what the three calls share, at argv[1 .. 6]: the target's handle, the transform (Float64Array(12), or null for the identity),
 // radius, scope, target scope and budget (a number, 0: the library's default); false: an error is pending
@@ -2141,6 +2211,7 @@ napi_value Init(napi_env env, napi_value exports)
         {"readSelection", ReadSelection}, {"eraseSelected", EraseSelected},
         {"hideSelected", HideSelected}, {"setHidden", SetHidden}, {"readHidden", ReadHidden}, {"selectHidden", SelectHidden},
         {"selectionBounds", SelectionBounds}, {"editSelected", EditSelected}, {"paintSelected", PaintSelected},
+        {"shRotation", ShRotation}, {"rotateSh", RotateSh}, {"rotateSelectedSh", RotateSelectedSh}, {"bakeShFrame", BakeShFrame},
         {"reserveScene", ReserveScene}, {"sceneCapacity", SceneCapacity}, {"duplicateSelected", DuplicateSelected}, {"appendSelected", AppendSelected},
         {"appendArrays", AppendArrays},
         {"contribReset", Call0<gsr_contrib_reset>}, {"contribAccumulate", Call0<gsr_contrib_accumulate_async>}, {"readContrib", ReadContrib},

@@ -477,11 +477,34 @@ class HIPRenderer {
             return { count, min: box.slice(0, 3), max: box.slice(3, 6) };
         };
         this.translateSelection = (v) => this._n.editSelected(this._h, 0, vec(v, 3), null);
-        this.rotateSelection = (q, options) => this._n.editSelected(this._h, 1, vec(q, 4), pivotOf(options));
+        // { sh: true }: the selected splats' SH coefficients turn with them (gsr_scene_rotate_selected_sh, below); default: today's path
+        this.rotateSelection = (q, options) => {
+            if (!(options && options.sh)) return this._n.editSelected(this._h, 1, vec(q, 4), pivotOf(options));
+            this._n.rotateSelectedSh(this._h, vec(q, 4), pivotOf(options));
+            shTurned(false);
+        };
         this.scaleSelection = (s, options) => this._n.editSelected(this._h, 2, vec(s, 3), pivotOf(options));
         this.paintSelection = (rgba) => {
             const [value, byteMask] = Scene.rgbaWord(rgba);
             this._n.paintSelected(this._h, value, byteMask);
+        };
+        // ---- rotating SH coefficients (gsr_scene_rotate_sh / _rotate_selected_sh / _bake_sh_frame): a selection turns with its SH colour ----
+        //   renderer.selectRegion(lasso); renderer.rotateSelection(q, { pivot, sh: true });    // the highlights turn with the object
+        //   renderer.bakeSHFrame();               // first, where a followed scene.rotate has left a frame: it moves into the coefficients
+        // rotateSH(q, { selected }) rotates the coefficients alone -- every SH row, or the selected splats' rows -- and returns the
+        // rows rotated; the SH frame is neither read nor written.  rotateSelection(q, { sh: true }) needs the identity frame, which
+        // bakeSHFrame() makes of any frame that is a rotation times a uniform scale; it returns the Quaternion it rotated by.  These
+        // act on THIS renderer's device copy; an attached Scene's shs_rgb mirror is marked stale and read back on its next use.
+        const shTurned = (baked) => { if (activeScene && activeScene._deviceTurnedSh) activeScene._deviceTurnedSh(baked); };
+        this.rotateSH = (q, options) => {
+            const rows = this._n.rotateSh(this._h, vec(q, 4), options && options.selected ? 1 : 0);
+            shTurned(false);
+            return rows;
+        };
+        this.bakeSHFrame = () => {
+            const q = this._n.bakeShFrame(this._h);
+            shTurned(true);
+            return new Quaternion(q[0], q[1], q[2], q[3]);
         };
         // ---- growing the scene (gsr_scene_reserve / _capacity / _duplicate_selected / _append_selected): copies and pasted splats ----
         //   renderer.selectRegion(lasso); const { first, count } = renderer.duplicateSelection();   // the copies are now the selection ...
@@ -844,4 +867,12 @@ function sortHost(viewProj, vertexCount, fBuffer, depthBuffer, depthIndex) {
     loadNative().sortHost(viewProj, vertexCount, fBuffer, depthBuffer || null, depthIndex);
 }
 
-module.exports = { HIPRenderer, sortHost };
+// The band matrices that rotate SH coefficients by q = (x, y, z, w) (gsr_sh_rotation; a pure function, no device): Float64Array views
+// of D_1 (3 x 3), D_2 (5 x 5) and D_3 (7 x 7), row-major.  q must be finite and not zero; it is normalised.
+function shRotation(q) {
+    const v = Array.isArray(q) || ArrayBuffer.isView(q) ? new Float64Array(q) : new Float64Array([q.x, q.y, q.z, q.w]);
+    const m = loadNative().shRotation(v);
+    return [m.subarray(0, 9), m.subarray(9, 34), m.subarray(34, 83)];
+}
+
+module.exports = { HIPRenderer, sortHost, shRotation };

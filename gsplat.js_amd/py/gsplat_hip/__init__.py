@@ -244,6 +244,16 @@ def rigid_decompose(M):
     return q, t
 
 
+def sh_rotation(q_xyzw):
+    """(D_1 float64[3, 3], D_2 float64[5, 5], D_3 float64[7, 7]) of gsr_sh_rotation: the band matrices that rotate SH coefficients
+    by the rotation of q = (x, y, z, w) (finite, not zero; normalised in f64).  Needs the library, not a device."""
+    L = load_library()
+    q = np.ascontiguousarray(q_xyzw, dtype=np.float64).reshape(4)
+    m = np.zeros(83, np.float64)
+    _pure("gsr_sh_rotation", L.gsr_sh_rotation(q.ctypes.data, m.ctypes.data))
+    return m[:9].reshape(3, 3), m[9:34].reshape(5, 5), m[34:].reshape(7, 7)
+
+
 def attr_edges(lo, hi, bins):
     """The bins + 1 edges of gsr_attr_histogram, by the header's f64 rule: w = (hi - lo) / bins, edge(k) = min(lo + k * w, hi) and
     edge(bins) = hi.  select_attr(attr, edges[a], edges[b]) selects exactly sum(counts[a:b]) splats."""
@@ -290,6 +300,7 @@ EXPORTS = [
     "gsr_select_region", "gsr_select_box", "gsr_selection_set", "gsr_selection_invert", "gsr_read_selection", "gsr_scene_erase_selected",
     "gsr_hide_selected", "gsr_hidden_set", "gsr_read_hidden", "gsr_select_hidden",
     "gsr_selection_bounds", "gsr_scene_translate_selected", "gsr_scene_rotate_selected", "gsr_scene_scale_selected", "gsr_scene_set_rgba_selected",
+    "gsr_sh_rotation", "gsr_scene_rotate_sh", "gsr_scene_rotate_selected_sh", "gsr_scene_bake_sh_frame",
     "gsr_scene_reserve", "gsr_scene_capacity", "gsr_scene_duplicate_selected", "gsr_scene_append_selected", "gsr_scene_append_arrays",
     "gsr_contrib_reset", "gsr_contrib_accumulate_async", "gsr_read_contrib", "gsr_select_contrib",
     "gsr_attr_stats", "gsr_attr_histogram", "gsr_select_attr",
@@ -304,6 +315,7 @@ EXPORTS = [
 ]
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p)
 GSR_COMM_ID_BYTES = 128
+GSR_SH_ALL, GSR_SH_SELECTED = 0, 1   # gsr_scene_rotate_sh's scope
 PICK_DTYPE = np.dtype([("index", np.uint32), ("depth", np.float32), ("mean", np.float32), ("alpha", np.float32)])   # gsr_pick_result
 
 
@@ -447,6 +459,10 @@ def load_library(path=None):
     L.gsr_selection_bounds.argtypes = [vp, ctypes.POINTER(GsrSelectionBounds)]
     L.gsr_scene_translate_selected.argtypes = [vp, vp]
     L.gsr_scene_rotate_selected.argtypes = [vp, vp, vp]
+    L.gsr_sh_rotation.argtypes = [vp, vp]
+    L.gsr_scene_rotate_sh.argtypes = [vp, vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+    L.gsr_scene_rotate_selected_sh.argtypes = [vp, vp, vp]
+    L.gsr_scene_bake_sh_frame.argtypes = [vp, vp]
     L.gsr_scene_scale_selected.argtypes = [vp, vp, vp]
     L.gsr_scene_set_rgba_selected.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32]
     L.gsr_scene_reserve.argtypes = [vp, ctypes.c_uint32]
@@ -1178,6 +1194,29 @@ class HIPRenderer:
         q = np.ascontiguousarray(q_xyzw, dtype=np.float64).reshape(4)
         p = self._pivot(pivot)
         self._check(self._L.gsr_scene_rotate_selected(self._ctx, q.ctypes.data, None if p is None else p.ctypes.data))
+
+    # -- rotating SH coefficients (gsr_scene_rotate_sh / _rotate_selected_sh / _bake_sh_frame) --
+    def scene_rotate_sh(self, q_xyzw, selected=False):
+        """Rotate, in place, the SH coefficients of every SH row (or of the selected splats' rows) by q = (x, y, z, w); returns the
+        rows rotated.  Acts in the coefficients' own frame: the SH frame is neither read nor written.  A scene edit."""
+        q = np.ascontiguousarray(q_xyzw, dtype=np.float64).reshape(4)
+        rows = ctypes.c_uint32(0)
+        self._check(self._L.gsr_scene_rotate_sh(self._ctx, q.ctypes.data, GSR_SH_SELECTED if selected else GSR_SH_ALL, ctypes.byref(rows)))
+        return rows.value
+
+    def scene_rotate_selected_sh(self, q_xyzw, pivot=None):
+        """scene_rotate_selected and the selected splats' SH coefficients with it, as one edit.  Allowed with set_sh_follow on or
+        off while the SH frame is the identity (scene_bake_sh_frame makes it one); without SH rows it is scene_rotate_selected."""
+        q = np.ascontiguousarray(q_xyzw, dtype=np.float64).reshape(4)
+        p = self._pivot(pivot)
+        self._check(self._L.gsr_scene_rotate_selected_sh(self._ctx, q.ctypes.data, None if p is None else p.ctypes.data))
+
+    def scene_bake_sh_frame(self):
+        """Move an SH frame that is a rotation times a positive uniform scale into the coefficients; the frame becomes the identity.
+        Returns the quaternion (x, y, z, w) float64[4] the coefficients were rotated by ((0, 0, 0, 1) for an identity frame)."""
+        q = np.zeros(4, dtype=np.float64)
+        self._check(self._L.gsr_scene_bake_sh_frame(self._ctx, q.ctypes.data))
+        return q
 
     def scene_scale_selected(self, s, pivot=None):
         """scene_scale on the selected splats only; pivot as in scene_rotate_selected.  Components must be finite; 0 is allowed."""

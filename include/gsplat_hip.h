@@ -656,6 +656,55 @@ int gsr_scene_rotate_selected(gsr_ctx *ctx, const double *q /* 4: x, y, z, w */,
 int gsr_scene_scale_selected(gsr_ctx *ctx, const double *s /* 3 */, const double *pivot /* 3, or NULL */);
 int gsr_scene_set_rgba_selected(gsr_ctx *ctx, uint32_t rgba, uint32_t byte_mask);
 
+/* ---- rotating SH coefficients ---- a selection turns with its SH colour; a frame is baked into the coefficients
+ * The SH frame (gsr_set_sh_follow, above) is one matrix per scene: it answers whole-scene edits and has no answer for "turn these
+ * splats about their own centre".  These calls rotate the coefficients themselves, per splat, on the device (DESIGN.md section 4,
+ * "Rotating SH coefficients").
+ * Basis: B_1 .. B_15 are the direction factors of eval_sh_rgb exactly as vertex.glsl.ts:72-98 writes them, constants and signs
+ *   included: band 1 is -C1*y, -C1*z, +C1*x; band 2 is C2[0]*xy .. C2[4]*(xx-yy); band 3 is C3[0]*y*(3xx-yy) .. C3[6]*x*(xx-3yy).
+ *   A channel's colour is C0*c_0 + sum c_k B_k(d) + 0.5.
+ * Matrices: for a rotation R the band matrices D_1 (3x3), D_2 (5x5), D_3 (7x7) are the unique matrices for which c' = D_l c gives
+ *   sum c'_k B_k(R d) = sum c_k B_k(d) for every unit d: after the edit, the colour seen from d is the colour formerly seen from
+ *   R^T d, which is what the SH frame does with linv = R^T.  The B_k are +- the orthonormal real SH, so every D_l is orthogonal.
+ * gsr_sh_rotation(q, m) is a pure host function that needs no GPU and no context: q = (x, y, z, w) must be finite and non-zero
+ *   (GSR_ERR_ARG otherwise; the message is read with gsr_last_error(NULL)); it is normalised in f64, |q| = sqrt(((xx+yy)+zz)+ww);
+ *   R is the matrix gsr_scene_rotate builds of the normalised q; m receives D_1, D_2, D_3 row-major, one after the other
+ *   (9 + 25 + 49 = 83 doubles).  x = y = z = 0 yields the exact identity.  Each D_l solves the normal equations of
+ *   Y_l(S)^T D_l = Y_l(R^T S)^T in f64 over S, 24 Fibonacci-sphere directions (phi = acos(1 - 2(i+0.5)/24),
+ *   theta = pi(1+sqrt 5)(i+0.5)); orthogonality, composition and the defining property hold to 2^-40.
+ * Apply: one SH row and one channel is 8 words, half 2j in the low 16 bits of word j.  c_j is the half's value, exact; M = (float)m,
+ *   rounded once; in f32, uncontracted, per band and for k in band order: s = M[k][j0]*c[j0]; s = s + M[k][j]*c[j] with j ascending
+ *   over the band; s is stored as a half rounded to nearest even, subnormals kept, overflow to infinity, any NaN stored as 0x7e00.
+ *   Half 0 (DC) keeps its bits.  All three bands are always rotated; a splat's degree only decides which bands the shader reads.
+ *   (Uploads truncate; the rotation rounds to nearest, because repeated truncation shrinks coefficients under repeated edits.)
+ * gsr_scene_rotate_sh rotates, in place, the coefficients of the SH rows in scope: every SH row (GSR_SH_ALL), or the rows of the
+ *   selected splats i > band_index[0] (GSR_SH_SELECTED; selected splats without an SH row are not touched).  rows (may be NULL)
+ *   receives the number of rows rotated; for GSR_SH_SELECTED it is counted on the device and copied back, the call's one wait.
+ *   It acts in the coefficients' own frame and never reads or writes linv.  No SH state, or GSR_SH_SELECTED with no selection
+ *   buffers: GSR_OK, rows = 0, no kernel is launched.  An unknown scope or a bad q: GSR_ERR_ARG, nothing touched.
+ * Ordering: a scene edit, ordered and marked exactly like gsr_scene_set_rgba_selected: the context's stream, events among the
+ *   members of a shared scene, every member's frame and sorted order marked as edited.  The SH textures are per-scene state, so one
+ *   call serves every member.  The selection, the hidden set, the accumulators, the frame and the follow switch are untouched.
+ * gsr_scene_rotate_selected_sh is gsr_scene_rotate_selected(q, pivot) followed by gsr_scene_rotate_sh(q, GSR_SH_SELECTED), as one
+ *   edit: the geometry goes through the same kernel with q as given, the coefficients use the normalised q.  It is allowed with
+ *   follow on or off, provided the SH frame is the identity; otherwise GSR_ERR_ARG with a message naming
+ *   gsr_scene_bake_sh_frame, and nothing is touched.  Without SH rows it is gsr_scene_rotate_selected.
+ *   gsr_scene_rotate_selected itself keeps its refusal.
+ * gsr_scene_bake_sh_frame moves a frame that is a rotation times a positive uniform scale into the coefficients:
+ *   s2 = (sum linv_ij^2) / 3; GSR_ERR_ARG with nothing changed unless max |(linv . linv^T)_ij / s2 - delta_ij| <= 2^-20 and
+ *   det > 0 (a condition, not a measurement: the projection rounds the frame to f32, so a frame within 2^-20 of a scaled rotation
+ *   is one as far as any direction it produces goes; a frame that holds a non-uniform scale has no rotation).  Q = linv / sqrt(s2);
+ *   q_used (4, may be NULL) is the quaternion of Q^T by Shepperd's four branches as gsr_rigid_decompose states them; then
+ *   gsr_scene_rotate_sh(q_used, GSR_SH_ALL), and the frame becomes the identity.  An identity frame: GSR_OK, q_used = (0, 0, 0, 1),
+ *   nothing launched.
+ * A NULL ctx or a NULL q returns GSR_ERR_ARG with nothing touched. */
+#define GSR_SH_ALL      0u
+#define GSR_SH_SELECTED 1u
+int gsr_sh_rotation(const double *q /* 4: x, y, z, w */, double *m /* 83 */);
+int gsr_scene_rotate_sh(gsr_ctx *ctx, const double *q /* 4: x, y, z, w */, uint32_t scope /* GSR_SH_ALL | GSR_SH_SELECTED */, uint32_t *rows);
+int gsr_scene_rotate_selected_sh(gsr_ctx *ctx, const double *q /* 4: x, y, z, w */, const double *pivot /* 3, or NULL */);
+int gsr_scene_bake_sh_frame(gsr_ctx *ctx, double *q_used /* 4, may be NULL */);
+
 /* ---- growing the scene ---- duplicate the selection, append another scene's selected splats or rows from the host, reserve capacity
  * Every call above keeps the splat count or lowers it.  These raise it on the device: copy an object, paste one capture's splats
  * into another scene, add rows -- with no gsr_read_scene / host loop / gsr_set_scene_arrays round trip (which re-uploads and

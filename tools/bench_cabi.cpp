@@ -3,7 +3,7 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--plane THRESHOLD[:HYPOTHESES]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--register RADIUS[:ITERATIONS]] [--merge CELL] [--share-scene]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--rotate-sh FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--plane THRESHOLD[:HYPOTHESES]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--register RADIUS[:ITERATIONS]] [--merge CELL] [--share-scene]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
@@ -36,6 +36,10 @@
 // --edit-selected FRACTION selects that fraction of the splats (scattered over the indices) through gsr_selection_set on every device
 // copy and adds a leg with a gsr_scene_rotate_selected by one degree about y, pivoted, behind every frame: only the selection turns.
 // The report carries the leg's rate and `edit_ms`, the wall time a frame of that leg takes beyond a frame of the plain timed loop.
+// --rotate-sh FRACTION, after the frame legs: gives every splat an SH row (seeded halves; bandsIndices -1, n / 3, 2n / 3), selects
+// that fraction of the splats (scattered over the indices) and reports the blocking time (the call and gsr_sync, the median of five)
+// of gsr_scene_rotate_sh over every row, of gsr_scene_rotate_sh over the selected rows with its count, and of
+// gsr_scene_rotate_selected_sh (the selected splats turned about a pivot with their coefficients), with the rows rotated.
 // --histogram ATTR[:BINS] (x, y, z, distance, red, green, blue, opacity, scale_x .. scale_max, contrib_weight .. contrib_pixels; 256
 // bins unless given; the contribution attributes go beside --contrib) asks the scene about itself: gsr_attr_stats, a
 // gsr_attr_histogram over [min, max] and a gsr_select_attr of the middle half of the bins, [edge(bins / 4), edge(bins - bins / 4)).
@@ -205,6 +209,7 @@ int main(int argc, char** argv)
     double hide_fraction = -1.0;   // < 0: off
     bool hide_edits = false;
     double edit_fraction = -1.0;   // < 0: off
+    double rotate_sh_fraction = -1.0;   // < 0: off
     double duplicate_fraction = -1.0;   // < 0: off
     bool reserve = false;
     std::string histogram_attr;         // empty: off
@@ -242,6 +247,7 @@ int main(int argc, char** argv)
         else if (a == "--overlay" && i + 1 < argc) { overlay_fraction = std::atof(argv[++i]); if (!(overlay_fraction >= 0.0 && overlay_fraction <= 1.0)) { std::fprintf(stderr, "--overlay FRACTION must be in [0, 1]\n"); return 2; } }
         else if (a == "--hide" && i + 1 < argc) { hide_fraction = std::atof(argv[++i]); if (!(hide_fraction >= 0.0 && hide_fraction <= 1.0)) { std::fprintf(stderr, "--hide FRACTION must be in [0, 1]\n"); return 2; } }
         else if (a == "--hide-edits") hide_edits = true;
+        else if (a == "--rotate-sh" && i + 1 < argc) { rotate_sh_fraction = std::atof(argv[++i]); if (!(rotate_sh_fraction >= 0.0 && rotate_sh_fraction <= 1.0)) { std::fprintf(stderr, "--rotate-sh FRACTION must be in [0, 1]\n"); return 2; } }
         else if (a == "--edit-selected" && i + 1 < argc) { edit_fraction = std::atof(argv[++i]); if (!(edit_fraction >= 0.0 && edit_fraction <= 1.0)) { std::fprintf(stderr, "--edit-selected FRACTION must be in [0, 1]\n"); return 2; } }
         else if (a == "--histogram" && i + 1 < argc) {
             histogram_attr = argv[++i];
@@ -295,7 +301,7 @@ int main(int argc, char** argv)
         else if (a == "--scene-edit") scene_edit = next();
         else if (a == "--share-scene") share_scene = true;
         else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--plane THRESHOLD[:HYPOTHESES]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--register RADIUS[:ITERATIONS]] [--merge CELL] [--share-scene]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--rotate-sh FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--plane THRESHOLD[:HYPOTHESES]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--register RADIUS[:ITERATIONS]] [--merge CELL] [--share-scene]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
@@ -626,6 +632,49 @@ int main(int argc, char** argv)
         for (gsr_ctx* c : ctx) { ctx0 = c; CHECK(gsr_sync(c)); }
         edit_selected_sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - e0).count();
     }
+    // --rotate-sh: the SH rows rotated on the device; behind the frame legs, which render the scene without SH
+    double rotate_sh_all_ms = 0, rotate_sh_selected_ms = 0, rotate_selected_sh_ms = 0;
+    uint32_t rotate_sh_rows_all = 0, rotate_sh_rows = 0;
+    if (rotate_sh_fraction >= 0.0) {
+        ctx0 = ctx[0];
+        {
+            std::vector<uint32_t> tex[3];
+            uint32_t state = 0x9e3779b9u;
+            for (auto& t : tex) {
+                t.resize((size_t)n * 8);
+                for (uint32_t& w : t) {   // two halves in (-1, 1): sign, exponent 8 .. 14, any mantissa
+                    state = state * 1664525u + 1013904223u;
+                    const uint32_t lo = (state >> 8) & 0xffffu, hi = (state >> 16) ^ (state & 0xffffu);
+                    auto half = [](uint32_t v) { return (v & 0x83ffu) | ((8u + ((v >> 10) & 31u) % 7u) << 10); };
+                    w = half(lo) | (half(hi) << 16);
+                }
+            }
+            const int32_t band[3] = {-1, (int32_t)(n / 3), (int32_t)(2 * (n / 3))};
+            CHECK(gsr_set_scene_sh(ctx[0], tex[0].data(), tex[1].data(), tex[2].data(), n, band));
+        }
+        std::vector<uint32_t> words((n + 31) / 32, 0u);
+        const uint64_t limit = (uint64_t)(rotate_sh_fraction * 4294967296.0);
+        for (uint32_t i = 0; i < n; i++)
+            if ((uint64_t)((i + 0x85ebca6bu) * 2654435761u) < limit) words[i >> 5] |= 1u << (i & 31);
+        CHECK(gsr_selection_set(ctx[0], words.data(), (uint32_t)words.size(), GSR_SELOP_REPLACE, nullptr));
+        const double half = 0.5 * 3.14159265358979323846 / 180.0, dq[4] = {0.0, std::sin(half), 0.0, std::cos(half)}, pivot[3] = {0.5, 0.0, -0.5};
+        auto median_ms = [&](auto call, double* out) -> int {
+            double t[5];
+            for (double& v : t) {
+                if (int rc = gsr_sync(ctx[0])) return rc;
+                const auto t0 = std::chrono::steady_clock::now();
+                if (int rc = call()) return rc;
+                if (int rc = gsr_sync(ctx[0])) return rc;
+                v = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3;
+            }
+            std::sort(t, t + 5);
+            *out = t[2];
+            return 0;
+        };
+        CHECK(median_ms([&] { return gsr_scene_rotate_sh(ctx[0], dq, GSR_SH_ALL, &rotate_sh_rows_all); }, &rotate_sh_all_ms));
+        CHECK(median_ms([&] { return gsr_scene_rotate_sh(ctx[0], dq, GSR_SH_SELECTED, &rotate_sh_rows); }, &rotate_sh_selected_ms));
+        CHECK(median_ms([&] { return gsr_scene_rotate_selected_sh(ctx[0], dq, pivot); }, &rotate_selected_sh_ms));
+    }
     // --hide-edits (last: it removes splats): the wall time of one gsr_hide_selected that hides a fifth of the scene, and of one
     // gsr_scene_erase_selected of another fifth while those are hidden (the compaction carries the hidden set: k_box_compact_bits)
     double hide_selected_ms = 0, erase_hidden_ms = 0, erase_plain_ms = 0;
@@ -897,6 +946,9 @@ int main(int argc, char** argv)
     if (edit_fraction >= 0.0)
         std::printf(", \"edit_selected_fraction\": %g, \"edit_selected\": %u, \"frames_per_sec_edit_selected\": %.1f, \"edit_ms\": %.4f", edit_fraction,
                     edit_selected, frames / edit_selected_sec, (edit_selected_sec - sec) / frames * 1e3);
+    if (rotate_sh_fraction >= 0.0)
+        std::printf(", \"rotate_sh\": {\"fraction\": %g, \"rows_all\": %u, \"all_ms\": %.4f, \"rows_selected\": %u, \"selected_ms\": %.4f, \"rotate_selected_sh_ms\": %.4f}",
+                    rotate_sh_fraction, rotate_sh_rows_all, rotate_sh_all_ms, rotate_sh_rows, rotate_sh_selected_ms, rotate_selected_sh_ms);
     auto json_num = [](double v) -> std::string {   // (an empty box is (+inf, -inf): not JSON numbers)
         char buf[40];
         std::snprintf(buf, sizeof buf, "%.17g", v);
