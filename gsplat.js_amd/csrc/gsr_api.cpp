@@ -177,6 +177,7 @@ int gsr_destroy(gsr_ctx* c)
     for (auto& e : c->nb.ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->cl.ev) if (e) (void)hipEventDestroy(e);
     if (c->knn.ev) (void)hipEventDestroy(c->knn.ev);
+    for (auto& e : c->nm.ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->pl.ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->mt.ev) if (e) (void)hipEventDestroy(e);
     if (c->words.fstate_host) (void)hipHostFree(c->words.fstate_host);

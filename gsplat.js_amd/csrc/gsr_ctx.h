@@ -543,6 +543,18 @@ struct gsr_ctx {
         float ms[2] = {0.0f, 0.0f};             // index with its bound, fill and walk of the last call (gsr_debug_knn_times)
     } knn;
 
+    // normals (gsr_normals.cpp): what gsr_normals / gsr_select_normal hold beside the neighbour scratch, the context's own; the
+    // first such call allocates it, it only grows, and the context's end frees it
+    struct Normals {
+        gsr::DevBuf<uint32_t> words;            // NORMAL_INFO_WORDS of NormalInfo
+        gsr::DevBuf<float> normals;             // 3 * `rows`
+        gsr::DevBuf<double> variation;          // `rows` each: the variation and the lists' lengths by splat
+        gsr::DevBuf<uint32_t> found;
+        uint32_t rows = 0;
+        hipEvent_t ev[2] = {nullptr, nullptr};  // in front of the OWN kernel; behind the walk or the OWN kernel
+        float ms[2] = {0.0f, 0.0f};             // index with its bound (0 for OWN), fill and walk of the last call (gsr_debug_normals_times)
+    } nm;
+
     // merging cells (gsr_merge.cpp): what gsr_cells / gsr_scene_merge_cells hold beside the neighbour scratch, the context's own; the
     // first such call allocates it, it only grows, and the context's end frees it
     struct Merge {

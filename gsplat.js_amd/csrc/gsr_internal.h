@@ -670,6 +670,39 @@ void launch_knn(const NbIndex& ix, uint32_t indexed, uint32_t n, uint32_t k, int
 // scratch <- the splats i < n in scope with lo <= values[i] && (values[i] < hi || open_hi): every word of it is stored
 void launch_knn_select(const double* values, const AttrScope& sc, uint32_t n, double lo, double hi, bool open_hi, uint32_t* scratch, uint32_t nwords, hipStream_t s);
 
+// Normals (k_normals.hip; DESIGN.md section 4, "Normals"): per splat in scope a unit normal (3 f32), the surface variation (f64) and
+// the list length, from the PCA of the k nearest within `radius` over the index above or from the splat's own shortest axis; and
+// the splats whose n . axis, |n . axis| or variation lies in a closed range as a picker.
+constexpr int NORMAL_KNN = 0, NORMAL_OWN = 1;                              // GSR_NORMAL_KNN / GSR_NORMAL_OWN
+constexpr int NORMAL_DOT = 0, NORMAL_ABS_DOT = 1, NORMAL_VARIATION = 2;    // GSR_NORMAL_DOT / _ABS_DOT / _VARIATION
+constexpr uint32_t NORMAL_MIN_K = 2;                                        // a normal needs two neighbours
+// the device words of one call, zeroed by the host in front of the kernels.  A variation is a non-negative double, so min and max
+// go through bit patterns as KnnInfo's do (0: no valid row).  in_scope and nonfinite are the OWN source's; the KNN source takes
+// them from the index.
+struct NormalInfo {
+    uint32_t valid, in_scope, nonfinite, pad;
+    unsigned long long nvmin, vmax;
+};
+struct NormalArrays {
+    float* normals;                        // 3 n
+    double* variation;                     // n
+    uint32_t* found;                       // n
+    NormalInfo* info;
+};
+struct NormalOrient { uint32_t oriented; double tx, ty, tz; };   // oriented != 0: normals face the viewpoint (tx, ty, tz)
+// every row as a splat outside the index has it: three quiet NaNs, a NaN variation, found 0
+void launch_normals_fill(uint32_t n, const NormalArrays& a, int cu_count, hipStream_t s);
+// the walk: normal, variation and found of every entry at its splat's row; a.info += valid, min and max.  indexed, n as
+// launch_nb_count's; px / py / pz: the scene's positions, gathered by the listed indices.  k in NORMAL_MIN_K .. KNN_MAX_K.
+void launch_normals_knn(const NbIndex& ix, uint32_t indexed, uint32_t n, uint32_t k, const float* px, const float* py, const float* pz, const NormalOrient& o,
+                        const NormalArrays& a, int cu_count, hipStream_t s);
+// every row from the splat's own rotation and scale; a.info += in_scope, nonfinite, valid, min and max
+void launch_normals_own(const SceneDev& scene, const AttrScope& sc, uint32_t n, const NormalOrient& o, const NormalArrays& a, int cu_count, hipStream_t s);
+// scratch <- the splats i < n with lo <= value_i && value_i <= hi, the value from the stored rows (axis: 3 f64 on the host, null
+// for NORMAL_VARIATION): every word of it is stored
+void launch_normals_select(const float* normals, const double* variation, uint32_t n, int stat, const double* axis, double lo, double hi, uint32_t* scratch,
+                           uint32_t nwords, hipStream_t s);
+
 // Merging cells (k_merge.hip; DESIGN.md section 4, "Merging cells"): the candidates of every cell of a uniform grid -- the splats
 // in scope whose ten floats are finite -- found through the index above with inv_h = 1 / cell, and every cell of two or more merged
 // into one splat by moment matching, written at its leader's row (the smallest member index).

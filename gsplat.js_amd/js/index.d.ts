@@ -118,6 +118,11 @@ export type KnnStat = "kth" | "mean";
 export interface KnnOptions { k?: number; stat?: KnnStat; scope?: NeighbourScope | NeighbourScope[]; budget?: number }
 export interface SplatKnn { found: Uint32Array; values: Float64Array; hist: Uint32Array; idx?: Uint32Array; d2?: Float64Array; inScope: number; nonfinite: number;
     pairBound: number; complete: number; finiteValues: number; valueMin: number; valueMax: number }
+export type NormalSource = "knn" | "own";
+export type NormalStat = "dot" | "abs_dot" | "variation";
+export interface NormalOptions { k?: number; source?: NormalSource; toward?: ArrayLike<number>; scope?: NeighbourScope | NeighbourScope[]; budget?: number }
+export interface SplatNormals { normals: Float32Array; variation: Float64Array; found: Uint32Array; inScope: number; nonfinite: number; pairBound: number;
+    valid: number; variationMin: number; variationMax: number }
 export interface CellOptions { scope?: NeighbourScope | NeighbourScope[]; budget?: number }
 export interface CellInfo { inScope: number; candidates: number; cells: number; mergedCells: number; mergedMembers: number; largest: number; rowsAfter: number;
     pairBound: number }
@@ -470,6 +475,19 @@ export class HIPRenderer {
     splatKnn(radius: number, options?: KnnOptions & { lists?: boolean }): SplatKnn;
     selectKnn(radius: number, options?: KnnOptions & { lo?: number; hi?: number; op?: SelectOp }): number;
     selectStatisticalOutliers(radius: number, options?: { k?: number; stdRatio?: number; scope?: NeighbourScope | NeighbourScope[]; budget?: number; op?: SelectOp }): { selected: number; threshold: number };
+    /** Normals: a unit surface normal per splat in scope, row i of normals at [3 * i].  source "knn" (the default): the eigenvector
+     *  of the smallest eigenvalue of the covariance of the splat and its k (2 .. 32, default 8) nearest others in scope within
+     *  `radius` (splatKnn's lists; at least two are needed); "own": the splat's own shortest axis, no index and no walk (radius is
+     *  not read; the scene must carry rotations and scales).  variation[i] = l_min / (l_0 + l_1 + l_2): 0 on a plane, large at edges
+     *  and corners.  toward: [x, y, z]: every normal faces that viewpoint; without it the first non-zero component is positive.  A
+     *  splat without a normal holds NaN in both; found[i] = the length of its list (0 for "own"); valid = the splats with a normal,
+     *  variationMin / variationMax over them.  selectNormal picks lo <= value <= hi, both ends closed (lo default -Infinity, hi
+     *  default Infinity), the value computed from the stored float32 normal: "dot" n . axis, "abs_dot" |n . axis| (for normals that
+     *  are not oriented: selectNormal("abs_dot", { axis: up, hi: 0.2, radius }) is "the walls"), "variation" (no axis); axis is
+     *  used as given, not normalised.  It folds them into the selection with `op` and returns the number of selected splats.
+     *  Both index the device scene as it is now; budget as splatNeighbours. */
+    splatNormals(radius: number | undefined, options?: NormalOptions): SplatNormals;
+    selectNormal(stat: NormalStat, options?: NormalOptions & { radius?: number; axis?: ArrayLike<number>; lo?: number; hi?: number; op?: SelectOp }): number;
     /** Merging cells: voxel simplification of this renderer's device copy.  The candidates -- the splats in scope with finite
      *  position, rotation and scale -- fall into the cells of a grid of side `cell`.  splatCells is the report: hist[k] = the cells
      *  with k members (hist[cap]: cap or more; cap 1 .. 4095, default 64), with leaders: true leader[i] = the smallest candidate

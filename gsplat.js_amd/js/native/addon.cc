@@ -2027,6 +2027,78 @@ napi_value SelectKnn(napi_env env, napi_callback_info info)
     return rc ? throw_gsr(env, c, rc, "gsr_select_knn") : count_value(env, count);
 }
 
+// ---- normals (gsr_normals / gsr_select_normal) ----
+// the options of the two calls below from argv[1 .. 9]: source, radius, k, scope, budget (a number, 0: the library's default),
+// oriented, and the three components of the viewpoint; false: an error is pending
+bool get_normal_options(napi_env env, napi_value* argv, gsr_normal_options* o)
+{
+    double b;
+    int32_t oriented;
+    if (!get_i32(env, argv[1], &o->source) || !get_f64(env, argv[2], &o->radius) || napi_get_value_uint32(env, argv[3], &o->k) != napi_ok ||
+        napi_get_value_uint32(env, argv[4], &o->scope) != napi_ok || !get_f64(env, argv[5], &b) || !get_i32(env, argv[6], &oriented) ||
+        !get_f64(env, argv[7], &o->toward[0]) || !get_f64(env, argv[8], &o->toward[1]) || !get_f64(env, argv[9], &o->toward[2])) {
+        napi_throw_type_error(env, nullptr, "normals: source, radius, k, scope, budget, oriented and toward must be numbers");
+        return false;
+    }
+    if (!(b >= 0.0 && b <= 18446744073709549568.0)) { napi_throw_range_error(env, nullptr, "normals: budget must be a non-negative number"); return false; }
+    o->budget = (uint64_t)b;
+    o->oriented = oriented ? 1u : 0u;
+    return true;
+}
+
+// normals(handle, source, radius, k, scope, budget, oriented, tx, ty, tz) -> { normals: Float32Array(3 n), variation: Float64Array(n),
+// found: Uint32Array(n); inScope, nonfinite, pairBound, budget, valid, variationMin, variationMax }
+napi_value Normals(napi_env env, napi_callback_info info)
+{
+    napi_value argv[10];
+    if (!get_args(env, info, 10, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    gsr_normal_options o{};
+    if (!c || !get_normal_options(env, argv, &o)) return nullptr;
+    uint32_t n = 0;
+    int rc = gsr_scene_count(c, &n);
+    if (rc) return throw_gsr(env, c, rc, "gsr_scene_count");
+    void *normals = nullptr, *variation = nullptr, *found = nullptr;
+    napi_value nb, narr, vb, varr, fb, farr, out;
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, (size_t)n * 12, &normals, &nb));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_float32_array, (size_t)n * 3, nb, 0, &narr));
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, (size_t)n * 8, &variation, &vb));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_float64_array, n, vb, 0, &varr));
+    NAPI_OK_OR_NULL(env, napi_create_arraybuffer(env, (size_t)n * 4, &found, &fb));
+    NAPI_OK_OR_NULL(env, napi_create_typedarray(env, napi_uint32_array, n, fb, 0, &farr));
+    gsr_normal_info ni{};
+    rc = gsr_normals(c, &o, n ? (float*)normals : nullptr, n ? (double*)variation : nullptr, n ? (uint32_t*)found : nullptr, n, &ni);
+    if (rc) return throw_gsr(env, c, rc, "gsr_normals");
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "normals", narr));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "variation", varr));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "found", farr));
+    if (!set_u32(env, out, "inScope", ni.in_scope) || !set_u32(env, out, "nonfinite", ni.nonfinite) || !set_f64(env, out, "pairBound", (double)ni.pair_bound) ||
+        !set_f64(env, out, "budget", (double)ni.budget) || !set_u32(env, out, "valid", ni.valid) || !set_f64(env, out, "variationMin", ni.variation_min) ||
+        !set_f64(env, out, "variationMax", ni.variation_max)) return nullptr;
+    return out;
+}
+
+// selectNormal(handle, source, radius, k, scope, budget, oriented, tx, ty, tz, stat, hasAxis, ax, ay, az, lo, hi, op) -> selected
+napi_value SelectNormal(napi_env env, napi_callback_info info)
+{
+    napi_value argv[18];
+    if (!get_args(env, info, 18, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    gsr_normal_options o{};
+    if (!c || !get_normal_options(env, argv, &o)) return nullptr;
+    int32_t stat, has_axis, op;
+    double axis[3], lo, hi;
+    if (!get_i32(env, argv[10], &stat) || !get_i32(env, argv[11], &has_axis) || !get_f64(env, argv[12], &axis[0]) || !get_f64(env, argv[13], &axis[1]) ||
+        !get_f64(env, argv[14], &axis[2]) || !get_f64(env, argv[15], &lo) || !get_f64(env, argv[16], &hi) || !get_i32(env, argv[17], &op)) {
+        napi_throw_type_error(env, nullptr, "selectNormal: stat, axis, lo, hi and op must be numbers");
+        return nullptr;
+    }
+    uint32_t count = 0;
+    const int rc = gsr_select_normal(c, &o, stat, has_axis ? axis : nullptr, lo, hi, op, &count, nullptr);
+    return rc ? throw_gsr(env, c, rc, "gsr_select_normal") : count_value(env, count);
+}
+
 // ---- merging cells (gsr_cells / gsr_scene_merge_cells) ----
 // cell, scope and budget of the two calls below (the budget a number, 0: the library's default); false: an error is pending
 bool get_cell_args(napi_env env, napi_value cell_v, napi_value scope_v, napi_value budget_v, double* cell, uint32_t* scope, uint64_t* budget)
@@ -2222,6 +2294,7 @@ napi_value Init(napi_env env, napi_value exports)
         {"matchScene", MatchScene}, {"selectMatch", SelectMatch}, {"registerTo", RegisterTo}, {"rigidDecompose", RigidDecompose},
         {"clusters", Clusters}, {"selectClusters", SelectClusters}, {"selectClusterAt", SelectClusterAt},
         {"knn", Knn}, {"selectKnn", SelectKnn},
+        {"normals", Normals}, {"selectNormal", SelectNormal},
         {"cells", Cells}, {"mergeCells", MergeCells},
         {"setOverlay", SetOverlay}, {"readOverlay", ReadOverlay}, {"readOverlayPixels", ReadOverlayPixels},
         {"deliverySetOverlay", DeliverySetOverlay}, {"setOutline", SetOutline},

@@ -784,6 +784,41 @@ class HIPRenderer {
             }
             return { selected: this.selectKnn(radius, { ...o3, lo: threshold, op: o2.op }), threshold };
         };
+        // ---- normals (gsr_normals / gsr_select_normal): per-splat surface normals, selection by direction or surface variation ----
+        //   renderer.selectNormal("abs_dot", { axis: [0, 1, 0], hi: 0.2, radius: 0.1, k: 8 });   // the walls: |n . up| small
+        //   const { normals, variation } = renderer.splatNormals(0.1, { k: 8, toward: camera.position });   // row i of normals at [3 * i]
+        // A unit normal per splat in scope: source "knn" (the default), the eigenvector of the smallest eigenvalue of the covariance of
+        // the splat and its k (2 .. 32, default 8) nearest others in scope within `radius`; "own", the splat's own shortest axis (no
+        // index, no walk; radius is not read).  variation[i] = l_min / (l_0 + l_1 + l_2): 0 on a plane, large at edges and corners.
+        // toward: [x, y, z], every normal faces that viewpoint; without it the first non-zero component is positive.  A splat without
+        // a normal holds NaN in both; found[i] is the length of its list.  selectNormal picks lo <= value <= hi, both ends closed,
+        // the value from the stored float32 normal: stat "dot" n . axis, "abs_dot" |n . axis|, "variation" (no axis).  scope and
+        // budget as splatNeighbours.
+        const NORMAL_SOURCES = { knn: 0, own: 1 }, NORMAL_STATS = { dot: 0, abs_dot: 1, variation: 2 };
+        const vec3 = (v, what) => {
+            if (!v || v.length !== 3) throw new Error(what + " must hold three numbers");
+            return [Number(v[0]), Number(v[1]), Number(v[2])];
+        };
+        const normalArgs = (radius, o) => {
+            const source = code(NORMAL_SOURCES, o.source, "knn", "source");
+            const k = o.k === undefined ? 8 : o.k, budget = o.budget === undefined || o.budget === null ? 0 : Number(o.budget);
+            if (source === 0 && (!Number.isInteger(k) || k < 2 || k > 32)) throw new Error("k must be an integer in 2 .. 32");
+            if (!(budget >= 0)) throw new Error("budget must be a non-negative number");
+            const oriented = o.toward !== undefined && o.toward !== null, t = oriented ? vec3(o.toward, "toward") : [0, 0, 0];
+            return [source, source === 0 ? Number(radius) : 0, source === 0 ? k : 0, nbScope(o), budget, oriented ? 1 : 0, t[0], t[1], t[2]];
+        };
+        this.splatNormals = (radius, options) => {
+            const r = this._n.normals(this._h, ...normalArgs(radius, options || {}));
+            return { normals: r.normals, variation: r.variation, found: r.found, inScope: r.inScope, nonfinite: r.nonfinite, pairBound: r.pairBound, valid: r.valid,
+                     variationMin: r.variationMin, variationMax: r.variationMax };
+        };
+        this.selectNormal = (stat, options) => {
+            const o2 = options || {}, args = normalArgs(o2.radius, o2), s = code(NORMAL_STATS, stat, undefined, "stat");
+            const lo = o2.lo === undefined || o2.lo === null ? -Infinity : Number(o2.lo), hi = o2.hi === undefined || o2.hi === null ? Infinity : Number(o2.hi);
+            if (Number.isNaN(lo) || Number.isNaN(hi) || lo > hi) throw new Error("selectNormal: lo <= hi must hold, neither a NaN");
+            const hasAxis = s !== 2, a = hasAxis ? vec3(o2.axis, "axis") : [0, 0, 0];
+            return this._n.selectNormal(this._h, ...args, s, hasAxis ? 1 : 0, a[0], a[1], a[2], lo, hi, code(OPS, o2.op, "replace", "op"));
+        };
         // ---- merging cells (gsr_cells / gsr_scene_merge_cells): voxel simplification of this renderer's copy ----
         //   const { rowsAfter, hist } = renderer.splatCells(0.05); renderer.mergeCells(0.05);   // the report, then the edit it announced
         // The candidates -- the splats in scope with finite position, rotation and scale -- fall into the cells of a grid of side

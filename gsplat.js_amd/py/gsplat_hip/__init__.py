@@ -103,6 +103,19 @@ class GsrKnnInfo(ctypes.Structure):
         return {k: (float if t is ctypes.c_double else int)(getattr(self, k)) for k, t in self._fields_}
 
 
+class GsrNormalOptions(ctypes.Structure):
+    _fields_ = [("source", ctypes.c_int32), ("k", ctypes.c_uint32), ("radius", ctypes.c_double), ("scope", ctypes.c_uint32), ("oriented", ctypes.c_uint32),
+                ("budget", ctypes.c_uint64), ("toward", ctypes.c_double * 3)]
+
+
+class GsrNormalInfo(ctypes.Structure):
+    _fields_ = [("in_scope", ctypes.c_uint32), ("nonfinite", ctypes.c_uint32), ("pair_bound", ctypes.c_uint64), ("budget", ctypes.c_uint64),
+                ("valid", ctypes.c_uint32), ("variation_min", ctypes.c_double), ("variation_max", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: (float if t is ctypes.c_double else int)(getattr(self, k)) for k, t in self._fields_}
+
+
 class GsrCellInfo(ctypes.Structure):
     _fields_ = [("in_scope", ctypes.c_uint32), ("candidates", ctypes.c_uint32), ("cells", ctypes.c_uint32), ("merged_cells", ctypes.c_uint32),
                 ("merged_members", ctypes.c_uint32), ("largest", ctypes.c_uint32), ("rows_after", ctypes.c_uint32), ("pad", ctypes.c_uint32),
@@ -170,6 +183,8 @@ NEIGHBOUR_MAX_CAP = 4095                                                   # GSR
 NEIGHBOUR_DEFAULT_BUDGET, NEIGHBOUR_MAX_BUDGET = 1 << 34, 1 << 38          # GSR_NEIGHBOUR_*_BUDGET
 KNN_MAX_K, KNN_NONE = 32, 0xffffffff                                       # GSR_KNN_MAX_K, GSR_KNN_NONE (an empty list slot)
 KNN_STATS = {"kth": 0, "mean": 1}                                          # GSR_KNN_*
+NORMAL_SOURCES = {"knn": 0, "own": 1}                                      # GSR_NORMAL_KNN / GSR_NORMAL_OWN
+NORMAL_STATS = {"dot": 0, "abs_dot": 1, "variation": 2}                    # GSR_NORMAL_DOT / _ABS_DOT / _VARIATION
 PLANE_MAX_HYPOTHESES = 4096                                               # GSR_PLANE_MAX_HYPOTHESES
 MATCH_NONE = 0xffffffff                                                    # GSR_MATCH_NONE (an unmatched splat)
 REGISTER_STATUS = {0: "converged", 1: "max_iterations", 2: "too_few"}      # GSR_REGISTER_*
@@ -310,6 +325,7 @@ EXPORTS = [
     "gsr_cells", "gsr_scene_merge_cells",
     "gsr_fit_plane", "gsr_plane_inliers", "gsr_select_plane", "gsr_plane_alignment",
     "gsr_match", "gsr_select_match", "gsr_register", "gsr_rigid_solve", "gsr_rigid_compose", "gsr_rigid_decompose",
+    "gsr_normals", "gsr_select_normal",
     "gsr_set_overlay", "gsr_overlay_async", "gsr_read_overlay", "gsr_read_overlay_rgba8", "gsr_overlay_device_ptr", "gsr_delivery_set_overlay",
     "gsr_set_overlay_outline",
 ]
@@ -504,6 +520,9 @@ def load_library(path=None):
     L.gsr_rigid_solve.argtypes = [ctypes.POINTER(GsrMatchSums), vp, ctypes.POINTER(ctypes.c_double)]
     L.gsr_rigid_compose.argtypes = [vp, vp, vp]
     L.gsr_rigid_decompose.argtypes = [vp, vp, vp]
+    no, nmi = ctypes.POINTER(GsrNormalOptions), ctypes.POINTER(GsrNormalInfo)
+    L.gsr_normals.argtypes = [vp, no, vp, vp, vp, ctypes.c_uint32, nmi]
+    L.gsr_select_normal.argtypes = [vp, no, ctypes.c_int32, vp, ctypes.c_double, ctypes.c_double, ctypes.c_int32, u32p, nmi]
     L.gsr_set_overlay.argtypes = [vp, ctypes.POINTER(GsrOverlayOptions)]
     L.gsr_set_overlay_outline.argtypes = [vp, ctypes.POINTER(GsrOutlineOptions)]
     L.gsr_overlay_async.argtypes = [vp]
@@ -1531,6 +1550,70 @@ class HIPRenderer:
         threshold = knn_outlier_threshold(values, std_ratio)
         selected, info = self.select_knn(radius, k=k, stat="mean", lo=threshold, hi=None, scope=scope, op=op)
         return selected, threshold, info
+
+    # -- normals (gsr_normals / gsr_select_normal): per-splat surface normals, selection by direction or surface variation --
+    def _normal_options(self, radius, k, source, toward, scope, budget):
+        if source not in NORMAL_SOURCES:
+            raise ValueError("unknown source %r (one of %s)" % (source, ", ".join(NORMAL_SOURCES)))
+        o = GsrNormalOptions()
+        o.source = NORMAL_SOURCES[source]
+        if source == "knn":
+            if radius is None:
+                raise ValueError("the knn source needs a radius")
+            k = int(k)
+            if not 2 <= k <= KNN_MAX_K:
+                raise ValueError("k must be in 2 .. %d" % KNN_MAX_K)
+            o.k, o.radius = k, float(radius)
+        budget = 0 if budget is None else int(budget)
+        if budget < 0:
+            raise ValueError("budget must not be negative")
+        o.scope, o.budget = self._scope_flags(scope), budget
+        if toward is not None:
+            o.oriented = 1
+            o.toward[:] = [float(v) for v in np.asarray(toward, dtype=np.float64).reshape(3)]
+        return o
+
+    def normals(self, radius=None, k=8, source="knn", toward=None, scope=(), budget=None, normals=True, variation=True, found=True):
+        """(normals float32[n, 3], variation float64[n], found uint32[n], info): a unit surface normal per splat in scope -- scope:
+        any of "selected", "visible"; () is every splat.  source "knn": the eigenvector of the smallest eigenvalue of the covariance
+        of the splat and its k nearest others in scope within `radius` (knn()'s lists; at least two are needed); "own": the
+        splat's own shortest axis, no index and no walk.  variation[i] = l_min / (l_0 + l_1 + l_2): 0 on a plane, large at edges and
+        corners.  toward=(x, y, z): every normal faces that viewpoint; None: its first non-zero component is positive.  A splat
+        without a normal holds NaN in both; found[i] is the length of its list (0 for "own").  A False argument: None in its place,
+        nothing copied.  info: in_scope, nonfinite, pair_bound, budget, valid, variation_min, variation_max.  budget as
+        neighbours() takes it."""
+        o = self._normal_options(radius, k, source, toward, scope, budget)
+        n = self._count()
+        nm = np.full((n, 3), np.nan, np.float32) if normals else None
+        v = np.full(n, np.nan, np.float64) if variation else None
+        f = np.zeros(n, np.uint32) if found else None
+        info = GsrNormalInfo()
+        ptr = lambda a: a.ctypes.data if a is not None and n else None
+        self._check_neighbours(self._L.gsr_normals(self._ctx, ctypes.byref(o), ptr(nm), ptr(v), ptr(f), n if normals or variation or found else 0,
+                                                   ctypes.byref(info)), info)
+        return nm, v, f, info.as_dict()
+
+    def select_normal(self, stat, lo=-np.inf, hi=np.inf, axis=None, radius=None, k=8, source="knn", toward=None, scope=(), op="replace", budget=None):
+        """(selected, info): pick the splats with a normal whose value has lo <= value <= hi (both ends closed) and fold them into
+        the selection.  stat "dot": n . axis; "abs_dot": |n . axis|, for normals that are not oriented -- select_normal("abs_dot",
+        hi=0.2, axis=up, ..) is "the walls"; "variation": the surface variation, no axis.  The value is computed from the stored
+        float32 normal, so with op "replace" exactly the splats that satisfy the rule on normals()' outputs for the same
+        arguments are selected.  axis is used as given, not normalised."""
+        if stat not in NORMAL_STATS:
+            raise ValueError("unknown stat %r (one of %s)" % (stat, ", ".join(NORMAL_STATS)))
+        o = self._normal_options(radius, k, source, toward, scope, budget)
+        lo, hi = float(lo), float(hi)
+        if lo != lo or hi != hi or lo > hi:
+            raise ValueError("lo <= hi must hold, neither a NaN")
+        a = None
+        if stat != "variation":
+            if axis is None:
+                raise ValueError("stat %r needs an axis" % stat)
+            a = np.ascontiguousarray(axis, dtype=np.float64).reshape(3)
+        count, info = ctypes.c_uint32(0), GsrNormalInfo()
+        self._check_neighbours(self._L.gsr_select_normal(self._ctx, ctypes.byref(o), NORMAL_STATS[stat], None if a is None else a.ctypes.data, lo, hi,
+                                                         self._select_code(SELECT_OPS, op, "op"), ctypes.byref(count), ctypes.byref(info)), info)
+        return count.value, info.as_dict()
 
     # -- merging cells (gsr_cells / gsr_scene_merge_cells): voxel simplification of the scene --
     @staticmethod

@@ -1350,6 +1350,88 @@ int gsr_rigid_solve(const gsr_match_sums *sums, double *D /* [12] */, double *rm
 int gsr_rigid_compose(const double *D, const double *M, double *out /* [12] */);
 int gsr_rigid_decompose(const double *M, double *q_xyzw, double *t /* [3] */);
 
+/* ---- normals ---- per-splat surface normals on the device, and selection by direction or by surface variation
+ * No interface of the reference stands behind this section either.  "Select the walls" (|n . up| small), "select what faces the
+ * camera", "select edges and corners" (high surface variation) and "select the flat parts" (low variation) all need a normal per
+ * splat, and a host would have to read the scene back and build a k-d tree for it.  These calls make the normals on the device
+ * from the lists of "k nearest neighbours", or from the splat's own shortest axis with no index at all.
+ * Definition ("Normals").  All arithmetic is f64, in the written order, uncontracted; p_i is the stored f32
+ *   position widened to f64; sqrt is correctly rounded.
+ *   GSR_NORMAL_KNN.  Scope S, near, the list nn_i[0 .. m_i-1] and m_i are exactly gsr_knn's at the same radius and k (ascending by
+ *   (d2, index)), with 2 <= k <= GSR_KNN_MAX_K.
+ *     1. q_0 = p_i, q_t = p_{nn_i[t-1]} for t = 1 .. m_i; M = m_i + 1 points.
+ *     2. mu_c = ((..(q_0c + q_1c) + ..) + q_{m}c) / (double)M.
+ *     3. d_t = q_t - mu; C_e = (sum over ascending t of d_tx * d_ty, starting from 0.0) / (double)M for e = 00, 01, 02, 11, 12, 22.
+ *     4. (lam, V) by the Jacobi of "merging cells" step 6: six cyclic sweeps over (0,1), (0,2), (1,2), a rotation skipped when
+ *        apq == 0.0, t = 1 / (|th| + sqrt(th*th + 1)) with th's sign, cs = 1 / sqrt(t*t + 1), sn = t * cs, in that section's
+ *        update order.
+ *     5. l_c = lam_c > 0 ? lam_c : 0; tot = (l_0 + l_1) + l_2; c* = the smallest c with l_c minimal.
+ *     6. the splat is VALID when it is in S, finite, m_i >= 2 and tot > 0.
+ *     7. u = (V[0][c*], V[1][c*], V[2][c*]), not re-normalised (its norm is within 1e-14 of 1).
+ *     8. variation = l_{c*} / tot: 0 on a plane, 1/3 at most.
+ *   GSR_NORMAL_OWN.  (r0..r3) and (s0, s1, s2) as stored; b[0..8] the rotation matrix of the packed covariance (Quaternion(r1, r2,
+ *   r3, -r0), row-major, in its written order: b[0] = 1 - 2*qy*qy - 2*qz*qz, b[1] = 2*qx*qy - 2*qz*qw, ..); the axis of scale k is
+ *   (b[3k], b[3k+1], b[3k+2]).
+ *     1. l_k = |s_k| * |s_k|; tot and c* as above (a tie goes to the smallest k).
+ *     2. a = that axis; nrm = sqrt((a0*a0 + a1*a1) + a2*a2); u_c = a_c / nrm.
+ *     3. VALID: in S; position, rotation and scales all finite; the rotation not all zero (a zero quaternion is no rotation,
+ *        though the formula alone would give the identity); tot > 0; nrm > 0 and finite.
+ *     4. found = 0.  The scene must carry rotations and scales (as the transforms demand).
+ *   Orientation, on u in f64, before the store.  If options->oriented: s = ((u0*(toward0 - px) + u1*(toward1 - py)) + u2*(toward2 -
+ *   pz)); s < 0 flips u, s > 0 keeps it.  Otherwise (s == 0, s a NaN, or not oriented) the first non-zero component of u is made
+ *   positive: gsr_fit_plane's convention.
+ *   Stores.  A valid row: normals[3i..] = (float)u, round to nearest; variation[i] = the value; found[i] = m_i.  A row that is not
+ *   valid: 0x7fc00000 three times, 0x7ff8000000000000, and found[i] = m_i when i is in S, else 0.
+ * gsr_normals: normals is 3 n floats, variation n doubles, found n words; any out pointer may be NULL; a non-NULL one with n not
+ *   equal to the scene's count is refused.  info may be NULL.
+ * info: in_scope, nonfinite, pair_bound and budget as in gsr_knn_info (OWN: pair_bound 0); valid = the valid rows; variation_min /
+ *   variation_max over them, through their bit patterns (the values are non-negative), +inf / -inf when there is none.  An empty
+ *   scene or an empty scope returns zeros and +inf / -inf.
+ * gsr_select_normal: value_i is computed from the STORED f32 normal widened to f64 -- a host holding gsr_normals' output
+ *   reproduces it exactly: GSR_NORMAL_DOT ((nx*ax + ny*ay) + nz*az), GSR_NORMAL_ABS_DOT its fabs, GSR_NORMAL_VARIATION variation_i.
+ *   axis is used as given (finite, not all zero, not normalised; NULL for VARIATION).  P = { i valid : lo <= value_i && value_i <=
+ *   hi }, both ends closed, infinite ends allowed, as in gsr_select_plane; P is folded with `op` as every picker folds.
+ * The consistency guarantee: with GSR_SELOP_REPLACE exactly the splats that satisfy the rule on gsr_normals' outputs for the same
+ *   options are selected.
+ * The work budget of the KNN source is the neighbour budget: if pair_bound > budget the call returns GSR_ERR_ARG with a message
+ *   naming both numbers, fills info's first four fields and launches no walk.
+ * Both calls are blocking and stateless, ordered like gsr_knn: they wait for every member's stream of a shared scene, read the
+ *   scene and write none of it; no frame state changes.
+ * Refusals (GSR_ERR_ARG with a message, nothing touched, the selection and its count included): a NULL ctx or NULL options; an
+ *   unknown source, stat, op or scope flag; KNN: gsr_knn's radius rules and k outside 2 .. 32; a non-finite toward when oriented;
+ *   a NULL, non-finite or all-zero axis for the two dot stats; a NaN bound or lo > hi; a wrong n; a budget above the maximum; a
+ *   bound above the budget; OWN on a scene without rotations and scales.
+ * The device scratch belongs to the context: the scratch of "neighbours" (KNN only) and 12 + 8 + 4 bytes per splat.  The first
+ *   call allocates it, it only grows, and gsr_destroy frees it; a context that never calls any of this allocates nothing and
+ *   launches nothing. */
+#define GSR_NORMAL_KNN 0        /* from the k nearest neighbours within radius (PCA of the neighbourhood) */
+#define GSR_NORMAL_OWN 1        /* the splat's own shortest axis; no index, no walk */
+#define GSR_NORMAL_DOT 0        /* picker value: n . axis */
+#define GSR_NORMAL_ABS_DOT 1    /* |n . axis|, for normals that are not oriented */
+#define GSR_NORMAL_VARIATION 2  /* l_min / (l_0 + l_1 + l_2) */
+typedef struct gsr_normal_options {
+    int32_t source;         /* GSR_NORMAL_KNN | GSR_NORMAL_OWN */
+    uint32_t k;             /* KNN: 2 .. GSR_KNN_MAX_K; OWN: ignored */
+    double radius;          /* KNN: as gsr_knn's; OWN: ignored */
+    uint32_t scope;         /* GSR_SCOPE_* flags, as everywhere */
+    uint32_t oriented;      /* != 0: toward[] is read */
+    uint64_t budget;        /* the neighbour budget, 0 = default */
+    double toward[3];       /* a viewpoint: normals are flipped to face it */
+} gsr_normal_options;
+typedef struct gsr_normal_info {
+    uint32_t in_scope;      /* splats in S */
+    uint32_t nonfinite;     /* of those, with a NaN or infinite position component */
+    uint64_t pair_bound;    /* as gsr_knn_info; OWN: 0 */
+    uint64_t budget;        /* the budget that applied */
+    uint32_t valid;         /* splats with a normal */
+    double variation_min;   /* over the valid; +inf: there is none */
+    double variation_max;   /* over the valid; -inf: there is none */
+} gsr_normal_info;
+int gsr_normals(gsr_ctx *ctx, const gsr_normal_options *options, float *normals /* 3n */, double *variation /* n */,
+                uint32_t *found /* n */, uint32_t n, gsr_normal_info *info);       /* any out pointer may be NULL */
+int gsr_select_normal(gsr_ctx *ctx, const gsr_normal_options *options, int32_t stat, const double *axis /* 3; NULL for VARIATION */,
+                      double lo, double hi, int32_t op, uint32_t *selected, gsr_normal_info *info);
+
 /* ---- selection overlay ---- the selected splats tinted, in read-backs and in delivered frames
  * No interface of the reference stands behind this section either.  gsr_read_selection returns bits; this shows them: a second
  * image beside the frame in which the selected splats carry a tint, and per pixel how much of it they are.

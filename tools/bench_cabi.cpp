@@ -3,7 +3,7 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--rotate-sh FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--plane THRESHOLD[:HYPOTHESES]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--register RADIUS[:ITERATIONS]] [--merge CELL] [--share-scene]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--rotate-sh FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--plane THRESHOLD[:HYPOTHESES]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--normals RADIUS:K[:own]] [--register RADIUS[:ITERATIONS]] [--merge CELL] [--share-scene]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
@@ -61,6 +61,11 @@
 // bound) and the walk (with its fill) apart; pair_bound and the pair tests per second it means for the walk, complete,
 // finite_values, the value range, and the check that gsr_select_knn(lo = the mean of the finite values, hi = +inf) selects exactly
 // the splats whose values[i] is at or above it (`values_equal_selection`).
+// --normals RADIUS:K[:own] computes every splat's surface normal: five gsr_normals calls from the K nearest neighbours within RADIUS
+// (with `own`: from the splat's own shortest axis, RADIUS and K unread), the best blocking time, and by the library's events on the
+// stream the index build (with its bound; 0 for own) and the walk (with its fill; own: the one kernel) apart; pair_bound, valid, the
+// variation range, and the check that gsr_select_normal(variation, lo = 0, hi = the mean of the valid variations) selects exactly the
+// splats whose variation[i] lies in that closed range (`variation_equals_selection`).
 // --register RADIUS[:ITERATIONS] (32 steps at most unless given) registers the scene to a copy of itself: a second context holds the
 // config's scene moved by a fixed small rigid motion (0.01 rad about (0.3, 0.9, 0.2), then (0.01, -0.005, 0.008)), so source and target
 // are one size; one gsr_register call from the identity at tolerance 2^-40: its blocking time, the status, every step's pairs and rms,
@@ -181,6 +186,7 @@ uint64_t fnv1a(const void* p, size_t bytes)
 extern "C" int gsr_debug_neighbour_times(gsr_ctx* ctx, float* out /* build_ms, count_ms */);   // not part of the ABI (gsr_neighbours.cpp)
 extern "C" int gsr_debug_plane_times(gsr_ctx* ctx, float* out /* candidates_ms, score_ms */);   // not part of the ABI (gsr_plane.cpp)
 extern "C" int gsr_debug_knn_times(gsr_ctx* ctx, float* out /* index_ms, walk_ms */);   // not part of the ABI (gsr_knn.cpp)
+extern "C" int gsr_debug_normals_times(gsr_ctx* ctx, float* out /* index_ms, walk_ms */);   // not part of the ABI (gsr_normals.cpp)
 extern "C" int gsr_debug_match_times(gsr_ctx* ctx, float* out /* index_ms, the last step's bound_ms, walk_ms, tree_ms, the steps' sums of the three, steps */);   // not part of the ABI (gsr_match.cpp)
 extern "C" int gsr_debug_cluster_times(gsr_ctx* ctx, float* out /* index_ms, core_ms, union_ms, border_ms */);   // not part of the ABI (gsr_clusters.cpp)
 
@@ -226,6 +232,9 @@ int main(int argc, char** argv)
     uint32_t reg_steps = 32;
     uint32_t knn_k = 8;
     int32_t knn_stat = GSR_KNN_MEAN;
+    double normals_radius = 0.0;        // 0: off
+    uint32_t normals_k = 8;
+    bool normals_own = false;
     int32_t pick_xy[2] = {0, 0};
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -286,6 +295,15 @@ int main(int argc, char** argv)
             if (!(knn_radius > 0.0) || k < 1 || k > (int)GSR_KNN_MAX_K || (stat != "kth" && stat != "mean")) { std::fprintf(stderr, "--knn RADIUS:K[:kth|mean]: RADIUS > 0, K in 1 .. 32\n"); return 2; }
             knn_k = (uint32_t)k; knn_stat = stat == "kth" ? GSR_KNN_KTH : GSR_KNN_MEAN;
         }
+        else if (a == "--normals" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            const size_t colon = v.find(':'), colon2 = colon == std::string::npos ? colon : v.find(':', colon + 1);
+            normals_radius = std::atof(v.c_str());
+            const int k = colon != std::string::npos ? std::atoi(v.c_str() + colon + 1) : 0;
+            const std::string source = colon2 != std::string::npos ? v.substr(colon2 + 1) : "knn";
+            if (!(normals_radius > 0.0) || k < 2 || k > (int)GSR_KNN_MAX_K || (source != "own" && source != "knn")) { std::fprintf(stderr, "--normals RADIUS:K[:own]: RADIUS > 0, K in 2 .. 32\n"); return 2; }
+            normals_k = (uint32_t)k; normals_own = source == "own";
+        }
         else if (a == "--register" && i + 1 < argc) {
             const std::string v = argv[++i];
             const size_t colon = v.find(':');
@@ -301,7 +319,7 @@ int main(int argc, char** argv)
         else if (a == "--scene-edit") scene_edit = next();
         else if (a == "--share-scene") share_scene = true;
         else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--rotate-sh FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--plane THRESHOLD[:HYPOTHESES]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--register RADIUS[:ITERATIONS]] [--merge CELL] [--share-scene]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--rotate-sh FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--plane THRESHOLD[:HYPOTHESES]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--normals RADIUS:K[:own]] [--register RADIUS[:ITERATIONS]] [--merge CELL] [--share-scene]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
@@ -829,6 +847,36 @@ int main(int argc, char** argv)
         CHECK(gsr_select_knn(ctx[0], knn_radius, knn_k, 0, 0, knn_stat, knn_lo, HUGE_VAL, GSR_SELOP_REPLACE, &knn_selected, nullptr));
         knn_select_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3;
     }
+    // --normals: every splat's normal and surface variation, the stages timed apart, the pick checked against the variations
+    gsr_normal_info nm_info{};
+    double nm_ms = 1e30, nm_index_ms = 1e30, nm_walk_ms = 1e30, nm_select_ms = 0, nm_hi = 0;
+    uint32_t nm_selected = 0, nm_n = 0;
+    unsigned long long nm_within = 0;
+    if (normals_radius > 0.0) {
+        ctx0 = ctx[0];
+        CHECK(gsr_scene_count(ctx[0], &nm_n));
+        gsr_normal_options no{};
+        no.source = normals_own ? GSR_NORMAL_OWN : GSR_NORMAL_KNN;
+        no.k = normals_k; no.radius = normals_radius;
+        std::vector<float> normals((size_t)nm_n * 3);
+        std::vector<double> variation(nm_n);
+        std::vector<uint32_t> found(nm_n);
+        for (int t = 0; t < 5; t++) {
+            const auto t0 = std::chrono::steady_clock::now();
+            CHECK(gsr_normals(ctx[0], &no, normals.data(), variation.data(), found.data(), nm_n, &nm_info));
+            nm_ms = std::min(nm_ms, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3);
+            float stage[2] = {0, 0};
+            CHECK(gsr_debug_normals_times(ctx[0], stage));
+            nm_index_ms = std::min(nm_index_ms, (double)stage[0]); nm_walk_ms = std::min(nm_walk_ms, (double)stage[1]);
+        }
+        double sum = 0;
+        for (uint32_t i = 0; i < nm_n; i++) if (!std::isnan(variation[i])) sum += variation[i];
+        nm_hi = nm_info.valid ? sum / (double)nm_info.valid : 0.0;
+        for (uint32_t i = 0; i < nm_n; i++) nm_within += variation[i] >= 0.0 && variation[i] <= nm_hi;
+        const auto t0 = std::chrono::steady_clock::now();
+        CHECK(gsr_select_normal(ctx[0], &no, GSR_NORMAL_VARIATION, nullptr, 0.0, nm_hi, GSR_SELOP_REPLACE, &nm_selected, nullptr));
+        nm_select_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3;
+    }
     // --register: the scene registered to a moved copy of itself in a second context, the stages timed apart
     gsr_register_info reg_info{};
     std::vector<uint64_t> reg_step_pairs(reg_steps, 0);
@@ -998,6 +1046,13 @@ int main(int argc, char** argv)
         for (uint32_t k = 0; k < reg_info.iterations; k++) std::printf("%s%s", k ? ", " : "", json_num(reg_step_rms[k]).c_str());
         std::printf("]}");
     }
+    if (normals_radius > 0.0)
+        std::printf(", \"normals\": {\"source\": \"%s\", \"radius\": %.17g, \"k\": %u, \"n\": %u, \"in_scope\": %u, \"nonfinite\": %u, \"pair_bound\": %llu, \"budget\": %llu, "
+                    "\"normals_ms\": %.4f, \"index_build_ms\": %.4f, \"walk_ms\": %.4f, \"valid\": %u, \"variation_min\": %s, \"variation_max\": %s, "
+                    "\"variation_hi\": %.17g, \"within\": %llu, \"select_normal_ms\": %.4f, \"selected\": %u, \"variation_equals_selection\": %s}",
+                    normals_own ? "own" : "knn", normals_radius, normals_k, nm_n, nm_info.in_scope, nm_info.nonfinite, (unsigned long long)nm_info.pair_bound,
+                    (unsigned long long)nm_info.budget, nm_ms, nm_index_ms, nm_walk_ms, nm_info.valid, json_num(nm_info.variation_min).c_str(),
+                    json_num(nm_info.variation_max).c_str(), nm_hi, nm_within, nm_select_ms, nm_selected, nm_within == nm_selected ? "true" : "false");
     if (knn_radius > 0.0)
         std::printf(", \"knn\": {\"radius\": %.17g, \"k\": %u, \"stat\": \"%s\", \"n\": %u, \"in_scope\": %u, \"nonfinite\": %u, \"pair_bound\": %llu, \"budget\": %llu, "
                     "\"knn_ms\": %.4f, \"index_build_ms\": %.4f, \"walk_ms\": %.4f, \"pair_tests_per_s\": %.4g, \"knn_lists_ms\": %.4f, \"lists_index_build_ms\": %.4f, "
