@@ -592,6 +592,8 @@ struct gsr_ctx {
         uint32_t rows = 0;
         gsr::DevBuf<double> tree;               // `tree_rows` rows of MATCH_ROW doubles: the partial rows of every level (calls that ask for sums)
         uint64_t tree_rows = 0;
+        gsr::DevBuf<double> surface_tree;       // `surface_rows` rows of MATCH_SURFACE_ROW doubles: the same for gsr_match_surface / gsr_register_surface
+        uint64_t surface_rows = 0;
         hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // around the index; in front of a step's bound, behind it, behind the walk, the tree
         float ms[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // of the last call: the index; bound, walk, tree of its last step; their sums over
                                                                           // its steps; the steps (gsr_debug_match_times)
@@ -737,6 +739,14 @@ int nb_prepare(gsr_ctx* c, const char* who, uint32_t cap, double inv_h, double r
 // the same for n rows that need not be the context's own scene's (n >= 1): the caller names the arrays to index when it builds
 // (gsr_match.cpp indexes ANOTHER context's scene into this context's scratch)
 int nb_prepare_rows(gsr_ctx* c, const char* who, uint32_t n, uint32_t cap, double inv_h, double r2, NbIndex* ix, uint32_t** hist);
+// gsr_normals.cpp, for gsr_match.cpp's point-to-plane calls, which take the TARGET's normals as gsr_normals stores them.
+// normal_check: the refusals gsr_normals and gsr_select_normal share, in the header's order; nothing is touched.  normal_run:
+// everything up to the read-backs into the context's normals scratch (*arrays) -- (KNN) the index and its bound (nb_index), the
+// fill and the walk, or (OWN) the one kernel -- and *info, final on the device and waited for.  GSR_ERR_ARG (with *info's first
+// four fields filled) for a bound above the budget: no walk has been launched.  n >= 1; the device is current and no member's
+// stream holds work.
+int normal_check(gsr_ctx* c, const char* who, const gsr_normal_options* o);
+int normal_run(gsr_ctx* c, const char* who, const gsr_normal_options* o, uint64_t budget, NormalArrays* arrays, gsr_normal_info* info);
 // gsr_contrib.cpp: what the blocking calls that read per-splat state of a scene do first: waits for every member's stream, so
 // that nothing of any member (a contribution pass, an edit) is in flight afterwards
 int settle_members(gsr_ctx* c);

@@ -799,7 +799,7 @@ struct MatchSource {
 // bit patterns order as unsigned integers (KnnInfo): d2max is the largest pattern, nd2min the largest COMPLEMENT of one.
 struct MatchInfo {
     uint32_t in_scope, nonfinite;          // source splats in scope; of those, with a non-finite position or transformed point
-    uint32_t matched, pad;
+    uint32_t matched, surface;             // (surface: the non-zero rows of k_match_surface_rows, 0 for every other call)
     unsigned long long nd2min, d2max;
     unsigned long long pair_bound;         // k_match_bound's sum
 };
@@ -820,6 +820,13 @@ void launch_match(const NbIndex& ix, uint32_t indexed, const MatchSource& src, u
 // levels one behind the other; the result is the last row.  n >= 1.
 void launch_match_tree(const MatchSource& src, const float* qx, const float* qy, const float* qz, uint32_t tn, const uint32_t* idx, const double* d2,
                        double* partial, hipStream_t s);
+// The point-to-plane tree ("Point-to-plane registration"): level 1 rebuilds every row of MATCH_SURFACE_ROW
+// doubles from idx[], d2[], the target's position and the target's stored f32 normal (3 tn floats, three NaNs where a splat has
+// none), and adds the non-zero rows to info->surface; the further levels are the tree above at that width.  partial:
+// match_tree_rows(n) rows of MATCH_SURFACE_ROW doubles; the result is the last row.  n >= 1.
+constexpr uint32_t MATCH_SURFACE_ROW = 29;                  // J_a * J_b for a <= b (21), J_a * r (6), r * r, d2
+void launch_match_surface_tree(const MatchSource& src, const float* qx, const float* qy, const float* qz, const float* normals, uint32_t tn, const uint32_t* idx,
+                               const double* d2, double* partial, MatchInfo* info, hipStream_t s);
 // scratch <- the source splats i < n in scope with lo <= sqrt(d2[i]) && (sqrt(d2[i]) < hi || open_hi): every word of it is stored
 void launch_match_select(const double* d2, const AttrScope& sc, uint32_t n, double lo, double hi, bool open_hi, uint32_t* scratch, uint32_t nwords, hipStream_t s);
 

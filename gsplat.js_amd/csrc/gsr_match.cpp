@@ -26,6 +26,7 @@ constexpr uint32_t MATCH_INFO_WORDS = 12;
 static_assert(sizeof(MatchInfo) <= MATCH_INFO_WORDS * 4, "MatchInfo fits its words");
 static_assert(MATCH_NONE == GSR_MATCH_NONE, "the header's word");
 static_assert(sizeof(gsr_match_info) == 48 && sizeof(gsr_match_sums) == 8 + MATCH_ROW * 8 && sizeof(gsr_register_info) == 56, "the header's layouts");
+static_assert(sizeof(gsr_surface_sums) == 16 + MATCH_SURFACE_ROW * 8 && sizeof(gsr_register_surface_info) == 88, "the header's layouts");
 constexpr double INF = std::numeric_limits<double>::infinity();
 const double IDENTITY[12] = {1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0};
 
@@ -42,8 +43,11 @@ int match_check(gsr_ctx* c, gsr_ctx* target, const char* who, const double* M, d
     return GSR_OK;
 }
 
-// the context's scratch for n source splats, with the tree's rows when `tree`: allocated by the first call, only ever grown
-int match_ensure(gsr_ctx* c, uint32_t n, bool tree)
+// which tree a step ends with: none, the sixteen sums of the rigid solve, the 29 of the point-to-plane solve
+enum MatchTree { TREE_NONE, TREE_POINT, TREE_SURFACE };
+
+// the context's scratch for n source splats, with the rows of the tree asked for: allocated by the first call, only ever grown
+int match_ensure(gsr_ctx* c, uint32_t n, MatchTree tree)
 {
     gsr_ctx::Match& mt = c->mt;
     if (!mt.words) { if (int r = mt.words.alloc(c, MATCH_INFO_WORDS)) return r; }
@@ -53,11 +57,16 @@ int match_ensure(gsr_ctx* c, uint32_t n, bool tree)
         if ((r = mt.idx.alloc(c, n)) || (r = mt.d2.alloc(c, n))) return r;
         mt.rows = n;
     }
-    const uint64_t rows = tree && n ? match_tree_rows(n) : 0u;
-    if (rows && (mt.tree_rows < rows || !mt.tree)) {
+    const uint64_t rows = tree != TREE_NONE && n ? match_tree_rows(n) : 0u;
+    if (rows && tree == TREE_POINT && (mt.tree_rows < rows || !mt.tree)) {
         mt.tree_rows = 0;
         if (int r = mt.tree.alloc(c, (size_t)rows * MATCH_ROW)) return r;
         mt.tree_rows = rows;
+    }
+    if (rows && tree == TREE_SURFACE && (mt.surface_rows < rows || !mt.surface_tree)) {
+        mt.surface_rows = 0;
+        if (int r = mt.surface_tree.alloc(c, (size_t)rows * MATCH_SURFACE_ROW)) return r;
+        mt.surface_rows = rows;
     }
     for (hipEvent_t& e : mt.ev) if (!e) HIP_TRY(c, hipEventCreate(&e));
     return GSR_OK;
@@ -84,7 +93,7 @@ struct MatchCall {
 
 // Everything that does not depend on the trial transform: both scenes settled, the scratch, the index over the target.  The
 // source scene holds n >= 1 splats; the device is current afterwards and no member's stream of either scene holds work.
-int match_index(gsr_ctx* c, gsr_ctx* target, const char* who, double radius, uint32_t scope, uint32_t target_scope, uint64_t budget, bool tree, MatchCall* call,
+int match_index(gsr_ctx* c, gsr_ctx* target, const char* who, double radius, uint32_t scope, uint32_t target_scope, uint64_t budget, MatchTree tree, MatchCall* call,
                 gsr_match_info* info)
 {
     HIP_TRY(c, hipSetDevice(c->device));
@@ -123,9 +132,11 @@ int match_index(gsr_ctx* c, gsr_ctx* target, const char* who, double radius, uin
     return GSR_OK;
 }
 
-// One step under the transform M: the bound against the budget, the walk, the tree (sums non-null) and *info, final on the device
-// and waited for.  GSR_ERR_ARG (with *info's first fields filled) for a bound above the budget: no walk has been launched.
-int match_step(gsr_ctx* c, const char* who, MatchCall* call, const double* M, gsr_match_sums* sums, gsr_match_info* info)
+// One step under the transform M: the bound against the budget, the walk, the tree the caller chose (sums non-null: the sixteen
+// sums; surface non-null: the 29 along `normals`, the target's stored rows, final on the device) and *info, final on the device and
+// waited for.  GSR_ERR_ARG (with *info's first fields filled) for a bound above the budget: no walk has been launched.
+int match_step(gsr_ctx* c, const char* who, MatchCall* call, const double* M, gsr_match_sums* sums, gsr_match_info* info, const float* normals = nullptr,
+               gsr_surface_sums* surface = nullptr)
 {
     gsr_ctx::Match& mt = c->mt;
     std::memcpy(call->src.xf.m, M ? M : IDENTITY, sizeof call->src.xf.m);
@@ -150,9 +161,13 @@ int match_step(gsr_ctx* c, const char* who, MatchCall* call, const double* M, gs
     launch_match(call->ix, call->indexed, call->src, mt.idx, mt.d2, dev, c->cu_count, c->stream);
     e0 = hipGetLastError();
     e1 = hipEventRecord(mt.ev[4], c->stream);
-    double row[MATCH_ROW] = {};
+    double row[MATCH_ROW] = {}, srow[MATCH_SURFACE_ROW] = {};
     hipError_t e4 = hipSuccess, e5 = hipSuccess;
-    if (sums) {
+    if (surface) {
+        launch_match_surface_tree(call->src, call->qx, call->qy, call->qz, normals, call->tn, mt.idx, mt.d2, mt.surface_tree, dev, c->stream);
+        e4 = hipGetLastError();
+        e5 = hipMemcpyAsync(srow, mt.surface_tree + (match_tree_rows(call->src.n) - 1u) * MATCH_SURFACE_ROW, sizeof srow, hipMemcpyDeviceToHost, c->stream);
+    } else if (sums) {
         launch_match_tree(call->src, call->qx, call->qy, call->qz, call->tn, mt.idx, mt.d2, mt.tree, c->stream);
         e4 = hipGetLastError();
         e5 = hipMemcpyAsync(row, mt.tree + (match_tree_rows(call->src.n) - 1u) * MATCH_ROW, sizeof row, hipMemcpyDeviceToHost, c->stream);
@@ -164,6 +179,8 @@ int match_step(gsr_ctx* c, const char* who, MatchCall* call, const double* M, gs
         if (e != hipSuccess) return fail(c, GSR_ERR_HIP, "%s failed: %s", who, hipGetErrorString(e));
     if (got.matched > got.in_scope - got.nonfinite)
         return fail(c, GSR_ERR_HIP, "%s: %u matches for %u queries", who, got.matched, got.in_scope - got.nonfinite);
+    if (got.surface > got.matched || (!surface && got.surface))
+        return fail(c, GSR_ERR_HIP, "%s: %u rows along a normal for %u matches", who, got.surface, got.matched);
     info->matched = got.matched;
     if (got.matched) {
         const uint64_t lo = ~(uint64_t)got.nd2min, hi = (uint64_t)got.d2max;
@@ -173,6 +190,11 @@ int match_step(gsr_ctx* c, const char* who, MatchCall* call, const double* M, gs
     if (sums) {
         sums->pairs = got.matched;
         std::memcpy(sums->sum, row, sizeof row);
+    }
+    if (surface) {
+        surface->pairs = got.matched;
+        surface->surface_pairs = got.surface;
+        std::memcpy(surface->sum, srow, sizeof srow);
     }
     float ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     bool ok = hipEventElapsedTime(&ms[0], mt.ev[0], mt.ev[1]) == hipSuccess;
@@ -186,6 +208,36 @@ int match_step(gsr_ctx* c, const char* who, MatchCall* call, const double* M, gs
 }
 
 double step_rms(const gsr_match_sums& s) { return s.pairs ? std::sqrt(s.sum[15] * (1.0 / (double)s.pairs)) : INF; }
+
+// What the two point-to-plane calls do between their refusals and their steps: the target's normals as gsr_normals(target,
+// options) stores them, by normal_run into TARGET's scratch.  Both scenes are settled first; normal_run waits for the target's
+// stream, so the rows kernel on c's stream reads final rows.  A message of the target's side becomes c's.  ts.n >= 1.
+int surface_normals(gsr_ctx* c, gsr_ctx* target, const char* who, const gsr_normal_options* o, const float** normals, uint32_t* valid)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int r = settle_members(c)) return r;
+    if (target->scene != c->scene)
+        if (int r = settle_members(target)) return fail(c, r, "%s: the target: %s", who, gsr_last_error(target));
+    NormalArrays a{};
+    gsr_normal_info ni{};
+    ni.budget = o->budget ? o->budget : GSR_NEIGHBOUR_DEFAULT_BUDGET;
+    if (int r = normal_run(target, who, o, ni.budget, &a, &ni)) return target == c ? r : fail(c, r, "%s", gsr_last_error(target));
+    HIP_TRY(c, hipStreamSynchronize(target->stream));   // (normal_run has waited: the order stated where the rows are read)
+    *normals = a.normals;
+    *valid = ni.valid;
+    return GSR_OK;
+}
+
+// the refusals of the point-to-plane calls behind match_check's: gsr_normals' on the target, and the one scope
+int surface_check(gsr_ctx* c, gsr_ctx* target, const char* who, uint32_t target_scope, const gsr_normal_options* o)
+{
+    if (!o) return fail(c, GSR_ERR_ARG, "%s: options is NULL", who);
+    if (int r = normal_check(target, who, o)) return target == c ? r : fail(c, r, "%s", gsr_last_error(target));
+    if (o->scope != target_scope) return fail(c, GSR_ERR_ARG, "%s: options->scope (%u) is not target_scope (%u)", who, o->scope, target_scope);
+    if (o->source == GSR_NORMAL_OWN && target->scene->n)
+        if (int r = require_rows(target)) return target == c ? r : fail(c, r, "%s: the target: %s", who, gsr_last_error(target));
+    return GSR_OK;
+}
 
 }  // namespace
 
@@ -206,7 +258,7 @@ int gsr_match(gsr_ctx* c, gsr_ctx* target, const double* M, double radius, uint3
         return GSR_OK;
     }
     MatchCall call;
-    int r = match_index(c, target, "gsr_match", radius, scope, target_scope, budget, sums != nullptr, &call, &got);
+    int r = match_index(c, target, "gsr_match", radius, scope, target_scope, budget, sums ? TREE_POINT : TREE_NONE, &call, &got);
     if (!r) r = match_step(c, "gsr_match", &call, M, sums, &got);
     if (info && (r == GSR_OK || r == GSR_ERR_ARG)) *info = got;
     if (r) return r;
@@ -238,7 +290,7 @@ int gsr_select_match(gsr_ctx* c, gsr_ctx* target, const double* M, double radius
     if (int r = settle_members(c)) return r;
     if (int r = select_ensure(c)) return r;   // (in front of the scope: a selection never allocated becomes the zeroed mask, the same set)
     MatchCall call;
-    int r = match_index(c, target, "gsr_select_match", radius, scope, target_scope, budget, false, &call, &got);
+    int r = match_index(c, target, "gsr_select_match", radius, scope, target_scope, budget, TREE_NONE, &call, &got);
     if (!r) r = match_step(c, "gsr_select_match", &call, M, nullptr, &got);
     if (info && (r == GSR_OK || r == GSR_ERR_ARG)) *info = got;
     if (r) return r;
@@ -269,7 +321,7 @@ int gsr_register(gsr_ctx* c, gsr_ctx* target, const double* M0, double radius, u
     MatchCall call;
     gsr_match_info mi = match_zero_info(budget);
     if (sc.n)
-        if (int r = match_index(c, target, "gsr_register", radius, scope, target_scope, budget, true, &call, &mi)) return r;
+        if (int r = match_index(c, target, "gsr_register", radius, scope, target_scope, budget, TREE_POINT, &call, &mi)) return r;
     for (uint32_t t = 0; t < max_iterations; t++) {
         gsr_match_sums sums{};
         if (sc.n)   // (an empty scene: a step of zeros)
@@ -288,6 +340,149 @@ int gsr_register(gsr_ctx* c, gsr_ctx* target, const double* M0, double radius, u
     }
     if (M_out) std::memcpy(M_out, M, sizeof M);
     if (info) *info = out;
+    return GSR_OK;
+}
+
+int gsr_match_surface(gsr_ctx* c, gsr_ctx* target, const double* M, double radius, uint32_t scope, uint32_t target_scope, uint64_t budget,
+                      const gsr_normal_options* o, gsr_surface_sums* sums, gsr_match_info* info)
+{
+    if (!c) return GSR_ERR_ARG;
+    if (int r = match_check(c, target, "gsr_match_surface", M, radius, scope, target_scope, budget)) return r;
+    if (int r = surface_check(c, target, "gsr_match_surface", target_scope, o)) return r;
+    if (!budget) budget = GSR_NEIGHBOUR_DEFAULT_BUDGET;
+    const SharedScene& sc = *c->scene;
+    gsr_match_info got = match_zero_info(budget);
+    if (sums) *sums = gsr_surface_sums{};
+    if (!sc.n) {
+        if (info) *info = got;
+        return GSR_OK;
+    }
+    const float* normals = nullptr;
+    uint32_t valid = 0u;
+    if (target->scene->n)   // (an empty target matches nothing: no row reads a normal)
+        if (int r = surface_normals(c, target, "gsr_match_surface", o, &normals, &valid)) return r;
+    MatchCall call;
+    gsr_surface_sums s{};
+    int r = match_index(c, target, "gsr_match_surface", radius, scope, target_scope, budget, TREE_SURFACE, &call, &got);
+    if (!r) r = match_step(c, "gsr_match_surface", &call, M, nullptr, &got, normals, &s);
+    if (info && (r == GSR_OK || r == GSR_ERR_ARG)) *info = got;
+    if (r) return r;
+    if (sums) *sums = s;
+    return GSR_OK;
+}
+
+int gsr_register_surface(gsr_ctx* c, gsr_ctx* target, const double* M0, double radius, uint32_t scope, uint32_t target_scope, uint64_t budget,
+                         const gsr_normal_options* o, uint32_t max_iterations, double tolerance, double* M_out, gsr_register_surface_info* info)
+{
+    static const char* who = "gsr_register_surface";
+    if (!c) return GSR_ERR_ARG;
+    if (int r = match_check(c, target, who, M0, radius, scope, target_scope, budget)) return r;
+    if (std::isnan(tolerance) || tolerance < 0.0) return fail(c, GSR_ERR_ARG, "%s: tolerance (%g) must be >= 0 and no NaN", who, tolerance);
+    if (max_iterations < 1u || max_iterations > GSR_REGISTER_MAX_ITERATIONS_LIMIT)
+        return fail(c, GSR_ERR_ARG, "%s: max_iterations (%u) must be in 1 .. %u", who, max_iterations, GSR_REGISTER_MAX_ITERATIONS_LIMIT);
+    if (info && (info->step_pairs || info->step_surface_pairs || info->step_rms || info->step_surface_rms) && info->step_rows < max_iterations)
+        return fail(c, GSR_ERR_ARG, "%s: step_rows (%u) is below max_iterations (%u)", who, info->step_rows, max_iterations);
+    if (int r = surface_check(c, target, who, target_scope, o)) return r;
+    if (!budget) budget = GSR_NEIGHBOUR_DEFAULT_BUDGET;
+    double M[12];
+    std::memcpy(M, M0 ? M0 : IDENTITY, sizeof M);
+    gsr_register_surface_info out{};
+    if (info) out = *info;
+    out.status = GSR_REGISTER_MAX_ITERATIONS; out.iterations = 0u; out.pairs = 0u; out.surface_pairs = 0u; out.rms = INF; out.surface_rms = INF; out.delta = INF;
+    out.valid = 0u;
+    const SharedScene& sc = *c->scene;
+    MatchCall call;
+    gsr_match_info mi = match_zero_info(budget);
+    const float* normals = nullptr;
+    if (sc.n) {
+        if (target->scene->n)
+            if (int r = surface_normals(c, target, who, o, &normals, &out.valid)) return r;
+        if (int r = match_index(c, target, who, radius, scope, target_scope, budget, TREE_SURFACE, &call, &mi)) return r;
+    }
+    for (uint32_t t = 0; t < max_iterations; t++) {
+        gsr_surface_sums sums{};
+        if (sc.n)   // (an empty scene: a step of zeros)
+            if (int r = match_step(c, who, &call, M, nullptr, &mi, normals, &sums)) return r;
+        out.iterations = t + 1u; out.pairs = sums.pairs; out.surface_pairs = sums.surface_pairs;
+        out.rms = sums.pairs ? std::sqrt(sums.sum[28] * (1.0 / (double)sums.pairs)) : INF;
+        out.surface_rms = sums.surface_pairs ? std::sqrt(sums.sum[27] * (1.0 / (double)sums.surface_pairs)) : INF;
+        if (out.step_pairs) out.step_pairs[t] = sums.pairs;
+        if (out.step_surface_pairs) out.step_surface_pairs[t] = sums.surface_pairs;
+        if (out.step_rms) out.step_rms[t] = out.rms;
+        if (out.step_surface_rms) out.step_surface_rms[t] = out.surface_rms;
+        if (sums.surface_pairs < 6u) { out.status = GSR_REGISTER_TOO_FEW; break; }
+        double D[12];
+        int32_t degenerate = 0;
+        if (gsr_surface_solve(&sums, D, nullptr, &degenerate)) return fail(c, GSR_ERR_HIP, "%s: step %u left sums that are not finite", who, t);
+        if (degenerate) { out.status = GSR_REGISTER_DEGENERATE; break; }
+        double delta = 0.0;
+        for (int k = 0; k < 12; k++) delta = std::fmax(delta, std::fabs(D[k] - IDENTITY[k]));
+        out.delta = delta;
+        gsr_rigid_compose(D, M, M);
+        if (delta <= tolerance) { out.status = GSR_REGISTER_CONVERGED; break; }
+    }
+    if (M_out) std::memcpy(M_out, M, sizeof M);
+    if (info) *info = out;
+    return GSR_OK;
+}
+
+// The 6 x 6 normal equations of the point-to-plane residuals by Cholesky, and the Cayley step, in the header's written order.
+// f64; no context, no device.
+int gsr_surface_solve(const gsr_surface_sums* sums, double* D, double* rms, int32_t* degenerate)
+{
+    if (!sums || !D || !degenerate) return fail(nullptr, GSR_ERR_ARG, "gsr_surface_solve: a NULL pointer");
+    if (sums->surface_pairs < 6u)
+        return fail(nullptr, GSR_ERR_ARG, "gsr_surface_solve: %llu pairs with a normal: at least 6 are needed", (unsigned long long)sums->surface_pairs);
+    for (uint32_t k = 0; k < MATCH_SURFACE_ROW; k++)
+        if (!std::isfinite(sums->sum[k])) return fail(nullptr, GSR_ERR_ARG, "gsr_surface_solve: sum %u is %g: it must be finite", k, sums->sum[k]);
+    const double* s = sums->sum;
+    const double inv = 1.0 / (double)sums->surface_pairs;
+    double A[6][6], g[6], L[6][6] = {};
+    for (int a = 0, at = 0; a < 6; a++)
+        for (int b = a; b < 6; b++, at++) A[a][b] = A[b][a] = s[at];
+    for (int a = 0; a < 6; a++) g[a] = -s[21 + a];
+    double top = A[0][0];
+    for (int a = 1; a < 6; a++) top = A[a][a] > top ? A[a][a] : top;
+    const double pivot_floor = top * 0x1p-40;
+    for (int j = 0; j < 6; j++) {
+        double v = A[j][j];
+        for (int k = 0; k < j; k++) v = v - L[j][k] * L[j][k];
+        if (!(v > pivot_floor)) {
+            *degenerate = j + 1;
+            std::memcpy(D, IDENTITY, sizeof IDENTITY);
+            return GSR_OK;
+        }
+        L[j][j] = std::sqrt(v);
+        for (int i = j + 1; i < 6; i++) {
+            v = A[i][j];
+            for (int k = 0; k < j; k++) v = v - L[i][k] * L[j][k];
+            L[i][j] = v / L[j][j];
+        }
+    }
+    double y[6], x[6];
+    for (int i = 0; i < 6; i++) {
+        double v = g[i];
+        for (int k = 0; k < i; k++) v = v - L[i][k] * y[k];
+        y[i] = v / L[i][i];
+    }
+    for (int i = 5; i >= 0; i--) {
+        double v = y[i];
+        for (int k = i + 1; k < 6; k++) v = v - L[k][i] * x[k];
+        x[i] = v / L[i][i];
+    }
+    double w = 1.0, qx = 0.5 * x[0], qy = 0.5 * x[1], qz = 0.5 * x[2];
+    const double len = std::sqrt(((w * w + qx * qx) + qy * qy) + qz * qz);
+    w = w / len; qx = qx / len; qy = qy / len; qz = qz / len;
+    double R[3][3];
+    R[0][0] = 1.0 - 2.0 * (qy * qy + qz * qz); R[0][1] = 2.0 * (qx * qy - qz * w); R[0][2] = 2.0 * (qx * qz + qy * w);
+    R[1][0] = 2.0 * (qx * qy + qz * w); R[1][1] = 1.0 - 2.0 * (qx * qx + qz * qz); R[1][2] = 2.0 * (qy * qz - qx * w);
+    R[2][0] = 2.0 * (qx * qz - qy * w); R[2][1] = 2.0 * (qy * qz + qx * w); R[2][2] = 1.0 - 2.0 * (qx * qx + qy * qy);
+    for (int k = 0; k < 3; k++) {
+        D[4 * k + 0] = R[k][0]; D[4 * k + 1] = R[k][1]; D[4 * k + 2] = R[k][2];
+        D[4 * k + 3] = x[3 + k];
+    }
+    if (rms) *rms = std::sqrt(s[27] * inv);
+    *degenerate = 0;
     return GSR_OK;
 }
 
@@ -419,7 +614,7 @@ int gsr_debug_match_scratch(gsr_ctx* c, uint64_t* bytes)
 {
     if (!c || !bytes) return GSR_ERR_ARG;
     const gsr_ctx::Match& mt = c->mt;
-    *bytes = (mt.words ? MATCH_INFO_WORDS * 4ull : 0ull) + (uint64_t)mt.rows * 12u + mt.tree_rows * MATCH_ROW * 8u;
+    *bytes = (mt.words ? MATCH_INFO_WORDS * 4ull : 0ull) + (uint64_t)mt.rows * 12u + mt.tree_rows * MATCH_ROW * 8u + mt.surface_rows * MATCH_SURFACE_ROW * 8u;
     return GSR_OK;
 }
 

@@ -26,22 +26,6 @@ static_assert(NORMAL_KNN == GSR_NORMAL_KNN && NORMAL_OWN == GSR_NORMAL_OWN && NO
 static_assert(sizeof(gsr_normal_options) == 56 && sizeof(gsr_normal_info) == 48, "the header's layout");
 constexpr double INF = std::numeric_limits<double>::infinity();
 
-// the refusals the two calls share, in the header's order.  Nothing is touched by a refused call.
-int normal_check(gsr_ctx* c, const char* who, const gsr_normal_options* o)
-{
-    if (!o) return fail(c, GSR_ERR_ARG, "%s: options is NULL", who);
-    if (o->source != GSR_NORMAL_KNN && o->source != GSR_NORMAL_OWN) return fail(c, GSR_ERR_ARG, "%s: unknown source %d", who, o->source);
-    if (o->source == GSR_NORMAL_KNN) {
-        if (int r = nb_check(c, who, o->radius, o->k, o->scope, o->budget, NORMAL_MIN_K, "k", GSR_KNN_MAX_K)) return r;
-    } else if (int r = scope_check(c, who, o->scope, o->budget)) {
-        return r;
-    }
-    if (o->oriented)
-        for (int j = 0; j < 3; j++)
-            if (!std::isfinite(o->toward[j])) return fail(c, GSR_ERR_ARG, "%s: toward[%d] is %g: it must be finite", who, j, o->toward[j]);
-    return GSR_OK;
-}
-
 // the context's scratch for n splats: allocated by the first call, only ever grown
 int normal_ensure(gsr_ctx* c, uint32_t n)
 {
@@ -64,6 +48,26 @@ gsr_normal_info normal_zero_info(uint64_t budget)
     z.variation_min = INF;
     z.variation_max = -INF;
     return z;
+}
+
+}  // namespace
+
+namespace gsr {
+
+// the refusals the two calls share, in the header's order.  Nothing is touched by a refused call.
+int normal_check(gsr_ctx* c, const char* who, const gsr_normal_options* o)
+{
+    if (!o) return fail(c, GSR_ERR_ARG, "%s: options is NULL", who);
+    if (o->source != GSR_NORMAL_KNN && o->source != GSR_NORMAL_OWN) return fail(c, GSR_ERR_ARG, "%s: unknown source %d", who, o->source);
+    if (o->source == GSR_NORMAL_KNN) {
+        if (int r = nb_check(c, who, o->radius, o->k, o->scope, o->budget, NORMAL_MIN_K, "k", GSR_KNN_MAX_K)) return r;
+    } else if (int r = scope_check(c, who, o->scope, o->budget)) {
+        return r;
+    }
+    if (o->oriented)
+        for (int j = 0; j < 3; j++)
+            if (!std::isfinite(o->toward[j])) return fail(c, GSR_ERR_ARG, "%s: toward[%d] is %g: it must be finite", who, j, o->toward[j]);
+    return GSR_OK;
 }
 
 // Everything up to the read-backs: (KNN) the index and its bound (nb_index), the fill and the walk, or (OWN) the one kernel; *info,
@@ -122,7 +126,7 @@ int normal_run(gsr_ctx* c, const char* who, const gsr_normal_options* o, uint64_
     return GSR_OK;
 }
 
-}  // namespace
+}  // namespace gsr
 
 extern "C" {
 

@@ -23,6 +23,13 @@
 // LDS, s = 32 .. 1 through __shfl_down in the first wave (tree_reduce).  Level 1 (k_match_rows) rebuilds each row from idx[i]
 // and d2[i]; the further levels (k_match_tree) read the partial rows.  1 M splats are three launches.
 //
+//
+// Point to plane ("Point-to-plane registration").  The same match, reduced to the sums of a 6 x 6 linear solve
+// along the TARGET's normals: a row is 29 doubles (J_a * J_b for a <= b, J_a * r, r * r, d2 with J = (T x n, n), r = n . (T - Q)),
+// non-zero iff the splat is matched and its match has a normal.  tree_reduce and tree_level are templates over the row width; a
+// component's tree does not depend on the other components, so the 29-wide tree is the 16-wide one per component.  One pass: 29 x
+// 256 doubles of LDS (59 392 bytes).  k_match_surface_rows also counts its non-zero rows, one atomic per wave.
+//
 // Compiled with -ffp-contract=off like the rest of the device code.
 #include "gsr_internal.h"
 #include "k_splat_ops.h"
@@ -31,6 +38,7 @@
 namespace gsr {
 
 GSR_BOUNDS_DECL(match)   // sites: 0 set word, 1 source row, 2 bucket, 3 entry slot, 4 target row, 5 partial row, 6 selection word, 7 LDS cell
+GSR_BOUNDS_DECL(match_surface)   // the sites behind those eight, in words of their own: 8 (word 0) the target's normal row
 
 // the sites of the shared helpers (k_splat_ops.h, k_neighbours.h)
 struct match_sites {
@@ -130,34 +138,35 @@ __global__ __launch_bounds__(NB_THREADS) void k_match(NbIndex ix, uint32_t m /* 
 }
 
 // ---- the tree ----
-// One group: every lane's row v summed into out[0 .. MATCH_ROW) by the tree of the header.  s_rows: MATCH_ROW * MATCH_GROUP doubles,
+// One group: every lane's row v of W doubles summed into out[0 .. W) by the tree of the header.  s_rows: W * MATCH_GROUP doubles,
 // component c of lane l at [c * MATCH_GROUP + l] (consecutive lanes on consecutive banks).  Every lane of the workgroup calls it.
-__device__ __forceinline__ void tree_reduce(double (&v)[MATCH_ROW], double* s_rows, double* __restrict__ out)
+template <uint32_t W>
+__device__ __forceinline__ void tree_reduce(double (&v)[W], double* s_rows, double* __restrict__ out)
 {
     const uint32_t l = threadIdx.x;
 #pragma unroll
-    for (uint32_t c = 0u; c < MATCH_ROW; c++) s_rows[c * MATCH_GROUP + l] = v[c];
+    for (uint32_t c = 0u; c < W; c++) s_rows[c * MATCH_GROUP + l] = v[c];
     __syncthreads();
     if (l < 128u) {
 #pragma unroll
-        for (uint32_t c = 0u; c < MATCH_ROW; c++) {
-            GSR_BOUND(match, 7, c * MATCH_GROUP + l + 128u, MATCH_ROW * MATCH_GROUP);
+        for (uint32_t c = 0u; c < W; c++) {
+            GSR_BOUND(match, 7, c * MATCH_GROUP + l + 128u, W * MATCH_GROUP);
             s_rows[c * MATCH_GROUP + l] = s_rows[c * MATCH_GROUP + l] + s_rows[c * MATCH_GROUP + l + 128u];
         }
     }
     __syncthreads();
     if (l >= 64u) return;   // the first wave, whole
 #pragma unroll
-    for (uint32_t c = 0u; c < MATCH_ROW; c++) v[c] = s_rows[c * MATCH_GROUP + l] + s_rows[c * MATCH_GROUP + l + 64u];
+    for (uint32_t c = 0u; c < W; c++) v[c] = s_rows[c * MATCH_GROUP + l] + s_rows[c * MATCH_GROUP + l + 64u];
     // x[l] = x[l] + x[l + s] for l < s: a lane at or above s adds what no lane below the next s reads
 #pragma unroll
     for (int s = 32; s > 0; s >>= 1) {
 #pragma unroll
-        for (uint32_t c = 0u; c < MATCH_ROW; c++) v[c] = v[c] + __shfl_down(v[c], s);
+        for (uint32_t c = 0u; c < W; c++) v[c] = v[c] + __shfl_down(v[c], s);
     }
     if (l != 0u) return;
 #pragma unroll
-    for (uint32_t c = 0u; c < MATCH_ROW; c++) out[c] = v[c];
+    for (uint32_t c = 0u; c < W; c++) out[c] = v[c];
 }
 
 // level 1: group g = rows [256 g, 256 g + 256) of the source, rebuilt from idx[] and d2[]
@@ -190,16 +199,73 @@ __global__ __launch_bounds__(MATCH_GROUP) void k_match_rows(MatchSource src, con
     tree_reduce(v, s_rows, out + (uint64_t)blockIdx.x * MATCH_ROW);
 }
 
-// a further level: group g = rows [256 g, 256 g + 256) of `in`, `count` rows
+// a further level: group g = rows [256 g, 256 g + 256) of `in`, `count` rows of W doubles
+template <uint32_t W>
+__device__ __forceinline__ void tree_level(const double* __restrict__ in, uint32_t count, double* __restrict__ out, uint32_t groups, double* s_rows)
+{
+    double v[W];
+    const uint64_t i = (uint64_t)blockIdx.x * MATCH_GROUP + threadIdx.x;
+#pragma unroll
+    for (uint32_t c = 0u; c < W; c++) v[c] = i < count ? in[i * W + c] : 0.0;
+    GSR_BOUND(match, 5, blockIdx.x, groups);
+    tree_reduce(v, s_rows, out + (uint64_t)blockIdx.x * W);
+}
+
 __global__ __launch_bounds__(MATCH_GROUP) void k_match_tree(const double* __restrict__ in, uint32_t count, double* __restrict__ out, uint32_t groups)
 {
     __shared__ double s_rows[MATCH_ROW * MATCH_GROUP];
-    double v[MATCH_ROW];
-    const uint64_t i = (uint64_t)blockIdx.x * MATCH_GROUP + threadIdx.x;
+    tree_level<MATCH_ROW>(in, count, out, groups, s_rows);
+}
+
+// ---- the point-to-plane tree ----
+// level 1: the row of source splat i from idx[i], d2[i], the target's position and the target's stored normal.  A NaN n_x is "no
+// normal": nothing of that row is computed, so no NaN enters the tree.
+__global__ __launch_bounds__(MATCH_GROUP) void k_match_surface_rows(MatchSource src, const float* __restrict__ qx, const float* __restrict__ qy,
+                                                                    const float* __restrict__ qz, const float* __restrict__ normals, uint32_t tn,
+                                                                    const uint32_t* __restrict__ idx, const double* __restrict__ d2, double* __restrict__ out,
+                                                                    uint32_t groups, MatchInfo* __restrict__ info)
+{
+    __shared__ double s_rows[MATCH_SURFACE_ROW * MATCH_GROUP];
+    double v[MATCH_SURFACE_ROW];
 #pragma unroll
-    for (uint32_t c = 0u; c < MATCH_ROW; c++) v[c] = i < count ? in[i * MATCH_ROW + c] : 0.0;
+    for (uint32_t c = 0u; c < MATCH_SURFACE_ROW; c++) v[c] = 0.0;
+    bool surface = false;
+    const uint64_t i = (uint64_t)blockIdx.x * MATCH_GROUP + threadIdx.x;
+    if (i < src.n) {
+        const uint32_t j = idx[i];
+        double t[3];
+        if (j != MATCH_NONE) GSR_BOUND(match, 4, j, tn);
+        if (j < tn && match_point(src, i, t[0], t[1], t[2])) {   // (a match is a query: its point is finite)
+            GSR_BOUND(match_surface, 0, 3ull * j + 2ull, 3ull * tn);
+            const float fx = normals[3ull * j], fy = normals[3ull * j + 1ull], fz = normals[3ull * j + 2ull];
+            if (fx == fx) {
+                const double n[3] = {(double)fx, (double)fy, (double)fz};
+                const double e[3] = {t[0] - (double)qx[j], t[1] - (double)qy[j], t[2] - (double)qz[j]};
+                const double r = (n[0] * e[0] + n[1] * e[1]) + n[2] * e[2];
+                const double J[6] = {t[1] * n[2] - t[2] * n[1], t[2] * n[0] - t[0] * n[2], t[0] * n[1] - t[1] * n[0], n[0], n[1], n[2]};
+#pragma unroll
+                for (int a = 0; a < 6; a++) {
+#pragma unroll
+                    for (int b = a; b < 6; b++) v[6 * a - a * (a - 1) / 2 + (b - a)] = J[a] * J[b];   // 00, 01, .., 05, 11, .., 55
+                }
+#pragma unroll
+                for (int a = 0; a < 6; a++) v[21 + a] = J[a] * r;
+                v[27] = r * r;
+                v[28] = d2[i];
+                surface = true;
+            }
+        }
+    }
+    const uint32_t rows = (uint32_t)__popcll(__ballot(surface));
+    if ((threadIdx.x & 63u) == 0u && rows) __hip_atomic_fetch_add(&info->surface, rows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     GSR_BOUND(match, 5, blockIdx.x, groups);
-    tree_reduce(v, s_rows, out + (uint64_t)blockIdx.x * MATCH_ROW);
+    tree_reduce(v, s_rows, out + (uint64_t)blockIdx.x * MATCH_SURFACE_ROW);
+}
+
+__global__ __launch_bounds__(MATCH_GROUP) void k_match_surface_tree(const double* __restrict__ in, uint32_t count, double* __restrict__ out, uint32_t groups)
+{
+    __shared__ double s_rows[MATCH_SURFACE_ROW * MATCH_GROUP];
+    tree_level<MATCH_SURFACE_ROW>(in, count, out, groups, s_rows);
 }
 
 // ---- the picker ----
@@ -242,6 +308,23 @@ void launch_match_tree(const MatchSource& src, const float* qx, const float* qy,
         groups = (count + MATCH_GROUP - 1u) / MATCH_GROUP;
         double* out = partial + behind * MATCH_ROW;
         hipLaunchKernelGGL(k_match_tree, dim3(groups), dim3(MATCH_GROUP), 0, s, in, count, out, groups);
+        in = out;
+        behind += groups;
+        count = groups;
+    }
+}
+
+void launch_match_surface_tree(const MatchSource& src, const float* qx, const float* qy, const float* qz, const float* normals, uint32_t tn, const uint32_t* idx,
+                               const double* d2, double* partial, MatchInfo* info, hipStream_t s)
+{
+    uint32_t groups = (uint32_t)(((uint64_t)src.n + MATCH_GROUP - 1u) / MATCH_GROUP);
+    hipLaunchKernelGGL(k_match_surface_rows, dim3(groups), dim3(MATCH_GROUP), 0, s, src, qx, qy, qz, normals, tn, idx, d2, partial, groups, info);
+    const double* in = partial;
+    uint64_t behind = groups;   // rows of the levels so far
+    for (uint32_t count = groups; count > 1u;) {
+        groups = (count + MATCH_GROUP - 1u) / MATCH_GROUP;
+        double* out = partial + behind * MATCH_SURFACE_ROW;
+        hipLaunchKernelGGL(k_match_surface_tree, dim3(groups), dim3(MATCH_GROUP), 0, s, in, count, out, groups);
         in = out;
         behind += groups;
         count = groups;

@@ -111,6 +111,15 @@ export interface SceneMatch { idx: Uint32Array; d2: Float64Array; inScope: numbe
 export type RegisterStatus = "converged" | "max_iterations" | "too_few";
 export interface Registration { transform: Float64Array; rotation: Quaternion; translation: Vector3; status: RegisterStatus; iterations: number; pairs: number;
     rms: number; stepPairs?: Float64Array; stepRms?: Float64Array }
+/** How a target's normals are made for point-to-plane registration: its splats' own shortest axes (the default), or the PCA of the
+ *  k (2 .. 32, default 8) nearest within radius, as splatNormals. */
+export interface SurfaceNormals { source?: "own" | "knn"; radius?: number; k?: number; budget?: number }
+export type SurfaceRegisterStatus = RegisterStatus | "degenerate";
+export interface SurfaceRegistration { transform: Float64Array; rotation: Quaternion; translation: Vector3; status: SurfaceRegisterStatus; iterations: number; pairs: number;
+    surfacePairs: number; rms: number; surfaceRms: number; delta: number; valid: number; stepPairs?: Float64Array; stepSurfacePairs?: Float64Array; stepRms?: Float64Array;
+    stepSurfaceRms?: Float64Array }
+export interface SurfaceMatch { pairs: number; surfacePairs: number; sums: Float64Array; inScope: number; nonfinite: number; targetIndexed: number; matched: number;
+    pairBound: number; d2Min: number; d2Max: number }
 export interface ClusterOptions { minPts?: number; scope?: NeighbourScope | NeighbourScope[]; budget?: number }
 export interface SplatClusters { labels: Uint32Array; sizes: Uint32Array; inScope: number; nonfinite: number; pairBound: number; core: number; border: number;
     noise: number; clusters: number; largestLabel: number; largestSize: number }
@@ -448,6 +457,15 @@ export class HIPRenderer {
     selectMatch(target: HIPRenderer, radius: number, options?: MatchOptions & { lo?: number; hi?: number; op?: SelectOp }): number;
     registerTo(target: HIPRenderer, radius: number, options?: MatchOptions & { maxIterations?: number; tolerance?: number; history?: boolean }): Registration;
     rigidDecompose(transform: RigidTransform): { rotation: Quaternion; translation: Vector3 };
+    /** Point-to-plane registration: registerTo with residual "surface" pulls every splat toward the target's SURFACE along the normal
+     *  of its match, not toward the nearest sample: far fewer steps on floors, walls and table tops, and no biased pose.  normals
+     *  says how the target's normals are made, once per call.  It stops "too_few" with fewer than 6 pairs that have a normal and
+     *  "degenerate" when the residuals leave a direction free (a target of one or two planes).  residual "point", the default, is
+     *  registerTo as above.  matchSurface is one such step as data: the 29 sums SPLAT.surfaceSolve takes. */
+    registerTo(target: HIPRenderer, radius: number, options: MatchOptions & { residual: "surface"; normals?: SurfaceNormals; maxIterations?: number; tolerance?: number;
+        history?: boolean }): SurfaceRegistration;
+    registerTo(target: HIPRenderer, radius: number, options: MatchOptions & { residual: "point"; maxIterations?: number; tolerance?: number; history?: boolean }): Registration;
+    matchSurface(target: HIPRenderer, radius: number, options?: MatchOptions & { normals?: SurfaceNormals }): SurfaceMatch;
     /** Clusters: the connected islands of the splats in scope at the linking radius `radius` (f64, distance exactly radius links).
      *  minPts (0 .. 4095, default 0: plain connected components) makes it DBSCAN: a splat with minPts or more others within radius is
      *  core, core splats within radius of each other share a cluster, a non-core splat beside a core one takes the smallest such
@@ -585,5 +603,8 @@ export class OrbitControls {
 /** The band matrices [D_1 (3 x 3), D_2 (5 x 5), D_3 (7 x 7)], row-major, that rotate SH coefficients by q (finite, not zero;
  *  normalised): c' = D_l c makes the colour seen from d the colour formerly seen from R(q)^T d.  A pure function: no device. */
 export function shRotation(q: Quaternion | [number, number, number, number] | Float64Array): [Float64Array, Float64Array, Float64Array];
+/** One point-to-plane step solved (a pure function, no device): the small rigid motion of matchSurface's sums.  degenerate = j + 1
+ *  when pivot j of the 6 x 6 system is not above its floor: transform is then the identity and rms NaN. */
+export function surfaceSolve(sums: { surfacePairs: number; sums: ArrayLike<number> }): { transform: Float64Array; rms: number; degenerate: number };
 export function sortHost(viewProj: Float32Array, vertexCount: number, fBuffer: Float32Array,
                          depthBuffer: Uint32Array | null, depthIndex: Uint32Array): void;

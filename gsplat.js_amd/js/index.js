@@ -1,7 +1,7 @@
 "use strict";
 // Public API: the export list of src/index.ts:1-12.  WebGLRenderer is the HIP renderer under the name callers of
 // the reference already use.
-const { HIPRenderer, sortHost, shRotation } = require("./renderers/HIPRenderer");
+const { HIPRenderer, sortHost, shRotation, surfaceSolve } = require("./renderers/HIPRenderer");
 module.exports = {
     Camera: require("./cameras/Camera").Camera,
     Scene: require("./core/Scene").Scene,
@@ -18,4 +18,5 @@ module.exports = {
     FadeInPass: require("./renderers/FadeInPass").FadeInPass,
     sortHost: sortHost,
     shRotation: shRotation,
+    surfaceSolve: surfaceSolve,
 };

@@ -5,6 +5,7 @@
 #include <node_api.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -1833,6 +1834,125 @@ napi_value RegisterTo(napi_env env, napi_callback_info info)
     return out;
 }
 
+// ---- point-to-plane registration (gsr_match_surface / gsr_register_surface / gsr_surface_solve) ----
+// the target's normals at argv[at .. at + 3]: source (GSR_NORMAL_*), radius, k and budget; the scope is the target scope's; false: an
+// error is pending
+bool get_surface_normals(napi_env env, napi_value* argv, int at, uint32_t target_scope, gsr_normal_options* o)
+{
+    double radius, b;
+    uint32_t k;
+    if (!get_i32(env, argv[at], &o->source) || !get_f64(env, argv[at + 1], &radius) || napi_get_value_uint32(env, argv[at + 2], &k) != napi_ok || !get_f64(env, argv[at + 3], &b)) {
+        napi_throw_type_error(env, nullptr, "normals: source, radius, k and budget must be numbers");
+        return false;
+    }
+    if (!(b >= 0.0 && b <= 18446744073709549568.0)) { napi_throw_range_error(env, nullptr, "normals: budget must be a non-negative number"); return false; }
+    o->radius = radius; o->k = k; o->budget = (uint64_t)b; o->scope = target_scope;
+    return true;
+}
+
+// matchSurface(handle, target, transform | null, radius, scope, targetScope, budget, normalSource, normalRadius, normalK, normalBudget) ->
+//   { pairs, surfacePairs, sums: Float64Array(29), inScope, nonfinite, targetIndexed, matched, pairBound, budget, d2Min, d2Max }
+napi_value MatchSurface(napi_env env, napi_callback_info info)
+{
+    napi_value argv[11];
+    if (!get_args(env, info, 11, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    MatchArgs a;
+    gsr_normal_options no{};
+    if (!c || !get_match_args(env, argv, &a) || !get_surface_normals(env, argv, 7, a.target_scope, &no)) return nullptr;
+    void* sum = nullptr;
+    napi_value sarr, out;
+    if (!(sarr = new_f64_array(env, 29, &sum))) return nullptr;
+    gsr_match_info mi{};
+    gsr_surface_sums ss{};
+    const int rc = gsr_match_surface(c, a.target, a.M, a.radius, a.scope, a.target_scope, a.budget, &no, &ss, &mi);
+    if (rc) return throw_gsr(env, c, rc, "gsr_match_surface");
+    std::memcpy(sum, ss.sum, sizeof ss.sum);
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "sums", sarr));
+    if (!set_f64(env, out, "pairs", (double)ss.pairs) || !set_f64(env, out, "surfacePairs", (double)ss.surface_pairs) || !set_u32(env, out, "inScope", mi.in_scope) ||
+        !set_u32(env, out, "nonfinite", mi.nonfinite) || !set_u32(env, out, "targetIndexed", mi.target_indexed) || !set_u32(env, out, "matched", mi.matched) ||
+        !set_f64(env, out, "pairBound", (double)mi.pair_bound) || !set_f64(env, out, "budget", (double)mi.budget) || !set_f64(env, out, "d2Min", mi.d2_min) ||
+        !set_f64(env, out, "d2Max", mi.d2_max)) return nullptr;
+    return out;
+}
+
+// registerSurface(handle, target, transform | null, radius, scope, targetScope, budget, normalSource, normalRadius, normalK, normalBudget, maxIterations,
+//   tolerance, history) -> { transform: Float64Array(12), q: Float64Array(4) (x, y, z, w), t: Float64Array(3), status, iterations, pairs, surfacePairs, rms,
+//   surfaceRms, delta, valid[, stepPairs, stepSurfacePairs, stepRms, stepSurfaceRms: Float64Array] }
+napi_value RegisterSurface(napi_env env, napi_callback_info info)
+{
+    napi_value argv[14];
+    if (!get_args(env, info, 14, argv)) return nullptr;
+    gsr_ctx* c = get_ctx(env, argv[0]);
+    MatchArgs a;
+    gsr_normal_options no{};
+    uint32_t steps;
+    double tolerance;
+    bool history = false;
+    if (!c || !get_match_args(env, argv, &a) || !get_surface_normals(env, argv, 7, a.target_scope, &no)) return nullptr;
+    if (napi_get_value_uint32(env, argv[11], &steps) != napi_ok || !get_f64(env, argv[12], &tolerance) || napi_get_value_bool(env, argv[13], &history) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "registerSurface: maxIterations and tolerance must be numbers, history a boolean");
+        return nullptr;
+    }
+    if (steps < 1 || steps > GSR_REGISTER_MAX_ITERATIONS_LIMIT) { napi_throw_range_error(env, nullptr, "registerSurface: maxIterations must be in 1 .. 256"); return nullptr; }
+    void *M = nullptr, *q = nullptr, *t = nullptr;
+    napi_value marr, qarr, tarr, out;
+    if (!(marr = new_f64_array(env, 12, &M)) || !(qarr = new_f64_array(env, 4, &q)) || !(tarr = new_f64_array(env, 3, &t))) return nullptr;
+    uint64_t step_pairs[GSR_REGISTER_MAX_ITERATIONS_LIMIT], step_surface_pairs[GSR_REGISTER_MAX_ITERATIONS_LIMIT];
+    double step_rms[GSR_REGISTER_MAX_ITERATIONS_LIMIT], step_surface_rms[GSR_REGISTER_MAX_ITERATIONS_LIMIT];
+    gsr_register_surface_info ri{};
+    if (history) { ri.step_pairs = step_pairs; ri.step_surface_pairs = step_surface_pairs; ri.step_rms = step_rms; ri.step_surface_rms = step_surface_rms; ri.step_rows = steps; }
+    int rc = gsr_register_surface(c, a.target, a.M, a.radius, a.scope, a.target_scope, a.budget, &no, steps, tolerance, (double*)M, &ri);
+    if (rc) return throw_gsr(env, c, rc, "gsr_register_surface");
+    rc = gsr_rigid_decompose((const double*)M, (double*)q, (double*)t);
+    if (rc) return throw_gsr(env, nullptr, rc, "gsr_rigid_decompose");
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "transform", marr));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "q", qarr));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "t", tarr));
+    if (history) {
+        const char* names[4] = {"stepPairs", "stepSurfacePairs", "stepRms", "stepSurfaceRms"};
+        for (int which = 0; which < 4; which++) {
+            void* p = nullptr;
+            napi_value arr = new_f64_array(env, ri.iterations, &p);
+            if (!arr) return nullptr;
+            for (uint32_t k = 0; k < ri.iterations; k++)
+                ((double*)p)[k] = which == 0 ? (double)step_pairs[k] : which == 1 ? (double)step_surface_pairs[k] : which == 2 ? step_rms[k] : step_surface_rms[k];
+            NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, names[which], arr));
+        }
+    }
+    if (!set_u32(env, out, "status", (uint32_t)ri.status) || !set_u32(env, out, "iterations", ri.iterations) || !set_f64(env, out, "pairs", (double)ri.pairs) ||
+        !set_f64(env, out, "surfacePairs", (double)ri.surface_pairs) || !set_f64(env, out, "rms", ri.rms) || !set_f64(env, out, "surfaceRms", ri.surface_rms) ||
+        !set_f64(env, out, "delta", ri.delta) || !set_u32(env, out, "valid", ri.valid)) return nullptr;
+    return out;
+}
+
+// surfaceSolve(surfacePairs, sums: Float64Array(29)) -> { transform: Float64Array(12), rms, degenerate }   (no handle: a pure function)
+napi_value SurfaceSolve(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    double pairs;
+    const double* sum = nullptr;
+    if (!get_f64(env, argv[0], &pairs) || !(pairs >= 0.0 && pairs <= 9007199254740992.0)) { napi_throw_type_error(env, nullptr, "surfaceSolve: surfacePairs must be a non-negative number"); return nullptr; }
+    if (!get_f64_array(env, argv[1], 29, "surfaceSolve: sums must hold 29 values", &sum)) return nullptr;
+    gsr_surface_sums ss{};
+    ss.pairs = ss.surface_pairs = (uint64_t)pairs;
+    std::memcpy(ss.sum, sum, sizeof ss.sum);
+    void* D = nullptr;
+    napi_value darr, out;
+    if (!(darr = new_f64_array(env, 12, &D))) return nullptr;
+    double rms = 0.0;
+    int32_t degenerate = 0;
+    const int rc = gsr_surface_solve(&ss, (double*)D, &rms, &degenerate);
+    if (rc) return throw_gsr(env, nullptr, rc, "gsr_surface_solve");
+    NAPI_OK_OR_NULL(env, napi_create_object(env, &out));
+    NAPI_OK_OR_NULL(env, napi_set_named_property(env, out, "transform", darr));
+    if (!set_f64(env, out, "rms", degenerate ? std::nan("") : rms) || !set_u32(env, out, "degenerate", (uint32_t)degenerate)) return nullptr;
+    return out;
+}
+
 // rigidDecompose(transform: Float64Array(12)) -> { q: Float64Array(4) (x, y, z, w), t: Float64Array(3) }   (no handle: a pure function)
 napi_value RigidDecompose(napi_env env, napi_callback_info info)
 {
@@ -2292,6 +2412,7 @@ napi_value Init(napi_env env, napi_value exports)
         {"neighbours", Neighbours}, {"selectNeighbours", SelectNeighbours},
         {"fitPlane", FitPlane}, {"planeInliers", PlaneInliers}, {"selectPlane", SelectPlane}, {"planeAlignment", PlaneAlignment},
         {"matchScene", MatchScene}, {"selectMatch", SelectMatch}, {"registerTo", RegisterTo}, {"rigidDecompose", RigidDecompose},
+        {"matchSurface", MatchSurface}, {"registerSurface", RegisterSurface}, {"surfaceSolve", SurfaceSolve},
         {"clusters", Clusters}, {"selectClusters", SelectClusters}, {"selectClusterAt", SelectClusterAt},
         {"knn", Knn}, {"selectKnn", SelectKnn},
         {"normals", Normals}, {"selectNormal", SelectNormal},

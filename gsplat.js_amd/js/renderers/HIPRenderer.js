@@ -685,11 +685,46 @@ class HIPRenderer {
             if (Number.isNaN(lo) || Number.isNaN(hi) || lo > hi) throw new Error("selectMatch: lo <= hi must hold, neither a NaN");
             return this._n.selectMatch(this._h, ...args, lo, hi, code(OPS, o2.op, "replace", "op"));
         };
+        // Point to plane (gsr_match_surface / gsr_register_surface): registerTo(other, radius, { residual: "surface", normals: { source:
+        // "own" | "knn", radius, k } }) pulls every splat toward the other capture's SURFACE along the normal of its match instead of
+        // toward the nearest sample -- far fewer steps on floors, walls and table tops, and no biased pose; normals says how `target`'s
+        // normals are made (default its splats' own shortest axes; "knn" as splatNormals), once per call.  It adds status "degenerate"
+        // (the residuals leave a direction free: a target of one or two planes; "too_few" is fewer than 6 pairs with a normal) and
+        // surfacePairs, surfaceRms, valid.  residual "point", the default, is the path above.  matchSurface is one such step as data:
+        // { pairs, surfacePairs, sums: Float64Array(29) }, what SPLAT.surfaceSolve takes.
+        const SURFACE_STATUS = REGISTER_STATUS.concat(["degenerate"]);
+        const surfaceNormals = (o) => {
+            const nm = o.normals || {}, source = code(NORMAL_SOURCES, nm.source, "own", "normals.source");
+            const budget = nm.budget === undefined || nm.budget === null ? 0 : Number(nm.budget);
+            if (!(budget >= 0)) throw new Error("normals.budget must be a non-negative number");
+            if (source === NORMAL_SOURCES.own) return [source, 0, 0, budget];
+            const k = nm.k === undefined ? 8 : nm.k;
+            if (!(Number(nm.radius) > 0)) throw new Error("normals: the knn source needs a radius");
+            if (!Number.isInteger(k) || k < 2 || k > 32) throw new Error("normals.k must be an integer in 2 .. 32");
+            return [source, Number(nm.radius), k, budget];
+        };
+        this.matchSurface = (target, radius, options) => {
+            const o2 = options || {};
+            const r = this._n.matchSurface(this._h, ...matchArgs(target, radius, o2), ...surfaceNormals(o2));
+            return { pairs: r.pairs, surfacePairs: r.surfacePairs, sums: r.sums, inScope: r.inScope, nonfinite: r.nonfinite, targetIndexed: r.targetIndexed,
+                     matched: r.matched, pairBound: r.pairBound, d2Min: r.d2Min, d2Max: r.d2Max };
+        };
         this.registerTo = (target, radius, options) => {
             const o2 = options || {}, args = matchArgs(target, radius, o2);
             const steps = o2.maxIterations === undefined ? 32 : o2.maxIterations, tolerance = o2.tolerance === undefined ? 2 ** -40 : Number(o2.tolerance);
             if (!Number.isInteger(steps) || steps < 1 || steps > 256) throw new Error("maxIterations must be an integer in 1 .. 256");
             if (!(tolerance >= 0)) throw new Error("tolerance must be a non-negative number");
+            const residual = o2.residual === undefined ? "point" : o2.residual;
+            if (residual !== "point" && residual !== "surface") throw new Error("residual is \"point\" or \"surface\"");
+            if (residual === "surface") {
+                const s = this._n.registerSurface(this._h, ...args, ...surfaceNormals(o2), steps, tolerance, !!o2.history);
+                const fit = { transform: s.transform, rotation: new Quaternion(s.q[0], s.q[1], s.q[2], s.q[3]), translation: new Vector3(s.t[0], s.t[1], s.t[2]),
+                              status: SURFACE_STATUS[s.status], iterations: s.iterations, pairs: s.pairs, surfacePairs: s.surfacePairs, rms: s.rms,
+                              surfaceRms: s.surfaceRms, delta: s.delta, valid: s.valid };
+                if (o2.history) { fit.stepPairs = s.stepPairs; fit.stepSurfacePairs = s.stepSurfacePairs; fit.stepRms = s.stepRms; fit.stepSurfaceRms = s.stepSurfaceRms; }
+                return fit;
+            }
+            if (o2.normals !== undefined) throw new Error("normals goes with residual: \"surface\"");
             const r = this._n.registerTo(this._h, ...args, steps, tolerance, !!o2.history);
             const out = { transform: r.transform, rotation: new Quaternion(r.q[0], r.q[1], r.q[2], r.q[3]), translation: new Vector3(r.t[0], r.t[1], r.t[2]),
                           status: REGISTER_STATUS[r.status], iterations: r.iterations, pairs: r.pairs, rms: r.rms };
@@ -910,4 +945,14 @@ function shRotation(q) {
     return [m.subarray(0, 9), m.subarray(9, 34), m.subarray(34, 83)];
 }
 
+// One point-to-plane step solved (gsr_surface_solve; a pure function, no device): from matchSurface's { surfacePairs, sums } the small
+// rigid motion { transform: Float64Array(12), rms, degenerate }.  degenerate = j + 1 when pivot j of the 6 x 6 system is not above
+// its floor (the residuals leave a direction free): transform is then the identity and rms NaN.
+function surfaceSolve(sums) {
+    const v = Float64Array.from(sums.sums);
+    if (v.length !== 29) throw new Error("surfaceSolve: sums holds 29 values");
+    return loadNative().surfaceSolve(Number(sums.surfacePairs), v);
+}
+
 module.exports = { HIPRenderer, sortHost, shRotation };
+module.exports.surfaceSolve = surfaceSolve;

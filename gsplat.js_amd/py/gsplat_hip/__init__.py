@@ -161,6 +161,24 @@ class GsrRegisterInfo(ctypes.Structure):
                 "delta": float(self.delta)}
 
 
+class GsrSurfaceSums(ctypes.Structure):
+    _fields_ = [("pairs", ctypes.c_uint64), ("surface_pairs", ctypes.c_uint64), ("sum", ctypes.c_double * 29)]
+
+    def as_dict(self):
+        return {"pairs": int(self.pairs), "surface_pairs": int(self.surface_pairs), "sum": np.array(self.sum, dtype=np.float64)}
+
+
+class GsrRegisterSurfaceInfo(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("iterations", ctypes.c_uint32), ("pairs", ctypes.c_uint64), ("surface_pairs", ctypes.c_uint64),
+                ("rms", ctypes.c_double), ("surface_rms", ctypes.c_double), ("delta", ctypes.c_double), ("valid", ctypes.c_uint32), ("step_rows", ctypes.c_uint32),
+                ("step_pairs", ctypes.c_void_p), ("step_surface_pairs", ctypes.c_void_p), ("step_rms", ctypes.c_void_p), ("step_surface_rms", ctypes.c_void_p)]
+
+    def as_dict(self):
+        return {"status": REGISTER_SURFACE_STATUS[self.status], "iterations": int(self.iterations), "pairs": int(self.pairs),
+                "surface_pairs": int(self.surface_pairs), "rms": float(self.rms), "surface_rms": float(self.surface_rms), "delta": float(self.delta),
+                "valid": int(self.valid)}
+
+
 class GsrDepthLayout(ctypes.Structure):
     _fields_ = [("format", ctypes.c_int32), ("step", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
                 ("stride", ctypes.c_int32), ("reserved", ctypes.c_int32), ("offset", ctypes.c_uint64), ("bytes", ctypes.c_uint64),
@@ -188,6 +206,7 @@ NORMAL_STATS = {"dot": 0, "abs_dot": 1, "variation": 2}                    # GSR
 PLANE_MAX_HYPOTHESES = 4096                                               # GSR_PLANE_MAX_HYPOTHESES
 MATCH_NONE = 0xffffffff                                                    # GSR_MATCH_NONE (an unmatched splat)
 REGISTER_STATUS = {0: "converged", 1: "max_iterations", 2: "too_few"}      # GSR_REGISTER_*
+REGISTER_SURFACE_STATUS = {**REGISTER_STATUS, 3: "degenerate"}             # with GSR_REGISTER_DEGENERATE (gsr_register_surface)
 REGISTER_MAX_ITERATIONS = 256                                              # GSR_REGISTER_MAX_ITERATIONS_LIMIT
 CELL_NONE = 0xffffffff                                                     # GSR_CELL_NONE (a leader: the splat is no candidate)
 CLUSTER_NONE = CLUSTER_LARGEST = 0xffffffff                                # GSR_CLUSTER_NONE (a label), GSR_CLUSTER_LARGEST (a seed)
@@ -240,6 +259,21 @@ def rigid_solve(sums):
     D, rms = np.zeros(12, np.float64), ctypes.c_double(0.0)
     _pure("gsr_rigid_solve", L.gsr_rigid_solve(ctypes.byref(s), D.ctypes.data, ctypes.byref(rms)))
     return D.reshape(3, 4), rms.value
+
+
+def surface_solve(sums):
+    """(D float64[3, 4], rms, degenerate) of gsr_surface_solve: the small rigid motion that takes the matched source points closest
+    to the target's surface along its normals (Cholesky on match_surface()'s sums, a dict with "surface_pairs" and "sum"; a Cayley
+    step for the rotation).  degenerate = j + 1 when pivot j of the 6 x 6 system is not above its floor -- the residuals leave a
+    direction free, as a target of one or two planes does: D is then the identity and rms None.  Needs the library, not a device."""
+    L = load_library()
+    s = GsrSurfaceSums()
+    s.pairs = int(sums.get("pairs", sums["surface_pairs"]))
+    s.surface_pairs = int(sums["surface_pairs"])
+    s.sum[:] = [float(v) for v in np.asarray(sums["sum"], dtype=np.float64).reshape(29)]
+    D, rms, deg = np.zeros(12, np.float64), ctypes.c_double(0.0), ctypes.c_int32(0)
+    _pure("gsr_surface_solve", L.gsr_surface_solve(ctypes.byref(s), D.ctypes.data, ctypes.byref(rms), ctypes.byref(deg)))
+    return D.reshape(3, 4), (None if deg.value else rms.value), deg.value
 
 
 def rigid_compose(D, M):
@@ -326,6 +360,7 @@ EXPORTS = [
     "gsr_fit_plane", "gsr_plane_inliers", "gsr_select_plane", "gsr_plane_alignment",
     "gsr_match", "gsr_select_match", "gsr_register", "gsr_rigid_solve", "gsr_rigid_compose", "gsr_rigid_decompose",
     "gsr_normals", "gsr_select_normal",
+    "gsr_match_surface", "gsr_surface_solve", "gsr_register_surface",
     "gsr_set_overlay", "gsr_overlay_async", "gsr_read_overlay", "gsr_read_overlay_rgba8", "gsr_overlay_device_ptr", "gsr_delivery_set_overlay",
     "gsr_set_overlay_outline",
 ]
@@ -523,6 +558,10 @@ def load_library(path=None):
     no, nmi = ctypes.POINTER(GsrNormalOptions), ctypes.POINTER(GsrNormalInfo)
     L.gsr_normals.argtypes = [vp, no, vp, vp, vp, ctypes.c_uint32, nmi]
     L.gsr_select_normal.argtypes = [vp, no, ctypes.c_int32, vp, ctypes.c_double, ctypes.c_double, ctypes.c_int32, u32p, nmi]
+    L.gsr_match_surface.argtypes = [vp, vp, vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, no, ctypes.POINTER(GsrSurfaceSums), mi]
+    L.gsr_surface_solve.argtypes = [ctypes.POINTER(GsrSurfaceSums), vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
+    L.gsr_register_surface.argtypes = [vp, vp, vp, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, u64, no, ctypes.c_uint32, ctypes.c_double, vp,
+                                       ctypes.POINTER(GsrRegisterSurfaceInfo)]
     L.gsr_set_overlay.argtypes = [vp, ctypes.POINTER(GsrOverlayOptions)]
     L.gsr_set_overlay_outline.argtypes = [vp, ctypes.POINTER(GsrOutlineOptions)]
     L.gsr_overlay_async.argtypes = [vp]
@@ -1779,6 +1818,61 @@ class HIPRenderer:
         d = info.as_dict()
         if history:
             d["step_pairs"], d["step_rms"] = sp[:info.iterations].copy(), sr[:info.iterations].copy()
+        return out.reshape(3, 4), d
+
+    # -- point-to-plane registration (gsr_match_surface / gsr_register_surface): aligned along the target's normals --
+    def _surface_normals(self, target, normals, target_scope):
+        """gsr_normal_options for the TARGET's normals: normals = dict(source="own" | "knn", radius=, k=, budget=); None is "own"."""
+        nm = dict(normals or {})
+        unknown = set(nm) - {"source", "radius", "k", "budget"}
+        if unknown:
+            raise ValueError("unknown normals option(s): %s" % ", ".join(sorted(unknown)))
+        return target._normal_options(nm.get("radius"), nm.get("k", 8), nm.get("source", "own"), None, target_scope, nm.get("budget"))
+
+    def match_surface(self, target, radius, normals=None, transform=None, scope=(), target_scope=(), budget=None):
+        """(sums, info): one point-to-plane step as data.  The match is match()'s; sums = {"pairs", "surface_pairs", "sum"
+        float64[29]}, what surface_solve takes -- per matched splat whose match has a normal the row (J_a * J_b for a <= b, J_a * r,
+        r * r, d2) with J = (T x n, n) and r = n . (T - Q), summed by the fixed tree.  normals: how `target`'s normals are made,
+        dict(source="own" | "knn", radius=, k=) as normals() takes them, over target_scope; None is "own".  info as match()'s.
+        Neither scene is written; `target` may be this renderer."""
+        radius, budget = self._match_args(target, radius, budget)
+        o = self._surface_normals(target, normals, target_scope)
+        m = _transform_arg(transform)
+        s, info = GsrSurfaceSums(), GsrMatchInfo()
+        self._check_neighbours(self._L.gsr_match_surface(self._ctx, target._ctx, None if m is None else m.ctypes.data, radius, self._scope_flags(scope),
+                                                         self._scope_flags(target_scope), budget, ctypes.byref(o), ctypes.byref(s), ctypes.byref(info)), info)
+        return s.as_dict(), info.as_dict()
+
+    def register_surface(self, target, radius, normals=None, transform=None, max_iterations=32, tolerance=2.0 ** -40, history=False, scope=(), target_scope=(),
+                         budget=None):
+        """(M float64[3, 4], info): register()'s loop with point-to-plane steps -- every source point is pulled toward the target's
+        SURFACE along the normal of its match, not toward the nearest sample, which converges in far fewer steps on floors, walls
+        and table tops and does not stop at a biased pose.  The same bits on every run.  It stops with status "too_few" when a step
+        has fewer than 6 pairs with a normal, "degenerate" when the residuals leave a direction free (a target of one or two
+        planes), "converged" and "max_iterations" as register().  normals as match_surface() takes them; they are made once per
+        call.  info: status, iterations, pairs, surface_pairs, rms, surface_rms and delta of the last step, valid (target splats
+        with a normal); history=True adds step_pairs, step_surface_pairs, step_rms and step_surface_rms.  The scene is not written."""
+        radius, budget = self._match_args(target, radius, budget)
+        max_iterations = int(max_iterations)
+        if not 1 <= max_iterations <= REGISTER_MAX_ITERATIONS:
+            raise ValueError("max_iterations must be in 1 .. %d" % REGISTER_MAX_ITERATIONS)
+        o = self._surface_normals(target, normals, target_scope)
+        m = _transform_arg(transform)
+        out = np.zeros(12, np.float64)
+        info = GsrRegisterSurfaceInfo()
+        steps = {"step_pairs": np.zeros(max_iterations, np.uint64), "step_surface_pairs": np.zeros(max_iterations, np.uint64),
+                 "step_rms": np.zeros(max_iterations, np.float64), "step_surface_rms": np.zeros(max_iterations, np.float64)}
+        if history:
+            for k, a in steps.items():
+                setattr(info, k, a.ctypes.data)
+            info.step_rows = max_iterations
+        self._check(self._L.gsr_register_surface(self._ctx, target._ctx, None if m is None else m.ctypes.data, radius, self._scope_flags(scope),
+                                                 self._scope_flags(target_scope), budget, ctypes.byref(o), max_iterations, float(tolerance), out.ctypes.data,
+                                                 ctypes.byref(info)))
+        d = info.as_dict()
+        if history:
+            for k, a in steps.items():
+                d[k] = a[:info.iterations].copy()
         return out.reshape(3, 4), d
 
     # -- selection overlay (gsr_set_overlay / gsr_overlay_async / gsr_read_overlay*): the selected splats tinted --

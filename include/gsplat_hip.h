@@ -1432,6 +1432,93 @@ int gsr_normals(gsr_ctx *ctx, const gsr_normal_options *options, float *normals 
 int gsr_select_normal(gsr_ctx *ctx, const gsr_normal_options *options, int32_t stat, const double *axis /* 3; NULL for VARIATION */,
                       double lo, double hi, int32_t op, uint32_t *selected, gsr_normal_info *info);
 
+/* ---- point-to-plane registration ---- a scene aligned with another one along the target's normals
+ * No interface of the reference stands behind this section either.  gsr_register pulls every source point toward the nearest
+ * target SAMPLE; on floors, walls and table tops, sampled at different points in each capture, that slides slowly and stops at a
+ * biased pose.  These calls pull every source point toward the target's SURFACE instead: the residual of a pair is its distance
+ * along the target splat's normal ("matching and registration" supplies the match, "normals" the normal), and a step is a 6 x 6
+ * linear solve.  The working name is "surface", to keep it apart from the planes of gsr_fit_plane.
+ * Definition ("Point-to-plane registration").  All arithmetic is f64, in the written order, uncontracted; /
+ *   and sqrt are correctly rounded; no sin, cos or atan appears anywhere, so numpy, this library's host code and the device agree
+ *   bit for bit (tests/surface_reference.py).
+ *   Match.  The match is gsr_match's, unchanged: index, walk, idx, d2, scopes and budget.
+ *   Target normals.  What gsr_normals(target, options) stores: the f32 rows, three NaNs where a splat has none.  They are computed
+ *   once per call, by the same device path, into the TARGET context's normals scratch, which is allocated or grown exactly as a
+ *   gsr_normals call on the target would.  target's scene, selection, hidden set and frame state are not changed.
+ *   options->scope must equal target_scope.  GSR_NORMAL_OWN and GSR_NORMAL_KNN are both allowed; KNN has its own radius, k and
+ *   budget under the rules of "neighbours".  oriented is taken as given and cannot matter: every product below is unchanged in
+ *   every bit when n is negated (but for the sign of a product that is exactly zero, which -0 + +0 = +0 removes from a sum as
+ *   soon as one row of its group is empty or padding).
+ *   Row of splat i: 29 doubles, non-zero iff i is matched and its match j has a normal (n_x is not a NaN).  T is the transformed
+ *   point of "matching and registration", Q = (double)q_j, n = (double)normal_j, e = T - Q;
+ *     r = (n_x*e_x + n_y*e_y) + n_z*e_z
+ *     c_x = T_y*n_z - T_z*n_y; c_y = T_z*n_x - T_x*n_z; c_z = T_x*n_y - T_y*n_x
+ *     J = (c_x, c_y, c_z, n_x, n_y, n_z)
+ *     row[0..20] = J_a*J_b for a <= b, row-major (00, 01, .., 05, 11, .., 55)
+ *     row[21+a] = J_a*r, row[27] = r*r, row[28] = d2_i.
+ *   Every other splat contributes 29 +0.0.
+ *   Sums.  The rows of splats 0 .. n-1 are summed by the fixed tree of "matching and registration", per component: groups of 256
+ *   rows, s = 128 .. 1, the group results reduced the same way.  pairs counts the matched splats, surface_pairs the non-zero
+ *   rows.  A NaN normal never enters a row.  A product may overflow to infinity; the solve refuses that.
+ * gsr_surface_solve(sums, D, rms, degenerate) is a pure function with no context.  Let inv = 1.0 / (double)surface_pairs.
+ *     1. A is the symmetric 6 x 6 built from sum[0..20]; g_a = -sum[21+a].
+ *     2. floor = max_a A_aa * 2^-40.
+ *     3. Cholesky, for j = 0..5: v = A_jj, then v = v - L_jk*L_jk for k = 0..j-1 in order.  If !(v > floor): *degenerate = j + 1,
+ *        D = (I | 0), *rms is not written, return GSR_OK.  L_jj = sqrt(v).  For i > j: v = A_ij, then v = v - L_ik*L_jk for k
+ *        ascending, then L_ij = v / L_jj.
+ *     4. Forward substitution, i ascending: y_i = (g_i - L_i0*y_0 - ..) taken left to right, then / L_ii.
+ *     5. Back substitution, i = 5..0, with k ascending from i+1: x_i = (y_i - L_ki*x_k ..) / L_ii.
+ *     6. (omega, v) = x.
+ *     7. The rotation is the Cayley step, which uses only sqrt and division: w = 1.0; (qx, qy, qz) = 0.5 * omega;
+ *        len = sqrt(((w*w + qx*qx) + qy*qy) + qz*qz), and all four are divided by len.  R follows from (x, y, z, w) = (qx, qy, qz,
+ *        w) by gsr_rigid_solve's nine formulas.
+ *     8. D = (R | v).  rms = sqrt(sum[27] * inv) (rms may be NULL).  *degenerate = 0.
+ *     9. Refused with GSR_ERR_ARG: a NULL sums, D or degenerate; surface_pairs < 6; a non-finite sum.
+ *   A target of one plane, or of two, leaves directions the residuals cannot see: a pivot is then exactly 0.0 and the solve says
+ *   so instead of dividing by it.
+ * gsr_match_surface is one step as data: the sums of the match under M.  An empty scene gives zeros, as gsr_match does; gsr_match
+ *   with the same arguments gives idx and d2 for a host that wants them.  sums and info may be NULL.
+ * gsr_register_surface runs gsr_register's loop.  The target's index and the target's normals are built once per call; the bound
+ *   is checked at every step.  Step t matches under M_t and reduces; surface_pairs < 6 ends the loop with GSR_REGISTER_TOO_FEW and
+ *   M_t; a degenerate solve ends it with GSR_REGISTER_DEGENERATE and M_t; otherwise M_{t+1} = D_t o M_t by gsr_rigid_compose.
+ *   delta, tolerance and max_iterations work as in gsr_register.  All four endings return GSR_OK.  info: status; iterations; the
+ *   last step's pairs and surface_pairs; rms = sqrt(sum[28] * (1.0 / pairs)) (+inf with no pair: the point distances of the
+ *   non-zero rows over the matched splats); surface_rms = sqrt(sum[27] * (1.0 / surface_pairs)) (+inf with none); delta; valid =
+ *   the target splats with a normal.  info is in / out: the four step arrays are NULL or the caller's, of step_rows >=
+ *   max_iterations entries.  The scene is never written.
+ * Refusals (GSR_ERR_ARG with a message, nothing touched): those of gsr_register and of gsr_normals (OWN on a target without
+ *   rotations and scales included; a message about the target's side is ctx's last error); NULL options; options->scope not equal
+ *   to target_scope.
+ * Both calls are blocking and stateless, ordered like gsr_register.  target == ctx and members of one shared scene are allowed.
+ * The device scratch: ctx's scratch of "matching and registration", with 29-wide partial rows (232 bytes per 256 source splats and
+ *   level) of their own; target's scratch of "normals" (and of "neighbours" for KNN). */
+typedef struct gsr_surface_sums {
+    uint64_t pairs;           /* matched splats */
+    uint64_t surface_pairs;   /* of those, with a normal at the match: the non-zero rows */
+    double sum[29];
+} gsr_surface_sums;           /* 248 bytes */
+typedef struct gsr_register_surface_info {
+    int32_t status;           /* GSR_REGISTER_* */
+    uint32_t iterations;
+    uint64_t pairs;
+    uint64_t surface_pairs;
+    double rms, surface_rms, delta;
+    uint32_t valid;           /* target splats with a normal */
+    uint32_t step_rows;       /* in */
+    uint64_t *step_pairs;     /* in: NULL, or step_rows entries */
+    uint64_t *step_surface_pairs;
+    double *step_rms;
+    double *step_surface_rms;
+} gsr_register_surface_info;  /* 88 bytes */
+#define GSR_REGISTER_DEGENERATE 3
+int gsr_match_surface(gsr_ctx *ctx, gsr_ctx *target, const double *M /* [12] or NULL */, double radius, uint32_t scope,
+                      uint32_t target_scope, uint64_t budget, const gsr_normal_options *options, gsr_surface_sums *sums,
+                      gsr_match_info *info);
+int gsr_surface_solve(const gsr_surface_sums *sums, double *D /* [12] */, double *rms, int32_t *degenerate);
+int gsr_register_surface(gsr_ctx *ctx, gsr_ctx *target, const double *M0, double radius, uint32_t scope, uint32_t target_scope,
+                         uint64_t budget, const gsr_normal_options *options, uint32_t max_iterations, double tolerance,
+                         double *M_out /* [12] */, gsr_register_surface_info *info);
+
 /* ---- selection overlay ---- the selected splats tinted, in read-backs and in delivered frames
  * No interface of the reference stands behind this section either.  gsr_read_selection returns bits; this shows them: a second
  * image beside the frame in which the selected splats carry a tint, and per pixel how much of it they are.

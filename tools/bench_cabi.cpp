@@ -3,7 +3,7 @@
 // this is the third.  It renders the bench's 120-pose orbit with F frames in flight and prints one
 // JSON line; with --rows / --dump it doubles as a cross-check of the other two hosts (same bytes in, same hashes out).
 //
-//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--rotate-sh FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--plane THRESHOLD[:HYPOTHESES]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--normals RADIUS:K[:own]] [--register RADIUS[:ITERATIONS]] [--merge CELL] [--share-scene]
+//   bench_cabi [--config C1|C2|C3|C4] [--rows file.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--rotate-sh FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--plane THRESHOLD[:HYPOTHESES]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--normals RADIUS:K[:own]] [--register RADIUS[:ITERATIONS]] [--register-surface RADIUS[:ITERATIONS[:K]]] [--merge CELL] [--share-scene]
 // --depth adds legs in which gsr_depth_async is enqueued behind every frame, alternated with plain legs in the same process,
 // and reports the frame rate with and without the pass; --pick X,Y prints what gsr_pick returns for that pixel of pose 0.
 // --deliver adds a leg in which every frame reaches the host as RGBA8 through the library's delivery ring (gsr_delivery_open,
@@ -71,6 +71,12 @@
 // are one size; one gsr_register call from the identity at tolerance 2^-40: its blocking time, the status, every step's pairs and rms,
 // and by the library's events on the stream the target's index (built once per call) and, of the last step and summed over the
 // steps, the bound, the walk and the tree apart (gsr_debug_match_times).
+// --register-surface RADIUS[:ITERATIONS[:K]] runs gsr_register_surface on --register's moved copy (made for either option): the
+// target's own normals without K, KNN normals with k = K at RADIUS; one call from the identity at tolerance 2^-40: its blocking
+// time, the status, every step's pairs, surface_pairs and both rms, and by the library's events the target's normals (index with
+// its bound, and walk or own kernel: gsr_debug_normals_times on the target), the target's index, and of the last step and summed
+// over the steps the bound, the walk and the rows + tree stage apart.  With --register in the same run the walk and the bound are
+// the same kernels on the same data, and the 16-wide rows + tree stage is the new stage's yardstick.
 // --merge CELL (behind everything else: it replaces the scene) merges the cells of a grid of side CELL: three gsr_cells calls, the
 // best wall time of the report, then the one gsr_scene_merge_cells call it announced: the blocking time, the rows before and after,
 // the members per cell, and the check that the edit left the announced rows with exactly the merged rows selected (`report_equals_edit`).
@@ -230,6 +236,8 @@ int main(int argc, char** argv)
     double merge_cell = 0.0;            // 0: off
     double reg_radius = 0.0;            // 0: off
     uint32_t reg_steps = 32;
+    double rs_radius = 0.0;             // --register-surface; 0: off
+    uint32_t rs_steps = 32, rs_k = 0;   // rs_k 0: the target's own normals
     uint32_t knn_k = 8;
     int32_t knn_stat = GSR_KNN_MEAN;
     double normals_radius = 0.0;        // 0: off
@@ -312,6 +320,17 @@ int main(int argc, char** argv)
             if (!(reg_radius > 0.0) || steps < 1 || steps > (int)GSR_REGISTER_MAX_ITERATIONS_LIMIT) { std::fprintf(stderr, "--register RADIUS[:ITERATIONS]: RADIUS > 0, ITERATIONS in 1 .. 256\n"); return 2; }
             reg_steps = (uint32_t)steps;
         }
+        else if (a == "--register-surface" && i + 1 < argc) {
+            const std::string v = argv[++i];
+            const size_t colon = v.find(':'), colon2 = colon == std::string::npos ? colon : v.find(':', colon + 1);
+            rs_radius = std::atof(v.c_str());
+            const int steps = colon != std::string::npos ? std::atoi(v.c_str() + colon + 1) : 32;
+            const int k = colon2 != std::string::npos ? std::atoi(v.c_str() + colon2 + 1) : 0;
+            if (!(rs_radius > 0.0) || steps < 1 || steps > (int)GSR_REGISTER_MAX_ITERATIONS_LIMIT || (colon2 != std::string::npos && (k < 2 || k > (int)GSR_KNN_MAX_K))) {
+                std::fprintf(stderr, "--register-surface RADIUS[:ITERATIONS[:K]]: RADIUS > 0, ITERATIONS in 1 .. 256, K in 2 .. 32\n"); return 2;
+            }
+            rs_steps = (uint32_t)steps; rs_k = (uint32_t)k;
+        }
         else if (a == "--merge" && i + 1 < argc) { merge_cell = std::atof(argv[++i]); if (!(merge_cell > 0.0)) { std::fprintf(stderr, "--merge CELL: CELL > 0\n"); return 2; } }
         else if (a == "--duplicate" && i + 1 < argc) { duplicate_fraction = std::atof(argv[++i]); if (!(duplicate_fraction >= 0.0 && duplicate_fraction <= 1.0)) { std::fprintf(stderr, "--duplicate FRACTION must be in [0, 1]\n"); return 2; } }
         else if (a == "--reserve") reserve = true;
@@ -319,7 +338,7 @@ int main(int argc, char** argv)
         else if (a == "--scene-edit") scene_edit = next();
         else if (a == "--share-scene") share_scene = true;
         else if (a == "--pick") { pick = std::sscanf(next(), "%d,%d", &pick_xy[0], &pick_xy[1]) == 2; if (!pick) { std::fprintf(stderr, "--pick X,Y\n"); return 2; } }
-        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--rotate-sh FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--plane THRESHOLD[:HYPOTHESES]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--normals RADIUS:K[:own]] [--register RADIUS[:ITERATIONS]] [--merge CELL] [--share-scene]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: bench_cabi [--config C1..C4] [--rows f.splat] [--frames K] [--warmup W] [--in-flight F] [--dump prefix] [--deliver] [--deliver-format nv12|i420] [--deliver-depth f32|u16] [--depth-step 1|2] [--depth-near X] [--depth] [--contrib] [--overlay FRACTION] [--outline WIDTH] [--hide FRACTION] [--hide-edits] [--pick X,Y] [--scene-arrays] [--scene-edit rotate] [--edit-selected FRACTION] [--rotate-sh FRACTION] [--duplicate FRACTION [--reserve]] [--histogram ATTR[:BINS]] [--neighbours RADIUS[:CAP]] [--plane THRESHOLD[:HYPOTHESES]] [--clusters RADIUS[:MIN_PTS]] [--knn RADIUS:K[:kth|mean]] [--normals RADIUS:K[:own]] [--register RADIUS[:ITERATIONS]] [--register-surface RADIUS[:ITERATIONS[:K]]] [--merge CELL] [--share-scene]\n"); return 2; }
     }
     const Config* cfg = nullptr;
     for (const Config& c : CONFIGS) if (config == c.name) cfg = &c;
@@ -884,7 +903,12 @@ int main(int argc, char** argv)
     double reg_ms = 0, reg_M[12] = {0};
     float reg_stage[8] = {0};
     uint32_t reg_n = 0, reg_target_n = 0;
-    if (reg_radius > 0.0) {
+    gsr_register_surface_info rs_info{};
+    std::vector<uint64_t> rs_step_pairs(rs_steps, 0), rs_step_surface_pairs(rs_steps, 0);
+    std::vector<double> rs_step_rms(rs_steps, 0.0), rs_step_surface_rms(rs_steps, 0.0);
+    double rs_ms = 0, rs_M[12] = {0};
+    float rs_stage[8] = {0}, rs_normals[2] = {0};
+    if (reg_radius > 0.0 || rs_radius > 0.0) {
         gsr_ctx* tgt = nullptr;
         gsr_options o{};
         o.device = 0; o.width = cfg->w; o.height = cfg->h;
@@ -899,11 +923,26 @@ int main(int argc, char** argv)
         CHECK(gsr_scene_count(tgt, &reg_target_n));
         ctx0 = ctx[0];
         CHECK(gsr_scene_count(ctx[0], &reg_n));
-        reg_info.step_pairs = reg_step_pairs.data(); reg_info.step_rms = reg_step_rms.data(); reg_info.step_rows = reg_steps;
-        const auto t0 = std::chrono::steady_clock::now();
-        CHECK(gsr_register(ctx[0], tgt, nullptr, reg_radius, 0, 0, 0, reg_steps, 1.0 / 1099511627776.0, reg_M, &reg_info));
-        reg_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3;
-        CHECK(gsr_debug_match_times(ctx[0], reg_stage));
+        if (reg_radius > 0.0) {
+            reg_info.step_pairs = reg_step_pairs.data(); reg_info.step_rms = reg_step_rms.data(); reg_info.step_rows = reg_steps;
+            const auto t0 = std::chrono::steady_clock::now();
+            CHECK(gsr_register(ctx[0], tgt, nullptr, reg_radius, 0, 0, 0, reg_steps, 1.0 / 1099511627776.0, reg_M, &reg_info));
+            reg_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3;
+            CHECK(gsr_debug_match_times(ctx[0], reg_stage));
+        }
+        if (rs_radius > 0.0) {
+            gsr_normal_options no{};
+            no.source = rs_k ? GSR_NORMAL_KNN : GSR_NORMAL_OWN; no.k = rs_k; no.radius = rs_radius;
+            rs_info.step_pairs = rs_step_pairs.data(); rs_info.step_surface_pairs = rs_step_surface_pairs.data();
+            rs_info.step_rms = rs_step_rms.data(); rs_info.step_surface_rms = rs_step_surface_rms.data(); rs_info.step_rows = rs_steps;
+            const auto t0 = std::chrono::steady_clock::now();
+            CHECK(gsr_register_surface(ctx[0], tgt, nullptr, rs_radius, 0, 0, 0, &no, rs_steps, 1.0 / 1099511627776.0, rs_M, &rs_info));
+            rs_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3;
+            CHECK(gsr_debug_match_times(ctx[0], rs_stage));
+            ctx0 = tgt;
+            CHECK(gsr_debug_normals_times(tgt, rs_normals));
+            ctx0 = ctx[0];
+        }
         gsr_destroy(tgt);
     }
     // --duplicate (last of all: it grows the scene): the selection duplicated on the device, twice
@@ -1044,6 +1083,28 @@ int main(int argc, char** argv)
         for (uint32_t k = 0; k < reg_info.iterations; k++) std::printf("%s%llu", k ? ", " : "", (unsigned long long)reg_step_pairs[k]);
         std::printf("], \"step_rms\": [");
         for (uint32_t k = 0; k < reg_info.iterations; k++) std::printf("%s%s", k ? ", " : "", json_num(reg_step_rms[k]).c_str());
+        std::printf("]}");
+    }
+    if (rs_radius > 0.0) {
+        std::printf(", \"register_surface\": {\"radius\": %.17g, \"max_iterations\": %u, \"normals\": \"%s\", \"k\": %u, \"n\": %u, \"target_n\": %u, \"status\": \"%s\", "
+                    "\"iterations\": %u, \"pairs\": %llu, \"surface_pairs\": %llu, \"valid\": %u, \"rms\": %s, \"surface_rms\": %s, \"delta\": %s, "
+                    "\"register_surface_ms\": %.4f, \"normals_index_ms\": %.4f, \"normals_walk_ms\": %.4f, \"index_build_ms\": %.4f, \"bound_ms\": %.4f, \"walk_ms\": %.4f, "
+                    "\"rows_tree_ms\": %.4f, \"steps_bound_ms\": %.4f, \"steps_walk_ms\": %.4f, \"steps_rows_tree_ms\": %.4f, \"transform\": [",
+                    rs_radius, rs_steps, rs_k ? "knn" : "own", rs_k, reg_n, reg_target_n,
+                    rs_info.status == GSR_REGISTER_CONVERGED ? "converged" : rs_info.status == GSR_REGISTER_TOO_FEW ? "too_few"
+                        : rs_info.status == GSR_REGISTER_DEGENERATE ? "degenerate" : "max_iterations",
+                    rs_info.iterations, (unsigned long long)rs_info.pairs, (unsigned long long)rs_info.surface_pairs, rs_info.valid, json_num(rs_info.rms).c_str(),
+                    json_num(rs_info.surface_rms).c_str(), json_num(rs_info.delta).c_str(), rs_ms, rs_normals[0], rs_normals[1], rs_stage[0], rs_stage[1], rs_stage[2],
+                    rs_stage[3], rs_stage[4], rs_stage[5], rs_stage[6]);
+        for (int k = 0; k < 12; k++) std::printf("%s%.17g", k ? ", " : "", rs_M[k]);
+        std::printf("], \"step_pairs\": [");
+        for (uint32_t k = 0; k < rs_info.iterations; k++) std::printf("%s%llu", k ? ", " : "", (unsigned long long)rs_step_pairs[k]);
+        std::printf("], \"step_surface_pairs\": [");
+        for (uint32_t k = 0; k < rs_info.iterations; k++) std::printf("%s%llu", k ? ", " : "", (unsigned long long)rs_step_surface_pairs[k]);
+        std::printf("], \"step_rms\": [");
+        for (uint32_t k = 0; k < rs_info.iterations; k++) std::printf("%s%s", k ? ", " : "", json_num(rs_step_rms[k]).c_str());
+        std::printf("], \"step_surface_rms\": [");
+        for (uint32_t k = 0; k < rs_info.iterations; k++) std::printf("%s%s", k ? ", " : "", json_num(rs_step_surface_rms[k]).c_str());
         std::printf("]}");
     }
     if (normals_radius > 0.0)
